@@ -6,6 +6,7 @@ Any-Precision weights, fused QKV / Up-Gate, on MI355X -- plus the AP-GEMV roofli
     python bench.py --backend qtip                               (BASELINE configs[3]: Llama-2-7b QTIP 2-bit)
     python bench.py --bits 3 | --bits 4                          (configs[2])
     python bench.py --model meta-llama/Llama-3.3-70B-Instruct    (configs[4] on one GPU; N > 1 adds the pipeline record)
+    python bench.py --dump-outputs DIR                           (also write the last timed step's token and logits to DIR/*.npy)
 
 A "step" is one decoded token (bs = 1): embedding, n_layer x (RMSNorm->wqkv GEMV, RoPE+KV+attention, wo GEMV+residual,
 RMSNorm->w1w3 GEMV+SiLU*up, w2 GEMV+residual), final norm + fp16 lm_head GEMV, top-k sampling -- the reference's
@@ -234,6 +235,32 @@ def decode_tok_s(model, dev, steps, warmup, torch_sampling=False):
     return graph, run_steps
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def last_step_outputs(model, graph):
+    """what a caller of the captured decode step receives from its last replay, as host arrays: the token it drew and the logits
+    the fused sampler drew it from (with the torch sampling ops: the probabilities they return)"""
+    import torch
+    torch.cuda.synchronize()
+    out = {"next_token": graph.next_tok.reshape(-1).double().cpu().numpy()}
+    if graph.native_sampling:
+        out["logits"] = model._native_state()["logits"].reshape(-1).float().cpu().numpy()
+    else:
+        out["next_prob"] = graph.next_prob.reshape(-1).float().cpu().numpy()
+    return out
+
+
+def write_outputs(dirname, arrays):
+    """DIR/<name>.npy for every array (float32 or float64, DUMP_LIMIT_BYTES in all)"""
+    import numpy as np
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 LEG_MARK = "GQ_LEG_JSON "
 # the legs of the N = 1 line next to the headline, in run order: (key in the line, group, --leg name, extra argv)
 LEGS = [
@@ -330,10 +357,16 @@ def main():
     ap.add_argument("--no-pp-record", action="store_true", help="N>1: skip the pipeline_70b / tp_70b sub-records")
     ap.add_argument("--model", default=None, help="model name from guidedquant_amd.model.transformer_configs; the headline metric is quoted on the default")
     ap.add_argument("--torch-sampling", action="store_true", help="sample with the reference's torch ops instead of the fused HIP sampler")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed token step computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--leg", default=None, help="(internal) run one side leg of the line in this process and print its record")
     args = ap.parse_args()
     if args.leg:
         return leg_main(args)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.parallel == "pp" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--dump-outputs: the layer pipeline (--parallel pp) has no last-step outputs on one rank")
     t_start = time.perf_counter()
 
     import torch
@@ -399,6 +432,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     tok_s = world * args.steps / dt
+    if args.dump_outputs and rank == 0:  # (before the untimed steps below overwrite the step's buffers)
+        write_outputs(args.dump_outputs, last_step_outputs(model, graph))
 
     # behind the timed region, same process, same graph: the reference's own definition of the metric (whole 100-token sequences,
     # generate.py:344-389) over 400 steps, and the same with ONE token step per graph replay
