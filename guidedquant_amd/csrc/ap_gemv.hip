@@ -1240,8 +1240,8 @@ struct QuadCfg {
 
 int num_cus() { return gq_cu_count(); }
 
-// `pt2`: the configuration is for the 2-bit pair-table kernel (4 waves per SIMD)
-bool pick_quad_cfg(u32 N, u32 K, int bits, QuadCfg &c, int pro = PRO_NONE, bool pt2 = false) {
+// `pt2`: the configuration is for the 2-bit pair-table kernel (4 waves per SIMD); `pairs`: the launch has the SiLU-pairs epilogue
+bool pick_quad_cfg(u32 N, u32 K, int bits, QuadCfg &c, int pro = PRO_NONE, bool pt2 = false, bool pairs = false) {
     if (K % 128u) return false;
     const u32 Q = K / 128u;
     if (Q > 512u) return false;
@@ -1297,6 +1297,14 @@ bool pick_quad_cfg(u32 N, u32 K, int bits, QuadCfg &c, int pro = PRO_NONE, bool 
     auto smem_for = [&](u32 s) { return (size_t)K * 2u + (size_t)s * c.RS * nchunks * 64u + 64u; };
     while (spb > 1 && smem_for(spb) > 150u * 1024u) spb--;
     if (smem_for(spb) > 160u * 1024u) return false;
+    // the SiLU-pairs epilogue combines rows (2i, 2i + 1) inside one block (rows_epilogue_n: the two halves of a wave), so a block must
+    // start on an even row and hold an even number of rows.  An odd row step (K = 4608: 256 threads, RS = 7; K = 11008: RS = 5) with an
+    // odd SPB would leave the pair at every block boundary split: SPB goes up by one, or down by one where the partials would not fit.
+    if (pairs && ((spb * c.RS) & 1u)) {
+        if (spb > 1u && smem_for(spb + 1u) > 150u * 1024u) spb--;
+        else spb++;
+        if (smem_for(spb) > 160u * 1024u) return false;
+    }
     c.SPB = spb;
     c.grid = (steps + spb - 1) / spb;
     if ((u32)d > spb) d = (int)spb;
@@ -1305,6 +1313,9 @@ bool pick_quad_cfg(u32 N, u32 K, int bits, QuadCfg &c, int pro = PRO_NONE, bool 
     return true;
 }
 
+// rows of 4096 weights at ring depth 1: the instance with the ordered reduction in registers (INREG above)
+bool inreg_plan(u32 K, const QuadCfg &c) { return c.D == 1u && K == 4096u && c.T % 64u == 0u && c.RS * 32u == c.T && gq_env_int("GQ_AP_INREG", 1) != 0; }
+
 template <int BITS, int D, int PRO>
 int launch_quad_inst(const ApArgs &a, const QuadCfg &c, u32 M, hipStream_t s) {
     dim3 grid(c.grid, M), block(c.T);
@@ -1312,7 +1323,7 @@ int launch_quad_inst(const ApArgs &a, const QuadCfg &c, u32 M, hipStream_t s) {
     if (GQ_STAMPS) ad.dbg = gq_debug_timing_buffer();
     // rows of 4096 weights at the shipped ring depth: the ordered reduction in registers (INREG above)
     if constexpr (D == 1) {
-        if (a.K == 4096u && c.T % 64u == 0u && c.RS * 32u == c.T && gq_env_int("GQ_AP_INREG", 1) != 0) {
+        if (inreg_plan(a.K, c)) {
             static GqPerDeviceOnce once_r;
             auto kern_r = ap_gemv_quad_kernel<BITS, D, PRO, true>;
             GQ_HIP_CHECK(once_r.max_dynamic_lds(reinterpret_cast<const void *>(kern_r), (int)(160u * 1024u)));
@@ -1350,24 +1361,54 @@ int launch_quad(const ApArgs &a, const QuadCfg &c, u32 M, int pro, hipStream_t s
     }
 }
 
+// the 2-bit pair-table kernel: asked for by GQ_AP_PT (0 never -- the default --, 1 rows of >= 8192 weights, 2 every shape it serves)
+bool pt2_wanted(int bits, u32 K) {
+    const int pt = gq_env_int("GQ_AP_PT", GQ_AP_PT_DEFAULT);
+    return bits == 2 && (pt >= 2 || (pt == 1 && K >= 8192u));
+}
+size_t pt2_smem(u32 K, const QuadCfg &c) {
+    const u32 nchunks = K / 1024u + ((K % 1024u) ? 1u : 0u);
+    return (((size_t)K * 2u + (size_t)c.SPB * c.RS * nchunks * 64u + 63u) & ~(size_t)63u) + (size_t)(c.T / 64u) * 128u + 64u;
+}
+// ... and the plans it serves: a wave spans at most two rows (64 or more quads per row, or exactly 32) and the tables fit
+bool pt2_serves(u32 K, const QuadCfg &c) {
+    const u32 Q = K / 128u;
+    return (Q == 32u || Q >= 64u) && !(c.T & 63u) && pt2_smem(K, c) <= 160u * 1024u;
+}
+
+// the exact-order launch the dispatcher makes for a shape (kernel: 0 v_perm kernel, 1 its INREG instance, 2 the pair-table kernel)
+bool exact_plan(u32 N, u32 K, int bits, int pro, bool pairs, QuadCfg &c, u32 &kernel) {
+    if (!pick_quad_cfg(N, K, bits, c, pro, false, pairs)) return false;
+    kernel = inreg_plan(K, c) ? 1u : 0u;
+    QuadCfg cp;
+    if (pt2_wanted(bits, K) && pick_quad_cfg(N, K, bits, cp, pro, true, pairs) && pt2_serves(K, cp)) c = cp, kernel = 2u;
+    return true;
+}
+
 }  // namespace
-extern "C" int gq_debug_exact_plan(uint32_t N, uint32_t K, int bits, int prologue, uint32_t *plan) {
+extern "C" int gq_debug_exact_plan_ex(uint32_t N, uint32_t K, int bits, int prologue, uint32_t epilogue, uint32_t *plan) {
     QuadCfg c;
-    if (!plan || bits < 2 || bits > 4 || !pick_quad_cfg(N, K, bits, c, prologue)) return GQ_ENOTSUP;
-    const bool inreg = c.D == 1u && K == 4096u && c.T % 64u == 0u && c.RS * 32u == c.T;
-    const u32 wpe = inreg ? (bits == 2 ? 4u : 3u) : (bits <= 3 && c.D == 1u ? 3u : 2u);  // (the kernels' amdgpu_waves_per_eu attributes)
+    u32 kernel = 0;
+    if (!plan || bits < 2 || bits > 4 || !exact_plan(N, K, bits, prologue, (epilogue & GQ_EPI_SILU_PAIRS) != 0, c, kernel)) return GQ_ENOTSUP;
+    // (the kernels' amdgpu_waves_per_eu attributes)
+    const u32 wpe = kernel == 2u ? 4u : (kernel == 1u ? (bits == 2 ? 4u : 3u) : (bits <= 3 && c.D == 1u ? 3u : 2u));
     plan[0] = c.T, plan[1] = c.RS, plan[2] = c.SPB, plan[3] = c.D, plan[4] = c.grid, plan[5] = std::max(1u, wpe * 4u / ((c.T + 63u) / 64u));
+    plan[6] = kernel;
     return GQ_OK;
 }
+extern "C" int gq_debug_exact_plan(uint32_t N, uint32_t K, int bits, int prologue, uint32_t *plan) {
+    uint32_t p[7];
+    const int rc = plan ? gq_debug_exact_plan_ex(N, K, bits, prologue, GQ_EPI_NONE, p) : GQ_ENOTSUP;
+    if (rc == GQ_OK)
+        for (int i = 0; i < 6; i++) plan[i] = p[i];
+    return rc;
+}
 namespace {
-// the 2-bit pair-table kernel on the quad kernel's configuration (+ the waves' tables behind the partial sums); GQ_ENOTSUP where a wave
-// could span more than two rows (fewer than 64 quads per row unless exactly 32) or the tables do not fit
+// the 2-bit pair-table kernel on the quad kernel's configuration (+ the waves' tables behind the partial sums); GQ_ENOTSUP where it does
+// not serve the plan (pt2_serves)
 int launch_pt2(const ApArgs &a, const QuadCfg &c, u32 M, int pro, hipStream_t s) {
-    const u32 Q = a.K / 128u;
-    if (!(Q == 32u || Q >= 64u) || (c.T & 63u) || (Q == 32u && (c.T % 64u))) return GQ_ENOTSUP;
-    const u32 nchunks = a.K / 1024u + ((a.K % 1024u) ? 1u : 0u);
-    const size_t smem = (((size_t)a.K * 2u + (size_t)c.SPB * c.RS * nchunks * 64u + 63u) & ~(size_t)63u) + (size_t)(c.T / 64u) * 128u + 64u;
-    if (smem > 160u * 1024u) return GQ_ENOTSUP;
+    if (!pt2_serves(a.K, c)) return GQ_ENOTSUP;
+    const size_t smem = pt2_smem(a.K, c);
     dim3 grid(c.grid, M), block(c.T);
 #define GQ_PT2(PRO_)                                                                                                            \
     do {                                                                                                                        \
@@ -1493,9 +1534,9 @@ int ap_gemv_dispatch_inner(ApArgs a, u32 M, int bits, hipStream_t s, GqHandover 
     }
     if (ho && ho->dry) return GQ_OK;  // (the exact-mode kernels have no hand-over form)
     const uint64_t qbytes = (uint64_t)bits * a.N * (a.K / 8u);
-    if (!force_generic && bits <= 4 && qbytes < 0x7FFFFFFFull && pick_quad_cfg(a.N, a.K, bits, c, pro) &&
-        (((uintptr_t)a.qw | (uintptr_t)a.x | (uintptr_t)a.normw) & 15u) == 0 && ((uintptr_t)a.lut & 15u) == 0 &&
-        !((a.epilogue & GQ_EPI_SILU_PAIRS) && ((c.SPB * c.RS) & 1u))) {
+    const bool pairs = (a.epilogue & GQ_EPI_SILU_PAIRS) != 0;
+    if (!force_generic && bits <= 4 && qbytes < 0x7FFFFFFFull && pick_quad_cfg(a.N, a.K, bits, c, pro, false, pairs) &&
+        (((uintptr_t)a.qw | (uintptr_t)a.x | (uintptr_t)a.normw) & 15u) == 0 && ((uintptr_t)a.lut & 15u) == 0) {
         a.RS = c.RS;
         a.SPB = c.SPB;
         // round 6: the pair-table kernel (GQ_AP_PT: 0 never -- the default --, 1 rows of >= 8192 weights, 2 every shape it serves).  It had
@@ -1503,10 +1544,8 @@ int ap_gemv_dispatch_inner(ApArgs a, u32 M, int bits, hipStream_t s, GqHandover 
         // CU beyond the occupancy); in one round the v_perm kernel is the faster one on every Llama shape (8B w2 8.9 vs 9.9 us; 70B w2 26.0
         // vs 33.6, wqkv 12.4 vs 13.5, wo 8.7 vs 10.0) except 70B w1w3 (41.7 vs 38.1): profiles/r06_exact_pair_table.txt, r06_exact_epilogue.txt
         {
-            const int pt = gq_env_int("GQ_AP_PT", GQ_AP_PT_DEFAULT);
             QuadCfg cp;
-            if (bits == 2 && (pt >= 2 || (pt == 1 && a.K >= 8192u)) && pick_quad_cfg(a.N, a.K, bits, cp, pro, true) &&
-                !((a.epilogue & GQ_EPI_SILU_PAIRS) && ((cp.SPB * cp.RS) & 1u))) {
+            if (pt2_wanted(bits, a.K) && pick_quad_cfg(a.N, a.K, bits, cp, pro, true, pairs)) {
                 ApArgs ap = a;
                 ap.RS = cp.RS;
                 ap.SPB = cp.SPB;

@@ -517,6 +517,10 @@ void gq_debug_set_qtip_timing_buffer(void *device_buffer); /* u64 [16 waves][8] 
  * once.  prologue: 0 none, 1 RMSNorm, 2 SiLU * up.  Returns GQ_ENOTSUP when the fast exact path does not serve the shape.  For the test that
  * no plan asks for more resident blocks than fit (a round-6 find: such a launch runs in two rounds). */
 int gq_debug_exact_plan(uint32_t N, uint32_t K, int bits, int prologue, uint32_t *plan);
+/* The same for a launch with the given epilogue flags (GQ_EPI_SILU_PAIRS plans keep every block on an even number of rows), with the
+ * GQ_AP_* knobs applied as the dispatcher applies them: plan[0..5] as above, plan[6] = the kernel the launch runs (0 the v_perm kernel,
+ * 1 its instance with the ordered reduction in registers, 2 the 2-bit pair-table kernel). */
+int gq_debug_exact_plan_ex(uint32_t N, uint32_t K, int bits, int prologue, uint32_t epilogue, uint32_t *plan);
 
 #ifdef __cplusplus
 }

@@ -523,3 +523,42 @@ def test_exact_gemv_plans_fit_the_occupancy():
                     assert grid * SPB * RS >= N, (model, N, K, bits, pro, list(plan))          # every row has a slot
                     assert grid <= 256 * bpc, (model, N, K, bits, pro, list(plan))             # one round of blocks
     assert seen >= 60
+
+
+def test_exact_gemv_pair_plans_keep_blocks_on_even_rows():
+    """the SiLU-pairs epilogue combines rows (2i, 2i + 1) inside one block, so every pairs plan has an even SPB * RS.  Rows of 4608,
+    11008 or 18944 weights have an odd row step (RS = 7, 5, 3): without the epilogue the planner picks odd blocks there (the launch
+    used to be refused), with it the block is rounded to an even number of rows.  Every GQ_AP_T the planner accepts, too."""
+    import ctypes
+    import os
+    from guidedquant_amd import _lib
+    L = _lib.lib()
+    widths = [128, 256, 2048, 2304, 3584, 4096, 4608, 5120, 8192, 11008, 12288, 14336, 18944, 28672]
+    odd_without, seen = 0, 0
+    try:
+        for envT in (None, 64, 192, 320, 448):
+            if envT is None:
+                os.environ.pop("GQ_AP_T", None)
+            else:
+                os.environ["GQ_AP_T"] = str(envT)
+            L.gq_reset_env_cache()
+            for K in widths:
+                for N in (2, 1000, 4098, 22016, 28672, 73728):
+                    for bits in (2, 3, 4):
+                        for pro in (0, 1, 2):
+                            plain, pairs, legacy = (ctypes.c_uint32 * 7)(), (ctypes.c_uint32 * 7)(), (ctypes.c_uint32 * 6)()
+                            rc0 = L.gq_debug_exact_plan_ex(N, K, bits, pro, 0, plain)
+                            rc4 = L.gq_debug_exact_plan_ex(N, K, bits, pro, 4, pairs)
+                            assert rc0 == rc4 == L.gq_debug_exact_plan(N, K, bits, pro, legacy), (envT, N, K, bits, pro)
+                            if rc0 != 0:
+                                continue
+                            seen += 1
+                            assert list(legacy) == list(plain)[:6]
+                            odd_without += (plain[1] * plain[2]) % 2
+                            T, RS, SPB, D, grid = list(pairs)[:5]
+                            assert (RS * SPB) % 2 == 0, (envT, N, K, bits, pro, list(pairs))
+                            assert grid * SPB * RS >= N and (grid - 1) * SPB * RS < N and 1 <= D <= SPB, (envT, N, K, bits, pro, list(pairs))
+    finally:
+        os.environ.pop("GQ_AP_T", None)
+        L.gq_reset_env_cache()
+    assert seen > 1000 and odd_without > 50, (seen, odd_without)
