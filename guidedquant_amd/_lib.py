@@ -24,6 +24,7 @@ EXPORTS = [
     "gq_qtip_linear_out_in", "gq_debug_stream_read", "gq_hop_alloc", "gq_hop_free", "gq_hop_export", "gq_hop_import", "gq_hop_close", "gq_hop_wait_copy",
     "gq_sample_topk_ex", "gq_anyprec_gemv_fused_ho", "gq_ssq_rows", "gq_anyprec_handover_plan", "gq_embed_lookup_ho", "gq_anyprec_gemv_qkv_rope_ho",
     "gq_anyprec_qkv_rope_attn_supported", "gq_anyprec_gemv_qkv_rope_attn", "gq_hop_is_finegrained", "gq_sample_topk_p",
+    "gq_qtip_decompress", "gq_qtip_gemm", "gq_qtip_gemm_ws", "gq_qtip_gemm_ws_bytes",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -115,6 +116,10 @@ def lib():
         L.gq_anyprec_gemm.argtypes = [vp, vp, vp, vp, u32, u32, u32, i32, vp]
         L.gq_anyprec_gemm_ws.argtypes = [vp, vp, vp, vp, u32, u32, u32, i32, vp, ctypes.c_size_t, vp]
         L.gq_anyprec_gemm_ws_bytes.argtypes = [u32, u32, u32, i32]
+        L.gq_qtip_decompress.argtypes = [vp, vp, vp, u32, u32, i32, vp]
+        L.gq_qtip_gemm.argtypes = [vp, vp, vp, vp, u32, u32, u32, i32, vp]
+        L.gq_qtip_gemm_ws.argtypes = [vp, vp, vp, vp, u32, u32, u32, i32, vp, ctypes.c_size_t, vp]
+        L.gq_qtip_gemm_ws_bytes.argtypes = [u32, u32, u32, i32]
         L.gq_rmsnorm_rows.argtypes = [vp, vp, vp, vp, u32, u32, f32, vp]
         L.gq_rope_cache_rows.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp]
         L.gq_silu_mul_rows.argtypes = [vp, vp, u32, u32, i32, vp]
@@ -142,10 +147,11 @@ def lib():
         for name in EXPORTS:
             if name in _VOID:
                 getattr(L, name).restype = None
-            elif name not in ("gq_last_error", "gq_anyprec_gemm_ws_bytes", "gq_anyprec_gemv_fused_ws_bytes"):
+            elif name not in ("gq_last_error", "gq_anyprec_gemm_ws_bytes", "gq_anyprec_gemv_fused_ws_bytes", "gq_qtip_gemm_ws_bytes"):
                 getattr(L, name).restype = i32
         L.gq_anyprec_gemm_ws_bytes.restype = ctypes.c_size_t
         L.gq_anyprec_gemv_fused_ws_bytes.restype = ctypes.c_size_t
+        L.gq_qtip_gemm_ws_bytes.restype = ctypes.c_size_t
         L.gq_last_error.restype = ctypes.c_char_p
         _lib = L
     return _lib

@@ -873,8 +873,9 @@ class Transformer(nn.Module):
 
     # ------------------------------------------------------------------------------------------------ prompt pass
     def prefill_ready(self, idx: Tensor) -> bool:
-        """the HIP prompt pass serves what the fused decode step serves for Any-Precision models: fp16, batch 1, on the GPU"""
-        return (self._native_kind() == "ap" and idx.is_cuda and idx.numel() > 1 and (idx.dim() == 1 or idx.shape[0] == 1)
+        """the HIP prompt pass serves what the native decode step serves (fused Any-Precision models, unfused QTIP models):
+        fp16, batch 1, on the GPU"""
+        return (self._native_kind() in ("ap", "qtip") and idx.is_cuda and idx.numel() > 1 and (idx.dim() == 1 or idx.shape[0] == 1)
                 and self.config.head_dim % 16 == 0 and self.config.dim % 8 == 0 and self.config.dim <= 16384
                 and self.config.intermediate_size % 8 == 0)
 
@@ -882,7 +883,8 @@ class Transformer(nn.Module):
         """The prompt pass (`Transformer.forward` with seq_len > 1, inference/model.py:206-266 semantics) with the element-wise
         steps between the linears as ONE HIP launch each (csrc/prefill.hip: RMSNorm rows, RoPE + KV-cache write, silu * up)
         instead of ~45 eager tensor ops per layer, the linears through `APLinear.forward` (fused prefill GEMM / split K /
-        the reference's two steps by size), attention over the keys [0, start + S) only instead of the whole cache.
+        the reference's two steps by size) or, for QTIP models, `QuantizedLinear.forward` (the trellis-decode GEMM), attention
+        over the keys [0, start + S) only instead of the whole cache.
         `input_pos` must be arange(start, start + S) (what generate() passes; `start` is the host copy of its first element).
         Same fp16 rounding points as the module forward: logits agree up to the summation order of the fp32 sums.
         last_only: logits of the last prompt token only, [1, 1, V] -- all generate() samples from -- else [1, S, V]."""
@@ -899,6 +901,7 @@ class Transformer(nn.Module):
         hbuf = torch.empty((S, inter), dtype=torch.float16, device=dev)
         mask = None if start == 0 else self.causal_mask[None, None, input_pos.long(), :T]
         rep = H // Hkv
+        qt = self._native_kind() == "qtip"  # QTIP: the linears through QuantizedLinear.forward (bs > 8: gq_qtip_gemm)
         pending = None  # the previous block's MLP output: its residual add rides in the next RMSNorm launch
         with torch.cuda.device(dev):
             st = _lib.current_stream_ptr()  # (the model's device's current stream: inside the guard)
@@ -906,7 +909,11 @@ class Transformer(nn.Module):
                 att, ff = b.attention, b.feed_forward
                 _lib.check(L.gq_rmsnorm_rows(x.data_ptr(), pending.data_ptr() if pending is not None else None, b.input_layernorm.weight.data_ptr(), xn.data_ptr(),
                                              S, D, b.input_layernorm.eps, st), "gq_rmsnorm_rows")
-                qkv = att.wqkv(xn.view(1, S, D)).view(S, -1)
+                if qt:  # (unfused QTIP linears: q | k | v side by side, the row layout gq_rope_cache_rows reads)
+                    xv = xn.view(1, S, D)
+                    qkv = torch.cat([att.wq(xv), att.wk(xv), att.wv(xv)], dim=-1).view(S, -1)
+                else:
+                    qkv = att.wqkv(xn.view(1, S, D)).view(S, -1)
                 kc, vc = att.kv_cache.k_cache, att.kv_cache.v_cache
                 _lib.check(L.gq_rope_cache_rows(qkv.data_ptr(), input_pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), q.data_ptr(),
                                                 kc.data_ptr(), vc.data_ptr(), S, H, Hkv, hd, kc.shape[2], st), "gq_rope_cache_rows")
@@ -915,8 +922,14 @@ class Transformer(nn.Module):
                 o = att.wo(y).view(S, D)
                 _lib.check(L.gq_rmsnorm_rows(x.data_ptr(), o.data_ptr(), b.post_attention_layernorm.weight.data_ptr(), xn.data_ptr(), S, D,
                                              b.post_attention_layernorm.eps, st), "gq_rmsnorm_rows")
-                gu = ff.w1w3(xn.view(1, S, D)).view(S, 2 * inter)
-                _lib.check(L.gq_silu_mul_rows(gu.data_ptr(), hbuf.data_ptr(), S, inter, 1 if getattr(ff.w1w3, "gq_row_pairs", False) else 0, st), "gq_silu_mul_rows")
+                if qt:  # (gate | up side by side: paired = 0)
+                    xv = xn.view(1, S, D)
+                    gu = torch.cat([ff.w1(xv), ff.w3(xv)], dim=-1).view(S, 2 * inter)
+                    paired = 0
+                else:
+                    gu = ff.w1w3(xn.view(1, S, D)).view(S, 2 * inter)
+                    paired = 1 if getattr(ff.w1w3, "gq_row_pairs", False) else 0
+                _lib.check(L.gq_silu_mul_rows(gu.data_ptr(), hbuf.data_ptr(), S, inter, paired, st), "gq_silu_mul_rows")
                 pending = ff.w2(hbuf.view(1, S, inter)).view(S, D)
         x = x + pending
         x = x[-1:] if last_only else x

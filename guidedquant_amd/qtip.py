@@ -8,6 +8,8 @@
     up-front for every linear shape of the models in `model.transformer_configs`.
   * `hadamard::hadamard(x, scale)` (inference/lib/utils/matmul_had.py:96-106) on gq_hadamard, `get_hadK`,
     `matmul_hadU_cuda` / `matmul_hadUt_cuda` (matmul_had.py:13-67,109-123).
+  * `quip_lib::qtip_gemm(compressed, x, codebook, m, R) -> Tensor[S, m]` fp32: the batched (bs > 8) middle step on
+    gq_qtip_gemm, and `decompress` (decode_compressed, kernel_decompress.py:5-55) on gq_qtip_decompress.
   * `BitshiftLinear.forward` eval path (inference/lib/codebook/bitshift.py:415-472) and `QuantizedLinear`
     (qtip/lib/linear/quantized_linear.py:12-153): buffers `trellis int16[(N/16)(K/16), 16R]`, `tlut fp16[512,2]`,
     `SU fp16[K]`, `SV fp32[N]`, `rcp`, `tp_rank`, non-persistent `had_left/had_right`.
@@ -109,6 +111,75 @@ def register_model_shapes():
         for m, k in {(d, d), (kv, d), (i, d), (d, i), (d + 2 * kv, d), (2 * i, d)}:
             for R in (2, 3, 4):
                 quip_lib_op(m, k, R)
+
+
+# --------------------------------------------------------------------------------------------- batched (prompt) path
+def decompress(trellis, tlut, M, K, R):
+    """decode_compressed (kernel_decompress.py:5-55) on gq_qtip_decompress: trellis (any int dtype, R*M*K/16 16-bit words)
+    + tlut fp16 [512, 2] -> dense fp16 W [M, K], bit for bit the reference's hatW"""
+    comp = trellis.contiguous().reshape(-1).view(torch.int32)
+    cb = tlut.contiguous().reshape(-1)
+    _chk(comp.is_cuda and cb.is_cuda, "decompress: tensors must be on the GPU")
+    _chk(cb.dtype == torch.float16 and cb.numel() == 1024, "decompress: tlut must be float16 [512, 2]")
+    _chk(comp.numel() * 32 == R * M * K, "decompress: trellis size != R * M * K / 32 words")
+    W = torch.empty((M, K), dtype=torch.float16, device=comp.device)
+    with torch.cuda.device(comp.device):
+        rc = _lib.lib().gq_qtip_decompress(W.data_ptr(), comp.data_ptr(), cb.data_ptr(), M, K, R, _lib.current_stream_ptr())
+    _lib.check(rc, "gq_qtip_decompress")
+    return W
+
+
+def _two_step_min_rows():
+    return int(os.environ.get("GQ_QTIP_TWO_STEP_S", "256"))
+
+
+def _decompress_mm(comp, cb, x16, m, R):
+    """the reference's two steps (kernel_decompress.py:82-91) with an fp32 output: dense fp16 W, one hipBLASLt GEMM"""
+    W = decompress(comp, cb, m, x16.shape[1], R)
+    return torch.mm(x16, W.T, out_dtype=torch.float32)
+
+
+def qtip_gemm(compressed, x, codebook, m, R):
+    """z fp32 [S, m] = x fp16 [S, K] @ decode(compressed)^T: exact fp16 products, fp32 accumulation and output.
+    S < GQ_QTIP_TWO_STEP_S (256): gq_qtip_gemm_ws, the decode fused into the MFMA loop; from there on -- where the decode of every
+    128 / 256-token tile costs more than writing and re-reading a dense W -- gq_qtip_decompress + one
+    matmul with an fp32 output.  A shape the GEMM does not serve (GQ_ENOTSUP) takes the two steps too -- never the row loop."""
+    comp = compressed.contiguous().reshape(-1).view(torch.int32)
+    cb = codebook.contiguous().reshape(-1)
+    x16 = x.to(torch.float16).contiguous()
+    S, K = x16.shape
+    _chk(comp.numel() * 32 == R * m * K, "qtip_gemm: compressed size != R * m * k / 32 words")
+    if S >= _two_step_min_rows():
+        return _decompress_mm(comp, cb, x16, m, R)
+    out = torch.empty((S, m), dtype=torch.float32, device=x16.device)
+    L = _lib.lib()
+    with torch.cuda.device(x16.device):
+        nbytes = L.gq_qtip_gemm_ws_bytes(S, m, K, R)
+        ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=x16.device) if nbytes else None
+        rc = L.gq_qtip_gemm_ws(out.data_ptr(), comp.data_ptr(), x16.data_ptr(), cb.data_ptr(), S, m, K, R,
+                               ws.data_ptr() if ws is not None else None, nbytes, _lib.current_stream_ptr())
+    if rc == _lib.GQ_ENOTSUP:
+        return _decompress_mm(comp, cb, x16, m, R)
+    _lib.check(rc, "gq_qtip_gemm")
+    return out
+
+
+if "quip_lib::qtip_gemm" not in _registered:
+    torch.library.define("quip_lib::qtip_gemm", "(Tensor compressed, Tensor x, Tensor codebook, int m, int R) -> Tensor")
+
+    @torch.library.register_fake("quip_lib::qtip_gemm")
+    def _qtip_gemm_fake(compressed, x, codebook, m, R):
+        return x.new_empty((x.shape[0], m), dtype=torch.float32)
+
+    @torch.library.impl("quip_lib::qtip_gemm", "cuda")
+    def _qtip_gemm_cuda(compressed, x, codebook, m, R):
+        return qtip_gemm(compressed, x, codebook, m, R)
+
+    _registered.add("quip_lib::qtip_gemm")
+
+
+def _gemm_enabled():
+    return os.environ.get("GQ_QTIP_GEMM", "1") != "0"
 
 
 if "hadamard::hadamard" not in _registered:
@@ -223,6 +294,9 @@ class BitshiftLinear(nn.Module):
             x = matmul_hadUt_cuda(x, had_left, K_left) / self.scale
         if bs == 1:
             x = quip_lib_op(m, n, self.K)(trellis, x, self.tlut)
+        elif bs > 8 and x.is_cuda and _gemm_enabled():
+            # the reference's own threshold (bitshift.py:449-470): one GEMM with the trellis decode fused in, fp32 output
+            x = torch.ops.quip_lib.qtip_gemm(trellis, x.to(torch.float16), self.tlut, m, self.K)
         else:
             # batched: row-by-row through the same kernel (the reference decodes + matmuls; same arithmetic class)
             x = torch.cat([quip_lib_op(m, n, self.K)(trellis, x[i:i + 1], self.tlut) for i in range(bs)], dim=0)

@@ -120,6 +120,35 @@ int gq_anyprec_gemm_ws(const void *x, void *out, const uint32_t *qweight, const 
                        int bits, void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * QTIP trellis decode to a dense fp16 matrix.  Replaces decode_compressed (qtip/lib/utils/kernel_decompress.py:5-55: index
+ * decode, quantlut_sym lookup, m16n8k16 de-swizzle), bit for bit.
+ *   W fp16 [M][K] (written), compressed int32 [R*M*K/32] (the packed trellis), codebook fp16 [512][2] (tlut).
+ * R 2..4, M and K positive multiples of 32 (GQ_ENOTSUP else); pointers 4-byte aligned.
+ */
+int gq_qtip_decompress(void *W, const void *compressed, const void *codebook, uint32_t M, uint32_t K, int R, void *stream);
+/*
+ * QTIP prompt GEMM with the trellis decode fused into the matrix-core loop.
+ *   out[s][m] = sum_k decode(compressed)[m][k] * x[s][k]     x fp16 [S][K], out fp32 [S][M] (written), S >= 1
+ * Replaces bitshift_linear_kernel (qtip/lib/utils/kernel_decompress.py:82-91), the bs > 8 branch of BitshiftLinear.forward
+ * (qtip/lib/codebook/bitshift.py:466-470): decode_compressed + torch.matmul -- without the dense fp16 copy of W.  Exact fp16
+ * products, fp32 accumulation, NO fp16 rounding of the output (the reference rounds z to fp16 there; the matvec route keeps it
+ * fp32, and this GEMM equals that route up to the fp32 summation order).  Serves every (M, K) gq_qtip_matvec serves: R 2..4,
+ * M and K positive multiples of 32 (GQ_ENOTSUP else).  out and x 16-byte aligned, compressed and codebook 4-byte aligned.
+ */
+int gq_qtip_gemm(void *out, const void *compressed, const void *x, const void *codebook, uint32_t S, uint32_t M, uint32_t K, int R,
+                 void *stream);
+/*
+ * The same GEMM with a caller-supplied fp32 workspace for SHORT GRIDS (fewer 128-row output tiles than compute units): K is then
+ * split over up to 16 ranges, each range leaves fp32 partial sums in the workspace and a second launch adds the ranges in
+ * ascending K order (deterministic; equal to gq_qtip_gemm's result up to the fp32 summation order).  gq_qtip_gemm_ws_bytes = the
+ * workspace this problem would use (0: no split planned); a null / too small workspace runs the single pass.  workspace 16-byte
+ * aligned.
+ */
+size_t gq_qtip_gemm_ws_bytes(uint32_t S, uint32_t M, uint32_t K, int R);
+int gq_qtip_gemm_ws(void *out, const void *compressed, const void *x, const void *codebook, uint32_t S, uint32_t M, uint32_t K, int R,
+                    void *workspace, size_t ws_bytes, void *stream);
+
+/*
  * The element-wise steps of the prompt pass (seq_len > 1) between the prefill GEMMs, one launch each; fp16 rows, the fp16 rounding
  * points of the tensor expressions they replace (`Transformer.forward`, inference/model.py:206-266):
  *   gq_rmsnorm_rows     RMSNorm.forward (model.py:84-96) on S rows of D: (x.float() * rsqrt(mean(x^2) + eps)).half() * weight;
