@@ -1,12 +1,20 @@
 #!/usr/bin/env python
 """bench.py -- BASELINE.json's metric on its config: bs=1 decode tokens/sec of Llama-3.1-8B-Instruct, 2-bit
-Any-Precision weights, fused QKV / Up-Gate, on MI355X -- plus the AP-GEMV roofline figures and CPU baselines.
+Any-Precision weights, fused QKV / Up-Gate, on MI355X -- and, with --full, the AP-GEMV roofline figures, CPU baselines and
+the other configs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (driver contract)
+    python bench.py [--gpus N] [--steps K] [--warmup W]          (driver contract: the headline only)
+    python bench.py --full                                       (+ every other record of the line, see "Output" below)
+    python bench.py --full --quick                               (+ tok_s_400, the single-step figure and `roofline` only)
     python bench.py --backend qtip                               (BASELINE configs[3]: Llama-2-7b QTIP 2-bit)
     python bench.py --bits 3 | --bits 4                          (configs[2])
-    python bench.py --model meta-llama/Llama-3.3-70B-Instruct    (configs[4] on one GPU; N > 1 adds the pipeline record)
+    python bench.py --model meta-llama/Llama-3.3-70B-Instruct    (configs[4] on one GPU; N > 1 with --full adds the pipeline record)
     python bench.py --dump-outputs DIR                           (also write the last timed step's token and logits to DIR/*.npy)
+
+A plain run sets up, warms up, times the K steps, writes DIR/*.npy if asked and prints the line: nothing it measures or
+checks besides the headline.  Everything below that is not the headline (`config.tok_s_400`, `config.tok_s_single_step_replay`,
+`roofline`, the side legs; for N > 1 `pipeline_70b` and `tp_70b`) is measured only with --full; without it these keys are null
+or absent.
 
 A "step" is one decoded token (bs = 1): embedding, n_layer x (RMSNorm->wqkv GEMV, RoPE+KV+attention, wo GEMV+residual,
 RMSNorm->w1w3 GEMV+SiLU*up, w2 GEMV+residual), final norm + fp16 lm_head GEMV, top-k sampling -- the reference's
@@ -23,12 +31,12 @@ data-path collective; "replicas only", weak scaling -- DESIGN.md section 6).  Th
 same run and reported as the `pipeline_70b` sub-record of the same JSON line, next to `tp_70b` (the row-split tensor-parallel decode of
 ONE sequence of the same model); both run in child processes with a process group of their own.
 
-Process model (round 6): this process measures the headline and the `roofline` object and nothing else; every other record of the
+Process model (--full): this process measures the headline and the `roofline` object and nothing else; every other record of the
 line (`cpu_baseline`, `roofline_by_shape`, exact mode, each of `other_configs`; for N > 1 `pipeline_70b` and `tp_70b`) is measured by a
 child process of its own (`python bench.py --leg NAME`, own timeout) and merged into the one line -- a leg that crashes, aborts or hangs
 becomes {"error": "rc -6"} in its place and costs nothing else.
 
-Output: ONE JSON line on rank 0 (schema in the task contract) with
+Output: ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, config, ...); with --full also
   `roofline`           dominant quantized kernel (the w1w3 AP-GEMV exactly as the decode graph launches it: RMSNorm prologue,
                        gate/up pair epilogue), algorithmic bytes B_ap / average launch duration, HIP events on the launch stream
                        over all layers' distinct weights; `traffic` = HBM bytes per launch from the committed PMC passes of
@@ -349,12 +357,16 @@ def main():
     ap.add_argument("--bits", type=int, default=2)
     ap.add_argument("--backend", choices=["ap", "qtip"], default="ap")
     ap.add_argument("--mode", choices=["default", "exact", "fast"], default="default")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the 3-/4-bit, QTIP and 70B single-GPU sub-records")
-    ap.add_argument("--quick", action="store_true", help="headline number and roofline object only (no shape table / exact-mode / CPU legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every record besides the headline: tok_s_400, the single-step figure, the roofline object and "
+                         "the side legs (CPU baseline, shape table, exact mode, other configs; N>1: pipeline_70b / tp_70b)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the 3-/4-bit, QTIP and 70B single-GPU sub-records")
+    ap.add_argument("--quick", action="store_true",
+                    help="with --full: headline, tok_s_400 and roofline object only (no shape table / exact-mode / CPU / other-config legs)")
     ap.add_argument("--parallel", choices=["replicas", "pp"], default="replicas",
                     help="N>1: what `value` measures -- independent replicas (default) or the layer pipeline (pp) of --model")
-    ap.add_argument("--no-pp-record", action="store_true", help="N>1: skip the pipeline_70b / tp_70b sub-records")
+    ap.add_argument("--no-pp-record", action="store_true", help="N>1 with --full: skip the pipeline_70b / tp_70b sub-records")
     ap.add_argument("--model", default=None, help="model name from guidedquant_amd.model.transformer_configs; the headline metric is quoted on the default")
     ap.add_argument("--torch-sampling", action="store_true", help="sample with the reference's torch ops instead of the fused HIP sampler")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -435,10 +447,10 @@ def main():
     if args.dump_outputs and rank == 0:  # (before the untimed steps below overwrite the step's buffers)
         write_outputs(args.dump_outputs, last_step_outputs(model, graph))
 
-    # behind the timed region, same process, same graph: the reference's own definition of the metric (whole 100-token sequences,
-    # generate.py:344-389) over 400 steps, and the same with ONE token step per graph replay
+    # --full, behind the timed region, same process, same graph: the reference's own definition of the metric (whole 100-token
+    # sequences, generate.py:344-389) over 400 steps, and the same with ONE token step per graph replay
     tok_s_400 = tok_s_single = None
-    if not pp and world == 1:
+    if args.full and not pp and world == 1:
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         run_steps(400)
@@ -454,10 +466,12 @@ def main():
             torch.cuda.synchronize()
             tok_s_single = round(SEQ_NEW_TOKENS / (time.perf_counter() - t1), 2)
 
-    try:
-        roofline = qtip_roofline(cfg, args.bits) if qtip else ap_roofline(model, args.bits, args.mode)
-    except Exception as e:  # (the headline stands on its own)
-        roofline = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
+    roofline = None
+    if args.full:
+        try:
+            roofline = qtip_roofline(cfg, args.bits) if qtip else ap_roofline(model, args.bits, args.mode)
+        except Exception as e:  # (the headline stands on its own)
+            roofline = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
     model_size, _ = _get_model_size(model)
 
     mode = {"default": "exact" if os.environ.get("GQ_AP_EXACT", "0") != "0" else "default"}.get(args.mode, args.mode)
@@ -477,23 +491,23 @@ def main():
                    "kv_positions_timed": "0..%d" % (min(args.steps, SEQ_NEW_TOKENS) - 1),
                    "token_steps_per_graph_replay": spr,
                    "untimed_setup_token_steps": (20 * spr + 1) if not (args.torch_sampling or pp) else 2,
-                   "tok_s_400": tok_s_400, "tok_s_single_step_replay": tok_s_single,
+                   "full": args.full, "tok_s_400": tok_s_400, "tok_s_single_step_replay": tok_s_single,
                    "note": "sequences of %d new tokens: --steps < %d times only the first positions of one sequence; tok_s_400 = the reference's "
                            "definition of the metric (whole 100-token sequences, generate.py:344-389), 400 steps timed in this process behind the "
-                           "timed region -- the figure to quote; tok_s_single_step_replay = one sequence with ONE token step per graph replay; "
-                           "untimed_setup_token_steps = replays of the captured graphs at set-up, before the --warmup steps (first replay of each "
-                           "graph, clocks up)" % (SEQ_NEW_TOKENS, SEQ_NEW_TOKENS)},
+                           "timed region -- the figure to quote; tok_s_single_step_replay = one sequence with ONE token step per graph replay "
+                           "(both measured with --full only, null without it); untimed_setup_token_steps = replays of the captured graphs at "
+                           "set-up, before the --warmup steps (first replay of each graph, clocks up)" % (SEQ_NEW_TOKENS, SEQ_NEW_TOKENS)},
         "roofline": roofline, "cpu_baseline": None,
     }
 
-    # ------------------------------------------------------------------ side legs, each in its own process (N = 1)
-    full = rank == 0 and world == 1 and not args.quick
-    if full:
+    # ------------------------------------------------------------------ side legs, each in its own process (N = 1, --full)
+    if args.full and rank == 0 and world == 1 and not args.quick:
         del graph, run_steps, model
         import gc
         gc.collect()
         torch.cuda.empty_cache()
-        budget = float(os.environ.get("GQ_BENCH_BUDGET_S", "900"))
+        # (540 s: with a leg that hangs the whole run still ends within 10 minutes)
+        budget = float(os.environ.get("GQ_BENCH_BUDGET_S", "540"))
         leg_limit = float(os.environ.get("GQ_BENCH_LEG_TIMEOUT_S", "300"))
         for key, group, leg, extra in LEGS:
             if qtip and key != "cpu_baseline":
@@ -533,7 +547,6 @@ def main():
                     r.update(us=roofline["avg_launch_us"], GBps=roofline["achieved"], frac=roofline["frac"],
                              stream_floor_us=roofline["stream_floor_us"], frac_of_stream_floor=roofline["frac_of_stream_floor"],
                              source="the `roofline` object of this line (the model's own 32 w1w3 tensors)")
-        line["bench_wall_s"] = round(time.perf_counter() - t_start, 1)
 
     if world > 1:
         # evidence that the collective library saw N ranks (the barrier / max-reduce above went through it)
@@ -546,7 +559,7 @@ def main():
                                "devices_visible": torch.cuda.device_count(), "one_gpu_shared": one_gpu}
 
     # ------------------------------------------------------------------ north-star multi-GPU config as sub-records (N > 1)
-    if world > 1 and not pp and not args.no_pp_record and not qtip:
+    if args.full and world > 1 and not pp and not args.no_pp_record and not qtip:
         # every rank starts a child of its own; the N children form their own process group on another port and run the 70B layer
         # pipeline (BASELINE configs[4]) and the tensor-parallel decode of the same model; a child that dies or hangs costs its record
         del graph, run_steps, model
@@ -562,6 +575,7 @@ def main():
                 line[leg] = rec
             dist.barrier()  # (the next group starts when every child of this one is gone)
     if rank == 0:
+        line["bench_wall_s"] = round(time.perf_counter() - t_start, 1)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

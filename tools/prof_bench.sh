@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$(pwd)
 mkdir -p $R/gpurun_out
 S=/tmp/prof_$tag; rm -rf $S; mkdir -p $S
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $S/bench_trace -o t -- python $R/bench.py --steps 100 --warmup 100 --quick > $S/bench_trace.log 2>&1
+rocprofv3 --kernel-trace --stats -d $S/bench_trace -o t -- python $R/bench.py --steps 100 --warmup 100 --full --quick > $S/bench_trace.log 2>&1
 for f in $(find $S/bench_trace -name "*.db"); do python $R/tools/rocpd_summary.py $f | cut -c1-160 | head -30; done > $R/gpurun_out/${tag}_bench_kernel_trace_stats.txt
 tail -1 $S/bench_trace.log | cut -c1-1200 >> $R/gpurun_out/${tag}_bench_kernel_trace_stats.txt
 BA="python $R/tools/bench_ap.py --bits 2 --shapes w1w3 --iters 40 --launch norm_pairs"
