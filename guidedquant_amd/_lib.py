@@ -24,10 +24,13 @@ EXPORTS = [
     "gq_qtip_linear_out_in", "gq_debug_stream_read", "gq_hop_alloc", "gq_hop_free", "gq_hop_export", "gq_hop_import", "gq_hop_close", "gq_hop_wait_copy",
     "gq_sample_topk_ex", "gq_anyprec_gemv_fused_ho", "gq_ssq_rows", "gq_anyprec_handover_plan", "gq_embed_lookup_ho", "gq_anyprec_gemv_qkv_rope_ho",
     "gq_anyprec_qkv_rope_attn_supported", "gq_anyprec_gemv_qkv_rope_attn", "gq_hop_is_finegrained", "gq_sample_topk_p",
-    "gq_qtip_decompress", "gq_qtip_gemm", "gq_qtip_gemm_ws", "gq_qtip_gemm_ws_bytes",
+    "gq_qtip_decompress", "gq_qtip_gemm", "gq_qtip_gemm_ws", "gq_qtip_gemm_ws_bytes", "gq_debug_ap_last_route", "gq_debug_ap_plan_route",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
+# include/gq_hip.h GQ_AP_ROUTE_*: the kernel family an AP-GEMV dispatch launched (gq_debug_ap_last_route, gq_debug_ap_plan_route)
+AP_ROUTES = ("none", "generic", "exact", "pair-table", "plane", "plane-local", "plane-chain", "stream", "stream-ksplit", "dq",
+             "stream-qkv-rope")
 _VOID = ("gq_reset_env_cache", "gq_debug_set_timing_buffer", "gq_debug_set_qtip_timing_buffer")
 
 
@@ -129,6 +132,8 @@ def lib():
         L.gq_debug_set_qtip_timing_buffer.argtypes = [vp]
         L.gq_debug_exact_plan.argtypes = [u32, u32, i32, i32, vp]
         L.gq_debug_exact_plan_ex.argtypes = [u32, u32, i32, i32, u32, vp]
+        L.gq_debug_ap_last_route.argtypes = [ctypes.POINTER(u32)]
+        L.gq_debug_ap_plan_route.argtypes = [u32, u32, i32, u32, i32, u32, ctypes.c_size_t, ctypes.POINTER(u32)]
         L.gq_hop_send.argtypes = [vp, vp, u32, vp, vp, u32, vp]
         L.gq_hop_wait.argtypes = [vp, vp, u32, vp, u32, vp]
         L.gq_debug_stream_read.argtypes = [vp, ctypes.c_size_t, vp, vp]
@@ -187,6 +192,24 @@ def check(rc, what):
     if rc != 0:
         msg = lib().gq_last_error()
         raise RuntimeError(f"{what}: {msg.decode() if msg else 'error'} (code {rc})")
+
+
+def _route(r):
+    return AP_ROUTES[r[0]] if r[0] < len(AP_ROUTES) else f"route {r[0]}", int(r[1]), int(r[2])
+
+
+def ap_last_route():
+    """(family, launches, exact variant) of the calling thread's last AP-GEMV dispatch: family is a name of AP_ROUTES."""
+    r = (ctypes.c_uint32 * 3)()
+    check(lib().gq_debug_ap_last_route(r), "gq_debug_ap_last_route")
+    return _route(r)
+
+
+def ap_plan_route(N, K, bits, M=1, has_norm=False, epilogue=0, ws_bytes=0):
+    """(family, launches, exact variant) a dry dispatch gives for the launch form, under the current mode and environment."""
+    r = (ctypes.c_uint32 * 3)()
+    check(lib().gq_debug_ap_plan_route(N, K, bits, M, 1 if has_norm else 0, epilogue, ws_bytes, r), "gq_debug_ap_plan_route")
+    return _route(r)
 
 
 def current_stream_ptr():

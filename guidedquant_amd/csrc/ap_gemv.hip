@@ -1069,6 +1069,7 @@ bool pick_dq_cfg(u32 N, u32 K, int bits, DqCfg &c) {
 }
 template <int BITS, int PRO, int QT>
 int launch_dq_q(const DqArgs &da, const DqCfg &c, hipStream_t s) {
+    if (gq_ap_route(GQ_AP_ROUTE_DQ, 1u)) return GQ_OK;
     static GqPerDeviceOnce once;
     auto kern = ap_gemv_dq_kernel<BITS, PRO, QT>;
     GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(kern), (int)(160u * 1024u)));
@@ -1324,6 +1325,7 @@ int launch_quad_inst(const ApArgs &a, const QuadCfg &c, u32 M, hipStream_t s) {
     // rows of 4096 weights at the shipped ring depth: the ordered reduction in registers (INREG above)
     if constexpr (D == 1) {
         if (inreg_plan(a.K, c)) {
+            if (gq_ap_route(GQ_AP_ROUTE_EXACT, 1u, 1u)) return GQ_OK;
             static GqPerDeviceOnce once_r;
             auto kern_r = ap_gemv_quad_kernel<BITS, D, PRO, true>;
             GQ_HIP_CHECK(once_r.max_dynamic_lds(reinterpret_cast<const void *>(kern_r), (int)(160u * 1024u)));
@@ -1332,6 +1334,7 @@ int launch_quad_inst(const ApArgs &a, const QuadCfg &c, u32 M, hipStream_t s) {
             return GQ_OK;
         }
     }
+    if (gq_ap_route(GQ_AP_ROUTE_EXACT, 1u, 0u)) return GQ_OK;
     static GqPerDeviceOnce once;
     auto kern = ap_gemv_quad_kernel<BITS, D, PRO>;
     GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(kern), (int)(160u * 1024u)));
@@ -1408,6 +1411,7 @@ namespace {
 // not serve the plan (pt2_serves)
 int launch_pt2(const ApArgs &a, const QuadCfg &c, u32 M, int pro, hipStream_t s) {
     if (!pt2_serves(a.K, c)) return GQ_ENOTSUP;
+    if (gq_ap_route(GQ_AP_ROUTE_PAIR_TABLE, 1u, 2u)) return GQ_OK;
     const size_t smem = pt2_smem(a.K, c);
     dim3 grid(c.grid, M), block(c.T);
 #define GQ_PT2(PRO_)                                                                                                            \
@@ -1429,6 +1433,7 @@ int launch_pt2(const ApArgs &a, const QuadCfg &c, u32 M, int pro, hipStream_t s)
 template <int BITS>
 int launch_generic(const ApArgs &a, u32 M, hipStream_t s) {
     const int ksplit = (M == 1 && a.K > 4096 && BITS >= 7) ? 1 : 0;  // anyprec.cu:611
+    if (gq_ap_route(GQ_AP_ROUTE_GENERIC, 1u)) return GQ_OK;
     dim3 grid((a.N + 7) / 8, M), block(256);
     hipLaunchKernelGGL(ap_gemv_generic_kernel<BITS>, grid, block, 0, s, a, ksplit);
     GQ_HIP_CHECK(hipGetLastError());
@@ -1465,8 +1470,19 @@ __global__ void __launch_bounds__(GQ_SSQ_SLOTS) ssq_rows_kernel(const uint16_t *
     gq_store_wt(ssq + threadIdx.x, acc);
 }
 
+// the route record (gq_internal.h: gq_ap_route) of the calling thread, and whether its dispatch is a dry run
+thread_local uint32_t t_route[3] = {GQ_AP_ROUTE_NONE, 0u, 0u};
+thread_local bool t_dry = false;
+}  // namespace
+bool gq_ap_route(uint32_t family, uint32_t launches, uint32_t variant) {
+    t_route[0] = family, t_route[1] = launches, t_route[2] = variant;
+    return t_dry;
+}
+namespace {
+
 int ap_gemv_dispatch_inner(ApArgs a, u32 M, int bits, hipStream_t s, GqHandover *ho);
 int ap_gemv_dispatch(ApArgs a, u32 M, int bits, hipStream_t s) {
+    gq_ap_route(GQ_AP_ROUTE_NONE, 0u);
     GqHandover ho;
     ho.ssq_in = a.ssq_in;
     ho.ssq_out = a.ssq_out;
@@ -1475,11 +1491,13 @@ int ap_gemv_dispatch(ApArgs a, u32 M, int bits, hipStream_t s) {
     if (rc == GQ_OK && ho.ssq_out && !ho.ssq_written) {  // the kernel that served the shape has no in-epilogue form: one small launch more
         hipLaunchKernelGGL(ssq_rows_kernel, dim3(1), dim3(GQ_SSQ_SLOTS), 0, s, a.out, a.N, ho.ssq_out);
         GQ_HIP_CHECK(hipGetLastError());
+        t_route[1]++;
     }
     return rc;
 }
 
 int ap_gemv_dispatch_inner(ApArgs a, u32 M, int bits, hipStream_t s, GqHandover *ho) {
+    gq_ap_route(GQ_AP_ROUTE_NONE, 0u);  // (until a launch site records what it launches)
     if (bits < 2 || bits > 8) return gq_fail(GQ_EINVAL, "Bitwidth must be between 2 and 8.");
     if (M < 1 || M > 8) return gq_fail(GQ_EINVAL, "batch size M must be between 1 and 8 (anyprec.cu:602).");
     if (a.K == 0 || a.K % 32u) return gq_fail(GQ_EINVAL, "input_feat (K) must be a positive multiple of 32.");
@@ -1523,7 +1541,7 @@ int ap_gemv_dispatch_inner(ApArgs a, u32 M, int bits, hipStream_t s, GqHandover 
                                              (bits == 4 ? nk >= 16000000ull
                                                         : (bits == 3 && nk >= 16000000ull &&
                                                            (nk < 200000000ull || (pro != PRO_RMSNORM && a.K >= 8192u)))));
-        if (!force_generic && !exact_mode() && bits <= 4 && ((dq_mask >> (bits - 2)) & 1) && dq_shape && !(ho && ho->dry)) {
+        if (!force_generic && !exact_mode() && bits <= 4 && ((dq_mask >> (bits - 2)) & 1) && dq_shape) {
             const int rc = dq_gemv_try(a, M, bits, pro, s);
             if (rc != GQ_ENOTSUP) return rc;
         }
@@ -1532,7 +1550,6 @@ int ap_gemv_dispatch_inner(ApArgs a, u32 M, int bits, hipStream_t s, GqHandover 
         int rc = gq_plane_gemv_try(a.x, a.out, a.qw, a.lut, M, a.N, a.K, bits, a.normw, a.eps, a.resid, pro, (a.epilogue & GQ_EPI_SILU_PAIRS) != 0, s, a.ws, a.ws_bytes, ho);
         if (rc != GQ_ENOTSUP) return rc;
     }
-    if (ho && ho->dry) return GQ_OK;  // (the exact-mode kernels have no hand-over form)
     const uint64_t qbytes = (uint64_t)bits * a.N * (a.K / 8u);
     const bool pairs = (a.epilogue & GQ_EPI_SILU_PAIRS) != 0;
     if (!force_generic && bits <= 4 && qbytes < 0x7FFFFFFFull && pick_quad_cfg(a.N, a.K, bits, c, pro, false, pairs) &&
@@ -1610,25 +1627,55 @@ extern "C" int gq_anyprec_gemv_fused_ws(const void *x, void *out, const uint32_t
     return gq_anyprec_gemv_fused_ho(x, out, qweight, lut, N, K, bits, norm_weight, eps, residual, epilogue, workspace, workspace_bytes, nullptr,
                                     nullptr, stream);
 }
-extern "C" int gq_anyprec_handover_plan(uint32_t N, uint32_t K, int bits, int has_norm, uint32_t epilogue) {
-    // which kernel would serve the launch, without launching: 1 = its RMSNorm prologue reads ssq_in, 2 = its epilogue writes ssq_out
+namespace {
+alignas(16) unsigned char g_stand_in[16];  // (a 16-byte aligned stand-in for every pointer of a dry dispatch: never dereferenced)
+// a dry dispatch (gq_ap_route) of the launch form: M rows, the RMSNorm prologue, the epilogue flags and the workspace as given
+int ap_dry_dispatch(u32 N, u32 K, int bits, u32 M, bool has_norm, u32 epilogue, size_t ws_bytes, GqHandover *ho) {
+    void *al = g_stand_in;
     ApArgs a{};
-    alignas(16) static const unsigned char al[16] = {0};  // (a 16-byte aligned stand-in for every pointer: never dereferenced)
     a.qw = (const u32 *)al;
     a.lut = (const uint16_t *)al;
     a.x = (const uint16_t *)al;
     a.out = (uint16_t *)al;
     a.normw = has_norm ? (const uint16_t *)al : nullptr;
     a.resid = (epilogue & GQ_EPI_RESIDUAL) ? (const uint16_t *)al : nullptr;
+    a.ws = ws_bytes ? al : nullptr;
+    a.ws_bytes = ws_bytes;
     a.N = N;
     a.K = K;
     a.epilogue = epilogue;
+    t_dry = true;
+    const int rc = ap_gemv_dispatch_inner(a, M, bits, nullptr, ho);
+    t_dry = false;
+    return rc;
+}
+}  // namespace
+extern "C" int gq_anyprec_handover_plan(uint32_t N, uint32_t K, int bits, int has_norm, uint32_t epilogue) {
+    // which kernel would serve the launch, without launching: 1 = its RMSNorm prologue reads ssq_in, 2 = its epilogue writes ssq_out
     GqHandover ho;
-    ho.dry = true;
-    ho.ssq_in = (const float *)al;
-    ho.ssq_out = (epilogue & GQ_EPI_SILU_PAIRS) ? nullptr : (float *)al;
-    if (ap_gemv_dispatch_inner(a, 1, bits, nullptr, &ho) != GQ_OK) return 0;
+    ho.ssq_in = (const float *)(void *)g_stand_in;
+    ho.ssq_out = (epilogue & GQ_EPI_SILU_PAIRS) ? nullptr : (float *)(void *)g_stand_in;
+    if (ap_dry_dispatch(N, K, bits, 1u, has_norm != 0, epilogue, 0, &ho) != GQ_OK) return 0;
     return (ho.ssq_consumed ? 1 : 0) | (ho.ssq_written ? 2 : 0);
+}
+extern "C" int gq_debug_ap_plan_route(uint32_t N, uint32_t K, int bits, uint32_t M, int has_norm, uint32_t epilogue, size_t ws_bytes,
+                                      uint32_t *route) {
+    if (!route) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    route[0] = GQ_AP_ROUTE_NONE, route[1] = route[2] = 0u;
+    // (the argument checks of gq_anyprec_gemv / gq_anyprec_gemv_fused_ws)
+    if (M != 1u && (has_norm || epilogue || ws_bytes)) return gq_fail(GQ_EINVAL, "prologue / epilogue / workspace: M = 1 only.");
+    if ((epilogue & GQ_PRO_SILU_MUL) && has_norm) return gq_fail(GQ_EINVAL, "RMSNorm and SiLU-mul prologues are exclusive.");
+    if ((epilogue & GQ_EPI_SILU_PAIRS) && ((epilogue & GQ_EPI_RESIDUAL) || (N & 1u)))
+        return gq_fail(GQ_EINVAL, "SILU_PAIRS epilogue needs an even N and excludes the residual epilogue.");
+    GqHandover ho;
+    const int rc = ap_dry_dispatch(N, K, bits, M, has_norm != 0, epilogue, ws_bytes, &ho);
+    for (int i = 0; i < 3; i++) route[i] = t_route[i];
+    return rc;
+}
+extern "C" int gq_debug_ap_last_route(uint32_t *route) {
+    if (!route) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    for (int i = 0; i < 3; i++) route[i] = t_route[i];
+    return GQ_OK;
 }
 extern "C" int gq_ssq_rows(const void *x, uint32_t n, float *ssq_out, void *stream) {
     if (!x || !ssq_out || n == 0) return gq_fail(GQ_EINVAL, "null pointer argument / empty vector.");
@@ -1640,6 +1687,7 @@ extern "C" int gq_anyprec_gemv_fused_ho(const void *x, void *out, const uint32_t
                                         uint32_t K, int bits, const void *norm_weight, float eps, const void *residual,
                                         uint32_t epilogue, void *workspace, size_t workspace_bytes, const float *ssq_in, float *ssq_out,
                                         void *stream) {
+    gq_ap_route(GQ_AP_ROUTE_NONE, 0u);
     ApArgs a{};
     a.ssq_in = norm_weight ? ssq_in : nullptr;
     a.ssq_out = ssq_out;

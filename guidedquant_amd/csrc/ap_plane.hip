@@ -1457,6 +1457,7 @@ bool pick_local_cfg(u32 N, u32 K, int bits, PlaneCfg &c) {
 
 template <int BITS, int PRO, int NC, bool SPEC = false>
 int launch_local_inst(const PlaneArgs &a, const PlaneCfg &c, u32 M, hipStream_t s) {
+    if (gq_ap_route(GQ_AP_ROUTE_PLANE_LOCAL, 1u)) return GQ_OK;
     static GqPerDeviceOnce once;
     auto kern = ap_plane_local_kernel<BITS, PRO, NC, SPEC>;
     GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(kern), (int)(160u * 1024u)));
@@ -1487,6 +1488,7 @@ int launch_local(const PlaneArgs &a, const PlaneCfg &c, u32 M, int pro, hipStrea
 
 template <int BITS, int PRO, int NI, int MBT = 1, bool SPEC = false>
 int launch_plane_inst(const PlaneArgs &a, const PlaneCfg &c, u32 M, hipStream_t s) {
+    if (gq_ap_route(GQ_AP_ROUTE_PLANE, 1u)) return GQ_OK;
     static GqPerDeviceOnce once;
     auto kern = ap_plane_kernel<BITS, PRO, NI, MBT, SPEC>;
     GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(kern), (int)(160u * 1024u)));
@@ -1614,7 +1616,6 @@ int plane_launch_slice(const void *x, void *out, const uint32_t *qweight, const 
         a.ssq_out = ho->ssq_out;
         ho->ssq_written = true;
     }
-    if (ho && ho->dry) return GQ_OK;
     if (local) {
         a.rawx = a.himg = 0u;
         switch (bits) {
@@ -1667,7 +1668,6 @@ int gq_plane_gemv_try(const void *x, void *out, const uint32_t *qweight, const v
     // epilogue (out[n] = out[n] + y2[n], every element read and written by the same lane).  Two fp16 roundings instead
     // of one; plain and residual epilogues only.
     if (K > 32768u || K % 256u || pro != PRO_NONE || pairs) return GQ_ENOTSUP;
-    if (ho && ho->dry) return GQ_OK;  // (plan only: the chained / K-split forms have no hand-over form, and nothing may be launched)
     if (ws && M == 1u) {  // with a workspace: K split over blocks, one fp16 rounding (ap_stream.hip)
         const int rc = gq_stream_gemv_ksplit(x, out, qweight, lut, N, K, bits, resid, ws, ws_bytes, stream);
         if (rc != GQ_ENOTSUP) return rc;
@@ -1677,5 +1677,7 @@ int gq_plane_gemv_try(const void *x, void *out, const uint32_t *qweight, const v
     if (!pick_plane_cfg(N, k1, bits, c) || !pick_plane_cfg(N, K - k1, bits, c)) return GQ_ENOTSUP;
     int rc = plane_launch_slice(x, out, qweight, lut, M, N, K, 0u, k1, bits, nullptr, eps, resid, pro, 0, stream);
     if (rc != GQ_OK) return rc;
-    return plane_launch_slice(x, out, qweight, lut, M, N, K, k1, K - k1, bits, nullptr, eps, out, pro, 0, stream);
+    rc = plane_launch_slice(x, out, qweight, lut, M, N, K, k1, K - k1, bits, nullptr, eps, out, pro, 0, stream);
+    if (rc == GQ_OK) gq_ap_route(GQ_AP_ROUTE_PLANE_CHAIN, 2u);  // (the two launches above: each recorded itself, and launched nothing if dry)
+    return rc;
 }

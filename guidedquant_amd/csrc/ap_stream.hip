@@ -1312,6 +1312,7 @@ bool pick_stream_cfg(u32 N, u32 K, int bits, StreamCfg &c, u32 rgb_force = 0) {
 
 template <int BITS, int PRO, int NPU, bool PSUM, int EPI = EPI_ANY>
 int launch_inst(const StreamArgs &a, const StreamCfg &c, hipStream_t s) {
+    if (gq_ap_route(a.rope ? GQ_AP_ROUTE_STREAM_QKV_ROPE : (a.part_out ? GQ_AP_ROUTE_STREAM_KSPLIT : GQ_AP_ROUTE_STREAM), 1u)) return GQ_OK;
     static GqPerDeviceOnce once;
     auto kern = ap_stream_kernel<BITS, PRO, NPU, PSUM, EPI>;
     GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(kern), (int)(160u * 1024u)));
@@ -1388,7 +1389,6 @@ int stream_launch(const void *x, void *out, const uint32_t *qweight, const void 
     a.part_out = ksp ? ksp->part : nullptr;
     a.ssq_in = (ho && pro == PRO_RMSNORM && !((uintptr_t)ho->ssq_in & 15u) && gq_env_int("GQ_SSQ_HANDOVER", 1)) ? ho->ssq_in : nullptr;
     if (ho) ho->ssq_consumed = a.ssq_in != nullptr;
-    if (ho && ho->dry) return GQ_OK;
     a.wpr_ld = K / 32u;
     a.RGB = c.RGB;
     a.img_off = c.img_off;
@@ -1416,7 +1416,7 @@ int stream_launch(const void *x, void *out, const uint32_t *qweight, const void 
         if (bits != 2 || pro != PRO_RMSNORM || !rope || c.psum || c.NPU != 1u || c.W != (u32)ST_W2 || c.gy != 1u || a.ssq_in || a.part_out || a.resid ||
             a.pairs || c.grid + a.H > (u32)gq_cu_count() || (u32)FUSE_ATTN_WAVES > c.W)
             return GQ_ENOTSUP;
-        if (fuse_dry) return GQ_OK;
+        if (fuse_dry || gq_ap_route(GQ_AP_ROUTE_STREAM_QKV_ROPE, 1u)) return GQ_OK;
         const u32 hd = 1u << a.lhd, ns = (u32)FUSE_ATTN_WAVES * 64u / (hd / 8u);
         const size_t asmem = ((size_t)2u * ns + (size_t)ns * hd + ns + 1u) * 4u;
         const size_t smem = c.smem > asmem ? c.smem : asmem;
@@ -1509,6 +1509,7 @@ int gq_stream_gemv_ksplit(const void *x, void *out, const uint32_t *qweight, con
     ks.KS = K / ks.kslice;
     const int rc = stream_launch(x, out, qweight, lut, N, K, bits, nullptr, 0.f, nullptr, PRO_NONE, 0, nullptr, stream, &ks);
     if (rc != GQ_OK) return rc;
+    if (gq_ap_route(GQ_AP_ROUTE_STREAM_KSPLIT, 2u)) return GQ_OK;
     hipLaunchKernelGGL(ap_ksplit_reduce_kernel, dim3((N / 4u + 256u) / 256u), dim3(256), 0, stream, (const float *)ws, (const uint16_t *)resid,
                        (uint16_t *)out, N, ks.KS);
     GQ_HIP_CHECK(hipGetLastError());
@@ -1558,6 +1559,7 @@ extern "C" int gq_anyprec_gemv_qkv_rope_ho(const void *x, void *q_out, const uin
     r.max_seq = max_seq;
     GqHandover ho;
     ho.ssq_in = ssq_in;
+    gq_ap_route(GQ_AP_ROUTE_NONE, 0u);
     const int rc = stream_launch(x, q_out, qweight, lut, N, K, bits, norm_weight, eps, nullptr, PRO_RMSNORM, 0, &r, (hipStream_t)stream, nullptr, &ho);
     return rc == GQ_ENOTSUP ? gq_fail(GQ_ENOTSUP, "gq_anyprec_gemv_qkv_rope: shape / bit width not served.") : rc;
 }

@@ -19,8 +19,12 @@ struct GqHandover {
     float *ssq_out = nullptr;
     bool ssq_written = false;   // the GEMV kernel writes ssq_out in its epilogue
     bool ssq_consumed = false;  // the GEMV kernel's RMSNorm prologue reads ssq_in
-    bool dry = false;           // plan only (gq_anyprec_handover_plan): the launchers record the two flags and return without launching
 };
+
+// The route record of the AP-GEMV dispatch (include/gq_hip.h: gq_debug_ap_last_route, ap_gemv.hip).  Every terminal launch site of the
+// dispatch calls gq_ap_route right in front of its launch, and launches nothing when it returns true: the dispatch is a dry run
+// (gq_anyprec_handover_plan, gq_debug_ap_plan_route), which takes every decision a real one takes.
+bool gq_ap_route(uint32_t family, uint32_t launches, uint32_t variant = 0u);
 
 // One-time per-DEVICE actions (function attributes such as the > 64 KiB dynamic-LDS opt-in are per device: a process that
 // drives several GPUs -- reference-style sequential sharding, device_map -- must repeat them on each one).

@@ -550,6 +550,25 @@ int gq_debug_exact_plan(uint32_t N, uint32_t K, int bits, int prologue, uint32_t
  * GQ_AP_* knobs applied as the dispatcher applies them: plan[0..5] as above, plan[6] = the kernel the launch runs (0 the v_perm kernel,
  * 1 its instance with the ordered reduction in registers, 2 the 2-bit pair-table kernel). */
 int gq_debug_exact_plan_ex(uint32_t N, uint32_t K, int bits, int prologue, uint32_t epilogue, uint32_t *plan);
+/* The route of an AP-GEMV dispatch, as its launch site records it: route[0] = the kernel family (GQ_AP_ROUTE_*), route[1] = the launches
+ * made, route[2] = the exact kernel that ran (as plan[6] above; 0 for the other families).  gq_debug_ap_last_route: the calling thread's
+ * last dispatch (gq_anyprec_gemv*, gq_anyprec_gemv_fused*, gq_anyprec_gemv_qkv_rope*, or a dry one; GQ_AP_ROUTE_NONE after a failed one).
+ * gq_debug_ap_plan_route: a dry dispatch of the launch gq_anyprec_gemv (M rows, has_norm = 0, epilogue = 0) or gq_anyprec_gemv_fused_ws
+ * (M = 1; ws_bytes: the workspace passed, 0 = none) would make under the current mode / environment: every decision of a real one,
+ * nothing launched. */
+#define GQ_AP_ROUTE_NONE 0u
+#define GQ_AP_ROUTE_GENERIC 1u          /* ap_gemv_generic_kernel */
+#define GQ_AP_ROUTE_EXACT 2u            /* ap_gemv_quad_kernel (v_perm, INREG) */
+#define GQ_AP_ROUTE_PAIR_TABLE 3u       /* ap_gemv_pt2_kernel */
+#define GQ_AP_ROUTE_PLANE 4u            /* ap_plane_kernel: shared image, and the rows-per-pass form of M > 1 */
+#define GQ_AP_ROUTE_PLANE_LOCAL 5u      /* ap_plane_local_kernel */
+#define GQ_AP_ROUTE_PLANE_CHAIN 6u      /* two ap_plane_kernel launches over the halves of K, the second adding to the first */
+#define GQ_AP_ROUTE_STREAM 7u           /* ap_stream_kernel */
+#define GQ_AP_ROUTE_STREAM_KSPLIT 8u    /* ap_stream_kernel over K slices + ap_ksplit_reduce_kernel (workspace) */
+#define GQ_AP_ROUTE_DQ 9u               /* ap_gemv_dq_kernel */
+#define GQ_AP_ROUTE_STREAM_QKV_ROPE 10u /* the stream kernel's q / k / v + RoPE form (gq_anyprec_gemv_qkv_rope*) */
+int gq_debug_ap_last_route(uint32_t *route);
+int gq_debug_ap_plan_route(uint32_t N, uint32_t K, int bits, uint32_t M, int has_norm, uint32_t epilogue, size_t ws_bytes, uint32_t *route);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,8 @@ import numpy as np
 
 def _fast(force_plane=True, local=1):
     """Fast mode.  By default the dispatcher sends only the shapes on which the plane-MFMA kernel wins to it
-    (DESIGN.md section 7); the parity tests of that kernel lift the thresholds so that every shape runs on it.
+    (DESIGN.md section 7); the parity tests of that kernel lift the thresholds and switch the decode-to-fp16 kernel off
+    (GQ_DQ=0: the dispatcher tries it first) so that every shape runs on it -- or on the stream kernel where GQ_ST sends it there.
     local = 0 keeps the shapes that would run the local-image variant (<= 16 rows per CU, 2/3-bit, no RMSNorm) on the
     shared-image kernel, so both are checked on the same inputs."""
     from guidedquant_amd import _lib
@@ -16,7 +17,20 @@ def _fast(force_plane=True, local=1):
         os.environ["GQ_PL_MIN_MWEIGHTS"] = "0"
         os.environ["GQ_PL_MAX_BITS"] = "4"
         os.environ["GQ_PL_LOCAL"] = str(local)
+        os.environ["GQ_DQ"] = "0"
         _lib.lib().gq_reset_env_cache()
+
+
+FAST_KNOBS = ("GQ_PL_MIN_MWEIGHTS", "GQ_PL_MAX_BITS", "GQ_PL_LOCAL", "GQ_DQ")  # what _fast() sets: the fixtures pop them again
+
+
+def assert_route(expect, what="the launch"):
+    """the calling thread's last AP-GEMV dispatch ran the kernel family `expect` (a name of _lib.AP_ROUTES, or a tuple of them)"""
+    from guidedquant_amd import _lib
+    route = _lib.ap_last_route()
+    allowed = (expect, ) if isinstance(expect, str) else tuple(expect)
+    assert route[0] in allowed, f"{what} ran the {route[0]} kernel ({route[1]} launches), not {' / '.join(allowed)}"
+    return route
 
 
 def _check_fast(got, x, q, lut, bits, oracle, rows=None, nround=None):
@@ -118,9 +132,10 @@ def lnq_like_layer(N, K, bits, seed, oracle=None):
     return q, lut, np.clip(x, -6e4, 6e4).astype(np.float16)
 
 
-def run_fused(x, q, lut, bits, norm_weight=None, eps=1e-5, residual=None, flags=0, out_elems=None, workspace=False):
+def run_fused(x, q, lut, bits, norm_weight=None, eps=1e-5, residual=None, flags=0, out_elems=None, workspace=False, expect=None):
     """gq_anyprec_gemv_fused through the C ABI on cuda:0 (numpy in, numpy out); out is pre-filled with NaN.
-    workspace: gq_anyprec_gemv_fused_ws with the bytes gq_anyprec_gemv_fused_ws_bytes asks for (NaN-filled)"""
+    workspace: gq_anyprec_gemv_fused_ws with the bytes gq_anyprec_gemv_fused_ws_bytes asks for (NaN-filled).
+    expect: the kernel family the launch must have run (assert_route)"""
     import torch
     from guidedquant_amd import _lib
     d = torch.device("cuda:0")
@@ -137,12 +152,16 @@ def run_fused(x, q, lut, bits, norm_weight=None, eps=1e-5, residual=None, flags=
                                                  nw.data_ptr() if nw is not None else None, eps, rs.data_ptr() if rs is not None else None,
                                                  flags, ws.data_ptr(), nb, _lib.current_stream_ptr())
         _lib.check(rc, "gq_anyprec_gemv_fused_ws")
+        if expect is not None:
+            assert_route(expect)
         torch.cuda.synchronize()
         return out.cpu().numpy()
     rc = _lib.lib().gq_anyprec_gemv_fused(xt.data_ptr(), out.data_ptr(), qt.data_ptr(), lt.data_ptr(), N, K, bits,
                                           nw.data_ptr() if nw is not None else None, eps, rs.data_ptr() if rs is not None else None,
                                           flags, _lib.current_stream_ptr())
     _lib.check(rc, "gq_anyprec_gemv_fused")
+    if expect is not None:
+        assert_route(expect)
     torch.cuda.synchronize()
     return out.cpu().numpy()
 

@@ -1,7 +1,9 @@
 """GPU parity of the kernels the benchmarked decode step actually runs: `gq_anyprec_gemv_fused` in the DEFAULT (fast,
-plane-MFMA) arithmetic mode with the RMSNorm prologue (wqkv, w1w3: `ap_plane_kernel<b, PRO_RMSNORM, *>`), the residual
-epilogue (wo, w2: `ap_plane_local_kernel` / `ap_plane_kernel`), the SiLU*up prologue, the gate/up pair epilogue and the
-two-launch K split (K = 28672), on the Llama-3.1-8B / 3.2-1B / 3.3-70B layer shapes at 2, 3 and 4 bits.
+plane-MFMA) arithmetic mode with the RMSNorm prologue (wqkv, w1w3: `ap_plane_kernel<b, PRO_RMSNORM, *>`; at 2 bits with K <= 4096
+the stream kernel, where the dispatch sends those), the residual epilogue (wo, w2: `ap_plane_local_kernel` / `ap_plane_kernel`), the
+SiLU*up prologue, the gate/up pair epilogue and the two-launch K split (K = 28672), on the Llama-3.1-8B / 3.2-1B / 3.3-70B layer shapes
+at 2, 3 and 4 bits.  `_fast()` switches the decode-to-fp16 kernel off (tests/test_ap_dq_gpu.py checks it), and every launch asserts
+the kernel family that ran (the dispatch's route record, ap_helpers.assert_route).
 
 Oracle side: the element-wise op is restated in numpy with the reference's rounding points (inference/model.py:281-292
 RMSNorm: fp32 norm -> fp16 -> fp16 multiply by the weight; :259-266 fp16 silu * up; :311-313 fp16 residual add), the
@@ -13,7 +15,7 @@ import os
 import numpy as np
 import pytest
 
-from ap_helpers import _check_fast, _fast, half_add, lnq_like_layer, rmsnorm_ref, run_fused, silu_mul_ref
+from ap_helpers import FAST_KNOBS, _check_fast, _fast, assert_route, half_add, lnq_like_layer, rmsnorm_ref, run_fused, silu_mul_ref
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -27,7 +29,7 @@ def _restore_mode():
     yield
     from guidedquant_amd import _lib
     _lib.lib().gq_set_ap_mode(-1)
-    for k in ("GQ_PL_MIN_MWEIGHTS", "GQ_PL_MAX_BITS", "GQ_PL_LOCAL"):
+    for k in FAST_KNOBS:
         os.environ.pop(k, None)
     _lib.lib().gq_reset_env_cache()
 
@@ -51,17 +53,16 @@ def _hidden(rng, K):
     return x.astype(np.float16)
 
 
-# wqkv / w1w3 of Llama-3.1-8B, 3.2-1B, 3.3-70B: the RMSNorm prologue always runs the shared-image plane kernel
+# wqkv / w1w3 of Llama-3.1-8B, 3.2-1B, 3.3-70B: the RMSNorm prologue runs the shared-image plane kernel -- at 2 bits with K <= 4096
+# the stream kernel (GQ_ST's default)
 @pytest.mark.parametrize("bits", [2, 3, 4])
 @pytest.mark.parametrize("N,K", [(6144, 4096), (28672, 4096), (3072, 2048), (16384, 2048), (10240, 8192), (57344, 8192)])
 def test_rmsnorm_prologue_fast_mode(oracle, bits, N, K):
-    if N == 57344 and bits != 2:
-        pytest.skip("70B gate/up at 3/4 bits: same kernel instance as 28672x4096, 2-bit covers the grid size")
     rng, q, lut = _layer(N, K, bits, bits * 101 + N + K)
     x = _hidden(rng, K)
     nw = (1 + 0.1 * rng.normal(0, 1, K)).astype(np.float16)
     _fast()
-    got = run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS)
+    got = run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS, expect="stream" if bits == 2 and K <= 4096 else "plane")
     assert np.isfinite(got.astype(np.float32)).all()
     xn = rmsnorm_ref(x, nw, EPS)
     _check_fast(got, xn, q, lut, bits, oracle, rows=_rows(rng, N))
@@ -77,11 +78,13 @@ def test_rmsnorm_prologue_default_dispatch_equals_unfused_chain(oracle, bits, N,
     x = _hidden(rng, K)
     nw = (1 + 0.1 * rng.normal(0, 1, K)).astype(np.float16)
     _fast(force_plane=False)
-    fused = run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS)
+    # (the default dispatch's families: 2 bits -- the stream kernel behind RMSNorm, and for the plain launch of >= 100 M weights; 3 / 4
+    # bits -- the decode-to-fp16 kernel)
+    fused = run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS, expect="stream" if bits == 2 else "dq")
     xt = torch.from_numpy(x).cuda().float()
     xn = ((xt * torch.rsqrt((xt * xt).mean() + EPS)).half() * torch.from_numpy(nw).cuda()).cpu().numpy()
     assert (xn.view(np.uint16) != rmsnorm_ref(x, nw, EPS).view(np.uint16)).sum() <= 4  # torch on the GPU vs the numpy restatement
-    plain = run_fused(xn, q, lut, bits)
+    plain = run_fused(xn, q, lut, bits, expect=("stream" if N * K >= 100e6 else "plane") if bits == 2 else "dq")
     rows = _rows(rng, N, 32)
     # which kernel family the default dispatch picks (ap_gemv.hip): behind the RMSNorm prologue the plane-MFMA kernel from 20 M weights
     # at every width (round 5); the plain launch from 20 M at 2 bits, 32 M at 3 / 4 bits -- below that the exact kernel
@@ -114,8 +117,10 @@ def test_residual_epilogue_fast_mode(oracle, bits, N, K, local):
     x = rng.normal(0, 1, K).astype(np.float16)
     resid = _hidden(rng, N)
     _fast(local=local)
-    plain = run_fused(x, q, lut, bits)
-    got = run_fused(x, q, lut, bits, residual=resid, flags=GQ_EPI_RESIDUAL)
+    # (the 70B wo at 2 bits: the stream kernel -- GQ_ST's default; every other shape here has <= 16 rows per CU)
+    fam = "stream" if (bits, N, K) == (2, 8192, 8192) else ("plane-local" if local and N <= 4096 else "plane")
+    plain = run_fused(x, q, lut, bits, expect=fam)
+    got = run_fused(x, q, lut, bits, residual=resid, flags=GQ_EPI_RESIDUAL, expect=fam)
     # the epilogue is one fp16 add behind the fp16-rounded GEMV result (model.py:311-313): bit-identical to the two ops
     assert np.array_equal(got.view(np.uint16), half_add(resid, plain).view(np.uint16))
     rows = _rows(rng, N)
@@ -128,17 +133,18 @@ def test_residual_epilogue_fast_mode(oracle, bits, N, K, local):
     assert (np.abs(got[rows].astype(np.float64) - e) <= 2.0**-11 * 1.002 * (np.abs(y64) + np.abs(e)) + 1e-5 * scale + 1e-7).all()
 
 
-@pytest.mark.parametrize("bits", [2, 3])
+@pytest.mark.parametrize("bits", [2, 3, 4])
 def test_residual_epilogue_two_launch_k_split(oracle, bits):
-    """K = 28672 (the 70B down projection): two launches over K-halves, the second adding to the first one's fp16 result
-    through the residual epilogue (resid == out), here with an external residual on top"""
+    """K = 28672 (the 70B down projection) without a workspace: two launches over K-halves, the second adding to the first one's fp16
+    result through the residual epilogue (resid == out), here with an external residual on top"""
     N, K = 8192, 28672
     rng, q, lut = _layer(N, K, bits, bits + 5)
     x = rng.normal(0, 1, K).astype(np.float16)
     resid = _hidden(rng, N)
     _fast()
-    got = run_fused(x, q, lut, bits, residual=resid, flags=GQ_EPI_RESIDUAL)
-    plain = run_fused(x, q, lut, bits)
+    got = run_fused(x, q, lut, bits, residual=resid, flags=GQ_EPI_RESIDUAL, expect="plane-chain")
+    assert assert_route("plane-chain")[1] == 2
+    plain = run_fused(x, q, lut, bits, expect="plane-chain")
     rows = _rows(rng, N, 24)
     _check_fast(plain, x, q, lut, bits, oracle, rows=rows)
     k1 = ((K // 2 + 1023) // 1024) * 1024
@@ -162,11 +168,12 @@ def test_silu_mul_prologue_fast_mode(oracle, bits, N, K, local):
     gu = rng.normal(0, 1.5, 2 * K).astype(np.float16)
     resid = _hidden(rng, N)
     _fast(local=local)
-    got = run_fused(gu, q, lut, bits, flags=GQ_PRO_SILU_MUL)
+    fam = "plane-local" if local else "plane"
+    got = run_fused(gu, q, lut, bits, flags=GQ_PRO_SILU_MUL, expect=fam)
     h = silu_mul_ref(gu[:K], gu[K:])
     rows = _rows(rng, N)
     _check_fast(got, h, q, lut, bits, oracle, rows=rows)
-    both = run_fused(gu, q, lut, bits, residual=resid, flags=GQ_PRO_SILU_MUL | GQ_EPI_RESIDUAL)
+    both = run_fused(gu, q, lut, bits, residual=resid, flags=GQ_PRO_SILU_MUL | GQ_EPI_RESIDUAL, expect=fam)
     assert np.array_equal(both.view(np.uint16), half_add(resid, got).view(np.uint16))
 
 
@@ -181,8 +188,9 @@ def test_rmsnorm_plus_pair_epilogue_fast_mode(oracle, bits, N, K):
     perm = np.stack((np.arange(half), np.arange(half, N)), axis=1).reshape(-1)
     qp, lp = np.ascontiguousarray(q[:, perm, :]), np.ascontiguousarray(lut[perm])
     _fast()
-    y = run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS)
-    o = run_fused(x, qp, lp, bits, norm_weight=nw, eps=EPS, flags=GQ_EPI_SILU_PAIRS, out_elems=half)
+    fam = "stream" if bits == 2 else "plane"  # (K <= 4096 behind RMSNorm at 2 bits: the stream kernel)
+    y = run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS, expect=fam)
+    o = run_fused(x, qp, lp, bits, norm_weight=nw, eps=EPS, flags=GQ_EPI_SILU_PAIRS, out_elems=half, expect=fam)
     want = silu_mul_ref(y[:half], y[half:])
     diff = np.abs(o.astype(np.float64) - want.astype(np.float64))
     assert (diff <= 2.0**-10 * np.abs(want.astype(np.float64)) + 1e-7).all()  # the only freedom: the last bit of exp()
@@ -200,11 +208,11 @@ def test_lnq_like_layers_fast_mode(oracle, bits, N, K, kind):
     _fast()
     if kind == "norm":
         nw = (1 + 0.1 * rng.normal(0, 1, K)).astype(np.float16)
-        got = run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS)
+        got = run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS, expect="stream" if bits == 2 else "plane")
         xin = rmsnorm_ref(x, nw, EPS)
     else:
         xin = (x.astype(np.float32) / 8).astype(np.float16)
-        got = run_fused(xin, q, lut, bits)
+        got = run_fused(xin, q, lut, bits, expect="plane-local")
     assert np.isfinite(got.astype(np.float32)).all()
     # rows: the outlier-centroid rows must be in the sample
     big = np.argsort(-np.abs(lut.astype(np.float32)).max(axis=1))[:24]
@@ -243,7 +251,7 @@ def test_hot_channels_plain(oracle, bits, nhot, local):
             hot[1] = hot[0] ^ 8   # two extracted elements in the same 128-element MFMA group
         x[hot] = 2.0**lr * np.sign(x[hot]) * rng.uniform(0.75, 1.0, nhot)
         x = x.astype(np.float16)
-        got = run_fused(x, q, lut, bits)
+        got = run_fused(x, q, lut, bits, expect="plane-local" if local else "plane")
         check_nonhot_accuracy(got, x, hot, q, lut, bits, oracle)
         _check_fast(got, x, q, lut, bits, oracle)
 
@@ -269,10 +277,13 @@ def test_hot_channels_rmsnorm_and_tails(oracle, bits, N, K):
         x = (x / 64).astype(np.float16)
         if K not in (14336, 28672):
             nw = (1 + 0.1 * rng.normal(0, 1, K)).astype(np.float16)
-            got = run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS)[rows]
+            got = run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS, expect="stream" if bits == 2 and K <= 4096 else "plane")[rows]
             xn = rmsnorm_ref(x, nw, EPS)
             check_nonhot_accuracy(got, xn, hot, qs, ls, bits, oracle)
-        got = run_fused(x, q, lut, bits)[rows]
+        # (plain: <= 16 rows per CU on the local-image kernel, the 70B down projection chained, the 70B wqkv width at 2 bits on the
+        # stream kernel)
+        fam = {4352: "plane-local", 14336: "plane-local", 28672: "plane-chain"}.get(K, "stream" if (bits, K) == (2, 8192) else "plane")
+        got = run_fused(x, q, lut, bits, expect=fam)[rows]
         if K > 16384:
             # two fp16 roundings, the first of a partial sum that may be larger than the result: bound it by the hot part's size
             W = np.abs(oracle.ap_dequant(qs, ls, bits).astype(np.float64))

@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from ap_helpers import _check_fast, _fast
+from ap_helpers import FAST_KNOBS, _check_fast, _fast, assert_route
 from conftest import golden_files
 
 torch = pytest.importorskip("torch")
@@ -22,7 +22,7 @@ def _exact_mode():
     _lib.check(_lib.lib().gq_set_ap_mode(1), "gq_set_ap_mode")
     yield
     _lib.lib().gq_set_ap_mode(-1)
-    for k in ("GQ_PL_MIN_MWEIGHTS", "GQ_PL_MAX_BITS", "GQ_PL_LOCAL"):
+    for k in FAST_KNOBS:
         os.environ.pop(k, None)
     _lib.lib().gq_reset_env_cache()
 
@@ -201,6 +201,20 @@ def test_aplinear_module_and_custom_op(oracle):
 
 
 # ----------------------------------------------------------------------------- fast (plane-MFMA) mode
+def _plane_family(N, K, bits, local):
+    """the kernel family _fast(local=local) sends a plain one-row launch to: the generic kernel where the fast kernels do not serve K
+    (K % 128: _check_fast's bit-identical branch), the two-launch chain above K = 16384, the stream kernel for the 2-bit plain launches
+    GQ_ST sends there (>= 100 M weights at K = 4096; the 70B wqkv width), the local-image kernel at <= 16 rows per CU (local = 1),
+    else the shared-image kernel"""
+    if K % 128:
+        return "generic"
+    if K > 16384:
+        return "plane-chain"
+    if bits == 2 and (N, K) in ((28672, 4096), (10240, 8192)):
+        return "stream"
+    return "plane-local" if local and N <= 4096 else "plane"
+
+
 @pytest.mark.parametrize("path", [p for p in golden_files("ap_b") if int(np.load(p)["bits"]) in (2, 3, 4)])
 @pytest.mark.parametrize("local", [1, 0])
 def test_fast_mode_goldens(oracle, path, local):
@@ -208,6 +222,7 @@ def test_fast_mode_goldens(oracle, path, local):
     bits = int(g["bits"])
     _fast(local=local)
     got = _run_gemv(g["x"], g["qweight"], g["lut"], bits)[0]
+    assert_route(_plane_family(g["qweight"].shape[1], g["qweight"].shape[2] * 32, bits, local))
     _check_fast(got, g["x"], g["qweight"], g["lut"], bits, oracle)
 
 
@@ -223,6 +238,7 @@ def test_fast_mode_random(oracle, bits, N, K, local):
     x = (rng.normal(0, 1, K) * np.where(rng.random(K) < 0.02, 40.0, 1.0)).astype(np.float16)
     _fast(local=local)
     got = _run_gemv(x, q, lut, bits)[0]
+    assert_route(_plane_family(N, K, bits, local))
     _check_fast(got, x, q, lut, bits, oracle)
 
 
@@ -238,6 +254,7 @@ def test_fast_mode_full_size_sampled_rows(oracle, bits, N, K, local):
     x = rng.normal(0, 1, K).astype(np.float16)
     _fast(local=local)
     got = _run_gemv(x, q, lut, bits)[0]
+    assert_route(_plane_family(N, K, bits, local))
     assert np.isfinite(got.astype(np.float32)).all()
     rows = np.unique(np.concatenate([np.arange(0, 40), np.arange(N - 40, N), rng.integers(0, N, 64)]))
     _check_fast(got, x, q, lut, bits, oracle, rows=rows)
@@ -261,19 +278,22 @@ def test_fast_mode_tiny_and_huge_activations(oracle, local):
     _check_fast(got, x, q, lut, bits, oracle)
     x = np.zeros(K, dtype=np.float16)
     assert (_run_gemv(x, q, lut, bits)[0] == 0).all()
+    assert_route(_plane_family(N, K, bits, local))
 
 
 def test_default_dispatch_is_hybrid(oracle):
     """Default fast mode without lifted thresholds: a small matrix is served by the exact-order kernel (bit-identical
-    to the reference order), the 8B gate/up matrix by the plane-MFMA kernel (fp32-class accuracy)."""
+    to the reference order), the 8B wo matrix by the local-image plane kernel and the 8B gate/up matrix by the stream kernel
+    (fp32-class accuracy)."""
     from guidedquant_amd import pack
     rng = np.random.default_rng(21)
     _fast(force_plane=False)
-    for N, K, plane in ((2048, 4096, False), (4096, 4096, True), (28672, 4096, True)):
+    for N, K, plane, fam in ((2048, 4096, False, "exact"), (4096, 4096, True, "plane-local"), (28672, 4096, True, "stream")):
         q = pack.random_planes(N, K, 2, seed=N)
         lut = np.sort(rng.normal(0, 0.02, (N, 4)).astype(np.float16), axis=1)
         x = rng.normal(0, 1, K).astype(np.float16)
         got = _run_gemv(x, q, lut, 2)[0]
+        assert_route(fam)
         rows = np.unique(rng.integers(0, N, 96))
         if plane:
             _check_fast(got, x, q, lut, 2, oracle, rows=rows)
@@ -301,6 +321,7 @@ def test_fast_mode_is_deterministic(bits, N, K):
         ap_gemv.anyprec_gemv(x, out, q, lut, bits)
         outs.append(out)
     torch.cuda.synchronize()
+    assert_route(_plane_family(N, K, bits, 1))
     ref = outs[0].view(torch.int16)
     assert bool(torch.isfinite(outs[0].float()).all())
     for o in outs[1:]:
@@ -318,6 +339,7 @@ def test_fast_mode_multi_batch(oracle, N, K):
     X = rng.normal(0, 1, (M, K)).astype(np.float16)
     _fast()
     got = _run_gemv(X, q, lut, bits, M=M)
+    assert_route("plane-chain" if K > 16384 else "plane")
     for mm in range(M):
         _check_fast(got[mm], X[mm], q, lut, bits, oracle)
 
@@ -328,7 +350,8 @@ def test_fast_mode_rows_share_one_pass(oracle, monkeypatch, bits, M, N, K):
     """M = 2 .. 8 batch rows, up to 4 per pass over the planes (the reference's multi_row kernel, anyprec.cu:381,425,494-506): one
     image per row in MFMA columns 4 mm .. 4 mm + 3.  The arithmetic of a row is that of the one-row launch: results bit-identical
     to GQ_PL_ONEPASS=0 (one block row per batch row, same image builders), row by row within the fast-mode envelope; one row carries massive channels
-    (extraction list entries tagged with their row).  Shapes whose images do not fit (K = 8192 at 3 / 4 bits) fall back."""
+    (extraction list entries tagged with their row).  Shapes whose images do not fit (K = 8192 and 4352 at 3 / 4 bits) fall back to one
+    block row per batch row -- on the local-image kernel, their <= 16 rows per CU."""
     from guidedquant_amd import _lib, pack
     rng = np.random.default_rng(bits * 31 + M + N + K)
     q = pack.random_planes(N, K, bits, seed=M + K)
@@ -340,12 +363,14 @@ def test_fast_mode_rows_share_one_pass(oracle, monkeypatch, bits, M, N, K):
     X = X.astype(np.float16)
     _fast()
     got = _run_gemv(X, q, lut, bits, M=M)
+    assert_route("plane-local" if bits > 2 and K in (8192, 4352) else "plane")
     monkeypatch.setenv("GQ_PL_ONEPASS", "0")
     # the same kernel and image builders for the reference run: the local-image variant (own scale per wave) and the late-wave image
     # helpers (sum(x) partials split differently) give last-bit differences
     monkeypatch.setenv("GQ_PL_HIMG", "0")
     _fast(local=0)
     ref = _run_gemv(X, q, lut, bits, M=M)
+    assert_route("plane")
     monkeypatch.delenv("GQ_PL_HIMG")
     _fast()
     ref_dflt = _run_gemv(X, q, lut, bits, M=M)  # (what a shape whose images do not fit falls back to: the default one-row dispatch)
@@ -374,6 +399,7 @@ def test_fast_mode_within_north_star_tolerance_of_reference_order(oracle, bits, 
     y64 = oracle.ap_gemv_f64(x, qs, ls, bits)[0]
     _fast()
     g = _run_gemv(x, q, lut, bits)[0][rows].astype(np.float64)
+    assert_route(_plane_family(N, K, bits, 1))
     rel = np.linalg.norm(g - ref) / np.linalg.norm(ref)
     assert rel <= REL_TOL, rel
     assert rel <= 1.1 * np.linalg.norm(y64 - ref) / np.linalg.norm(ref) + 1e-5

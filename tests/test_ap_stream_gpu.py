@@ -10,7 +10,7 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-from ap_helpers import _check_fast, _fast, check_nonhot_accuracy, half_add, rmsnorm_ref, run_fused, silu_mul_ref  # noqa: E402
+from ap_helpers import FAST_KNOBS, _check_fast, _fast, check_nonhot_accuracy, half_add, rmsnorm_ref, run_fused, silu_mul_ref  # noqa: E402
 
 EPS = 1e-5
 
@@ -29,7 +29,7 @@ def _stream_everywhere():
     os.environ["GQ_ST"] = "3"
     _lib.lib().gq_reset_env_cache()
     yield
-    for k in ("GQ_ST", "GQ_PL_MIN_MWEIGHTS", "GQ_PL_MAX_BITS", "GQ_PL_LOCAL"):  # (_fast() lifts the dispatch thresholds: not for the tests that follow)
+    for k in ("GQ_ST", ) + FAST_KNOBS:  # (_fast() lifts the dispatch thresholds: not for the tests that follow)
         os.environ.pop(k, None)
     _lib.lib().gq_reset_env_cache()
     _lib.lib().gq_set_ap_mode(-1)
@@ -62,10 +62,11 @@ def test_stream_kernel_plain_and_residual(oracle, bits, N, K):
     rng, q, lut = _layer(N, K, bits, 3 * bits + N + K)
     x = rng.normal(0, 1, K).astype(np.float16)
     rows = _rows(rng, N)
-    got = run_fused(x, q, lut, bits)
+    fam = "plane-local" if K == 14336 and bits > 2 else "stream"
+    got = run_fused(x, q, lut, bits, expect=fam)
     _check_fast(got, x, q, lut, bits, oracle, rows=rows)
     res = rng.normal(0, 1, N).astype(np.float16)
-    got_r = run_fused(x, q, lut, bits, residual=res, flags=1)
+    got_r = run_fused(x, q, lut, bits, residual=res, flags=1, expect=fam)
     assert np.array_equal(got_r.view(np.uint16), half_add(res, got).view(np.uint16))  # fp16 add of the same sums (model.py:311-313)
 
 
@@ -78,10 +79,10 @@ def test_stream_kernel_rmsnorm_and_pairs(oracle, bits, N, K):
     x = x.astype(np.float16)
     nw = (1 + 0.1 * rng.normal(0, 1, K)).astype(np.float16)
     xn = rmsnorm_ref(x, nw, EPS)
-    got = run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS)
+    got = run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS, expect="stream")
     _check_fast(got, xn, q, lut, bits, oracle, rows=_rows(rng, N))
     # gate/up pair epilogue on the same sums: silu(y[2i]) * y[2i+1] with the reference's fp16 rounding points (model.py:259-266)
-    pairs = run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS, flags=4, out_elems=N // 2)
+    pairs = run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS, flags=4, out_elems=N // 2, expect="stream")
     assert np.array_equal(pairs.view(np.uint16), silu_mul_ref(got[0::2], got[1::2]).view(np.uint16))
 
 
@@ -91,7 +92,7 @@ def test_stream_kernel_silu_prologue(oracle, N, K):
     rng, q, lut = _layer(N, K, bits, 17 + N + K)
     gu = rng.normal(0, 1, 2 * K).astype(np.float16)
     xs = silu_mul_ref(gu[:K], gu[K:])
-    got = run_fused(gu, q, lut, bits, flags=2)
+    got = run_fused(gu, q, lut, bits, flags=2, expect="stream")
     _check_fast(got, xs, q, lut, bits, oracle, rows=_rows(rng, N))
 
 
@@ -105,8 +106,8 @@ def test_stream_kernel_massive_channels(oracle, lr):
     x[hot] = 2.0**lr * np.sign(x[hot])
     x = (x / 64).astype(np.float16)
     nw = (1 + 0.1 * rng.normal(0, 1, K)).astype(np.float16)
-    check_nonhot_accuracy(run_fused(x, q, lut, bits), x, hot, q, lut, bits, oracle)
-    check_nonhot_accuracy(run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS), rmsnorm_ref(x, nw, EPS), hot, q, lut, bits, oracle)
+    check_nonhot_accuracy(run_fused(x, q, lut, bits, expect="stream"), x, hot, q, lut, bits, oracle)
+    check_nonhot_accuracy(run_fused(x, q, lut, bits, norm_weight=nw, eps=EPS, expect="stream"), rmsnorm_ref(x, nw, EPS), hot, q, lut, bits, oracle)
 
 
 # ----------------------------------------------------------------------------- rows wider than 16384: K split over blocks
@@ -127,11 +128,11 @@ def test_k_split_over_blocks_with_a_workspace(oracle, monkeypatch, N, K, kslice)
     x[rng.choice(K, 6, replace=False)] *= 40.0  # massive channels (the SiLU * up product is where Llama has them)
     x = x.astype(np.float16)
     rows = _rows(rng, N)
-    got = run_fused(x, q, lut, 2, workspace=True)
+    got = run_fused(x, q, lut, 2, workspace=True, expect="stream-ksplit")
     assert np.isfinite(got).all()
     _check_fast(got, x, q, lut, 2, oracle, rows=rows, nround=1.0)
     res = rng.normal(0, 1, N).astype(np.float16)
-    got_r = run_fused(x, q, lut, 2, residual=res, flags=1, workspace=True)
+    got_r = run_fused(x, q, lut, 2, residual=res, flags=1, workspace=True, expect="stream-ksplit")
     assert np.array_equal(got_r.view(np.uint16), half_add(res, got).view(np.uint16))
     _lib.lib().gq_reset_env_cache()
 
@@ -150,5 +151,5 @@ def test_k_split_hot_channels_at_the_70b_down_projection(oracle):
     x[hot] = rng.choice([-1.0, 1.0], 5) * rng.uniform(40.0, 120.0, 5)
     x = x.astype(np.float16)
     rows = _rows(rng, N, n=24)
-    got = run_fused(x, q, lut, 2, workspace=True)
+    got = run_fused(x, q, lut, 2, workspace=True, expect="stream-ksplit")
     check_nonhot_accuracy(got[rows], x, hot, np.ascontiguousarray(q[:, rows, :]), lut[rows], 2, oracle, nround=1.0)

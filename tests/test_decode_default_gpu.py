@@ -180,8 +180,9 @@ def test_default_vs_exact_mode_greedy_tokens_over_100_steps():
     assert len(set(seq_e)) > 10  # the sequence is not a degenerate fixed point
 
 
-def test_default_mode_over_all_32_layers_of_the_benchmark_model():
-    """the FULL Llama-3.1-8B depth the benchmark times (32 layers, 2-bit), against the TRUE value: the same network with the
+@pytest.mark.parametrize("bits", [2, 3, 4])
+def test_default_mode_over_all_32_layers_of_the_benchmark_model(bits):
+    """the FULL Llama-3.1-8B depth the benchmark times (32 layers; 2-bit: the headline, 3- and 4-bit: ap_3bit / ap_4bit), against the TRUE value: the same network with the
     dequantised weights as dense fp32 matrices, every op in fp32.  Teacher-forced over 24 positions, the default-mode logits
     (what bench.py times) and the exact-mode logits (the reference kernel's fp16 accumulation order, bit for bit) are both
     compared with it: the default mode is at least as close to the true logits as the reference's own arithmetic (norm-wise,
@@ -190,7 +191,7 @@ def test_default_mode_over_all_32_layers_of_the_benchmark_model():
     from guidedquant_amd import ap_gemv
     from guidedquant_amd.model import Transformer
     d = torch.device("cuda:0")
-    m = _model(2, n_layer=32, seed=5)
+    m = _model(bits, n_layer=32, seed=5)
     # the dense fp32 twin, built before the native decode pairs the gate / up rows in place
     ref = Transformer(torch.float32, m.config).to(device=d, dtype=torch.float32).eval()
     with torch.no_grad():
@@ -202,7 +203,7 @@ def test_default_mode_over_all_32_layers_of_the_benchmark_model():
             lr.post_attention_layernorm.weight.copy_(lq.post_attention_layernorm.weight.float())
             for get in (lambda b: b.attention.wqkv, lambda b: b.attention.wo, lambda b: b.feed_forward.w1w3, lambda b: b.feed_forward.w2):
                 q = get(lq)
-                get(lr).weight.copy_(ap_gemv.anyprec_dequant(q.qweight, q.lut, 2).float())
+                get(lr).weight.copy_(ap_gemv.anyprec_dequant(q.qweight, q.lut, bits).float())
     n = 24
     m.setup_caches(1, n + 8)
     ref.setup_caches(1, n + 8)
