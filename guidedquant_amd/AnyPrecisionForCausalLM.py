@@ -352,6 +352,8 @@ class AnyPrecisionForCausalLM(nn.Module):
              fused sampler at its end -- opt-in: measured SLOWER than route 3 on the 8B model (172 vs 249 tokens/s: the module tree's
              ~1,500 small launches per token cost more as graph nodes than as stream launches; the fused model is the fast form);
           3. transformers' own generate on the module tree (anything else: beams, top_p, processors, batches; or `native=False`).
+        Route 1 serves every precision of the checkpoint, 2 to 8 bits: the decode step's GEMVs run the exact fp16-order kernels
+        below 5 bits and ap_wide.hip's LDS-table kernel from 5 to 8 (a parent of 8 bits serves precision=5..8 without the module tree).
         Returns the [1, prompt + new] token tensor like HF does; stops at EOS (checked every 32 tokens, the tail is cut); honours
         min_new_tokens, streamer, precision=."""
         prev_precision = self.precision

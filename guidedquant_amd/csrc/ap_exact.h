@@ -1,0 +1,245 @@
+// ap_exact.h -- device code shared by the Any-Precision GEMV kernels that keep the reference's fp16 order: the launch arguments, the
+// fused prologues' arithmetic, the natural-order activation staging and the ordered reduction + epilogues.  Included by ap_gemv.hip
+// (ap_gemv_quad_kernel, ap_gemv_pt2_kernel, ap_gemv_dq_kernel) and ap_wide.hip (ap_gemv_wide_kernel, bits 5..8).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ap_core.h"
+#include "gq_internal.h"
+
+namespace {
+using namespace gq;
+
+struct ApArgs {
+    const u32 *qw;         // [bits][N][K/32]
+    const uint16_t *lut;   // [N][2^bits]
+    const uint16_t *x;     // [M][K]
+    uint16_t *out;         // [M][N] (or [M][N/2] with SILU_MUL)
+    const uint16_t *normw; // [K] or null
+    const uint16_t *resid; // [N] or null
+    u32 N, K;
+    u32 RS;                // row slots per block step = blockDim.x / Q
+    u32 SPB;               // row steps per block
+    u32 epilogue;
+    float eps;
+    void *ws;              // optional caller workspace (gq_anyprec_gemv_fused_ws) and its size
+    size_t ws_bytes;
+    const float *ssq_in;   // statistics hand-over (gq_anyprec_gemv_fused_ho): partial sums of squares of x / of the outputs
+    float *ssq_out;
+    unsigned long long *dbg = nullptr;  // GQ_STAMPS builds: the debug buffer of gq_debug_set_timing_buffer (tools/r6/exact_stamps.py)
+};
+
+__device__ __forceinline__ uint4 ld16(const void *p) { return *reinterpret_cast<const uint4 *>(p); }
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint4 ld16_nt(const void *p) {
+    u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+__device__ __forceinline__ float h2f(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
+__device__ __forceinline__ uint16_t f2h(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
+
+// Fused prologues, with the same fp16 rounding points as the reference's separate kernels (ap_gemv.hip::stage_x, stage_x_natural below):
+//   PRO_RMSNORM: y = (x.float() * rsqrt(mean(x^2) + eps)).half() * w        (inference/model.py:281-292)
+//   PRO_SILUMUL: y = silu(g) * u with g = x[0:K], u = x[K:2K]                (inference/model.py:266)
+enum { PRO_NONE = 0, PRO_RMSNORM = 1, PRO_SILUMUL = 2 };
+
+__device__ __forceinline__ u32 silu_mul_pk(u32 g, u32 u) {
+    // F.silu on an fp16 tensor evaluates x / (1 + exp(-x)) in fp32 and rounds to fp16; then an fp16 multiply.
+    float g0 = h2f(g & 0xFFFF), g1 = h2f(g >> 16);
+    _Float16 s0 = (_Float16)(g0 / (1.0f + __expf(-g0)));
+    _Float16 s1 = (_Float16)(g1 / (1.0f + __expf(-g1)));
+    _Float16 r0 = s0 * __builtin_bit_cast(_Float16, (uint16_t)(u & 0xFFFF));
+    _Float16 r1 = s1 * __builtin_bit_cast(_Float16, (uint16_t)(u >> 16));
+    return (u32)__builtin_bit_cast(uint16_t, r0) | ((u32)__builtin_bit_cast(uint16_t, r1) << 16);
+}
+
+// ----------------------------------------------------------------------------------------------
+// Final reduction of one row from its per-(chunk, virtual lane) fp16 partials in LDS:
+// chunks in ascending order per lane (anyprec.cu:505), then the 16,8,4,2,1 shuffle tree (anyprec.cu:363-370).
+// Called by 32 consecutive lanes (t = lane & 31).  Returns the row value in lane t == 0.
+// ----------------------------------------------------------------------------------------------
+// The chain is what the reference computes; how the values travel is this chip's: the partials of four chunks are read from LDS in
+// one round trip, the 16-lane step is one v_permlane16_swap (rows 0 / 1 of the wave exchanged in registers), the 8 / 4 / 2 / 1 steps are
+// DPP operands of the adds (row_ror:8, row_shl:4, quad_perm) -- lane t < sh receives lane t + sh exactly as __shfl_down(.., sh, 32) hands
+// it over, the other lanes' values are never used.  (Round 6: with one ds_read / ds_bpermute round trip per add the epilogue of a block
+// was 0.6 us per pass of T / 32 rows -- 2.8 of the 12.7 us of a w1w3 block; tools/r6/exact_stamps.py.)
+__device__ __forceinline__ uint16_t h_add_dpp16(uint16_t p) {  // p[t] + p[t + 16], t < 16 of every 32
+    const u32 v = p;
+    auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);  // r[0] = rows (0, 0, 2, 2), r[1] = rows (1, 1, 3, 3)
+    return h_add((uint16_t)r[0], (uint16_t)r[1]);
+}
+template <int CTRL>
+__device__ __forceinline__ uint16_t h_add_dpp(uint16_t p) {
+    return h_add(p, (uint16_t)__builtin_amdgcn_update_dpp(0, (int)(u32)p, CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ uint16_t reduce_tree(uint16_t p) {
+    p = h_add_dpp16(p);
+    p = h_add_dpp<0x128>(p);  // row_ror:8   lane t <- t + 8 (mod 16)
+    p = h_add_dpp<0x104>(p);  // row_shl:4   lane t <- t + 4
+    p = h_add_dpp<0x4E>(p);   // quad_perm [2,3,0,1]
+    p = h_add_dpp<0xB1>(p);   // quad_perm [1,0,3,2]
+    return p;
+}
+__device__ __forceinline__ uint16_t reduce_row(const RowGeom &G, const uint16_t *sv, u32 t, u32 c0, u32 c1) {
+    uint16_t p = 0;
+    for (u32 i0 = c0; i0 < c1; i0 += 4u) {
+        uint16_t v[4];
+        bool ok[4];
+#pragma unroll
+        for (u32 j = 0; j < 4u; j++) {
+            const u32 i = i0 + j;
+            ok[j] = i < c1 && !(i == G.nfull && t >= G.eff);  // (the lanes past the end of a partial last chunk hold no partial: no add)
+            v[j] = sv[(ok[j] ? i : c0) * 32u + t];
+        }
+#pragma unroll
+        for (u32 j = 0; j < 4u; j++) p = ok[j] ? h_add(p, v[j]) : p;
+    }
+    return reduce_tree(p);
+}
+
+// NCH > 0: rows of exactly NCH full chunks (no predicates, one LDS round trip for all partials of a row)
+template <int NCH>
+__device__ __forceinline__ uint16_t reduce_row_n(const RowGeom &G, const uint16_t *sv, u32 t) {
+    if constexpr (NCH == 0) return reduce_row(G, sv, t, 0u, G.nchunks);
+    else {
+        uint16_t v[NCH];
+#pragma unroll
+        for (int i = 0; i < NCH; i++) v[i] = sv[(u32)i * 32u + t];
+        uint16_t p = 0;
+#pragma unroll
+        for (int i = 0; i < NCH; i++) p = h_add(p, v[i]);
+        return reduce_tree(p);
+    }
+}
+
+// Ordered reduction + epilogue of the R rows of a block, 32 lanes per row, TWO rows per 32-lane group and trip (their LDS round trips
+// and add chains are independent: the compiler interleaves them); the residual is requested before the row's partials are read.
+// KS: the reference's K-split (anyprec.cu:611, bits >= 7 and K > 4096 at one batch row): groups of 4 chunks, each through the chunk
+// sum and the tree, added in ascending order into a zeroed fp16 cell (ap_wide.hip)
+__device__ __forceinline__ uint16_t reduce_row_ksplit(const RowGeom &G, const uint16_t *sv, u32 t) {
+    uint16_t total = 0;
+    for (u32 c0 = 0; c0 < G.nchunks; c0 += 4u) total = h_add(total, reduce_row(G, sv, t, c0, c0 + 4u < G.nchunks ? c0 + 4u : G.nchunks));
+    return total;
+}
+
+template <int NCH, bool KS = false>
+__device__ __forceinline__ void rows_epilogue_n(const RowGeom &G, const ApArgs &a, const uint16_t *sv, u32 svrow, u32 R, u32 row0, u32 m,
+                                                u32 tid, u32 T) {
+    const u32 t = tid & 31u, stride = T >> 5;
+    const bool pairs = a.epilogue & GQ_EPI_SILU_PAIRS;
+    for (u32 r0 = tid >> 5; r0 < R; r0 += 2u * stride) {
+        const u32 r1 = r0 + stride;
+        const bool has1 = r1 < R;
+        const u32 row[2] = {row0 + r0, row0 + r1};
+        const bool live[2] = {true, has1};
+        uint16_t res[2] = {0, 0};
+        if (!pairs && a.resid) {
+#pragma unroll
+            for (int e = 0; e < 2; e++)
+                if (live[e] && row[e] < a.N) res[e] = a.resid[(size_t)m * a.N + row[e]];
+        }
+        uint16_t y[2];
+        if constexpr (KS) {
+            y[0] = reduce_row_ksplit(G, sv + (size_t)r0 * svrow, t);
+            y[1] = reduce_row_ksplit(G, sv + (size_t)(has1 ? r1 : r0) * svrow, t);
+        } else {
+            y[0] = reduce_row_n<NCH>(G, sv + (size_t)r0 * svrow, t);
+            y[1] = reduce_row_n<NCH>(G, sv + (size_t)(has1 ? r1 : r0) * svrow, t);
+        }
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            if (pairs) {
+                // rows (2i, 2i+1) = (gate_i, up_i) sit in the two halves of the wave: F.silu(gate) * up on fp16 values
+                // (inference/model.py:266), written to out[i]
+                const u32 yy = y[e];
+                auto sw = __builtin_amdgcn_permlane32_swap(yy, yy, false, false);  // sw[1]: lanes 32..63 of y in both halves
+                const uint16_t yo = (uint16_t)sw[1];
+                if (live[e] && t == 0 && !(tid & 32u) && row[e] + 1u < a.N) {
+                    const float gv = (float)__builtin_bit_cast(_Float16, y[e]);
+                    const _Float16 o = (_Float16)(gv / (1.0f + __expf(-gv))) * __builtin_bit_cast(_Float16, yo);
+                    a.out[(size_t)m * (a.N >> 1) + (row[e] >> 1)] = __builtin_bit_cast(uint16_t, o);
+                }
+            } else if (live[e] && t == 0 && row[e] < a.N) {
+                if (a.resid) y[e] = h_add(res[e], y[e]);
+                a.out[(size_t)m * a.N + row[e]] = y[e];
+            }
+        }
+    }
+}
+template <bool KS = false>
+__device__ __forceinline__ void rows_epilogue(const RowGeom &G, const ApArgs &a, const uint16_t *sv, u32 svrow, u32 R, u32 row0, u32 m, u32 tid,
+                                              u32 T) {
+    if constexpr (KS) {
+        rows_epilogue_n<0, true>(G, a, sv, svrow, R, row0, m, tid, T);
+        return;
+    }
+    // (compiled-in chunk counts of the Llama rows: K = 4096, 8192, 14336; everything else -- partial last chunks too -- on the general one)
+    const u32 nch = G.eff ? 0u : G.nchunks;
+    if (nch == 4u) rows_epilogue_n<4>(G, a, sv, svrow, R, row0, m, tid, T);
+    else if (nch == 8u) rows_epilogue_n<8>(G, a, sv, svrow, R, row0, m, tid, T);
+    else if (nch == 14u) rows_epilogue_n<14>(G, a, sv, svrow, R, row0, m, tid, T);
+    else rows_epilogue_n<0>(G, a, sv, svrow, R, row0, m, tid, T);
+}
+
+// ----------------------------------------------------------------------------------------------
+// The activation image in LDS in x's natural order (a lane's 8 activations of (word v, byte c) are 16 contiguous bytes), with the
+// prologues of stage_x (ap_gemv.hip).
+// ----------------------------------------------------------------------------------------------
+template <int PRO>
+__device__ __forceinline__ void stage_x_natural(const RowGeom &G, const uint16_t *x, const uint16_t *normw, float eps, uint16_t *xlds, float *red,
+                                                bool stager, u32 T) {
+    // 16-byte units (8 activations) per stager thread; same arithmetic and rounding points as stage_x
+    const u32 tid = threadIdx.x, nun = G.K / 8u;
+    float scale = 0.f;
+    if constexpr (PRO == PRO_RMSNORM) {
+        // (the sum of squares in stage_x's order -- thread idx takes the 32 activations of (quad idx / 4, byte idx % 4) -- so that both
+        // exact kernels normalise with the same fp32 statistic, bit for bit)
+        float ss = 0.f;
+        for (u32 idx = stager ? tid : 4u * G.Q; idx < 4u * G.Q; idx += T) {
+            const u32 e0 = G.xindex(idx >> 2, 0u, idx & 3u, 0u);
+#pragma unroll
+            for (int v = 0; v < 4; v++) {
+                const uint4 t4 = ld16(x + e0 + 8 * v);
+                const u32 w[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const float a = h2f(w[i] & 0xFFFF), b = h2f(w[i] >> 16);
+                    ss += a * a;
+                    ss += b * b;
+                }
+            }
+        }
+        ss = gq_wave_allsum(ss);
+        if ((tid & 63u) == 0 && stager) red[tid >> 6] = ss;
+        __syncthreads();
+        // (the stager waves' sums: one LDS round trip + the same register tree, instead of one dependent ds_read per wave)
+        const float tot = gq_wave_allsum((tid & 63u) < (T + 63u) / 64u ? red[tid & 63u] : 0.f);
+        scale = 1.0f / sqrtf(tot / (float)G.K + eps);
+    }
+    for (u32 u = stager ? tid : nun; u < nun; u += T) {
+        uint4 t4 = ld16(x + 8u * u);
+        u32 in[4] = {t4.x, t4.y, t4.z, t4.w};
+        if constexpr (PRO == PRO_RMSNORM) {
+            const uint4 n4 = ld16(normw + 8u * u);
+            const u32 nw[4] = {n4.x, n4.y, n4.z, n4.w};
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const uint16_t a = f2h(gq_pin_f32(h2f(in[i] & 0xFFFF) * scale)), b = f2h(gq_pin_f32(h2f(in[i] >> 16) * scale));
+                const _Float16 ra = __builtin_bit_cast(_Float16, a) * __builtin_bit_cast(_Float16, (uint16_t)(nw[i] & 0xFFFF));
+                const _Float16 rb = __builtin_bit_cast(_Float16, b) * __builtin_bit_cast(_Float16, (uint16_t)(nw[i] >> 16));
+                in[i] = (u32)__builtin_bit_cast(uint16_t, ra) | ((u32)__builtin_bit_cast(uint16_t, rb) << 16);
+            }
+        }
+        if constexpr (PRO == PRO_SILUMUL) {
+            const uint4 u4 = ld16(x + G.K + 8u * u);
+            const u32 uw[4] = {u4.x, u4.y, u4.z, u4.w};
+#pragma unroll
+            for (int i = 0; i < 4; i++) in[i] = silu_mul_pk(in[i], uw[i]);
+        }
+        *reinterpret_cast<uint4 *>(xlds + 8u * u) = make_uint4(in[0], in[1], in[2], in[3]);
+    }
+}
+
+}  // namespace

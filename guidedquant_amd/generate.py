@@ -483,7 +483,7 @@ if __name__ == "__main__":
     parser.add_argument('--profile', type=str, default=None, help='accepted for compatibility (use rocprofv3)')
     parser.add_argument('--device', type=str, default="cuda")
     parser.add_argument('--model_name', type=str, default=None)
-    parser.add_argument('--bitwidth', type=int, default=None, choices=[2, 3, 4, 16])
+    parser.add_argument('--bitwidth', type=int, default=None, choices=[2, 3, 4, 5, 6, 7, 8, 16])
     parser.add_argument('--checkpoint_path', type=str, default=None)
     parser.add_argument('--config_path', type=str, default=None, help='QTIP config path')
     parser.add_argument('--dtype', type=str, default="float16", choices=["float16", "float32", "bfloat16"])

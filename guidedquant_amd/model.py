@@ -384,7 +384,7 @@ class Transformer(nn.Module):
         return self._native_kind() is not None
 
     def _native_kind(self):
-        """'ap': fused-linear Any-Precision model (<= 4 bit) -> gq_anyprec_gemv_fused chain; 'qtip': unfused QTIP model
+        """'ap': fused-linear Any-Precision model (<= 8 bit) -> gq_anyprec_gemv_fused chain; 'qtip': unfused QTIP model
         with power-of-two widths -> gq_qtip_linear_in / _out chain; None: the module-by-module forward."""
         from .APLinear import APLinear
         if not (self.cache_initialized and self.output.weight.is_cuda):
@@ -396,7 +396,7 @@ class Transformer(nn.Module):
             return kind or None
         kind = ""
         if self.fuse_linears:
-            if all(isinstance(m, APLinear) and m.bias is None and m.bitwidth <= 4 and m.in_features % 128 == 0
+            if all(isinstance(m, APLinear) and m.bias is None and m.bitwidth <= 8 and m.in_features % 128 == 0
                    for b in self.layers for m in (b.attention.wqkv, b.attention.wo, b.feed_forward.w1w3, b.feed_forward.w2)):
                 kind = "ap"
         elif os.environ.get("GQ_NATIVE_QTIP", "1") != "0":

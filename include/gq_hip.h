@@ -567,6 +567,7 @@ int gq_debug_exact_plan_ex(uint32_t N, uint32_t K, int bits, int prologue, uint3
 #define GQ_AP_ROUTE_STREAM_KSPLIT 8u    /* ap_stream_kernel over K slices + ap_ksplit_reduce_kernel (workspace) */
 #define GQ_AP_ROUTE_DQ 9u               /* ap_gemv_dq_kernel */
 #define GQ_AP_ROUTE_STREAM_QKV_ROPE 10u /* the stream kernel's q / k / v + RoPE form (gq_anyprec_gemv_qkv_rope*) */
+#define GQ_AP_ROUTE_WIDE 11u            /* ap_gemv_wide_kernel: bits 5..8, one batch row, the reference's order */
 int gq_debug_ap_last_route(uint32_t *route);
 int gq_debug_ap_plan_route(uint32_t N, uint32_t K, int bits, uint32_t M, int has_norm, uint32_t epilogue, size_t ws_bytes, uint32_t *route);
 
