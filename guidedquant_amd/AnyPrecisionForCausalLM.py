@@ -212,6 +212,12 @@ class AnyPrecisionForCausalLM(nn.Module):
             meta = [b for b, buf in mod._buffers.items() if buf is not None and buf.is_meta]
             if not meta:
                 continue
+            # (a scalar buffer whose value the module also keeps as a Python number: Gemma3's embedding scale, `scalar_embed_scale`)
+            for b in [b for b in meta if hasattr(mod, "scalar_" + b)]:
+                mod._buffers[b] = torch.tensor(getattr(mod, "scalar_" + b), dtype=mod._buffers[b].dtype)
+                meta.remove(b)
+            if not meta:
+                continue
             if not hasattr(mod, "config"):
                 raise RuntimeError(f"buffers {meta} of {type(mod).__name__} have no data in the checkpoint")
             with torch.device("cpu"):
@@ -377,10 +383,18 @@ class AnyPrecisionForCausalLM(nn.Module):
                         raise ValueError(f"native=True: prompt + max_new_tokens = {req['T'] + req['max_new']} exceeds the fused model's "
                                          f"context ({dec.config.block_size})")
                     dec = None  # (automatic route: transformers' generate decides what a request beyond the context means)
+                from ._lib import SAMPLER_MAX_VOCAB
+                if dec is not None and dec.config.vocab_size > SAMPLER_MAX_VOCAB:
+                    # (the captured step ends in the fused sampler: 128 blocks x 1024 logits.  Qwen3's published vocabulary, 151936, is
+                    # beyond it -- such a checkpoint keeps `native_decoder()` / `decode_native` / `prefill_native`, not this route)
+                    if native is True:
+                        raise ValueError(f"native=True: vocabulary {dec.config.vocab_size} exceeds the fused sampler's {SAMPLER_MAX_VOCAB}")
+                    dec = None
                 if dec is not None:
                     return self._generate_native(dec, req)
                 if native is True:
-                    raise ValueError("native=True: this checkpoint has no fused decode form at %d bits" % self.precision)
+                    why_not = getattr(self, "_no_native_reason", None)
+                    raise ValueError("native=True: this checkpoint has no fused decode form at %d bits%s" % (self.precision, ": " + why_not if why_not else ""))
             if capture is True:
                 if req is None:
                     raise ValueError("capture=True: " + why)
@@ -402,8 +416,10 @@ class AnyPrecisionForCausalLM(nn.Module):
     def _native_decoder_or_none(self, bitwidth, release_planes=False):
         try:
             dec = self.native_decoder(bitwidth, release_planes=release_planes)
-        except (ValueError, NotImplementedError):  # "this checkpoint / precision has no fused form"; anything else is a real error
+        except (ValueError, NotImplementedError) as e:  # "this checkpoint / precision has no fused form"; anything else is a real error
+            self._no_native_reason = str(e)
             return None
+        self._no_native_reason = None
         dec.setup_caches(1, 8) if not dec.cache_initialized else None
         return dec if dec.native_ready() else None
 
@@ -634,6 +650,9 @@ class AnyPrecisionForCausalLM(nn.Module):
                     raise NotImplementedError("fused decode model: biased linears")
                 blk.input_layernorm.weight = hf_layer.input_layernorm.weight
                 blk.post_attention_layernorm.weight = hf_layer.post_attention_layernorm.weight
+                if args.qk_norm:  # (Qwen3: the per-head norms by reference, like the layer norms)
+                    blk.attention.q_norm.weight = hf_layer.self_attn.q_norm.weight
+                    blk.attention.k_norm.weight = hf_layer.self_attn.k_norm.weight
                 lut = lambda m: m._buffers[f"lut{bitwidth}"].to(torch.float16)  # noqa: E731
                 put(blk.attention.wo, L["o"].qweight[:bitwidth], lut(L["o"]))           # (a prefix of the planes: contiguous view)
                 put(blk.feed_forward.w2, L["down"].qweight[:bitwidth], lut(L["down"]))

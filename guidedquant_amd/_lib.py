@@ -25,9 +25,11 @@ EXPORTS = [
     "gq_sample_topk_ex", "gq_anyprec_gemv_fused_ho", "gq_ssq_rows", "gq_anyprec_handover_plan", "gq_embed_lookup_ho", "gq_anyprec_gemv_qkv_rope_ho",
     "gq_anyprec_qkv_rope_attn_supported", "gq_anyprec_gemv_qkv_rope_attn", "gq_hop_is_finegrained", "gq_sample_topk_p",
     "gq_qtip_decompress", "gq_qtip_gemm", "gq_qtip_gemm_ws", "gq_qtip_gemm_ws_bytes", "gq_debug_ap_last_route", "gq_debug_ap_plan_route",
+    "gq_attn_decode_split_qknorm", "gq_qknorm_rope_cache_rows",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
+SAMPLER_MAX_VOCAB = 131072  # gq_sample_topk / _ex / _p: 128 blocks x 1024 logits (csrc/decode.hip)
 # include/gq_hip.h GQ_AP_ROUTE_*: the kernel family an AP-GEMV dispatch launched (gq_debug_ap_last_route, gq_debug_ap_plan_route)
 AP_ROUTES = ("none", "generic", "exact", "pair-table", "plane", "plane-local", "plane-chain", "stream", "stream-ksplit", "dq",
              "stream-qkv-rope", "wide")
@@ -109,6 +111,7 @@ def lib():
         L.gq_embed_lookup.argtypes = [vp, vp, vp, u32, u32, vp]
         L.gq_attn_decode.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, vp]
         L.gq_attn_decode_split.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, vp]
+        L.gq_attn_decode_split_qknorm.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, vp, vp, f32, vp]
         L.gq_attn_decode_qtip.argtypes = [ctypes.POINTER(GqQtipOut), vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, vp]
         L.gq_dense_gemv_f16.argtypes = [vp, vp, vp, u32, u32, vp, f32, vp]
         L.gq_sample_topk.argtypes = [vp, u32, i32, f32, u32, vp, vp, vp, vp, vp, vp, vp]
@@ -125,6 +128,7 @@ def lib():
         L.gq_qtip_gemm_ws_bytes.argtypes = [u32, u32, u32, i32]
         L.gq_rmsnorm_rows.argtypes = [vp, vp, vp, vp, u32, u32, f32, vp]
         L.gq_rope_cache_rows.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp]
+        L.gq_qknorm_rope_cache_rows.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, f32, vp]
         L.gq_silu_mul_rows.argtypes = [vp, vp, u32, u32, i32, vp]
         L.gq_anyprec_pack.argtypes = [vp, vp, u32, u32, i32, vp]
         L.gq_lnq_cd_block.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, vp]

@@ -6,6 +6,8 @@ decode harness loads.  State-dict transformations only (host code).
     down_proj->w2, lm_head->output), keep only `lut{bitwidth}` as `lut`, cast bf16 / LUTs to fp16, keep the first
     `bitwidth` bit-planes of every qweight (any-precision prefix property), then fuse q/k/v -> wqkv and gate/up -> w1w3
     by concatenating qweight along dim 1 (rows) and lut along dim 0.
+    Every other tensor keeps its renamed key: a Qwen3 checkpoint's `self_attn.{q,k}_norm.weight` arrive as
+    `layers.{i}.attention.{q,k}_norm.weight`, the keys of `Attention.q_norm` / `k_norm`.
     Generalised: the reference only accepts "Llama-2-*" directory names (:62-69); here the layer count is an argument or
     inferred from the keys, so Llama-3 checkpoints convert too.
   * `convert_qtip_no_fuse(state_dict)`  ==  inference/qtip_convert_no_fuse.py:9-46: key renames only (wq/wk/wv/wo,

@@ -97,10 +97,24 @@ struct AttnQt {
     u32 M[3], parts[3];
     float mscale[3];                // (float)M^-1/2
 };
-template <int HD, bool QT>
+// QKN (Qwen3: modeling_qwen3.Qwen3Attention.forward, q_norm / k_norm = Qwen3RMSNorm over head_dim in front of the rotation): the block
+// normalises its q head and its KV group's k head before it rotates them -- sum of squares of the HD fp16 values in fp32 (one wave at
+// HD = 64, two waves added in wave order at HD = 128), x * rsqrt(ssq / HD + eps) rounded to fp16, then the fp16 product with the
+// weight: Qwen3RMSNorm's rounding points (= RMSNorm.forward of model.py).  v is untouched.  Every split block normalises q; the
+// block that owns the current position writes the normalised, rotated k.  A compile-time form: the QKN = false instances take
+// an empty argument behind the old ones and keep the instructions they had.
+template <bool QKN>
+struct AttnQkNorm {};  // (nothing to pass: the instances without the norm keep their arguments)
+template <>
+struct AttnQkNorm<true> {
+    const uint16_t *qw, *kw;  // q_norm / k_norm weights, fp16 [HD]
+    float eps;
+};
+template <int HD, bool QT, bool QKN = false>
 __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint16_t *qkv, const int *pos_ptr, const uint16_t *cos_t,
                                                           const uint16_t *sin_t, uint16_t *kc, uint16_t *vc, uint16_t *out,
-                                                          u32 H, u32 Hkv, u32 max_seq, float scale, u32 nsplit, float *ws, AttnQt qt) {
+                                                          u32 H, u32 Hkv, u32 max_seq, float scale, u32 nsplit, float *ws, AttnQt qt,
+                                                          AttnQkNorm<QKN> nm) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr u32 NW = ATTN_WAVES;
     float *sc = reinterpret_cast<float *>(smem);  // [2 * NW * 64 / (HD / 8)] running max / sum of the position streams
@@ -213,6 +227,27 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
     const u32 per = nsplit > 1u ? (((pos + nsplit) / nsplit + PASS - 1u) / PASS) * PASS : pos + 1u;
     const u32 p0 = sp * per, p1 = min(pos + 1u, p0 + per);  // (p0 >= p1: nothing to do, a neutral partial result is written)
     const bool has_cur = p0 <= pos && pos < p1;             // the split that covers the current token
+    if constexpr (QKN) {
+        // per-head statistics: thread d < HD holds element d of q and of k (the other waves add zeros); fixed order
+        const float qf = h2f(qd_b), kf = h2f(kd_b);  // (0 for tid >= HD)
+        float sq = wave_reduce<false>(qf * qf), sk = wave_reduce<false>(kf * kf);
+        if constexpr (HD > 64) {
+            if (l == 0u && w < (u32)(HD / 64)) red[w] = sq, red[HD / 64 + w] = sk;
+            __syncthreads();  // (block-uniform: behind the position checks above)
+            sq = 0.f, sk = 0.f;
+#pragma unroll
+            for (int i = 0; i < HD / 64; i++) sq += red[i], sk += red[HD / 64 + i];
+        }
+        const float rq = rsqrtf(sq / (float)HD + nm.eps), rk = rsqrtf(sk / (float)HD + nm.eps);
+        if (tid < HD) {
+            const u32 d = tid, dr = d < HD / 2 ? d + HD / 2 : d - HD / 2;
+            // (x.float() * rsqrt(..)).half() * weight -- for the element and for its rotation partner
+            qd_b = h2u((h16)(qf * rq) * u2h(nm.qw[d]));
+            kd_b = h2u((h16)(kf * rk) * u2h(nm.kw[d]));
+            qr_b = h2u((h16)(h2f(qr_b) * rq) * u2h(nm.qw[dr]));
+            kr_b = h2u((h16)(h2f(kr_b) * rk) * u2h(nm.kw[dr]));
+        }
+    }
     if (tid < HD) {
         const u32 d = tid;
         const h16 c = u2h(cos_t[(size_t)pos * HD + d]), s = u2h(sin_t[(size_t)pos * HD + d]);
@@ -961,11 +996,13 @@ extern "C" int gq_embed_lookup_ho(const int *token, const void *table, void *out
 }
 
 namespace {
-template <bool QT>
+template <bool QT, bool QKN = false>
 int attn_launch(const void *qkv, const AttnQt &qt, const int *pos, const void *cos_table, const void *sin_table, void *k_cache, void *v_cache,
                 void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split,
-                float *workspace, void *stream) {
+                float *workspace, void *stream, const void *q_norm_weight = nullptr, const void *k_norm_weight = nullptr, float eps = 0.f) {
+    static_assert(!(QT && QKN), "the QK-norm form reads fp16 q / k / v");
     if ((!QT && !qkv) || !pos || !cos_table || !sin_table || !k_cache || !v_cache || !out) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    if (QKN && (!q_norm_weight || !k_norm_weight)) return gq_fail(GQ_EINVAL, "null pointer argument.");
     if (n_kv_head == 0 || n_head % n_kv_head) return gq_fail(GQ_EINVAL, "n_head must be a multiple of n_kv_head.");
     if (head_dim != 64 && head_dim != 128) return gq_fail(GQ_ENOTSUP, "head_dim must be 64 or 128.");
     if (n_split < 1u || n_split > 64u || (n_split > 1u && !workspace)) return gq_fail(GQ_EINVAL, "n_split in 1..64, with a workspace when > 1.");
@@ -974,21 +1011,21 @@ int attn_launch(const void *qkv, const AttnQt &qt, const int *pos, const void *c
     if (QT) smem += 3u * (size_t)head_dim * 4u + 3u * head_dim * 2u + 3u * (size_t)(64u * ATTN_WAVES / (head_dim / 4u)) * head_dim * 4u;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(n_head, n_split);
-    if (head_dim == 128) {
-        static GqPerDeviceOnce once;
-        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_decode_kernel<128, QT>), 160 * 1024));
-        hipLaunchKernelGGL((attn_decode_kernel<128, QT>), grid, dim3(64 * ATTN_WAVES), smem, s, (const uint16_t *)qkv, pos,
-                           (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)k_cache, (uint16_t *)v_cache,
-                           (uint16_t *)out, n_head, n_kv_head, max_seq, scale, n_split, workspace, qt);
-        if (n_split > 1u) hipLaunchKernelGGL(attn_combine_kernel<128>, dim3(n_head), dim3(128), 0, s, workspace, (uint16_t *)out, n_split, pos, max_seq);
-    } else {
-        static GqPerDeviceOnce once;
-        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_decode_kernel<64, QT>), 160 * 1024));
-        hipLaunchKernelGGL((attn_decode_kernel<64, QT>), grid, dim3(64 * ATTN_WAVES), smem, s, (const uint16_t *)qkv, pos,
-                           (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)k_cache, (uint16_t *)v_cache,
-                           (uint16_t *)out, n_head, n_kv_head, max_seq, scale, n_split, workspace, qt);
-        if (n_split > 1u) hipLaunchKernelGGL(attn_combine_kernel<64>, dim3(n_head), dim3(64), 0, s, workspace, (uint16_t *)out, n_split, pos, max_seq);
-    }
+#define GQ_LAUNCH_ATTN(HD_)                                                                                                                   \
+    do {                                                                                                                                      \
+        static GqPerDeviceOnce once;                                                                                                          \
+        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_decode_kernel<HD_, QT, QKN>), 160 * 1024));                     \
+        hipLaunchKernelGGL((attn_decode_kernel<HD_, QT, QKN>), grid, dim3(64 * ATTN_WAVES), smem, s, (const uint16_t *)qkv, pos,              \
+                           (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)k_cache, (uint16_t *)v_cache,                \
+                           (uint16_t *)out, n_head, n_kv_head, max_seq, scale, n_split, workspace, qt, nm);                                   \
+        if (n_split > 1u)                                                                                                                     \
+            hipLaunchKernelGGL(attn_combine_kernel<HD_>, dim3(n_head), dim3(HD_), 0, s, workspace, (uint16_t *)out, n_split, pos, max_seq);   \
+    } while (0)
+    AttnQkNorm<QKN> nm{};
+    if constexpr (QKN) nm = AttnQkNorm<true>{(const uint16_t *)q_norm_weight, (const uint16_t *)k_norm_weight, eps};
+    if (head_dim == 128) GQ_LAUNCH_ATTN(128);
+    else GQ_LAUNCH_ATTN(64);
+#undef GQ_LAUNCH_ATTN
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
 }
@@ -999,6 +1036,16 @@ extern "C" int gq_attn_decode_split(const void *qkv, const int *pos, const void 
                                     float scale, uint32_t n_split, float *workspace, void *stream) {
     return attn_launch<false>(qkv, AttnQt{}, pos, cos_table, sin_table, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split,
                               workspace, stream);
+}
+
+// Qwen3 layers: gq_attn_decode_split with the per-head RMSNorm of q and k (weights fp16 [head_dim], shared by all heads) in front of
+// the rotation, inside the same launch
+extern "C" int gq_attn_decode_split_qknorm(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,
+                                           void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                                           float scale, uint32_t n_split, float *workspace, const void *q_norm_weight,
+                                           const void *k_norm_weight, float eps, void *stream) {
+    return attn_launch<false, true>(qkv, AttnQt{}, pos, cos_table, sin_table, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale,
+                                    n_split, workspace, stream, q_norm_weight, k_norm_weight, eps);
 }
 
 // QTIP models: the same attention with the transform-out of the q, k and v linears folded in (qkv_lin[0..2]: the GqQtipOut

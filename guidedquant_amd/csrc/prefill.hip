@@ -85,6 +85,31 @@ __global__ void __launch_bounds__(256) rmsnorm_rows_kernel(uint16_t *__restrict_
     }
 }
 
+// apply_rotary_pos_emb on one thread's unit: a = elements d .. d + 7, b = elements d + HD / 2 .. of a head, at cache position p
+__device__ __forceinline__ void rope_unit(const uint4 a, const uint4 b, const uint16_t *__restrict__ cos_t, const uint16_t *__restrict__ sin_t, u32 p,
+                                          u32 max_seq, u32 HD, u32 d, u32 (&o1)[4], u32 (&o2)[4]) {
+    const uint16_t *cr = cos_t + (size_t)min(p, max_seq - 1u) * HD, *sr = sin_t + (size_t)min(p, max_seq - 1u) * HD;
+    const uint4 c1 = *reinterpret_cast<const uint4 *>(cr + d), c2 = *reinterpret_cast<const uint4 *>(cr + d + HD / 2u);
+    const uint4 s1 = *reinterpret_cast<const uint4 *>(sr + d), s2 = *reinterpret_cast<const uint4 *>(sr + d + HD / 2u);
+    const u32 x1[4] = {a.x, a.y, a.z, a.w}, x2[4] = {b.x, b.y, b.z, b.w};
+    const u32 cc1[4] = {c1.x, c1.y, c1.z, c1.w}, cc2[4] = {c2.x, c2.y, c2.z, c2.w}, ss1[4] = {s1.x, s1.y, s1.z, s1.w}, ss2[4] = {s2.x, s2.y, s2.z, s2.w};
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        u32 r1 = 0, r2 = 0;
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            const u32 sh = 16u * (u32)k;
+            const h16 a1 = hbits((uint16_t)(x1[e] >> sh)), a2 = hbits((uint16_t)(x2[e] >> sh));
+            // first half:  x1 * cos + (-x2) * sin ;  second half:  x2 * cos + x1 * sin   (rotate_half = cat(-x2, x1))
+            const h16 f = (a1 * hbits((uint16_t)(cc1[e] >> sh))) + ((-a2) * hbits((uint16_t)(ss1[e] >> sh)));
+            const h16 g = (a2 * hbits((uint16_t)(cc2[e] >> sh))) + (a1 * hbits((uint16_t)(ss2[e] >> sh)));
+            r1 |= (u32)bitsh(f) << sh;
+            r2 |= (u32)bitsh(g) << sh;
+        }
+        o1[e] = r1, o2[e] = r2;
+    }
+}
+
 // qkv [S][(H + 2 Hkv) HD] -> q_out [H][S][HD] (rotated), k_cache / v_cache [Hkv][max_seq][HD] at pos[s] (k rotated).
 // One thread per (token, head of q | k | v, 8 elements of the FIRST half): it owns elements d .. d + 7 and d + HD / 2 ..
 __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__restrict__ qkv, const int *__restrict__ pos,
@@ -105,27 +130,85 @@ __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__
             }
             continue;
         }
-        const uint16_t *cr = cos_t + (size_t)min(p, max_seq - 1u) * HD, *sr = sin_t + (size_t)min(p, max_seq - 1u) * HD;
-        const uint4 c1 = *reinterpret_cast<const uint4 *>(cr + d), c2 = *reinterpret_cast<const uint4 *>(cr + d + HD / 2u);
-        const uint4 s1 = *reinterpret_cast<const uint4 *>(sr + d), s2 = *reinterpret_cast<const uint4 *>(sr + d + HD / 2u);
-        const u32 x1[4] = {a.x, a.y, a.z, a.w}, x2[4] = {b.x, b.y, b.z, b.w};
-        const u32 cc1[4] = {c1.x, c1.y, c1.z, c1.w}, cc2[4] = {c2.x, c2.y, c2.z, c2.w}, ss1[4] = {s1.x, s1.y, s1.z, s1.w}, ss2[4] = {s2.x, s2.y, s2.z, s2.w};
         u32 o1[4], o2[4];
+        rope_unit(a, b, cos_t, sin_t, p, max_seq, HD, d, o1, o2);
+        uint16_t *dst;
+        if (hh < H) {
+            dst = q_out + ((size_t)hh * S + s) * HD;
+        } else {
+            if (p >= max_seq) continue;
+            dst = kc + ((size_t)(hh - H) * max_seq + p) * HD;
+        }
+        *reinterpret_cast<uint4 *>(dst + d) = make_uint4(o1[0], o1[1], o1[2], o1[3]);
+        *reinterpret_cast<uint4 *>(dst + d + HD / 2u) = make_uint4(o2[0], o2[1], o2[2], o2[3]);
+    }
+}
+
+// The same with Qwen3's per-head RMSNorm of q and k in front of the rotation (modeling_qwen3.Qwen3Attention.forward: q_norm / k_norm =
+// Qwen3RMSNorm over head_dim, weights [HD] shared by the heads): the HD / 16 threads of a (token, head) are neighbouring lanes of one
+// wave; each adds the squares of its 16 values in fp32, an xor butterfly over the group gives every lane the same sum, then
+// (x.float() * rsqrt(ssq / HD + eps)).half() * weight -- the rounding points of gq_rmsnorm_rows -- and the rotation above.  v is copied.
+// The loop bound is block-uniform (whole groups are active or idle together: total is a multiple of HD / 16 <= 8).
+__global__ void __launch_bounds__(256) qknorm_rope_cache_rows_kernel(const uint16_t *__restrict__ qkv, const int *__restrict__ pos,
+                                                                     const uint16_t *__restrict__ cos_t, const uint16_t *__restrict__ sin_t,
+                                                                     uint16_t *__restrict__ q_out, uint16_t *__restrict__ kc, uint16_t *__restrict__ vc,
+                                                                     const uint16_t *__restrict__ qnw, const uint16_t *__restrict__ knw, float eps,
+                                                                     u32 S, u32 H, u32 Hkv, u32 HD, u32 max_seq) {
+    const u32 upr = HD / 16u, heads = H + 2u * Hkv, total = S * heads * upr;
+    for (u32 base = blockIdx.x * 256u; base < total; base += gridDim.x * 256u) {
+        const u32 i = base + threadIdx.x;
+        const bool active = i < total;
+        const u32 ic = active ? i : 0u;
+        const u32 u = ic % upr, hh = (ic / upr) % heads, s = ic / (upr * heads), d = 8u * u;
+        const u32 p = (u32)pos[s];
+        const uint16_t *src = qkv + (size_t)s * heads * HD + (size_t)hh * HD;
+        uint4 a = *reinterpret_cast<const uint4 *>(src + d), b = *reinterpret_cast<const uint4 *>(src + d + HD / 2u);
+        const u32 x1[4] = {a.x, a.y, a.z, a.w}, x2[4] = {b.x, b.y, b.z, b.w};
+        float ss = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const float f0 = h2f((uint16_t)(x1[e] & 0xFFFF)), f1 = h2f((uint16_t)(x1[e] >> 16));
+            ss += f0 * f0;
+            ss += f1 * f1;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const float f0 = h2f((uint16_t)(x2[e] & 0xFFFF)), f1 = h2f((uint16_t)(x2[e] >> 16));
+            ss += f0 * f0;
+            ss += f1 * f1;
+        }
+        for (u32 sh = 1u; sh < upr; sh <<= 1) ss += __shfl_xor(ss, (int)sh, 64);  // (upr is wave-uniform: 4 or 8 lanes, aligned)
+        if (!active) continue;
+        if (hh >= H + Hkv) {  // v: copied
+            if (p < max_seq) {
+                uint16_t *dst = vc + ((size_t)(hh - H - Hkv) * max_seq + p) * HD;
+                *reinterpret_cast<uint4 *>(dst + d) = a;
+                *reinterpret_cast<uint4 *>(dst + d + HD / 2u) = b;
+            }
+            continue;
+        }
+        const float rs = rsqrtf(ss / (float)HD + eps);
+        const uint16_t *wn = hh < H ? qnw : knw;
+        const uint4 w1 = *reinterpret_cast<const uint4 *>(wn + d), w2 = *reinterpret_cast<const uint4 *>(wn + d + HD / 2u);
+        const u32 ww1[4] = {w1.x, w1.y, w1.z, w1.w}, ww2[4] = {w2.x, w2.y, w2.z, w2.w};
+        u32 n1[4], n2[4];
 #pragma unroll
         for (int e = 0; e < 4; e++) {
             u32 r1 = 0, r2 = 0;
 #pragma unroll
             for (int k = 0; k < 2; k++) {
                 const u32 sh = 16u * (u32)k;
-                const h16 a1 = hbits((uint16_t)(x1[e] >> sh)), a2 = hbits((uint16_t)(x2[e] >> sh));
-                // first half:  x1 * cos + (-x2) * sin ;  second half:  x2 * cos + x1 * sin   (rotate_half = cat(-x2, x1))
-                const h16 f = (a1 * hbits((uint16_t)(cc1[e] >> sh))) + ((-a2) * hbits((uint16_t)(ss1[e] >> sh)));
-                const h16 g = (a2 * hbits((uint16_t)(cc2[e] >> sh))) + (a1 * hbits((uint16_t)(ss2[e] >> sh)));
-                r1 |= (u32)bitsh(f) << sh;
-                r2 |= (u32)bitsh(g) << sh;
+                const h16 v1 = (h16)(h2f((uint16_t)(x1[e] >> sh)) * rs) * hbits((uint16_t)(ww1[e] >> sh));
+                const h16 v2 = (h16)(h2f((uint16_t)(x2[e] >> sh)) * rs) * hbits((uint16_t)(ww2[e] >> sh));
+                r1 |= (u32)bitsh(v1) << sh;
+                r2 |= (u32)bitsh(v2) << sh;
             }
-            o1[e] = r1, o2[e] = r2;
+            n1[e] = r1, n2[e] = r2;
         }
+        a = make_uint4(n1[0], n1[1], n1[2], n1[3]);
+        b = make_uint4(n2[0], n2[1], n2[2], n2[3]);
+        u32 o1[4], o2[4];
+        rope_unit(a, b, cos_t, sin_t, p, max_seq, HD, d, o1, o2);
         uint16_t *dst;
         if (hh < H) {
             dst = q_out + ((size_t)hh * S + s) * HD;
@@ -200,6 +283,28 @@ extern "C" int gq_rope_cache_rows(const void *qkv, const int *pos, const void *c
     hipLaunchKernelGGL(rope_cache_rows_kernel, dim3(blocks > 65535u ? 65535u : blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)qkv, pos,
                        (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)q_out, (uint16_t *)k_cache, (uint16_t *)v_cache, S, n_head,
                        n_kv_head, head_dim, max_seq);
+    GQ_HIP_CHECK(hipGetLastError());
+    return GQ_OK;
+}
+
+extern "C" int gq_qknorm_rope_cache_rows(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
+                                         void *v_cache, uint32_t S, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                                         const void *q_norm_weight, const void *k_norm_weight, float eps, void *stream) {
+    if (!qkv || !pos || !cos_table || !sin_table || !q_out || !k_cache || !v_cache || !q_norm_weight || !k_norm_weight)
+        return gq_fail(GQ_EINVAL, "null pointer argument.");
+    if (S == 0) return GQ_OK;
+    // (the statistic of a head is added inside an aligned group of head_dim / 16 lanes: a power of two, within one wave)
+    if ((head_dim != 64u && head_dim != 128u) || n_head == 0 || n_kv_head == 0 || max_seq == 0)
+        return gq_fail(GQ_ENOTSUP, "gq_qknorm_rope_cache_rows: head_dim must be 64 or 128.");
+    if (((uintptr_t)qkv | (uintptr_t)cos_table | (uintptr_t)sin_table | (uintptr_t)q_out | (uintptr_t)k_cache | (uintptr_t)v_cache |
+         (uintptr_t)q_norm_weight | (uintptr_t)k_norm_weight) & 15u)
+        return gq_fail(GQ_EINVAL, "gq_qknorm_rope_cache_rows: 16-byte aligned pointers.");
+    const uint64_t total = (uint64_t)S * (n_head + 2u * n_kv_head) * (head_dim / 16u);
+    if (total >= 0x7FFFFFFFull) return gq_fail(GQ_ENOTSUP, "gq_qknorm_rope_cache_rows: problem too large.");
+    const u32 blocks = (u32)((total + 255u) / 256u);
+    hipLaunchKernelGGL(qknorm_rope_cache_rows_kernel, dim3(blocks > 65535u ? 65535u : blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)qkv, pos,
+                       (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)q_out, (uint16_t *)k_cache, (uint16_t *)v_cache,
+                       (const uint16_t *)q_norm_weight, (const uint16_t *)k_norm_weight, eps, S, n_head, n_kv_head, head_dim, max_seq);
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
 }

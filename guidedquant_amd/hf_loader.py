@@ -1,5 +1,5 @@
 """Loader for HF-layout GuidedQuant / Any-Precision checkpoints: a directory with
-`config.json` (a Llama config plus the `anyprec` section, any_precision/modules/AnyPrecisionForCausalLM.py:43-47) and the
+`config.json` (a Llama, Mistral or Qwen3 config plus the `anyprec` section, any_precision/modules/AnyPrecisionForCausalLM.py:43-47) and the
 weights as `pytorch_model.bin` or (sharded) safetensors with the HF keys `model.layers.{i}.self_attn.q_proj.{qweight,lut{b}}`
 (any_precision/quantization/pack.py:112-123) -> the fused gpt-fast `Transformer` of this package, ready for the HIP
 decode path.  Equivalent to running inference/sqllm_llama_convert_fuse.py and then inference/generate.py::load_model,
@@ -16,17 +16,52 @@ from .convert import convert_anyprec_fuse
 from .model import ModelArgs, Transformer
 
 
+def _no_sliding_window(cfg: dict, what: str):
+    """the fused route attends over the whole cache: a checkpoint whose layers use a sliding window shorter than its context is declined"""
+    lt = cfg.get("layer_types")
+    if lt and any(t != "full_attention" for t in lt):
+        raise NotImplementedError(f"{what}: layer_types {sorted(set(lt))} (only full_attention layers have a fused decode form)")
+    if what == "qwen3" and cfg.get("use_sliding_window"):
+        raise NotImplementedError("qwen3: use_sliding_window (sliding-window attention has no fused decode form)")
+    sw = cfg.get("sliding_window")
+    if what == "mistral" and sw is not None and int(sw) < int(cfg.get("max_position_embeddings", 8192)):
+        raise NotImplementedError(f"mistral: sliding_window {sw} < max_position_embeddings (sliding-window attention has no fused decode form)")
+
+
 def model_args_from_hf_config(cfg: dict) -> ModelArgs:
-    """Llama `config.json` -> ModelArgs (inference/model.py:27-51 field meanings)."""
-    name = os.path.basename(str(cfg.get("_name_or_path") or cfg.get("model_type", "llama")).rstrip("/")) or "llama"
-    if "llama" not in name.lower():  # (the block layout is Llama's whatever the checkpoint directory is called)
-        name = "llama-" + name
+    """HF `config.json` -> ModelArgs (inference/model.py:27-51 field meanings), by `model_type`:
+      llama (or no model_type)  the Llama block;
+      mistral                   the same block, head_dim from the config when it has one; only without a sliding window that bites;
+      qwen3                     head_dim of its own and the per-head q / k RMSNorm (qk_norm); dense full-attention layers only.
+    Anything else (gemma3*, phi*, opt, qwen2 with its biased linears, MoE models, ..) raises NotImplementedError: the fused decode
+    model knows these block layouts and no other, and a layout it does not know must not be decoded as if it were Llama's."""
+    mt = str(cfg.get("model_type") or "llama").lower()
+    if mt not in ("llama", "mistral", "qwen3"):
+        raise NotImplementedError(f"model_type {mt!r} has no fused decode form (llama, mistral without a sliding window, qwen3 dense have)")
+    name = os.path.basename(str(cfg.get("_name_or_path") or mt).rstrip("/")) or mt
+    if mt not in name.lower():  # (the block layout is the model type's whatever the checkpoint directory is called)
+        name = mt + "-" + name
+    extra = {}
+    if mt != "llama":
+        _no_sliding_window(cfg, mt)
+        if cfg.get("head_dim"):
+            extra["head_dim"] = int(cfg["head_dim"])
+    if mt == "qwen3":
+        if cfg.get("attention_bias"):
+            raise NotImplementedError("qwen3: attention_bias (biased linears have no fused decode form)")
+        extra["qk_norm"] = True
+    rope_theta, rope_scaling = cfg.get("rope_theta"), cfg.get("rope_scaling")
+    rp = cfg.get("rope_parameters")  # (newer transformers keep base and scaling together)
+    if isinstance(rp, dict):
+        rope_theta = rp.get("rope_theta", rope_theta) if rope_theta is None else rope_theta
+        if rope_scaling is None and rp.get("rope_type", "default") != "default":
+            rope_scaling = {k: v for k, v in rp.items() if k != "rope_theta"}
     return ModelArgs(block_size=int(cfg.get("max_position_embeddings", 8192)), vocab_size=int(cfg["vocab_size"]),
                      n_layer=int(cfg["num_hidden_layers"]), n_head=int(cfg["num_attention_heads"]), dim=int(cfg["hidden_size"]),
                      intermediate_size=int(cfg["intermediate_size"]),
-                     n_local_heads=int(cfg.get("num_key_value_heads", cfg["num_attention_heads"])),
-                     rope_base=float(cfg.get("rope_theta", 10000.0)), norm_eps=float(cfg.get("rms_norm_eps", 1e-5)),
-                     rope_scaling=cfg.get("rope_scaling"), model_name=os.path.basename(str(name)))
+                     n_local_heads=int(cfg.get("num_key_value_heads") or cfg["num_attention_heads"]),
+                     rope_base=float(10000.0 if rope_theta is None else rope_theta), norm_eps=float(cfg.get("rms_norm_eps", 1e-5)),
+                     rope_scaling=rope_scaling, model_name=os.path.basename(str(name)), **extra)
 
 
 def read_hf_state_dict(path: str) -> dict:

@@ -16,6 +16,10 @@ Two execution paths:
     an embedding lookup and a fused final-norm + lm_head GEMV: no allocation, no host sync, token / position read
     from device memory, so the whole step is hipGraph-capturable (generate.py).
 
+Block layouts: Llama's, and with `ModelArgs.head_dim` / `qk_norm` Mistral's and Qwen3's (RMSNorm over head_dim on every q and k head in
+front of the rotation, modeling_qwen3.Qwen3Attention.forward): in `Attention.forward` for the module path, inside the attention launch
+(gq_attn_decode_split_qknorm) and the prompt pass's RoPE launch (gq_qknorm_rope_cache_rows) for the HIP path.
+
 Model table: the reference's entries (model.py:53-61) plus Llama-3.2-1B-Instruct and Llama-3.3-70B-Instruct, which
 BASELINE.json's configs name and the reference table lacks.
 """
@@ -48,11 +52,12 @@ class ModelArgs:
     dim: int = 4096
     intermediate_size: int = None
     n_local_heads: int = -1
-    head_dim: int = 64
+    head_dim: Optional[int] = None  # None: dim // n_head (Llama); Qwen3 / Mistral configs carry their own
     rope_base: float = 10000
     norm_eps: float = 1e-5
     rope_scaling: Optional[dict] = None
     model_name: Optional[str] = None
+    qk_norm: bool = False  # Qwen3: RMSNorm over head_dim on every q and k head in front of the rotation
 
     def __post_init__(self):
         if self.n_local_heads == -1:
@@ -61,7 +66,9 @@ class ModelArgs:
             hidden_dim = 4 * self.dim
             n_hidden = int(2 * hidden_dim / 3)
             self.intermediate_size = find_multiple(n_hidden, 256)
-        self.head_dim = self.dim // self.n_head
+        if self.head_dim is None:
+            assert self.dim % self.n_head == 0
+            self.head_dim = self.dim // self.n_head
 
     @classmethod
     def from_name(cls, name: str):
@@ -83,6 +90,11 @@ transformer_configs = {
                                              rope_scaling=dict(rope_type="llama3", factor=32.0, low_freq_factor=1.0, high_freq_factor=4.0, original_max_position_embeddings=8192)),
     "meta-llama/Llama-3.3-70B-Instruct": dict(model_name="Llama-3.3-70B-Instruct", block_size=8192, n_layer=80, n_head=64, n_local_heads=8, dim=8192, intermediate_size=28672, vocab_size=128256, rope_base=500000,
                                               rope_scaling=dict(rope_type="llama3", factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0, original_max_position_embeddings=8192)),
+    # Qwen3 dense (QK-norm, head_dim of its own).  The figures restate the public config from memory and could not be checked
+    # offline: they serve as a shape set for --random_init runs and timing (tools/qwen3_decode_timing.py), not as a loader's truth --
+    # a checkpoint's own config.json goes through hf_loader.model_args_from_hf_config.
+    "Qwen/Qwen3-8B": dict(model_name="Qwen3-8B", block_size=8192, n_layer=36, n_head=32, n_local_heads=8, dim=4096, head_dim=128, intermediate_size=12288,
+                          vocab_size=151936, rope_base=1000000, norm_eps=1e-6, qk_norm=True),
 }
 
 
@@ -192,7 +204,6 @@ class Attention(nn.Module):
 
     def __init__(self, config: ModelArgs, linear_class=nn.Linear, linear_kwargs=None, fuse_linears=True) -> None:
         super().__init__()
-        assert config.dim % config.n_head == 0
         total_head_dim = (config.n_head + 2 * config.n_local_heads) * config.head_dim
         if fuse_linears:
             self.wqkv = linear_class(config.dim, total_head_dim, bias=False, **(linear_kwargs or {}))
@@ -200,7 +211,11 @@ class Attention(nn.Module):
             self.wq = linear_class(config.dim, config.n_head * config.head_dim, bias=False, **(linear_kwargs or {}))
             self.wk = linear_class(config.dim, config.n_local_heads * config.head_dim, bias=False, **(linear_kwargs or {}))
             self.wv = linear_class(config.dim, config.n_local_heads * config.head_dim, bias=False, **(linear_kwargs or {}))
-        self.wo = linear_class(config.dim, config.dim, bias=False, **(linear_kwargs or {}))
+        self.wo = linear_class(config.n_head * config.head_dim, config.dim, bias=False, **(linear_kwargs or {}))
+        if config.qk_norm:  # (modeling_qwen3.Qwen3Attention: Qwen3RMSNorm(head_dim) -- RMSNorm.forward has its rounding points)
+            self.q_norm = RMSNorm(config.head_dim, eps=config.norm_eps)
+            self.k_norm = RMSNorm(config.head_dim, eps=config.norm_eps)
+        self.qk_norm = config.qk_norm
         self.kv_cache = None
         self.n_head = config.n_head
         self.head_dim = config.head_dim
@@ -213,12 +228,14 @@ class Attention(nn.Module):
         bsz, seqlen, _ = x.shape
         kv_size = self.n_local_heads * self.head_dim
         if self.fuse_linears:
-            q, k, v = self.wqkv(x).split([self.dim, kv_size, kv_size], dim=-1)
+            q, k, v = self.wqkv(x).split([self.n_head * self.head_dim, kv_size, kv_size], dim=-1)
         else:
             q, k, v = self.wq(x), self.wk(x), self.wv(x)
         q = q.view(bsz, seqlen, self.n_head, self.head_dim)
         k = k.view(bsz, seqlen, self.n_local_heads, self.head_dim)
         v = v.view(bsz, seqlen, self.n_local_heads, self.head_dim)
+        if self.qk_norm:
+            q, k = self.q_norm(q), self.k_norm(k)
         q, k, v = map(lambda t: t.transpose(1, 2), (q, k, v))
         q, k = apply_rotary_pos_emb(q, k, cos[input_pos].unsqueeze(0), sin[input_pos].unsqueeze(0))
         if self.kv_cache is not None:
@@ -302,7 +319,7 @@ class TransformerBlock(nn.Module):
         super().__init__()
         self.attention = Attention(config, linear_class, linear_kwargs, fuse_linears)
         self.feed_forward = FeedForward(config, linear_class, linear_kwargs, fuse_linears)
-        if "llama" in config.model_name.lower():
+        if any(n in config.model_name.lower() for n in ("llama", "mistral", "qwen3")):  # (one block layout: pre-norm, gated MLP)
             self.input_layernorm = RMSNorm(config.dim, config.norm_eps)
             self.post_attention_layernorm = RMSNorm(config.dim, config.norm_eps)
         else:
@@ -356,7 +373,7 @@ class Transformer(nn.Module):
     def setup_caches(self, max_batch_size, max_seq_length):
         if self.max_seq_length >= max_seq_length and self.max_batch_size >= max_batch_size:
             return
-        head_dim = self.config.dim // self.config.n_head
+        head_dim = self.config.head_dim
         max_seq_length = find_multiple(max_seq_length, 8)
         self.max_seq_length = max_seq_length
         self.max_batch_size = max_batch_size
@@ -395,7 +412,9 @@ class Transformer(nn.Module):
         if kind is not None:
             return kind or None
         kind = ""
-        if self.fuse_linears:
+        if self.config.qk_norm and (self.config.head_dim not in (64, 128) or not self.fuse_linears):
+            pass  # (QK-norm is served by gq_attn_decode_split_qknorm, head_dim 64 / 128, fused Any-Precision models: else the module forward)
+        elif self.fuse_linears:
             if all(isinstance(m, APLinear) and m.bias is None and m.bitwidth <= 8 and m.in_features % 128 == 0
                    for b in self.layers for m in (b.attention.wqkv, b.attention.wo, b.feed_forward.w1w3, b.feed_forward.w2)):
                 kind = "ap"
@@ -425,7 +444,7 @@ class Transformer(nn.Module):
             c = self.config
             f16 = dict(dtype=torch.float16, device=dev)
             self._native = dict(
-                x=torch.zeros(c.dim, **f16), h=torch.zeros(c.dim, **f16), y=torch.zeros(c.dim, **f16),
+                x=torch.zeros(c.dim, **f16), h=torch.zeros(c.dim, **f16), y=torch.zeros(c.n_head * c.head_dim, **f16),
                 qkv=torch.zeros((c.n_head + 2 * c.n_local_heads) * c.head_dim, **f16),
                 ssq=torch.zeros(_lib.SSQ_SLOTS, dtype=torch.float32, device=dev),  # statistics hand-over slots (gq_hip.h GQ_SSQ_SLOTS)
                 # one flag line per query head for the attention heads that run inside the wqkv launch (gq_anyprec_gemv_qkv_rope_attn:
@@ -439,8 +458,9 @@ class Transformer(nn.Module):
             # grouped-query models whose wqkv launch rotates q / k (gq_attn_decode_roped): the four query heads of a KV group share a
             # block, so the splits can be as short as one 128-position pass -- n_kv_head x n_split blocks ~ one per CU
             l0 = self.layers[0].attention
+            # (not for QK-norm models: their wqkv launch never rotates, see native_layers)
             if (S > 1024 and c.n_head % (4 * c.n_local_heads) == 0 and self._native_kind() != "qtip" and os.environ.get("GQ_ATTN_GQA", "1") != "0"
-                    and _lib.lib().gq_anyprec_qkv_rope_supported(l0.wqkv.out_features, c.dim, l0.wqkv.bitwidth, c.head_dim)):
+                    and not c.qk_norm and _lib.lib().gq_anyprec_qkv_rope_supported(l0.wqkv.out_features, c.dim, l0.wqkv.bitwidth, c.head_dim)):
                 ns = max(4, min(32, (S + 127) // 128, 256 // max(1, c.n_head // 4)))
             ns = int(os.environ.get("GQ_ATTN_SPLIT", ns))
             self._native["attn_split"] = ns
@@ -622,7 +642,7 @@ class Transformer(nn.Module):
         prev_down = None
         for b in self.layers:
             at, ff = b.attention, b.feed_forward
-            qkv_outs = [qkv.data_ptr(), qkv.data_ptr() + c.dim * e, qkv.data_ptr() + (c.dim + kv) * e]
+            qkv_outs = [qkv.data_ptr(), qkv.data_ptr() + qw * e, qkv.data_ptr() + (qw + kv) * e]
             can_o = fold and at.wo.K_right == 1 and ff.w1.K_left == 1
             # GQ_QTIP_MLP_MID (default ON): a factor MLP width n = Kf * 64 (Llama-2-7b: 172 * 64) -- the two gq_qtip_transform launches
             # between the matvecs of gate / up and down (output side, then input side with silu * up) become ONE launch that works
@@ -781,7 +801,7 @@ class Transformer(nn.Module):
             return dict(qkv_in=False, w13=False, w2_out=False)
         qkv_in = on and bool(L.gq_anyprec_handover_plan(at.wqkv.out_features, c.dim, at.wqkv.bitwidth, 1, 0) & 1)
         w13_in = on and bool(L.gq_anyprec_handover_plan(2 * c.intermediate_size, c.dim, ff.w1w3.bitwidth, 1, 4) & 1)
-        wo_out = bool(L.gq_anyprec_handover_plan(c.dim, c.dim, at.wo.bitwidth, 0, 1) & 2)
+        wo_out = bool(L.gq_anyprec_handover_plan(c.dim, c.n_head * c.head_dim, at.wo.bitwidth, 0, 1) & 2)
         w2_out = bool(L.gq_anyprec_handover_plan(c.dim, c.intermediate_size, ff.w2.bitwidth, 0, 1) & 2)
         return dict(qkv_in=qkv_in, w13=w13_in and wo_out, w2_out=w2_out)
 
@@ -805,6 +825,7 @@ class Transformer(nn.Module):
         ck = _lib.check
         scale = 1.0 / math.sqrt(c.head_dim)
         kv_stride = c.n_local_heads * self.max_seq_length * c.head_dim * 2  # bytes per batch slot
+        qdim = c.n_head * c.head_dim  # (wo's input width: not dim for a model with a head_dim of its own)
         ssq = b["ssq"].data_ptr()
         x_has_ssq = ssq_ready  # the slots hold the statistics of the current x
         for li, blk in enumerate(self.layers[l0:l1]):
@@ -818,7 +839,18 @@ class Transformer(nn.Module):
             # RoPE + KV-cache write in the epilogue of the wqkv GEMV, attention without them, where the library serves the layer's
             # wqkv that way (fast mode, 2-bit, K <= 4096: csrc/ap_stream.hip); else the two launches of rounds 1-3
             use_ssq = x_has_ssq and ho["qkv_in"]
-            if (b["attn_split"] == 1 and not use_ssq
+            if c.qk_norm:
+                # Qwen3: q and k are normalised per head BEFORE the rotation, so the wqkv launch must not rotate (its RoPE epilogue holds a
+                # head's rows in eight 16-row groups: no per-head statistic there) -- plain wqkv GEMV, then ONE attention launch that
+                # normalises, rotates, writes the cache row and attends
+                ck(L.gq_anyprec_gemv_fused_ho(x.data_ptr(), qkv.data_ptr(), at.wqkv.qweight.data_ptr(), at.wqkv.lut.data_ptr(),
+                                              at.wqkv.out_features, c.dim, at.wqkv.bitwidth, blk.input_layernorm.weight.data_ptr(),
+                                              c.norm_eps, None, 0, None, 0, ssq if use_ssq else None, None, st), "wqkv")
+                ck(L.gq_attn_decode_split_qknorm(qkv.data_ptr(), pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), kc, vc,
+                                                 y.data_ptr(), c.n_head, c.n_local_heads, c.head_dim, self.max_seq_length, scale,
+                                                 b["attn_split"], ws, at.q_norm.weight.data_ptr(), at.k_norm.weight.data_ptr(),
+                                                 at.q_norm.eps, st), "attn+qknorm")
+            elif (b["attn_split"] == 1 and not use_ssq
                     and L.gq_anyprec_qkv_rope_attn_supported(at.wqkv.out_features, c.dim, at.wqkv.bitwidth, c.head_dim, c.n_head, c.n_local_heads)):
                 # round 6: the attention heads as extra blocks of the wqkv launch (they wait on device flags for q / the new cache row):
                 # one launch and one kernel boundary less per layer, outputs bit-identical to the two launches below
@@ -845,7 +877,7 @@ class Transformer(nn.Module):
             x_has_ssq = False
             if pairs:
                 w13 = ssq if ho["w13"] else None
-                ck(L.gq_anyprec_gemv_fused_ho(y.data_ptr(), h.data_ptr(), at.wo.qweight.data_ptr(), at.wo.lut.data_ptr(), c.dim, c.dim,
+                ck(L.gq_anyprec_gemv_fused_ho(y.data_ptr(), h.data_ptr(), at.wo.qweight.data_ptr(), at.wo.lut.data_ptr(), c.dim, qdim,
                                               at.wo.bitwidth, None, 0.0, x.data_ptr(), 1, None, 0, None, w13, st), "wo")
                 ck(L.gq_anyprec_gemv_fused_ho(h.data_ptr(), gu.data_ptr(), ff.w1w3.qweight.data_ptr(), ff.w1w3.lut.data_ptr(), 2 * c.intermediate_size,
                                               c.dim, ff.w1w3.bitwidth, blk.post_attention_layernorm.weight.data_ptr(), c.norm_eps, None, 4,
@@ -856,7 +888,7 @@ class Transformer(nn.Module):
                                               None, w2_ssq, st), "w2")
                 x_has_ssq = w2_ssq is not None
                 continue
-            ck(L.gq_anyprec_gemv_fused(y.data_ptr(), h.data_ptr(), at.wo.qweight.data_ptr(), at.wo.lut.data_ptr(), c.dim, c.dim,
+            ck(L.gq_anyprec_gemv_fused(y.data_ptr(), h.data_ptr(), at.wo.qweight.data_ptr(), at.wo.lut.data_ptr(), c.dim, qdim,
                                        at.wo.bitwidth, None, 0.0, x.data_ptr(), 1, st), "wo")
             ck(L.gq_anyprec_gemv_fused(h.data_ptr(), gu.data_ptr(), ff.w1w3.qweight.data_ptr(), ff.w1w3.lut.data_ptr(),
                                        2 * c.intermediate_size, c.dim, ff.w1w3.bitwidth,
@@ -915,8 +947,14 @@ class Transformer(nn.Module):
                 else:
                     qkv = att.wqkv(xn.view(1, S, D)).view(S, -1)
                 kc, vc = att.kv_cache.k_cache, att.kv_cache.v_cache
-                _lib.check(L.gq_rope_cache_rows(qkv.data_ptr(), input_pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), q.data_ptr(),
-                                                kc.data_ptr(), vc.data_ptr(), S, H, Hkv, hd, kc.shape[2], st), "gq_rope_cache_rows")
+                if cfg.qk_norm:  # (Qwen3: the per-head RMSNorm of q and k in front of the rotation, same launch)
+                    _lib.check(L.gq_qknorm_rope_cache_rows(qkv.data_ptr(), input_pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(),
+                                                           q.data_ptr(), kc.data_ptr(), vc.data_ptr(), S, H, Hkv, hd, kc.shape[2],
+                                                           att.q_norm.weight.data_ptr(), att.k_norm.weight.data_ptr(), att.q_norm.eps, st),
+                               "gq_qknorm_rope_cache_rows")
+                else:
+                    _lib.check(L.gq_rope_cache_rows(qkv.data_ptr(), input_pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), q.data_ptr(),
+                                                    kc.data_ptr(), vc.data_ptr(), S, H, Hkv, hd, kc.shape[2], st), "gq_rope_cache_rows")
                 y = _sdpa_gqa(q.unsqueeze(0), kc[:1, :, :T], vc[:1, :, :T], mask, rep)
                 y = y.transpose(1, 2).reshape(1, S, H * hd)
                 o = att.wo(y).view(S, D)

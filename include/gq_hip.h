@@ -163,6 +163,11 @@ int gq_qtip_gemm_ws(void *out, const void *compressed, const void *x, const void
 int gq_rmsnorm_rows(void *x, const void *delta, const void *weight, void *out, uint32_t S, uint32_t D, float eps, void *stream);
 int gq_rope_cache_rows(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache, void *v_cache,
                        uint32_t S, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, void *stream);
+/* gq_rope_cache_rows for Qwen3 layers, ONE launch: the RMSNorm over head_dim of every (row, head) of q and k (Qwen3RMSNorm's
+ * rounding points, as gq_attn_decode_split_qknorm below; weights fp16 [head_dim]) in front of the rotation; v copied.  head_dim 64 or 128. */
+int gq_qknorm_rope_cache_rows(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
+                              void *v_cache, uint32_t S, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                              const void *q_norm_weight, const void *k_norm_weight, float eps, void *stream);
 int gq_silu_mul_rows(const void *y, void *out, uint32_t S, uint32_t inter, int paired, void *stream);
 
 /*
@@ -423,6 +428,17 @@ int gq_attn_decode(const void *qkv, const int *pos, const void *cos_table, const
 int gq_attn_decode_split(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,
                          void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
                          float scale, uint32_t n_split, float *workspace, void *stream);
+/* Qwen3 layers: gq_attn_decode_split with the per-head RMSNorm of q and k in front of the rotation, inside the same launch.
+ * Restates transformers' modeling_qwen3.Qwen3Attention.forward (q_norm / k_norm on q and k viewed as [.., heads, head_dim], then
+ * apply_rotary_pos_emb) with Qwen3RMSNorm's rounding points: sum of squares of a head's head_dim fp16 values in fp32,
+ * (x * rsqrt(ssq / head_dim + eps)) rounded to fp16, then the fp16 product with the weight.  v is untouched; the cache receives
+ * the normalised, rotated k.  q_norm_weight, k_norm_weight: fp16 [head_dim], shared by all heads.  head_dim 64 or 128; n_split,
+ * workspace and the NaN result at *pos >= max_seq as gq_attn_decode_split.  (The reference has no Qwen3 attention of its own:
+ * any_precision/analyzer/splitted_models/qwen3.py subclasses transformers' Qwen3Model.) */
+int gq_attn_decode_split_qknorm(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,
+                                void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                                float scale, uint32_t n_split, float *workspace, const void *q_norm_weight, const void *k_norm_weight,
+                                float eps, void *stream);
 
 /*
  * Device-to-device hand-over of the layer pipeline (round 4; reference precedent: the host-side `.to(device)` hops of
