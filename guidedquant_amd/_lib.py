@@ -189,6 +189,7 @@ def _ensure_selfcheck():
     _selfchecked = True
 
 
+GQ_EINVAL = -22  # include/gq_hip.h: bad argument (shape / bitwidth / alignment)
 GQ_ENOTSUP = -95  # include/gq_hip.h: valid request this build has no kernel for
 
 

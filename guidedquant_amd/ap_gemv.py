@@ -98,30 +98,42 @@ def anyprec_dequant(qweight, lut, bitwidth):
 
 
 def anyprec_gemm_supported(x, qweight, bitwidth):
-    """True when a seq_len > 1 call should take the fused prefill GEMM (gq_anyprec_gemm_ws).  It serves GPU fp16 tensors, 2..4
-    bits, K % 64 == 0.  GQ_PREFILL_FUSED=1 sends every such call to it, =0 none; by default ("auto") only the calls it was
+    """True when a seq_len > 1 call should take the fused prefill GEMM (gq_anyprec_gemm_ws).  It serves GPU fp16 tensors, 2..8
+    bits, K % 64 == 0 (2..4 bits: csrc/ap_gemm.hip, 5..8 bits: csrc/ap_gemm_wide.hip).  GQ_PREFILL_FUSED=1 sends every such call to it, =0 none; by default ("auto") only the calls it was
     measured faster on than the reference's two steps (dequantise + hipBLASLt GEMM; profiles/r03_prefill_gemm.txt, 8B shapes):
     every matrix up to 160 rows (S = 128, 2-bit: wqkv 25 vs 44 us, wo 21 vs 37, gate/up 50 vs 97, down 36 vs 83 -- K split over
     fp32 partial sums where the grid is short), up to 640 rows every matrix at 2 / 3 bits and the large ones (gate/up, down) at 4 bits
     (S = 512, 2-bit: 48 vs 52, 38 vs 41, 125 vs 158, 84 vs 101); longer prompts keep the two steps (S = 2048: the fused kernel
-    reaches 0.35-0.43 of the fp16 MFMA peak against ~0.5 for hipBLASLt and loses by 12-30 %)."""
+    reaches 0.35-0.43 of the fp16 MFMA peak against ~0.5 for hipBLASLt and loses by 12-30 %).  At 5..8 bits "auto" keeps the two
+    steps everywhere: the kernel measured slower on every shape (`_wide_gemm_auto`)."""
     import os
-    if not (x.is_cuda and qweight.is_cuda and x.dtype == torch.float16 and 2 <= int(bitwidth) <= 4 and x.shape[-1] % 64 == 0):
+    if not (x.is_cuda and qweight.is_cuda and x.dtype == torch.float16 and 2 <= int(bitwidth) <= 8 and x.shape[-1] % 64 == 0):
         return False
     mode = os.environ.get("GQ_PREFILL_FUSED", "auto")
     if mode in ("0", "1"):
         return mode == "1"
     rows = x.numel() // x.shape[-1]
+    if int(bitwidth) >= 5:
+        return _wide_gemm_auto(rows, qweight.size(1) * x.shape[-1], int(bitwidth))
     if rows <= 160:
         return True
     return rows <= 640 and (int(bitwidth) <= 3 or qweight.size(1) * x.shape[-1] >= 50_000_000)
+
+
+def _wide_gemm_auto(rows, weights, bitwidth):
+    """the "auto" rule at 5..8 bits: never.  On the 8B shapes at S = 128 / 512 / 2048 (profiles/prefill_gemm_bits_5_to_8.json, medians
+    over a rotating weight set) the LDS-table kernel of csrc/ap_gemm_wide.hip loses to dequantise + hipBLASLt at every width, matrix
+    and row count: 0.80-0.86 of the two steps' speed at best (gate/up, S = 128: 138 vs 119 us at 5 bits, 179 vs 144 at 8), 0.21-0.46
+    everywhere else, far outside the 1-8 % p10-p90 spread of either side.  So "auto" keeps the two steps at these widths;
+    GQ_PREFILL_FUSED=1 still reaches the kernel (no dense fp16 copy of W: the choice when that transient does not fit)."""
+    return False
 
 
 def anyprec_gemm(x, qweight, lut, bitwidth):
     """x fp16 [..., K] (more than one row) -> fp16 [..., N] = x @ dequant(qweight, lut).T with the dequantisation fused into
     the MFMA loop: the seq_len > 1 branch of APLinear.forward (inference/APLinear.py:35-50) without the dense copy of W."""
     bitwidth = int(bitwidth)
-    _chk(2 <= bitwidth <= 4, "fused prefill GEMM serves bit widths 2..4.")
+    _chk(2 <= bitwidth <= 8, "fused prefill GEMM serves bit widths 2..8.")
     _chk(qweight.dtype == torch.int32 and qweight.dim() == 3 and qweight.size(0) >= bitwidth, "qweight tensor must be int32 of shape (>= bitwidth, N, K/32).")
     _chk(lut.dtype == torch.float16 and lut.dim() == 2 and lut.size(0) == qweight.size(1) and lut.size(1) == (1 << bitwidth),
          "lut tensor must be float16 of shape (output_feat, 2 ** bitwidth).")

@@ -18,7 +18,8 @@
 // Block = 256 threads = 4 waves, tile 128 weight rows x 128 tokens (wave: 32 rows x 4 token tiles = 64 accumulator VGPRs);
 // x tiles are double-buffered through registers (next stage's global loads in flight during the MFMAs); weights are read
 // once per (row tile, token tile).  fp32 accumulation over all of K, one rounding to fp16 (as a cuBLAS fp16 GEMM).
-// Requires K % 64 == 0 (tail chunks of 64 .. 960 weights are served), 2 <= bits <= 4; other widths keep the dequant path.
+// Requires K % 64 == 0 (tail chunks of 64 .. 960 weights are served).  This file: 2 <= bits <= 4; 5 to 8 bits enter through the same
+// entry points (bottom of the file) and are served by ap_gemm_wide.hip (row LUTs in LDS).
 // Two kernels: `ap_gemm_kernel` (round 2: the mapping above, x staged through registers, any K % 64 == 0) and, for K % 256 == 0,
 // `ap_gemm_pipe_kernel` further down (round 3: x through a ring of direct-to-LDS loads, plane words requested a group ahead,
 // hand software pipeline, RF x CF fragments per wave, optional K split) -- `launch_gemm` picks kernel and tile per problem.
@@ -626,15 +627,19 @@ int launch_gemm(const void *x, void *out, const uint32_t *qw, const void *lut, u
 }
 }  // namespace
 
+// 5 to 8 bits: the row LUTs in LDS, the block decodes a weight tile per K stage (ap_gemm_wide.hip) -- one tile shape, no split K
+int gq_ap_gemm_wide(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t S, uint32_t N, uint32_t K, int bits,
+                    hipStream_t stream);
+
 extern "C" size_t gq_anyprec_gemm_ws_bytes(uint32_t S, uint32_t N, uint32_t K, int bits) {
-    if (bits < 2 || bits > 4 || K == 0 || S == 0 || N == 0) return 0;
+    if (bits < 2 || bits > 4 || K == 0 || S == 0 || N == 0) return 0;  // (5..8 bits: served, never split)
     const u32 nks = gemm_plan_ksplit(S, N, K, bits).nks;
     return nks > 1u ? (size_t)nks * S * N * 4u : 0;
 }
 
 extern "C" int gq_anyprec_gemm_ws(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t S, uint32_t N, uint32_t K,
                                   int bits, void *workspace, size_t ws_bytes, void *stream) {
-    if (bits < 2 || bits > 4) return gq_fail(GQ_ENOTSUP, "gq_anyprec_gemm: bits must be 2, 3 or 4 (wider: dequantise + GEMM).");
+    if (bits < 2 || bits > 8) return gq_fail(GQ_ENOTSUP, "gq_anyprec_gemm: bits must be 2 to 8.");
     if (K == 0 || K % 64u) return gq_fail(GQ_ENOTSUP, "gq_anyprec_gemm: K must be a positive multiple of 64.");
     if (S == 0 || N == 0) return gq_fail(GQ_EINVAL, "gq_anyprec_gemm: empty problem.");
     if (!x || !out || !qweight || !lut) return gq_fail(GQ_EINVAL, "null pointer argument.");
@@ -643,6 +648,7 @@ extern "C" int gq_anyprec_gemm_ws(const void *x, void *out, const uint32_t *qwei
     if (workspace && ((uintptr_t)workspace & 15u)) return gq_fail(GQ_EINVAL, "gq_anyprec_gemm_ws: workspace must be 16-byte aligned.");
     hipStream_t s = (hipStream_t)stream;
     float *ws = (float *)workspace;
+    if (bits > 4) return gq_ap_gemm_wide(x, out, qweight, lut, S, N, K, bits, s);  // (takes no workspace)
     switch (bits) {
         case 2: return launch_gemm<2>(x, out, qweight, lut, S, N, K, s, ws, ws_bytes);
         case 3: return launch_gemm<3>(x, out, qweight, lut, S, N, K, s, ws, ws_bytes);

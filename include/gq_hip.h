@@ -104,7 +104,9 @@ int gq_lnq_cd_block(const float *W, const float *B, const float *Hn, const float
  * Replaces the seq_len > 1 branch of APLinear.forward / AnyPrecisionLinear.forward (inference/APLinear.py:35-50,
  * any_precision/modules/AnyPrecisionLinear.py:69-71): ap_gemv.anyprec_dequant (dequant_kbit_store, anyprec.cu:294-359) followed
  * by torch.matmul -- without writing and re-reading the dense fp16 copy of W.  fp32 accumulation, one rounding to fp16.
- * bits 2..4, K % 64 == 0 (GQ_ENOTSUP otherwise: the caller keeps the dequant path); qweight may hold more planes than bits.
+ * bits 2..8, K % 64 == 0 (GQ_ENOTSUP otherwise: the caller keeps the dequant path); qweight may hold more planes than bits.
+ * 2..4 bits decode in registers (v_perm byte pools of the row LUT, csrc/ap_gemm.hip); 5..8 bits keep the tile's row LUTs in LDS and
+ * decode a weight tile per K stage there (csrc/ap_gemm_wide.hip).  Same argument checks, arithmetic and rounding at every width.
  */
 int gq_anyprec_gemm(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t S, uint32_t N, uint32_t K,
                     int bits, void *stream);
@@ -113,7 +115,9 @@ int gq_anyprec_gemm(const void *x, void *out, const uint32_t *qweight, const voi
  * prompt of <= 512 tokens on the 4096-row matrices): K is then split over up to 16 ranges, each block leaves fp32 partial sums
  * in the workspace and a second launch adds the ranges in order and rounds once to fp16 (results equal to gq_anyprec_gemm's up
  * to the fp32 summation order).  gq_anyprec_gemm_ws_bytes = the workspace this problem would use (0: no split planned);
- * a null / too small workspace runs the single pass.  workspace 16-byte aligned.
+ * a null / too small workspace runs the single pass.  workspace 16-byte aligned.  K is split at 2..4 bits only: at 5..8 bits
+ * gq_anyprec_gemm_ws_bytes is 0 and gq_anyprec_gemm_ws runs the single pass whatever workspace it is given (as for bits outside
+ * 2..8, where gq_anyprec_gemm_ws_bytes is 0 and the GEMM returns GQ_ENOTSUP).
  */
 size_t gq_anyprec_gemm_ws_bytes(uint32_t S, uint32_t N, uint32_t K, int bits);
 int gq_anyprec_gemm_ws(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t S, uint32_t N, uint32_t K,
