@@ -6,7 +6,7 @@
 #include <stdint.h>
 
 #include "ap_core.h"
-#include "gq_internal.h"
+#include "ap_dispatch.h"
 
 namespace {
 using namespace gq;
@@ -29,6 +29,13 @@ struct ApArgs {
     float *ssq_out;
     unsigned long long *dbg = nullptr;  // GQ_STAMPS builds: the debug buffer of gq_debug_set_timing_buffer (tools/r6/exact_stamps.py)
 };
+// the kernel arguments of a launch on a plan of RS row slots and SPB row steps per block (the workspace and the hand-over are not these kernels')
+inline ApArgs ap_args(const ApLaunch &L, u32 RS, u32 SPB) {
+    ApArgs a{};
+    a.qw = L.qweight, a.lut = L.lut, a.x = L.x, a.out = L.out, a.normw = L.normw, a.resid = L.resid;
+    a.N = L.N, a.K = L.K, a.RS = RS, a.SPB = SPB, a.epilogue = L.epilogue, a.eps = L.eps;
+    return a;
+}
 
 __device__ __forceinline__ uint4 ld16(const void *p) { return *reinterpret_cast<const uint4 *>(p); }
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
@@ -43,7 +50,6 @@ __device__ __forceinline__ uint16_t f2h(float f) { return __builtin_bit_cast(uin
 // Fused prologues, with the same fp16 rounding points as the reference's separate kernels (ap_gemv.hip::stage_x, stage_x_natural below):
 //   PRO_RMSNORM: y = (x.float() * rsqrt(mean(x^2) + eps)).half() * w        (inference/model.py:281-292)
 //   PRO_SILUMUL: y = silu(g) * u with g = x[0:K], u = x[K:2K]                (inference/model.py:266)
-enum { PRO_NONE = 0, PRO_RMSNORM = 1, PRO_SILUMUL = 2 };
 
 __device__ __forceinline__ u32 silu_mul_pk(u32 g, u32 u) {
     // F.silu on an fp16 tensor evaluates x / (1 + exp(-x)) in fp32 and rounds to fp16; then an fp16 multiply.

@@ -26,7 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ap_core.h"
-#include "gq_internal.h"
+#include "ap_dispatch.h"
 
 namespace {
 using gq::u32;
@@ -627,10 +627,6 @@ int launch_gemm(const void *x, void *out, const uint32_t *qw, const void *lut, u
 }
 }  // namespace
 
-// 5 to 8 bits: the row LUTs in LDS, the block decodes a weight tile per K stage (ap_gemm_wide.hip) -- one tile shape, no split K
-int gq_ap_gemm_wide(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t S, uint32_t N, uint32_t K, int bits,
-                    hipStream_t stream);
-
 extern "C" size_t gq_anyprec_gemm_ws_bytes(uint32_t S, uint32_t N, uint32_t K, int bits) {
     if (bits < 2 || bits > 4 || K == 0 || S == 0 || N == 0) return 0;  // (5..8 bits: served, never split)
     const u32 nks = gemm_plan_ksplit(S, N, K, bits).nks;
@@ -648,6 +644,7 @@ extern "C" int gq_anyprec_gemm_ws(const void *x, void *out, const uint32_t *qwei
     if (workspace && ((uintptr_t)workspace & 15u)) return gq_fail(GQ_EINVAL, "gq_anyprec_gemm_ws: workspace must be 16-byte aligned.");
     hipStream_t s = (hipStream_t)stream;
     float *ws = (float *)workspace;
+    // 5 to 8 bits: the row LUTs in LDS, the block decodes a weight tile per K stage (ap_gemm_wide.hip) -- one tile shape, no split K
     if (bits > 4) return gq_ap_gemm_wide(x, out, qweight, lut, S, N, K, bits, s);  // (takes no workspace)
     switch (bits) {
         case 2: return launch_gemm<2>(x, out, qweight, lut, S, N, K, s, ws, ws_bytes);

@@ -43,7 +43,7 @@
 #include <stdint.h>
 
 #include "ap_core.h"
-#include "gq_internal.h"
+#include "ap_dispatch.h"
 
 namespace {
 using gq::u32;

@@ -20,8 +20,6 @@
 
 using namespace gq;
 
-unsigned long long *gq_debug_timing_buffer();  // ap_plane.hip (gq_debug_set_timing_buffer)
-
 namespace {
 
 // ----------------------------------------------------------------------------------------------
@@ -891,20 +889,18 @@ int launch_dq(const DqArgs &da, const DqCfg &c, int pro, hipStream_t s) {
         default: return launch_dq_inst<BITS, PRO_NONE>(da, c, s);
     }
 }
+}  // namespace
 // GQ_ENOTSUP when the shape is not served (the caller goes on to the plane / exact kernels)
-int dq_gemv_try(const ApArgs &a, u32 M, int bits, int pro, hipStream_t s) {
+int gq_ap_dq_try(const ApLaunch &L) {
     DqCfg c;
-    if (M != 1u || !pick_dq_cfg(a.N, a.K, bits, c)) return GQ_ENOTSUP;
-    if ((uint64_t)bits * a.N * (a.K / 8u) >= 0x7FFFFFFFull) return GQ_ENOTSUP;
-    if ((((uintptr_t)a.qw | (uintptr_t)a.x | (uintptr_t)a.normw | (uintptr_t)a.lut) & 15u) != 0) return GQ_ENOTSUP;
-    if ((a.epilogue & GQ_EPI_SILU_PAIRS) && (a.N & 1u)) return GQ_ENOTSUP;
-    DqArgs da{a, c.RGB, c.NU, c.part_off, GQ_STAMPS ? gq_debug_timing_buffer() : nullptr};
-    switch (bits) {
-        case 2: return launch_dq<2>(da, c, pro, s);
-        case 3: return launch_dq<3>(da, c, pro, s);
-        default: return launch_dq<4>(da, c, pro, s);
-    }
+    if (L.M != 1u || !pick_dq_cfg(L.N, L.K, L.bits, c)) return GQ_ENOTSUP;
+    if (L.qbytes() >= 0x7FFFFFFFull) return GQ_ENOTSUP;
+    if (L.unaligned16()) return GQ_ENOTSUP;
+    if (L.pairs && (L.N & 1u)) return GQ_ENOTSUP;
+    DqArgs da{ap_args(L, 0u, 0u), c.RGB, c.NU, c.part_off, GQ_STAMPS ? gq_debug_timing_buffer() : nullptr};
+    return gq_with_bits<2, 4>(L.bits, [&](auto B) { return launch_dq<B()>(da, c, L.pro, L.stream); });
 }
+namespace {
 
 // ----------------------------------------------------------------------------------------------
 // Generic path: any 2 <= BITS <= 8, any K % 32 == 0.  32 lanes per row exactly like the reference warp
@@ -1028,9 +1024,6 @@ __global__ void __launch_bounds__(256) ap_dequant_kernel(const u32 *qw, const ui
 // ----------------------------------------------------------------------------------------------
 #ifndef GQ_AP_PT_DEFAULT
 #define GQ_AP_PT_DEFAULT 0  // exact mode, 2 bits: the LDS pair-table kernel (ap_gemv_pt2_kernel) instead of the v_perm kernel: 1 long rows, 2 all
-#endif
-#ifndef GQ_DQ_DEFAULT
-#define GQ_DQ_DEFAULT 6  // (bit mask over the bit widths 2, 3, 4 the decode-to-fp16 kernel may take: 3 and 4)
 #endif
 struct QuadCfg {
     u32 T, RS, SPB, D, grid;
@@ -1240,279 +1233,24 @@ int launch_generic(const ApArgs &a, u32 M, hipStream_t s) {
 
 }  // namespace
 
-int gq_plane_gemv_try(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t M, uint32_t N, uint32_t K,
-                      int bits, const void *normw, float eps, const void *resid, int pro, int pairs, hipStream_t stream, void *ws, size_t ws_bytes,
-                      GqHandover *ho);
-size_t gq_stream_ksplit_ws_bytes(uint32_t N, uint32_t K, int bits);  // ap_stream.hip
-int gq_ap_wide_try(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t M, uint32_t N, uint32_t K, int bits,
-                   const void *normw, float eps, const void *resid, int pro, uint32_t epilogue, hipStream_t stream);  // ap_wide.hip
-bool gq_plane_local_shape(uint32_t N, uint32_t K, int bits);
-
 namespace {
-
-int g_ap_mode = -1;  // -1: unset (env GQ_AP_MODE or default fast), 0: fast (plane-MFMA), 1: exact (fp16-order)
-bool exact_mode() {
-    if (g_ap_mode >= 0) return g_ap_mode == 1;
-    return gq_env_int("GQ_AP_EXACT", 0) != 0;
+// the launches the fp16-order kernels serve, and the v_perm kernel's plan for them
+bool exact_serves(const ApLaunch &L, QuadCfg &c) {
+    return L.bits >= 2 && L.bits <= 4 && L.qbytes() < 0x7FFFFFFFull && pick_quad_cfg(L.N, L.K, L.bits, c, L.pro, false, L.pairs) && !L.unaligned16();
 }
 }  // namespace
-bool gq_ap_exact_mode() { return exact_mode(); }  // (ap_stream.hip: the fused q / k / v + RoPE launch is a fast-mode kernel)
-namespace {
-
-// Stand-alone producer of the hand-over statistics: GQ_SSQ_SLOTS partial sums of squares of an fp16 vector (slot t: elements t, t + 1024,
-// ..).  What a GEMV launch without the in-epilogue form is followed by when the caller asked for ssq_out; also gq_ssq_rows.
-__global__ void __launch_bounds__(GQ_SSQ_SLOTS) ssq_rows_kernel(const uint16_t *x, u32 n, float *ssq) {
-    float acc = 0.f;
-    for (u32 i = threadIdx.x; i < n; i += (u32)GQ_SSQ_SLOTS) {
-        const float v = h2f(x[i]);
-        acc += v * v;
-    }
-    gq_store_wt(ssq + threadIdx.x, acc);
+int gq_ap_pair_table_try(const ApLaunch &L) {
+    QuadCfg c, cp;
+    if (!pt2_wanted(L.bits, L.K) || !exact_serves(L, c) || !pick_quad_cfg(L.N, L.K, L.bits, cp, L.pro, true, L.pairs)) return GQ_ENOTSUP;
+    return launch_pt2(ap_args(L, cp.RS, cp.SPB), cp, L.M, L.pro, L.stream);
 }
-
-// the route record (gq_internal.h: gq_ap_route) of the calling thread, and whether its dispatch is a dry run
-thread_local uint32_t t_route[3] = {GQ_AP_ROUTE_NONE, 0u, 0u};
-thread_local bool t_dry = false;
-}  // namespace
-bool gq_ap_route(uint32_t family, uint32_t launches, uint32_t variant) {
-    t_route[0] = family, t_route[1] = launches, t_route[2] = variant;
-    return t_dry;
-}
-namespace {
-
-int ap_gemv_dispatch_inner(ApArgs a, u32 M, int bits, hipStream_t s, GqHandover *ho);
-int ap_gemv_dispatch(ApArgs a, u32 M, int bits, hipStream_t s) {
-    gq_ap_route(GQ_AP_ROUTE_NONE, 0u);
-    GqHandover ho;
-    ho.ssq_in = a.ssq_in;
-    ho.ssq_out = a.ssq_out;
-    if (ho.ssq_out && ((a.epilogue & GQ_EPI_SILU_PAIRS) || M != 1u)) return gq_fail(GQ_EINVAL, "ssq_out: plain / residual epilogue, M = 1 only.");
-    const int rc = ap_gemv_dispatch_inner(a, M, bits, s, &ho);
-    if (rc == GQ_OK && ho.ssq_out && !ho.ssq_written) {  // the kernel that served the shape has no in-epilogue form: one small launch more
-        hipLaunchKernelGGL(ssq_rows_kernel, dim3(1), dim3(GQ_SSQ_SLOTS), 0, s, a.out, a.N, ho.ssq_out);
-        GQ_HIP_CHECK(hipGetLastError());
-        t_route[1]++;
-    }
-    return rc;
-}
-
-int ap_gemv_dispatch_inner(ApArgs a, u32 M, int bits, hipStream_t s, GqHandover *ho) {
-    gq_ap_route(GQ_AP_ROUTE_NONE, 0u);  // (until a launch site records what it launches)
-    if (bits < 2 || bits > 8) return gq_fail(GQ_EINVAL, "Bitwidth must be between 2 and 8.");
-    if (M < 1 || M > 8) return gq_fail(GQ_EINVAL, "batch size M must be between 1 and 8 (anyprec.cu:602).");
-    if (a.K == 0 || a.K % 32u) return gq_fail(GQ_EINVAL, "input_feat (K) must be a positive multiple of 32.");
-    if (a.N == 0) return gq_fail(GQ_EINVAL, "output_feat (N) must be positive.");
-    if (!a.x || !a.out || !a.qw || !a.lut) return gq_fail(GQ_EINVAL, "null pointer argument.");
-    const bool force_generic = gq_env_int("GQ_AP_FORCE_GENERIC", 0) != 0;
+int gq_ap_exact_try(const ApLaunch &L) {
     QuadCfg c;
-    const int pro = a.normw ? PRO_RMSNORM : ((a.epilogue & GQ_PRO_SILU_MUL) ? PRO_SILUMUL : PRO_NONE);
-    // fast mode serves the shapes on which the plane-MFMA kernel beats the exact kernel (measured):
-    // 2-bit matrices of >= 20 M weights (wqkv, w1w3, w2 of the 8B / 70B models), 3- and 4-bit matrices of >= 32 M weights
-    // (w1w3, w2); everything else runs the exact kernels, whose results are bit-identical to the reference.
-    // GQ_PL_MIN_MWEIGHTS overrides the threshold for every bit width, GQ_PL_MAX_BITS the widest plane-served width.
-    const int env_min = gq_env_int("GQ_PL_MIN_MWEIGHTS", -1);
-    // (matrices of <= 16 rows per CU without the RMSNorm prologue run the local-image variant, which needs no block-wide
-    // activation pass: >= 16 M weights at 2 and 3 bits -- wo)
-    const bool local = pro != PRO_RMSNORM && bits <= 3 && gq_plane_local_shape(a.N, a.K, bits);
-    // (round 5: behind the RMSNorm prologue the plane kernel wins from 20 M weights at 3 and 4 bits too -- 8B wqkv, 25 M: 7.2 vs 8.4 us
-    // at 3 bits, 10.2 vs 12.0 at 4 -- the exact kernel normalises the whole vector in every block in front of its first row step;
-    // without the prologue the 32 M threshold stands: wo at 4 bits 6.6 exact vs 7.6 plane.  profiles/r05_dispatch_3_4_bits.txt)
-    const int def_min = local ? 16 : ((bits == 2 || pro == PRO_RMSNORM) ? 20 : 32);
-    const uint64_t min_w = (uint64_t)(env_min >= 0 ? env_min : def_min) * 1000000ull;
-    const int max_bits = gq_env_int("GQ_PL_MAX_BITS", 4);
-    // round 6: decode-to-fp16 on the matrix cores (ap_gemv_dq_kernel) where it measured faster than the other kernels
-    // (profiles/r06_dq_kernel.txt, 8B shapes, decode-graph launch forms, same box): at 4 bits every matrix of >= 16 M weights -- wqkv 9.1
-    // vs 10.3 us, wo 6.6 vs 6.8 (exact kernel), w1w3 22.9 vs 24.4, w2 13.9 vs 15.0 --, at 3 bits the matrices of 16 .. 32 M weights (wqkv
-    // 6.5 vs 7.2, wo 4.9 vs 5.3; Llama-2-7B's wqkv 50 M 8.1 vs 9.5, w1w3 90 M 12.7 vs 14.2) up to 100 M, and the long-row launches
-    // without the RMSNorm prologue at any size (8B w2 9.35 vs 9.65, 70B w2 235 M 26.5 vs 34.8; 70B wqkv 84 M 13.2 vs 14.8); the big
-    // RMSNorm + pair launches stay on the plane kernel (70B w1w3 470 M 45.7 vs 43.0; 8B w1w3 117 M was 15.3 vs 14.8 and, with the item
-    // loop's divisions gone, is 14.6 vs 14.8 alone and 13.5 vs 14.0 in the decode graph: 3-bit decode 720 -> 736 tokens/s -- the bound moved
-    // from 100 M to 200 M); never at 2 bits
-    // (8B w1w3 11.6 vs 8.5, 70B w1w3 37 vs 25).
-    // GQ_DQ: bit mask of the widths it may take (bit b - 2; 0 = never), GQ_DQ_MIN_MWEIGHTS >= 0: every matrix of at least that many
-    // million weights at those widths.
-    {
-        const int dq_mask = gq_env_int("GQ_DQ", GQ_DQ_DEFAULT), dq_min = gq_env_int("GQ_DQ_MIN_MWEIGHTS", -1);
-        const uint64_t nk = (uint64_t)a.N * a.K;
-        const bool dq_shape = dq_min >= 0 ? nk >= (uint64_t)dq_min * 1000000ull
-                                          // (and at least one 16-row group per CU: Llama-3.2-1B's w2, 2048 x 8192 = 128 blocks, is faster on the
-                                          // exact kernel -- 4-bit 1B decode 1555 vs 1508 tokens/s; Llama-3.3-70B at 4 bits: 72 -> 86 tokens/s here)
-                                          : (a.N >= 4096u &&
-                                             (bits == 4 ? nk >= 16000000ull
-                                                        : (bits == 3 && nk >= 16000000ull &&
-                                                           (nk < 200000000ull || (pro != PRO_RMSNORM && a.K >= 8192u)))));
-        if (!force_generic && !exact_mode() && bits <= 4 && ((dq_mask >> (bits - 2)) & 1) && dq_shape) {
-            const int rc = dq_gemv_try(a, M, bits, pro, s);
-            if (rc != GQ_ENOTSUP) return rc;
-        }
-    }
-    if (!force_generic && !exact_mode() && bits <= max_bits && (uint64_t)a.N * a.K >= min_w) {
-        int rc = gq_plane_gemv_try(a.x, a.out, a.qw, a.lut, M, a.N, a.K, bits, a.normw, a.eps, a.resid, pro, (a.epilogue & GQ_EPI_SILU_PAIRS) != 0, s, a.ws, a.ws_bytes, ho);
-        if (rc != GQ_ENOTSUP) return rc;
-    }
-    const uint64_t qbytes = (uint64_t)bits * a.N * (a.K / 8u);
-    const bool pairs = (a.epilogue & GQ_EPI_SILU_PAIRS) != 0;
-    if (!force_generic && bits <= 4 && qbytes < 0x7FFFFFFFull && pick_quad_cfg(a.N, a.K, bits, c, pro, false, pairs) &&
-        (((uintptr_t)a.qw | (uintptr_t)a.x | (uintptr_t)a.normw) & 15u) == 0 && ((uintptr_t)a.lut & 15u) == 0) {
-        a.RS = c.RS;
-        a.SPB = c.SPB;
-        // round 6: the pair-table kernel (GQ_AP_PT: 0 never -- the default --, 1 rows of >= 8192 weights, 2 every shape it serves).  It had
-        // measured faster on 8B w2 (11.3 vs 12.7 us) while BOTH kernels ran that launch in two rounds of blocks (pick_quad_cfg: blocks per
-        // CU beyond the occupancy); in one round the v_perm kernel is the faster one on every Llama shape (8B w2 8.9 vs 9.9 us; 70B w2 26.0
-        // vs 33.6, wqkv 12.4 vs 13.5, wo 8.7 vs 10.0) except 70B w1w3 (41.7 vs 38.1): profiles/r06_exact_pair_table.txt, r06_exact_epilogue.txt
-        {
-            QuadCfg cp;
-            if (pt2_wanted(bits, a.K) && pick_quad_cfg(a.N, a.K, bits, cp, pro, true, pairs)) {
-                ApArgs ap = a;
-                ap.RS = cp.RS;
-                ap.SPB = cp.SPB;
-                const int rc = launch_pt2(ap, cp, M, pro, s);
-                if (rc != GQ_ENOTSUP) return rc;
-            }
-        }
-        switch (bits) {
-            case 2: return launch_quad<2>(a, c, M, pro, s);
-            case 3: return launch_quad<3>(a, c, M, pro, s);
-            default: return launch_quad<4>(a, c, M, pro, s);
-        }
-    }
-    // bits 5..8, one batch row, both modes: the LDS-table kernel (ap_wide.hip), in the reference's order like the generic kernel
-    if (!force_generic && bits >= 5) {
-        const int rc = gq_ap_wide_try(a.x, a.out, a.qw, a.lut, M, a.N, a.K, bits, a.normw, a.eps, a.resid, pro, a.epilogue, s);
-        if (rc != GQ_ENOTSUP) return rc;
-    }
-    if (pro != PRO_NONE || (a.epilogue & GQ_EPI_SILU_PAIRS))
-        return gq_fail(GQ_ENOTSUP, "fused prologue / pair epilogue needs K % 128 == 0 (<= 32768 at 5..8 bits) and 16-byte aligned buffers.");
-    if ((uintptr_t)a.x & 15u) return gq_fail(GQ_EINVAL, "input must be 16-byte aligned.");
-    switch (bits) {
-        case 2: return launch_generic<2>(a, M, s);
-        case 3: return launch_generic<3>(a, M, s);
-        case 4: return launch_generic<4>(a, M, s);
-        case 5: return launch_generic<5>(a, M, s);
-        case 6: return launch_generic<6>(a, M, s);
-        case 7: return launch_generic<7>(a, M, s);
-        default: return launch_generic<8>(a, M, s);
-    }
+    if (!exact_serves(L, c)) return GQ_ENOTSUP;
+    return gq_with_bits<2, 4>(L.bits, [&](auto B) { return launch_quad<B()>(ap_args(L, c.RS, c.SPB), c, L.M, L.pro, L.stream); });
 }
-
-}  // namespace
-
-extern "C" int gq_set_ap_mode(int mode) {
-    if (mode < -1 || mode > 1) return gq_fail(GQ_EINVAL, "mode must be -1 (default), 0 (fast) or 1 (exact)");
-    g_ap_mode = mode;
-    return GQ_OK;
-}
-
-extern "C" int gq_anyprec_gemv(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t M, uint32_t N,
-                               uint32_t K, int bits, int dtype, void *stream) {
-    if (dtype != GQ_DTYPE_F16) return gq_fail(GQ_ENOTSUP, "only fp16 is implemented (as in the reference, gemv.cu:46-49).");
-    ApArgs a{};
-    a.qw = qweight;
-    a.lut = (const uint16_t *)lut;
-    a.x = (const uint16_t *)x;
-    a.out = (uint16_t *)out;
-    a.N = N;
-    a.K = K;
-    a.epilogue = GQ_EPI_NONE;
-    return ap_gemv_dispatch(a, M, bits, (hipStream_t)stream);
-}
-
-extern "C" size_t gq_anyprec_gemv_fused_ws_bytes(uint32_t N, uint32_t K, int bits, uint32_t epilogue) {
-    if ((epilogue & (GQ_PRO_SILU_MUL | GQ_EPI_SILU_PAIRS)) || exact_mode()) return 0;
-    return gq_stream_ksplit_ws_bytes(N, K, bits);
-}
-extern "C" int gq_anyprec_gemv_fused(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t N,
-                                     uint32_t K, int bits, const void *norm_weight, float eps, const void *residual,
-                                     uint32_t epilogue, void *stream) {
-    return gq_anyprec_gemv_fused_ws(x, out, qweight, lut, N, K, bits, norm_weight, eps, residual, epilogue, nullptr, 0, stream);
-}
-extern "C" int gq_anyprec_gemv_fused_ws(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t N,
-                                        uint32_t K, int bits, const void *norm_weight, float eps, const void *residual,
-                                        uint32_t epilogue, void *workspace, size_t workspace_bytes, void *stream) {
-    return gq_anyprec_gemv_fused_ho(x, out, qweight, lut, N, K, bits, norm_weight, eps, residual, epilogue, workspace, workspace_bytes, nullptr,
-                                    nullptr, stream);
-}
-namespace {
-alignas(16) unsigned char g_stand_in[16];  // (a 16-byte aligned stand-in for every pointer of a dry dispatch: never dereferenced)
-// a dry dispatch (gq_ap_route) of the launch form: M rows, the RMSNorm prologue, the epilogue flags and the workspace as given
-int ap_dry_dispatch(u32 N, u32 K, int bits, u32 M, bool has_norm, u32 epilogue, size_t ws_bytes, GqHandover *ho) {
-    void *al = g_stand_in;
-    ApArgs a{};
-    a.qw = (const u32 *)al;
-    a.lut = (const uint16_t *)al;
-    a.x = (const uint16_t *)al;
-    a.out = (uint16_t *)al;
-    a.normw = has_norm ? (const uint16_t *)al : nullptr;
-    a.resid = (epilogue & GQ_EPI_RESIDUAL) ? (const uint16_t *)al : nullptr;
-    a.ws = ws_bytes ? al : nullptr;
-    a.ws_bytes = ws_bytes;
-    a.N = N;
-    a.K = K;
-    a.epilogue = epilogue;
-    t_dry = true;
-    const int rc = ap_gemv_dispatch_inner(a, M, bits, nullptr, ho);
-    t_dry = false;
-    return rc;
-}
-}  // namespace
-extern "C" int gq_anyprec_handover_plan(uint32_t N, uint32_t K, int bits, int has_norm, uint32_t epilogue) {
-    // which kernel would serve the launch, without launching: 1 = its RMSNorm prologue reads ssq_in, 2 = its epilogue writes ssq_out
-    GqHandover ho;
-    ho.ssq_in = (const float *)(void *)g_stand_in;
-    ho.ssq_out = (epilogue & GQ_EPI_SILU_PAIRS) ? nullptr : (float *)(void *)g_stand_in;
-    if (ap_dry_dispatch(N, K, bits, 1u, has_norm != 0, epilogue, 0, &ho) != GQ_OK) return 0;
-    return (ho.ssq_consumed ? 1 : 0) | (ho.ssq_written ? 2 : 0);
-}
-extern "C" int gq_debug_ap_plan_route(uint32_t N, uint32_t K, int bits, uint32_t M, int has_norm, uint32_t epilogue, size_t ws_bytes,
-                                      uint32_t *route) {
-    if (!route) return gq_fail(GQ_EINVAL, "null pointer argument.");
-    route[0] = GQ_AP_ROUTE_NONE, route[1] = route[2] = 0u;
-    // (the argument checks of gq_anyprec_gemv / gq_anyprec_gemv_fused_ws)
-    if (M != 1u && (has_norm || epilogue || ws_bytes)) return gq_fail(GQ_EINVAL, "prologue / epilogue / workspace: M = 1 only.");
-    if ((epilogue & GQ_PRO_SILU_MUL) && has_norm) return gq_fail(GQ_EINVAL, "RMSNorm and SiLU-mul prologues are exclusive.");
-    if ((epilogue & GQ_EPI_SILU_PAIRS) && ((epilogue & GQ_EPI_RESIDUAL) || (N & 1u)))
-        return gq_fail(GQ_EINVAL, "SILU_PAIRS epilogue needs an even N and excludes the residual epilogue.");
-    GqHandover ho;
-    const int rc = ap_dry_dispatch(N, K, bits, M, has_norm != 0, epilogue, ws_bytes, &ho);
-    for (int i = 0; i < 3; i++) route[i] = t_route[i];
-    return rc;
-}
-extern "C" int gq_debug_ap_last_route(uint32_t *route) {
-    if (!route) return gq_fail(GQ_EINVAL, "null pointer argument.");
-    for (int i = 0; i < 3; i++) route[i] = t_route[i];
-    return GQ_OK;
-}
-extern "C" int gq_ssq_rows(const void *x, uint32_t n, float *ssq_out, void *stream) {
-    if (!x || !ssq_out || n == 0) return gq_fail(GQ_EINVAL, "null pointer argument / empty vector.");
-    hipLaunchKernelGGL(ssq_rows_kernel, dim3(1), dim3(GQ_SSQ_SLOTS), 0, (hipStream_t)stream, (const uint16_t *)x, n, ssq_out);
-    GQ_HIP_CHECK(hipGetLastError());
-    return GQ_OK;
-}
-extern "C" int gq_anyprec_gemv_fused_ho(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t N,
-                                        uint32_t K, int bits, const void *norm_weight, float eps, const void *residual,
-                                        uint32_t epilogue, void *workspace, size_t workspace_bytes, const float *ssq_in, float *ssq_out,
-                                        void *stream) {
-    gq_ap_route(GQ_AP_ROUTE_NONE, 0u);
-    ApArgs a{};
-    a.ssq_in = norm_weight ? ssq_in : nullptr;
-    a.ssq_out = ssq_out;
-    a.ws = workspace;
-    a.ws_bytes = workspace ? workspace_bytes : 0;
-    a.qw = qweight;
-    a.lut = (const uint16_t *)lut;
-    a.x = (const uint16_t *)x;
-    a.out = (uint16_t *)out;
-    a.normw = (const uint16_t *)norm_weight;
-    a.resid = (epilogue & GQ_EPI_RESIDUAL) ? (const uint16_t *)residual : nullptr;
-    a.eps = eps;
-    a.N = N;
-    a.K = K;
-    a.epilogue = epilogue;
-    if ((epilogue & GQ_EPI_RESIDUAL) && !residual) return gq_fail(GQ_EINVAL, "RESIDUAL epilogue needs a residual pointer.");
-    if ((epilogue & GQ_PRO_SILU_MUL) && norm_weight) return gq_fail(GQ_EINVAL, "RMSNorm and SiLU-mul prologues are exclusive.");
-    if ((epilogue & GQ_EPI_SILU_PAIRS) && ((epilogue & GQ_EPI_RESIDUAL) || (N & 1u)))
-        return gq_fail(GQ_EINVAL, "SILU_PAIRS epilogue needs an even N and excludes the residual epilogue.");
-    return ap_gemv_dispatch(a, 1, bits, (hipStream_t)stream);
+int gq_ap_generic(const ApLaunch &L) {
+    return gq_with_bits<2, 8>(L.bits, [&](auto B) { return launch_generic<B()>(ap_args(L, 0u, 0u), L.M, L.stream); });
 }
 
 extern "C" int gq_anyprec_dequant(const uint32_t *qweight, const void *lut, void *W, uint32_t N, uint32_t K, int bits,
@@ -1525,15 +1263,10 @@ extern "C" int gq_anyprec_dequant(const uint32_t *qweight, const void *lut, void
     hipStream_t s = (hipStream_t)stream;
     const uint16_t *l = (const uint16_t *)lut;
     uint16_t *w = (uint16_t *)W;
-    switch (bits) {
-        case 2: hipLaunchKernelGGL(ap_dequant_kernel<2>, grid, block, 0, s, qweight, l, w, N, K); break;
-        case 3: hipLaunchKernelGGL(ap_dequant_kernel<3>, grid, block, 0, s, qweight, l, w, N, K); break;
-        case 4: hipLaunchKernelGGL(ap_dequant_kernel<4>, grid, block, 0, s, qweight, l, w, N, K); break;
-        case 5: hipLaunchKernelGGL(ap_dequant_kernel<5>, grid, block, 0, s, qweight, l, w, N, K); break;
-        case 6: hipLaunchKernelGGL(ap_dequant_kernel<6>, grid, block, 0, s, qweight, l, w, N, K); break;
-        case 7: hipLaunchKernelGGL(ap_dequant_kernel<7>, grid, block, 0, s, qweight, l, w, N, K); break;
-        default: hipLaunchKernelGGL(ap_dequant_kernel<8>, grid, block, 0, s, qweight, l, w, N, K); break;
-    }
+    gq_with_bits<2, 8>(bits, [&](auto B) {
+        hipLaunchKernelGGL(ap_dequant_kernel<B()>, grid, block, 0, s, qweight, l, w, N, K);
+        return GQ_OK;
+    });
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
 }

@@ -21,7 +21,7 @@
 #include <stdint.h>
 #include <type_traits>
 
-#include "gq_internal.h"
+#include "ap_dispatch.h"
 #include "plane_core.h"
 
 using namespace gqp;
@@ -68,7 +68,6 @@ struct PlaneArgs {
 #ifndef PL_SSQ_MODE
 #define PL_SSQ_MODE 2  // statistics hand-over slots: plain stores, slots grouped by XCD (see plane_epilogue)
 #endif
-enum { PRO_NONE = 0, PRO_RMSNORM = 1, PRO_SILUMUL = 2 };
 
 __device__ __forceinline__ float h2f(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
 __device__ __forceinline__ uint16_t f2h(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
@@ -1423,7 +1422,7 @@ bool pick_plane_cfg(u32 N, u32 K, int bits, PlaneCfg &c, u32 MB = 1u) {
 bool pick_local_cfg(u32 N, u32 K, int bits, PlaneCfg &c) {
     // (4 bits: rounds 2-4 kept the shared image with the late-wave helpers; re-measured in round 5 -- stamps and ablation switches
     // compiled out, one ring slot per wave -- the local image wins on w2: 16.8 -> 15.3 us, decode 461 -> 472 tokens/s.  wo at 4 bits
-    // stays on the exact kernel: the dispatcher's threshold, ap_gemv.hip.  profiles/r05_knob_sweep.txt)
+    // stays on the exact kernel: the dispatcher's threshold, ap_dispatch.hip.  profiles/r05_knob_sweep.txt)
     if (K % 256u || bits > gq_env_int("GQ_PL_LOCAL_MAXBITS", 4)) return false;
     const u32 nchunks = K / 1024u + ((K % 1024u) ? 1u : 0u);
     const u32 RGt = (N + 15u) / 16u, ncu = (u32)cus(), W = bits == 2 ? 16u : 8u;
@@ -1541,14 +1540,14 @@ unsigned long long *g_dbg = nullptr;
 }  // namespace
 
 extern "C" void gq_debug_set_timing_buffer(void *p) { g_dbg = (unsigned long long *)p; }
-unsigned long long *gq_debug_timing_buffer() { return g_dbg; }  // (ap_stream.hip stamps into the same buffer)
-int gq_stream_gemv_try(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t M, uint32_t N, uint32_t K, int bits,
-                       const void *normw, float eps, const void *resid, int pro, int pairs, hipStream_t stream, GqHandover *ho);  // ap_stream.hip
-
+unsigned long long *gq_debug_timing_buffer() { return g_dbg; }  // (every AP-GEMV kernel file stamps into the same buffer)
 namespace {
-int plane_launch_slice(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t M, uint32_t N, uint32_t Kfull,
-                       uint32_t k0, uint32_t Ks, int bits, const void *normw, float eps, const void *resid, int pro, int pairs,
-                       hipStream_t stream, GqHandover *ho = nullptr) {
+// the columns [k0, k0 + Ks) of the launch's rows
+int plane_launch_slice(const ApLaunch &L, u32 k0, u32 Ks) {
+    const u32 M = L.M, N = L.N;
+    const int bits = L.bits, pro = L.pro;
+    const bool pairs = L.pairs;
+    GqHandover *const ho = L.ho;
     PlaneCfg c;
     // M = 2 .. 8 batch rows: up to 4 of them share ONE pass over the planes (shared-image kernel, one image per row) when the images
     // fit LDS next to the rings and the staged copy -- K <= 4096 for 4 rows, K <= 8192 for 2 --; else one block row per batch row
@@ -1576,17 +1575,17 @@ int plane_launch_slice(const void *x, void *out, const uint32_t *qweight, const 
         }
     }
     PlaneArgs a{};
-    a.qw = qweight;
-    a.lut = (const uint16_t *)lut;
-    a.x = (const uint16_t *)x + k0;
-    a.out = (uint16_t *)out;
-    a.normw = (const uint16_t *)normw;
-    a.resid = (const uint16_t *)resid;
+    a.qw = L.qweight;
+    a.lut = L.lut;
+    a.x = L.x + k0;
+    a.out = L.out;
+    a.normw = L.normw;
+    a.resid = L.resid;
     a.N = N;
     a.K = Ks;
-    a.wpr_ld = Kfull / 32u;
+    a.wpr_ld = L.K / 32u;
     a.word0 = k0 / 32u;
-    a.x_ld = pro == PRO_SILUMUL ? 2u * Kfull : Kfull;
+    a.x_ld = pro == PRO_SILUMUL ? 2u * L.K : L.K;
     a.RGB = c.RGB;
     a.log2CS = c.log2CS;
     a.cpi = c.cpi;
@@ -1602,14 +1601,10 @@ int plane_launch_slice(const void *x, void *out, const uint32_t *qweight, const 
     if (MB > 1u) {
         a.rawx = 1u;
         a.himg = 0u;
-        switch (bits) {
-            case 2: return launch_plane_rows<2>(a, c, M, stream);
-            case 3: return launch_plane_rows<3>(a, c, M, stream);
-            default: return launch_plane_rows<4>(a, c, M, stream);
-        }
+        return gq_with_bits<2, 4>(bits, [&](auto B) { return launch_plane_rows<B()>(a, c, M, L.stream); });
     }
     a.xflags = (u32)gq_env_int("GQ_PL_XFLAGS", 0);
-    a.eps = eps;
+    a.eps = L.eps;
     a.dbg = g_dbg;
     // the block's outputs in whole epilogue waves of ONE pass, one slot per wave (plane_epilogue)
     if (ho && ho->ssq_out && M == 1u && !pairs && c.RGB * 16u * (1u << bits) <= c.T && c.grid * ((c.RGB * 16u * (1u << bits)) >> 6) <= (u32)GQ_SSQ_SLOTS) {
@@ -1618,17 +1613,9 @@ int plane_launch_slice(const void *x, void *out, const uint32_t *qweight, const 
     }
     if (local) {
         a.rawx = a.himg = 0u;
-        switch (bits) {
-            case 2: return launch_local<2>(a, c, M, pro, stream);
-            case 3: return launch_local<3>(a, c, M, pro, stream);
-            default: return launch_local<4>(a, c, M, pro, stream);
-        }
+        return gq_with_bits<2, 4>(bits, [&](auto B) { return launch_local<B()>(a, c, M, pro, L.stream); });
     }
-    switch (bits) {
-        case 2: return launch_plane<2>(a, c, M, pro, stream);
-        case 3: return launch_plane<3>(a, c, M, pro, stream);
-        default: return launch_plane<4>(a, c, M, pro, stream);
-    }
+    return gq_with_bits<2, 4>(bits, [&](auto B) { return launch_plane<B()>(a, c, M, pro, L.stream); });
 }
 }  // namespace
 
@@ -1639,45 +1626,25 @@ bool gq_plane_local_shape(uint32_t N, uint32_t K, int bits) {
 }
 
 // returns GQ_ENOTSUP when the shape is not served by this path (caller falls back to the exact kernels)
-int gq_stream_gemv_ksplit(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t N, uint32_t K, int bits,
-                          const void *resid, void *ws, size_t ws_bytes, hipStream_t stream);  // ap_stream.hip
-int gq_plane_gemv_try(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t M, uint32_t N, uint32_t K,
-                      int bits, const void *normw, float eps, const void *resid, int pro, int pairs, hipStream_t stream, void *ws, size_t ws_bytes,
-                      GqHandover *ho) {
-    if (bits < 2 || bits > 4) return GQ_ENOTSUP;
-    const uint64_t qbytes = (uint64_t)bits * N * (K / 8u);
-    if (qbytes >= 0x7FFFFFFFull) return GQ_ENOTSUP;
-    if (((uintptr_t)qweight | (uintptr_t)x | (uintptr_t)normw) & 15u) return GQ_ENOTSUP;
-    // the stream kernel (ap_stream.hip) first where it measured faster (profiles/r04_stream_kernel.txt): the RMSNorm-prologue
-    // launches of the widths up to 4096 at 2 bits (8B wqkv / w1w3); GQ_ST = 0 never, 2 every shape it serves, 3 every prologue too
-    {
-        const int st = gq_env_int("GQ_ST", 1);
-        // (and the 70B attention output projection, 8192 x 8192 without a prologue: 7.6 vs 7.9 us)
-        if (st >= 3 || (st == 2 && pro == PRO_RMSNORM) || (st == 1 && pro == PRO_RMSNORM && bits == 2 && K <= 4096u) ||
-            (st == 1 && pro == PRO_NONE && !pairs && bits == 2 && K == 8192u && N >= 8192u && M == 1u) ||
-            // (round 5: and the plain launch -- the reference's own operator -- of the 8B gate / up matrix: 8.39 vs 9.26 us; wqkv, wo
-            // and w2 stay on the plane kernels: 4.95 / 4.03 / 6.44 vs 5.26 / 4.68 / 7.62.  profiles/r05_plain_launch_dispatch.txt)
-            (st == 1 && pro == PRO_NONE && bits == 2 && K <= 4096u && (uint64_t)N * K >= 100000000ull && M == 1u)) {
-            const int rc = gq_stream_gemv_try(x, out, qweight, lut, M, N, K, bits, normw, eps, resid, pro, pairs, stream, ho);
-            if (rc != GQ_ENOTSUP) return rc;
-        }
-    }
-    if (K <= 16384u) return plane_launch_slice(x, out, qweight, lut, M, N, K, 0u, K, bits, normw, eps, resid, pro, pairs, stream, ho);
+int gq_plane_gemv_try(const ApLaunch &L) {
+    if (L.bits < 2 || L.bits > 4) return GQ_ENOTSUP;
+    if (L.qbytes() >= 0x7FFFFFFFull) return GQ_ENOTSUP;
+    if (((uintptr_t)L.qweight | (uintptr_t)L.x | (uintptr_t)L.normw) & 15u) return GQ_ENOTSUP;
+    if (L.K <= 16384u) return plane_launch_slice(L, 0u, L.K);
     // 16384 < K <= 32768 (the 70B down projection): the B image of the whole row does not fit LDS, so the row is split at a
     // chunk boundary into two launches; the second adds its half to the first one's fp16 result through the residual
     // epilogue (out[n] = out[n] + y2[n], every element read and written by the same lane).  Two fp16 roundings instead
     // of one; plain and residual epilogues only.
-    if (K > 32768u || K % 256u || pro != PRO_NONE || pairs) return GQ_ENOTSUP;
-    if (ws && M == 1u) {  // with a workspace: K split over blocks, one fp16 rounding (ap_stream.hip)
-        const int rc = gq_stream_gemv_ksplit(x, out, qweight, lut, N, K, bits, resid, ws, ws_bytes, stream);
-        if (rc != GQ_ENOTSUP) return rc;
-    }
-    const uint32_t k1 = ((K / 2u + 1023u) / 1024u) * 1024u;
+    if (L.K > 32768u || L.K % 256u || L.pro != PRO_NONE || L.pairs) return GQ_ENOTSUP;
+    const uint32_t k1 = ((L.K / 2u + 1023u) / 1024u) * 1024u;
     PlaneCfg c;
-    if (!pick_plane_cfg(N, k1, bits, c) || !pick_plane_cfg(N, K - k1, bits, c)) return GQ_ENOTSUP;
-    int rc = plane_launch_slice(x, out, qweight, lut, M, N, K, 0u, k1, bits, nullptr, eps, resid, pro, 0, stream);
+    if (!pick_plane_cfg(L.N, k1, L.bits, c) || !pick_plane_cfg(L.N, L.K - k1, L.bits, c)) return GQ_ENOTSUP;
+    ApLaunch half = L;
+    half.ho = nullptr;
+    int rc = plane_launch_slice(half, 0u, k1);
     if (rc != GQ_OK) return rc;
-    rc = plane_launch_slice(x, out, qweight, lut, M, N, K, k1, K - k1, bits, nullptr, eps, out, pro, 0, stream);
+    half.resid = L.out;
+    rc = plane_launch_slice(half, k1, L.K - k1);
     if (rc == GQ_OK) gq_ap_route(GQ_AP_ROUTE_PLANE_CHAIN, 2u);  // (the two launches above: each recorded itself, and launched nothing if dry)
     return rc;
 }

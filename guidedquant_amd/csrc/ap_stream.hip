@@ -20,7 +20,7 @@
 #include <stdint.h>
 #include <type_traits>
 
-#include "gq_internal.h"
+#include "ap_dispatch.h"
 #include "plane_core.h"
 
 using namespace gqp;
@@ -65,7 +65,6 @@ struct StreamArgs {
     const float *ssq_in;
 };
 
-enum { PRO_NONE = 0, PRO_RMSNORM = 1, PRO_SILUMUL = 2 };
 constexpr u32 HOTCAP = 8u;  // Markov: |x| > 64 mean|x| holds for fewer than 512 / 64 elements of a unit
 constexpr u32 OOB = 0x80000000u;
 
@@ -1352,20 +1351,20 @@ int launch_pro(const StreamArgs &a, const StreamCfg &c, int pro, hipStream_t s) 
 }
 }  // namespace
 
-unsigned long long *gq_debug_timing_buffer();  // ap_plane.hip (gq_debug_set_timing_buffer)
-
 namespace {
 struct KSplit {
     float *part;      // [KS][N] fp32
     u32 KS, kslice;   // K = KS * kslice
 };
-int stream_launch(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t N, uint32_t K, int bits, const void *normw,
-                  float eps, const void *resid, int pro, int pairs, const StreamArgs *rope, hipStream_t stream, const KSplit *ksp = nullptr,
-                  GqHandover *ho = nullptr, AttnFuse *fuse = nullptr, bool fuse_dry = false) {
+// the launch on the stream kernel: with the RoPE epilogue's arguments (`rope`), K split over blocks (`ksp`), or the attention heads as extra
+// blocks (`fuse`; fuse_dry: only whether that form serves the shape -- no pointer of L is looked at)
+int stream_launch(const ApLaunch &L, const StreamArgs *rope, const KSplit *ksp = nullptr, AttnFuse *fuse = nullptr, bool fuse_dry = false) {
+    const u32 N = L.N, K = L.K;
+    const int bits = L.bits, pro = L.pro;
+    GqHandover *const ho = L.ho;
     if (bits < 2 || bits > gq_env_int("GQ_ST_MAXBITS", 4)) return GQ_ENOTSUP;
-    const uint64_t qbytes = (uint64_t)bits * N * (K / 8u);
-    if (qbytes >= 0x7FFFFFFFull) return GQ_ENOTSUP;
-    if (((uintptr_t)qweight | (uintptr_t)x | (uintptr_t)normw | (uintptr_t)lut) & 15u) return GQ_ENOTSUP;
+    if (L.qbytes() >= 0x7FFFFFFFull) return GQ_ENOTSUP;
+    if (L.unaligned16()) return GQ_ENOTSUP;
     StreamCfg c;
     const u32 Kk = ksp ? ksp->kslice : K;  // activations a block multiplies
     if (ksp) {
@@ -1377,12 +1376,12 @@ int stream_launch(const void *x, void *out, const uint32_t *qweight, const void 
     if (rope && c.psum) return GQ_ENOTSUP;
     StreamArgs a{};
     if (rope) a = *rope;
-    a.qw = qweight;
-    a.lut = (const uint16_t *)lut;
-    a.x = (const uint16_t *)x;
-    a.out = (uint16_t *)out;
-    a.normw = (const uint16_t *)normw;
-    a.resid = (const uint16_t *)resid;
+    a.qw = L.qweight;
+    a.lut = L.lut;
+    a.x = L.x;
+    a.out = L.out;
+    a.normw = L.normw;
+    a.resid = L.resid;
     a.N = N;
     a.K = Kk;
     a.Kx = K;
@@ -1400,8 +1399,8 @@ int stream_launch(const void *x, void *out, const uint32_t *qweight, const void 
             for (u32 i = 0; i < 5u; i++)
                 if ((1u << i) == NCU) a.lq = i;
     }
-    a.pairs = pairs ? 1u : 0u;
-    a.eps = eps;
+    a.pairs = L.pairs ? 1u : 0u;
+    a.eps = L.eps;
     a.dbg = gq_debug_timing_buffer();
     a.dbg_off = (u32)((c.smem + 15u) & ~(size_t)15u);
     if (a.dbg) {
@@ -1426,23 +1425,16 @@ int stream_launch(const void *x, void *out, const uint32_t *qweight, const void 
         if (hd == 128u) {
             static GqPerDeviceOnce once;
             GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(ap_qkv_attn_kernel<128>), (int)(160u * 1024u)));
-            hipLaunchKernelGGL(ap_qkv_attn_kernel<128>, dim3(c.grid + a.H), dim3(64u * c.W), smem, stream, a, *fuse);
+            hipLaunchKernelGGL(ap_qkv_attn_kernel<128>, dim3(c.grid + a.H), dim3(64u * c.W), smem, L.stream, a, *fuse);
         } else {
             static GqPerDeviceOnce once;
             GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(ap_qkv_attn_kernel<64>), (int)(160u * 1024u)));
-            hipLaunchKernelGGL(ap_qkv_attn_kernel<64>, dim3(c.grid + a.H), dim3(64u * c.W), smem, stream, a, *fuse);
+            hipLaunchKernelGGL(ap_qkv_attn_kernel<64>, dim3(c.grid + a.H), dim3(64u * c.W), smem, L.stream, a, *fuse);
         }
         GQ_HIP_CHECK(hipGetLastError());
         return GQ_OK;
     }
-    if (bits == 2) return launch_pro<2>(a, c, pro, stream);
-#if ST_MAXBITS >= 3
-    if (bits == 3) return launch_pro<3>(a, c, pro, stream);
-#endif
-#if ST_MAXBITS >= 4
-    if (bits == 4) return launch_pro<4>(a, c, pro, stream);
-#endif
-    return GQ_ENOTSUP;
+    return gq_with_bits<2, ST_MAXBITS>(bits, [&](auto B) { return launch_pro<B()>(a, c, pro, L.stream); });
 }
 }  // namespace
 
@@ -1501,30 +1493,48 @@ size_t gq_stream_ksplit_ws_bytes(uint32_t N, uint32_t K, int bits) {
     return ksl ? (size_t)(K / ksl) * N * 4u : 0;
 }
 // plain / residual epilogue, no prologue; GQ_ENOTSUP when the shape is not served or the workspace is too small
-int gq_stream_gemv_ksplit(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t N, uint32_t K, int bits,
-                          const void *resid, void *ws, size_t ws_bytes, hipStream_t stream) {
-    const size_t need = gq_stream_ksplit_ws_bytes(N, K, bits);
-    if (!need || !ws || ws_bytes < need || ((uintptr_t)ws & 15u) || ((uintptr_t)out & 7u) || ((uintptr_t)resid & 7u)) return GQ_ENOTSUP;
-    KSplit ks{(float *)ws, 0u, ksplit_slice(K)};
-    ks.KS = K / ks.kslice;
-    const int rc = stream_launch(x, out, qweight, lut, N, K, bits, nullptr, 0.f, nullptr, PRO_NONE, 0, nullptr, stream, &ks);
+int gq_stream_gemv_ksplit(const ApLaunch &L) {
+    const size_t need = gq_stream_ksplit_ws_bytes(L.N, L.K, L.bits);
+    if (L.pro != PRO_NONE || L.pairs || L.M != 1u) return GQ_ENOTSUP;
+    if (!need || !L.ws || L.ws_bytes < need || ((uintptr_t)L.ws & 15u) || ((uintptr_t)L.out & 7u) || ((uintptr_t)L.resid & 7u)) return GQ_ENOTSUP;
+    KSplit ks{(float *)L.ws, 0u, ksplit_slice(L.K)};
+    ks.KS = L.K / ks.kslice;
+    ApLaunch part = L;  // (the slices leave fp32 sums in the workspace: the residual is the reduction's, the hand-over nobody's)
+    part.resid = nullptr, part.ho = nullptr;
+    const int rc = stream_launch(part, nullptr, &ks);
     if (rc != GQ_OK) return rc;
     if (gq_ap_route(GQ_AP_ROUTE_STREAM_KSPLIT, 2u)) return GQ_OK;
-    hipLaunchKernelGGL(ap_ksplit_reduce_kernel, dim3((N / 4u + 256u) / 256u), dim3(256), 0, stream, (const float *)ws, (const uint16_t *)resid,
-                       (uint16_t *)out, N, ks.KS);
+    hipLaunchKernelGGL(ap_ksplit_reduce_kernel, dim3((L.N / 4u + 256u) / 256u), dim3(256), 0, L.stream, (const float *)L.ws, L.resid, L.out, L.N, ks.KS);
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
 }
 
 // returns GQ_ENOTSUP when the shape is not served by this kernel (the caller goes on to ap_plane.hip / the exact kernels)
-int gq_stream_gemv_try(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t M, uint32_t N, uint32_t K, int bits,
-                       const void *normw, float eps, const void *resid, int pro, int pairs, hipStream_t stream, GqHandover *ho) {
-    if (M != 1u) return GQ_ENOTSUP;
-    return stream_launch(x, out, qweight, lut, N, K, bits, normw, eps, resid, pro, pairs, nullptr, stream, nullptr, ho);
+int gq_stream_gemv_try(const ApLaunch &L) {
+    if (L.M != 1u) return GQ_ENOTSUP;
+    return stream_launch(L, nullptr);
 }
 
 // The fused q / k / v projection of a decode step with RoPE and the KV-cache write in its epilogue (include/gq_hip.h).
-bool gq_ap_exact_mode();  // ap_gemv.hip
+namespace {
+// the RMSNorm-prologue launch of the q / k / v matrix and the head geometry of its RoPE epilogue (the callers add the tables and the caches)
+ApLaunch qkv_launch(const void *x, void *q_out, const uint32_t *qweight, const void *lut, const void *norm_weight, uint32_t N, uint32_t K, int bits) {
+    ApLaunch L{};
+    L.x = (const uint16_t *)x, L.out = (uint16_t *)q_out, L.qweight = qweight, L.lut = (const uint16_t *)lut, L.normw = (const uint16_t *)norm_weight;
+    L.M = 1u, L.N = N, L.K = K, L.bits = bits, L.epilogue = GQ_EPI_NONE;
+    L.pro = PRO_RMSNORM, L.pairs = false;  // (the form of this entry whatever the pointers: its dry query has none)
+    return L;
+}
+StreamArgs rope_heads(uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq) {
+    StreamArgs r{};
+    r.rope = 1u;
+    r.H = n_head;
+    r.Hkv = n_kv_head;
+    r.lhd = head_dim == 128u ? 7u : 6u;
+    r.max_seq = max_seq;
+    return r;
+}
+}  // namespace
 extern "C" int gq_anyprec_qkv_rope_supported(uint32_t N, uint32_t K, int bits, uint32_t head_dim) {
     StreamCfg c;
     return bits == 2 && (head_dim == 64u || head_dim == 128u) && N % head_dim == 0u && gq_env_int("GQ_QKV_ROPE", 1) &&
@@ -1546,47 +1556,31 @@ extern "C" int gq_anyprec_gemv_qkv_rope_ho(const void *x, void *q_out, const uin
         return gq_fail(GQ_EINVAL, "null pointer argument.");
     if (N != (n_head + 2u * n_kv_head) * head_dim) return gq_fail(GQ_EINVAL, "N must be (n_head + 2 n_kv_head) * head_dim.");
     if (!gq_anyprec_qkv_rope_supported(N, K, bits, head_dim)) return gq_fail(GQ_ENOTSUP, "gq_anyprec_gemv_qkv_rope: shape / bit width not served.");
-    StreamArgs r{};
+    StreamArgs r = rope_heads(n_head, n_kv_head, head_dim, max_seq);
     r.pos = pos;
     r.cos_t = (const uint16_t *)cos_table;
     r.sin_t = (const uint16_t *)sin_table;
     r.kc = (uint16_t *)k_cache;
     r.vc = (uint16_t *)v_cache;
-    r.rope = 1u;
-    r.H = n_head;
-    r.Hkv = n_kv_head;
-    r.lhd = head_dim == 128u ? 7u : 6u;
-    r.max_seq = max_seq;
     GqHandover ho;
     ho.ssq_in = ssq_in;
+    ApLaunch L = qkv_launch(x, q_out, qweight, lut, norm_weight, N, K, bits);
+    L.eps = eps, L.stream = (hipStream_t)stream, L.ho = &ho;
     gq_ap_route(GQ_AP_ROUTE_NONE, 0u);
-    const int rc = stream_launch(x, q_out, qweight, lut, N, K, bits, norm_weight, eps, nullptr, PRO_RMSNORM, 0, &r, (hipStream_t)stream, nullptr, &ho);
+    const int rc = stream_launch(L, &r);
     return rc == GQ_ENOTSUP ? gq_fail(GQ_ENOTSUP, "gq_anyprec_gemv_qkv_rope: shape / bit width not served.") : rc;
 }
 
 // ---- round 6: the same launch with the attention heads as extra blocks (see ap_qkv_attn_kernel)
 namespace {
-int qkv_rope_attn_launch(const void *x, void *q_out, const uint32_t *qweight, const void *lut, uint32_t N, uint32_t K, int bits, const void *norm_weight,
-                         float eps, const int *pos, const void *cos_table, const void *sin_table, void *k_cache, void *v_cache, uint32_t n_head,
-                         uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, void *attn_out, float scale, uint32_t *flags, void *stream, bool dry) {
-    StreamArgs r{};
-    r.pos = pos;
-    r.cos_t = (const uint16_t *)cos_table;
-    r.sin_t = (const uint16_t *)sin_table;
-    r.kc = (uint16_t *)k_cache;
-    r.vc = (uint16_t *)v_cache;
-    r.rope = 1u;
-    r.H = n_head;
-    r.Hkv = n_kv_head;
-    r.lhd = head_dim == 128u ? 7u : 6u;
-    r.max_seq = max_seq;
+AttnFuse attn_fuse(const void *q, void *attn_out, float scale, uint32_t *flags) {
     AttnFuse f{};
-    f.q = (const uint16_t *)q_out;
+    f.q = (const uint16_t *)q;
     f.out = (uint16_t *)attn_out;
     f.flags = flags;
     f.scale = scale;
     f.spin_limit = (u32)gq_env_int("GQ_QKV_ATTN_SPINS", 1 << 21);
-    return stream_launch(x, q_out, qweight, lut, N, K, bits, norm_weight, eps, nullptr, PRO_RMSNORM, 0, &r, (hipStream_t)stream, nullptr, nullptr, &f, dry);
+    return f;
 }
 }  // namespace
 extern "C" int gq_anyprec_qkv_rope_attn_supported(uint32_t N, uint32_t K, int bits, uint32_t head_dim, uint32_t n_head, uint32_t n_kv_head) {
@@ -1595,9 +1589,9 @@ extern "C" int gq_anyprec_qkv_rope_attn_supported(uint32_t N, uint32_t K, int bi
     // after that) costs what the kernel boundary it removes costs: 8B decode 904-905 vs 909.5 tokens/s (profiles/r06_attention_in_wqkv_launch.txt)
     if (!gq_env_int("GQ_QKV_ATTN", 0) || n_kv_head == 0u || n_head % n_kv_head || N != (n_head + 2u * n_kv_head) * head_dim) return 0;
     if (!gq_anyprec_qkv_rope_supported(N, K, bits, head_dim)) return 0;
-    return qkv_rope_attn_launch(nullptr, nullptr, nullptr, nullptr, N, K, bits, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, n_head, n_kv_head,
-                                head_dim, 1u, nullptr, 0.f, nullptr, nullptr, true) == GQ_OK
-               ? 1 : 0;
+    const StreamArgs r = rope_heads(n_head, n_kv_head, head_dim, 1u);
+    AttnFuse f = attn_fuse(nullptr, nullptr, 0.f, nullptr);
+    return stream_launch(qkv_launch(nullptr, nullptr, nullptr, nullptr, nullptr, N, K, bits), &r, nullptr, &f, true) == GQ_OK ? 1 : 0;
 }
 extern "C" int gq_anyprec_gemv_qkv_rope_attn(const void *x, void *q_out, const uint32_t *qweight, const void *lut, uint32_t N, uint32_t K, int bits,
                                              const void *norm_weight, float eps, const int *pos, const void *cos_table, const void *sin_table,
@@ -1609,7 +1603,15 @@ extern "C" int gq_anyprec_gemv_qkv_rope_attn(const void *x, void *q_out, const u
     if (((uintptr_t)flags & 127u)) return gq_fail(GQ_EINVAL, "gq_anyprec_gemv_qkv_rope_attn: the flag words must be 128-byte aligned.");
     if (!gq_anyprec_qkv_rope_attn_supported(N, K, bits, head_dim, n_head, n_kv_head))
         return gq_fail(GQ_ENOTSUP, "gq_anyprec_gemv_qkv_rope_attn: shape / bit width / head geometry not served.");
-    const int rc = qkv_rope_attn_launch(x, q_out, qweight, lut, N, K, bits, norm_weight, eps, pos, cos_table, sin_table, k_cache, v_cache, n_head, n_kv_head,
-                                        head_dim, max_seq, attn_out, scale, flags, stream, false);
+    StreamArgs r = rope_heads(n_head, n_kv_head, head_dim, max_seq);
+    r.pos = pos;
+    r.cos_t = (const uint16_t *)cos_table;
+    r.sin_t = (const uint16_t *)sin_table;
+    r.kc = (uint16_t *)k_cache;
+    r.vc = (uint16_t *)v_cache;
+    AttnFuse f = attn_fuse(q_out, attn_out, scale, flags);
+    ApLaunch L = qkv_launch(x, q_out, qweight, lut, norm_weight, N, K, bits);
+    L.eps = eps, L.stream = (hipStream_t)stream;
+    const int rc = stream_launch(L, &r, nullptr, &f);
     return rc == GQ_ENOTSUP ? gq_fail(GQ_ENOTSUP, "gq_anyprec_gemv_qkv_rope_attn: shape / bit width / head geometry not served.") : rc;
 }

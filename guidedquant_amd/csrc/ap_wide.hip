@@ -20,7 +20,6 @@
 
 #include "ap_core.h"
 #include "ap_exact.h"
-#include "gq_internal.h"
 
 using namespace gq;
 
@@ -219,33 +218,14 @@ int launch_wide(const ApArgs &a, const WideCfg &c, int pro, hipStream_t s) {
 
 }  // namespace
 
-// ap_gemv.hip's dispatcher, bits 5..8: GQ_ENOTSUP where the kernel does not serve the launch (M > 1, K % 128 != 0 or K > 32768,
+// the dispatcher's rung at bits 5..8 (ap_dispatch.hip): GQ_ENOTSUP where the kernel does not serve the launch (M > 1, K % 128 != 0 or K > 32768,
 // misaligned buffers) -- the generic kernel takes the plain form of those
-int gq_ap_wide_try(const void *x, void *out, const uint32_t *qweight, const void *lut, uint32_t M, uint32_t N, uint32_t K, int bits,
-                   const void *normw, float eps, const void *resid, int pro, uint32_t epilogue, hipStream_t stream) {
-    if (bits < 5 || bits > 8 || M != 1u) return GQ_ENOTSUP;
-    if ((uint64_t)bits * N * (K / 8u) >= 0x7FFFFFFFull || (uint64_t)N * (2u << bits) >= 0x7FFFFFFFull) return GQ_ENOTSUP;
-    if ((((uintptr_t)qweight | (uintptr_t)x | (uintptr_t)normw | (uintptr_t)lut) & 15u) != 0) return GQ_ENOTSUP;
-    if ((epilogue & GQ_EPI_SILU_PAIRS) && (N & 1u)) return GQ_ENOTSUP;
+int gq_ap_wide_try(const ApLaunch &L) {
+    if (L.bits < 5 || L.bits > 8 || L.M != 1u) return GQ_ENOTSUP;
+    if (L.qbytes() >= 0x7FFFFFFFull || (uint64_t)L.N * (2u << L.bits) >= 0x7FFFFFFFull) return GQ_ENOTSUP;
+    if (L.unaligned16()) return GQ_ENOTSUP;
+    if (L.pairs && (L.N & 1u)) return GQ_ENOTSUP;
     WideCfg c;
-    if (!wide_plan(N, K, bits, c)) return GQ_ENOTSUP;
-    ApArgs a{};
-    a.qw = qweight;
-    a.lut = (const uint16_t *)lut;
-    a.x = (const uint16_t *)x;
-    a.out = (uint16_t *)out;
-    a.normw = (const uint16_t *)normw;
-    a.resid = (const uint16_t *)resid;
-    a.eps = eps;
-    a.N = N;
-    a.K = K;
-    a.RS = c.RS;
-    a.SPB = c.SPB;
-    a.epilogue = epilogue;
-    switch (bits) {
-        case 5: return launch_wide<5>(a, c, pro, stream);
-        case 6: return launch_wide<6>(a, c, pro, stream);
-        case 7: return launch_wide<7>(a, c, pro, stream);
-        default: return launch_wide<8>(a, c, pro, stream);
-    }
+    if (!wide_plan(L.N, L.K, L.bits, c)) return GQ_ENOTSUP;
+    return gq_with_bits<5, 8>(L.bits, [&](auto B) { return launch_wide<B()>(ap_args(L, c.RS, c.SPB), c, L.pro, L.stream); });
 }

@@ -21,7 +21,7 @@ struct GqHandover {
     bool ssq_consumed = false;  // the GEMV kernel's RMSNorm prologue reads ssq_in
 };
 
-// The route record of the AP-GEMV dispatch (include/gq_hip.h: gq_debug_ap_last_route, ap_gemv.hip).  Every terminal launch site of the
+// The route record of the AP-GEMV dispatch (include/gq_hip.h: gq_debug_ap_last_route, ap_dispatch.hip).  Every terminal launch site of the
 // dispatch calls gq_ap_route right in front of its launch, and launches nothing when it returns true: the dispatch is a dry run
 // (gq_anyprec_handover_plan, gq_debug_ap_plan_route), which takes every decision a real one takes.
 bool gq_ap_route(uint32_t family, uint32_t launches, uint32_t variant = 0u);

@@ -348,7 +348,7 @@ def test_multi_batch_plain_launch_across_ring_depths(oracle, bits, D):
 # ------------------------------------------------------------------------------------------------ 3. the default dispatch
 @pytest.mark.parametrize("N,K,bits", [(3072, 2048, 2), (3072, 2048, 3), (3072, 2048, 4), (2048, 4096, 4), (2048, 2048, 3), (4096, 2048, 3)])
 def test_default_dispatch_small_matrices_are_reference_exact(N, K, bits):
-    """matrices below the plane and dq thresholds (ap_gemv.hip, ap_gemv_dispatch_inner) run the exact kernel in the default mode
+    """matrices below the plane and dq thresholds (ap_dispatch.hip, ap_serve) run the exact kernel in the default mode
     too: Llama-3.2-1B's wqkv, a 4-bit 2048 x 4096, 3-bit matrices under 16 M weights -- every fused form bit-identical to exact mode,
     which is the reference chain"""
     from guidedquant_amd import _lib

@@ -86,7 +86,7 @@ def test_rmsnorm_prologue_default_dispatch_equals_unfused_chain(oracle, bits, N,
     assert (xn.view(np.uint16) != rmsnorm_ref(x, nw, EPS).view(np.uint16)).sum() <= 4  # torch on the GPU vs the numpy restatement
     plain = run_fused(xn, q, lut, bits, expect=("stream" if N * K >= 100e6 else "plane") if bits == 2 else "dq")
     rows = _rows(rng, N, 32)
-    # which kernel family the default dispatch picks (ap_gemv.hip): behind the RMSNorm prologue the plane-MFMA kernel from 20 M weights
+    # which kernel family the default dispatch picks (ap_dispatch.hip): behind the RMSNorm prologue the plane-MFMA kernel from 20 M weights
     # at every width (round 5); the plain launch from 20 M at 2 bits, 32 M at 3 / 4 bits -- below that the exact kernel
     # (round 6: at 4 bits every launch from 20 M weights runs the decode-to-fp16 matrix-core kernel, ap_gemv_dq_kernel -- a fast-mode kernel)
     # (and from 16 M weights at 3 and 4 bits -- 3 bits: below 32 M, where the plane kernel takes over: fast-mode kernels either way)
