@@ -385,8 +385,9 @@ class AnyPrecisionForCausalLM(nn.Module):
                     dec = None  # (automatic route: transformers' generate decides what a request beyond the context means)
                 from ._lib import SAMPLER_MAX_VOCAB
                 if dec is not None and dec.config.vocab_size > SAMPLER_MAX_VOCAB:
-                    # (the captured step ends in the fused sampler: 128 blocks x 1024 logits.  Qwen3's published vocabulary, 151936, is
-                    # beyond it -- such a checkpoint keeps `native_decoder()` / `decode_native` / `prefill_native`, not this route)
+                    # (the captured step ends in the fused sampler: 128 blocks x 2048 logits at the most.  Qwen3's published vocabulary,
+                    # 151936, is within it; a checkpoint beyond 262144 keeps `native_decoder()` / `decode_native` / `prefill_native`,
+                    # not this route)
                     if native is True:
                         raise ValueError(f"native=True: vocabulary {dec.config.vocab_size} exceeds the fused sampler's {SAMPLER_MAX_VOCAB}")
                     dec = None

@@ -638,6 +638,8 @@ __global__ void __launch_bounds__(HD) attn_combine_kernel(const float *ws, uint1
 // Two launches: per-block candidates, then a single-block merge.  Writes the next token AND feeds it back into
 // `tok_io` / increments `pos_io` so a captured graph advances by itself.
 constexpr int SAMP_BLOCKS = 128, SAMP_K = 64;  // (the kernels are built for 32 and for 64 candidates per block)
+constexpr u32 SAMP_MAX_VOCAB = GQ_SAMPLER_MAX_VOCAB;  // SAMP_BLOCKS slices of <= 2048 logits (the wide instance; <= 131072: slices of <= 1024)
+static_assert(SAMP_MAX_VOCAB == 2048u * SAMP_BLOCKS, "the wide instance's slice");
 static_assert(GQ_SSQ_SLOTS == 1024, "sample_stage2 writes one hand-over slot per thread");
 
 __device__ __forceinline__ u32 hash32(u32 x) {
@@ -655,14 +657,17 @@ __device__ __forceinline__ uint16_t unordered_key16(u32 o) { return (o & 0x8000u
 // scalar population counts -- no LDS, no barrier (the block-wide version above pays a 1024-thread barrier per bit: 13 us
 // for 33 bits).  Two levels of it replace a block-wide search: every wave keeps its own top K (a global top-K key is in
 // the top K of its wave), one wave then searches the survivors.
-// The low `lowbits` bits of a key are the tie-breaking position: they are searched only when the value bits leave more than
+// The low LOWBITS bits of a key are the tie-breaking position: they are searched only when the value bits leave more than
 // K keys at the threshold (rare), which halves the rounds.
-template <int EPT, typename KeyT>
-__device__ __forceinline__ KeyT wave_select_threshold(const KeyT (&key)[EPT], int nbits, int lowbits, int K) {
+// (The key widths are template parameters, not arguments: the sampler has two instances of them, and as arguments they would share
+// one function between the instances -- the compiler then no longer sees them as constants of that function, and the code of the
+// narrow kernels changes although their source does not.  ISA diffed: with the parameters the narrow kernels are unchanged.)
+template <int EPT, typename KeyT, int NBITS, int LOWBITS>
+__device__ __forceinline__ KeyT wave_select_threshold(const KeyT (&key)[EPT], int K) {
     KeyT t = 0;
     int ct = 0x7FFFFFFF;  // count of keys >= t
-    for (int bit = nbits - 1; bit >= 0; bit--) {
-        if (bit == lowbits - 1 && ct == K) break;  // exactly K keys carry a value >= the threshold value: no tie to break
+    for (int bit = NBITS - 1; bit >= 0; bit--) {
+        if (bit == LOWBITS - 1 && ct == K) break;  // exactly K keys carry a value >= the threshold value: no tie to break
         const KeyT cand = t | ((KeyT)1 << bit);
         int c = 0;
 #pragma unroll
@@ -735,12 +740,17 @@ __device__ __forceinline__ void sample_embed(int chosen, u32 tid, const SampleEx
     if (ex.ssq_out) gq_store_wt(ex.ssq_out + tid, acc);  // (1024 threads = GQ_SSQ_SLOTS)
 }
 
-// stage 1: each of the 128 blocks selects the top KM of its slice (<= 1024 logits, 4 per thread in registers); KM = 32 or 64
-template <int KM>
+// stage 1: each of the 128 blocks selects the top KM of its slice (<= 256 * EPT logits, EPT per thread in registers); KM = 32 or 64.
+// Two instances of the widths: EPT = 4, LB = 10 (slices of <= 1024: vocab <= 131072) and EPT = 8, LB = 11 (slices of <= 2048: vocab <=
+// 262144).  The grid is SAMP_BLOCKS either way -- the callers' work areas are 128 * KM words -- so a wider vocabulary is a longer slice.
+// key = (order-preserving image of the fp16 logit) << LB | (2^LB - 1 - position in the slice): 16 + LB bits.
+template <int KM, int EPT, int LB>
 __global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32 V, float *cand_val, int *cand_idx, const int *ban, const int *pos_io) {
+    static_assert(256 * EPT == 1 << LB && 16 + LB <= 32, "a slice is one position per key of the block; the key is a u32");
+    constexpr u32 LMASK = (1u << LB) - 1u;
     __shared__ u32 surv[4 * KM];
     __shared__ u32 fin[KM];
-    const u32 per = (V + SAMP_BLOCKS - 1) / SAMP_BLOCKS;  // <= 1024
+    const u32 per = (V + SAMP_BLOCKS - 1) / SAMP_BLOCKS;  // <= 256 * EPT
     const u32 lo = blockIdx.x * per, hi = min(lo + per, V);
     const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
     int nban = 0, bid[4] = {-1, -1, -1, -1};
@@ -750,40 +760,43 @@ __global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32
 #pragma unroll
         for (int i = 0; i < 4; i++) bid[i] = i < nban ? ban[2 + i] : -1;
     }
-    u32 key[4];
+    u32 key[EPT];
 #pragma unroll
-    for (int e = 0; e < 4; e++) {
-        const u32 li = tid * 4u + (u32)e, gi = lo + li;
+    for (int e = 0; e < EPT; e++) {
+        const u32 li = tid * (u32)EPT + (u32)e, gi = lo + li;
         // key = (order-preserving image of the fp16 logit, position): unique, and both parts are recovered from it
         const bool banned = (int)gi == bid[0] || (int)gi == bid[1] || (int)gi == bid[2] || (int)gi == bid[3];
-        key[e] = (gi < hi && !banned) ? ((ordered_key16(logits[gi]) << 10) | (1023u - li)) : 0u;
+        key[e] = (gi < hi && !banned) ? ((ordered_key16(logits[gi]) << LB) | (LMASK - li)) : 0u;
     }
     if (l < KM / 2) reinterpret_cast<unsigned long long *>(surv + w * KM)[l] = 0ull;  // (a wave's LDS ops are in order)
-    const u32 t = wave_select_threshold<4, u32>(key, 26, 10, KM);
-    wave_compact<4, u32>(key, t, surv + w * KM, KM, l);
+    const u32 t = wave_select_threshold<EPT, u32, 16 + LB, LB>(key, KM);
+    wave_compact<EPT, u32>(key, t, surv + w * KM, KM, l);
     __syncthreads();
     if (w == 0) {  // top KM of the 4 * KM survivors
         u32 k2[KM / 16];
 #pragma unroll
         for (int e = 0; e < KM / 16; e++) k2[e] = surv[(u32)e * 64u + l];
-        const u32 t2 = wave_select_threshold<KM / 16, u32>(k2, 26, 10, KM);
+        const u32 t2 = wave_select_threshold<KM / 16, u32, 16 + LB, LB>(k2, KM);
         if (l < KM) fin[l] = 0u;
         const int n = wave_compact<KM / 16, u32>(k2, t2, fin, KM, l);
         if (l < KM) {
             const u32 k = fin[l];
             const bool ok = (int)l < n && k != 0u;
-            const u32 li = 1023u - (k & 1023u);
-            cand_val[blockIdx.x * KM + l] = ok ? h2f(unordered_key16(k >> 10)) : -3.0e38f;  // slice shorter than K: padded
+            const u32 li = LMASK - (k & LMASK);
+            cand_val[blockIdx.x * KM + l] = ok ? h2f(unordered_key16(k >> LB)) : -3.0e38f;  // slice shorter than K: padded
             cand_idx[blockIdx.x * KM + l] = ok ? (int)(lo + li) : -1;
         }
     }
 }
 
-// stage 2: one block, 128 * KM candidates (KM / 8 per thread), select the global top-k, then the exponential-race draw
-template <int KM>
+// stage 2: one block, 128 * KM candidates (KM / 8 per thread), select the global top-k, then the exponential-race draw.
+// key = (order-preserving image of the fp16 value) << IB | (2^IB - 1 - token id): IB = 17 (vocab <= 131072) or 18 (<= 262144); everything
+// behind the selection sees token ids only and is the same in both instances.
+template <int KM, int IB>
 __global__ void __launch_bounds__(1024) sample_stage2(const float *cand_val, const int *cand_idx, int top_k, float temperature,
                                                       u32 seed, int *counter, int *tok_io, int *pos_io, int *next_tok, SampleEx ex) {
     constexpr int EPT = KM / 8;  // candidates per thread
+    constexpr u32 IMASK = (1u << IB) - 1u;
     __shared__ float selv[KM];
     __shared__ int seli[KM];
     __shared__ unsigned long long surv[16 * KM];
@@ -797,25 +810,25 @@ __global__ void __launch_bounds__(1024) sample_stage2(const float *cand_val, con
         const float v = cand_val[c];
         const int id = cand_idx[c];
         const uint16_t hb = __builtin_bit_cast(uint16_t, (h16)v);  // candidates are fp16 values: exact
-        key[e] = id >= 0 ? (((unsigned long long)ordered_key16(hb) << 17) | (unsigned long long)(131071u - (u32)id)) : 0ull;
+        key[e] = id >= 0 ? (((unsigned long long)ordered_key16(hb) << IB) | (unsigned long long)(IMASK - (u32)id)) : 0ull;
     }
     const int K = top_k < 1 ? 1 : (top_k > KM ? KM : top_k);
     if (l < KM) surv[w * KM + l] = 0ull;
-    const unsigned long long t = wave_select_threshold<EPT, unsigned long long>(key, 33, 17, K);
+    const unsigned long long t = wave_select_threshold<EPT, unsigned long long, 16 + IB, IB>(key, K);
     wave_compact<EPT, unsigned long long>(key, t, surv + w * KM, KM, l);
     __syncthreads();
     if (w == 0) {
         unsigned long long k8[KM / 4];
 #pragma unroll
         for (int e = 0; e < KM / 4; e++) k8[e] = surv[(u32)e * 64u + l];
-        const unsigned long long t2 = wave_select_threshold<KM / 4, unsigned long long>(k8, 33, 17, K);
+        const unsigned long long t2 = wave_select_threshold<KM / 4, unsigned long long, 16 + IB, IB>(k8, K);
         if (l < KM) fin[l] = 0ull;
         const int n2 = wave_compact<KM / 4, unsigned long long>(k8, t2, fin, KM, l);
         if (l == 0) slot = n2;
         if (l < KM) {
             const unsigned long long k = fin[l];
-            selv[l] = h2f(unordered_key16((u32)(k >> 17)));
-            seli[l] = (int)(131071u - (u32)(k & 131071ull));
+            selv[l] = h2f(unordered_key16((u32)(k >> IB)));
+            seli[l] = (int)(IMASK - ((u32)k & IMASK));
         }
     }
     __syncthreads();
@@ -1163,20 +1176,28 @@ extern "C" int gq_dense_gemv_f16(const void *x, const void *W, void *out, uint32
 }
 
 namespace {
+// the pair of one width (logits per thread, local-position bits, token-id bits): candidates per block by top_k
+template <int EPT, int LB, int IB>
+void sample_launch_w(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter, float *work_val, int *work_idx,
+                     int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, hipStream_t s) {
+    if (top_k <= 32) {
+        hipLaunchKernelGGL((sample_stage1<32, EPT, LB>), dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban, pos_io);
+        hipLaunchKernelGGL((sample_stage2<32, IB>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex);
+    } else {
+        hipLaunchKernelGGL((sample_stage1<64, EPT, LB>), dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban, pos_io);
+        hipLaunchKernelGGL((sample_stage2<64, IB>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex);
+    }
+}
 int sample_launch(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter, float *work_val, int *work_idx,
                   int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, void *stream) {
     if (!logits || !counter || !work_val || !work_idx || !next_tok) return gq_fail(GQ_EINVAL, "null pointer argument.");
     if (top_k > SAMP_K) return gq_fail(GQ_ENOTSUP, "top_k > 64 is not supported by the fused sampler.");
-    const u32 per = (vocab + SAMP_BLOCKS - 1) / SAMP_BLOCKS;
-    if (per > 1024u || vocab > 131072u) return gq_fail(GQ_ENOTSUP, "vocab too large for the fused sampler (<= 131072).");
+    if (vocab > SAMP_MAX_VOCAB) return gq_fail(GQ_ENOTSUP, "vocab too large for the fused sampler (<= 262144).");
     hipStream_t s = (hipStream_t)stream;
-    if (top_k <= 32) {
-        hipLaunchKernelGGL(sample_stage1<32>, dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban, pos_io);
-        hipLaunchKernelGGL(sample_stage2<32>, dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex);
-    } else {
-        hipLaunchKernelGGL(sample_stage1<64>, dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban, pos_io);
-        hipLaunchKernelGGL(sample_stage2<64>, dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex);
-    }
+    if (vocab <= 131072u)  // slices of <= 1024 logits, 17-bit token ids
+        sample_launch_w<4, 10, 17>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, s);
+    else  // slices of <= 2048 logits through the same 128 blocks, 18-bit token ids
+        sample_launch_w<8, 11, 18>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, s);
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
 }

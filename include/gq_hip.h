@@ -534,7 +534,12 @@ int gq_dense_gemv_f16(const void *x, const void *W, void *out, uint32_t N, uint3
 /* Top-k sampling with the reference's distribution (inference/generate.py:53-73: logits / max(T,1e-5), top-k, softmax,
  * exponential-race draw).  work_val / work_idx: 128*32 floats / ints of scratch; counter: one int of RNG state in
  * device memory (incremented per call).  If tok_io / pos_io are non-NULL the sampled token is written to *tok_io and
- * *pos_io is incremented, so a captured decode graph advances by itself.  top_k <= 32. */
+ * *pos_io is incremented, so a captured decode graph advances by itself.  top_k <= 32.
+ * vocab <= GQ_SAMPLER_MAX_VOCAB (all three entry points; beyond it: GQ_ENOTSUP).  The grid is 128 blocks and the work buffers are
+ * 128 * 32 (128 * 64) elements at every width: up to 131072 logits a block takes a slice of at most 1024, from there to 262144 -- the
+ * published Qwen3 vocabulary is 151936 -- a slice of at most 2048 (a second pair of kernel instances; ban ids, seq_out and the embedding
+ * row take token ids of the whole range). */
+#define GQ_SAMPLER_MAX_VOCAB 262144
 int gq_sample_topk(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter,
                    float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, void *stream);
 /* Round 5: the same draw with up to 64 candidates (work_val / work_idx: 128 * 64 elements) and three optional extras for a decode

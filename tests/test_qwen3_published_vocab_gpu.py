@@ -1,0 +1,125 @@
+"""GPU, end to end: an Any-Precision Qwen3 checkpoint with the PUBLISHED vocabulary (151936 logits, EOS ids above 2^17) through
+`AnyPrecisionForCausalLM.generate` -- the captured decode step ends in the wide instance of the fused sampler (csrc/decode.hip), so the
+plain call takes the fused route, `native=True` is served, sampled calls and EOS suppression work with token ids beyond 131072, and a
+DecodeGraph with several steps per replay and the embedding folded into the sampler decodes what single steps decode."""
+import pytest
+
+torch = pytest.importorskip("torch")
+transformers = pytest.importorskip("transformers")
+pytestmark = pytest.mark.gpu
+
+VOCAB, EOS = 151936, 151645
+_NAMES = ["self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"]
+
+
+def _hf_model(cfg, seed=5):
+    """as test_qwen3_fused_gpu.py::_hf_model: 2-bit planes only, embeddings / lm_head scaled for margins, q_norm / k_norm weights far from 1"""
+    from guidedquant_amd.AnyPrecisionForCausalLM import AnyPrecisionForCausalLM
+    cfg.anyprec = dict(seed_precision=2, parent_precision=2, group_count=1, arch_config=dict(module_names=_NAMES, model_name="model", layers_name="layers"))
+    m = AnyPrecisionForCausalLM.from_config_random(cfg, device=torch.device("cuda:0"), seed=seed)
+    g = torch.Generator(device=m.device)
+    g.manual_seed(seed + 1)
+    with torch.no_grad():
+        m.model.model.embed_tokens.weight.mul_(25.0)
+        m.model.lm_head.weight.mul_(10.0)
+        for layer in m.get_model_layers():
+            for n in ("q_norm", "k_norm"):
+                w = getattr(layer.self_attn, n, None)
+                if w is not None:
+                    w.weight.copy_((1 + 0.3 * torch.randn(w.weight.shape, device=m.device, generator=g)).half())
+    return m
+
+
+@pytest.fixture(scope="module")
+def model():
+    """the tiny checkpoint, with EOS made the arg-max of the first new token: its lm_head row is 1.5 x the row of the token transformers'
+    greedy route draws there (done before any fused form of the model exists)"""
+    from guidedquant_amd import _lib
+    # (hidden 512, not 256: the fused step's lm_head GEMV, gq_dense_gemv_f16, takes K % 512 == 0 -- the smallest width the route serves)
+    m = _hf_model(transformers.Qwen3Config(hidden_size=512, intermediate_size=1024, num_hidden_layers=1, num_attention_heads=8, num_key_value_heads=2,
+                                           head_dim=64, vocab_size=VOCAB, max_position_embeddings=256, rms_norm_eps=1e-6, tie_word_embeddings=False))
+    ids = _ids(m)
+    with torch.no_grad():
+        lg = m.model(ids).logits[0, -1].float()
+        first = int(lg.argmax())
+        assert first != EOS and float(lg[first]) > 1.0
+        head = m.model.lm_head.weight
+        head[EOS].copy_((head[first].float() * 1.5).half())
+        assert int(m.model(ids).logits[0, -1].float().argmax()) == EOS
+    assert not any(k[0] in ("decoder", "graph") for k in m._native_cache)
+    m.first_free_token = first
+    yield m
+    m._evict("graph")
+    m._evict("cap")
+    _lib.lib().gq_set_ap_mode(-1)
+
+
+def _ids(m):
+    return torch.tensor([[3, 17, 140000, 60, 151643, 9]], device=m.device)  # (prompt ids on both sides of 2^17)
+
+
+def test_plain_generate_takes_the_fused_route_and_agrees_with_transformers(model):
+    m, ids = model, _ids(model)
+    assert VOCAB <= __import__("guidedquant_amd")._lib.SAMPLER_MAX_VOCAB
+    plain = m.generate(ids, max_new_tokens=8, do_sample=False, pad_token_id=0)
+    assert any(k[0] == "graph" for k in m._native_cache) and ("decoder", 2) in m._native_cache  # route 1, taken automatically
+    assert m._native_cache[("decoder", 2)].config.vocab_size == VOCAB
+    eager = m.generate(ids, max_new_tokens=8, do_sample=False, native=False, pad_token_id=0)
+    assert plain.shape == eager.shape == (1, 14) and plain.dtype == ids.dtype
+    assert torch.equal(plain, eager), (plain, eager)
+    assert int(plain[0, 6]) == EOS and int(plain[0, 6:].max()) < VOCAB and int(plain[0, 6:].min()) >= 0  # (an id beyond 2^17 is drawn and fed back)
+    forced = m.generate(ids, max_new_tokens=8, do_sample=False, native=True, pad_token_id=0)  # (raised "vocabulary ..." before)
+    assert torch.equal(forced, plain)
+
+
+def test_the_captured_module_tree_route_ends_in_the_sampler_at_this_width(model):
+    m, ids = model, _ids(model)
+    ref = m.generate(ids, max_new_tokens=8, do_sample=False, native=False, pad_token_id=0)  # (first: the module tree takes back what native=True released)
+    cap = m.generate(ids, max_new_tokens=8, do_sample=False, native=False, capture=True, pad_token_id=0)
+    assert any(k[0] == "cap" for k in m._native_cache)
+    assert torch.equal(cap, ref) and int(cap[0, 6]) == EOS
+
+
+def test_sampled_calls_are_reproducible_and_eos_beyond_131072_is_suppressed(model):
+    m, ids = model, _ids(model)
+    kw = dict(max_new_tokens=16, do_sample=True, top_k=50, top_p=0.9, pad_token_id=0, native=True)
+    torch.manual_seed(21)
+    a = m.generate(ids, **kw)
+    b = m.generate(ids, **kw)
+    torch.manual_seed(21)
+    a2 = m.generate(ids, **kw)
+    assert torch.equal(a, a2) and a.shape == b.shape == (1, 22)
+    assert int(a.max()) < VOCAB and int(b.max()) < VOCAB and int(a.min()) >= 0
+    # EOS (151645) is the arg-max of the first new token (the fixture): drawn at once without min_new_tokens, held back with them
+    now = m.generate(ids, max_new_tokens=12, do_sample=False, eos_token_id=EOS, pad_token_id=0)
+    assert now.shape == (1, 7) and int(now[0, 6]) == EOS, now
+    held = m.generate(ids, max_new_tokens=12, min_new_tokens=6, do_sample=False, eos_token_id=EOS, pad_token_id=0)
+    assert held.shape[1] >= 6 + 6 and EOS not in held[0, 6:12].tolist() and int(held[0, 6]) == m.first_free_token, held
+    torch.manual_seed(5)
+    smp = m.generate(ids, max_new_tokens=12, min_new_tokens=6, do_sample=True, top_k=50, top_p=0.9, eos_token_id=EOS, pad_token_id=0)
+    assert smp.shape[1] >= 6 + 6 and EOS not in smp[0, 6:12].tolist() and int(smp.max()) < VOCAB, smp
+    assert any(k[0] == "graph" for k in m._native_cache)
+
+
+def test_decode_graph_with_four_steps_per_replay_and_the_embedding_folded_in(model):
+    from guidedquant_amd.generate import DecodeGraph
+    m = model
+    dec = m.native_decoder(2)
+    dec.setup_caches(1, 64)
+    assert dec.native_ready() and dec.config.vocab_size == VOCAB
+    seqs = []
+    for spr in (1, 4):
+        for b in dec.layers:
+            b.attention.kv_cache.k_cache.zero_()
+            b.attention.kv_cache.v_cache.zero_()
+        g = DecodeGraph(dec, m.device, native_sampling=True, temperature=0.0, top_k=32, seq_capacity=65, steps_per_replay=spr, fold_embed=True)
+        assert g.native_sampling and g.steps_per_replay == spr
+        g.set_token(140000, 0)
+        for _ in range(24 // spr):
+            g.step()
+        torch.cuda.synchronize()
+        assert int(g.pos.item()) == 24
+        seqs.append(g.seq[1:25].tolist())
+        g.close() if hasattr(g, "close") else None
+    assert seqs[0] == seqs[1], seqs
+    assert all(0 <= t < VOCAB for t in seqs[0])

@@ -9,10 +9,12 @@ restated), three things on one box in one run:
 
 The Qwen3-8B figures (36 layers, hidden 4096, MLP 12288, 32 / 8 heads of 128, vocab 151936, rope_theta 1e6, eps 1e-6) restate the public
 config from memory; they could not be checked offline and matter here only as a shape set (guidedquant_amd.model.transformer_configs).
-The captured step ends in the fused sampler, which serves at most 131072 logits: all three legs run the Qwen3 geometry with the
-vocabulary cut to that (`vocab_size_timed` in the record).
+The captured step ends in the fused sampler, which serves up to 262144 logits: all three legs run the Qwen3 geometry at its published
+vocabulary, 151936 (`vocab_size_timed` in the record: the vocabulary the timed model has; a table entry beyond the sampler's limit
+would be cut to it).
 
-Prints one JSON record and merges it into profiles/qwen3_fused_route.json under "timing" (other keys of that file are kept).
+Prints one JSON record and merges it into profiles/qwen3_fused_route.json under "timing_published_vocab" (other keys of that file are
+kept: "timing" is the record taken while the sampler stopped at 131072 logits, with Qwen3's vocabulary cut to that).
     python tools/qwen3_decode_timing.py [--steps 20] [--warmup 5] [--repeats 3] [--no-module-tree]
 """
 import argparse
@@ -30,8 +32,8 @@ OUT = os.path.join(ROOT, "profiles", "qwen3_fused_route.json")
 
 
 def timed_config(name):
-    """the table entry, with the vocabulary cut to what the fused sampler at the end of the captured step serves (Qwen3's 151936 -> 131072:
-    the lm_head GEMV of the timed model is 14 % smaller than the published model's)"""
+    """the table entry; a vocabulary beyond what the fused sampler at the end of the captured step serves (262144) would be cut to that --
+    Qwen3's 151936 and Llama's 128256 are timed as published"""
     from guidedquant_amd._lib import SAMPLER_MAX_VOCAB
     from guidedquant_amd.model import transformer_configs
     c = dict(transformer_configs[name])
@@ -121,7 +123,7 @@ def main():
     if os.path.exists(OUT):
         with open(OUT) as f:
             whole = json.load(f)
-    whole["timing"] = rec
+    whole["timing_published_vocab"] = rec
     with open(OUT, "w") as f:
         json.dump(whole, f, indent=1)
         f.write("\n")
