@@ -23,9 +23,7 @@ front of the rotation, modeling_qwen3.Qwen3Attention.forward): in `Attention.for
 Model table: the reference's entries (model.py:53-61) plus Llama-3.2-1B-Instruct and Llama-3.3-70B-Instruct, which
 BASELINE.json's configs name and the reference table lacks.
 """
-import ctypes
 import math
-import os
 from dataclasses import dataclass
 from typing import Optional
 
@@ -34,7 +32,7 @@ import torch.nn as nn
 from torch import Tensor
 from torch.nn import functional as F
 
-from . import _lib
+from . import _lib, native_step
 
 
 def find_multiple(n: int, k: int) -> int:
@@ -397,6 +395,7 @@ class Transformer(nn.Module):
         return self.output(x)
 
     # ------------------------------------------------------------------------------------------ fused HIP decode step
+    # (guidedquant_amd/native_step.py: the buffers, launch plans and launches; here its surface on the model)
     def native_ready(self) -> bool:
         return self._native_kind() is not None
 
@@ -418,7 +417,7 @@ class Transformer(nn.Module):
             if all(isinstance(m, APLinear) and m.bias is None and m.bitwidth <= 8 and m.in_features % 128 == 0
                    for b in self.layers for m in (b.attention.wqkv, b.attention.wo, b.feed_forward.w1w3, b.feed_forward.w2)):
                 kind = "ap"
-        elif os.environ.get("GQ_NATIVE_QTIP", "1") != "0":
+        elif native_step.native_qtip():
             from .qtip import QuantizedLinear
 
             p2 = lambda n: n > 0 and (n & (n - 1)) == 0  # noqa: E731
@@ -439,469 +438,27 @@ class Transformer(nn.Module):
         return kind or None
 
     def _native_state(self):
+        """buffers and launch plans of the step (native_step.ApStep / QtipStep), built on first use; subscriptable by field name"""
         if self._native is None:
-            dev = self.output.weight.device
-            c = self.config
-            f16 = dict(dtype=torch.float16, device=dev)
-            self._native = dict(
-                x=torch.zeros(c.dim, **f16), h=torch.zeros(c.dim, **f16), y=torch.zeros(c.n_head * c.head_dim, **f16),
-                qkv=torch.zeros((c.n_head + 2 * c.n_local_heads) * c.head_dim, **f16),
-                ssq=torch.zeros(_lib.SSQ_SLOTS, dtype=torch.float32, device=dev),  # statistics hand-over slots (gq_hip.h GQ_SSQ_SLOTS)
-                # one flag line per query head for the attention heads that run inside the wqkv launch (gq_anyprec_gemv_qkv_rope_attn:
-                # zero between launches; one buffer for all layers)
-                attn_flags=torch.zeros(c.n_head * _lib.ATTN_FLAG_STRIDE, dtype=torch.int32, device=dev),
-                gu=torch.zeros(2 * c.intermediate_size, **f16), logits=torch.zeros(1, 1, c.vocab_size, **f16))
-            # long caches: split-KV attention (gq_attn_decode_split), n_split blocks per head + a combine launch; a context of
-            # up to 256 positions is still finished by one block per head at run time
-            S = self.max_seq_length
-            ns = 1 if S <= 1024 else (4 if S <= 2048 else 8)
-            # grouped-query models whose wqkv launch rotates q / k (gq_attn_decode_roped): the four query heads of a KV group share a
-            # block, so the splits can be as short as one 128-position pass -- n_kv_head x n_split blocks ~ one per CU
-            l0 = self.layers[0].attention
-            # (not for QK-norm models: their wqkv launch never rotates, see native_layers)
-            if (S > 1024 and c.n_head % (4 * c.n_local_heads) == 0 and self._native_kind() != "qtip" and os.environ.get("GQ_ATTN_GQA", "1") != "0"
-                    and not c.qk_norm and _lib.lib().gq_anyprec_qkv_rope_supported(l0.wqkv.out_features, c.dim, l0.wqkv.bitwidth, c.head_dim)):
-                ns = max(4, min(32, (S + 127) // 128, 256 // max(1, c.n_head // 4)))
-            ns = int(os.environ.get("GQ_ATTN_SPLIT", ns))
-            self._native["attn_split"] = ns
-            self._native["attn_ws"] = torch.zeros(c.n_head * ns * (c.head_dim + 2), dtype=torch.float32, device=dev) if ns > 1 else None
-            # Gate/up pairing (GQ_EPI_SILU_PAIRS): every fused w1w3 tensor is re-ordered in place to (gate_0, up_0, gate_1,
-            # up_1, ..) rows so that the w1w3 GEMV writes silu(gate) * up directly (model.py:266 of the reference) and w2
-            # reads a plain vector; state_dict() still exports the reference layout (pair_gate_up_rows_).
-            self._native["pairs"] = False
-            self._native["ap_ws"] = None
-            if self._native_kind() == "qtip":
-                self._native_qtip_state(self._native)
-            else:
-                # workspace of the down projection where the library splits its rows along K over blocks (K > 16384: 70B)
-                wb = max(int(_lib.lib().gq_anyprec_gemv_fused_ws_bytes(c.dim, c.intermediate_size, b.feed_forward.w2.bitwidth, 1)) for b in self.layers)
-                if wb:
-                    self._native["ap_ws"] = torch.zeros(wb // 4, dtype=torch.float32, device=dev)
-            if self._native_kind() == "qtip":
-                pass
-            elif os.environ.get("GQ_NATIVE_PAIRS", "1") != "0":
-                for b in self.layers:
-                    pair_gate_up_rows_(b.feed_forward.w1w3)
-                self._native["pairs"] = True
-            else:
-                assert not any(getattr(b.feed_forward.w1w3, "gq_row_pairs", False) for b in self.layers), \
-                    "GQ_NATIVE_PAIRS=0 on a model whose gate/up rows were already paired"
+            self._native = (native_step.QtipStep if self._native_kind() == "qtip" else native_step.ApStep)(self)
         return self._native
-
-    def _native_qtip_state(self, st):
-        """launch plans of the QTIP linears, per layer four groups of linears that share an input -- (q, k, v), (o),
-        (gate, up), (down) -- each a list of (entry point name, argument tuple) built once: SU as fp32, SV * 32 as fp32 (the
-        values BitshiftLinear.forward multiplies with, bitshift.py:441,470), q/k/v landing in the packed buffer the
-        attention kernel reads.  Per side of a linear: power-of-two width -> the fused kernels (gq_qtip_linear_in / _out);
-        width with a Hadamard factor -> gq_qtip_transform around the bare matvec (GQ_QPRO_PRETRANSFORMED)."""
-        c = self.config
-        dev = self.output.weight.device
-        kv = c.n_local_heads * c.head_dim
-        st["g"] = torch.zeros(c.intermediate_size, dtype=torch.float16, device=dev)
-        st["u"] = torch.zeros(c.intermediate_size, dtype=torch.float16, device=dev)
-        mmax = max(c.dim, c.intermediate_size)
-        # [linear][split-K part][M]; rows 3 / 4: the sums of wo / down while their transform-out is folded into the next launch
-        st["y32"] = torch.zeros(5, 4 * mmax, dtype=torch.float32, device=dev)
-        st["xs16"] = torch.zeros(3, mmax, dtype=torch.float16, device=dev)     # transformed inputs (factor widths)
-        keep = []    # fp32 copies and descriptor arrays the plans point into
-        tables = {}  # one fp32 device copy per distinct Hadamard factor table (every layer's module holds its own buffer)
-
-        def f32(t, mul=1.0):
-            t = (t.detach().to(dev).float() * mul).contiguous()
-            keep.append(t)
-            return t.data_ptr()
-
-        def table(t):
-            key = (tuple(t.shape), hash(t.detach().float().cpu().numpy().tobytes()))
-            if key not in tables:
-                tables[key] = f32(t)
-            return tables[key]
-
-        def table16(t):  # (gq_qtip_mlp_mid reads its factor tables as fp16: +-1 entries, checked by pm1)
-            t16 = t.detach().to(dev).half().contiguous()
-            key = ("h", tuple(t16.shape), hash(t16.cpu().numpy().tobytes()))
-            if key not in tables:
-                keep.append(t16)
-                tables[key] = t16.data_ptr()
-            return tables[key]
-
-        def pm1(t):
-            return bool((t.detach().float().abs() == 1.0).all())
-
-        def ksplit(m):  # K ranges per band: the split with the fewest band-equivalents per block (wo, down: 128 bands on 256 units -> 2)
-            if os.environ.get("GQ_QTIP_KSPLIT", "1") == "0":
-                return 1
-            return int(_lib.lib().gq_qtip_plan_ksplit(1, (ctypes.c_uint32 * 1)(m.out_features), m.in_features, 2))
-
-        def ksplit_group(mods):  # the same for linears that share a launch (q / k / v: 384 bands on 256 units -> 2 K ranges, 3 rounds of half a band)
-            if os.environ.get("GQ_QTIP_KSPLIT", "1") == "0" or os.environ.get("GQ_QTIP_KSPLIT_GROUP", "1") == "0":
-                return 1
-            return int(_lib.lib().gq_qtip_plan_ksplit(len(mods), (ctypes.c_uint32 * len(mods))(*[m.out_features for m in mods]), mods[0].in_features, 4))
-
-        y32, xs16 = st["y32"], st["xs16"]
-
-        def group(mods, xp, x2p, normw, pro, outs, resid, prev=None, defer=None, out_to=None, parts_ok=False):
-            """launches of one group: mods share the input vector xp (x2p for silu*mul); outs[i] fp16 destinations.
-            prev: GqQtipOut of the linear that PRODUCES xp, its transform-out folded into this group's first launch (which then
-            stores xp itself); defer = row of y32: this group's own transform-out is left to the consumer (-> returned descriptor)"""
-            R, K = mods[0].K, mods[0].in_features
-            plan = []
-            # split-K partial sums are added by the consumer of the sums: the fused transform-out (single linears with a power-of-two
-            # output width), the attention launch with the q / k / v transform-out folded in (out_to), gq_qtip_mlp_mid (parts_ok)
-            if len(mods) == 1:
-                ks = ksplit(mods[0]) if mods[0].K_right == 1 else 1
-            elif mods[0].K_left == 1 and ((out_to is not None and all(m.K_right == 1 for m in mods)) or parts_ok):
-                ks = ksplit_group(mods)
-            else:
-                ks = 1
-            ysl = [y32[defer]] if defer is not None else [y32[i] for i in range(len(mods))]
-            if mods[0].K_left == 1:  # fused transform-in + matvec, all linears in one launch
-                arr = (_lib.GqQtipIn * len(mods))(*[_lib.GqQtipIn(m.trellis.data_ptr(), f32(m.SU), m.tlut.data_ptr(), ysl[i].data_ptr(), m.out_features)
-                                                    for i, m in enumerate(mods)])
-                keep.append(arr)
-                if prev is not None:
-                    parr = (_lib.GqQtipOut * 1)(prev)
-                    keep.append(parr)
-                    plan.append(("gq_qtip_linear_in", (None, None, normw, c.norm_eps, pro, K, R, len(mods), arr, 1, parr, ks)))
-                else:
-                    plan.append(("gq_qtip_linear_in", (xp, x2p, normw, c.norm_eps, pro, K, R, len(mods), arr, 0, None, ks)))
-            else:  # factor transform of the shared input (one launch), then the bare matvec per linear
-                xf = (_lib.GqQtipXf * len(mods))(*[_lib.GqQtipXf(None, f32(m.SU), table(m.had_left), None, xs16[i].data_ptr())
-                                                   for i, m in enumerate(mods)])
-                keep.append(xf)
-                plan.append(("gq_qtip_transform", (1, xp, x2p, normw, c.norm_eps, pro, len(mods), xf, K, mods[0].K_left, 1)))
-                assert prev is None
-                for i, m in enumerate(mods):
-                    arr = (_lib.GqQtipIn * 1)(_lib.GqQtipIn(m.trellis.data_ptr(), None, m.tlut.data_ptr(), ysl[i].data_ptr(), m.out_features))
-                    keep.append(arr)
-                    plan.append(("gq_qtip_linear_in", (xs16[i].data_ptr(), None, None, 0.0, 3, K, R, 1, arr, 0, None, ks)))
-            p2 = [i for i, m in enumerate(mods) if m.K_right == 1]
-            fac = [i for i, m in enumerate(mods) if m.K_right != 1]
-            # One launch for transform-in + matvec + transform-out (gq_qtip_linear: the block that finishes a linear last
-            # transforms it): every linear of the group has a power-of-two output width, nothing is folded or deferred
-            if (one_launch and defer is None and prev is None and not fac and plan and plan[-1][0] == "gq_qtip_linear_in"
-                    and all(m.out_features <= 16384 for m in mods)):
-                name, args = plan.pop()
-                fin = (_lib.GqQtipOut * len(mods))(*[_lib.GqQtipOut(ysl[i].data_ptr(), f32(mods[i].SV, 32.0), resid, outs[i], mods[i].out_features, ks)
-                                                     for i in range(len(mods))])
-                ctr = torch.zeros(4, dtype=torch.int32, device=dev)
-                keep.extend([fin, ctr])
-                plan.append(("gq_qtip_linear", args[:9] + (fin, ks, ctr.data_ptr())))
-                return plan
-            if out_to is not None and not fac:
-                # the consumer rebuilds the outputs itself (q / k / v: gq_attn_decode_qtip, the transform-out inside the attention
-                # launch): descriptors instead of the gq_qtip_linear_out launch
-                arr = (_lib.GqQtipOut * len(mods))(*[_lib.GqQtipOut(ysl[i].data_ptr(), f32(mods[i].SV, 32.0), None, outs[i], mods[i].out_features, ks)
-                                                     for i in range(len(mods))])
-                keep.append(arr)
-                out_to.append(arr)
-                return plan
-            if defer is not None:  # (a single linear with a power-of-two output width)
-                desc = _lib.GqQtipOut(ysl[0].data_ptr(), f32(mods[0].SV, 32.0), resid, outs[0], mods[0].out_features, ks)
-                arr = (_lib.GqQtipOut * 1)(desc)
-                keep.append(arr)
-                return plan, desc, [("gq_qtip_linear_out", (1, arr))]
-            if p2:
-                arr = (_lib.GqQtipOut * len(p2))(*[_lib.GqQtipOut(ysl[i].data_ptr(), f32(mods[i].SV, 32.0), resid, outs[i], mods[i].out_features, ks)
-                                                   for i in p2])
-                keep.append(arr)
-                # M / 128 blocks per linear instead of one (GQ_QTIP_OUT_SEG, default ON; equal up to fp32 rounding): 2.9 vs 4.6 us
-                seg = out_seg and all(128 <= mods[i].out_features <= 8192 for i in p2)
-                plan.append(("gq_qtip_linear_out_seg" if seg else "gq_qtip_linear_out", (len(p2), arr)))
-            for Kf, M in sorted({(mods[i].K_right, mods[i].out_features) for i in fac}):
-                idx = [i for i in fac if (mods[i].K_right, mods[i].out_features) == (Kf, M)]
-                xf = (_lib.GqQtipXf * len(idx))(*[_lib.GqQtipXf(ysl[i].data_ptr(), f32(mods[i].SV, 32.0), table(mods[i].had_right), resid, outs[i])
-                                                  for i in idx])
-                keep.append(xf)
-                plan.append(("gq_qtip_transform", (0, None, None, None, 0.0, 0, len(idx), xf, M, Kf, 0)))
-            return plan
-
-        x, h, y, qkv = st["x"], st["h"], st["y"], st["qkv"]
-        e = qkv.element_size()
-        # Folding (GQ_QTIP_FOLD=1, default OFF): the transform-out of wo (+ residual) is rebuilt by the gate / up launch, that of
-        # down (+ residual) by the NEXT layer's q / k / v launch (gq_qtip_linear_in with n_prev = 1; bit-identical, the vector is
-        # stored once for the residual stream): two launches per layer less, but every one of the 256 blocks repeats the
-        # 4096-point transform and takes the slower prologue path -- measured 365 vs 385 tokens/s on the Llama-2-7b shape
-        # (400 vs 422 with a power-of-two MLP), so it stays off.  Needs power-of-two widths on both sides of the fold.
-        fold = os.environ.get("GQ_QTIP_FOLD", "0") != "0"
-        # GQ_QTIP_ONE_LAUNCH=1 (default OFF): transform-out inside the matvec launch (gq_qtip_linear, see group()).  Bit-identical,
-        # three launches per layer less -- and measured 302 vs 384 tokens/s on the Llama-2-7b shape: the device-scope release /
-        # acquire fences around the per-linear counter (L2 write-back + invalidate on 8 XCDs) cost ~7 us per launch, more than the
-        # launch they save.
-        one_launch = os.environ.get("GQ_QTIP_ONE_LAUNCH", "0") != "0"
-        out_seg = os.environ.get("GQ_QTIP_OUT_SEG", "1") != "0"
-        mlp_mid = os.environ.get("GQ_QTIP_MLP_MID", "1") != "0"
-        # GQ_QTIP_ATTN_FOLD (default ON): the transform-out of q / k / v runs inside the attention launch -- every head block needs
-        # head_dim of the outputs: the segments combined with the signs of its row, then one head_dim-point transform (equal to
-        # gq_qtip_linear_out up to fp32 rounding) --: one launch (4.8 us) per layer less.  Needs power-of-two q / k / v widths.
-        # (gq_attn_decode_qtip serves n_head * head_dim <= 8192, a power of two; wider models keep gq_qtip_linear_out + attention)
-        qw = c.n_head * c.head_dim
-        attn_fold = (os.environ.get("GQ_QTIP_ATTN_FOLD", "1") != "0" and not one_launch and c.head_dim in (64, 128)
-                     and qw <= 8192 and (qw & (qw - 1)) == 0)
-        layers = []
-        prev_down = None
-        for b in self.layers:
-            at, ff = b.attention, b.feed_forward
-            qkv_outs = [qkv.data_ptr(), qkv.data_ptr() + qw * e, qkv.data_ptr() + (qw + kv) * e]
-            can_o = fold and at.wo.K_right == 1 and ff.w1.K_left == 1
-            # GQ_QTIP_MLP_MID (default ON): a factor MLP width n = Kf * 64 (Llama-2-7b: 172 * 64) -- the two gq_qtip_transform launches
-            # between the matvecs of gate / up and down (output side, then input side with silu * up) become ONE launch that works
-            # column by column (gq_qtip_mlp_mid), the 64-point row transforms of the input side move into the prologue of down's
-            # matvec launch (gq_qtip_linear_in_rows).  gate / up bit-identical, the input of down equal up to fp32 rounding.
-            w1, w3, w2 = ff.w1, ff.w3, ff.w2
-            n_mlp, Kf = w2.in_features, w2.K_left
-            mid_ok = (mlp_mid and not can_o and not one_launch and Kf != 1 and w1.K_right == Kf and w3.K_right == Kf and n_mlp == Kf * 64
-                      and Kf <= 176 and Kf % 4 == 0 and w1.K_left == 1 and w3.K_left == 1 and w2.K_right == 1
-                      and w1.out_features == n_mlp and w3.out_features == n_mlp
-                      and torch.equal(w1.had_right, w3.had_right) and pm1(w1.had_right) and pm1(w2.had_left))
-            can_d = fold and ff.w2.K_right == 1 and at.wq.K_left == 1
-        
-            fold_here = attn_fold and all(m.K_right == 1 for m in (at.wq, at.wk, at.wv))
-            desc = [] if fold_here else None
-            d = dict(qkv=group([at.wq, at.wk, at.wv], x.data_ptr(), None, b.input_layernorm.weight.data_ptr(), 1, qkv_outs, None, out_to=desc))
-            # (q / k / v of this layer with the previous layer's down folded in; the first layer of a range takes the plain form)
-            desc_f = [] if fold_here else None
-            d["qkv_f"] = group([at.wq, at.wk, at.wv], None, None, b.input_layernorm.weight.data_ptr(), 1, qkv_outs, None, prev=prev_down, out_to=desc_f) \
-                if prev_down is not None else None
-            d["attn_qt"] = desc[0] if fold_here else None
-            if can_o:
-                d["o"], desc_o, _ = group([at.wo], y.data_ptr(), None, None, 0, [h.data_ptr()], x.data_ptr(), defer=3)
-                d["gu"] = group([ff.w1, ff.w3], None, None, b.post_attention_layernorm.weight.data_ptr(), 1,
-                                [st["g"].data_ptr(), st["u"].data_ptr()], None, prev=desc_o)
-            else:
-                d["o"] = group([at.wo], y.data_ptr(), None, None, 0, [h.data_ptr()], x.data_ptr())
-                d["gu"] = group([ff.w1, ff.w3], h.data_ptr(), None, b.post_attention_layernorm.weight.data_ptr(), 1,
-                                [st["g"].data_ptr(), st["u"].data_ptr()], None, parts_ok=mid_ok)
-            if can_d:
-                d["d"], prev_down, d["d_out"] = group([ff.w2], st["g"].data_ptr(), st["u"].data_ptr(), None, 2, [x.data_ptr()], h.data_ptr(), defer=4)
-            else:
-                d["d"], prev_down, d["d_out"] = group([ff.w2], st["g"].data_ptr(), st["u"].data_ptr(), None, 2, [x.data_ptr()], h.data_ptr()), None, None
-            if mid_ok:
-                assert (d["gu"][-1][0] == "gq_qtip_transform" and d["d"][0][0] == "gq_qtip_transform"
-                        and d["d"][1][0] == "gq_qtip_linear_in" and d["d"][1][1][4] == 3), "unexpected launch plan of a factor-width MLP"
-                ks_gu = d["gu"][0][1][11]  # (split-K parts of the gate / up sums)
-                if "z32" not in st:
-                    st["z32"] = torch.zeros(mmax, dtype=torch.float32, device=dev)
-                mid = _lib.GqQtipMid(y32[0].data_ptr(), y32[1].data_ptr(), f32(w1.SV, 32.0), f32(w3.SV, 32.0),
-                                     table16(w1.had_right.t()), f32(w2.SU), table16(w2.had_left), st["z32"].data_ptr(), None, None)
-                keep.append(mid)
-                a_in = d["d"][1][1]  # (xs16, None, None, 0.0, 3, K, R, 1, arr, 0, None, ks)
-                d["gu"] = d["gu"][:-1]
-                d["d"] = [("gq_qtip_mlp_mid", (ctypes.pointer(mid), ks_gu, n_mlp, Kf)),
-                          ("gq_qtip_linear_in_rows", (st["z32"].data_ptr(), n_mlp, 64, a_in[6], 1, a_in[8], a_in[11]))] + d["d"][2:]
-            layers.append(d)
-        # Round 5 (GQ_QTIP_PRE=1; default OFF -- measured 421 vs 427 tokens/s on Llama-2-7b, profiles/r05_qtip_pre.txt: the one-block
-        # launch grows by more than the 256-block launch shrinks, whose prologue ran under its first tile requests anyway): the
-        # transform-out launch of wo / down ALSO runs the transform-in of the linears that read
-        # its output through an RMSNorm -- gate / up, the next layer's q / k / v -- one block per consumer (gq_qtip_linear_out_in), and
-        # their matvec launch takes the pre-transformed vectors as they are: its 256 blocks no longer repeat RMSNorm . SU . Hadamard.
-        # Needs power-of-two widths on that edge and the plain launch forms (no folding, no one-launch form).
-        st["xt"] = torch.zeros(3, c.dim, dtype=torch.float16, device=dev)
-        pre_on = os.environ.get("GQ_QTIP_PRE", "0") != "0" and not fold and not one_launch and 256 <= c.dim <= 8192 and (c.dim & (c.dim - 1)) == 0
-
-        def with_pre(plan_out, plan_in, normw, mods):
-            """(plan of the producer with its last launch -- the transform-out -- replaced, plan of the consumers' matvec launch on the
-            pre-transformed vectors), or None when the launches are not of the plain form"""
-            if not (pre_on and plan_out and plan_in and plan_out[-1][0] in ("gq_qtip_linear_out", "gq_qtip_linear_out_seg") and plan_out[-1][1][0] == 1
-                    and plan_in[0][0] == "gq_qtip_linear_in" and plan_in[0][1][4] == 1 and plan_in[0][1][9] == 0
-                    and all(m.K_left == 1 and m.in_features == c.dim for m in mods)):
-                return None
-            desc = plan_out[-1][1][1]  # GqQtipOut array of one element
-            n = len(mods)
-            su = (ctypes.c_void_p * n)(*[f32(m.SU) for m in mods])
-            xt = (ctypes.c_void_p * n)(*[st["xt"][i].data_ptr() for i in range(n)])
-            a_in = plan_in[0][1]  # (xp, x2p, normw, eps, pro, K, R, n, arr, 0, None, ks)
-            arr = (_lib.GqQtipIn * n)(*[_lib.GqQtipIn(a_in[8][i].trellis, st["xt"][i].data_ptr(), a_in[8][i].tlut, a_in[8][i].y32, a_in[8][i].M) for i in range(n)])
-            keep.extend([su, xt, arr])
-            return (plan_out[:-1] + [("gq_qtip_linear_out_in", (desc, normw, c.norm_eps, n, su, xt))],
-                    [("gq_qtip_linear_in", (None, None, None, 0.0, 3, a_in[5], a_in[6], n, arr, 0, None, a_in[11]))] + plan_in[1:])
-
-        for li, (d, b) in enumerate(zip(layers, self.layers)):
-            at, ff = b.attention, b.feed_forward
-            r = with_pre(d["o"], d["gu"], b.post_attention_layernorm.weight.data_ptr(), [ff.w1, ff.w3])
-            if r is not None:
-                d["o"], d["gu"] = r
-            d["d_pre"] = d["qkv_pre"] = None
-        for li in range(len(layers) - 1):
-            nb = self.layers[li + 1]
-            r = with_pre(layers[li]["d"], layers[li + 1]["qkv"], nb.input_layernorm.weight.data_ptr(), [nb.attention.wq, nb.attention.wk, nb.attention.wv])
-            if r is not None and layers[li]["d_out"] is None:
-                layers[li]["d_pre"], layers[li + 1]["qkv_pre"] = r
-        st["qtip_layers"] = layers
-        st["qtip_keep"] = keep
-
-    def _native_layers_qtip(self, x: Tensor, pos: Tensor, l0: int, l1: int, slot: int = 0):
-        """one decode step of layers [l0, l1) of an unfused QTIP model (A = transform-in + trellis matvec, B = transform-out):
-        A(q,k,v | RMSNorm) B(q,k,v) attention A(o) B(o + residual) A(gate,up | RMSNorm) B(gate,up) A(down | silu*mul)
-        B(down + residual) -- 9 launches per layer with power-of-two widths; a width with a Hadamard factor replaces the A / B
-        on its side by gq_qtip_transform (+ the bare matvec): 11 launches for Llama-2-7b / 70b (MLP width only)."""
-        L = _lib.lib()
-        sp = _lib.current_stream_ptr()
-        c = self.config
-        b = self._native_state()
-        assert x.data_ptr() == b["x"].data_ptr(), "the QTIP launch plans are bound to the model's own hidden-state buffer"
-        y, qkv = b["y"], b["qkv"]
-        ck = _lib.check
-        scale = 1.0 / math.sqrt(c.head_dim)
-        kv_stride = c.n_local_heads * self.max_seq_length * c.head_dim * 2
-
-        def run(plan):
-            for name, args in plan:
-                ck(getattr(L, name)(*args, sp), name)
-
-        pending = None  # transform-out of the previous layer's down projection, not yet run
-        pre_in = False  # the previous layer's down launch left this layer's q / k / v inputs pre-transformed
-        for li in range(l0, l1):
-            d, at = b["qtip_layers"][li], self.layers[li].attention
-            if pre_in:
-                run(d["qkv_pre"])
-            elif pending is not None and d["qkv_f"] is not None:
-                run(d["qkv_f"])  # (rebuilds and stores the hidden state itself)
-            else:
-                if pending is not None:
-                    run(pending)
-                run(d["qkv"])
-            if d["attn_qt"] is not None:
-                ck(L.gq_attn_decode_qtip(d["attn_qt"], pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(),
-                                         at.kv_cache.k_cache.data_ptr() + slot * kv_stride, at.kv_cache.v_cache.data_ptr() + slot * kv_stride,
-                                         y.data_ptr(), c.n_head, c.n_local_heads, c.head_dim, self.max_seq_length, scale, b["attn_split"],
-                                         b["attn_ws"].data_ptr() if b["attn_ws"] is not None else None, sp), "attn_qtip")
-            else:
-                ck(L.gq_attn_decode_split(qkv.data_ptr(), pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(),
-                                          at.kv_cache.k_cache.data_ptr() + slot * kv_stride, at.kv_cache.v_cache.data_ptr() + slot * kv_stride,
-                                          y.data_ptr(), c.n_head, c.n_local_heads, c.head_dim, self.max_seq_length, scale, b["attn_split"],
-                                          b["attn_ws"].data_ptr() if b["attn_ws"] is not None else None, sp), "attn")
-            run(d["o"])
-            run(d["gu"])
-            pre_in = li + 1 < l1 and d["d_pre"] is not None
-            run(d["d_pre"] if pre_in else d["d"])
-            pending = d["d_out"]
-        if pending is not None:
-            run(pending)
 
     def native_embed(self, tok: Tensor, x: Tensor, ssq: Optional[Tensor] = None):
         """x = tok_embeddings[tok]; with `ssq` (the hand-over slots of _native_state) also the statistics of x for layer 0's RMSNorm"""
-        _lib.check(_lib.lib().gq_embed_lookup_ho(tok.data_ptr(), self.tok_embeddings.weight.data_ptr(), x.data_ptr(), self.config.dim,
-                                                 self.config.vocab_size, ssq.data_ptr() if ssq is not None else None,
-                                                 _lib.current_stream_ptr()), "gq_embed_lookup")
+        native_step.embed(self, tok, x, ssq)
 
     def _handover_plan(self, blk):
-        """Statistics hand-over (include/gq_hip.h, round 5) on the two RMSNorm edges of a layer -- (w2 or the embedding) -> wqkv and
-        wo -> w1w3: the producer's residual epilogue leaves the partial sums of squares of the hidden state it writes, the consumer's
-        RMSNorm prologue adds them instead of exchanging per-wave sums.  An edge is used only when BOTH ends have the form (the plan is
-        the library's own dispatch run dry): 8B-class 2-bit models.  OFF by default (GQ_SSQ_HANDOVER=1 turns it on): measured on the
-        8B decode it LOSES 1.4 % (855 vs 867 tokens/s, profiles/r05_handover.txt) -- the partial sums come out of memory no earlier
-        than the activations themselves, the wave that adds them holds the launch barrier ~700 cycles, and the producers pay 0.1 us."""
-        # (not cached: the answer follows gq_set_ap_mode / the environment like the dispatch itself; 4 host calls per layer, paid by
-        # eager steps and graph captures only)
-        L = _lib.lib()
-        c, at, ff = self.config, blk.attention, blk.feed_forward
-        on = os.environ.get("GQ_SSQ_HANDOVER", "0") != "0"
-        if not on:
-            return dict(qkv_in=False, w13=False, w2_out=False)
-        qkv_in = on and bool(L.gq_anyprec_handover_plan(at.wqkv.out_features, c.dim, at.wqkv.bitwidth, 1, 0) & 1)
-        w13_in = on and bool(L.gq_anyprec_handover_plan(2 * c.intermediate_size, c.dim, ff.w1w3.bitwidth, 1, 4) & 1)
-        wo_out = bool(L.gq_anyprec_handover_plan(c.dim, c.n_head * c.head_dim, at.wo.bitwidth, 0, 1) & 2)
-        w2_out = bool(L.gq_anyprec_handover_plan(c.dim, c.intermediate_size, ff.w2.bitwidth, 0, 1) & 2)
-        return dict(qkv_in=qkv_in, w13=w13_in and wo_out, w2_out=w2_out)
+        """which RMSNorm edges of a layer hand their statistics over (native_step.handover_plan; GQ_SSQ_HANDOVER, off by default)"""
+        return native_step.handover_plan(self, blk)
 
     def native_layers(self, x: Tensor, pos: Tensor, l0: int, l1: int, slot: int = 0, ssq_ready: bool = False):
         """layers [l0, l1) of one decode step, in place on the hidden state `x` (fp16 [dim]); `slot` = batch index of
         the KV caches to use (layer-pipelined decode keeps one sequence per slot).  ssq_ready: the hand-over slots hold the
         statistics of `x` (native_embed(..., ssq) ran on it)."""
-        if self._native_kind() == "qtip":
-            return self._native_layers_qtip(x, pos, l0, l1, slot)
-        L = _lib.lib()
-        st = _lib.current_stream_ptr()
-        c = self.config
-        b = self._native_state()
-        h, y, qkv, gu, pairs = b["h"], b["y"], b["qkv"], b["gu"], b["pairs"]
-        apws = b["ap_ws"]
-        if pairs:  # a load_state_dict into a sub-module bypasses _reset_native: the rows must still be paired at launch
-            for blk in self.layers[l0:l1]:
-                if not getattr(blk.feed_forward.w1w3, "gq_row_pairs", False):
-                    pair_gate_up_rows_(blk.feed_forward.w1w3)
-                    self._alloc_gen = getattr(self, "_alloc_gen", 0) + 1  # (the re-pair assigned new tensors)
-        ck = _lib.check
-        scale = 1.0 / math.sqrt(c.head_dim)
-        kv_stride = c.n_local_heads * self.max_seq_length * c.head_dim * 2  # bytes per batch slot
-        qdim = c.n_head * c.head_dim  # (wo's input width: not dim for a model with a head_dim of its own)
-        ssq = b["ssq"].data_ptr()
-        x_has_ssq = ssq_ready  # the slots hold the statistics of the current x
-        for li, blk in enumerate(self.layers[l0:l1]):
-            at, ff = blk.attention, blk.feed_forward
-            kc, vc = at.kv_cache.k_cache.data_ptr() + slot * kv_stride, at.kv_cache.v_cache.data_ptr() + slot * kv_stride
-            ws = b["attn_ws"].data_ptr() if b["attn_ws"] is not None else None
-            ho = self._handover_plan(blk)
-            nxt = self.layers[l0 + li + 1] if l0 + li + 1 < len(self.layers) else None
-            # (w2 writes the statistics only when the NEXT layer's wqkv reads them: the last layer feeds the lm_head's own norm)
-            w2_ssq = ssq if (pairs and ho["w2_out"] and nxt is not None and l0 + li + 1 < l1 and self._handover_plan(nxt)["qkv_in"]) else None
-            # RoPE + KV-cache write in the epilogue of the wqkv GEMV, attention without them, where the library serves the layer's
-            # wqkv that way (fast mode, 2-bit, K <= 4096: csrc/ap_stream.hip); else the two launches of rounds 1-3
-            use_ssq = x_has_ssq and ho["qkv_in"]
-            if c.qk_norm:
-                # Qwen3: q and k are normalised per head BEFORE the rotation, so the wqkv launch must not rotate (its RoPE epilogue holds a
-                # head's rows in eight 16-row groups: no per-head statistic there) -- plain wqkv GEMV, then ONE attention launch that
-                # normalises, rotates, writes the cache row and attends
-                ck(L.gq_anyprec_gemv_fused_ho(x.data_ptr(), qkv.data_ptr(), at.wqkv.qweight.data_ptr(), at.wqkv.lut.data_ptr(),
-                                              at.wqkv.out_features, c.dim, at.wqkv.bitwidth, blk.input_layernorm.weight.data_ptr(),
-                                              c.norm_eps, None, 0, None, 0, ssq if use_ssq else None, None, st), "wqkv")
-                ck(L.gq_attn_decode_split_qknorm(qkv.data_ptr(), pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), kc, vc,
-                                                 y.data_ptr(), c.n_head, c.n_local_heads, c.head_dim, self.max_seq_length, scale,
-                                                 b["attn_split"], ws, at.q_norm.weight.data_ptr(), at.k_norm.weight.data_ptr(),
-                                                 at.q_norm.eps, st), "attn+qknorm")
-            elif (b["attn_split"] == 1 and not use_ssq
-                    and L.gq_anyprec_qkv_rope_attn_supported(at.wqkv.out_features, c.dim, at.wqkv.bitwidth, c.head_dim, c.n_head, c.n_local_heads)):
-                # round 6: the attention heads as extra blocks of the wqkv launch (they wait on device flags for q / the new cache row):
-                # one launch and one kernel boundary less per layer, outputs bit-identical to the two launches below
-                ck(L.gq_anyprec_gemv_qkv_rope_attn(x.data_ptr(), qkv.data_ptr(), at.wqkv.qweight.data_ptr(), at.wqkv.lut.data_ptr(),
-                                                   at.wqkv.out_features, c.dim, at.wqkv.bitwidth, blk.input_layernorm.weight.data_ptr(),
-                                                   c.norm_eps, pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), kc, vc,
-                                                   c.n_head, c.n_local_heads, c.head_dim, self.max_seq_length, y.data_ptr(), scale,
-                                                   b["attn_flags"].data_ptr(), st), "wqkv+rope+attention")
-            elif L.gq_anyprec_qkv_rope_supported(at.wqkv.out_features, c.dim, at.wqkv.bitwidth, c.head_dim):
-                ck(L.gq_anyprec_gemv_qkv_rope_ho(x.data_ptr(), qkv.data_ptr(), at.wqkv.qweight.data_ptr(), at.wqkv.lut.data_ptr(),
-                                                 at.wqkv.out_features, c.dim, at.wqkv.bitwidth, blk.input_layernorm.weight.data_ptr(),
-                                                 c.norm_eps, pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), kc, vc,
-                                                 c.n_head, c.n_local_heads, c.head_dim, self.max_seq_length,
-                                                 ssq if (x_has_ssq and ho["qkv_in"]) else None, st), "wqkv+rope")
-                ck(L.gq_attn_decode_roped(qkv.data_ptr(), pos.data_ptr(), kc, vc, y.data_ptr(), c.n_head, c.n_local_heads, c.head_dim,
-                                          self.max_seq_length, scale, b["attn_split"], ws, st), "attn")
-            else:
-                ck(L.gq_anyprec_gemv_fused(x.data_ptr(), qkv.data_ptr(), at.wqkv.qweight.data_ptr(), at.wqkv.lut.data_ptr(),
-                                           at.wqkv.out_features, c.dim, at.wqkv.bitwidth, blk.input_layernorm.weight.data_ptr(),
-                                           c.norm_eps, None, 0, st), "wqkv")
-                ck(L.gq_attn_decode_split(qkv.data_ptr(), pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), kc, vc,
-                                          y.data_ptr(), c.n_head, c.n_local_heads, c.head_dim, self.max_seq_length, scale, b["attn_split"],
-                                          ws, st), "attn")
-            x_has_ssq = False
-            if pairs:
-                w13 = ssq if ho["w13"] else None
-                ck(L.gq_anyprec_gemv_fused_ho(y.data_ptr(), h.data_ptr(), at.wo.qweight.data_ptr(), at.wo.lut.data_ptr(), c.dim, qdim,
-                                              at.wo.bitwidth, None, 0.0, x.data_ptr(), 1, None, 0, None, w13, st), "wo")
-                ck(L.gq_anyprec_gemv_fused_ho(h.data_ptr(), gu.data_ptr(), ff.w1w3.qweight.data_ptr(), ff.w1w3.lut.data_ptr(), 2 * c.intermediate_size,
-                                              c.dim, ff.w1w3.bitwidth, blk.post_attention_layernorm.weight.data_ptr(), c.norm_eps, None, 4,
-                                              None, 0, w13, None, st), "w1w3")
-                ck(L.gq_anyprec_gemv_fused_ho(gu.data_ptr(), x.data_ptr(), ff.w2.qweight.data_ptr(), ff.w2.lut.data_ptr(), c.dim,
-                                              c.intermediate_size, ff.w2.bitwidth, None, 0.0, h.data_ptr(), 1,
-                                              apws.data_ptr() if apws is not None else None, apws.numel() * 4 if apws is not None else 0,
-                                              None, w2_ssq, st), "w2")
-                x_has_ssq = w2_ssq is not None
-                continue
-            ck(L.gq_anyprec_gemv_fused(y.data_ptr(), h.data_ptr(), at.wo.qweight.data_ptr(), at.wo.lut.data_ptr(), c.dim, qdim,
-                                       at.wo.bitwidth, None, 0.0, x.data_ptr(), 1, st), "wo")
-            ck(L.gq_anyprec_gemv_fused(h.data_ptr(), gu.data_ptr(), ff.w1w3.qweight.data_ptr(), ff.w1w3.lut.data_ptr(),
-                                       2 * c.intermediate_size, c.dim, ff.w1w3.bitwidth,
-                                       blk.post_attention_layernorm.weight.data_ptr(), c.norm_eps, None, 0, st), "w1w3")
-            ck(L.gq_anyprec_gemv_fused(gu.data_ptr(), x.data_ptr(), ff.w2.qweight.data_ptr(), ff.w2.lut.data_ptr(), c.dim,
-                                       c.intermediate_size, ff.w2.bitwidth, None, 0.0, h.data_ptr(), 1 | 2, st), "w2")
+        self._native_state().layers(x, pos, l0, l1, slot, ssq_ready)
 
     def native_head(self, x: Tensor) -> Tensor:
-        b = self._native_state()
-        c = self.config
-        _lib.check(_lib.lib().gq_dense_gemv_f16(x.data_ptr(), self.output.weight.data_ptr(), b["logits"].data_ptr(), c.vocab_size,
-                                                c.dim, self.norm.weight.data_ptr(), c.norm_eps, _lib.current_stream_ptr()), "lm_head")
-        return b["logits"]
+        return self._native_state().head(x)
 
     # ------------------------------------------------------------------------------------------------ prompt pass
     def prefill_ready(self, idx: Tensor) -> bool:

@@ -1,5 +1,5 @@
-"""The AP-GEMV launches the benchmark makes, in the form the decode step issues them (guidedquant_amd/model.py::native_layers, pair
-path) and as roofline_by_shape times the plain operator, each with the kernel family the default dispatch sends it to on an MI355X
+"""The AP-GEMV launches the benchmark makes, in the form the decode step issues them (guidedquant_amd/native_step.py::ApStep.layers,
+pair path) and as roofline_by_shape times the plain operator, each with the kernel family the default dispatch sends it to on an MI355X
 (256 CUs, M = 1).  Data only: tests/test_dispatch_table_cpu.py checks the dry dispatch against it, tests/test_dispatch_parity_gpu.py
 runs every row on its route against the oracle.
 
