@@ -428,7 +428,10 @@ int gq_attn_decode(const void *qkv, const int *pos, const void *cos_table, const
 /* Split-KV form for long contexts: n_split blocks per head, each over a contiguous range of the cached positions (whole
  * passes of 128 positions at head_dim 128), partial (max, sum, weighted V) results in `workspace` (f32
  * [n_head][n_split][head_dim + 2]) combined by a second small launch.  One block per head keeps only n_head CUs
- * streaming the cache: 51 us per layer at 4096 positions.  n_split = 1 is gq_attn_decode (no workspace, one launch). */
+ * streaming the cache: 51 us per layer at 4096 positions.  n_split = 1 is gq_attn_decode (no workspace, one launch).
+ * n_split in 1..64, for every form below as well.  Splits beyond the context are legal: a split whose range starts behind *pos
+ * writes a neutral partial result (max -3e38, sum 0, weighted V 0) that adds exactly nothing in the combine; a context of at most
+ * two passes is finished by one block per head and the workspace is neither written nor read. */
 int gq_attn_decode_split(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,
                          void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
                          float scale, uint32_t n_split, float *workspace, void *stream);
