@@ -541,7 +541,18 @@ int gq_dense_gemv_f16(const void *x, const void *W, void *out, uint32_t N, uint3
  * vocab <= GQ_SAMPLER_MAX_VOCAB (all three entry points; beyond it: GQ_ENOTSUP).  The grid is 128 blocks and the work buffers are
  * 128 * 32 (128 * 64) elements at every width: up to 131072 logits a block takes a slice of at most 1024, from there to 262144 -- the
  * published Qwen3 vocabulary is 151936 -- a slice of at most 2048 (a second pair of kernel instances; ban ids, seq_out and the embedding
- * row take token ids of the whole range). */
+ * row take token ids of the whole range).
+ * The draw is a pure function of (logits, top_k, top_p, temperature, seed, *counter, ban list, *pos_io), pinned draw for draw by
+ * tests/sampler_model.py:
+ *   candidates  the first top_k tokens of the order (fp16 value descending, token id ascending), top_k clamped to [1, 64].  The order is
+ *               that of the fp16 bit patterns: -0 sorts directly BELOW +0, so among zeros at the k-th place every +0 is taken before any
+ *               -0 (either is a valid top-k among equal values; the nucleus filter and the race compare values, where -0 == +0).
+ *               Fewer tokens than top_k (a short vocabulary, banned ids): all of them.  A -inf logit is a candidate like any other and
+ *               counts towards top_k; its probability is 0 and it is never drawn while one candidate is finite.
+ *   race        score = value / max(T, 1e-5) - log(-log u), u = ((r >> 8) + 1) / 2^24, r = hash32(seed ^ hash32(ctr * 0x9E3779B9 + id + 1))
+ *               in 32-bit arithmetic with ctr = (uint32_t)*counter; the largest score wins, equal scores go to the lower id.
+ *   counter     *counter = ctr + 1 modulo 2^32: it runs through the sign bit of the int and wraps to 0; the random numbers depend on
+ *               the 32 bits alone. */
 #define GQ_SAMPLER_MAX_VOCAB 262144
 int gq_sample_topk(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter,
                    float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, void *stream);
