@@ -647,8 +647,10 @@ class AnyPrecisionForCausalLM(nn.Module):
         try:
             for hf_layer, blk in zip(self.get_model_layers(), dec.layers):
                 L = self._layer_linears(hf_layer)
-                if any(m.bias is not None for m in L.values()):
-                    raise NotImplementedError("fused decode model: biased linears")
+                # (a bias only where the block layout has one: q / k / v of a Qwen2 tree, all three)
+                biased = sorted(n for n, m in L.items() if m.bias is not None)
+                if biased != (["k", "q", "v"] if args.attn_bias else []):
+                    raise NotImplementedError("fused decode model: biased linears (%s)" % ", ".join(biased or ["q / k / v without a bias"]))
                 blk.input_layernorm.weight = hf_layer.input_layernorm.weight
                 blk.post_attention_layernorm.weight = hf_layer.post_attention_layernorm.weight
                 if args.qk_norm:  # (Qwen3: the per-head norms by reference, like the layer norms)
@@ -661,6 +663,8 @@ class AnyPrecisionForCausalLM(nn.Module):
                     torch.cat([lut(L[n]) for n in "qkv"], dim=0).contiguous())
                 put(blk.feed_forward.w1w3, torch.cat([L["gate"].qweight[:bitwidth], L["up"].qweight[:bitwidth]], dim=1).contiguous(),
                     torch.cat([lut(L["gate"]), lut(L["up"])], dim=0).contiguous())
+                if args.attn_bias:  # (a new tensor, like the concatenated planes; the module tree keeps its own three)
+                    blk.attention.wqkv._buffers["bias"] = torch.cat([L[n].bias.to(torch.float16) for n in "qkv"], dim=0).contiguous()
                 if single:
                     released.append(hf_layer)
                     for n in ("q", "k", "v", "gate", "up"):

@@ -8,6 +8,8 @@ decode harness loads.  State-dict transformations only (host code).
     by concatenating qweight along dim 1 (rows) and lut along dim 0.
     Every other tensor keeps its renamed key: a Qwen3 checkpoint's `self_attn.{q,k}_norm.weight` arrive as
     `layers.{i}.attention.{q,k}_norm.weight`, the keys of `Attention.q_norm` / `k_norm`.
+    A Qwen2 checkpoint's `self_attn.{q,k,v}_proj.bias` are concatenated to `layers.{i}.attention.wqkv.bias` (fp16); a bias on any
+    other linear is an error (no block layout served here has one).
     Generalised: the reference only accepts "Llama-2-*" directory names (:62-69); here the layer count is an argument or
     inferred from the keys, so Llama-3 checkpoints convert too.
   * `convert_qtip_no_fuse(state_dict)`  ==  inference/qtip_convert_no_fuse.py:9-46: key renames only (wq/wk/wv/wo,
@@ -89,6 +91,14 @@ def convert_anyprec_fuse(state_dict, bitwidth, n_layer=None):
                 dim=dim).contiguous()
             new_dict[f + 'w1w3.' + suffix] = torch.cat(
                 (new_dict.pop(f + 'gate_proj.' + suffix), new_dict.pop(f + 'up_proj.' + suffix)), dim=dim).contiguous()
+        for key in (a + 'wo.bias', f + 'gate_proj.bias', f + 'up_proj.bias', f + 'w2.bias'):
+            if key in new_dict:
+                raise ValueError(f"{key}: a bias on o_proj / gate_proj / up_proj / down_proj has no fused decode form (q / k / v only: Qwen2)")
+        qkv_bias = [a + n + '_proj.bias' for n in 'qkv']
+        if any(k in new_dict for k in qkv_bias):
+            if not all(k in new_dict for k in qkv_bias):
+                raise ValueError(f"layer {i}: q_proj / k_proj / v_proj must all carry a bias or none")
+            new_dict[a + 'wqkv.bias'] = torch.cat([new_dict.pop(k).half() for k in qkv_bias], dim=0).contiguous()
     return new_dict
 
 

@@ -110,11 +110,24 @@ struct AttnQkNorm<true> {
     const uint16_t *qw, *kw;  // q_norm / k_norm weights, fp16 [HD]
     float eps;
 };
-template <int HD, bool QT, bool QKN = false>
+// QB (Qwen2 / Qwen2.5: modeling_qwen2.Qwen2Attention, q_proj / k_proj / v_proj = nn.Linear(bias=True); the quantized linears add the
+// bias as ONE fp16 add behind the fp16-rounded GEMV result, any_precision/modules/AnyPrecisionLinear.py `output += bias`): thread
+// d < HD adds the bias of its q / k / v element (and of the rotation partners) in fp16 right behind the loads, in front of the
+// rotation -- bit for bit what the module forward rotates and caches.  The bias is laid out like the packed q | k | v vector; its loads
+// go out with the q / k / v loads, in front of the position read.  A compile-time form like QKN: the QB = false instances take an
+// empty argument and keep the instructions they had.
+template <bool QB>
+struct AttnBias {};  // (nothing to pass)
+template <>
+struct AttnBias<true> {
+    const uint16_t *qkv;  // fp16 [(H + 2 Hkv) * HD]
+};
+template <int HD, bool QT, bool QKN = false, bool QB = false>
 __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint16_t *qkv, const int *pos_ptr, const uint16_t *cos_t,
                                                           const uint16_t *sin_t, uint16_t *kc, uint16_t *vc, uint16_t *out,
                                                           u32 H, u32 Hkv, u32 max_seq, float scale, u32 nsplit, float *ws, AttnQt qt,
-                                                          AttnQkNorm<QKN> nm) {
+                                                          AttnQkNorm<QKN> nm, AttnBias<QB> bs) {
+    static_assert(!(QB && (QT || QKN)), "the bias form is the plain fp16 q / k / v form plus the add");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr u32 NW = ATTN_WAVES;
     float *sc = reinterpret_cast<float *>(smem);  // [2 * NW * 64 / (HD / 8)] running max / sum of the position streams
@@ -204,6 +217,16 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
         qr_b = q[dr];
         kr_b = k[dr];
         vd_b = v[d];
+        if constexpr (QB) {
+            // (the same offsets into the bias as into the packed vector; all ten loads in flight together)
+            const uint16_t *bq = bs.qkv + (q - qkv), *bk = bs.qkv + (k - qkv), *bv = bs.qkv + (v - qkv);
+            const uint16_t bqd = bq[d], bkd = bk[d], bqr = bq[dr], bkr = bk[dr], bvd = bv[d];
+            qd_b = h2u(u2h(qd_b) + u2h(bqd));
+            kd_b = h2u(u2h(kd_b) + u2h(bkd));
+            qr_b = h2u(u2h(qr_b) + u2h(bqr));
+            kr_b = h2u(u2h(kr_b) + u2h(bkr));
+            vd_b = h2u(u2h(vd_b) + u2h(bvd));
+        }
     }
     u32 pos = (u32)pos_ptr[0];
     if (pos >= max_seq) {  // decoding past the cache: nothing is written to it, the head's output is poisoned (NaN logits)
@@ -1009,13 +1032,17 @@ extern "C" int gq_embed_lookup_ho(const int *token, const void *table, void *out
 }
 
 namespace {
-template <bool QT, bool QKN = false>
+template <bool QT, bool QKN = false, bool QB = false>
 int attn_launch(const void *qkv, const AttnQt &qt, const int *pos, const void *cos_table, const void *sin_table, void *k_cache, void *v_cache,
                 void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split,
-                float *workspace, void *stream, const void *q_norm_weight = nullptr, const void *k_norm_weight = nullptr, float eps = 0.f) {
+                float *workspace, void *stream, const void *q_norm_weight = nullptr, const void *k_norm_weight = nullptr, float eps = 0.f,
+                const void *qkv_bias = nullptr) {
     static_assert(!(QT && QKN), "the QK-norm form reads fp16 q / k / v");
+    static_assert(!(QB && (QT || QKN)), "the bias form does not combine with the QTIP or the QK-norm form");
     if ((!QT && !qkv) || !pos || !cos_table || !sin_table || !k_cache || !v_cache || !out) return gq_fail(GQ_EINVAL, "null pointer argument.");
     if (QKN && (!q_norm_weight || !k_norm_weight)) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    if (QB && !qkv_bias) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    if (QB && ((uintptr_t)qkv_bias & 15u)) return gq_fail(GQ_EINVAL, "gq_attn_decode_split_bias: 16-byte aligned bias.");
     if (n_kv_head == 0 || n_head % n_kv_head) return gq_fail(GQ_EINVAL, "n_head must be a multiple of n_kv_head.");
     if (head_dim != 64 && head_dim != 128) return gq_fail(GQ_ENOTSUP, "head_dim must be 64 or 128.");
     if (n_split < 1u || n_split > 64u || (n_split > 1u && !workspace)) return gq_fail(GQ_EINVAL, "n_split in 1..64, with a workspace when > 1.");
@@ -1027,15 +1054,17 @@ int attn_launch(const void *qkv, const AttnQt &qt, const int *pos, const void *c
 #define GQ_LAUNCH_ATTN(HD_)                                                                                                                   \
     do {                                                                                                                                      \
         static GqPerDeviceOnce once;                                                                                                          \
-        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_decode_kernel<HD_, QT, QKN>), 160 * 1024));                     \
-        hipLaunchKernelGGL((attn_decode_kernel<HD_, QT, QKN>), grid, dim3(64 * ATTN_WAVES), smem, s, (const uint16_t *)qkv, pos,              \
+        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_decode_kernel<HD_, QT, QKN, QB>), 160 * 1024));                 \
+        hipLaunchKernelGGL((attn_decode_kernel<HD_, QT, QKN, QB>), grid, dim3(64 * ATTN_WAVES), smem, s, (const uint16_t *)qkv, pos,          \
                            (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)k_cache, (uint16_t *)v_cache,                \
-                           (uint16_t *)out, n_head, n_kv_head, max_seq, scale, n_split, workspace, qt, nm);                                   \
+                           (uint16_t *)out, n_head, n_kv_head, max_seq, scale, n_split, workspace, qt, nm, bs);                               \
         if (n_split > 1u)                                                                                                                     \
             hipLaunchKernelGGL(attn_combine_kernel<HD_>, dim3(n_head), dim3(HD_), 0, s, workspace, (uint16_t *)out, n_split, pos, max_seq);   \
     } while (0)
     AttnQkNorm<QKN> nm{};
     if constexpr (QKN) nm = AttnQkNorm<true>{(const uint16_t *)q_norm_weight, (const uint16_t *)k_norm_weight, eps};
+    AttnBias<QB> bs{};
+    if constexpr (QB) bs = AttnBias<true>{(const uint16_t *)qkv_bias};
     if (head_dim == 128) GQ_LAUNCH_ATTN(128);
     else GQ_LAUNCH_ATTN(64);
 #undef GQ_LAUNCH_ATTN
@@ -1059,6 +1088,15 @@ extern "C" int gq_attn_decode_split_qknorm(const void *qkv, const int *pos, cons
                                            const void *k_norm_weight, float eps, void *stream) {
     return attn_launch<false, true>(qkv, AttnQt{}, pos, cos_table, sin_table, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale,
                                     n_split, workspace, stream, q_norm_weight, k_norm_weight, eps);
+}
+
+// Qwen2 / Qwen2.5 layers: gq_attn_decode_split with the bias of the q / k / v linears (fp16 [(n_head + 2 n_kv_head) * head_dim], laid out
+// like the packed q | k | v vector, 16-byte aligned) added in fp16 in front of the rotation, inside the same launch
+extern "C" int gq_attn_decode_split_bias(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,
+                                         void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                                         float scale, uint32_t n_split, float *workspace, const void *qkv_bias, void *stream) {
+    return attn_launch<false, false, true>(qkv, AttnQt{}, pos, cos_table, sin_table, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq,
+                                           scale, n_split, workspace, stream, nullptr, nullptr, 0.f, qkv_bias);
 }
 
 // QTIP models: the same attention with the transform-out of the q, k and v linears folded in (qkv_lin[0..2]: the GqQtipOut

@@ -315,6 +315,16 @@ def random_init_(model: Transformer, seed: int = 0, lut_std: float = 0.02, cheap
             mod.qweight.copy_(torch.randint(-2**31, 2**31 - 1, mod.qweight.shape, dtype=torch.int32, device=dev, generator=gd))
             lut = (torch.randn(mod.lut.shape, device=dev, generator=gd) * lut_std).sort(dim=1).values
             mod.lut.copy_(lut.to(mod.lut.dtype))
+            if mod.bias is not None:
+                # (Qwen2's q / k / v bias: of the order of the q / k / v values themselves, and a few k entries -- the second quarter of the
+                # wqkv rows at most -- in the tens, as published Qwen2 k biases are)
+                bias = torch.randn(mod.bias.shape, device=dev, generator=gd)
+                if name.endswith("wqkv"):
+                    c = model.config
+                    k0, nk = c.n_head * c.head_dim, c.n_local_heads * c.head_dim
+                    big = k0 + torch.randperm(nk, device=dev, generator=gd)[:max(1, nk // 64)]
+                    bias[big] *= 30.0
+                mod.bias.copy_(bias.to(mod.bias.dtype))
         elif isinstance(mod, LUTGEMMLinear):
             mod.qweight.copy_(torch.randint(-2**31, 2**31 - 1, mod.qweight.shape, dtype=torch.int32, device=dev, generator=gd))
             mod.alpha.copy_((torch.rand(mod.alpha.shape, device=dev, generator=gd) * lut_std).to(mod.alpha.dtype))

@@ -1,5 +1,5 @@
 """Loader for HF-layout GuidedQuant / Any-Precision checkpoints: a directory with
-`config.json` (a Llama, Mistral or Qwen3 config plus the `anyprec` section, any_precision/modules/AnyPrecisionForCausalLM.py:43-47) and the
+`config.json` (a Llama, Mistral, Qwen2 or Qwen3 config plus the `anyprec` section, any_precision/modules/AnyPrecisionForCausalLM.py:43-47) and the
 weights as `pytorch_model.bin` or (sharded) safetensors with the HF keys `model.layers.{i}.self_attn.q_proj.{qweight,lut{b}}`
 (any_precision/quantization/pack.py:112-123) -> the fused gpt-fast `Transformer` of this package, ready for the HIP
 decode path.  Equivalent to running inference/sqllm_llama_convert_fuse.py and then inference/generate.py::load_model,
@@ -21,8 +21,13 @@ def _no_sliding_window(cfg: dict, what: str):
     lt = cfg.get("layer_types")
     if lt and any(t != "full_attention" for t in lt):
         raise NotImplementedError(f"{what}: layer_types {sorted(set(lt))} (only full_attention layers have a fused decode form)")
-    if what == "qwen3" and cfg.get("use_sliding_window"):
-        raise NotImplementedError("qwen3: use_sliding_window (sliding-window attention has no fused decode form)")
+    if what == "qwen2" and "use_sliding_window" not in cfg and not lt:
+        # (every Qwen2 config.json transformers has written carries `use_sliding_window`, and newer ones `layer_types` as well: a dict
+        # that names the model type and states neither is not such a file, and whether its layers attend over the whole cache is a guess)
+        raise NotImplementedError("qwen2: the config states neither use_sliding_window nor layer_types (a Qwen2 config.json does; the fused "
+                                  "decode form attends over the whole cache and does not guess)")
+    if what in ("qwen2", "qwen3") and cfg.get("use_sliding_window"):
+        raise NotImplementedError(f"{what}: use_sliding_window (sliding-window attention has no fused decode form)")
     sw = cfg.get("sliding_window")
     if what == "mistral" and sw is not None and int(sw) < int(cfg.get("max_position_embeddings", 8192)):
         raise NotImplementedError(f"mistral: sliding_window {sw} < max_position_embeddings (sliding-window attention has no fused decode form)")
@@ -32,12 +37,16 @@ def model_args_from_hf_config(cfg: dict) -> ModelArgs:
     """HF `config.json` -> ModelArgs (inference/model.py:27-51 field meanings), by `model_type`:
       llama (or no model_type)  the Llama block;
       mistral                   the same block, head_dim from the config when it has one; only without a sliding window that bites;
-      qwen3                     head_dim of its own and the per-head q / k RMSNorm (qk_norm); dense full-attention layers only.
-    Anything else (gemma3*, phi*, opt, qwen2 with its biased linears, MoE models, ..) raises NotImplementedError: the fused decode
+      qwen2                     (Qwen2 / Qwen2.5) the same block with a bias on q_proj / k_proj / v_proj (attn_bias); head_dim from the config
+                                when it has one, else hidden_size / num_attention_heads; dense full-attention layers only, and the
+                                config must say so (`use_sliding_window` or `layer_types`, as every Qwen2 config.json does);
+      qwen3                     head_dim of its own and the per-head q / k RMSNorm (qk_norm); dense full-attention layers only, no
+                                attention_bias.
+    Anything else (gemma3*, phi*, opt, MoE models, ..) raises NotImplementedError: the fused decode
     model knows these block layouts and no other, and a layout it does not know must not be decoded as if it were Llama's."""
     mt = str(cfg.get("model_type") or "llama").lower()
-    if mt not in ("llama", "mistral", "qwen3"):
-        raise NotImplementedError(f"model_type {mt!r} has no fused decode form (llama, mistral without a sliding window, qwen3 dense have)")
+    if mt not in ("llama", "mistral", "qwen2", "qwen3"):
+        raise NotImplementedError(f"model_type {mt!r} has no fused decode form (llama, mistral without a sliding window, qwen2 and qwen3 dense have)")
     name = os.path.basename(str(cfg.get("_name_or_path") or mt).rstrip("/")) or mt
     if mt not in name.lower():  # (the block layout is the model type's whatever the checkpoint directory is called)
         name = mt + "-" + name
@@ -46,9 +55,11 @@ def model_args_from_hf_config(cfg: dict) -> ModelArgs:
         _no_sliding_window(cfg, mt)
         if cfg.get("head_dim"):
             extra["head_dim"] = int(cfg["head_dim"])
+    if mt == "qwen2":  # (modeling_qwen2.Qwen2Attention: q_proj / k_proj / v_proj with bias=True, o_proj and the MLP without)
+        extra["attn_bias"] = True
     if mt == "qwen3":
         if cfg.get("attention_bias"):
-            raise NotImplementedError("qwen3: attention_bias (biased linears have no fused decode form)")
+            raise NotImplementedError("qwen3: attention_bias (the fused decode step has no form with both the per-head norm and a bias)")
         extra["qk_norm"] = True
     rope_theta, rope_scaling = cfg.get("rope_theta"), cfg.get("rope_scaling")
     rp = cfg.get("rope_parameters")  # (newer transformers keep base and scaling together)

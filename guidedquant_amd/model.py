@@ -18,7 +18,9 @@ Two execution paths:
 
 Block layouts: Llama's, and with `ModelArgs.head_dim` / `qk_norm` Mistral's and Qwen3's (RMSNorm over head_dim on every q and k head in
 front of the rotation, modeling_qwen3.Qwen3Attention.forward): in `Attention.forward` for the module path, inside the attention launch
-(gq_attn_decode_split_qknorm) and the prompt pass's RoPE launch (gq_qknorm_rope_cache_rows) for the HIP path.
+(gq_attn_decode_split_qknorm) and the prompt pass's RoPE launch (gq_qknorm_rope_cache_rows) for the HIP path.  With `attn_bias` Qwen2's /
+Qwen2.5's (modeling_qwen2.Qwen2Attention: a bias on q_proj / k_proj / v_proj, none on o_proj or the MLP): the quantized linear adds it in the
+module path and the prompt pass, the attention launch (gq_attn_decode_split_bias) in the decode step.
 
 Model table: the reference's entries (model.py:53-61) plus Llama-3.2-1B-Instruct and Llama-3.3-70B-Instruct, which
 BASELINE.json's configs name and the reference table lacks.
@@ -56,6 +58,7 @@ class ModelArgs:
     rope_scaling: Optional[dict] = None
     model_name: Optional[str] = None
     qk_norm: bool = False  # Qwen3: RMSNorm over head_dim on every q and k head in front of the rotation
+    attn_bias: bool = False  # Qwen2 / Qwen2.5: q / k / v linears carry a bias (wo and the MLP do not)
 
     def __post_init__(self):
         if self.n_local_heads == -1:
@@ -93,6 +96,9 @@ transformer_configs = {
     # a checkpoint's own config.json goes through hf_loader.model_args_from_hf_config.
     "Qwen/Qwen3-8B": dict(model_name="Qwen3-8B", block_size=8192, n_layer=36, n_head=32, n_local_heads=8, dim=4096, head_dim=128, intermediate_size=12288,
                           vocab_size=151936, rope_base=1000000, norm_eps=1e-6, qk_norm=True),
+    # Qwen2.5 dense (q / k / v bias).  Restated from memory like the Qwen3 entry: a shape set for --random_init runs and timing.
+    "Qwen/Qwen2.5-7B": dict(model_name="Qwen2.5-7B", block_size=8192, n_layer=28, n_head=28, n_local_heads=4, dim=3584, head_dim=128,
+                            intermediate_size=18944, vocab_size=152064, rope_base=1000000, norm_eps=1e-6, attn_bias=True),
 }
 
 
@@ -204,11 +210,11 @@ class Attention(nn.Module):
         super().__init__()
         total_head_dim = (config.n_head + 2 * config.n_local_heads) * config.head_dim
         if fuse_linears:
-            self.wqkv = linear_class(config.dim, total_head_dim, bias=False, **(linear_kwargs or {}))
+            self.wqkv = linear_class(config.dim, total_head_dim, bias=config.attn_bias, **(linear_kwargs or {}))
         else:
-            self.wq = linear_class(config.dim, config.n_head * config.head_dim, bias=False, **(linear_kwargs or {}))
-            self.wk = linear_class(config.dim, config.n_local_heads * config.head_dim, bias=False, **(linear_kwargs or {}))
-            self.wv = linear_class(config.dim, config.n_local_heads * config.head_dim, bias=False, **(linear_kwargs or {}))
+            self.wq = linear_class(config.dim, config.n_head * config.head_dim, bias=config.attn_bias, **(linear_kwargs or {}))
+            self.wk = linear_class(config.dim, config.n_local_heads * config.head_dim, bias=config.attn_bias, **(linear_kwargs or {}))
+            self.wv = linear_class(config.dim, config.n_local_heads * config.head_dim, bias=config.attn_bias, **(linear_kwargs or {}))
         self.wo = linear_class(config.n_head * config.head_dim, config.dim, bias=False, **(linear_kwargs or {}))
         if config.qk_norm:  # (modeling_qwen3.Qwen3Attention: Qwen3RMSNorm(head_dim) -- RMSNorm.forward has its rounding points)
             self.q_norm = RMSNorm(config.head_dim, eps=config.norm_eps)
@@ -317,7 +323,7 @@ class TransformerBlock(nn.Module):
         super().__init__()
         self.attention = Attention(config, linear_class, linear_kwargs, fuse_linears)
         self.feed_forward = FeedForward(config, linear_class, linear_kwargs, fuse_linears)
-        if any(n in config.model_name.lower() for n in ("llama", "mistral", "qwen3")):  # (one block layout: pre-norm, gated MLP)
+        if any(n in config.model_name.lower() for n in ("llama", "mistral", "qwen3", "qwen2")):  # (one block layout: pre-norm, gated MLP)
             self.input_layernorm = RMSNorm(config.dim, config.norm_eps)
             self.post_attention_layernorm = RMSNorm(config.dim, config.norm_eps)
         else:
@@ -414,7 +420,12 @@ class Transformer(nn.Module):
         if self.config.qk_norm and (self.config.head_dim not in (64, 128) or not self.fuse_linears):
             pass  # (QK-norm is served by gq_attn_decode_split_qknorm, head_dim 64 / 128, fused Any-Precision models: else the module forward)
         elif self.fuse_linears:
-            if all(isinstance(m, APLinear) and m.bias is None and m.bitwidth <= 8 and m.in_features % 128 == 0
+            # (a bias only where the block layout has one -- wqkv of an attn_bias model -- and the attention launch that adds it serves the
+            # head_dim: gq_attn_decode_split_bias, 64 / 128; a bias anywhere else has no fused form)
+            # (and not next to QK-norm: the bias form and the norm form of the launch do not combine)
+            qkv_bias_ok = self.config.attn_bias and not self.config.qk_norm and self.config.head_dim in (64, 128)
+            if all(isinstance(m, APLinear) and (m.bias is None or (qkv_bias_ok and m is b.attention.wqkv)) and m.bitwidth <= 8
+                   and m.in_features % 128 == 0
                    for b in self.layers for m in (b.attention.wqkv, b.attention.wo, b.feed_forward.w1w3, b.feed_forward.w2)):
                 kind = "ap"
         elif native_step.native_qtip():

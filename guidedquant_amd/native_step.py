@@ -109,9 +109,9 @@ class StepState(_Keyed):
         # grouped-query models whose wqkv launch rotates q / k (gq_attn_decode_roped): the four query heads of a KV group share a
         # block, so the splits can be as short as one 128-position pass -- n_kv_head x n_split blocks ~ one per CU
         l0 = model.layers[0].attention
-        # (not for QK-norm models: their wqkv launch never rotates, see ApStep.layers)
+        # (not for QK-norm or attn_bias models: their wqkv launch never rotates, see ApStep.layers)
         if (S > 1024 and c.n_head % (4 * c.n_local_heads) == 0 and model._native_kind() != "qtip" and attn_gqa()
-                and not c.qk_norm and _lib.lib().gq_anyprec_qkv_rope_supported(l0.wqkv.out_features, c.dim, l0.wqkv.bitwidth, c.head_dim)):
+                and not c.qk_norm and not c.attn_bias and _lib.lib().gq_anyprec_qkv_rope_supported(l0.wqkv.out_features, c.dim, l0.wqkv.bitwidth, c.head_dim)):
             ns = max(4, min(32, (S + 127) // 128, 256 // max(1, c.n_head // 4)))
         self.attn_split = attn_split_knob(ns)
         self.attn_ws = torch.zeros(c.n_head * self.attn_split * (c.head_dim + 2), dtype=torch.float32, device=dev) if self.attn_split > 1 else None
@@ -123,7 +123,7 @@ class StepState(_Keyed):
         return at.kv_cache.k_cache.data_ptr() + off, at.kv_cache.v_cache.data_ptr() + off
 
     def attend(self, entry, src, pos, kv, sp, extra=()):
-        """the attention launch, entry = gq_attn_decode_split / _split_qknorm / _roped / _qtip.  src: the packed q | k | v vector (or
+        """the attention launch, entry = gq_attn_decode_split / _split_qknorm / _split_bias / _roped / _qtip.  src: the packed q | k | v vector (or
         the q / k / v descriptors of gq_attn_decode_qtip); _roped takes no tables (the wqkv launch rotated); extra: what an entry
         point takes behind the workspace"""
         m, c = self.m, self.m.config
@@ -227,6 +227,12 @@ class ApStep(StepState):
                 # normalises, rotates, writes the cache row and attends
                 launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
                 self.attend("gq_attn_decode_split_qknorm", qkv, pos, kv, sp, (at.q_norm.weight.data_ptr(), at.k_norm.weight.data_ptr(), at.q_norm.eps))
+            elif at.wqkv.bias is not None:
+                # Qwen2 / Qwen2.5: the bias of q / k / v belongs in front of the rotation, and the RoPE epilogues of the wqkv launch
+                # (gq_anyprec_gemv_qkv_rope*) rotate what the GEMV summed -- the unbiased q / k.  Plain wqkv GEMV, then ONE attention launch
+                # that adds the bias, rotates, writes the cache row and attends (_native_kind admits a bias here only on attn_bias models)
+                launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
+                self.attend("gq_attn_decode_split_bias", qkv, pos, kv, sp, (at.wqkv.bias.data_ptr(),))
             elif (self.attn_split == 1 and ssq_in is None
                     and L.gq_anyprec_qkv_rope_attn_supported(at.wqkv.out_features, c.dim, at.wqkv.bitwidth, c.head_dim, c.n_head, c.n_local_heads)):
                 # round 6: the attention heads as extra blocks of the wqkv launch (they wait on device flags for q / the new cache row):

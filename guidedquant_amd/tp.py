@@ -37,9 +37,11 @@ class TensorParallelDecoder:
     def __init__(self, model: Transformer, group, rank: int, world: int, max_new_tokens: int, temperature=0.0, top_k=32, seed=1234, bos_id=1):
         c = model.config
         assert model.fuse_linears, "tensor-parallel decode takes the fused (wqkv / w1w3) Any-Precision model"
-        if c.qk_norm or c.n_head * c.head_dim != c.dim:
-            # (this class builds its own launches: no QK-norm attention, and the attention output is exchanged as a dim-wide vector)
-            raise NotImplementedError("tensor-parallel decode serves the Llama block only: no QK-norm (Qwen3), no head_dim other than dim / n_head")
+        if c.qk_norm or c.attn_bias or c.n_head * c.head_dim != c.dim:
+            # (this class builds its own launches: no QK-norm attention, no q / k / v bias, and the attention output is exchanged as a
+            # dim-wide vector)
+            raise NotImplementedError("tensor-parallel decode serves the Llama block only: no QK-norm (Qwen3), no q / k / v bias (Qwen2), "
+                                      "no head_dim other than dim / n_head")
         assert c.n_head % world == 0 and c.n_local_heads % world == 0 and c.dim % (16 * world) == 0 and c.intermediate_size % (16 * world) == 0, \
             "heads, KV heads, dim / 16 and intermediate / 16 must divide by the world size"
         self.model, self.group, self.rank, self.world = model, group, rank, world

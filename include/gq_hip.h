@@ -446,6 +446,16 @@ int gq_attn_decode_split_qknorm(const void *qkv, const int *pos, const void *cos
                                 void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
                                 float scale, uint32_t n_split, float *workspace, const void *q_norm_weight, const void *k_norm_weight,
                                 float eps, void *stream);
+/* Qwen2 / Qwen2.5 layers: gq_attn_decode_split with the bias of the q / k / v linears added in front of the rotation, inside the
+ * same launch.  Restates the bias add of the quantized linears (any_precision/modules/AnyPrecisionLinear.py: the GEMV result rounded
+ * to fp16, then `output += bias`, ONE fp16 add) for transformers' modeling_qwen2.Qwen2Attention (q_proj / k_proj / v_proj with
+ * bias=True, o_proj without): fp16(q[d]) + fp16(bias[d]) for every q, k and v element, then the rotation of q and k; the cache
+ * receives the biased, rotated k and the biased v.  Bit-identical to gq_attn_decode_split on a vector the bias was added to in fp16.
+ * qkv_bias: fp16 [(n_head + 2 n_kv_head) * head_dim], laid out like the packed q | k | v vector, 16-byte aligned.  head_dim 64 or
+ * 128; n_split, workspace and the NaN result at *pos >= max_seq as gq_attn_decode_split. */
+int gq_attn_decode_split_bias(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,
+                              void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                              float scale, uint32_t n_split, float *workspace, const void *qkv_bias, void *stream);
 
 /*
  * Device-to-device hand-over of the layer pipeline (round 4; reference precedent: the host-side `.to(device)` hops of

@@ -16,6 +16,11 @@ would be cut to it).
 Prints one JSON record and merges it into profiles/qwen3_fused_route.json under "timing_published_vocab" (other keys of that file are
 kept: "timing" is the record taken while the sampler stopped at 131072 logits, with Qwen3's vocabulary cut to that).
     python tools/qwen3_decode_timing.py [--steps 20] [--warmup 5] [--repeats 3] [--no-module-tree]
+
+`--arch qwen2`: the same protocol for the Qwen2.5-7B geometry (28 layers, hidden 3584, MLP 18944, 28 / 4 heads of 128, vocab 152064, a bias
+on q / k / v; restated from memory like the Qwen3 figures) -- the fused route (plain wqkv GEMV, then gq_attn_decode_split_bias) against
+the module-tree route (`generate(native=False)` over transformers' Qwen2 modules) in the same run.  Written to
+profiles/qwen2_fused_route.json under "timing".
 """
 import argparse
 import json
@@ -27,8 +32,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 QWEN3 = "Qwen/Qwen3-8B"
+QWEN2 = "Qwen/Qwen2.5-7B"
 LLAMA = "meta-llama/Meta-Llama-3.1-8B-Instruct"
 OUT = os.path.join(ROOT, "profiles", "qwen3_fused_route.json")
+OUT_QWEN2 = os.path.join(ROOT, "profiles", "qwen2_fused_route.json")
 
 
 def timed_config(name):
@@ -72,16 +79,21 @@ def fused_tok_s(name, dev, steps, warmup, repeats):
     return rec
 
 
-def module_tree_tok_s(dev, new_tokens=100):
-    """route 3 of AnyPrecisionForCausalLM.generate on the Qwen3-8B geometry (random 2-bit planes), and the plain call (route 1) beside it"""
+def module_tree_tok_s(dev, new_tokens=100, name=QWEN3):
+    """route 3 of AnyPrecisionForCausalLM.generate on the Qwen3-8B (or Qwen2.5-7B) geometry (random 2-bit planes), and the plain call
+    (route 1) beside it"""
     import torch
     import transformers
     from guidedquant_amd.AnyPrecisionForCausalLM import AnyPrecisionForCausalLM
-    c = timed_config(QWEN3)
-    cfg = transformers.Qwen3Config(hidden_size=c["dim"], intermediate_size=c["intermediate_size"], num_hidden_layers=c["n_layer"],
-                                   num_attention_heads=c["n_head"], num_key_value_heads=c["n_local_heads"], head_dim=c["head_dim"],
-                                   vocab_size=c["vocab_size"], max_position_embeddings=c["block_size"], rms_norm_eps=c["norm_eps"],
-                                   tie_word_embeddings=False)
+    c = timed_config(name)
+    kw = dict(hidden_size=c["dim"], intermediate_size=c["intermediate_size"], num_hidden_layers=c["n_layer"], num_attention_heads=c["n_head"],
+              num_key_value_heads=c["n_local_heads"], vocab_size=c["vocab_size"], max_position_embeddings=c["block_size"], rms_norm_eps=c["norm_eps"],
+              tie_word_embeddings=False)
+    if name == QWEN2:  # (head_dim = hidden_size / num_attention_heads; the q / k / v biases are part of the module tree)
+        assert c["dim"] // c["n_head"] == c["head_dim"]
+        cfg = transformers.Qwen2Config(**kw)
+    else:
+        cfg = transformers.Qwen3Config(head_dim=c["head_dim"], **kw)
     names = ["self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"]
     cfg.anyprec = dict(seed_precision=2, parent_precision=2, group_count=1, arch_config=dict(module_names=names, model_name="model", layers_name="layers"))
     m = AnyPrecisionForCausalLM.from_config_random(cfg, device=dev, seed=0)
@@ -106,11 +118,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--no-module-tree", action="store_true")
+    ap.add_argument("--arch", choices=["qwen3", "qwen2"], default="qwen3")
     args = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "needs a GPU (the HIP path has no fallback)"
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
+    if args.arch == "qwen2":
+        return main_qwen2(args, dev)
     rec = dict(protocol="bench.py headline: random init, 2-bit, DecodeGraph with 10 steps per replay, %d warm-up steps, %d-step window, %d windows"
                % (args.warmup, args.steps, args.repeats),
                qwen3_fused=fused_tok_s(QWEN3, dev, args.steps, args.warmup, args.repeats),
@@ -125,6 +140,25 @@ def main():
             whole = json.load(f)
     whole["timing_published_vocab"] = rec
     with open(OUT, "w") as f:
+        json.dump(whole, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+
+
+def main_qwen2(args, dev):
+    rec = dict(protocol="bench.py headline: random init, 2-bit, DecodeGraph with 10 steps per replay, %d warm-up steps, %d-step window, %d windows; "
+               "module tree: generate(native=False), 100 new tokens after an 8-token warm-up call" % (args.warmup, args.steps, args.repeats),
+               qwen2_fused=fused_tok_s(QWEN2, dev, args.steps, args.warmup, args.repeats))
+    if not args.no_module_tree:
+        rec["qwen2_hf_generate"] = module_tree_tok_s(dev, name=QWEN2)
+        rec["fused_over_module_tree"] = round(max(rec["qwen2_fused"]["tok_s"]) / rec["qwen2_hf_generate"]["module_tree_tok_s"], 2)
+        assert rec["qwen2_hf_generate"]["plain_call_on_fused_route"]
+    whole = {}
+    if os.path.exists(OUT_QWEN2):
+        with open(OUT_QWEN2) as f:
+            whole = json.load(f)
+    whole["timing"] = rec
+    with open(OUT_QWEN2, "w") as f:
         json.dump(whole, f, indent=1)
         f.write("\n")
     print(json.dumps(rec))
