@@ -620,7 +620,7 @@ class AnyPrecisionForCausalLM(nn.Module):
         if bitwidth not in self.precisions:
             raise ValueError(f"bitwidth {bitwidth} not among the loaded precisions {self.precisions}")
         cfg = self.config.to_dict() if hasattr(self.config, "to_dict") else dict(self.config)
-        args = model_args_from_hf_config(cfg)
+        args = model_args_from_hf_config(cfg, sliding_window=True)
         dev = self.device
         with torch.device("meta"):
             dec = Transformer(torch.float16, args, linear_class=APLinear, linear_kwargs=dict(bitwidth=bitwidth, device="meta"), fuse_linears=True)

@@ -122,11 +122,28 @@ template <>
 struct AttnBias<true> {
     const uint16_t *qkv;  // fp16 [(H + 2 Hkv) * HD]
 };
-template <int HD, bool QT, bool QKN = false, bool QB = false>
+// WIN (sliding-window layers: transformers' masking_utils.sliding_window_overlay on top of the causal mask): the query at position pos
+// attends the cached rows (pos - W, pos] -- lo = max(0, pos + 1 - W), n = pos + 1 - lo rows.  The geometry of a launch is that of the
+// launch without a window at position n - 1, shifted by lo: the solo rule and the split length are taken from n, split s covers
+// [lo + s per, ..), row t takes the (pass, wave, u, sub) slot row t - lo has there; merge and combine order as they are.  No row below lo
+// is requested behind the position read (they hold real rows of the sequence).  A compile-time form like QKN / QB: the WIN = false
+// instances take an empty argument and keep the instructions they had.  W >= 1 (checked by the host), so lo <= pos: nothing underflows.
+template <bool WIN>
+struct AttnWindow {};  // (nothing to pass)
+template <>
+struct AttnWindow<true> {
+    u32 w;  // rows a query attends, itself included
+};
+template <bool WIN>
+__device__ __forceinline__ u32 window_lo(u32 pos, const AttnWindow<WIN> &wn) {
+    if constexpr (WIN) return pos + 1u > wn.w ? pos + 1u - wn.w : 0u;
+    else return 0u;
+}
+template <int HD, bool QT, bool QKN = false, bool QB = false, bool WIN = false>
 __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint16_t *qkv, const int *pos_ptr, const uint16_t *cos_t,
                                                           const uint16_t *sin_t, uint16_t *kc, uint16_t *vc, uint16_t *out,
                                                           u32 H, u32 Hkv, u32 max_seq, float scale, u32 nsplit, float *ws, AttnQt qt,
-                                                          AttnQkNorm<QKN> nm, AttnBias<QB> bs) {
+                                                          AttnQkNorm<QKN> nm, AttnBias<QB> bs, AttnWindow<WIN> wn) {
     static_assert(!(QB && (QT || QKN)), "the bias form is the plain fp16 q / k / v form plus the add");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr u32 NW = ATTN_WAVES;
@@ -242,13 +259,14 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
     const u32 sp = blockIdx.y;
     // a short context (up to two passes) is not worth splitting: split 0 does it all and writes the result itself, the
     // other blocks and the combine launch return at once
-    const bool solo = nsplit > 1u && pos + 1u <= 2u * PASS;
+    const u32 lo = window_lo(pos, wn), n = pos + 1u - lo;  // (WIN = false: lo = 0, n = pos + 1)
+    const bool solo = nsplit > 1u && n <= 2u * PASS;
     if (solo) {
         if (sp > 0u) return;
         nsplit = 1u;
     }
-    const u32 per = nsplit > 1u ? (((pos + nsplit) / nsplit + PASS - 1u) / PASS) * PASS : pos + 1u;
-    const u32 p0 = sp * per, p1 = min(pos + 1u, p0 + per);  // (p0 >= p1: nothing to do, a neutral partial result is written)
+    const u32 per = nsplit > 1u ? (((n - 1u + nsplit) / nsplit + PASS - 1u) / PASS) * PASS : n;
+    const u32 p0 = lo + sp * per, p1 = min(pos + 1u, p0 + per);  // (p0 >= p1: nothing to do, a neutral partial result is written)
     const bool has_cur = p0 <= pos && pos < p1;             // the split that covers the current token
     if constexpr (QKN) {
         // per-head statistics: thread d < HD holds element d of q and of k (the other waves add zeros); fixed order
@@ -409,9 +427,12 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
 // (19 us per layer on Llama-3-8B); here the next pass is requested before the current one is multiplied.  Per head the
 // arithmetic, the position -> stream assignment and the merge order are those of the QH = 1 form: bit-identical outputs.
 // A short context (the `solo` rule) is finished by ONE block per head: block (hq, sp < QH) takes head hq * QH + sp alone.
-template <int HD, int QH>
+// WIN: the window form (see attn_decode_kernel).  The rows requested ahead of the position are usable only when lo == 0; with lo > 0 they
+// are dropped (p0 >= lo > 0 below) and the first batch is requested once lo is known.
+template <int HD, int QH, bool WIN = false>
 __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint16_t *q, const int *pos_ptr, const uint16_t *kc, const uint16_t *vc,
-                                                                     uint16_t *out, u32 H, u32 Hkv, u32 max_seq, float scale, u32 nsplit, float *ws) {
+                                                                     uint16_t *out, u32 H, u32 Hkv, u32 max_seq, float scale, u32 nsplit, float *ws,
+                                                                     AttnWindow<WIN> wn) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr u32 NW = ATTN_WAVES;
     constexpr int LPP = HD / 8, PPW = 64 / LPP, U = 4;
@@ -449,7 +470,8 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         if (sp == 0u && tid < (u32)QH * HD) out[(size_t)h0 * HD + tid] = 0x7e00u;
         return;
     }
-    const bool solo = nsplit > 1u && pos + 1u <= 2u * PASS;  // a short context is not worth splitting (see attn_decode_kernel)
+    const u32 lo = window_lo(pos, wn), n = pos + 1u - lo;  // (WIN = false: lo = 0, n = pos + 1)
+    const bool solo = nsplit > 1u && n <= 2u * PASS;  // a short context is not worth splitting (see attn_decode_kernel)
     u32 nh = QH, hb = h0;  // heads of this block: [hb, hb + nh)
     if (solo) {
         if (sp >= (u32)QH) return;
@@ -457,8 +479,8 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         nsplit = 1u;
     }
     const u32 spx = solo ? 0u : sp;
-    const u32 per = nsplit > 1u ? (((pos + nsplit) / nsplit + PASS - 1u) / PASS) * PASS : pos + 1u;
-    const u32 p0 = spx * per, p1 = min(pos + 1u, p0 + per);
+    const u32 per = nsplit > 1u ? (((n - 1u + nsplit) / nsplit + PASS - 1u) / PASS) * PASS : n;
+    const u32 p0 = lo + spx * per, p1 = min(pos + 1u, p0 + per);
     float qreg[QH][8];
 #pragma unroll
     for (int qh = 0; qh < QH; qh++) {
@@ -606,13 +628,17 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
 }
 
 // split-KV combine: out[h] = sum_s o_s e^(M_s - M) / sum_s l_s e^(M_s - M)
-template <int HD>
-__global__ void __launch_bounds__(HD) attn_combine_kernel(const float *ws, uint16_t *out, u32 nsplit, const int *pos_ptr, u32 max_seq) {
+template <int HD, bool WIN = false>
+__global__ void __launch_bounds__(HD) attn_combine_kernel(const float *ws, uint16_t *out, u32 nsplit, const int *pos_ptr, u32 max_seq, AttnWindow<WIN> wn) {
     const u32 h = blockIdx.x, tid = threadIdx.x;
     {   // (the same rule as in attn_decode_kernel: a short context was finished by split 0)
         constexpr u32 PASS = ATTN_WAVES * (64u / (HD / 8u)) * 4u;
         u32 pos = (u32)pos_ptr[0];
-        if (pos >= max_seq || pos + 1u <= 2u * PASS) return;
+        if constexpr (WIN) {  // (the rule on the n rows of the window)
+            if (pos >= max_seq || pos + 1u - window_lo(pos, wn) <= 2u * PASS) return;
+        } else {
+            if (pos >= max_seq || pos + 1u <= 2u * PASS) return;
+        }
     }
     const float *wp = ws + (size_t)h * nsplit * (HD + 2u);
     // Every load of this kernel reads what another CU has just written (an L2 miss each): a loop with one dependent load per split
@@ -1032,12 +1058,14 @@ extern "C" int gq_embed_lookup_ho(const int *token, const void *table, void *out
 }
 
 namespace {
-template <bool QT, bool QKN = false, bool QB = false>
+template <bool QT, bool QKN = false, bool QB = false, bool WIN = false>
 int attn_launch(const void *qkv, const AttnQt &qt, const int *pos, const void *cos_table, const void *sin_table, void *k_cache, void *v_cache,
                 void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split,
                 float *workspace, void *stream, const void *q_norm_weight = nullptr, const void *k_norm_weight = nullptr, float eps = 0.f,
-                const void *qkv_bias = nullptr) {
+                const void *qkv_bias = nullptr, uint32_t window = 0u) {
     static_assert(!(QT && QKN), "the QK-norm form reads fp16 q / k / v");
+    static_assert(!(QT && WIN), "the QTIP form has no window form");
+    if (WIN && window == 0u) return gq_fail(GQ_EINVAL, "window must be at least 1 (the query attends itself).");
     static_assert(!(QB && (QT || QKN)), "the bias form does not combine with the QTIP or the QK-norm form");
     if ((!QT && !qkv) || !pos || !cos_table || !sin_table || !k_cache || !v_cache || !out) return gq_fail(GQ_EINVAL, "null pointer argument.");
     if (QKN && (!q_norm_weight || !k_norm_weight)) return gq_fail(GQ_EINVAL, "null pointer argument.");
@@ -1054,13 +1082,16 @@ int attn_launch(const void *qkv, const AttnQt &qt, const int *pos, const void *c
 #define GQ_LAUNCH_ATTN(HD_)                                                                                                                   \
     do {                                                                                                                                      \
         static GqPerDeviceOnce once;                                                                                                          \
-        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_decode_kernel<HD_, QT, QKN, QB>), 160 * 1024));                 \
-        hipLaunchKernelGGL((attn_decode_kernel<HD_, QT, QKN, QB>), grid, dim3(64 * ATTN_WAVES), smem, s, (const uint16_t *)qkv, pos,          \
+        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_decode_kernel<HD_, QT, QKN, QB, WIN>), 160 * 1024));            \
+        hipLaunchKernelGGL((attn_decode_kernel<HD_, QT, QKN, QB, WIN>), grid, dim3(64 * ATTN_WAVES), smem, s, (const uint16_t *)qkv, pos,     \
                            (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)k_cache, (uint16_t *)v_cache,                \
-                           (uint16_t *)out, n_head, n_kv_head, max_seq, scale, n_split, workspace, qt, nm, bs);                               \
+                           (uint16_t *)out, n_head, n_kv_head, max_seq, scale, n_split, workspace, qt, nm, bs, wn);                           \
         if (n_split > 1u)                                                                                                                     \
-            hipLaunchKernelGGL(attn_combine_kernel<HD_>, dim3(n_head), dim3(HD_), 0, s, workspace, (uint16_t *)out, n_split, pos, max_seq);   \
+            hipLaunchKernelGGL((attn_combine_kernel<HD_, WIN>), dim3(n_head), dim3(HD_), 0, s, workspace, (uint16_t *)out, n_split, pos,      \
+                               max_seq, wn);                                                                                                  \
     } while (0)
+    AttnWindow<WIN> wn{};
+    if constexpr (WIN) wn = AttnWindow<true>{window};
     AttnQkNorm<QKN> nm{};
     if constexpr (QKN) nm = AttnQkNorm<true>{(const uint16_t *)q_norm_weight, (const uint16_t *)k_norm_weight, eps};
     AttnBias<QB> bs{};
@@ -1099,6 +1130,29 @@ extern "C" int gq_attn_decode_split_bias(const void *qkv, const int *pos, const 
                                            scale, n_split, workspace, stream, nullptr, nullptr, 0.f, qkv_bias);
 }
 
+// Sliding-window layers (Mistral, Qwen2 / Qwen3 with use_sliding_window): the three forms above over the cached rows (*pos - window, *pos]
+// only -- the geometry of the launch without a window at position n - 1, shifted by lo (see attn_decode_kernel, WIN)
+extern "C" int gq_attn_decode_split_window(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,
+                                           void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                                           float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream) {
+    return attn_launch<false, false, false, true>(qkv, AttnQt{}, pos, cos_table, sin_table, k_cache, v_cache, out, n_head, n_kv_head, head_dim,
+                                                  max_seq, scale, n_split, workspace, stream, nullptr, nullptr, 0.f, nullptr, window);
+}
+extern "C" int gq_attn_decode_split_qknorm_window(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,
+                                                  void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim,
+                                                  uint32_t max_seq, float scale, uint32_t n_split, float *workspace, const void *q_norm_weight,
+                                                  const void *k_norm_weight, float eps, uint32_t window, void *stream) {
+    return attn_launch<false, true, false, true>(qkv, AttnQt{}, pos, cos_table, sin_table, k_cache, v_cache, out, n_head, n_kv_head, head_dim,
+                                                 max_seq, scale, n_split, workspace, stream, q_norm_weight, k_norm_weight, eps, nullptr, window);
+}
+extern "C" int gq_attn_decode_split_bias_window(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,
+                                                void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                                                float scale, uint32_t n_split, float *workspace, const void *qkv_bias, uint32_t window,
+                                                void *stream) {
+    return attn_launch<false, false, true, true>(qkv, AttnQt{}, pos, cos_table, sin_table, k_cache, v_cache, out, n_head, n_kv_head, head_dim,
+                                                 max_seq, scale, n_split, workspace, stream, nullptr, nullptr, 0.f, qkv_bias, window);
+}
+
 // QTIP models: the same attention with the transform-out of the q, k and v linears folded in (qkv_lin[0..2]: the GqQtipOut
 // descriptors gq_qtip_linear_out would take; resid / out unused).  Equal to gq_qtip_linear_out + gq_attn_decode_split up to fp32
 // rounding (the segments are combined first: the additions of the full transform in another order), not bit for bit.
@@ -1125,9 +1179,13 @@ extern "C" int gq_attn_decode_qtip(const GqQtipOut *qkv_lin, const int *pos, con
 
 // Attention of the decode step when the wqkv launch has already rotated q / k and written k / v of the current token into the
 // caches (gq_anyprec_gemv_qkv_rope): q fp16 [n_head * head_dim] rotated; the caches hold every position <= *pos.
-extern "C" int gq_attn_decode_roped(const void *q, const int *pos, const void *k_cache, const void *v_cache, void *out, uint32_t n_head,
-                                    uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split, float *workspace,
-                                    void *stream) {
+namespace {
+template <bool WIN>
+int roped_launch(const void *q, const int *pos, const void *k_cache, const void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head,
+                 uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream) {
+    if (WIN && window == 0u) return gq_fail(GQ_EINVAL, "window must be at least 1 (the query attends itself).");
+    AttnWindow<WIN> wn{};
+    if constexpr (WIN) wn = AttnWindow<true>{window};
     if (!q || !pos || !k_cache || !v_cache || !out) return gq_fail(GQ_EINVAL, "null pointer argument.");
     if (n_kv_head == 0 || n_head % n_kv_head) return gq_fail(GQ_EINVAL, "n_head must be a multiple of n_kv_head.");
     if (head_dim != 64 && head_dim != 128) return gq_fail(GQ_ENOTSUP, "head_dim must be 64 or 128.");
@@ -1143,11 +1201,11 @@ extern "C" int gq_attn_decode_roped(const void *q, const int *pos, const void *k
     const u32 qh = gqa_p || gqa ? 4u : 1u;
     const size_t smem = (size_t)qh * ((size_t)2u * nstreams + (size_t)nstreams * head_dim + nstreams + 1u) * 4u;
     const dim3 grid(n_head / qh, gqa_p ? copies : n_split);
-    if (gqa_p) {
+    if (gqa_p && !WIN) {
         static GqPerDeviceOnce once;
         GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<128, 4>), 160 * 1024));
         hipLaunchKernelGGL((attn_roped_kernel<128, 4>), grid, dim3(64 * ATTN_WAVES), smem, s, (const uint16_t *)q, pos, (const uint16_t *)k_cache,
-                           (const uint16_t *)v_cache, (uint16_t *)out, n_head, n_kv_head, max_seq, scale, 1u, workspace);
+                           (const uint16_t *)v_cache, (uint16_t *)out, n_head, n_kv_head, max_seq, scale, 1u, workspace, AttnWindow<false>{});
         GQ_HIP_CHECK(hipGetLastError());
         return GQ_OK;
     }
@@ -1159,12 +1217,13 @@ extern "C" int gq_attn_decode_roped(const void *q, const int *pos, const void *k
 #define GQ_LAUNCH_ROPED(HD_, QH_)                                                                                                    \
     do {                                                                                                                             \
         static GqPerDeviceOnce once;                                                                                                 \
-        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<HD_, QH_>), 160 * 1024));                  \
-        hipLaunchKernelGGL((attn_roped_kernel<HD_, QH_>), grid, dim3(64 * ATTN_WAVES), smem, s, (const uint16_t *)q, pos,             \
+        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<HD_, QH_, WIN>), 160 * 1024));             \
+        hipLaunchKernelGGL((attn_roped_kernel<HD_, QH_, WIN>), grid, dim3(64 * ATTN_WAVES), smem, s, (const uint16_t *)q, pos,        \
                            (const uint16_t *)k_cache, (const uint16_t *)v_cache, (uint16_t *)out, n_head, n_kv_head, max_seq, scale,   \
-                           n_split, workspace);                                                                                      \
+                           n_split, workspace, wn);                                                                                  \
         if (n_split > 1u)                                                                                                            \
-            hipLaunchKernelGGL(attn_combine_kernel<HD_>, dim3(n_head), dim3(HD_), 0, s, workspace, (uint16_t *)out, n_split, pos, max_seq); \
+            hipLaunchKernelGGL((attn_combine_kernel<HD_, WIN>), dim3(n_head), dim3(HD_), 0, s, workspace, (uint16_t *)out, n_split,   \
+                               pos, max_seq, wn);                                                                                    \
     } while (0)
     if (head_dim == 128) {
         if (gqa) GQ_LAUNCH_ROPED(128, 4);
@@ -1176,6 +1235,19 @@ extern "C" int gq_attn_decode_roped(const void *q, const int *pos, const void *k
 #undef GQ_LAUNCH_ROPED
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
+}
+}  // namespace
+
+extern "C" int gq_attn_decode_roped(const void *q, const int *pos, const void *k_cache, const void *v_cache, void *out, uint32_t n_head,
+                                    uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split, float *workspace,
+                                    void *stream) {
+    return roped_launch<false>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, 0u, stream);
+}
+// the window form (the caches hold every row of (*pos - window, *pos]; rows below stay in the cache and are not read)
+extern "C" int gq_attn_decode_roped_window(const void *q, const int *pos, const void *k_cache, const void *v_cache, void *out, uint32_t n_head,
+                                           uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split,
+                                           float *workspace, uint32_t window, void *stream) {
+    return roped_launch<true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, window, stream);
 }
 
 extern "C" int gq_attn_decode(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,

@@ -17,7 +17,8 @@ from .model import ModelArgs, Transformer
 
 
 def _no_sliding_window(cfg: dict, what: str):
-    """the fused route attends over the whole cache: a checkpoint whose layers use a sliding window shorter than its context is declined"""
+    """for a caller that attends over the whole cache (model_args_from_hf_config without sliding_window=True): a checkpoint whose layers use
+    a sliding window shorter than its context is declined"""
     lt = cfg.get("layer_types")
     if lt and any(t != "full_attention" for t in lt):
         raise NotImplementedError(f"{what}: layer_types {sorted(set(lt))} (only full_attention layers have a fused decode form)")
@@ -33,7 +34,39 @@ def _no_sliding_window(cfg: dict, what: str):
         raise NotImplementedError(f"mistral: sliding_window {sw} < max_position_embeddings (sliding-window attention has no fused decode form)")
 
 
-def model_args_from_hf_config(cfg: dict) -> ModelArgs:
+def _layer_windows(cfg: dict, what: str):
+    """the window of every layer (None: the whole context), as transformers resolves it: from `layer_types` where the config has them
+    (full_attention / sliding_attention; anything else -- chunked_attention, .. -- has no fused form), else Mistral: every layer, else
+    Qwen2 / Qwen3 with use_sliding_window: the layers i >= max_window_layers.  W = `sliding_window`; a window the context never outgrows
+    (W >= max_position_embeddings) is no window."""
+    n = int(cfg["num_hidden_layers"])
+    lt, sw = cfg.get("layer_types"), cfg.get("sliding_window")
+    if lt:
+        other = sorted(set(lt) - {"full_attention", "sliding_attention"})
+        if other:
+            raise NotImplementedError(f"{what}: layer_types {other} (full_attention and sliding_attention layers have a fused decode form)")
+        if len(lt) != n:
+            raise ValueError(f"{what}: {len(lt)} layer_types for {n} layers")
+        sliding = [t == "sliding_attention" for t in lt]
+    elif what == "mistral":
+        sliding = [sw is not None] * n
+    elif what in ("qwen2", "qwen3") and cfg.get("use_sliding_window"):
+        first = int(cfg.get("max_window_layers", n))
+        sliding = [i >= first for i in range(n)]
+    else:
+        sliding = [False] * n
+    if not any(sliding):
+        return None
+    if sw is None:
+        raise ValueError(f"{what}: sliding-window layers without a sliding_window")
+    if int(sw) < 1:
+        raise ValueError(f"{what}: sliding_window {sw}")
+    if int(sw) >= int(cfg.get("max_position_embeddings", 8192)):
+        return None
+    return tuple(int(sw) if s else None for s in sliding)
+
+
+def model_args_from_hf_config(cfg: dict, sliding_window: bool = False) -> ModelArgs:
     """HF `config.json` -> ModelArgs (inference/model.py:27-51 field meanings), by `model_type`:
       llama (or no model_type)  the Llama block;
       mistral                   the same block, head_dim from the config when it has one; only without a sliding window that bites;
@@ -42,17 +75,27 @@ def model_args_from_hf_config(cfg: dict) -> ModelArgs:
                                 config must say so (`use_sliding_window` or `layer_types`, as every Qwen2 config.json does);
       qwen3                     head_dim of its own and the per-head q / k RMSNorm (qk_norm); dense full-attention layers only, no
                                 attention_bias.
+    sliding_window=True: a config with sliding-window layers is not declined but resolved to ModelArgs.layer_windows (`_layer_windows`) --
+    what the loaders of this package pass, whose decode step and prompt pass serve a per-layer window; the default keeps declining for a
+    caller that attends over the whole cache itself.
     Anything else (gemma3*, phi*, opt, MoE models, ..) raises NotImplementedError: the fused decode
     model knows these block layouts and no other, and a layout it does not know must not be decoded as if it were Llama's."""
     mt = str(cfg.get("model_type") or "llama").lower()
     if mt not in ("llama", "mistral", "qwen2", "qwen3"):
-        raise NotImplementedError(f"model_type {mt!r} has no fused decode form (llama, mistral without a sliding window, qwen2 and qwen3 dense have)")
+        raise NotImplementedError(f"model_type {mt!r} has no fused decode form (llama, mistral, qwen2 and qwen3 dense have)")
     name = os.path.basename(str(cfg.get("_name_or_path") or mt).rstrip("/")) or mt
     if mt not in name.lower():  # (the block layout is the model type's whatever the checkpoint directory is called)
         name = mt + "-" + name
     extra = {}
     if mt != "llama":
-        _no_sliding_window(cfg, mt)
+        if sliding_window:
+            if mt == "qwen2" and "use_sliding_window" not in cfg and not cfg.get("layer_types"):
+                _no_sliding_window(cfg, mt)  # (a dict that states neither is no Qwen2 config.json: raises)
+            lw = _layer_windows(cfg, mt)
+            if lw is not None:
+                extra["layer_windows"] = lw
+        else:
+            _no_sliding_window(cfg, mt)
         if cfg.get("head_dim"):
             extra["head_dim"] = int(cfg["head_dim"])
     if mt == "qwen2":  # (modeling_qwen2.Qwen2Attention: q_proj / k_proj / v_proj with bias=True, o_proj and the MLP without)
@@ -112,7 +155,7 @@ def load_anyprec_hf(path: str, bitwidth: int = None, device="cuda", dtype=torch.
 
 def anyprec_state_dict_to_transformer(sd: dict, cfg: dict, bitwidth: int, device="cuda", dtype=torch.float16) -> Transformer:
     """HF-keyed Any-Precision tensors (host or device) + the config dict -> the fused decode model at `bitwidth`"""
-    args = model_args_from_hf_config(cfg)
+    args = model_args_from_hf_config(cfg, sliding_window=True)
     sd = {k: v for k, v in sd.items() if "rotary_emb" not in k}
     if "lm_head.weight" not in sd and cfg.get("tie_word_embeddings", False):
         sd["lm_head.weight"] = sd["model.embed_tokens.weight"]  # tied embeddings (Llama-3.2-1B)

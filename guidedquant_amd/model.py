@@ -59,6 +59,9 @@ class ModelArgs:
     model_name: Optional[str] = None
     qk_norm: bool = False  # Qwen3: RMSNorm over head_dim on every q and k head in front of the rotation
     attn_bias: bool = False  # Qwen2 / Qwen2.5: q / k / v linears carry a bias (wo and the MLP do not)
+    # sliding-window layers (Mistral; Qwen2 / Qwen3 with use_sliding_window): per layer None (the whole context) or W >= 1 -- the query at
+    # position p attends the keys (p - W, p].  None: every layer attends the whole context.
+    layer_windows: Optional[tuple] = None
 
     def __post_init__(self):
         if self.n_local_heads == -1:
@@ -70,6 +73,11 @@ class ModelArgs:
         if self.head_dim is None:
             assert self.dim % self.n_head == 0
             self.head_dim = self.dim // self.n_head
+        if self.layer_windows is not None:
+            self.layer_windows = tuple(None if w is None else int(w) for w in self.layer_windows)
+            assert len(self.layer_windows) == self.n_layer and all(w is None or w >= 1 for w in self.layer_windows), self.layer_windows
+            if all(w is None for w in self.layer_windows):
+                self.layer_windows = None
 
     @classmethod
     def from_name(cls, name: str):
@@ -152,6 +160,15 @@ def apply_rotary_pos_emb(q, k, cos, sin, unsqueeze_dim=1):
     q_embed = (q * cos) + (rotate_half(q) * sin)
     k_embed = (k * cos) + (rotate_half(k) * sin)
     return q_embed, k_embed
+
+
+def window_mask(n: int, window: Optional[int], device=None) -> Tensor:
+    """bool [n, n], True where query row q attends key column kv: causal (kv <= q), and with a window W also kv > q - W -- transformers'
+    masking_utils.sliding_window_overlay on top of the causal mask"""
+    q = torch.arange(n, device=device)[:, None]
+    kv = torch.arange(n, device=device)[None, :]
+    m = kv <= q
+    return m if window is None else m & (kv > q - int(window))
 
 
 _SDPA_GQA = [True]  # F.scaled_dot_product_attention(enable_gqa=True): grouped K / V heads without the repeat_interleave copies
@@ -344,6 +361,8 @@ class Transformer(nn.Module):
         self.dtype = dtype
         if halve_layers:
             config.n_layer = config.n_layer // 2
+            if config.layer_windows is not None:
+                config.layer_windows = config.layer_windows[:config.n_layer]
         self.tok_embeddings = nn.Embedding(config.vocab_size, config.dim)
         self.layers = nn.ModuleList(
             TransformerBlock(config, linear_class, linear_kwargs, fuse_linears) for _ in range(config.n_layer))
@@ -386,6 +405,9 @@ class Transformer(nn.Module):
         for b in self.layers:
             b.attention.kv_cache = KVCache(max_batch_size, max_seq_length, self.config.n_local_heads, head_dim, dtype, device)
         self.causal_mask = torch.tril(torch.ones(self.max_seq_length, self.max_seq_length, dtype=torch.bool, device=device))
+        # one mask per distinct window that is shorter than the cache (a window the cache never outgrows is the causal mask)
+        lw = self.config.layer_windows or ()
+        self.window_masks = {w: window_mask(self.max_seq_length, w, device) for w in sorted({w for w in lw if w is not None and w < self.max_seq_length})}
         self.rope_cos, self.rope_sin = rope_tables(head_dim, max_seq_length, self.config.rope_base, device, dtype,
                                                    rope_scaling=self.config.rope_scaling)
         self.cache_initialized = True
@@ -394,9 +416,11 @@ class Transformer(nn.Module):
     def forward(self, idx: Tensor, input_pos: Optional[Tensor] = None) -> Tensor:
         assert self.cache_initialized, "Caches must be initialized first"
         mask = self.causal_mask[None, None, input_pos]
+        wmask = {w: wm[None, None, input_pos] for w, wm in self.window_masks.items()}  # (empty for a model without windows)
+        lw = self.config.layer_windows or (None,) * len(self.layers)
         x = self.tok_embeddings(idx)
-        for layer in self.layers:
-            x = layer(x, input_pos, mask, self.rope_cos, self.rope_sin)
+        for layer, w in zip(self.layers, lw):
+            x = layer(x, input_pos, wmask.get(w, mask), self.rope_cos, self.rope_sin)
         x = self.norm(x)
         return self.output(x)
 
@@ -428,7 +452,7 @@ class Transformer(nn.Module):
                    and m.in_features % 128 == 0
                    for b in self.layers for m in (b.attention.wqkv, b.attention.wo, b.feed_forward.w1w3, b.feed_forward.w2)):
                 kind = "ap"
-        elif native_step.native_qtip():
+        elif native_step.native_qtip() and self.config.layer_windows is None:  # (no window form of gq_attn_decode_qtip)
             from .qtip import QuantizedLinear
 
             p2 = lambda n: n > 0 and (n & (n - 1)) == 0  # noqa: E731
@@ -500,12 +524,15 @@ class Transformer(nn.Module):
         q = torch.empty((H, S, hd), dtype=torch.float16, device=dev)
         hbuf = torch.empty((S, inter), dtype=torch.float16, device=dev)
         mask = None if start == 0 else self.causal_mask[None, None, input_pos.long(), :T]
+        # a sliding-window layer whose window the T keys outgrow: the explicit mask, at start == 0 too (is_causal would attend them all)
+        wmask = {w: wm[None, None, input_pos.long(), :T] for w, wm in self.window_masks.items() if T > w}
+        lw = cfg.layer_windows or (None,) * len(self.layers)
         rep = H // Hkv
         qt = self._native_kind() == "qtip"  # QTIP: the linears through QuantizedLinear.forward (bs > 8: gq_qtip_gemm)
         pending = None  # the previous block's MLP output: its residual add rides in the next RMSNorm launch
         with torch.cuda.device(dev):
             st = _lib.current_stream_ptr()  # (the model's device's current stream: inside the guard)
-            for b in self.layers:
+            for b, win in zip(self.layers, lw):
                 att, ff = b.attention, b.feed_forward
                 _lib.check(L.gq_rmsnorm_rows(x.data_ptr(), pending.data_ptr() if pending is not None else None, b.input_layernorm.weight.data_ptr(), xn.data_ptr(),
                                              S, D, b.input_layernorm.eps, st), "gq_rmsnorm_rows")
@@ -523,7 +550,7 @@ class Transformer(nn.Module):
                 else:
                     _lib.check(L.gq_rope_cache_rows(qkv.data_ptr(), input_pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), q.data_ptr(),
                                                     kc.data_ptr(), vc.data_ptr(), S, H, Hkv, hd, kc.shape[2], st), "gq_rope_cache_rows")
-                y = _sdpa_gqa(q.unsqueeze(0), kc[:1, :, :T], vc[:1, :, :T], mask, rep)
+                y = _sdpa_gqa(q.unsqueeze(0), kc[:1, :, :T], vc[:1, :, :T], wmask.get(win, mask), rep)
                 y = y.transpose(1, 2).reshape(1, S, H * hd)
                 o = att.wo(y).view(S, D)
                 _lib.check(L.gq_rmsnorm_rows(x.data_ptr(), o.data_ptr(), b.post_attention_layernorm.weight.data_ptr(), xn.data_ptr(), S, D,

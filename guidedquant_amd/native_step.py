@@ -105,16 +105,29 @@ class StepState(_Keyed):
         # long caches: split-KV attention (gq_attn_decode_split), n_split blocks per head + a combine launch; a context of
         # up to 256 positions is still finished by one block per head at run time
         S = model.max_seq_length
-        ns = 1 if S <= 1024 else (4 if S <= 2048 else 8)
-        # grouped-query models whose wqkv launch rotates q / k (gq_attn_decode_roped): the four query heads of a KV group share a
-        # block, so the splits can be as short as one 128-position pass -- n_kv_head x n_split blocks ~ one per CU
         l0 = model.layers[0].attention
-        # (not for QK-norm or attn_bias models: their wqkv launch never rotates, see ApStep.layers)
-        if (S > 1024 and c.n_head % (4 * c.n_local_heads) == 0 and model._native_kind() != "qtip" and attn_gqa()
-                and not c.qk_norm and not c.attn_bias and _lib.lib().gq_anyprec_qkv_rope_supported(l0.wqkv.out_features, c.dim, l0.wqkv.bitwidth, c.head_dim)):
-            ns = max(4, min(32, (S + 127) // 128, 256 // max(1, c.n_head // 4)))
-        self.attn_split = attn_split_knob(ns)
-        self.attn_ws = torch.zeros(c.n_head * self.attn_split * (c.head_dim + 2), dtype=torch.float32, device=dev) if self.attn_split > 1 else None
+
+        def plan(S):
+            ns = 1 if S <= 1024 else (4 if S <= 2048 else 8)
+            # grouped-query models whose wqkv launch rotates q / k (gq_attn_decode_roped): the four query heads of a KV group share a
+            # block, so the splits can be as short as one 128-position pass -- n_kv_head x n_split blocks ~ one per CU
+            # (not for QK-norm or attn_bias models: their wqkv launch never rotates, see ApStep.layers)
+            if (S > 1024 and c.n_head % (4 * c.n_local_heads) == 0 and model._native_kind() != "qtip" and attn_gqa()
+                    and not c.qk_norm and not c.attn_bias and _lib.lib().gq_anyprec_qkv_rope_supported(l0.wqkv.out_features, c.dim, l0.wqkv.bitwidth, c.head_dim)):
+                ns = max(4, min(32, (S + 127) // 128, 256 // max(1, c.n_head // 4)))
+            return attn_split_knob(ns)
+
+        self.attn_split = plan(S)
+        # sliding-window layers (ModelArgs.layer_windows): a layer whose window is shorter than the cache attends the rows
+        # (pos - W, pos] through the _window entry of its form; it never reads more than W rows, so its splits are planned from
+        # min(S, W) by the same rule.  Layers without a window (or with one the cache never outgrows) launch what they always did.
+        lw = getattr(c, "layer_windows", None) or (None,) * len(model.layers)
+        assert len(lw) == len(model.layers), "ModelArgs.layer_windows: one entry per layer"
+        self.layer_window = [int(w) if w is not None and int(w) < S else None for w in lw]
+        assert all(w is None or w >= 1 for w in self.layer_window), "ModelArgs.layer_windows: a window is at least 1"
+        self.layer_split = [self.attn_split if w is None else plan(w) for w in self.layer_window]
+        ns_max = max([self.attn_split] + self.layer_split)  # (one workspace, sized for the largest)
+        self.attn_ws = torch.zeros(c.n_head * ns_max * (c.head_dim + 2), dtype=torch.float32, device=dev) if ns_max > 1 else None
 
     def kv(self, at, slot):
         """the K / V cache of batch slot `slot` of one attention module"""
@@ -122,14 +135,19 @@ class StepState(_Keyed):
         off = slot * c.n_local_heads * self.m.max_seq_length * c.head_dim * 2  # bytes per batch slot
         return at.kv_cache.k_cache.data_ptr() + off, at.kv_cache.v_cache.data_ptr() + off
 
-    def attend(self, entry, src, pos, kv, sp, extra=()):
+    def attend(self, entry, src, pos, kv, sp, extra=(), layer=None):
         """the attention launch, entry = gq_attn_decode_split / _split_qknorm / _split_bias / _roped / _qtip.  src: the packed q | k | v vector (or
         the q / k / v descriptors of gq_attn_decode_qtip); _roped takes no tables (the wqkv launch rotated); extra: what an entry
-        point takes behind the workspace"""
+        point takes behind the workspace.  layer: its index -- a sliding-window layer takes the `_window` entry of the form, with its own
+        split count and the window behind `extra`"""
         m, c = self.m, self.m.config
         rope = () if entry == "gq_attn_decode_roped" else (m.rope_cos.data_ptr(), m.rope_sin.data_ptr())
+        win, ns = (None, self.attn_split) if layer is None else (self.layer_window[layer], self.layer_split[layer])
+        if win is not None:
+            assert entry != "gq_attn_decode_qtip", "QTIP models have no sliding-window form"
+            entry, extra = entry + "_window", (*extra, win)
         _lib.check(getattr(_lib.lib(), entry)(src, pos.data_ptr(), *rope, *kv, self.y.data_ptr(), c.n_head, c.n_local_heads, c.head_dim,
-                                              m.max_seq_length, 1.0 / math.sqrt(c.head_dim), self.attn_split, _ptr(self.attn_ws), *extra, sp), entry)
+                                              m.max_seq_length, 1.0 / math.sqrt(c.head_dim), ns, _ptr(self.attn_ws), *extra, sp), entry)
 
     def head(self, x):
         m, c = self.m, self.m.config
@@ -226,24 +244,24 @@ class ApStep(StepState):
                 # head's rows in eight 16-row groups: no per-head statistic there) -- plain wqkv GEMV, then ONE attention launch that
                 # normalises, rotates, writes the cache row and attends
                 launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
-                self.attend("gq_attn_decode_split_qknorm", qkv, pos, kv, sp, (at.q_norm.weight.data_ptr(), at.k_norm.weight.data_ptr(), at.q_norm.eps))
+                self.attend("gq_attn_decode_split_qknorm", qkv, pos, kv, sp, (at.q_norm.weight.data_ptr(), at.k_norm.weight.data_ptr(), at.q_norm.eps), layer=l0 + li)
             elif at.wqkv.bias is not None:
                 # Qwen2 / Qwen2.5: the bias of q / k / v belongs in front of the rotation, and the RoPE epilogues of the wqkv launch
                 # (gq_anyprec_gemv_qkv_rope*) rotate what the GEMV summed -- the unbiased q / k.  Plain wqkv GEMV, then ONE attention launch
                 # that adds the bias, rotates, writes the cache row and attends (_native_kind admits a bias here only on attn_bias models)
                 launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
-                self.attend("gq_attn_decode_split_bias", qkv, pos, kv, sp, (at.wqkv.bias.data_ptr(),))
-            elif (self.attn_split == 1 and ssq_in is None
+                self.attend("gq_attn_decode_split_bias", qkv, pos, kv, sp, (at.wqkv.bias.data_ptr(),), layer=l0 + li)
+            elif (self.attn_split == 1 and ssq_in is None and self.layer_window[l0 + li] is None  # (no window form inside the wqkv launch)
                     and L.gq_anyprec_qkv_rope_attn_supported(at.wqkv.out_features, c.dim, at.wqkv.bitwidth, c.head_dim, c.n_head, c.n_local_heads)):
                 # round 6: the attention heads as extra blocks of the wqkv launch (they wait on device flags for q / the new cache row):
                 # one launch and one kernel boundary less per layer, outputs bit-identical to the two launches below
                 launch("gq_anyprec_gemv_qkv_rope_attn", *wqkv, *rope, y, 1.0 / math.sqrt(c.head_dim), self.attn_flags.data_ptr())
             elif L.gq_anyprec_qkv_rope_supported(at.wqkv.out_features, c.dim, at.wqkv.bitwidth, c.head_dim):
                 launch("gq_anyprec_gemv_qkv_rope_ho", *wqkv, *rope, ssq_in)
-                self.attend("gq_attn_decode_roped", qkv, pos, kv, sp)
+                self.attend("gq_attn_decode_roped", qkv, pos, kv, sp, layer=l0 + li)
             else:
                 launch("gq_anyprec_gemv_fused", *wqkv, None, 0)
-                self.attend("gq_attn_decode_split", qkv, pos, kv, sp)
+                self.attend("gq_attn_decode_split", qkv, pos, kv, sp, layer=l0 + li)
             # x, out, weights, norm weight, eps, residual (wo's input width is n_head * head_dim: not dim for a model with a head_dim of its own)
             wo = (y, h, *_lin(at.wo), None, 0.0, xp)
             w13 = (h, gu, *_lin(ff.w1w3), blk.post_attention_layernorm.weight.data_ptr(), c.norm_eps, None)

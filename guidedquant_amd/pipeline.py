@@ -92,6 +92,8 @@ class PipelinedDecoder:
     def __init__(self, model, rank: int, world: int, layers: range, n_seq: Optional[int] = None, max_new_tokens: int = 100,
                  temperature: float = 0.0, top_k: Optional[int] = 32, bos_id: int = 1, native: Optional[bool] = None, group=None,
                  feedback_group=None, use_graphs: Optional[bool] = None, seed: int = 1234, hop: Optional[str] = None):
+        if getattr(model.config, "layer_windows", None) is not None:  # (the stages build their masks and slots themselves)
+            raise NotImplementedError("layer-pipelined decode has no sliding-window form (layer_windows)")
         self.model, self.rank, self.world, self.layers = model, rank, world, layers
         self.n_seq = S = n_seq or world
         self.group = group

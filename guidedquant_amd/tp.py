@@ -42,6 +42,8 @@ class TensorParallelDecoder:
             # dim-wide vector)
             raise NotImplementedError("tensor-parallel decode serves the Llama block only: no QK-norm (Qwen3), no q / k / v bias (Qwen2), "
                                       "no head_dim other than dim / n_head")
+        if c.layer_windows is not None:  # (this class launches attention itself, over the whole cache)
+            raise NotImplementedError("tensor-parallel decode has no sliding-window form (layer_windows)")
         assert c.n_head % world == 0 and c.n_local_heads % world == 0 and c.dim % (16 * world) == 0 and c.intermediate_size % (16 * world) == 0, \
             "heads, KV heads, dim / 16 and intermediate / 16 must divide by the world size"
         self.model, self.group, self.rank, self.world = model, group, rank, world

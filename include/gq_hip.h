@@ -456,6 +456,26 @@ int gq_attn_decode_split_qknorm(const void *qkv, const int *pos, const void *cos
 int gq_attn_decode_split_bias(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,
                               void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
                               float scale, uint32_t n_split, float *workspace, const void *qkv_bias, void *stream);
+/* Sliding-window layers (Mistral; Qwen2 / Qwen3 with use_sliding_window; transformers' masking_utils.sliding_window_overlay on top of the
+ * causal mask): the query at *pos attends the cached rows t with *pos - window < t <= *pos -- lo = *pos + 1 > window ? *pos + 1 - window
+ * : 0, n = *pos + 1 - lo rows, and no row outside [lo, *pos] reaches a score or a weighted sum (rows below lo hold real rows of the
+ * sequence, rows above *pos stale ones).  The caches stay as they are: max_seq rows, row *pos written at *pos.  The geometry is that of
+ * the launch without a window at position n - 1, shifted by lo: one block per head while n is at most two passes (the rule is taken on
+ * n, in the attention launch and in the combine alike), split s over [lo + s per, ..) with per from n, row t in the slot of row t - lo --
+ * bit for bit the old entry on a cache that holds rows [lo, *pos] as rows [0, n - 1].  window = 0 is GQ_EINVAL; window >= max_seq is
+ * legal and equals the entry without a window bit for bit.  Every other argument, the NaN result at *pos >= max_seq and the workspace as
+ * in the entry of the same name.  gq_attn_decode_roped_window: the rows requested ahead of the position serve only while lo = 0.
+ * (gq_attn_decode_qtip and gq_anyprec_gemv_qkv_rope_attn have no window form.) */
+int gq_attn_decode_split_window(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,
+                                void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                                float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream);
+int gq_attn_decode_split_qknorm_window(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,
+                                       void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                                       float scale, uint32_t n_split, float *workspace, const void *q_norm_weight,
+                                       const void *k_norm_weight, float eps, uint32_t window, void *stream);
+int gq_attn_decode_split_bias_window(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,
+                                     void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                                     float scale, uint32_t n_split, float *workspace, const void *qkv_bias, uint32_t window, void *stream);
 
 /*
  * Device-to-device hand-over of the layer pipeline (round 4; reference precedent: the host-side `.to(device)` hops of
@@ -517,6 +537,9 @@ int gq_anyprec_gemv_qkv_rope_ho(const void *x, void *q_out, const uint32_t *qwei
 int gq_attn_decode_roped(const void *q, const int *pos, const void *k_cache, const void *v_cache, void *out, uint32_t n_head,
                          uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split, float *workspace,
                          void *stream);
+int gq_attn_decode_roped_window(const void *q, const int *pos, const void *k_cache, const void *v_cache, void *out, uint32_t n_head,
+                                uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split, float *workspace,
+                                uint32_t window, void *stream);
 
 /*
  * Round 6: gq_anyprec_gemv_qkv_rope AND gq_attn_decode_roped (n_split = 1) as ONE launch -- the attention heads are extra blocks of the
