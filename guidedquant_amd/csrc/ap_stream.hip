@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "ap_dispatch.h"
+#include "attn_core.h"
 #include "plane_core.h"
 
 using namespace gqp;
@@ -1028,7 +1029,7 @@ __global__ void __launch_bounds__(64 * st_waves<BITS>()) ap_stream_kernel(Stream
 //   consumers  each wave of a head block polls its head's flag with agent-scope loads until it reads 3 * head_dim / 16 (the row
 //              groups of its q, k and v heads), then reads q and row *pos of the caches with AGENT-SCOPE loads (sc1: the block's own
 //              L2 may hold older copies of those lines -- profiles/r06_flag_handoff.txt: plain loads do see them, sc1 loads never
-//              did) and runs the arithmetic of attn_roped_kernel<HD, 1> (decode.hip) operation for operation: same position ->
+//              did) and runs the arithmetic attn_roped_kernel<HD, 1> (decode.hip) runs, from attn_core.h: same position ->
 //              stream assignment, same online softmax per stream, same merge order -- bit-identical outputs.
 // One flag LINE per head (GQ_ATTN_FLAG_STRIDE words apart: agent-scope atomics on one line serialise at the memory side, 5.4 us
 // instead of 0.7 us until the flag is seen); the head block re-arms its flag (stores 0) before it ends -- the next launch's
@@ -1049,7 +1050,6 @@ struct AttnFuse {
     do {                                                                                                                \
         if (GQ_STAMPS && f.dbg && threadIdx.x == 0) f.dbg[(size_t)blockIdx.x * 8u + (i)] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
-constexpr int FUSE_ATTN_WAVES = GQ_ATTN_WAVES;
 
 __device__ __forceinline__ u32 ld_flag_sc1(const u32 *p) {
     u32 v;
@@ -1088,17 +1088,19 @@ __device__ __forceinline__ void fuse_signal(const StreamArgs &a, const AttnFuse 
     }
 }
 
-// one query head: attn_roped_kernel<HD, 1> (decode.hip) with n_split = 1, its loads re-ordered around the flag
+// one query head: the geometry, arithmetic, merge and LDS layout (attn_core.h) of attn_roped_kernel<HD, 1> with n_split = 1, its loads
+// ordered around the flag
 template <int HD>
 __device__ __forceinline__ void fuse_attn_head(const StreamArgs &a, const AttnFuse &f, u32 h) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
-    constexpr u32 NW = FUSE_ATTN_WAVES;
-    constexpr int LPP = HD / 8, PPW = 64 / LPP, U = 4;
-    constexpr u32 NS = NW * PPW;
+    using G = gq_attn::AttnGeom<HD>;
+    using L = gq_attn::RopedLds<HD, 1>;
+    constexpr u32 NW = G::NW, NS = G::NS;
+    constexpr int LPP = G::LPP, PPW = G::PPW, U = G::U;
     const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
     if (w >= NW) return;  // (the launch has the GEMV's 16 waves per block; a head uses 8 -- ended waves leave the block's barriers)
-    float *sc = reinterpret_cast<float *>(smem);  // [2 * NS] running max / sum of the position streams
-    float *red2 = sc + 2u * NS;                   // [NS][HD] partial outputs
+    float *lds = reinterpret_cast<float *>(smem);
+    float *sc = lds + L::sc, *red2 = lds + L::red2, *fl = lds + L::fl;
     const u32 H = a.H, Hkv = a.Hkv, max_seq = a.max_seq;
     const u32 g = h / (H / Hkv);
     const u32 sub = l / LPP, ld = l % LPP;
@@ -1175,11 +1177,7 @@ __device__ __forceinline__ void fuse_attn_head(const StreamArgs &a, const AttnFu
     }
     FUSE_STAMP(3);
     float qreg[8];
-    {
-        const u32 qw[4] = {q4.x, q4.y, q4.z, q4.w};
-#pragma unroll
-        for (int e = 0; e < 4; e++) qreg[2 * e] = h2f((uint16_t)(qw[e] & 0xFFFF)), qreg[2 * e + 1] = h2f((uint16_t)(qw[e] >> 16));
-    }
+    gq_attn::unpack8(make_uint4(q4.x, q4.y, q4.z, q4.w), qreg);
     const float scale = f.scale;
     float m_run = -3.0e38f, s_run = 0.f, acc[8];
 #pragma unroll
@@ -1190,39 +1188,21 @@ __device__ __forceinline__ void fuse_attn_head(const StreamArgs &a, const AttnFu
         for (int u = 0; u < U; u++) {
             const u32 t = t0 + (u32)u * PPW + sub;
             const bool valid = t < p1;
-            const u32 kw[4] = {kv[u].x, kv[u].y, kv[u].z, kv[u].w}, vw[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
+            const u32 vw[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
             float kf[8];
+            gq_attn::unpack8(kv[u], kf);
 #pragma unroll
             for (int e = 0; e < 4; e++) {
-                kf[2 * e] = h2f((uint16_t)(kw[e] & 0xFFFF));
-                kf[2 * e + 1] = h2f((uint16_t)(kw[e] >> 16));
                 vfu[u][2 * e] = valid ? h2f((uint16_t)(vw[e] & 0xFFFF)) : 0.f;
                 vfu[u][2 * e + 1] = valid ? h2f((uint16_t)(vw[e] >> 16)) : 0.f;
             }
             float p = 0.f;
 #pragma unroll
             for (int e = 0; e < 8; e++) p += qreg[e] * kf[e];
-            p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0xB1, 0xF, 0xF, false));
-            p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x4E, 0xF, 0xF, false));
-            p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x141, 0xF, 0xF, false));
-            if (LPP == 16) p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x140, 0xF, 0xF, false));
+            p = gq_attn::row_sum<LPP>(p);
             pu[u] = valid ? p * scale : -3.0e38f;
         }
-        float m_new = m_run;
-#pragma unroll
-        for (int u = 0; u < U; u++) m_new = fmaxf(m_new, pu[u]);
-        const float resc = __expf(m_run - m_new);
-        s_run *= resc;
-#pragma unroll
-        for (int e = 0; e < 8; e++) acc[e] *= resc;
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const float wgt = pu[u] > -2.0e38f ? __expf(pu[u] - m_new) : 0.f;
-            s_run += wgt;
-#pragma unroll
-            for (int e = 0; e < 8; e++) acc[e] += wgt * vfu[u][e];
-        }
-        m_run = m_new;
+        gq_attn::softmax_update<U>(m_run, s_run, acc, pu, vfu);
         if (t0 + NW * PPW * U < p1) request(kv, vv, t0 + NW * PPW * U, true);
     }
     FUSE_STAMP(4);
@@ -1236,9 +1216,8 @@ __device__ __forceinline__ void fuse_attn_head(const StreamArgs &a, const AttnFu
     __syncthreads();
     FUSE_STAMP(5);
     if (tid == 0) gq_store_wt(const_cast<u32 *>(flag), 0u);  // (every wave has seen the flag: re-armed for the next launch)
-    float *fl = red2 + (size_t)NS * HD;  // [NS] factors, [1] maximum
-    const u32 nw_act = min(NW, (p1 + (u32)(PPW * U) - 1u) / (u32)(PPW * U));
-    const u32 ng = (nw_act * (u32)PPW + 7u) >> 3;
+    // the merge of attn_core.h (spelled out here and in decode.hip::attn_roped_kernel)
+    const u32 ng = gq_attn::merge_groups<HD>(p1);
     if (tid < NS) {
         float M = -3.0e38f;
         for (u32 g8 = 0; g8 < ng; g8++)
@@ -1252,12 +1231,7 @@ __device__ __forceinline__ void fuse_attn_head(const StreamArgs &a, const AttnFu
         float o = 0.f, sum = 0.f;
         for (u32 g8 = 0; g8 < ng; g8++)
 #pragma unroll
-            for (u32 k = 0; k < 8u; k++) {
-                const u32 i = 8u * g8 + k;
-                const float fi = fl[i];
-                sum += sc[NS + i] * fi;
-                o += red2[i * HD + tid] * fi;
-            }
+            for (u32 k = 0; k < 8u; k++) gq_attn::merge_step<HD>(sc, red2, fl, 8u * g8 + k, tid, o, sum);
         f.out[(size_t)h * HD + tid] = __builtin_bit_cast(uint16_t, (_Float16)(o / sum));
     }
     FUSE_STAMP(6);
@@ -1413,11 +1387,11 @@ int stream_launch(const ApLaunch &L, const StreamArgs *rope, const KSplit *ksp =
     if (fuse) {
         // the attention heads as extra blocks of this launch (ap_qkv_attn_kernel): the EPI_ROPE instance's configuration, one CU per block
         if (bits != 2 || pro != PRO_RMSNORM || !rope || c.psum || c.NPU != 1u || c.W != (u32)ST_W2 || c.gy != 1u || a.ssq_in || a.part_out || a.resid ||
-            a.pairs || c.grid + a.H > (u32)gq_cu_count() || (u32)FUSE_ATTN_WAVES > c.W)
+            a.pairs || c.grid + a.H > (u32)gq_cu_count() || (u32)GQ_ATTN_WAVES > c.W)
             return GQ_ENOTSUP;
         if (fuse_dry || gq_ap_route(GQ_AP_ROUTE_STREAM_QKV_ROPE, 1u)) return GQ_OK;
-        const u32 hd = 1u << a.lhd, ns = (u32)FUSE_ATTN_WAVES * 64u / (hd / 8u);
-        const size_t asmem = ((size_t)2u * ns + (size_t)ns * hd + ns + 1u) * 4u;
+        const u32 hd = 1u << a.lhd;
+        const size_t asmem = hd == 128u ? gq_attn::RopedLds<128, 1>::bytes() : gq_attn::RopedLds<64, 1>::bytes();
         const size_t smem = c.smem > asmem ? c.smem : asmem;
         fuse->gemv_blocks = c.grid;
         fuse->dbg = GQ_STAMPS ? gq_debug_timing_buffer() : nullptr;

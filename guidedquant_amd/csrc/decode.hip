@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "gq_internal.h"
+#include "attn_core.h"
 #include "fwht.h"
 
 namespace {
@@ -17,6 +18,9 @@ typedef uint32_t u32;
 typedef _Float16 h16;
 typedef h16 h16x2 __attribute__((ext_vector_type(2)));
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+using gq_attn::AttnGeom;
+using gq_attn::AttnWindow;
+using gq_attn::window_lo;
 
 __device__ __forceinline__ float h2f(uint16_t h) { return (float)__builtin_bit_cast(h16, h); }
 __device__ __forceinline__ h16 u2h(uint16_t h) { return __builtin_bit_cast(h16, h); }
@@ -80,11 +84,9 @@ __global__ void __launch_bounds__(GQ_SSQ_SLOTS) embed_ssq_kernel(const int *tok,
 //   q_embed = (q * cos) + (rotate_half(q) * sin)   -- three fp16-rounded operations, cos/sin are fp16 tables
 // built by the host from fp32 (LlamaRotaryEmbedding.forward, model.py:379-405).  The rotated k and the v of this
 // token are written to the cache at `pos` (KVCache.update, model.py:69-79) by the first head of each KV group.
-// Scores / softmax / weighted sum run in fp32 from the fp16 operands; the output is rounded to fp16 once.
-#ifndef GQ_ATTN_WAVES
-#define GQ_ATTN_WAVES 8
-#endif
-constexpr int ATTN_WAVES = GQ_ATTN_WAVES;  // 8 waves x 4 positions x 4 in flight = 128 positions per pass (HD = 128)
+// Scores / softmax / weighted sum run in fp32 from the fp16 operands; the output is rounded to fp16 once.  The split geometry, the
+// arithmetic of a cached row and of the online softmax, and the LDS layout are those of attn_core.h.
+constexpr int ATTN_WAVES = GQ_ATTN_WAVES;
 // QT (QTIP models): q / k / v are not read as fp16 vectors but rebuilt from the trellis matvecs' fp32 sums -- the transform-out of
 // BitshiftLinear.forward (inference/lib/codebook/bitshift.py:470: hadamard(y) * m^-1/2 * (SV * 32) -> fp16), i.e. what
 // gq_qtip_linear_out computes in a launch of its own.  A head needs HD of the M outputs of each vector and the Sylvester matrix
@@ -122,23 +124,7 @@ template <>
 struct AttnBias<true> {
     const uint16_t *qkv;  // fp16 [(H + 2 Hkv) * HD]
 };
-// WIN (sliding-window layers: transformers' masking_utils.sliding_window_overlay on top of the causal mask): the query at position pos
-// attends the cached rows (pos - W, pos] -- lo = max(0, pos + 1 - W), n = pos + 1 - lo rows.  The geometry of a launch is that of the
-// launch without a window at position n - 1, shifted by lo: the solo rule and the split length are taken from n, split s covers
-// [lo + s per, ..), row t takes the (pass, wave, u, sub) slot row t - lo has there; merge and combine order as they are.  No row below lo
-// is requested behind the position read (they hold real rows of the sequence).  A compile-time form like QKN / QB: the WIN = false
-// instances take an empty argument and keep the instructions they had.  W >= 1 (checked by the host), so lo <= pos: nothing underflows.
-template <bool WIN>
-struct AttnWindow {};  // (nothing to pass)
-template <>
-struct AttnWindow<true> {
-    u32 w;  // rows a query attends, itself included
-};
-template <bool WIN>
-__device__ __forceinline__ u32 window_lo(u32 pos, const AttnWindow<WIN> &wn) {
-    if constexpr (WIN) return pos + 1u > wn.w ? pos + 1u - wn.w : 0u;
-    else return 0u;
-}
+// WIN: the sliding-window form (attn_core.h, AttnWindow).
 template <int HD, bool QT, bool QKN = false, bool QB = false, bool WIN = false>
 __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint16_t *qkv, const int *pos_ptr, const uint16_t *cos_t,
                                                           const uint16_t *sin_t, uint16_t *kc, uint16_t *vc, uint16_t *out,
@@ -146,22 +132,20 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
                                                           AttnQkNorm<QKN> nm, AttnBias<QB> bs, AttnWindow<WIN> wn) {
     static_assert(!(QB && (QT || QKN)), "the bias form is the plain fp16 q / k / v form plus the add");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr u32 NW = ATTN_WAVES;
-    float *sc = reinterpret_cast<float *>(smem);  // [2 * NW * 64 / (HD / 8)] running max / sum of the position streams
-    float *qs = sc + 2u * NW * (64u / (HD / 8u));  // [HD]
-    float *kcur = qs + HD;                        // [HD]
-    float *vcur = kcur + HD;                      // [HD]
-    float *red = vcur + HD;                       // [4 * HD] (+ 2 * NW scratch at 4*HD)
-    float *red2 = red + 4 * HD + 2 * NW;          // [NW waves * positions-per-wave-instruction][HD] partial outputs
+    using Geo = AttnGeom<HD>;
+    using L = gq_attn::DecodeLds<HD>;
+    constexpr u32 NW = Geo::NW, NS = Geo::NS;
+    constexpr int LPP = Geo::LPP, PPW = Geo::PPW, U = Geo::U;
+    float *lds = reinterpret_cast<float *>(smem);
+    float *sc = lds + L::sc, *qs = lds + L::qs, *kcur = lds + L::kcur, *vcur = lds + L::vcur, *red = lds + L::red, *red2 = lds + L::red2;
     const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
     const u32 h = blockIdx.x, g = kv_group_of(h, H, Hkv);
     const uint16_t *q = qkv + (size_t)h * HD;
     const uint16_t *k = qkv + (size_t)H * HD + (size_t)g * HD;
     const uint16_t *v = qkv + (size_t)(H + Hkv) * HD + (size_t)g * HD;
     if constexpr (QT) {
-        // LDS behind the attention's own arrays: 3 x HD floats (the combined segments), then 3 x HD fp16 results
-        float *tv = red2 + (size_t)NW * (64u / (HD / 8u)) * HD;
-        uint16_t *res16 = reinterpret_cast<uint16_t *>(tv + 3 * HD);
+        float *tv = lds + L::tv;
+        uint16_t *res16 = reinterpret_cast<uint16_t *>(lds + L::res16);
         // H_M = H_(M / HD) (x) H_HD: the HD outputs of segment `seg` are the HD-point transform of  z[b] = sum_c s(c) y[c HD + b],
         // s(c) = (-1)^popcount(c & seg)  (row `seg` of the M / HD-point Sylvester matrix): 4096 signed additions and ONE short
         // transform instead of the whole vector's butterflies.  The additions are those of the full transform in another order
@@ -173,7 +157,7 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
         {
             constexpr u32 Q = HD / 4u;
             const u32 T = blockDim.x, G = T / Q;  // G thread groups per element group
-            float *ps = tv + 3 * HD + 3 * HD / 2;  // [3][G][HD] partial sums (behind the fp16 results)
+            float *ps = lds + L::ps;  // [3][G][HD] partial sums
             float4 y[3][4];
             u32 cnt[3];
 #pragma unroll
@@ -252,22 +236,16 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
     }
     uint16_t *kcg = kc + (size_t)g * max_seq * HD;
     uint16_t *vcg = vc + (size_t)g * max_seq * HD;
-    // split-KV (long contexts): block (head, sp) takes the positions [p0, p1) of the pos + 1 cached ones, in whole passes
-    // of the block (NW waves x 64 / (HD / 8) positions x 4 in flight); one head per block leaves all but H CUs idle and
-    // is bound by what H CUs can stream (51 us at 4096 positions)
-    constexpr u32 PASS = NW * (64u / (HD / 8u)) * 4u;
+    // the rows [p0, p1) of this block (attn_core.h: the solo rule, the rows of a split)
     const u32 sp = blockIdx.y;
-    // a short context (up to two passes) is not worth splitting: split 0 does it all and writes the result itself, the
-    // other blocks and the combine launch return at once
     const u32 lo = window_lo(pos, wn), n = pos + 1u - lo;  // (WIN = false: lo = 0, n = pos + 1)
-    const bool solo = nsplit > 1u && n <= 2u * PASS;
-    if (solo) {
+    if (gq_attn::attn_solo<HD>(n, nsplit)) {
         if (sp > 0u) return;
         nsplit = 1u;
     }
-    const u32 per = nsplit > 1u ? (((n - 1u + nsplit) / nsplit + PASS - 1u) / PASS) * PASS : n;
-    const u32 p0 = lo + sp * per, p1 = min(pos + 1u, p0 + per);  // (p0 >= p1: nothing to do, a neutral partial result is written)
-    const bool has_cur = p0 <= pos && pos < p1;             // the split that covers the current token
+    const u32 per = gq_attn::attn_per<HD>(n, nsplit);
+    const u32 p0 = lo + sp * per, p1 = min(pos + 1u, p0 + per);
+    const bool has_cur = p0 <= pos && pos < p1;  // the split that covers the current token
     if constexpr (QKN) {
         // per-head statistics: thread d < HD holds element d of q and of k (the other waves add zeros); fixed order
         const float qf = h2f(qd_b), kf = h2f(kd_b);  // (0 for tid >= HD)
@@ -306,14 +284,8 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
         }
     }
     __syncthreads();
-    // One pass, online softmax per position stream.  16 lanes per position (8 dims = one 16-byte load per lane, a
-    // position's K / V row is one coalesced 256-byte line pair), PPW positions per wave instruction, U independent
-    // positions in flight per lane group; the K and the V rows of a batch are requested together (one memory round trip
-    // instead of two), and each lane group keeps a running (max, sum, weighted V) that is rescaled when the max moves.
-    // The NW * PPW streams of the block are combined once, through LDS.
-    constexpr int LPP = HD / 8;          // lanes per position: 16 (HD=128) or 8 (HD=64)
-    constexpr int PPW = 64 / LPP;        // positions per wave instruction
-    constexpr int U = 4;
+    // One pass, online softmax per position stream (attn_core.h).  The K and the V rows of a batch are requested together (one memory
+    // round trip instead of two); the NS streams of the block are combined once, through LDS.
     const u32 sub = l / LPP, ld = l % LPP;
     float qreg[8];
 #pragma unroll
@@ -330,15 +302,13 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
             kv[u] = cached ? *reinterpret_cast<const uint4 *>(kcg + (size_t)t * HD + ld * 8) : make_uint4(0, 0, 0, 0);
             vv[u] = cached ? *reinterpret_cast<const uint4 *>(vcg + (size_t)t * HD + ld * 8) : make_uint4(0, 0, 0, 0);
         }
-        // the U positions of the batch share one rescale of the running (max, sum, weighted V): scores first, then one
-        // exp for the old maximum and one per position
         float pu[U], vfu[U][8];
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const u32 t = t0 + (u32)u * PPW + sub;
             const u32 kw[4] = {kv[u].x, kv[u].y, kv[u].z, kv[u].w}, vw[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
             float p = 0.f;
-            if (t == pos) {
+            if (t == pos) {  // (the current token: staged in LDS above, its cache row may not have landed)
 #pragma unroll
                 for (int e = 0; e < 8; e++) {
                     p += qreg[e] * kcur[ld * 8 + e];
@@ -353,31 +323,11 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
                     vfu[u][2 * e + 1] = h2f((uint16_t)(vw[e] >> 16));
                 }
             }
-            // sum over the LPP lanes of this position (xor butterflies inside a 16-lane DPP row): every lane gets the score
-            p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0xB1, 0xF, 0xF, false));
-            p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x4E, 0xF, 0xF, false));
-            p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x141, 0xF, 0xF, false));
-            if (LPP == 16) p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x140, 0xF, 0xF, false));
+            p = gq_attn::row_sum<LPP>(p);  // (every lane takes part: in front of the select)
             pu[u] = t < p1 ? p * scale : -3.0e38f;
         }
-        float m_new = m_run;
-#pragma unroll
-        for (int u = 0; u < U; u++) m_new = fmaxf(m_new, pu[u]);
-        const float resc = __expf(m_run - m_new);
-        s_run *= resc;
-#pragma unroll
-        for (int e = 0; e < 8; e++) acc[e] *= resc;
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const float wgt = pu[u] > -2.0e38f ? __expf(pu[u] - m_new) : 0.f;
-            s_run += wgt;
-#pragma unroll
-            for (int e = 0; e < 8; e++) acc[e] += wgt * vfu[u][e];
-        }
-        m_run = m_new;
+        gq_attn::softmax_update<U>(m_run, s_run, acc, pu, vfu);
     }
-    // combine the streams: red2[stream][HD] weighted sums, sc[stream] = running max, sc[NS + stream] = running sum
-    constexpr u32 NS = NW * PPW;
     const u32 stream = w * PPW + sub;
 #pragma unroll
     for (int e = 0; e < 8; e++) red2[stream * HD + ld * 8 + e] = acc[e];
@@ -386,6 +336,7 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
         sc[NS + stream] = s_run;
     }
     __syncthreads();
+    // (not attn_core.h's merge: one exponential per thread and stream over all NS streams -- another instruction sequence, kept for its speed)
     if (tid < HD) {
         float M = -3.0e38f;
 #pragma unroll
@@ -417,7 +368,7 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
 // does not wait for the position either: the rows [0, PASS) are requested together with q and the position (one memory round trip
 // instead of two); which of them are valid (t <= pos) is decided when they have landed.  Rows past the position hold whatever
 // an earlier sequence left (finite or not): their scores are replaced and their V rows zeroed before use.
-// Same arithmetic as attn_decode_kernel otherwise (fp32 scores / softmax / weighted sum from fp16 operands, one fp16 rounding).
+// The arithmetic is attn_core.h's, shared with attn_decode_kernel (fp32 scores / softmax / weighted sum from fp16 operands, one fp16 rounding).
 #ifndef GQ_ATTN_SPEC
 #define GQ_ATTN_SPEC 32  // cached rows requested before the position is known (a multiple of 16)
 #endif
@@ -427,21 +378,22 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
 // (19 us per layer on Llama-3-8B); here the next pass is requested before the current one is multiplied.  Per head the
 // arithmetic, the position -> stream assignment and the merge order are those of the QH = 1 form: bit-identical outputs.
 // A short context (the `solo` rule) is finished by ONE block per head: block (hq, sp < QH) takes head hq * QH + sp alone.
-// WIN: the window form (see attn_decode_kernel).  The rows requested ahead of the position are usable only when lo == 0; with lo > 0 they
+// WIN: the window form (attn_core.h, AttnWindow).  The rows requested ahead of the position are usable only when lo == 0; with lo > 0 they
 // are dropped (p0 >= lo > 0 below) and the first batch is requested once lo is known.
 template <int HD, int QH, bool WIN = false>
 __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint16_t *q, const int *pos_ptr, const uint16_t *kc, const uint16_t *vc,
                                                                      uint16_t *out, u32 H, u32 Hkv, u32 max_seq, float scale, u32 nsplit, float *ws,
                                                                      AttnWindow<WIN> wn) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr u32 NW = ATTN_WAVES;
-    constexpr int LPP = HD / 8, PPW = 64 / LPP, U = 4;
-    constexpr u32 NS = NW * PPW, PASS = NW * PPW * U;
+    using Geo = AttnGeom<HD>;
+    using L = gq_attn::RopedLds<HD, QH>;
+    constexpr u32 NW = Geo::NW, NS = Geo::NS;
+    constexpr int LPP = Geo::LPP, PPW = Geo::PPW, U = Geo::U;
     // (the merge and the NaN poisoning below index the block's QH * HD outputs by thread id: a build with fewer waves would silently
     // leave the upper heads of a group unwritten)
     static_assert(64 * ATTN_WAVES >= QH * HD, "attn_roped_kernel: the block must have a thread per output of its QH heads (GQ_ATTN_WAVES)");
-    float *sc = reinterpret_cast<float *>(smem);  // [QH][2 * NS] running max / sum of the position streams
-    float *red2 = sc + (size_t)QH * 2u * NS;      // [QH][NS][HD] partial outputs
+    float *lds = reinterpret_cast<float *>(smem);
+    float *sc = lds + L::sc, *red2 = lds + L::red2;
     const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
 #ifdef GQ_ATTN_PROBE  // timing probe (tools/r5): blockIdx.y = identical copies of the whole-group form, every copy writes the same outputs
     const u32 h0 = blockIdx.x * QH, g = kv_group_of(h0, H, Hkv), sp = 0u;
@@ -471,15 +423,15 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         return;
     }
     const u32 lo = window_lo(pos, wn), n = pos + 1u - lo;  // (WIN = false: lo = 0, n = pos + 1)
-    const bool solo = nsplit > 1u && n <= 2u * PASS;  // a short context is not worth splitting (see attn_decode_kernel)
+    const bool solo = gq_attn::attn_solo<HD>(n, nsplit);
     u32 nh = QH, hb = h0;  // heads of this block: [hb, hb + nh)
-    if (solo) {
+    if (solo) {  // (every block sp < QH finishes a head)
         if (sp >= (u32)QH) return;
         if (QH > 1) nh = 1u, hb = h0 + sp;
         nsplit = 1u;
     }
     const u32 spx = solo ? 0u : sp;
-    const u32 per = nsplit > 1u ? (((n - 1u + nsplit) / nsplit + PASS - 1u) / PASS) * PASS : n;
+    const u32 per = gq_attn::attn_per<HD>(n, nsplit);
     const u32 p0 = lo + spx * per, p1 = min(pos + 1u, p0 + per);
     float qreg[QH][8];
 #pragma unroll
@@ -490,9 +442,7 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
             for (int j = 1; j < QH; j++)
                 if (sp == (u32)j) qq = q4[j];
         }
-        const u32 qw[4] = {qq.x, qq.y, qq.z, qq.w};
-#pragma unroll
-        for (int e = 0; e < 4; e++) qreg[qh][2 * e] = h2f((uint16_t)(qw[e] & 0xFFFF)), qreg[qh][2 * e + 1] = h2f((uint16_t)(qw[e] >> 16));
+        gq_attn::unpack8(qq, qreg[qh]);
     }
     float m_run[QH], s_run[QH], acc[QH][8];
 #pragma unroll
@@ -522,12 +472,11 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         for (int u = 0; u < U; u++) {
             const u32 t = t0 + (u32)u * PPW + sub;
             const bool valid = t < p1;
-            const u32 kw[4] = {kv[u].x, kv[u].y, kv[u].z, kv[u].w}, vw[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
             float kf[8];
+            const u32 vw[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
+            gq_attn::unpack8(kv[u], kf);
 #pragma unroll
             for (int e = 0; e < 4; e++) {
-                kf[2 * e] = h2f((uint16_t)(kw[e] & 0xFFFF));
-                kf[2 * e + 1] = h2f((uint16_t)(kw[e] >> 16));
                 vfu[u][2 * e] = valid ? h2f((uint16_t)(vw[e] & 0xFFFF)) : 0.f;
                 vfu[u][2 * e + 1] = valid ? h2f((uint16_t)(vw[e] >> 16)) : 0.f;
             }
@@ -537,31 +486,14 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
                 float p = 0.f;
 #pragma unroll
                 for (int e = 0; e < 8; e++) p += qreg[qh][e] * kf[e];
-                p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0xB1, 0xF, 0xF, false));
-                p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x4E, 0xF, 0xF, false));
-                p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x141, 0xF, 0xF, false));
-                if (LPP == 16) p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x140, 0xF, 0xF, false));
+                p = gq_attn::row_sum<LPP>(p);
                 pu[qh][u] = valid ? p * scale : -3.0e38f;  // (a stale row past the position may have produced anything, NaN included)
             }
         }
 #pragma unroll
         for (int qh = 0; qh < QH; qh++) {
             if (QH > 1 && (u32)qh >= nh) continue;  // (wave-uniform: a solo block multiplies one head)
-            float m_new = m_run[qh];
-#pragma unroll
-            for (int u = 0; u < U; u++) m_new = fmaxf(m_new, pu[qh][u]);
-            const float resc = __expf(m_run[qh] - m_new);
-            s_run[qh] *= resc;
-#pragma unroll
-            for (int e = 0; e < 8; e++) acc[qh][e] *= resc;
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                const float wgt = pu[qh][u] > -2.0e38f ? __expf(pu[qh][u] - m_new) : 0.f;
-                s_run[qh] += wgt;
-#pragma unroll
-                for (int e = 0; e < 8; e++) acc[qh][e] += wgt * vfu[u][e];
-            }
-            m_run[qh] = m_new;
+            gq_attn::softmax_update<U>(m_run[qh], s_run[qh], acc[qh], pu[qh], vfu);
         }
         if (QH > 1) {
 #pragma unroll
@@ -582,14 +514,9 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         }
     }
     __syncthreads();
-    // the factors e^(m_i - M) of the streams once per head (one thread per stream) instead of once per output element: the same
-    // values, 32 exponentials less on the tail of every thread
-    float *fl = red2 + (size_t)QH * NS * HD;  // [QH][NS] factors, [QH] maxima
-    // Streams that saw no position (a short context: wave w starts at position p0 + 16 w) hold m = -3e38, l = 0, o = 0: their factor
-    // is exactly 0 and they add exactly 0 -- the merge runs over the groups of 8 streams that can hold something, same sums bit for bit
-    // (at the 50 positions of an average bench step: 16 of the 32 streams).
-    const u32 nw_act = min(NW, (p1 - p0 + (u32)(PPW * U) - 1u) / (u32)(PPW * U));
-    const u32 ng = (nw_act * (u32)PPW + 7u) >> 3;
+    // the merge of attn_core.h (spelled out here and in ap_stream.hip::fuse_attn_head): the factors and the maximum of a head to fl ..
+    float *fl = lds + L::fl;  // [QH][NS] factors, [QH] maxima behind them
+    const u32 ng = gq_attn::merge_groups<HD>(p1 - p0);
     if (tid < nh * NS) {
         const u32 qh = tid / NS, i = tid % NS;
         const float *scq = sc + qh * 2u * NS;
@@ -601,19 +528,14 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         if (i == 0u) fl[(u32)QH * NS + qh] = M;
     }
     __syncthreads();
-    if (tid < nh * HD) {  // thread (head, dim): the streams of the head merged in ascending order
+    if (tid < nh * HD) {  // .. then thread (head, dim): the streams of the head merged in ascending order
         const u32 qh = tid / HD, dd = tid % HD, h = hb + qh;
         const float *scq = sc + qh * 2u * NS, *rq = red2 + (size_t)qh * NS * HD, *fq = fl + qh * NS;
         const float M = fl[(u32)QH * NS + qh];
         float o = 0.f, sum = 0.f;
         for (u32 g8 = 0; g8 < ng; g8++)
 #pragma unroll
-            for (u32 k = 0; k < 8u; k++) {
-                const u32 i = 8u * g8 + k;
-                const float f = fq[i];
-                sum += scq[NS + i] * f;
-                o += rq[i * HD + dd] * f;
-            }
+            for (u32 k = 0; k < 8u; k++) gq_attn::merge_step<HD>(scq, rq, fq, 8u * g8 + k, dd, o, sum);
         if (nsplit > 1u) {
             float *wp = ws + ((size_t)h * nsplit + sp) * (HD + 2u);
             wp[dd] = o;
@@ -631,13 +553,13 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
 template <int HD, bool WIN = false>
 __global__ void __launch_bounds__(HD) attn_combine_kernel(const float *ws, uint16_t *out, u32 nsplit, const int *pos_ptr, u32 max_seq, AttnWindow<WIN> wn) {
     const u32 h = blockIdx.x, tid = threadIdx.x;
-    {   // (the same rule as in attn_decode_kernel: a short context was finished by split 0)
-        constexpr u32 PASS = ATTN_WAVES * (64u / (HD / 8u)) * 4u;
-        u32 pos = (u32)pos_ptr[0];
-        if constexpr (WIN) {  // (the rule on the n rows of the window)
-            if (pos >= max_seq || pos + 1u - window_lo(pos, wn) <= 2u * PASS) return;
+    {   // (a short context was finished by the blocks of split 0)
+        const u32 pos = (u32)pos_ptr[0];  // (the solo rule: n_split > 1 here; two spellings that keep each instance's instructions)
+        if constexpr (WIN) {
+            if (pos >= max_seq || gq_attn::attn_short<HD>(pos + 1u - window_lo(pos, wn))) return;
         } else {
-            if (pos >= max_seq || pos + 1u <= 2u * PASS) return;
+            const bool done = gq_attn::attn_short<HD>(pos + 1u);
+            if (pos >= max_seq || done) return;
         }
     }
     const float *wp = ws + (size_t)h * nsplit * (HD + 2u);
@@ -1058,6 +980,19 @@ extern "C" int gq_embed_lookup_ho(const int *token, const void *table, void *out
 }
 
 namespace {
+// the argument checks every attention launch shares, in the order they have always been made (any_null: one of the launch's own pointer
+// arguments is null; misaligned: the message of the launch's own alignment check where it failed and comes in front of the sizes)
+int attn_check_args(bool any_null, const char *misaligned, bool win, uint32_t window, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim,
+                    uint32_t n_split, const float *workspace) {
+    if (win && window == 0u) return gq_fail(GQ_EINVAL, "window must be at least 1 (the query attends itself).");
+    if (any_null) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    if (misaligned) return gq_fail(GQ_EINVAL, misaligned);
+    if (n_kv_head == 0 || n_head % n_kv_head) return gq_fail(GQ_EINVAL, "n_head must be a multiple of n_kv_head.");
+    if (head_dim != 64 && head_dim != 128) return gq_fail(GQ_ENOTSUP, "head_dim must be 64 or 128.");
+    if (n_split < 1u || n_split > 64u || (n_split > 1u && !workspace)) return gq_fail(GQ_EINVAL, "n_split in 1..64, with a workspace when > 1.");
+    return GQ_OK;
+}
+
 template <bool QT, bool QKN = false, bool QB = false, bool WIN = false>
 int attn_launch(const void *qkv, const AttnQt &qt, const int *pos, const void *cos_table, const void *sin_table, void *k_cache, void *v_cache,
                 void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split,
@@ -1065,26 +1000,19 @@ int attn_launch(const void *qkv, const AttnQt &qt, const int *pos, const void *c
                 const void *qkv_bias = nullptr, uint32_t window = 0u) {
     static_assert(!(QT && QKN), "the QK-norm form reads fp16 q / k / v");
     static_assert(!(QT && WIN), "the QTIP form has no window form");
-    if (WIN && window == 0u) return gq_fail(GQ_EINVAL, "window must be at least 1 (the query attends itself).");
     static_assert(!(QB && (QT || QKN)), "the bias form does not combine with the QTIP or the QK-norm form");
-    if ((!QT && !qkv) || !pos || !cos_table || !sin_table || !k_cache || !v_cache || !out) return gq_fail(GQ_EINVAL, "null pointer argument.");
-    if (QKN && (!q_norm_weight || !k_norm_weight)) return gq_fail(GQ_EINVAL, "null pointer argument.");
-    if (QB && !qkv_bias) return gq_fail(GQ_EINVAL, "null pointer argument.");
-    if (QB && ((uintptr_t)qkv_bias & 15u)) return gq_fail(GQ_EINVAL, "gq_attn_decode_split_bias: 16-byte aligned bias.");
-    if (n_kv_head == 0 || n_head % n_kv_head) return gq_fail(GQ_EINVAL, "n_head must be a multiple of n_kv_head.");
-    if (head_dim != 64 && head_dim != 128) return gq_fail(GQ_ENOTSUP, "head_dim must be 64 or 128.");
-    if (n_split < 1u || n_split > 64u || (n_split > 1u && !workspace)) return gq_fail(GQ_EINVAL, "n_split in 1..64, with a workspace when > 1.");
-    const u32 nstreams = (u32)ATTN_WAVES * 64u / (head_dim / 8u);
-    size_t smem = ((size_t)2u * nstreams + 7u * head_dim + 2u * ATTN_WAVES + 16u + (size_t)nstreams * head_dim) * 4u;
-    if (QT) smem += 3u * (size_t)head_dim * 4u + 3u * head_dim * 2u + 3u * (size_t)(64u * ATTN_WAVES / (head_dim / 4u)) * head_dim * 4u;
+    const bool any_null = (!QT && !qkv) || !pos || !cos_table || !sin_table || !k_cache || !v_cache || !out ||
+                          (QKN && (!q_norm_weight || !k_norm_weight)) || (QB && !qkv_bias);
+    const char *misaligned = QB && ((uintptr_t)qkv_bias & 15u) ? "gq_attn_decode_split_bias: 16-byte aligned bias." : nullptr;
+    if (const int rc = attn_check_args(any_null, misaligned, WIN, window, n_head, n_kv_head, head_dim, n_split, workspace)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(n_head, n_split);
 #define GQ_LAUNCH_ATTN(HD_)                                                                                                                   \
     do {                                                                                                                                      \
         static GqPerDeviceOnce once;                                                                                                          \
         GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_decode_kernel<HD_, QT, QKN, QB, WIN>), 160 * 1024));            \
-        hipLaunchKernelGGL((attn_decode_kernel<HD_, QT, QKN, QB, WIN>), grid, dim3(64 * ATTN_WAVES), smem, s, (const uint16_t *)qkv, pos,     \
-                           (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)k_cache, (uint16_t *)v_cache,                \
+        hipLaunchKernelGGL((attn_decode_kernel<HD_, QT, QKN, QB, WIN>), grid, dim3(64 * ATTN_WAVES), gq_attn::DecodeLds<HD_>::bytes(QT), s,   \
+                           (const uint16_t *)qkv, pos, (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)k_cache, (uint16_t *)v_cache, \
                            (uint16_t *)out, n_head, n_kv_head, max_seq, scale, n_split, workspace, qt, nm, bs, wn);                           \
         if (n_split > 1u)                                                                                                                     \
             hipLaunchKernelGGL((attn_combine_kernel<HD_, WIN>), dim3(n_head), dim3(HD_), 0, s, workspace, (uint16_t *)out, n_split, pos,      \
@@ -1131,7 +1059,7 @@ extern "C" int gq_attn_decode_split_bias(const void *qkv, const int *pos, const 
 }
 
 // Sliding-window layers (Mistral, Qwen2 / Qwen3 with use_sliding_window): the three forms above over the cached rows (*pos - window, *pos]
-// only -- the geometry of the launch without a window at position n - 1, shifted by lo (see attn_decode_kernel, WIN)
+// only -- the geometry of the launch without a window at position n - 1, shifted by lo (attn_core.h, AttnWindow)
 extern "C" int gq_attn_decode_split_window(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,
                                            void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
                                            float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream) {
@@ -1183,15 +1111,11 @@ namespace {
 template <bool WIN>
 int roped_launch(const void *q, const int *pos, const void *k_cache, const void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head,
                  uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream) {
-    if (WIN && window == 0u) return gq_fail(GQ_EINVAL, "window must be at least 1 (the query attends itself).");
+    const bool any_null = !q || !pos || !k_cache || !v_cache || !out;
+    if (const int rc = attn_check_args(any_null, nullptr, WIN, window, n_head, n_kv_head, head_dim, n_split, workspace)) return rc;
     AttnWindow<WIN> wn{};
     if constexpr (WIN) wn = AttnWindow<true>{window};
-    if (!q || !pos || !k_cache || !v_cache || !out) return gq_fail(GQ_EINVAL, "null pointer argument.");
-    if (n_kv_head == 0 || n_head % n_kv_head) return gq_fail(GQ_EINVAL, "n_head must be a multiple of n_kv_head.");
-    if (head_dim != 64 && head_dim != 128) return gq_fail(GQ_ENOTSUP, "head_dim must be 64 or 128.");
-    if (n_split < 1u || n_split > 64u || (n_split > 1u && !workspace)) return gq_fail(GQ_EINVAL, "n_split in 1..64, with a workspace when > 1.");
     if (((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15u) return gq_fail(GQ_EINVAL, "buffers must be 16-byte aligned.");
-    const u32 nstreams = (u32)ATTN_WAVES * 64u / (head_dim / 8u);
     hipStream_t s = (hipStream_t)stream;
     // grouped-query models with a split cache: the 4 query heads of a KV group in one block (every cached row loaded once)
     const bool gqa = n_split >= 4u && (n_head / n_kv_head) % 4u == 0u && gq_env_int("GQ_ATTN_GQA", 1);  // (8 heads per group: two blocks of 4)
@@ -1199,28 +1123,27 @@ int roped_launch(const void *q, const int *pos, const void *k_cache, const void 
     const u32 copies = (u32)gq_env_int("GQ_ATTN_PROBE_COPIES", 0);
     const bool gqa_p = copies > 0u;
     const u32 qh = gqa_p || gqa ? 4u : 1u;
-    const size_t smem = (size_t)qh * ((size_t)2u * nstreams + (size_t)nstreams * head_dim + nstreams + 1u) * 4u;
     const dim3 grid(n_head / qh, gqa_p ? copies : n_split);
     if (gqa_p && !WIN) {
         static GqPerDeviceOnce once;
         GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<128, 4>), 160 * 1024));
-        hipLaunchKernelGGL((attn_roped_kernel<128, 4>), grid, dim3(64 * ATTN_WAVES), smem, s, (const uint16_t *)q, pos, (const uint16_t *)k_cache,
-                           (const uint16_t *)v_cache, (uint16_t *)out, n_head, n_kv_head, max_seq, scale, 1u, workspace, AttnWindow<false>{});
+        hipLaunchKernelGGL((attn_roped_kernel<128, 4>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<128, 4>::bytes()), s, (const uint16_t *)q, pos,
+                           (const uint16_t *)k_cache, (const uint16_t *)v_cache, (uint16_t *)out, n_head, n_kv_head, max_seq, scale, 1u, workspace,
+                           AttnWindow<false>{});
         GQ_HIP_CHECK(hipGetLastError());
         return GQ_OK;
     }
 #else
     const u32 qh = gqa ? 4u : 1u;
-    const size_t smem = (size_t)qh * ((size_t)2u * nstreams + (size_t)nstreams * head_dim + nstreams + 1u) * 4u;
     const dim3 grid(n_head / qh, n_split);
 #endif
 #define GQ_LAUNCH_ROPED(HD_, QH_)                                                                                                    \
     do {                                                                                                                             \
         static GqPerDeviceOnce once;                                                                                                 \
         GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<HD_, QH_, WIN>), 160 * 1024));             \
-        hipLaunchKernelGGL((attn_roped_kernel<HD_, QH_, WIN>), grid, dim3(64 * ATTN_WAVES), smem, s, (const uint16_t *)q, pos,        \
-                           (const uint16_t *)k_cache, (const uint16_t *)v_cache, (uint16_t *)out, n_head, n_kv_head, max_seq, scale,   \
-                           n_split, workspace, wn);                                                                                  \
+        hipLaunchKernelGGL((attn_roped_kernel<HD_, QH_, WIN>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<HD_, QH_>::bytes()), s, \
+                           (const uint16_t *)q, pos, (const uint16_t *)k_cache, (const uint16_t *)v_cache, (uint16_t *)out, n_head,   \
+                           n_kv_head, max_seq, scale, n_split, workspace, wn);                                                       \
         if (n_split > 1u)                                                                                                            \
             hipLaunchKernelGGL((attn_combine_kernel<HD_, WIN>), dim3(n_head), dim3(HD_), 0, s, workspace, (uint16_t *)out, n_split,   \
                                pos, max_seq, wn);                                                                                    \

@@ -12,7 +12,7 @@ What each probe pins
            rescale paths, against float64.
 Rows behind the position hold NaN / +-Inf / 65504 (stale rows of an earlier sequence): they must never reach a result.
 
-Geometry of the launches, restated from the comments in decode.hip (NW = 8 waves, U = 4 rows in flight per lane group):
+Geometry of the launches, restated from csrc/attn_core.h (AttnGeom, attn_solo, attn_per; NW = 8 waves, U = 4 rows in flight per lane group):
   LPP = hd / 8 lanes per row, PPW = 64 / LPP rows per wave instruction, PASS = NW * PPW * U rows per pass of a block
   solo: n_split > 1 and pos + 1 <= 2 PASS -> one block does it all (n_split := 1), no combine
   per = ceil(ceil((pos + 1) / n_split) / PASS) * PASS; split s takes [s per, min(pos + 1, (s + 1) per))
