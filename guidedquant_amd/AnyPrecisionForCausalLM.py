@@ -60,9 +60,10 @@ class _CapturedStep:
     """State of route 2 (`generate(capture=True)`): the StaticCache, the device words the captured step reads and writes, and the
     hipGraph of one token step of the HF module tree.  A plain object -- no closure over its own state, so no reference cycle owns the
     graph -- with an explicit `close()`: the owner (`AnyPrecisionForCausalLM._evict`) destroys the graph when it drops the entry."""
-    __slots__ = ("model", "V", "top_k", "top_p", "temperature", "seed", "cache", "tok64", "tok", "pos", "nxt", "ctr", "wv", "wi", "ban", "seq", "logits", "graph")
+    __slots__ = ("model", "V", "top_k", "top_p", "temperature", "seed", "cache", "tok64", "tok", "pos", "nxt", "ctr", "wv", "wi", "ban", "seq", "logits", "graph",
+                 "rp", "seen", "suppress")
 
-    def __init__(self, model, config, dev, total, temperature, top_k, seed, top_p=1.0):
+    def __init__(self, model, config, dev, total, temperature, top_k, seed, top_p=1.0, repetition_penalty=1.0, suppress_tokens=()):
         from transformers import StaticCache
         self.model, self.V, self.top_k, self.temperature, self.seed = model, int(config.vocab_size), int(top_k), float(temperature), int(seed)
         self.top_p = float(top_p)
@@ -73,12 +74,34 @@ class _CapturedStep:
         self.wv, self.wi, self.ban = z(128 * 64, torch.float32), z(128 * 64, torch.int32), z(6, torch.int32)
         self.seq, self.logits = z(total + 1, torch.int32), z(self.V, torch.float16)
         self.graph = None
+        # (a penalty or a suppress list: the token sets of gq_sample_topk_rep; without either, the call and the buffers of before)
+        self.rp, self.seen, self.suppress = float(repetition_penalty), None, None
+        if self.rp != 1.0 or suppress_tokens:
+            self.seen = z((self.V + 31) // 32, torch.int32)
+            if suppress_tokens:
+                self.suppress = z((self.V + 31) // 32, torch.int32)
+                self.build_set(self.suppress, torch.tensor(list(suppress_tokens), dtype=torch.int32, device=dev))
+
+    def build_set(self, words, ids):
+        """words = the set of `ids` (cleared first), one launch outside the graph"""
+        from . import _lib
+        ids = ids.to(device=words.device, dtype=torch.int32).contiguous().view(-1)
+        _lib.check(_lib.lib().gq_token_set_build(ids.data_ptr() if ids.numel() else None, ids.numel(), self.V, words.data_ptr(), 1,
+                                                _lib.current_stream_ptr()), "gq_token_set_build")
 
     def step(self):
         from . import _lib
         # (positions come from the cache itself: StaticLayer.cumulative_length is a device word the layer advances in place)
         out = self.model(input_ids=self.tok64, past_key_values=self.cache, use_cache=True)
         self.logits.copy_(out.logits.view(-1))
+        if self.seen is not None:
+            _lib.check(_lib.lib().gq_sample_topk_rep(self.logits.data_ptr(), self.V, self.top_k, self.top_p, self.temperature, self.seed, self.ctr.data_ptr(),
+                                                    self.wv.data_ptr(), self.wi.data_ptr(), self.tok.data_ptr(), self.pos.data_ptr(), self.nxt.data_ptr(),
+                                                    self.ban.data_ptr(), self.seq.data_ptr(), self.seq.numel(), None, None, 0, None, self.rp,
+                                                    self.seen.data_ptr(), self.suppress.data_ptr() if self.suppress is not None else None,
+                                                    _lib.current_stream_ptr()), "gq_sample_topk_rep")
+            self.tok64.copy_(self.tok.view(1, 1))
+            return
         _lib.check(_lib.lib().gq_sample_topk_p(self.logits.data_ptr(), self.V, self.top_k, self.top_p, self.temperature, self.seed, self.ctr.data_ptr(),
                                               self.wv.data_ptr(), self.wi.data_ptr(), self.tok.data_ptr(), self.pos.data_ptr(), self.nxt.data_ptr(),
                                               self.ban.data_ptr(), self.seq.data_ptr(), self.seq.numel(), None, None, 0, None,
@@ -93,7 +116,7 @@ class _CapturedStep:
     def capture(self, T):
         """two eager steps on a side stream, then the capture; the cache and the positions are re-set behind them"""
         from ._graphs import capture
-        keep = (self.tok64.clone(), self.tok.clone(), self.ctr.clone())
+        keep = (self.tok64.clone(), self.tok.clone(), self.ctr.clone(), self.seen.clone() if self.seen is not None else None)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -111,6 +134,8 @@ class _CapturedStep:
         self.tok64.copy_(keep[0])
         self.tok.copy_(keep[1])
         self.ctr.copy_(keep[2])
+        if self.seen is not None:  # (the warm-up steps left their draws in the set)
+            self.seen.copy_(keep[3])
         self.pos.fill_(T - 1)
         if T == 1:  # (no prompt pass ran: the layers allocated their tensors inside the warm-up)
             self.cache.reset()
@@ -278,11 +303,14 @@ class AnyPrecisionForCausalLM(nn.Module):
     # keyword arguments of `generate` the fused routes understand (everything else -> transformers' own generate)
     _ROUTE_KW = {"input_ids", "inputs", "max_new_tokens", "min_new_tokens", "max_length", "do_sample", "temperature", "top_k", "top_p",
                  "pad_token_id", "eos_token_id", "attention_mask", "cache_implementation", "use_cache", "streamer", "num_beams",
-                 "num_return_sequences", "repetition_penalty", "return_dict_in_generate"}
+                 "num_return_sequences", "repetition_penalty", "suppress_tokens", "return_dict_in_generate"}
 
-    def _route_request(self, args, kwargs):
+    def _route_request(self, args, kwargs, sampler_processors=False):
         """(params, None) when the request is one the fused decode routes serve -- ONE sequence, greedy or top-k (<= 64) sampling with
-        or without a nucleus (top_p), no logits processors beyond min_new_tokens on EOS -- else (None, reason).  Missing sampling arguments come from
+        or without a nucleus (top_p), no logits processors beyond min_new_tokens on EOS, a repetition penalty (finite, > 0) and
+        suppress_tokens (a flat list of ids < vocab), both applied inside the fused sampler -- else (None, reason).
+        sampler_processors: `generate` asks with True.  The two-argument form keeps the answer it always gave -- a repetition penalty
+        other than 1 or a suppress list is declined -- for callers that drive a sampler without the token sets (gq_sample_topk_p).  Missing sampling arguments come from
         the model's generation_config exactly as in transformers (top_k defaults to 50 there)."""
         if len(args) > 1 or any(k not in self._ROUTE_KW for k in kwargs):
             return None, "arguments outside the fused routes: %s" % sorted(k for k in kwargs if k not in self._ROUTE_KW)
@@ -309,9 +337,24 @@ class AnyPrecisionForCausalLM(nn.Module):
         if (g("num_beams", 1) or 1) != 1 or (g("num_return_sequences", 1) or 1) != 1 or g("return_dict_in_generate", False) or g("use_cache", True) is False:
             return None, "beam search / several return sequences / dict output / use_cache=False"
         rp = g("repetition_penalty", 1.0)
-        if rp is not None and float(rp) != 1.0:
-            return None, "repetition_penalty"
-        for name in ("no_repeat_ngram_size", "encoder_no_repeat_ngram_size", "bad_words_ids", "force_words_ids", "suppress_tokens", "begin_suppress_tokens",
+        try:  # (transformers demands a strictly positive float; the sampler a finite one)
+            rp = 1.0 if rp is None else float(rp)
+        except (TypeError, ValueError):
+            return None, "repetition_penalty is not a number"
+        if not (0.0 < rp < float("inf")):
+            return None, "repetition_penalty must be finite and > 0"
+        sup = g("suppress_tokens", None)
+        if sup is None:
+            sup = ()
+        else:
+            vocab = int(getattr(self.config, "vocab_size", 0) or 0)
+            sup = sup.tolist() if torch.is_tensor(sup) and sup.dim() == 1 else sup
+            if not isinstance(sup, (list, tuple)) or any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < vocab for t in sup):
+                return None, "suppress_tokens must be a flat list of token ids below the vocabulary size"
+            sup = tuple(sorted(set(int(t) for t in sup)))
+        if not sampler_processors and (rp != 1.0 or sup):
+            return None, "repetition_penalty" if rp != 1.0 else "suppress_tokens"
+        for name in ("no_repeat_ngram_size", "encoder_no_repeat_ngram_size", "bad_words_ids", "force_words_ids", "begin_suppress_tokens",
                      "forced_bos_token_id", "forced_eos_token_id", "sequence_bias", "typical_p", "epsilon_cutoff", "eta_cutoff", "min_p", "penalty_alpha",
                      "min_length"):
             v = getattr(gc_, name, None) if gc_ is not None else None
@@ -346,20 +389,29 @@ class AnyPrecisionForCausalLM(nn.Module):
         if len(eos) > 4:
             return None, "more than 4 EOS ids"
         return dict(ids=ids, T=T, max_new=int(max_new), min_new=min(int(g("min_new_tokens", 0) or 0), int(max_new)), temperature=temperature,
-                    top_k=int(top_k), top_p=float(top_p), eos=eos, streamer=kwargs.get("streamer"), do_sample=do_sample), None
+                    top_k=int(top_k), top_p=float(top_p), eos=eos, streamer=kwargs.get("streamer"), do_sample=do_sample,
+                    repetition_penalty=rp, suppress_tokens=sup), None
 
     def generate(self, *args, **kwargs):
         """`generate` of the reference's HF surface (inference_example.py:34-77).  Three routes behind the one call:
           1. the fused decode model of the same checkpoint (`native_decoder`: prompt through the HIP prompt pass, every new token one
              replay of the captured 5-launches-per-layer graph, sampling / EOS suppression / embedding of the next token on the device)
-             -- taken AUTOMATICALLY for a request it serves (`_route_request`: one sequence, greedy or top-k <= 64 at top_p = 1 -- the
-             reference's own call); `native=False` opts out, `native=True` insists (ValueError when the request is not served);
+             -- taken AUTOMATICALLY for a request it serves (`_route_request`: one sequence, greedy or top-k <= 64 sampling with or
+             without a nucleus top_p, min_new_tokens, repetition_penalty, suppress_tokens -- the reference's own call and the published
+             Qwen2.5-Instruct generation config); `native=False` opts out, `native=True` insists (ValueError when the request is not
+             served).  The automatic route keeps the module tree whole, so the fused q/k/v/gate/up tensors are a SECOND copy of those
+             weights on the device (1.1 GB for an 8B 2-bit model, about 14 GB for a 70B one; see `native_decoder`); `native=True` releases the module tree's copy;
           2. `capture=True`: the HF module tree with its decode step captured as ONE hipGraph over a transformers StaticCache, the
              fused sampler at its end -- opt-in: measured SLOWER than route 3 on the 8B model (172 vs 249 tokens/s: the module tree's
              ~1,500 small launches per token cost more as graph nodes than as stream launches; the fused model is the fast form);
-          3. transformers' own generate on the module tree (anything else: beams, top_p, processors, batches; or `native=False`).
+          3. transformers' own generate on the module tree (anything else: beams, top_k > 64 or none, other logits processors, batches,
+             dict output; or `native=False`).
         Route 1 serves every precision of the checkpoint, 2 to 8 bits: the decode step's GEMVs run the exact fp16-order kernels
         below 5 bits and ap_wide.hip's LDS-table kernel from 5 to 8 (a parent of 8 bits serves precision=5..8 without the module tree).
+        repetition_penalty (finite, > 0; keyword or generation config) and suppress_tokens (a flat list of ids) are applied INSIDE the
+        fused sampler of routes 1 and 2, as transformers applies RepetitionPenaltyLogitsProcessor and SuppressTokensLogitsProcessor to the
+        fp32 scores: a token of the sequence so far (prompt included) has its logit divided by the penalty when positive and multiplied
+        when negative, once per distinct token; a suppressed token is never drawn (and, stricter than -inf, takes no top_k place).
         Returns the [1, prompt + new] token tensor like HF does; stops at EOS (checked every 32 tokens, the tail is cut); honours
         min_new_tokens, streamer, precision=."""
         prev_precision = self.precision
@@ -368,7 +420,7 @@ class AnyPrecisionForCausalLM(nn.Module):
         native = kwargs.pop('native', None)
         capture = kwargs.pop('capture', None)
         try:
-            req, why = self._route_request(args, kwargs) if (native is not False or capture is True) else (None, "opted out")
+            req, why = self._route_request(args, kwargs, sampler_processors=True) if (native is not False or capture is True) else (None, "opted out")
             if req is not None and self.device.type != "cuda":
                 req, why = None, "the fused routes need the GPU"
             if native is True and req is None:
@@ -459,14 +511,15 @@ class AnyPrecisionForCausalLM(nn.Module):
         # causal mask is quadratic in it).
         cap = total if total > 16384 else max(256, 1 << (total - 1).bit_length())
         dec.setup_caches(1, min(cap, dec.config.block_size))
-        key = (self.precision, dec.max_seq_length, req["temperature"], req["top_k"], req["top_p"])
+        key = (self.precision, dec.max_seq_length, req["temperature"], req["top_k"], req["top_p"], req["repetition_penalty"], req["suppress_tokens"])
         graph = self._native_cache.get(("graph",) + key)
         if graph is None:
             self._evict("graph")
             # (eight token steps per graph replay -- the host looks at the sequence once per `chunk` = 32 tokens anyway; what is left of a
             # chunk runs through the single-step graph over the same state: exactly the steps asked for)
             graph = gen.DecodeGraph(dec, self.device, native_sampling=True, fold_embed=True, seq_capacity=dec.max_seq_length + 1,
-                                    seed=self._SAMPLER_SEED, temperature=req["temperature"], top_k=req["top_k"], top_p=req["top_p"], steps_per_replay=8)
+                                    seed=self._SAMPLER_SEED, temperature=req["temperature"], top_k=req["top_k"], top_p=req["top_p"], steps_per_replay=8,
+                                    repetition_penalty=req["repetition_penalty"], suppress_tokens=req["suppress_tokens"])
             self._native_cache[("graph",) + key] = graph
         if req.get("do_sample"):
             graph.rng_counter.copy_(self._fresh_rng_word())
@@ -485,6 +538,7 @@ class AnyPrecisionForCausalLM(nn.Module):
                 else:
                     dec(pre.view(1, -1), pos)
             graph.set_token(ids32[T - 1:T], T - 1)
+            graph.set_history(ids32)  # (the penalty's token set: all T prompt tokens, rebuilt per request)
             if req["streamer"] is not None:
                 req["streamer"].put(ids.cpu())
             done, cut = 0, None
@@ -512,14 +566,15 @@ class AnyPrecisionForCausalLM(nn.Module):
         captured once per (precision, cache length, sampling) and replayed; the prompt runs eagerly through the same cache."""
         ids, T, max_new = req["ids"].to(self.device), req["T"], req["max_new"]
         total = T + max_new
-        key = ("cap", self.precision, total, req["temperature"], req["top_k"], req["top_p"])
+        key = ("cap", self.precision, total, req["temperature"], req["top_k"], req["top_p"], req["repetition_penalty"], req["suppress_tokens"])
         st = self._native_cache.get(key)
         # (no_grad, not inference_mode: the first graph capture of a process creates the generator's graph-safe state tensors, and
         # inference tensors could not be updated by the captures that follow outside inference mode)
         with torch.no_grad():
             if st is None:
                 self._evict("cap")  # (the old entry's graph is destroyed HERE, before the new capture begins)
-                st = _CapturedStep(self.model, self.config, self.device, total, req["temperature"], req["top_k"], self._SAMPLER_SEED, req["top_p"])
+                st = _CapturedStep(self.model, self.config, self.device, total, req["temperature"], req["top_k"], self._SAMPLER_SEED, req["top_p"],
+                                   req["repetition_penalty"], req["suppress_tokens"])
                 self._native_cache[key] = st
             st.cache.reset()
             st.seq[:T].copy_(ids.view(-1).to(torch.int32))
@@ -527,6 +582,8 @@ class AnyPrecisionForCausalLM(nn.Module):
             st.ban.copy_(torch.tensor(ban, dtype=torch.int32))
             if req.get("do_sample"):
                 st.ctr.copy_(self._fresh_rng_word())
+            if st.seen is not None:  # (all T prompt tokens, per request; the capture's warm-up steps restore it)
+                st.build_set(st.seen, ids.view(-1))
             if T > 1:
                 self.model(input_ids=ids[:, :T - 1], past_key_values=st.cache, use_cache=True)
             st.tok64.copy_(ids[:, T - 1:T])

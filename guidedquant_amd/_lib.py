@@ -27,6 +27,7 @@ EXPORTS = [
     "gq_qtip_decompress", "gq_qtip_gemm", "gq_qtip_gemm_ws", "gq_qtip_gemm_ws_bytes", "gq_debug_ap_last_route", "gq_debug_ap_plan_route",
     "gq_attn_decode_split_qknorm", "gq_qknorm_rope_cache_rows", "gq_attn_decode_split_bias",
     "gq_attn_decode_split_window", "gq_attn_decode_split_qknorm_window", "gq_attn_decode_split_bias_window", "gq_attn_decode_roped_window",
+    "gq_token_set_build", "gq_sample_topk_rep",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -124,6 +125,9 @@ def lib():
         L.gq_sample_topk.argtypes = [vp, u32, i32, f32, u32, vp, vp, vp, vp, vp, vp, vp]
         L.gq_sample_topk_ex.argtypes = [vp, u32, i32, f32, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp]
         L.gq_sample_topk_p.argtypes = [vp, u32, i32, f32, f32, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp]
+        # (gq_sample_topk_p + repetition_penalty, seen, suppress in front of the stream)
+        L.gq_sample_topk_rep.argtypes = [vp, u32, i32, f32, f32, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, f32, vp, vp, vp]
+        L.gq_token_set_build.argtypes = [vp, u32, u32, vp, i32, vp]
         L.gq_anyprec_gemv_cpu.argtypes = [vp, vp, vp, vp, u32, u32, u32, i32, i32, i32]
         L.gq_anyprec_dequant_cpu.argtypes = [vp, vp, vp, u32, u32, i32, i32]
         L.gq_anyprec_gemm.argtypes = [vp, vp, vp, vp, u32, u32, u32, i32, vp]

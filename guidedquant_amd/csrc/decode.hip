@@ -623,6 +623,9 @@ __device__ __forceinline__ u32 hash32(u32 x) {
 // (registers + one DPP wave reduction + one LDS combine per round) instead of K rounds of block-wide arg-max.
 __device__ __forceinline__ u32 ordered_key16(uint16_t h) { return (h & 0x8000u) ? (u32)(uint16_t)~h : ((u32)h | 0x8000u); }
 __device__ __forceinline__ uint16_t unordered_key16(u32 o) { return (o & 0x8000u) ? (uint16_t)(o & 0x7FFFu) : (uint16_t)~o; }
+// the same image of an fp32 bit pattern (gq_sample_topk_rep: a penalised logit is an fp32 number that in general is no fp16 value)
+__device__ __forceinline__ u32 ordered_key32(u32 b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
+__device__ __forceinline__ u32 unordered_key32(u32 o) { return (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o; }
 
 // The K-th largest of the 64 * EPT keys of ONE wave by binary search on the key bits: the count of a round is EPT ballots +
 // scalar population counts -- no LDS, no barrier (the block-wide version above pays a 1024-thread barrier per bit: 13 us
@@ -684,7 +687,11 @@ struct SampleEx {
 };
 
 // what both draw kernels do with the token: outputs, token / position feedback, the sequence store
-__device__ __forceinline__ void sample_publish(int tokc, u32 ctr, int *counter, int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex) {
+// (seen: the token set of gq_sample_topk_rep or NULL -- the drawn token's bit, by a vector atomic from this one lane; the next step's
+// stage 1 reads the word behind a kernel boundary.  The token of an empty candidate set is no id of the vocabulary and sets nothing.)
+__device__ __forceinline__ void sample_publish(int tokc, u32 ctr, int *counter, int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex,
+                                               u32 *seen = nullptr, u32 V = 0u) {
+    if (seen && (u32)tokc < V) atomicOr(seen + ((u32)tokc >> 5), 1u << ((u32)tokc & 31u));
     next_tok[0] = tokc;
     counter[0] = (int)(ctr + 1u);
     if (tok_io) tok_io[0] = tokc;
@@ -857,6 +864,190 @@ __global__ void __launch_bounds__(1024) sample_stage2(const float *cand_val, con
     if (ex.x_out) {
         __syncthreads();
         sample_embed(chosen, tid, ex);
+    }
+}
+
+// ---- gq_sample_topk_rep: the two stages over fp32 candidate values, with the token sets
+// KERNELS OF THEIR OWN, on purpose.  Sharing a body with sample_stage1 / sample_stage2 through a template parameter was tried first and
+// changed the code of the old instances (tools/cmp_kernels.py: 3 instructions of stage 1, 23 to 61 of stage 2 and its register count --
+// LDS arrays handed to a common body as pointers lose what the compiler knew about them).  What gq_sample_topk / _ex / _p launch must
+// not move, so the text below repeats theirs where the two agree; the differences are marked (REP).
+struct SampleRep {
+    float rp;
+    const u32 *seen, *suppress;
+};
+// stage 1 (REP): a token of `suppress` is no candidate, a token of `seen` carries s = v < 0 ? v * rp : v / rp in fp32, and the key is
+//   (order-preserving image of ALL 32 bits of s) << LB | (2^LB - 1 - position in the slice): u64 keys of 32 + LB <= 43 bits.
+// The words of the two sets are read where the logits are: a thread's EPT <= 8 consecutive tokens lie in at most two of them (a slice
+// starts at any token, not at a multiple of 32).
+template <int KM, int EPT, int LB>
+__global__ void __launch_bounds__(256) sample_stage1_rep(const uint16_t *logits, u32 V, float *cand_val, int *cand_idx, const int *ban, const int *pos_io,
+                                                         SampleRep rep) {
+    typedef unsigned long long u64;
+    static_assert(256 * EPT == 1 << LB && EPT <= 8, "a slice is one position per key of the block; a thread's tokens span two set words");
+    constexpr u32 LMASK = (1u << LB) - 1u;
+    __shared__ u64 surv[4 * KM];
+    __shared__ u64 fin[KM];
+    const u32 per = (V + SAMP_BLOCKS - 1) / SAMP_BLOCKS;  // <= 256 * EPT
+    const u32 lo = blockIdx.x * per, hi = min(lo + per, V);
+    const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
+    int nban = 0, bid[4] = {-1, -1, -1, -1};
+    if (ban) {  // (wave-uniform scalar loads)
+        nban = ban[0];
+        if (pos_io && pos_io[0] >= ban[1]) nban = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) bid[i] = i < nban ? ban[2 + i] : -1;
+    }
+    u64 sbits = 0ull, pbits = 0ull;  // (REP) bit e: token lo + tid * EPT + e is seen / suppressed
+    const u32 g0 = lo + tid * (u32)EPT;
+    if (g0 < hi) {  // (words of tokens < hi <= V only: a set is ceil(V / 32) words)
+        const u32 w0 = g0 >> 5, w1 = min(g0 + (u32)EPT - 1u, hi - 1u) >> 5;
+        if (rep.seen) sbits = ((u64)rep.seen[w0] | ((u64)(w1 != w0 ? rep.seen[w1] : 0u) << 32)) >> (g0 & 31u);
+        if (rep.suppress) pbits = ((u64)rep.suppress[w0] | ((u64)(w1 != w0 ? rep.suppress[w1] : 0u) << 32)) >> (g0 & 31u);
+    }
+    u64 key[EPT];
+#pragma unroll
+    for (int e = 0; e < EPT; e++) {
+        const u32 li = tid * (u32)EPT + (u32)e, gi = lo + li;
+        const bool banned = (int)gi == bid[0] || (int)gi == bid[1] || (int)gi == bid[2] || (int)gi == bid[3];
+        u64 k = 0ull;
+        if (gi < hi && !banned && !((pbits >> e) & 1ull)) {
+            const float v = h2f(logits[gi]);
+            // (-0 is not < 0; the division is IEEE's, correctly rounded: the library is built without fast-math)
+            const float sv = ((sbits >> e) & 1ull) ? (v < 0.f ? v * rep.rp : v / rep.rp) : v;
+            k = ((u64)ordered_key32(__builtin_bit_cast(u32, sv)) << LB) | (u64)(LMASK - li);
+        }
+        key[e] = k;
+    }
+    if (l < KM) surv[w * KM + l] = 0ull;
+    const u64 t = wave_select_threshold<EPT, u64, 32 + LB, LB>(key, KM);
+    wave_compact<EPT, u64>(key, t, surv + w * KM, KM, l);
+    __syncthreads();
+    if (w == 0) {  // top KM of the 4 * KM survivors
+        u64 k2[KM / 16];
+#pragma unroll
+        for (int e = 0; e < KM / 16; e++) k2[e] = surv[(u32)e * 64u + l];
+        const u64 t2 = wave_select_threshold<KM / 16, u64, 32 + LB, LB>(k2, KM);
+        if (l < KM) fin[l] = 0ull;
+        const int n = wave_compact<KM / 16, u64>(k2, t2, fin, KM, l);
+        if (l < KM) {
+            const u64 k = fin[l];
+            const bool ok = (int)l < n && k != 0ull;
+            const u32 li = LMASK - ((u32)k & LMASK);
+            cand_val[blockIdx.x * KM + l] = ok ? __builtin_bit_cast(float, unordered_key32((u32)(k >> LB))) : -3.0e38f;  // (REP) s itself, 32 bits
+            cand_idx[blockIdx.x * KM + l] = ok ? (int)(lo + li) : -1;
+        }
+    }
+}
+
+// stage 2 (REP): key = (image of the 32 bits of the candidate value) << IB | (2^IB - 1 - token id), 32 + IB <= 50 bits, built from
+// cand_val directly; the publishing lane sets the drawn token's bit in `seen`.  Behind the selection: the text of sample_stage2.
+template <int KM, int IB>
+__global__ void __launch_bounds__(1024) sample_stage2_rep(const float *cand_val, const int *cand_idx, int top_k, float temperature,
+                                                          u32 seed, int *counter, int *tok_io, int *pos_io, int *next_tok, SampleEx ex, u32 *seen, u32 V) {
+    constexpr int EPT = KM / 8;  // candidates per thread
+    constexpr u32 IMASK = (1u << IB) - 1u;
+    __shared__ float selv[KM];
+    __shared__ int seli[KM];
+    __shared__ unsigned long long surv[16 * KM];
+    __shared__ unsigned long long fin[KM];
+    __shared__ int slot, chosen;
+    const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
+    unsigned long long key[EPT];
+#pragma unroll
+    for (int e = 0; e < EPT; e++) {
+        const u32 c = tid * (u32)EPT + (u32)e;
+        const float v = cand_val[c];
+        const int id = cand_idx[c];
+        key[e] = id >= 0 ? (((unsigned long long)ordered_key32(__builtin_bit_cast(u32, v)) << IB) | (unsigned long long)(IMASK - (u32)id)) : 0ull;  // (REP)
+    }
+    const int K = top_k < 1 ? 1 : (top_k > KM ? KM : top_k);
+    if (l < KM) surv[w * KM + l] = 0ull;
+    const unsigned long long t = wave_select_threshold<EPT, unsigned long long, 32 + IB, IB>(key, K);
+    wave_compact<EPT, unsigned long long>(key, t, surv + w * KM, KM, l);
+    __syncthreads();
+    if (w == 0) {
+        unsigned long long k8[KM / 4];
+#pragma unroll
+        for (int e = 0; e < KM / 4; e++) k8[e] = surv[(u32)e * 64u + l];
+        const unsigned long long t2 = wave_select_threshold<KM / 4, unsigned long long, 32 + IB, IB>(k8, K);
+        if (l < KM) fin[l] = 0ull;
+        const int n2 = wave_compact<KM / 4, unsigned long long>(k8, t2, fin, KM, l);
+        if (l == 0) slot = n2;
+        if (l < KM) {
+            const unsigned long long k = fin[l];
+            selv[l] = __builtin_bit_cast(float, unordered_key32((u32)(k >> IB)));  // (REP)
+            seli[l] = (int)(IMASK - ((u32)k & IMASK));
+        }
+    }
+    __syncthreads();
+    if (w == 0) {
+        const int n = min(slot, K);
+        const float T = fmaxf(temperature, 1e-5f);
+        const u32 ctr = (u32)counter[0];
+        float score = -3.0e38f;
+        int tokc = 0x7FFFFFFF;
+        // nucleus filter on the top-k survivors -- transformers' TopPLogitsWarper behind TopKLogitsWarper behind the temperature
+        // (generation/logits_process.py: probabilities of the scaled, top-k-filtered scores, cumulative sum in ASCENDING order, a token
+        // goes when the sum up to and including it is <= 1 - top_p, the most probable one always stays).  n <= 64 candidates, one per
+        // lane: the cumulative sum of a lane is a loop over the wave (ties ordered by token id, higher id first = the lower key).
+        bool keep = (int)l < n;
+        if (ex.top_p > 0.f && ex.top_p < 1.f) {
+            const float v = (int)l < n ? selv[l] / T : -3.0e38f;
+            float mx = v;
+#pragma unroll
+            for (int sh = 32; sh >= 1; sh >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sh, 64));
+            const float e = (int)l < n ? __expf(v - mx) : 0.f;
+            float z = e;
+#pragma unroll
+            for (int sh = 32; sh >= 1; sh >>= 1) z += __shfl_xor(z, sh, 64);
+            const float pr = e / z;
+            const int myid = (int)l < n ? seli[l] : -1;
+            float cum = 0.f;
+            int greater = 0;
+            for (int j = 0; j < n; j++) {
+                const float vj = __shfl(v, j, 64), pj = __shfl(pr, j, 64);
+                const int idj = __shfl(myid, j, 64);
+                const bool below = vj < v || (vj == v && idj > myid);  // j sorts before this lane in ascending order
+                cum += (below || j == (int)l) ? pj : 0.f;
+                greater += (vj > v || (vj == v && idj < myid)) ? 1 : 0;
+            }
+            keep = keep && (greater == 0 || !(cum <= 1.0f - ex.top_p));
+        }
+        if (keep) {
+            // q ~ Exp(1) = -log(u), u in (0,1]; the random number is tied to the TOKEN id, not to the slot
+            const u32 r = hash32(seed ^ hash32(ctr * 0x9E3779B9u + (u32)seli[l] + 1u));
+            const float u = ((float)(r >> 8) + 1.0f) * (1.0f / 16777216.0f);
+            score = selv[l] / T - __logf(-__logf(u));
+            tokc = seli[l];
+        }
+#pragma unroll
+        for (int sh = 32; sh >= 1; sh >>= 1) {
+            const float os = __shfl_xor(score, sh, 64);
+            const int ot = __shfl_xor(tokc, sh, 64);
+            if (os > score || (os == score && ot < tokc)) { score = os; tokc = ot; }
+        }
+        if (l == 0) {
+            sample_publish(tokc, ctr, counter, tok_io, pos_io, next_tok, ex, seen, V);
+            chosen = tokc;
+        }
+    }
+    if (ex.x_out) {
+        __syncthreads();
+        sample_embed(chosen, tid, ex);
+    }
+}
+
+// token set of gq_token_set_build: one block -- the words are cleared (clear != 0), the block meets, then every id in [0, V) sets its
+// bit with a vector atomic (duplicates and ids of one word from several threads are then no race)
+__global__ void __launch_bounds__(1024) token_set_build_kernel(const int *ids, u32 n, u32 V, u32 *set, int clear) {
+    const u32 words = (V + 31u) / 32u;
+    if (clear)
+        for (u32 i = threadIdx.x; i < words; i += 1024u) set[i] = 0u;
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < n; i += 1024u) {
+        const u32 t = (u32)ids[i];
+        if (t < V) atomicOr(set + (t >> 5), 1u << (t & 31u));
     }
 }
 
@@ -1210,6 +1401,18 @@ extern "C" int gq_dense_gemv_f16(const void *x, const void *W, void *out, uint32
 
 namespace {
 // the pair of one width (logits per thread, local-position bits, token-id bits): candidates per block by top_k
+// (gq_sample_topk_rep: the kernels of fp32 candidate values -- kernels of their own, the pairs above are launched as before)
+template <int EPT, int LB, int IB>
+void sample_launch_rep_w(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter, float *work_val, int *work_idx,
+                         int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, const SampleRep &rep, u32 *seen, hipStream_t s) {
+    if (top_k <= 32) {
+        hipLaunchKernelGGL((sample_stage1_rep<32, EPT, LB>), dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban, pos_io, rep);
+        hipLaunchKernelGGL((sample_stage2_rep<32, IB>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex, seen, vocab);
+    } else {
+        hipLaunchKernelGGL((sample_stage1_rep<64, EPT, LB>), dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban, pos_io, rep);
+        hipLaunchKernelGGL((sample_stage2_rep<64, IB>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex, seen, vocab);
+    }
+}
 template <int EPT, int LB, int IB>
 void sample_launch_w(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter, float *work_val, int *work_idx,
                      int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, hipStream_t s) {
@@ -1221,13 +1424,19 @@ void sample_launch_w(const void *logits, uint32_t vocab, int top_k, float temper
         hipLaunchKernelGGL((sample_stage2<64, IB>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex);
     }
 }
+// rep == NULL: the kernels of gq_sample_topk / _ex / _p
 int sample_launch(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter, float *work_val, int *work_idx,
-                  int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, void *stream) {
+                  int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, void *stream, const SampleRep *rep = nullptr, u32 *seen = nullptr) {
     if (!logits || !counter || !work_val || !work_idx || !next_tok) return gq_fail(GQ_EINVAL, "null pointer argument.");
     if (top_k > SAMP_K) return gq_fail(GQ_ENOTSUP, "top_k > 64 is not supported by the fused sampler.");
     if (vocab > SAMP_MAX_VOCAB) return gq_fail(GQ_ENOTSUP, "vocab too large for the fused sampler (<= 262144).");
     hipStream_t s = (hipStream_t)stream;
-    if (vocab <= 131072u)  // slices of <= 1024 logits, 17-bit token ids
+    if (rep) {
+        if (vocab <= 131072u)
+            sample_launch_rep_w<4, 10, 17>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, *rep, seen, s);
+        else
+            sample_launch_rep_w<8, 11, 18>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, *rep, seen, s);
+    } else if (vocab <= 131072u)  // slices of <= 1024 logits, 17-bit token ids
         sample_launch_w<4, 10, 17>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, s);
     else  // slices of <= 2048 logits through the same 128 blocks, 18-bit token ids
         sample_launch_w<8, 11, 18>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, s);
@@ -1248,11 +1457,11 @@ extern "C" int gq_sample_topk_ex(const void *logits, uint32_t vocab, int top_k, 
     return gq_sample_topk_p(logits, vocab, top_k, 1.0f, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ban, seq_out, seq_cap,
                             embed_table, x_out, dim, ssq_out, stream);
 }
-extern "C" int gq_sample_topk_p(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
-                                float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
-                                uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, void *stream) {
+namespace {
+// the extras of gq_sample_topk_p / gq_sample_topk_rep, checked
+int sample_extras(SampleEx &ex, uint32_t vocab, float top_p, const int *ban, int *seq_out, uint32_t seq_cap, const void *embed_table, void *x_out,
+                  uint32_t dim, float *ssq_out) {
     if (!(top_p > 0.f)) return gq_fail(GQ_EINVAL, "top_p must be in (0, 1] (1 = no nucleus filter).");
-    SampleEx ex{};
     ex.top_p = top_p;
     ex.ban = ban;
     ex.seq_out = seq_out;
@@ -1267,5 +1476,34 @@ extern "C" int gq_sample_topk_p(const void *logits, uint32_t vocab, int top_k, f
     } else if (ssq_out) {
         return gq_fail(GQ_EINVAL, "ssq_out without x_out.");
     }
+    return GQ_OK;
+}
+}  // namespace
+extern "C" int gq_sample_topk_p(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
+                                float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                                uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, void *stream) {
+    SampleEx ex{};
+    if (int rc = sample_extras(ex, vocab, top_p, ban, seq_out, seq_cap, embed_table, x_out, dim, ssq_out)) return rc;
     return sample_launch(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, stream);
+}
+
+extern "C" int gq_sample_topk_rep(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
+                                  float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                                  uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                                  uint32_t *seen, const uint32_t *suppress, void *stream) {
+    if (!(repetition_penalty > 0.f) || !(repetition_penalty < INFINITY))
+        return gq_fail(GQ_EINVAL, "repetition_penalty must be finite and > 0 (1 = no penalty).");
+    if (!seen && repetition_penalty != 1.0f) return gq_fail(GQ_EINVAL, "repetition_penalty != 1 needs the `seen` token set.");
+    SampleEx ex{};
+    if (int rc = sample_extras(ex, vocab, top_p, ban, seq_out, seq_cap, embed_table, x_out, dim, ssq_out)) return rc;
+    const SampleRep rep{repetition_penalty, seen, suppress};
+    return sample_launch(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, stream, &rep, seen);
+}
+
+extern "C" int gq_token_set_build(const int *ids, uint32_t n, uint32_t vocab, uint32_t *set, int clear, void *stream) {
+    if (!set || (n && !ids) || !vocab) return gq_fail(GQ_EINVAL, "gq_token_set_build: null pointer argument or vocab == 0.");
+    if (!n && !clear) return GQ_OK;
+    hipLaunchKernelGGL(token_set_build_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, ids, n, vocab, set, clear);
+    GQ_HIP_CHECK(hipGetLastError());
+    return GQ_OK;
 }

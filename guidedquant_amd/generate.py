@@ -98,7 +98,7 @@ class DecodeGraph:
     (the manual-graph path of generate.py:95-113)."""
 
     def __init__(self, model: Transformer, device, native_sampling=False, seed=1234, fold_embed=False, seq_capacity=0, steps_per_replay=1,
-                 **sampling_kwargs):
+                 repetition_penalty=1.0, suppress_tokens=None, **sampling_kwargs):
         """native_sampling: draw the token with the fused HIP sampler (gq_sample_topk_ex: same distribution as `sample`,
         own counter-based RNG, top_k <= 64) and feed token / position back inside the graph; `next_prob` is then
         not produced.  Default False = the reference's torch sampling ops, captured in the graph.
@@ -111,7 +111,13 @@ class DecodeGraph:
         steps_per_replay > 1 (native sampling only): the graph holds that many consecutive token steps -- token, position and RNG
         counter are fed back on the device, so step i + 1 needs nothing from the host; one replay then decodes `steps_per_replay`
         tokens (`next_tok` = the last of them, all of them in `self.seq` when seq_capacity > 0) and the boundary between two graph
-        launches is paid once per replay instead of once per token."""
+        launches is paid once per replay instead of once per token.
+        repetition_penalty != 1 / suppress_tokens (native sampling only; the torch-sampling path raises ValueError): transformers'
+        RepetitionPenaltyLogitsProcessor and SuppressTokensLogitsProcessor inside the sampler (gq_sample_topk_rep).  The graph then owns two
+        token sets, `self.seen` and `self.suppress` (uint32 bitmaps over the vocabulary); every drawn token joins `seen` on the device.
+        `seen` is EMPTY when the constructor returns (the warm-up draws are cleared): like `set_token`, `set_history(ids)` must be called
+        with the whole sequence so far -- the prompt -- before the first step of every request.  With the defaults the step makes
+        exactly the gq_sample_topk_p call it always made and nothing is allocated."""
         prime_graph_rng_state(device)
         self.model = model
         self.native_sampling = bool(native_sampling) and model.native_ready() and (sampling_kwargs.get("top_k") or 0) <= 64 \
@@ -129,6 +135,20 @@ class DecodeGraph:
         self.seq = torch.zeros((int(seq_capacity), ), dtype=torch.int32, device=device) if seq_capacity else None
         self.ban = torch.zeros((6, ), dtype=torch.int32, device=device)
         self.sampling_kwargs = sampling_kwargs
+        self.repetition_penalty = float(repetition_penalty if repetition_penalty is not None else 1.0)
+        suppress_tokens = [int(t) for t in (suppress_tokens if suppress_tokens is not None else ())]
+        self.seen = self.suppress = None
+        if self.repetition_penalty != 1.0 or suppress_tokens:
+            if not self.native_sampling:
+                raise ValueError("repetition_penalty / suppress_tokens are served by the fused sampler only (native_sampling=True on a model "
+                                 "with the fused decode step, top_k <= 64): the torch-sampling graph does not apply them")
+            if not (self.repetition_penalty > 0.0 and self.repetition_penalty != float("inf")):
+                raise ValueError(f"repetition_penalty must be finite and > 0, not {repetition_penalty!r}")
+            words = (model.config.vocab_size + 31) // 32
+            self.seen = torch.zeros((words, ), dtype=torch.int32, device=device)
+            if suppress_tokens:
+                self.suppress = torch.zeros((words, ), dtype=torch.int32, device=device)
+                self._build_set(self.suppress, torch.tensor(suppress_tokens, dtype=torch.int32, device=device))
         # warm up on a side stream (lazy kernel attributes, allocator), then capture
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -149,8 +169,23 @@ class DecodeGraph:
             with capture(self.graph1):
                 self._step()
             torch.cuda.synchronize()
+        if self.seen is not None:  # (the warm-up and capture-time steps drew tokens: their bits go)
+            self.seen.zero_()
         self._bound = self._signature()
         self._gen = getattr(model, "_alloc_gen", 0)
+
+    def _build_set(self, words, ids, clear=True):
+        from . import _lib
+        ids = ids.to(device=words.device, dtype=torch.int32).contiguous().view(-1)
+        _lib.check(_lib.lib().gq_token_set_build(ids.data_ptr() if ids.numel() else None, ids.numel(), self.model.config.vocab_size, words.data_ptr(),
+                                                1 if clear else 0, _lib.current_stream_ptr()), "gq_token_set_build")
+
+    def set_history(self, ids):
+        """the sequence so far (a tensor or list of token ids: the prompt, with whatever was generated before): `seen` is cleared and
+        rebuilt from it, outside the graph.  To be called next to `set_token` before the first step of a request; without a penalty or a
+        suppress list there is no set and nothing happens."""
+        if self.seen is not None:
+            self._build_set(self.seen, ids if torch.is_tensor(ids) else torch.tensor(list(ids), dtype=torch.int32))
 
     def close(self):
         """destroy the captured graphs now (an owner that drops a DecodeGraph calls this instead of leaving the executable graphs to
@@ -213,6 +248,18 @@ class DecodeGraph:
                 logits = m.decode_native(self.tok.view(1), self.pos.view(1))
                 emb = xo = so = None
             kw = self.sampling_kwargs
+            if self.seen is not None:  # (a penalty or a suppress list: the instances over fp32 candidate values and the token sets)
+                _lib.check(_lib.lib().gq_sample_topk_rep(logits.data_ptr(), m.config.vocab_size, int(kw["top_k"]), float(kw.get("top_p") or 1.0),
+                                                        float(kw.get("temperature", 1.0)), int(self.seed), self.rng_counter.data_ptr(),
+                                                        self.work_val.data_ptr(), self.work_idx.data_ptr(), self.tok.data_ptr(),
+                                                        self.pos.data_ptr(), self.next_tok.data_ptr(), self.ban.data_ptr(),
+                                                        self.seq.data_ptr() if self.seq is not None else None,
+                                                        self.seq.numel() if self.seq is not None else 0, emb, xo, m.config.dim, so,
+                                                        self.repetition_penalty, self.seen.data_ptr(),
+                                                        self.suppress.data_ptr() if self.suppress is not None else None,
+                                                        _lib.current_stream_ptr()),
+                           "gq_sample_topk_rep")
+                return
             # (top_p: nucleus filter on the top-k survivors, transformers' warper chain -- 1 = off)
             _lib.check(_lib.lib().gq_sample_topk_p(logits.data_ptr(), m.config.vocab_size, int(kw["top_k"]), float(kw.get("top_p") or 1.0),
                                                   float(kw.get("temperature", 1.0)), int(self.seed), self.rng_counter.data_ptr(),

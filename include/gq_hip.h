@@ -607,6 +607,36 @@ int gq_sample_topk_p(const void *logits, uint32_t vocab, int top_k, float top_p,
                      float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
                      uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, void *stream);
 
+/* Token sets: transformers' RepetitionPenaltyLogitsProcessor and SuppressTokensLogitsProcessor inside the fused sampler.
+ * A token set is uint32_t [ceil(vocab / 32)] in device memory; token t is bit (t & 31) of word (t >> 5).
+ * gq_token_set_build: ONE launch that zeroes the set when clear != 0 and then sets the bits of ids[0 .. n).  Ids outside [0, vocab) are
+ * ignored, duplicates are harmless, n == 0 with clear just clears (n == 0 without it launches nothing). */
+int gq_token_set_build(const int *ids, uint32_t n, uint32_t vocab, uint32_t *set, int clear, void *stream);
+/* gq_sample_topk_p with a repetition penalty over the tokens of `seen` (read, and updated with the drawn token) and the tokens of
+ * `suppress` (read only, may be NULL) taken out.  One draw, in this order, pinned draw for draw by tests/sampler_rep_model.py:
+ *   suppress   a token of `suppress` is no candidate at all -- exactly like a token of the ban list, which stays and combines with it
+ *              (transformers sets such a logit to -inf; here it does not even count towards top_k).  When every token is suppressed or
+ *              banned the candidate set is empty and the draw is that of the other entry points with an empty set: the token written
+ *              (next_tok, tok_io, seq_out) is INT_MAX (0x7FFFFFFF), the counter and the position advance as always, x_out receives
+ *              row 0 of the table, and `seen` is left as it was.
+ *   penalty    v = the fp16 logit widened to fp32, rp = repetition_penalty.  A token of `seen` gets s = v < 0 ? fl32(v * rp) : fl32(v / rp),
+ *              both correctly rounded, the division a true IEEE division (no reciprocal); -0 is not < 0; +-inf and NaN go through the
+ *              same formulas.  Any other token has s = v.  This is the processor applied to the fp32 copy of the logits transformers'
+ *              _sample makes, once per distinct token; `seen` holds the prompt and everything drawn so far.
+ *   order      everything behind it is gq_sample_topk_p with s in place of the fp16 value: top-k over (s descending AS FP32, token id
+ *              ascending), -0 directly below +0 (the order of the fp32 bit patterns), temperature, nucleus, race, counter, ban
+ *              expiry, tok_io / pos_io / next_tok / seq_out and the embedding fold.  s is in general NO fp16 value: the selection
+ *              keys and the candidate buffer carry all of its 32 bits (work_val / work_idx stay 128 * 64 elements).
+ *   state      after the draw the bit of the drawn token is set in `seen` (an atomic OR; the next call reads it behind the kernel
+ *              boundary, inside a captured multi-step graph as well).
+ * repetition_penalty must be finite and > 0 (GQ_EINVAL otherwise); seen == NULL only with repetition_penalty == 1; top_k > 64 and
+ * vocab > GQ_SAMPLER_MAX_VOCAB: GQ_ENOTSUP as above.  With repetition_penalty == 1 and both sets NULL the entry draws the tokens and
+ * leaves the state of gq_sample_topk_p.  The kernels are instances of their own: the three entry points above launch what they did. */
+int gq_sample_topk_rep(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
+                       float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                       uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                       uint32_t *seen, const uint32_t *suppress, void *stream);
+
 /* Test / tuning hooks (not part of the reference's surface).  gq_reset_env_cache: drop the cached GQ_* environment
  * knobs so that a test can flip them between calls.  gq_debug_set_timing_buffer: device buffer the plane kernels write
  * s_memtime phase stamps into (tools/phase_timing.py); NULL (default) disables it. */
