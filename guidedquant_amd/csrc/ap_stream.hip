@@ -1339,6 +1339,10 @@ int stream_launch(const ApLaunch &L, const StreamArgs *rope, const KSplit *ksp =
     if (bits < 2 || bits > gq_env_int("GQ_ST_MAXBITS", 4)) return GQ_ENOTSUP;
     if (L.qbytes() >= 0x7FFFFFFFull) return GQ_ENOTSUP;
     if (L.unaligned16()) return GQ_ENOTSUP;
+    // the residual epilogue fetches a lane's four residual values with ONE 64-bit buffer load bounded by N * 2 bytes: with an odd N the
+    // dword that holds residual[N - 1] straddles that bound and reads as zero (out[N - 1] = y alone) -- no model has such a matrix; the
+    // launch goes on to the plane kernels.  (The K split hands its residual to ap_ksplit_reduce_kernel, which has a scalar tail.)
+    if (L.resid && (N & 1u)) return GQ_ENOTSUP;
     StreamCfg c;
     const u32 Kk = ksp ? ksp->kslice : K;  // activations a block multiplies
     if (ksp) {

@@ -166,6 +166,57 @@ def run_fused(x, q, lut, bits, norm_weight=None, eps=1e-5, residual=None, flags=
     return out.cpu().numpy()
 
 
+def run_fused_guarded(x, q, lut, bits, norm_weight=None, eps=1e-5, residual=None, flags=0, out_elems=None, workspace=False, expect=None,
+                      want_ssq=False):
+    """run_fused with every buffer allocated through tests/guarded.py: x, qweight, lut, norm_weight and residual flush against a poisoned
+    guard, out / the workspace / the hand-over slots pre-filled with the poison (NaN as fp16, 8.4e37 as fp32) between two guards.  The
+    workspace has exactly gq_anyprec_gemv_fused_ws_bytes bytes.  Asserts that no guard byte changed; returns out (and the GQ_SSQ_SLOTS
+    floats with want_ssq: gq_anyprec_gemv_fused_ho)."""
+    import guarded
+    from guidedquant_amd import _lib
+    L = _lib.lib()
+    N, K = q.shape[1], q.shape[2] * 32
+    g = guarded.Guards()
+    f16 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float16)  # noqa: E731
+    xb, qb, lb = g.inp("x", f16(x)), g.inp("qweight", np.ascontiguousarray(q)), g.inp("lut", f16(lut))
+    nw, rs = g.inp("norm_weight", f16(norm_weight)), g.inp("residual", f16(residual))
+    out = g.out("out", 2 * (out_elems or N))
+    ws, nb = None, 0
+    if workspace:
+        nb = int(L.gq_anyprec_gemv_fused_ws_bytes(N, K, bits, flags))
+        assert nb > 0, "no workspace form for this shape"
+        ws = g.out("workspace", nb)
+    so = g.out("ssq_out", 4 * _lib.SSQ_SLOTS) if want_ssq else None
+    p = guarded.ptr
+    rc = L.gq_anyprec_gemv_fused_ho(p(xb), p(out), p(qb), p(lb), N, K, bits, p(nw), eps, p(rs), flags, p(ws), nb, None, p(so),
+                                    _lib.current_stream_ptr())
+    _lib.check(rc, "gq_anyprec_gemv_fused_ho")
+    if expect is not None:
+        assert_route(expect)
+    g.check()
+    o = out.numpy(np.float16)
+    return (o, so.numpy(np.float32)) if want_ssq else o
+
+
+def run_gemv_guarded(X, q, lut, bits, expect=None):
+    """gq_anyprec_gemv (M = X.shape[0] batch rows, 1..8) through the C ABI with guarded buffers; returns out [M][N]"""
+    import guarded
+    from guidedquant_amd import _lib
+    X = np.ascontiguousarray(X, dtype=np.float16)
+    M, K = X.shape
+    N = q.shape[1]
+    assert K == q.shape[2] * 32
+    g = guarded.Guards()
+    xb, qb, lb = g.inp("x", X), g.inp("qweight", np.ascontiguousarray(q)), g.inp("lut", np.ascontiguousarray(lut, dtype=np.float16))
+    out = g.out("out", 2 * M * N)
+    rc = _lib.lib().gq_anyprec_gemv(xb.ptr(), out.ptr(), qb.ptr(), lb.ptr(), M, N, K, bits, 0, _lib.current_stream_ptr())
+    _lib.check(rc, "gq_anyprec_gemv")
+    if expect is not None:
+        assert_route(expect)
+    g.check()
+    return out.numpy(np.float16, (M, N))
+
+
 def tiny_hf_anyprec_checkpoint(path, D=128, I=256, H=4, KV=2, Lr=2, V=96, seed=2):
     """write an HF-layout Any-Precision checkpoint directory (config.json with the `anyprec` section incl. arch_config,
     pack.py:190-195; model.safetensors with `...{qweight,lut2,lut3}` keys, pack.py:112-123) of a tiny Llama; returns
