@@ -412,6 +412,9 @@ class AnyPrecisionForCausalLM(nn.Module):
         fused sampler of routes 1 and 2, as transformers applies RepetitionPenaltyLogitsProcessor and SuppressTokensLogitsProcessor to the
         fp32 scores: a token of the sequence so far (prompt included) has its logit divided by the penalty when positive and multiplied
         when negative, once per distinct token; a suppressed token is never drawn (and, stricter than -inf, takes no top_k place).
+        Prompt length on route 1: prompt + max_new_tokens up to the decoder's `block_size` (the checkpoint's max_position_embeddings) --
+        a prompt of more than GQ_PREFILL_CHUNK (4096) tokens goes through the chunked HIP prompt pass (`Transformer.prefill_native`),
+        its intermediates sized by the chunk and its attention by gq_attn_prefill; the caches keep no quadratic mask table.
         Returns the [1, prompt + new] token tensor like HF does; stops at EOS (checked every 32 tokens, the tail is cut); honours
         min_new_tokens, streamer, precision=."""
         prev_precision = self.precision
@@ -507,8 +510,7 @@ class AnyPrecisionForCausalLM(nn.Module):
             raise ValueError(f"prompt + max_new_tokens = {total} exceeds the model's context ({dec.config.block_size})")
         # caches (and with them the captured graphs, keyed by the cache length) grow in powers of two from 256 positions: a serving loop
         # with varying lengths re-captures at most log2 times, not per request (the attention launch reads rows up to the position
-        # only; a longer cache costs memory, not time).  Beyond 16384 positions the request's own length (the fallback route's
-        # causal mask is quadratic in it).
+        # only; a longer cache costs memory, not time).  Beyond 16384 positions the request's own length.
         cap = total if total > 16384 else max(256, 1 << (total - 1).bit_length())
         dec.setup_caches(1, min(cap, dec.config.block_size))
         key = (self.precision, dec.max_seq_length, req["temperature"], req["top_k"], req["top_p"], req["repetition_penalty"], req["suppress_tokens"])

@@ -27,10 +27,11 @@ EXPORTS = [
     "gq_qtip_decompress", "gq_qtip_gemm", "gq_qtip_gemm_ws", "gq_qtip_gemm_ws_bytes", "gq_debug_ap_last_route", "gq_debug_ap_plan_route",
     "gq_attn_decode_split_qknorm", "gq_qknorm_rope_cache_rows", "gq_attn_decode_split_bias",
     "gq_attn_decode_split_window", "gq_attn_decode_split_qknorm_window", "gq_attn_decode_split_bias_window", "gq_attn_decode_roped_window",
-    "gq_token_set_build", "gq_sample_topk_rep",
+    "gq_token_set_build", "gq_sample_topk_rep", "gq_attn_prefill_supported", "gq_attn_prefill",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
+PREFILL_ATTN_BQ, PREFILL_ATTN_BK = 64, 64  # include/gq_hip.h GQ_PREFILL_ATTN_BQ / _BK: query rows and key rows per tile of gq_attn_prefill
 SAMPLER_MAX_VOCAB = 262144  # gq_sample_topk / _ex / _p: 128 blocks x 2048 logits (csrc/decode.hip; up to 131072: x 1024)
 # include/gq_hip.h GQ_AP_ROUTE_*: the kernel family an AP-GEMV dispatch launched (gq_debug_ap_last_route, gq_debug_ap_plan_route)
 AP_ROUTES = ("none", "generic", "exact", "pair-table", "plane", "plane-local", "plane-chain", "stream", "stream-ksplit", "dq",
@@ -141,6 +142,8 @@ def lib():
         L.gq_rope_cache_rows.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp]
         L.gq_qknorm_rope_cache_rows.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, f32, vp]
         L.gq_silu_mul_rows.argtypes = [vp, vp, u32, u32, i32, vp]
+        L.gq_attn_prefill_supported.argtypes = [u32, u32, u32]
+        L.gq_attn_prefill.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, f32, u32, vp]
         L.gq_anyprec_pack.argtypes = [vp, vp, u32, u32, i32, vp]
         L.gq_lnq_cd_block.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, vp]
         L.gq_debug_set_timing_buffer.argtypes = [vp]

@@ -1,0 +1,212 @@
+// prefill_attn.hip -- the attention of the PROMPT pass: a flash-attention forward for gfx950 over one batch slot of the KV cache,
+// causal, with an offset (a later chunk of a prompt attends the cached chunks in front of it), a sliding window, grouped heads.
+//   q    fp16 [n_head][S][head_dim]            (what gq_rope_cache_rows / gq_qknorm_rope_cache_rows write)
+//   k, v fp16 [n_kv_head][max_seq][head_dim]   (one batch slot of KVCache; rows [0, start + S) written)
+//   out  fp16 [S][n_head * head_dim]           (the rows wo reads)
+// Query row i sits at position p = start + i and attends the cache rows t <= p, with a window also t > p - window
+// (model.py window_mask).
+//
+// One block of 4 waves per (tile of BQ = 64 query rows, head); wave w owns 16 query rows.  Key tiles of BK = 64 rows go through LDS,
+// row-major for K and for V, the next tile's global loads in flight (in registers) while the current one is computed.  Both
+// products run on v_mfma_f32_16x16x32_f16 and are TRANSPOSED, so that the query is the accumulator's column (its lane, l & 15) in
+// both and the softmax statistics never leave their lane group:
+//   S^T = K Q^T    A = K rows (ds_read_b128), B = Q^T from registers.  The 16 MFMA rows of score block b are the tile's keys
+//                  32 (b >> 1) + 8 (row >> 2) + 4 (b & 1) + (row & 3): lane group g = l >> 4 then holds, in blocks 2c and 2c + 1, the
+//                  EIGHT CONSECUTIVE keys 32 c + 8 g .. + 7 of its query -- exactly the B fragment of k-step c of the second product.
+//   O^T = V^T P^T  A = V^T through ds_read_b64_tr_b16 on the row-major image (two reads of 4 keys x 16 columns per fragment),
+//                  B = P^T = exp2 of the scores, rounded to fp16, straight from the accumulators.
+// The online softmax is fp32 with scale * log2(e) folded into one multiply and v_exp_f32; a masked score is REPLACED (select), a
+// masked P is exactly 0, and a row that has seen only masked keys so far keeps sum 0 (its running maximum stays at NEG, finite).
+// Tiles wholly above the diagonal or below the window are never visited by the block, a wave skips the visited ones it has no
+// key in, and only tiles astride an edge evaluate the element mask.  Rows >= start + S of a tile are not read: they are staged as
+// zeros (0 x NaN inside an MFMA is NaN), so nothing at or behind row max_seq is touched.  The tile loops hold no integer division.
+#include <hip/hip_runtime.h>
+
+#include "gq_internal.h"
+
+namespace {
+using u32 = uint32_t;
+typedef _Float16 h16;
+typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr u32 BQ = GQ_PREFILL_ATTN_BQ, BK = GQ_PREFILL_ATTN_BK;
+static_assert(BQ == 64 && BK == 64, "4 waves x 16 query rows; 4 score blocks of 16 keys");
+constexpr float NEG = -1.0e30f;  // a masked score: finite, so NEG - NEG = 0 and never Inf - Inf
+
+__device__ __forceinline__ h16x4 lds_read_tr(const h16 *p) {
+    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+    return __builtin_bit_cast(h16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)p));
+}
+
+template <int HD>
+__global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__restrict__ q, const uint16_t *__restrict__ kc, const uint16_t *__restrict__ vc,
+                                                           uint16_t *__restrict__ out, u32 S, u32 start, u32 H, u32 group, u32 max_seq, float c,
+                                                           u32 window) {
+    constexpr u32 LD = HD + 8;             // halves per LDS row: 16 bytes of padding
+    constexpr u32 CH = HD / 8;             // 16-byte chunks per row
+    constexpr u32 NCH = BK * CH / 256;     // chunks per thread and matrix
+    constexpr u32 KS = HD / 32, DB = HD / 16;
+    __shared__ __attribute__((aligned(16))) h16 sK[BK * LD];
+    __shared__ __attribute__((aligned(16))) h16 sV[BK * LD];
+
+    const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u, g = l >> 4, li = l & 15u;
+    const u32 head = blockIdx.y, kvh = head / group;  // (once per block)
+    const u32 q0 = (gridDim.x - 1u - blockIdx.x) * BQ;  // the long rows of the triangle first
+    const u32 T = start + S;
+    const uint16_t *kbase = kc + (size_t)kvh * max_seq * HD, *vbase = vc + (size_t)kvh * max_seq * HD;
+
+    // the block's key range: [klo, khi] covers every key one of its rows attends
+    const u32 p_lo = start + q0, khi = start + min(q0 + BQ - 1u, S - 1u);
+    const u32 klo = (window && p_lo + 1u > window) ? p_lo + 1u - window : 0u;
+    const u32 kt0 = klo / BK, kt1 = khi / BK;
+
+    // the wave's rows (rows >= S repeat row S - 1 and are not stored)
+    const u32 wq0 = q0 + 16u * w;
+    const bool wave_active = wq0 < S;
+    const u32 qrow = wq0 + li, qi = min(qrow, S - 1u), p = start + qi;
+    const u32 pmin = start + min(wq0, S - 1u), pmax = start + min(wq0 + 15u, S - 1u);
+
+    h16x8 qf[KS];
+    {
+        const uint16_t *qr = q + ((size_t)head * S + qi) * HD + 8u * g;
+#pragma unroll
+        for (u32 ks = 0; ks < KS; ks++) qf[ks] = __builtin_bit_cast(h16x8, *reinterpret_cast<const uint4 *>(qr + 32u * ks));
+    }
+
+    uint4 kreg[NCH], vreg[NCH];
+    auto load_tile = [&](u32 kt) {
+#pragma unroll
+        for (u32 i = 0; i < NCH; i++) {
+            const u32 id = tid + 256u * i, row = id / CH, col = id % CH, t = kt * BK + row;  // (CH: a power of two)
+            if (t < T) {
+                kreg[i] = *reinterpret_cast<const uint4 *>(kbase + (size_t)t * HD + 8u * col);
+                vreg[i] = *reinterpret_cast<const uint4 *>(vbase + (size_t)t * HD + 8u * col);
+            } else {
+                kreg[i] = make_uint4(0u, 0u, 0u, 0u);
+                vreg[i] = make_uint4(0u, 0u, 0u, 0u);
+            }
+        }
+    };
+
+    f32x4 o[DB];
+#pragma unroll
+    for (u32 d = 0; d < DB; d++) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m_run = NEG, l_run = 0.f;  // l_run: this lane's share of the row sum (the four lane groups of a query are added at the end)
+
+    load_tile(kt0);
+    for (u32 kt = kt0; kt <= kt1; kt++) {
+        __syncthreads();  // every wave is through with the tile in LDS
+#pragma unroll
+        for (u32 i = 0; i < NCH; i++) {
+            const u32 id = tid + 256u * i, row = id / CH, col = id % CH;
+            *reinterpret_cast<uint4 *>(&sK[row * LD + 8u * col]) = kreg[i];
+            *reinterpret_cast<uint4 *>(&sV[row * LD + 8u * col]) = vreg[i];
+        }
+        __syncthreads();
+        if (kt < kt1) load_tile(kt + 1u);  // in flight under the products below
+
+        const u32 tb = kt * BK;
+        // (wave-uniform: EXEC stays full for the transposed reads)
+        if (!(wave_active && tb <= pmax && (window == 0u || tb + (BK - 1u) + window > pmin))) continue;
+        const bool edge = tb + (BK - 1u) > pmin || (window != 0u && tb + window <= pmax);
+
+        f32x4 s[4];
+#pragma unroll
+        for (u32 b = 0; b < 4; b++) {
+            s[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+            const u32 krow = 32u * (b >> 1) + 8u * (li >> 2) + 4u * (b & 1u) + (li & 3u);
+#pragma unroll
+            for (u32 ks = 0; ks < KS; ks++) {
+                const h16x8 a = *reinterpret_cast<const h16x8 *>(&sK[krow * LD + 32u * ks + 8u * g]);
+                s[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, qf[ks], s[b], 0, 0, 0);
+            }
+        }
+        // scores in the exp2 domain; the masked ones replaced
+        bool ok[4][4];
+        float mloc = NEG;
+#pragma unroll
+        for (u32 b = 0; b < 4; b++) {
+#pragma unroll
+            for (u32 r = 0; r < 4; r++) {
+                const u32 t = tb + 32u * (b >> 1) + 8u * g + 4u * (b & 1u) + r;
+                ok[b][r] = !edge || (t <= p && (window == 0u || t + window > p));
+                const float x = s[b][r] * c;
+                s[b][r] = ok[b][r] ? x : NEG;
+                mloc = fmaxf(mloc, s[b][r]);
+            }
+        }
+        mloc = fmaxf(mloc, __shfl_xor(mloc, 16, 64));
+        mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+        const float m_new = fmaxf(m_run, mloc);
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        m_run = m_new;
+        float psum = 0.f;
+        h16x8 pf[2];
+#pragma unroll
+        for (u32 b = 0; b < 4; b++) {
+#pragma unroll
+            for (u32 r = 0; r < 4; r++) {
+                const float pe = ok[b][r] ? __builtin_amdgcn_exp2f(s[b][r] - m_new) : 0.f;
+                psum += pe;
+                pf[b >> 1][4u * (b & 1u) + r] = (h16)pe;
+            }
+        }
+        l_run = l_run * alpha + psum;
+#pragma unroll
+        for (u32 d = 0; d < DB; d++) {
+            o[d] *= alpha;
+#pragma unroll
+            for (u32 cc = 0; cc < 2; cc++) {
+                // lane 4 q + p of a group of 16 addresses row q, columns 4 p .. 4 p + 3 of a block of 4 keys x 16 columns
+                const h16 *vp = &sV[(32u * cc + 8u * g + (li >> 2)) * LD + 16u * d + 4u * (li & 3u)];
+                const h16x4 lo = lds_read_tr(vp), hi = lds_read_tr(vp + 4u * LD);
+                const h16x8 a = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                o[d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, pf[cc], o[d], 0, 0, 0);
+            }
+        }
+    }
+
+    l_run += __shfl_xor(l_run, 16, 64);
+    l_run += __shfl_xor(l_run, 32, 64);
+    if (qrow < S) {
+        const float inv = 1.0f / l_run;
+        uint16_t *orow = out + (size_t)qrow * H * HD + (size_t)head * HD + 4u * g;
+#pragma unroll
+        for (u32 d = 0; d < DB; d++) {
+            const h16x4 v = {(h16)(o[d][0] * inv), (h16)(o[d][1] * inv), (h16)(o[d][2] * inv), (h16)(o[d][3] * inv)};
+            *reinterpret_cast<uint2 *>(orow + 16u * d) = __builtin_bit_cast(uint2, v);
+        }
+    }
+}
+}  // namespace
+
+extern "C" int gq_attn_prefill_supported(uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim) {
+    return (head_dim == 64u || head_dim == 128u) && n_head != 0u && n_kv_head != 0u && n_head % n_kv_head == 0u && n_head <= 65535u;
+}
+
+extern "C" int gq_attn_prefill(const void *q, const void *k_cache, const void *v_cache, void *out, uint32_t S, uint32_t start, uint32_t n_head,
+                               uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t window, void *stream) {
+    if (!gq_attn_prefill_supported(n_head, n_kv_head, head_dim))
+        return gq_fail(GQ_ENOTSUP, "gq_attn_prefill: head_dim 64 or 128, n_head a multiple of n_kv_head.");
+    if (!q || !k_cache || !v_cache || !out) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    if (((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)out) & 15u) return gq_fail(GQ_EINVAL, "gq_attn_prefill: 16-byte aligned pointers.");
+    const uint64_t T = (uint64_t)start + S;
+    if (T > max_seq) return gq_fail(GQ_EINVAL, "gq_attn_prefill: start + S exceeds max_seq.");
+    if (max_seq > 0x40000000u) return gq_fail(GQ_ENOTSUP, "gq_attn_prefill: max_seq beyond 2^30.");
+    if (S == 0) return GQ_OK;
+    if (window >= T) window = 0u;  // a window no row outgrows
+    const float c = scale * 1.4426950408889634f;
+    const dim3 grid((S + BQ - 1u) / BQ, n_head), block(256);
+    const uint32_t group = n_head / n_kv_head;
+    if (head_dim == 64u)
+        hipLaunchKernelGGL(prefill_attn_kernel<64>, grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const uint16_t *)k_cache, (const uint16_t *)v_cache,
+                           (uint16_t *)out, S, start, n_head, group, max_seq, c, window);
+    else
+        hipLaunchKernelGGL(prefill_attn_kernel<128>, grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const uint16_t *)k_cache, (const uint16_t *)v_cache,
+                           (uint16_t *)out, S, start, n_head, group, max_seq, c, window);
+    GQ_HIP_CHECK(hipGetLastError());
+    return GQ_OK;
+}

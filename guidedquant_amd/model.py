@@ -171,6 +171,24 @@ def window_mask(n: int, window: Optional[int], device=None) -> Tensor:
     return m if window is None else m & (kv > q - int(window))
 
 
+MASK_TABLE_MAX = 16384  # rows of a cache up to which setup_caches keeps [n, n] mask tables (1 GiB per table at 32768 rows: none above)
+
+
+def mask_rows(input_pos: Tensor, n: int, window: Optional[int] = None) -> Tensor:
+    """bool [len(input_pos), n]: the rows `window_mask(m, window)[input_pos, :n]` of any table of m >= n rows, built from the positions on
+    the spot -- key t is attended by the query at position p when t <= p, and with a window also t > p - window"""
+    p = input_pos.long()[:, None]
+    t = torch.arange(n, device=input_pos.device)[None, :]
+    m = t <= p
+    return m if window is None else m & (t > p - int(window))
+
+
+def prefill_chunks(S: int, chunk: int, start: int = 0):
+    """the (start, S) pieces a prompt of S tokens at position `start` is passed in: whole chunks in order, then the tail (one token included)"""
+    assert S >= 1 and chunk >= 1
+    return [(start + a, min(chunk, S - a)) for a in range(0, S, chunk)]
+
+
 _SDPA_GQA = [True]  # F.scaled_dot_product_attention(enable_gqa=True): grouped K / V heads without the repeat_interleave copies
 
 
@@ -404,10 +422,16 @@ class Transformer(nn.Module):
         device = self.output.weight.device
         for b in self.layers:
             b.attention.kv_cache = KVCache(max_batch_size, max_seq_length, self.config.n_local_heads, head_dim, dtype, device)
-        self.causal_mask = torch.tril(torch.ones(self.max_seq_length, self.max_seq_length, dtype=torch.bool, device=device))
-        # one mask per distinct window that is shorter than the cache (a window the cache never outgrows is the causal mask)
+        # the [n, n] tables only for a cache of at most MASK_TABLE_MAX rows (tests and pipeline.py index them); above it every consumer
+        # builds the rows it needs from the positions (mask_rows: the same bits)
         lw = self.config.layer_windows or ()
-        self.window_masks = {w: window_mask(self.max_seq_length, w, device) for w in sorted({w for w in lw if w is not None and w < self.max_seq_length})}
+        self._window_set = sorted({w for w in lw if w is not None and w < self.max_seq_length})
+        if self.max_seq_length <= MASK_TABLE_MAX:
+            self.causal_mask = torch.tril(torch.ones(self.max_seq_length, self.max_seq_length, dtype=torch.bool, device=device))
+            # one mask per distinct window that is shorter than the cache (a window the cache never outgrows is the causal mask)
+            self.window_masks = {w: window_mask(self.max_seq_length, w, device) for w in self._window_set}
+        else:
+            self.causal_mask, self.window_masks = None, None
         self.rope_cos, self.rope_sin = rope_tables(head_dim, max_seq_length, self.config.rope_base, device, dtype,
                                                    rope_scaling=self.config.rope_scaling)
         self.cache_initialized = True
@@ -415,8 +439,12 @@ class Transformer(nn.Module):
 
     def forward(self, idx: Tensor, input_pos: Optional[Tensor] = None) -> Tensor:
         assert self.cache_initialized, "Caches must be initialized first"
-        mask = self.causal_mask[None, None, input_pos]
-        wmask = {w: wm[None, None, input_pos] for w, wm in self.window_masks.items()}  # (empty for a model without windows)
+        if self.causal_mask is not None:
+            mask = self.causal_mask[None, None, input_pos]
+            wmask = {w: wm[None, None, input_pos] for w, wm in self.window_masks.items()}  # (empty for a model without windows)
+        else:  # (a cache beyond MASK_TABLE_MAX rows keeps no tables)
+            mask = mask_rows(input_pos, self.max_seq_length)[None, None]
+            wmask = {w: mask_rows(input_pos, self.max_seq_length, w)[None, None] for w in self._window_set}
         lw = self.config.layer_windows or (None,) * len(self.layers)
         x = self.tok_embeddings(idx)
         for layer, w in zip(self.layers, lw):
@@ -503,7 +531,7 @@ class Transformer(nn.Module):
                 and self.config.head_dim % 16 == 0 and self.config.dim % 8 == 0 and self.config.dim <= 16384
                 and self.config.intermediate_size % 8 == 0)
 
-    def prefill_native(self, idx: Tensor, input_pos: Tensor, start: int = 0, last_only: bool = True) -> Tensor:
+    def prefill_native(self, idx: Tensor, input_pos: Tensor, start: int = 0, last_only: bool = True, chunk: Optional[int] = None) -> Tensor:
         """The prompt pass (`Transformer.forward` with seq_len > 1, inference/model.py:206-266 semantics) with the element-wise
         steps between the linears as ONE HIP launch each (csrc/prefill.hip: RMSNorm rows, RoPE + KV-cache write, silu * up)
         instead of ~45 eager tensor ops per layer, the linears through `APLinear.forward` (fused prefill GEMM / split K /
@@ -511,26 +539,73 @@ class Transformer(nn.Module):
         over the keys [0, start + S) only instead of the whole cache.
         `input_pos` must be arange(start, start + S) (what generate() passes; `start` is the host copy of its first element).
         Same fp16 rounding points as the module forward: logits agree up to the summation order of the fp32 sums.
-        last_only: logits of the last prompt token only, [1, 1, V] -- all generate() samples from -- else [1, S, V]."""
+        last_only: logits of the last prompt token only, [1, 1, V] -- all generate() samples from -- else [1, S, V].
+        chunk (None: GQ_PREFILL_CHUNK, default 4096): a prompt of more than `chunk` tokens goes through in pieces of `chunk` tokens
+        (`prefill_chunks`: chunks outer, layers inner, over the same caches; a tail of one token included), so the intermediates are
+        sized by the chunk, not by the prompt; with last_only only the last piece runs the head.
+        Attention follows GQ_PREFILL_ATTN: "auto" (default) -- the HIP kernel gq_attn_prefill (csrc/prefill_attn.hip) inside a chunked
+        pass where gq_attn_prefill_supported, torch SDPA everywhere else (a prompt of at most `chunk` tokens launches what it always
+        did); "1" -- the kernel wherever it is supported; "0" -- never.  `last_prefill_plan` records what the pass did:
+        dict(chunks=[(start, S), ..], attn=["hip" | "sdpa" per layer])."""
+        import os
+        from . import _lib
+        L = _lib.lib()
+        cfg = self.config
+        S, H, Hkv, hd = idx.numel(), cfg.n_head, cfg.n_local_heads, cfg.head_dim
+        assert self.prefill_ready(idx) and input_pos.numel() == S and input_pos.dtype == torch.int32 and start + S <= self.max_seq_length
+        if chunk is None:
+            chunk = int(os.environ.get("GQ_PREFILL_CHUNK", "4096"))
+        assert chunk >= 1, chunk
+        pieces = prefill_chunks(S, chunk, start)
+        mode = os.environ.get("GQ_PREFILL_ATTN", "auto")
+        if mode not in ("auto", "0", "1"):
+            raise ValueError(f"GQ_PREFILL_ATTN={mode!r}: auto, 0 or 1")
+        hip = mode != "0" and (mode == "1" or len(pieces) > 1) and bool(L.gq_attn_prefill_supported(H, Hkv, hd))
+        self.last_prefill_plan = dict(chunks=pieces, attn=["hip" if hip else "sdpa"] * len(self.layers))
+        dev = idx.device
+        Sc = min(chunk, S)
+        bufs = dict(xn=torch.empty((Sc, cfg.dim), dtype=torch.float16, device=dev), q=torch.empty((H * Sc * hd, ), dtype=torch.float16, device=dev),
+                    hbuf=torch.empty((Sc, cfg.intermediate_size), dtype=torch.float16, device=dev),
+                    y=torch.empty((Sc, H * hd), dtype=torch.float16, device=dev) if hip else None)
+        flat, out = idx.reshape(-1), []
+        for a, n in pieces:
+            o = a - start
+            head = (not last_only) or a + n == start + S
+            r = self._prefill_piece(flat[o:o + n], input_pos[o:o + n], a, bufs, hip, head, last_only)
+            if head:
+                out.append(r)
+        return out[0] if len(out) == 1 else torch.cat(out, dim=1)
+
+    def _prefill_piece(self, idx: Tensor, input_pos: Tensor, start: int, bufs: dict, hip: bool, head: bool, last_only: bool):
+        """one piece of the prompt pass: S tokens at positions start .. start + S - 1 through every layer, attending the cache rows
+        [0, start + S); the logits ([1, 1 | S, V]) when `head`, else None"""
         from . import _lib
         L = _lib.lib()
         cfg = self.config
         S, D, H, Hkv, hd, inter = idx.numel(), cfg.dim, cfg.n_head, cfg.n_local_heads, cfg.head_dim, cfg.intermediate_size
         T = start + S
-        assert self.prefill_ready(idx) and input_pos.numel() == S and input_pos.dtype == torch.int32 and T <= self.max_seq_length
-        dev = idx.device
         x = self.tok_embeddings(idx.view(1, S)).view(S, D).contiguous()
-        xn = torch.empty_like(x)
-        q = torch.empty((H, S, hd), dtype=torch.float16, device=dev)
-        hbuf = torch.empty((S, inter), dtype=torch.float16, device=dev)
-        mask = None if start == 0 else self.causal_mask[None, None, input_pos.long(), :T]
-        # a sliding-window layer whose window the T keys outgrow: the explicit mask, at start == 0 too (is_causal would attend them all)
-        wmask = {w: wm[None, None, input_pos.long(), :T] for w, wm in self.window_masks.items() if T > w}
+        xn, hbuf = bufs["xn"][:S], bufs["hbuf"][:S]
+        q = bufs["q"][:H * S * hd].view(H, S, hd)
+        y_hip = bufs["y"][:S] if hip else None
         lw = cfg.layer_windows or (None,) * len(self.layers)
+        masks = {}
+
+        def sdpa_mask(win):
+            # the [S, T] rows SDPA needs, from the positions: none at start == 0 without a window (is_causal); a sliding-window layer whose
+            # window the T keys outgrow takes the explicit mask at start == 0 too (is_causal would attend them all)
+            if win is not None and T <= win:
+                win = None
+            if win is None and start == 0:
+                return None
+            if win not in masks:
+                masks[win] = mask_rows(input_pos, T, win)[None, None]
+            return masks[win]
         rep = H // Hkv
+        scale = 1.0 / math.sqrt(hd)
         qt = self._native_kind() == "qtip"  # QTIP: the linears through QuantizedLinear.forward (bs > 8: gq_qtip_gemm)
         pending = None  # the previous block's MLP output: its residual add rides in the next RMSNorm launch
-        with torch.cuda.device(dev):
+        with torch.cuda.device(x.device):
             st = _lib.current_stream_ptr()  # (the model's device's current stream: inside the guard)
             for b, win in zip(self.layers, lw):
                 att, ff = b.attention, b.feed_forward
@@ -550,8 +625,13 @@ class Transformer(nn.Module):
                 else:
                     _lib.check(L.gq_rope_cache_rows(qkv.data_ptr(), input_pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), q.data_ptr(),
                                                     kc.data_ptr(), vc.data_ptr(), S, H, Hkv, hd, kc.shape[2], st), "gq_rope_cache_rows")
-                y = _sdpa_gqa(q.unsqueeze(0), kc[:1, :, :T], vc[:1, :, :T], wmask.get(win, mask), rep)
-                y = y.transpose(1, 2).reshape(1, S, H * hd)
+                if hip:  # (batch slot 0 of the caches; the output already in the row layout wo reads)
+                    _lib.check(L.gq_attn_prefill(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), y_hip.data_ptr(), S, start, H, Hkv, hd, kc.shape[2], scale,
+                                                 0 if win is None else int(win), st), "gq_attn_prefill")
+                    y = y_hip.view(1, S, H * hd)
+                else:
+                    y = _sdpa_gqa(q.unsqueeze(0), kc[:1, :, :T], vc[:1, :, :T], sdpa_mask(win), rep)
+                    y = y.transpose(1, 2).reshape(1, S, H * hd)
                 o = att.wo(y).view(S, D)
                 _lib.check(L.gq_rmsnorm_rows(x.data_ptr(), o.data_ptr(), b.post_attention_layernorm.weight.data_ptr(), xn.data_ptr(), S, D,
                                              b.post_attention_layernorm.eps, st), "gq_rmsnorm_rows")
@@ -564,6 +644,8 @@ class Transformer(nn.Module):
                     paired = 1 if getattr(ff.w1w3, "gq_row_pairs", False) else 0
                 _lib.check(L.gq_silu_mul_rows(gu.data_ptr(), hbuf.data_ptr(), S, inter, paired, st), "gq_silu_mul_rows")
                 pending = ff.w2(hbuf.view(1, S, inter)).view(S, D)
+        if not head:
+            return None
         x = x + pending
         x = x[-1:] if last_only else x
         return self.output(self.norm(x)).view(1, -1, cfg.vocab_size)

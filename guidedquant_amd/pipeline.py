@@ -38,6 +38,7 @@ import torch
 import torch.distributed as dist
 
 from ._graphs import capture
+from .model import mask_rows
 
 
 def stage_ranges(n_layer: int, world: int, head_cost_layers: float = 0.0) -> List[range]:
@@ -286,7 +287,8 @@ class PipelinedDecoder:
             self.h[slot].copy_(m.tok_embeddings(self.tok[slot:slot + 1].long()).view(-1))
         x = self.h[slot].view(1, 1, -1)
         ip = torch.tensor([self.pos[slot]], dtype=torch.long, device=self.dev)
-        mask = m.causal_mask[None, None, ip]
+        # (a cache beyond model.MASK_TABLE_MAX rows keeps no mask table: the row from the position)
+        mask = m.causal_mask[None, None, ip] if m.causal_mask is not None else mask_rows(ip, m.max_seq_length)[None, None]
         for li in self.layers:
             blk = m.layers[li]
             kv = blk.attention.kv_cache

@@ -175,6 +175,25 @@ int gq_qknorm_rope_cache_rows(const void *qkv, const int *pos, const void *cos_t
 int gq_silu_mul_rows(const void *y, void *out, uint32_t S, uint32_t inter, int paired, void *stream);
 
 /*
+ * The attention of the prompt pass (csrc/prefill_attn.hip): a flash-attention forward over one batch slot of the KV cache.
+ *   q        fp16 [n_head][S][head_dim]           what gq_rope_cache_rows / gq_qknorm_rope_cache_rows write
+ *   k_cache, v_cache  fp16 [n_kv_head][max_seq][head_dim], rows [0, start + S) written before the launch
+ *   out      fp16 [S][n_head * head_dim]          the rows wo reads
+ * Query row i has position p = start + i and attends the cache rows t <= p, with window != 0 also t > p - window (window 0: the
+ * whole context).  start + S <= max_seq (GQ_EINVAL else); rows >= start + S of the caches may hold anything and are not read.
+ * softmax(scale * q k^T) in fp32, P rounded to fp16 in front of P V:  |out - exact| <= 2^-9 max|V| at a few hundred keys.
+ * gq_attn_prefill_supported (host logic, launches nothing): 1 for head_dim 64 / 128 and n_head a multiple of n_kv_head (any group
+ * size), else 0 -- gq_attn_prefill then returns GQ_ENOTSUP and writes nothing.  All pointers 16-byte aligned.
+ * Key tiles of GQ_PREFILL_ATTN_BK rows per block of GQ_PREFILL_ATTN_BQ query rows and one head; tiles wholly above the diagonal or
+ * below the window are skipped, so a window layer costs S x window.
+ */
+#define GQ_PREFILL_ATTN_BQ 64
+#define GQ_PREFILL_ATTN_BK 64
+int gq_attn_prefill_supported(uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim);
+int gq_attn_prefill(const void *q, const void *k_cache, const void *v_cache, void *out, uint32_t S, uint32_t start, uint32_t n_head,
+                    uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t window, void *stream);
+
+/*
  * Host (CPU) twins of the two Any-Precision entry points: same arguments with HOST pointers, no stream; `nthreads` <= 0
  * uses the OpenMP default.  They serve BASELINE.json configs[0] ("CPU reference APLinear path via generate.py"): the module
  * semantics of inference/APLinear.py:35-60 with the tensors in host memory (the reference hard-codes 'cuda',
