@@ -422,10 +422,18 @@ class AnyPrecisionForCausalLM(nn.Module):
             self.set_precision(kwargs.pop('precision'))
         native = kwargs.pop('native', None)
         capture = kwargs.pop('capture', None)
+        # kv_cache_dtype="fp8": the KV cache of the fused decode model as e4m3 codes (Transformer.setup_caches).  Served by route 1 only;
+        # a request it cannot serve raises -- it never falls back to an fp16 cache silently.  (popped: it never reaches transformers)
+        from .model import kv_cache_dtype_name
+        kv = kv_cache_dtype_name(kwargs.pop('kv_cache_dtype', None))
         try:
+            if kv == "fp8" and (native is False or capture is True):
+                raise ValueError("kv_cache_dtype='fp8': served by the fused decode model only (not with native=False or capture=True)")
             req, why = self._route_request(args, kwargs, sampler_processors=True) if (native is not False or capture is True) else (None, "opted out")
             if req is not None and self.device.type != "cuda":
                 req, why = None, "the fused routes need the GPU"
+            if kv == "fp8" and req is None:
+                raise ValueError("kv_cache_dtype='fp8': " + why)
             if native is True and req is None:
                 raise ValueError("native=True: " + why)
             if req is not None and native is not False:
@@ -446,8 +454,13 @@ class AnyPrecisionForCausalLM(nn.Module):
                     if native is True:
                         raise ValueError(f"native=True: vocabulary {dec.config.vocab_size} exceeds the fused sampler's {SAMPLER_MAX_VOCAB}")
                     dec = None
+                if dec is not None and kv == "fp8" and dec.kv8_unserved():
+                    raise ValueError("kv_cache_dtype='fp8': " + dec.kv8_unserved())
                 if dec is not None:
-                    return self._generate_native(dec, req)
+                    return self._generate_native(dec, req, kv_cache_dtype=kv)
+                if kv == "fp8":
+                    why_not = getattr(self, "_no_native_reason", None)
+                    raise ValueError("kv_cache_dtype='fp8': no fused decode model serves this request%s" % (": " + why_not if why_not else " (context or vocabulary beyond it)"))
                 if native is True:
                     why_not = getattr(self, "_no_native_reason", None)
                     raise ValueError("native=True: this checkpoint has no fused decode form at %d bits%s" % (self.precision, ": " + why_not if why_not else ""))
@@ -476,7 +489,7 @@ class AnyPrecisionForCausalLM(nn.Module):
             self._no_native_reason = str(e)
             return None
         self._no_native_reason = None
-        dec.setup_caches(1, 8) if not dec.cache_initialized else None
+        dec.setup_caches(1, 8, kv_cache_dtype=dec.kv_cache_dtype) if not dec.cache_initialized else None
         return dec if dec.native_ready() else None
 
     def _evict(self, kind):
@@ -502,7 +515,7 @@ class AnyPrecisionForCausalLM(nn.Module):
             req["streamer"].put(seq_host[lo:(cut or hi)])
         return cut
 
-    def _generate_native(self, dec, req, chunk=32):
+    def _generate_native(self, dec, req, chunk=32, kv_cache_dtype="fp16"):
         from . import generate as gen
         ids, T, max_new = req["ids"].to(self.device), req["T"], req["max_new"]
         total = T + max_new
@@ -512,8 +525,8 @@ class AnyPrecisionForCausalLM(nn.Module):
         # with varying lengths re-captures at most log2 times, not per request (the attention launch reads rows up to the position
         # only; a longer cache costs memory, not time).  Beyond 16384 positions the request's own length.
         cap = total if total > 16384 else max(256, 1 << (total - 1).bit_length())
-        dec.setup_caches(1, min(cap, dec.config.block_size))
-        key = (self.precision, dec.max_seq_length, req["temperature"], req["top_k"], req["top_p"], req["repetition_penalty"], req["suppress_tokens"])
+        dec.setup_caches(1, min(cap, dec.config.block_size), kv_cache_dtype=kv_cache_dtype)
+        key = (self.precision, dec.max_seq_length, dec.kv_cache_dtype, req["temperature"], req["top_k"], req["top_p"], req["repetition_penalty"], req["suppress_tokens"])
         graph = self._native_cache.get(("graph",) + key)
         if graph is None:
             self._evict("graph")
@@ -647,7 +660,7 @@ class AnyPrecisionForCausalLM(nn.Module):
         raise NotImplementedError("layer fusion inside the HF module tree is not implemented (as in the reference); use "
                                   "native_decoder(bitwidth) for the fused QKV / Up-Gate decode path")
 
-    def native_decoder(self, bitwidth: Optional[int] = None, release_planes: bool = False):
+    def native_decoder(self, bitwidth: Optional[int] = None, release_planes: bool = False, kv_cache_dtype=None):
         """the same checkpoint as the fused gpt-fast `Transformer` (fused QKV / Up-Gate Any-Precision linears at one precision)
         whose bs=1 decode step runs as the captured 5-launches-per-layer HIP graph.  Built from the module tree's tensors BY
         REFERENCE: embedding, lm_head, norms, o_proj and down_proj are the same storage; q/k/v and gate/up are concatenated into the
@@ -657,6 +670,8 @@ class AnyPrecisionForCausalLM(nn.Module):
         weight; restored from the fused tensors the first time the module tree is used again through this wrapper, a linear's forward,
         `state_dict()` of the wrapper or of `self.model`, or `.to()` -- `_restore_module_tree`).  The default keeps the module tree whole
         (the fused q/k/v/gate/up tensors are then a second copy: 1.1 GB for an 8B 2-bit model)."""
+        from .model import kv_cache_dtype_name
+        kv = None if kv_cache_dtype is None else kv_cache_dtype_name(kv_cache_dtype)
         bitwidth = bitwidth or min(self.precisions)
         dec = self._native_cache.get(("decoder", bitwidth))
         if dec is not None and release_planes and not self._released and all(lin.qweight.shape[0] == bitwidth for lin in self.ap_linears):
@@ -666,6 +681,11 @@ class AnyPrecisionForCausalLM(nn.Module):
             self._restore_module_tree()  # (a decoder of another precision may hold the q/k/v/gate/up planes)
             dec = self._build_native(bitwidth, release_planes)
             self._native_cache[("decoder", bitwidth)] = dec
+        if kv is not None and (kv != dec.kv_cache_dtype or not dec.cache_initialized):
+            # (kv_cache_dtype given: the decoder comes back with caches of that dtype -- the ones it has, re-allocated, or 8 positions)
+            if kv == "fp8" and dec.kv8_unserved():
+                raise ValueError("kv_cache_dtype='fp8': " + dec.kv8_unserved())
+            dec.setup_caches(max(1, dec.max_batch_size), max(8, dec.max_seq_length), kv_cache_dtype=kv)
         return dec
 
     def _layer_linears(self, layer):

@@ -28,6 +28,7 @@ EXPORTS = [
     "gq_attn_decode_split_qknorm", "gq_qknorm_rope_cache_rows", "gq_attn_decode_split_bias",
     "gq_attn_decode_split_window", "gq_attn_decode_split_qknorm_window", "gq_attn_decode_split_bias_window", "gq_attn_decode_roped_window",
     "gq_token_set_build", "gq_sample_topk_rep", "gq_attn_prefill_supported", "gq_attn_prefill",
+    "gq_rope_cache_rows_kv8", "gq_attn_decode_roped_kv8", "gq_attn_prefill_kv8",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -144,6 +145,10 @@ def lib():
         L.gq_silu_mul_rows.argtypes = [vp, vp, u32, u32, i32, vp]
         L.gq_attn_prefill_supported.argtypes = [u32, u32, u32]
         L.gq_attn_prefill.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, f32, u32, vp]
+        # (the fp8 cache forms: scales / reciprocal scales fp32 [n_kv_head] behind the caches)
+        L.gq_rope_cache_rows_kv8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, f32, vp, vp]
+        L.gq_attn_decode_roped_kv8.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, u32, vp]
+        L.gq_attn_prefill_kv8.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, f32, u32, vp]
         L.gq_anyprec_pack.argtypes = [vp, vp, u32, u32, i32, vp]
         L.gq_lnq_cd_block.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, vp]
         L.gq_debug_set_timing_buffer.argtypes = [vp]

@@ -74,6 +74,39 @@ __device__ __forceinline__ void unpack8(const uint4 &row, float (&f)[8]) {  // 1
         f[2 * e + 1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(w[e] >> 16));
     }
 }
+// 8 bytes of an fp8 K / V row: 8 OCP e4m3 codes, converted in hardware (v_cvt_pk_f32_fp8).  Every e4m3 value is an fp16 value, so the
+// floats are those unpack8 gives for the fp16 row that holds the same numbers: the arithmetic behind the unpack does not know the format.
+__device__ __forceinline__ void unpack8_fp8(const uint2 &row, float (&f)[8]) {
+    const u32 w[2] = {row.x, row.y};
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[e], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[e], true);
+        f[4 * e] = lo[0], f[4 * e + 1] = lo[1], f[4 * e + 2] = hi[0], f[4 * e + 3] = hi[1];
+    }
+}
+// the cache format of a launch: element type, the load of a lane's 8 dims of a row (16 bytes of fp16, 8 bytes of fp8), its unpack
+template <bool KV8>
+struct CacheFmt {
+    typedef uint16_t elem;
+    typedef uint4 row;
+    static __device__ __forceinline__ row zero() { return make_uint4(0, 0, 0, 0); }
+    static __device__ __forceinline__ void unpack(const row &r, float (&f)[8]) { unpack8(r, f); }
+};
+template <>
+struct CacheFmt<true> {
+    typedef uint8_t elem;
+    typedef uint2 row;
+    static __device__ __forceinline__ row zero() { return make_uint2(0, 0); }
+    static __device__ __forceinline__ void unpack(const row &r, float (&f)[8]) { unpack8_fp8(r, f); }
+};
+// the per-KV-head scales of an fp8 cache (fp32 [n_kv_head], device memory): value = code * scale.  Compile-time like AttnWindow: the
+// fp16 instances take an empty argument.
+template <bool KV8>
+struct AttnKv8 {};
+template <>
+struct AttnKv8<true> {
+    const float *k_scale, *v_scale;
+};
 // sum over the LPP lanes of a row (xor butterflies inside a 16-lane DPP row): every lane gets the score
 template <int LPP>
 __device__ __forceinline__ float row_sum(float p) {

@@ -380,10 +380,16 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
 // A short context (the `solo` rule) is finished by ONE block per head: block (hq, sp < QH) takes head hq * QH + sp alone.
 // WIN: the window form (attn_core.h, AttnWindow).  The rows requested ahead of the position are usable only when lo == 0; with lo > 0 they
 // are dropped (p0 >= lo > 0 below) and the first batch is requested once lo is known.
-template <int HD, int QH, bool WIN = false>
-__global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint16_t *q, const int *pos_ptr, const uint16_t *kc, const uint16_t *vc,
-                                                                     uint16_t *out, u32 H, u32 Hkv, u32 max_seq, float scale, u32 nsplit, float *ws,
-                                                                     AttnWindow<WIN> wn) {
+// KV8: the caches hold OCP e4m3 codes (gq_attn_decode_roped_kv8): a row is one 8-byte load per lane and unpack8_fp8, the K scale of the
+// head's KV group is folded into the score factor, the V scale multiplies the merged weighted sum (the final one in front of the
+// division, a split's partial one in front of the workspace, so that attn_combine_kernel serves as it is).  Everything else is shared.
+template <int HD, int QH, bool WIN = false, bool KV8 = false>
+__global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint16_t *q, const int *pos_ptr, const typename gq_attn::CacheFmt<KV8>::elem *kc,
+                                                                     const typename gq_attn::CacheFmt<KV8>::elem *vc, uint16_t *out, u32 H, u32 Hkv,
+                                                                     u32 max_seq, float scale, u32 nsplit, float *ws, AttnWindow<WIN> wn,
+                                                                     gq_attn::AttnKv8<KV8> k8) {
+    using Fmt = gq_attn::CacheFmt<KV8>;
+    using Row = typename Fmt::row;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     using Geo = AttnGeom<HD>;
     using L = gq_attn::RopedLds<HD, QH>;
@@ -401,12 +407,12 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
     const u32 h0 = blockIdx.x * QH, g = kv_group_of(h0, H, Hkv), sp = blockIdx.y;
 #endif
     const u32 sub = l / LPP, ld = l % LPP;
-    const uint16_t *kcg = kc + (size_t)g * max_seq * HD, *vcg = vc + (size_t)g * max_seq * HD;
+    const typename Fmt::elem *kcg = kc + (size_t)g * max_seq * HD, *vcg = vc + (size_t)g * max_seq * HD;
     // requests that do not depend on the position: q, and (blocks that may start at row 0) the first batch of cached rows
     uint4 q4[QH];
 #pragma unroll
     for (int qh = 0; qh < QH; qh++) q4[qh] = *reinterpret_cast<const uint4 *>(q + (size_t)(h0 + qh) * HD + ld * 8);
-    uint4 kv[U], vv[U];
+    Row kv[U], vv[U];
     u32 t0 = w * PPW * U;
 #pragma unroll
     for (int u = 0; u < U; u++) {
@@ -414,9 +420,10 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         // (only the first GQ_ATTN_SPEC rows: every row requested ahead of the position is HBM traffic whether it is needed or not --
         // 128 rows x 32 heads = 2 MiB per layer, which costs what the saved round trip gains)
         const bool in = sp < (u32)QH && t < max_seq && t < (u32)GQ_ATTN_SPEC;
-        kv[u] = in ? *reinterpret_cast<const uint4 *>(kcg + (size_t)t * HD + ld * 8) : make_uint4(0, 0, 0, 0);
-        vv[u] = in ? *reinterpret_cast<const uint4 *>(vcg + (size_t)t * HD + ld * 8) : make_uint4(0, 0, 0, 0);
+        kv[u] = in ? *reinterpret_cast<const Row *>(kcg + (size_t)t * HD + ld * 8) : Fmt::zero();
+        vv[u] = in ? *reinterpret_cast<const Row *>(vcg + (size_t)t * HD + ld * 8) : Fmt::zero();
     }
+    if constexpr (KV8) scale *= k8.k_scale[g];  // (block-uniform: one scalar load next to the position's)
     const u32 pos = (u32)pos_ptr[0];
     if (pos >= max_seq) {  // decoding past the cache: the head's output is poisoned (NaN logits), like attn_decode_kernel
         if (sp == 0u && tid < (u32)QH * HD) out[(size_t)h0 * HD + tid] = 0x7e00u;
@@ -451,20 +458,20 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
 #pragma unroll
         for (int e = 0; e < 8; e++) acc[qh][e] = 0.f;
     }
-    auto request = [&](uint4 (&kd)[U], uint4 (&vd)[U], u32 tb) {
+    auto request = [&](Row (&kd)[U], Row (&vd)[U], u32 tb) {
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const u32 t = tb + (u32)u * PPW + sub;
             const bool in = t < p1;
-            kd[u] = in ? *reinterpret_cast<const uint4 *>(kcg + (size_t)t * HD + ld * 8) : make_uint4(0, 0, 0, 0);
-            vd[u] = in ? *reinterpret_cast<const uint4 *>(vcg + (size_t)t * HD + ld * 8) : make_uint4(0, 0, 0, 0);
+            kd[u] = in ? *reinterpret_cast<const Row *>(kcg + (size_t)t * HD + ld * 8) : Fmt::zero();
+            vd[u] = in ? *reinterpret_cast<const Row *>(vcg + (size_t)t * HD + ld * 8) : Fmt::zero();
         }
     };
     t0 = p0 + w * PPW * U;
     const bool have = p0 == 0u && t0 + PPW * U <= (u32)GQ_ATTN_SPEC;  // the batch at t0 is already in registers
     if (!have && t0 < p1) request(kv, vv, t0);
     for (; t0 < p1; t0 += NW * PPW * U) {
-        uint4 kn[U], vn[U];
+        Row kn[U], vn[U];
         const bool more = QH > 1 && t0 + NW * PPW * U < p1;  // (QH > 1: the next pass is on its way while this one is multiplied)
         if (more) request(kn, vn, t0 + NW * PPW * U);
         float pu[QH][U], vfu[U][8];
@@ -473,12 +480,19 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
             const u32 t = t0 + (u32)u * PPW + sub;
             const bool valid = t < p1;
             float kf[8];
-            const u32 vw[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
-            gq_attn::unpack8(kv[u], kf);
+            Fmt::unpack(kv[u], kf);
+            if constexpr (KV8) {
+                float vf[8];
+                Fmt::unpack(vv[u], vf);
 #pragma unroll
-            for (int e = 0; e < 4; e++) {
-                vfu[u][2 * e] = valid ? h2f((uint16_t)(vw[e] & 0xFFFF)) : 0.f;
-                vfu[u][2 * e + 1] = valid ? h2f((uint16_t)(vw[e] >> 16)) : 0.f;
+                for (int e = 0; e < 8; e++) vfu[u][e] = valid ? vf[e] : 0.f;
+            } else {
+                const u32 vw[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    vfu[u][2 * e] = valid ? h2f((uint16_t)(vw[e] & 0xFFFF)) : 0.f;
+                    vfu[u][2 * e + 1] = valid ? h2f((uint16_t)(vw[e] >> 16)) : 0.f;
+                }
             }
 #pragma unroll
             for (int qh = 0; qh < QH; qh++) {
@@ -536,6 +550,7 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         for (u32 g8 = 0; g8 < ng; g8++)
 #pragma unroll
             for (u32 k = 0; k < 8u; k++) gq_attn::merge_step<HD>(scq, rq, fq, 8u * g8 + k, dd, o, sum);
+        if constexpr (KV8) o *= k8.v_scale[g];
         if (nsplit > 1u) {
             float *wp = ws + ((size_t)h * nsplit + sp) * (HD + 2u);
             wp[dd] = o;
@@ -1299,13 +1314,17 @@ extern "C" int gq_attn_decode_qtip(const GqQtipOut *qkv_lin, const int *pos, con
 // Attention of the decode step when the wqkv launch has already rotated q / k and written k / v of the current token into the
 // caches (gq_anyprec_gemv_qkv_rope): q fp16 [n_head * head_dim] rotated; the caches hold every position <= *pos.
 namespace {
-template <bool WIN>
+template <bool WIN, bool KV8 = false>
 int roped_launch(const void *q, const int *pos, const void *k_cache, const void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head,
-                 uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream) {
-    const bool any_null = !q || !pos || !k_cache || !v_cache || !out;
+                 uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream,
+                 const float *k_scale = nullptr, const float *v_scale = nullptr) {
+    using CE = typename gq_attn::CacheFmt<KV8>::elem;
+    const bool any_null = !q || !pos || !k_cache || !v_cache || !out || (KV8 && (!k_scale || !v_scale));
     if (const int rc = attn_check_args(any_null, nullptr, WIN, window, n_head, n_kv_head, head_dim, n_split, workspace)) return rc;
     AttnWindow<WIN> wn{};
     if constexpr (WIN) wn = AttnWindow<true>{window};
+    gq_attn::AttnKv8<KV8> k8{};
+    if constexpr (KV8) k8 = gq_attn::AttnKv8<true>{k_scale, v_scale};
     if (((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15u) return gq_fail(GQ_EINVAL, "buffers must be 16-byte aligned.");
     hipStream_t s = (hipStream_t)stream;
     // grouped-query models with a split cache: the 4 query heads of a KV group in one block (every cached row loaded once)
@@ -1317,10 +1336,10 @@ int roped_launch(const void *q, const int *pos, const void *k_cache, const void 
     const dim3 grid(n_head / qh, gqa_p ? copies : n_split);
     if (gqa_p && !WIN) {
         static GqPerDeviceOnce once;
-        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<128, 4>), 160 * 1024));
-        hipLaunchKernelGGL((attn_roped_kernel<128, 4>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<128, 4>::bytes()), s, (const uint16_t *)q, pos,
-                           (const uint16_t *)k_cache, (const uint16_t *)v_cache, (uint16_t *)out, n_head, n_kv_head, max_seq, scale, 1u, workspace,
-                           AttnWindow<false>{});
+        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<128, 4, false, KV8>), 160 * 1024));
+        hipLaunchKernelGGL((attn_roped_kernel<128, 4, false, KV8>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<128, 4>::bytes()), s, (const uint16_t *)q, pos,
+                           (const CE *)k_cache, (const CE *)v_cache, (uint16_t *)out, n_head, n_kv_head, max_seq, scale, 1u, workspace,
+                           AttnWindow<false>{}, k8);
         GQ_HIP_CHECK(hipGetLastError());
         return GQ_OK;
     }
@@ -1331,10 +1350,10 @@ int roped_launch(const void *q, const int *pos, const void *k_cache, const void 
 #define GQ_LAUNCH_ROPED(HD_, QH_)                                                                                                    \
     do {                                                                                                                             \
         static GqPerDeviceOnce once;                                                                                                 \
-        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<HD_, QH_, WIN>), 160 * 1024));             \
-        hipLaunchKernelGGL((attn_roped_kernel<HD_, QH_, WIN>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<HD_, QH_>::bytes()), s, \
-                           (const uint16_t *)q, pos, (const uint16_t *)k_cache, (const uint16_t *)v_cache, (uint16_t *)out, n_head,   \
-                           n_kv_head, max_seq, scale, n_split, workspace, wn);                                                       \
+        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<HD_, QH_, WIN, KV8>), 160 * 1024));        \
+        hipLaunchKernelGGL((attn_roped_kernel<HD_, QH_, WIN, KV8>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<HD_, QH_>::bytes()), s, \
+                           (const uint16_t *)q, pos, (const CE *)k_cache, (const CE *)v_cache, (uint16_t *)out, n_head,               \
+                           n_kv_head, max_seq, scale, n_split, workspace, wn, k8);                                                   \
         if (n_split > 1u)                                                                                                            \
             hipLaunchKernelGGL((attn_combine_kernel<HD_, WIN>), dim3(n_head), dim3(HD_), 0, s, workspace, (uint16_t *)out, n_split,   \
                                pos, max_seq, wn);                                                                                    \
@@ -1362,6 +1381,17 @@ extern "C" int gq_attn_decode_roped_window(const void *q, const int *pos, const 
                                            uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split,
                                            float *workspace, uint32_t window, void *stream) {
     return roped_launch<true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, window, stream);
+}
+// the fp8 (e4m3) cache form of the two entries above (window 0: the whole context): the same launches over caches of one byte per
+// element, scales fp32 [n_kv_head] in device memory
+extern "C" int gq_attn_decode_roped_kv8(const void *q, const int *pos, const void *k_cache, const void *v_cache, const float *k_scale,
+                                        const float *v_scale, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                                        float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream) {
+    if (window)
+        return roped_launch<true, true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, window, stream,
+                                        k_scale, v_scale);
+    return roped_launch<false, true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, 0u, stream,
+                                     k_scale, v_scale);
 }
 
 extern "C" int gq_attn_decode(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,

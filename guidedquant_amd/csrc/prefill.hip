@@ -221,6 +221,129 @@ __global__ void __launch_bounds__(256) qknorm_rope_cache_rows_kernel(const uint1
     }
 }
 
+// ------------------------------------------------------------------------------------------------ fp8 (e4m3) KV cache
+// 8 fp16 values (4 words) -> 8 OCP e4m3 codes by THE write rule of the fp8 cache, the only rounding the format adds:
+//   code = fp8_rne(clamp(float(x16) * inv, -448, 448))
+// inv = 1 / scale of the KV head, an fp32 the host computed (no division here).  The clamp is explicit (v_med3_f32): v_cvt_pk_fp8_f32
+// turns a magnitude beyond 448 into NaN, not into 448.  The host model: (x16.float() * inv).clamp(-448, 448).to(torch.float8_e4m3fn).
+__device__ __forceinline__ uint2 fp8_quant8(const u32 (&w)[4], float inv) {
+    u32 o[2];
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+        float f[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            f[k] = __builtin_amdgcn_fmed3f(h2f((uint16_t)(w[2 * e + (k >> 1)] >> (16 * (k & 1)))) * inv, -448.f, 448.f);
+        int r = 0;
+        r = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], r, false);
+        r = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], r, true);
+        o[e] = (u32)r;
+    }
+    return make_uint2(o[0], o[1]);
+}
+
+// rope_cache_rows_kernel / qknorm_rope_cache_rows_kernel for caches of one byte per element: the same thread units, the same fp16
+// values up to the store -- q_out is bit for bit what the fp16 kernels write -- and k / v stored by fp8_quant8 with the reciprocal
+// scale of their KV head.  QKN: the per-head RMSNorm of q and k in front of the rotation (the block above).  QB: the bias of the q / k / v
+// linears (fp16, laid out like a qkv row), ONE fp16 add in front of the rotation (decode.hip, AttnBias).  The loop has the block-uniform
+// bound of the QK-norm kernel in every form.
+template <bool QKN, bool QB>
+__global__ void __launch_bounds__(256) rope_cache_rows_kv8_kernel(const uint16_t *__restrict__ qkv, const int *__restrict__ pos,
+                                                                  const uint16_t *__restrict__ cos_t, const uint16_t *__restrict__ sin_t,
+                                                                  uint16_t *__restrict__ q_out, uint8_t *__restrict__ kc, uint8_t *__restrict__ vc,
+                                                                  const float *__restrict__ k_inv, const float *__restrict__ v_inv,
+                                                                  const uint16_t *__restrict__ qnw, const uint16_t *__restrict__ knw, float eps,
+                                                                  const uint16_t *__restrict__ bias, u32 S, u32 H, u32 Hkv, u32 HD, u32 max_seq) {
+    const u32 upr = HD / 16u, heads = H + 2u * Hkv, total = S * heads * upr;
+    for (u32 base = blockIdx.x * 256u; base < total; base += gridDim.x * 256u) {
+        const u32 i = base + threadIdx.x;
+        const bool active = i < total;
+        const u32 ic = active ? i : 0u;
+        const u32 u = ic % upr, hh = (ic / upr) % heads, s = ic / (upr * heads), d = 8u * u;
+        const u32 p = (u32)pos[s];
+        const uint16_t *src = qkv + (size_t)s * heads * HD + (size_t)hh * HD;
+        uint4 a = *reinterpret_cast<const uint4 *>(src + d), b = *reinterpret_cast<const uint4 *>(src + d + HD / 2u);
+        u32 x1[4] = {a.x, a.y, a.z, a.w}, x2[4] = {b.x, b.y, b.z, b.w};
+        if constexpr (QB) {
+            const uint16_t *br = bias + (size_t)hh * HD;
+            const uint4 b1 = *reinterpret_cast<const uint4 *>(br + d), b2 = *reinterpret_cast<const uint4 *>(br + d + HD / 2u);
+            const u32 bb1[4] = {b1.x, b1.y, b1.z, b1.w}, bb2[4] = {b2.x, b2.y, b2.z, b2.w};
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                u32 r1 = 0, r2 = 0;
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    const u32 sh = 16u * (u32)k;
+                    r1 |= (u32)bitsh(hbits((uint16_t)(x1[e] >> sh)) + hbits((uint16_t)(bb1[e] >> sh))) << sh;
+                    r2 |= (u32)bitsh(hbits((uint16_t)(x2[e] >> sh)) + hbits((uint16_t)(bb2[e] >> sh))) << sh;
+                }
+                x1[e] = r1, x2[e] = r2;
+            }
+        }
+        float ss = 0.f;
+        if constexpr (QKN) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const float f0 = h2f((uint16_t)(x1[e] & 0xFFFF)), f1 = h2f((uint16_t)(x1[e] >> 16));
+                ss += f0 * f0;
+                ss += f1 * f1;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const float f0 = h2f((uint16_t)(x2[e] & 0xFFFF)), f1 = h2f((uint16_t)(x2[e] >> 16));
+                ss += f0 * f0;
+                ss += f1 * f1;
+            }
+            for (u32 sh = 1u; sh < upr; sh <<= 1) ss += __shfl_xor(ss, (int)sh, 64);  // (upr is wave-uniform: 4 or 8 lanes, aligned)
+        }
+        if (!active) continue;
+        if (hh >= H + Hkv) {  // v: quantised as it is
+            if (p < max_seq) {
+                const u32 g = hh - H - Hkv;
+                uint8_t *dst = vc + ((size_t)g * max_seq + p) * HD;
+                const float inv = v_inv[g];
+                *reinterpret_cast<uint2 *>(dst + d) = fp8_quant8(x1, inv);
+                *reinterpret_cast<uint2 *>(dst + d + HD / 2u) = fp8_quant8(x2, inv);
+            }
+            continue;
+        }
+        if constexpr (QKN) {
+            const float rs = rsqrtf(ss / (float)HD + eps);
+            const uint16_t *wn = hh < H ? qnw : knw;
+            const uint4 w1 = *reinterpret_cast<const uint4 *>(wn + d), w2 = *reinterpret_cast<const uint4 *>(wn + d + HD / 2u);
+            const u32 ww1[4] = {w1.x, w1.y, w1.z, w1.w}, ww2[4] = {w2.x, w2.y, w2.z, w2.w};
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                u32 r1 = 0, r2 = 0;
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    const u32 sh = 16u * (u32)k;
+                    const h16 v1 = (h16)(h2f((uint16_t)(x1[e] >> sh)) * rs) * hbits((uint16_t)(ww1[e] >> sh));
+                    const h16 v2 = (h16)(h2f((uint16_t)(x2[e] >> sh)) * rs) * hbits((uint16_t)(ww2[e] >> sh));
+                    r1 |= (u32)bitsh(v1) << sh;
+                    r2 |= (u32)bitsh(v2) << sh;
+                }
+                x1[e] = r1, x2[e] = r2;
+            }
+        }
+        a = make_uint4(x1[0], x1[1], x1[2], x1[3]);
+        b = make_uint4(x2[0], x2[1], x2[2], x2[3]);
+        u32 o1[4], o2[4];
+        rope_unit(a, b, cos_t, sin_t, p, max_seq, HD, d, o1, o2);
+        if (hh < H) {
+            uint16_t *dst = q_out + ((size_t)hh * S + s) * HD;
+            *reinterpret_cast<uint4 *>(dst + d) = make_uint4(o1[0], o1[1], o1[2], o1[3]);
+            *reinterpret_cast<uint4 *>(dst + d + HD / 2u) = make_uint4(o2[0], o2[1], o2[2], o2[3]);
+        } else if (p < max_seq) {
+            const u32 g = hh - H;
+            uint8_t *dst = kc + ((size_t)g * max_seq + p) * HD;
+            const float inv = k_inv[g];
+            *reinterpret_cast<uint2 *>(dst + d) = fp8_quant8(o1, inv);
+            *reinterpret_cast<uint2 *>(dst + d + HD / 2u) = fp8_quant8(o2, inv);
+        }
+    }
+}
+
 // y [S][2 I] -> out [S][I]; paired: (gate_i, up_i) adjacent (the decode step's row order), else gate = y[:, :I], up = y[:, I:]
 __global__ void __launch_bounds__(256) silu_mul_rows_kernel(const uint16_t *__restrict__ y, uint16_t *__restrict__ out, u32 S, u32 I, u32 paired) {
     const u32 upr = I / 8u, total = S * upr;
@@ -305,6 +428,37 @@ extern "C" int gq_qknorm_rope_cache_rows(const void *qkv, const int *pos, const 
     hipLaunchKernelGGL(qknorm_rope_cache_rows_kernel, dim3(blocks > 65535u ? 65535u : blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)qkv, pos,
                        (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)q_out, (uint16_t *)k_cache, (uint16_t *)v_cache,
                        (const uint16_t *)q_norm_weight, (const uint16_t *)k_norm_weight, eps, S, n_head, n_kv_head, head_dim, max_seq);
+    GQ_HIP_CHECK(hipGetLastError());
+    return GQ_OK;
+}
+
+extern "C" int gq_rope_cache_rows_kv8(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
+                                      void *v_cache, const float *k_inv, const float *v_inv, uint32_t S, uint32_t n_head, uint32_t n_kv_head,
+                                      uint32_t head_dim, uint32_t max_seq, const void *q_norm_weight, const void *k_norm_weight, float eps,
+                                      const void *qkv_bias, void *stream) {
+    if (!qkv || !pos || !cos_table || !sin_table || !q_out || !k_cache || !v_cache || !k_inv || !v_inv) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    const bool qkn = q_norm_weight || k_norm_weight;
+    if (qkn && (!q_norm_weight || !k_norm_weight)) return gq_fail(GQ_EINVAL, "gq_rope_cache_rows_kv8: both norm weights or none.");
+    if (qkn && qkv_bias) return gq_fail(GQ_EINVAL, "gq_rope_cache_rows_kv8: the norm form and the bias form do not combine.");
+    if (S == 0) return GQ_OK;
+    if ((head_dim != 64u && head_dim != 128u) || n_head == 0 || n_kv_head == 0 || max_seq == 0)
+        return gq_fail(GQ_ENOTSUP, "gq_rope_cache_rows_kv8: head_dim must be 64 or 128.");
+    if (((uintptr_t)qkv | (uintptr_t)cos_table | (uintptr_t)sin_table | (uintptr_t)q_out | (uintptr_t)k_cache | (uintptr_t)v_cache |
+         (uintptr_t)q_norm_weight | (uintptr_t)k_norm_weight | (uintptr_t)qkv_bias) & 15u)
+        return gq_fail(GQ_EINVAL, "gq_rope_cache_rows_kv8: 16-byte aligned pointers.");
+    const uint64_t total = (uint64_t)S * (n_head + 2u * n_kv_head) * (head_dim / 16u);
+    if (total >= 0x7FFFFFFFull) return gq_fail(GQ_ENOTSUP, "gq_rope_cache_rows_kv8: problem too large.");
+    const u32 nb = (u32)((total + 255u) / 256u);
+    const dim3 grid(nb > 65535u ? 65535u : nb), block(256);
+#define GQ_LAUNCH_ROWS_KV8(QKN_, QB_)                                                                                                          \
+    hipLaunchKernelGGL((rope_cache_rows_kv8_kernel<QKN_, QB_>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)qkv, pos,              \
+                       (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)q_out, (uint8_t *)k_cache, (uint8_t *)v_cache, k_inv, \
+                       v_inv, (const uint16_t *)q_norm_weight, (const uint16_t *)k_norm_weight, eps, (const uint16_t *)qkv_bias, S, n_head,   \
+                       n_kv_head, head_dim, max_seq)
+    if (qkn) GQ_LAUNCH_ROWS_KV8(true, false);
+    else if (qkv_bias) GQ_LAUNCH_ROWS_KV8(false, true);
+    else GQ_LAUNCH_ROWS_KV8(false, false);
+#undef GQ_LAUNCH_ROWS_KV8
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
 }

@@ -41,10 +41,45 @@ __device__ __forceinline__ h16x4 lds_read_tr(const h16 *p) {
     return __builtin_bit_cast(h16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)p));
 }
 
-template <int HD>
-__global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__restrict__ q, const uint16_t *__restrict__ kc, const uint16_t *__restrict__ vc,
-                                                           uint16_t *__restrict__ out, u32 S, u32 start, u32 H, u32 group, u32 max_seq, float c,
-                                                           u32 window) {
+// the cache format of an instance.  fp8 (gq_attn_prefill_kv8): a chunk of 8 elements is 8 bytes of OCP e4m3 codes, converted to fp16 --
+// exactly: every e4m3 value is an fp16 value -- between the global load and the LDS store, so the LDS image, the fragments and both
+// products are those of the fp16 instance on the same numbers; the scales (fp32 per KV head, device memory) stay outside the products
+template <bool KV8>
+struct TileFmt {
+    typedef uint16_t elem;
+    typedef uint4 chunk;
+    struct Scales {};
+    static __device__ __forceinline__ chunk zero() { return make_uint4(0u, 0u, 0u, 0u); }
+    static __device__ __forceinline__ uint4 to_f16(const chunk &v) { return v; }
+};
+template <>
+struct TileFmt<true> {
+    typedef uint8_t elem;
+    typedef uint2 chunk;
+    struct Scales {
+        const float *k_scale, *v_scale;
+    };
+    static __device__ __forceinline__ chunk zero() { return make_uint2(0u, 0u); }
+    static __device__ __forceinline__ uint4 to_f16(const chunk &v) {
+        const u32 w[2] = {v.x, v.y};
+        u32 o[4];
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[e], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[e], true);
+            o[2 * e] = (u32)__builtin_bit_cast(uint16_t, (h16)lo[0]) | ((u32)__builtin_bit_cast(uint16_t, (h16)lo[1]) << 16);
+            o[2 * e + 1] = (u32)__builtin_bit_cast(uint16_t, (h16)hi[0]) | ((u32)__builtin_bit_cast(uint16_t, (h16)hi[1]) << 16);
+        }
+        return make_uint4(o[0], o[1], o[2], o[3]);
+    }
+};
+
+template <int HD, bool KV8 = false>
+__global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__restrict__ q, const typename TileFmt<KV8>::elem *__restrict__ kc,
+                                                           const typename TileFmt<KV8>::elem *__restrict__ vc, uint16_t *__restrict__ out, u32 S,
+                                                           u32 start, u32 H, u32 group, u32 max_seq, float c, u32 window,
+                                                           typename TileFmt<KV8>::Scales sc) {
+    using Fmt = TileFmt<KV8>;
+    using Chunk = typename Fmt::chunk;
     constexpr u32 LD = HD + 8;             // halves per LDS row: 16 bytes of padding
     constexpr u32 CH = HD / 8;             // 16-byte chunks per row
     constexpr u32 NCH = BK * CH / 256;     // chunks per thread and matrix
@@ -56,7 +91,8 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
     const u32 head = blockIdx.y, kvh = head / group;  // (once per block)
     const u32 q0 = (gridDim.x - 1u - blockIdx.x) * BQ;  // the long rows of the triangle first
     const u32 T = start + S;
-    const uint16_t *kbase = kc + (size_t)kvh * max_seq * HD, *vbase = vc + (size_t)kvh * max_seq * HD;
+    const typename Fmt::elem *kbase = kc + (size_t)kvh * max_seq * HD, *vbase = vc + (size_t)kvh * max_seq * HD;
+    if constexpr (KV8) c *= sc.k_scale[kvh];  // (the K scale: one factor of the scores)
 
     // the block's key range: [klo, khi] covers every key one of its rows attends
     const u32 p_lo = start + q0, khi = start + min(q0 + BQ - 1u, S - 1u);
@@ -76,17 +112,17 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
         for (u32 ks = 0; ks < KS; ks++) qf[ks] = __builtin_bit_cast(h16x8, *reinterpret_cast<const uint4 *>(qr + 32u * ks));
     }
 
-    uint4 kreg[NCH], vreg[NCH];
+    Chunk kreg[NCH], vreg[NCH];
     auto load_tile = [&](u32 kt) {
 #pragma unroll
         for (u32 i = 0; i < NCH; i++) {
             const u32 id = tid + 256u * i, row = id / CH, col = id % CH, t = kt * BK + row;  // (CH: a power of two)
             if (t < T) {
-                kreg[i] = *reinterpret_cast<const uint4 *>(kbase + (size_t)t * HD + 8u * col);
-                vreg[i] = *reinterpret_cast<const uint4 *>(vbase + (size_t)t * HD + 8u * col);
+                kreg[i] = *reinterpret_cast<const Chunk *>(kbase + (size_t)t * HD + 8u * col);
+                vreg[i] = *reinterpret_cast<const Chunk *>(vbase + (size_t)t * HD + 8u * col);
             } else {
-                kreg[i] = make_uint4(0u, 0u, 0u, 0u);
-                vreg[i] = make_uint4(0u, 0u, 0u, 0u);
+                kreg[i] = Fmt::zero();
+                vreg[i] = Fmt::zero();
             }
         }
     };
@@ -102,8 +138,8 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
 #pragma unroll
         for (u32 i = 0; i < NCH; i++) {
             const u32 id = tid + 256u * i, row = id / CH, col = id % CH;
-            *reinterpret_cast<uint4 *>(&sK[row * LD + 8u * col]) = kreg[i];
-            *reinterpret_cast<uint4 *>(&sV[row * LD + 8u * col]) = vreg[i];
+            *reinterpret_cast<uint4 *>(&sK[row * LD + 8u * col]) = Fmt::to_f16(kreg[i]);
+            *reinterpret_cast<uint4 *>(&sV[row * LD + 8u * col]) = Fmt::to_f16(vreg[i]);
         }
         __syncthreads();
         if (kt < kt1) load_tile(kt + 1u);  // in flight under the products below
@@ -172,7 +208,8 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
     l_run += __shfl_xor(l_run, 16, 64);
     l_run += __shfl_xor(l_run, 32, 64);
     if (qrow < S) {
-        const float inv = 1.0f / l_run;
+        float inv = 1.0f / l_run;
+        if constexpr (KV8) inv *= sc.v_scale[kvh];  // (the V scale: on the output, in front of its one fp16 rounding)
         uint16_t *orow = out + (size_t)qrow * H * HD + (size_t)head * HD + 4u * g;
 #pragma unroll
         for (u32 d = 0; d < DB; d++) {
@@ -187,8 +224,12 @@ extern "C" int gq_attn_prefill_supported(uint32_t n_head, uint32_t n_kv_head, ui
     return (head_dim == 64u || head_dim == 128u) && n_head != 0u && n_kv_head != 0u && n_head % n_kv_head == 0u && n_head <= 65535u;
 }
 
-extern "C" int gq_attn_prefill(const void *q, const void *k_cache, const void *v_cache, void *out, uint32_t S, uint32_t start, uint32_t n_head,
-                               uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t window, void *stream) {
+namespace {
+template <bool KV8>
+int prefill_attn_launch(const void *q, const void *k_cache, const void *v_cache, void *out, uint32_t S, uint32_t start, uint32_t n_head,
+                        uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t window, void *stream,
+                        typename TileFmt<KV8>::Scales sc) {
+    using CE = typename TileFmt<KV8>::elem;
     if (!gq_attn_prefill_supported(n_head, n_kv_head, head_dim))
         return gq_fail(GQ_ENOTSUP, "gq_attn_prefill: head_dim 64 or 128, n_head a multiple of n_kv_head.");
     if (!q || !k_cache || !v_cache || !out) return gq_fail(GQ_EINVAL, "null pointer argument.");
@@ -202,11 +243,24 @@ extern "C" int gq_attn_prefill(const void *q, const void *k_cache, const void *v
     const dim3 grid((S + BQ - 1u) / BQ, n_head), block(256);
     const uint32_t group = n_head / n_kv_head;
     if (head_dim == 64u)
-        hipLaunchKernelGGL(prefill_attn_kernel<64>, grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const uint16_t *)k_cache, (const uint16_t *)v_cache,
-                           (uint16_t *)out, S, start, n_head, group, max_seq, c, window);
+        hipLaunchKernelGGL((prefill_attn_kernel<64, KV8>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
+                           (uint16_t *)out, S, start, n_head, group, max_seq, c, window, sc);
     else
-        hipLaunchKernelGGL(prefill_attn_kernel<128>, grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const uint16_t *)k_cache, (const uint16_t *)v_cache,
-                           (uint16_t *)out, S, start, n_head, group, max_seq, c, window);
+        hipLaunchKernelGGL((prefill_attn_kernel<128, KV8>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
+                           (uint16_t *)out, S, start, n_head, group, max_seq, c, window, sc);
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
+}
+}  // namespace
+
+extern "C" int gq_attn_prefill(const void *q, const void *k_cache, const void *v_cache, void *out, uint32_t S, uint32_t start, uint32_t n_head,
+                               uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t window, void *stream) {
+    return prefill_attn_launch<false>(q, k_cache, v_cache, out, S, start, n_head, n_kv_head, head_dim, max_seq, scale, window, stream, {});
+}
+
+extern "C" int gq_attn_prefill_kv8(const void *q, const void *k_cache, const void *v_cache, const float *k_scale, const float *v_scale, void *out,
+                                   uint32_t S, uint32_t start, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale,
+                                   uint32_t window, void *stream) {
+    if (!k_scale || !v_scale) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    return prefill_attn_launch<true>(q, k_cache, v_cache, out, S, start, n_head, n_kv_head, head_dim, max_seq, scale, window, stream, {k_scale, v_scale});
 }

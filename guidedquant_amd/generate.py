@@ -198,7 +198,9 @@ class DecodeGraph:
         """what the captured launches point at: the graph bakes in raw pointers (KV caches, RoPE tables, the native step's
         buffers) and max_seq_length; `setup_caches` with a longer length re-allocates all of them"""
         m = self.model
-        sig = [m.max_seq_length, m.max_batch_size, m.rope_cos.data_ptr(), m.rope_sin.data_ptr()]
+        sig = [m.max_seq_length, m.max_batch_size, m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), getattr(m, "kv_cache_dtype", "fp16")]
+        # (an fp8 cache's scale buffers are buffers of the layers: their pointers are in the list below; their VALUES are read by the
+        # kernels at every replay)
         sig += [b.attention.kv_cache.k_cache.data_ptr() for b in m.layers]
         # the weight tensors the captured launches read (model.to() / .half() or an in-place re-pair after a sub-module
         # load_state_dict assign new ones; `_alloc_gen` is bumped on those events, this is what the re-validation compares)
@@ -324,12 +326,13 @@ def decode_n_tokens(model: Transformer, cur_token: torch.Tensor, input_pos: torc
 
 @torch.no_grad()
 def generate(model: Transformer, prompt: torch.Tensor, max_new_tokens: int, batch_size: int = 1, callback=lambda x: x,
-             use_graph=True, graph: Optional[DecodeGraph] = None, **sampling_kwargs) -> torch.Tensor:
+             use_graph=True, graph: Optional[DecodeGraph] = None, kv_cache_dtype=None, **sampling_kwargs) -> torch.Tensor:
+    """kv_cache_dtype: None / "fp16" / "fp8" (Transformer.setup_caches); a `graph` must have been captured over caches of that dtype"""
     T = prompt.size(-1)
     T_new = T + max_new_tokens
     max_seq_length = min(T_new, model.config.block_size)
     device, dtype = prompt.device, prompt.dtype
-    model.setup_caches(max_batch_size=batch_size, max_seq_length=max_seq_length)
+    model.setup_caches(max_batch_size=batch_size, max_seq_length=max_seq_length, kv_cache_dtype=kv_cache_dtype)
     seq = torch.empty(batch_size, T_new, dtype=dtype, device=device)
     prompt = prompt.view(1, -1).repeat(batch_size, 1)
     seq[:, :T] = prompt
@@ -467,7 +470,7 @@ def benchmark_decode(model: Transformer, device, num_samples=5, max_new_tokens=1
 
 def main(prompt=None, num_samples=5, max_new_tokens=100, batch_size=1, top_k=200, temperature=0.8, compile=2,
          compile_prefill=False, profile=None, device="cuda", model_name=None, backend=None, bitwidth=None,
-         checkpoint_path=None, config_path=None, dtype=None, print_result=False, random_init=False):
+         checkpoint_path=None, config_path=None, dtype=None, print_result=False, random_init=False, kv_cache_dtype=None):
     """generate.py:268-389 -- same arguments and printed report.  `compile` selects the decode driver: 0 = eager per-token
     launches, >= 1 = the captured hipGraph of the decode step (the role torch.compile(mode='max-autotune') plays in the
     reference).  A tokenizer is only needed for a text prompt / --print_result; without one the BOS id of the model
@@ -493,7 +496,7 @@ def main(prompt=None, num_samples=5, max_new_tokens=100, batch_size=1, top_k=200
     prompt_length = encoded.size(-1)
     torch.manual_seed(1234)
     model_size, params = _get_model_size(model)
-    model.setup_caches(1, prompt_length + max_new_tokens)
+    model.setup_caches(1, prompt_length + max_new_tokens, kv_cache_dtype=kv_cache_dtype)
     use_graph = bool(compile) and "cuda" in str(device)
     graph = DecodeGraph(model, device, temperature=temperature, top_k=top_k) if use_graph else None
     tps = []
@@ -501,7 +504,7 @@ def main(prompt=None, num_samples=5, max_new_tokens=100, batch_size=1, top_k=200
         if "cuda" in str(device):
             torch.cuda.synchronize()
         t1 = time.perf_counter()
-        y = generate(model, encoded, max_new_tokens, use_graph=use_graph, graph=graph, temperature=temperature, top_k=top_k)
+        y = generate(model, encoded, max_new_tokens, use_graph=use_graph, graph=graph, kv_cache_dtype=kv_cache_dtype, temperature=temperature, top_k=top_k)
         if "cuda" in str(device):
             torch.cuda.synchronize()
         elapsed = time.perf_counter() - t1
@@ -547,6 +550,8 @@ if __name__ == "__main__":
     parser.add_argument('--backend', type=str, default=None, choices=["ap", "lutgemm", "qtip", None])
     parser.add_argument('--print_result', action='store_true')
     parser.add_argument('--random_init', action='store_true')
+    parser.add_argument('--kv_cache_dtype', type=str, default=None, choices=["fp16", "fp8"],
+                        help='fp8: the KV cache as e4m3 codes, scale 1.0 per head (fused Any-Precision models; default fp16)')
     a = parser.parse_args()
     main(a.prompt, a.num_samples, a.max_new_tokens, a.batch_size, a.top_k, a.temperature, a.compile, a.compile_prefill, a.profile,
-         a.device, a.model_name, a.backend, a.bitwidth, a.checkpoint_path, a.config_path, a.dtype, a.print_result, a.random_init)
+         a.device, a.model_name, a.backend, a.bitwidth, a.checkpoint_path, a.config_path, a.dtype, a.print_result, a.random_init, a.kv_cache_dtype)

@@ -207,16 +207,57 @@ def _sdpa_gqa(q, k, v, mask, rep):
     return F.scaled_dot_product_attention(q, k, v, attn_mask=mask, dropout_p=0.0, is_causal=mask is None)
 
 
-class KVCache(nn.Module):
+FP8_MAX = 448.0  # the largest e4m3 magnitude
 
-    def __init__(self, max_batch_size, max_seq_length, n_heads, head_dim, dtype=torch.half, device=None):
+
+def kv_cache_dtype_name(kv_cache_dtype) -> str:
+    """None / "fp16" -> "fp16" (the cache in the model's own dtype: the default), "fp8" -> "fp8" (OCP e4m3 codes + a scale per KV head)"""
+    name = "fp16" if kv_cache_dtype is None else str(kv_cache_dtype)
+    if name not in ("fp16", "fp8"):
+        raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r}: None, 'fp16' or 'fp8'")
+    return name
+
+
+def fp8_quantize(x16: Tensor, inv: Tensor) -> Tensor:
+    """THE write rule of the fp8 cache (include/gq_hip.h), the only rounding the format adds: code = fp8_rne(clamp(float(x16) * inv,
+    -448, 448)).  x16 [.., n_kv_head, n, head_dim], inv fp32 [n_kv_head]; returns the codes as uint8."""
+    return (x16.float() * inv[:, None, None]).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+class KVCache(nn.Module):
+    """k_cache / v_cache [batch][n_kv_head][max_seq][head_dim] in `dtype`.  fp8=True: torch.float8_e4m3fn caches with four fp32
+    [n_kv_head] buffers -- k_scale / v_scale (value = code * scale, default 1.0) and their reciprocals k_inv / v_inv, which the host
+    fills (`set_scales`: torch.reciprocal; no kernel divides).  `dtype` is then what `update` dequantises to."""
+
+    def __init__(self, max_batch_size, max_seq_length, n_heads, head_dim, dtype=torch.half, device=None, fp8=False):
         super().__init__()
         cache_shape = (max_batch_size, n_heads, max_seq_length, head_dim)
-        self.register_buffer('k_cache', torch.zeros(cache_shape, dtype=dtype, device=device))
-        self.register_buffer('v_cache', torch.zeros(cache_shape, dtype=dtype, device=device))
+        self.fp8, self.out_dtype = bool(fp8), dtype
+        store = torch.float8_e4m3fn if fp8 else dtype
+        self.register_buffer('k_cache', torch.zeros(cache_shape, dtype=store, device=device))
+        self.register_buffer('v_cache', torch.zeros(cache_shape, dtype=store, device=device))
+        if fp8:
+            for name in ("k_scale", "v_scale", "k_inv", "v_inv"):
+                self.register_buffer(name, torch.ones(n_heads, dtype=torch.float32, device=device))
+
+    def set_scales(self, k_scale, v_scale):
+        """new scales IN PLACE (the kernels read them from device memory: a captured graph sees them at its next replay)"""
+        assert self.fp8
+        self.k_scale.copy_(k_scale)
+        self.v_scale.copy_(v_scale)
+        self.k_inv.copy_(torch.reciprocal(self.k_scale))
+        self.v_inv.copy_(torch.reciprocal(self.v_scale))
+
+    def dequant(self, cache, scale):
+        """the read rule: value = float(code) * scale, handed on in the model's dtype"""
+        return (cache.float() * scale[:, None, None]).to(self.out_dtype)
 
     def update(self, input_pos, k_val, v_val):
         assert input_pos.shape[0] == k_val.shape[2]
+        if self.fp8:  # stored by the write rule, returned dequantised: the module forward restates what the HIP route computes
+            self.k_cache.view(torch.uint8)[:, :, input_pos] = fp8_quantize(k_val, self.k_inv)
+            self.v_cache.view(torch.uint8)[:, :, input_pos] = fp8_quantize(v_val, self.v_inv)
+            return self.dequant(self.k_cache, self.k_scale), self.dequant(self.v_cache, self.v_scale)
         k_out = self.k_cache
         v_out = self.v_cache
         k_out[:, :, input_pos] = k_val
@@ -388,6 +429,7 @@ class Transformer(nn.Module):
         self.output = nn.Linear(config.dim, config.vocab_size, bias=False)
         self.max_batch_size = -1
         self.max_seq_length = -1
+        self.kv_cache_dtype = "fp16"
         self.cache_initialized = False
         self.fuse_linears = fuse_linears
         self._native = None
@@ -411,9 +453,28 @@ class Transformer(nn.Module):
         return cls(dtype, ModelArgs.from_name(name), linear_class=linear_class, linear_kwargs=linear_kwargs,
                    halve_layers=halve_layers, fuse_linears=fuse_linears)
 
-    def setup_caches(self, max_batch_size, max_seq_length):
-        if self.max_seq_length >= max_seq_length and self.max_batch_size >= max_batch_size:
+    def kv8_unserved(self) -> Optional[str]:
+        """why the fused HIP route cannot serve this model with an fp8 KV cache (None: it can).  Host logic, no device needed."""
+        from .APLinear import APLinear
+        if not self.fuse_linears:
+            return "the model is not a fused-linear Any-Precision model"
+        if self.config.head_dim not in (64, 128):
+            return f"head_dim {self.config.head_dim} (the fp8 launches serve 64 and 128)"
+        if not all(isinstance(m, APLinear) for b in self.layers for m in (b.attention.wqkv, b.attention.wo, b.feed_forward.w1w3, b.feed_forward.w2)):
+            return "the linears are not Any-Precision linears"
+        if self.output.weight.dtype != torch.float16:
+            return "the model is not fp16"
+        return None
+
+    def setup_caches(self, max_batch_size, max_seq_length, kv_cache_dtype=None):
+        """kv_cache_dtype: None / "fp16" (the default: caches in the model's dtype) or "fp8" (e4m3 codes, a scale per layer and KV head,
+        `set_kv_scales`; served by the fused Any-Precision route and the module forward).  A change of the dtype re-allocates the caches
+        even when their size suffices."""
+        kv = kv_cache_dtype_name(kv_cache_dtype)
+        if self.max_seq_length >= max_seq_length and self.max_batch_size >= max_batch_size and kv == self.kv_cache_dtype:
             return
+        if kv == "fp8" and not self.fuse_linears and type(self.layers[0].attention.wq).__name__ == "QuantizedLinear":
+            raise NotImplementedError("fp8 KV cache: QTIP models keep the fp16 cache (gq_attn_decode_qtip has no fp8 form)")
         head_dim = self.config.head_dim
         max_seq_length = find_multiple(max_seq_length, 8)
         self.max_seq_length = max_seq_length
@@ -421,7 +482,8 @@ class Transformer(nn.Module):
         dtype = self.output.weight.dtype
         device = self.output.weight.device
         for b in self.layers:
-            b.attention.kv_cache = KVCache(max_batch_size, max_seq_length, self.config.n_local_heads, head_dim, dtype, device)
+            b.attention.kv_cache = KVCache(max_batch_size, max_seq_length, self.config.n_local_heads, head_dim, dtype, device, fp8=(kv == "fp8"))
+        self.kv_cache_dtype = kv
         # the [n, n] tables only for a cache of at most MASK_TABLE_MAX rows (tests and pipeline.py index them); above it every consumer
         # builds the rows it needs from the positions (mask_rows: the same bits)
         lw = self.config.layer_windows or ()
@@ -436,6 +498,24 @@ class Transformer(nn.Module):
                                                    rope_scaling=self.config.rope_scaling)
         self.cache_initialized = True
         self._reset_native()
+
+    def set_kv_scales(self, k: Tensor, v: Tensor) -> None:
+        """the scales of an fp8 cache, fp32 [n_layer][n_kv_head] each (value = code * scale; default 1.0), every entry finite and > 0.
+        Written in place into the caches' buffers, reciprocals with them: no re-allocation, a captured decode graph needs no re-capture.
+        Rows already in the caches keep their codes: set the scales before the prompt."""
+        if not (self.cache_initialized and self.kv_cache_dtype == "fp8"):
+            raise ValueError("set_kv_scales: the caches are not fp8 (setup_caches(.., kv_cache_dtype='fp8') first)")
+        shape = (len(self.layers), self.config.n_local_heads)
+        ts = []
+        for name, t in (("k", k), ("v", v)):
+            t = torch.as_tensor(t, dtype=torch.float32)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"set_kv_scales: {name} has shape {tuple(t.shape)}, expected [n_layer][n_kv_head] = {shape}")
+            if not bool((torch.isfinite(t) & (t > 0)).all()):
+                raise ValueError(f"set_kv_scales: every entry of {name} must be finite and > 0")
+            ts.append(t)
+        for i, b in enumerate(self.layers):
+            b.attention.kv_cache.set_scales(ts[0][i], ts[1][i])
 
     def forward(self, idx: Tensor, input_pos: Optional[Tensor] = None) -> Tensor:
         assert self.cache_initialized, "Caches must be initialized first"
@@ -560,8 +640,14 @@ class Transformer(nn.Module):
         mode = os.environ.get("GQ_PREFILL_ATTN", "auto")
         if mode not in ("auto", "0", "1"):
             raise ValueError(f"GQ_PREFILL_ATTN={mode!r}: auto, 0 or 1")
-        hip = mode != "0" and (mode == "1" or len(pieces) > 1) and bool(L.gq_attn_prefill_supported(H, Hkv, hd))
-        self.last_prefill_plan = dict(chunks=pieces, attn=["hip" if hip else "sdpa"] * len(self.layers))
+        kv8 = self.kv_cache_dtype == "fp8"
+        if kv8:  # (the fp8 cache: gq_attn_prefill_kv8 wherever it is supported, for any number of chunks; else SDPA on the dequantised rows)
+            assert self._native_kind() == "ap" and self.kv8_unserved() is None, self.kv8_unserved()
+            hip = mode != "0" and bool(L.gq_attn_prefill_supported(H, Hkv, hd))
+            self.last_prefill_plan = dict(chunks=pieces, attn=["hip-kv8" if hip else "sdpa-kv8"] * len(self.layers))
+        else:
+            hip = mode != "0" and (mode == "1" or len(pieces) > 1) and bool(L.gq_attn_prefill_supported(H, Hkv, hd))
+            self.last_prefill_plan = dict(chunks=pieces, attn=["hip" if hip else "sdpa"] * len(self.layers))
         dev = idx.device
         Sc = min(chunk, S)
         bufs = dict(xn=torch.empty((Sc, cfg.dim), dtype=torch.float16, device=dev), q=torch.empty((H * Sc * hd, ), dtype=torch.float16, device=dev),
@@ -604,6 +690,7 @@ class Transformer(nn.Module):
         rep = H // Hkv
         scale = 1.0 / math.sqrt(hd)
         qt = self._native_kind() == "qtip"  # QTIP: the linears through QuantizedLinear.forward (bs > 8: gq_qtip_gemm)
+        kv8 = self.kv_cache_dtype == "fp8"
         pending = None  # the previous block's MLP output: its residual add rides in the next RMSNorm launch
         with torch.cuda.device(x.device):
             st = _lib.current_stream_ptr()  # (the model's device's current stream: inside the guard)
@@ -617,7 +704,23 @@ class Transformer(nn.Module):
                 else:
                     qkv = att.wqkv(xn.view(1, S, D)).view(S, -1)
                 kc, vc = att.kv_cache.k_cache, att.kv_cache.v_cache
-                if cfg.qk_norm:  # (Qwen3: the per-head RMSNorm of q and k in front of the rotation, same launch)
+                if kv8:
+                    # the fp8 cache: ONE row-write launch for every layout (the norm weights ride along; a bias is already in the rows --
+                    # the quantized linear added it), then the fp8 instance of the prompt kernel
+                    kvc = att.kv_cache
+                    qn = (att.q_norm.weight.data_ptr(), att.k_norm.weight.data_ptr(), att.q_norm.eps) if cfg.qk_norm else (None, None, 0.0)
+                    _lib.check(L.gq_rope_cache_rows_kv8(qkv.data_ptr(), input_pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), q.data_ptr(),
+                                                        kc.data_ptr(), vc.data_ptr(), kvc.k_inv.data_ptr(), kvc.v_inv.data_ptr(), S, H, Hkv, hd, kc.shape[2],
+                                                        *qn, None, st), "gq_rope_cache_rows_kv8")
+                    if hip:
+                        _lib.check(L.gq_attn_prefill_kv8(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), kvc.k_scale.data_ptr(), kvc.v_scale.data_ptr(),
+                                                         y_hip.data_ptr(), S, start, H, Hkv, hd, kc.shape[2], scale, 0 if win is None else int(win), st),
+                                   "gq_attn_prefill_kv8")
+                        y = y_hip.view(1, S, H * hd)
+                    else:
+                        y = _sdpa_gqa(q.unsqueeze(0), kvc.dequant(kc[:1, :, :T], kvc.k_scale), kvc.dequant(vc[:1, :, :T], kvc.v_scale), sdpa_mask(win), rep)
+                        y = y.transpose(1, 2).reshape(1, S, H * hd)
+                elif cfg.qk_norm:  # (Qwen3: the per-head RMSNorm of q and k in front of the rotation, same launch)
                     _lib.check(L.gq_qknorm_rope_cache_rows(qkv.data_ptr(), input_pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(),
                                                            q.data_ptr(), kc.data_ptr(), vc.data_ptr(), S, H, Hkv, hd, kc.shape[2],
                                                            att.q_norm.weight.data_ptr(), att.k_norm.weight.data_ptr(), att.q_norm.eps, st),
@@ -625,7 +728,9 @@ class Transformer(nn.Module):
                 else:
                     _lib.check(L.gq_rope_cache_rows(qkv.data_ptr(), input_pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), q.data_ptr(),
                                                     kc.data_ptr(), vc.data_ptr(), S, H, Hkv, hd, kc.shape[2], st), "gq_rope_cache_rows")
-                if hip:  # (batch slot 0 of the caches; the output already in the row layout wo reads)
+                if kv8:
+                    pass  # (attended above)
+                elif hip:  # (batch slot 0 of the caches; the output already in the row layout wo reads)
                     _lib.check(L.gq_attn_prefill(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), y_hip.data_ptr(), S, start, H, Hkv, hd, kc.shape[2], scale,
                                                  0 if win is None else int(win), st), "gq_attn_prefill")
                     y = y_hip.view(1, S, H * hd)

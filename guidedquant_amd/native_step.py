@@ -75,6 +75,11 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+def kv_slot_bytes(n_kv_head, max_seq, head_dim, elem_size):
+    """bytes of one batch slot of a K (or V) cache [batch][n_kv_head][max_seq][head_dim]: elem_size 2 (fp16) or 1 (fp8)"""
+    return n_kv_head * max_seq * head_dim * elem_size
+
+
 class _Keyed:
     """state["x"] for state.x"""
 
@@ -128,11 +133,14 @@ class StepState(_Keyed):
         self.layer_split = [self.attn_split if w is None else plan(w) for w in self.layer_window]
         ns_max = max([self.attn_split] + self.layer_split)  # (one workspace, sized for the largest)
         self.attn_ws = torch.zeros(c.n_head * ns_max * (c.head_dim + 2), dtype=torch.float32, device=dev) if ns_max > 1 else None
+        # an fp8 KV cache (Transformer.setup_caches(.., kv_cache_dtype="fp8")): the rotated q of attend_kv8
+        self.kv8 = getattr(model, "kv_cache_dtype", "fp16") == "fp8"
+        self.q8 = torch.zeros(c.n_head * c.head_dim, **f16) if self.kv8 else None
 
     def kv(self, at, slot):
         """the K / V cache of batch slot `slot` of one attention module"""
         c = self.m.config
-        off = slot * c.n_local_heads * self.m.max_seq_length * c.head_dim * 2  # bytes per batch slot
+        off = slot * kv_slot_bytes(c.n_local_heads, self.m.max_seq_length, c.head_dim, at.kv_cache.k_cache.element_size())
         return at.kv_cache.k_cache.data_ptr() + off, at.kv_cache.v_cache.data_ptr() + off
 
     def attend(self, entry, src, pos, kv, sp, extra=(), layer=None):
@@ -148,6 +156,19 @@ class StepState(_Keyed):
             entry, extra = entry + "_window", (*extra, win)
         _lib.check(getattr(_lib.lib(), entry)(src, pos.data_ptr(), *rope, *kv, self.y.data_ptr(), c.n_head, c.n_local_heads, c.head_dim,
                                               m.max_seq_length, 1.0 / math.sqrt(c.head_dim), ns, _ptr(self.attn_ws), *extra, sp), entry)
+
+    def attend_kv8(self, at, pos, kv, sp, layer):
+        """the fp8 cache's route of one layer, behind the plain wqkv GEMV: gq_rope_cache_rows_kv8 (S = 1, the graph's position word; the
+        layer's norm weights or bias) rotates q into its own buffer and writes the cache row, gq_attn_decode_roped_kv8 attends it with the
+        layer's window and split plan.  One route for Llama, Mistral, Qwen2 and Qwen3; one launch per layer more than the fp16 routes."""
+        m, c, L, kvc = self.m, self.m.config, _lib.lib(), at.kv_cache
+        qn = (at.q_norm.weight.data_ptr(), at.k_norm.weight.data_ptr(), at.q_norm.eps) if c.qk_norm else (None, None, 0.0)
+        _lib.check(L.gq_rope_cache_rows_kv8(self.qkv.data_ptr(), pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), self.q8.data_ptr(), *kv,
+                                            kvc.k_inv.data_ptr(), kvc.v_inv.data_ptr(), 1, c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, *qn,
+                                            _ptr(at.wqkv.bias), sp), "gq_rope_cache_rows_kv8")
+        _lib.check(L.gq_attn_decode_roped_kv8(self.q8.data_ptr(), pos.data_ptr(), *kv, kvc.k_scale.data_ptr(), kvc.v_scale.data_ptr(), self.y.data_ptr(),
+                                              c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, 1.0 / math.sqrt(c.head_dim),
+                                              self.layer_split[layer], _ptr(self.attn_ws), self.layer_window[layer] or 0, sp), "gq_attn_decode_roped_kv8")
 
     def head(self, x):
         m, c = self.m, self.m.config
@@ -194,6 +215,8 @@ class ApStep(StepState):
         from .model import pair_gate_up_rows_
         super().__init__(model)
         c = model.config
+        if self.kv8 and model.kv8_unserved():
+            raise ValueError("fp8 KV cache: " + model.kv8_unserved())
         # workspace of the down projection where the library splits its rows along K over blocks (K > 16384: 70B)
         wb = max(int(_lib.lib().gq_anyprec_gemv_fused_ws_bytes(c.dim, c.intermediate_size, b.feed_forward.w2.bitwidth, 1)) for b in model.layers)
         if wb:
@@ -239,7 +262,10 @@ class ApStep(StepState):
             rope = (pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), *kv, c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length)
             # RoPE + KV-cache write in the epilogue of the wqkv GEMV, attention without them, where the library serves the layer's
             # wqkv that way (fast mode, 2-bit, K <= 4096: csrc/ap_stream.hip); else the two launches of rounds 1-3
-            if c.qk_norm:
+            if self.kv8:
+                launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
+                self.attend_kv8(at, pos, kv, sp, l0 + li)
+            elif c.qk_norm:
                 # Qwen3: q and k are normalised per head BEFORE the rotation, so the wqkv launch must not rotate (its RoPE epilogue holds a
                 # head's rows in eight 16-row groups: no per-head statistic there) -- plain wqkv GEMV, then ONE attention launch that
                 # normalises, rotates, writes the cache row and attends
@@ -523,6 +549,8 @@ class QtipStep(StepState):
 
     def __init__(self, model):
         super().__init__(model)
+        if self.kv8:
+            raise NotImplementedError("fp8 KV cache: QTIP models keep the fp16 cache (gq_attn_decode_qtip has no fp8 form)")
         c, dev = model.config, self.x.device
         self.g = torch.zeros(c.intermediate_size, dtype=torch.float16, device=dev)
         self.u = torch.zeros(c.intermediate_size, dtype=torch.float16, device=dev)

@@ -93,6 +93,8 @@ class PipelinedDecoder:
     def __init__(self, model, rank: int, world: int, layers: range, n_seq: Optional[int] = None, max_new_tokens: int = 100,
                  temperature: float = 0.0, top_k: Optional[int] = 32, bos_id: int = 1, native: Optional[bool] = None, group=None,
                  feedback_group=None, use_graphs: Optional[bool] = None, seed: int = 1234, hop: Optional[str] = None):
+        if getattr(model, "kv_cache_dtype", "fp16") == "fp8":  # (the stages address the cache slots themselves, two bytes per element)
+            raise NotImplementedError("fp8 KV cache: layer-pipelined decode has no fp8 form (setup_caches(.., kv_cache_dtype='fp16'))")
         if getattr(model.config, "layer_windows", None) is not None:  # (the stages build their masks and slots themselves)
             raise NotImplementedError("layer-pipelined decode has no sliding-window form (layer_windows)")
         self.model, self.rank, self.world, self.layers = model, rank, world, layers

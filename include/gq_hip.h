@@ -194,6 +194,39 @@ int gq_attn_prefill(const void *q, const void *k_cache, const void *v_cache, voi
                     uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t window, void *stream);
 
 /*
+ * The fp8 KV cache (kv_cache_dtype="fp8"): caches of OCP e4m3 codes, one byte per element, [n_kv_head][max_seq][head_dim] per batch
+ * slot, with fp32 scales per KV head in device memory (read by the kernels at every launch: new values need no re-capture).
+ *   write rule  code  = fp8_rne(clamp(float(x16) * inv, -448, 448)),  inv = 1 / scale computed by the host (no kernel divides);
+ *               x16 is the fp16 value the fp16 path would have stored.  The only rounding the format adds.  Non-finite x16: undefined.
+ *   read rule   value = float(code) * scale.  Every e4m3 value is an fp16 value, so the conversion is exact: the K scale is one factor
+ *               of the score (scale * k_scale[g]), the V scale multiplies the weighted sum in front of the division and the one fp16
+ *               rounding.  With scales that are powers of two the results equal, bit for bit, those of the fp16 entries on an fp16
+ *               cache that holds code * scale.
+ * gq_rope_cache_rows_kv8: gq_rope_cache_rows for S >= 1 rows (the prompt pass, and the decode step with S = 1 and pos the graph's device
+ *   word) into fp8 caches.  q_norm_weight / k_norm_weight (both or neither; eps): the rounding points of gq_qknorm_rope_cache_rows.
+ *   qkv_bias (fp16 [(n_head + 2 n_kv_head) head_dim]): one fp16 add on q, k and v in front of the rotation, as gq_attn_decode_split_bias.
+ *   Norm weights AND a bias: GQ_EINVAL.  q_out fp16 [n_head][S][head_dim], bit for bit what the fp16 entries write; a buffer of its
+ *   own (never qkv).  k_inv / v_inv: fp32 [n_kv_head] reciprocal scales.  Positions >= max_seq are not written.  head_dim 64 or 128
+ *   (GQ_ENOTSUP else, nothing written); all pointers 16-byte aligned.
+ * gq_attn_decode_roped_kv8: gq_attn_decode_roped (window = 0) / gq_attn_decode_roped_window (window >= 1) over fp8 caches that hold
+ *   every attended row, the current token's included (its dequantised value is what is attended: a result is a function of the cache
+ *   alone).  The same geometry, solo rule, split length, stream assignment and merge order (csrc/attn_core.h); one 8-byte load per lane
+ *   and row.  Partials reach the workspace multiplied by v_scale; the combine launch is the fp16 one.  *pos >= max_seq: NaN output.
+ * gq_attn_prefill_kv8: gq_attn_prefill over fp8 caches; tiles are converted to fp16 between the global load and LDS, so the LDS image
+ *   and both matrix products are those of gq_attn_prefill.  Governed by gq_attn_prefill_supported like it.
+ */
+int gq_rope_cache_rows_kv8(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
+                           void *v_cache, const float *k_inv, const float *v_inv, uint32_t S, uint32_t n_head, uint32_t n_kv_head,
+                           uint32_t head_dim, uint32_t max_seq, const void *q_norm_weight, const void *k_norm_weight, float eps,
+                           const void *qkv_bias, void *stream);
+int gq_attn_decode_roped_kv8(const void *q, const int *pos, const void *k_cache, const void *v_cache, const float *k_scale,
+                             const float *v_scale, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                             float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream);
+int gq_attn_prefill_kv8(const void *q, const void *k_cache, const void *v_cache, const float *k_scale, const float *v_scale, void *out,
+                        uint32_t S, uint32_t start, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale,
+                        uint32_t window, void *stream);
+
+/*
  * Host (CPU) twins of the two Any-Precision entry points: same arguments with HOST pointers, no stream; `nthreads` <= 0
  * uses the OpenMP default.  They serve BASELINE.json configs[0] ("CPU reference APLinear path via generate.py"): the module
  * semantics of inference/APLinear.py:35-60 with the tensors in host memory (the reference hard-codes 'cuda',
