@@ -473,6 +473,109 @@ class AnyPrecisionForCausalLM(nn.Module):
         finally:
             self.set_precision(prev_precision)
 
+    # -- scoring: log-likelihood and perplexity of given token ids ------------------------------------------------------
+    @staticmethod
+    def _score_rows(logits, targets, rows=512):
+        """(logprob fp32 [n], top1 [n]) of logits [n, V] and targets [n]: float -> log_softmax -> gather / argmax in blocks of `rows`
+        rows (the torch scoring head of Transformer._score_head; HF's loss upcasts the same way)"""
+        lps, tops = [], []
+        for a in range(0, logits.shape[0], rows):
+            ls = torch.nn.functional.log_softmax(logits[a:a + rows].float(), dim=-1)
+            lps.append(ls.gather(1, targets[a:a + rows, None])[:, 0])
+            tops.append(ls.argmax(dim=-1))
+        return torch.cat(lps), torch.cat(tops)
+
+    def score(self, input_ids, precision=None, kv_cache_dtype=None, native=None):
+        """Log-probabilities of one token sequence ([1, T] or [T], T >= 2): dict(logprobs fp32 [T - 1], greedy bool [T - 1], nll float)
+        with logprobs[i] = log p(ids[i + 1] | ids[:i + 1]), greedy[i] = (the most probable next token is ids[i + 1]) and nll the mean of
+        -logprobs -- the `outputs.loss` of the module tree for `labels=input_ids` (any_precision/evaluate/eval.py:222-223).
+        Routing follows `generate`: the fused decode model's HIP prompt pass with the scoring head (`Transformer.score_native`: no
+        [T, V] logits in memory) when the checkpoint has one at this precision and T fits its context, else the module tree's forward
+        and the same formula in torch.  native=False opts out, native=True raises instead of falling back, and
+        kv_cache_dtype="fp8" (the fused model's e4m3 cache) never falls back silently.  Ids outside [0, vocab) raise ValueError before
+        anything is launched."""
+        from .model import kv_cache_dtype_name
+        kv = kv_cache_dtype_name(kv_cache_dtype)
+        ids = torch.as_tensor(input_ids)
+        if ids.is_floating_point() or ids.dim() not in (1, 2) or (ids.dim() == 2 and ids.shape[0] != 1):
+            raise ValueError("score: input_ids must be one sequence of token ids, [1, T] or [T]")
+        ids = ids.reshape(-1)
+        T = int(ids.numel())
+        if T < 2:
+            raise ValueError("score: at least two tokens (the first one is only ever context)")
+        host = ids.cpu()
+        vocab = int(self.config.vocab_size)
+        if int(host.min()) < 0 or int(host.max()) >= vocab:
+            raise ValueError(f"score: token ids must lie in [0, {vocab})")
+        if kv == "fp8" and native is False:
+            raise ValueError("kv_cache_dtype='fp8': served by the fused decode model only (not with native=False)")
+        prev_precision = self.precision
+        if precision is not None:
+            self.set_precision(precision)
+        try:
+            dec, why = None, "opted out"
+            if native is not False:
+                if self.device.type != "cuda":
+                    why = "the fused routes need the GPU"
+                else:
+                    dec = self._native_decoder_or_none(self.precision, release_planes=native is True)
+                    why = getattr(self, "_no_native_reason", None) or "this checkpoint has no fused decode form at %d bits" % self.precision
+                    if dec is not None and T > dec.config.block_size:
+                        dec, why = None, f"{T} tokens exceed the fused model's context ({dec.config.block_size})"
+                    if dec is not None and kv == "fp8" and dec.kv8_unserved():
+                        dec, why = None, dec.kv8_unserved()
+                    if dec is not None and not dec.prefill_ready(ids.to(self.device).to(torch.int32)):
+                        dec, why = None, "the fused model's prompt pass does not serve this model"
+            if dec is None and kv == "fp8":
+                raise ValueError("kv_cache_dtype='fp8': " + why)
+            if dec is None and native is True:
+                raise ValueError("native=True: " + why)
+            if dec is not None:
+                # the caches sized as `_generate_native` sizes them, and like there allocated OUTSIDE inference mode (tensors made inside
+                # it refuse in-place updates elsewhere: set_kv_scales, the module forward's cache write); graphs captured over caches
+                # about to be replaced go first
+                cap = min(T if T > 16384 else max(256, 1 << (T - 1).bit_length()), dec.config.block_size)
+                if not (dec.max_seq_length >= cap and dec.max_batch_size >= 1 and dec.kv_cache_dtype == kv):
+                    self._evict("graph")
+                dec.setup_caches(1, cap, kv_cache_dtype=kv)
+            with torch.inference_mode():
+                if dec is not None:
+                    lp, greedy = dec.score_native(ids.to(self.device).to(torch.int32))
+                else:
+                    dev_ids = ids.to(self.device).long()
+                    logits = self.model(input_ids=dev_ids.view(1, -1)).logits[0, :-1]
+                    lp, top1 = self._score_rows(logits, dev_ids[1:])
+                    greedy = top1 == dev_ids[1:]
+            return dict(logprobs=lp, greedy=greedy, nll=float(-lp.double().mean()))
+        finally:
+            self.set_precision(prev_precision)
+
+    def perplexity(self, token_ids, chunk_size=2048, **score_kwargs):
+        """Perplexity of a 1-D token stream by the reference's definition (any_precision/evaluate/eval.py:205-226): the stream is cut
+        into len // chunk_size non-overlapping chunks (a shorter tail is dropped), each chunk's mean negative log-likelihood is taken
+        on its own (`score`; its first token is context only), and the result is exp of the mean of those means.
+        Returns dict(ppl, nll_per_chunk).  `score_kwargs` (precision, kv_cache_dtype, native) go to `score`."""
+        ids = torch.as_tensor(token_ids)
+        if ids.dim() != 1:
+            raise ValueError("perplexity: token_ids must be a 1-D stream of token ids")
+        chunk_size = int(chunk_size)
+        n = int(ids.numel()) // chunk_size if chunk_size >= 2 else 0
+        if n < 1:
+            raise ValueError(f"perplexity: chunk_size >= 2 and at least one whole chunk of {chunk_size} tokens")
+        nlls = [self.score(ids[i * chunk_size:(i + 1) * chunk_size], **score_kwargs)["nll"] for i in range(n)]
+        import math
+        return dict(ppl=math.exp(sum(nlls) / n), nll_per_chunk=nlls)
+
+    def loglikelihood(self, context_ids, continuation_ids, **score_kwargs):
+        """lm-eval's pair for a (context, continuation): (the sum of the continuation tokens' log-probabilities given everything in
+        front of them, whether every one of them is the model's most probable token), from ONE pass over context + continuation."""
+        ctx, cont = torch.as_tensor(context_ids).reshape(-1), torch.as_tensor(continuation_ids).reshape(-1)
+        if ctx.numel() < 1 or cont.numel() < 1:
+            raise ValueError("loglikelihood: a context and a continuation of at least one token each")
+        r = self.score(torch.cat([ctx.cpu(), cont.cpu()]), **score_kwargs)
+        k = int(cont.numel())
+        return float(r["logprobs"][-k:].double().sum()), bool(r["greedy"][-k:].all())
+
     # -- route 1: the fused decode model ---------------------------------------------------------------------------------
     _SAMPLER_SEED = 0x2545F491  # (a constant: what varies between sampled calls is the counter word, drawn from torch's generator)
 

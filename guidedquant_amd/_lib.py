@@ -28,7 +28,7 @@ EXPORTS = [
     "gq_attn_decode_split_qknorm", "gq_qknorm_rope_cache_rows", "gq_attn_decode_split_bias",
     "gq_attn_decode_split_window", "gq_attn_decode_split_qknorm_window", "gq_attn_decode_split_bias_window", "gq_attn_decode_roped_window",
     "gq_token_set_build", "gq_sample_topk_rep", "gq_attn_prefill_supported", "gq_attn_prefill",
-    "gq_rope_cache_rows_kv8", "gq_attn_decode_roped_kv8", "gq_attn_prefill_kv8",
+    "gq_rope_cache_rows_kv8", "gq_attn_decode_roped_kv8", "gq_attn_prefill_kv8", "gq_head_nll_ws_bytes", "gq_head_nll",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -149,6 +149,9 @@ def lib():
         L.gq_rope_cache_rows_kv8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, f32, vp, vp]
         L.gq_attn_decode_roped_kv8.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, u32, vp]
         L.gq_attn_prefill_kv8.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, f32, u32, vp]
+        # (the scoring head: xn, W, target, S, V, D, logprob, lse, top1, splits, ws, ws_bytes, stream)
+        L.gq_head_nll_ws_bytes.argtypes = [u32, u32, u32, u32]
+        L.gq_head_nll.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp, u32, vp, ctypes.c_size_t, vp]
         L.gq_anyprec_pack.argtypes = [vp, vp, u32, u32, i32, vp]
         L.gq_lnq_cd_block.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, vp]
         L.gq_debug_set_timing_buffer.argtypes = [vp]
@@ -175,11 +178,13 @@ def lib():
         for name in EXPORTS:
             if name in _VOID:
                 getattr(L, name).restype = None
-            elif name not in ("gq_last_error", "gq_anyprec_gemm_ws_bytes", "gq_anyprec_gemv_fused_ws_bytes", "gq_qtip_gemm_ws_bytes"):
+            elif name not in ("gq_last_error", "gq_anyprec_gemm_ws_bytes", "gq_anyprec_gemv_fused_ws_bytes", "gq_qtip_gemm_ws_bytes",
+                              "gq_head_nll_ws_bytes"):
                 getattr(L, name).restype = i32
         L.gq_anyprec_gemm_ws_bytes.restype = ctypes.c_size_t
         L.gq_anyprec_gemv_fused_ws_bytes.restype = ctypes.c_size_t
         L.gq_qtip_gemm_ws_bytes.restype = ctypes.c_size_t
+        L.gq_head_nll_ws_bytes.restype = ctypes.c_size_t
         L.gq_last_error.restype = ctypes.c_char_p
         _lib = L
     return _lib

@@ -627,6 +627,11 @@ class Transformer(nn.Module):
         pass where gq_attn_prefill_supported, torch SDPA everywhere else (a prompt of at most `chunk` tokens launches what it always
         did); "1" -- the kernel wherever it is supported; "0" -- never.  `last_prefill_plan` records what the pass did:
         dict(chunks=[(start, S), ..], attn=["hip" | "sdpa" per layer])."""
+        return self._prompt_pass(idx, input_pos, start, last_only, chunk)
+
+    def _prompt_pass(self, idx: Tensor, input_pos: Tensor, start: int, last_only: bool, chunk: Optional[int], score: Optional[dict] = None):
+        """the chunk loop of `prefill_native` (score None: its logits) and of `score_native` (score = dict(targets int32 [S], kernel bool):
+        every piece runs the scoring head on its rows; the list of the pieces' (logprob, top1))"""
         import os
         from . import _lib
         L = _lib.lib()
@@ -657,14 +662,19 @@ class Transformer(nn.Module):
         for a, n in pieces:
             o = a - start
             head = (not last_only) or a + n == start + S
-            r = self._prefill_piece(flat[o:o + n], input_pos[o:o + n], a, bufs, hip, head, last_only)
+            piece_score = None if score is None else dict(score, targets=score["targets"][o:o + n])
+            r = self._prefill_piece(flat[o:o + n], input_pos[o:o + n], a, bufs, hip, head, last_only, piece_score)
             if head:
                 out.append(r)
+        if score is not None:
+            return out
         return out[0] if len(out) == 1 else torch.cat(out, dim=1)
 
-    def _prefill_piece(self, idx: Tensor, input_pos: Tensor, start: int, bufs: dict, hip: bool, head: bool, last_only: bool):
+    def _prefill_piece(self, idx: Tensor, input_pos: Tensor, start: int, bufs: dict, hip: bool, head: bool, last_only: bool,
+                       score: Optional[dict] = None):
         """one piece of the prompt pass: S tokens at positions start .. start + S - 1 through every layer, attending the cache rows
-        [0, start + S); the logits ([1, 1 | S, V]) when `head`, else None"""
+        [0, start + S); the logits ([1, 1 | S, V]) when `head`, else None.  With `score` (the third head mode) the head is the scoring
+        head on the piece's rows and targets: (logprob fp32 [S], top1 int [S])"""
         from . import _lib
         L = _lib.lib()
         cfg = self.config
@@ -752,8 +762,69 @@ class Transformer(nn.Module):
         if not head:
             return None
         x = x + pending
+        if score is not None:
+            return self._score_head(x, score["targets"], score["kernel"])
         x = x[-1:] if last_only else x
         return self.output(self.norm(x)).view(1, -1, cfg.vocab_size)
+
+    SCORE_HEAD_ROWS = 512  # rows per block of the torch scoring head: its fp16 + fp32 logits are bounded by 512 x V x 6 bytes
+    # what GQ_SCORE_HEAD=auto takes where the kernel serves the shape: the kernel -- no slower than the torch head at both measured sizes
+    # (8B geometry: 3.2 against 3.6 ms at 2048 rows, 6.4 against 7.1 ms at 4096; profiles/score_head.json)
+    SCORE_HEAD_AUTO = "1"
+
+    def _score_head(self, x: Tensor, targets: Tensor, kernel: bool):
+        """the scoring head on the residual rows x fp16 [n, D] and targets int32 [n] (negative: ignored, logprob 0): (logprob fp32 [n],
+        top1 [n]).  Both forms read the fp16 rows norm(x) the logits head feeds to `self.output`: the kernel gq_head_nll
+        (csrc/head_nll.hip; no logits in memory), or output -> float -> log_softmax -> gather / argmax in blocks of SCORE_HEAD_ROWS rows."""
+        n, V = x.shape[0], self.config.vocab_size
+        if kernel:
+            from . import _lib
+            L = _lib.lib()
+            xn = self.norm(x).contiguous()
+            W = self.output.weight
+            assert xn.dtype == torch.float16 and W.dtype == torch.float16 and W.is_contiguous() and targets.dtype == torch.int32 and targets.numel() == n
+            lp = torch.empty(n, dtype=torch.float32, device=x.device)
+            top1 = torch.empty(n, dtype=torch.int32, device=x.device)
+            with torch.cuda.device(x.device):  # (the automatic split follows the compute units of the model's device: one guard for both calls)
+                nws = int(L.gq_head_nll_ws_bytes(n, V, xn.shape[1], 0))
+                ws = torch.empty(max(nws, 4), dtype=torch.uint8, device=x.device)
+                _lib.check(L.gq_head_nll(xn.data_ptr(), W.data_ptr(), targets.data_ptr(), n, V, xn.shape[1], lp.data_ptr(), None, top1.data_ptr(), 0,
+                                         ws.data_ptr(), nws, _lib.current_stream_ptr()), "gq_head_nll")
+            return lp, top1
+        lps, tops = [], []
+        for a in range(0, n, self.SCORE_HEAD_ROWS):
+            t = targets[a:a + self.SCORE_HEAD_ROWS].long()
+            ls = F.log_softmax(self.output(self.norm(x[a:a + self.SCORE_HEAD_ROWS])).float(), dim=-1)
+            lp = ls.gather(1, t.clamp(min=0)[:, None])[:, 0]
+            lps.append(torch.where(t >= 0, lp, torch.zeros_like(lp)))
+            tops.append(ls.argmax(dim=-1).to(torch.int32))
+        return torch.cat(lps), torch.cat(tops)
+
+    def score_native(self, idx: Tensor, chunk: Optional[int] = None):
+        """Log-probabilities of a token sequence on the HIP prompt pass: (logprob fp32 [S - 1], greedy bool [S - 1]) with
+        logprob[i] = log p(idx[i + 1] | idx[:i + 1]) and greedy[i] = (the most probable next token == idx[i + 1]) -- what the module tree's
+        `labels=` loss and lm-eval's loglikelihood are made of.  The pass is `prefill_native`'s from position 0 (the same pieces, caches,
+        GQ_PREFILL_CHUNK and GQ_PREFILL_ATTN; everything `prefill_ready` serves, the fp8 cache included) with the scoring head on every
+        piece, so no [S, V] logits exist.  GQ_SCORE_HEAD: "1" the kernel gq_head_nll, "0" the torch head in blocks of 512 rows, "auto"
+        (default) SCORE_HEAD_AUTO where the kernel serves the shape (dim % 64 == 0, fp16) and the torch head elsewhere.
+        `last_prefill_plan["head"]` records it ("hip-nll" | "torch").  The caches hold the sequence afterwards, as after a prompt."""
+        import os
+        flat = idx.reshape(-1)
+        S = flat.numel()
+        assert self.prefill_ready(idx) and 2 <= S <= self.max_seq_length
+        mode = os.environ.get("GQ_SCORE_HEAD", "auto")
+        if mode not in ("auto", "0", "1"):
+            raise ValueError(f"GQ_SCORE_HEAD={mode!r}: auto, 0 or 1")
+        served = self.config.dim % 64 == 0 and self.output.weight.dtype == torch.float16  # (else the kernel answers GQ_ENOTSUP)
+        kernel = mode == "1" or (mode == "auto" and served and self.SCORE_HEAD_AUTO == "1")
+        flat = flat.to(torch.int32)
+        targets = torch.cat([flat[1:], torch.full((1, ), -1, dtype=torch.int32, device=flat.device)])
+        pos = torch.arange(0, S, device=flat.device, dtype=torch.int32)
+        out = self._prompt_pass(flat, pos, 0, False, chunk, score=dict(targets=targets, kernel=kernel))
+        self.last_prefill_plan["head"] = "hip-nll" if kernel else "torch"
+        lp = torch.cat([o[0] for o in out])[:S - 1]
+        top1 = torch.cat([o[1] for o in out])[:S - 1]
+        return lp, top1 == flat[1:]
 
     def decode_native(self, tok: Tensor, pos: Tensor) -> Tensor:
         """One bs=1 decode step.  tok, pos: int32 device tensors with one element.  Returns logits fp16 [1,1,V]

@@ -200,6 +200,9 @@ class PipelinedDecoder:
                           seq_tok=base + self._fg_layout["seq_tok"])
         dist.barrier(group=self.group)  # every mapping is open before anybody may free or reuse
 
+    def score_native(self, *args, **kwargs):
+        raise NotImplementedError("pipelined scoring is not implemented: score on one device (Transformer.score_native)")
+
     def close_ipc(self):
         """unmap the peer's slots and free this stage's (after a barrier of the caller's: nobody may still be sending)"""
         from . import _lib

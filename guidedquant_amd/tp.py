@@ -138,6 +138,9 @@ class TensorParallelDecoder:
             self._peer[q] = base
         dist.barrier(group=self.group)
 
+    def score_native(self, *args, **kwargs):
+        raise NotImplementedError("tensor-parallel scoring is not implemented: score on one device (Transformer.score_native)")
+
     def close(self):
         for m in self._maps:
             self.L.gq_hop_close(m)

@@ -227,6 +227,26 @@ int gq_attn_prefill_kv8(const void *q, const void *k_cache, const void *v_cache,
                         uint32_t window, void *stream);
 
 /*
+ * The scoring head of the prompt pass: per-token log-probabilities without the logits (csrc/head_nll.hip).  What the reference's
+ * perplexity loop computes with the module tree and `labels=` (any_precision/evaluate/eval.py:205-226: lm_head logits [1, S, V] in
+ * fp16, HF's loss upcasts them to fp32 and takes the cross entropy) from the rows behind the final RMSNorm, in one pass over the
+ * vocabulary:
+ *   xn fp16 [S][D], W fp16 [V][D] (output.weight as stored), target int [S]
+ *   logit[s][v] = fp16(sum_k xn[s][k] W[v][k])     fp32 accumulation, ONE rounding: where the fp16 lm_head rounds
+ *   lse[s]      = log sum_v exp(logit[s][v])       fp32
+ *   logprob[s]  = logit[s][target[s]] - lse[s]     exactly 0.0f for a negative target ("ignored"); a target >= V is the caller's error
+ *   top1[s]     = the lowest id among the largest fp16 logits
+ * lse and top1 may be NULL.  Any S >= 1 and V >= 1 (odd V included: only whole rows of W are ragged); D % 64 == 0, else GQ_ENOTSUP.
+ * The vocabulary is cut into `splits` ranges of whole 128-row tiles, one block per (128 sequence rows, range); splits == 0 lets the
+ * library choose, splits >= 1 forces that many (a range without a tile contributes the neutral element).  The partials -- five words
+ * per (row, range) -- go through `ws` (gq_head_nll_ws_bytes for the same S, V, D, splits; smaller: GQ_EINVAL; left as found otherwise)
+ * and a second launch folds them in ascending range order: the results depend on `splits`, never on the run.
+ */
+size_t gq_head_nll_ws_bytes(uint32_t S, uint32_t V, uint32_t D, uint32_t splits);
+int gq_head_nll(const void *xn, const void *W, const int *target, uint32_t S, uint32_t V, uint32_t D, float *logprob, float *lse,
+                int *top1, uint32_t splits, void *ws, size_t ws_bytes, void *stream);
+
+/*
  * Host (CPU) twins of the two Any-Precision entry points: same arguments with HOST pointers, no stream; `nthreads` <= 0
  * uses the OpenMP default.  They serve BASELINE.json configs[0] ("CPU reference APLinear path via generate.py"): the module
  * semantics of inference/APLinear.py:35-60 with the tensors in host memory (the reference hard-codes 'cuda',
