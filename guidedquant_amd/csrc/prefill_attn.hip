@@ -14,9 +14,19 @@
 //                  32 (b >> 1) + 8 (row >> 2) + 4 (b & 1) + (row & 3): lane group g = l >> 4 then holds, in blocks 2c and 2c + 1, the
 //                  EIGHT CONSECUTIVE keys 32 c + 8 g .. + 7 of its query -- exactly the B fragment of k-step c of the second product.
 //   O^T = V^T P^T  A = V^T through ds_read_b64_tr_b16 on the row-major image (two reads of 4 keys x 16 columns per fragment),
-//                  B = P^T = exp2 of the scores, rounded to fp16, straight from the accumulators.
+//                  B = P^T = exp2 of the scores, rounded to fp16 AT THE SCALE 2^PK, straight from the accumulators.
 // The online softmax is fp32 with scale * log2(e) folded into one multiply and v_exp_f32; a masked score is REPLACED (select), a
 // masked P is exactly 0, and a row that has seen only masked keys so far keeps sum 0 (its running maximum stays at NEG, finite).
+// P = exp2(s - m) <= 1 is taken as exp2(s - (m - PK)) = P 2^PK <= 32768 (PK = 15: one subtraction per tile), the numerator AND the
+// normaliser accumulate the scaled weights, and o / l is what it was: a power of two moves through every step exactly.  Unscaled, a
+// weight under 2^-14 was an fp16 subnormal and one under 2^-25 exactly 0 in the numerator while the fp32 normaliser kept it: behind a
+// large first key (an attention sink) T keys of weight just under 2^-25 lost T 2^-25 of the softmax with one sign -- 0.4 % of max|V|
+// at 2^17 keys, twice that at 2^18, where the decode kernels (fp32 weights, attn_core.h) lose nothing.  Scaled, the flush sits at
+// 2^-40 relative to the row maximum and every weight above 2^-29 is a normal fp16 number.
+// Error against float64, elementwise, over T keys: (4 2^-11 + (T / 32 + T / 64) 2^-24) max|V| -- P's fp16 rounding in the numerator
+// (2^-11 relative) and at most as much in the normaliser, the output's own fp16 rounding, one fp32 rounding of the accumulator per MFMA
+// (32 keys) and one of a lane's normaliser share per tile, taken with one sign (tests/prefill_attn_model.py error_bound).  The sums
+// stay far inside fp32: l <= 2^15 T / 4 per lane, |o| <= 2^15 T max|V|, T <= 2^30.
 // Tiles wholly above the diagonal or below the window are never visited by the block, a wave skips the visited ones it has no
 // key in, and only tiles astride an edge evaluate the element mask.  Rows >= start + S of a tile are not read: they are staged as
 // zeros (0 x NaN inside an MFMA is NaN), so nothing at or behind row max_seq is touched.  The tile loops hold no integer division.
@@ -35,6 +45,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr u32 BQ = GQ_PREFILL_ATTN_BQ, BK = GQ_PREFILL_ATTN_BK;
 static_assert(BQ == 64 && BK == 64, "4 waves x 16 query rows; 4 score blocks of 16 keys");
 constexpr float NEG = -1.0e30f;  // a masked score: finite, so NEG - NEG = 0 and never Inf - Inf
+constexpr float PK = 15.0f;      // P is rounded to fp16 as P 2^PK (<= 32768 < 65504)
 
 __device__ __forceinline__ h16x4 lds_read_tr(const h16 *p) {
     typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
@@ -130,7 +141,7 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
     f32x4 o[DB];
 #pragma unroll
     for (u32 d = 0; d < DB; d++) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run = NEG, l_run = 0.f;  // l_run: this lane's share of the row sum (the four lane groups of a query are added at the end)
+    float m_run = NEG, l_run = 0.f;  // l_run: this lane's share of the row sum of P 2^PK (the four lane groups of a query are added at the end)
 
     load_tile(kt0);
     for (u32 kt = kt0; kt <= kt1; kt++) {
@@ -179,13 +190,14 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
         const float m_new = fmaxf(m_run, mloc);
         const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
         m_run = m_new;
+        const float m_pk = m_new - PK;  // (NEG - PK = NEG: a row of masked keys only is unchanged)
         float psum = 0.f;
         h16x8 pf[2];
 #pragma unroll
         for (u32 b = 0; b < 4; b++) {
 #pragma unroll
             for (u32 r = 0; r < 4; r++) {
-                const float pe = ok[b][r] ? __builtin_amdgcn_exp2f(s[b][r] - m_new) : 0.f;
+                const float pe = ok[b][r] ? __builtin_amdgcn_exp2f(s[b][r] - m_pk) : 0.f;
                 psum += pe;
                 pf[b >> 1][4u * (b & 1u) + r] = (h16)pe;
             }

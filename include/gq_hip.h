@@ -181,7 +181,8 @@ int gq_silu_mul_rows(const void *y, void *out, uint32_t S, uint32_t inter, int p
  *   out      fp16 [S][n_head * head_dim]          the rows wo reads
  * Query row i has position p = start + i and attends the cache rows t <= p, with window != 0 also t > p - window (window 0: the
  * whole context).  start + S <= max_seq (GQ_EINVAL else); rows >= start + S of the caches may hold anything and are not read.
- * softmax(scale * q k^T) in fp32, P rounded to fp16 in front of P V:  |out - exact| <= 2^-9 max|V| at a few hundred keys.
+ * softmax(scale * q k^T) in fp32, P rounded to fp16 in front of P V at the scale 2^15 (a weight flushes to 0 only under 2^-40 of the
+ * row's largest):  |out - exact| <= (2^-9 + (T / 32 + T / 64) 2^-24) max|V| over T = start + S keys.
  * gq_attn_prefill_supported (host logic, launches nothing): 1 for head_dim 64 / 128 and n_head a multiple of n_kv_head (any group
  * size), else 0 -- gq_attn_prefill then returns GQ_ENOTSUP and writes nothing.  All pointers 16-byte aligned.
  * Key tiles of GQ_PREFILL_ATTN_BK rows per block of GQ_PREFILL_ATTN_BQ query rows and one head; tiles wholly above the diagonal or
