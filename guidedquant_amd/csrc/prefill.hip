@@ -110,118 +110,6 @@ __device__ __forceinline__ void rope_unit(const uint4 a, const uint4 b, const ui
     }
 }
 
-// qkv [S][(H + 2 Hkv) HD] -> q_out [H][S][HD] (rotated), k_cache / v_cache [Hkv][max_seq][HD] at pos[s] (k rotated).
-// One thread per (token, head of q | k | v, 8 elements of the FIRST half): it owns elements d .. d + 7 and d + HD / 2 ..
-__global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__restrict__ qkv, const int *__restrict__ pos,
-                                                              const uint16_t *__restrict__ cos_t, const uint16_t *__restrict__ sin_t,
-                                                              uint16_t *__restrict__ q_out, uint16_t *__restrict__ kc, uint16_t *__restrict__ vc,
-                                                              u32 S, u32 H, u32 Hkv, u32 HD, u32 max_seq) {
-    const u32 upr = HD / 16u, heads = H + 2u * Hkv, total = S * heads * upr;  // units of 8 in the first half
-    for (u32 i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-        const u32 u = i % upr, hh = (i / upr) % heads, s = i / (upr * heads), d = 8u * u;
-        const u32 p = (u32)pos[s];
-        const uint16_t *src = qkv + (size_t)s * heads * HD + (size_t)hh * HD;
-        const uint4 a = *reinterpret_cast<const uint4 *>(src + d), b = *reinterpret_cast<const uint4 *>(src + d + HD / 2u);
-        if (hh >= H + Hkv) {  // v: copied
-            if (p < max_seq) {
-                uint16_t *dst = vc + ((size_t)(hh - H - Hkv) * max_seq + p) * HD;
-                *reinterpret_cast<uint4 *>(dst + d) = a;
-                *reinterpret_cast<uint4 *>(dst + d + HD / 2u) = b;
-            }
-            continue;
-        }
-        u32 o1[4], o2[4];
-        rope_unit(a, b, cos_t, sin_t, p, max_seq, HD, d, o1, o2);
-        uint16_t *dst;
-        if (hh < H) {
-            dst = q_out + ((size_t)hh * S + s) * HD;
-        } else {
-            if (p >= max_seq) continue;
-            dst = kc + ((size_t)(hh - H) * max_seq + p) * HD;
-        }
-        *reinterpret_cast<uint4 *>(dst + d) = make_uint4(o1[0], o1[1], o1[2], o1[3]);
-        *reinterpret_cast<uint4 *>(dst + d + HD / 2u) = make_uint4(o2[0], o2[1], o2[2], o2[3]);
-    }
-}
-
-// The same with Qwen3's per-head RMSNorm of q and k in front of the rotation (modeling_qwen3.Qwen3Attention.forward: q_norm / k_norm =
-// Qwen3RMSNorm over head_dim, weights [HD] shared by the heads): the HD / 16 threads of a (token, head) are neighbouring lanes of one
-// wave; each adds the squares of its 16 values in fp32, an xor butterfly over the group gives every lane the same sum, then
-// (x.float() * rsqrt(ssq / HD + eps)).half() * weight -- the rounding points of gq_rmsnorm_rows -- and the rotation above.  v is copied.
-// The loop bound is block-uniform (whole groups are active or idle together: total is a multiple of HD / 16 <= 8).
-__global__ void __launch_bounds__(256) qknorm_rope_cache_rows_kernel(const uint16_t *__restrict__ qkv, const int *__restrict__ pos,
-                                                                     const uint16_t *__restrict__ cos_t, const uint16_t *__restrict__ sin_t,
-                                                                     uint16_t *__restrict__ q_out, uint16_t *__restrict__ kc, uint16_t *__restrict__ vc,
-                                                                     const uint16_t *__restrict__ qnw, const uint16_t *__restrict__ knw, float eps,
-                                                                     u32 S, u32 H, u32 Hkv, u32 HD, u32 max_seq) {
-    const u32 upr = HD / 16u, heads = H + 2u * Hkv, total = S * heads * upr;
-    for (u32 base = blockIdx.x * 256u; base < total; base += gridDim.x * 256u) {
-        const u32 i = base + threadIdx.x;
-        const bool active = i < total;
-        const u32 ic = active ? i : 0u;
-        const u32 u = ic % upr, hh = (ic / upr) % heads, s = ic / (upr * heads), d = 8u * u;
-        const u32 p = (u32)pos[s];
-        const uint16_t *src = qkv + (size_t)s * heads * HD + (size_t)hh * HD;
-        uint4 a = *reinterpret_cast<const uint4 *>(src + d), b = *reinterpret_cast<const uint4 *>(src + d + HD / 2u);
-        const u32 x1[4] = {a.x, a.y, a.z, a.w}, x2[4] = {b.x, b.y, b.z, b.w};
-        float ss = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const float f0 = h2f((uint16_t)(x1[e] & 0xFFFF)), f1 = h2f((uint16_t)(x1[e] >> 16));
-            ss += f0 * f0;
-            ss += f1 * f1;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const float f0 = h2f((uint16_t)(x2[e] & 0xFFFF)), f1 = h2f((uint16_t)(x2[e] >> 16));
-            ss += f0 * f0;
-            ss += f1 * f1;
-        }
-        for (u32 sh = 1u; sh < upr; sh <<= 1) ss += __shfl_xor(ss, (int)sh, 64);  // (upr is wave-uniform: 4 or 8 lanes, aligned)
-        if (!active) continue;
-        if (hh >= H + Hkv) {  // v: copied
-            if (p < max_seq) {
-                uint16_t *dst = vc + ((size_t)(hh - H - Hkv) * max_seq + p) * HD;
-                *reinterpret_cast<uint4 *>(dst + d) = a;
-                *reinterpret_cast<uint4 *>(dst + d + HD / 2u) = b;
-            }
-            continue;
-        }
-        const float rs = rsqrtf(ss / (float)HD + eps);
-        const uint16_t *wn = hh < H ? qnw : knw;
-        const uint4 w1 = *reinterpret_cast<const uint4 *>(wn + d), w2 = *reinterpret_cast<const uint4 *>(wn + d + HD / 2u);
-        const u32 ww1[4] = {w1.x, w1.y, w1.z, w1.w}, ww2[4] = {w2.x, w2.y, w2.z, w2.w};
-        u32 n1[4], n2[4];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            u32 r1 = 0, r2 = 0;
-#pragma unroll
-            for (int k = 0; k < 2; k++) {
-                const u32 sh = 16u * (u32)k;
-                const h16 v1 = (h16)(h2f((uint16_t)(x1[e] >> sh)) * rs) * hbits((uint16_t)(ww1[e] >> sh));
-                const h16 v2 = (h16)(h2f((uint16_t)(x2[e] >> sh)) * rs) * hbits((uint16_t)(ww2[e] >> sh));
-                r1 |= (u32)bitsh(v1) << sh;
-                r2 |= (u32)bitsh(v2) << sh;
-            }
-            n1[e] = r1, n2[e] = r2;
-        }
-        a = make_uint4(n1[0], n1[1], n1[2], n1[3]);
-        b = make_uint4(n2[0], n2[1], n2[2], n2[3]);
-        u32 o1[4], o2[4];
-        rope_unit(a, b, cos_t, sin_t, p, max_seq, HD, d, o1, o2);
-        uint16_t *dst;
-        if (hh < H) {
-            dst = q_out + ((size_t)hh * S + s) * HD;
-        } else {
-            if (p >= max_seq) continue;
-            dst = kc + ((size_t)(hh - H) * max_seq + p) * HD;
-        }
-        *reinterpret_cast<uint4 *>(dst + d) = make_uint4(o1[0], o1[1], o1[2], o1[3]);
-        *reinterpret_cast<uint4 *>(dst + d + HD / 2u) = make_uint4(o2[0], o2[1], o2[2], o2[3]);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ fp8 (e4m3) KV cache
 // 8 fp16 values (4 words) -> 8 OCP e4m3 codes by THE write rule of the fp8 cache, the only rounding the format adds:
 //   code = fp8_rne(clamp(float(x16) * inv, -448, 448))
 // inv = 1 / scale of the KV head, an fp32 the host computed (no division here).  The clamp is explicit (v_med3_f32): v_cvt_pk_fp8_f32
@@ -242,19 +130,49 @@ __device__ __forceinline__ uint2 fp8_quant8(const u32 (&w)[4], float inv) {
     return make_uint2(o[0], o[1]);
 }
 
-// rope_cache_rows_kernel / qknorm_rope_cache_rows_kernel for caches of one byte per element: the same thread units, the same fp16
-// values up to the store -- q_out is bit for bit what the fp16 kernels write -- and k / v stored by fp8_quant8 with the reciprocal
-// scale of their KV head.  QKN: the per-head RMSNorm of q and k in front of the rotation (the block above).  QB: the bias of the q / k / v
-// linears (fp16, laid out like a qkv row), ONE fp16 add in front of the rotation (decode.hip, AttnBias).  The loop has the block-uniform
-// bound of the QK-norm kernel in every form.
-template <bool QKN, bool QB>
-__global__ void __launch_bounds__(256) rope_cache_rows_kv8_kernel(const uint16_t *__restrict__ qkv, const int *__restrict__ pos,
-                                                                  const uint16_t *__restrict__ cos_t, const uint16_t *__restrict__ sin_t,
-                                                                  uint16_t *__restrict__ q_out, uint8_t *__restrict__ kc, uint8_t *__restrict__ vc,
-                                                                  const float *__restrict__ k_inv, const float *__restrict__ v_inv,
-                                                                  const uint16_t *__restrict__ qnw, const uint16_t *__restrict__ knw, float eps,
-                                                                  const uint16_t *__restrict__ bias, u32 S, u32 H, u32 Hkv, u32 HD, u32 max_seq) {
-    const u32 upr = HD / 16u, heads = H + 2u * Hkv, total = S * heads * upr;
+// a thread's two units (elements d .. d + 7 and d + HD / 2 .. of a head's row `dst`): as they are into an fp16 row (q_out, an fp16
+// cache), by fp8_quant8 with the reciprocal scale of the KV head into a row of one byte per element
+template <typename E>
+__device__ __forceinline__ void store_units(E *dst, u32 d, u32 HD, const u32 (&w1)[4], const u32 (&w2)[4], float inv) {
+    if constexpr (sizeof(E) == 1) {
+        *reinterpret_cast<uint2 *>(dst + d) = fp8_quant8(w1, inv);
+        *reinterpret_cast<uint2 *>(dst + d + HD / 2u) = fp8_quant8(w2, inv);
+    } else {
+        *reinterpret_cast<uint4 *>(dst + d) = make_uint4(w1[0], w1[1], w1[2], w1[3]);
+        *reinterpret_cast<uint4 *>(dst + d + HD / 2u) = make_uint4(w2[0], w2[1], w2[2], w2[3]);
+    }
+}
+
+template <bool KV8>
+struct CacheElem {
+    typedef uint16_t type;
+};
+template <>
+struct CacheElem<true> {
+    typedef uint8_t type;
+};
+
+// THE row write of the prompt pass (and of the fp8 decode step, S = 1), one kernel for every layout:
+//   qkv [S][(H + 2 Hkv) HD] -> q_out [H][S][HD] (rotated), k_cache / v_cache [Hkv][max_seq][HD] at pos[s] (k rotated).
+// One thread per (token, head of q | k | v, 8 elements of the FIRST half): it owns elements d .. d + 7 and d + HD / 2 ..
+// KV8: caches of one byte per element -- the same fp16 values up to the store (q_out is bit for bit what the fp16 form writes), k / v
+//   stored by fp8_quant8 with the reciprocal scale of their KV head (k_inv / v_inv: read in this form only).
+// QKN: Qwen3's per-head RMSNorm of q and k in front of the rotation (modeling_qwen3.Qwen3Attention.forward: q_norm / k_norm =
+//   Qwen3RMSNorm over head_dim, weights [HD] shared by the heads): the HD / 16 threads of a (token, head) are neighbouring lanes of one
+//   wave; each adds the squares of its 16 values in fp32, an xor butterfly over the group gives every lane the same sum, then
+//   (x.float() * rsqrt(ssq / HD + eps)).half() * weight -- the rounding points of gq_rmsnorm_rows -- and the rotation.  v is not normed.
+// QB: the bias of the q / k / v linears (fp16, laid out like a qkv row), ONE fp16 add in front of the rotation (decode.hip, AttnBias).
+//   Only the fp8 decode step has it: the prompt pass's linears add the bias themselves, so no fp16 form is instantiated.
+// The loop bound is block-uniform in every form (QKN needs it: whole groups are active or idle together, total is a multiple of HD / 16).
+template <bool QKN, bool QB, bool KV8>
+__global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__restrict__ qkv, const int *__restrict__ pos,
+                                                              const uint16_t *__restrict__ cos_t, const uint16_t *__restrict__ sin_t,
+                                                              uint16_t *__restrict__ q_out, typename CacheElem<KV8>::type *__restrict__ kc,
+                                                              typename CacheElem<KV8>::type *__restrict__ vc, const float *__restrict__ k_inv,
+                                                              const float *__restrict__ v_inv, const uint16_t *__restrict__ qnw,
+                                                              const uint16_t *__restrict__ knw, float eps, const uint16_t *__restrict__ bias, u32 S,
+                                                              u32 H, u32 Hkv, u32 HD, u32 max_seq) {
+    const u32 upr = HD / 16u, heads = H + 2u * Hkv, total = S * heads * upr;  // units of 8 in the first half
     for (u32 base = blockIdx.x * 256u; base < total; base += gridDim.x * 256u) {
         const u32 i = base + threadIdx.x;
         const bool active = i < total;
@@ -297,13 +215,12 @@ __global__ void __launch_bounds__(256) rope_cache_rows_kv8_kernel(const uint16_t
             for (u32 sh = 1u; sh < upr; sh <<= 1) ss += __shfl_xor(ss, (int)sh, 64);  // (upr is wave-uniform: 4 or 8 lanes, aligned)
         }
         if (!active) continue;
-        if (hh >= H + Hkv) {  // v: quantised as it is
+        if (hh >= H + Hkv) {  // v: stored as it is
             if (p < max_seq) {
                 const u32 g = hh - H - Hkv;
-                uint8_t *dst = vc + ((size_t)g * max_seq + p) * HD;
-                const float inv = v_inv[g];
-                *reinterpret_cast<uint2 *>(dst + d) = fp8_quant8(x1, inv);
-                *reinterpret_cast<uint2 *>(dst + d + HD / 2u) = fp8_quant8(x2, inv);
+                float inv = 0.f;
+                if constexpr (KV8) inv = v_inv[g];
+                store_units(vc + ((size_t)g * max_seq + p) * HD, d, HD, x1, x2, inv);
             }
             continue;
         }
@@ -331,15 +248,12 @@ __global__ void __launch_bounds__(256) rope_cache_rows_kv8_kernel(const uint16_t
         u32 o1[4], o2[4];
         rope_unit(a, b, cos_t, sin_t, p, max_seq, HD, d, o1, o2);
         if (hh < H) {
-            uint16_t *dst = q_out + ((size_t)hh * S + s) * HD;
-            *reinterpret_cast<uint4 *>(dst + d) = make_uint4(o1[0], o1[1], o1[2], o1[3]);
-            *reinterpret_cast<uint4 *>(dst + d + HD / 2u) = make_uint4(o2[0], o2[1], o2[2], o2[3]);
+            store_units(q_out + ((size_t)hh * S + s) * HD, d, HD, o1, o2, 0.f);
         } else if (p < max_seq) {
             const u32 g = hh - H;
-            uint8_t *dst = kc + ((size_t)g * max_seq + p) * HD;
-            const float inv = k_inv[g];
-            *reinterpret_cast<uint2 *>(dst + d) = fp8_quant8(o1, inv);
-            *reinterpret_cast<uint2 *>(dst + d + HD / 2u) = fp8_quant8(o2, inv);
+            float inv = 0.f;
+            if constexpr (KV8) inv = k_inv[g];
+            store_units(kc + ((size_t)g * max_seq + p) * HD, d, HD, o1, o2, inv);
         }
     }
 }
@@ -380,6 +294,48 @@ __global__ void __launch_bounds__(256) silu_mul_rows_kernel(const uint16_t *__re
         *reinterpret_cast<uint4 *>(out + (size_t)s * I + 8u * u) = make_uint4(o[0], o[1], o[2], o[3]);
     }
 }
+
+// what the three entries of the row write do not share behind their null checks: the head_dims served and the texts of the failures
+// (literals: callers compare gq_last_error)
+struct RowsEntry {
+    bool any_hd16;  // every head_dim % 16 == 0 (no group of lanes adds a statistic), else 64 and 128
+    const char *bad_hd, *unaligned, *too_large;
+};
+
+// the checks from `S == 0` on, the grid rule and the launch of rope_cache_rows_kernel<QKN, QB, KV8>: the norm form with norm weights,
+// the bias form with a bias, the fp8 form with `kv8` (k_inv / v_inv are read by that form only)
+int rope_cache_rows(const RowsEntry &e, bool kv8, const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
+                    void *v_cache, const float *k_inv, const float *v_inv, u32 S, u32 n_head, u32 n_kv_head, u32 head_dim, u32 max_seq,
+                    const void *q_norm_weight, const void *k_norm_weight, float eps, const void *qkv_bias, void *stream) {
+    if (S == 0) return GQ_OK;
+    // (QKN: the statistic of a head is added inside an aligned group of head_dim / 16 lanes: a power of two, within one wave)
+    const bool hd_ok = e.any_hd16 ? (head_dim != 0 && head_dim % 16u == 0) : (head_dim == 64u || head_dim == 128u);
+    if (!hd_ok || n_head == 0 || n_kv_head == 0 || max_seq == 0) return gq_fail(GQ_ENOTSUP, e.bad_hd);
+    if (((uintptr_t)qkv | (uintptr_t)cos_table | (uintptr_t)sin_table | (uintptr_t)q_out | (uintptr_t)k_cache | (uintptr_t)v_cache |
+         (uintptr_t)q_norm_weight | (uintptr_t)k_norm_weight | (uintptr_t)qkv_bias) & 15u)
+        return gq_fail(GQ_EINVAL, e.unaligned);
+    const uint64_t total = (uint64_t)S * (n_head + 2u * n_kv_head) * (head_dim / 16u);
+    if (total >= 0x7FFFFFFFull) return gq_fail(GQ_ENOTSUP, e.too_large);
+    const u32 nb = (u32)((total + 255u) / 256u);
+    const dim3 grid(nb > 65535u ? 65535u : nb), block(256);
+#define GQ_LAUNCH_ROWS(QKN_, QB_, KV8_)                                                                                                       \
+    hipLaunchKernelGGL((rope_cache_rows_kernel<QKN_, QB_, KV8_>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)qkv, pos,            \
+                       (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)q_out, (CacheElem<KV8_>::type *)k_cache,         \
+                       (CacheElem<KV8_>::type *)v_cache, k_inv, v_inv, (const uint16_t *)q_norm_weight, (const uint16_t *)k_norm_weight, eps, \
+                       (const uint16_t *)qkv_bias, S, n_head, n_kv_head, head_dim, max_seq)
+    if (kv8) {
+        if (q_norm_weight) GQ_LAUNCH_ROWS(true, false, true);
+        else if (qkv_bias) GQ_LAUNCH_ROWS(false, true, true);
+        else GQ_LAUNCH_ROWS(false, false, true);
+    } else if (q_norm_weight) {
+        GQ_LAUNCH_ROWS(true, false, false);
+    } else {
+        GQ_LAUNCH_ROWS(false, false, false);
+    }
+#undef GQ_LAUNCH_ROWS
+    GQ_HIP_CHECK(hipGetLastError());
+    return GQ_OK;
+}
 }  // namespace
 
 extern "C" int gq_rmsnorm_rows(void *x, const void *delta, const void *weight, void *out, uint32_t S, uint32_t D, float eps, void *stream) {
@@ -396,18 +352,10 @@ extern "C" int gq_rmsnorm_rows(void *x, const void *delta, const void *weight, v
 extern "C" int gq_rope_cache_rows(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
                                   void *v_cache, uint32_t S, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, void *stream) {
     if (!qkv || !pos || !cos_table || !sin_table || !q_out || !k_cache || !v_cache) return gq_fail(GQ_EINVAL, "null pointer argument.");
-    if (S == 0) return GQ_OK;
-    if (head_dim == 0 || head_dim % 16u || n_head == 0 || n_kv_head == 0 || max_seq == 0) return gq_fail(GQ_ENOTSUP, "gq_rope_cache_rows: head_dim must be a multiple of 16.");
-    if (((uintptr_t)qkv | (uintptr_t)cos_table | (uintptr_t)sin_table | (uintptr_t)q_out | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15u)
-        return gq_fail(GQ_EINVAL, "gq_rope_cache_rows: 16-byte aligned pointers.");
-    const uint64_t total = (uint64_t)S * (n_head + 2u * n_kv_head) * (head_dim / 16u);
-    if (total >= 0x7FFFFFFFull) return gq_fail(GQ_ENOTSUP, "gq_rope_cache_rows: problem too large.");
-    const u32 blocks = (u32)((total + 255u) / 256u);
-    hipLaunchKernelGGL(rope_cache_rows_kernel, dim3(blocks > 65535u ? 65535u : blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)qkv, pos,
-                       (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)q_out, (uint16_t *)k_cache, (uint16_t *)v_cache, S, n_head,
-                       n_kv_head, head_dim, max_seq);
-    GQ_HIP_CHECK(hipGetLastError());
-    return GQ_OK;
+    static const RowsEntry e = {true, "gq_rope_cache_rows: head_dim must be a multiple of 16.", "gq_rope_cache_rows: 16-byte aligned pointers.",
+                                "gq_rope_cache_rows: problem too large."};
+    return rope_cache_rows(e, false, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim, max_seq,
+                           nullptr, nullptr, 0.f, nullptr, stream);
 }
 
 extern "C" int gq_qknorm_rope_cache_rows(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
@@ -415,21 +363,10 @@ extern "C" int gq_qknorm_rope_cache_rows(const void *qkv, const int *pos, const 
                                          const void *q_norm_weight, const void *k_norm_weight, float eps, void *stream) {
     if (!qkv || !pos || !cos_table || !sin_table || !q_out || !k_cache || !v_cache || !q_norm_weight || !k_norm_weight)
         return gq_fail(GQ_EINVAL, "null pointer argument.");
-    if (S == 0) return GQ_OK;
-    // (the statistic of a head is added inside an aligned group of head_dim / 16 lanes: a power of two, within one wave)
-    if ((head_dim != 64u && head_dim != 128u) || n_head == 0 || n_kv_head == 0 || max_seq == 0)
-        return gq_fail(GQ_ENOTSUP, "gq_qknorm_rope_cache_rows: head_dim must be 64 or 128.");
-    if (((uintptr_t)qkv | (uintptr_t)cos_table | (uintptr_t)sin_table | (uintptr_t)q_out | (uintptr_t)k_cache | (uintptr_t)v_cache |
-         (uintptr_t)q_norm_weight | (uintptr_t)k_norm_weight) & 15u)
-        return gq_fail(GQ_EINVAL, "gq_qknorm_rope_cache_rows: 16-byte aligned pointers.");
-    const uint64_t total = (uint64_t)S * (n_head + 2u * n_kv_head) * (head_dim / 16u);
-    if (total >= 0x7FFFFFFFull) return gq_fail(GQ_ENOTSUP, "gq_qknorm_rope_cache_rows: problem too large.");
-    const u32 blocks = (u32)((total + 255u) / 256u);
-    hipLaunchKernelGGL(qknorm_rope_cache_rows_kernel, dim3(blocks > 65535u ? 65535u : blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)qkv, pos,
-                       (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)q_out, (uint16_t *)k_cache, (uint16_t *)v_cache,
-                       (const uint16_t *)q_norm_weight, (const uint16_t *)k_norm_weight, eps, S, n_head, n_kv_head, head_dim, max_seq);
-    GQ_HIP_CHECK(hipGetLastError());
-    return GQ_OK;
+    static const RowsEntry e = {false, "gq_qknorm_rope_cache_rows: head_dim must be 64 or 128.", "gq_qknorm_rope_cache_rows: 16-byte aligned pointers.",
+                                "gq_qknorm_rope_cache_rows: problem too large."};
+    return rope_cache_rows(e, false, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim, max_seq,
+                           q_norm_weight, k_norm_weight, eps, nullptr, stream);
 }
 
 extern "C" int gq_rope_cache_rows_kv8(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
@@ -440,27 +377,10 @@ extern "C" int gq_rope_cache_rows_kv8(const void *qkv, const int *pos, const voi
     const bool qkn = q_norm_weight || k_norm_weight;
     if (qkn && (!q_norm_weight || !k_norm_weight)) return gq_fail(GQ_EINVAL, "gq_rope_cache_rows_kv8: both norm weights or none.");
     if (qkn && qkv_bias) return gq_fail(GQ_EINVAL, "gq_rope_cache_rows_kv8: the norm form and the bias form do not combine.");
-    if (S == 0) return GQ_OK;
-    if ((head_dim != 64u && head_dim != 128u) || n_head == 0 || n_kv_head == 0 || max_seq == 0)
-        return gq_fail(GQ_ENOTSUP, "gq_rope_cache_rows_kv8: head_dim must be 64 or 128.");
-    if (((uintptr_t)qkv | (uintptr_t)cos_table | (uintptr_t)sin_table | (uintptr_t)q_out | (uintptr_t)k_cache | (uintptr_t)v_cache |
-         (uintptr_t)q_norm_weight | (uintptr_t)k_norm_weight | (uintptr_t)qkv_bias) & 15u)
-        return gq_fail(GQ_EINVAL, "gq_rope_cache_rows_kv8: 16-byte aligned pointers.");
-    const uint64_t total = (uint64_t)S * (n_head + 2u * n_kv_head) * (head_dim / 16u);
-    if (total >= 0x7FFFFFFFull) return gq_fail(GQ_ENOTSUP, "gq_rope_cache_rows_kv8: problem too large.");
-    const u32 nb = (u32)((total + 255u) / 256u);
-    const dim3 grid(nb > 65535u ? 65535u : nb), block(256);
-#define GQ_LAUNCH_ROWS_KV8(QKN_, QB_)                                                                                                          \
-    hipLaunchKernelGGL((rope_cache_rows_kv8_kernel<QKN_, QB_>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)qkv, pos,              \
-                       (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)q_out, (uint8_t *)k_cache, (uint8_t *)v_cache, k_inv, \
-                       v_inv, (const uint16_t *)q_norm_weight, (const uint16_t *)k_norm_weight, eps, (const uint16_t *)qkv_bias, S, n_head,   \
-                       n_kv_head, head_dim, max_seq)
-    if (qkn) GQ_LAUNCH_ROWS_KV8(true, false);
-    else if (qkv_bias) GQ_LAUNCH_ROWS_KV8(false, true);
-    else GQ_LAUNCH_ROWS_KV8(false, false);
-#undef GQ_LAUNCH_ROWS_KV8
-    GQ_HIP_CHECK(hipGetLastError());
-    return GQ_OK;
+    static const RowsEntry e = {false, "gq_rope_cache_rows_kv8: head_dim must be 64 or 128.", "gq_rope_cache_rows_kv8: 16-byte aligned pointers.",
+                                "gq_rope_cache_rows_kv8: problem too large."};
+    return rope_cache_rows(e, true, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, k_inv, v_inv, S, n_head, n_kv_head, head_dim, max_seq, q_norm_weight,
+                           k_norm_weight, eps, qkv_bias, stream);
 }
 
 extern "C" int gq_silu_mul_rows(const void *y, void *out, uint32_t S, uint32_t inter, int paired, void *stream) {

@@ -6,7 +6,7 @@ keys (`layers.{i}.attention.{wqkv,wo}`, `layers.{i}.feed_forward.{w1w3,w2}`, `..
 `output.weight`, `tok_embeddings.weight`; inference/sqllm_llama_convert_fuse.py:73-116), so a
 `converted_pytorch_model.bin` written for the reference loads unchanged.
 
-Two execution paths:
+Three execution paths:
   * `forward(idx, input_pos)`: plain PyTorch ops around `linear_class` modules -- the reference's semantics
     (model.py:121-130, 151-166, 206-266), used for prefill, for any linear class, and as the on-device statement the
     fused path is tested against.  RoPE is re-stated here (`rope_tables`): the reference imports
@@ -14,7 +14,10 @@ Two execution paths:
   * `decode_native(tok, pos)`: one bs=1 decode step as 5 HIP launches per layer through the C ABI
     (RMSNorm -> wqkv | RoPE + KV update + attention | wo + residual | RMSNorm -> w1w3 | SiLU*up -> w2 + residual),
     an embedding lookup and a fused final-norm + lm_head GEMV: no allocation, no host sync, token / position read
-    from device memory, so the whole step is hipGraph-capturable (generate.py).
+    from device memory, so the whole step is hipGraph-capturable (generate.py).  Its host side is native_step.py.
+  * `prefill_native(idx, input_pos)` / `score_native(idx)`: the prompt pass (seq_len > 1, batch 1) with the element-wise steps between
+    the linears as one HIP launch each and the attention as a HIP kernel or SDPA; logits, or log-probabilities through the scoring head.
+    Its host side is native_prompt.py; `mask_rows`, `prefill_chunks` and `_sdpa_gqa` are re-exported from there.
 
 Block layouts: Llama's, and with `ModelArgs.head_dim` / `qk_norm` Mistral's and Qwen3's (RMSNorm over head_dim on every q and k head in
 front of the rotation, modeling_qwen3.Qwen3Attention.forward): in `Attention.forward` for the module path, inside the attention launch
@@ -34,7 +37,8 @@ import torch.nn as nn
 from torch import Tensor
 from torch.nn import functional as F
 
-from . import _lib, native_step
+from . import _lib, native_prompt, native_step
+from .native_prompt import _SDPA_GQA, _sdpa_gqa, mask_rows, prefill_chunks  # noqa: F401  (the prompt pass's own; importable from here as they always were)
 
 
 def find_multiple(n: int, k: int) -> int:
@@ -172,39 +176,6 @@ def window_mask(n: int, window: Optional[int], device=None) -> Tensor:
 
 
 MASK_TABLE_MAX = 16384  # rows of a cache up to which setup_caches keeps [n, n] mask tables (1 GiB per table at 32768 rows: none above)
-
-
-def mask_rows(input_pos: Tensor, n: int, window: Optional[int] = None) -> Tensor:
-    """bool [len(input_pos), n]: the rows `window_mask(m, window)[input_pos, :n]` of any table of m >= n rows, built from the positions on
-    the spot -- key t is attended by the query at position p when t <= p, and with a window also t > p - window"""
-    p = input_pos.long()[:, None]
-    t = torch.arange(n, device=input_pos.device)[None, :]
-    m = t <= p
-    return m if window is None else m & (t > p - int(window))
-
-
-def prefill_chunks(S: int, chunk: int, start: int = 0):
-    """the (start, S) pieces a prompt of S tokens at position `start` is passed in: whole chunks in order, then the tail (one token included)"""
-    assert S >= 1 and chunk >= 1
-    return [(start + a, min(chunk, S - a)) for a in range(0, S, chunk)]
-
-
-_SDPA_GQA = [True]  # F.scaled_dot_product_attention(enable_gqa=True): grouped K / V heads without the repeat_interleave copies
-
-
-def _sdpa_gqa(q, k, v, mask, rep):
-    """q [1, H, S, hd], k / v [1, Hkv, T, hd] (views of the cache), causal when mask is None.  Bit-identical to the form with the
-    K / V heads repeated (measured on this stack: 21.6 vs 34.3 us at S = 128); older torch versions take the copies."""
-    if _SDPA_GQA[0] and rep > 1:
-        try:
-            return F.scaled_dot_product_attention(q, k, v, attn_mask=mask, dropout_p=0.0, is_causal=mask is None, enable_gqa=True)
-        except (TypeError, RuntimeError):
-            _SDPA_GQA[0] = False
-    if rep > 1:
-        Hkv, T, hd = k.shape[1], k.shape[2], k.shape[3]
-        k = k[0].unsqueeze(1).expand(Hkv, rep, T, hd).reshape(1, Hkv * rep, T, hd)
-        v = v[0].unsqueeze(1).expand(Hkv, rep, T, hd).reshape(1, Hkv * rep, T, hd)
-    return F.scaled_dot_product_attention(q, k, v, attn_mask=mask, dropout_p=0.0, is_causal=mask is None)
 
 
 FP8_MAX = 448.0  # the largest e4m3 magnitude
@@ -604,12 +575,11 @@ class Transformer(nn.Module):
         return self._native_state().head(x)
 
     # ------------------------------------------------------------------------------------------------ prompt pass
+    # (guidedquant_amd/native_prompt.py: the chunk loop, one piece, the heads; here its surface on the model)
     def prefill_ready(self, idx: Tensor) -> bool:
         """the HIP prompt pass serves what the native decode step serves (fused Any-Precision models, unfused QTIP models):
         fp16, batch 1, on the GPU"""
-        return (self._native_kind() in ("ap", "qtip") and idx.is_cuda and idx.numel() > 1 and (idx.dim() == 1 or idx.shape[0] == 1)
-                and self.config.head_dim % 16 == 0 and self.config.dim % 8 == 0 and self.config.dim <= 16384
-                and self.config.intermediate_size % 8 == 0)
+        return native_prompt.ready(self, idx)
 
     def prefill_native(self, idx: Tensor, input_pos: Tensor, start: int = 0, last_only: bool = True, chunk: Optional[int] = None) -> Tensor:
         """The prompt pass (`Transformer.forward` with seq_len > 1, inference/model.py:206-266 semantics) with the element-wise
@@ -627,145 +597,7 @@ class Transformer(nn.Module):
         pass where gq_attn_prefill_supported, torch SDPA everywhere else (a prompt of at most `chunk` tokens launches what it always
         did); "1" -- the kernel wherever it is supported; "0" -- never.  `last_prefill_plan` records what the pass did:
         dict(chunks=[(start, S), ..], attn=["hip" | "sdpa" per layer])."""
-        return self._prompt_pass(idx, input_pos, start, last_only, chunk)
-
-    def _prompt_pass(self, idx: Tensor, input_pos: Tensor, start: int, last_only: bool, chunk: Optional[int], score: Optional[dict] = None):
-        """the chunk loop of `prefill_native` (score None: its logits) and of `score_native` (score = dict(targets int32 [S], kernel bool):
-        every piece runs the scoring head on its rows; the list of the pieces' (logprob, top1))"""
-        import os
-        from . import _lib
-        L = _lib.lib()
-        cfg = self.config
-        S, H, Hkv, hd = idx.numel(), cfg.n_head, cfg.n_local_heads, cfg.head_dim
-        assert self.prefill_ready(idx) and input_pos.numel() == S and input_pos.dtype == torch.int32 and start + S <= self.max_seq_length
-        if chunk is None:
-            chunk = int(os.environ.get("GQ_PREFILL_CHUNK", "4096"))
-        assert chunk >= 1, chunk
-        pieces = prefill_chunks(S, chunk, start)
-        mode = os.environ.get("GQ_PREFILL_ATTN", "auto")
-        if mode not in ("auto", "0", "1"):
-            raise ValueError(f"GQ_PREFILL_ATTN={mode!r}: auto, 0 or 1")
-        kv8 = self.kv_cache_dtype == "fp8"
-        if kv8:  # (the fp8 cache: gq_attn_prefill_kv8 wherever it is supported, for any number of chunks; else SDPA on the dequantised rows)
-            assert self._native_kind() == "ap" and self.kv8_unserved() is None, self.kv8_unserved()
-            hip = mode != "0" and bool(L.gq_attn_prefill_supported(H, Hkv, hd))
-            self.last_prefill_plan = dict(chunks=pieces, attn=["hip-kv8" if hip else "sdpa-kv8"] * len(self.layers))
-        else:
-            hip = mode != "0" and (mode == "1" or len(pieces) > 1) and bool(L.gq_attn_prefill_supported(H, Hkv, hd))
-            self.last_prefill_plan = dict(chunks=pieces, attn=["hip" if hip else "sdpa"] * len(self.layers))
-        dev = idx.device
-        Sc = min(chunk, S)
-        bufs = dict(xn=torch.empty((Sc, cfg.dim), dtype=torch.float16, device=dev), q=torch.empty((H * Sc * hd, ), dtype=torch.float16, device=dev),
-                    hbuf=torch.empty((Sc, cfg.intermediate_size), dtype=torch.float16, device=dev),
-                    y=torch.empty((Sc, H * hd), dtype=torch.float16, device=dev) if hip else None)
-        flat, out = idx.reshape(-1), []
-        for a, n in pieces:
-            o = a - start
-            head = (not last_only) or a + n == start + S
-            piece_score = None if score is None else dict(score, targets=score["targets"][o:o + n])
-            r = self._prefill_piece(flat[o:o + n], input_pos[o:o + n], a, bufs, hip, head, last_only, piece_score)
-            if head:
-                out.append(r)
-        if score is not None:
-            return out
-        return out[0] if len(out) == 1 else torch.cat(out, dim=1)
-
-    def _prefill_piece(self, idx: Tensor, input_pos: Tensor, start: int, bufs: dict, hip: bool, head: bool, last_only: bool,
-                       score: Optional[dict] = None):
-        """one piece of the prompt pass: S tokens at positions start .. start + S - 1 through every layer, attending the cache rows
-        [0, start + S); the logits ([1, 1 | S, V]) when `head`, else None.  With `score` (the third head mode) the head is the scoring
-        head on the piece's rows and targets: (logprob fp32 [S], top1 int [S])"""
-        from . import _lib
-        L = _lib.lib()
-        cfg = self.config
-        S, D, H, Hkv, hd, inter = idx.numel(), cfg.dim, cfg.n_head, cfg.n_local_heads, cfg.head_dim, cfg.intermediate_size
-        T = start + S
-        x = self.tok_embeddings(idx.view(1, S)).view(S, D).contiguous()
-        xn, hbuf = bufs["xn"][:S], bufs["hbuf"][:S]
-        q = bufs["q"][:H * S * hd].view(H, S, hd)
-        y_hip = bufs["y"][:S] if hip else None
-        lw = cfg.layer_windows or (None,) * len(self.layers)
-        masks = {}
-
-        def sdpa_mask(win):
-            # the [S, T] rows SDPA needs, from the positions: none at start == 0 without a window (is_causal); a sliding-window layer whose
-            # window the T keys outgrow takes the explicit mask at start == 0 too (is_causal would attend them all)
-            if win is not None and T <= win:
-                win = None
-            if win is None and start == 0:
-                return None
-            if win not in masks:
-                masks[win] = mask_rows(input_pos, T, win)[None, None]
-            return masks[win]
-        rep = H // Hkv
-        scale = 1.0 / math.sqrt(hd)
-        qt = self._native_kind() == "qtip"  # QTIP: the linears through QuantizedLinear.forward (bs > 8: gq_qtip_gemm)
-        kv8 = self.kv_cache_dtype == "fp8"
-        pending = None  # the previous block's MLP output: its residual add rides in the next RMSNorm launch
-        with torch.cuda.device(x.device):
-            st = _lib.current_stream_ptr()  # (the model's device's current stream: inside the guard)
-            for b, win in zip(self.layers, lw):
-                att, ff = b.attention, b.feed_forward
-                _lib.check(L.gq_rmsnorm_rows(x.data_ptr(), pending.data_ptr() if pending is not None else None, b.input_layernorm.weight.data_ptr(), xn.data_ptr(),
-                                             S, D, b.input_layernorm.eps, st), "gq_rmsnorm_rows")
-                if qt:  # (unfused QTIP linears: q | k | v side by side, the row layout gq_rope_cache_rows reads)
-                    xv = xn.view(1, S, D)
-                    qkv = torch.cat([att.wq(xv), att.wk(xv), att.wv(xv)], dim=-1).view(S, -1)
-                else:
-                    qkv = att.wqkv(xn.view(1, S, D)).view(S, -1)
-                kc, vc = att.kv_cache.k_cache, att.kv_cache.v_cache
-                if kv8:
-                    # the fp8 cache: ONE row-write launch for every layout (the norm weights ride along; a bias is already in the rows --
-                    # the quantized linear added it), then the fp8 instance of the prompt kernel
-                    kvc = att.kv_cache
-                    qn = (att.q_norm.weight.data_ptr(), att.k_norm.weight.data_ptr(), att.q_norm.eps) if cfg.qk_norm else (None, None, 0.0)
-                    _lib.check(L.gq_rope_cache_rows_kv8(qkv.data_ptr(), input_pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), q.data_ptr(),
-                                                        kc.data_ptr(), vc.data_ptr(), kvc.k_inv.data_ptr(), kvc.v_inv.data_ptr(), S, H, Hkv, hd, kc.shape[2],
-                                                        *qn, None, st), "gq_rope_cache_rows_kv8")
-                    if hip:
-                        _lib.check(L.gq_attn_prefill_kv8(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), kvc.k_scale.data_ptr(), kvc.v_scale.data_ptr(),
-                                                         y_hip.data_ptr(), S, start, H, Hkv, hd, kc.shape[2], scale, 0 if win is None else int(win), st),
-                                   "gq_attn_prefill_kv8")
-                        y = y_hip.view(1, S, H * hd)
-                    else:
-                        y = _sdpa_gqa(q.unsqueeze(0), kvc.dequant(kc[:1, :, :T], kvc.k_scale), kvc.dequant(vc[:1, :, :T], kvc.v_scale), sdpa_mask(win), rep)
-                        y = y.transpose(1, 2).reshape(1, S, H * hd)
-                elif cfg.qk_norm:  # (Qwen3: the per-head RMSNorm of q and k in front of the rotation, same launch)
-                    _lib.check(L.gq_qknorm_rope_cache_rows(qkv.data_ptr(), input_pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(),
-                                                           q.data_ptr(), kc.data_ptr(), vc.data_ptr(), S, H, Hkv, hd, kc.shape[2],
-                                                           att.q_norm.weight.data_ptr(), att.k_norm.weight.data_ptr(), att.q_norm.eps, st),
-                               "gq_qknorm_rope_cache_rows")
-                else:
-                    _lib.check(L.gq_rope_cache_rows(qkv.data_ptr(), input_pos.data_ptr(), self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), q.data_ptr(),
-                                                    kc.data_ptr(), vc.data_ptr(), S, H, Hkv, hd, kc.shape[2], st), "gq_rope_cache_rows")
-                if kv8:
-                    pass  # (attended above)
-                elif hip:  # (batch slot 0 of the caches; the output already in the row layout wo reads)
-                    _lib.check(L.gq_attn_prefill(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), y_hip.data_ptr(), S, start, H, Hkv, hd, kc.shape[2], scale,
-                                                 0 if win is None else int(win), st), "gq_attn_prefill")
-                    y = y_hip.view(1, S, H * hd)
-                else:
-                    y = _sdpa_gqa(q.unsqueeze(0), kc[:1, :, :T], vc[:1, :, :T], sdpa_mask(win), rep)
-                    y = y.transpose(1, 2).reshape(1, S, H * hd)
-                o = att.wo(y).view(S, D)
-                _lib.check(L.gq_rmsnorm_rows(x.data_ptr(), o.data_ptr(), b.post_attention_layernorm.weight.data_ptr(), xn.data_ptr(), S, D,
-                                             b.post_attention_layernorm.eps, st), "gq_rmsnorm_rows")
-                if qt:  # (gate | up side by side: paired = 0)
-                    xv = xn.view(1, S, D)
-                    gu = torch.cat([ff.w1(xv), ff.w3(xv)], dim=-1).view(S, 2 * inter)
-                    paired = 0
-                else:
-                    gu = ff.w1w3(xn.view(1, S, D)).view(S, 2 * inter)
-                    paired = 1 if getattr(ff.w1w3, "gq_row_pairs", False) else 0
-                _lib.check(L.gq_silu_mul_rows(gu.data_ptr(), hbuf.data_ptr(), S, inter, paired, st), "gq_silu_mul_rows")
-                pending = ff.w2(hbuf.view(1, S, inter)).view(S, D)
-        if not head:
-            return None
-        x = x + pending
-        if score is not None:
-            return self._score_head(x, score["targets"], score["kernel"])
-        x = x[-1:] if last_only else x
-        return self.output(self.norm(x)).view(1, -1, cfg.vocab_size)
+        return native_prompt.prompt_pass(self, idx, input_pos, start, last_only, chunk)
 
     SCORE_HEAD_ROWS = 512  # rows per block of the torch scoring head: its fp16 + fp32 logits are bounded by 512 x V x 6 bytes
     # what GQ_SCORE_HEAD=auto takes where the kernel serves the shape: the kernel -- no slower than the torch head at both measured sizes
@@ -776,29 +608,7 @@ class Transformer(nn.Module):
         """the scoring head on the residual rows x fp16 [n, D] and targets int32 [n] (negative: ignored, logprob 0): (logprob fp32 [n],
         top1 [n]).  Both forms read the fp16 rows norm(x) the logits head feeds to `self.output`: the kernel gq_head_nll
         (csrc/head_nll.hip; no logits in memory), or output -> float -> log_softmax -> gather / argmax in blocks of SCORE_HEAD_ROWS rows."""
-        n, V = x.shape[0], self.config.vocab_size
-        if kernel:
-            from . import _lib
-            L = _lib.lib()
-            xn = self.norm(x).contiguous()
-            W = self.output.weight
-            assert xn.dtype == torch.float16 and W.dtype == torch.float16 and W.is_contiguous() and targets.dtype == torch.int32 and targets.numel() == n
-            lp = torch.empty(n, dtype=torch.float32, device=x.device)
-            top1 = torch.empty(n, dtype=torch.int32, device=x.device)
-            with torch.cuda.device(x.device):  # (the automatic split follows the compute units of the model's device: one guard for both calls)
-                nws = int(L.gq_head_nll_ws_bytes(n, V, xn.shape[1], 0))
-                ws = torch.empty(max(nws, 4), dtype=torch.uint8, device=x.device)
-                _lib.check(L.gq_head_nll(xn.data_ptr(), W.data_ptr(), targets.data_ptr(), n, V, xn.shape[1], lp.data_ptr(), None, top1.data_ptr(), 0,
-                                         ws.data_ptr(), nws, _lib.current_stream_ptr()), "gq_head_nll")
-            return lp, top1
-        lps, tops = [], []
-        for a in range(0, n, self.SCORE_HEAD_ROWS):
-            t = targets[a:a + self.SCORE_HEAD_ROWS].long()
-            ls = F.log_softmax(self.output(self.norm(x[a:a + self.SCORE_HEAD_ROWS])).float(), dim=-1)
-            lp = ls.gather(1, t.clamp(min=0)[:, None])[:, 0]
-            lps.append(torch.where(t >= 0, lp, torch.zeros_like(lp)))
-            tops.append(ls.argmax(dim=-1).to(torch.int32))
-        return torch.cat(lps), torch.cat(tops)
+        return native_prompt.score_head(self, x, targets, kernel)
 
     def score_native(self, idx: Tensor, chunk: Optional[int] = None):
         """Log-probabilities of a token sequence on the HIP prompt pass: (logprob fp32 [S - 1], greedy bool [S - 1]) with
@@ -808,23 +618,7 @@ class Transformer(nn.Module):
         piece, so no [S, V] logits exist.  GQ_SCORE_HEAD: "1" the kernel gq_head_nll, "0" the torch head in blocks of 512 rows, "auto"
         (default) SCORE_HEAD_AUTO where the kernel serves the shape (dim % 64 == 0, fp16) and the torch head elsewhere.
         `last_prefill_plan["head"]` records it ("hip-nll" | "torch").  The caches hold the sequence afterwards, as after a prompt."""
-        import os
-        flat = idx.reshape(-1)
-        S = flat.numel()
-        assert self.prefill_ready(idx) and 2 <= S <= self.max_seq_length
-        mode = os.environ.get("GQ_SCORE_HEAD", "auto")
-        if mode not in ("auto", "0", "1"):
-            raise ValueError(f"GQ_SCORE_HEAD={mode!r}: auto, 0 or 1")
-        served = self.config.dim % 64 == 0 and self.output.weight.dtype == torch.float16  # (else the kernel answers GQ_ENOTSUP)
-        kernel = mode == "1" or (mode == "auto" and served and self.SCORE_HEAD_AUTO == "1")
-        flat = flat.to(torch.int32)
-        targets = torch.cat([flat[1:], torch.full((1, ), -1, dtype=torch.int32, device=flat.device)])
-        pos = torch.arange(0, S, device=flat.device, dtype=torch.int32)
-        out = self._prompt_pass(flat, pos, 0, False, chunk, score=dict(targets=targets, kernel=kernel))
-        self.last_prefill_plan["head"] = "hip-nll" if kernel else "torch"
-        lp = torch.cat([o[0] for o in out])[:S - 1]
-        top1 = torch.cat([o[1] for o in out])[:S - 1]
-        return lp, top1 == flat[1:]
+        return native_prompt.score(self, idx, chunk)
 
     def decode_native(self, tok: Tensor, pos: Tensor) -> Tensor:
         """One bs=1 decode step.  tok, pos: int32 device tensors with one element.  Returns logits fp16 [1,1,V]

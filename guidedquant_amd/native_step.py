@@ -75,6 +75,12 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+def qk_norm_args(at, c):
+    """(q_norm weight, k_norm weight, eps) of an attention module for the launches that take a QK-norm form by argument (null weights:
+    the plain form): gq_rope_cache_rows_kv8 of the decode step and the prompt pass, gq_qknorm_rope_cache_rows"""
+    return (at.q_norm.weight.data_ptr(), at.k_norm.weight.data_ptr(), at.q_norm.eps) if c.qk_norm else (None, None, 0.0)
+
+
 def kv_slot_bytes(n_kv_head, max_seq, head_dim, elem_size):
     """bytes of one batch slot of a K (or V) cache [batch][n_kv_head][max_seq][head_dim]: elem_size 2 (fp16) or 1 (fp8)"""
     return n_kv_head * max_seq * head_dim * elem_size
@@ -162,9 +168,8 @@ class StepState(_Keyed):
         layer's norm weights or bias) rotates q into its own buffer and writes the cache row, gq_attn_decode_roped_kv8 attends it with the
         layer's window and split plan.  One route for Llama, Mistral, Qwen2 and Qwen3; one launch per layer more than the fp16 routes."""
         m, c, L, kvc = self.m, self.m.config, _lib.lib(), at.kv_cache
-        qn = (at.q_norm.weight.data_ptr(), at.k_norm.weight.data_ptr(), at.q_norm.eps) if c.qk_norm else (None, None, 0.0)
         _lib.check(L.gq_rope_cache_rows_kv8(self.qkv.data_ptr(), pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), self.q8.data_ptr(), *kv,
-                                            kvc.k_inv.data_ptr(), kvc.v_inv.data_ptr(), 1, c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, *qn,
+                                            kvc.k_inv.data_ptr(), kvc.v_inv.data_ptr(), 1, c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, *qk_norm_args(at, c),
                                             _ptr(at.wqkv.bias), sp), "gq_rope_cache_rows_kv8")
         _lib.check(L.gq_attn_decode_roped_kv8(self.q8.data_ptr(), pos.data_ptr(), *kv, kvc.k_scale.data_ptr(), kvc.v_scale.data_ptr(), self.y.data_ptr(),
                                               c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, 1.0 / math.sqrt(c.head_dim),
@@ -270,7 +275,7 @@ class ApStep(StepState):
                 # head's rows in eight 16-row groups: no per-head statistic there) -- plain wqkv GEMV, then ONE attention launch that
                 # normalises, rotates, writes the cache row and attends
                 launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
-                self.attend("gq_attn_decode_split_qknorm", qkv, pos, kv, sp, (at.q_norm.weight.data_ptr(), at.k_norm.weight.data_ptr(), at.q_norm.eps), layer=l0 + li)
+                self.attend("gq_attn_decode_split_qknorm", qkv, pos, kv, sp, qk_norm_args(at, c), layer=l0 + li)
             elif at.wqkv.bias is not None:
                 # Qwen2 / Qwen2.5: the bias of q / k / v belongs in front of the rotation, and the RoPE epilogues of the wqkv launch
                 # (gq_anyprec_gemv_qkv_rope*) rotate what the GEMV summed -- the unbiased q / k.  Plain wqkv GEMV, then ONE attention launch

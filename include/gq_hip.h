@@ -163,6 +163,8 @@ int gq_qtip_gemm_ws(void *out, const void *compressed, const void *x, const void
  *   gq_silu_mul_rows    F.silu(gate) * up (model.py:266) of y [S][2 inter] -> out [S][inter]; paired != 0: (gate_i, up_i) adjacent
  *                       (the decode step's row order of the fused gate/up matrix), else gate = y[:, :inter], up = y[:, inter:]
  * All pointers 16-byte aligned device pointers; D, inter multiples of 8 (D <= 16384), head_dim a multiple of 16.
+ * gq_rope_cache_rows, gq_qknorm_rope_cache_rows and gq_rope_cache_rows_kv8 (below) launch instances of ONE kernel
+ * (csrc/prefill.hip: rope_cache_rows_kernel<QKN, QB, KV8>); each entry keeps its own checks.
  */
 int gq_rmsnorm_rows(void *x, const void *delta, const void *weight, void *out, uint32_t S, uint32_t D, float eps, void *stream);
 int gq_rope_cache_rows(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache, void *v_cache,

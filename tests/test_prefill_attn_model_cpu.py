@@ -1,4 +1,4 @@
-"""CPU: the host side of the long-prompt pass (guidedquant_amd/model.py) -- the mask rows built from positions, the chunk planner, a
+"""CPU: the host side of the long-prompt pass (guidedquant_amd/native_prompt.py, guidedquant_amd/model.py) -- the mask rows built from positions, the chunk planner, a
 cache beyond MASK_TABLE_MAX rows without [n, n] tables -- and the test models of tests/prefill_attn_model.py against each other:
 the long grids, the sink profiles, and the float32 emulation of the kernel's online softmax (pam.emulate_row), which states on the
 CPU what rounding P to fp16 at scale 1 loses behind a large first key at 2^17 keys, and that the scale 2^15 keeps it."""

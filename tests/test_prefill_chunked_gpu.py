@@ -1,4 +1,4 @@
-"""GPU: the chunked prompt pass (`Transformer.prefill_native(..., chunk=)`, guidedquant_amd/model.py) with the HIP prompt attention
+"""GPU: the chunked prompt pass (`Transformer.prefill_native(..., chunk=)`, guidedquant_amd/native_prompt.py) with the HIP prompt attention
 (gq_attn_prefill) and with SDPA, against the module forward; a cache beyond MASK_TABLE_MAX rows; `generate()` on a long-for-its-chunk
 prompt.  Tolerances: tests/test_prefill_native_gpu.py's (max error <= 1e-2 max|logit|, relative norm <= 3e-3, caches <= 1e-2 of their max)."""
 import pytest

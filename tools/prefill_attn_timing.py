@@ -2,7 +2,7 @@
 prompt pass of the 8B model, on one GPU.
 
   attention  q [32][S][128] against caches of 8 KV heads (the Llama-3-8B and the Mistral-7B geometry: the two differ in the window), random
-             normal data, for (S, start, W) in CASES: the kernel and SDPA (`model._sdpa_gqa`: is_causal at start = 0 without a window,
+             normal data, for (S, start, W) in CASES: the kernel and SDPA (`native_prompt._sdpa_gqa`: is_causal at start = 0 without a window,
              else the explicit [S, T] mask built from the positions) ALTERNATING, `--launches` launches between two events per run,
              `--repeats` runs each, after a warm-up of both at the shape.  Recorded per case: the microseconds of every run, the
              attended (query, key) pairs, the kernel's rate in TFLOP/s over them (4 * head_dim flops per pair and head), and
