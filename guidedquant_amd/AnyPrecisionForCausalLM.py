@@ -42,6 +42,22 @@ def _get_by_path(root, dotted):
     return root
 
 
+_LOGPROBS_OUTPUT = None
+
+
+def GenerateLogprobsOutput(**fields):
+    """what `generate(output_logprobs=True)` returns: a transformers ModelOutput with `sequences` [1, T + new], `logprobs` and
+    `sampled_logprobs` (fp32 [1, new]).  (The class is made on first use: this module imports transformers lazily.)"""
+    global _LOGPROBS_OUTPUT
+    if _LOGPROBS_OUTPUT is None:
+        import dataclasses
+        from transformers.utils import ModelOutput
+        _LOGPROBS_OUTPUT = dataclasses.dataclass(type("GenerateLogprobsOutput", (ModelOutput, ), {
+            "__annotations__": {"sequences": Optional[torch.Tensor], "logprobs": Optional[torch.Tensor], "sampled_logprobs": Optional[torch.Tensor]},
+            "sequences": None, "logprobs": None, "sampled_logprobs": None, "__module__": __name__}))
+    return _LOGPROBS_OUTPUT(**fields)
+
+
 class _WeakRestore:
     """`wrapper._restore_module_tree()` through a weak reference (a state_dict pre-hook of the inner model / the `_gq_restore` of a
     released linear): no reference cycle through the wrapper"""
@@ -416,7 +432,15 @@ class AnyPrecisionForCausalLM(nn.Module):
         a prompt of more than GQ_PREFILL_CHUNK (4096) tokens goes through the chunked HIP prompt pass (`Transformer.prefill_native`),
         its intermediates sized by the chunk and its attention by gq_attn_prefill; the caches keep no quadratic mask table.
         Returns the [1, prompt + new] token tensor like HF does; stops at EOS (checked every 32 tokens, the tail is cut); honours
-        min_new_tokens, streamer, precision=."""
+        min_new_tokens, streamer, precision=.
+        output_logprobs=True (route 1 only; `native=False`, `capture=True` or a request route 1 does not serve raise ValueError, it never
+        falls back): returns a `GenerateLogprobsOutput` instead -- `sequences` (the tensor the call returns without the keyword),
+        `logprobs` fp32 [1, new]: the log-probability of every generated token under the model's unprocessed distribution, as `score`
+        defines it for given text but from the logits of the decode step the token was drawn at; and `sampled_logprobs` fp32 [1, new]:
+        under the distribution the draw was made from (after repetition penalty, suppress list, temperature, top-k and top-p; 0 for a
+        greedy request) -- transformers' compute_transition_scores(normalize_logits=True).  `logprobs[0, j]` belongs to
+        `sequences[0, T + j]`; both are cut at EOS where the sequence is.  The fused sampler writes them in the launch that draws the
+        token (gq_sample_topk_lp): no [steps, vocab] scores are kept."""
         prev_precision = self.precision
         if 'precision' in kwargs:
             self.set_precision(kwargs.pop('precision'))
@@ -426,7 +450,11 @@ class AnyPrecisionForCausalLM(nn.Module):
         # a request it cannot serve raises -- it never falls back to an fp16 cache silently.  (popped: it never reaches transformers)
         from .model import kv_cache_dtype_name
         kv = kv_cache_dtype_name(kwargs.pop('kv_cache_dtype', None))
+        # output_logprobs=True: per-token log-probabilities from the fused sampler.  Route 1 only, never a fall-back.  (popped as well)
+        lp = bool(kwargs.pop('output_logprobs', False))
         try:
+            if lp and (native is False or capture is True):
+                raise ValueError("output_logprobs=True: served by the fused decode model only (not with native=False or capture=True)")
             if kv == "fp8" and (native is False or capture is True):
                 raise ValueError("kv_cache_dtype='fp8': served by the fused decode model only (not with native=False or capture=True)")
             req, why = self._route_request(args, kwargs, sampler_processors=True) if (native is not False or capture is True) else (None, "opted out")
@@ -434,6 +462,8 @@ class AnyPrecisionForCausalLM(nn.Module):
                 req, why = None, "the fused routes need the GPU"
             if kv == "fp8" and req is None:
                 raise ValueError("kv_cache_dtype='fp8': " + why)
+            if lp and req is None:
+                raise ValueError("output_logprobs=True: " + why)
             if native is True and req is None:
                 raise ValueError("native=True: " + why)
             if req is not None and native is not False:
@@ -442,6 +472,9 @@ class AnyPrecisionForCausalLM(nn.Module):
                 # see every tensor)
                 dec = self._native_decoder_or_none(self.precision, release_planes=native is True)
                 if dec is not None and req["T"] + req["max_new"] > dec.config.block_size:
+                    if lp:
+                        raise ValueError(f"output_logprobs=True: prompt + max_new_tokens = {req['T'] + req['max_new']} exceeds the fused "
+                                         f"model's context ({dec.config.block_size})")
                     if native is True:
                         raise ValueError(f"native=True: prompt + max_new_tokens = {req['T'] + req['max_new']} exceeds the fused model's "
                                          f"context ({dec.config.block_size})")
@@ -451,13 +484,18 @@ class AnyPrecisionForCausalLM(nn.Module):
                     # (the captured step ends in the fused sampler: 128 blocks x 2048 logits at the most.  Qwen3's published vocabulary,
                     # 151936, is within it; a checkpoint beyond 262144 keeps `native_decoder()` / `decode_native` / `prefill_native`,
                     # not this route)
+                    if lp:
+                        raise ValueError(f"output_logprobs=True: vocabulary {dec.config.vocab_size} exceeds the fused sampler's {SAMPLER_MAX_VOCAB}")
                     if native is True:
                         raise ValueError(f"native=True: vocabulary {dec.config.vocab_size} exceeds the fused sampler's {SAMPLER_MAX_VOCAB}")
                     dec = None
                 if dec is not None and kv == "fp8" and dec.kv8_unserved():
                     raise ValueError("kv_cache_dtype='fp8': " + dec.kv8_unserved())
                 if dec is not None:
-                    return self._generate_native(dec, req, kv_cache_dtype=kv)
+                    return self._generate_native(dec, req, kv_cache_dtype=kv, logprobs=lp)
+                if lp:
+                    why_not = getattr(self, "_no_native_reason", None)
+                    raise ValueError("output_logprobs=True: this checkpoint has no fused decode form at %d bits%s" % (self.precision, ": " + why_not if why_not else ""))
                 if kv == "fp8":
                     why_not = getattr(self, "_no_native_reason", None)
                     raise ValueError("kv_cache_dtype='fp8': no fused decode model serves this request%s" % (": " + why_not if why_not else " (context or vocabulary beyond it)"))
@@ -618,7 +656,7 @@ class AnyPrecisionForCausalLM(nn.Module):
             req["streamer"].put(seq_host[lo:(cut or hi)])
         return cut
 
-    def _generate_native(self, dec, req, chunk=32, kv_cache_dtype="fp16"):
+    def _generate_native(self, dec, req, chunk=32, kv_cache_dtype="fp16", logprobs=False):
         from . import generate as gen
         ids, T, max_new = req["ids"].to(self.device), req["T"], req["max_new"]
         total = T + max_new
@@ -629,7 +667,8 @@ class AnyPrecisionForCausalLM(nn.Module):
         # only; a longer cache costs memory, not time).  Beyond 16384 positions the request's own length.
         cap = total if total > 16384 else max(256, 1 << (total - 1).bit_length())
         dec.setup_caches(1, min(cap, dec.config.block_size), kv_cache_dtype=kv_cache_dtype)
-        key = (self.precision, dec.max_seq_length, dec.kv_cache_dtype, req["temperature"], req["top_k"], req["top_p"], req["repetition_penalty"], req["suppress_tokens"])
+        key = (self.precision, dec.max_seq_length, dec.kv_cache_dtype, req["temperature"], req["top_k"], req["top_p"], req["repetition_penalty"], req["suppress_tokens"]) \
+            + ((("logprobs", True), ) if logprobs else ())
         graph = self._native_cache.get(("graph",) + key)
         if graph is None:
             self._evict("graph")
@@ -637,7 +676,8 @@ class AnyPrecisionForCausalLM(nn.Module):
             # chunk runs through the single-step graph over the same state: exactly the steps asked for)
             graph = gen.DecodeGraph(dec, self.device, native_sampling=True, fold_embed=True, seq_capacity=dec.max_seq_length + 1,
                                     seed=self._SAMPLER_SEED, temperature=req["temperature"], top_k=req["top_k"], top_p=req["top_p"], steps_per_replay=8,
-                                    repetition_penalty=req["repetition_penalty"], suppress_tokens=req["suppress_tokens"])
+                                    repetition_penalty=req["repetition_penalty"], suppress_tokens=req["suppress_tokens"],
+                                    **({"logprobs": True} if logprobs else {}))
             self._native_cache[("graph",) + key] = graph
         if req.get("do_sample"):
             graph.rng_counter.copy_(self._fresh_rng_word())
@@ -673,6 +713,9 @@ class AnyPrecisionForCausalLM(nn.Module):
                 done += n
             end = cut if cut is not None else T + done
             out = graph.seq[:end].to(ids.dtype).view(1, -1).clone()
+            if logprobs:  # (slot i of the two arrays describes seq[i]: the sampler's index)
+                out = GenerateLogprobsOutput(sequences=out, logprobs=graph.lp_raw[T:end].view(1, -1).clone(),
+                                             sampled_logprobs=graph.lp_drawn[T:end].view(1, -1).clone())
         if req["streamer"] is not None:
             req["streamer"].end()
         return out

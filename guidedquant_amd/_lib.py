@@ -29,9 +29,11 @@ EXPORTS = [
     "gq_attn_decode_split_window", "gq_attn_decode_split_qknorm_window", "gq_attn_decode_split_bias_window", "gq_attn_decode_roped_window",
     "gq_token_set_build", "gq_sample_topk_rep", "gq_attn_prefill_supported", "gq_attn_prefill",
     "gq_rope_cache_rows_kv8", "gq_attn_decode_roped_kv8", "gq_attn_prefill_kv8", "gq_head_nll_ws_bytes", "gq_head_nll",
+    "gq_sample_topk_lp",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
+SAMPLER_LP_WS = 2 * 128  # floats of gq_sample_topk_lp's lp_ws
 PREFILL_ATTN_BQ, PREFILL_ATTN_BK = 64, 64  # include/gq_hip.h GQ_PREFILL_ATTN_BQ / _BK: query rows and key rows per tile of gq_attn_prefill
 SAMPLER_MAX_VOCAB = 262144  # gq_sample_topk / _ex / _p: 128 blocks x 2048 logits (csrc/decode.hip; up to 131072: x 1024)
 # include/gq_hip.h GQ_AP_ROUTE_*: the kernel family an AP-GEMV dispatch launched (gq_debug_ap_last_route, gq_debug_ap_plan_route)
@@ -129,6 +131,8 @@ def lib():
         L.gq_sample_topk_p.argtypes = [vp, u32, i32, f32, f32, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp]
         # (gq_sample_topk_p + repetition_penalty, seen, suppress in front of the stream)
         L.gq_sample_topk_rep.argtypes = [vp, u32, i32, f32, f32, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, f32, vp, vp, vp]
+        # (gq_sample_topk_rep + lp_ws, lp_raw, lp_drawn, lp_cap in front of the stream)
+        L.gq_sample_topk_lp.argtypes = [vp, u32, i32, f32, f32, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, f32, vp, vp, vp, vp, vp, u32, vp]
         L.gq_token_set_build.argtypes = [vp, u32, u32, vp, i32, vp]
         L.gq_anyprec_gemv_cpu.argtypes = [vp, vp, vp, vp, u32, u32, u32, i32, i32, i32]
         L.gq_anyprec_dequant_cpu.argtypes = [vp, vp, vp, u32, u32, i32, i32]

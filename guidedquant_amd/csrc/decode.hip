@@ -1053,6 +1053,266 @@ __global__ void __launch_bounds__(1024) sample_stage2_rep(const float *cand_val,
     }
 }
 
+// ---- gq_sample_topk_lp: the draw of gq_sample_topk_rep + the drawn token's log-probabilities
+// KERNELS OF THEIR OWN again, for the reason above SampleRep: what the four other entry points launch must not move.  The text repeats
+// sample_stage1_rep / sample_stage2_rep; the additions are marked (LP).  The selection keys are integers and the race is the same
+// sequence of fp32 operations, so the draw is the _rep kernels' bit for bit.
+// REP = false: no penalty and no token sets -- every value is the fp16 logit itself, and the keys are the 16-bit ones of sample_stage1 /
+// sample_stage2 (the draw of gq_sample_topk_rep is then gq_sample_topk_p's, pinned bit for bit by tests/test_sampler_rep_exact_gpu.py).
+// Measured on the 8B geometry: the fp32 keys cost 10.8 us per token against the fp16 ones, the log-probabilities 0.9 us; a request for
+// log-probabilities alone should not pay for a penalty it does not use.  These kernels are new, so here one body serves both forms.
+//   ws: 2 * SAMP_BLOCKS floats, (m_b) then (z_b = sum exp(v - m_b)) of block b's slice, over the RAW fp16 logits -- banned, suppressed
+//       and penalised tokens count with the value the model gave them.  NULL: no raw log-probability is asked for.
+struct SampleLp {
+    float *ws, *raw, *drawn;
+    u32 cap;
+    const uint16_t *logits;  // stage 2 reads the drawn token's raw logit
+};
+constexpr float LP_NINF = -__builtin_inff();
+template <bool REP> struct LpKey1 { typedef unsigned long long T; };  // stage-1 key: 32 + LB bits (REP) or 16 + LB
+template <> struct LpKey1<false> { typedef u32 T; };
+
+template <int KM, int EPT, int LB, bool REP>
+__global__ void __launch_bounds__(256) sample_stage1_lp(const uint16_t *logits, u32 V, float *cand_val, int *cand_idx, const int *ban, const int *pos_io,
+                                                        SampleRep rep, float *lp_ws) {
+    typedef unsigned long long u64;
+    static_assert(256 * EPT == 1 << LB && EPT <= 8, "a slice is one position per key of the block; a thread's tokens span two set words");
+    typedef typename LpKey1<REP>::T KeyT;
+    constexpr int VB = REP ? 32 : 16;  // value bits of a key
+    constexpr u32 LMASK = (1u << LB) - 1u;
+    __shared__ KeyT surv[4 * KM];
+    __shared__ KeyT fin[KM];
+    __shared__ float lpm[4], lpz[4];  // (LP) a wave's maximum and its sum of exp(v - maximum)
+    const u32 per = (V + SAMP_BLOCKS - 1) / SAMP_BLOCKS;  // <= 256 * EPT
+    const u32 lo = blockIdx.x * per, hi = min(lo + per, V);
+    const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
+    int nban = 0, bid[4] = {-1, -1, -1, -1};
+    if (ban) {  // (wave-uniform scalar loads)
+        nban = ban[0];
+        if (pos_io && pos_io[0] >= ban[1]) nban = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) bid[i] = i < nban ? ban[2 + i] : -1;
+    }
+    u64 sbits = 0ull, pbits = 0ull;  // bit e: token lo + tid * EPT + e is seen / suppressed
+    const u32 g0 = lo + tid * (u32)EPT;
+    if (REP && g0 < hi) {  // (words of tokens < hi <= V only: a set is ceil(V / 32) words)
+        const u32 w0 = g0 >> 5, w1 = min(g0 + (u32)EPT - 1u, hi - 1u) >> 5;
+        if (rep.seen) sbits = ((u64)rep.seen[w0] | ((u64)(w1 != w0 ? rep.seen[w1] : 0u) << 32)) >> (g0 & 31u);
+        if (rep.suppress) pbits = ((u64)rep.suppress[w0] | ((u64)(w1 != w0 ? rep.suppress[w1] : 0u) << 32)) >> (g0 & 31u);
+    }
+    KeyT key[EPT];
+    float raw[EPT];  // (LP) every logit of the slice, the banned and the suppressed ones too; -inf past the end
+#pragma unroll
+    for (int e = 0; e < EPT; e++) {
+        const u32 li = tid * (u32)EPT + (u32)e, gi = lo + li;
+        const bool banned = (int)gi == bid[0] || (int)gi == bid[1] || (int)gi == bid[2] || (int)gi == bid[3];
+        const uint16_t hb = gi < hi ? logits[gi] : (uint16_t)0xFC00u;  // (-inf past the end)
+        const float v = h2f(hb);
+        raw[e] = v;
+        KeyT k = 0;
+        if (gi < hi && !banned && !((pbits >> e) & 1ull)) {
+            if constexpr (REP) {
+                // (-0 is not < 0; the division is IEEE's, correctly rounded: the library is built without fast-math)
+                const float sv = ((sbits >> e) & 1ull) ? (v < 0.f ? v * rep.rp : v / rep.rp) : v;
+                k = ((u64)ordered_key32(__builtin_bit_cast(u32, sv)) << LB) | (u64)(LMASK - li);
+            } else {
+                k = (ordered_key16(hb) << LB) | (LMASK - li);
+            }
+        }
+        key[e] = k;
+    }
+    if (lp_ws) {  // (LP) (m_w, sum exp(v - m_w)) of the wave: a finite v has a finite m_w >= v, a -inf one contributes 0
+        float mt = raw[0];
+#pragma unroll
+        for (int e = 1; e < EPT; e++) mt = fmaxf(mt, raw[e]);
+        const float mw = wave_reduce<true>(mt);
+        float zt = 0.f;
+#pragma unroll
+        for (int e = 0; e < EPT; e++) zt += raw[e] == LP_NINF ? 0.f : expf(raw[e] - mw);
+        const float zw = wave_reduce<false>(zt);
+        if (l == 0) {
+            lpm[w] = mw;
+            lpz[w] = zw;
+        }
+    }
+    if (l < KM) surv[w * KM + l] = 0;
+    const KeyT t = wave_select_threshold<EPT, KeyT, VB + LB, LB>(key, KM);
+    wave_compact<EPT, KeyT>(key, t, surv + w * KM, KM, l);
+    __syncthreads();
+    if (w == 0) {  // top KM of the 4 * KM survivors
+        KeyT k2[KM / 16];
+#pragma unroll
+        for (int e = 0; e < KM / 16; e++) k2[e] = surv[(u32)e * 64u + l];
+        const KeyT t2 = wave_select_threshold<KM / 16, KeyT, VB + LB, LB>(k2, KM);
+        if (l < KM) fin[l] = 0;
+        const int n = wave_compact<KM / 16, KeyT>(k2, t2, fin, KM, l);
+        if (l < KM) {
+            const KeyT k = fin[l];
+            const bool ok = (int)l < n && k != 0;
+            const u32 li = LMASK - ((u32)k & LMASK);
+            const float val = REP ? __builtin_bit_cast(float, unordered_key32((u32)((u64)k >> LB))) : h2f(unordered_key16((u32)(k >> LB)));
+            cand_val[blockIdx.x * KM + l] = ok ? val : -3.0e38f;
+            cand_idx[blockIdx.x * KM + l] = ok ? (int)(lo + li) : -1;
+        }
+        if (lp_ws && l == 0) {  // (LP) the four waves in a fixed order; a block wholly past the end leaves (-inf, 0)
+            const float mb = fmaxf(fmaxf(lpm[0], lpm[1]), fmaxf(lpm[2], lpm[3]));
+            float zb = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; i++) zb += lpm[i] == LP_NINF ? 0.f : lpz[i] * expf(lpm[i] - mb);
+            lp_ws[blockIdx.x] = mb;
+            lp_ws[SAMP_BLOCKS + blockIdx.x] = zb;
+        }
+    }
+}
+
+// stage 2 (LP): the text of sample_stage2_rep.  Wave 1, idle while wave 0 selects, combines the 128 partials of stage 1 (two per lane,
+// then the wave in a fixed butterfly: no atomics) and leaves (M, log Z) in LDS; wave 0 loads the raw logits of its candidates in front of
+// the nucleus code (the latency hides behind it), normalises the kept candidates' a_c = s_c / T behind the race, and lane 0 stores the two
+// numbers at the index seq_out uses.
+template <int KM, int IB, bool REP>
+__global__ void __launch_bounds__(1024) sample_stage2_lp(const float *cand_val, const int *cand_idx, int top_k, float temperature,
+                                                         u32 seed, int *counter, int *tok_io, int *pos_io, int *next_tok, SampleEx ex, u32 *seen, u32 V,
+                                                         SampleLp lp) {
+    static_assert(SAMP_BLOCKS == 128, "two partials per lane of wave 0");
+    constexpr int EPT = KM / 8;  // candidates per thread
+    constexpr int VB = REP ? 32 : 16;  // value bits of a key (REP = false: the candidates are fp16 values, exact)
+    constexpr u32 IMASK = (1u << IB) - 1u;
+    __shared__ float selv[KM];
+    __shared__ int seli[KM];
+    __shared__ unsigned long long surv[16 * KM];
+    __shared__ unsigned long long fin[KM];
+    __shared__ int slot, chosen;
+    __shared__ float lpM, lpLogZ;  // (LP) max m_b and log sum z_b exp(m_b - M)
+    const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
+    float pm0 = LP_NINF, pm1 = LP_NINF, pz0 = 0.f, pz1 = 0.f;  // (LP) loaded here, used behind the first barrier
+    if (lp.ws && w == 1) {
+        pm0 = lp.ws[l];
+        pm1 = lp.ws[64u + l];
+        pz0 = lp.ws[SAMP_BLOCKS + l];
+        pz1 = lp.ws[SAMP_BLOCKS + 64u + l];
+    }
+    unsigned long long key[EPT];
+#pragma unroll
+    for (int e = 0; e < EPT; e++) {
+        const u32 c = tid * (u32)EPT + (u32)e;
+        const float v = cand_val[c];
+        const int id = cand_idx[c];
+        const u32 img = REP ? ordered_key32(__builtin_bit_cast(u32, v)) : ordered_key16(__builtin_bit_cast(uint16_t, (h16)v));
+        key[e] = id >= 0 ? (((unsigned long long)img << IB) | (unsigned long long)(IMASK - (u32)id)) : 0ull;
+    }
+    const int K = top_k < 1 ? 1 : (top_k > KM ? KM : top_k);
+    if (l < KM) surv[w * KM + l] = 0ull;
+    const unsigned long long t = wave_select_threshold<EPT, unsigned long long, VB + IB, IB>(key, K);
+    wave_compact<EPT, unsigned long long>(key, t, surv + w * KM, KM, l);
+    __syncthreads();
+    if (w == 0) {
+        unsigned long long k8[KM / 4];
+#pragma unroll
+        for (int e = 0; e < KM / 4; e++) k8[e] = surv[(u32)e * 64u + l];
+        const unsigned long long t2 = wave_select_threshold<KM / 4, unsigned long long, VB + IB, IB>(k8, K);
+        if (l < KM) fin[l] = 0ull;
+        const int n2 = wave_compact<KM / 4, unsigned long long>(k8, t2, fin, KM, l);
+        if (l == 0) slot = n2;
+        if (l < KM) {
+            const unsigned long long k = fin[l];
+            selv[l] = REP ? __builtin_bit_cast(float, unordered_key32((u32)(k >> IB))) : h2f(unordered_key16((u32)(k >> IB)));
+            seli[l] = (int)(IMASK - ((u32)k & IMASK));
+        }
+    } else if (w == 1 && lp.ws) {  // (LP) M = max m_b, Z = sum z_b exp(m_b - M): a -inf partial (a block past the end) contributes 0
+        float M = fmaxf(pm0, pm1);
+#pragma unroll
+        for (int sh = 32; sh >= 1; sh >>= 1) M = fmaxf(M, __shfl_xor(M, sh, 64));
+        float Z = (pm0 == LP_NINF ? 0.f : pz0 * expf(pm0 - M)) + (pm1 == LP_NINF ? 0.f : pz1 * expf(pm1 - M));
+#pragma unroll
+        for (int sh = 32; sh >= 1; sh >>= 1) Z += __shfl_xor(Z, sh, 64);
+        if (l == 0) {
+            lpM = M;
+            lpLogZ = logf(Z);
+        }
+    }
+    __syncthreads();
+    if (w == 0) {
+        const int n = min(slot, K);
+        const float T = fmaxf(temperature, 1e-5f);
+        const u32 ctr = (u32)counter[0];
+        float score = -3.0e38f;
+        int tokc = 0x7FFFFFFF;
+        // (LP) the raw logit of this lane's candidate (an id of the vocabulary), asked for here and used behind the race
+        const float rawv = (lp.raw && (int)l < n) ? h2f(lp.logits[seli[l]]) : 0.f;
+        // nucleus filter on the top-k survivors -- transformers' TopPLogitsWarper behind TopKLogitsWarper behind the temperature
+        // (generation/logits_process.py: probabilities of the scaled, top-k-filtered scores, cumulative sum in ASCENDING order, a token
+        // goes when the sum up to and including it is <= 1 - top_p, the most probable one always stays).  n <= 64 candidates, one per
+        // lane: the cumulative sum of a lane is a loop over the wave (ties ordered by token id, higher id first = the lower key).
+        bool keep = (int)l < n;
+        if (ex.top_p > 0.f && ex.top_p < 1.f) {
+            const float v = (int)l < n ? selv[l] / T : -3.0e38f;
+            float mx = v;
+#pragma unroll
+            for (int sh = 32; sh >= 1; sh >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sh, 64));
+            const float e = (int)l < n ? __expf(v - mx) : 0.f;
+            float z = e;
+#pragma unroll
+            for (int sh = 32; sh >= 1; sh >>= 1) z += __shfl_xor(z, sh, 64);
+            const float pr = e / z;
+            const int myid = (int)l < n ? seli[l] : -1;
+            float cum = 0.f;
+            int greater = 0;
+            for (int j = 0; j < n; j++) {
+                const float vj = __shfl(v, j, 64), pj = __shfl(pr, j, 64);
+                const int idj = __shfl(myid, j, 64);
+                const bool below = vj < v || (vj == v && idj > myid);  // j sorts before this lane in ascending order
+                cum += (below || j == (int)l) ? pj : 0.f;
+                greater += (vj > v || (vj == v && idj < myid)) ? 1 : 0;
+            }
+            keep = keep && (greater == 0 || !(cum <= 1.0f - ex.top_p));
+        }
+        if (keep) {
+            // q ~ Exp(1) = -log(u), u in (0,1]; the random number is tied to the TOKEN id, not to the slot
+            const u32 r = hash32(seed ^ hash32(ctr * 0x9E3779B9u + (u32)seli[l] + 1u));
+            const float u = ((float)(r >> 8) + 1.0f) * (1.0f / 16777216.0f);
+            score = selv[l] / T - __logf(-__logf(u));
+            tokc = seli[l];
+        }
+#pragma unroll
+        for (int sh = 32; sh >= 1; sh >>= 1) {
+            const float os = __shfl_xor(score, sh, 64);
+            const int ot = __shfl_xor(tokc, sh, 64);
+            if (os > score || (os == score && ot < tokc)) { score = os; tokc = ot; }
+        }
+        // (LP) every lane holds the drawn token now.  An empty candidate set (no id of the vocabulary): both numbers are NaN.
+        const bool drew = (u32)tokc < V;
+        float lraw = __builtin_nanf(""), ldrawn = __builtin_nanf("");
+        if (drew) {
+            const int win = (int)__builtin_ctzll(__builtin_amdgcn_ballot_w64(keep && seli[l] == tokc));  // one lane: token ids are unique
+            // v_tok - lse over the whole vocabulary, as (v_tok - M) - log Z: the difference's rounding is in units of the result
+            if (lp.raw) lraw = (__shfl(rawv, win, 64) - lpM) - lpLogZ;
+            if (lp.drawn) {  // a_tok - log sum_C exp(a_c) over the kept candidates, a_c as the race forms it
+                const float a = keep ? selv[l] / T : LP_NINF;
+                float mx = a;
+#pragma unroll
+                for (int sh = 32; sh >= 1; sh >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sh, 64));
+                float z = (keep && a != LP_NINF) ? expf(a - mx) : 0.f;
+#pragma unroll
+                for (int sh = 32; sh >= 1; sh >>= 1) z += __shfl_xor(z, sh, 64);
+                ldrawn = (__shfl(a, win, 64) - mx) - logf(z);
+            }
+        }
+        if (l == 0) {
+            const int p = pos_io ? pos_io[0] : 0;  // (LP) before sample_publish increments it
+            sample_publish(tokc, ctr, counter, tok_io, pos_io, next_tok, ex, seen, V);
+            chosen = tokc;
+            if ((u32)(p + 1) < lp.cap) {
+                if (lp.raw) lp.raw[p + 1] = lraw;
+                if (lp.drawn) lp.drawn[p + 1] = ldrawn;
+            }
+        }
+    }
+    if (ex.x_out) {
+        __syncthreads();
+        sample_embed(chosen, tid, ex);
+    }
+}
+
 // token set of gq_token_set_build: one block -- the words are cleared (clear != 0), the block meets, then every id in [0, V) sets its
 // bit with a vector atomic (duplicates and ids of one word from several threads are then no race)
 __global__ void __launch_bounds__(1024) token_set_build_kernel(const int *ids, u32 n, u32 V, u32 *set, int clear) {
@@ -1443,6 +1703,18 @@ void sample_launch_rep_w(const void *logits, uint32_t vocab, int top_k, float te
         hipLaunchKernelGGL((sample_stage2_rep<64, IB>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex, seen, vocab);
     }
 }
+// (gq_sample_topk_lp: the pair that also leaves the log-probabilities)
+template <int EPT, int LB, int IB, bool REP>
+void sample_launch_lp_w(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter, float *work_val, int *work_idx,
+                        int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, const SampleRep &rep, u32 *seen, const SampleLp &lp, hipStream_t s) {
+    if (top_k <= 32) {
+        hipLaunchKernelGGL((sample_stage1_lp<32, EPT, LB, REP>), dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban, pos_io, rep, lp.ws);
+        hipLaunchKernelGGL((sample_stage2_lp<32, IB, REP>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex, seen, vocab, lp);
+    } else {
+        hipLaunchKernelGGL((sample_stage1_lp<64, EPT, LB, REP>), dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban, pos_io, rep, lp.ws);
+        hipLaunchKernelGGL((sample_stage2_lp<64, IB, REP>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex, seen, vocab, lp);
+    }
+}
 template <int EPT, int LB, int IB>
 void sample_launch_w(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter, float *work_val, int *work_idx,
                      int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, hipStream_t s) {
@@ -1454,14 +1726,26 @@ void sample_launch_w(const void *logits, uint32_t vocab, int top_k, float temper
         hipLaunchKernelGGL((sample_stage2<64, IB>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex);
     }
 }
-// rep == NULL: the kernels of gq_sample_topk / _ex / _p
+// rep == NULL: the kernels of gq_sample_topk / _ex / _p;  lp != NULL (with rep): the kernels of gq_sample_topk_lp
 int sample_launch(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter, float *work_val, int *work_idx,
-                  int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, void *stream, const SampleRep *rep = nullptr, u32 *seen = nullptr) {
+                  int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, void *stream, const SampleRep *rep = nullptr, u32 *seen = nullptr,
+                  const SampleLp *lp = nullptr) {
     if (!logits || !counter || !work_val || !work_idx || !next_tok) return gq_fail(GQ_EINVAL, "null pointer argument.");
     if (top_k > SAMP_K) return gq_fail(GQ_ENOTSUP, "top_k > 64 is not supported by the fused sampler.");
     if (vocab > SAMP_MAX_VOCAB) return gq_fail(GQ_ENOTSUP, "vocab too large for the fused sampler (<= 262144).");
     hipStream_t s = (hipStream_t)stream;
-    if (rep) {
+    if (rep && lp) {
+        // (no penalty and no sets: the instances with the fp16 keys -- the same draw, see above SampleLp)
+        const bool plain = rep->rp == 1.0f && !rep->seen && !rep->suppress && !seen;
+        if (vocab <= 131072u && plain)
+            sample_launch_lp_w<4, 10, 17, false>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, *rep, seen, *lp, s);
+        else if (vocab <= 131072u)
+            sample_launch_lp_w<4, 10, 17, true>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, *rep, seen, *lp, s);
+        else if (plain)
+            sample_launch_lp_w<8, 11, 18, false>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, *rep, seen, *lp, s);
+        else
+            sample_launch_lp_w<8, 11, 18, true>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, *rep, seen, *lp, s);
+    } else if (rep) {
         if (vocab <= 131072u)
             sample_launch_rep_w<4, 10, 17>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, *rep, seen, s);
         else
@@ -1528,6 +1812,24 @@ extern "C" int gq_sample_topk_rep(const void *logits, uint32_t vocab, int top_k,
     if (int rc = sample_extras(ex, vocab, top_p, ban, seq_out, seq_cap, embed_table, x_out, dim, ssq_out)) return rc;
     const SampleRep rep{repetition_penalty, seen, suppress};
     return sample_launch(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, stream, &rep, seen);
+}
+
+extern "C" int gq_sample_topk_lp(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
+                                 float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                                 uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                                 uint32_t *seen, const uint32_t *suppress, float *lp_ws, float *lp_raw, float *lp_drawn, uint32_t lp_cap,
+                                 void *stream) {
+    if (!(repetition_penalty > 0.f) || !(repetition_penalty < INFINITY))
+        return gq_fail(GQ_EINVAL, "repetition_penalty must be finite and > 0 (1 = no penalty).");
+    if (!seen && repetition_penalty != 1.0f) return gq_fail(GQ_EINVAL, "repetition_penalty != 1 needs the `seen` token set.");
+    if (lp_raw && !lp_ws) return gq_fail(GQ_EINVAL, "gq_sample_topk_lp: lp_raw needs the lp_ws workspace (2 * 128 floats).");
+    SampleEx ex{};
+    if (int rc = sample_extras(ex, vocab, top_p, ban, seq_out, seq_cap, embed_table, x_out, dim, ssq_out)) return rc;
+    const SampleRep rep{repetition_penalty, seen, suppress};
+    if (!lp_raw && !lp_drawn)  // only the draw: the kernels of gq_sample_topk_rep
+        return sample_launch(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, stream, &rep, seen);
+    const SampleLp lp{lp_raw ? lp_ws : nullptr, lp_raw, lp_drawn, lp_cap, (const uint16_t *)logits};
+    return sample_launch(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, stream, &rep, seen, &lp);
 }
 
 extern "C" int gq_token_set_build(const int *ids, uint32_t n, uint32_t vocab, uint32_t *set, int clear, void *stream) {

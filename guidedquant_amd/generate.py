@@ -98,7 +98,7 @@ class DecodeGraph:
     (the manual-graph path of generate.py:95-113)."""
 
     def __init__(self, model: Transformer, device, native_sampling=False, seed=1234, fold_embed=False, seq_capacity=0, steps_per_replay=1,
-                 repetition_penalty=1.0, suppress_tokens=None, **sampling_kwargs):
+                 repetition_penalty=1.0, suppress_tokens=None, logprobs=False, **sampling_kwargs):
         """native_sampling: draw the token with the fused HIP sampler (gq_sample_topk_ex: same distribution as `sample`,
         own counter-based RNG, top_k <= 64) and feed token / position back inside the graph; `next_prob` is then
         not produced.  Default False = the reference's torch sampling ops, captured in the graph.
@@ -117,7 +117,12 @@ class DecodeGraph:
         token sets, `self.seen` and `self.suppress` (uint32 bitmaps over the vocabulary); every drawn token joins `seen` on the device.
         `seen` is EMPTY when the constructor returns (the warm-up draws are cleared): like `set_token`, `set_history(ids)` must be called
         with the whole sequence so far -- the prompt -- before the first step of every request.  With the defaults the step makes
-        exactly the gq_sample_topk_p call it always made and nothing is allocated."""
+        exactly the gq_sample_topk_p call it always made and nothing is allocated.
+        logprobs=True (native sampling and seq_capacity > 0 only; ValueError otherwise): the sampler also leaves the log-probability of
+        every token it draws (gq_sample_topk_lp, no extra launch): `self.lp_raw[pos + 1]` under the model's unprocessed distribution and
+        `self.lp_drawn[pos + 1]` under the distribution the draw was made from (fp32 [seq_capacity], the index `self.seq` uses -- it
+        comes from the device position, so a multi-step replay fills consecutive slots).  With the default the step makes exactly the
+        call it makes without the argument and allocates nothing."""
         prime_graph_rng_state(device)
         self.model = model
         self.native_sampling = bool(native_sampling) and model.native_ready() and (sampling_kwargs.get("top_k") or 0) <= 64 \
@@ -149,6 +154,16 @@ class DecodeGraph:
             if suppress_tokens:
                 self.suppress = torch.zeros((words, ), dtype=torch.int32, device=device)
                 self._build_set(self.suppress, torch.tensor(suppress_tokens, dtype=torch.int32, device=device))
+        self.logprobs = bool(logprobs)
+        self.lp_raw = self.lp_drawn = self._lp_ws = None
+        if self.logprobs:
+            if not self.native_sampling or self.seq is None:
+                raise ValueError("logprobs=True is served by the fused sampler only (native_sampling=True on a model with the fused decode "
+                                 "step, top_k <= 64) and needs seq_capacity > 0: the log-probabilities are stored where the tokens are")
+            from . import _lib
+            self.lp_raw = torch.zeros((int(seq_capacity), ), dtype=torch.float32, device=device)
+            self.lp_drawn = torch.zeros((int(seq_capacity), ), dtype=torch.float32, device=device)
+            self._lp_ws = torch.zeros((_lib.SAMPLER_LP_WS, ), dtype=torch.float32, device=device)
         # warm up on a side stream (lazy kernel attributes, allocator), then capture
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -250,6 +265,18 @@ class DecodeGraph:
                 logits = m.decode_native(self.tok.view(1), self.pos.view(1))
                 emb = xo = so = None
             kw = self.sampling_kwargs
+            if self.logprobs:  # (the draw of gq_sample_topk_rep -- without the sets: of gq_sample_topk_p -- and its log-probabilities)
+                _lib.check(_lib.lib().gq_sample_topk_lp(logits.data_ptr(), m.config.vocab_size, int(kw["top_k"]), float(kw.get("top_p") or 1.0),
+                                                       float(kw.get("temperature", 1.0)), int(self.seed), self.rng_counter.data_ptr(),
+                                                       self.work_val.data_ptr(), self.work_idx.data_ptr(), self.tok.data_ptr(),
+                                                       self.pos.data_ptr(), self.next_tok.data_ptr(), self.ban.data_ptr(),
+                                                       self.seq.data_ptr(), self.seq.numel(), emb, xo, m.config.dim, so,
+                                                       self.repetition_penalty, self.seen.data_ptr() if self.seen is not None else None,
+                                                       self.suppress.data_ptr() if self.suppress is not None else None,
+                                                       self._lp_ws.data_ptr(), self.lp_raw.data_ptr(), self.lp_drawn.data_ptr(),
+                                                       self.lp_raw.numel(), _lib.current_stream_ptr()),
+                           "gq_sample_topk_lp")
+                return
             if self.seen is not None:  # (a penalty or a suppress list: the instances over fp32 candidate values and the token sets)
                 _lib.check(_lib.lib().gq_sample_topk_rep(logits.data_ptr(), m.config.vocab_size, int(kw["top_k"]), float(kw.get("top_p") or 1.0),
                                                         float(kw.get("temperature", 1.0)), int(self.seed), self.rng_counter.data_ptr(),

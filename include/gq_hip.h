@@ -712,6 +712,36 @@ int gq_sample_topk_rep(const void *logits, uint32_t vocab, int top_k, float top_
                        uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
                        uint32_t *seen, const uint32_t *suppress, void *stream);
 
+/* gq_sample_topk_rep that also leaves the drawn token's log-probabilities: every parameter of gq_sample_topk_rep up to `suppress`, then
+ *   lp_ws     caller workspace of 2 * 128 floats (the per-block partials of the log-sum-exp), needed when lp_raw != NULL;
+ *   lp_raw, lp_drawn   float [lp_cap] each, either may be NULL;
+ * pinned draw for draw by tests/sampler_lp_model.py.
+ *   draw       gq_sample_topk_rep's.  For the same inputs everything that entry writes -- next_tok, tok_io, pos_io, counter, seq_out,
+ *              seen, x_out, ssq_out, the empty-set token INT_MAX included -- is bit-identical, and so are the status codes.  With
+ *              repetition_penalty == 1 and both sets NULL it is therefore gq_sample_topk_p's draw as well.
+ *   index      p = *pos_io before the increment (0 when pos_io is NULL), i = p + 1 (the index seq_out uses): two floats are written when
+ *              i < lp_cap.  No other element of the two arrays is touched.
+ *   lp_raw[i]  the drawn token's log-probability under the model's UNPROCESSED distribution, v_tok - lse: v_t the fp16 logit widened to
+ *              fp32, lse = log sum_t exp(v_t) over all `vocab` tokens in fp32.  Banned, suppressed and penalised tokens count with their
+ *              raw value; a -inf logit contributes 0.  The number score() defines for given text, and the one serving APIs report.
+ *   lp_drawn[i]  the log-probability under the distribution the race drew from, a_tok - log sum_{c in C} exp(a_c): C the candidate set
+ *              after suppress / ban, penalty, top-k and nucleus, a_c = s_c / max(T, 1e-5) in fp32 as the race forms it.  A one-member C
+ *              gives exactly 0.0.  What transformers' compute_transition_scores(..., normalize_logits=True) yields on its processed scores.
+ *   special    empty candidate set: both outputs are a quiet NaN.  Logits that are NaN or +inf, or all -inf: the two outputs are
+ *              unspecified; the draw stays gq_sample_topk_rep's.
+ *   determinism  both outputs are pure functions of the inputs: per-block partials (stage 1: wave reductions and one combine of the four
+ *              waves) are combined by stage 2 in a fixed order inside the existing launch, no floating-point atomics; two calls on the
+ *              same state give the same bits.  No extra launch, no [steps, vocab] buffer.
+ *   NULL forms lp_raw != NULL with lp_ws == NULL is GQ_EINVAL and writes nothing; with both outputs NULL the entry only draws (it then
+ *              launches gq_sample_topk_rep's kernels).
+ * The kernels are instances of their own: the four entry points above launch what they did.  With repetition_penalty == 1 and both sets
+ * NULL the instances with gq_sample_topk_p's 16-bit value keys are launched (the same draw; the fp32 keys of the penalty cost more per
+ * token than the two numbers do). */
+int gq_sample_topk_lp(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
+                      float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                      uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                      uint32_t *seen, const uint32_t *suppress, float *lp_ws, float *lp_raw, float *lp_drawn, uint32_t lp_cap, void *stream);
+
 /* Test / tuning hooks (not part of the reference's surface).  gq_reset_env_cache: drop the cached GQ_* environment
  * knobs so that a test can flip them between calls.  gq_debug_set_timing_buffer: device buffer the plane kernels write
  * s_memtime phase stamps into (tools/phase_timing.py); NULL (default) disables it. */
