@@ -113,30 +113,57 @@ __device__ __forceinline__ void rope_unit(const uint4 a, const uint4 b, const ui
 // 8 fp16 values (4 words) -> 8 OCP e4m3 codes by THE write rule of the fp8 cache, the only rounding the format adds:
 //   code = fp8_rne(clamp(float(x16) * inv, -448, 448))
 // inv = 1 / scale of the KV head, an fp32 the host computed (no division here).  The clamp is explicit (v_med3_f32): v_cvt_pk_fp8_f32
-// turns a magnitude beyond 448 into NaN, not into 448.  The host model: (x16.float() * inv).clamp(-448, 448).to(torch.float8_e4m3fn).
-__device__ __forceinline__ uint2 fp8_quant8(const u32 (&w)[4], float inv) {
+// turns a magnitude beyond 448 into NaN, not into 448; +-Inf clamps to +-448.  The host model:
+// (x16.float() * inv).clamp(-448, 448).to(torch.float8_e4m3fn).  A NaN must be stored as a NaN code, and the clamp loses it (v_med3_f32
+// with a NaN operand returns the smaller of the other two, -448): NAN_PASS puts the NaNs among the products v back behind the clamp.
+template <bool NAN_PASS>
+__device__ __forceinline__ uint2 fp8_quant8(const float (&v)[8]) {
+    float f[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        f[k] = __builtin_amdgcn_fmed3f(v[k], -448.f, 448.f);
+        if constexpr (NAN_PASS) f[k] = v[k] != v[k] ? v[k] : f[k];
+    }
     u32 o[2];
 #pragma unroll
     for (int e = 0; e < 2; e++) {
-        float f[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            f[k] = __builtin_amdgcn_fmed3f(h2f((uint16_t)(w[2 * e + (k >> 1)] >> (16 * (k & 1)))) * inv, -448.f, 448.f);
         int r = 0;
-        r = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], r, false);
-        r = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], r, true);
+        r = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * e], f[4 * e + 1], r, false);
+        r = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * e + 2], f[4 * e + 3], r, true);
         o[e] = (u32)r;
     }
     return make_uint2(o[0], o[1]);
 }
 
 // a thread's two units (elements d .. d + 7 and d + HD / 2 .. of a head's row `dst`): as they are into an fp16 row (q_out, an fp16
-// cache), by fp8_quant8 with the reciprocal scale of the KV head into a row of one byte per element
+// cache), by fp8_quant8 with the reciprocal scale of the KV head into a row of one byte per element.  The fp8 row is stored by the clamp
+// alone first; the test for a NaN -- a chain of fused multiply-adds through the 16 products, which a NaN survives, and one unordered
+// compare -- runs behind the stores, off their path, and a thread that finds one stores its 16 bytes again with the NaNs in place (the
+// same thread, the same addresses: in order).  A compare and a select per value in front of the store cost the S = 4096 launch 2 %.
 template <typename E>
 __device__ __forceinline__ void store_units(E *dst, u32 d, u32 HD, const u32 (&w1)[4], const u32 (&w2)[4], float inv) {
     if constexpr (sizeof(E) == 1) {
-        *reinterpret_cast<uint2 *>(dst + d) = fp8_quant8(w1, inv);
-        *reinterpret_cast<uint2 *>(dst + d + HD / 2u) = fp8_quant8(w2, inv);
+        float v1[8], v2[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            v1[k] = h2f((uint16_t)(w1[k >> 1] >> (16 * (k & 1)))) * inv;
+            v2[k] = h2f((uint16_t)(w2[k >> 1] >> (16 * (k & 1)))) * inv;
+        }
+        *reinterpret_cast<uint2 *>(dst + d) = fp8_quant8<false>(v1);
+        *reinterpret_cast<uint2 *>(dst + d + HD / 2u) = fp8_quant8<false>(v2);
+        // a NaN among the 16 products makes t a NaN, or is v2[7] (Infs may do so too: the pass below is right for any input)
+        float t = __builtin_fmaf(v1[0], v1[1], v1[2]);
+        t = __builtin_fmaf(v1[3], v1[4], t);
+        t = __builtin_fmaf(v1[5], v1[6], t);
+        t = __builtin_fmaf(v1[7], v2[0], t);
+        t = __builtin_fmaf(v2[1], v2[2], t);
+        t = __builtin_fmaf(v2[3], v2[4], t);
+        t = __builtin_fmaf(v2[5], v2[6], t);
+        const bool nan = __builtin_isunordered(t, v2[7]);
+        if (nan) {
+            *reinterpret_cast<uint2 *>(dst + d) = fp8_quant8<true>(v1);
+            *reinterpret_cast<uint2 *>(dst + d + HD / 2u) = fp8_quant8<true>(v2);
+        }
     } else {
         *reinterpret_cast<uint4 *>(dst + d) = make_uint4(w1[0], w1[1], w1[2], w1[3]);
         *reinterpret_cast<uint4 *>(dst + d + HD / 2u) = make_uint4(w2[0], w2[1], w2[2], w2[3]);

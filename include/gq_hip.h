@@ -200,7 +200,9 @@ int gq_attn_prefill(const void *q, const void *k_cache, const void *v_cache, voi
  * The fp8 KV cache (kv_cache_dtype="fp8"): caches of OCP e4m3 codes, one byte per element, [n_kv_head][max_seq][head_dim] per batch
  * slot, with fp32 scales per KV head in device memory (read by the kernels at every launch: new values need no re-capture).
  *   write rule  code  = fp8_rne(clamp(float(x16) * inv, -448, 448)),  inv = 1 / scale computed by the host (no kernel divides);
- *               x16 is the fp16 value the fp16 path would have stored.  The only rounding the format adds.  Non-finite x16: undefined.
+ *               x16 is the fp16 value the fp16 path would have stored.  The only rounding the format adds.  Non-finite x16: +-Inf
+ *               clamps to +-448 (0x7e / 0xfe); a NaN stores a NaN code (0x7f or 0xff), which every read turns into NaN output -- as an
+ *               fp16 cache would show it.
  *   read rule   value = float(code) * scale.  Every e4m3 value is an fp16 value, so the conversion is exact: the K scale is one factor
  *               of the score (scale * k_scale[g]), the V scale multiplies the weighted sum in front of the division and the one fp16
  *               rounding.  With scales that are powers of two the results equal, bit for bit, those of the fp16 entries on an fp16
