@@ -129,7 +129,8 @@ __device__ __forceinline__ void softmax_update(float &m_run, float &s_run, float
     for (int e = 0; e < 8; e++) acc[e] *= resc;
 #pragma unroll
     for (int u = 0; u < U; u++) {
-        const float wgt = pu[u] > -2.0e38f ? __expf(pu[u] - m_new) : 0.f;
+        // (not `pu > -2e38`: a NaN score compares false and would be dropped with weight 0 -- it must poison the head)
+        const float wgt = !(pu[u] <= -2.0e38f) ? __expf(pu[u] - m_new) : 0.f;
         s_run += wgt;
 #pragma unroll
         for (int e = 0; e < 8; e++) acc[e] += wgt * vfu[u][e];

@@ -641,6 +641,8 @@ __device__ __forceinline__ uint16_t unordered_key16(u32 o) { return (o & 0x8000u
 // the same image of an fp32 bit pattern (gq_sample_topk_rep: a penalised logit is an fp32 number that in general is no fp16 value)
 __device__ __forceinline__ u32 ordered_key32(u32 b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 __device__ __forceinline__ u32 unordered_key32(u32 o) { return (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o; }
+// stage 1 of every instance gives a NaN logit (or a penalised one) the key 0: never a candidate, whatever its sign
+__device__ __forceinline__ bool is_nan16(uint16_t h) { return (h & 0x7FFFu) > 0x7C00u; }
 
 // The K-th largest of the 64 * EPT keys of ONE wave by binary search on the key bits: the count of a round is EPT ballots +
 // scalar population counts -- no LDS, no barrier (the block-wide version above pays a 1024-thread barrier per bit: 13 us
@@ -759,7 +761,9 @@ __global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32
         const u32 li = tid * (u32)EPT + (u32)e, gi = lo + li;
         // key = (order-preserving image of the fp16 logit, position): unique, and both parts are recovered from it
         const bool banned = (int)gi == bid[0] || (int)gi == bid[1] || (int)gi == bid[2] || (int)gi == bid[3];
-        key[e] = (gi < hi && !banned) ? ((ordered_key16(logits[gi]) << LB) | (LMASK - li)) : 0u;
+        // a NaN logit of either sign is no candidate (key 0, like a banned id): its image would lie above +inf (0x7E00) or below -inf (0xFE00)
+        const uint16_t hb = (gi < hi && !banned) ? logits[gi] : (uint16_t)0x7E00u;
+        key[e] = is_nan16(hb) ? 0u : ((ordered_key16(hb) << LB) | (LMASK - li));
     }
     if (l < KM / 2) reinterpret_cast<unsigned long long *>(surv + w * KM)[l] = 0ull;  // (a wave's LDS ops are in order)
     const u32 t = wave_select_threshold<EPT, u32, 16 + LB, LB>(key, KM);
@@ -930,7 +934,7 @@ __global__ void __launch_bounds__(256) sample_stage1_rep(const uint16_t *logits,
             const float v = h2f(logits[gi]);
             // (-0 is not < 0; the division is IEEE's, correctly rounded: the library is built without fast-math)
             const float sv = ((sbits >> e) & 1ull) ? (v < 0.f ? v * rep.rp : v / rep.rp) : v;
-            k = ((u64)ordered_key32(__builtin_bit_cast(u32, sv)) << LB) | (u64)(LMASK - li);
+            if (sv == sv) k = ((u64)ordered_key32(__builtin_bit_cast(u32, sv)) << LB) | (u64)(LMASK - li);  // (a NaN is no candidate)
         }
         key[e] = k;
     }
@@ -1114,9 +1118,9 @@ __global__ void __launch_bounds__(256) sample_stage1_lp(const uint16_t *logits, 
             if constexpr (REP) {
                 // (-0 is not < 0; the division is IEEE's, correctly rounded: the library is built without fast-math)
                 const float sv = ((sbits >> e) & 1ull) ? (v < 0.f ? v * rep.rp : v / rep.rp) : v;
-                k = ((u64)ordered_key32(__builtin_bit_cast(u32, sv)) << LB) | (u64)(LMASK - li);
+                if (sv == sv) k = ((u64)ordered_key32(__builtin_bit_cast(u32, sv)) << LB) | (u64)(LMASK - li);  // (a NaN is no candidate)
             } else {
-                k = (ordered_key16(hb) << LB) | (LMASK - li);
+                if (!is_nan16(hb)) k = (ordered_key16(hb) << LB) | (LMASK - li);
             }
         }
         key[e] = k;
@@ -1158,7 +1162,9 @@ __global__ void __launch_bounds__(256) sample_stage1_lp(const uint16_t *logits, 
             const float mb = fmaxf(fmaxf(lpm[0], lpm[1]), fmaxf(lpm[2], lpm[3]));
             float zb = 0.f;
 #pragma unroll
-            for (int i = 0; i < 4; i++) zb += lpm[i] == LP_NINF ? 0.f : lpz[i] * expf(lpm[i] - mb);
+            // (a partial is left out by its SUM being 0, not by its maximum being -inf: fmaxf drops a NaN, so a wave whose only logits
+            // are NaN has m = -inf and z = NaN, and that NaN has to reach the log-probability.  z == 0 happens with m = -inf only.)
+            for (int i = 0; i < 4; i++) zb += lpz[i] == 0.f ? 0.f : lpz[i] * expf(lpm[i] - mb);
             lp_ws[blockIdx.x] = mb;
             lp_ws[SAMP_BLOCKS + blockIdx.x] = zb;
         }
@@ -1222,7 +1228,7 @@ __global__ void __launch_bounds__(1024) sample_stage2_lp(const float *cand_val, 
         float M = fmaxf(pm0, pm1);
 #pragma unroll
         for (int sh = 32; sh >= 1; sh >>= 1) M = fmaxf(M, __shfl_xor(M, sh, 64));
-        float Z = (pm0 == LP_NINF ? 0.f : pz0 * expf(pm0 - M)) + (pm1 == LP_NINF ? 0.f : pz1 * expf(pm1 - M));
+        float Z = (pz0 == 0.f ? 0.f : pz0 * expf(pm0 - M)) + (pz1 == 0.f ? 0.f : pz1 * expf(pm1 - M));  // (z == 0: as in stage 1)
 #pragma unroll
         for (int sh = 32; sh >= 1; sh >>= 1) Z += __shfl_xor(Z, sh, 64);
         if (l == 0) {

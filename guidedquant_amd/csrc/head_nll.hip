@@ -95,7 +95,11 @@ __global__ void __launch_bounds__(256) head_nll_kernel(const uint16_t *__restric
 #pragma unroll
     for (u32 b = 0; b < 2; b++) {
         tg[b] = target[min(s0 + 32u * w + 16u * b + li, S - 1u)];
-        m_run[b] = NEG, l_run[b] = 0.f, t_run[b] = NEG, bv[b] = NEG, bi[b] = NO_ID;
+        // (the target logit's neutral element is -inf, not NEG: a target whose logit IS -inf then scores -inf, not -1e30.  A target that
+        // matches no column -- target >= V, the caller's error by the header -- now scores -inf as well, where it scored -1e30 - lse.
+        // The fold of the target logit is fmaxf and drops a NaN; a NaN target logit still gives a NaN logprob, through lse: the same
+        // NaN logit is in the row's sum.)
+        m_run[b] = NEG, l_run[b] = 0.f, t_run[b] = -__builtin_inff(), bv[b] = NEG, bi[b] = NO_ID;
     }
 
     if (t0 < t1) {
@@ -195,7 +199,7 @@ __global__ void __launch_bounds__(256) head_nll_merge_kernel(Partials ws, const 
                                                              float *__restrict__ lse, int *__restrict__ top1) {
     const u32 row = blockIdx.x * 256u + threadIdx.x;
     if (row >= S) return;
-    float m = NEG, sum = 0.f, tl = NEG, bv = NEG;
+    float m = NEG, sum = 0.f, tl = -__builtin_inff(), bv = NEG;
     int bi = NO_ID;
     for (u32 sp = 0; sp < splits; sp++) {  // ascending: one order of the fp32 sums
         const size_t o = (size_t)sp * S + row;

@@ -132,8 +132,9 @@ def lnq_like_layer(N, K, bits, seed, oracle=None):
     return q, lut, np.clip(x, -6e4, 6e4).astype(np.float16)
 
 
-def run_fused(x, q, lut, bits, norm_weight=None, eps=1e-5, residual=None, flags=0, out_elems=None, workspace=False, expect=None):
-    """gq_anyprec_gemv_fused through the C ABI on cuda:0 (numpy in, numpy out); out is pre-filled with NaN.
+def run_fused(x, q, lut, bits, norm_weight=None, eps=1e-5, residual=None, flags=0, out_elems=None, workspace=False, expect=None, fill=float("nan")):
+    """gq_anyprec_gemv_fused through the C ABI on cuda:0 (numpy in, numpy out); out is pre-filled with NaN (`fill`: the non-finite tests
+    pre-fill out and the workspace with a finite value instead).
     workspace: gq_anyprec_gemv_fused_ws with the bytes gq_anyprec_gemv_fused_ws_bytes asks for (NaN-filled).
     expect: the kernel family the launch must have run (assert_route)"""
     import torch
@@ -143,11 +144,11 @@ def run_fused(x, q, lut, bits, norm_weight=None, eps=1e-5, residual=None, flags=
     t = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(d)  # noqa: E731
     xt, qt, lt = t(x, np.float16), torch.from_numpy(np.ascontiguousarray(q)).to(d), t(lut, np.float16)
     nw, rs = t(norm_weight, np.float16), t(residual, np.float16)
-    out = torch.full((out_elems or N, ), float("nan"), dtype=torch.float16, device=d)
+    out = torch.full((out_elems or N, ), fill, dtype=torch.float16, device=d)
     if workspace:
         nb = int(_lib.lib().gq_anyprec_gemv_fused_ws_bytes(N, K, bits, flags))
         assert nb > 0, "no workspace form for this shape"
-        ws = torch.full((nb // 4, ), float("nan"), dtype=torch.float32, device=d)
+        ws = torch.full((nb // 4, ), fill, dtype=torch.float32, device=d)
         rc = _lib.lib().gq_anyprec_gemv_fused_ws(xt.data_ptr(), out.data_ptr(), qt.data_ptr(), lt.data_ptr(), N, K, bits,
                                                  nw.data_ptr() if nw is not None else None, eps, rs.data_ptr() if rs is not None else None,
                                                  flags, ws.data_ptr(), nb, _lib.current_stream_ptr())

@@ -11,7 +11,8 @@ drew, and says what the two numbers of each of them must be)
             sampler_rep_model.run forms them), a_c = fl32(s_c / max(T, 1e-5)): the fp32 quotient the race forms; the sum in float64.
             A one-member C gives exactly 0
   empty C   both are NaN (the token is EMPTY_TOKEN)
-Logits with NaN or +inf, or all -inf: unspecified (`specified`).
+Logits with +inf, or all -inf: unspecified (`specified`).  A NaN logit is no candidate (sampler_model.py): lp_drawn is taken over the kept
+candidates as ever, and lp_raw, whose sum runs over ALL tokens, is NaN for every draw (`lse64` returns NaN); all logits NaN: empty C.
 
 Which draws' lp_drawn a device run may decide differently: the kept set is key-exact behind top-k; behind a nucleus it depends on an fp32
 cumulative sum against 1 - top_p.  A draw whose nearest cumulative sum lies within NUCLEUS_GRANT = 1e-5 of the threshold -- the distance
@@ -76,6 +77,7 @@ def run(logits, tokens, top_k, T, top_p=1.0, pos=0, ban=None, rp=1.0, seen0=(), 
     v32 = logits.astype(np.float32)
     dead = np.zeros(V, dtype=bool)
     dead[np.asarray([t for t in suppress if 0 <= t < V], dtype=np.int64)] = True
+    dead[np.isnan(v32)] = True  # (no candidate; in lp_raw's sum over ALL tokens it counts as what it is: the sum is NaN)
     static = np.lexsort((np.arange(V), -rm.image32(v32)))
     static = static[~dead[static]]
     nb, until, bids = (ban[0], ban[1], [b for b in ban[2][:ban[0]] if 0 <= b < V]) if ban is not None and ban[0] > 0 else (0, 0, [])

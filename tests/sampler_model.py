@@ -34,6 +34,11 @@ and the subtraction are correctly rounded, u_i is exact).  Against the float64 s
 A candidate j is ADMISSIBLE next to the winner w when score_w - score_j <= e_w + e_j.  A draw with more than one admissible token
 is UNDECIDED.  -inf scores and NaN never are admissible next to a finite winner.
 
+NaN logits: a NaN of either sign is never a candidate -- it ranks with the banned ids, and the finite tokens are drawn exactly as if the
+NaN entries were banned.  A step whose unbanned logits are all NaN has an empty candidate set: the token is EMPTY_TOKEN (no id of the
+vocabulary), the state advances as for any draw.  NAN_CASES run the profiles nan_few / nan_block / nan_all; NAN_FAULTS are the two
+readings a sampler that orders NaN by its bits would give (tests/test_sampler_model_cpu.py shows that the cases catch them).
+
 `fault=` injects one deviation (FAULTS); it is used by tests/test_sampler_model_cpu.py only, to show that the cases below catch it.
 """
 from collections import namedtuple
@@ -45,6 +50,8 @@ BLOCKS = 128
 MAX_VOCAB = 262144
 FAULTS = ("temp_x1.05", "rng_by_slot", "counter_stuck", "top_k_plus_1", "top_k_minus_1", "tie_to_higher_index", "nucleus_lt",
           "nucleus_descending", "top_unprotected", "ban_le")
+NAN_FAULTS = ("nan_wins", "neg_nan_as_number")
+EMPTY_TOKEN = 0x7FFFFFFF  # what an empty candidate set publishes (decode.hip: sample_publish)
 M32 = np.uint64(0xFFFFFFFF)
 
 
@@ -86,7 +93,13 @@ def candidates(logits, top_k, banned=(), fault=None):
         k = max(k - 1, 1)
     key = order_key(bits)
     idx = np.arange(bits.size, dtype=np.int64)
-    live = np.ones(bits.size, dtype=bool)
+    nan = (bits & 0x7FFF) > 0x7C00
+    if fault == "nan_wins":           # ordered by its bits: +NaN above +inf, -NaN below -inf, both candidates
+        live = np.ones(bits.size, dtype=bool)
+    elif fault == "neg_nan_as_number":   # told by `bits > 0x7C00` on the pattern: a -NaN stays, below -inf
+        live = ~(nan & (bits < 0x8000))
+    else:
+        live = ~nan
     for b in banned:
         if 0 <= b < bits.size:
             live[b] = False
@@ -154,6 +167,12 @@ def run(logits, n, top_k, T, top_p=1.0, seed=0, counter=0, pos=0, ban=None, seq_
             continue
         ids = candidates(logits, top_k, ids_banned if state else (), fault)
         ncand.append(ids.size)
+        isnan = np.isnan(logits[ids].astype(np.float32))
+        if ids.size == 0 or isnan.any():   # empty: no token; (faults only) a NaN candidate wins the draw: its score compares false
+            t = EMPTY_TOKEN if ids.size == 0 else int(ids[isnan].min())
+            for r in rows:
+                tokens[r], admissible[r], detail[r] = t, np.array([t]), (ids[:0], np.zeros(0), np.zeros(0))
+            continue
         v = logits[ids].astype(np.float64)
         with np.errstate(over="ignore"):
             a = v / Tq
@@ -251,6 +270,20 @@ def profile(name, V, salt=0):
         x = np.full(V, -np.inf, dtype=np.float16)
         x[rng.permutation(V)[:10]] = (rng.standard_normal(10) * 2).astype(np.float16)
         return x
+    if name in ("nan_few", "nan_block", "nan_all"):
+        x = (rng.standard_normal(V) * 2).astype(np.float16)
+        b = x.view(np.uint16)
+        if name == "nan_few":      # 5 NaN of both signs and both payload kinds, one of them where the arg-max would be
+            where = np.concatenate([[int(np.argmax(x.astype(np.float32)))], rng.permutation(V)[:6]])
+            where = where[np.sort(np.unique(where, return_index=True)[1])][:5]
+            b[where] = np.array([0x7E00, 0xFE00, 0x7C01, 0xFFFF, 0x7E00], dtype=np.uint16)[:where.size]
+        elif name == "nan_block":  # the whole stage-1 slice that holds the arg-max, signs alternating
+            blk = int(np.argmax(x.astype(np.float32))) // per
+            n = min((blk + 1) * per, V) - blk * per
+            b[blk * per:blk * per + n] = np.where(np.arange(n) % 2 == 0, 0x7E00, 0xFE00).astype(np.uint16)
+        else:
+            b[:] = np.where(np.arange(V) % 3 == 0, 0xFE00, 0x7E00).astype(np.uint16)
+        return x
     if name == "planted_high_id":  # the arg-max sits at id V - 5 (>= 131072 on the wide instance)
         x = (rng.standard_normal(V) * 2).astype(np.float16)
         x[V - 5] = 12.0
@@ -341,8 +374,27 @@ CASES = [
     _case("embed_256", 4096, "quant", 64, 2.5, top_p=0.95, dim=256, n=500, seed=0),
     _case("embed_8200", 300, "gauss", 50, 1.0, dim=8200, n=300, counter=WRAP31),
 ]
-CASE_BY_NAME = {c.name: c for c in CASES}
-assert len(CASE_BY_NAME) == len(CASES)
+# NaN logits (not in CASES: an empty candidate set publishes EMPTY_TOKEN, which the consumers of CASES index the vocabulary with).
+# Every entry point, both vocabulary widths, T = 0 and 0.8, top_k 1 / 32 / 50.
+NAN_CASES = [
+    _case("nan_few_k1_greedy", 4096, "nan_few", 1, 0.0, entry="topk"),
+    _case("nan_few_k32", 32000, "nan_few", 32, 0.8, entry="topk", n=300),
+    _case("nan_few_k50", 32000, "nan_few", 50, 0.8, n=300),
+    _case("nan_few_k50_greedy_wide", 151936, "nan_few", 50, 0.0),
+    _case("nan_few_k50_p_wide", 151936, "nan_few", 50, 0.8, top_p=0.9, n=300),
+    _case("nan_few_v5", 5, "nan_few", 50, 0.8, n=16),   # every logit NaN: 5 tokens, 5 NaN
+    _case("nan_few_ban", 4096, "nan_few", 32, 0.8, ban=(1, 10**6, "argmax"), n=300),
+    _case("nan_block_k32", 32000, "nan_block", 32, 0.8, entry="topk", n=300),
+    _case("nan_block_k50_greedy", 4096, "nan_block", 50, 0.0),
+    _case("nan_block_k50_p", 32000, "nan_block", 50, 0.8, top_p=0.9, n=300),
+    _case("nan_block_k1_wide", 262144, "nan_block", 1, 0.8, n=16),
+    _case("nan_block_v100", 100, "nan_block", 50, 0.8, n=300),   # slices of one logit: one NaN, 99 candidates
+    _case("nan_all_k1", 4096, "nan_all", 1, 0.0, entry="topk"),
+    _case("nan_all_k50", 32000, "nan_all", 50, 0.8, n=16),
+    _case("nan_all_k32_p_wide", 151936, "nan_all", 32, 0.8, top_p=0.9, n=16),
+]
+CASE_BY_NAME = {c.name: c for c in CASES + NAN_CASES}
+assert len(CASE_BY_NAME) == len(CASES) + len(NAN_CASES)
 
 
 def case_inputs(c):

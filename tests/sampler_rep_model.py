@@ -80,6 +80,7 @@ def run(logits, n, top_k, T, top_p=1.0, seed=0, counter=0, pos=0, ban=None, seq_
     sup = np.asarray([t for t in suppress if 0 <= t < V], dtype=np.int64)
     if fault != "suppress_ignored":
         dead[sup] = True
+    dead[np.isnan(v32)] = True  # a NaN logit of either sign is never a candidate (sampler_model.py): it ranks with the suppressed ids
     drop_after = dead if fault == "suppressed_counts_to_top_k" else None  # (fault: selected with the others, removed behind the top-k)
     sel_dead = np.zeros(V, dtype=bool) if drop_after is not None else dead
     img0 = image32(v32)

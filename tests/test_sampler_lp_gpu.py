@@ -241,3 +241,50 @@ def test_argument_forms():
         assert out["ctr"][0] == one.counter and out["pos"][0] == one.pos0 and out["tok"][0] == -5, kw
         for k in ("nt", "seq", "raw", "drawn", "ws", "wv", "x", "ssq"):
             assert (out[k].view(np.uint8) == guarded.POISON).all(), (kw, k)
+
+
+def _nan_seen_case():
+    """the penalised NaN: the NaN ids of nan_few are in the history (s = NaN * rp or NaN / rp is NaN: the fp32 keys)"""
+    ids = tuple(int(t) for t in np.flatnonzero(np.isnan(sm.profile("nan_few", 4096).astype(np.float32))))
+    return rm._case("nan_few_seen_rp1.3", 4096, "nan_few", 50, 0.8, 1.3, seen0=ids + (17, 18), n=300)
+
+
+NAN_LP_CASES = [c for c in sm.NAN_CASES if c.entry in ("ex", "p")] + [_nan_seen_case()]
+
+
+@pytest.mark.parametrize("c", NAN_LP_CASES, ids=lambda c: c.name)
+def test_nan_logits_through_rep_and_lp(c):
+    """NaN logits through gq_sample_topk_rep and gq_sample_topk_lp: no NaN token is drawn and the decided draws are the model's; lp_raw,
+    whose sum runs over ALL logits, is NaN for every draw (no hiding); lp_drawn is taken over the kept candidates and keeps the bound of
+    test_case; all logits NaN: the empty set's token and NaN in both"""
+    x, kw = lp.case_args(c)
+    old, new = _run(c, "rep"), _run(c, "lp", check_each=True)
+    assert _same_state(old, new) == [], c.name
+    got = new["nt"][:c.n].astype(np.int64)
+    nan = np.isnan(x.astype(np.float32))
+    if hasattr(c, "rp"):
+        m = rm.case_run(c)
+    else:
+        m = sm.case_run(c)
+    dec = ~m.undecided
+    assert np.array_equal(got[dec], m.tokens[dec]), ("decided draws differ", c.name, [(i, int(got[i]), int(m.tokens[i])) for i in np.nonzero(dec & (got != m.tokens))[0][:8]])
+    live = got != rm.EMPTY_TOKEN
+    assert not nan[got[live]].any() and live.all() != nan.all()
+    sl = slice(c.pos0 + 1, c.pos0 + c.n + 1)
+    assert np.isnan(new["raw"][sl]).all(), (c.name, "lp_raw hides a NaN logit", new["raw"][sl][:8])
+    if nan.all():
+        assert np.isnan(new["drawn"][sl]).all()
+        return
+    model = lp.run(x, got, lp_cap=c.pos0 + c.n + 2, **kw)
+    compared = 0
+    for d in model.draws:
+        g = float(new["drawn"][d.slot])
+        assert np.isnan(d.raw) and d.member
+        if c.top_k == 1:
+            assert g == 0.0
+        if c.T == 0.0:
+            assert np.isfinite(g) and g <= 0.0
+        elif c.top_p >= 1.0 or d.decided:
+            assert abs(g - d.drawn) <= _bound(d.a, d.lse_drawn), (c.name, d.slot, g, d.drawn)
+            compared += 1
+    assert c.T == 0.0 or compared >= c.n // 2

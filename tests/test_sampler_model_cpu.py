@@ -219,3 +219,56 @@ def test_fault_table():
         assert any(h.startswith(CAUGHT_BY[f] + " ") for h in hits), (f, hits)
     print("\n" + "\n".join(lines))
     assert _old_frequency_bound_passes(None)
+
+
+# ------------------------------------------------------------------------------------------------ NaN logits
+def test_nan_profiles_are_what_their_names_say():
+    for V in (4096, 32000, 151936):
+        x = sm.profile("nan_few", V)
+        b = x.view(np.uint16)
+        nan = np.isnan(x.astype(np.float32))
+        clean = sm.profile("gauss", V)   # (the same generator state: the finite logits are the gauss profile's)
+        assert nan.sum() == 5 and nan[int(np.argmax(clean.astype(np.float32)))] and np.array_equal(x[~nan], clean[~nan])
+        assert (b[nan] >= 0x8000).any() and (b[nan] < 0x8000).any() and 0x7C01 in b[nan].tolist()
+        y = sm.profile("nan_block", V)
+        per = -(-V // sm.BLOCKS)
+        blk = np.flatnonzero(np.isnan(y.astype(np.float32)))
+        assert blk.size == per and blk[0] % per == 0 and blk[-1] == blk[0] + per - 1 and blk[0] <= int(np.argmax(clean.astype(np.float32))) <= blk[-1]
+        assert np.isnan(sm.profile("nan_all", V).astype(np.float32)).all() and np.unique(sm.profile("nan_all", V).view(np.uint16)).size == 2
+
+
+@pytest.mark.parametrize("name", [c.name for c in sm.NAN_CASES])
+def test_nan_logits_are_never_candidates(name):
+    """the draws are those of the same logits with every NaN entry banned: here, replaced by -inf, which is never drawn while a finite
+    candidate exists and never displaces one; all NaN: the empty set's token"""
+    c = sm.CASE_BY_NAME[name]
+    x, ban = sm.case_inputs(c)
+    m = _run(name)
+    nan = np.isnan(x.astype(np.float32))
+    assert nan.any() and not nan[m.tokens[m.tokens != sm.EMPTY_TOKEN]].any()
+    if nan.all():
+        assert (m.tokens == sm.EMPTY_TOKEN).all() and m.n_candidates == [0] * len(m.n_candidates) and m.tok == sm.EMPTY_TOKEN
+        assert m.pos == c.pos0 + c.n and not m.undecided.any()
+        return
+    y = x.copy()
+    y[nan] = -np.inf
+    r = sm.run(y, c.n, c.top_k, c.T, c.top_p, c.seed, c.counter, c.pos0, ban, c.seq_cap)
+    assert np.array_equal(r.tokens, m.tokens) and np.array_equal(r.undecided, m.undecided) and float(m.undecided.mean()) <= 0.05
+    assert np.isfinite(x[m.tokens].astype(np.float32)).all()
+
+
+@pytest.mark.parametrize("fault", sm.NAN_FAULTS)
+def test_nan_faults_change_decided_draws(fault):
+    """a NaN that wins the draw, and a negative NaN treated differently from a positive one: each changes decided draws of committed cases"""
+    caught = []
+    for c in sm.NAN_CASES:
+        good, bad = _run(c.name), sm.case_run(c, fault)
+        if (good.tokens != bad.tokens)[~good.undecided].any():
+            caught.append(c.name)
+    print(fault, "caught by", caught)
+    assert len(caught) >= 3 and any("nan_all" in n for n in caught)
+    if fault == "nan_wins":   # the positive NaN planted where the arg-max would be takes every draw
+        c = sm.CASE_BY_NAME["nan_few_k50"]
+        x = sm.profile(c.prof, c.V)
+        t = sm.case_run(c, fault).tokens
+        assert np.isnan(x[t].astype(np.float32)).all()
