@@ -614,6 +614,115 @@ class AnyPrecisionForCausalLM(nn.Module):
         k = int(cont.numel())
         return float(r["logprobs"][-k:].double().sum()), bool(r["greedy"][-k:].all())
 
+    # -- scoring many sequences: packs of short sequences through one prompt pass each ----------------------------------------
+    def _checked_ids(self, input_ids, what):
+        """`score`'s validation of one sequence: its ids as a 1-D host tensor"""
+        ids = torch.as_tensor(input_ids)
+        if ids.is_floating_point() or ids.dim() not in (1, 2) or (ids.dim() == 2 and ids.shape[0] != 1):
+            raise ValueError(f"{what}: every sequence must be token ids, [1, T] or [T]")
+        host = ids.reshape(-1).cpu()
+        if int(host.numel()) < 2:
+            raise ValueError(f"{what}: at least two tokens per sequence (the first one is only ever context)")
+        vocab = int(self.config.vocab_size)
+        if int(host.min()) < 0 or int(host.max()) >= vocab:
+            raise ValueError(f"{what}: token ids must lie in [0, {vocab})")
+        return host
+
+    def _score_packs(self, seqs, tails, pack_tokens, precision, native, what):
+        """[(logprobs fp32 [t_i], greedy bool [t_i])] in input order: the last `tails[i]` log-probabilities of sequence i (None: all of its
+        T_i - 1).  On the fused route the sequences go through `Transformer.score_packed_native` in packs (native_prompt.pack_plan: first
+        fit in input order), and only the rows asked for reach the scoring head; a sequence longer than a pack, and every sequence off the
+        fused route, goes through `score`."""
+        if pack_tokens is not None and int(pack_tokens) < 2:
+            raise ValueError(f"{what}: pack_tokens must be at least 2")
+        from . import native_prompt
+
+        def tail(lp, greedy, t):
+            return (lp, greedy) if t is None else (lp[-t:], greedy[-t:])
+        prev_precision = self.precision
+        if precision is not None:
+            self.set_precision(precision)
+        try:
+            dec, why = None, "opted out"
+            if native is not False:
+                if self.device.type != "cuda":
+                    why = "the fused routes need the GPU"
+                else:
+                    dec = self._native_decoder_or_none(self.precision, release_planes=native is True)
+                    why = getattr(self, "_no_native_reason", None) or "this checkpoint has no fused decode form at %d bits" % self.precision
+                    longest = max((int(s.numel()) for s in seqs), default=0)
+                    if dec is not None and longest > dec.config.block_size:
+                        dec, why = None, f"{longest} tokens exceed the fused model's context ({dec.config.block_size})"
+                    if dec is not None and seqs and not dec.prefill_ready(seqs[0].to(self.device).to(torch.int32)):
+                        dec, why = None, "the fused model's prompt pass does not serve this model"
+            if dec is None and native is True:
+                raise ValueError("native=True: " + why)
+            if dec is None:
+                out = []
+                for s, t in zip(seqs, tails):
+                    r = self.score(s, native=native)
+                    out.append(tail(r["logprobs"], r["greedy"], t))
+                return out
+            capacity = native_prompt.pack_capacity(dec) if pack_tokens is None else min(int(pack_tokens), int(dec.config.block_size))
+            lens = [int(s.numel()) for s in seqs]
+            packs = native_prompt.pack_plan(lens, capacity)
+            out = [None] * len(seqs)
+            rows_max = max((sum(lens[i] for i in p) for p in packs if sum(lens[i] for i in p) <= capacity), default=0)
+            if rows_max:
+                # (the caches as `score` sizes them, allocated outside inference mode; graphs captured over caches about to be replaced go first)
+                cap = min(max(256, 1 << (rows_max - 1).bit_length()), dec.config.block_size)
+                if not (dec.max_seq_length >= cap and dec.max_batch_size >= 1 and dec.kv_cache_dtype == "fp16"):
+                    self._evict("graph")
+                dec.setup_caches(1, cap, kv_cache_dtype="fp16")
+            for p in packs:
+                if sum(lens[i] for i in p) > capacity:  # (one sequence longer than a pack: the one-sequence pass, chunked as it is there)
+                    r = self.score(seqs[p[0]], native=native)
+                    out[p[0]] = tail(r["logprobs"], r["greedy"], tails[p[0]])
+                    continue
+                dev_seqs = [seqs[i].to(self.device).to(torch.int32) for i in p]
+                rows, counts = None, [lens[i] - 1 if tails[i] is None else tails[i] for i in p]
+                if any(tails[i] is not None for i in p):
+                    mask, b = torch.zeros(sum(lens[i] for i in p), dtype=torch.bool), 0
+                    for i, c in zip(p, counts):
+                        mask[b + lens[i] - 1 - c:b + lens[i] - 1] = True
+                        b += lens[i]
+                    rows = mask.to(self.device)
+                with torch.inference_mode():
+                    lp, hit = dec.score_packed_native(dev_seqs, rows)
+                b = 0
+                for i, c in zip(p, counts):
+                    out[i] = (lp[b:b + c], hit[b:b + c])
+                    b += lens[i] if rows is None else c  # (rows None: the head ran on every row, and a sequence's last row is no prediction)
+            return out
+        finally:
+            self.set_precision(prev_precision)
+
+    def score_many(self, list_of_ids, pack_tokens=None, precision=None, native=None):
+        """`score` for many sequences: a list of its dicts (logprobs fp32 [T_i - 1], greedy bool [T_i - 1], nll float) in input order.
+        On the fused route the sequences are packed -- first fit in input order into packs of at most `pack_tokens` rows (default: the
+        smaller of GQ_PREFILL_CHUNK and the model's context) -- and every pack is ONE prompt pass (`Transformer.score_packed_native`:
+        varlen attention, the weights read once per pack instead of once per sequence); a sequence longer than a pack goes through
+        `score`.  A packed result is a rounding of the same model as `score`'s, not bit-equal to it: the GEMMs see other row counts.
+        Validation, `precision` and `native` as in `score`: off the fused route (native=False, no fused form, the CPU) this is a loop
+        over `score`, and native=True raises instead of falling back.  fp16 KV cache."""
+        seqs = [self._checked_ids(ids, "score_many") for ids in list_of_ids]
+        res = self._score_packs(seqs, [None] * len(seqs), pack_tokens, precision, native, "score_many")
+        return [dict(logprobs=lp, greedy=g, nll=float(-lp.double().mean())) for lp, g in res]
+
+    def loglikelihood_many(self, pairs, pack_tokens=None, precision=None, native=None):
+        """`loglikelihood` for many (context, continuation) pairs -- the requests lm-eval issues by the thousand: a list of (sum of the
+        continuation's log-probabilities, all of them greedy) in input order, packed like `score_many`.  Only the rows that predict a
+        continuation token reach the final norm and the lm_head."""
+        seqs, tails = [], []
+        for ctx, cont in pairs:
+            ctx, cont = torch.as_tensor(ctx).reshape(-1), torch.as_tensor(cont).reshape(-1)
+            if ctx.numel() < 1 or cont.numel() < 1:
+                raise ValueError("loglikelihood_many: a context and a continuation of at least one token each")
+            seqs.append(self._checked_ids(torch.cat([ctx.cpu(), cont.cpu()]), "loglikelihood_many"))
+            tails.append(int(cont.numel()))
+        res = self._score_packs(seqs, tails, pack_tokens, precision, native, "loglikelihood_many")
+        return [(float(lp.double().sum()), bool(g.all())) for lp, g in res]
+
     # -- route 1: the fused decode model ---------------------------------------------------------------------------------
     _SAMPLER_SEED = 0x2545F491  # (a constant: what varies between sampled calls is the counter word, drawn from torch's generator)
 

@@ -29,7 +29,7 @@ EXPORTS = [
     "gq_attn_decode_split_window", "gq_attn_decode_split_qknorm_window", "gq_attn_decode_split_bias_window", "gq_attn_decode_roped_window",
     "gq_token_set_build", "gq_sample_topk_rep", "gq_attn_prefill_supported", "gq_attn_prefill",
     "gq_rope_cache_rows_kv8", "gq_attn_decode_roped_kv8", "gq_attn_prefill_kv8", "gq_head_nll_ws_bytes", "gq_head_nll",
-    "gq_sample_topk_lp",
+    "gq_sample_topk_lp", "gq_attn_prefill_packed", "gq_rope_cache_rows_packed",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -153,6 +153,9 @@ def lib():
         L.gq_rope_cache_rows_kv8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, f32, vp, vp]
         L.gq_attn_decode_roped_kv8.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, u32, vp]
         L.gq_attn_prefill_kv8.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, f32, u32, vp]
+        # (the packed pass: seg_begin behind the caches and no start; pos, row in front of the tables)
+        L.gq_attn_prefill_packed.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, f32, u32, vp]
+        L.gq_rope_cache_rows_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, f32, vp]
         # (the scoring head: xn, W, target, S, V, D, logprob, lse, top1, splits, ws, ws_bytes, stream)
         L.gq_head_nll_ws_bytes.argtypes = [u32, u32, u32, u32]
         L.gq_head_nll.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp, u32, vp, ctypes.c_size_t, vp]

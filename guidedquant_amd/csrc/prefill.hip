@@ -190,15 +190,24 @@ struct CacheElem<true> {
 //   (x.float() * rsqrt(ssq / HD + eps)).half() * weight -- the rounding points of gq_rmsnorm_rows -- and the rotation.  v is not normed.
 // QB: the bias of the q / k / v linears (fp16, laid out like a qkv row), ONE fp16 add in front of the rotation (decode.hip, AttnBias).
 //   Only the fp8 decode step has it: the prompt pass's linears add the bias themselves, so no fp16 form is instantiated.
+// PKD (gq_rope_cache_rows_packed: several sequences as one run of rows): the cache row is tail.row[s], apart from the RoPE position
+//   pos[s] inside the row's own sequence.  Every other form has the empty tail and writes row pos[s].
 // The loop bound is block-uniform in every form (QKN needs it: whole groups are active or idle together, total is a multiple of HD / 16).
-template <bool QKN, bool QB, bool KV8>
+template <bool PKD>
+struct RowsTail {};
+template <>
+struct RowsTail<true> {
+    const int *row;
+};
+
+template <bool QKN, bool QB, bool KV8, bool PKD = false>
 __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__restrict__ qkv, const int *__restrict__ pos,
                                                               const uint16_t *__restrict__ cos_t, const uint16_t *__restrict__ sin_t,
                                                               uint16_t *__restrict__ q_out, typename CacheElem<KV8>::type *__restrict__ kc,
                                                               typename CacheElem<KV8>::type *__restrict__ vc, const float *__restrict__ k_inv,
                                                               const float *__restrict__ v_inv, const uint16_t *__restrict__ qnw,
                                                               const uint16_t *__restrict__ knw, float eps, const uint16_t *__restrict__ bias, u32 S,
-                                                              u32 H, u32 Hkv, u32 HD, u32 max_seq) {
+                                                              u32 H, u32 Hkv, u32 HD, u32 max_seq, RowsTail<PKD> tail) {
     const u32 upr = HD / 16u, heads = H + 2u * Hkv, total = S * heads * upr;  // units of 8 in the first half
     for (u32 base = blockIdx.x * 256u; base < total; base += gridDim.x * 256u) {
         const u32 i = base + threadIdx.x;
@@ -206,6 +215,8 @@ __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__
         const u32 ic = active ? i : 0u;
         const u32 u = ic % upr, hh = (ic / upr) % heads, s = ic / (upr * heads), d = 8u * u;
         const u32 p = (u32)pos[s];
+        u32 cr = p;  // the cache row
+        if constexpr (PKD) cr = (u32)tail.row[s];
         const uint16_t *src = qkv + (size_t)s * heads * HD + (size_t)hh * HD;
         uint4 a = *reinterpret_cast<const uint4 *>(src + d), b = *reinterpret_cast<const uint4 *>(src + d + HD / 2u);
         u32 x1[4] = {a.x, a.y, a.z, a.w}, x2[4] = {b.x, b.y, b.z, b.w};
@@ -243,11 +254,11 @@ __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__
         }
         if (!active) continue;
         if (hh >= H + Hkv) {  // v: stored as it is
-            if (p < max_seq) {
+            if (cr < max_seq) {
                 const u32 g = hh - H - Hkv;
                 float inv = 0.f;
                 if constexpr (KV8) inv = v_inv[g];
-                store_units(vc + ((size_t)g * max_seq + p) * HD, d, HD, x1, x2, inv);
+                store_units(vc + ((size_t)g * max_seq + cr) * HD, d, HD, x1, x2, inv);
             }
             continue;
         }
@@ -276,11 +287,11 @@ __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__
         rope_unit(a, b, cos_t, sin_t, p, max_seq, HD, d, o1, o2);
         if (hh < H) {
             store_units(q_out + ((size_t)hh * S + s) * HD, d, HD, o1, o2, 0.f);
-        } else if (p < max_seq) {
+        } else if (cr < max_seq) {
             const u32 g = hh - H;
             float inv = 0.f;
             if constexpr (KV8) inv = k_inv[g];
-            store_units(kc + ((size_t)g * max_seq + p) * HD, d, HD, o1, o2, inv);
+            store_units(kc + ((size_t)g * max_seq + cr) * HD, d, HD, o1, o2, inv);
         }
     }
 }
@@ -333,7 +344,7 @@ struct RowsEntry {
 // the bias form with a bias, the fp8 form with `kv8` (k_inv / v_inv are read by that form only)
 int rope_cache_rows(const RowsEntry &e, bool kv8, const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
                     void *v_cache, const float *k_inv, const float *v_inv, u32 S, u32 n_head, u32 n_kv_head, u32 head_dim, u32 max_seq,
-                    const void *q_norm_weight, const void *k_norm_weight, float eps, const void *qkv_bias, void *stream) {
+                    const void *q_norm_weight, const void *k_norm_weight, float eps, const void *qkv_bias, void *stream, const int *row = nullptr) {
     if (S == 0) return GQ_OK;
     // (QKN: the statistic of a head is added inside an aligned group of head_dim / 16 lanes: a power of two, within one wave)
     const bool hd_ok = e.any_hd16 ? (head_dim != 0 && head_dim % 16u == 0) : (head_dim == 64u || head_dim == 128u);
@@ -345,19 +356,24 @@ int rope_cache_rows(const RowsEntry &e, bool kv8, const void *qkv, const int *po
     if (total >= 0x7FFFFFFFull) return gq_fail(GQ_ENOTSUP, e.too_large);
     const u32 nb = (u32)((total + 255u) / 256u);
     const dim3 grid(nb > 65535u ? 65535u : nb), block(256);
-#define GQ_LAUNCH_ROWS(QKN_, QB_, KV8_)                                                                                                       \
-    hipLaunchKernelGGL((rope_cache_rows_kernel<QKN_, QB_, KV8_>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)qkv, pos,            \
+#define GQ_LAUNCH_ROWS(QKN_, QB_, KV8_, PKD_, TAIL_)                                                                                          \
+    hipLaunchKernelGGL((rope_cache_rows_kernel<QKN_, QB_, KV8_, PKD_>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)qkv, pos,      \
                        (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)q_out, (CacheElem<KV8_>::type *)k_cache,         \
                        (CacheElem<KV8_>::type *)v_cache, k_inv, v_inv, (const uint16_t *)q_norm_weight, (const uint16_t *)k_norm_weight, eps, \
-                       (const uint16_t *)qkv_bias, S, n_head, n_kv_head, head_dim, max_seq)
-    if (kv8) {
-        if (q_norm_weight) GQ_LAUNCH_ROWS(true, false, true);
-        else if (qkv_bias) GQ_LAUNCH_ROWS(false, true, true);
-        else GQ_LAUNCH_ROWS(false, false, true);
+                       (const uint16_t *)qkv_bias, S, n_head, n_kv_head, head_dim, max_seq, TAIL_)
+    const RowsTail<false> none = {};
+    const RowsTail<true> rows = {row};
+    if (row) {  // (the packed pass: fp16 caches)
+        if (q_norm_weight) GQ_LAUNCH_ROWS(true, false, false, true, rows);
+        else GQ_LAUNCH_ROWS(false, false, false, true, rows);
+    } else if (kv8) {
+        if (q_norm_weight) GQ_LAUNCH_ROWS(true, false, true, false, none);
+        else if (qkv_bias) GQ_LAUNCH_ROWS(false, true, true, false, none);
+        else GQ_LAUNCH_ROWS(false, false, true, false, none);
     } else if (q_norm_weight) {
-        GQ_LAUNCH_ROWS(true, false, false);
+        GQ_LAUNCH_ROWS(true, false, false, false, none);
     } else {
-        GQ_LAUNCH_ROWS(false, false, false);
+        GQ_LAUNCH_ROWS(false, false, false, false, none);
     }
 #undef GQ_LAUNCH_ROWS
     GQ_HIP_CHECK(hipGetLastError());
@@ -408,6 +424,21 @@ extern "C" int gq_rope_cache_rows_kv8(const void *qkv, const int *pos, const voi
                                 "gq_rope_cache_rows_kv8: problem too large."};
     return rope_cache_rows(e, true, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, k_inv, v_inv, S, n_head, n_kv_head, head_dim, max_seq, q_norm_weight,
                            k_norm_weight, eps, qkv_bias, stream);
+}
+
+extern "C" int gq_rope_cache_rows_packed(const void *qkv, const int *pos, const int *row, const void *cos_table, const void *sin_table, void *q_out,
+                                         void *k_cache, void *v_cache, uint32_t S, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                                         const void *q_norm_weight, const void *k_norm_weight, float eps, void *stream) {
+    if (!qkv || !pos || !row || !cos_table || !sin_table || !q_out || !k_cache || !v_cache) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    const bool qkn = q_norm_weight || k_norm_weight;
+    if (qkn && (!q_norm_weight || !k_norm_weight)) return gq_fail(GQ_EINVAL, "gq_rope_cache_rows_packed: both norm weights or none.");
+    // (the head_dims of the entry each form restates: any multiple of 16 without the norm, 64 and 128 with it)
+    static const RowsEntry plain = {true, "gq_rope_cache_rows_packed: head_dim must be a multiple of 16.", "gq_rope_cache_rows_packed: 16-byte aligned pointers.",
+                                    "gq_rope_cache_rows_packed: problem too large."};
+    static const RowsEntry norm = {false, "gq_rope_cache_rows_packed: head_dim must be 64 or 128 with the norm weights.",
+                                   "gq_rope_cache_rows_packed: 16-byte aligned pointers.", "gq_rope_cache_rows_packed: problem too large."};
+    return rope_cache_rows(qkn ? norm : plain, false, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim,
+                           max_seq, q_norm_weight, k_norm_weight, eps, nullptr, stream, row);
 }
 
 extern "C" int gq_silu_mul_rows(const void *y, void *out, uint32_t S, uint32_t inter, int paired, void *stream) {

@@ -84,11 +84,39 @@ struct TileFmt<true> {
     }
 };
 
-template <int HD, bool KV8 = false>
+// the kernel's last argument: the scales of an fp8 cache, or -- PACKED, fp16 caches -- the segment begins (an instance that is neither
+// keeps the empty struct it had: its arguments and its code are those of the kernel without the flag)
+template <bool KV8, bool PACKED>
+struct TailArg {
+    typedef typename TileFmt<KV8>::Scales type;
+};
+template <>
+struct TailArg<false, true> {
+    struct type {
+        const int *seg_begin;
+    };
+};
+
+// PACKED: the first key row `i` attends: its segment's begin, clamped to i (a malformed array never leaves rows [0, S)), or the window's
+__device__ __forceinline__ u32 packed_lo(const int *__restrict__ seg_begin, u32 i, u32 window) {
+    const u32 sb = min((u32)seg_begin[i], i);
+    return (window && i + 1u > window) ? max(sb, i + 1u - window) : sb;
+}
+
+// PACKED (gq_attn_prefill_packed): N sequences as one run of S rows from cache row 0.  Row i attends max(seg_begin[i], i + 1 - window)
+// <= t <= i.  Both bounds are non-decreasing in i, so the block's first tile comes from its first row, a wave's rows attend one run of
+// keys [lo of its first row, its last row], and a tile every row of the wave attends whole lies inside ONE segment.  Every other visited
+// tile is an edge tile: the element mask gets the term t >= lo(i), and the second product runs once per segment among the wave's 16
+// rows, with the V fragment's keys outside [that segment's begin, its last row in the wave] replaced by zeros and the result kept by
+// that segment's rows only -- P = 0 alone does not keep another sequence's rows out: 0 x NaN inside an MFMA is NaN.  For a row the
+// products and their order are those of the one-sequence kernel (a masked key adds +-0 either way), so row i is bit for bit row i of
+// gq_attn_prefill(S = i + 1, start = 0, window = min(i - seg_begin[i] + 1, window)).
+template <int HD, bool KV8 = false, bool PACKED = false>
 __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__restrict__ q, const typename TileFmt<KV8>::elem *__restrict__ kc,
                                                            const typename TileFmt<KV8>::elem *__restrict__ vc, uint16_t *__restrict__ out, u32 S,
                                                            u32 start, u32 H, u32 group, u32 max_seq, float c, u32 window,
-                                                           typename TileFmt<KV8>::Scales sc) {
+                                                           typename TailArg<KV8, PACKED>::type sc) {
+    static_assert(!(KV8 && PACKED), "the packed pass has fp16 caches");
     using Fmt = TileFmt<KV8>;
     using Chunk = typename Fmt::chunk;
     constexpr u32 LD = HD + 8;             // halves per LDS row: 16 bytes of padding
@@ -107,7 +135,9 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
 
     // the block's key range: [klo, khi] covers every key one of its rows attends
     const u32 p_lo = start + q0, khi = start + min(q0 + BQ - 1u, S - 1u);
-    const u32 klo = (window && p_lo + 1u > window) ? p_lo + 1u - window : 0u;
+    u32 klo;
+    if constexpr (PACKED) klo = packed_lo(sc.seg_begin, q0, window);  // (start == 0: a position is a row)
+    else klo = (window && p_lo + 1u > window) ? p_lo + 1u - window : 0u;
     const u32 kt0 = klo / BK, kt1 = khi / BK;
 
     // the wave's rows (rows >= S repeat row S - 1 and are not stored)
@@ -115,6 +145,14 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
     const bool wave_active = wq0 < S;
     const u32 qrow = wq0 + li, qi = min(qrow, S - 1u), p = start + qi;
     const u32 pmin = start + min(wq0, S - 1u), pmax = start + min(wq0 + 15u, S - 1u);
+    // PACKED: the row's own first key and segment begin; the first keys of the wave's first and last row (lanes 0 and 15)
+    u32 lo = 0u, sb = 0u, lo_min = 0u, lo_max = 0u;
+    if constexpr (PACKED) {
+        lo = packed_lo(sc.seg_begin, qi, window);
+        sb = min((u32)sc.seg_begin[qi], qi);
+        lo_min = (u32)__builtin_amdgcn_readlane((int)lo, 0);
+        lo_max = (u32)__builtin_amdgcn_readlane((int)lo, 15);
+    }
 
     h16x8 qf[KS];
     {
@@ -157,8 +195,14 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
 
         const u32 tb = kt * BK;
         // (wave-uniform: EXEC stays full for the transposed reads)
-        if (!(wave_active && tb <= pmax && (window == 0u || tb + (BK - 1u) + window > pmin))) continue;
-        const bool edge = tb + (BK - 1u) > pmin || (window != 0u && tb + window <= pmax);
+        bool edge;
+        if constexpr (PACKED) {
+            if (!(wave_active && tb <= pmax && tb + (BK - 1u) >= lo_min)) continue;
+            edge = tb + (BK - 1u) > pmin || tb < lo_max;
+        } else {
+            if (!(wave_active && tb <= pmax && (window == 0u || tb + (BK - 1u) + window > pmin))) continue;
+            edge = tb + (BK - 1u) > pmin || (window != 0u && tb + window <= pmax);
+        }
 
         f32x4 s[4];
 #pragma unroll
@@ -179,7 +223,8 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
 #pragma unroll
             for (u32 r = 0; r < 4; r++) {
                 const u32 t = tb + 32u * (b >> 1) + 8u * g + 4u * (b & 1u) + r;
-                ok[b][r] = !edge || (t <= p && (window == 0u || t + window > p));
+                if constexpr (PACKED) ok[b][r] = !edge || (t <= p && t >= lo);
+                else ok[b][r] = !edge || (t <= p && (window == 0u || t + window > p));
                 const float x = s[b][r] * c;
                 s[b][r] = ok[b][r] ? x : NEG;
                 mloc = fmaxf(mloc, s[b][r]);
@@ -203,6 +248,38 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
             }
         }
         l_run = l_run * alpha + psum;
+        if constexpr (PACKED) {
+            if (edge) {
+#pragma unroll
+                for (u32 d = 0; d < DB; d++) o[d] *= alpha;
+                unsigned long long todo = 0xFFFFull;  // the wave's 16 queries (lanes 0 .. 15 hold one each), a segment at a time
+                while (todo) {
+                    const u32 sfirst = (u32)__builtin_amdgcn_readlane((int)sb, __builtin_ctzll(todo));
+                    const bool mine = sb == sfirst;
+                    const unsigned long long members = __ballot(mine) & 0xFFFFull;  // (never empty: the lane read from is one)
+                    todo &= ~members;
+                    const u32 slast = (u32)__builtin_amdgcn_readlane((int)p, 63 - __builtin_clzll(members));
+#pragma unroll
+                    for (u32 d = 0; d < DB; d++) {
+#pragma unroll
+                        for (u32 cc = 0; cc < 2; cc++) {
+                            const h16 *vp = &sV[(32u * cc + 8u * g + (li >> 2)) * LD + 16u * d + 4u * (li & 3u)];
+                            const h16x4 vlo = lds_read_tr(vp), vhi = lds_read_tr(vp + 4u * LD);
+                            h16x8 a = __builtin_shufflevector(vlo, vhi, 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+                            for (u32 j = 0; j < 8; j++) {
+                                const u32 t = tb + 32u * cc + 8u * g + j;
+                                a[j] = (t >= sfirst && t <= slast) ? a[j] : (h16)0.f;
+                            }
+                            const f32x4 on = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, pf[cc], o[d], 0, 0, 0);
+#pragma unroll
+                            for (u32 r = 0; r < 4; r++) o[d][r] = mine ? on[r] : o[d][r];
+                        }
+                    }
+                }
+                continue;
+            }
+        }
 #pragma unroll
         for (u32 d = 0; d < DB; d++) {
             o[d] *= alpha;
@@ -237,14 +314,18 @@ extern "C" int gq_attn_prefill_supported(uint32_t n_head, uint32_t n_kv_head, ui
 }
 
 namespace {
-template <bool KV8>
+template <bool KV8, bool PACKED = false>
 int prefill_attn_launch(const void *q, const void *k_cache, const void *v_cache, void *out, uint32_t S, uint32_t start, uint32_t n_head,
                         uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t window, void *stream,
-                        typename TileFmt<KV8>::Scales sc) {
+                        typename TailArg<KV8, PACKED>::type sc) {
     using CE = typename TileFmt<KV8>::elem;
     if (!gq_attn_prefill_supported(n_head, n_kv_head, head_dim))
         return gq_fail(GQ_ENOTSUP, "gq_attn_prefill: head_dim 64 or 128, n_head a multiple of n_kv_head.");
     if (!q || !k_cache || !v_cache || !out) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    if constexpr (PACKED) {
+        if (!sc.seg_begin) return gq_fail(GQ_EINVAL, "null pointer argument.");
+        if (S == 0) return gq_fail(GQ_EINVAL, "gq_attn_prefill_packed: no rows.");
+    }
     if (((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)out) & 15u) return gq_fail(GQ_EINVAL, "gq_attn_prefill: 16-byte aligned pointers.");
     const uint64_t T = (uint64_t)start + S;
     if (T > max_seq) return gq_fail(GQ_EINVAL, "gq_attn_prefill: start + S exceeds max_seq.");
@@ -255,10 +336,10 @@ int prefill_attn_launch(const void *q, const void *k_cache, const void *v_cache,
     const dim3 grid((S + BQ - 1u) / BQ, n_head), block(256);
     const uint32_t group = n_head / n_kv_head;
     if (head_dim == 64u)
-        hipLaunchKernelGGL((prefill_attn_kernel<64, KV8>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
+        hipLaunchKernelGGL((prefill_attn_kernel<64, KV8, PACKED>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
                            (uint16_t *)out, S, start, n_head, group, max_seq, c, window, sc);
     else
-        hipLaunchKernelGGL((prefill_attn_kernel<128, KV8>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
+        hipLaunchKernelGGL((prefill_attn_kernel<128, KV8, PACKED>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
                            (uint16_t *)out, S, start, n_head, group, max_seq, c, window, sc);
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
@@ -275,4 +356,10 @@ extern "C" int gq_attn_prefill_kv8(const void *q, const void *k_cache, const voi
                                    uint32_t window, void *stream) {
     if (!k_scale || !v_scale) return gq_fail(GQ_EINVAL, "null pointer argument.");
     return prefill_attn_launch<true>(q, k_cache, v_cache, out, S, start, n_head, n_kv_head, head_dim, max_seq, scale, window, stream, {k_scale, v_scale});
+}
+
+extern "C" int gq_attn_prefill_packed(const void *q, const void *k_cache, const void *v_cache, const int *seg_begin, void *out, uint32_t S,
+                                      uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t window,
+                                      void *stream) {
+    return prefill_attn_launch<false, true>(q, k_cache, v_cache, out, S, 0u, n_head, n_kv_head, head_dim, max_seq, scale, window, stream, {seg_begin});
 }

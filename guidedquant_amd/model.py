@@ -620,6 +620,17 @@ class Transformer(nn.Module):
         `last_prefill_plan["head"]` records it ("hip-nll" | "torch").  The caches hold the sequence afterwards, as after a prompt."""
         return native_prompt.score(self, idx, chunk)
 
+    def score_packed_native(self, seqs, rows: Optional[Tensor] = None):
+        """Log-probabilities of SEVERAL token sequences in one HIP prompt pass (varlen attention): the sequences are laid end to end as
+        one run of S rows from cache row 0 and go through every layer as ONE piece, so the weights are read once per pack.  Row i is
+        rotated by its position inside its own sequence (gq_rope_cache_rows_packed) and attends only rows of its own sequence, causally
+        and within the layer's window (gq_attn_prefill_packed; under GQ_PREFILL_ATTN=0 or an unserved geometry SDPA with the
+        block-diagonal mask).  `rows` (bool [S]): only these rows reach the final norm and the scoring head.  Returns (logprob fp32 [k],
+        hit bool [k]) over the head's rows in packed order (native_prompt.score_packed).  fp16 caches only; the caches grow to S rows
+        where they are smaller and hold the pack afterwards.  `last_prefill_plan` records chunks=[(0, S)], attn "hip-packed" |
+        "sdpa-packed" per layer, the head and packed=dict(sequences, rows, head_rows)."""
+        return native_prompt.score_packed(self, seqs, rows)
+
     def decode_native(self, tok: Tensor, pos: Tensor) -> Tensor:
         """One bs=1 decode step.  tok, pos: int32 device tensors with one element.  Returns logits fp16 [1,1,V]
         (a persistent buffer, like the quantized linears' outputs).  Enqueues on the current stream only."""

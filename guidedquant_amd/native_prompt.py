@@ -11,6 +11,9 @@ through the C ABI (include/gq_hip.h) and the quantized linears' own forwards.
   * the heads: logits (`Transformer.output`), or the scoring head (`score_head`: gq_head_nll, or log_softmax in row blocks), chosen by
     `score_head_choice`, a pure function of the GQ_SCORE_HEAD mode.
 
+  * packed scoring: `pack_plan` (first fit in input order) and `score_packed` -- several short sequences as ONE piece, `_PackedPiece`'s
+    `rows_and_attention` through gq_rope_cache_rows_packed and gq_attn_prefill_packed (or SDPA under the block-diagonal `packed_mask`).
+
 `Transformer` keeps `prefill_ready`, `prefill_native`, `score_native` and `_score_head` as delegations to this module, and the attributes the
 pass reads and writes on the model (`last_prefill_plan`, `SCORE_HEAD_ROWS`, `SCORE_HEAD_AUTO`).  What a pass launches, in which order, with
 which arguments, is pinned by tests/golden/prefill_calls.json.
@@ -266,3 +269,121 @@ def score(model, idx, chunk: Optional[int] = None):
     lp = torch.cat([o[0] for o in out])[:S - 1]
     top1 = torch.cat([o[1] for o in out])[:S - 1]
     return lp, top1 == flat[1:]
+
+
+# ------------------------------------------------------------------------------------------------ packed scoring
+def pack_capacity(model) -> int:
+    """the rows of a pack where the caller names none: a chunk of the prompt pass, within the model's context"""
+    return min(int(os.environ.get("GQ_PREFILL_CHUNK", "4096")), int(model.config.block_size))
+
+
+def pack_plan(lengths, capacity: int):
+    """Groups the sequences 0 .. n - 1 of the given lengths into packs of at most `capacity` rows: first fit in input order -- a sequence
+    goes into the first pack it still fits into, else it opens a new pack -- so the same lengths always give the same packs, the indices
+    ascend inside a pack and the packs are ordered by their first index.  A sequence longer than `capacity` is a pack of its own (the
+    caller scores it through the one-sequence pass).  Pure host logic."""
+    capacity = int(capacity)
+    if capacity < 1:
+        raise ValueError(f"pack_plan: capacity {capacity}")
+    packs, room = [], []
+    for i, n in enumerate(lengths):
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"pack_plan: sequence {i} has length {n}")
+        for j, r in enumerate(room):
+            if n <= r:
+                packs[j].append(i)
+                room[j] -= n
+                break
+        else:
+            packs.append([i])
+            room.append(capacity - n if n <= capacity else 0)
+    return packs
+
+
+def packed_mask(seg_begin: Tensor, window: Optional[int] = None) -> Tensor:
+    """bool [S, S]: packed row i attends row t when max(seg_begin[i], i + 1 - window) <= t <= i -- the causal (and window) masks of the
+    sequences, block-diagonal"""
+    S = seg_begin.numel()
+    i = torch.arange(S, device=seg_begin.device)[:, None]
+    t = torch.arange(S, device=seg_begin.device)[None, :]
+    m = (t <= i) & (t >= seg_begin.long()[:, None])
+    return m if window is None else m & (t > i - int(window))
+
+
+class _PackedPiece(_Piece):
+    """a pack as one piece: the position of a row inside its sequence apart from its cache row, and a segment begin per row"""
+
+    def __init__(self, model, pos, row, seg_begin, bufs: dict, plan: str):
+        super().__init__(model, pos, 0, bufs, plan)
+        self.row, self.seg_begin = row, seg_begin
+
+    def rows_and_attention(self, att, qkv, win, st):
+        """gq_rope_cache_rows_packed (the rotation by the position inside the sequence, k / v to the packed row), then
+        gq_attn_prefill_packed or SDPA under the block-diagonal mask over the cache rows [0, S)"""
+        m, cfg, L, kvc = self.m, self.m.config, _lib.lib(), att.kv_cache
+        S, H, Hkv, hd = self.S, cfg.n_head, cfg.n_local_heads, cfg.head_dim
+        kc, vc = kvc.k_cache, kvc.v_cache
+        norm = native_step.qk_norm_args(att, cfg)  # (null weights: the plain form)
+        _lib.check(L.gq_rope_cache_rows_packed(qkv.data_ptr(), self.pos.data_ptr(), self.row.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(),
+                                               self.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), S, H, Hkv, hd, kc.shape[2], *norm, st), "gq_rope_cache_rows_packed")
+        if self.plan.startswith("hip"):
+            _lib.check(L.gq_attn_prefill_packed(self.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), self.seg_begin.data_ptr(), self.y.data_ptr(), S, H, Hkv, hd,
+                                                kc.shape[2], 1.0 / math.sqrt(hd), 0 if win is None else int(win), st), "gq_attn_prefill_packed")
+            return self.y.view(1, S, H * hd)
+        if win is not None and win >= S:
+            win = None
+        if win not in self.masks:
+            self.masks[win] = packed_mask(self.seg_begin, win)[None, None]
+        return _sdpa_gqa(self.q.unsqueeze(0), kc[:1, :, :S], vc[:1, :, :S], self.masks[win], H // Hkv).transpose(1, 2).reshape(1, S, H * hd)
+
+
+def score_packed(model, seqs, rows: Optional[Tensor] = None):
+    """`Transformer.score_packed_native`: the sequences `seqs` (1-D int tensors on the model's device, two tokens or more each) as ONE
+    piece of S = sum of their lengths rows -- never chunked -- with the scoring head on the rows `rows` (bool [S]; None: every row).
+    Returns (logprob fp32 [k], hit bool [k]) over the head's rows in packed order: logprob of the next token of the row's own sequence
+    and whether it is the most probable one; a sequence's last row has no next token (logprob 0, hit False)."""
+    if model.kv_cache_dtype == "fp8":
+        raise NotImplementedError("packed scoring: fp8 KV cache")
+    cfg = model.config
+    lens = [int(s.numel()) for s in seqs]
+    if not lens or min(lens) < 2:
+        raise ValueError("packed scoring: at least one sequence, two tokens or more each")
+    flat = torch.cat([s.reshape(-1) for s in seqs]).to(torch.int32)
+    S, dev = int(flat.numel()), flat.device
+    if model.max_seq_length < S:
+        model.setup_caches(max(1, model.max_batch_size), S, kv_cache_dtype=model.kv_cache_dtype)
+    assert model.prefill_ready(flat) and max(lens) <= model.max_seq_length
+    H, Hkv, hd = cfg.n_head, cfg.n_local_heads, cfg.head_dim
+    mode = os.environ.get("GQ_PREFILL_ATTN", "auto")
+    attention_plan(mode, 1, False, True)  # (a bad mode raises here)
+    plan = "hip-packed" if mode != "0" and _lib.lib().gq_attn_prefill_supported(H, Hkv, hd) else "sdpa-packed"
+    served = cfg.dim % 64 == 0 and model.output.weight.dtype == torch.float16
+    kernel = score_head_choice(os.environ.get("GQ_SCORE_HEAD", "auto"), served, model.SCORE_HEAD_AUTO)
+    begins = [0]
+    for n in lens[:-1]:
+        begins.append(begins[-1] + n)
+    lens_t = torch.tensor(lens, device=dev)
+    seg_begin = torch.repeat_interleave(torch.tensor(begins, dtype=torch.int32, device=dev), lens_t)
+    row = torch.arange(S, dtype=torch.int32, device=dev)
+    pos = row - seg_begin
+    targets = torch.cat([flat[1:], torch.full((1, ), -1, dtype=torch.int32, device=dev)])
+    targets[torch.tensor([b + n - 1 for b, n in zip(begins, lens)], device=dev)] = -1
+    f16 = dict(dtype=torch.float16, device=dev)
+    bufs = dict(xn=torch.empty((S, cfg.dim), **f16), q=torch.empty((H * S * hd, ), **f16), hbuf=torch.empty((S, cfg.intermediate_size), **f16),
+                y=torch.empty((S, H * hd), **f16) if plan.startswith("hip") else None)
+    x = model.tok_embeddings(flat.view(1, S)).view(S, cfg.dim).contiguous()
+    pending = _PackedPiece(model, pos, row, seg_begin, bufs, plan).layers(x)
+    if rows is None:
+        x = x + pending
+    else:
+        assert rows.dtype == torch.bool and rows.numel() == S
+        sel = torch.nonzero(rows.to(dev)).reshape(-1)
+        x, targets = x[sel] + pending[sel], targets[sel].contiguous()
+    k = int(x.shape[0])
+    model.last_prefill_plan = dict(chunks=[(0, S)], attn=[plan] * len(model.layers), head="hip-nll" if kernel else "torch",
+                                   packed=dict(sequences=len(lens), rows=S, head_rows=k))
+    if k == 0:
+        return torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.bool, device=dev)
+    lp, top1 = score_head(model, x, targets, kernel)
+    return lp, top1 == targets

@@ -203,6 +203,9 @@ class PipelinedDecoder:
     def score_native(self, *args, **kwargs):
         raise NotImplementedError("pipelined scoring is not implemented: score on one device (Transformer.score_native)")
 
+    def score_packed_native(self, *args, **kwargs):
+        raise NotImplementedError("pipelined packed scoring is not implemented: score on one device (Transformer.score_packed_native)")
+
     def close_ipc(self):
         """unmap the peer's slots and free this stage's (after a barrier of the caller's: nobody may still be sending)"""
         from . import _lib

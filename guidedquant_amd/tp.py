@@ -141,6 +141,9 @@ class TensorParallelDecoder:
     def score_native(self, *args, **kwargs):
         raise NotImplementedError("tensor-parallel scoring is not implemented: score on one device (Transformer.score_native)")
 
+    def score_packed_native(self, *args, **kwargs):
+        raise NotImplementedError("tensor-parallel packed scoring is not implemented: score on one device (Transformer.score_packed_native)")
+
     def close(self):
         for m in self._maps:
             self.L.gq_hop_close(m)

@@ -197,6 +197,28 @@ int gq_attn_prefill(const void *q, const void *k_cache, const void *v_cache, voi
                     uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t window, void *stream);
 
 /*
+ * The packed pass: N sequences as ONE run of S rows (varlen attention), fp16 caches.  Packed row i is token pos[i] of the sequence that
+ * begins at packed row seg_begin[i]; its k and v live in cache row i.
+ * gq_attn_prefill_packed: gq_attn_prefill with start = 0 (the same layouts, tile grid, softmax and store; a further instance of its
+ *   kernel) and a segment begin per row: seg_begin int32 [S], device memory, non-decreasing, seg_begin[i] <= i.  Query row i attends
+ *   the cache rows max(seg_begin[i], i + 1 - window) <= t <= i (window 0: no window).  The kernel uses min(seg_begin[i], i): a
+ *   malformed array gives wrong numbers, never an address outside rows [0, S).  Row i of out is, bit for bit, row i of
+ *   gq_attn_prefill(S = i + 1, start = 0, window = min(i - seg_begin[i] + 1, window)) over the same caches, and the cache rows of
+ *   another sequence never reach it, whatever they hold (NaN and Inf included).  Governed by gq_attn_prefill_supported (GQ_ENOTSUP,
+ *   nothing written); S == 0, S > max_seq and a null seg_begin: GQ_EINVAL.
+ * gq_rope_cache_rows_packed: the row write with the cache row apart from the RoPE position: the rotation uses pos[s], k and v go to
+ *   cache row row[s] (rows >= max_seq are not written), q_out [n_head][S][head_dim] is indexed by s.  q_norm_weight / k_norm_weight
+ *   both given: the rounding points of gq_qknorm_rope_cache_rows (head_dim 64 or 128); neither: those of gq_rope_cache_rows; one
+ *   of them: GQ_EINVAL.  A further instance of the row-write kernel.
+ */
+int gq_attn_prefill_packed(const void *q, const void *k_cache, const void *v_cache, const int *seg_begin, void *out, uint32_t S,
+                           uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t window,
+                           void *stream);
+int gq_rope_cache_rows_packed(const void *qkv, const int *pos, const int *row, const void *cos_table, const void *sin_table, void *q_out,
+                              void *k_cache, void *v_cache, uint32_t S, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim,
+                              uint32_t max_seq, const void *q_norm_weight, const void *k_norm_weight, float eps, void *stream);
+
+/*
  * The fp8 KV cache (kv_cache_dtype="fp8"): caches of OCP e4m3 codes, one byte per element, [n_kv_head][max_seq][head_dim] per batch
  * slot, with fp32 scales per KV head in device memory (read by the kernels at every launch: new values need no re-capture).
  *   write rule  code  = fp8_rne(clamp(float(x16) * inv, -448, 448)),  inv = 1 / scale computed by the host (no kernel divides);
