@@ -35,7 +35,7 @@ ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
 SAMPLER_LP_WS = 2 * 128  # floats of gq_sample_topk_lp's lp_ws
 PREFILL_ATTN_BQ, PREFILL_ATTN_BK = 64, 64  # include/gq_hip.h GQ_PREFILL_ATTN_BQ / _BK: query rows and key rows per tile of gq_attn_prefill
-SAMPLER_MAX_VOCAB = 262144  # gq_sample_topk / _ex / _p: 128 blocks x 2048 logits (csrc/decode.hip; up to 131072: x 1024)
+SAMPLER_MAX_VOCAB = 262144  # gq_sample_topk / _ex / _p: 128 blocks x 2048 logits (csrc/sampler.hip; up to 131072: x 1024)
 # include/gq_hip.h GQ_AP_ROUTE_*: the kernel family an AP-GEMV dispatch launched (gq_debug_ap_last_route, gq_debug_ap_plan_route)
 AP_ROUTES = ("none", "generic", "exact", "pair-table", "plane", "plane-local", "plane-chain", "stream", "stream-ksplit", "dq",
              "stream-qkv-rope", "wide")

@@ -10,35 +10,22 @@
 
 #include "gq_internal.h"
 #include "attn_core.h"
+#include "decode_util.h"
 #include "fwht.h"
 
 namespace {
 
-typedef uint32_t u32;
-typedef _Float16 h16;
+using gq_dec::h16;
+using gq_dec::h2f;
+using gq_dec::h2u;
+using gq_dec::u2h;
+using gq_dec::u32;
+using gq_dec::wave_reduce;
 typedef h16 h16x2 __attribute__((ext_vector_type(2)));
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 using gq_attn::AttnGeom;
 using gq_attn::AttnWindow;
 using gq_attn::window_lo;
-
-__device__ __forceinline__ float h2f(uint16_t h) { return (float)__builtin_bit_cast(h16, h); }
-__device__ __forceinline__ h16 u2h(uint16_t h) { return __builtin_bit_cast(h16, h); }
-__device__ __forceinline__ uint16_t h2u(h16 h) { return __builtin_bit_cast(uint16_t, h); }
-
-template <bool MAX>
-__device__ __forceinline__ float wave_reduce(float v) {
-    auto comb = [](float a, float b) { return MAX ? fmaxf(a, b) : a + b; };
-    v = comb(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false)));
-    v = comb(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false)));
-    v = comb(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false)));
-    v = comb(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false)));
-    // row_bcast15 -> rows 1,3 ; row_bcast31 -> rows 2,3 ; lanes not written keep `old` = identity for the combine
-    const float ident = MAX ? -3.0e38f : 0.f;
-    v = comb(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, ident), __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, false)));
-    v = comb(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, ident), __builtin_bit_cast(int, v), 0x143, 0xC, 0xF, false)));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
 
 // KV group of query head h: h / (H / Hkv).  Both divisions sit in front of the first load of an attention launch (the cache base
 // needs g) -- ~25 scalar / vector instructions each on this chip (no integer divide); the group size is a power of two for every
@@ -615,727 +602,6 @@ __global__ void __launch_bounds__(HD) attn_combine_kernel(const float *ws, uint1
     out[(size_t)h * HD + tid] = h2u((h16)(o / sum));
 }
 
-// ------------------------------------------------------------------------------------------------ sampling
-// Top-k sampling exactly as generate.py:53-73 defines the distribution: logits / max(T, 1e-5), keep the top k,
-// softmax, then draw with the exponential race  argmax_i p_i / q_i, q ~ Exp(1)   (multinomial_sample_one_no_sync).
-// Equivalent form used here: argmax_i (logit_i / T - log q_i) over the k candidates.  The random numbers come from a
-// counter-based hash of (seed, step counter in device memory) -- torch's Philox stream is not reproduced (the
-// reference's sampling is not reproducible across runs either: no fixed generator on the sampled path).
-// Two launches: per-block candidates, then a single-block merge.  Writes the next token AND feeds it back into
-// `tok_io` / increments `pos_io` so a captured graph advances by itself.
-constexpr int SAMP_BLOCKS = 128, SAMP_K = 64;  // (the kernels are built for 32 and for 64 candidates per block)
-constexpr u32 SAMP_MAX_VOCAB = GQ_SAMPLER_MAX_VOCAB;  // SAMP_BLOCKS slices of <= 2048 logits (the wide instance; <= 131072: slices of <= 1024)
-static_assert(SAMP_MAX_VOCAB == 2048u * SAMP_BLOCKS, "the wide instance's slice");
-static_assert(GQ_SSQ_SLOTS == 1024, "sample_stage2 writes one hand-over slot per thread");
-
-__device__ __forceinline__ u32 hash32(u32 x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-
-// Selection of the K largest by binary search on a UNIQUE integer key (monotone image of the fp16 value in the high
-// bits, inverted index in the low bits so that ties go to the lowest index): nbits rounds of "count keys >= candidate"
-// (registers + one DPP wave reduction + one LDS combine per round) instead of K rounds of block-wide arg-max.
-__device__ __forceinline__ u32 ordered_key16(uint16_t h) { return (h & 0x8000u) ? (u32)(uint16_t)~h : ((u32)h | 0x8000u); }
-__device__ __forceinline__ uint16_t unordered_key16(u32 o) { return (o & 0x8000u) ? (uint16_t)(o & 0x7FFFu) : (uint16_t)~o; }
-// the same image of an fp32 bit pattern (gq_sample_topk_rep: a penalised logit is an fp32 number that in general is no fp16 value)
-__device__ __forceinline__ u32 ordered_key32(u32 b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
-__device__ __forceinline__ u32 unordered_key32(u32 o) { return (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o; }
-// stage 1 of every instance gives a NaN logit (or a penalised one) the key 0: never a candidate, whatever its sign
-__device__ __forceinline__ bool is_nan16(uint16_t h) { return (h & 0x7FFFu) > 0x7C00u; }
-
-// The K-th largest of the 64 * EPT keys of ONE wave by binary search on the key bits: the count of a round is EPT ballots +
-// scalar population counts -- no LDS, no barrier (the block-wide version above pays a 1024-thread barrier per bit: 13 us
-// for 33 bits).  Two levels of it replace a block-wide search: every wave keeps its own top K (a global top-K key is in
-// the top K of its wave), one wave then searches the survivors.
-// The low LOWBITS bits of a key are the tie-breaking position: they are searched only when the value bits leave more than
-// K keys at the threshold (rare), which halves the rounds.
-// (The key widths are template parameters, not arguments: the sampler has two instances of them, and as arguments they would share
-// one function between the instances -- the compiler then no longer sees them as constants of that function, and the code of the
-// narrow kernels changes although their source does not.  ISA diffed: with the parameters the narrow kernels are unchanged.)
-template <int EPT, typename KeyT, int NBITS, int LOWBITS>
-__device__ __forceinline__ KeyT wave_select_threshold(const KeyT (&key)[EPT], int K) {
-    KeyT t = 0;
-    int ct = 0x7FFFFFFF;  // count of keys >= t
-    for (int bit = NBITS - 1; bit >= 0; bit--) {
-        if (bit == LOWBITS - 1 && ct == K) break;  // exactly K keys carry a value >= the threshold value: no tie to break
-        const KeyT cand = t | ((KeyT)1 << bit);
-        int c = 0;
-#pragma unroll
-        for (int e = 0; e < EPT; e++) c += __popcll(__builtin_amdgcn_ballot_w64(key[e] >= cand));
-        if (c >= K) {  // wave-uniform
-            t = cand;
-            ct = c;
-        }
-    }
-    return t;
-}
-// writes the keys >= t (and != 0) of the wave to dst[0 .. count) in lane order; returns the count (<= K for a threshold
-// from wave_select_threshold: keys are unique)
-template <int EPT, typename KeyT>
-__device__ __forceinline__ int wave_compact(const KeyT (&key)[EPT], KeyT t, KeyT *dst, int cap, u32 l) {
-    int base = 0;
-#pragma unroll
-    for (int e = 0; e < EPT; e++) {
-        const bool p = key[e] >= t && key[e] != 0;
-        const unsigned long long b = __builtin_amdgcn_ballot_w64(p);
-        const int pos = base + __popcll(b & ((1ull << l) - 1ull));
-        if (p && pos < cap) dst[pos] = key[e];
-        base += __popcll(b);
-    }
-    return base;
-}
-
-// Extras of the extended entry point (gq_sample_topk_ex, round 5); all optional:
-//   ban: device words {n (<= 4), until_pos, id0..id3} -- while *pos_io < until_pos the listed tokens cannot be drawn (HF's
-//        MinNewTokensLengthLogitsProcessor: EOS is suppressed until min_new_tokens are out);
-//   seq_out[*pos_io + 1] = the drawn token (the host reads whole chunks of the sequence instead of cloning one word per step);
-//   emb_table / x_out / ssq_out: the embedding row of the drawn token -> the hidden-state buffer of the NEXT step (+ its statistics
-//        hand-over, gq_embed_lookup_ho) -- the step's graph then starts at layer 0's first GEMV, one launch less per token.
-struct SampleEx {
-    const int *ban;
-    int *seq_out;
-    u32 seq_cap;
-    const uint16_t *emb_table;
-    uint16_t *x_out;
-    u32 dim, vocab;
-    float *ssq_out;
-    float top_p;  // nucleus threshold (round 6: gq_sample_topk_p); >= 1 or <= 0: off
-};
-
-// what both draw kernels do with the token: outputs, token / position feedback, the sequence store
-// (seen: the token set of gq_sample_topk_rep or NULL -- the drawn token's bit, by a vector atomic from this one lane; the next step's
-// stage 1 reads the word behind a kernel boundary.  The token of an empty candidate set is no id of the vocabulary and sets nothing.)
-__device__ __forceinline__ void sample_publish(int tokc, u32 ctr, int *counter, int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex,
-                                               u32 *seen = nullptr, u32 V = 0u) {
-    if (seen && (u32)tokc < V) atomicOr(seen + ((u32)tokc >> 5), 1u << ((u32)tokc & 31u));
-    next_tok[0] = tokc;
-    counter[0] = (int)(ctr + 1u);
-    if (tok_io) tok_io[0] = tokc;
-    const int p = pos_io ? pos_io[0] : 0;
-    if (ex.seq_out && (u32)(p + 1) < ex.seq_cap) ex.seq_out[p + 1] = tokc;
-    if (pos_io) pos_io[0] = p + 1;
-}
-// the next step's hidden state: tok_embeddings[token] (+ the statistics hand-over for layer 0's RMSNorm); 1024 threads
-__device__ __forceinline__ void sample_embed(int chosen, u32 tid, const SampleEx &ex) {
-    u32 tk = (u32)chosen;
-    if (tk >= ex.vocab) tk = 0;
-    float acc = 0.f;
-    for (u32 i = tid; i < ex.dim / 8u; i += 1024u) {
-        const uint4 v = reinterpret_cast<const uint4 *>(ex.emb_table + (size_t)tk * ex.dim)[i];
-        gq_store_wt(reinterpret_cast<uint4 *>(ex.x_out) + i, v);
-        const u32 wd[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const float a = (float)__builtin_bit_cast(_Float16, (uint16_t)(wd[k] & 0xFFFFu)), b = (float)__builtin_bit_cast(_Float16, (uint16_t)(wd[k] >> 16));
-            acc += a * a;
-            acc += b * b;
-        }
-    }
-    if (ex.ssq_out) gq_store_wt(ex.ssq_out + tid, acc);  // (1024 threads = GQ_SSQ_SLOTS)
-}
-
-// stage 1: each of the 128 blocks selects the top KM of its slice (<= 256 * EPT logits, EPT per thread in registers); KM = 32 or 64.
-// Two instances of the widths: EPT = 4, LB = 10 (slices of <= 1024: vocab <= 131072) and EPT = 8, LB = 11 (slices of <= 2048: vocab <=
-// 262144).  The grid is SAMP_BLOCKS either way -- the callers' work areas are 128 * KM words -- so a wider vocabulary is a longer slice.
-// key = (order-preserving image of the fp16 logit) << LB | (2^LB - 1 - position in the slice): 16 + LB bits.
-template <int KM, int EPT, int LB>
-__global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32 V, float *cand_val, int *cand_idx, const int *ban, const int *pos_io) {
-    static_assert(256 * EPT == 1 << LB && 16 + LB <= 32, "a slice is one position per key of the block; the key is a u32");
-    constexpr u32 LMASK = (1u << LB) - 1u;
-    __shared__ u32 surv[4 * KM];
-    __shared__ u32 fin[KM];
-    const u32 per = (V + SAMP_BLOCKS - 1) / SAMP_BLOCKS;  // <= 256 * EPT
-    const u32 lo = blockIdx.x * per, hi = min(lo + per, V);
-    const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
-    int nban = 0, bid[4] = {-1, -1, -1, -1};
-    if (ban) {  // (wave-uniform scalar loads)
-        nban = ban[0];
-        if (pos_io && pos_io[0] >= ban[1]) nban = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) bid[i] = i < nban ? ban[2 + i] : -1;
-    }
-    u32 key[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; e++) {
-        const u32 li = tid * (u32)EPT + (u32)e, gi = lo + li;
-        // key = (order-preserving image of the fp16 logit, position): unique, and both parts are recovered from it
-        const bool banned = (int)gi == bid[0] || (int)gi == bid[1] || (int)gi == bid[2] || (int)gi == bid[3];
-        // a NaN logit of either sign is no candidate (key 0, like a banned id): its image would lie above +inf (0x7E00) or below -inf (0xFE00)
-        const uint16_t hb = (gi < hi && !banned) ? logits[gi] : (uint16_t)0x7E00u;
-        key[e] = is_nan16(hb) ? 0u : ((ordered_key16(hb) << LB) | (LMASK - li));
-    }
-    if (l < KM / 2) reinterpret_cast<unsigned long long *>(surv + w * KM)[l] = 0ull;  // (a wave's LDS ops are in order)
-    const u32 t = wave_select_threshold<EPT, u32, 16 + LB, LB>(key, KM);
-    wave_compact<EPT, u32>(key, t, surv + w * KM, KM, l);
-    __syncthreads();
-    if (w == 0) {  // top KM of the 4 * KM survivors
-        u32 k2[KM / 16];
-#pragma unroll
-        for (int e = 0; e < KM / 16; e++) k2[e] = surv[(u32)e * 64u + l];
-        const u32 t2 = wave_select_threshold<KM / 16, u32, 16 + LB, LB>(k2, KM);
-        if (l < KM) fin[l] = 0u;
-        const int n = wave_compact<KM / 16, u32>(k2, t2, fin, KM, l);
-        if (l < KM) {
-            const u32 k = fin[l];
-            const bool ok = (int)l < n && k != 0u;
-            const u32 li = LMASK - (k & LMASK);
-            cand_val[blockIdx.x * KM + l] = ok ? h2f(unordered_key16(k >> LB)) : -3.0e38f;  // slice shorter than K: padded
-            cand_idx[blockIdx.x * KM + l] = ok ? (int)(lo + li) : -1;
-        }
-    }
-}
-
-// stage 2: one block, 128 * KM candidates (KM / 8 per thread), select the global top-k, then the exponential-race draw.
-// key = (order-preserving image of the fp16 value) << IB | (2^IB - 1 - token id): IB = 17 (vocab <= 131072) or 18 (<= 262144); everything
-// behind the selection sees token ids only and is the same in both instances.
-template <int KM, int IB>
-__global__ void __launch_bounds__(1024) sample_stage2(const float *cand_val, const int *cand_idx, int top_k, float temperature,
-                                                      u32 seed, int *counter, int *tok_io, int *pos_io, int *next_tok, SampleEx ex) {
-    constexpr int EPT = KM / 8;  // candidates per thread
-    constexpr u32 IMASK = (1u << IB) - 1u;
-    __shared__ float selv[KM];
-    __shared__ int seli[KM];
-    __shared__ unsigned long long surv[16 * KM];
-    __shared__ unsigned long long fin[KM];
-    __shared__ int slot, chosen;
-    const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
-    unsigned long long key[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; e++) {
-        const u32 c = tid * (u32)EPT + (u32)e;
-        const float v = cand_val[c];
-        const int id = cand_idx[c];
-        const uint16_t hb = __builtin_bit_cast(uint16_t, (h16)v);  // candidates are fp16 values: exact
-        key[e] = id >= 0 ? (((unsigned long long)ordered_key16(hb) << IB) | (unsigned long long)(IMASK - (u32)id)) : 0ull;
-    }
-    const int K = top_k < 1 ? 1 : (top_k > KM ? KM : top_k);
-    if (l < KM) surv[w * KM + l] = 0ull;
-    const unsigned long long t = wave_select_threshold<EPT, unsigned long long, 16 + IB, IB>(key, K);
-    wave_compact<EPT, unsigned long long>(key, t, surv + w * KM, KM, l);
-    __syncthreads();
-    if (w == 0) {
-        unsigned long long k8[KM / 4];
-#pragma unroll
-        for (int e = 0; e < KM / 4; e++) k8[e] = surv[(u32)e * 64u + l];
-        const unsigned long long t2 = wave_select_threshold<KM / 4, unsigned long long, 16 + IB, IB>(k8, K);
-        if (l < KM) fin[l] = 0ull;
-        const int n2 = wave_compact<KM / 4, unsigned long long>(k8, t2, fin, KM, l);
-        if (l == 0) slot = n2;
-        if (l < KM) {
-            const unsigned long long k = fin[l];
-            selv[l] = h2f(unordered_key16((u32)(k >> IB)));
-            seli[l] = (int)(IMASK - ((u32)k & IMASK));
-        }
-    }
-    __syncthreads();
-    if (w == 0) {
-        const int n = min(slot, K);
-        const float T = fmaxf(temperature, 1e-5f);
-        const u32 ctr = (u32)counter[0];
-        float score = -3.0e38f;
-        int tokc = 0x7FFFFFFF;
-        // nucleus filter on the top-k survivors -- transformers' TopPLogitsWarper behind TopKLogitsWarper behind the temperature
-        // (generation/logits_process.py: probabilities of the scaled, top-k-filtered scores, cumulative sum in ASCENDING order, a token
-        // goes when the sum up to and including it is <= 1 - top_p, the most probable one always stays).  n <= 64 candidates, one per
-        // lane: the cumulative sum of a lane is a loop over the wave (ties ordered by token id, higher id first = the lower key).
-        bool keep = (int)l < n;
-        if (ex.top_p > 0.f && ex.top_p < 1.f) {
-            const float v = (int)l < n ? selv[l] / T : -3.0e38f;
-            float mx = v;
-#pragma unroll
-            for (int sh = 32; sh >= 1; sh >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sh, 64));
-            const float e = (int)l < n ? __expf(v - mx) : 0.f;
-            float z = e;
-#pragma unroll
-            for (int sh = 32; sh >= 1; sh >>= 1) z += __shfl_xor(z, sh, 64);
-            const float pr = e / z;
-            const int myid = (int)l < n ? seli[l] : -1;
-            float cum = 0.f;
-            int greater = 0;
-            for (int j = 0; j < n; j++) {
-                const float vj = __shfl(v, j, 64), pj = __shfl(pr, j, 64);
-                const int idj = __shfl(myid, j, 64);
-                const bool below = vj < v || (vj == v && idj > myid);  // j sorts before this lane in ascending order
-                cum += (below || j == (int)l) ? pj : 0.f;
-                greater += (vj > v || (vj == v && idj < myid)) ? 1 : 0;
-            }
-            keep = keep && (greater == 0 || !(cum <= 1.0f - ex.top_p));
-        }
-        if (keep) {
-            // q ~ Exp(1) = -log(u), u in (0,1]; the random number is tied to the TOKEN id, not to the slot
-            const u32 r = hash32(seed ^ hash32(ctr * 0x9E3779B9u + (u32)seli[l] + 1u));
-            const float u = ((float)(r >> 8) + 1.0f) * (1.0f / 16777216.0f);
-            score = selv[l] / T - __logf(-__logf(u));
-            tokc = seli[l];
-        }
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) {
-            const float os = __shfl_xor(score, sh, 64);
-            const int ot = __shfl_xor(tokc, sh, 64);
-            if (os > score || (os == score && ot < tokc)) { score = os; tokc = ot; }
-        }
-        if (l == 0) {
-            sample_publish(tokc, ctr, counter, tok_io, pos_io, next_tok, ex);
-            chosen = tokc;
-        }
-    }
-    if (ex.x_out) {
-        __syncthreads();
-        sample_embed(chosen, tid, ex);
-    }
-}
-
-// ---- gq_sample_topk_rep: the two stages over fp32 candidate values, with the token sets
-// KERNELS OF THEIR OWN, on purpose.  Sharing a body with sample_stage1 / sample_stage2 through a template parameter was tried first and
-// changed the code of the old instances (tools/cmp_kernels.py: 3 instructions of stage 1, 23 to 61 of stage 2 and its register count --
-// LDS arrays handed to a common body as pointers lose what the compiler knew about them).  What gq_sample_topk / _ex / _p launch must
-// not move, so the text below repeats theirs where the two agree; the differences are marked (REP).
-struct SampleRep {
-    float rp;
-    const u32 *seen, *suppress;
-};
-// stage 1 (REP): a token of `suppress` is no candidate, a token of `seen` carries s = v < 0 ? v * rp : v / rp in fp32, and the key is
-//   (order-preserving image of ALL 32 bits of s) << LB | (2^LB - 1 - position in the slice): u64 keys of 32 + LB <= 43 bits.
-// The words of the two sets are read where the logits are: a thread's EPT <= 8 consecutive tokens lie in at most two of them (a slice
-// starts at any token, not at a multiple of 32).
-template <int KM, int EPT, int LB>
-__global__ void __launch_bounds__(256) sample_stage1_rep(const uint16_t *logits, u32 V, float *cand_val, int *cand_idx, const int *ban, const int *pos_io,
-                                                         SampleRep rep) {
-    typedef unsigned long long u64;
-    static_assert(256 * EPT == 1 << LB && EPT <= 8, "a slice is one position per key of the block; a thread's tokens span two set words");
-    constexpr u32 LMASK = (1u << LB) - 1u;
-    __shared__ u64 surv[4 * KM];
-    __shared__ u64 fin[KM];
-    const u32 per = (V + SAMP_BLOCKS - 1) / SAMP_BLOCKS;  // <= 256 * EPT
-    const u32 lo = blockIdx.x * per, hi = min(lo + per, V);
-    const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
-    int nban = 0, bid[4] = {-1, -1, -1, -1};
-    if (ban) {  // (wave-uniform scalar loads)
-        nban = ban[0];
-        if (pos_io && pos_io[0] >= ban[1]) nban = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) bid[i] = i < nban ? ban[2 + i] : -1;
-    }
-    u64 sbits = 0ull, pbits = 0ull;  // (REP) bit e: token lo + tid * EPT + e is seen / suppressed
-    const u32 g0 = lo + tid * (u32)EPT;
-    if (g0 < hi) {  // (words of tokens < hi <= V only: a set is ceil(V / 32) words)
-        const u32 w0 = g0 >> 5, w1 = min(g0 + (u32)EPT - 1u, hi - 1u) >> 5;
-        if (rep.seen) sbits = ((u64)rep.seen[w0] | ((u64)(w1 != w0 ? rep.seen[w1] : 0u) << 32)) >> (g0 & 31u);
-        if (rep.suppress) pbits = ((u64)rep.suppress[w0] | ((u64)(w1 != w0 ? rep.suppress[w1] : 0u) << 32)) >> (g0 & 31u);
-    }
-    u64 key[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; e++) {
-        const u32 li = tid * (u32)EPT + (u32)e, gi = lo + li;
-        const bool banned = (int)gi == bid[0] || (int)gi == bid[1] || (int)gi == bid[2] || (int)gi == bid[3];
-        u64 k = 0ull;
-        if (gi < hi && !banned && !((pbits >> e) & 1ull)) {
-            const float v = h2f(logits[gi]);
-            // (-0 is not < 0; the division is IEEE's, correctly rounded: the library is built without fast-math)
-            const float sv = ((sbits >> e) & 1ull) ? (v < 0.f ? v * rep.rp : v / rep.rp) : v;
-            if (sv == sv) k = ((u64)ordered_key32(__builtin_bit_cast(u32, sv)) << LB) | (u64)(LMASK - li);  // (a NaN is no candidate)
-        }
-        key[e] = k;
-    }
-    if (l < KM) surv[w * KM + l] = 0ull;
-    const u64 t = wave_select_threshold<EPT, u64, 32 + LB, LB>(key, KM);
-    wave_compact<EPT, u64>(key, t, surv + w * KM, KM, l);
-    __syncthreads();
-    if (w == 0) {  // top KM of the 4 * KM survivors
-        u64 k2[KM / 16];
-#pragma unroll
-        for (int e = 0; e < KM / 16; e++) k2[e] = surv[(u32)e * 64u + l];
-        const u64 t2 = wave_select_threshold<KM / 16, u64, 32 + LB, LB>(k2, KM);
-        if (l < KM) fin[l] = 0ull;
-        const int n = wave_compact<KM / 16, u64>(k2, t2, fin, KM, l);
-        if (l < KM) {
-            const u64 k = fin[l];
-            const bool ok = (int)l < n && k != 0ull;
-            const u32 li = LMASK - ((u32)k & LMASK);
-            cand_val[blockIdx.x * KM + l] = ok ? __builtin_bit_cast(float, unordered_key32((u32)(k >> LB))) : -3.0e38f;  // (REP) s itself, 32 bits
-            cand_idx[blockIdx.x * KM + l] = ok ? (int)(lo + li) : -1;
-        }
-    }
-}
-
-// stage 2 (REP): key = (image of the 32 bits of the candidate value) << IB | (2^IB - 1 - token id), 32 + IB <= 50 bits, built from
-// cand_val directly; the publishing lane sets the drawn token's bit in `seen`.  Behind the selection: the text of sample_stage2.
-template <int KM, int IB>
-__global__ void __launch_bounds__(1024) sample_stage2_rep(const float *cand_val, const int *cand_idx, int top_k, float temperature,
-                                                          u32 seed, int *counter, int *tok_io, int *pos_io, int *next_tok, SampleEx ex, u32 *seen, u32 V) {
-    constexpr int EPT = KM / 8;  // candidates per thread
-    constexpr u32 IMASK = (1u << IB) - 1u;
-    __shared__ float selv[KM];
-    __shared__ int seli[KM];
-    __shared__ unsigned long long surv[16 * KM];
-    __shared__ unsigned long long fin[KM];
-    __shared__ int slot, chosen;
-    const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
-    unsigned long long key[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; e++) {
-        const u32 c = tid * (u32)EPT + (u32)e;
-        const float v = cand_val[c];
-        const int id = cand_idx[c];
-        key[e] = id >= 0 ? (((unsigned long long)ordered_key32(__builtin_bit_cast(u32, v)) << IB) | (unsigned long long)(IMASK - (u32)id)) : 0ull;  // (REP)
-    }
-    const int K = top_k < 1 ? 1 : (top_k > KM ? KM : top_k);
-    if (l < KM) surv[w * KM + l] = 0ull;
-    const unsigned long long t = wave_select_threshold<EPT, unsigned long long, 32 + IB, IB>(key, K);
-    wave_compact<EPT, unsigned long long>(key, t, surv + w * KM, KM, l);
-    __syncthreads();
-    if (w == 0) {
-        unsigned long long k8[KM / 4];
-#pragma unroll
-        for (int e = 0; e < KM / 4; e++) k8[e] = surv[(u32)e * 64u + l];
-        const unsigned long long t2 = wave_select_threshold<KM / 4, unsigned long long, 32 + IB, IB>(k8, K);
-        if (l < KM) fin[l] = 0ull;
-        const int n2 = wave_compact<KM / 4, unsigned long long>(k8, t2, fin, KM, l);
-        if (l == 0) slot = n2;
-        if (l < KM) {
-            const unsigned long long k = fin[l];
-            selv[l] = __builtin_bit_cast(float, unordered_key32((u32)(k >> IB)));  // (REP)
-            seli[l] = (int)(IMASK - ((u32)k & IMASK));
-        }
-    }
-    __syncthreads();
-    if (w == 0) {
-        const int n = min(slot, K);
-        const float T = fmaxf(temperature, 1e-5f);
-        const u32 ctr = (u32)counter[0];
-        float score = -3.0e38f;
-        int tokc = 0x7FFFFFFF;
-        // nucleus filter on the top-k survivors -- transformers' TopPLogitsWarper behind TopKLogitsWarper behind the temperature
-        // (generation/logits_process.py: probabilities of the scaled, top-k-filtered scores, cumulative sum in ASCENDING order, a token
-        // goes when the sum up to and including it is <= 1 - top_p, the most probable one always stays).  n <= 64 candidates, one per
-        // lane: the cumulative sum of a lane is a loop over the wave (ties ordered by token id, higher id first = the lower key).
-        bool keep = (int)l < n;
-        if (ex.top_p > 0.f && ex.top_p < 1.f) {
-            const float v = (int)l < n ? selv[l] / T : -3.0e38f;
-            float mx = v;
-#pragma unroll
-            for (int sh = 32; sh >= 1; sh >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sh, 64));
-            const float e = (int)l < n ? __expf(v - mx) : 0.f;
-            float z = e;
-#pragma unroll
-            for (int sh = 32; sh >= 1; sh >>= 1) z += __shfl_xor(z, sh, 64);
-            const float pr = e / z;
-            const int myid = (int)l < n ? seli[l] : -1;
-            float cum = 0.f;
-            int greater = 0;
-            for (int j = 0; j < n; j++) {
-                const float vj = __shfl(v, j, 64), pj = __shfl(pr, j, 64);
-                const int idj = __shfl(myid, j, 64);
-                const bool below = vj < v || (vj == v && idj > myid);  // j sorts before this lane in ascending order
-                cum += (below || j == (int)l) ? pj : 0.f;
-                greater += (vj > v || (vj == v && idj < myid)) ? 1 : 0;
-            }
-            keep = keep && (greater == 0 || !(cum <= 1.0f - ex.top_p));
-        }
-        if (keep) {
-            // q ~ Exp(1) = -log(u), u in (0,1]; the random number is tied to the TOKEN id, not to the slot
-            const u32 r = hash32(seed ^ hash32(ctr * 0x9E3779B9u + (u32)seli[l] + 1u));
-            const float u = ((float)(r >> 8) + 1.0f) * (1.0f / 16777216.0f);
-            score = selv[l] / T - __logf(-__logf(u));
-            tokc = seli[l];
-        }
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) {
-            const float os = __shfl_xor(score, sh, 64);
-            const int ot = __shfl_xor(tokc, sh, 64);
-            if (os > score || (os == score && ot < tokc)) { score = os; tokc = ot; }
-        }
-        if (l == 0) {
-            sample_publish(tokc, ctr, counter, tok_io, pos_io, next_tok, ex, seen, V);
-            chosen = tokc;
-        }
-    }
-    if (ex.x_out) {
-        __syncthreads();
-        sample_embed(chosen, tid, ex);
-    }
-}
-
-// ---- gq_sample_topk_lp: the draw of gq_sample_topk_rep + the drawn token's log-probabilities
-// KERNELS OF THEIR OWN again, for the reason above SampleRep: what the four other entry points launch must not move.  The text repeats
-// sample_stage1_rep / sample_stage2_rep; the additions are marked (LP).  The selection keys are integers and the race is the same
-// sequence of fp32 operations, so the draw is the _rep kernels' bit for bit.
-// REP = false: no penalty and no token sets -- every value is the fp16 logit itself, and the keys are the 16-bit ones of sample_stage1 /
-// sample_stage2 (the draw of gq_sample_topk_rep is then gq_sample_topk_p's, pinned bit for bit by tests/test_sampler_rep_exact_gpu.py).
-// Measured on the 8B geometry: the fp32 keys cost 10.8 us per token against the fp16 ones, the log-probabilities 0.9 us; a request for
-// log-probabilities alone should not pay for a penalty it does not use.  These kernels are new, so here one body serves both forms.
-//   ws: 2 * SAMP_BLOCKS floats, (m_b) then (z_b = sum exp(v - m_b)) of block b's slice, over the RAW fp16 logits -- banned, suppressed
-//       and penalised tokens count with the value the model gave them.  NULL: no raw log-probability is asked for.
-struct SampleLp {
-    float *ws, *raw, *drawn;
-    u32 cap;
-    const uint16_t *logits;  // stage 2 reads the drawn token's raw logit
-};
-constexpr float LP_NINF = -__builtin_inff();
-template <bool REP> struct LpKey1 { typedef unsigned long long T; };  // stage-1 key: 32 + LB bits (REP) or 16 + LB
-template <> struct LpKey1<false> { typedef u32 T; };
-
-template <int KM, int EPT, int LB, bool REP>
-__global__ void __launch_bounds__(256) sample_stage1_lp(const uint16_t *logits, u32 V, float *cand_val, int *cand_idx, const int *ban, const int *pos_io,
-                                                        SampleRep rep, float *lp_ws) {
-    typedef unsigned long long u64;
-    static_assert(256 * EPT == 1 << LB && EPT <= 8, "a slice is one position per key of the block; a thread's tokens span two set words");
-    typedef typename LpKey1<REP>::T KeyT;
-    constexpr int VB = REP ? 32 : 16;  // value bits of a key
-    constexpr u32 LMASK = (1u << LB) - 1u;
-    __shared__ KeyT surv[4 * KM];
-    __shared__ KeyT fin[KM];
-    __shared__ float lpm[4], lpz[4];  // (LP) a wave's maximum and its sum of exp(v - maximum)
-    const u32 per = (V + SAMP_BLOCKS - 1) / SAMP_BLOCKS;  // <= 256 * EPT
-    const u32 lo = blockIdx.x * per, hi = min(lo + per, V);
-    const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
-    int nban = 0, bid[4] = {-1, -1, -1, -1};
-    if (ban) {  // (wave-uniform scalar loads)
-        nban = ban[0];
-        if (pos_io && pos_io[0] >= ban[1]) nban = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) bid[i] = i < nban ? ban[2 + i] : -1;
-    }
-    u64 sbits = 0ull, pbits = 0ull;  // bit e: token lo + tid * EPT + e is seen / suppressed
-    const u32 g0 = lo + tid * (u32)EPT;
-    if (REP && g0 < hi) {  // (words of tokens < hi <= V only: a set is ceil(V / 32) words)
-        const u32 w0 = g0 >> 5, w1 = min(g0 + (u32)EPT - 1u, hi - 1u) >> 5;
-        if (rep.seen) sbits = ((u64)rep.seen[w0] | ((u64)(w1 != w0 ? rep.seen[w1] : 0u) << 32)) >> (g0 & 31u);
-        if (rep.suppress) pbits = ((u64)rep.suppress[w0] | ((u64)(w1 != w0 ? rep.suppress[w1] : 0u) << 32)) >> (g0 & 31u);
-    }
-    KeyT key[EPT];
-    float raw[EPT];  // (LP) every logit of the slice, the banned and the suppressed ones too; -inf past the end
-#pragma unroll
-    for (int e = 0; e < EPT; e++) {
-        const u32 li = tid * (u32)EPT + (u32)e, gi = lo + li;
-        const bool banned = (int)gi == bid[0] || (int)gi == bid[1] || (int)gi == bid[2] || (int)gi == bid[3];
-        const uint16_t hb = gi < hi ? logits[gi] : (uint16_t)0xFC00u;  // (-inf past the end)
-        const float v = h2f(hb);
-        raw[e] = v;
-        KeyT k = 0;
-        if (gi < hi && !banned && !((pbits >> e) & 1ull)) {
-            if constexpr (REP) {
-                // (-0 is not < 0; the division is IEEE's, correctly rounded: the library is built without fast-math)
-                const float sv = ((sbits >> e) & 1ull) ? (v < 0.f ? v * rep.rp : v / rep.rp) : v;
-                if (sv == sv) k = ((u64)ordered_key32(__builtin_bit_cast(u32, sv)) << LB) | (u64)(LMASK - li);  // (a NaN is no candidate)
-            } else {
-                if (!is_nan16(hb)) k = (ordered_key16(hb) << LB) | (LMASK - li);
-            }
-        }
-        key[e] = k;
-    }
-    if (lp_ws) {  // (LP) (m_w, sum exp(v - m_w)) of the wave: a finite v has a finite m_w >= v, a -inf one contributes 0
-        float mt = raw[0];
-#pragma unroll
-        for (int e = 1; e < EPT; e++) mt = fmaxf(mt, raw[e]);
-        const float mw = wave_reduce<true>(mt);
-        float zt = 0.f;
-#pragma unroll
-        for (int e = 0; e < EPT; e++) zt += raw[e] == LP_NINF ? 0.f : expf(raw[e] - mw);
-        const float zw = wave_reduce<false>(zt);
-        if (l == 0) {
-            lpm[w] = mw;
-            lpz[w] = zw;
-        }
-    }
-    if (l < KM) surv[w * KM + l] = 0;
-    const KeyT t = wave_select_threshold<EPT, KeyT, VB + LB, LB>(key, KM);
-    wave_compact<EPT, KeyT>(key, t, surv + w * KM, KM, l);
-    __syncthreads();
-    if (w == 0) {  // top KM of the 4 * KM survivors
-        KeyT k2[KM / 16];
-#pragma unroll
-        for (int e = 0; e < KM / 16; e++) k2[e] = surv[(u32)e * 64u + l];
-        const KeyT t2 = wave_select_threshold<KM / 16, KeyT, VB + LB, LB>(k2, KM);
-        if (l < KM) fin[l] = 0;
-        const int n = wave_compact<KM / 16, KeyT>(k2, t2, fin, KM, l);
-        if (l < KM) {
-            const KeyT k = fin[l];
-            const bool ok = (int)l < n && k != 0;
-            const u32 li = LMASK - ((u32)k & LMASK);
-            const float val = REP ? __builtin_bit_cast(float, unordered_key32((u32)((u64)k >> LB))) : h2f(unordered_key16((u32)(k >> LB)));
-            cand_val[blockIdx.x * KM + l] = ok ? val : -3.0e38f;
-            cand_idx[blockIdx.x * KM + l] = ok ? (int)(lo + li) : -1;
-        }
-        if (lp_ws && l == 0) {  // (LP) the four waves in a fixed order; a block wholly past the end leaves (-inf, 0)
-            const float mb = fmaxf(fmaxf(lpm[0], lpm[1]), fmaxf(lpm[2], lpm[3]));
-            float zb = 0.f;
-#pragma unroll
-            // (a partial is left out by its SUM being 0, not by its maximum being -inf: fmaxf drops a NaN, so a wave whose only logits
-            // are NaN has m = -inf and z = NaN, and that NaN has to reach the log-probability.  z == 0 happens with m = -inf only.)
-            for (int i = 0; i < 4; i++) zb += lpz[i] == 0.f ? 0.f : lpz[i] * expf(lpm[i] - mb);
-            lp_ws[blockIdx.x] = mb;
-            lp_ws[SAMP_BLOCKS + blockIdx.x] = zb;
-        }
-    }
-}
-
-// stage 2 (LP): the text of sample_stage2_rep.  Wave 1, idle while wave 0 selects, combines the 128 partials of stage 1 (two per lane,
-// then the wave in a fixed butterfly: no atomics) and leaves (M, log Z) in LDS; wave 0 loads the raw logits of its candidates in front of
-// the nucleus code (the latency hides behind it), normalises the kept candidates' a_c = s_c / T behind the race, and lane 0 stores the two
-// numbers at the index seq_out uses.
-template <int KM, int IB, bool REP>
-__global__ void __launch_bounds__(1024) sample_stage2_lp(const float *cand_val, const int *cand_idx, int top_k, float temperature,
-                                                         u32 seed, int *counter, int *tok_io, int *pos_io, int *next_tok, SampleEx ex, u32 *seen, u32 V,
-                                                         SampleLp lp) {
-    static_assert(SAMP_BLOCKS == 128, "two partials per lane of wave 0");
-    constexpr int EPT = KM / 8;  // candidates per thread
-    constexpr int VB = REP ? 32 : 16;  // value bits of a key (REP = false: the candidates are fp16 values, exact)
-    constexpr u32 IMASK = (1u << IB) - 1u;
-    __shared__ float selv[KM];
-    __shared__ int seli[KM];
-    __shared__ unsigned long long surv[16 * KM];
-    __shared__ unsigned long long fin[KM];
-    __shared__ int slot, chosen;
-    __shared__ float lpM, lpLogZ;  // (LP) max m_b and log sum z_b exp(m_b - M)
-    const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
-    float pm0 = LP_NINF, pm1 = LP_NINF, pz0 = 0.f, pz1 = 0.f;  // (LP) loaded here, used behind the first barrier
-    if (lp.ws && w == 1) {
-        pm0 = lp.ws[l];
-        pm1 = lp.ws[64u + l];
-        pz0 = lp.ws[SAMP_BLOCKS + l];
-        pz1 = lp.ws[SAMP_BLOCKS + 64u + l];
-    }
-    unsigned long long key[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; e++) {
-        const u32 c = tid * (u32)EPT + (u32)e;
-        const float v = cand_val[c];
-        const int id = cand_idx[c];
-        const u32 img = REP ? ordered_key32(__builtin_bit_cast(u32, v)) : ordered_key16(__builtin_bit_cast(uint16_t, (h16)v));
-        key[e] = id >= 0 ? (((unsigned long long)img << IB) | (unsigned long long)(IMASK - (u32)id)) : 0ull;
-    }
-    const int K = top_k < 1 ? 1 : (top_k > KM ? KM : top_k);
-    if (l < KM) surv[w * KM + l] = 0ull;
-    const unsigned long long t = wave_select_threshold<EPT, unsigned long long, VB + IB, IB>(key, K);
-    wave_compact<EPT, unsigned long long>(key, t, surv + w * KM, KM, l);
-    __syncthreads();
-    if (w == 0) {
-        unsigned long long k8[KM / 4];
-#pragma unroll
-        for (int e = 0; e < KM / 4; e++) k8[e] = surv[(u32)e * 64u + l];
-        const unsigned long long t2 = wave_select_threshold<KM / 4, unsigned long long, VB + IB, IB>(k8, K);
-        if (l < KM) fin[l] = 0ull;
-        const int n2 = wave_compact<KM / 4, unsigned long long>(k8, t2, fin, KM, l);
-        if (l == 0) slot = n2;
-        if (l < KM) {
-            const unsigned long long k = fin[l];
-            selv[l] = REP ? __builtin_bit_cast(float, unordered_key32((u32)(k >> IB))) : h2f(unordered_key16((u32)(k >> IB)));
-            seli[l] = (int)(IMASK - ((u32)k & IMASK));
-        }
-    } else if (w == 1 && lp.ws) {  // (LP) M = max m_b, Z = sum z_b exp(m_b - M): a -inf partial (a block past the end) contributes 0
-        float M = fmaxf(pm0, pm1);
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) M = fmaxf(M, __shfl_xor(M, sh, 64));
-        float Z = (pz0 == 0.f ? 0.f : pz0 * expf(pm0 - M)) + (pz1 == 0.f ? 0.f : pz1 * expf(pm1 - M));  // (z == 0: as in stage 1)
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) Z += __shfl_xor(Z, sh, 64);
-        if (l == 0) {
-            lpM = M;
-            lpLogZ = logf(Z);
-        }
-    }
-    __syncthreads();
-    if (w == 0) {
-        const int n = min(slot, K);
-        const float T = fmaxf(temperature, 1e-5f);
-        const u32 ctr = (u32)counter[0];
-        float score = -3.0e38f;
-        int tokc = 0x7FFFFFFF;
-        // (LP) the raw logit of this lane's candidate (an id of the vocabulary), asked for here and used behind the race
-        const float rawv = (lp.raw && (int)l < n) ? h2f(lp.logits[seli[l]]) : 0.f;
-        // nucleus filter on the top-k survivors -- transformers' TopPLogitsWarper behind TopKLogitsWarper behind the temperature
-        // (generation/logits_process.py: probabilities of the scaled, top-k-filtered scores, cumulative sum in ASCENDING order, a token
-        // goes when the sum up to and including it is <= 1 - top_p, the most probable one always stays).  n <= 64 candidates, one per
-        // lane: the cumulative sum of a lane is a loop over the wave (ties ordered by token id, higher id first = the lower key).
-        bool keep = (int)l < n;
-        if (ex.top_p > 0.f && ex.top_p < 1.f) {
-            const float v = (int)l < n ? selv[l] / T : -3.0e38f;
-            float mx = v;
-#pragma unroll
-            for (int sh = 32; sh >= 1; sh >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sh, 64));
-            const float e = (int)l < n ? __expf(v - mx) : 0.f;
-            float z = e;
-#pragma unroll
-            for (int sh = 32; sh >= 1; sh >>= 1) z += __shfl_xor(z, sh, 64);
-            const float pr = e / z;
-            const int myid = (int)l < n ? seli[l] : -1;
-            float cum = 0.f;
-            int greater = 0;
-            for (int j = 0; j < n; j++) {
-                const float vj = __shfl(v, j, 64), pj = __shfl(pr, j, 64);
-                const int idj = __shfl(myid, j, 64);
-                const bool below = vj < v || (vj == v && idj > myid);  // j sorts before this lane in ascending order
-                cum += (below || j == (int)l) ? pj : 0.f;
-                greater += (vj > v || (vj == v && idj < myid)) ? 1 : 0;
-            }
-            keep = keep && (greater == 0 || !(cum <= 1.0f - ex.top_p));
-        }
-        if (keep) {
-            // q ~ Exp(1) = -log(u), u in (0,1]; the random number is tied to the TOKEN id, not to the slot
-            const u32 r = hash32(seed ^ hash32(ctr * 0x9E3779B9u + (u32)seli[l] + 1u));
-            const float u = ((float)(r >> 8) + 1.0f) * (1.0f / 16777216.0f);
-            score = selv[l] / T - __logf(-__logf(u));
-            tokc = seli[l];
-        }
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) {
-            const float os = __shfl_xor(score, sh, 64);
-            const int ot = __shfl_xor(tokc, sh, 64);
-            if (os > score || (os == score && ot < tokc)) { score = os; tokc = ot; }
-        }
-        // (LP) every lane holds the drawn token now.  An empty candidate set (no id of the vocabulary): both numbers are NaN.
-        const bool drew = (u32)tokc < V;
-        float lraw = __builtin_nanf(""), ldrawn = __builtin_nanf("");
-        if (drew) {
-            const int win = (int)__builtin_ctzll(__builtin_amdgcn_ballot_w64(keep && seli[l] == tokc));  // one lane: token ids are unique
-            // v_tok - lse over the whole vocabulary, as (v_tok - M) - log Z: the difference's rounding is in units of the result
-            if (lp.raw) lraw = (__shfl(rawv, win, 64) - lpM) - lpLogZ;
-            if (lp.drawn) {  // a_tok - log sum_C exp(a_c) over the kept candidates, a_c as the race forms it
-                const float a = keep ? selv[l] / T : LP_NINF;
-                float mx = a;
-#pragma unroll
-                for (int sh = 32; sh >= 1; sh >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sh, 64));
-                float z = (keep && a != LP_NINF) ? expf(a - mx) : 0.f;
-#pragma unroll
-                for (int sh = 32; sh >= 1; sh >>= 1) z += __shfl_xor(z, sh, 64);
-                ldrawn = (__shfl(a, win, 64) - mx) - logf(z);
-            }
-        }
-        if (l == 0) {
-            const int p = pos_io ? pos_io[0] : 0;  // (LP) before sample_publish increments it
-            sample_publish(tokc, ctr, counter, tok_io, pos_io, next_tok, ex, seen, V);
-            chosen = tokc;
-            if ((u32)(p + 1) < lp.cap) {
-                if (lp.raw) lp.raw[p + 1] = lraw;
-                if (lp.drawn) lp.drawn[p + 1] = ldrawn;
-            }
-        }
-    }
-    if (ex.x_out) {
-        __syncthreads();
-        sample_embed(chosen, tid, ex);
-    }
-}
-
-// token set of gq_token_set_build: one block -- the words are cleared (clear != 0), the block meets, then every id in [0, V) sets its
-// bit with a vector atomic (duplicates and ids of one word from several threads are then no race)
-__global__ void __launch_bounds__(1024) token_set_build_kernel(const int *ids, u32 n, u32 V, u32 *set, int clear) {
-    const u32 words = (V + 31u) / 32u;
-    if (clear)
-        for (u32 i = threadIdx.x; i < words; i += 1024u) set[i] = 0u;
-    __syncthreads();
-    for (u32 i = threadIdx.x; i < n; i += 1024u) {
-        const u32 t = (u32)ids[i];
-        if (t < V) atomicOr(set + (t >> 5), 1u << (t & 31u));
-    }
-}
-
-// (Round 5, measured and removed: a ONE-launch greedy draw -- one 1024-thread block keeps the largest key of its 16-byte units of the
-// logits -- for temperature 0.  21 us with a load loop, no better than the two launches above with all 16 loads of a thread in flight
-// (865.6 / 864.1 against 867.9 / 868.3 tokens/s): one CU takes the 250 KiB of logits slower than 128 blocks + one do.)
-
 // ------------------------------------------------------------------------------------------------ dense fp16 GEMV
 // out[n] = sum_k x[k] * W[n][k], fp32 accumulation (v_dot2_f32_f16), fp16 output -- what nn.Linear(fp16) gives at M = 1.
 // Optional RMSNorm prologue on x (final norm before lm_head).  One wave = RW rows at a time, 16-byte loads,
@@ -1691,157 +957,6 @@ extern "C" int gq_dense_gemv_f16(const void *x, const void *W, void *out, uint32
     GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(dense_gemv_kernel<RW>), 160 * 1024));
     hipLaunchKernelGGL(dense_gemv_kernel<RW>, dim3(grid), dim3(256), smem, (hipStream_t)stream, (const uint16_t *)x,
                        (const uint16_t *)W, (uint16_t *)out, N, K, (const uint16_t *)norm_weight, eps, rpb);
-    GQ_HIP_CHECK(hipGetLastError());
-    return GQ_OK;
-}
-
-namespace {
-// the pair of one width (logits per thread, local-position bits, token-id bits): candidates per block by top_k
-// (gq_sample_topk_rep: the kernels of fp32 candidate values -- kernels of their own, the pairs above are launched as before)
-template <int EPT, int LB, int IB>
-void sample_launch_rep_w(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter, float *work_val, int *work_idx,
-                         int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, const SampleRep &rep, u32 *seen, hipStream_t s) {
-    if (top_k <= 32) {
-        hipLaunchKernelGGL((sample_stage1_rep<32, EPT, LB>), dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban, pos_io, rep);
-        hipLaunchKernelGGL((sample_stage2_rep<32, IB>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex, seen, vocab);
-    } else {
-        hipLaunchKernelGGL((sample_stage1_rep<64, EPT, LB>), dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban, pos_io, rep);
-        hipLaunchKernelGGL((sample_stage2_rep<64, IB>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex, seen, vocab);
-    }
-}
-// (gq_sample_topk_lp: the pair that also leaves the log-probabilities)
-template <int EPT, int LB, int IB, bool REP>
-void sample_launch_lp_w(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter, float *work_val, int *work_idx,
-                        int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, const SampleRep &rep, u32 *seen, const SampleLp &lp, hipStream_t s) {
-    if (top_k <= 32) {
-        hipLaunchKernelGGL((sample_stage1_lp<32, EPT, LB, REP>), dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban, pos_io, rep, lp.ws);
-        hipLaunchKernelGGL((sample_stage2_lp<32, IB, REP>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex, seen, vocab, lp);
-    } else {
-        hipLaunchKernelGGL((sample_stage1_lp<64, EPT, LB, REP>), dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban, pos_io, rep, lp.ws);
-        hipLaunchKernelGGL((sample_stage2_lp<64, IB, REP>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex, seen, vocab, lp);
-    }
-}
-template <int EPT, int LB, int IB>
-void sample_launch_w(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter, float *work_val, int *work_idx,
-                     int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, hipStream_t s) {
-    if (top_k <= 32) {
-        hipLaunchKernelGGL((sample_stage1<32, EPT, LB>), dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban, pos_io);
-        hipLaunchKernelGGL((sample_stage2<32, IB>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex);
-    } else {
-        hipLaunchKernelGGL((sample_stage1<64, EPT, LB>), dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban, pos_io);
-        hipLaunchKernelGGL((sample_stage2<64, IB>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io, next_tok, ex);
-    }
-}
-// rep == NULL: the kernels of gq_sample_topk / _ex / _p;  lp != NULL (with rep): the kernels of gq_sample_topk_lp
-int sample_launch(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter, float *work_val, int *work_idx,
-                  int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, void *stream, const SampleRep *rep = nullptr, u32 *seen = nullptr,
-                  const SampleLp *lp = nullptr) {
-    if (!logits || !counter || !work_val || !work_idx || !next_tok) return gq_fail(GQ_EINVAL, "null pointer argument.");
-    if (top_k > SAMP_K) return gq_fail(GQ_ENOTSUP, "top_k > 64 is not supported by the fused sampler.");
-    if (vocab > SAMP_MAX_VOCAB) return gq_fail(GQ_ENOTSUP, "vocab too large for the fused sampler (<= 262144).");
-    hipStream_t s = (hipStream_t)stream;
-    if (rep && lp) {
-        // (no penalty and no sets: the instances with the fp16 keys -- the same draw, see above SampleLp)
-        const bool plain = rep->rp == 1.0f && !rep->seen && !rep->suppress && !seen;
-        if (vocab <= 131072u && plain)
-            sample_launch_lp_w<4, 10, 17, false>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, *rep, seen, *lp, s);
-        else if (vocab <= 131072u)
-            sample_launch_lp_w<4, 10, 17, true>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, *rep, seen, *lp, s);
-        else if (plain)
-            sample_launch_lp_w<8, 11, 18, false>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, *rep, seen, *lp, s);
-        else
-            sample_launch_lp_w<8, 11, 18, true>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, *rep, seen, *lp, s);
-    } else if (rep) {
-        if (vocab <= 131072u)
-            sample_launch_rep_w<4, 10, 17>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, *rep, seen, s);
-        else
-            sample_launch_rep_w<8, 11, 18>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, *rep, seen, s);
-    } else if (vocab <= 131072u)  // slices of <= 1024 logits, 17-bit token ids
-        sample_launch_w<4, 10, 17>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, s);
-    else  // slices of <= 2048 logits through the same 128 blocks, 18-bit token ids
-        sample_launch_w<8, 11, 18>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, s);
-    GQ_HIP_CHECK(hipGetLastError());
-    return GQ_OK;
-}
-}  // namespace
-
-extern "C" int gq_sample_topk(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter,
-                              float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, void *stream) {
-    if (top_k > 32) return gq_fail(GQ_ENOTSUP, "top_k > 32 is not supported by gq_sample_topk (work buffers of 128 * 32: gq_sample_topk_ex takes 64).");
-    return sample_launch(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, SampleEx{}, stream);
-}
-
-extern "C" int gq_sample_topk_ex(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter,
-                                 float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
-                                 uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, void *stream) {
-    return gq_sample_topk_p(logits, vocab, top_k, 1.0f, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ban, seq_out, seq_cap,
-                            embed_table, x_out, dim, ssq_out, stream);
-}
-namespace {
-// the extras of gq_sample_topk_p / gq_sample_topk_rep, checked
-int sample_extras(SampleEx &ex, uint32_t vocab, float top_p, const int *ban, int *seq_out, uint32_t seq_cap, const void *embed_table, void *x_out,
-                  uint32_t dim, float *ssq_out) {
-    if (!(top_p > 0.f)) return gq_fail(GQ_EINVAL, "top_p must be in (0, 1] (1 = no nucleus filter).");
-    ex.top_p = top_p;
-    ex.ban = ban;
-    ex.seq_out = seq_out;
-    ex.seq_cap = seq_cap;
-    if (x_out) {
-        if (!embed_table || dim % 8u) return gq_fail(GQ_EINVAL, "x_out needs the embedding table and dim % 8 == 0.");
-        ex.emb_table = (const uint16_t *)embed_table;
-        ex.x_out = (uint16_t *)x_out;
-        ex.dim = dim;
-        ex.vocab = vocab;
-        ex.ssq_out = ssq_out;
-    } else if (ssq_out) {
-        return gq_fail(GQ_EINVAL, "ssq_out without x_out.");
-    }
-    return GQ_OK;
-}
-}  // namespace
-extern "C" int gq_sample_topk_p(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
-                                float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
-                                uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, void *stream) {
-    SampleEx ex{};
-    if (int rc = sample_extras(ex, vocab, top_p, ban, seq_out, seq_cap, embed_table, x_out, dim, ssq_out)) return rc;
-    return sample_launch(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, stream);
-}
-
-extern "C" int gq_sample_topk_rep(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
-                                  float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
-                                  uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
-                                  uint32_t *seen, const uint32_t *suppress, void *stream) {
-    if (!(repetition_penalty > 0.f) || !(repetition_penalty < INFINITY))
-        return gq_fail(GQ_EINVAL, "repetition_penalty must be finite and > 0 (1 = no penalty).");
-    if (!seen && repetition_penalty != 1.0f) return gq_fail(GQ_EINVAL, "repetition_penalty != 1 needs the `seen` token set.");
-    SampleEx ex{};
-    if (int rc = sample_extras(ex, vocab, top_p, ban, seq_out, seq_cap, embed_table, x_out, dim, ssq_out)) return rc;
-    const SampleRep rep{repetition_penalty, seen, suppress};
-    return sample_launch(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, stream, &rep, seen);
-}
-
-extern "C" int gq_sample_topk_lp(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
-                                 float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
-                                 uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
-                                 uint32_t *seen, const uint32_t *suppress, float *lp_ws, float *lp_raw, float *lp_drawn, uint32_t lp_cap,
-                                 void *stream) {
-    if (!(repetition_penalty > 0.f) || !(repetition_penalty < INFINITY))
-        return gq_fail(GQ_EINVAL, "repetition_penalty must be finite and > 0 (1 = no penalty).");
-    if (!seen && repetition_penalty != 1.0f) return gq_fail(GQ_EINVAL, "repetition_penalty != 1 needs the `seen` token set.");
-    if (lp_raw && !lp_ws) return gq_fail(GQ_EINVAL, "gq_sample_topk_lp: lp_raw needs the lp_ws workspace (2 * 128 floats).");
-    SampleEx ex{};
-    if (int rc = sample_extras(ex, vocab, top_p, ban, seq_out, seq_cap, embed_table, x_out, dim, ssq_out)) return rc;
-    const SampleRep rep{repetition_penalty, seen, suppress};
-    if (!lp_raw && !lp_drawn)  // only the draw: the kernels of gq_sample_topk_rep
-        return sample_launch(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, stream, &rep, seen);
-    const SampleLp lp{lp_raw ? lp_ws : nullptr, lp_raw, lp_drawn, lp_cap, (const uint16_t *)logits};
-    return sample_launch(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, stream, &rep, seen, &lp);
-}
-
-extern "C" int gq_token_set_build(const int *ids, uint32_t n, uint32_t vocab, uint32_t *set, int clear, void *stream) {
-    if (!set || (n && !ids) || !vocab) return gq_fail(GQ_EINVAL, "gq_token_set_build: null pointer argument or vocab == 0.");
-    if (!n && !clear) return GQ_OK;
-    hipLaunchKernelGGL(token_set_build_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, ids, n, vocab, set, clear);
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
 }

@@ -1,4 +1,4 @@
-"""Host model of the fused sampler (csrc/decode.hip: sample_stage1 / sample_stage2 behind gq_sample_topk, gq_sample_topk_ex and
+"""Host model of the fused sampler (csrc/sampler.hip: sample_stage1 / sample_stage2 behind gq_sample_topk, gq_sample_topk_ex and
 gq_sample_topk_p), in numpy and float64.  It restates the CONTRACT -- include/gq_hip.h and the comments above the kernels -- not the
 kernels' data flow: no slices, waves, keys or work buffers appear here.
 
@@ -51,12 +51,12 @@ MAX_VOCAB = 262144
 FAULTS = ("temp_x1.05", "rng_by_slot", "counter_stuck", "top_k_plus_1", "top_k_minus_1", "tie_to_higher_index", "nucleus_lt",
           "nucleus_descending", "top_unprotected", "ban_le")
 NAN_FAULTS = ("nan_wins", "neg_nan_as_number")
-EMPTY_TOKEN = 0x7FFFFFFF  # what an empty candidate set publishes (decode.hip: sample_publish)
+EMPTY_TOKEN = 0x7FFFFFFF  # what an empty candidate set publishes (sampler.hip: sample_publish)
 M32 = np.uint64(0xFFFFFFFF)
 
 
 def hash32(x):
-    """decode.hip::hash32 on an array of u32 values held in uint64"""
+    """sampler.hip::hash32 on an array of u32 values held in uint64"""
     x = np.asarray(x, dtype=np.uint64) & M32
     x ^= x >> np.uint64(16)
     x = (x * np.uint64(0x7feb352d)) & M32

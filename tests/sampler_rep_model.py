@@ -1,4 +1,4 @@
-"""Host model of gq_sample_topk_rep (csrc/decode.hip: sample_stage1_rep / sample_stage2_rep) and of gq_token_set_build, in numpy.
+"""Host model of gq_sample_topk_rep (csrc/sampler.hip: the REP instances of sample_stage1 / sample_stage2) and of gq_token_set_build, in numpy.
 Like tests/sampler_model.py it restates the CONTRACT of include/gq_hip.h, not the kernels: no slices, keys or work buffers.  hash32,
 uniform, nucleus, the logit profiles and the error constants are sampler_model's own.
 

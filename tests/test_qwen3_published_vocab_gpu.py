@@ -1,5 +1,5 @@
 """GPU, end to end: an Any-Precision Qwen3 checkpoint with the PUBLISHED vocabulary (151936 logits, EOS ids above 2^17) through
-`AnyPrecisionForCausalLM.generate` -- the captured decode step ends in the wide instance of the fused sampler (csrc/decode.hip), so the
+`AnyPrecisionForCausalLM.generate` -- the captured decode step ends in the wide instance of the fused sampler (csrc/sampler.hip), so the
 plain call takes the fused route, `native=True` is served, sampled calls and EOS suppression work with token ids beyond 131072, and a
 DecodeGraph with several steps per replay and the embedding folded into the sampler decodes what single steps decode."""
 import pytest

@@ -1,5 +1,5 @@
 """CPU: the fused sampler's vocabulary limit is stated once per layer and the statements agree -- `_lib.SAMPLER_MAX_VOCAB` (what
-`AnyPrecisionForCausalLM.generate` gates its fused routes on), `GQ_SAMPLER_MAX_VOCAB` of include/gq_hip.h (which csrc/decode.hip
+`AnyPrecisionForCausalLM.generate` gates its fused routes on), `GQ_SAMPLER_MAX_VOCAB` of include/gq_hip.h (which csrc/sampler.hip
 compiles its check from) and the message of the refusal."""
 import os
 import re
@@ -13,7 +13,7 @@ def test_sampler_limit_is_262144_in_the_binding_the_header_and_the_kernel_file()
     header = open(os.path.join(ROOT, "include", "gq_hip.h")).read()
     m = re.search(r"#define\s+GQ_SAMPLER_MAX_VOCAB\s+(\d+)", header)
     assert m and int(m.group(1)) == _lib.SAMPLER_MAX_VOCAB
-    src = open(os.path.join(ROOT, "guidedquant_amd", "csrc", "decode.hip")).read()
+    src = open(os.path.join(ROOT, "guidedquant_amd", "csrc", "sampler.hip")).read()
     assert "SAMP_MAX_VOCAB = GQ_SAMPLER_MAX_VOCAB" in src
     msg = re.search(r'"vocab too large for the fused sampler \(<= (\d+)\)\."', src)
     assert msg and int(msg.group(1)) == _lib.SAMPLER_MAX_VOCAB

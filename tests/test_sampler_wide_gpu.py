@@ -1,4 +1,4 @@
-"""GPU: the wide instance of the fused sampler (csrc/decode.hip: 131072 < vocab <= 262144 -- the published Qwen3 vocabulary is 151936)
+"""GPU: the wide instance of the fused sampler (csrc/sampler.hip: 131072 < vocab <= 262144 -- the published Qwen3 vocabulary is 151936)
 through the C ABI: gq_sample_topk_p with the 128 x 64 work buffers every caller allocates, gq_sample_topk with 128 x 32 for one case.
 
 The reference is computed with torch on the host.  The candidates are the first k of the order (fp16 value descending, index
