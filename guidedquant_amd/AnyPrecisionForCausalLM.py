@@ -76,52 +76,27 @@ class _CapturedStep:
     """State of route 2 (`generate(capture=True)`): the StaticCache, the device words the captured step reads and writes, and the
     hipGraph of one token step of the HF module tree.  A plain object -- no closure over its own state, so no reference cycle owns the
     graph -- with an explicit `close()`: the owner (`AnyPrecisionForCausalLM._evict`) destroys the graph when it drops the entry."""
-    __slots__ = ("model", "V", "top_k", "top_p", "temperature", "seed", "cache", "tok64", "tok", "pos", "nxt", "ctr", "wv", "wi", "ban", "seq", "logits", "graph",
-                 "rp", "seen", "suppress")
+    __slots__ = ("model", "sampler", "cache", "tok64", "tok", "pos", "nxt", "logits", "graph")
 
     def __init__(self, model, config, dev, total, temperature, top_k, seed, top_p=1.0, repetition_penalty=1.0, suppress_tokens=()):
         from transformers import StaticCache
-        self.model, self.V, self.top_k, self.temperature, self.seed = model, int(config.vocab_size), int(top_k), float(temperature), int(seed)
-        self.top_p = float(top_p)
+        from .fused_sampler import FusedSampler
+        self.model = model
         self.cache = StaticCache(config=config, max_cache_len=total)
+        # (the fused sampler and its state: counter, workspace, ban, the sequence store and -- with a penalty or a suppress list -- the sets)
+        self.sampler = FusedSampler(config.vocab_size, dev, top_k, top_p, temperature, seed, seq_capacity=total + 1,
+                                    repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens)
         z = lambda n, dt: torch.zeros(n, dtype=dt, device=dev)  # noqa: E731
         self.tok64 = z((1, 1), torch.long)
-        self.tok, self.pos, self.nxt, self.ctr = z((1, ), torch.int32), z((1, ), torch.int32), z((1, ), torch.int32), z((1, ), torch.int32)
-        self.wv, self.wi, self.ban = z(128 * 64, torch.float32), z(128 * 64, torch.int32), z(6, torch.int32)
-        self.seq, self.logits = z(total + 1, torch.int32), z(self.V, torch.float16)
+        self.tok, self.pos, self.nxt = z((1, ), torch.int32), z((1, ), torch.int32), z((1, ), torch.int32)
+        self.logits = z(int(config.vocab_size), torch.float16)
         self.graph = None
-        # (a penalty or a suppress list: the token sets of gq_sample_topk_rep; without either, the call and the buffers of before)
-        self.rp, self.seen, self.suppress = float(repetition_penalty), None, None
-        if self.rp != 1.0 or suppress_tokens:
-            self.seen = z((self.V + 31) // 32, torch.int32)
-            if suppress_tokens:
-                self.suppress = z((self.V + 31) // 32, torch.int32)
-                self.build_set(self.suppress, torch.tensor(list(suppress_tokens), dtype=torch.int32, device=dev))
-
-    def build_set(self, words, ids):
-        """words = the set of `ids` (cleared first), one launch outside the graph"""
-        from . import _lib
-        ids = ids.to(device=words.device, dtype=torch.int32).contiguous().view(-1)
-        _lib.check(_lib.lib().gq_token_set_build(ids.data_ptr() if ids.numel() else None, ids.numel(), self.V, words.data_ptr(), 1,
-                                                _lib.current_stream_ptr()), "gq_token_set_build")
 
     def step(self):
-        from . import _lib
         # (positions come from the cache itself: StaticLayer.cumulative_length is a device word the layer advances in place)
         out = self.model(input_ids=self.tok64, past_key_values=self.cache, use_cache=True)
         self.logits.copy_(out.logits.view(-1))
-        if self.seen is not None:
-            _lib.check(_lib.lib().gq_sample_topk_rep(self.logits.data_ptr(), self.V, self.top_k, self.top_p, self.temperature, self.seed, self.ctr.data_ptr(),
-                                                    self.wv.data_ptr(), self.wi.data_ptr(), self.tok.data_ptr(), self.pos.data_ptr(), self.nxt.data_ptr(),
-                                                    self.ban.data_ptr(), self.seq.data_ptr(), self.seq.numel(), None, None, 0, None, self.rp,
-                                                    self.seen.data_ptr(), self.suppress.data_ptr() if self.suppress is not None else None,
-                                                    _lib.current_stream_ptr()), "gq_sample_topk_rep")
-            self.tok64.copy_(self.tok.view(1, 1))
-            return
-        _lib.check(_lib.lib().gq_sample_topk_p(self.logits.data_ptr(), self.V, self.top_k, self.top_p, self.temperature, self.seed, self.ctr.data_ptr(),
-                                              self.wv.data_ptr(), self.wi.data_ptr(), self.tok.data_ptr(), self.pos.data_ptr(), self.nxt.data_ptr(),
-                                              self.ban.data_ptr(), self.seq.data_ptr(), self.seq.numel(), None, None, 0, None,
-                                              _lib.current_stream_ptr()), "gq_sample_topk_p")
+        self.sampler.launch(self.logits, self.tok, self.pos, self.nxt)
         self.tok64.copy_(self.tok.view(1, 1))
 
     def _set_cache_length(self, n):
@@ -130,28 +105,20 @@ class _CapturedStep:
                 layer.cumulative_length.fill_(n)
 
     def capture(self, T):
-        """two eager steps on a side stream, then the capture; the cache and the positions are re-set behind them"""
-        from ._graphs import capture
-        keep = (self.tok64.clone(), self.tok.clone(), self.ctr.clone(), self.seen.clone() if self.seen is not None else None)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self.step()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with capture(g):
-            self.step()
-        torch.cuda.synchronize()
-        self.graph = g
+        """two eager steps on a side stream, then the capture; the cache, the positions and the request's sampler state (its counter
+        word, the `seen` set of its prompt) are re-set behind them"""
+        from ._graphs import captured, warm_up
+        s = self.sampler
+        keep = (self.tok64.clone(), self.tok.clone(), s.counter.clone(), s.seen.clone() if s.seen is not None else None)
+        warm_up(self.step, 2)
+        self.graph = captured(self.step)
         # the warm-up steps wrote cache rows T-1 .. T+1 and moved the positions: rows past the position are overwritten before they are
         # read (causal), the rest is restored
         self.tok64.copy_(keep[0])
         self.tok.copy_(keep[1])
-        self.ctr.copy_(keep[2])
-        if self.seen is not None:  # (the warm-up steps left their draws in the set)
-            self.seen.copy_(keep[3])
+        s.reseed(keep[2])
+        if s.seen is not None:  # (the warm-up steps left their draws in the set)
+            s.seen.copy_(keep[3])
         self.pos.fill_(T - 1)
         if T == 1:  # (no prompt pass ran: the layers allocated their tensors inside the warm-up)
             self.cache.reset()
@@ -765,6 +732,39 @@ class AnyPrecisionForCausalLM(nn.Module):
             req["streamer"].put(seq_host[lo:(cut or hi)])
         return cut
 
+    def _run_request(self, req, ids, sampler, run, chunk=32, logprobs=False):
+        """One request on a fused route, from the point where the caches hold the prompt but for its last token and that token and its
+        position are set: the sampler's per-request state (the sequence prefix, the `ban` words of min_new_tokens, a fresh counter word
+        for a sampled call, the `seen` set of the prompt), then `run(n)` -- n token steps of the route -- in chunks of `chunk` tokens with
+        the EOS check and the streamer in between; returns what `generate` returns."""
+        T, max_new = req["T"], req["max_new"]
+        ids32 = ids.view(-1).to(torch.int32)
+        sampler.seq[:T].copy_(ids32)
+        # EOS cannot be drawn before min_new_tokens are out: the token of the step at position p is new token number p + 2 - T
+        sampler.set_ban(req["eos"], T - 1 + req["min_new"])
+        if req.get("do_sample"):
+            sampler.reseed(self._fresh_rng_word())
+        sampler.set_history(ids32)  # (the penalty's token set: all T prompt tokens, rebuilt per request)
+        if req["streamer"] is not None:
+            req["streamer"].put(ids.cpu())
+        done, cut = 0, None
+        host_checks = bool(req["eos"]) and req["min_new"] < max_new or req["streamer"] is not None
+        while done < max_new and cut is None:
+            n = min(chunk, max_new - done) if host_checks else max_new - done
+            run(n)
+            if host_checks:
+                seq_host = sampler.seq[:T + done + n].cpu().long()
+                cut = self._emit(req, seq_host, T + done, T + done + n)
+            done += n
+        end = cut if cut is not None else T + done
+        out = sampler.seq[:end].to(ids.dtype).view(1, -1).clone()
+        if logprobs:  # (slot i of the two arrays describes seq[i]: the sampler's index)
+            out = GenerateLogprobsOutput(sequences=out, logprobs=sampler.lp_raw[T:end].view(1, -1).clone(),
+                                         sampled_logprobs=sampler.lp_drawn[T:end].view(1, -1).clone())
+        if req["streamer"] is not None:
+            req["streamer"].end()
+        return out
+
     def _generate_native(self, dec, req, chunk=32, kv_cache_dtype="fp16", logprobs=False):
         from . import generate as gen
         ids, T, max_new = req["ids"].to(self.device), req["T"], req["max_new"]
@@ -788,14 +788,14 @@ class AnyPrecisionForCausalLM(nn.Module):
                                     repetition_penalty=req["repetition_penalty"], suppress_tokens=req["suppress_tokens"],
                                     **({"logprobs": True} if logprobs else {}))
             self._native_cache[("graph",) + key] = graph
-        if req.get("do_sample"):
-            graph.rng_counter.copy_(self._fresh_rng_word())
         ids32 = ids.view(-1).to(torch.int32)
+
+        def run(n):
+            for _ in range(n // graph.steps_per_replay):
+                graph.step()
+            for _ in range(n % graph.steps_per_replay):
+                graph.step_one()
         with torch.inference_mode():
-            graph.seq[:T].copy_(ids32)
-            # EOS cannot be drawn before min_new_tokens are out: the token of the step at position p is new token number p + 2 - T
-            ban = [len(req["eos"]), T - 1 + req["min_new"]] + req["eos"] + [0] * (4 - len(req["eos"]))
-            graph.ban.copy_(torch.tensor(ban, dtype=torch.int32), non_blocking=False)
             if T > 1:  # the prompt but for its last token fills the caches (HIP prompt pass; one eager step for a single token)
                 pre, pos = ids32[:T - 1], torch.arange(0, T - 1, device=self.device, dtype=torch.int32)
                 if dec.prefill_ready(pre):
@@ -805,34 +805,12 @@ class AnyPrecisionForCausalLM(nn.Module):
                 else:
                     dec(pre.view(1, -1), pos)
             graph.set_token(ids32[T - 1:T], T - 1)
-            graph.set_history(ids32)  # (the penalty's token set: all T prompt tokens, rebuilt per request)
-            if req["streamer"] is not None:
-                req["streamer"].put(ids.cpu())
-            done, cut = 0, None
-            host_checks = bool(req["eos"]) and req["min_new"] < max_new or req["streamer"] is not None
-            while done < max_new and cut is None:
-                n = min(chunk, max_new - done) if host_checks else max_new - done
-                for _ in range(n // graph.steps_per_replay):
-                    graph.step()
-                for _ in range(n % graph.steps_per_replay):
-                    graph.step_one()
-                if host_checks:
-                    seq_host = graph.seq[:T + done + n].cpu().long()
-                    cut = self._emit(req, seq_host, T + done, T + done + n)
-                done += n
-            end = cut if cut is not None else T + done
-            out = graph.seq[:end].to(ids.dtype).view(1, -1).clone()
-            if logprobs:  # (slot i of the two arrays describes seq[i]: the sampler's index)
-                out = GenerateLogprobsOutput(sequences=out, logprobs=graph.lp_raw[T:end].view(1, -1).clone(),
-                                             sampled_logprobs=graph.lp_drawn[T:end].view(1, -1).clone())
-        if req["streamer"] is not None:
-            req["streamer"].end()
-        return out
+            return self._run_request(req, ids, graph.sampler, run, chunk, logprobs)
 
     # -- route 2: the module tree, decode step captured -------------------------------------------------------------------
     def _generate_captured(self, req, chunk=32):
         """bs = 1 decode on the HF module tree with ONE hipGraph per token: the step `logits = model(input_ids [1,1], StaticCache,
-        cache_position)` + the fused sampler (gq_sample_topk_ex: the draw, EOS suppression, the sequence store, token feedback) are
+        cache_position)` + the fused sampler (FusedSampler.launch: the draw, EOS suppression, the sequence store, token feedback) are
         captured once per (precision, cache length, sampling) and replayed; the prompt runs eagerly through the same cache."""
         ids, T, max_new = req["ids"].to(self.device), req["T"], req["max_new"]
         total = T + max_new
@@ -847,37 +825,18 @@ class AnyPrecisionForCausalLM(nn.Module):
                                    req["repetition_penalty"], req["suppress_tokens"])
                 self._native_cache[key] = st
             st.cache.reset()
-            st.seq[:T].copy_(ids.view(-1).to(torch.int32))
-            ban = [len(req["eos"]), T - 1 + req["min_new"]] + req["eos"] + [0] * (4 - len(req["eos"]))
-            st.ban.copy_(torch.tensor(ban, dtype=torch.int32))
-            if req.get("do_sample"):
-                st.ctr.copy_(self._fresh_rng_word())
-            if st.seen is not None:  # (all T prompt tokens, per request; the capture's warm-up steps restore it)
-                st.build_set(st.seen, ids.view(-1))
             if T > 1:
                 self.model(input_ids=ids[:, :T - 1], past_key_values=st.cache, use_cache=True)
             st.tok64.copy_(ids[:, T - 1:T])
             st.tok.copy_(ids.view(-1)[T - 1:T].to(torch.int32))
             st.pos.fill_(T - 1)
-            if st.graph is None:
-                st.capture(T)
-            if req["streamer"] is not None:
-                req["streamer"].put(ids.cpu())
-            done, cut = 0, None
-            host_checks = bool(req["eos"]) and req["min_new"] < max_new or req["streamer"] is not None
-            while done < max_new and cut is None:
-                n = min(chunk, max_new - done) if host_checks else max_new - done
+
+            def run(n):
+                if st.graph is None:  # (behind the request's set-up: the capture restores the counter word and the prompt's `seen` set)
+                    st.capture(T)
                 for _ in range(n):
                     st.graph.replay()
-                if host_checks:
-                    seq_host = st.seq[:T + done + n].cpu().long()
-                    cut = self._emit(req, seq_host, T + done, T + done + n)
-                done += n
-            end = cut if cut is not None else T + done
-            out = st.seq[:end].to(ids.dtype).view(1, -1).clone()
-        if req["streamer"] is not None:
-            req["streamer"].end()
-        return out
+            return self._run_request(req, ids, st.sampler, run, chunk)
 
     @staticmethod
     def _load_config(model_path, trust_remote_code=True):

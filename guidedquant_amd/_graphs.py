@@ -32,6 +32,27 @@ def capture(graph, stream=None, **kw):
             gc.enable()
 
 
+def warm_up(fn, times=1):
+    """what goes before a capture: `fn()` `times` times on a side stream (lazy kernel attributes, the allocator), the current stream
+    and the side stream waiting for each other, then a device synchronize"""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(times):
+            fn()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+
+
+def captured(fn):
+    """a fresh graph of the launches `fn()` makes, through `capture()`; the device is idle when it returns"""
+    g = torch.cuda.CUDAGraph()
+    with capture(g):
+        fn()
+    torch.cuda.synchronize()
+    return g
+
+
 def release(*graphs):
     """destroy the executable graphs NOW (idempotent; None entries are skipped).  Must not be called while a stream is capturing."""
     for g in graphs:

@@ -1,0 +1,99 @@
+"""The host side of the fused sampler (csrc/sampler.hip): its device state, its validation and its one C call.
+
+Every decode route that draws on the device -- `generate.DecodeGraph`, route 2's `_CapturedStep`, `tp.TensorParallelDecoder`,
+`pipeline.PipelinedDecoder` -- owns one `FusedSampler` and ends its token step with `launch`.  Which entry point a configuration
+needs is decided here and nowhere else:
+  * log-probabilities                  -> gq_sample_topk_lp;
+  * a penalty or a suppress list       -> gq_sample_topk_rep (the instances over fp32 candidate values and the token sets);
+  * everything else                    -> gq_sample_topk_p -- never _rep or _lp with neutral arguments: those launch the fp32-key
+                                          instances, about 10.8 us per token more;
+  * a workspace of 32 candidates/block -> gq_sample_topk, the narrow call of the layer pipeline (draw only: no ban, no sequence store).
+"""
+import torch
+
+from . import _lib
+
+BLOCKS = 128  # (stage 1's grid: the workspace holds `candidates` entries of each block)
+
+
+class FusedSampler:
+    """State: `counter` (the RNG counter word), `work_val` / `work_idx` (stage 1's candidates), `ban` (int32 {n, until_pos, id0..id3}:
+    tokens that cannot be drawn while pos < until_pos) -- and, only when asked for, `seq` (seq_capacity > 0: every drawn token at
+    seq[pos + 1]), `seen` / `suppress` (a penalty != 1 or a suppress list: uint32 bitmaps over the vocabulary; every drawn token joins
+    `seen` on the device), `lp_ws` / `lp_raw` / `lp_drawn` (logprobs: the log-probability of every drawn token at [pos + 1], under the
+    model's unprocessed distribution and under the one the draw was made from).  A request without them allocates nothing extra."""
+
+    def __init__(self, vocab_size, device, top_k, top_p=1.0, temperature=1.0, seed=1234, seq_capacity=0, repetition_penalty=1.0,
+                 suppress_tokens=(), logprobs=False, candidates=64):
+        self.vocab_size, self.top_k, self.top_p, self.temperature, self.seed = int(vocab_size), top_k, float(top_p or 1.0), float(temperature), int(seed)
+        self.repetition_penalty = float(repetition_penalty if repetition_penalty is not None else 1.0)
+        suppress_tokens = [int(t) for t in (suppress_tokens if suppress_tokens is not None else ())]
+        self.logprobs, self.narrow = bool(logprobs), candidates == 32
+        if not (self.repetition_penalty > 0.0 and self.repetition_penalty != float("inf")):
+            raise ValueError(f"repetition_penalty must be finite and > 0, not {repetition_penalty!r}")
+        if self.logprobs and not seq_capacity:
+            raise ValueError("logprobs=True needs seq_capacity > 0: the log-probabilities are stored where the tokens are")
+        if self.narrow and (seq_capacity or self.repetition_penalty != 1.0 or suppress_tokens or self.top_p != 1.0):
+            raise ValueError("a workspace of 32 candidates per block serves the draw alone (gq_sample_topk)")
+
+        def z(n, dtype=torch.int32):
+            return torch.zeros((int(n), ), dtype=dtype, device=device)
+        self.counter, self.ban = z(1), z(6)
+        self.work_val, self.work_idx = z(BLOCKS * candidates, torch.float32), z(BLOCKS * candidates)
+        self.seq = z(seq_capacity) if seq_capacity else None
+        self.seen = self.suppress = self.lp_ws = self.lp_raw = self.lp_drawn = None
+        if self.repetition_penalty != 1.0 or suppress_tokens:
+            words = (self.vocab_size + 31) // 32
+            self.seen = z(words)
+            if suppress_tokens:
+                self.suppress = z(words)
+                self.build_set(self.suppress, torch.tensor(suppress_tokens, dtype=torch.int32, device=device))
+        if self.logprobs:
+            self.lp_raw, self.lp_drawn = z(seq_capacity, torch.float32), z(seq_capacity, torch.float32)
+            self.lp_ws = z(_lib.SAMPLER_LP_WS, torch.float32)
+
+    def build_set(self, words, ids, clear=True):
+        """words = (clear: the set of `ids`; else: joined by `ids`), one launch outside any graph"""
+        ids = ids.to(device=words.device, dtype=torch.int32).contiguous().view(-1)
+        _lib.check(_lib.lib().gq_token_set_build(ids.data_ptr() if ids.numel() else None, ids.numel(), self.vocab_size, words.data_ptr(),
+                                                1 if clear else 0, _lib.current_stream_ptr()), "gq_token_set_build")
+
+    def set_history(self, ids):
+        """the sequence so far (a tensor or list of token ids: the prompt, with whatever was generated before): `seen` is cleared and
+        rebuilt from it.  Before the first step of every request; without a penalty or a suppress list there is no set and nothing happens."""
+        if self.seen is not None:
+            self.build_set(self.seen, ids if torch.is_tensor(ids) else torch.tensor(list(ids), dtype=torch.int32))
+
+    def set_ban(self, eos_ids, until_pos):
+        """the (at most 4) tokens that cannot be drawn while pos < until_pos: HF's min_new_tokens on EOS"""
+        eos_ids = [int(e) for e in eos_ids]
+        self.ban.copy_(torch.tensor([len(eos_ids), int(until_pos)] + eos_ids + [0] * (4 - len(eos_ids)), dtype=torch.int32))
+
+    def reseed(self, word):
+        """the start of the counter stream (a device word or an int): the captured launches read it from device memory"""
+        if torch.is_tensor(word):
+            self.counter.copy_(word)
+        else:
+            self.counter.fill_(int(word))
+
+    def clear_warmup(self):
+        """the warm-up and capture-time draws joined `seen`: their bits go"""
+        if self.seen is not None:
+            self.seen.zero_()
+
+    def launch(self, logits, tok_io, pos_io, next_tok, embed_table=None, x_out=None, dim=0, ssq_out=None):
+        """one draw from `logits` on the current stream: the token to `next_tok` and, fed back, to `tok_io`, with `pos_io` advanced;
+        embed_table / x_out / dim / ssq_out: the last block also writes the NEXT step's hidden state and its hand-over statistics"""
+        def p(t):
+            return t.data_ptr() if t is not None else None
+        draw = (self.temperature, self.seed, p(self.counter), p(self.work_val), p(self.work_idx), p(tok_io), p(pos_io), p(next_tok))
+        if self.narrow:
+            name, args = "gq_sample_topk", (p(logits), self.vocab_size, int(self.top_k)) + draw
+        else:
+            name, args = "gq_sample_topk_p", (p(logits), self.vocab_size, int(self.top_k), self.top_p) + draw + (
+                p(self.ban), p(self.seq), self.seq.numel() if self.seq is not None else 0, p(embed_table), p(x_out), dim, p(ssq_out))
+            if self.logprobs or self.seen is not None:
+                name, args = "gq_sample_topk_rep", args + (self.repetition_penalty, p(self.seen), p(self.suppress))
+            if self.logprobs:
+                name, args = "gq_sample_topk_lp", args + (p(self.lp_ws), p(self.lp_raw), p(self.lp_drawn), self.lp_raw.numel())
+        _lib.check(getattr(_lib.lib(), name)(*args, _lib.current_stream_ptr()), name)

@@ -16,8 +16,9 @@ import torch
 import torch.nn as nn
 
 from . import pack
-from ._graphs import capture, release
+from ._graphs import capture, captured, release, warm_up
 from .APLinear import APLinear
+from .fused_sampler import FusedSampler
 from .LUTGEMMLinear import LUTGEMMLinear
 from .model import Transformer
 
@@ -99,9 +100,10 @@ class DecodeGraph:
 
     def __init__(self, model: Transformer, device, native_sampling=False, seed=1234, fold_embed=False, seq_capacity=0, steps_per_replay=1,
                  repetition_penalty=1.0, suppress_tokens=None, logprobs=False, **sampling_kwargs):
-        """native_sampling: draw the token with the fused HIP sampler (gq_sample_topk_ex: same distribution as `sample`,
-        own counter-based RNG, top_k <= 64) and feed token / position back inside the graph; `next_prob` is then
-        not produced.  Default False = the reference's torch sampling ops, captured in the graph.
+        """native_sampling: draw the token with the fused HIP sampler (`self.sampler`, a fused_sampler.FusedSampler, which picks the
+        entry point: same distribution as `sample`, own counter-based RNG, top_k <= 64) and feed token / position back inside the
+        graph; `next_prob` is then not produced.  Default False = the reference's torch sampling ops, captured in the graph.
+        `rng_counter`, `work_val`, `work_idx`, `ban`, `seq`, `seen`, `suppress`, `lp_raw` and `lp_drawn` are the sampler's own tensors.
         fold_embed (native sampling only): the sampler's last block also writes the NEXT step's hidden state (the embedding row of
         the token it drew, model.py:121-130) and its hand-over statistics, so the captured step starts at layer 0's first GEMV -- one
         launch less per token.  The token of the first step must then be set through `set_token` (which runs the lookup once);
@@ -130,77 +132,32 @@ class DecodeGraph:
         self.fold_embed = bool(fold_embed) and self.native_sampling
         self.steps_per_replay = max(1, int(steps_per_replay)) if self.native_sampling else 1
         self.seed = seed
-        self.rng_counter = torch.zeros((1, ), dtype=torch.int32, device=device)
-        self.work_val = torch.zeros((128 * 64, ), dtype=torch.float32, device=device)
-        self.work_idx = torch.zeros((128 * 64, ), dtype=torch.int32, device=device)
+        self.sampling_kwargs = sampling_kwargs
+        if not self.native_sampling and ((repetition_penalty or 1.0) != 1.0 or suppress_tokens or logprobs):
+            raise ValueError("repetition_penalty / suppress_tokens / logprobs are served by the fused sampler only (native_sampling=True on a "
+                             "model with the fused decode step, top_k <= 64): the torch-sampling graph does not apply them")
+        # (the sampler's state under the names this class documents: the same tensor objects, not copies)
+        self.sampler = s = FusedSampler(model.config.vocab_size, device, sampling_kwargs.get("top_k"), sampling_kwargs.get("top_p"),
+                                        sampling_kwargs.get("temperature", 1.0), seed, seq_capacity, repetition_penalty, suppress_tokens, logprobs)
+        self.rng_counter, self.work_val, self.work_idx, self.ban, self.seq = s.counter, s.work_val, s.work_idx, s.ban, s.seq
+        self.seen, self.suppress, self._lp_ws, self.lp_raw, self.lp_drawn = s.seen, s.suppress, s.lp_ws, s.lp_raw, s.lp_drawn
+        self.repetition_penalty, self.logprobs = s.repetition_penalty, s.logprobs
         self.tok = torch.zeros((1, 1), dtype=torch.int32, device=device)
         self.pos = torch.zeros((1, ), dtype=torch.int32, device=device)
         self.next_tok = torch.zeros((1, 1), dtype=torch.int32, device=device)
         self.next_prob = torch.zeros((1, model.config.vocab_size), dtype=torch.float32, device=device)
-        self.seq = torch.zeros((int(seq_capacity), ), dtype=torch.int32, device=device) if seq_capacity else None
-        self.ban = torch.zeros((6, ), dtype=torch.int32, device=device)
-        self.sampling_kwargs = sampling_kwargs
-        self.repetition_penalty = float(repetition_penalty if repetition_penalty is not None else 1.0)
-        suppress_tokens = [int(t) for t in (suppress_tokens if suppress_tokens is not None else ())]
-        self.seen = self.suppress = None
-        if self.repetition_penalty != 1.0 or suppress_tokens:
-            if not self.native_sampling:
-                raise ValueError("repetition_penalty / suppress_tokens are served by the fused sampler only (native_sampling=True on a model "
-                                 "with the fused decode step, top_k <= 64): the torch-sampling graph does not apply them")
-            if not (self.repetition_penalty > 0.0 and self.repetition_penalty != float("inf")):
-                raise ValueError(f"repetition_penalty must be finite and > 0, not {repetition_penalty!r}")
-            words = (model.config.vocab_size + 31) // 32
-            self.seen = torch.zeros((words, ), dtype=torch.int32, device=device)
-            if suppress_tokens:
-                self.suppress = torch.zeros((words, ), dtype=torch.int32, device=device)
-                self._build_set(self.suppress, torch.tensor(suppress_tokens, dtype=torch.int32, device=device))
-        self.logprobs = bool(logprobs)
-        self.lp_raw = self.lp_drawn = self._lp_ws = None
-        if self.logprobs:
-            if not self.native_sampling or self.seq is None:
-                raise ValueError("logprobs=True is served by the fused sampler only (native_sampling=True on a model with the fused decode "
-                                 "step, top_k <= 64) and needs seq_capacity > 0: the log-probabilities are stored where the tokens are")
-            from . import _lib
-            self.lp_raw = torch.zeros((int(seq_capacity), ), dtype=torch.float32, device=device)
-            self.lp_drawn = torch.zeros((int(seq_capacity), ), dtype=torch.float32, device=device)
-            self._lp_ws = torch.zeros((_lib.SAMPLER_LP_WS, ), dtype=torch.float32, device=device)
-        # warm up on a side stream (lazy kernel attributes, allocator), then capture
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self._step()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with capture(self.graph):
-            for _ in range(self.steps_per_replay):
-                self._step()
-        torch.cuda.synchronize()
+        warm_up(self._step, 2)
+        self.graph = captured(lambda: [self._step() for _ in range(self.steps_per_replay)])
         # (a single-step graph over the same state tensors for what is left of a sequence: `step_one`)
-        self.graph1 = self.graph
-        if self.steps_per_replay > 1:
-            self.graph1 = torch.cuda.CUDAGraph()
-            with capture(self.graph1):
-                self._step()
-            torch.cuda.synchronize()
-        if self.seen is not None:  # (the warm-up and capture-time steps drew tokens: their bits go)
-            self.seen.zero_()
+        self.graph1 = captured(self._step) if self.steps_per_replay > 1 else self.graph
+        s.clear_warmup()
         self._bound = self._signature()
         self._gen = getattr(model, "_alloc_gen", 0)
 
-    def _build_set(self, words, ids, clear=True):
-        from . import _lib
-        ids = ids.to(device=words.device, dtype=torch.int32).contiguous().view(-1)
-        _lib.check(_lib.lib().gq_token_set_build(ids.data_ptr() if ids.numel() else None, ids.numel(), self.model.config.vocab_size, words.data_ptr(),
-                                                1 if clear else 0, _lib.current_stream_ptr()), "gq_token_set_build")
-
     def set_history(self, ids):
-        """the sequence so far (a tensor or list of token ids: the prompt, with whatever was generated before): `seen` is cleared and
-        rebuilt from it, outside the graph.  To be called next to `set_token` before the first step of a request; without a penalty or a
-        suppress list there is no set and nothing happens."""
-        if self.seen is not None:
-            self._build_set(self.seen, ids if torch.is_tensor(ids) else torch.tensor(list(ids), dtype=torch.int32))
+        """the sequence so far (the prompt, with whatever was generated before): `seen` is rebuilt from it, outside the graph
+        (FusedSampler.set_history).  To be called next to `set_token` before the first step of a request."""
+        self.sampler.set_history(ids)
 
     def close(self):
         """destroy the captured graphs now (an owner that drops a DecodeGraph calls this instead of leaving the executable graphs to
@@ -252,7 +209,6 @@ class DecodeGraph:
 
     def _step(self):
         if self.native_sampling:
-            from . import _lib
             m = self.model
             if self.fold_embed:
                 with torch.cuda.device(m.output.weight.device):
@@ -260,45 +216,11 @@ class DecodeGraph:
                     ho0 = self._ho0()
                     m.native_layers(st["x"], self.pos.view(1), 0, len(m.layers), ssq_ready=ho0)
                     logits = m.native_head(st["x"])
-                emb, xo, so = m.tok_embeddings.weight.data_ptr(), st["x"].data_ptr(), (st["ssq"].data_ptr() if ho0 else None)
+                emb, xo, so = m.tok_embeddings.weight, st["x"], (st["ssq"] if ho0 else None)
             else:
                 logits = m.decode_native(self.tok.view(1), self.pos.view(1))
                 emb = xo = so = None
-            kw = self.sampling_kwargs
-            if self.logprobs:  # (the draw of gq_sample_topk_rep -- without the sets: of gq_sample_topk_p -- and its log-probabilities)
-                _lib.check(_lib.lib().gq_sample_topk_lp(logits.data_ptr(), m.config.vocab_size, int(kw["top_k"]), float(kw.get("top_p") or 1.0),
-                                                       float(kw.get("temperature", 1.0)), int(self.seed), self.rng_counter.data_ptr(),
-                                                       self.work_val.data_ptr(), self.work_idx.data_ptr(), self.tok.data_ptr(),
-                                                       self.pos.data_ptr(), self.next_tok.data_ptr(), self.ban.data_ptr(),
-                                                       self.seq.data_ptr(), self.seq.numel(), emb, xo, m.config.dim, so,
-                                                       self.repetition_penalty, self.seen.data_ptr() if self.seen is not None else None,
-                                                       self.suppress.data_ptr() if self.suppress is not None else None,
-                                                       self._lp_ws.data_ptr(), self.lp_raw.data_ptr(), self.lp_drawn.data_ptr(),
-                                                       self.lp_raw.numel(), _lib.current_stream_ptr()),
-                           "gq_sample_topk_lp")
-                return
-            if self.seen is not None:  # (a penalty or a suppress list: the instances over fp32 candidate values and the token sets)
-                _lib.check(_lib.lib().gq_sample_topk_rep(logits.data_ptr(), m.config.vocab_size, int(kw["top_k"]), float(kw.get("top_p") or 1.0),
-                                                        float(kw.get("temperature", 1.0)), int(self.seed), self.rng_counter.data_ptr(),
-                                                        self.work_val.data_ptr(), self.work_idx.data_ptr(), self.tok.data_ptr(),
-                                                        self.pos.data_ptr(), self.next_tok.data_ptr(), self.ban.data_ptr(),
-                                                        self.seq.data_ptr() if self.seq is not None else None,
-                                                        self.seq.numel() if self.seq is not None else 0, emb, xo, m.config.dim, so,
-                                                        self.repetition_penalty, self.seen.data_ptr(),
-                                                        self.suppress.data_ptr() if self.suppress is not None else None,
-                                                        _lib.current_stream_ptr()),
-                           "gq_sample_topk_rep")
-                return
-            # (top_p: nucleus filter on the top-k survivors, transformers' warper chain -- 1 = off)
-            _lib.check(_lib.lib().gq_sample_topk_p(logits.data_ptr(), m.config.vocab_size, int(kw["top_k"]), float(kw.get("top_p") or 1.0),
-                                                  float(kw.get("temperature", 1.0)), int(self.seed), self.rng_counter.data_ptr(),
-                                                   self.work_val.data_ptr(), self.work_idx.data_ptr(), self.tok.data_ptr(),
-                                                   self.pos.data_ptr(), self.next_tok.data_ptr(), self.ban.data_ptr(),
-                                                   self.seq.data_ptr() if self.seq is not None else None,
-                                                   self.seq.numel() if self.seq is not None else 0, emb, xo, m.config.dim, so,
-                                                   _lib.current_stream_ptr()),
-                       "gq_sample_topk_p")
-            return
+            return self.sampler.launch(logits, self.tok, self.pos, self.next_tok, emb, xo, m.config.dim, so)
         t, p = decode_one_token(self.model, self.tok, self.pos, **{k: v for k, v in self.sampling_kwargs.items() if k != "top_p"})
         self.next_tok.copy_(t)
         self.next_prob.copy_(p)

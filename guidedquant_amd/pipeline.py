@@ -37,7 +37,8 @@ from typing import List, Optional
 import torch
 import torch.distributed as dist
 
-from ._graphs import capture
+from ._graphs import captured, warm_up
+from .fused_sampler import FusedSampler
 from .model import mask_rows
 
 
@@ -133,9 +134,8 @@ class PipelinedDecoder:
             self.h_host = torch.zeros(S, c.dim, dtype=dt).pin_memory()
             self.tok_host = torch.zeros(S, dtype=torch.int32).pin_memory()
         if self.native and self.last:
-            self.rng_counter = torch.zeros(1, dtype=torch.int32, device=dev)
-            self.work_val = torch.zeros(128 * 32, dtype=torch.float32, device=dev)
-            self.work_idx = torch.zeros(128 * 32, dtype=torch.int32, device=dev)
+            # (32 candidates per block: FusedSampler then makes the narrow gq_sample_topk call -- the draw alone, top_k <= 32)
+            self.sampler = FusedSampler(c.vocab_size, dev, top_k, 1.0, temperature, seed, candidates=32)
         if self.native:
             # the QTIP launch plans are bound to the model's own hidden-state buffer: compute there, copy in / out
             self._x = model._native_state()["x"] if model._native_kind() == "qtip" else None
@@ -276,12 +276,8 @@ class PipelinedDecoder:
             h.copy_(x)
 
     def _sample_native(self, logits, slot):
-        from . import _lib
         if self.top_k is not None and self.top_k <= 32:
-            _lib.check(_lib.lib().gq_sample_topk(logits.data_ptr(), self.model.config.vocab_size, int(self.top_k), float(self.temperature),
-                                                int(self.seed), self.rng_counter.data_ptr(), self.work_val.data_ptr(),
-                                                self.work_idx.data_ptr(), None, None, self.tok_out[slot:slot + 1].data_ptr(),
-                                                _lib.current_stream_ptr()), "gq_sample_topk")
+            self.sampler.launch(logits, None, None, self.tok_out[slot:slot + 1])
         else:
             from .generate import sample
             idx, _ = sample(logits.view(1, 1, -1), temperature=self.temperature, top_k=self.top_k)
@@ -315,23 +311,11 @@ class PipelinedDecoder:
 
     def _capture(self):
         """one hipGraph per slot (the slot selects the KV caches, buffers and position word the launches point at)"""
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s), torch.no_grad():
-            for slot in range(self.n_seq):  # warm-up: lazy kernel attributes, allocator (without the hops: no peer is ticking yet)
-                self._tick_native(slot)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        self.graphs = []
-        for slot in range(self.n_seq):
-            g = torch.cuda.CUDAGraph()
-            with capture(g), torch.no_grad():
-                if self.hop == "ipc":
-                    self._tick_ipc(slot)
-                else:
-                    self._tick_native(slot)
-            self.graphs.append(g)
-        torch.cuda.synchronize()
+        tick = self._tick_ipc if self.hop == "ipc" else self._tick_native
+        with torch.no_grad():
+            # warm-up: lazy kernel attributes, allocator (without the hops: no peer is ticking yet)
+            warm_up(lambda: [self._tick_native(slot) for slot in range(self.n_seq)])
+            self.graphs = [captured(lambda: tick(slot)) for slot in range(self.n_seq)]
         self.reset()
 
     def reset(self):
@@ -339,7 +323,7 @@ class PipelinedDecoder:
         self.pos_dev.zero_()
         self.pos = [0] * self.n_seq
         if self.native and self.last:
-            self.rng_counter.zero_()
+            self.sampler.reseed(0)
         if self.hop == "ipc":
             self.tick.zero_()
             self.tick64.zero_()

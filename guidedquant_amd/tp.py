@@ -23,7 +23,8 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from ._graphs import capture
+from ._graphs import captured, warm_up
+from .fused_sampler import FusedSampler
 from .model import Transformer, _pair_perm
 
 
@@ -91,10 +92,8 @@ class TensorParallelDecoder:
         self.tok = torch.zeros(1, dtype=torch.int32, device=dev)
         self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
         self.next_tok = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.rng_counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.work_val = torch.zeros(128 * 64, dtype=torch.float32, device=dev)
-        self.work_idx = torch.zeros(128 * 64, dtype=torch.int32, device=dev)
-        self.out_buf = torch.zeros(max_new_tokens + 1, dtype=torch.int32, device=dev)
+        self.sampler = FusedSampler(c.vocab_size, dev, top_k, 1.0, temperature, seed, seq_capacity=max_new_tokens + 1)
+        self.out_buf = self.sampler.seq  # (the sampler's sequence store: the token drawn at position p at [p + 1])
         self.tick = torch.zeros(1, dtype=torch.int32, device=dev)   # exchanges completed before this step: step * 4 * n_layer
         self.err = torch.zeros(1, dtype=torch.int32, device=dev)
         self.spins = int(os.environ.get("GQ_HOP_SPINS", str(1 << 21)))
@@ -205,32 +204,23 @@ class TensorParallelDecoder:
                                        c.intermediate_size, bits, None, 0.0, h.data_ptr() + r * self.Dl * 2, 1, st), "w2")
             self._allgather(3, x, self.Dl, add + 4)
         logits = m.native_head(x)
-        ck(L.gq_sample_topk_ex(logits.data_ptr(), c.vocab_size, int(self.top_k), float(self.temperature), int(self.seed), self.rng_counter.data_ptr(),
-                               self.work_val.data_ptr(), self.work_idx.data_ptr(), self.tok.data_ptr(), self.pos.data_ptr(), self.next_tok.data_ptr(),
-                               None, self.out_buf.data_ptr(), self.out_buf.numel(), None, None, 0, None, st), "sample")
+        self.sampler.launch(logits, self.tok, self.pos, self.next_tok)
         self.tick.add_(4 * len(self.layers))
 
     def _capture(self):
         from .generate import prime_graph_rng_state
         prime_graph_rng_state(self.dev)
         self._exchange = False  # warm-up without the hops (lazy kernel attributes, allocator): no peer is stepping yet
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s), torch.no_grad():
-            self._step()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        self._exchange = True
-        self.graph = torch.cuda.CUDAGraph()
-        with capture(self.graph), torch.no_grad():
-            self._step()
-        torch.cuda.synchronize()
+        with torch.no_grad():
+            warm_up(self._step)
+            self._exchange = True
+            self.graph = captured(self._step)
         self.reset()
 
     def reset(self):
         self.tok.fill_(self.bos_id)
         self.pos.zero_()
-        self.rng_counter.zero_()
+        self.sampler.reseed(0)
         self.tick.zero_()
         self._seq.zero_()
         self.out_buf.zero_()
