@@ -7,9 +7,16 @@
 
 #include "ap_core.h"
 #include "ap_dispatch.h"
+#include "wave_util.h"
 
 namespace {
 using namespace gq;
+using gqw::f2h;
+using gqw::h2f;
+using gqw::make_rsrc;
+using gqw::rsrc_t;
+using gqw::u32x4;
+using gqw::wave_allsum;
 
 struct ApArgs {
     const u32 *qw;         // [bits][N][K/32]
@@ -38,14 +45,10 @@ inline ApArgs ap_args(const ApLaunch &L, u32 RS, u32 SPB) {
 }
 
 __device__ __forceinline__ uint4 ld16(const void *p) { return *reinterpret_cast<const uint4 *>(p); }
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 ld16_nt(const void *p) {
     u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
     return make_uint4(v.x, v.y, v.z, v.w);
 }
-
-__device__ __forceinline__ float h2f(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-__device__ __forceinline__ uint16_t f2h(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
 
 // Fused prologues, with the same fp16 rounding points as the reference's separate kernels (ap_gemv.hip::stage_x, stage_x_natural below):
 //   PRO_RMSNORM: y = (x.float() * rsqrt(mean(x^2) + eps)).half() * w        (inference/model.py:281-292)
@@ -217,11 +220,11 @@ __device__ __forceinline__ void stage_x_natural(const RowGeom &G, const uint16_t
                 }
             }
         }
-        ss = gq_wave_allsum(ss);
+        ss = wave_allsum(ss);
         if ((tid & 63u) == 0 && stager) red[tid >> 6] = ss;
         __syncthreads();
         // (the stager waves' sums: one LDS round trip + the same register tree, instead of one dependent ds_read per wave)
-        const float tot = gq_wave_allsum((tid & 63u) < (T + 63u) / 64u ? red[tid & 63u] : 0.f);
+        const float tot = wave_allsum((tid & 63u) < (T + 63u) / 64u ? red[tid & 63u] : 0.f);
         scale = 1.0f / sqrtf(tot / (float)G.K + eps);
     }
     for (u32 u = stager ? tid : nun; u < nun; u += T) {

@@ -27,11 +27,13 @@
 
 #include "ap_core.h"
 #include "ap_dispatch.h"
+#include "wave_util.h"
 
 namespace {
 using gq::u32;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using gqw::f16x8;
+using gqw::f32x16;
+using gqw::u32x4;
 
 constexpr u32 BS = 128, BN = 128, ROWB = 272;  // token tile, weight-row tile, bytes per token row of an x stage (256 + 16 pad)
 constexpr u32 STAGE_BYTES = BS * ROWB;
@@ -74,7 +76,6 @@ __device__ __forceinline__ f16x8 decode_byte(const u32 *w, u32 shift, const gq::
     u32 v[4];
     decode4<BITS>(hn, L, v[0], v[1]);
     decode4<BITS>(ln, L, v[2], v[3]);
-    typedef u32 u32x4 __attribute__((ext_vector_type(4)));
     u32x4 t = {v[0], v[1], v[2], v[3]};
     return __builtin_bit_cast(f16x8, t);
 }
@@ -200,7 +201,6 @@ __global__ void __launch_bounds__(256, 2) ap_gemm_kernel(const uint16_t *__restr
 #pragma unroll
                     for (int p = 0; p < BITS; p++) wq[p] = w[f][p][q];
                     if (dbg & 1u) {  // ablation (GQ_GEMM_DBG=1): no decode
-                        typedef u32 u32x4 __attribute__((ext_vector_type(4)));
                         u32x4 t = {wq[0], wq[1], wq[0] ^ shift, wq[1] + (u32)q};
                         a[f] = __builtin_bit_cast(f16x8, t);
                     } else {
@@ -270,23 +270,11 @@ int launch_gemm_first(const void *x, void *out, const uint32_t *qw, const void *
 //   waitcnt pass would drain the queue before every LDS read): per iteration i the wave issues its 4 loads of stage i + 3
 //   and, at the first stage of a plane-word group, the RF * BITS 16-byte plane loads of the NEXT group; "at most 8 behind"
 //   at the end of iteration i therefore means stage i + 1 (and every plane word older than that) has landed.
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void g_dma16(u32x4 rsrc, u32 lds_base, u32 voff, u32 soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_base), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-__device__ __forceinline__ u32x4 g_load16(u32x4 rsrc, u32 voff, u32 soff) {
-    u32x4 r;
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(r) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-    return r;
-}
-template <int N>
-__device__ __forceinline__ void g_wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ u32x4 g_rsrc(const void *p, u32 bytes) {
-    const uint64_t a = (uint64_t)(uintptr_t)p;
-    return (u32x4){(u32)a, (u32)(a >> 32) & 0xFFFFu, bytes, 0x00020000u};  // raw buffer: reads past `bytes` return 0
-}
+//   (dma16<false>, bload128, wait_vm, make_rsrc4: wave_util.h "hand-issued vector memory"; reads past a descriptor's bytes return 0)
+using gqw::bload128;
+using gqw::dma16;
+using gqw::make_rsrc4;
+using gqw::wait_vm;
 
 constexpr u32 P_RING = 4u;  // stages in the ring (16 KiB each for 128 tokens, 32 KiB for 256)
 
@@ -320,8 +308,8 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) ap_gemm_pipe_kernel(
     const u32 g0 = ks * gper, ngroups = min(ngroups_all, g0 + gper), nst = 4u * ngroups;  // this block: groups [g0, ngroups), stages [4 g0, nst)
     const u32 plane_bytes = N * wpr * 4u;
 
-    const u32x4 rx = g_rsrc(x + (size_t)s0 * K, min(BT, S - s0) * K * 2u);
-    const u32x4 rq = g_rsrc(qw, plane_bytes * (u32)BITS);
+    const u32x4 rx = make_rsrc4(x + (size_t)s0 * K, min(BT, S - s0) * K * 2u);
+    const u32x4 rq = make_rsrc4(qw, plane_bytes * (u32)BITS);
 
     gq::LutPools<BITS> L[RF];
     u32 rowoff[RF];  // byte offset of the lane's row in a plane
@@ -367,7 +355,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) ap_gemm_pipe_kernel(
 #pragma unroll
         for (int i = 0; i < (int)DSPAN; i++) {
             const u32 dseg = ((dsl0 >> 2) ^ (u32)(i & 1)) & 1u;
-            g_dma16(rx, lds0 + 1024u * (u32)i, (drow + 8u * (u32)i) * (2u * K) + dpart * 16u + dseg * 16u * hw, 2u * kseg0);
+            dma16<false>(rx, lds0 + 1024u * (u32)i, (drow + 8u * (u32)i) * (2u * K) + dpart * 16u + dseg * 16u * hw, 2u * kseg0);
         }
     };
     // plane words of group gi: the request writes INTO the loop-carried registers ("+v": a fresh output register would be
@@ -394,7 +382,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) ap_gemm_pipe_kernel(
     issue_planes(g0);
     for (u32 st = 4u * g0; st < 4u * g0 + 3u; st++)
         if (st < nst) issue_stage(st);
-    g_wait_vm<0>();
+    wait_vm<0>();
     __syncthreads();
 
     // one group = 4 stages (byte lanes c) on the same plane words.  FULL: all 4 K-steps present (every group of a whole chunk):
@@ -408,9 +396,9 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) ap_gemm_pipe_kernel(
     // request sits between them, which makes the wait stricter, never weaker); the last stages drain the queue
     auto stage_end = [&](u32 st) {
         if (st + 3u < nst)
-            g_wait_vm<2 * (int)DSPAN>();
+            wait_vm<2 * (int)DSPAN>();
         else
-            g_wait_vm<0>();
+            wait_vm<0>();
         __syncthreads();
     };
     auto take_words = [&](u32 (&w)[RF][BITS][4], u32 nq) {

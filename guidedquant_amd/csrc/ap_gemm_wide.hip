@@ -44,11 +44,13 @@
 
 #include "ap_core.h"
 #include "ap_dispatch.h"
+#include "wave_util.h"
 
 namespace {
 using gq::u32;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using gqw::f16x8;
+using gqw::f32x16;
+using gqw::lds_addr;
 
 constexpr u32 BS = 128, BN = 128, ROWB = 128;  // token tile, weight-row tile, bytes per tile row of a stage (64 fp16)
 constexpr u32 STAGE_BYTES = BS * ROWB;
@@ -61,9 +63,6 @@ struct GemmWideGeom {
     static constexpr size_t SMEM = 4u * STAGE_BYTES + BN * TS;
 };
 
-__device__ __forceinline__ u32 lds_addr(const void *p) {
-    return (u32)(uintptr_t)(__attribute__((address_space(3))) const unsigned char *)reinterpret_cast<const unsigned char *>(p);
-}
 __device__ __forceinline__ u32 lds_u16(u32 addr) { return *(const __attribute__((address_space(3))) uint16_t *)(uintptr_t)addr; }
 
 template <int BITS>

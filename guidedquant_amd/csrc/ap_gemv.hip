@@ -64,11 +64,11 @@ __device__ __forceinline__ void stage_x(const RowGeom &G, const uint16_t *x, con
                 }
             }
         }
-        ss = gq_wave_allsum(ss);
+        ss = wave_allsum(ss);
         if ((tid & 63u) == 0 && stager) red[tid >> 6] = ss;
         __syncthreads();
         // (the stager waves' sums: one LDS round trip + the same register tree, instead of one dependent ds_read per wave)
-        const float tot = gq_wave_allsum((tid & 63u) < (T + 63u) / 64u ? red[tid & 63u] : 0.f);
+        const float tot = wave_allsum((tid & 63u) < (T + 63u) / 64u ? red[tid & 63u] : 0.f);
         scale = 1.0f / sqrtf(tot / (float)G.K + eps);
     }
     for (u32 idx = idx0; idx < 4u * G.Q; idx += T) {
@@ -192,8 +192,8 @@ ap_gemv_quad_kernel(ApArgs a) {
     constexpr int NRAW = (1 << BITS) / 2;
     constexpr u32 OOB = 0x80000000u;
     const u32 plane_bytes = a.N * G.wpr * 4u;
-    __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void *)a.qw, 0, (int)(plane_bytes * (u32)BITS), 0x00020000);
-    __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void *)a.lut, 0, (int)(a.N * (u32)NRAW * 4u), 0x00020000);
+    rsrc_t rq = make_rsrc(a.qw, plane_bytes * (u32)BITS);
+    rsrc_t rl = make_rsrc(a.lut, a.N * (u32)NRAW * 4u);
 
     u32x4 P[D][BITS];
     u32 lraw[D][NRAW];
@@ -358,8 +358,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) a
     u32 *tabs = reinterpret_cast<u32 *>(smem + (((size_t)G.K * 2u + (size_t)SPB * RS * svrow * 2u + 63u) & ~(size_t)63u)) + wv * 32u;
     constexpr u32 OOB = 0x80000000u;
     const u32 plane_bytes = a.N * G.wpr * 4u;
-    __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void *)a.qw, 0, (int)(plane_bytes * (u32)BITS), 0x00020000);
-    __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void *)a.lut, 0, (int)(a.N * (u32)NRAW * 4u), 0x00020000);
+    rsrc_t rq = make_rsrc(a.qw, plane_bytes * (u32)BITS);
+    rsrc_t rl = make_rsrc(a.lut, a.N * (u32)NRAW * 4u);
     u32x4 P[BITS];
     u32 lraw[NRAW];
     auto issue = [&](u32 step) {
@@ -468,8 +468,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) a
 // Work: item = (16-row group, unit of 4 quads = 512 weights per row); wave w of a 16-wave block takes items w, w + 16, ..; the
 // K-split partial sums of a row group meet in LDS and are added in unit order (deterministic).
 // ----------------------------------------------------------------------------------------------
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using gqw::f16x8;
+using gqw::f32x4;
 
 template <int BITS>
 struct DqItem;  // run(P, L, emit): emit(v, k, w01 @ 2 k, w23 @ 2 k, w01 @ 2 k + 1, w23 @ 2 k + 1) for word v = 0..3, pair k = 0..3
@@ -585,11 +585,11 @@ __device__ __forceinline__ void stage_x_dqv(const RowGeom &G, const uint16_t *x,
                 }
             }
         }
-        ss = gq_wave_allsum(ss);
+        ss = wave_allsum(ss);
         if ((tid & 63u) == 0 && stager) red[tid >> 6] = ss;
         __syncthreads();
         // (the stager waves' sums: one LDS round trip + the same register tree, instead of one dependent ds_read per wave)
-        const float tot = gq_wave_allsum((tid & 63u) < (T + 63u) / 64u ? red[tid & 63u] : 0.f);
+        const float tot = wave_allsum((tid & 63u) < (T + 63u) / 64u ? red[tid & 63u] : 0.f);
         scale = 1.0f / sqrtf(tot / (float)G.K + eps);
     }
     for (u32 idx = idx0; idx < 4u * G.Q; idx += T) {
@@ -694,8 +694,8 @@ __global__ void __launch_bounds__(64 * DQ_WAVES) __attribute__((amdgpu_waves_per
     constexpr int NRAW = (1 << BITS) / 2;
     constexpr u32 OOB = 0x80000000u;
     const u32 plane_bytes = a.N * G.wpr * 4u;
-    __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void *)a.qw, 0, (int)(plane_bytes * (u32)BITS), 0x00020000);
-    __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void *)a.lut, 0, (int)(a.N * (u32)NRAW * 4u), 0x00020000);
+    rsrc_t rq = make_rsrc(a.qw, plane_bytes * (u32)BITS);
+    rsrc_t rl = make_rsrc(a.lut, a.N * (u32)NRAW * 4u);
     constexpr int D = DQ_RING;
     u32x4 P[D][BITS];
     u32 lraw[D][NRAW];
@@ -1030,7 +1030,6 @@ struct QuadCfg {
     size_t smem;
 };
 
-int num_cus() { return gq_cu_count(); }
 
 // `pt2`: the configuration is for the 2-bit pair-table kernel (4 waves per SIMD); `pairs`: the launch has the SiLU-pairs epilogue
 bool pick_quad_cfg(u32 N, u32 K, int bits, QuadCfg &c, int pro = PRO_NONE, bool pt2 = false, bool pairs = false) {
@@ -1066,7 +1065,7 @@ bool pick_quad_cfg(u32 N, u32 K, int bits, QuadCfg &c, int pro = PRO_NONE, bool 
     if (d < 1 || d > 4) d = bits <= 3 ? 1 : 2;
     if (bits == 4 && d > 3) d = 3;
     // persistent-style grid: about `bpc` blocks per CU (what the kernel's occupancy allows), every block the same number of steps
-    const u32 cus = (u32)num_cus();
+    const u32 cus = (u32)gq_cu_count();
     u32 bpc_def = bits <= 3 && d == 1 ? 3u : 2u;
     // a block of an RMSNorm launch normalises the whole vector before its first step: with ONE step per block (few rows: wqkv) the
     // 2-3 resident blocks of a CU repeat that side by side -- one block per CU then (measured, 8B wqkv: 3-bit 8.8 -> 8.4 us, 4-bit

@@ -1,6 +1,8 @@
 // ap_plane.hip -- "fast mode" Any-Precision GEMV for gfx950: binary bit-plane GEMVs on the matrix cores.
 //
-// See plane_core.h for the algorithm and the measured hardware facts.  What runs where:
+// See plane_core.h for the algorithm and the measured hardware facts; the device pieces shared with ap_stream.hip (the scaled MFMA,
+// the bf8 split of one value, the extraction threshold, SiLU * up) are in plane_mfma.h, the reductions, descriptors and hand-issued
+// vector-memory requests (why they are asm, how they are waited for) in wave_util.h.  What runs where:
 //   HBM    : the stored bit-planes, whole 128-byte lines (one row x one plane x one 1024-weight chunk), fetched by
 //            direct-to-LDS loads (buffer_load_dwordx4 ... lds) into per-wave rings of A tiles; the late half of the
 //            waves requests its tiles in its first instructions, the early half after it has built the B image.
@@ -22,16 +24,12 @@
 #include <type_traits>
 
 #include "ap_dispatch.h"
-#include "plane_core.h"
+#include "plane_mfma.h"
 
 using namespace gqp;
+using namespace gqw;  // (wave_util.h: casts, vector types, wave_reduce_l63 / row_sum, descriptors, the asm vector-memory requests)
 
 namespace {
-
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 
 struct PlaneArgs {
     const u32 *qw;
@@ -65,94 +63,6 @@ struct PlaneArgs {
 #define GQ_ABLATION 0
 #endif
 #define PL_XF(bit) (GQ_ABLATION && (a.xflags & (bit)))
-#ifndef PL_SSQ_MODE
-#define PL_SSQ_MODE 2  // statistics hand-over slots: plain stores, slots grouped by XCD (see plane_epilogue)
-#endif
-
-__device__ __forceinline__ float h2f(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-__device__ __forceinline__ uint16_t f2h(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
-
-// wave64 reductions on the DPP path (no LDS round trips): result valid in lane 63
-template <bool MAX>
-__device__ __forceinline__ float wave_reduce(float v) {
-    auto step = [&](auto dpp) {
-        float o = __builtin_bit_cast(float, dpp(__builtin_bit_cast(int, v)));
-        v = MAX ? fmaxf(v, o) : v + o;
-    };
-    step([](int x) { return __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false); });   // quad_perm [1,0,3,2]
-    step([](int x) { return __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false); });   // quad_perm [2,3,0,1]
-    step([](int x) { return __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false); });  // row_half_mirror
-    step([](int x) { return __builtin_amdgcn_update_dpp(x, x, 0x140, 0xF, 0xF, false); });  // row_mirror
-    {   // row_bcast15 into rows 1 and 3, row_bcast31 into rows 2 and 3 (identity elsewhere)
-        const int ident = MAX ? 0 : 0;  // |x| >= 0 and the sum identity are both 0.0f
-        float o = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(ident, __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, false));
-        v = MAX ? fmaxf(v, o) : v + o;
-        o = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(ident, __builtin_bit_cast(int, v), 0x143, 0xC, 0xF, false));
-        v = MAX ? fmaxf(v, o) : v + o;
-    }
-    return v;
-}
-
-
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef uint16_t us2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ h2v u2h2(u32 u) { return __builtin_bit_cast(h2v, u); }
-__device__ __forceinline__ u32 h22u(h2v h) { return __builtin_bit_cast(u32, h); }
-
-// The scaled MFMA with A = FP4 (4 registers; the upper half of the builtin's 8-register vector is ignored for cbsz = 4),
-// B = BF8.  Through the BUILTIN, not inline asm: the compiler must see the instruction to insert the MFMA hazard wait
-// states.  An asm version with a tied accumulator was tried (the register allocator otherwise lets vDst != SrcC wander):
-// no faster, and unsafe -- the compiler copied accumulators between registers right behind an MFMA it could not see.
-__device__ __forceinline__ void mfma_f4_bf8(v4f &acc, v4i a, v8i b, int scale_a, int scale_b) {
-    const v8i a8 = __builtin_shufflevector(a, a, 0, 1, 2, 3, -1, -1, -1, -1);
-    acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8, b, acc, 4, 1, 0, scale_a, 0, scale_b);
-}
-
-// --- hand-scheduled vector memory.  The compiler's waitcnt pass treats an LDS-DMA load as "may alias every later
-// LDS access" and drains vmcnt before the first ds_read / barrier, which would serialise the prologue behind the
-// whole plane stream.  So the plane loads and the activation loads that must overtake them are issued from inline
-// asm (invisible to that pass) and waited for with explicit s_waitcnt vmcnt(n) (vector memory returns in order).
-__device__ __forceinline__ void dma16(u32x4 rsrc, u32 lds_base, u32 voff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen nt lds" ::"s"(lds_base), "v"(voff), "s"(rsrc)
-                 : "memory");  // m0 is not otherwise used in this kernel (no compiler-generated LDS-DMA / movrel)
-}
-__device__ __forceinline__ void dma16s(u32x4 rsrc, u32 lds_base, u32 voff, u32 soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen nt lds" ::"s"(lds_base), "v"(voff), "s"(rsrc), "s"(soff)
-                 : "memory");
-}
-__device__ __forceinline__ u32 bload16s(u32x4 rsrc, u32 voff, u32 soff) {  // zero-extended 16-bit load
-    u32 r;
-    asm volatile("buffer_load_ushort %0, %1, %2, %3 offen" : "=v"(r) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-    return r;
-}
-__device__ __forceinline__ u32x4 bload128(u32x4 rsrc, u32 voff, u32 soff) {
-    u32x4 r;
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(r) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-    return r;
-}
-__device__ __forceinline__ void tie128(u32x4 &r) { asm volatile("" : "+v"(r)); }
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// wait until at most n * LPS vector-memory instructions of this wave are outstanding (n uniform, 0..4)
-template <int LPS>
-__device__ __forceinline__ void wait_vm_steps(u32 n) {
-    switch (n) {
-        case 0: wait_vm<0>(); break;
-        case 1: wait_vm<LPS>(); break;
-        case 2: wait_vm<2 * LPS>(); break;
-        case 3: wait_vm<3 * LPS>(); break;
-        default: wait_vm<4 * LPS>(); break;
-    }
-}
-// data dependence of asm-loaded registers on the preceding s_waitcnt (volatile asm statements keep their order)
-__device__ __forceinline__ void tie4(u32 (&r)[4]) { asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3])); }
-
-__device__ __forceinline__ u32x4 make_rsrc(const void *p, u32 bytes) {
-    const uint64_t a = (uint64_t)(uintptr_t)p;
-    return (u32x4){(u32)a, (u32)(a >> 32) & 0xFFFFu, bytes, 0x00020000u};  // raw buffer: stride 0, num_records = bytes
-}
 
 // software barrier among a subset of the waves (LDS counter): waves that may sit in the vector-memory issue queue
 // (issuing blocks once the CU's memory pipe is full) must not hold up a hardware barrier
@@ -262,23 +172,14 @@ __device__ __forceinline__ void mfma_chunk(v4f (&acc)[(1 << BITS) - 1], const u3
 // chance, and what stays in the image (<= 2^6 x the typical element) is below the ratio where the window starts to matter -- costs the early
 // waves one more sum in the statistics pass and every wave one scalar compare per step.
 //   entry = {key = row << 16 | chunk << 10 | (b * 2 + h) << 7 | k,  the 4 bf8 pieces of x * 2^ksh (byte p = piece p)}
-struct HotEnt {
-    u32 key, pieces;
-};
+// (HotEnt, GQ_HOT_T, hot_tau_bits: plane_mfma.h)
 typedef __attribute__((address_space(3))) u32 lds_u32;
 __device__ __forceinline__ void hot_append_inl(u32 *cnt_, HotEnt *list_, u32 cap, u32 key, uint16_t xh, uint16_t kh16) {
     // explicit LDS pointers: through generic ones the counter becomes a FLAT atomic (vmcnt: the wave's plane stream drains)
     lds_u32 *cnt = (lds_u32 *)cnt_, *list = (lds_u32 *)list_;
     const u32 idx = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (idx >= cap) return;  // unreachable (Chebyshev bound), kept as a guard against memory corruption
-    _Float16 rem = __builtin_bit_cast(_Float16, xh) * __builtin_bit_cast(_Float16, kh16);
-    u32 pieces = 0;
-#pragma unroll
-    for (u32 p = 0; p < 4; p++) {
-        const uint16_t pb = __builtin_bit_cast(uint16_t, rem) & 0xFF00u;
-        pieces |= (u32)(pb >> 8) << (8u * p);
-        rem = rem - __builtin_bit_cast(_Float16, pb);
-    }
+    const u32 pieces = bf8_split(xh, kh16);
     list[2u * idx] = key;
     list[2u * idx + 1u] = pieces;
 }
@@ -336,22 +237,6 @@ __device__ __forceinline__ void hot_step(v4f (&acc)[(1 << BITS) - 1], const u32 
         }
     }
 }
-// threshold of the extraction as an fp16 bit pattern (rounded up): 64 x the mean magnitude, 1 % above it for the roundings of the
-// estimate (sum1 = sum |x| over K elements)
-#define GQ_HOT_T 64.0f
-#ifndef HOT_ABL
-#define HOT_ABL 0  // ablation experiments (build-time): 1 no threshold, 2 no detection, 4 no extra MFMA sets
-#endif
-__device__ __forceinline__ u32 hot_tau_bits(float sum1, float K) {
-#if HOT_ABL & 1
-    return 0x7C00u;
-#endif
-    // the hardware reciprocal (1 ulp) is plenty next to the 1 % margin
-    const float tau = GQ_HOT_T * 1.01f * sum1 * __builtin_amdgcn_rcpf(K);
-    if (!(tau < 65000.f)) return 0x7C00u;  // nothing exceeds +inf: no extraction
-    return (u32)__builtin_bit_cast(uint16_t, (_Float16)tau) + 1u;
-}
-
 // item done: add the 4 piece columns (lanes col = 0..3 of each 16-lane group), park 16 x NP1 sums in LDS
 // (pitem[subset][row]: lane (col 0, kb) owns rows 4kb..4kb+3) and clear the accumulators
 template <int NP1>
@@ -361,10 +246,7 @@ __device__ __forceinline__ void park_item(v4f (&acc)[NP1], float *pitem, u32 col
         v4f v = acc[cm];
 #pragma unroll
         for (int q4 = 0; q4 < 4; q4++) {
-            float f = v[q4];
-            f += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, f), 0xB1, 0xF, 0xF, false));
-            f += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, f), 0x4E, 0xF, 0xF, false));
-            v[q4] = f;
+            v[q4] = row_sum<4>(v[q4]);
         }
         // (batch row mm = col / 4 of the multi-row instances: pitem[row][subset][16])
         if ((col & 3u) == 0u && (col >> 2) < MB) *reinterpret_cast<v4f *>(pitem + ((size_t)(col >> 2) * NP1 + cm) * 16u + 4u * kb) = v;
@@ -447,44 +329,19 @@ __device__ __forceinline__ void plane_epilogue(const PlaneArgs &a, const u32 *lu
             // values just stored, one slot per epilogue wave (whole waves: 16 RGB 2^b is a multiple of 64; host: one pass of this
             // loop, M = 1, plain / residual epilogue).  Fixed DPP tree: deterministic.
             const float v = (c == 0u && row < a.N) ? (float)yh * (float)yh : 0.f;
-            const float tot = wave_reduce<false>(v);
+            const float tot = wave_reduce_l63<false>(v);
             // slot: blocks go to the XCDs round-robin (block b on XCD b % 8) -- the 32 slots of a 128-byte line belong to ONE XCD's
-            // blocks, so the line is assembled in that XCD's L2 and written once (PL_SSQ_MODE: 0 write-through + linear slots, which
-            // measured +0.6 us on wo / w2: 8 XCDs read-modify-write each 32-byte sector)
+            // blocks, so the line is assembled in that XCD's L2 and written once, by plain stores (write-through stores into linear slots
+            // measured +0.6 us on wo / w2: 8 XCDs read-modify-write each 32-byte sector -- DESIGN.md section 3.7)
             const u32 sl = blockIdx.x * ((a.RGB * 16u * (u32)NP) >> 6) + (tid >> 6);
-#if PL_SSQ_MODE == 0
-            if ((tid & 63u) == 63u) gq_store_wt(a.ssq_out + sl, tot);
-#elif PL_SSQ_MODE == 1
-            if ((tid & 63u) == 63u) gq_store_wt(a.ssq_out + ((sl & 7u) * ((u32)GQ_SSQ_SLOTS / 8u) + (sl >> 3)), tot);
-#elif PL_SSQ_MODE == 2
             if ((tid & 63u) == 63u) a.ssq_out[(sl & 7u) * ((u32)GQ_SSQ_SLOTS / 8u) + (sl >> 3)] = tot;
-#else
-            if ((tid & 63u) == 63u) a.ssq_out[sl] = tot;
-#endif
         }
     }
     // (the consumer adds all GQ_SSQ_SLOTS: block 0 clears the slots no wave of the grid writes)
     if (f_ssq && blockIdx.x == 0u)
-        for (u32 i = gridDim.x * ((a.RGB * 16u * (u32)NP) >> 6) + tid; i < (u32)GQ_SSQ_SLOTS; i += T) {
-#if PL_SSQ_MODE == 1 || PL_SSQ_MODE == 2
+        for (u32 i = gridDim.x * ((a.RGB * 16u * (u32)NP) >> 6) + tid; i < (u32)GQ_SSQ_SLOTS; i += T)
             a.ssq_out[(i & 7u) * ((u32)GQ_SSQ_SLOTS / 8u) + (i >> 3)] = 0.f;
-#else
-            a.ssq_out[i] = 0.f;
-#endif
-        }
 }
-
-// F.silu(gate) * up on two packed fp16 pairs -- inference/model.py:266
-__device__ __forceinline__ u32 silu_mul2(u32 gw, u32 uw) {
-    _Float16 hh[2];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const float gv = h2f((uint16_t)(gw >> (16 * k)));
-        hh[k] = (_Float16)(gv / (1.0f + __expf(-gv))) * __builtin_bit_cast(_Float16, (uint16_t)(uw >> (16 * k)));
-    }
-    return (u32)__builtin_bit_cast(uint16_t, hh[0]) | ((u32)__builtin_bit_cast(uint16_t, hh[1]) << 16);
-}
-
 
 // Work unit ("step") = 16 rows x one 1024-weight chunk x all planes = one A tile of BITS * 2 KiB; an item = cpi
 // consecutive chunks of a row group, accumulated in registers by one wave.  Every wave streams its own tiles
@@ -496,12 +353,6 @@ __device__ __forceinline__ u32 silu_mul2(u32 gw, u32 uw) {
 // Items: i < L (= W - E late waves) -> the first item of late wave E + i; i >= L -> wave (i - L) mod W.
 #ifndef PL_WPE
 #define PL_WPE 4
-#endif
-#ifndef PL_BOOB
-#define PL_BOOB 1
-#endif
-#ifndef PL_LOOB
-#define PL_LOOB 1
 #endif
 // local-image kernel: activations before tiles in the memory queue (0: round-2 order -- tiles requested at once, the wait counts them;
 // 1: tiles only when the activations have landed; 2: the later half of the waves also builds its image first).  Per bit width: at 2
@@ -561,7 +412,7 @@ __global__ void __launch_bounds__(pl_threads<BITS>(), BITS == 2 ? PL_WPE : (pl_t
     // image stride: + 64 B between the rows' images, so that the MFMA lanes of a ds_read_b128 group -- columns of different
     // rows at the same piece / unit -- fall into different banks (units {0,8,2,10} + 4 mm of the 16 per bank row)
     const u32 IMGS = G.nchunks * 4096u + (MBT > 1 ? 64u : 0u);
-    unsigned char *zero32 = bimg + MBA * IMGS;
+    unsigned char *zero32 = bimg + MBA * IMGS;  // (64 zero bytes no reader is left for -- the idle columns read outside the allocation, see the main loop; kept: every offset behind it)
     float *red = reinterpret_cast<float *>(zero32 + 64);  // 64 floats per batch row (statistics, sums, scale); the counters in row 0's
     u32 *ctr = reinterpret_cast<u32 *>(red + 60);  // 0, 1, 3: software barriers; 2: extracted elements
     HotEnt *hotl = reinterpret_cast<HotEnt *>(red + 64u * MBA);
@@ -590,12 +441,12 @@ __global__ void __launch_bounds__(pl_threads<BITS>(), BITS == 2 ? PL_WPE : (pl_t
     const u32 pt = l & 31u, pb = ((w & 1u) << 1) | (l >> 5);  // the same for every pass (E * 64 is a multiple of 128)
     stamp2(5);
     if (early) {
-        const u32x4 rsx = make_rsrc(a.x + (size_t)m * a.x_ld, (PRO == PRO_SILUMUL ? 4u : 2u) * G.K);
-        const u32x4 rsa = make_rsrc(PRO == PRO_RMSNORM ? a.normw : a.x, 2u * G.K);
+        const u32x4 rsx = make_rsrc4(a.x + (size_t)m * a.x_ld, (PRO == PRO_SILUMUL ? 4u : 2u) * G.K);
+        const u32x4 rsa = make_rsrc4(PRO == PRO_RMSNORM ? a.normw : a.x, 2u * G.K);
         if (rawx) {
 #pragma unroll
             for (u32 mm = 0; mm < (u32)MBT; mm++) {  // (every row's loads are in flight before the first one is used)
-                const u32x4 rsm = MBT == 1 ? rsx : make_rsrc(a.x + (size_t)(m + mm) * a.x_ld, mm < MB ? 2u * G.K : 0u);
+                const u32x4 rsm = MBT == 1 ? rsx : make_rsrc4(a.x + (size_t)(m + mm) * a.x_ld, mm < MB ? 2u * G.K : 0u);
 #pragma unroll
                 for (u32 n = 0; n < (u32)NI; n++) {
                     const u32 idx = tid + n * (E * 64u);  // 16-byte unit of the vector
@@ -651,7 +502,7 @@ __global__ void __launch_bounds__(pl_threads<BITS>(), BITS == 2 ? PL_WPE : (pl_t
     auto item_after = [&](u32 item) { return item < L ? L + w : item + W; };  // the wave's next item
     const u32 item0 = first_late ? w - E : L + w;
     const u32 plane_bytes = a.N * a.wpr_ld * 4u;
-    const u32x4 rq = make_rsrc(a.qw, plane_bytes * (u32)BITS);
+    const u32x4 rq = make_rsrc4(a.qw, plane_bytes * (u32)BITS);
     const u32 ring_lds = (u32)(uintptr_t)ring;
     // Per-lane part of a tile address is constant (atile_src); the tile part is wave-uniform and goes into the
     // scalar offset.  No per-lane validity: rows >= N and the words of a short tail chunk beyond the row fetch
@@ -678,7 +529,7 @@ __global__ void __launch_bounds__(pl_threads<BITS>(), BITS == 2 ? PL_WPE : (pl_t
 #pragma unroll
         for (u32 p = 0; p < (u32)BITS; p++)
 #pragma unroll
-            for (u32 h = 0; h < 2; h++) dma16s(rq, slot_lds + (p * 2u + h) * 1024u, lane_off[h], tile_off + p * plane_bytes);
+            for (u32 h = 0; h < 2; h++) dma16<true>(rq, slot_lds + (p * 2u + h) * 1024u, lane_off[h], tile_off + p * plane_bytes);
         if (++iq_c == cpi) {
             iq_c = 0;
             iq_item = item_after(iq_item);
@@ -695,10 +546,10 @@ __global__ void __launch_bounds__(pl_threads<BITS>(), BITS == 2 ? PL_WPE : (pl_t
         // late wave: first item now (this may block in the issue queue: nothing else to do before the image is built)
         while (iq_n < my_steps && iq_n < S && (!PL_XF(256u) || iq_n < cpi * first_late)) issue();
         if (nlut) {
-            const u32x4 rl = make_rsrc(a.lut, a.N * (u32)NP * 2u);
+            const u32x4 rl = make_rsrc4(a.lut, a.N * (u32)NP * 2u);
             const u32 want = a.RGB * 16u * (u32)NP * 2u;
             for (u32 o = 0; o < lut_bytes; o += 1024u)
-                dma16(rl, (u32)(uintptr_t)lutb + o, o + 16u * l < want ? rg0 * 16u * (u32)NP * 2u + o + 16u * l : OOB);
+                dma16<true>(rl, (u32)(uintptr_t)lutb + o, o + 16u * l < want ? rg0 * 16u * (u32)NP * 2u + o + 16u * l : OOB);
             lut_after = nlut;
         }
     }
@@ -746,7 +597,7 @@ __global__ void __launch_bounds__(pl_threads<BITS>(), BITS == 2 ? PL_WPE : (pl_t
                 mine = fmaxf(mine, fmaxf(p, q));
             }
         }
-        s1 = wave_reduce<false>(s1);
+        s1 = wave_reduce_l63<false>(s1);
         const float sum1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, s1), 63));
         const float cnt = (float)((G.K + ND - 1u) / ND);  // (>= the sample size: a lower threshold, the bound on the count stands)
         const float tau_raw = GQ_HOT_T * 1.01f * sum1 * __builtin_amdgcn_rcpf(cnt);
@@ -852,8 +703,8 @@ __global__ void __launch_bounds__(pl_threads<BITS>(), BITS == 2 ? PL_WPE : (pl_t
             }
         }
         float mx = PRO == PRO_RMSNORM ? mxf : h2f(max(mxp[0], mxp[1]));
-        mx = wave_reduce<true>(mx);
-        if constexpr (PRO == PRO_RMSNORM) ss = wave_reduce<false>(ss);
+        mx = wave_reduce_l63<true>(mx);
+        if constexpr (PRO == PRO_RMSNORM) ss = wave_reduce_l63<false>(ss);
         if (l == 63) {
             redm[w] = mx;
             if constexpr (PRO == PRO_RMSNORM) redm[16 + w] = ss;
@@ -941,7 +792,7 @@ __global__ void __launch_bounds__(pl_threads<BITS>(), BITS == 2 ? PL_WPE : (pl_t
                 *reinterpret_cast<u32 *>(img + p * 128u + ((32u * g) ^ bimg_swz(p)) + 4u) = __builtin_amdgcn_perm(P[p][0], P[p][1], 0x07050301u);
             }
         }
-        xsum = wave_reduce<false>(xsum);
+        xsum = wave_reduce_l63<false>(xsum);
         if (l == 63) {
             redm[32 + w] = xsum;
             if (w == 0) redm[48] = __builtin_bit_cast(float, (u32)(127 - ksh));  // E8M0 scale of every B block, for the late waves
@@ -1010,18 +861,13 @@ __global__ void __launch_bounds__(pl_threads<BITS>(), BITS == 2 ? PL_WPE : (pl_t
         if (chunk < G.nchunks && !PL_XF(1u)) {
             // MFMA columns without a piece (col >= 4 MB) must read zeros (measured: with real data in them -- the same addresses as
             // columns 0..3, an LDS broadcast -- w1w3 runs 10.7 instead of 9.8 us: the matrix cores draw more power on non-zero
-            // operands and the chip clocks down).  PL_BOOB: their base address lies outside the workgroup's LDS allocation (192 KiB
+            // operands and the chip clocks down).  Their base address lies outside the workgroup's LDS allocation (192 KiB
             // and up; this chip has 160 KiB), where ds_read returns zeros (tools/ubench/lds_oob.hip) -- so the (b, h) block and k + 64
             // distances are immediates of the ds_reads for EVERY lane instead of per-lane address arithmetic (1.1 instructions per
-            // MFMA less in a loop that issues more than the SIMD hides).  PL_BOOB = 0: a 64-byte zero area and per-lane strides 0.
-#if PL_BOOB
+            // MFMA less in a loop that issues more than the SIMD hides; the arm that read a 64-byte zero area with per-lane strides 0
+            // instead: DESIGN.md section 3.7).
             const unsigned char *bbase = bcol ? bimg + mcol * IMGS + bimg4_off(chunk, 0u, 0u, col & 3u) + ((16u * kb) ^ bimg_swz(col & 3u)) : smem + 0x30000u;
-            mfma_chunk<BITS>(acc, Wd, bbase, 512u, 64u, sb);
-#else
-            const unsigned char *bbase = bcol ? bimg + mcol * IMGS + bimg4_off(chunk, 0u, 0u, col & 3u) + ((16u * kb) ^ bimg_swz(col & 3u)) : zero32;
-            // next (b, h): 4 pieces * 128 B; second run of the lane at k + 64
-            mfma_chunk<BITS>(acc, Wd, bbase, bcol ? 512u : 0u, bcol ? 64u : 0u, sb);
-#endif
+            mfma_chunk<BITS>(acc, Wd, bbase, 512u, 64u, sb);  // next (b, h): 4 pieces * 128 B; second run of the lane at k + 64
             if (!(HOT_ABL & 4) && __builtin_expect(nhot != 0u, 0)) hot_step<BITS>(acc, Wd, hotl, nhot, chunk, sb, col, kb);
         } else if PL_XF(1u) {
             acc[0][0] += __builtin_bit_cast(float, Wd[0][0] ^ Wd[BITS - 1][7]);
@@ -1114,7 +960,7 @@ __global__ void __launch_bounds__(BITS == 2 ? 1024 : 512) ap_plane_local_kernel(
     // ---- 0. this wave's activations (16-byte units u = l, l + 64 of each chunk), then all of its tiles
     u32x4 xv[NC][2], gv[NC][2];
     {
-        const u32x4 rsx = make_rsrc(a.x + (size_t)m * a.x_ld, (PRO == PRO_SILUMUL ? 4u : 2u) * G.K);
+        const u32x4 rsx = make_rsrc4(a.x + (size_t)m * a.x_ld, (PRO == PRO_SILUMUL ? 4u : 2u) * G.K);
 #pragma unroll
         for (u32 n = 0; n < (u32)NC; n++) {
             const u32 chunk = chunk0 + n;
@@ -1130,7 +976,7 @@ __global__ void __launch_bounds__(BITS == 2 ? 1024 : 512) ap_plane_local_kernel(
         }
     }
     const u32 plane_bytes = a.N * a.wpr_ld * 4u;
-    const u32x4 rq = make_rsrc(a.qw, plane_bytes * (u32)BITS);
+    const u32x4 rq = make_rsrc4(a.qw, plane_bytes * (u32)BITS);
     const u32 ring_lds = (u32)(uintptr_t)ring;
     u32 lane_off[2];
     {
@@ -1149,7 +995,7 @@ __global__ void __launch_bounds__(BITS == 2 ? 1024 : 512) ap_plane_local_kernel(
 #pragma unroll
         for (u32 p = 0; p < (u32)BITS; p++)
 #pragma unroll
-            for (u32 h = 0; h < 2; h++) dma16s(rq, slot_lds + (p * 2u + h) * 1024u, lane_off[h], tile_off + p * plane_bytes);
+            for (u32 h = 0; h < 2; h++) dma16<true>(rq, slot_lds + (p * 2u + h) * 1024u, lane_off[h], tile_off + p * plane_bytes);
         if (++iq_c == cpi) {
             iq_c = 0;
             iq_item += W;
@@ -1169,10 +1015,10 @@ __global__ void __launch_bounds__(BITS == 2 ? 1024 : 512) ap_plane_local_kernel(
         // LUT rows of the block: pseudo steps of exactly LPS loads in the queue of the last wave (see the kernel above)
         nlut = w == W - 1u ? lut_bytes / (LPS * 1024u) : 0u;
         if (nlut) {
-            const u32x4 rl = make_rsrc(a.lut, a.N * (u32)NP * 2u);
+            const u32x4 rl = make_rsrc4(a.lut, a.N * (u32)NP * 2u);
             const u32 want = a.RGB * 16u * (u32)NP * 2u;
             for (u32 o = 0; o < lut_bytes; o += 1024u)
-                dma16(rl, (u32)(uintptr_t)lutb + o, o + 16u * l < want ? rg0 * 16u * (u32)NP * 2u + o + 16u * l : OOB);
+                dma16<true>(rl, (u32)(uintptr_t)lutb + o, o + 16u * l < want ? rg0 * 16u * (u32)NP * 2u + o + 16u * l : OOB);
         }
         lut_from = iq_n, lut_after = nlut;
     };
@@ -1207,8 +1053,8 @@ __global__ void __launch_bounds__(BITS == 2 ? 1024 : 512) ap_plane_local_kernel(
                 }
             }
         const u32 mxi = max(mxp[0], mxp[1]);
-        const float mx = wave_reduce<true>(h2f((uint16_t)mxi));
-        s2 = wave_reduce<false>(s2);
+        const float mx = wave_reduce_l63<true>(h2f((uint16_t)mxi));
+        s2 = wave_reduce_l63<false>(s2);
         const float xmax = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mx), 63));
         const float tot2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, s2), 63));
         const u32 tau = hot_tau_bits(tot2, (float)(NC * 1024u));
@@ -1300,7 +1146,7 @@ __global__ void __launch_bounds__(BITS == 2 ? 1024 : 512) ap_plane_local_kernel(
                 if (t >= tp) reinterpret_cast<u32 *>(img + n * 4096u)[o] = 0u;
             }
         }
-        xsum = wave_reduce<false>(xsum);
+        xsum = wave_reduce_l63<false>(xsum);
         if (l == 63) red[32 + w] = w < CS ? xsum : 0.f;  // sum(x): every chunk range counted once
         if (__builtin_expect(any_hot, 0)) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1318,13 +1164,9 @@ __global__ void __launch_bounds__(BITS == 2 ? 1024 : 512) ap_plane_local_kernel(
     // ---- 2. the steps of this wave
     const u32 r = l & 15u, kb = l >> 4, col = l & 15u;
     const u32 offA0 = atile_unit(r, 2u * kb) * 16u, offA1 = atile_unit(r, 2u * kb + 1u) * 16u;
-    // columns 4..15 carry no piece: zeros from outside the LDS allocation (PL_BOOB, see the shared-image kernel; their sums are
-    // never read, but non-zero operands cost power and with it clock) -- PL_LOOB = 0: they repeat columns 0..3
-#if PL_LOOB
+    // columns 4..15 carry no piece: zeros from outside the LDS allocation (see the shared-image kernel; their sums are never read,
+    // but non-zero operands cost power and with it clock)
     const unsigned char *blane = col < 4u ? img + ((col & 3u) << 7) + ((16u * kb) ^ bimg_swz(col & 3u)) : smem + 0x30000u;
-#else
-    const unsigned char *blane = img + ((col & 3u) << 7) + ((16u * kb) ^ bimg_swz(col & 3u));
-#endif
     v4f acc[NP1];
 #pragma unroll
     for (int i = 0; i < NP1; i++) acc[i] = (v4f){0.f, 0.f, 0.f, 0.f};
@@ -1370,13 +1212,11 @@ struct PlaneCfg {
     size_t smem;
 };
 
-int cus() { return gq_cu_count(); }
-
 bool pick_plane_cfg(u32 N, u32 K, int bits, PlaneCfg &c, u32 MB = 1u) {
     if (K % 256u || K > 16384u) return false;
     const u32 nchunks = K / 1024u + ((K % 1024u) ? 1u : 0u);
     const u32 RGt = (N + 15u) / 16u;
-    const u32 ncu = (u32)cus();
+    const u32 ncu = (u32)gq_cu_count();
     const u32 W = bits == 2 ? 16u : (bits == 3 ? (u32)PL_T3 / 64u : 8u);
     c.T = 64u * W;
     // one block per CU when the matrix is big enough
@@ -1425,7 +1265,7 @@ bool pick_local_cfg(u32 N, u32 K, int bits, PlaneCfg &c) {
     // stays on the exact kernel: the dispatcher's threshold, ap_dispatch.hip.  profiles/r05_knob_sweep.txt)
     if (K % 256u || bits > gq_env_int("GQ_PL_LOCAL_MAXBITS", 4)) return false;
     const u32 nchunks = K / 1024u + ((K % 1024u) ? 1u : 0u);
-    const u32 RGt = (N + 15u) / 16u, ncu = (u32)cus(), W = bits == 2 ? 16u : 8u;
+    const u32 RGt = (N + 15u) / 16u, ncu = (u32)gq_cu_count(), W = bits == 2 ? 16u : 8u;
     c.T = 64u * W;
     c.RGB = (RGt + ncu - 1u) / ncu;
     if (c.RGB < 1) c.RGB = 1;

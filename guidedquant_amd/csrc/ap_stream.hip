@@ -1,6 +1,7 @@
 // ap_stream.hip -- "stream" form of the plane-MFMA Any-Precision GEMV (fast mode, one batch row) for gfx950.
 //
-// Same arithmetic as ap_plane.hip (plane_core.h: a b-bit LUT is multilinear in the code bits, so y is 2^b - 1 BINARY GEMVs over
+// Same arithmetic as ap_plane.hip, through the same device pieces: plane_mfma.h, and wave_util.h for the reductions and the
+// hand-issued plane loads (plane_core.h: a b-bit LUT is multilinear in the code bits, so y is 2^b - 1 BINARY GEMVs over
 // the stored bit-planes; FP4 single-bit A operands built with one v_and per 8 weights, the activations as 4 exact bf8 pieces in
 // 4 MFMA columns, fp32 accumulation) -- replaces anyprec.cu:372-542 for M = 1.  What is different is where the bytes go
 // (round 4; measured reasons in DESIGN.md section 3.5):
@@ -22,19 +23,13 @@
 
 #include "ap_dispatch.h"
 #include "attn_core.h"
-#include "plane_core.h"
+#include "plane_mfma.h"
 
 using namespace gqp;
+using namespace gqw;  // (wave_util.h: casts, vector types, wave_reduce_l63 / row_sum, descriptors, the asm vector-memory requests)
 
 namespace {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-typedef u32 u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef uint16_t us2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) u32 lds_u32;
 
 struct StreamArgs {
@@ -69,53 +64,7 @@ struct StreamArgs {
 constexpr u32 HOTCAP = 8u;  // Markov: |x| > 64 mean|x| holds for fewer than 512 / 64 elements of a unit
 constexpr u32 OOB = 0x80000000u;
 
-__device__ __forceinline__ float h2f(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-__device__ __forceinline__ h2v u2h2(u32 u) { return __builtin_bit_cast(h2v, u); }
-__device__ __forceinline__ u32 h22u(h2v h) { return __builtin_bit_cast(u32, h); }
-
-// wave64 reductions on the DPP path: result valid in lane 63
-template <bool MAX>
-__device__ __forceinline__ float wave_reduce(float v) {
-    auto step = [&](auto dpp) {
-        float o = __builtin_bit_cast(float, dpp(__builtin_bit_cast(int, v)));
-        v = MAX ? fmaxf(v, o) : v + o;
-    };
-    step([](int x) { return __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false); });   // quad_perm [1,0,3,2]
-    step([](int x) { return __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false); });   // quad_perm [2,3,0,1]
-    step([](int x) { return __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false); });  // row_half_mirror
-    step([](int x) { return __builtin_amdgcn_update_dpp(x, x, 0x140, 0xF, 0xF, false); });  // row_mirror
-    {   // row_bcast15 into rows 1 and 3, row_bcast31 into rows 2 and 3 (|x| >= 0 and the sum identity are both 0.0f)
-        float o = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, false));
-        v = MAX ? fmaxf(v, o) : v + o;
-        o = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xC, 0xF, false));
-        v = MAX ? fmaxf(v, o) : v + o;
-    }
-    return v;
-}
-__device__ __forceinline__ float lane63(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63)); }
-
-// A = FP4 (4 registers; the upper half of the builtin's vector is ignored for cbsz = 4), B = BF8.  Through the builtin: the
-// compiler must see the instruction to insert the MFMA hazard wait states.
-__device__ __forceinline__ void mfma_f4_bf8(v4f &acc, v4i a, v8i b, int scale_a, int scale_b) {
-    const v8i a8 = __builtin_shufflevector(a, a, 0, 1, 2, 3, -1, -1, -1, -1);
-    acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8, b, acc, 4, 1, 0, scale_a, 0, scale_b);
-}
-
-// F.silu(gate) * up on two packed fp16 pairs -- inference/model.py:266
-__device__ __forceinline__ u32 silu_mul2(u32 gw, u32 uw) {
-    _Float16 hh[2];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const float gv = h2f((uint16_t)(gw >> (16 * k)));
-        hh[k] = (_Float16)(gv / (1.0f + __expf(-gv))) * __builtin_bit_cast(_Float16, (uint16_t)(uw >> (16 * k)));
-    }
-    return (u32)__builtin_bit_cast(uint16_t, hh[0]) | ((u32)__builtin_bit_cast(uint16_t, hh[1]) << 16);
-}
-
-struct HotEnt {
-    u32 key, pieces;  // key = b << 7 | k (logical k of the unit's (b) block), pieces: byte p = bf8 piece p of x * 2^ksh
-};
-#define GQ_ST_HOT_T 64.0f
+// (mfma_f4_bf8, silu_mul2, HotEnt -- here key = b << 7 | k, the logical k of the unit's (b) block -- and GQ_HOT_T: plane_mfma.h)
 
 // LDS flags / counters through explicit LDS pointers (a generic pointer becomes a FLAT access whose vmcnt(0) drains the
 // wave's plane loads) and without fences: the LDS serves one wave's operations in order, so a flag written behind the data
@@ -133,47 +82,14 @@ __device__ __forceinline__ void lds_wait_ge(const u32 *p, u32 target) {
     while (lds_load(p) < target) __builtin_amdgcn_s_sleep(1);
 }
 
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void *p, u32 bytes) {  // raw buffer: stride 0, num_records = bytes
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), (short)0, (int)bytes, 0x00020000);
-}
-#ifndef ST_AUX
-#define ST_AUX 2  // cache policy of the plane loads: 2 = nt (streamed once)
-#endif
+// 16 bytes per lane through the compiler's builtin (its waitcnt pass counts these: the activations and the probe loads of the prologue)
 template <int AUX>
 __device__ __forceinline__ u32x4 bload128(rsrc_t rsrc, u32 voff, u32 soff) {
     return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, (int)soff, AUX));
 }
 
-// The plane words are requested from inline asm and waited for with explicit s_waitcnt vmcnt(n) (vector memory returns in
-// order): the compiler's own counting gives up at the loop's control-flow joins and drains the queue (vmcnt(0)) before every
-// unit, which serialises the memory latency with the MFMAs.  The destination is an in-out operand of the request (an output
-// of its own may be copied by the compiler before the data lands) and is tied again behind the wait.
-__device__ __forceinline__ u32x4 make_rsrc4(const void *p, u32 bytes) {
-    const uint64_t a = (uint64_t)(uintptr_t)p;
-    return (u32x4){(u32)a, (u32)(a >> 32) & 0xFFFFu, bytes, 0x00020000u};
-}
-__device__ __forceinline__ void aload128(u32x4 &dst, u32x4 rsrc, u32 voff, u32 soff) {
-#if ST_AUX == 2
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen nt" : "+v"(dst) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-#else
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "+v"(dst) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-#endif
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// wait until at most n * LPU plane loads of this wave are outstanding (n wave-uniform)
-template <int LPU>
-__device__ __forceinline__ void wait_vm_units(u32 n) {
-    switch (n) {
-        case 0: wait_vm<0>(); break;
-        case 1: wait_vm<LPU>(); break;
-        case 2: wait_vm<2 * LPU>(); break;
-        default: wait_vm<3 * LPU>(); break;
-    }
-}
+// (The plane words are requested from inline asm -- aload128<true>: nt, streamed once -- into in-out register slots and waited for
+// with wait_vm_units: wave_util.h "hand-issued vector memory".)
 
 // The MFMAs of one (unit half hh, nibble bit NB) block: FP4 operands of the plane subsets built on the fly (the mask commutes
 // with AND; depth-first over the subset lattice).  Plane p holds code bit BITS-1-p; subset index cm = OR of the code bits.
@@ -258,22 +174,6 @@ __device__ __forceinline__ void hot_unit(v4f (&acc)[(1 << BITS) - 1], const u32x
     }
 }
 
-// 16-lane (DPP row) butterflies: every lane of the row ends up with the row's result -- no row_bcast steps, no readlane
-__device__ __forceinline__ float row_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));
-    return v;
-}
-__device__ __forceinline__ u32 row_max(u32 v) {
-    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false));
-    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false));
-    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false));
-    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false));
-    return v;
-}
-
 // Geometry.  A 1024-weight chunk of a row is 32 plane words t; bit 8 (3 - c) + (7 - j) of word t is the weight of activation
 // 1024 chunk + 256 c + 8 t + j (plane_core.h).  Unit q = (chunk, hh) = q >> 1, q & 1: words t = 16 hh + tt, tt = 0..15 -- 64
 // bytes of every row and plane, 512 activations (4 runs of 128).
@@ -292,9 +192,6 @@ constexpr u32 META_W = 16u;
 #ifndef ST_XFLAGS
 #define ST_XFLAGS 0  // build-time experiments: 1 no MFMA work, 2 no plane loads
 #endif
-#ifndef ST_MAINPRIO
-#define ST_MAINPRIO 0
-#endif
 #ifndef ST_W2
 #define ST_W2 16  // waves per block at 2 bits
 #endif
@@ -306,15 +203,6 @@ constexpr u32 META_W = 16u;
 #endif
 #ifndef ST_KO
 #define ST_KO 0   // build-time knock-outs, WRONG numerics, timing only (bit mask): 1 no sum-of-squares exchange, 8 no image reads, 16 the activations arrive as 4 fp32 partial vectors (loads only)
-#endif
-#ifndef ST_DPPIMG
-#define ST_DPPIMG 0  // 1: consumers read their unit image with two dense ds_read_b128 and spread it over the piece lanes by DPP instead of
-                     // eight reads that only the 16 piece lanes take part in -- correct (GPU suite green) and SLOWER: wqkv 5.80 vs 5.65 us, decode 904
-                     // vs 911 tokens/s (profiles/r05_stream_phase_variants.txt): the masked reads are not what the image phase waits for
-#endif
-#ifndef ST_TAU_SCALE
-#define ST_TAU_SCALE 1  // a unit's power of two from its extraction threshold (what stays in the image is <= tau) instead of its maximum:
-                        // one wave-wide reduction less per unit; the extracted elements take their own power of two (round 5)
 #endif
 #ifndef ST_NH
 #define ST_NH 1   // unit halves per consumer unit: 1 = a wave multiplies half chunks (32 image registers), 2 = whole chunks (64)
@@ -430,7 +318,7 @@ __device__ __forceinline__ void ap_stream_body(const StreamArgs &a) {
                 ss += __builtin_bit_cast(float, t);
             }
         }
-        ss = wave_reduce<false>(ss);
+        ss = wave_reduce_l63<false>(ss);
         if (l == 63u) lds_store(reinterpret_cast<u32 *>(red), __builtin_bit_cast(u32, 1.0f / sqrtf(ss / (float)a.Kx + a.eps)));
     }
     if (is_pro) {
@@ -503,7 +391,7 @@ __device__ __forceinline__ void ap_stream_body(const StreamArgs &a) {
 #pragma unroll
         for (u32 hh = 0; hh < (u32)NH; hh++)
 #pragma unroll
-            for (u32 p = 0; p < (u32)BITS; p++) aload128(Ar[s][hh][p], rq, lane_off, soff + 64u * hh + p * plane_bytes);
+            for (u32 p = 0; p < (u32)BITS; p++) aload128<true>(Ar[s][hh][p], rq, lane_off, soff + 64u * hh + p * plane_bytes);
         i_rg += 1u << lrs;
         if (++i_ri == nrg) i_ri = 0, i_rg = rgs, i_q += W;
         iu++;
@@ -554,7 +442,7 @@ __device__ __forceinline__ void ap_stream_body(const StreamArgs &a) {
 #pragma unroll
                 for (int k = 0; k < 4; k++)  // (requests outside the vector returned zeros)
                     ss = __builtin_amdgcn_fdot2(u2h2(xv[n][k]), u2h2(xv[n][k]), ss, false);
-            ss = wave_reduce<false>(ss);
+            ss = wave_reduce_l63<false>(ss);
 #if ST_KO & 1
             nscale = 1.0f / sqrtf(lane63(ss) * (float)npw / (float)a.K + a.eps);
 #else
@@ -604,36 +492,31 @@ __device__ __forceinline__ void ap_stream_body(const StreamArgs &a) {
             // soon as the blocks of a unit differed -- the scale operand does not act per 32-element block the way that assumed),
             // mean magnitude -> extraction threshold; per DPP row the sum for the coef[0] term
             const u32 mxl = max((u32)mxp[0], (u32)mxp[1]);
-            const float tot1 = lane63(wave_reduce<false>(s1));
-            xsum = row_sum(xsum);
+            const float tot1 = lane63(wave_reduce_l63<false>(s1));
+            xsum = row_sum<16>(xsum);
             // threshold of the extraction as an fp16 bit pattern (rounded up): 64 x the unit's mean magnitude, + 1 % for the roundings
             u32 tau = 0x7C00u;
             {
-                const float tf = GQ_ST_HOT_T * 1.01f * tot1 * (1.0f / 512.0f);
+                const float tf = GQ_HOT_T * 1.01f * tot1 * (1.0f / 512.0f);
                 if (tf < 65000.f) tau = (u32)__builtin_bit_cast(uint16_t, (_Float16)tf) + 1u;
             }
-#if ST_TAU_SCALE
-            // what stays in the image is <= tau: the unit's power of two from the threshold, no maximum over the wave (a unit whose
-            // threshold is not finite -- mean magnitude above 1000 -- takes its maximum)
+            // what stays in the image is <= tau: the unit's power of two from the threshold, no maximum over the wave -- one wave-wide
+            // reduction less per unit than taking it from the unit's maximum; a unit whose threshold is not
+            // finite -- mean magnitude above 1000 -- takes its maximum
             float xmax = h2f((uint16_t)tau);
-            if (__builtin_expect(tau >= 0x7C00u, 0)) xmax = lane63(wave_reduce<true>(h2f((uint16_t)mxl)));
+            if (__builtin_expect(tau >= 0x7C00u, 0)) xmax = lane63(wave_reduce_l63<true>(h2f((uint16_t)mxl)));
             if (tot1 == 0.f) xmax = 0.f;
-#else
-            const float xmax = lane63(wave_reduce<true>(h2f((uint16_t)mxl)));
-#endif
             stamp2(4);
             // x * 2^k with max|x| * 2^k in [2^14, 2^15) (plane_core.h piece_shift): k + 15 = 44 - (biased fp16 exponent of the maximum)
             const u32 ke = (u32)(piece_shift(xmax) + 15);
             const u32 k16 = ke << 10;  // fp16 bits of 2^k
             HotEnt *hl = hotl + (size_t)q * HOTCAP;
             u32 nh = 0;
-            u32 k16h = k16, keh = ke;  // the extracted elements' own power of two (ST_TAU_SCALE: the image's comes from the threshold)
+            u32 k16h = k16, keh = ke;  // the extracted elements' own power of two (the image's comes from the threshold)
             if (__builtin_expect(__builtin_amdgcn_ballot_w64(mxl > tau) != 0ull, 0)) {
                 // rare: the lane's elements above the threshold leave the image (ascending lane order: deterministic list)
-#if ST_TAU_SCALE
-                keh = (u32)(piece_shift(lane63(wave_reduce<true>(h2f((uint16_t)mxl)))) + 15);
+                keh = (u32)(piece_shift(lane63(wave_reduce_l63<true>(h2f((uint16_t)mxl)))) + 15);
                 k16h = keh << 10;
-#endif
 #pragma unroll
                 for (u32 k = 0; k < 4; k++)
 #pragma unroll
@@ -683,21 +566,11 @@ __device__ __forceinline__ void ap_stream_body(const StreamArgs &a) {
                 const u32 v01 = __builtin_amdgcn_perm(P[p][1], P[p][3], 0x05010703u);
                 // b = 2: j = 5, 1 (byte 3 of words 2, 0); b = 3: j = 4, 0 (byte 1 of words 2, 0)
                 const u32 v23 = __builtin_amdgcn_perm(P[p][0], P[p][2], 0x05010703u);
-#if ST_DPPIMG
-                // (dense-read layout: row c = 4 b + p keeps byte k at k ^ 16 (c / 2) = k ^ (32 b + 16 (p / 2)) -- see the consumers' read)
-                unsigned char *d = dst + p * 128u;
-                const u32 kx = k0 ^ (16u * (p >> 1));
-                *reinterpret_cast<uint16_t *>(d + kx) = (uint16_t)v01;
-                *reinterpret_cast<uint16_t *>(d + 512u + (kx ^ 32u)) = (uint16_t)(v01 >> 16);
-                *reinterpret_cast<uint16_t *>(d + 1024u + (kx ^ 64u)) = (uint16_t)v23;
-                *reinterpret_cast<uint16_t *>(d + 1536u + (kx ^ 96u)) = (uint16_t)(v23 >> 16);
-#else
                 unsigned char *d = dst + p * 128u + (k0 ^ bimg_swz(p));
                 *reinterpret_cast<uint16_t *>(d) = (uint16_t)v01;
                 *reinterpret_cast<uint16_t *>(d + 512u) = (uint16_t)(v01 >> 16);
                 *reinterpret_cast<uint16_t *>(d + 1024u) = (uint16_t)v23;
                 *reinterpret_cast<uint16_t *>(d + 1536u) = (uint16_t)(v23 >> 16);
-#endif
             }
             // sum(x) as a pseudo partial sum [unit][piece column = g][16 rows]: the epilogue lanes of the coef[0] term run the
             // same loads and additions as the others (no divergent branch on the tail of the kernel)
@@ -749,15 +622,8 @@ __device__ __forceinline__ void ap_stream_body(const StreamArgs &a) {
     // ---------------------------------------------------------------- 2. the units of this wave
     // Instruction issue is arbitrated by priority, then age: left alone the oldest wave of a SIMD runs ahead and the youngest is left
     // to multiply its units alone at the end, at the single-wave rate (tools/ubench/mfma_mix.hip: 19.6 ns per MFMA against 15.2 ns
-    // with four waves interleaving) -- ST_MAINPRIO: the later a wave started, the higher its priority in the main loop
-#if ST_MAINPRIO == 1
-    __builtin_amdgcn_s_setprio(0);
-    if (w >= 3u * W / 4u) __builtin_amdgcn_s_setprio(3);
-    else if (w >= W / 2u) __builtin_amdgcn_s_setprio(2);
-    else if (w >= W / 4u) __builtin_amdgcn_s_setprio(1);
-#elif ST_MAINPRIO == 2
-    if (w >= W / 2u) __builtin_amdgcn_s_setprio(1);
-#endif
+    // with four waves interleaving).  Raising the priority of the later waves in the main loop was tried and dropped (DESIGN.md
+    // section 3.7).
     const u32 col = l & 15u, kb = l >> 4;
     v8i Bv[NH][4];
     int sb[NH];
@@ -782,27 +648,6 @@ __device__ __forceinline__ void ap_stream_body(const StreamArgs &a) {
                 } while (fl[0] == 0u);
                 nhot[hh] = __builtin_amdgcn_readfirstlane(fl[1]);
                 sb[hh] = (int)meta[META_W * q + 2u];
-#if ST_DPPIMG
-                // Round 5 experiment: the image comes in with TWO dense reads (every lane 16 bytes: lane (row kb, column c = 4 b + p)
-                // takes the units kb and kb + 4 of image row c) instead of eight reads that only the 16 piece lanes take part in.  The
-                // piece lanes (columns 0..3 of each DPP row) then pull the rows of the other nibble bits from the lanes 4 b to
-                // their right (row_shl, bank mask 1: the other lanes keep the zero they start from -- the idle MFMA columns stay
-                // zero without a read).  Image row c keeps its unit u at u ^ (c / 2): the 16 lanes of a DPP row hit 16 different
-                // 16-byte bank groups.
-                {
-                    const unsigned char *src = img + (size_t)q * 2048u + col * 128u;
-                    const u32 u0x = (kb ^ (col >> 1)) << 4, u1x = ((kb + 4u) ^ (col >> 1)) << 4;
-                    const uint4 r0 = *reinterpret_cast<const uint4 *>(src + u0x), r1 = *reinterpret_cast<const uint4 *>(src + u1x);
-                    const int raw[8] = {(int)r0.x, (int)r0.y, (int)r0.z, (int)r0.w, (int)r1.x, (int)r1.y, (int)r1.z, (int)r1.w};
-#pragma unroll
-                    for (int j = 0; j < 8; j++) {
-                        Bv[hh][0][j] = __builtin_amdgcn_update_dpp(0, raw[j], 0xE4, 0xF, 0x1, false);   // quad_perm [0,1,2,3]: own lane
-                        Bv[hh][1][j] = __builtin_amdgcn_update_dpp(0, raw[j], 0x104, 0xF, 0x1, false);  // row_shl:4
-                        Bv[hh][2][j] = __builtin_amdgcn_update_dpp(0, raw[j], 0x108, 0xF, 0x1, false);  // row_shl:8
-                        Bv[hh][3][j] = __builtin_amdgcn_update_dpp(0, raw[j], 0x10C, 0xF, 0x1, false);  // row_shl:12
-                    }
-                }
-#else
                 const unsigned char *src = img + (size_t)q * 2048u + (col & 3u) * 128u + ((16u * kb) ^ bimg_swz(col & 3u));
 #pragma unroll
                 for (u32 b = 0; b < 4; b++) {
@@ -813,7 +658,6 @@ __device__ __forceinline__ void ap_stream_body(const StreamArgs &a) {
                     }
                     Bv[hh][b] = (v8i){(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, (int)b1.x, (int)b1.y, (int)b1.z, (int)b1.w};
                 }
-#endif
             }
             if (!stamped) stamp(2), stamped = true;
         }

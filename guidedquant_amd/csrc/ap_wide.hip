@@ -25,12 +25,9 @@ using namespace gq;
 
 namespace {
 
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef gqw::h2v f16x2;
 
-// LDS byte address of a pointer into the block's LDS
-__device__ __forceinline__ u32 lds_addr(const void *p) {
-    return (u32)(uintptr_t)(__attribute__((address_space(3))) const unsigned char *)reinterpret_cast<const unsigned char *>(p);
-}
+using gqw::lds_addr;
 __device__ __forceinline__ _Float16 lds_f16(u32 addr) { return *(const __attribute__((address_space(3))) _Float16 *)(uintptr_t)addr; }
 
 template <int BITS>
@@ -65,8 +62,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) a
 
     constexpr u32 OOB = 0x80000000u;
     const u32 plane_bytes = a.N * G.wpr * 4u;
-    __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void *)a.qw, 0, (int)(plane_bytes * (u32)BITS), 0x00020000);
-    __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void *)a.lut, 0, (int)(a.N * WG::NC * 2u), 0x00020000);
+    rsrc_t rq = make_rsrc(a.qw, plane_bytes * (u32)BITS);
+    rsrc_t rl = make_rsrc(a.lut, a.N * WG::NC * 2u);
     // the lane's share of a step's LUT rows (RS consecutive rows = one contiguous run of RS * NW words): words w0 .. w0 + LW - 1
     const u32 w0 = tid * WG::LW, lr = w0 / WG::NW;
     u32x4 P[BITS];

@@ -8,9 +8,11 @@
 #include <stdint.h>
 
 #include "gq_internal.h"
+#include "wave_util.h"
 
 namespace gq_attn {
 typedef uint32_t u32;
+using gqw::row_sum;  // the score of a cached row: the sum over the LPP lanes that share it, in every one of them
 
 // ------------------------------------------------------------------------------------------------ geometry
 // A block has NW waves.  LPP lanes share a cached row (8 dims = one 16-byte load per lane: a K / V row is one coalesced line pair),
@@ -107,15 +109,6 @@ template <>
 struct AttnKv8<true> {
     const float *k_scale, *v_scale;
 };
-// sum over the LPP lanes of a row (xor butterflies inside a 16-lane DPP row): every lane gets the score
-template <int LPP>
-__device__ __forceinline__ float row_sum(float p) {
-    p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0xB1, 0xF, 0xF, false));
-    p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x4E, 0xF, 0xF, false));
-    p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x141, 0xF, 0xF, false));
-    if (LPP == 16) p += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x140, 0xF, 0xF, false));
-    return p;
-}
 // the online softmax of one stream over a batch of U rows (scores pu, -3e38 = no row; V rows vfu): the rows share ONE rescale of the
 // running (max, sum, weighted V) -- one exp for the old maximum and one per row
 template <int U>

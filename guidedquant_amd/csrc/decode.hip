@@ -10,19 +10,19 @@
 
 #include "gq_internal.h"
 #include "attn_core.h"
-#include "decode_util.h"
+#include "wave_util.h"
 #include "fwht.h"
 
 namespace {
 
-using gq_dec::h16;
-using gq_dec::h2f;
-using gq_dec::h2u;
-using gq_dec::u2h;
-using gq_dec::u32;
-using gq_dec::wave_reduce;
-typedef h16 h16x2 __attribute__((ext_vector_type(2)));
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32;
+using gqw::h16;
+using gqw::h16x2;
+using gqw::h2f;
+using gqw::h2u;
+using gqw::u2h;
+using gqw::u32x4;
+using gqw::wave_reduce_bcast;
 using gq_attn::AttnGeom;
 using gq_attn::AttnWindow;
 using gq_attn::window_lo;
@@ -236,7 +236,7 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
     if constexpr (QKN) {
         // per-head statistics: thread d < HD holds element d of q and of k (the other waves add zeros); fixed order
         const float qf = h2f(qd_b), kf = h2f(kd_b);  // (0 for tid >= HD)
-        float sq = wave_reduce<false>(qf * qf), sk = wave_reduce<false>(kf * kf);
+        float sq = wave_reduce_bcast<false>(qf * qf), sk = wave_reduce_bcast<false>(kf * kf);
         if constexpr (HD > 64) {
             if (l == 0u && w < (u32)(HD / 64)) red[w] = sq, red[HD / 64 + w] = sk;
             __syncthreads();  // (block-uniform: behind the position checks above)
@@ -649,7 +649,7 @@ __global__ void __launch_bounds__(256) dense_gemv_kernel(const uint16_t *x, cons
 #pragma unroll
         for (u32 k = 0; k < NPRE; k++) sq8(xpre[k], ss);  // (units beyond K are zero)
         for (u32 g = tid + 256u * NPRE; g < K / 8u; g += 256) sq8(reinterpret_cast<const uint4 *>(x)[g], ss);
-        ss = wave_reduce<false>(ss);
+        ss = wave_reduce_bcast<false>(ss);
         if (l == 0) red[w] = ss;
         __syncthreads();
         nscale = 1.0f / sqrtf((red[0] + red[1] + red[2] + red[3]) / (float)K + eps);
@@ -689,13 +689,12 @@ __global__ void __launch_bounds__(256) dense_gemv_kernel(const uint16_t *x, cons
         }
 #pragma unroll
         for (int r = 0; r < RW; r++) {
-            const float s = wave_reduce<false>(acc[r]);
+            const float s = wave_reduce_bcast<false>(acc[r]);
             if (l == 0 && r0 + (u32)r < row_end) out[r0 + r] = h2u((h16)s);
         }
     }
 }
 
-int cu_count() { return gq_cu_count(); }
 
 }  // namespace
 
@@ -941,7 +940,7 @@ extern "C" int gq_dense_gemv_f16(const void *x, const void *W, void *out, uint32
     const size_t smem = (size_t)K * 2u + 64u;
     if (smem > 160u * 1024u) return gq_fail(GQ_ENOTSUP, "K too large.");
     constexpr int RW = 4;
-    const u32 ncu = (u32)cu_count();
+    const u32 ncu = (u32)gq_cu_count();
     // ~3 blocks per CU (measured over 2 .. 16 on the 128256 x 4096 lm_head inside the decode step: 3 is 0.4 % of the token faster than 4,
     // 6 is 0.7 % slower), every block a multiple of 4 waves * RW rows
     const int bpc_env = gq_env_int("GQ_DENSE_BPC", 3);

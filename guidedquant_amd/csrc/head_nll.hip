@@ -22,12 +22,13 @@
 #include <hip/hip_runtime.h>
 
 #include "gq_internal.h"
+#include "wave_util.h"
 
 namespace {
 using u32 = uint32_t;
-typedef _Float16 h16;
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using gqw::f32x4;
+using gqw::h16;
+using gqw::h16x8;
 
 constexpr u32 BS = 128, BV = 128, BKK = 64;
 constexpr u32 LD = BKK + 8;          // halves per LDS row: 16 bytes of padding

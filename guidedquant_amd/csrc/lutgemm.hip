@@ -11,12 +11,13 @@
 #include <stdint.h>
 
 #include "gq_internal.h"
+#include "wave_util.h"
 
 namespace {
 typedef uint32_t u32;
-typedef _Float16 h16;
-__device__ __forceinline__ h16 u2h(uint16_t h) { return __builtin_bit_cast(h16, h); }
-__device__ __forceinline__ uint16_t h2u(h16 h) { return __builtin_bit_cast(uint16_t, h); }
+using gqw::h16;
+using gqw::h2u;
+using gqw::u2h;
 
 constexpr int G = 16;   // tiles per LDS round: 16 * 4 * 256 halves = 32 KiB
 constexpr int OB = 64;  // outputs per block; the 4 waves of a block take the tiles of a round in an interleaved way

@@ -12,14 +12,15 @@
 #include <hip/hip_runtime.h>
 
 #include "gq_internal.h"
+#include "wave_util.h"
 
 namespace {
 using u32 = uint32_t;
-typedef _Float16 h16;
-__device__ __forceinline__ float h2f(uint16_t h) { return (float)__builtin_bit_cast(h16, h); }
-__device__ __forceinline__ uint16_t f2h(float f) { return __builtin_bit_cast(uint16_t, (h16)f); }
-__device__ __forceinline__ h16 hbits(uint16_t h) { return __builtin_bit_cast(h16, h); }
-__device__ __forceinline__ uint16_t bitsh(h16 h) { return __builtin_bit_cast(uint16_t, h); }
+using gqw::f2h;
+using gqw::h16;
+using gqw::h2f;
+using gqw::h2u;
+using gqw::u2h;
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -47,8 +48,8 @@ __global__ void __launch_bounds__(256) rmsnorm_rows_kernel(uint16_t *__restrict_
             u32 r[4];
 #pragma unroll
             for (int e = 0; e < 4; e++) {
-                const h16 lo = hbits((uint16_t)(xa[e] & 0xFFFF)) + hbits((uint16_t)(da[e] & 0xFFFF)), hi = hbits((uint16_t)(xa[e] >> 16)) + hbits((uint16_t)(da[e] >> 16));
-                r[e] = (u32)bitsh(lo) | ((u32)bitsh(hi) << 16);
+                const h16 lo = u2h((uint16_t)(xa[e] & 0xFFFF)) + u2h((uint16_t)(da[e] & 0xFFFF)), hi = u2h((uint16_t)(xa[e] >> 16)) + u2h((uint16_t)(da[e] >> 16));
+                r[e] = (u32)h2u(lo) | ((u32)h2u(hi) << 16);
             }
             v[i] = make_uint4(r[0], r[1], r[2], r[3]);
             xr[u] = v[i];
@@ -78,8 +79,8 @@ __global__ void __launch_bounds__(256) rmsnorm_rows_kernel(uint16_t *__restrict_
         for (int e = 0; e < 4; e++) {
             // (x.float() * rs).half(), then the fp16 product with the weight
             const h16 n0 = (h16)(h2f((uint16_t)(xx[e] & 0xFFFF)) * rs), n1 = (h16)(h2f((uint16_t)(xx[e] >> 16)) * rs);
-            const h16 p0 = n0 * hbits((uint16_t)(ww[e] & 0xFFFF)), p1 = n1 * hbits((uint16_t)(ww[e] >> 16));
-            o[e] = (u32)bitsh(p0) | ((u32)bitsh(p1) << 16);
+            const h16 p0 = n0 * u2h((uint16_t)(ww[e] & 0xFFFF)), p1 = n1 * u2h((uint16_t)(ww[e] >> 16));
+            o[e] = (u32)h2u(p0) | ((u32)h2u(p1) << 16);
         }
         orow[u] = make_uint4(o[0], o[1], o[2], o[3]);
     }
@@ -99,12 +100,12 @@ __device__ __forceinline__ void rope_unit(const uint4 a, const uint4 b, const ui
 #pragma unroll
         for (int k = 0; k < 2; k++) {
             const u32 sh = 16u * (u32)k;
-            const h16 a1 = hbits((uint16_t)(x1[e] >> sh)), a2 = hbits((uint16_t)(x2[e] >> sh));
+            const h16 a1 = u2h((uint16_t)(x1[e] >> sh)), a2 = u2h((uint16_t)(x2[e] >> sh));
             // first half:  x1 * cos + (-x2) * sin ;  second half:  x2 * cos + x1 * sin   (rotate_half = cat(-x2, x1))
-            const h16 f = (a1 * hbits((uint16_t)(cc1[e] >> sh))) + ((-a2) * hbits((uint16_t)(ss1[e] >> sh)));
-            const h16 g = (a2 * hbits((uint16_t)(cc2[e] >> sh))) + (a1 * hbits((uint16_t)(ss2[e] >> sh)));
-            r1 |= (u32)bitsh(f) << sh;
-            r2 |= (u32)bitsh(g) << sh;
+            const h16 f = (a1 * u2h((uint16_t)(cc1[e] >> sh))) + ((-a2) * u2h((uint16_t)(ss1[e] >> sh)));
+            const h16 g = (a2 * u2h((uint16_t)(cc2[e] >> sh))) + (a1 * u2h((uint16_t)(ss2[e] >> sh)));
+            r1 |= (u32)h2u(f) << sh;
+            r2 |= (u32)h2u(g) << sh;
         }
         o1[e] = r1, o2[e] = r2;
     }
@@ -230,8 +231,8 @@ __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__
 #pragma unroll
                 for (int k = 0; k < 2; k++) {
                     const u32 sh = 16u * (u32)k;
-                    r1 |= (u32)bitsh(hbits((uint16_t)(x1[e] >> sh)) + hbits((uint16_t)(bb1[e] >> sh))) << sh;
-                    r2 |= (u32)bitsh(hbits((uint16_t)(x2[e] >> sh)) + hbits((uint16_t)(bb2[e] >> sh))) << sh;
+                    r1 |= (u32)h2u(u2h((uint16_t)(x1[e] >> sh)) + u2h((uint16_t)(bb1[e] >> sh))) << sh;
+                    r2 |= (u32)h2u(u2h((uint16_t)(x2[e] >> sh)) + u2h((uint16_t)(bb2[e] >> sh))) << sh;
                 }
                 x1[e] = r1, x2[e] = r2;
             }
@@ -273,10 +274,10 @@ __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__
 #pragma unroll
                 for (int k = 0; k < 2; k++) {
                     const u32 sh = 16u * (u32)k;
-                    const h16 v1 = (h16)(h2f((uint16_t)(x1[e] >> sh)) * rs) * hbits((uint16_t)(ww1[e] >> sh));
-                    const h16 v2 = (h16)(h2f((uint16_t)(x2[e] >> sh)) * rs) * hbits((uint16_t)(ww2[e] >> sh));
-                    r1 |= (u32)bitsh(v1) << sh;
-                    r2 |= (u32)bitsh(v2) << sh;
+                    const h16 v1 = (h16)(h2f((uint16_t)(x1[e] >> sh)) * rs) * u2h((uint16_t)(ww1[e] >> sh));
+                    const h16 v2 = (h16)(h2f((uint16_t)(x2[e] >> sh)) * rs) * u2h((uint16_t)(ww2[e] >> sh));
+                    r1 |= (u32)h2u(v1) << sh;
+                    r2 |= (u32)h2u(v2) << sh;
                 }
                 x1[e] = r1, x2[e] = r2;
             }
@@ -325,7 +326,7 @@ __global__ void __launch_bounds__(256) silu_mul_rows_kernel(const uint16_t *__re
                 const u32 sh = 16u * (u32)k;
                 const float gf = h2f((uint16_t)(gw[e] >> sh));
                 const h16 sl = (h16)(gf / (1.0f + expf(-gf)));  // F.silu on fp16: computed in fp32, rounded
-                r |= (u32)bitsh(sl * hbits((uint16_t)(uw[e] >> sh))) << sh;
+                r |= (u32)h2u(sl * u2h((uint16_t)(uw[e] >> sh))) << sh;
             }
             o[e] = r;
         }

@@ -33,14 +33,15 @@
 #include <hip/hip_runtime.h>
 
 #include "gq_internal.h"
+#include "wave_util.h"
 
 namespace {
 using u32 = uint32_t;
-typedef _Float16 h16;
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
+using gqw::f32x4;
+using gqw::h16;
+using gqw::h16x8;
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr u32 BQ = GQ_PREFILL_ATTN_BQ, BK = GQ_PREFILL_ATTN_BK;
 static_assert(BQ == 64 && BK == 64, "4 waves x 16 query rows; 4 score blocks of 16 keys");

@@ -19,6 +19,7 @@
 
 #include "gq_internal.h"
 #include "fwht.h"
+#include "wave_util.h"
 
 #ifndef QT_XOOB
 #define QT_XOOB 1
@@ -27,8 +28,15 @@ namespace {
 typedef uint32_t u32;
 using gq_fwht::fwht_lds;
 typedef unsigned long long u64;
-typedef _Float16 h16;
-typedef h16 h16x2 __attribute__((ext_vector_type(2)));
+using gqw::f32x4;
+using gqw::h16;
+using gqw::h16x2;
+using gqw::h16x8;
+using gqw::make_rsrc;
+using gqw::rsrc_t;
+using gqw::u32x2;
+using gqw::u32x4;
+using gqw::wave_allsum;
 
 template <int R>
 __device__ __forceinline__ u32 unit_of(const u32 (&d)[R], u32 j);  // R-byte little-endian unit j of the 4R-byte s-row
@@ -49,11 +57,7 @@ __device__ __forceinline__ u32 unit_of<4>(const u32 (&d)[4], u32 j) { return d[j
 #ifndef QT_ABL
 #define QT_ABL 0  // experiments (tools/qtip_ablation.sh): 1 no codebook lookups, 2 no MFMA, 4 no ds_bpermute, 8 no activation read, 16 no state arithmetic, 32 no FWHT, 64 no codebook fill
 #endif
-typedef h16 h16x8 __attribute__((ext_vector_type(8)));
 unsigned long long *g_qdbg = nullptr;  // optional per-wave phase stamps of the middle block (tools/qtip_phase_timing.py)
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-typedef u32 u32x2 __attribute__((ext_vector_type(2)));
 
 // ------------------------------------------------------------------------------------------------ the band engine
 // Round 2 redesign (round 1: one v_dot2 per state, one 2 KiB codebook with ~3.5-way bank conflicts, 8 VALU per state).
@@ -169,7 +173,7 @@ struct QtChunk {
 };
 
 template <int R>
-__device__ __forceinline__ void qtip_load_chunk(u32 (&d)[QtChunk<R>::LD], __amdgpu_buffer_rsrc_t rs, u32 voff, u32 soff) {
+__device__ __forceinline__ void qtip_load_chunk(u32 (&d)[QtChunk<R>::LD], rsrc_t rs, u32 voff, u32 soff) {
     if constexpr (R == 3) {
         const auto v = __builtin_amdgcn_raw_buffer_load_b96(rs, voff, soff, 2 /* nt */);
         d[0] = v[0], d[1] = v[1], d[2] = v[2];
@@ -199,7 +203,7 @@ __device__ __forceinline__ void qtip_engine(const u32 *tab, const uint16_t *xsp,
     // R = 4: raw rows of four dword units; this lane wants units a4 and 2 + a4 (column tiles 0 / 1) of its row and the neighbour's
     const unsigned char *own_p = slot + (R == 2 ? 16u * (s >> 1) + 8u * a4 + 4u * (s & 1u) : s * (4u * R) + (R == 4 ? 4u * a4 : 0u));
     const unsigned char *nbr_p = slot + (R == 2 ? 16u * (sn >> 1) + 8u * a4 + 4u * (sn & 1u) : sn * (4u * R) + (R == 4 ? 4u * a4 : 0u));
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)comp, 0, (int)comp_bytes, 0x00020000);
+    const rsrc_t rs = make_rsrc(comp, comp_bytes);
 #ifndef QT_PF
 #define QT_PF 2
 #endif
@@ -366,7 +370,7 @@ __device__ __forceinline__ void qtip_engine(const u32 *tab, const uint16_t *xsp,
     };
     // this lane group's 8 activations of tile block K2: xg + 32 K2.  QT_XOOB: only column 0 of the B operand carries them; the
     // lanes of columns 1..15 read from 192 KiB above -- outside the LDS allocation, where ds_read returns zeros (tools/ubench/
-    // lds_oob.hip): 15 equal copies of the activations in the matrix cores cost power, and with it clock (ap_plane.hip, PL_BOOB)
+    // lds_oob.hip): 15 equal copies of the activations in the matrix cores cost power, and with it clock (ap_plane.hip: the idle MFMA columns)
 #if QT_XOOB
     const uint16_t *xg = xsp + 8u * g + ((l & 15u) ? 0x18000u : 0u);
 #else
@@ -735,11 +739,11 @@ __global__ void __launch_bounds__(1024) qtip_linear_in_kernel(QtipInArgs a) {
                         ss += f * f;
                     }
             }
-            ss = gq_wave_allsum(ss);  // (round 6: register tree instead of six ds_bpermute round trips)
+            ss = wave_allsum(ss);  // (round 6: register tree instead of six ds_bpermute round trips)
             if ((tid & 63u) == 0) redf[tid >> 6] = ss;
             __syncthreads();
             {  // every wave adds the wave sums through the same tree (one LDS round trip): no second barrier, no serial thread
-                const float t = gq_wave_allsum((tid & 63u) < (T >> 6) ? redf[tid & 63u] : 0.f);
+                const float t = wave_allsum((tid & 63u) < (T >> 6) ? redf[tid & 63u] : 0.f);
                 nscale = 1.0f / sqrtf(t / (float)K + a.eps);
             }
         }
@@ -920,10 +924,10 @@ __global__ void __launch_bounds__(1024) qtip_out_in_kernel(QtipOutInArgs a) {
             const float f = (float)__builtin_bit_cast(h16, hs[8u * u + e]);
             ss += f * f;
         }
-    ss = gq_wave_allsum(ss);
+    ss = wave_allsum(ss);
     if ((tid & 63u) == 0) redf[tid >> 6] = ss;
     __syncthreads();
-    const float t = gq_wave_allsum((tid & 63u) < (T >> 6) ? redf[tid & 63u] : 0.f);  // (as qtip_linear_in_kernel's prologue: the same tree)
+    const float t = wave_allsum((tid & 63u) < (T >> 6) ? redf[tid & 63u] : 0.f);  // (as qtip_linear_in_kernel's prologue: the same tree)
     const float nscale = 1.0f / sqrtf(t / (float)K + a.eps);
 #pragma unroll
     for (u32 k = 0; k < NU; k++) {
@@ -1066,10 +1070,10 @@ __global__ void __launch_bounds__(1024) qtip_transform_kernel(QtipXfArgs a) {
                 const float f = (float)__builtin_bit_cast(h16, a.x[i]);
                 ss += f * f;
             }
-            ss = gq_wave_allsum(ss);
+            ss = wave_allsum(ss);
             if ((tid & 63u) == 0) redf[tid >> 6] = ss;
             __syncthreads();
-            rs = 1.0f / sqrtf(gq_wave_allsum((tid & 63u) < (T >> 6) ? redf[tid & 63u] : 0.f) / (float)n + a.eps);
+            rs = 1.0f / sqrtf(wave_allsum((tid & 63u) < (T >> 6) ? redf[tid & 63u] : 0.f) / (float)n + a.eps);
         }
         for (u32 u = tid; u < n / 8u; u += T) {  // 8 activations per 16-byte load
             const uint4 xq = reinterpret_cast<const uint4 *>(a.x)[u];
@@ -1190,8 +1194,8 @@ __global__ void __launch_bounds__(MID_T) qtip_mlp_mid_kernel(QtipMidArgs a) {
     const u32 c16 = tid & 15u, rq = tid >> 4;
     u32x4 xq[6];
     {
-        const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.y32g), (short)0, (int)(a.parts * a.n * 4u), 0x00020000);
-        const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.y32u), (short)0, (int)(a.parts * a.n * 4u), 0x00020000);
+        const rsrc_t rg = make_rsrc(a.y32g, a.parts * a.n * 4u);
+        const rsrc_t ru = make_rsrc(a.y32u, a.parts * a.n * 4u);
 #pragma unroll
         for (u32 i = 0; i < 3; i++) {
             const u32 row = rq + 64u * i;
@@ -1203,8 +1207,8 @@ __global__ void __launch_bounds__(MID_T) qtip_mlp_mid_kernel(QtipMidArgs a) {
     // the tables: flat 16-byte units, 4 per thread and table (a wave instruction moves 1 KiB: 8 instead of 32 requests per wave)
     u32x4 tq[8];
     {
-        const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(a.hadT_out), (short)0, (int)tbytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(a.had_in), (short)0, (int)tbytes, 0x00020000);
+        const rsrc_t ro = make_rsrc(a.hadT_out, tbytes);
+        const rsrc_t ri = make_rsrc(a.had_in, tbytes);
 #pragma unroll
         for (u32 i = 0; i < 4; i++) {
             tq[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ro, (int)((tid + MID_T * i) * 16u), 0, 0));

@@ -33,13 +33,14 @@
 #include <stdint.h>
 
 #include "gq_internal.h"
+#include "wave_util.h"
 
 namespace {
 typedef uint32_t u32;
 typedef unsigned long long u64;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+using gqw::f16x8;
+using gqw::f32x16;
+using gqw::u32x4;
 
 constexpr u32 WAVES = 4, BM = 32u * WAVES;  // weight rows per block
 // tile blocks (32 columns each) per x stage: 2, or 1 beside the 128 accumulator registers of 8 token fragments

@@ -6,14 +6,14 @@
 #include <stdint.h>
 
 #include "gq_internal.h"
-#include "decode_util.h"
+#include "wave_util.h"
 
 namespace {
 
-using gq_dec::h16;
-using gq_dec::h2f;
-using gq_dec::u32;
-using gq_dec::wave_reduce;
+typedef uint32_t u32;
+using gqw::h16;
+using gqw::h2f;
+using gqw::wave_reduce_bcast;
 typedef unsigned long long u64;
 
 // Top-k sampling exactly as generate.py:53-73 defines the distribution: logits / max(T, 1e-5), keep the top k,
@@ -258,11 +258,11 @@ __global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32
         float mt = raw[0];
 #pragma unroll
         for (int e = 1; e < EPT; e++) mt = fmaxf(mt, raw[e]);
-        const float mw = wave_reduce<true>(mt);
+        const float mw = wave_reduce_bcast<true>(mt);
         float zt = 0.f;
 #pragma unroll
         for (int e = 0; e < EPT; e++) zt += raw[e] == LP_NINF ? 0.f : expf(raw[e] - mw);
-        const float zw = wave_reduce<false>(zt);
+        const float zw = wave_reduce_bcast<false>(zt);
         if (l == 0) {
             lpm[w] = mw;
             lpz[w] = zw;

@@ -1,0 +1,64 @@
+"""CPU: a source scan of guidedquant_amd/csrc -- the device helpers the kernel files share are defined ONCE (wave_util.h: casts,
+reductions, descriptors, the asm vector-memory requests; plane_mfma.h: the pieces of the plane arithmetic), under names that tell
+their contracts apart, and the settled build-time forks are gone.  A second copy under the same name is how wave_reduce<true> came
+to mean two things (identity 0 in one file, -3e38 in another)."""
+import glob
+import os
+import re
+
+import pytest
+
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "guidedquant_amd", "csrc")
+SOURCES = {os.path.basename(p): open(p).read() for p in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h")))}
+
+# name -> the one file that defines it.  A device function's definition is a line that STARTS with __device__ and names it in front
+# of its parameter list (a call never starts a line that way).  ap_core.h's gq::u2h / gq::h2u are other functions under these names:
+# the packed-pair casts of the exact path, host + device (GQ_HD) because the CPU twins compile them -- not matched, not meant.
+DEVICE_FUNCTIONS = {
+    "wave_util.h": ["h2f", "f2h", "u2h", "h2u", "u2h2", "h22u",                                             # the casts
+                    "wave_reduce_l63", "lane63", "wave_reduce_bcast", "wave_allsum", "row_sum",             # the reductions
+                    "make_rsrc", "make_rsrc4",                                                              # the descriptor
+                    "dma16", "aload128", "bload16s", "tie128", "tie4", "wait_vm", "wait_vm_steps", "wait_vm_units", "lds_addr"],
+    "plane_mfma.h": ["mfma_f4_bf8", "bf8_split", "hot_tau_bits", "silu_mul2"],
+}
+OTHER_DEFINITIONS = {  # pattern -> the one file
+    r"^\s*struct HotEnt\b": "plane_mfma.h",
+    r"^\s*#\s*define\s+GQ_HOT_T\b": "plane_mfma.h",
+    r"0x00020000": "wave_util.h",  # the descriptor's flags word, named once (RSRC_FLAGS)
+}
+# names that must not come back: the reduction name that had two contracts, the second threshold, the helpers' former private spellings
+RETIRED = ["wave_reduce", "gq_wave_allsum", "GQ_ST_HOT_T", "g_dma16", "g_load16", "g_wait_vm", "g_rsrc"]
+# build-time forks that were decided and taken out (DESIGN.md sections 3.5 - 3.7 keep the verdicts)
+REMOVED_FORKS = ["PL_SSQ_MODE", "PL_BOOB", "PL_LOOB", "ST_DPPIMG", "ST_TAU_SCALE", "ST_MAINPRIO", "ST_AUX"]
+
+
+def files_matching(pattern):
+    rx = re.compile(pattern, re.M)
+    return sorted(f for f, text in SOURCES.items() if rx.search(text))
+
+
+def test_the_scan_sees_the_tree():
+    assert len(SOURCES) >= 25 and "wave_util.h" in SOURCES and "plane_mfma.h" in SOURCES and "decode_util.h" not in SOURCES
+
+
+@pytest.mark.parametrize("home,name", [(h, n) for h, names in DEVICE_FUNCTIONS.items() for n in names])
+def test_device_helper_is_defined_in_one_file(home, name):
+    assert files_matching(r"^\s*__device__[^;=\n]*[\s\*&]" + name + r"\s*\(") == [home]
+
+
+@pytest.mark.parametrize("pattern,home", sorted(OTHER_DEFINITIONS.items()))
+def test_type_and_constant_are_defined_in_one_file(pattern, home):
+    assert files_matching(pattern) == [home]
+
+
+@pytest.mark.parametrize("name", RETIRED + REMOVED_FORKS)
+def test_retired_name_is_gone(name):
+    assert files_matching(r"(?<![A-Za-z0-9_])" + name + r"(?![A-Za-z0-9_])") == []
+
+
+def test_plane_core_stays_host_compilable():
+    # (tests/test_lane_program_cpu.py and the CPU twins compile plane_core.h with a host compiler: the device pieces live next to it)
+    text = SOURCES["plane_core.h"]
+    assert "wave_util.h" not in text and "plane_mfma.h" not in text and "__builtin_amdgcn" not in text
