@@ -65,12 +65,12 @@ extern "C" void gq_reset_env_cache(void) {
     g_env_cache.clear();
 }
 
-// Self-check of a hardware behaviour three kernels rest on (the two kernels of ap_plane.hip; qtip.hip QT_XOOB): a ds_read from an
+// Self-check of a hardware behaviour three kernels rest on (the two kernels of ap_plane.hip; the band engine of qtip.hip): a ds_read from an
 // LDS address beyond the workgroup's allocation (192 KiB and up; the chip has 160 KiB) returns zeros -- the idle MFMA columns of
 // those kernels take their zeros from there.  Verified on gfx950 (tools/ubench/lds_oob.hip); another architecture, a sanitizer or
 // a compiler that lowers the access to flat addressing would corrupt sums silently, so the binding runs this once per process
-// and refuses to go on if it fails.  (qtip.hip keeps a build without it, -DQT_XOOB=0; the plane kernels' arms that read a zero area
-// in LDS instead were taken out once the fork was settled -- DESIGN.md section 3.7 names the commit that still has them.)
+// and refuses to go on if it fails.  (The arms that read a zero area in LDS instead were taken out once the fork was settled:
+// DESIGN.md sections 3.7 (plane kernels) and 3.13 (qtip.hip) name the commits that still have them.)
 namespace {
 __global__ void lds_oob_probe(unsigned *out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
@@ -90,7 +90,7 @@ extern "C" int gq_selfcheck(void) {
     if (e != hipSuccess) return gq_fail_hip(e, "gq_selfcheck");
     for (unsigned v : h)
         if (v) return gq_fail(GQ_ENOTSUP, "LDS reads beyond the workgroup's allocation do not return zero on this device: the plane-MFMA kernels "
-                                           "(csrc/ap_plane.hip) and the QTIP kernels (csrc/qtip.hip, -DQT_XOOB=0) rest on it.");
+                                           "(csrc/ap_plane.hip) and the QTIP kernels (csrc/qtip.hip) rest on it.");
     return GQ_OK;
 }
 

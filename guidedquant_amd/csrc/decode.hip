@@ -12,6 +12,7 @@
 #include "attn_core.h"
 #include "wave_util.h"
 #include "fwht.h"
+#include "qtip_xform.h"
 
 namespace {
 
@@ -140,17 +141,16 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
         // every thread takes 16-byte units of the three vectors (all loads of a thread in flight together: one round trip to L2):
         // unit u of a vector = segment c = u / (HD / 4), elements 4 (u % (HD / 4)) ..; a thread's units of one vector share the
         // element group (T is a multiple of HD / 4), so it keeps one signed partial sum per vector; the T / (HD / 4) partial sums
-        // of an element are added in a fixed order behind the barrier
+        // of an element are added in a fixed order behind the barrier.  gqq::seg_load / seg_signed_sum (qtip_xform.h), written out: as calls
+        // the kernel's scalar loads of `qt` come out in another order
         {
             constexpr u32 Q = HD / 4u;
             const u32 T = blockDim.x, G = T / Q;  // G thread groups per element group
             float *ps = lds + L::ps;  // [3][G][HD] partial sums
             float4 y[3][4];
-            u32 cnt[3];
 #pragma unroll
             for (u32 vi = 0; vi < 3; vi++) {
                 const u32 M4 = qt.M[vi] / 4u;
-                cnt[vi] = 0;
 #pragma unroll
                 for (u32 k = 0; k < 4; k++) {
                     const u32 u = tid + k * T;
@@ -189,8 +189,7 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
         gq_fwht::fwht_lds(tv, 3u * HD, (u32)HD);  // the three HD-point transforms (barrier behind)
         if (tid < 3u * HD) {
             const u32 vi = tid / HD, b = tid % HD, seg = vi == 0u ? h : g;
-            const h16 o = (h16)gq_pin_f32((tv[tid] * qt.mscale[vi]) * qt.sv32[vi][(size_t)seg * HD + b]);
-            res16[tid] = h2u(o);
+            res16[tid] = h2u(gqq::xf_out(tv[tid], qt.mscale[vi], qt.sv32[vi][(size_t)seg * HD + b]));
         }
         __syncthreads();
         q = res16, k = res16 + HD, v = res16 + 2 * HD;

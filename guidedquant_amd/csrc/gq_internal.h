@@ -44,6 +44,17 @@ struct GqPerDeviceOnce {
     }
 };
 
+// Host pieces the two QTIP translation units share (qtip.hip: the trellis side, qtip_xf.hip: the transform side, which defines them).
+extern unsigned long long *g_qdbg;  // optional per-wave phase stamps (gq_debug_set_qtip_timing_buffer; tools/qtip_phase_timing.py)
+float gq_inv_sqrt_f(uint32_t n);    // (float)n^-1/2, rounded from double like the scale argument of hadamard()
+namespace gqq {
+struct QtipOut;  // csrc/qtip_xform.h: the kernels' form of a GqQtipOut
+}
+// What every entry point asks of a GqQtipOut -- sums and scales (need_out: and the output) not null, parts <= 4 -- and its kernel
+// form (mscale = M^-1/2, parts 0 -> 1).  Widths, alignments and the error texts stay with the entry points.
+enum GqQtipOutErr { GQ_QOUT_OK = 0, GQ_QOUT_NULL, GQ_QOUT_PARTS };
+GqQtipOutErr gq_qtip_out_desc(const GqQtipOut &g, bool need_out, gqq::QtipOut &o);
+
 // Phase stamps (tools/phase_timing.py, qtip_phase_timing.py, qtip_mid_timing.py: per-wave shader-clock timestamps into a debug buffer)
 // are compiled OUT of the shipped library: even switched off at run time every stamp site costs a wave two or three scalar
 // instructions and a branch on its critical path (the stream kernel's prologue alone had ~20 sites).  A library with the sites:

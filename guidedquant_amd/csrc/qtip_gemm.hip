@@ -51,8 +51,8 @@ template <int CF>
 constexpr u32 rowb_of() { return 64u * tb_of<CF>() + 16u; }
 constexpr u32 MAX_KSPLIT = 16;
 
-// unit j = 2 a3 + a4 of an s-row (R dwords, R-byte little-endian units) -- the lines of qtip.hip's unit_of, with a4 a
-// per-lane value and a3 a compile-time one
+// unit j = 2 a3 + a4 of an s-row (R dwords, R-byte little-endian units) -- with a4 a per-lane value and a3 a
+// compile-time one
 template <int R>
 __device__ __forceinline__ u32 unit_sel(const u32 (&d)[R], u32 a3, u32 a4) {
     if constexpr (R == 2) {

@@ -1,6 +1,6 @@
 """CPU: a source scan of guidedquant_amd/csrc -- the device helpers the kernel files share are defined ONCE (wave_util.h: casts,
-reductions, descriptors, the asm vector-memory requests; plane_mfma.h: the pieces of the plane arithmetic), under names that tell
-their contracts apart, and the settled build-time forks are gone.  A second copy under the same name is how wave_reduce<true> came
+reductions, descriptors, the asm vector-memory requests; plane_mfma.h: the pieces of the plane arithmetic; qtip_xform.h: the element-wise
+arithmetic of the QTIP transform-in / transform-out), under names that tell their contracts apart, and the settled build-time forks are gone.  A second copy under the same name is how wave_reduce<true> came
 to mean two things (identity 0 in one file, -3e38 in another)."""
 import glob
 import os
@@ -22,6 +22,8 @@ DEVICE_FUNCTIONS = {
                     "make_rsrc", "make_rsrc4",                                                              # the descriptor
                     "dma16", "aload128", "bload16s", "tie128", "tie4", "wait_vm", "wait_vm_steps", "wait_vm_units", "lds_addr"],
     "plane_mfma.h": ["mfma_f4_bf8", "bf8_split", "hot_tau_bits", "silu_mul2"],
+    "qtip_xform.h": ["h16_of", "sum_parts", "sum_parts4", "xf_out", "xf_resid", "xf_in", "xf_in_unit", "xf_in_h16", "xf_in_pack",  # the elements
+                     "ssq_unit", "block_rms_scale", "seg_load", "seg_signed_sum", "qtip_transform_out"],
 }
 OTHER_DEFINITIONS = {  # pattern -> the one file
     r"^\s*struct HotEnt\b": "plane_mfma.h",
@@ -31,7 +33,10 @@ OTHER_DEFINITIONS = {  # pattern -> the one file
 # names that must not come back: the reduction name that had two contracts, the second threshold, the helpers' former private spellings
 RETIRED = ["wave_reduce", "gq_wave_allsum", "GQ_ST_HOT_T", "g_dma16", "g_load16", "g_wait_vm", "g_rsrc"]
 # build-time forks that were decided and taken out (DESIGN.md sections 3.5 - 3.7 keep the verdicts)
-REMOVED_FORKS = ["PL_SSQ_MODE", "PL_BOOB", "PL_LOOB", "ST_DPPIMG", "ST_TAU_SCALE", "ST_MAINPRIO", "ST_AUX"]
+REMOVED_FORKS = ["PL_SSQ_MODE", "PL_BOOB", "PL_LOOB", "ST_DPPIMG", "ST_TAU_SCALE", "ST_MAINPRIO", "ST_AUX",
+                 # qtip.hip's, and the helpers nothing called
+                 "QT_ABL", "QT_SB", "QT_XOOB", "QT_PF", "QT_ENGINE_STAMPS", "unit_of", "qtip_xpos", "QtipNoop", "qtip_sum_parts"]
+QTIP_UNITS = [f for f in SOURCES if f.startswith("qtip") and f.endswith(".hip")]
 
 
 def files_matching(pattern):
@@ -56,6 +61,16 @@ def test_type_and_constant_are_defined_in_one_file(pattern, home):
 @pytest.mark.parametrize("name", RETIRED + REMOVED_FORKS)
 def test_retired_name_is_gone(name):
     assert files_matching(r"(?<![A-Za-z0-9_])" + name + r"(?![A-Za-z0-9_])") == []
+
+
+def test_the_qtip_rounding_points_stand_in_the_header_only():
+    # the division of the transform-in and the SiLU of its prologue: spelled in qtip_xform.h, in no kernel file (comments included)
+    assert sorted(QTIP_UNITS) == ["qtip.hip", "qtip_gemm.hip", "qtip_xf.hip"]
+    for f in QTIP_UNITS:
+        assert "/ 32.0f" not in SOURCES[f] and "1.0f + __expf" not in SOURCES[f], f
+    assert "/ 32.0f" in SOURCES["qtip_xform.h"] and "1.0f + __expf" in SOURCES["qtip_xform.h"]
+    # n^-1/2 is rounded from double in one place (gq_inv_sqrt_f)
+    assert SOURCES["qtip.hip"].count("pow((double)") + SOURCES["qtip_xf.hip"].count("pow((double)") <= 1
 
 
 def test_plane_core_stays_host_compilable():
