@@ -1010,7 +1010,19 @@ __global__ void __launch_bounds__(BITS == 2 ? 1024 : 512) ap_plane_local_kernel(
     // in the issue queue) -- they build their image first and request their tiles then.  The tile stream (57 KiB per CU for w2) is
     // short next to the image builds it overlaps with.
     u32 lut_from = 0, lut_after = 0, nlut = 0;
-    auto request_tiles = [&]() {
+    // TAIL (the 2-bit decode instance: the 64 epilogue lanes of a one-row-group block are one wave): when the last wave has no chunk
+    // to multiply -- no item (wo: 4 items on 16 waves) or an item past the last chunk (w2: 14 chunks, 16 items) -- it owns the
+    // epilogue lanes instead of wave 0, which is on the critical path until the last barrier.  It is the wave whose queue carries the
+    // LUT rows, so behind its own wait it has them without a barrier: it computes its lane's coefficient and has its residual
+    // element in a register BEFORE the barrier; behind it only the sums are read and added (same values, same order).
+    // Launch-constant geometry; no multiply wave runs a test for it in front of its steps (the request sits in the last wave's
+    // LUT branch).  Every other geometry (a last wave with steps, several row groups) keeps plane_epilogue on wave 0.
+    // (the last wave requests its tiles behind its image build -- pl_xfirst 2 -- and the residual request has that ONE site)
+    constexpr int XFIRST = pl_xfirst<BITS>();
+    constexpr bool TAIL = SPEC && BITS == 2 && NC == 1 && XFIRST == 2;
+    const bool tail_staged = TAIL && a.RGB == 1u && CS <= W && (nIt < W || (W - 1u) * cpi >= G.nchunks);
+    u32 tail_res = 0u;   // the lane's residual element (fp16 bits)
+    auto request_tiles = [&](auto late) {
         while (iq_n < my_steps && iq_n < S) issue();
         // LUT rows of the block: pseudo steps of exactly LPS loads in the queue of the last wave (see the kernel above)
         nlut = w == W - 1u ? lut_bytes / (LPS * 1024u) : 0u;
@@ -1019,13 +1031,22 @@ __global__ void __launch_bounds__(BITS == 2 ? 1024 : 512) ap_plane_local_kernel(
             const u32 want = a.RGB * 16u * (u32)NP * 2u;
             for (u32 o = 0; o < lut_bytes; o += 1024u)
                 dma16<true>(rl, (u32)(uintptr_t)lutb + o, o + 16u * l < want ? rg0 * 16u * (u32)NP * 2u + o + 16u * l : OOB);
+            if constexpr (TAIL && decltype(late)::value) {
+                // the residual elements of the block's rows (lane = (row, c): the c == 0 lanes), behind the LUT rows in this wave's
+                // queue: the stricter count this gives the wave's own step wait costs nothing, its step multiplies nothing.  An
+                // in-out destination: it is looked at ~5,000 cycles later (wave_util.h, "Register copies"); no residual: no bytes.
+                if (tail_staged) {
+                    const u32 row = rg0 * 16u + (l >> 2);
+                    const u32x4 rr = make_rsrc4(a.resid ? a.resid + (size_t)m * a.N : nullptr, a.resid ? a.N * 2u : 0u);
+                    aload16s(tail_res, rr, ((l & 3u) == 0u && row < a.N) ? 2u * row : OOB, 0u);
+                }
+            }
         }
         lut_from = iq_n, lut_after = nlut;
     };
-    constexpr int XFIRST = pl_xfirst<BITS>();
     const bool tiles_late = XFIRST == 2 && w >= W / 2u;
     if constexpr (XFIRST != 0) wait_vm<0>();
-    if (!tiles_late) request_tiles();
+    if (!tiles_late) request_tiles(std::false_type{});
     stamp(6);
 
     // ---- 1. scale of this wave, pieces, image
@@ -1158,7 +1179,7 @@ __global__ void __launch_bounds__(BITS == 2 ? 1024 : 512) ap_plane_local_kernel(
     }
     stamp(1);
     asm volatile("" ::: "memory");  // the image of this wave is read by this wave only: program order suffices
-    if (tiles_late) request_tiles();
+    if (tiles_late) request_tiles(std::true_type{});
     if (prio) __builtin_amdgcn_s_setprio(0);
 
     // ---- 2. the steps of this wave
@@ -1194,12 +1215,91 @@ __global__ void __launch_bounds__(BITS == 2 ? 1024 : 512) ap_plane_local_kernel(
     }
     wait_vm<0>();
     stamp(3);
+    // (a single wave issues an instruction every ~5 cycles: what counts behind the barrier is the NUMBER of instructions there)
+    typedef __attribute__((address_space(3))) const float lds_f;
+    typedef __attribute__((address_space(3))) const v4f lds_v4f;
+    float tail_coef = 0.f;
+    lds_f *tail_pp = nullptr;
+    lds_v4f *tail_xp = nullptr;
+    uint16_t *tail_out = nullptr;
+    if constexpr (TAIL) {
+        // the epilogue wave's lane = (row l / 4, Moebius index c = l % 4): its LUT row came through this wave's own queue and
+        // has landed with the wait above, like its residual element; plane_epilogue's operations, in its order.  Its addresses
+        // are formed here too (pinned in registers: the compiler would form them again behind the barrier).
+        if (tail_staged && w == W - 1u) {
+            asm volatile("" : "+v"(tail_res));
+            float f[NP];
+#pragma unroll
+            for (int cc = 0; cc < NP / 2; cc++) {
+                const u32 lw = lutl[(size_t)(l >> 2) * (NP / 2) + cc];
+                f[2 * cc] = h2f((uint16_t)(lw & 0xFFFF));
+                f[2 * cc + 1] = h2f((uint16_t)(lw >> 16));
+            }
+            moebius<BITS>(f);
+            const u32 c = l & 3u, rr = l >> 2, row = rg0 * 16u + rr;
+            tail_coef = f[0];
+#pragma unroll
+            for (int cc = 1; cc < NP; cc++) tail_coef = c == (u32)cc ? f[cc] : tail_coef;
+            // (the c == 0 lanes read subset 0's sums and drop them; lanes that store nothing keep a null pointer)
+            tail_pp = (lds_f *)(part + (c ? c - 1u : 0u) * 16u + rr);
+            tail_xp = (lds_v4f *)(red + 32);
+            tail_out = (c == 0u && row < a.N) ? a.out + (size_t)m * a.N + row : nullptr;
+            asm volatile("" : "+v"(tail_coef), "+v"(tail_pp), "+v"(tail_xp), "+v"(tail_out));
+        }
+    }
     __syncthreads();
     stamp(4);
-    float X = 0.f;
+    if (TAIL && tail_staged) {
+        if (w == W - 1u) {
+            // behind the barrier: sum(x) and the lane's K-split partial sums, every read in flight before the first add, then
+            // the adds in plane_epilogue's order (host: one row group and 16 waves give CS = 1, 2, 4, 8 or 16 items)
+            constexpr u32 PS = NP1 * 16u;
+            v4f xs[W / 4u];
 #pragma unroll
-    for (u32 i = 0; i < W; i++) X += red[32 + i];
-    plane_epilogue<BITS, SPEC>(a, lutl, part, X, rg0, m, tid, T, NP1 * 16u);
+            for (u32 i = 0; i < W / 4u; i++) xs[i] = tail_xp[i];
+            float term = 0.f;
+            if (CS == 16u) {
+                float v[16];
+#pragma unroll
+                for (u32 k = 0; k < 16; k++) v[k] = tail_pp[k * PS];
+                __builtin_amdgcn_sched_barrier(0);  // (every read is requested before the first add waits: one LDS round trip)
+#pragma unroll
+                for (u32 k = 0; k < 16; k++) term += v[k];
+            } else if (CS == 8u) {
+                float v[8];
+#pragma unroll
+                for (u32 k = 0; k < 8; k++) v[k] = tail_pp[k * PS];
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (u32 k = 0; k < 8; k++) term += v[k];
+            } else {
+                // (no branch around a read: an item that does not exist re-reads the last one and counts as the zero it was)
+                float v[4];
+#pragma unroll
+                for (u32 k = 0; k < 4; k++) v[k] = tail_pp[min(k, CS - 1u) * PS];
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (u32 k = 0; k < 4; k++) term += k < CS ? v[k] : 0.f;
+            }
+            float X = 0.f;
+#pragma unroll
+            for (u32 i = 0; i < W; i++) X += xs[i >> 2][i & 3u];
+            term = (l & 3u) == 0u ? X : term;
+            float y = tail_coef * term;
+            y += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y), 0xB1, 0xF, 0xF, false));
+            y += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y), 0x4E, 0xF, 0xF, false));
+            _Float16 yh = (_Float16)y;
+            if (tail_out) {
+                if (a.resid) yh = __builtin_bit_cast(_Float16, (uint16_t)tail_res) + yh;
+                store_out16(tail_out, __builtin_bit_cast(uint16_t, yh));
+            }
+        }
+    } else {
+        float X = 0.f;
+#pragma unroll
+        for (u32 i = 0; i < W; i++) X += red[32 + i];
+        plane_epilogue<BITS, SPEC>(a, lutl, part, X, rg0, m, tid, T, NP1 * 16u);
+    }
     stamp(5);
     if (GQ_STAMPS == 2 && a.dbg && blockIdx.y == 0u) {
         __syncthreads();

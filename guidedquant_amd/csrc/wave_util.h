@@ -170,6 +170,10 @@ __device__ __forceinline__ uint32_t bload16s(u32x4 rsrc, uint32_t voff, uint32_t
     asm volatile("buffer_load_ushort %0, %1, %2, %3 offen" : "=v"(r) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
     return r;
 }
+// ... into a register that stays live until a wait far behind the request (in-out, like aload128)
+__device__ __forceinline__ void aload16s(uint32_t &dst, u32x4 rsrc, uint32_t voff, uint32_t soff) {
+    asm volatile("buffer_load_ushort %0, %1, %2, %3 offen" : "+v"(dst) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+}
 __device__ __forceinline__ void tie128(u32x4 &r) { asm volatile("" : "+v"(r)); }
 __device__ __forceinline__ void tie4(uint32_t (&r)[4]) { asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3])); }
 template <int N>
