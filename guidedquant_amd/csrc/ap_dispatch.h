@@ -1,6 +1,6 @@
 // ap_dispatch.h -- the interface between the translation units of the Any-Precision GEMV: one launch descriptor, and every function one
 // of them defines for another.  ap_dispatch.hip decides which kernel family serves a launch ("Dispatch order"); a kernel file
-// (ap_gemv.hip, ap_plane.hip, ap_stream.hip, ap_wide.hip) only serves the launch it is handed, or returns GQ_ENOTSUP.
+// (ap_gemv.hip, ap_dq.hip, ap_plane.hip, ap_stream.hip, ap_wide.hip) only serves the launch it is handed, or returns GQ_ENOTSUP.
 #pragma once
 #include <type_traits>
 
@@ -47,7 +47,7 @@ int gq_with_bits(int bits, F &&f) {
 bool gq_ap_exact_mode();  // gq_set_ap_mode / GQ_AP_EXACT: the fp16-order kernels only
 
 // ---- the kernel files: serve the launch, or GQ_ENOTSUP (shape, bit width, alignment: each checks what its kernels need)
-int gq_ap_dq_try(const ApLaunch &L);          // ap_gemv.hip: decode-to-fp16 on the matrix cores, bits 2..4, M = 1
+int gq_ap_dq_try(const ApLaunch &L);          // ap_dq.hip: decode-to-fp16 on the matrix cores, bits 2..4, M = 1
 int gq_ap_pair_table_try(const ApLaunch &L);  // ap_gemv.hip: the 2-bit LDS pair-table kernel, where GQ_AP_PT asks for it
 int gq_ap_exact_try(const ApLaunch &L);       // ap_gemv.hip: the fp16-order v_perm kernel, bits 2..4
 int gq_ap_generic(const ApLaunch &L);         // ap_gemv.hip: the reference-shaped kernel, plain launches only (the caller checks)

@@ -1,6 +1,6 @@
 // ap_dispatch.hip -- which kernel family serves an Any-Precision GEMV launch: the argument checks, the mode, the route record, the
 // ordered list of "try this family under this condition" (ap_serve; DESIGN.md, "Dispatch order") and the entry points of include/gq_hip.h
-// that are nothing but that.  No GEMV kernel lives here: the families are ap_gemv.hip (exact, pair-table, dq, generic), ap_plane.hip
+// that are nothing but that.  No GEMV kernel lives here: the families are ap_gemv.hip (exact, pair-table, generic), ap_dq.hip (dq), ap_plane.hip
 // (plane, plane-local, plane-chain), ap_stream.hip (stream, stream-ksplit) and ap_wide.hip (wide), behind the entries of ap_dispatch.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,6 +1,8 @@
-// ap_exact.h -- device code shared by the Any-Precision GEMV kernels that keep the reference's fp16 order: the launch arguments, the
-// fused prologues' arithmetic, the natural-order activation staging and the ordered reduction + epilogues.  Included by ap_gemv.hip
-// (ap_gemv_quad_kernel, ap_gemv_pt2_kernel, ap_gemv_dq_kernel) and ap_wide.hip (ap_gemv_wide_kernel, bits 5..8).
+// ap_exact.h -- device code shared by the Any-Precision GEMV kernels that decode with ap_core.h: the launch arguments, the fused
+// prologues (their arithmetic, the RMSNorm statistic, the item loop of the image builders, the natural-order staging), the plane-word
+// and LUT-row request, and the ordered reduction + epilogues with the gate/up pair output.  Each stands here once (DESIGN.md section
+// 3.15; tests/test_csrc_single_definition_cpu.py).  Included by ap_gemv.hip (ap_gemv_quad_kernel, ap_gemv_pt2_kernel), ap_wide.hip
+// (ap_gemv_wide_kernel, bits 5..8) -- the kernels that keep the reference's fp16 order -- and ap_dq.hip (ap_gemv_dq_kernel, fast mode).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,18 +52,154 @@ __device__ __forceinline__ uint4 ld16_nt(const void *p) {
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-// Fused prologues, with the same fp16 rounding points as the reference's separate kernels (ap_gemv.hip::stage_x, stage_x_natural below):
+// Fused prologues, with the same fp16 rounding points as the reference's separate kernels.  Their arithmetic stands here once; the
+// kernels differ only in which 16-byte units a thread takes and where the words go in LDS (stage_items, stage_x_natural below):
 //   PRO_RMSNORM: y = (x.float() * rsqrt(mean(x^2) + eps)).half() * w        (inference/model.py:281-292)
 //   PRO_SILUMUL: y = silu(g) * u with g = x[0:K], u = x[K:2K]                (inference/model.py:266)
 
-__device__ __forceinline__ u32 silu_mul_pk(u32 g, u32 u) {
-    // F.silu on an fp16 tensor evaluates x / (1 + exp(-x)) in fp32 and rounds to fp16; then an fp16 multiply.
+// F.silu on an fp16 value evaluates x / (1 + exp(-x)) in fp32 and rounds to fp16; then an fp16 multiply (the gate/up pair outputs too)
+__device__ __forceinline__ _Float16 silu_pair(_Float16 gate, _Float16 up) {
+    const float gv = (float)gate;
+    return (_Float16)(gv / (1.0f + __expf(-gv))) * up;
+}
+__device__ __forceinline__ u32 silu_mul_pk(u32 g, u32 u) {  // (silu_pair on both halves, spelled out: through it the SiLU * up kernels grow by six s_nop)
     float g0 = h2f(g & 0xFFFF), g1 = h2f(g >> 16);
     _Float16 s0 = (_Float16)(g0 / (1.0f + __expf(-g0)));
     _Float16 s1 = (_Float16)(g1 / (1.0f + __expf(-g1)));
     _Float16 r0 = s0 * __builtin_bit_cast(_Float16, (uint16_t)(u & 0xFFFF));
     _Float16 r1 = s1 * __builtin_bit_cast(_Float16, (uint16_t)(u >> 16));
     return (u32)__builtin_bit_cast(uint16_t, r0) | ((u32)__builtin_bit_cast(uint16_t, r1) << 16);
+}
+// the normalise of a packed fp16 pair: (x.float() * scale).half() * w
+__device__ __forceinline__ u32 norm_pk(u32 x, u32 w, float scale) {
+    const uint16_t a = f2h(gq_pin_f32(h2f(x & 0xFFFF) * scale)), b = f2h(gq_pin_f32(h2f(x >> 16) * scale));
+    const _Float16 ra = __builtin_bit_cast(_Float16, a) * __builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFF));
+    const _Float16 rb = __builtin_bit_cast(_Float16, b) * __builtin_bit_cast(_Float16, (uint16_t)(w >> 16));
+    return (u32)__builtin_bit_cast(uint16_t, ra) | ((u32)__builtin_bit_cast(uint16_t, rb) << 16);
+}
+
+// A staging work item is 32 activations: four 16-byte units.  Item idx = (quad q = idx / 4, sub-item s = idx % 4) starts at activation
+// e0 = Lay::base(G, q, s), and its unit c of a vector p is at Lay::unit(p, e0, c).  The sums of the statistic are fp32 and their order
+// is part of the result, so the partition of the vector into items belongs to the kernel (its layout type):
+//   QuadItems (here): item = (quad idx / 4, byte idx % 4), 64 contiguous bytes -- both exact kernels, so that they normalise with the
+//                     same fp32 statistic bit for bit;
+//   DqImage (ap_dq.hip): item = (quad, word), units 512 bytes apart.
+struct QuadItems {
+    __device__ __forceinline__ static u32 base(const RowGeom &G, u32 q, u32 c) { return G.xindex(q, 0u, c, 0u); }
+    __device__ __forceinline__ static const uint16_t *unit(const uint16_t *p, u32 e0, int v) { return p + e0 + 8 * v; }
+};
+struct FirstItem {  // the activations and norm weights of a thread's first item
+    u32 in[4][4], nw[4][4];
+};
+// The RMSNorm statistic: rsqrt(mean(x^2) + eps) over the stager threads' items (thread tid takes items tid, tid + T, ..), the wave sums
+// exchanged through red[] (>= 16 floats of LDS) behind one barrier.
+// KEEP -- ONE memory round trip (round 5): a stager thread requests the activations AND the norm weights of its first item (4 + 4
+// sixteen-byte loads) up front, takes the sum of squares from those registers, and normalises from them behind the barrier.  The first
+// version read x, reduced, and only then requested x again together with the norm weights -- a layer weight that comes from HBM: two
+// extra round trips, +2.1 us (3 bits) / +3.3 us (4 bits) on the 8B wqkv launch against the plain one (bench.py roofline_by_shape,
+// round 5).  Items beyond the first (K > 16 T) are re-read.
+template <bool KEEP, typename Lay>
+__device__ __forceinline__ float rms_scale(const RowGeom &G, const uint16_t *x, const uint16_t *normw, float eps, float *red,
+                                           bool stager, u32 T, FirstItem *first) {
+    const u32 tid = threadIdx.x, idx0 = stager ? tid : 4u * G.Q;
+    float ss = 0.f;
+    for (u32 idx = idx0; idx < 4u * G.Q; idx += T) {
+        const u32 e0 = Lay::base(G, idx >> 2, idx & 3u);
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+            const uint4 t4 = ld16(Lay::unit(x, e0, v));
+            const u32 w[4] = {t4.x, t4.y, t4.z, t4.w};
+            if constexpr (KEEP) {
+                if (idx == idx0) {
+                    const uint4 n4 = ld16(Lay::unit(normw, e0, v));
+                    first->in[v][0] = t4.x, first->in[v][1] = t4.y, first->in[v][2] = t4.z, first->in[v][3] = t4.w;
+                    first->nw[v][0] = n4.x, first->nw[v][1] = n4.y, first->nw[v][2] = n4.z, first->nw[v][3] = n4.w;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const float a = h2f(w[i] & 0xFFFF), b = h2f(w[i] >> 16);
+                ss += a * a;
+                ss += b * b;
+            }
+        }
+    }
+    ss = wave_allsum(ss);
+    if ((tid & 63u) == 0 && stager) red[tid >> 6] = ss;
+    __syncthreads();
+    // (the stager waves' sums: one LDS round trip + the same register tree, instead of one dependent ds_read per wave)
+    const float tot = wave_allsum((tid & 63u) < (T + 63u) / 64u ? red[tid & 63u] : 0.f);
+    return 1.0f / sqrtf(tot / (float)G.K + eps);
+}
+
+// The item loop of the two image builders (ap_gemv.hip::QuadImage, ap_dq.hip::DqImage): load the item's four units, apply the
+// prologue, and hand the 4 x 4 words to Lay::put, which permutes them into the kernel's LDS image.
+template <int PRO, typename Lay>
+__device__ __forceinline__ void stage_items(const RowGeom &G, const uint16_t *x, const uint16_t *normw, float eps, uint16_t *xlds,
+                                            float *red /* >= 16 floats of LDS */, bool stager, u32 T) {
+    const u32 idx0 = stager ? threadIdx.x : 4u * G.Q;
+    float scale = 0.f;
+    FirstItem first;
+    if constexpr (PRO == PRO_RMSNORM) scale = rms_scale<true, Lay>(G, x, normw, eps, red, stager, T, &first);
+    for (u32 idx = idx0; idx < 4u * G.Q; idx += T) {
+        const u32 q = idx >> 2, s = idx & 3u;
+        const u32 e0 = Lay::base(G, q, s);
+        u32 in[4][4];
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+            if constexpr (PRO == PRO_RMSNORM) {
+                u32 nw[4];
+                if (idx == idx0) {
+#pragma unroll
+                    for (int i = 0; i < 4; i++) in[v][i] = first.in[v][i], nw[i] = first.nw[v][i];
+                } else {
+                    const uint4 t4 = ld16(Lay::unit(x, e0, v)), n4 = ld16(Lay::unit(normw, e0, v));
+                    in[v][0] = t4.x, in[v][1] = t4.y, in[v][2] = t4.z, in[v][3] = t4.w;
+                    nw[0] = n4.x, nw[1] = n4.y, nw[2] = n4.z, nw[3] = n4.w;
+                }
+#pragma unroll
+                for (int i = 0; i < 4; i++) in[v][i] = norm_pk(in[v][i], nw[i], scale);
+            } else {
+                const uint4 t4 = ld16(Lay::unit(x, e0, v));
+                in[v][0] = t4.x, in[v][1] = t4.y, in[v][2] = t4.z, in[v][3] = t4.w;
+                if constexpr (PRO == PRO_SILUMUL) {
+                    const uint4 u4 = ld16(Lay::unit(x + G.K, e0, v));
+                    const u32 uw[4] = {u4.x, u4.y, u4.z, u4.w};
+#pragma unroll
+                    for (int i = 0; i < 4; i++) in[v][i] = silu_mul_pk(in[v][i], uw[i]);
+                }
+            }
+        }
+        Lay::put(G, xlds, q, s, in);
+    }
+}
+
+// The plane words and the LUT row of one (row, quad), requested with raw buffer loads into the caller's registers.  A dead request
+// (!ok: a row past the end, an idle lane) gets an out-of-range offset, which the hardware answers with zeros and no memory traffic: no
+// divergent control flow, and the compiler's vmcnt bookkeeping stays exact.
+template <int BITS>
+__device__ __forceinline__ void request_row(rsrc_t rq, rsrc_t rl, bool ok, u32 row, u32 quad, u32 wpr, u32 plane_bytes, u32x4 (&P)[BITS],
+                                            u32 (&lraw)[(1 << BITS) / 2]) {
+    constexpr int NRAW = (1 << BITS) / 2;
+    constexpr u32 OOB = 0x80000000u;
+    const u32 off = ok ? (row * wpr + 4u * quad) * 4u : OOB;
+#pragma unroll
+    for (int p = 0; p < BITS; p++) P[p] = __builtin_amdgcn_raw_buffer_load_b128(rq, ok ? off + (u32)p * plane_bytes : OOB, 0, 2 /* nt */);
+    const u32 loff = ok ? row * (u32)NRAW * 4u : OOB;
+    if constexpr (NRAW == 2) {
+        auto v = __builtin_amdgcn_raw_buffer_load_b64(rl, loff, 0, 0);
+        lraw[0] = v[0];
+        lraw[1] = v[1];
+    } else {
+#pragma unroll
+        for (int i = 0; i < NRAW; i += 4) {
+            u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rl, ok ? loff + (u32)i * 4u : OOB, 0, 0);
+            lraw[i] = v.x;
+            lraw[i + 1] = v.y;
+            lraw[i + 2] = v.z;
+            lraw[i + 3] = v.w;
+        }
+    }
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -166,8 +304,7 @@ __device__ __forceinline__ void rows_epilogue_n(const RowGeom &G, const ApArgs &
                 auto sw = __builtin_amdgcn_permlane32_swap(yy, yy, false, false);  // sw[1]: lanes 32..63 of y in both halves
                 const uint16_t yo = (uint16_t)sw[1];
                 if (live[e] && t == 0 && !(tid & 32u) && row[e] + 1u < a.N) {
-                    const float gv = (float)__builtin_bit_cast(_Float16, y[e]);
-                    const _Float16 o = (_Float16)(gv / (1.0f + __expf(-gv))) * __builtin_bit_cast(_Float16, yo);
+                    const _Float16 o = silu_pair(__builtin_bit_cast(_Float16, y[e]), __builtin_bit_cast(_Float16, yo));
                     a.out[(size_t)m * (a.N >> 1) + (row[e] >> 1)] = __builtin_bit_cast(uint16_t, o);
                 }
             } else if (live[e] && t == 0 && row[e] < a.N) {
@@ -193,40 +330,15 @@ __device__ __forceinline__ void rows_epilogue(const RowGeom &G, const ApArgs &a,
 }
 
 // ----------------------------------------------------------------------------------------------
-// The activation image in LDS in x's natural order (a lane's 8 activations of (word v, byte c) are 16 contiguous bytes), with the
-// prologues of stage_x (ap_gemv.hip).
+// The activation image in LDS in x's natural order (a lane's 8 activations of (word v, byte c) are 16 contiguous bytes): a flat loop over
+// the 16-byte units, behind the shared statistic in QuadItems' order.
 // ----------------------------------------------------------------------------------------------
 template <int PRO>
 __device__ __forceinline__ void stage_x_natural(const RowGeom &G, const uint16_t *x, const uint16_t *normw, float eps, uint16_t *xlds, float *red,
                                                 bool stager, u32 T) {
-    // 16-byte units (8 activations) per stager thread; same arithmetic and rounding points as stage_x
     const u32 tid = threadIdx.x, nun = G.K / 8u;
     float scale = 0.f;
-    if constexpr (PRO == PRO_RMSNORM) {
-        // (the sum of squares in stage_x's order -- thread idx takes the 32 activations of (quad idx / 4, byte idx % 4) -- so that both
-        // exact kernels normalise with the same fp32 statistic, bit for bit)
-        float ss = 0.f;
-        for (u32 idx = stager ? tid : 4u * G.Q; idx < 4u * G.Q; idx += T) {
-            const u32 e0 = G.xindex(idx >> 2, 0u, idx & 3u, 0u);
-#pragma unroll
-            for (int v = 0; v < 4; v++) {
-                const uint4 t4 = ld16(x + e0 + 8 * v);
-                const u32 w[4] = {t4.x, t4.y, t4.z, t4.w};
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const float a = h2f(w[i] & 0xFFFF), b = h2f(w[i] >> 16);
-                    ss += a * a;
-                    ss += b * b;
-                }
-            }
-        }
-        ss = wave_allsum(ss);
-        if ((tid & 63u) == 0 && stager) red[tid >> 6] = ss;
-        __syncthreads();
-        // (the stager waves' sums: one LDS round trip + the same register tree, instead of one dependent ds_read per wave)
-        const float tot = wave_allsum((tid & 63u) < (T + 63u) / 64u ? red[tid & 63u] : 0.f);
-        scale = 1.0f / sqrtf(tot / (float)G.K + eps);
-    }
+    if constexpr (PRO == PRO_RMSNORM) scale = rms_scale<false, QuadItems>(G, x, normw, eps, red, stager, T, nullptr);
     for (u32 u = stager ? tid : nun; u < nun; u += T) {
         uint4 t4 = ld16(x + 8u * u);
         u32 in[4] = {t4.x, t4.y, t4.z, t4.w};
@@ -234,12 +346,7 @@ __device__ __forceinline__ void stage_x_natural(const RowGeom &G, const uint16_t
             const uint4 n4 = ld16(normw + 8u * u);
             const u32 nw[4] = {n4.x, n4.y, n4.z, n4.w};
 #pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const uint16_t a = f2h(gq_pin_f32(h2f(in[i] & 0xFFFF) * scale)), b = f2h(gq_pin_f32(h2f(in[i] >> 16) * scale));
-                const _Float16 ra = __builtin_bit_cast(_Float16, a) * __builtin_bit_cast(_Float16, (uint16_t)(nw[i] & 0xFFFF));
-                const _Float16 rb = __builtin_bit_cast(_Float16, b) * __builtin_bit_cast(_Float16, (uint16_t)(nw[i] >> 16));
-                in[i] = (u32)__builtin_bit_cast(uint16_t, ra) | ((u32)__builtin_bit_cast(uint16_t, rb) << 16);
-            }
+            for (int i = 0; i < 4; i++) in[i] = norm_pk(in[i], nw[i], scale);
         }
         if constexpr (PRO == PRO_SILUMUL) {
             const uint4 u4 = ld16(x + G.K + 8u * u);

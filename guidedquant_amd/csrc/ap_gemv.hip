@@ -10,6 +10,9 @@
 //   * accumulates in packed fp16 FMAs in EXACTLY the reference's per-lane order, so results are
 //     bit-identical to the CUDA kernel (see ap_core.h and DESIGN.md),
 //   * reduces through LDS in the reference's chunk order + 16/8/4/2/1 tree.
+// Here: the v_perm kernel (ap_gemv_quad_kernel) with its INREG instance, the 2-bit pair-table kernel (ap_gemv_pt2_kernel), the
+// reference-shaped generic kernel, the dequantiser, the exact-order planner and the plan entry points.  What these kernels share with
+// ap_wide.hip and ap_dq.hip is in ap_exact.h; the fast mode's decode-to-fp16 matrix-core kernel is ap_dq.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
@@ -23,91 +26,12 @@ using namespace gq;
 namespace {
 
 // ----------------------------------------------------------------------------------------------
-// Stage the activation vector into LDS in the lane-linear image of ap_core.h::xlds_pos.
-// Work item = (quad q, byte c): 4 virtual lanes x 8 activations = 64 contiguous bytes of x, regrouped with
-// 16 v_perm_b32 into the 4 sixteen-byte slots (c, jj) of quad q.
-// Optional fused prologues, with the same fp16 rounding points as the reference's separate kernels:
-//   PRO_RMSNORM: y = (x.float() * rsqrt(mean(x^2) + eps)).half() * w        (inference/model.py:281-292)
-//   PRO_SILUMUL: y = silu(g) * u with g = x[0:K], u = x[K:2K]                (inference/model.py:266)
+// The activation vector in LDS in the lane-linear image of ap_core.h::xlds_pos, built by ap_exact.h::stage_items (which has the fused
+// prologues).  Work item = (quad q, byte c): 4 virtual lanes x 8 activations = 64 contiguous bytes of x, regrouped with 16 v_perm_b32
+// into the 4 sixteen-byte slots (c, jj) of quad q.
 // ----------------------------------------------------------------------------------------------
-
-template <int PRO>
-__device__ __forceinline__ void stage_x(const RowGeom &G, const uint16_t *x, const uint16_t *normw, float eps,
-                                        uint16_t *xlds, float *red /* >= 16 floats of LDS */, bool stager, u32 T) {
-    const u32 tid = threadIdx.x;
-    float scale = 0.f;
-    // RMSNorm (round 5): ONE memory round trip.  A stager thread requests the activations AND the norm weights of its first item (32
-    // activations: 4 + 4 sixteen-byte loads) up front, takes the sum of squares from those registers, and normalises from them behind
-    // the barrier.  The first version read x, reduced, and only then requested x again together with the norm weights -- a layer
-    // weight that comes from HBM: two extra round trips, +2.1 us (3 bits) / +3.3 us (4 bits) on the 8B wqkv launch against the plain one
-    // (bench.py roofline_by_shape, round 5).  Items beyond the first (K > 16 T) are re-read as before.
-    u32 in0[4][4], nw0[4][4];
-    const u32 idx0 = stager ? tid : 4u * G.Q;
-    if constexpr (PRO == PRO_RMSNORM) {
-        float ss = 0.f;
-        for (u32 idx = idx0; idx < 4u * G.Q; idx += T) {
-            const u32 e0 = G.xindex(idx >> 2, 0u, idx & 3u, 0u);
-#pragma unroll
-            for (int v = 0; v < 4; v++) {
-                const uint4 t4 = ld16(x + e0 + 8 * v);
-                const u32 w[4] = {t4.x, t4.y, t4.z, t4.w};
-                if (idx == idx0) {
-                    const uint4 n4 = ld16(normw + e0 + 8 * v);
-                    in0[v][0] = t4.x, in0[v][1] = t4.y, in0[v][2] = t4.z, in0[v][3] = t4.w;
-                    nw0[v][0] = n4.x, nw0[v][1] = n4.y, nw0[v][2] = n4.z, nw0[v][3] = n4.w;
-                }
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    float a = h2f(w[i] & 0xFFFF), b = h2f(w[i] >> 16);
-                    ss += a * a;
-                    ss += b * b;
-                }
-            }
-        }
-        ss = wave_allsum(ss);
-        if ((tid & 63u) == 0 && stager) red[tid >> 6] = ss;
-        __syncthreads();
-        // (the stager waves' sums: one LDS round trip + the same register tree, instead of one dependent ds_read per wave)
-        const float tot = wave_allsum((tid & 63u) < (T + 63u) / 64u ? red[tid & 63u] : 0.f);
-        scale = 1.0f / sqrtf(tot / (float)G.K + eps);
-    }
-    for (u32 idx = idx0; idx < 4u * G.Q; idx += T) {
-        const u32 q = idx >> 2, c = idx & 3u;
-        const u32 e0 = G.xindex(q, 0u, c, 0u);  // 32 consecutive activations: v = 0..3, j = 0..7
-        u32 in[4][4];
-#pragma unroll
-        for (int v = 0; v < 4; v++) {
-            if constexpr (PRO == PRO_RMSNORM) {
-                u32 nw[4];
-                if (idx == idx0) {
-#pragma unroll
-                    for (int i = 0; i < 4; i++) in[v][i] = in0[v][i], nw[i] = nw0[v][i];
-                } else {
-                    const uint4 t4 = ld16(x + e0 + 8 * v), n4 = ld16(normw + e0 + 8 * v);
-                    in[v][0] = t4.x, in[v][1] = t4.y, in[v][2] = t4.z, in[v][3] = t4.w;
-                    nw[0] = n4.x, nw[1] = n4.y, nw[2] = n4.z, nw[3] = n4.w;
-                }
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    uint16_t a = f2h(gq_pin_f32(h2f(in[v][i] & 0xFFFF) * scale)), b = f2h(gq_pin_f32(h2f(in[v][i] >> 16) * scale));
-                    _Float16 ra = __builtin_bit_cast(_Float16, a) * __builtin_bit_cast(_Float16, (uint16_t)(nw[i] & 0xFFFF));
-                    _Float16 rb = __builtin_bit_cast(_Float16, b) * __builtin_bit_cast(_Float16, (uint16_t)(nw[i] >> 16));
-                    in[v][i] = (u32)__builtin_bit_cast(uint16_t, ra) | ((u32)__builtin_bit_cast(uint16_t, rb) << 16);
-                }
-            } else {
-                uint4 t4 = ld16(x + e0 + 8 * v);
-                in[v][0] = t4.x;
-                in[v][1] = t4.y;
-                in[v][2] = t4.z;
-                in[v][3] = t4.w;
-                if constexpr (PRO == PRO_SILUMUL) {
-                    uint4 u4 = ld16(x + G.K + e0 + 8 * v);
-                    const u32 uw[4] = {u4.x, u4.y, u4.z, u4.w};
-#pragma unroll
-                    for (int i = 0; i < 4; i++) in[v][i] = silu_mul_pk(in[v][i], uw[i]);
-                }
-            }
-        }
+struct QuadImage : QuadItems {
+    __device__ __forceinline__ static void put(const RowGeom &G, uint16_t *xlds, u32 q, u32 c, const u32 (&in)[4][4]) {
 #pragma unroll
         for (u32 mth = 0; mth < 4; mth++) {
             uint4 o;
@@ -118,8 +42,7 @@ __device__ __forceinline__ void stage_x(const RowGeom &G, const uint16_t *x, con
             *reinterpret_cast<uint4 *>(xlds + (((c * 4u + mth) * G.Q + q) << 3)) = o;
         }
     }
-}
-
+};
 
 // ----------------------------------------------------------------------------------------------
 // Fast path: BITS in {2,3,4}, K % 128 == 0, Q = K/128 <= blockDim.x.
@@ -160,9 +83,15 @@ __device__ __forceinline__ uint16_t inreg_reduce_row(u32 s01, u32 s23) {
     return h_add((uint16_t)(pp & 0xFFFFu), (uint16_t)(pp >> 16));                  // t + 1
 }
 
+// Waves per SIMD the instances are compiled for (their amdgpu_waves_per_eu attributes), read by the planner and the plan entry points
+// too: a planner that believed in more resident blocks than the attribute allows cost 8B w2 a second round of blocks.
+// Register budget (tests/test_kernel_resources_cpu.py checks that no instance the dispatcher can pick spills): D = 1 fits 3 waves per
+// SIMD at 2 / 3 bits (<= 168 VGPRs), and the INREG instance 4 at 2 bits, 3 at 4 bits; deeper rings and 4 bits are compiled for 2.
+constexpr int quad_wpe(int bits, int D, bool inreg) { return inreg && bits == 2 ? 4 : ((bits <= 3 || inreg) && D == 1 ? 3 : 2); }
+constexpr int PT2_WPE = 4;  // the pair-table kernel (105 VGPRs)
+
 template <int BITS, int D, int PRO, bool INREG = false>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(INREG && BITS == 2 ? 4 : ((BITS <= 3 || INREG) && D == 1 ? 3 : 2))))
-ap_gemv_quad_kernel(ApArgs a) {
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(quad_wpe(BITS, D, INREG)))) ap_gemv_quad_kernel(ApArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     RowGeom G;
     G.init(a.K);
@@ -190,7 +119,6 @@ ap_gemv_quad_kernel(ApArgs a) {
     if (GQ_STAMPS == 2 && qdbg) qdbg[0] = __builtin_amdgcn_s_memrealtime();
 
     constexpr int NRAW = (1 << BITS) / 2;
-    constexpr u32 OOB = 0x80000000u;
     const u32 plane_bytes = a.N * G.wpr * 4u;
     rsrc_t rq = make_rsrc(a.qw, plane_bytes * (u32)BITS);
     rsrc_t rl = make_rsrc(a.lut, a.N * (u32)NRAW * 4u);
@@ -199,26 +127,7 @@ ap_gemv_quad_kernel(ApArgs a) {
     u32 lraw[D][NRAW];
     auto issue = [&](int d, u32 step) {
         const u32 row = row0 + step * RS + rs;
-        const bool ok = active && step < SPB && row < a.N;
-        const u32 off = ok ? (row * G.wpr + 4u * q) * 4u : OOB;
-#pragma unroll
-        for (int p = 0; p < BITS; p++)
-            P[d][p] = __builtin_amdgcn_raw_buffer_load_b128(rq, ok ? off + (u32)p * plane_bytes : OOB, 0, 2 /* nt */);
-        const u32 loff = ok ? row * (u32)NRAW * 4u : OOB;
-        if constexpr (NRAW == 2) {
-            auto v = __builtin_amdgcn_raw_buffer_load_b64(rl, loff, 0, 0);
-            lraw[d][0] = v[0];
-            lraw[d][1] = v[1];
-        } else {
-#pragma unroll
-            for (int i = 0; i < NRAW; i += 4) {
-                u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rl, ok ? loff + (u32)i * 4u : OOB, 0, 0);
-                lraw[d][i] = v.x;
-                lraw[d][i + 1] = v.y;
-                lraw[d][i + 2] = v.z;
-                lraw[d][i + 3] = v.w;
-            }
-        }
+        request_row<BITS>(rq, rl, active && step < SPB && row < a.N, row, q, G.wpr, plane_bytes, P[d], lraw[d]);
     };
 
     // 1. vector-memory results return in order: waves that stage x must not have plane loads queued in front of
@@ -230,8 +139,8 @@ ap_gemv_quad_kernel(ApArgs a) {
         for (int d = 0; d < D; d++) issue(d, (u32)d);
     }
     // 2. activations -> LDS (lane-linear image) -> 64 VGPRs
-    stage_x<PRO>(G, a.x + (size_t)m * (PRO == PRO_SILUMUL ? 2u * G.K : G.K), a.normw, a.eps, xlds, red, stager,
-                 nw < 2u ? T : (nw / 2u) * 64u);
+    stage_items<PRO, QuadImage>(G, a.x + (size_t)m * (PRO == PRO_SILUMUL ? 2u * G.K : G.K), a.normw, a.eps, xlds, red, stager,
+                     nw < 2u ? T : (nw / 2u) * 64u);
     if (stager) {
 #pragma unroll
         for (int d = 0; d < D; d++) issue(d, (u32)d);
@@ -292,8 +201,7 @@ ap_gemv_quad_kernel(ApArgs a) {
                     const u32 yy = y;
                     auto sw = __builtin_amdgcn_permlane32_swap(yy, yy, false, false);  // sw[1]: lanes 32..63 of y in both halves
                     if (lead && !(tid & 32u) && rvalid && row + 1u < a.N) {
-                        const float gv = (float)__builtin_bit_cast(_Float16, y);
-                        const _Float16 o = (_Float16)(gv / (1.0f + __expf(-gv))) * __builtin_bit_cast(_Float16, (uint16_t)sw[1]);
+                        const _Float16 o = silu_pair(__builtin_bit_cast(_Float16, y), __builtin_bit_cast(_Float16, (uint16_t)sw[1]));
                         a.out[(size_t)m * (a.N >> 1) + (row >> 1)] = __builtin_bit_cast(uint16_t, o);
                     }
                 } else if (lead && rvalid) {
@@ -338,7 +246,7 @@ ap_gemv_quad_kernel(ApArgs a) {
 // ----------------------------------------------------------------------------------------------
 
 template <int PRO>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) ap_gemv_pt2_kernel(ApArgs a) {  // (105 VGPRs)
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(PT2_WPE))) ap_gemv_pt2_kernel(ApArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int BITS = 2, NRAW = 2;
     RowGeom G;
@@ -356,7 +264,6 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) a
     const u32 q = active ? tid - rs * G.Q : 0u;
     // pair tables of this wave: [2 rows of the wave][16 entries] words, behind sv
     u32 *tabs = reinterpret_cast<u32 *>(smem + (((size_t)G.K * 2u + (size_t)SPB * RS * svrow * 2u + 63u) & ~(size_t)63u)) + wv * 32u;
-    constexpr u32 OOB = 0x80000000u;
     const u32 plane_bytes = a.N * G.wpr * 4u;
     rsrc_t rq = make_rsrc(a.qw, plane_bytes * (u32)BITS);
     rsrc_t rl = make_rsrc(a.lut, a.N * (u32)NRAW * 4u);
@@ -364,13 +271,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) a
     u32 lraw[NRAW];
     auto issue = [&](u32 step) {
         const u32 row = row0 + step * RS + rs;
-        const bool ok = active && step < SPB && row < a.N;
-        const u32 off = ok ? (row * G.wpr + 4u * q) * 4u : OOB;
-#pragma unroll
-        for (int p = 0; p < BITS; p++) P[p] = __builtin_amdgcn_raw_buffer_load_b128(rq, ok ? off + (u32)p * plane_bytes : OOB, 0, 2 /* nt */);
-        auto v = __builtin_amdgcn_raw_buffer_load_b64(rl, ok ? row * (u32)NRAW * 4u : OOB, 0, 0);
-        lraw[0] = v[0];
-        lraw[1] = v[1];
+        request_row<BITS>(rq, rl, active && step < SPB && row < a.N, row, q, G.wpr, plane_bytes, P, lraw);
     };
     const u32 nw = T >> 6;
     const bool stager = nw < 2u || wv < nw / 2u;
@@ -445,462 +346,6 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) a
     rows_epilogue(G, a, sv, svrow, SPB * RS, row0, m, tid, T);
 }
 
-// ----------------------------------------------------------------------------------------------
-// Round 6 -- "decode to fp16, accumulate on the matrix cores" (fast mode, 3 and 4 bits, one batch row).
-//
-// The plane-MFMA kernels (ap_plane.hip / ap_stream.hip) multiply 2^b - 1 BINARY matrices per b-bit LUT: 3 at 2 bits, 7 at 3, 15
-// at 4 -- 24 / 56 / 120 FP4 x BF8 MFMAs of 32 cycles per 16 rows x 1024 weights, with ~8 VALU instructions per MFMA to build the
-// operands: at 4 bits ~1,040 instructions per block, instruction-issue-bound at 2.3 x the matrix floor (w1w3 24 us, 0.30 of the
-// HBM roofline).  The decode of the exact kernels (ap_core.h: v_perm_b32 look-ups in the row's LUT held as VGPR byte pools) grows far
-// more slowly with b -- 1.6 / 2.2 / 3.9 VALU operations per weight -- and what it yields, packed fp16 pairs of four weights at one bit
-// position, IS an A fragment of v_mfma_f32_16x16x32_f16: lane (row r = l % 16, quad g = l / 16) holds 8 weights of row r, and the K
-// index of a matrix-core product is only a label -- any 8 weights do, as long as the B fragment of lane (column, g) holds the 8
-// activations that belong to them: one 16-byte slot of an activation image staged in LDS in the decode's own order (the first version
-// used the exact kernels' image, ap_core.h::xlds_pos, and their byte transpose of the quad; the second -- DqItem / stage_x_dqv below --
-// drops the transpose: profiles/r06_dq_kernel.txt).  So:
-//   * A = two look-ups (4 VGPRs), B = one ds_read_b128 of the staged image (column 0 reads it, columns 1..15 read zeros from
-//     outside the block's LDS allocation -- idle columns fed real data cost 8 % in clocks), one MFMA
-//     of 16 cycles per 16 rows x 32 weights: 32 per 16 x 1024 block instead of 56 / 120, no bf8 pieces, no image build, no
-//     extraction of large activations, no Moebius coefficients;
-//   * products of fp16 values are exact in the fp32 accumulator, sums in fp32, one fp16 rounding: the fast-mode envelope
-//     (tests/ap_helpers.py::_check_fast) -- not the reference's fp16 accumulation order (that is the exact mode);
-//   * prologues (RMSNorm, SiLU * up) as stage_x has them, with the reference's rounding points; plain / residual / gate-up pair epilogues.
-// Work: item = (16-row group, unit of 4 quads = 512 weights per row); wave w of a 16-wave block takes items w, w + 16, ..; the
-// K-split partial sums of a row group meet in LDS and are added in unit order (deterministic).
-// ----------------------------------------------------------------------------------------------
-using gqw::f16x8;
-using gqw::f32x4;
-
-template <int BITS>
-struct DqItem;  // run(P, L, emit): emit(v, k, w01 @ 2 k, w23 @ 2 k, w01 @ 2 k + 1, w23 @ 2 k + 1) for word v = 0..3, pair k = 0..3
-// NO byte transpose of the quad (ap_core.h::transpose_quad, 8 v_perm per plane): the exact kernels need it to keep the reference's
-// chain order, a matrix-core product does not care which 8 weights share an operand.  A selector taken from ONE word holds the codes
-// of the same bit position j of its four bytes c = 3, 2, 1, 0 (byte 0 = c 3: pack.py's byte order); the look-up returns
-// w01 = (w[c3], w[c2]), w23 = (w[c1], w[c0]) at that j -- the activation image (stage_x_dqv) keeps the matching order.
-template <>
-struct DqItem<2> {
-    template <typename E>
-    __device__ __forceinline__ static void run(const u32 P[2][4], const LutPools<2> &L, E emit) {
-#pragma unroll
-        for (int v = 0; v < 4; v++) {
-            const u32 Cm = bfi(0xAAAAAAAAu, P[0][v], P[1][v] >> 1), Dm = bfi(0xAAAAAAAAu, P[0][v] << 1, P[1][v]);
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                u32 a01, a23, b01, b23;
-                lookup4<2>(L, (Cm >> (6 - 2 * k)) & 0x03030303u, 0u, a01, a23);
-                lookup4<2>(L, (Dm >> (6 - 2 * k)) & 0x03030303u, 0u, b01, b23);
-                emit(v, k, a01, a23, b01, b23);
-            }
-        }
-    }
-};
-template <>
-struct DqItem<3> {
-    template <typename E>
-    __device__ __forceinline__ static void run(const u32 P[3][4], const LutPools<3> &L, E emit) {
-#pragma unroll
-        for (int v = 0; v < 4; v++) {
-            u32 nib[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) nib[r] = bfi(0x44444444u, shl(P[0][v], 2 - r), bfi(0x22222222u, shl(P[1][v], 1 - r), P[2][v] >> r));
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                u32 w[2][2];
-#pragma unroll
-                for (int par = 0; par < 2; par++) {
-                    const int s = 7 - (2 * k + par);
-                    const u32 S = ((s & 4) ? (nib[s & 3] >> 4) : nib[s & 3]) & 0x07070707u;
-                    lookup4<3>(L, S, 0u, w[par][0], w[par][1]);
-                }
-                emit(v, k, w[0][0], w[0][1], w[1][0], w[1][1]);
-            }
-        }
-    }
-};
-template <>
-struct DqItem<4> {
-    template <typename E>
-    __device__ __forceinline__ static void run(const u32 P[4][4], const LutPools<4> &L, E emit) {
-#pragma unroll
-        for (int v = 0; v < 4; v++) {
-            u32 nib[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) nib[r] = bfi(0x44444444u, shl(P[1][v], 2 - r), bfi(0x22222222u, shl(P[2][v], 1 - r), P[3][v] >> r));
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                u32 w[2][2];
-#pragma unroll
-                for (int par = 0; par < 2; par++) {
-                    const int s = 7 - (2 * k + par);
-                    const u32 S = ((s & 4) ? (nib[s & 3] >> 4) : nib[s & 3]) & 0x07070707u;
-                    // the MSB plane picks the pool: 0x00 / 0xFF per byte as x * 255 = (x << 8) - x (mod 2^32: exact for bytes of 0 / 1) -- two
-                    // VOP2 operations instead of ap_core.h's selector OR + v_perm.  (A 24-bit multiply by 255 is one operation and WRONG: it
-                    // drops byte 3 -- 531 tokens/s and 11 failed tests.)
-                    const u32 mb = (P[0][v] >> s) & 0x01010101u;
-                    const u32 m = (mb << 8) - mb;
-                    const u32 lo = bfi(m, perm(L.lo[3], L.lo[2], S), perm(L.lo[1], L.lo[0], S));
-                    const u32 hi = bfi(m, perm(L.hi[3], L.hi[2], S), perm(L.hi[1], L.hi[0], S));
-                    w[par][0] = perm(hi, lo, 0x05010400u);
-                    w[par][1] = perm(hi, lo, 0x07030602u);
-                }
-                emit(v, k, w[0][0], w[0][1], w[1][0], w[1][1]);
-            }
-        }
-    }
-};
-
-// The activation image of the dq kernel: 16-byte slot (v * 4 + k) * Q + q = the 8 activations that meet the A operand of (quad q,
-// word v, pair k): [x(c3, 2k), x(c2, 2k), x(c1, 2k), x(c0, 2k), x(c3, 2k+1), x(c2, 2k+1), x(c1, 2k+1), x(c0, 2k+1)], x(c, j) =
-// x[G.xindex(q, v, c, j)].  Work item = (quad q, word v): four 16-byte loads (one per byte c), four v_perm per slot.  Prologues as stage_x.
-template <int PRO>
-__device__ __forceinline__ void stage_x_dqv(const RowGeom &G, const uint16_t *x, const uint16_t *normw, float eps, uint16_t *xlds, float *red, bool stager,
-                                            u32 T) {
-    const u32 tid = threadIdx.x;
-    float scale = 0.f;
-    const u32 idx0 = stager ? tid : 4u * G.Q;
-    // (K % 1024 == 0 for this kernel: whole chunks only -- item idx = (quad q = idx / 4, word v = idx % 4) starts at activation
-    // 1024 (q / 8) + 8 (4 (q % 8) + v) = 1024 (idx / 32) + 8 (idx % 32); byte c adds 256)
-    auto xbase = [](u32 idx) -> u32 { return 1024u * (idx >> 5) + 8u * (idx & 31u); };
-    // RMSNorm in ONE memory round trip (as stage_x): the activations AND the norm weights of a thread's first item are requested up front,
-    // the sum of squares is taken from those registers, and they are normalised behind the barrier without being read again
-    u32 in0[4][4], nw0[4][4];
-    if constexpr (PRO == PRO_RMSNORM) {
-        float ss = 0.f;
-        for (u32 idx = idx0; idx < 4u * G.Q; idx += T) {
-#pragma unroll
-            for (u32 c = 0; c < 4; c++) {
-                const u32 e0 = xbase(idx) + 256u * c;
-                const uint4 t4 = ld16(x + e0);
-                const u32 w[4] = {t4.x, t4.y, t4.z, t4.w};
-                if (idx == idx0) {
-                    const uint4 n4 = ld16(normw + e0);
-                    in0[c][0] = t4.x, in0[c][1] = t4.y, in0[c][2] = t4.z, in0[c][3] = t4.w;
-                    nw0[c][0] = n4.x, nw0[c][1] = n4.y, nw0[c][2] = n4.z, nw0[c][3] = n4.w;
-                }
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const float a = h2f(w[i] & 0xFFFF), b = h2f(w[i] >> 16);
-                    ss += a * a;
-                    ss += b * b;
-                }
-            }
-        }
-        ss = wave_allsum(ss);
-        if ((tid & 63u) == 0 && stager) red[tid >> 6] = ss;
-        __syncthreads();
-        // (the stager waves' sums: one LDS round trip + the same register tree, instead of one dependent ds_read per wave)
-        const float tot = wave_allsum((tid & 63u) < (T + 63u) / 64u ? red[tid & 63u] : 0.f);
-        scale = 1.0f / sqrtf(tot / (float)G.K + eps);
-    }
-    for (u32 idx = idx0; idx < 4u * G.Q; idx += T) {
-        const u32 q = idx >> 2, v = idx & 3u;
-        u32 in[4][4];  // [c][k]: (x(c, 2k), x(c, 2k+1))
-#pragma unroll
-        for (u32 c = 0; c < 4; c++) {
-            const u32 e0 = xbase(idx) + 256u * c;
-            if constexpr (PRO == PRO_RMSNORM) {
-                u32 nw[4];
-                if (idx == idx0) {
-#pragma unroll
-                    for (int i = 0; i < 4; i++) in[c][i] = in0[c][i], nw[i] = nw0[c][i];
-                } else {
-                    const uint4 t4 = ld16(x + e0), n4 = ld16(normw + e0);
-                    in[c][0] = t4.x, in[c][1] = t4.y, in[c][2] = t4.z, in[c][3] = t4.w;
-                    nw[0] = n4.x, nw[1] = n4.y, nw[2] = n4.z, nw[3] = n4.w;
-                }
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const uint16_t a = f2h(gq_pin_f32(h2f(in[c][i] & 0xFFFF) * scale)), b = f2h(gq_pin_f32(h2f(in[c][i] >> 16) * scale));
-                    const _Float16 ra = __builtin_bit_cast(_Float16, a) * __builtin_bit_cast(_Float16, (uint16_t)(nw[i] & 0xFFFF));
-                    const _Float16 rb = __builtin_bit_cast(_Float16, b) * __builtin_bit_cast(_Float16, (uint16_t)(nw[i] >> 16));
-                    in[c][i] = (u32)__builtin_bit_cast(uint16_t, ra) | ((u32)__builtin_bit_cast(uint16_t, rb) << 16);
-                }
-            } else {
-                const uint4 t4 = ld16(x + e0);
-                in[c][0] = t4.x, in[c][1] = t4.y, in[c][2] = t4.z, in[c][3] = t4.w;
-                if constexpr (PRO == PRO_SILUMUL) {
-                    const uint4 u4 = ld16(x + G.K + e0);
-                    const u32 uw[4] = {u4.x, u4.y, u4.z, u4.w};
-#pragma unroll
-                    for (int i = 0; i < 4; i++) in[c][i] = silu_mul_pk(in[c][i], uw[i]);
-                }
-            }
-        }
-#pragma unroll
-        for (u32 k = 0; k < 4; k++) {
-            uint4 o;
-            o.x = perm(in[2][k], in[3][k], 0x05040100u);  // (x(c3, 2k), x(c2, 2k))
-            o.y = perm(in[0][k], in[1][k], 0x05040100u);  // (x(c1, 2k), x(c0, 2k))
-            o.z = perm(in[2][k], in[3][k], 0x07060302u);  // (x(c3, 2k+1), x(c2, 2k+1))
-            o.w = perm(in[0][k], in[1][k], 0x07060302u);  // (x(c1, 2k+1), x(c0, 2k+1))
-            *reinterpret_cast<uint4 *>(xlds + (((v * 4u + k) * G.Q + q) << 3)) = o;
-        }
-    }
-}
-
-struct DqArgs {
-    ApArgs a;
-    u32 RGB;      // 16-row groups per block
-    u32 NU;       // units (512 weights) per row
-    u32 part_off; // LDS offset of the partial sums
-    unsigned long long *dbg;  // GQ_STAMPS builds: the debug buffer of gq_debug_set_timing_buffer
-};
-#ifndef DQ_WAVES_N
-#define DQ_WAVES_N 16
-#endif
-constexpr u32 DQ_WAVES = DQ_WAVES_N;
-// (also measured slower, round 6: two or three items' plane words in flight per wave with ONE copy of the decode -- slots moved into work
-// registers behind explicit s_waitcnt vmcnt(n), re-requested 2 / 3 items ahead: w1w3 3-bit 18.0 / 19.6 vs 15.7 us, 4-bit 26.3 / 40.9 vs 23.0.
-// More plane words in flight do not help this kernel: issuing a load blocks the wave once the CU's memory pipe is full.)
-// ring depth 1: the next item's plane words are requested while this one is decoded.  Deeper rings measured SLOWER (w1w3 3-bit 15.5 /
-// 17.4 / 19.1 us, 4-bit 22.9 / 25.2 / 27.7 us at depth 1 / 2 / 3, profiles/r06_dq_kernel.txt): the unrolled decode of one item is
-// ~600 instructions (5 KB) already, and every slot of a ring is another copy of it in the instruction cache
-#ifndef DQ_RING
-#define DQ_RING 1
-#endif
-#ifndef DQ_KO
-#define DQ_KO 0  // build-time knock-outs, WRONG numerics, timing only (bit mask): 1 no B reads, 2 no MFMAs, 4 no plane loads
-#endif
-// occupancy the instances are compiled for (waves per SIMD): the decode is a dependent chain (transpose -> selectors -> look-ups ->
-// MFMA), so more resident waves = fewer idle issue slots
-// (measured: ONE 16-wave block per CU is the fastest form -- 8-wave blocks at 3 / 4 per CU, <= 64 / 80 VGPRs: w1w3 3-bit 17.6 vs 16.3 us,
-// 4-bit 26.9 vs 22.9, and their RMSNorm instances spill; profiles/r06_dq_kernel.txt)
-#ifndef DQ_WPE3
-#define DQ_WPE3 4
-#endif
-#ifndef DQ_WPE4
-#define DQ_WPE4 4
-#endif
-template <int BITS>
-constexpr int dq_wpe() { return BITS <= 3 ? DQ_WPE3 : DQ_WPE4; }
-
-// QT: quads per row compiled in (32: K = 4096, 112: K = 14336 -- the 8B widths; 0: read from the launch): the sixteen B-fragment
-// addresses of an item are then immediate offsets of ONE base register instead of sixteen v_add (7 % of the 3-bit item's VALU)
-template <int BITS, int PRO, int QT>
-__global__ void __launch_bounds__(64 * DQ_WAVES) __attribute__((amdgpu_waves_per_eu(dq_wpe<BITS>()))) ap_gemv_dq_kernel(DqArgs da) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const ApArgs &a = da.a;
-    RowGeom G;
-    G.init(a.K);
-    uint16_t *xlds = reinterpret_cast<uint16_t *>(smem);
-    float *part = reinterpret_cast<float *>(smem + da.part_off);
-    float *red = part;  // (RMSNorm reduction scratch: before the partial sums exist)
-    const u32 tid = threadIdx.x, l = tid & 63u, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const u32 r = l & 15u, g = l >> 4;
-    const u32 rg0 = blockIdx.x * da.RGB, NU = da.NU;
-    const u32 RGt = (a.N + 15u) >> 4;
-    const u32 rgb = min(da.RGB, RGt - rg0);  // row groups of this block
-    const u32 nitems = rgb * NU;
-    constexpr int NRAW = (1 << BITS) / 2;
-    constexpr u32 OOB = 0x80000000u;
-    const u32 plane_bytes = a.N * G.wpr * 4u;
-    rsrc_t rq = make_rsrc(a.qw, plane_bytes * (u32)BITS);
-    rsrc_t rl = make_rsrc(a.lut, a.N * (u32)NRAW * 4u);
-    constexpr int D = DQ_RING;
-    u32x4 P[D][BITS];
-    u32 lraw[D][NRAW];
-    // (item it = (row group rgl, unit u) = (it / NU, it % NU): the loop below carries the pair along -- an integer division is ~30
-    // instructions on this chip, and NU = 28 for the 14336-wide rows)
-    auto issue = [&](int d, u32 it, u32 rgl, u32 u) {
-        const u32 row = (rg0 + rgl) * 16u + r;
-        const bool ok = it < nitems && row < a.N && !(DQ_KO & 4);  // (knock-out 4: no plane loads)
-        const u32 off = ok ? (row * G.wpr + 4u * (4u * u + g)) * 4u : OOB;
-#pragma unroll
-        for (int p = 0; p < BITS; p++) P[d][p] = __builtin_amdgcn_raw_buffer_load_b128(rq, ok ? off + (u32)p * plane_bytes : OOB, 0, 2 /* nt */);
-        const u32 loff = ok ? row * (u32)NRAW * 4u : OOB;
-        if constexpr (NRAW == 2) {
-            auto v = __builtin_amdgcn_raw_buffer_load_b64(rl, loff, 0, 0);
-            lraw[d][0] = v[0];
-            lraw[d][1] = v[1];
-        } else {
-#pragma unroll
-            for (int i = 0; i < NRAW; i += 4) {
-                u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rl, ok ? loff + (u32)i * 4u : OOB, 0, 0);
-                lraw[d][i] = v.x;
-                lraw[d][i + 1] = v.y;
-                lraw[d][i + 2] = v.z;
-                lraw[d][i + 3] = v.w;
-            }
-        }
-    };
-    auto first_requests = [&]() {
-#pragma unroll
-        for (int d = 0; d < D; d++) {
-            const u32 it = w + (u32)d * DQ_WAVES;
-            issue(d, it, it / NU, it % NU);
-        }
-    };
-    // the waves that stage x (the lower half) request their first items behind the activations, the others at once (the CU's
-    // memory pipe serves requests in order)
-    const bool stager = DQ_WAVES < 2u || w < DQ_WAVES / 2u;
-    if (!stager) first_requests();
-    stage_x_dqv<PRO>(G, a.x, a.normw, a.eps, xlds, red, stager, (DQ_WAVES < 2u ? 1u : DQ_WAVES / 2u) * 64u);
-    if (stager) first_requests();
-    __syncthreads();
-    // B fragments: column 0 reads the image, the other columns read zeros from beyond the block's LDS allocation (192 KiB up)
-    const u32 Q = QT ? (u32)QT : G.Q;
-    auto decode_item = [&](u32 it, u32 u, const u32 (&Pw)[BITS][4], const u32 (&lw)[NRAW]) {
-        LutPools<BITS> L;
-        L.build(lw);
-        const u32 q = 4u * u + g;
-        const unsigned char *bb = r == 0u ? reinterpret_cast<const unsigned char *>(xlds) + (size_t)q * 16u
-                                          : reinterpret_cast<const unsigned char *>(smem) + 0x30000u;
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        DqItem<BITS>::run(Pw, L, [&](int v, int jj, u32 a01, u32 a23, u32 b01, u32 b23) {
-            const u32x4 av = {a01, a23, b01, b23};
-#if DQ_KO & 1  // (timing knock-out, WRONG numerics: no B reads)
-            const u32x4 bvv = {(u32)v, (u32)jj, q, Q};
-#else
-            const uint4 bv = *reinterpret_cast<const uint4 *>(bb + (size_t)((u32)(v * 4 + jj) * Q) * 16u);
-            const u32x4 bvv = {bv.x, bv.y, bv.z, bv.w};
-#endif
-#if DQ_KO & 2  // (no MFMAs)
-            acc0[0] += __builtin_bit_cast(float, av[0] ^ av[1] ^ av[2] ^ av[3] ^ bvv[0]);
-#else
-            if (jj & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, av), __builtin_bit_cast(f16x8, bvv), acc1, 0, 0, 0);
-            else acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, av), __builtin_bit_cast(f16x8, bvv), acc0, 0, 0, 0);
-#endif
-        });
-        // D[row 4 g + e][column r]: column 0 holds the sums
-        if (r == 0u) *reinterpret_cast<f32x4 *>(part + (size_t)it * 16u + 4u * g) = acc0 + acc1;
-    };
-    // (GQ_STAMPS builds: s_memrealtime per wave of the middle block -- kernel start, then per item {top, plane words in hand, next item
-    // requested, decoded}: tools/r6/dq_stamps.py)
-    unsigned long long *dqdbg = (GQ_STAMPS && da.dbg && blockIdx.x == gridDim.x / 2u && l == 0u) ? da.dbg + (size_t)w * 32u : nullptr;
-    u32 nst = 0;
-    auto dstamp = [&]() {
-        if (GQ_STAMPS && dqdbg && nst < 32u) dqdbg[nst++] = __builtin_amdgcn_s_memrealtime();
-    };
-    dstamp();
-    static_assert(D == 1, "the (row group, unit) pair of an item is carried for ring depth 1");
-    const u32 step_rg = DQ_WAVES / NU, step_u = DQ_WAVES - step_rg * NU;  // one division per launch
-    u32 c_rg = w / NU, c_u = w - c_rg * NU;                                 // (row group, unit) of the item being decoded
-    u32 n_rg = c_rg + step_rg, n_u = c_u + step_u;                           // .. and of the one being requested
-    if (n_u >= NU) n_u -= NU, n_rg++;
-    for (u32 it0 = w; it0 < nitems; it0 += (u32)D * DQ_WAVES) {
-#pragma unroll
-        for (int d = 0; d < D; d++) {
-            const u32 it = it0 + (u32)d * DQ_WAVES;
-            dstamp();
-            u32 Pw[BITS][4];
-#pragma unroll
-            for (int p = 0; p < BITS; p++) {
-                Pw[p][0] = P[d][p].x;
-                Pw[p][1] = P[d][p].y;
-                Pw[p][2] = P[d][p].z;
-                Pw[p][3] = P[d][p].w;
-            }
-            u32 lw[NRAW];
-#pragma unroll
-            for (int i = 0; i < NRAW; i++) lw[i] = lraw[d][i];
-            if (GQ_STAMPS) {
-#pragma unroll
-                for (int p = 0; p < BITS; p++) asm volatile("" : "+v"(Pw[p][0]), "+v"(Pw[p][3]));  // (the wait for the plane words sits here)
-                dstamp();
-            }
-            issue(d, it + (u32)D * DQ_WAVES, n_rg, n_u);
-            if (GQ_STAMPS) dstamp();
-            const u32 u_now = c_u;
-            c_rg = n_rg, c_u = n_u;
-            n_rg += step_rg, n_u += step_u;
-            if (n_u >= NU) n_u -= NU, n_rg++;
-            if (it >= nitems) continue;  // (wave-uniform)
-            decode_item(it, u_now, Pw, lw);
-            if (GQ_STAMPS) dstamp();
-        }
-    }
-    __syncthreads();
-    // ordered K-split sum + epilogue: one thread per row of the block.  The residual is requested BEFORE the sums are read, and the
-    // partial sums of eight units come in one LDS round trip (added in unit order as before): with one dependent ds_read per unit and the
-    // residual behind the sum, the tail of a w2 launch (28 units) was 28 LDS round trips + one memory round trip long.
-    const bool pairs = (a.epilogue & GQ_EPI_SILU_PAIRS) != 0u;
-    for (u32 rl = tid; rl < rgb * 16u; rl += 64u * DQ_WAVES) {
-        const u32 row = rg0 * 16u + rl;
-        uint16_t res = 0;
-        if (!pairs && a.resid && row < a.N) res = a.resid[row];
-        const float *pp = part + (size_t)(rl >> 4) * NU * 16u + (rl & 15u);
-        float y = 0.f;
-        u32 u = 0;
-        for (; u + 8u <= NU; u += 8u) {
-            float v[8];
-#pragma unroll
-            for (u32 j = 0; j < 8u; j++) v[j] = pp[(size_t)(u + j) * 16u];
-#pragma unroll
-            for (u32 j = 0; j < 8u; j++) y += v[j];
-        }
-        for (; u < NU; u++) y += pp[(size_t)u * 16u];
-        _Float16 yh = (_Float16)y;
-        if (pairs) {
-            // rows (2 i, 2 i + 1) = (gate_i, up_i): F.silu(gate) * up on fp16 values (inference/model.py:266), written to out[i]
-            const uint16_t yo = (uint16_t)__builtin_amdgcn_update_dpp(0, (int)__builtin_bit_cast(uint16_t, yh), 0xB1, 0xF, 0xF, true);  // lane ^ 1
-            if (!(rl & 1u) && row + 1u < a.N) {
-                const float gv = (float)yh;
-                const _Float16 o = (_Float16)(gv / (1.0f + __expf(-gv))) * __builtin_bit_cast(_Float16, yo);
-                gq_store_wt(a.out + (row >> 1), __builtin_bit_cast(uint16_t, o));
-            }
-        } else if (row < a.N) {
-            if (a.resid) yh = __builtin_bit_cast(_Float16, res) + yh;
-            gq_store_wt(a.out + row, __builtin_bit_cast(uint16_t, yh));
-        }
-    }
-}
-
-struct DqCfg {
-    u32 grid, RGB, NU, part_off;
-    size_t smem;
-};
-bool pick_dq_cfg(u32 N, u32 K, int bits, DqCfg &c) {
-    if (bits < 2 || bits > 4 || K % 1024u || K > 32768u || N < 16u) return false;
-    const u32 RGt = (N + 15u) / 16u, cus = (u32)gq_cu_count();
-    c.NU = K / 512u;
-    // blocks per CU the instance's occupancy allows (waves per SIMD x 4 SIMDs / waves per block)
-    u32 bpc = (u32)gq_env_int("GQ_DQ_BPC", 0);
-    if (!bpc) bpc = (u32)(bits <= 3 ? DQ_WPE3 : DQ_WPE4) * 4u / DQ_WAVES;
-    if (bpc < 1u) bpc = 1u;
-    c.RGB = (RGt + cus * bpc - 1u) / (cus * bpc);
-    c.grid = (RGt + c.RGB - 1u) / c.RGB;
-    c.part_off = (K * 2u + 255u) / 256u * 256u;
-    c.smem = (size_t)c.part_off + (size_t)c.RGB * c.NU * 64u + 64u;
-    return c.smem <= 150u * 1024u;
-}
-template <int BITS, int PRO, int QT>
-int launch_dq_q(const DqArgs &da, const DqCfg &c, hipStream_t s) {
-    if (gq_ap_route(GQ_AP_ROUTE_DQ, 1u)) return GQ_OK;
-    static GqPerDeviceOnce once;
-    auto kern = ap_gemv_dq_kernel<BITS, PRO, QT>;
-    GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(kern), (int)(160u * 1024u)));
-    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(64u * DQ_WAVES), c.smem, s, da);
-    GQ_HIP_CHECK(hipGetLastError());
-    return GQ_OK;
-}
-template <int BITS, int PRO>
-int launch_dq_inst(const DqArgs &da, const DqCfg &c, hipStream_t s) {
-    switch (da.a.K) {
-        case 4096u: return launch_dq_q<BITS, PRO, 32>(da, c, s);
-        case 14336u: return launch_dq_q<BITS, PRO, 112>(da, c, s);
-        default: return launch_dq_q<BITS, PRO, 0>(da, c, s);
-    }
-}
-template <int BITS>
-int launch_dq(const DqArgs &da, const DqCfg &c, int pro, hipStream_t s) {
-    switch (pro) {
-        case PRO_RMSNORM: return launch_dq_inst<BITS, PRO_RMSNORM>(da, c, s);
-        case PRO_SILUMUL: return launch_dq_inst<BITS, PRO_SILUMUL>(da, c, s);
-        default: return launch_dq_inst<BITS, PRO_NONE>(da, c, s);
-    }
-}
-}  // namespace
-// GQ_ENOTSUP when the shape is not served (the caller goes on to the plane / exact kernels)
-int gq_ap_dq_try(const ApLaunch &L) {
-    DqCfg c;
-    if (L.M != 1u || !pick_dq_cfg(L.N, L.K, L.bits, c)) return GQ_ENOTSUP;
-    if (L.qbytes() >= 0x7FFFFFFFull) return GQ_ENOTSUP;
-    if (L.unaligned16()) return GQ_ENOTSUP;
-    if (L.pairs && (L.N & 1u)) return GQ_ENOTSUP;
-    DqArgs da{ap_args(L, 0u, 0u), c.RGB, c.NU, c.part_off, GQ_STAMPS ? gq_debug_timing_buffer() : nullptr};
-    return gq_with_bits<2, 4>(L.bits, [&](auto B) { return launch_dq<B()>(da, c, L.pro, L.stream); });
-}
-namespace {
 
 // ----------------------------------------------------------------------------------------------
 // Generic path: any 2 <= BITS <= 8, any K % 32 == 0.  32 lanes per row exactly like the reference warp
@@ -1022,14 +467,15 @@ __global__ void __launch_bounds__(256) ap_dequant_kernel(const u32 *qw, const ui
 // ----------------------------------------------------------------------------------------------
 // Launchers
 // ----------------------------------------------------------------------------------------------
-#ifndef GQ_AP_PT_DEFAULT
-#define GQ_AP_PT_DEFAULT 0  // exact mode, 2 bits: the LDS pair-table kernel (ap_gemv_pt2_kernel) instead of the v_perm kernel: 1 long rows, 2 all
-#endif
 struct QuadCfg {
     u32 T, RS, SPB, D, grid;
     size_t smem;
 };
 
+// the shapes the INREG instance serves: rows of 4096 weights (a row is one half of a wave) at ring depth 1
+bool inreg_shape(u32 K, const QuadCfg &c) { return c.D == 1u && K == 4096u && c.T % 64u == 0u && c.RS * 32u == c.T; }
+// .. and whether a launch on the plan takes it
+bool inreg_plan(u32 K, const QuadCfg &c) { return inreg_shape(K, c) && gq_env_int("GQ_AP_INREG", 1) != 0; }
 
 // `pt2`: the configuration is for the 2-bit pair-table kernel (4 waves per SIMD); `pairs`: the launch has the SiLU-pairs epilogue
 bool pick_quad_cfg(u32 N, u32 K, int bits, QuadCfg &c, int pro = PRO_NONE, bool pt2 = false, bool pairs = false) {
@@ -1058,9 +504,8 @@ bool pick_quad_cfg(u32 N, u32 K, int bits, QuadCfg &c, int pro = PRO_NONE, bool 
     c.T = bestT;
     c.RS = bestT / Q;
     const u32 steps = (N + c.RS - 1) / c.RS;
-    // ring depth D (steps of plane words + LUT row in flight per lane).  Register budget (tests/test_kernel_resources_cpu.py checks that
-    // no instance the dispatcher can pick spills): D = 1 fits 3 waves per SIMD at 2 / 3 bits (<= 168 VGPRs); deeper rings and 4 bits are
-    // compiled for 2 waves per SIMD (256 VGPRs), where 4 bits fits D <= 3
+    // ring depth D (steps of plane words + LUT row in flight per lane): the register budget is quad_wpe's; at 2 waves per SIMD (256
+    // VGPRs) 4 bits fits D <= 3
     int d = gq_env_int("GQ_AP_D", 0);
     if (d < 1 || d > 4) d = bits <= 3 ? 1 : 2;
     if (bits == 4 && d > 3) d = 3;
@@ -1073,9 +518,11 @@ bool pick_quad_cfg(u32 N, u32 K, int bits, QuadCfg &c, int pro = PRO_NONE, bool 
     if (pro == PRO_RMSNORM && steps <= cus * bpc_def) bpc_def = 1u;
     // never more blocks per CU than the instance's occupancy holds at once (round 6, per-block start stamps: 8B w2 in exact mode, 512-thread
     // blocks of a 3-waves-per-SIMD kernel = ONE resident block per CU, was launched as 512 blocks -- two rounds of 5 us each;
-    // profiles/r06_exact_epilogue.txt).  Waves per SIMD: the kernels' amdgpu_waves_per_eu attributes.
-    const bool inreg = !pt2 && d == 1 && K == 4096u && c.T % 64u == 0u && c.RS * 32u == c.T;
-    const u32 wpe = pt2 ? 4u : (inreg ? (bits == 2 ? 4u : 3u) : (bits <= 3 && d == 1 ? 3u : 2u));
+    // profiles/r06_exact_epilogue.txt).
+    // (Known quirk, kept: the cap takes the INREG instance's occupancy from the shape alone -- under GQ_AP_INREG=0 the launch goes to the
+    // plain instance, which at 2 bits holds 3 waves per SIMD, not 4.  tests/golden/exact_plans.json pins the plans as they are.)
+    c.D = (u32)d;  // (the depth asked for: capped by SPB below)
+    const u32 wpe = pt2 ? (u32)PT2_WPE : (u32)quad_wpe(bits, d, inreg_shape(K, c));
     const u32 bpc_max = std::max(1u, wpe * 4u / ((c.T + 63u) / 64u));
     if (bpc_def > bpc_max) bpc_def = bpc_max;
     u32 bpc = (u32)gq_env_int("GQ_AP_BPC", (int)bpc_def);
@@ -1103,9 +550,6 @@ bool pick_quad_cfg(u32 N, u32 K, int bits, QuadCfg &c, int pro = PRO_NONE, bool 
     c.smem = smem_for(spb);
     return true;
 }
-
-// rows of 4096 weights at ring depth 1: the instance with the ordered reduction in registers (INREG above)
-bool inreg_plan(u32 K, const QuadCfg &c) { return c.D == 1u && K == 4096u && c.T % 64u == 0u && c.RS * 32u == c.T && gq_env_int("GQ_AP_INREG", 1) != 0; }
 
 template <int BITS, int D, int PRO>
 int launch_quad_inst(const ApArgs &a, const QuadCfg &c, u32 M, hipStream_t s) {
@@ -1156,7 +600,7 @@ int launch_quad(const ApArgs &a, const QuadCfg &c, u32 M, int pro, hipStream_t s
 
 // the 2-bit pair-table kernel: asked for by GQ_AP_PT (0 never -- the default --, 1 rows of >= 8192 weights, 2 every shape it serves)
 bool pt2_wanted(int bits, u32 K) {
-    const int pt = gq_env_int("GQ_AP_PT", GQ_AP_PT_DEFAULT);
+    const int pt = gq_env_int("GQ_AP_PT", 0);
     return bits == 2 && (pt >= 2 || (pt == 1 && K >= 8192u));
 }
 size_t pt2_smem(u32 K, const QuadCfg &c) {
@@ -1183,8 +627,7 @@ extern "C" int gq_debug_exact_plan_ex(uint32_t N, uint32_t K, int bits, int prol
     QuadCfg c;
     u32 kernel = 0;
     if (!plan || bits < 2 || bits > 4 || !exact_plan(N, K, bits, prologue, (epilogue & GQ_EPI_SILU_PAIRS) != 0, c, kernel)) return GQ_ENOTSUP;
-    // (the kernels' amdgpu_waves_per_eu attributes)
-    const u32 wpe = kernel == 2u ? 4u : (kernel == 1u ? (bits == 2 ? 4u : 3u) : (bits <= 3 && c.D == 1u ? 3u : 2u));
+    const u32 wpe = kernel == 2u ? (u32)PT2_WPE : (u32)quad_wpe(bits, (int)c.D, kernel == 1u);
     plan[0] = c.T, plan[1] = c.RS, plan[2] = c.SPB, plan[3] = c.D, plan[4] = c.grid, plan[5] = std::max(1u, wpe * 4u / ((c.T + 63u) / 64u));
     plan[6] = kernel;
     return GQ_OK;

@@ -11,7 +11,7 @@
 // So every result is bit-identical to ap_gemv_generic_kernel, which served these widths before (GQ_AP_FORCE_GENERIC=1 still picks it).
 //
 // Code formation: a selector word S[s] of one plane word set holds in byte (3 - c) the code of the weight at bit s of byte c (the
-// DqItem trick of ap_gemv.hip: no byte transpose), built with one shift + one and-or per plane; below 8 bits the code is formed
+// DqItem trick of ap_dq.hip: no byte transpose), built with one shift + one and-or per plane; below 8 bits the code is formed
 // already doubled (the byte offset of its fp16 entry), so one v_perm with the table's 256-aligned base is the LDS address.
 #include <hip/hip_runtime.h>
 #include <stdint.h>

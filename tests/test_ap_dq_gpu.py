@@ -1,4 +1,4 @@
-"""GPU: the decode-to-fp16 matrix-core GEMV (csrc/ap_gemv.hip::ap_gemv_dq_kernel, round 6; the fast mode's 4-bit kernel for the large
+"""GPU: the decode-to-fp16 matrix-core GEMV (csrc/ap_dq.hip::ap_gemv_dq_kernel, round 6; the fast mode's 4-bit kernel for the large
 matrices, replaces anyprec.cu:372-542 for M = 1) -- exact fp16 x fp16 products, fp32 accumulation, one fp16 rounding: the fast-mode
 envelope against the oracle's fp64 product (ap_helpers._check_fast: never farther from the reference-order result than the correctly
 rounded exact result, + 2 ulp), and the fused prologues / epilogues against the reference's rounding points (inference/model.py:259-
@@ -42,7 +42,7 @@ def _rows(rng, N, n=48):
 
 
 # 8B wqkv / wo / w1w3 / w2, a 1B width, a 70B width, ragged row counts (the last 16-row group partly / almost empty), the 70B down
-# projection's width (more staging items than staging threads: the re-read path of stage_x_dqv), and the 70B w1w3 / wo / w2 grids the
+# projection's width (more staging items than staging threads: the re-read path of the staging loop, ap_exact.h::stage_items), and the 70B w1w3 / wo / w2 grids the
 # default dispatch sends here at 3 / 4 bits (tests/dispatch_table.py)
 SHAPES = [(6144, 4096), (4096, 4096), (28672, 4096), (4096, 14336), (3072, 2048), (10240, 8192), (1000, 4096), (4097, 1024), (520, 28672),
           (57344, 8192), (8192, 8192), (8192, 28672)]

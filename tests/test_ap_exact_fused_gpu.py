@@ -223,7 +223,7 @@ def test_fused_forms_match_the_reference_chain(N, K, bits):
 @pytest.mark.parametrize("bits", [2, 3, 4])
 def test_rmsnorm_prologue_rereads_items_on_long_rows(bits):
     """520 x 28672 with RMSNorm: K = 28672 is more than 16 x the stager threads' 32-activation items, so items beyond a thread's
-    first are read again behind the statistic (stage_x); the residual epilogue behind it"""
+    first are read again behind the statistic (ap_exact.h::stage_items); the residual epilogue behind it"""
     N, K = 520, 28672
     rng = np.random.default_rng(bits)
     q, lut = _layer(N, K, bits, seed=bits + 11)

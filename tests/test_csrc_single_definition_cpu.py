@@ -1,6 +1,7 @@
 """CPU: a source scan of guidedquant_amd/csrc -- the device helpers the kernel files share are defined ONCE (wave_util.h: casts,
 reductions, descriptors, the asm vector-memory requests; plane_mfma.h: the pieces of the plane arithmetic; qtip_xform.h: the element-wise
-arithmetic of the QTIP transform-in / transform-out), under names that tell their contracts apart, and the settled build-time forks are gone.  A second copy under the same name is how wave_reduce<true> came
+arithmetic of the QTIP transform-in / transform-out; ap_exact.h: the fused prologues, the row request and the ordered reduction of the
+exact / wide / dq GEMV kernels), under names that tell their contracts apart, and the settled build-time forks are gone.  A second copy under the same name is how wave_reduce<true> came
 to mean two things (identity 0 in one file, -3e38 in another)."""
 import glob
 import os
@@ -24,6 +25,9 @@ DEVICE_FUNCTIONS = {
     "plane_mfma.h": ["mfma_f4_bf8", "bf8_split", "hot_tau_bits", "silu_mul2"],
     "qtip_xform.h": ["h16_of", "sum_parts", "sum_parts4", "xf_out", "xf_resid", "xf_in", "xf_in_unit", "xf_in_h16", "xf_in_pack",  # the elements
                      "ssq_unit", "block_rms_scale", "seg_load", "seg_signed_sum", "qtip_transform_out"],
+    # the fused prologues, the row request and the ordered reduction of the exact / wide / dq GEMV kernels
+    "ap_exact.h": ["silu_mul_pk", "norm_pk", "rms_scale", "stage_items", "request_row", "silu_pair", "reduce_tree", "rows_epilogue_n",
+                   "stage_x_natural"],
 }
 OTHER_DEFINITIONS = {  # pattern -> the one file
     r"^\s*struct HotEnt\b": "plane_mfma.h",
@@ -35,7 +39,9 @@ RETIRED = ["wave_reduce", "gq_wave_allsum", "GQ_ST_HOT_T", "g_dma16", "g_load16"
 # build-time forks that were decided and taken out (DESIGN.md sections 3.5 - 3.7 keep the verdicts)
 REMOVED_FORKS = ["PL_SSQ_MODE", "PL_BOOB", "PL_LOOB", "ST_DPPIMG", "ST_TAU_SCALE", "ST_MAINPRIO", "ST_AUX",
                  # qtip.hip's, and the helpers nothing called
-                 "QT_ABL", "QT_SB", "QT_XOOB", "QT_PF", "QT_ENGINE_STAMPS", "unit_of", "qtip_xpos", "QtipNoop", "qtip_sum_parts"]
+                 "QT_ABL", "QT_SB", "QT_XOOB", "QT_PF", "QT_ENGINE_STAMPS", "unit_of", "qtip_xpos", "QtipNoop", "qtip_sum_parts",
+                 # the dq kernel's and the pair-table default
+                 "DQ_RING", "DQ_WAVES_N", "DQ_WPE3", "DQ_WPE4", "GQ_AP_PT_DEFAULT"]
 QTIP_UNITS = [f for f in SOURCES if f.startswith("qtip") and f.endswith(".hip")]
 
 
@@ -71,6 +77,15 @@ def test_the_qtip_rounding_points_stand_in_the_header_only():
     assert "/ 32.0f" in SOURCES["qtip_xform.h"] and "1.0f + __expf" in SOURCES["qtip_xform.h"]
     # n^-1/2 is rounded from double in one place (gq_inv_sqrt_f)
     assert SOURCES["qtip.hip"].count("pow((double)") + SOURCES["qtip_xf.hip"].count("pow((double)") <= 1
+
+
+def test_the_exact_gemv_rounding_points_stand_in_the_header_only():
+    # the SiLU of the SiLU * up prologue and of the gate/up pair outputs: spelled in ap_exact.h, in no kernel file that includes it
+    units = sorted(f for f, text in SOURCES.items() if f.startswith("ap_") and f.endswith(".hip") and '#include "ap_exact.h"' in text)
+    assert units == ["ap_dispatch.hip", "ap_dq.hip", "ap_gemv.hip", "ap_wide.hip"]  # (the dispatcher takes the launch arguments from it)
+    for f in units:
+        assert "1.0f + __expf" not in SOURCES[f] and "gq_pin_f32" not in SOURCES[f], f
+    assert "1.0f + __expf" in SOURCES["ap_exact.h"] and "gq_pin_f32" in SOURCES["ap_exact.h"]
 
 
 def test_plane_core_stays_host_compilable():

@@ -1,4 +1,4 @@
-"""round 6: the decode-to-fp16 MFMA kernel (ap_gemv.hip::ap_gemv_dq_kernel, GQ_DQ bit mask) against the default dispatch: accuracy on
+"""round 6: the decode-to-fp16 MFMA kernel (ap_dq.hip::ap_gemv_dq_kernel, GQ_DQ bit mask) against the default dispatch: accuracy on
 sampled rows (tests/ap_helpers._check_fast: the fast-mode envelope against the oracle's fp64 product) and us per launch (bench.py's
 bench_ap_shape: > 512 MB of weights rotating inside one captured graph), Llama-3-8B shapes, plain launch and the decode graph's form."""
 import json

@@ -1,4 +1,4 @@
-"""phase stamps of the dq kernel (GQ_STAMPS build of ap_gemv.hip): per wave of the middle block, s_memrealtime (10 ns) at kernel start of
+"""phase stamps of the dq kernel (GQ_STAMPS build of ap_dq.hip): per wave of the middle block, s_memrealtime (10 ns) at kernel start of
 the main loop and per item {top, plane words in hand, next item requested, decoded}"""
 import json, os, sys
 import numpy as np
