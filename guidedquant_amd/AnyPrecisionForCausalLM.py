@@ -286,15 +286,19 @@ class AnyPrecisionForCausalLM(nn.Module):
     # keyword arguments of `generate` the fused routes understand (everything else -> transformers' own generate)
     _ROUTE_KW = {"input_ids", "inputs", "max_new_tokens", "min_new_tokens", "max_length", "do_sample", "temperature", "top_k", "top_p",
                  "pad_token_id", "eos_token_id", "attention_mask", "cache_implementation", "use_cache", "streamer", "num_beams",
-                 "num_return_sequences", "repetition_penalty", "suppress_tokens", "return_dict_in_generate"}
+                 "num_return_sequences", "repetition_penalty", "suppress_tokens", "return_dict_in_generate", "min_p"}
 
-    def _route_request(self, args, kwargs, sampler_processors=False):
+    def _route_request(self, args, kwargs, sampler_processors=False, full_sampler=False):
         """(params, None) when the request is one the fused decode routes serve -- ONE sequence, greedy or top-k (<= 64) sampling with
         or without a nucleus (top_p), no logits processors beyond min_new_tokens on EOS, a repetition penalty (finite, > 0) and
         suppress_tokens (a flat list of ids < vocab), both applied inside the fused sampler -- else (None, reason).
         sampler_processors: `generate` asks with True.  The two-argument form keeps the answer it always gave -- a repetition penalty
         other than 1 or a suppress list is declined -- for callers that drive a sampler without the token sets (gq_sample_topk_p).  Missing sampling arguments come from
-        the model's generation_config exactly as in transformers (top_k defaults to 50 there)."""
+        the model's generation_config exactly as in transformers (top_k defaults to 50 there).
+        full_sampler: `generate` asks with True for route 1, whose sampler draws from the whole vocabulary (gq_sample_full): sampling without
+        a top-k filter (top_k=0, or None from a transformers-4 style config) and min_p in (0, 1] (keyword or generation config) are then
+        served.  top_k above 64 stays declined on this surface.  Without the flag the answers are the ones always given: no top_k, and
+        any min_p, decline."""
         if len(args) > 1 or any(k not in self._ROUTE_KW for k in kwargs):
             return None, "arguments outside the fused routes: %s" % sorted(k for k in kwargs if k not in self._ROUTE_KW)
         ids = args[0] if args else kwargs.get("input_ids", kwargs.get("inputs"))
@@ -337,9 +341,17 @@ class AnyPrecisionForCausalLM(nn.Module):
             sup = tuple(sorted(set(int(t) for t in sup)))
         if not sampler_processors and (rp != 1.0 or sup):
             return None, "repetition_penalty" if rp != 1.0 else "suppress_tokens"
+        min_p = g("min_p", None)
+        if min_p is not None and not isinstance(min_p, (int, float)):
+            return None, "min_p is not a number"
+        min_p = float(min_p or 0.0)
+        if min_p != 0.0 and not full_sampler:
+            return None, "min_p" if "min_p" in kwargs and kwargs["min_p"] is not None else "generation_config.min_p"
+        if not 0.0 <= min_p <= 1.0:
+            return None, "min_p outside [0, 1]"
         for name in ("no_repeat_ngram_size", "encoder_no_repeat_ngram_size", "bad_words_ids", "force_words_ids", "begin_suppress_tokens",
-                     "forced_bos_token_id", "forced_eos_token_id", "sequence_bias", "typical_p", "epsilon_cutoff", "eta_cutoff", "min_p", "penalty_alpha",
-                     "min_length"):
+                     "forced_bos_token_id", "forced_eos_token_id", "sequence_bias", "typical_p", "epsilon_cutoff", "eta_cutoff", "penalty_alpha",
+                     "min_length"):  # (min_p: above)
             v = getattr(gc_, name, None) if gc_ is not None else None
             if v not in (None, 0, 0.0, 1.0, [], False):
                 return None, "generation_config.%s" % name
@@ -365,29 +377,37 @@ class AnyPrecisionForCausalLM(nn.Module):
             # (round 6: top_p < 1 is served -- the fused sampler filters the nucleus of its top-k survivors the way transformers chains
             # TopKLogitsWarper and TopPLogitsWarper; without a top_k <= 64 the nucleus of the FULL distribution would be needed: declined)
             # (top_k None or 0 = no top-k filtering in transformers: the full distribution, which the 64-candidate sampler does not draw from)
-            if not top_k or int(top_k) < 1 or int(top_k) > 64 or temperature <= 0.0:
+            # (full_sampler: no top-k filter is served by the whole-vocabulary sampler; 65.. stays declined on this surface)
+            if full_sampler and not top_k and temperature > 0.0:
+                top_k = 0
+            elif not top_k or int(top_k) < 1 or int(top_k) > 64 or temperature <= 0.0:
                 return None, "top_k outside 1..64 (the fused sampler's candidates)"
+        else:
+            min_p = 0.0  # (greedy: transformers applies no warper)
         eos = g("eos_token_id", None)
         eos = [] if eos is None else ([int(eos)] if isinstance(eos, int) else [int(e) for e in eos])
         if len(eos) > 4:
             return None, "more than 4 EOS ids"
         return dict(ids=ids, T=T, max_new=int(max_new), min_new=min(int(g("min_new_tokens", 0) or 0), int(max_new)), temperature=temperature,
                     top_k=int(top_k), top_p=float(top_p), eos=eos, streamer=kwargs.get("streamer"), do_sample=do_sample,
-                    repetition_penalty=rp, suppress_tokens=sup), None
+                    repetition_penalty=rp, suppress_tokens=sup, min_p=min_p), None
 
     def generate(self, *args, **kwargs):
         """`generate` of the reference's HF surface (inference_example.py:34-77).  Three routes behind the one call:
           1. the fused decode model of the same checkpoint (`native_decoder`: prompt through the HIP prompt pass, every new token one
              replay of the captured 5-launches-per-layer graph, sampling / EOS suppression / embedding of the next token on the device)
-             -- taken AUTOMATICALLY for a request it serves (`_route_request`: one sequence, greedy or top-k <= 64 sampling with or
-             without a nucleus top_p, min_new_tokens, repetition_penalty, suppress_tokens -- the reference's own call and the published
-             Qwen2.5-Instruct generation config); `native=False` opts out, `native=True` insists (ValueError when the request is not
+             -- taken AUTOMATICALLY for a request it serves (`_route_request`: one sequence, greedy or sampling with top_k in 1..64 or
+             with NO top-k filter (top_k=0, or None in a transformers-4 style config), with or without a nucleus top_p and min_p,
+             min_new_tokens, repetition_penalty, suppress_tokens -- the reference's own call and the published Qwen2.5-Instruct
+             generation config).  Without a top-k filter, or with min_p, the step ends in the whole-vocabulary sampler (gq_sample_full);
+             top_k above 64 is NOT served on this surface yet (tests/test_hf_routes_gpu.py pins that it raises with native=True; lifting
+             it is a follow-up) -- `DecodeGraph(native_sampling=True, top_k=200)` serves it; `native=False` opts out, `native=True` insists (ValueError when the request is not
              served).  The automatic route keeps the module tree whole, so the fused q/k/v/gate/up tensors are a SECOND copy of those
              weights on the device (1.1 GB for an 8B 2-bit model, about 14 GB for a 70B one; see `native_decoder`); `native=True` releases the module tree's copy;
           2. `capture=True`: the HF module tree with its decode step captured as ONE hipGraph over a transformers StaticCache, the
              fused sampler at its end -- opt-in: measured SLOWER than route 3 on the 8B model (172 vs 249 tokens/s: the module tree's
              ~1,500 small launches per token cost more as graph nodes than as stream launches; the fused model is the fast form);
-          3. transformers' own generate on the module tree (anything else: beams, top_k > 64 or none, other logits processors, batches,
+          3. transformers' own generate on the module tree (anything else: beams, top_k > 64, other logits processors, batches,
              dict output; or `native=False`).
         Route 1 serves every precision of the checkpoint, 2 to 8 bits: the decode step's GEMVs run the exact fp16-order kernels
         below 5 bits and ap_wide.hip's LDS-table kernel from 5 to 8 (a parent of 8 bits serves precision=5..8 without the module tree).
@@ -424,7 +444,9 @@ class AnyPrecisionForCausalLM(nn.Module):
                 raise ValueError("output_logprobs=True: served by the fused decode model only (not with native=False or capture=True)")
             if kv == "fp8" and (native is False or capture is True):
                 raise ValueError("kv_cache_dtype='fp8': served by the fused decode model only (not with native=False or capture=True)")
-            req, why = self._route_request(args, kwargs, sampler_processors=True) if (native is not False or capture is True) else (None, "opted out")
+            # (full_sampler: route 1's sampler draws from the whole vocabulary; route 2 keeps the 64-candidate kernels and their answers)
+            req, why = self._route_request(args, kwargs, sampler_processors=True, full_sampler=capture is not True) \
+                if (native is not False or capture is True) else (None, "opted out")
             if req is not None and self.device.type != "cuda":
                 req, why = None, "the fused routes need the GPU"
             if kv == "fp8" and req is None:
@@ -777,7 +799,7 @@ class AnyPrecisionForCausalLM(nn.Module):
         cap = total if total > 16384 else max(256, 1 << (total - 1).bit_length())
         dec.setup_caches(1, min(cap, dec.config.block_size), kv_cache_dtype=kv_cache_dtype)
         key = (self.precision, dec.max_seq_length, dec.kv_cache_dtype, req["temperature"], req["top_k"], req["top_p"], req["repetition_penalty"], req["suppress_tokens"]) \
-            + ((("logprobs", True), ) if logprobs else ())
+            + ((("logprobs", True), ) if logprobs else ()) + ((("min_p", req["min_p"]), ) if req["min_p"] else ())
         graph = self._native_cache.get(("graph",) + key)
         if graph is None:
             self._evict("graph")
@@ -786,7 +808,7 @@ class AnyPrecisionForCausalLM(nn.Module):
             graph = gen.DecodeGraph(dec, self.device, native_sampling=True, fold_embed=True, seq_capacity=dec.max_seq_length + 1,
                                     seed=self._SAMPLER_SEED, temperature=req["temperature"], top_k=req["top_k"], top_p=req["top_p"], steps_per_replay=8,
                                     repetition_penalty=req["repetition_penalty"], suppress_tokens=req["suppress_tokens"],
-                                    **({"logprobs": True} if logprobs else {}))
+                                    **({"logprobs": True} if logprobs else {}), **({"min_p": req["min_p"]} if req["min_p"] else {}))
             self._native_cache[("graph",) + key] = graph
         ids32 = ids.view(-1).to(torch.int32)
 

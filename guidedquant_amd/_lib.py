@@ -30,6 +30,7 @@ EXPORTS = [
     "gq_token_set_build", "gq_sample_topk_rep", "gq_attn_prefill_supported", "gq_attn_prefill",
     "gq_rope_cache_rows_kv8", "gq_attn_decode_roped_kv8", "gq_attn_prefill_kv8", "gq_head_nll_ws_bytes", "gq_head_nll",
     "gq_sample_topk_lp", "gq_attn_prefill_packed", "gq_rope_cache_rows_packed",
+    "gq_sample_full_ws_bytes", "gq_sample_full",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -133,6 +134,11 @@ def lib():
         L.gq_sample_topk_rep.argtypes = [vp, u32, i32, f32, f32, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, f32, vp, vp, vp]
         # (gq_sample_topk_rep + lp_ws, lp_raw, lp_drawn, lp_cap in front of the stream)
         L.gq_sample_topk_lp.argtypes = [vp, u32, i32, f32, f32, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, f32, vp, vp, vp, vp, vp, u32, vp]
+        # (logits, vocab, top_k, top_p, min_p, temperature, seed, counter, ws, ws_bytes, tok_io, pos_io, next_tok, ban, seq_out, seq_cap, embed_table,
+        #  x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_raw, lp_drawn, lp_cap, stream)
+        L.gq_sample_full.argtypes = [vp, u32, i32, f32, f32, f32, u32, vp, vp, ctypes.c_size_t, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, f32, vp, vp, vp, vp, u32, vp]
+        L.gq_sample_full_ws_bytes.argtypes = [u32]
+        L.gq_sample_full_ws_bytes.restype = ctypes.c_size_t
         L.gq_token_set_build.argtypes = [vp, u32, u32, vp, i32, vp]
         L.gq_anyprec_gemv_cpu.argtypes = [vp, vp, vp, vp, u32, u32, u32, i32, i32, i32]
         L.gq_anyprec_dequant_cpu.argtypes = [vp, vp, vp, u32, u32, i32, i32]

@@ -7,7 +7,9 @@ needs is decided here and nowhere else:
   * a penalty or a suppress list       -> gq_sample_topk_rep (the instances over fp32 candidate values and the token sets);
   * everything else                    -> gq_sample_topk_p -- never _rep or _lp with neutral arguments: those launch the fp32-key
                                           instances, about 10.8 us per token more;
-  * a workspace of 32 candidates/block -> gq_sample_topk, the narrow call of the layer pipeline (draw only: no ban, no sequence store).
+  * a workspace of 32 candidates/block -> gq_sample_topk, the narrow call of the layer pipeline (draw only: no ban, no sequence store);
+  * no top_k (None / 0), top_k > 64, or min_p > 0 -> gq_sample_full (csrc/sampler_full.hip: the whole vocabulary; it serves the penalty,
+                                          the sets and the log-probabilities itself, from its own workspace).
 """
 import torch
 
@@ -17,14 +19,23 @@ BLOCKS = 128  # (stage 1's grid: the workspace holds `candidates` entries of eac
 
 
 class FusedSampler:
-    """State: `counter` (the RNG counter word), `work_val` / `work_idx` (stage 1's candidates), `ban` (int32 {n, until_pos, id0..id3}:
+    """State: `counter` (the RNG counter word), `work_val` / `work_idx` (stage 1's candidates; a whole-vocabulary configuration -- `full`: top_k
+    None / 0 / above 64, or min_p > 0 -- has `ws`, gq_sample_full's workspace, instead), `ban` (int32 {n, until_pos, id0..id3}:
     tokens that cannot be drawn while pos < until_pos) -- and, only when asked for, `seq` (seq_capacity > 0: every drawn token at
     seq[pos + 1]), `seen` / `suppress` (a penalty != 1 or a suppress list: uint32 bitmaps over the vocabulary; every drawn token joins
     `seen` on the device), `lp_ws` / `lp_raw` / `lp_drawn` (logprobs: the log-probability of every drawn token at [pos + 1], under the
     model's unprocessed distribution and under the one the draw was made from).  A request without them allocates nothing extra."""
 
     def __init__(self, vocab_size, device, top_k, top_p=1.0, temperature=1.0, seed=1234, seq_capacity=0, repetition_penalty=1.0,
-                 suppress_tokens=(), logprobs=False, candidates=64):
+                 suppress_tokens=(), logprobs=False, candidates=64, min_p=0.0):
+        self.min_p = float(min_p or 0.0)
+        if not 0.0 <= self.min_p <= 1.0:
+            raise ValueError(f"min_p must be in [0, 1], not {min_p!r}")
+        if top_k is not None and int(top_k) < 0:
+            raise ValueError(f"top_k must be None or >= 0, not {top_k!r}")
+        # the whole-vocabulary entry: no top-k filter (None / 0), more candidates than the 64 of the two-stage kernels, or min_p
+        self.full = top_k is None or int(top_k) == 0 or int(top_k) > 64 or self.min_p > 0.0
+        top_k = int(top_k or 0) if self.full else top_k
         self.vocab_size, self.top_k, self.top_p, self.temperature, self.seed = int(vocab_size), top_k, float(top_p or 1.0), float(temperature), int(seed)
         self.repetition_penalty = float(repetition_penalty if repetition_penalty is not None else 1.0)
         suppress_tokens = [int(t) for t in (suppress_tokens if suppress_tokens is not None else ())]
@@ -35,11 +46,19 @@ class FusedSampler:
             raise ValueError("logprobs=True needs seq_capacity > 0: the log-probabilities are stored where the tokens are")
         if self.narrow and (seq_capacity or self.repetition_penalty != 1.0 or suppress_tokens or self.top_p != 1.0):
             raise ValueError("a workspace of 32 candidates per block serves the draw alone (gq_sample_topk)")
+        if self.narrow and self.full:
+            raise ValueError("a workspace of 32 candidates per block serves top_k in 1..32 without min_p (gq_sample_topk)")
 
         def z(n, dtype=torch.int32):
             return torch.zeros((int(n), ), dtype=dtype, device=device)
         self.counter, self.ban = z(1), z(6)
-        self.work_val, self.work_idx = z(BLOCKS * candidates, torch.float32), z(BLOCKS * candidates)
+        self.work_val = self.work_idx = self.ws = None
+        if self.full:
+            self.ws = z(_lib.lib().gq_sample_full_ws_bytes(self.vocab_size) // 8, torch.int64)  # (the 128 x 64 work buffers are not needed)
+            if not self.ws.numel():
+                raise ValueError(f"the fused sampler serves vocabularies up to {_lib.SAMPLER_MAX_VOCAB}, not {self.vocab_size}")
+        else:
+            self.work_val, self.work_idx = z(BLOCKS * candidates, torch.float32), z(BLOCKS * candidates)
         self.seq = z(seq_capacity) if seq_capacity else None
         self.seen = self.suppress = self.lp_ws = self.lp_raw = self.lp_drawn = None
         if self.repetition_penalty != 1.0 or suppress_tokens:
@@ -50,7 +69,7 @@ class FusedSampler:
                 self.build_set(self.suppress, torch.tensor(suppress_tokens, dtype=torch.int32, device=device))
         if self.logprobs:
             self.lp_raw, self.lp_drawn = z(seq_capacity, torch.float32), z(seq_capacity, torch.float32)
-            self.lp_ws = z(_lib.SAMPLER_LP_WS, torch.float32)
+            self.lp_ws = z(_lib.SAMPLER_LP_WS, torch.float32) if not self.full else None
 
     def build_set(self, words, ids, clear=True):
         """words = (clear: the set of `ids`; else: joined by `ids`), one launch outside any graph"""
@@ -86,6 +105,12 @@ class FusedSampler:
         embed_table / x_out / dim / ssq_out: the last block also writes the NEXT step's hidden state and its hand-over statistics"""
         def p(t):
             return t.data_ptr() if t is not None else None
+        if self.full:
+            args = (p(logits), self.vocab_size, int(self.top_k), self.top_p, self.min_p, self.temperature, self.seed, p(self.counter), p(self.ws),
+                    self.ws.numel() * 8, p(tok_io), p(pos_io), p(next_tok), p(self.ban), p(self.seq), self.seq.numel() if self.seq is not None else 0,
+                    p(embed_table), p(x_out), dim, p(ssq_out), self.repetition_penalty, p(self.seen), p(self.suppress), p(self.lp_raw), p(self.lp_drawn),
+                    self.lp_raw.numel() if self.lp_raw is not None else 0)
+            return _lib.check(_lib.lib().gq_sample_full(*args, _lib.current_stream_ptr()), "gq_sample_full")
         draw = (self.temperature, self.seed, p(self.counter), p(self.work_val), p(self.work_idx), p(tok_io), p(pos_io), p(next_tok))
         if self.narrow:
             name, args = "gq_sample_topk", (p(logits), self.vocab_size, int(self.top_k)) + draw

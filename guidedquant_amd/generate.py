@@ -99,11 +99,15 @@ class DecodeGraph:
     (the manual-graph path of generate.py:95-113)."""
 
     def __init__(self, model: Transformer, device, native_sampling=False, seed=1234, fold_embed=False, seq_capacity=0, steps_per_replay=1,
-                 repetition_penalty=1.0, suppress_tokens=None, logprobs=False, **sampling_kwargs):
+                 repetition_penalty=1.0, suppress_tokens=None, logprobs=False, min_p=0.0, **sampling_kwargs):
         """native_sampling: draw the token with the fused HIP sampler (`self.sampler`, a fused_sampler.FusedSampler, which picks the
-        entry point: same distribution as `sample`, own counter-based RNG, top_k <= 64) and feed token / position back inside the
-        graph; `next_prob` is then not produced.  Default False = the reference's torch sampling ops, captured in the graph.
-        `rng_counter`, `work_val`, `work_idx`, `ban`, `seq`, `seen`, `suppress`, `lp_raw` and `lp_drawn` are the sampler's own tensors.
+        entry point: same distribution as `sample`, own counter-based RNG) and feed token / position back inside the
+        graph; `next_prob` is then not produced.  top_k in 1..64 without min_p launches the two-stage kernels it always launched; top_k
+        None / 0 (no top-k filter), top_k > 64 or min_p > 0 the whole-vocabulary sampler (gq_sample_full: temperature -> top_k -> top_p ->
+        min_p as transformers chains them) -- with fold_embed, steps_per_replay, the penalty, the suppress list and logprobs as ever.
+        min_p > 0 needs native sampling: the torch-sampling path has no such filter and raises ValueError rather than dropping it.  Default False = the reference's torch sampling ops, captured in the graph.
+        `rng_counter`, `work_val`, `work_idx`, `ban`, `seq`, `seen`, `suppress`, `lp_raw` and `lp_drawn` are the sampler's own tensors
+        (`work_val` / `work_idx` and the log-sum workspace are None with the whole-vocabulary sampler, which works in `self.sampler.ws`).
         fold_embed (native sampling only): the sampler's last block also writes the NEXT step's hidden state (the embedding row of
         the token it drew, model.py:121-130) and its hand-over statistics, so the captured step starts at layer 0's first GEMV -- one
         launch less per token.  The token of the first step must then be set through `set_token` (which runs the lookup once);
@@ -127,18 +131,25 @@ class DecodeGraph:
         call it makes without the argument and allocates nothing."""
         prime_graph_rng_state(device)
         self.model = model
-        self.native_sampling = bool(native_sampling) and model.native_ready() and (sampling_kwargs.get("top_k") or 0) <= 64 \
-            and sampling_kwargs.get("top_k") is not None
+        self.native_sampling = bool(native_sampling) and model.native_ready()
+        if not self.native_sampling and (min_p or 0.0) > 0.0:
+            raise ValueError("min_p is served by the fused sampler only (native_sampling=True on a model with the fused decode step): the "
+                             "torch-sampling graph does not apply it")
         self.fold_embed = bool(fold_embed) and self.native_sampling
         self.steps_per_replay = max(1, int(steps_per_replay)) if self.native_sampling else 1
         self.seed = seed
         self.sampling_kwargs = sampling_kwargs
         if not self.native_sampling and ((repetition_penalty or 1.0) != 1.0 or suppress_tokens or logprobs):
             raise ValueError("repetition_penalty / suppress_tokens / logprobs are served by the fused sampler only (native_sampling=True on a "
-                             "model with the fused decode step, top_k <= 64): the torch-sampling graph does not apply them")
+                             "model with the fused decode step): the torch-sampling graph does not apply them")
         # (the sampler's state under the names this class documents: the same tensor objects, not copies)
-        self.sampler = s = FusedSampler(model.config.vocab_size, device, sampling_kwargs.get("top_k"), sampling_kwargs.get("top_p"),
-                                        sampling_kwargs.get("temperature", 1.0), seed, seq_capacity, repetition_penalty, suppress_tokens, logprobs)
+        # (the torch-sampling graph never launches the sampler; it keeps the state tensors under their documented names.  With a top_k the
+        # two-stage kernels do not serve it gets a plain one, so that nothing of the whole-vocabulary sampler is allocated for it.)
+        k = sampling_kwargs.get("top_k")
+        if not self.native_sampling and (k is None or not 1 <= k <= 64):
+            k = 1
+        self.sampler = s = FusedSampler(model.config.vocab_size, device, k, sampling_kwargs.get("top_p"), sampling_kwargs.get("temperature", 1.0), seed,
+                                        seq_capacity, repetition_penalty, suppress_tokens, logprobs, min_p=min_p if self.native_sampling else 0.0)
         self.rng_counter, self.work_val, self.work_idx, self.ban, self.seq = s.counter, s.work_val, s.work_idx, s.ban, s.seq
         self.seen, self.suppress, self._lp_ws, self.lp_raw, self.lp_drawn = s.seen, s.suppress, s.lp_ws, s.lp_raw, s.lp_drawn
         self.repetition_penalty, self.logprobs = s.repetition_penalty, s.logprobs

@@ -135,7 +135,8 @@ class PipelinedDecoder:
             self.tok_host = torch.zeros(S, dtype=torch.int32).pin_memory()
         if self.native and self.last:
             # (32 candidates per block: FusedSampler then makes the narrow gq_sample_topk call -- the draw alone, top_k <= 32)
-            self.sampler = FusedSampler(c.vocab_size, dev, top_k, 1.0, temperature, seed, candidates=32)
+            # (a top_k that call does not serve -- None, 0, above 32 -- goes through torch's `sample` in _sample_native: the sampler is then state only)
+            self.sampler = FusedSampler(c.vocab_size, dev, top_k if top_k is not None and 1 <= top_k <= 32 else 32, 1.0, temperature, seed, candidates=32)
         if self.native:
             # the QTIP launch plans are bound to the model's own hidden-state buffer: compute there, copy in / out
             self._x = model._native_state()["x"] if model._native_kind() == "qtip" else None

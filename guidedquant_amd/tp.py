@@ -92,7 +92,12 @@ class TensorParallelDecoder:
         self.tok = torch.zeros(1, dtype=torch.int32, device=dev)
         self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
         self.next_tok = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.sampler = FusedSampler(c.vocab_size, dev, top_k, 1.0, temperature, seed, seq_capacity=max_new_tokens + 1)
+        # The whole-vocabulary sampler is not wired into the tensor-parallel step: a top_k the two-stage sampler does not serve raises here
+        # (it used to fail at the first launch: GQ_ENOTSUP above 64, a TypeError for None).  top_k < 1 keeps what the C entry always did
+        # with it: the clamp to 1 -- made here, since FusedSampler reads top_k = 0 as "no top-k filter".
+        if top_k is None or int(top_k) > 64:
+            raise ValueError(f"tensor-parallel decode draws from at most 64 candidates (the two-stage fused sampler), not top_k={top_k!r}")
+        self.sampler = FusedSampler(c.vocab_size, dev, max(int(top_k), 1), 1.0, temperature, seed, seq_capacity=max_new_tokens + 1)
         self.out_buf = self.sampler.seq  # (the sampler's sequence store: the token drawn at position p at [p + 1])
         self.tick = torch.zeros(1, dtype=torch.int32, device=dev)   # exchanges completed before this step: step * 4 * n_layer
         self.err = torch.zeros(1, dtype=torch.int32, device=dev)

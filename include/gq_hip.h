@@ -766,6 +766,43 @@ int gq_sample_topk_lp(const void *logits, uint32_t vocab, int top_k, float top_p
                       uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
                       uint32_t *seen, const uint32_t *suppress, float *lp_ws, float *lp_raw, float *lp_drawn, uint32_t lp_cap, void *stream);
 
+/* The fused sampler over the WHOLE vocabulary (csrc/sampler_full.hip): gq_sample_topk_lp's draw without the limit of 64 candidates, with
+ * min_p.  One draw is a pure function of the inputs, pinned draw for draw by tests/sampler_full_model.py, defined in this order:
+ *   live       every token but a NaN logit of either sign, an id of the ban list while *pos_io < until_pos, and a token of `suppress`
+ *              (ban and suppress exactly as in gq_sample_topk_rep);
+ *   value      s_t = the fp16 logit widened to fp32; for a token of `seen`, s = v < 0 ? fl32(v * rp) : fl32(v / rp) (a true IEEE division,
+ *              -0 is not < 0): gq_sample_topk_rep's rule;
+ *   order      (s descending as fp32, token id ascending), -0 directly below +0;
+ *   top_k      0: no filter.  >= 1: the first n_k = min(top_k, live) tokens of the order stay -- no clamp to 64.  < 0: GQ_EINVAL.  A -inf
+ *              logit is a candidate like any other;
+ *   scale      T = max(temperature, 1e-5f), a_t = fl32(s_t / T), m = a of the first token of the order;
+ *   nucleus    0 < top_p < 1 (1: off, anything else GQ_EINVAL): w_t = exp(a_t - m), Z_k = sum of w over the n_k survivors; the token at
+ *              rank j goes when sum_{i >= j} w_i <= (1 - top_p) * Z_k (1 - top_p the fp32 difference); among equal values the higher id
+ *              goes first; rank 0 always stays: n_p tokens (transformers' TopPLogitsWarper behind TopKLogitsWarper);
+ *   min_p      0 < min_p <= 1 (0: off, anything else GQ_EINVAL): a token goes when w_t < min_p (MinPLogitsWarper: p_t < min_p * p_max);
+ *              rank 0 always stays: n_m tokens;
+ *   candidates the first n = min(n_p, n_m) tokens of the order -- the chain temperature -> top_k -> top_p -> min_p;
+ *   race, counter, publishing, embedding fold: gq_sample_topk_rep's -- score = fl32(fl32(s / T) - logf(-logf(u))) with the same hash32
+ *              stream keyed on (seed, counter, token id), the lower id wins a tie, `seen` gets the drawn token's bit; an empty candidate set
+ *              publishes 0x7FFFFFFF, embeds row 0 and leaves `seen` alone;
+ *   lp_raw / lp_drawn   either may be NULL; gq_sample_topk_lp's meaning and index (*pos_io + 1 < lp_cap).  lp_drawn = a_tok - log sum_C
+ *              exp(a_c) over the n candidates; both are a quiet NaN for an empty set.
+ * Error model of the two mass cuts: the masses are sums of w * 2^44 in 64-bit integers (order-independent, exact), w = expf(fl32(a - m));
+ * tests/sampler_full_model.py derives the grants.  The top_k cut is exact.
+ * ws: gq_sample_full_ws_bytes(vocab) bytes, 16-byte aligned, owned by the call (histograms, partials).  gq_sample_full_ws_bytes is host
+ * only, launches nothing, and is 0 for vocab > GQ_SAMPLER_MAX_VOCAB.  TEST HOOK: after a call the first 24 bytes of ws hold
+ * {uint32 n, uint32 n_k, double Z_k, double Z_kept} -- Z_k, Z_kept the sums of w over the n_k and the n tokens; nothing in the package
+ * reads them.
+ * Six launches whose grids depend on nothing but the build; no host read-back; counter, pos_io, ban, seen are read from device memory:
+ * a captured graph replays it.  Deterministic: integer atomics only.
+ * Refusals, nothing launched or written: vocab > GQ_SAMPLER_MAX_VOCAB: GQ_ENOTSUP.  ws_bytes too small, a NULL required pointer (logits,
+ * counter, ws, next_tok), repetition_penalty != 1 without seen, ssq_out without x_out, a top_k / top_p / min_p outside the above: GQ_EINVAL. */
+size_t gq_sample_full_ws_bytes(uint32_t vocab);
+int gq_sample_full(const void *logits, uint32_t vocab, int top_k, float top_p, float min_p, float temperature, uint32_t seed,
+                   int *counter, void *ws, size_t ws_bytes, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                   uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                   uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, void *stream);
+
 /* Test / tuning hooks (not part of the reference's surface).  gq_reset_env_cache: drop the cached GQ_* environment
  * knobs so that a test can flip them between calls.  gq_debug_set_timing_buffer: device buffer the plane kernels write
  * s_memtime phase stamps into (tools/phase_timing.py); NULL (default) disables it. */
