@@ -47,14 +47,16 @@ _LOGPROBS_OUTPUT = None
 
 def GenerateLogprobsOutput(**fields):
     """what `generate(output_logprobs=True)` returns: a transformers ModelOutput with `sequences` [1, T + new], `logprobs` and
-    `sampled_logprobs` (fp32 [1, new]).  (The class is made on first use: this module imports transformers lazily.)"""
+    `sampled_logprobs` (fp32 [1, new]) and, with top_logprobs=n, `top_logprobs_ids` (int64 [1, new, n]) and `top_logprobs` (fp32 [1, new, n]; both
+    None without it).  (The class is made on first use: this module imports transformers lazily.)"""
     global _LOGPROBS_OUTPUT
     if _LOGPROBS_OUTPUT is None:
         import dataclasses
         from transformers.utils import ModelOutput
         _LOGPROBS_OUTPUT = dataclasses.dataclass(type("GenerateLogprobsOutput", (ModelOutput, ), {
-            "__annotations__": {"sequences": Optional[torch.Tensor], "logprobs": Optional[torch.Tensor], "sampled_logprobs": Optional[torch.Tensor]},
-            "sequences": None, "logprobs": None, "sampled_logprobs": None, "__module__": __name__}))
+            "__annotations__": {"sequences": Optional[torch.Tensor], "logprobs": Optional[torch.Tensor], "sampled_logprobs": Optional[torch.Tensor],
+                                "top_logprobs_ids": Optional[torch.Tensor], "top_logprobs": Optional[torch.Tensor]},
+            "sequences": None, "logprobs": None, "sampled_logprobs": None, "top_logprobs_ids": None, "top_logprobs": None, "__module__": __name__}))
     return _LOGPROBS_OUTPUT(**fields)
 
 
@@ -427,7 +429,14 @@ class AnyPrecisionForCausalLM(nn.Module):
         under the distribution the draw was made from (after repetition penalty, suppress list, temperature, top-k and top-p; 0 for a
         greedy request) -- transformers' compute_transition_scores(normalize_logits=True).  `logprobs[0, j]` belongs to
         `sequences[0, T + j]`; both are cut at EOS where the sequence is.  The fused sampler writes them in the launch that draws the
-        token (gq_sample_topk_lp): no [steps, vocab] scores are kept."""
+        token (gq_sample_topk_lp): no [steps, vocab] scores are kept.
+        top_logprobs=n, 1..20 (with output_logprobs=True only; without it, with n outside the range, `native=False`, `capture=True` or a
+        request route 1 does not serve: ValueError, never a fall-back, and the keyword never reaches transformers): the output gains
+        `top_logprobs_ids` int64 [1, new, n] -- the n most probable tokens of the model's UNPROCESSED distribution at each step, most
+        probable first, equal logits by ascending id, -1 where the vocabulary has fewer -- and `top_logprobs` fp32 [1, new, n], their
+        log-probabilities against the log-sum-exp `logprobs` is taken against: where the drawn token is listed its entry equals
+        `logprobs[0, j]` bit for bit.  Penalty, suppress list, min_new_tokens' EOS ban, temperature and the filters do not enter the list.
+        Both are cut at EOS where `sequences` is.  Two launches per token behind the sampler's (csrc/topn.hip)."""
         prev_precision = self.precision
         if 'precision' in kwargs:
             self.set_precision(kwargs.pop('precision'))
@@ -439,7 +448,12 @@ class AnyPrecisionForCausalLM(nn.Module):
         kv = kv_cache_dtype_name(kwargs.pop('kv_cache_dtype', None))
         # output_logprobs=True: per-token log-probabilities from the fused sampler.  Route 1 only, never a fall-back.  (popped as well)
         lp = bool(kwargs.pop('output_logprobs', False))
+        top_n = kwargs.pop('top_logprobs', None)  # (popped as well; validated inside the try: the precision is restored on a refusal)
         try:
+            from .fused_sampler import check_top_logprobs
+            if top_n is not None and not check_top_logprobs(top_n, lp):  # (the keyword, once given, asks for a list: None alone is "off" here)
+                raise ValueError(f"top_logprobs must be an integer in 1..20, not {top_n!r}")
+            top_n = int(top_n or 0)  # (top_n > 0 implies lp: every refusal of output_logprobs below is one of top_logprobs)
             if lp and (native is False or capture is True):
                 raise ValueError("output_logprobs=True: served by the fused decode model only (not with native=False or capture=True)")
             if kv == "fp8" and (native is False or capture is True):
@@ -481,7 +495,7 @@ class AnyPrecisionForCausalLM(nn.Module):
                 if dec is not None and kv == "fp8" and dec.kv8_unserved():
                     raise ValueError("kv_cache_dtype='fp8': " + dec.kv8_unserved())
                 if dec is not None:
-                    return self._generate_native(dec, req, kv_cache_dtype=kv, logprobs=lp)
+                    return self._generate_native(dec, req, kv_cache_dtype=kv, logprobs=lp, top_logprobs=top_n)
                 if lp:
                     why_not = getattr(self, "_no_native_reason", None)
                     raise ValueError("output_logprobs=True: this checkpoint has no fused decode form at %d bits%s" % (self.precision, ": " + why_not if why_not else ""))
@@ -754,7 +768,7 @@ class AnyPrecisionForCausalLM(nn.Module):
             req["streamer"].put(seq_host[lo:(cut or hi)])
         return cut
 
-    def _run_request(self, req, ids, sampler, run, chunk=32, logprobs=False):
+    def _run_request(self, req, ids, sampler, run, chunk=32, logprobs=False, top_logprobs=0):
         """One request on a fused route, from the point where the caches hold the prompt but for its last token and that token and its
         position are set: the sampler's per-request state (the sequence prefix, the `ban` words of min_new_tokens, a fresh counter word
         for a sampled call, the `seen` set of the prompt), then `run(n)` -- n token steps of the route -- in chunks of `chunk` tokens with
@@ -782,12 +796,14 @@ class AnyPrecisionForCausalLM(nn.Module):
         out = sampler.seq[:end].to(ids.dtype).view(1, -1).clone()
         if logprobs:  # (slot i of the two arrays describes seq[i]: the sampler's index)
             out = GenerateLogprobsOutput(sequences=out, logprobs=sampler.lp_raw[T:end].view(1, -1).clone(),
-                                         sampled_logprobs=sampler.lp_drawn[T:end].view(1, -1).clone())
+                                         sampled_logprobs=sampler.lp_drawn[T:end].view(1, -1).clone(),
+                                         **(dict(top_logprobs_ids=sampler.top_ids[T:end].long().unsqueeze(0), top_logprobs=sampler.top_lps[T:end].unsqueeze(0).clone())
+                                            if top_logprobs else {}))
         if req["streamer"] is not None:
             req["streamer"].end()
         return out
 
-    def _generate_native(self, dec, req, chunk=32, kv_cache_dtype="fp16", logprobs=False):
+    def _generate_native(self, dec, req, chunk=32, kv_cache_dtype="fp16", logprobs=False, top_logprobs=0):
         from . import generate as gen
         ids, T, max_new = req["ids"].to(self.device), req["T"], req["max_new"]
         total = T + max_new
@@ -799,7 +815,8 @@ class AnyPrecisionForCausalLM(nn.Module):
         cap = total if total > 16384 else max(256, 1 << (total - 1).bit_length())
         dec.setup_caches(1, min(cap, dec.config.block_size), kv_cache_dtype=kv_cache_dtype)
         key = (self.precision, dec.max_seq_length, dec.kv_cache_dtype, req["temperature"], req["top_k"], req["top_p"], req["repetition_penalty"], req["suppress_tokens"]) \
-            + ((("logprobs", True), ) if logprobs else ()) + ((("min_p", req["min_p"]), ) if req["min_p"] else ())
+            + ((("logprobs", True), ) if logprobs else ()) + ((("min_p", req["min_p"]), ) if req["min_p"] else ()) \
+            + ((("top_logprobs", top_logprobs), ) if top_logprobs else ())
         graph = self._native_cache.get(("graph",) + key)
         if graph is None:
             self._evict("graph")
@@ -808,7 +825,8 @@ class AnyPrecisionForCausalLM(nn.Module):
             graph = gen.DecodeGraph(dec, self.device, native_sampling=True, fold_embed=True, seq_capacity=dec.max_seq_length + 1,
                                     seed=self._SAMPLER_SEED, temperature=req["temperature"], top_k=req["top_k"], top_p=req["top_p"], steps_per_replay=8,
                                     repetition_penalty=req["repetition_penalty"], suppress_tokens=req["suppress_tokens"],
-                                    **({"logprobs": True} if logprobs else {}), **({"min_p": req["min_p"]} if req["min_p"] else {}))
+                                    **({"logprobs": True} if logprobs else {}), **({"min_p": req["min_p"]} if req["min_p"] else {}),
+                                    **({"top_logprobs": top_logprobs} if top_logprobs else {}))
             self._native_cache[("graph",) + key] = graph
         ids32 = ids.view(-1).to(torch.int32)
 
@@ -827,7 +845,7 @@ class AnyPrecisionForCausalLM(nn.Module):
                 else:
                     dec(pre.view(1, -1), pos)
             graph.set_token(ids32[T - 1:T], T - 1)
-            return self._run_request(req, ids, graph.sampler, run, chunk, logprobs)
+            return self._run_request(req, ids, graph.sampler, run, chunk, logprobs, top_logprobs)
 
     # -- route 2: the module tree, decode step captured -------------------------------------------------------------------
     def _generate_captured(self, req, chunk=32):

@@ -30,11 +30,13 @@ EXPORTS = [
     "gq_token_set_build", "gq_sample_topk_rep", "gq_attn_prefill_supported", "gq_attn_prefill",
     "gq_rope_cache_rows_kv8", "gq_attn_decode_roped_kv8", "gq_attn_prefill_kv8", "gq_head_nll_ws_bytes", "gq_head_nll",
     "gq_sample_topk_lp", "gq_attn_prefill_packed", "gq_rope_cache_rows_packed",
-    "gq_sample_full_ws_bytes", "gq_sample_full",
+    "gq_sample_full_ws_bytes", "gq_sample_full", "gq_sample_topk_lp_topn", "gq_sample_full_topn",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
 SAMPLER_LP_WS = 2 * 128  # floats of gq_sample_topk_lp's lp_ws
+TOPN_MAX = 20  # include/gq_hip.h GQ_TOPN_MAX
+TOPN_WS_BYTES = 16 + 128 * TOPN_MAX * 8  # include/gq_hip.h GQ_TOPN_WS_BYTES
 PREFILL_ATTN_BQ, PREFILL_ATTN_BK = 64, 64  # include/gq_hip.h GQ_PREFILL_ATTN_BQ / _BK: query rows and key rows per tile of gq_attn_prefill
 SAMPLER_MAX_VOCAB = 262144  # gq_sample_topk / _ex / _p: 128 blocks x 2048 logits (csrc/sampler.hip; up to 131072: x 1024)
 # include/gq_hip.h GQ_AP_ROUTE_*: the kernel family an AP-GEMV dispatch launched (gq_debug_ap_last_route, gq_debug_ap_plan_route)
@@ -138,6 +140,9 @@ def lib():
         #  x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_raw, lp_drawn, lp_cap, stream)
         L.gq_sample_full.argtypes = [vp, u32, i32, f32, f32, f32, u32, vp, vp, ctypes.c_size_t, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, f32, vp, vp, vp, vp, u32, vp]
         L.gq_sample_full_ws_bytes.argtypes = [u32]
+        # (the top-n forms: top_n, top_ids, top_lps, topn_ws in front of the stream)
+        L.gq_sample_topk_lp_topn.argtypes = L.gq_sample_topk_lp.argtypes[:-1] + [i32, vp, vp, vp, vp]
+        L.gq_sample_full_topn.argtypes = L.gq_sample_full.argtypes[:-1] + [i32, vp, vp, vp, vp]
         L.gq_sample_full_ws_bytes.restype = ctypes.c_size_t
         L.gq_token_set_build.argtypes = [vp, u32, u32, vp, i32, vp]
         L.gq_anyprec_gemv_cpu.argtypes = [vp, vp, vp, vp, u32, u32, u32, i32, i32, i32]

@@ -44,6 +44,14 @@ struct GqPerDeviceOnce {
     }
 };
 
+// The top-n selection behind a sampler's launches (topn.hip; the entry points are gq_sample_topk_lp_topn there and gq_sample_full_topn in
+// sampler_full.hip, which knows where its partials lie).  gq_topn_check: the refusals of include/gq_hip.h, nothing launched; lse_source: the
+// sampler's log-sum-exp partials as the request will leave them, NULL when it asks for no lp_raw.  gq_topn_launch: the launch pair;
+// lse_part = 2 * 128 floats, (m_b) then (z_b), as the sampler's own last launch reads them.
+int gq_topn_check(uint32_t vocab, int n, const void *top_ids, const void *top_lps, const void *ws, const void *lse_source);
+int gq_topn_launch(const void *logits, uint32_t vocab, int n, const float *lse_part, const int *pos_io, int *top_ids, float *top_lps, uint32_t cap,
+                   void *ws, void *stream);
+
 // Host pieces the two QTIP translation units share (qtip.hip: the trellis side, qtip_xf.hip: the transform side, which defines them).
 extern unsigned long long *g_qdbg;  // optional per-wave phase stamps (gq_debug_set_qtip_timing_buffer; tools/qtip_phase_timing.py)
 float gq_inv_sqrt_f(uint32_t n);    // (float)n^-1/2, rounded from double like the scale argument of hadamard()

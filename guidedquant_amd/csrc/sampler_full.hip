@@ -17,6 +17,7 @@
 //                            is a prefix over these counts); nothing to do when every token at Kc stays.
 //   full_race    128 blocks  the exponential race over the slice's candidates: the best (score, id) per block.
 //   full_finish  1 block     the best of the 128, the log-probabilities, publishing, the embedding fold.
+// gq_sample_full_topn (at the end of the file): the same six launches, then topn.hip's pair, which reads the partials full_hist left at WS_LP.
 // hash32, the value images, sample_publish and sample_embed are sampler.hip's, written out again here (anonymous namespace): sharing them
 // through a header would have to be shown not to move one instruction of that file's pinned instances ("One sampler kernel pair").
 #include <hip/hip_runtime.h>
@@ -623,4 +624,17 @@ extern "C" int gq_sample_full(const void *logits, uint32_t vocab, int top_k, flo
                        (const float *)lp_part, F);
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
+}
+
+extern "C" int gq_sample_full_topn(const void *logits, uint32_t vocab, int top_k, float top_p, float min_p, float temperature, uint32_t seed,
+                                   int *counter, void *ws, size_t ws_bytes, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                                   uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                                   uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n, int *top_ids,
+                                   float *top_lps, void *topn_ws, void *stream) {
+    if (int rc = gq_topn_check(vocab, top_n, top_ids, top_lps, topn_ws, lp_raw && ws ? ws : nullptr)) return rc;
+    if (int rc = gq_sample_full(logits, vocab, top_k, top_p, min_p, temperature, seed, counter, ws, ws_bytes, tok_io, pos_io, next_tok, ban, seq_out, seq_cap,
+                                embed_table, x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_raw, lp_drawn, lp_cap, stream))
+        return rc;
+    // (the partials full_hist left for full_finish: the same words, combined in the same order)
+    return gq_topn_launch(logits, vocab, top_n, (const float *)((unsigned char *)ws + WS_LP), pos_io, top_ids, top_lps, lp_cap, topn_ws, stream);
 }

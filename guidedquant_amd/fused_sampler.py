@@ -4,6 +4,8 @@ Every decode route that draws on the device -- `generate.DecodeGraph`, route 2's
 `pipeline.PipelinedDecoder` -- owns one `FusedSampler` and ends its token step with `launch`.  Which entry point a configuration
 needs is decided here and nowhere else:
   * log-probabilities                  -> gq_sample_topk_lp;
+  * top_logprobs = n > 0               -> the entry with the suffix _topn (gq_sample_topk_lp_topn / gq_sample_full_topn, csrc/topn.hip): the
+                                          same draw, and two launches behind it for the n alternatives.  n = 0 calls what it called;
   * a penalty or a suppress list       -> gq_sample_topk_rep (the instances over fp32 candidate values and the token sets);
   * everything else                    -> gq_sample_topk_p -- never _rep or _lp with neutral arguments: those launch the fp32-key
                                           instances, about 10.8 us per token more;
@@ -18,16 +20,29 @@ from . import _lib
 BLOCKS = 128  # (stage 1's grid: the workspace holds `candidates` entries of each block)
 
 
+def check_top_logprobs(n, logprobs):
+    """top_logprobs as an int: 0 / None = off, else 1 .. _lib.TOPN_MAX and only next to the log-probabilities (ValueError otherwise)"""
+    if n is None or n is False:
+        return 0
+    if isinstance(n, bool) or int(n) != n or not 0 <= int(n) <= _lib.TOPN_MAX:
+        raise ValueError(f"top_logprobs must be an integer in 1..{_lib.TOPN_MAX} (0 / None: off), not {n!r}")
+    if int(n) and not logprobs:
+        raise ValueError("top_logprobs needs the log-probabilities (logprobs=True / output_logprobs=True): the list is normalised by lp_raw's log-sum-exp")
+    return int(n)
+
+
 class FusedSampler:
     """State: `counter` (the RNG counter word), `work_val` / `work_idx` (stage 1's candidates; a whole-vocabulary configuration -- `full`: top_k
     None / 0 / above 64, or min_p > 0 -- has `ws`, gq_sample_full's workspace, instead), `ban` (int32 {n, until_pos, id0..id3}:
     tokens that cannot be drawn while pos < until_pos) -- and, only when asked for, `seq` (seq_capacity > 0: every drawn token at
     seq[pos + 1]), `seen` / `suppress` (a penalty != 1 or a suppress list: uint32 bitmaps over the vocabulary; every drawn token joins
     `seen` on the device), `lp_ws` / `lp_raw` / `lp_drawn` (logprobs: the log-probability of every drawn token at [pos + 1], under the
-    model's unprocessed distribution and under the one the draw was made from).  A request without them allocates nothing extra."""
+    model's unprocessed distribution and under the one the draw was made from), `top_ids` / `top_lps` / `topn_ws` (top_logprobs = n in
+    1..20, with logprobs: int32 / fp32 [seq_capacity, n], row [pos + 1] = the n most probable tokens of the unprocessed distribution and
+    their log-probabilities, against the log-sum-exp lp_raw is taken against).  A request without them allocates nothing extra."""
 
     def __init__(self, vocab_size, device, top_k, top_p=1.0, temperature=1.0, seed=1234, seq_capacity=0, repetition_penalty=1.0,
-                 suppress_tokens=(), logprobs=False, candidates=64, min_p=0.0):
+                 suppress_tokens=(), logprobs=False, candidates=64, min_p=0.0, top_logprobs=0):
         self.min_p = float(min_p or 0.0)
         if not 0.0 <= self.min_p <= 1.0:
             raise ValueError(f"min_p must be in [0, 1], not {min_p!r}")
@@ -40,6 +55,7 @@ class FusedSampler:
         self.repetition_penalty = float(repetition_penalty if repetition_penalty is not None else 1.0)
         suppress_tokens = [int(t) for t in (suppress_tokens if suppress_tokens is not None else ())]
         self.logprobs, self.narrow = bool(logprobs), candidates == 32
+        self.top_logprobs = check_top_logprobs(top_logprobs, self.logprobs)
         if not (self.repetition_penalty > 0.0 and self.repetition_penalty != float("inf")):
             raise ValueError(f"repetition_penalty must be finite and > 0, not {repetition_penalty!r}")
         if self.logprobs and not seq_capacity:
@@ -70,6 +86,11 @@ class FusedSampler:
         if self.logprobs:
             self.lp_raw, self.lp_drawn = z(seq_capacity, torch.float32), z(seq_capacity, torch.float32)
             self.lp_ws = z(_lib.SAMPLER_LP_WS, torch.float32) if not self.full else None
+        self.top_ids = self.top_lps = self.topn_ws = None
+        if self.top_logprobs:
+            n = self.top_logprobs
+            self.top_ids, self.top_lps = z(seq_capacity * n).view(seq_capacity, n), z(seq_capacity * n, torch.float32).view(seq_capacity, n)
+            self.topn_ws = z(_lib.TOPN_WS_BYTES // 8, torch.int64)
 
     def build_set(self, words, ids, clear=True):
         """words = (clear: the set of `ids`; else: joined by `ids`), one launch outside any graph"""
@@ -110,7 +131,10 @@ class FusedSampler:
                     self.ws.numel() * 8, p(tok_io), p(pos_io), p(next_tok), p(self.ban), p(self.seq), self.seq.numel() if self.seq is not None else 0,
                     p(embed_table), p(x_out), dim, p(ssq_out), self.repetition_penalty, p(self.seen), p(self.suppress), p(self.lp_raw), p(self.lp_drawn),
                     self.lp_raw.numel() if self.lp_raw is not None else 0)
-            return _lib.check(_lib.lib().gq_sample_full(*args, _lib.current_stream_ptr()), "gq_sample_full")
+            name = "gq_sample_full"
+            if self.top_logprobs:
+                name, args = "gq_sample_full_topn", args + (self.top_logprobs, p(self.top_ids), p(self.top_lps), p(self.topn_ws))
+            return _lib.check(getattr(_lib.lib(), name)(*args, _lib.current_stream_ptr()), name)
         draw = (self.temperature, self.seed, p(self.counter), p(self.work_val), p(self.work_idx), p(tok_io), p(pos_io), p(next_tok))
         if self.narrow:
             name, args = "gq_sample_topk", (p(logits), self.vocab_size, int(self.top_k)) + draw
@@ -121,4 +145,6 @@ class FusedSampler:
                 name, args = "gq_sample_topk_rep", args + (self.repetition_penalty, p(self.seen), p(self.suppress))
             if self.logprobs:
                 name, args = "gq_sample_topk_lp", args + (p(self.lp_ws), p(self.lp_raw), p(self.lp_drawn), self.lp_raw.numel())
+            if self.top_logprobs:
+                name, args = "gq_sample_topk_lp_topn", args + (self.top_logprobs, p(self.top_ids), p(self.top_lps), p(self.topn_ws))
         _lib.check(getattr(_lib.lib(), name)(*args, _lib.current_stream_ptr()), name)

@@ -18,7 +18,7 @@ import torch.nn as nn
 from . import pack
 from ._graphs import capture, captured, release, warm_up
 from .APLinear import APLinear
-from .fused_sampler import FusedSampler
+from .fused_sampler import FusedSampler, check_top_logprobs
 from .LUTGEMMLinear import LUTGEMMLinear
 from .model import Transformer
 
@@ -99,7 +99,7 @@ class DecodeGraph:
     (the manual-graph path of generate.py:95-113)."""
 
     def __init__(self, model: Transformer, device, native_sampling=False, seed=1234, fold_embed=False, seq_capacity=0, steps_per_replay=1,
-                 repetition_penalty=1.0, suppress_tokens=None, logprobs=False, min_p=0.0, **sampling_kwargs):
+                 repetition_penalty=1.0, suppress_tokens=None, logprobs=False, min_p=0.0, top_logprobs=0, **sampling_kwargs):
         """native_sampling: draw the token with the fused HIP sampler (`self.sampler`, a fused_sampler.FusedSampler, which picks the
         entry point: same distribution as `sample`, own counter-based RNG) and feed token / position back inside the
         graph; `next_prob` is then not produced.  top_k in 1..64 without min_p launches the two-stage kernels it always launched; top_k
@@ -128,7 +128,13 @@ class DecodeGraph:
         every token it draws (gq_sample_topk_lp, no extra launch): `self.lp_raw[pos + 1]` under the model's unprocessed distribution and
         `self.lp_drawn[pos + 1]` under the distribution the draw was made from (fp32 [seq_capacity], the index `self.seq` uses -- it
         comes from the device position, so a multi-step replay fills consecutive slots).  With the default the step makes exactly the
-        call it makes without the argument and allocates nothing."""
+        call it makes without the argument and allocates nothing.
+        top_logprobs=n in 1..20 (with logprobs=True, so native sampling and seq_capacity > 0; ValueError otherwise, never dropped): the step
+        also leaves the n most probable tokens of the model's unprocessed distribution, `self.top_ids[pos + 1]` (int32 [seq_capacity, n], -1
+        where the vocabulary has fewer) and their log-probabilities `self.top_lps[pos + 1]` (fp32, against lp_raw's log-sum-exp: the drawn
+        token's entry, where it is listed, equals lp_raw bit for bit) -- two launches behind the sampler's (gq_sample_topk_lp_topn /
+        gq_sample_full_topn).  Ban list, suppress list, penalty, temperature and the filters do not enter the list.  0 (the default): the
+        step launches what it launches without the argument."""
         prime_graph_rng_state(device)
         self.model = model
         self.native_sampling = bool(native_sampling) and model.native_ready()
@@ -145,14 +151,19 @@ class DecodeGraph:
         # (the sampler's state under the names this class documents: the same tensor objects, not copies)
         # (the torch-sampling graph never launches the sampler; it keeps the state tensors under their documented names.  With a top_k the
         # two-stage kernels do not serve it gets a plain one, so that nothing of the whole-vocabulary sampler is allocated for it.)
+        if check_top_logprobs(top_logprobs, True) and not (self.native_sampling and logprobs and seq_capacity):
+            raise ValueError("top_logprobs needs logprobs=True, native_sampling=True on a model with the fused decode step, and seq_capacity > 0: "
+                             "the lists are stored where the tokens and their log-probabilities are")
         k = sampling_kwargs.get("top_k")
         if not self.native_sampling and (k is None or not 1 <= k <= 64):
             k = 1
         self.sampler = s = FusedSampler(model.config.vocab_size, device, k, sampling_kwargs.get("top_p"), sampling_kwargs.get("temperature", 1.0), seed,
-                                        seq_capacity, repetition_penalty, suppress_tokens, logprobs, min_p=min_p if self.native_sampling else 0.0)
+                                        seq_capacity, repetition_penalty, suppress_tokens, logprobs, min_p=min_p if self.native_sampling else 0.0,
+                                        top_logprobs=top_logprobs)
         self.rng_counter, self.work_val, self.work_idx, self.ban, self.seq = s.counter, s.work_val, s.work_idx, s.ban, s.seq
         self.seen, self.suppress, self._lp_ws, self.lp_raw, self.lp_drawn = s.seen, s.suppress, s.lp_ws, s.lp_raw, s.lp_drawn
         self.repetition_penalty, self.logprobs = s.repetition_penalty, s.logprobs
+        self.top_logprobs, self.top_ids, self.top_lps = s.top_logprobs, s.top_ids, s.top_lps
         self.tok = torch.zeros((1, 1), dtype=torch.int32, device=device)
         self.pos = torch.zeros((1, ), dtype=torch.int32, device=device)
         self.next_tok = torch.zeros((1, 1), dtype=torch.int32, device=device)

@@ -803,6 +803,50 @@ int gq_sample_full(const void *logits, uint32_t vocab, int top_k, float top_p, f
                    uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
                    uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, void *stream);
 
+/* Top-n alternatives: gq_sample_topk_lp / gq_sample_full that also leave, for the step they draw, the n most probable tokens of the model's
+ * UNPROCESSED distribution with their log-probabilities (csrc/topn.hip; serving APIs' top_logprobs = n).  Every parameter of the entry
+ * without the suffix up to lp_cap, then
+ *   top_n     1 .. GQ_TOPN_MAX;
+ *   top_ids   int   [lp_cap * top_n], row-major;
+ *   top_lps   float [lp_cap * top_n];
+ *   topn_ws   GQ_TOPN_WS_BYTES bytes, 8-byte aligned, owned by the call;
+ * pinned by tests/topn_model.py.
+ *   draw       the entry's without the suffix: for the same inputs everything it writes -- next_tok, tok_io, pos_io, counter, seq_out, seen,
+ *              x_out, ssq_out, lp_raw, lp_drawn, the empty-set token INT_MAX included -- is bit-identical, and so are its status codes.
+ *   index      p = *pos_io before the increment, row i = p + 1 (the index seq_out and lp_raw use); pos_io == NULL: row i = 0 (the arrays of a
+ *              single draw are 0-based; lp_raw keeps its index 1 there).  The two rows are written when i < lp_cap; no other row is touched.
+ *   order      the RAW order: the fp16 logit descending as a bit pattern (-0 directly below +0), the token id ascending among equal patterns.
+ *              A NaN logit of either sign is not listed.  Nothing else enters: ban list, suppress, seen / repetition_penalty, temperature,
+ *              top_k, top_p and min_p do not -- a suppressed token with the largest logit is listed first, and the rows of a draw with an
+ *              empty candidate set are the raw order's like any other.
+ *   top_ids[i][j], j < top_n   the first top_n tokens of that order; with fewer than top_n tokens that are no NaN the remaining places hold
+ *              id -1 and log-probability -inf.
+ *   top_lps[i][j]   fl32(fl32(v - M) - L): v the fp16 logit widened to fp32 and (M, L) = (max, log sum exp(. - max)), the two fp32 numbers
+ *              lp_raw of this step is taken against, in lp_raw's two subtractions.  Whenever the drawn token is top_ids[i][j],
+ *              top_lps[i][j] == lp_raw[i] bit for bit.  A -inf logit is listed like any other, with -inf.  Where lp_raw is unspecified
+ *              (a +inf logit, all -inf, a NaN logit: the sum is NaN) the numbers are the same expression's.
+ *   how        two launches of their own behind the sampler's (128 blocks: the best top_n of each slice of <= 1024 logits up to 131072, of
+ *              <= 2048 up to 262144; one block: the best of the 128 * top_n), which read the log-sum-exp partials the sampler's launches
+ *              left in lp_ws / ws and combine them in the same fixed order.  Grids depend on nothing but the build, the row index is read
+ *              from device memory, no host read-back: a captured graph replays them.  Integer maxima only, no atomics: two calls on the
+ *              same state give the same bits.
+ *   TEST HOOK  after a call the first two floats of topn_ws hold (M, L); nothing in the package reads them.
+ * Refusals, nothing launched or written: vocab > GQ_SAMPLER_MAX_VOCAB: GQ_ENOTSUP.  top_n outside 1 .. GQ_TOPN_MAX, a NULL top_ids / top_lps /
+ * topn_ws, a topn_ws that is not 8-byte aligned, lp_raw == NULL (or its workspace: lp_ws / ws): GQ_EINVAL.  Then the refusals of the entry
+ * without the suffix, with its codes.  The entries without the suffix launch what they launched. */
+#define GQ_TOPN_MAX 20
+#define GQ_TOPN_WS_BYTES (16 + 128 * GQ_TOPN_MAX * 8)
+int gq_sample_topk_lp_topn(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
+                           float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                           uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                           uint32_t *seen, const uint32_t *suppress, float *lp_ws, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n,
+                           int *top_ids, float *top_lps, void *topn_ws, void *stream);
+int gq_sample_full_topn(const void *logits, uint32_t vocab, int top_k, float top_p, float min_p, float temperature, uint32_t seed,
+                        int *counter, void *ws, size_t ws_bytes, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                        uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                        uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n, int *top_ids,
+                        float *top_lps, void *topn_ws, void *stream);
+
 /* Test / tuning hooks (not part of the reference's surface).  gq_reset_env_cache: drop the cached GQ_* environment
  * knobs so that a test can flip them between calls.  gq_debug_set_timing_buffer: device buffer the plane kernels write
  * s_memtime phase stamps into (tools/phase_timing.py); NULL (default) disables it. */
