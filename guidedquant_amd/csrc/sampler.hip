@@ -6,15 +6,15 @@
 #include <stdint.h>
 
 #include "gq_internal.h"
+#include "sampler_core.h"
 #include "wave_util.h"
 
 namespace {
 
-typedef uint32_t u32;
+using namespace gqs;  // the images, the race, the ban list, the log-sum-exp merge, publishing, the host checks: sampler_core.h
 using gqw::h16;
 using gqw::h2f;
 using gqw::wave_reduce_bcast;
-typedef unsigned long long u64;
 
 // Top-k sampling exactly as generate.py:53-73 defines the distribution: logits / max(T, 1e-5), keep the top k,
 // softmax, then draw with the exponential race  argmax_i p_i / q_i, q ~ Exp(1)   (multinomial_sample_one_no_sync).
@@ -26,32 +26,23 @@ typedef unsigned long long u64;
 constexpr int SAMP_BLOCKS = 128, SAMP_K = 64;  // (the kernels are built for 32 and for 64 candidates per block)
 constexpr u32 SAMP_MAX_VOCAB = GQ_SAMPLER_MAX_VOCAB;  // SAMP_BLOCKS slices of <= 2048 logits (the wide instance; <= 131072: slices of <= 1024)
 static_assert(SAMP_MAX_VOCAB == 2048u * SAMP_BLOCKS, "the wide instance's slice");
-static_assert(GQ_SSQ_SLOTS == 1024, "sample_stage2 writes one hand-over slot per thread");
-
-__device__ __forceinline__ u32 hash32(u32 x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
 
 // Selection of the K largest by binary search on a UNIQUE integer key (monotone image of the value in the high
 // bits, inverted index in the low bits so that ties go to the lowest index): nbits rounds of "count keys >= candidate"
 // (registers + one DPP wave reduction + one LDS combine per round) instead of K rounds of block-wide arg-max.
-__device__ __forceinline__ u32 ordered_key16(uint16_t h) { return (h & 0x8000u) ? (u32)(uint16_t)~h : ((u32)h | 0x8000u); }
-__device__ __forceinline__ uint16_t unordered_key16(u32 o) { return (o & 0x8000u) ? (uint16_t)(o & 0x7FFFu) : (uint16_t)~o; }
-// the same image of an fp32 bit pattern (a penalised logit is an fp32 number that in general is no fp16 value)
-__device__ __forceinline__ u32 ordered_key32(u32 b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
-__device__ __forceinline__ u32 unordered_key32(u32 o) { return (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o; }
-// stage 1 of every instance gives a NaN logit (or a penalised one) the key 0: never a candidate, whatever its sign
-__device__ __forceinline__ bool is_nan16(uint16_t h) { return (h & 0x7FFFu) > 0x7C00u; }
-// the bits of a candidate value that the keys carry -- all 32 of a penalised value (REP), else the 16 of the fp16 logit it is -- their
+// The bits of a candidate value that the keys carry -- all 32 of a penalised value (REP), else the 16 of the fp16 logit it is -- their
 // image, and the value an image stands for
 template <bool REP>
 __device__ __forceinline__ auto value_bits(float v) {
     if constexpr (REP) return __builtin_bit_cast(u32, v);
     else return __builtin_bit_cast(uint16_t, (h16)v);
 }
-__device__ __forceinline__ u32 key_image(uint16_t h) { return ordered_key16(h); }
-__device__ __forceinline__ u32 key_image(u32 b) { return ordered_key32(b); }
+__device__ __forceinline__ u32 key_image(uint16_t h) {
+    return ordered_key16(h);
+}
+__device__ __forceinline__ u32 key_image(u32 b) {
+    return ordered_key32(b);
+}
 template <bool REP>
 __device__ __forceinline__ float key_value(u32 img) {
     if constexpr (REP) return __builtin_bit_cast(float, unordered_key32(img));
@@ -99,22 +90,6 @@ __device__ __forceinline__ int wave_compact(const KeyT (&key)[EPT], KeyT t, KeyT
     return base;
 }
 
-// Extras of the extended entry points (gq_sample_topk_ex / _p); all optional:
-//   ban: device words {n (<= 4), until_pos, id0..id3} -- while *pos_io < until_pos the listed tokens cannot be drawn (HF's
-//        MinNewTokensLengthLogitsProcessor: EOS is suppressed until min_new_tokens are out);
-//   seq_out[*pos_io + 1] = the drawn token (the host reads whole chunks of the sequence instead of cloning one word per step);
-//   emb_table / x_out / ssq_out: the embedding row of the drawn token -> the hidden-state buffer of the NEXT step (+ its statistics
-//        hand-over, gq_embed_lookup_ho) -- the step's graph then starts at layer 0's first GEMV, one launch less per token.
-struct SampleEx {
-    const int *ban;
-    int *seq_out;
-    u32 seq_cap;
-    const uint16_t *emb_table;
-    uint16_t *x_out;
-    u32 dim, vocab;
-    float *ssq_out;
-    float top_p;  // nucleus threshold (gq_sample_topk_p); >= 1 or <= 0: off
-};
 // REP (gq_sample_topk_rep): a token of `suppress` is no candidate, a token of `seen` carries s = v < 0 ? v * rp : v / rp in fp32.  The
 // candidate values are then fp32 numbers and the keys carry all 32 bits of them.
 struct SampleRep {
@@ -130,7 +105,6 @@ struct SampleLp {
     u32 cap;
     const uint16_t *logits;  // stage 2 reads the drawn token's raw logit
 };
-constexpr float LP_NINF = -__builtin_inff();
 
 // A kernel argument only the instances with ON take: an instance without it keeps the argument list (and the kernarg layout) it
 // would have had alone, and reads T{} -- a constant the compiler folds every test of away.
@@ -145,38 +119,6 @@ struct Opt<true, T> {
     Opt(const T &x) : v(x) {}
     __device__ __forceinline__ T get() const { return v; }
 };
-
-// what stage 2 does with the token: outputs, token / position feedback, the sequence store
-// (seen: the token set of gq_sample_topk_rep or NULL -- the drawn token's bit, by a vector atomic from this one lane; the next step's
-// stage 1 reads the word behind a kernel boundary.  The token of an empty candidate set is no id of the vocabulary and sets nothing.)
-__device__ __forceinline__ void sample_publish(int tokc, u32 ctr, int *counter, int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex,
-                                               u32 *seen, u32 V) {
-    if (seen && (u32)tokc < V) atomicOr(seen + ((u32)tokc >> 5), 1u << ((u32)tokc & 31u));
-    next_tok[0] = tokc;
-    counter[0] = (int)(ctr + 1u);
-    if (tok_io) tok_io[0] = tokc;
-    const int p = pos_io ? pos_io[0] : 0;
-    if (ex.seq_out && (u32)(p + 1) < ex.seq_cap) ex.seq_out[p + 1] = tokc;
-    if (pos_io) pos_io[0] = p + 1;
-}
-// the next step's hidden state: tok_embeddings[token] (+ the statistics hand-over for layer 0's RMSNorm); 1024 threads
-__device__ __forceinline__ void sample_embed(int chosen, u32 tid, const SampleEx &ex) {
-    u32 tk = (u32)chosen;
-    if (tk >= ex.vocab) tk = 0;
-    float acc = 0.f;
-    for (u32 i = tid; i < ex.dim / 8u; i += 1024u) {
-        const uint4 v = reinterpret_cast<const uint4 *>(ex.emb_table + (size_t)tk * ex.dim)[i];
-        gq_store_wt(reinterpret_cast<uint4 *>(ex.x_out) + i, v);
-        const u32 wd[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const float a = (float)__builtin_bit_cast(_Float16, (uint16_t)(wd[k] & 0xFFFFu)), b = (float)__builtin_bit_cast(_Float16, (uint16_t)(wd[k] >> 16));
-            acc += a * a;
-            acc += b * b;
-        }
-    }
-    if (ex.ssq_out) gq_store_wt(ex.ssq_out + tid, acc);  // (1024 threads = GQ_SSQ_SLOTS)
-}
 
 // The two kernels below are ONE text for every instance: <REP, LP> = <false, false> is what gq_sample_topk / _ex / _p launch (and what
 // bench.py and a default generate() run), <true, false> serves gq_sample_topk_rep, <., true> gq_sample_topk_lp.  The instructions of the
@@ -211,13 +153,8 @@ __global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32
     const u32 per = (V + SAMP_BLOCKS - 1) / SAMP_BLOCKS;  // <= 256 * EPT
     const u32 lo = blockIdx.x * per, hi = min(lo + per, V);
     const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
-    int nban = 0, bid[4] = {-1, -1, -1, -1};
-    if (ban) {  // (wave-uniform scalar loads)
-        nban = ban[0];
-        if (pos_io && pos_io[0] >= ban[1]) nban = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) bid[i] = i < nban ? ban[2 + i] : -1;
-    }
+    int bid[4] = {-1, -1, -1, -1};
+    ban_ids(ban, pos_io, bid);
     u64 sbits = 0ull, pbits = 0ull;  // bit e: token lo + tid * EPT + e is seen / suppressed
     const u32 g0 = lo + tid * (u32)EPT;
     if (REP && g0 < hi) {  // (words of tokens < hi <= V only: a set is ceil(V / 32) words)
@@ -230,6 +167,7 @@ __global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32
 #pragma unroll
     for (int e = 0; e < EPT; e++) {
         const u32 li = tid * (u32)EPT + (u32)e, gi = lo + li;
+        // put back (id test): gqs::is_banned(gi, bid), written out -- as a call it reorders the compares of every instance, the plain ones too
         const bool banned = (int)gi == bid[0] || (int)gi == bid[1] || (int)gi == bid[2] || (int)gi == bid[3];
         // fork (slice load): LP needs every logit of the slice for its statistics (-inf past the end); the others load their candidates
         // only -- one global_load_ushort under the candidate test
@@ -242,8 +180,7 @@ __global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32
         KeyT k = 0;
         if constexpr (REP) {
             if (cand) {
-                // (-0 is not < 0; the division is IEEE's, correctly rounded: the library is built without fast-math)
-                const float v = h2f(hb), sv = ((sbits >> e) & 1ull) ? (v < 0.f ? v * rep.rp : v / rep.rp) : v;
+                const float v = h2f(hb), sv = ((sbits >> e) & 1ull) ? penalise(v, rep.rp) : v;
                 if (sv == sv) k = ((u64)ordered_key32(__builtin_bit_cast(u32, sv)) << LB) | (u64)(LMASK - li);
             }
         } else if constexpr (LP) {
@@ -261,7 +198,7 @@ __global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32
         const float mw = wave_reduce_bcast<true>(mt);
         float zt = 0.f;
 #pragma unroll
-        for (int e = 0; e < EPT; e++) zt += raw[e] == LP_NINF ? 0.f : expf(raw[e] - mw);
+        for (int e = 0; e < EPT; e++) zt += raw[e] == NINF ? 0.f : expf(raw[e] - mw);
         const float zw = wave_reduce_bcast<false>(zt);
         if (l == 0) {
             lpm[w] = mw;
@@ -336,7 +273,7 @@ __global__ void __launch_bounds__(1024) sample_stage2(const float *cand_val, con
     const u32 V = V_.get();
     const SampleLp lp = lp_.get();
     const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
-    float pm0 = LP_NINF, pm1 = LP_NINF, pz0 = 0.f, pz1 = 0.f;  // (LP) loaded here, used behind the first barrier
+    float pm0 = NINF, pm1 = NINF, pz0 = 0.f, pz1 = 0.f;  // (LP) loaded here, used behind the first barrier
     if (LP && lp.ws && w == 1) {
         pm0 = lp.ws[l];
         pm1 = lp.ws[64u + l];
@@ -377,17 +314,8 @@ __global__ void __launch_bounds__(1024) sample_stage2(const float *cand_val, con
             selv[l] = key_value<REP>((u32)(k >> IB));
             seli[l] = (int)(IMASK - ((u32)k & IMASK));
         }
-    } else if (LP && w == 1 && lp.ws) {  // M = max m_b, Z = sum z_b exp(m_b - M): a -inf partial (a block past the end) contributes 0
-        float M = fmaxf(pm0, pm1);
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) M = fmaxf(M, __shfl_xor(M, sh, 64));
-        float Z = (pz0 == 0.f ? 0.f : pz0 * expf(pm0 - M)) + (pz1 == 0.f ? 0.f : pz1 * expf(pm1 - M));  // (z == 0: as in stage 1)
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) Z += __shfl_xor(Z, sh, 64);
-        if (l == 0) {
-            lpM = M;
-            lpLogZ = logf(Z);
-        }
+    } else if (LP && w == 1 && lp.ws) {
+        lse_merge128(pm0, pm1, pz0, pz1, l, lpM, lpLogZ);
     }
     __syncthreads();
     if (w == 0) {
@@ -426,10 +354,7 @@ __global__ void __launch_bounds__(1024) sample_stage2(const float *cand_val, con
             keep = keep && (greater == 0 || !(cum <= 1.0f - ex.top_p));
         }
         if (keep) {
-            // q ~ Exp(1) = -log(u), u in (0,1]; the random number is tied to the TOKEN id, not to the slot
-            const u32 r = hash32(seed ^ hash32(ctr * 0x9E3779B9u + (u32)seli[l] + 1u));
-            const float u = ((float)(r >> 8) + 1.0f) * (1.0f / 16777216.0f);
-            score = selv[l] / T - __logf(-__logf(u));
+            score = race_score(selv[l], T, race_u(seed, ctr, (u32)seli[l]));
             tokc = seli[l];
         }
 #pragma unroll
@@ -447,11 +372,11 @@ __global__ void __launch_bounds__(1024) sample_stage2(const float *cand_val, con
                 // v_tok - lse over the whole vocabulary, as (v_tok - M) - log Z: the difference's rounding is in units of the result
                 if (lp.raw) lraw = (__shfl(rawv, win, 64) - lpM) - lpLogZ;
                 if (lp.drawn) {  // a_tok - log sum_C exp(a_c) over the kept candidates, a_c as the race forms it
-                    const float a = keep ? selv[l] / T : LP_NINF;
+                    const float a = keep ? selv[l] / T : NINF;
                     float mx = a;
 #pragma unroll
                     for (int sh = 32; sh >= 1; sh >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sh, 64));
-                    float z = (keep && a != LP_NINF) ? expf(a - mx) : 0.f;
+                    float z = (keep && a != NINF) ? expf(a - mx) : 0.f;
 #pragma unroll
                     for (int sh = 32; sh >= 1; sh >>= 1) z += __shfl_xor(z, sh, 64);
                     ldrawn = (__shfl(a, win, 64) - mx) - logf(z);
@@ -520,7 +445,7 @@ int sample_launch(const void *logits, uint32_t vocab, int top_k, float temperatu
                   const SampleLp *lp = nullptr) {
     if (!logits || !counter || !work_val || !work_idx || !next_tok) return gq_fail(GQ_EINVAL, "null pointer argument.");
     if (top_k > SAMP_K) return gq_fail(GQ_ENOTSUP, "top_k > 64 is not supported by the fused sampler.");
-    if (vocab > SAMP_MAX_VOCAB) return gq_fail(GQ_ENOTSUP, "vocab too large for the fused sampler (<= 262144).");
+    if (int rc = sample_vocab_ok(vocab)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const SampleRep r = rep ? *rep : SampleRep{};
     const SampleLp q = lp ? *lp : SampleLp{};
@@ -537,33 +462,6 @@ int sample_launch(const void *logits, uint32_t vocab, int top_k, float temperatu
     else
         sample_launch_form<false, false>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, r, seen, q, s);
     GQ_HIP_CHECK(hipGetLastError());
-    return GQ_OK;
-}
-
-// the extras of gq_sample_topk_p / _rep / _lp, checked
-int sample_extras(SampleEx &ex, uint32_t vocab, float top_p, const int *ban, int *seq_out, uint32_t seq_cap, const void *embed_table, void *x_out,
-                  uint32_t dim, float *ssq_out) {
-    if (!(top_p > 0.f)) return gq_fail(GQ_EINVAL, "top_p must be in (0, 1] (1 = no nucleus filter).");
-    ex.top_p = top_p;
-    ex.ban = ban;
-    ex.seq_out = seq_out;
-    ex.seq_cap = seq_cap;
-    if (x_out) {
-        if (!embed_table || dim % 8u) return gq_fail(GQ_EINVAL, "x_out needs the embedding table and dim % 8 == 0.");
-        ex.emb_table = (const uint16_t *)embed_table;
-        ex.x_out = (uint16_t *)x_out;
-        ex.dim = dim;
-        ex.vocab = vocab;
-        ex.ssq_out = ssq_out;
-    } else if (ssq_out) {
-        return gq_fail(GQ_EINVAL, "ssq_out without x_out.");
-    }
-    return GQ_OK;
-}
-int sample_penalty_ok(float repetition_penalty, const uint32_t *seen) {
-    if (!(repetition_penalty > 0.f) || !(repetition_penalty < INFINITY))
-        return gq_fail(GQ_EINVAL, "repetition_penalty must be finite and > 0 (1 = no penalty).");
-    if (!seen && repetition_penalty != 1.0f) return gq_fail(GQ_EINVAL, "repetition_penalty != 1 needs the `seen` token set.");
     return GQ_OK;
 }
 }  // namespace

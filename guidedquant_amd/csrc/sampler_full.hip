@@ -18,19 +18,19 @@
 //   full_race    128 blocks  the exponential race over the slice's candidates: the best (score, id) per block.
 //   full_finish  1 block     the best of the 128, the log-probabilities, publishing, the embedding fold.
 // gq_sample_full_topn (at the end of the file): the same six launches, then topn.hip's pair, which reads the partials full_hist left at WS_LP.
-// hash32, the value images, sample_publish and sample_embed are sampler.hip's, written out again here (anonymous namespace): sharing them
-// through a header would have to be shown not to move one instruction of that file's pinned instances ("One sampler kernel pair").
+// The value images, the penalty, the ban list, the race, the log-sum-exp merge, publishing and the embedding fold are sampler_core.h's: the
+// functions sampler.hip's kernels are built from, so the two samplers agree bit for bit where their contracts say so.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "gq_internal.h"
+#include "sampler_core.h"
 #include "wave_util.h"
 
 namespace {
 
-typedef uint32_t u32;
-typedef unsigned long long u64;
+using namespace gqs;
 using gqw::h2f;
 
 constexpr int FB = 128, FT = 256, EPT = 8;  // blocks, threads, consecutive tokens per thread: slices of <= 2048 logits
@@ -38,7 +38,6 @@ static_assert((u32)FB * FT * EPT == GQ_SAMPLER_MAX_VOCAB, "one slice position pe
 constexpr u32 NBIN = 65536u, SPN = 65600u;  // bins of a histogram; entries of a suffix array (NBIN + 1, padded)
 constexpr u32 OLO = 0x03FFu, OHI = 0xFC00u;  // the bins of -inf and +inf: the ones outside hold NaN patterns and stay empty
 constexpr double WONE = 17592186044416.0;    // 2^44: the fixed-point unit of a mass (262144 tokens of w <= 1: sums < 2^63)
-constexpr float NINF = -__builtin_inff();
 constexpr u32 ALL = 0xFFFFFFFFu;
 
 // workspace (bytes): the report, the cut, the per-block partials, the histograms and their suffix arrays
@@ -55,18 +54,9 @@ struct Cut {  // at WS_CUT
     u64 zkept;       // sum of w over the candidates, fixed point
 };
 
-__device__ __forceinline__ u32 hash32(u32 x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
+__device__ __forceinline__ u32 image_of(float s) {
+    return ordered_key32(__builtin_bit_cast(u32, s));
 }
-__device__ __forceinline__ u32 ordered_key16(uint16_t h) { return (h & 0x8000u) ? (u32)(uint16_t)~h : ((u32)h | 0x8000u); }
-__device__ __forceinline__ uint16_t unordered_key16(u32 o) { return (o & 0x8000u) ? (uint16_t)(o & 0x7FFFu) : (uint16_t)~o; }
-__device__ __forceinline__ u32 ordered_key32(u32 b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
-__device__ __forceinline__ u32 unordered_key32(u32 o) { return (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o; }
-__device__ __forceinline__ bool is_nan16(uint16_t h) { return (h & 0x7FFFu) > 0x7C00u; }
-// (-0 is not < 0; the division is IEEE's, correctly rounded: the library is built without fast-math)
-__device__ __forceinline__ float penalise(float v, float rp) { return v < 0.f ? v * rp : v / rp; }
-__device__ __forceinline__ u32 image_of(float s) { return ordered_key32(__builtin_bit_cast(u32, s)); }
 // the images of bin o of the two histograms
 __device__ __forceinline__ u32 bin_image(u32 o, bool pen, float rp) {
     const float v = h2f(unordered_key16(o));
@@ -83,20 +73,14 @@ struct Toks {
 };
 struct Slice {
     u32 lo, hi;
-    int bid[4];
+    int bid[4] = {-1, -1, -1, -1};
 };
 __device__ __forceinline__ Slice slice_of(const Toks &t) {
     Slice s;
     const u32 per = (t.V + FB - 1) / FB;
     s.lo = min(blockIdx.x * per, t.V);
     s.hi = min(s.lo + per, t.V);
-    int nban = 0;
-    if (t.ban) {
-        nban = t.ban[0];
-        if (t.pos_io && t.pos_io[0] >= t.ban[1]) nban = 0;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) s.bid[i] = (t.ban && i < nban) ? t.ban[2 + i] : -1;
+    ban_ids(t.ban, t.pos_io, s.bid);
     return s;
 }
 // token gi of the slice: live or not, its raw pattern, whether the penalty applies, its value s
@@ -109,10 +93,9 @@ __device__ __forceinline__ Tok tok_of(const Toks &t, const Slice &sl, u32 gi) {
     Tok k{false, false, (uint16_t)0xFC00u, NINF};
     if (gi >= sl.hi) return k;
     k.h = t.logits[gi];
-    const bool banned = (int)gi == sl.bid[0] || (int)gi == sl.bid[1] || (int)gi == sl.bid[2] || (int)gi == sl.bid[3];
     const u32 bit = 1u << (gi & 31u);
     const bool sup = t.suppress && (t.suppress[gi >> 5] & bit);
-    k.live = !banned && !sup && !is_nan16(k.h);
+    k.live = !is_banned(gi, sl.bid) && !sup && !is_nan16(k.h);
     k.pen = t.rp != 1.0f && t.seen && (t.seen[gi >> 5] & bit);
     const float v = h2f(k.h);
     k.s = k.pen ? penalise(v, t.rp) : v;
@@ -452,7 +435,7 @@ __global__ void __launch_bounds__(FT) full_race(Toks t, const unsigned char *ws,
         for (u32 x = 0; x < w; x++) rank += wt[x];
     }
     float score = -3.0e38f;
-    int tokc = 0x7FFFFFFF;
+    int tokc = NO_TOKEN;
 #pragma unroll
     for (int e = 0; e < EPT; e++) {
         const u32 gi = sl.lo + tid * EPT + e, img = image_of(k[e].s);
@@ -462,11 +445,8 @@ __global__ void __launch_bounds__(FT) full_race(Toks t, const unsigned char *ws,
             rank++;
         }
         if (cand) {
-            // q ~ Exp(1) = -log(u), u in (0,1]; the random number is tied to the TOKEN id (sampler.hip's stream and expression)
-            const u32 r = hash32(seed ^ hash32(ctr * 0x9E3779B9u + gi + 1u));
-            const float u = ((float)(r >> 8) + 1.0f) * (1.0f / 16777216.0f);
-            const float sc = k[e].s / T - __logf(-__logf(u));
-            if (tokc == 0x7FFFFFFF || sc > score) {  // (ids ascend: an equal score keeps the lower id; a NaN score never replaces one)
+            const float sc = race_score(k[e].s, T, race_u(seed, ctr, gi));
+            if (tokc == NO_TOKEN || sc > score) {  // (ids ascend: an equal score keeps the lower id; a NaN score never replaces one)
                 score = sc;
                 tokc = (int)gi;
             }
@@ -476,7 +456,7 @@ __global__ void __launch_bounds__(FT) full_race(Toks t, const unsigned char *ws,
     for (int sh = 32; sh >= 1; sh >>= 1) {
         const float os = __shfl_xor(score, sh, 64);
         const int ot = __shfl_xor(tokc, sh, 64);
-        if (ot != 0x7FFFFFFF && (tokc == 0x7FFFFFFF || os > score || (os == score && ot < tokc))) { score = os; tokc = ot; }
+        if (better(os, ot, score, tokc)) { score = os; tokc = ot; }
     }
     if (l == 0) {
         rs[w] = score;
@@ -485,19 +465,15 @@ __global__ void __launch_bounds__(FT) full_race(Toks t, const unsigned char *ws,
     __syncthreads();
     if (tid == 0) {
         for (int x = 1; x < FT / 64; x++)
-            if (rt[x] != 0x7FFFFFFF && (tokc == 0x7FFFFFFF || rs[x] > score || (rs[x] == score && rt[x] < tokc))) { score = rs[x]; tokc = rt[x]; }
+            if (better(rs[x], rt[x], score, tokc)) { score = rs[x]; tokc = rt[x]; }
         best_score[blockIdx.x] = score;
         best_tok[blockIdx.x] = tokc;
     }
 }
 
 struct FinishArgs {
-    int *counter, *tok_io, *pos_io, *next_tok, *seq_out;
-    u32 seq_cap;
-    const uint16_t *emb_table;
-    uint16_t *x_out;
-    u32 dim;
-    float *ssq_out;
+    int *counter, *tok_io, *pos_io, *next_tok;
+    SampleEx ex;  // (ban and top_p are not read here: Toks and the scan have them)
     u32 *seen_out;
     float *lp_raw, *lp_drawn;
     u32 lp_cap;
@@ -509,19 +485,8 @@ __global__ void __launch_bounds__(1024) full_finish(Toks t, const unsigned char 
     __shared__ int chosen;
     __shared__ float lpM, lpLogZ;
     const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
-    if (w == 1 && F.lp_raw) {  // M = max m_b, Z = sum z_b exp(m_b - M) in a fixed butterfly (z == 0: a slice that contributes nothing)
-        const float pm0 = lp_part[l], pm1 = lp_part[64u + l], pz0 = lp_part[FB + l], pz1 = lp_part[FB + 64u + l];
-        float M = fmaxf(pm0, pm1);
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) M = fmaxf(M, __shfl_xor(M, sh, 64));
-        float Z = (pz0 == 0.f ? 0.f : pz0 * expf(pm0 - M)) + (pz1 == 0.f ? 0.f : pz1 * expf(pm1 - M));
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) Z += __shfl_xor(Z, sh, 64);
-        if (l == 0) {
-            lpM = M;
-            lpLogZ = logf(Z);
-        }
-    }
+    // the slices' partials -> (M, log Z), the numbers topn_merge forms from the same words
+    if (w == 1 && F.lp_raw) lse_merge128(lp_part[l], lp_part[64u + l], lp_part[FB + l], lp_part[FB + 64u + l], l, lpM, lpLogZ);
     __syncthreads();
     if (w == 0) {
         float score = best_score[l];
@@ -529,13 +494,13 @@ __global__ void __launch_bounds__(1024) full_finish(Toks t, const unsigned char 
         {
             const float os = best_score[64u + l];
             const int ot = best_tok[64u + l];
-            if (ot != 0x7FFFFFFF && (tokc == 0x7FFFFFFF || os > score || (os == score && ot < tokc))) { score = os; tokc = ot; }
+            if (better(os, ot, score, tokc)) { score = os; tokc = ot; }
         }
 #pragma unroll
         for (int sh = 32; sh >= 1; sh >>= 1) {
             const float os = __shfl_xor(score, sh, 64);
             const int ot = __shfl_xor(tokc, sh, 64);
-            if (ot != 0x7FFFFFFF && (tokc == 0x7FFFFFFF || os > score || (os == score && ot < tokc))) { score = os; tokc = ot; }
+            if (better(os, ot, score, tokc)) { score = os; tokc = ot; }
         }
         if (l == 0) {
             const Cut cut = *reinterpret_cast<const Cut *>(ws + WS_CUT);
@@ -551,13 +516,7 @@ __global__ void __launch_bounds__(1024) full_finish(Toks t, const unsigned char 
                 // (a == m: the first token's own value, infinite or not -- the difference is 0, as w_of has w = 1)
                 if (F.lp_drawn) ldrawn = (float)((double)(a == cut.m ? 0.f : a - cut.m) - log((double)cut.zkept * (1.0 / WONE)));
             }
-            // publish: sampler.hip's sample_publish
-            if (F.seen_out && (u32)tokc < t.V) atomicOr(F.seen_out + ((u32)tokc >> 5), 1u << ((u32)tokc & 31u));
-            F.next_tok[0] = tokc;
-            F.counter[0] = (int)(ctr + 1u);
-            if (F.tok_io) F.tok_io[0] = tokc;
-            if (F.seq_out && (u32)(p + 1) < F.seq_cap) F.seq_out[p + 1] = tokc;
-            if (F.pos_io) F.pos_io[0] = p + 1;
+            sample_publish(tokc, ctr, F.counter, F.tok_io, F.pos_io, F.next_tok, F.ex, F.seen_out, t.V);
             if ((u32)(p + 1) < F.lp_cap) {
                 if (F.lp_raw) F.lp_raw[p + 1] = lraw;
                 if (F.lp_drawn) F.lp_drawn[p + 1] = ldrawn;
@@ -565,27 +524,11 @@ __global__ void __launch_bounds__(1024) full_finish(Toks t, const unsigned char 
             chosen = tokc;
         }
     }
-    if (F.x_out) {  // the next step's hidden state: sampler.hip's sample_embed
+    if (F.ex.x_out) {
         __syncthreads();
-        u32 tk = (u32)chosen;
-        if (tk >= t.V) tk = 0;
-        float acc = 0.f;
-        for (u32 i = tid; i < F.dim / 8u; i += 1024u) {
-            const uint4 v = reinterpret_cast<const uint4 *>(F.emb_table + (size_t)tk * F.dim)[i];
-            gq_store_wt(reinterpret_cast<uint4 *>(F.x_out) + i, v);
-            const u32 wd[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const float a = (float)__builtin_bit_cast(_Float16, (uint16_t)(wd[k] & 0xFFFFu)), b = (float)__builtin_bit_cast(_Float16, (uint16_t)(wd[k] >> 16));
-                acc += a * a;
-                acc += b * b;
-            }
-        }
-        if (F.ssq_out) gq_store_wt(F.ssq_out + tid, acc);  // (1024 threads = GQ_SSQ_SLOTS)
+        sample_embed(chosen, tid, F.ex);
     }
 }
-static_assert(GQ_SSQ_SLOTS == 1024, "full_finish writes one hand-over slot per thread");
-
 }  // namespace
 
 extern "C" size_t gq_sample_full_ws_bytes(uint32_t vocab) { return vocab > GQ_SAMPLER_MAX_VOCAB ? 0 : WS_BYTES; }
@@ -595,16 +538,14 @@ extern "C" int gq_sample_full(const void *logits, uint32_t vocab, int top_k, flo
                               uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
                               uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, void *stream) {
     if (!logits || !counter || !ws || !next_tok) return gq_fail(GQ_EINVAL, "gq_sample_full: null pointer argument.");
-    if (vocab > GQ_SAMPLER_MAX_VOCAB) return gq_fail(GQ_ENOTSUP, "vocab too large for the fused sampler (<= 262144).");
+    if (int rc = sample_vocab_ok(vocab)) return rc;
     if (ws_bytes < WS_BYTES || ((uintptr_t)ws & 15u)) return gq_fail(GQ_EINVAL, "gq_sample_full: the workspace is gq_sample_full_ws_bytes(vocab) bytes, 16-byte aligned.");
     if (top_k < 0) return gq_fail(GQ_EINVAL, "gq_sample_full: top_k must be >= 0 (0 = no top-k filter).");
-    if (!(top_p > 0.f && top_p <= 1.f)) return gq_fail(GQ_EINVAL, "top_p must be in (0, 1] (1 = no nucleus filter).");
+    if (int rc = sample_top_p_ok(top_p, true)) return rc;
     if (!(min_p >= 0.f && min_p <= 1.f)) return gq_fail(GQ_EINVAL, "min_p must be in [0, 1] (0 = no min_p filter).");
-    if (!(repetition_penalty > 0.f) || !(repetition_penalty < INFINITY))
-        return gq_fail(GQ_EINVAL, "repetition_penalty must be finite and > 0 (1 = no penalty).");
-    if (!seen && repetition_penalty != 1.0f) return gq_fail(GQ_EINVAL, "repetition_penalty != 1 needs the `seen` token set.");
-    if (x_out && (!embed_table || dim % 8u)) return gq_fail(GQ_EINVAL, "x_out needs the embedding table and dim % 8 == 0.");
-    if (!x_out && ssq_out) return gq_fail(GQ_EINVAL, "ssq_out without x_out.");
+    if (int rc = sample_penalty_ok(repetition_penalty, seen)) return rc;
+    SampleEx ex{};
+    if (int rc = sample_extras(ex, vocab, top_p, ban, seq_out, seq_cap, embed_table, x_out, dim, ssq_out)) return rc;  // (ex.vocab = vocab)
     hipStream_t s = (hipStream_t)stream;
     unsigned char *w8 = (unsigned char *)ws;
     const bool rep = repetition_penalty != 1.0f;
@@ -618,8 +559,7 @@ extern "C" int gq_sample_full(const void *logits, uint32_t vocab, int top_k, flo
     hipLaunchKernelGGL(full_scan, dim3(1), dim3(1024), 0, s, w8, ScanArgs{top_k, top_p, min_p, temperature, repetition_penalty, rep ? 1 : 0});
     hipLaunchKernelGGL(full_ties, dim3(FB), dim3(FT), 0, s, t, (const unsigned char *)w8, ties);
     hipLaunchKernelGGL(full_race, dim3(FB), dim3(FT), 0, s, t, (const unsigned char *)w8, (const u32 *)ties, temperature, seed, (const int *)counter, best_score, best_tok);
-    const FinishArgs F{counter, tok_io, pos_io, next_tok, seq_out, seq_cap, (const uint16_t *)embed_table, (uint16_t *)x_out, dim, ssq_out, seen,
-                       lp_raw, lp_drawn, lp_cap, temperature};
+    const FinishArgs F{counter, tok_io, pos_io, next_tok, ex, seen, lp_raw, lp_drawn, lp_cap, temperature};
     hipLaunchKernelGGL(full_finish, dim3(1), dim3(1024), 0, s, t, (const unsigned char *)w8, (const float *)best_score, (const int *)best_tok,
                        (const float *)lp_part, F);
     GQ_HIP_CHECK(hipGetLastError());

@@ -19,23 +19,18 @@
 #include <stdint.h>
 
 #include "gq_internal.h"
+#include "sampler_core.h"
 #include "wave_util.h"
 
 namespace {
 
-typedef uint32_t u32;
+using namespace gqs;  // the value images and the log-sum-exp merge: the sampler's own, so a list's order and its log Z are the sampler's
 using gqw::h2f;
 
 constexpr int TB = 128, TT = 256, TN = GQ_TOPN_MAX;  // blocks, threads, candidate slots per block
 constexpr size_t WS_HEAD = 16;                      // {M, log Z} of the last call (the test hook), then uint2 cand[TB * TN]
 static_assert(GQ_TOPN_WS_BYTES == WS_HEAD + (size_t)TB * TN * 8, "the workspace of include/gq_hip.h");
 static_assert(GQ_SAMPLER_MAX_VOCAB == 2048 * TB && TB * TN < 4096, "slices of <= 2048 logits; a slot number is 12 bits of the merge key");
-constexpr float NINF = -__builtin_inff();
-
-// (sampler.hip's images, written out again: anonymous namespace)
-__device__ __forceinline__ u32 ordered_key16(uint16_t h) { return (h & 0x8000u) ? (u32)(uint16_t)~h : ((u32)h | 0x8000u); }
-__device__ __forceinline__ uint16_t unordered_key16(u32 o) { return (o & 0x8000u) ? (uint16_t)(o & 0x7FFFu) : (uint16_t)~o; }
-__device__ __forceinline__ bool is_nan16(uint16_t h) { return (h & 0x7FFFu) > 0x7C00u; }
 
 // the maximum of an unsigned word over the 64 lanes, in every lane: wave_reduce_bcast's DPP tree with 0, the identity, wherever a lane
 // has no source
@@ -123,19 +118,8 @@ __global__ void __launch_bounds__(TT) topn_merge(const uint2 *cand, int n, const
     wave_top_n<10>(key, n, [&](int j, u32 k) {
         if (l == 0) surv[w * TN + j] = k;
     });
-    if (w == 1) {  // M = max m_b, Z = sum z_b exp(m_b - M): the text of sample_stage2 / full_finish, operation for operation
-        const float pm0 = lse_part[l], pm1 = lse_part[64u + l], pz0 = lse_part[TB + l], pz1 = lse_part[TB + 64u + l];
-        float M = fmaxf(pm0, pm1);
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) M = fmaxf(M, __shfl_xor(M, sh, 64));
-        float Z = (pz0 == 0.f ? 0.f : pz0 * expf(pm0 - M)) + (pz1 == 0.f ? 0.f : pz1 * expf(pm1 - M));
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) Z += __shfl_xor(Z, sh, 64);
-        if (l == 0) {
-            lpM = M;
-            lpLogZ = logf(Z);
-        }
-    }
+    // (M, log Z) by the function sample_stage2 / full_finish formed theirs with, from the same words
+    if (w == 1) lse_merge128(lse_part[l], lse_part[64u + l], lse_part[TB + l], lse_part[TB + 64u + l], l, lpM, lpLogZ);
     __syncthreads();
     if (w != 0) return;
     u32 ks[2];
@@ -168,7 +152,7 @@ __global__ void __launch_bounds__(TT) topn_merge(const uint2 *cand, int n, const
 }  // namespace
 
 int gq_topn_check(uint32_t vocab, int n, const void *top_ids, const void *top_lps, const void *ws, const void *lse_source) {
-    if (vocab > GQ_SAMPLER_MAX_VOCAB) return gq_fail(GQ_ENOTSUP, "vocab too large for the fused sampler (<= 262144).");
+    if (int rc = gqs::sample_vocab_ok(vocab)) return rc;
     if (n < 1 || n > GQ_TOPN_MAX) return gq_fail(GQ_EINVAL, "top_n must be in 1..20.");
     if (!top_ids || !top_lps || !ws) return gq_fail(GQ_EINVAL, "top-n: top_ids, top_lps and topn_ws must not be NULL.");
     if ((uintptr_t)ws & 7u) return gq_fail(GQ_EINVAL, "top-n: topn_ws must be 8-byte aligned.");

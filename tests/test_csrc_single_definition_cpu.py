@@ -1,7 +1,8 @@
 """CPU: a source scan of guidedquant_amd/csrc -- the device helpers the kernel files share are defined ONCE (wave_util.h: casts,
 reductions, descriptors, the asm vector-memory requests; plane_mfma.h: the pieces of the plane arithmetic; qtip_xform.h: the element-wise
 arithmetic of the QTIP transform-in / transform-out; ap_exact.h: the fused prologues, the row request and the ordered reduction of the
-exact / wide / dq GEMV kernels), under names that tell their contracts apart, and the settled build-time forks are gone.  A second copy under the same name is how wave_reduce<true> came
+exact / wide / dq GEMV kernels; sampler_core.h: the value images, the penalty, the race, the ban list, the log-sum-exp merge, publishing and
+the embedding fold of the three sampler units), under names that tell their contracts apart, and the settled build-time forks are gone.  A second copy under the same name is how wave_reduce<true> came
 to mean two things (identity 0 in one file, -3e38 in another)."""
 import glob
 import os
@@ -28,7 +29,11 @@ DEVICE_FUNCTIONS = {
     # the fused prologues, the row request and the ordered reduction of the exact / wide / dq GEMV kernels
     "ap_exact.h": ["silu_mul_pk", "norm_pk", "rms_scale", "stage_items", "request_row", "silu_pair", "reduce_tree", "rows_epilogue_n",
                    "stage_x_natural"],
+    # what sampler.hip, sampler_full.hip and topn.hip compare bit for bit ("The sampler's shared arithmetic once")
+    "sampler_core.h": ["hash32", "ordered_key16", "unordered_key16", "ordered_key32", "unordered_key32", "is_nan16", "penalise",
+                       "race_u", "race_score", "better", "ban_ids", "is_banned", "lse_merge128", "sample_publish", "sample_embed"],
 }
+SAMPLER_UNITS = ["sampler.hip", "sampler_full.hip", "topn.hip"]
 OTHER_DEFINITIONS = {  # pattern -> the one file
     r"^\s*struct HotEnt\b": "plane_mfma.h",
     r"^\s*#\s*define\s+GQ_HOT_T\b": "plane_mfma.h",
@@ -86,6 +91,20 @@ def test_the_exact_gemv_rounding_points_stand_in_the_header_only():
     for f in units:
         assert "1.0f + __expf" not in SOURCES[f] and "gq_pin_f32" not in SOURCES[f], f
     assert "1.0f + __expf" in SOURCES["ap_exact.h"] and "gq_pin_f32" in SOURCES["ap_exact.h"]
+
+
+def test_the_race_stands_in_the_sampler_header_only():
+    # the stream's constant and the score's two logarithms: spelled in sampler_core.h, in no sampler kernel file (comments included)
+    for f in SAMPLER_UNITS:
+        assert "0x9E3779B9" not in SOURCES[f] and "__logf(-__logf(" not in SOURCES[f], f
+    assert SOURCES["sampler_core.h"].count("0x9E3779B9") == 1 and SOURCES["sampler_core.h"].count("__logf(-__logf(") == 1
+
+
+def test_the_sampler_units_include_the_header():
+    assert sorted(f for f, text in SOURCES.items() if '#include "sampler_core.h"' in text) == SAMPLER_UNITS
+    # a host refusal the entry points share is one string: one message per mistake
+    for msg in ("vocab too large for the fused sampler", "top_p must be in (0, 1]", "repetition_penalty must be finite", "ssq_out without x_out"):
+        assert files_matching(re.escape(msg)) == ["sampler_core.h"], msg
 
 
 def test_plane_core_stays_host_compilable():
