@@ -436,7 +436,12 @@ class AnyPrecisionForCausalLM(nn.Module):
         probable first, equal logits by ascending id, -1 where the vocabulary has fewer -- and `top_logprobs` fp32 [1, new, n], their
         log-probabilities against the log-sum-exp `logprobs` is taken against: where the drawn token is listed its entry equals
         `logprobs[0, j]` bit for bit.  Penalty, suppress list, min_new_tokens' EOS ban, temperature and the filters do not enter the list.
-        Both are cut at EOS where `sequences` is.  Two launches per token behind the sampler's (csrc/topn.hip)."""
+        Both are cut at EOS where `sequences` is.  Two launches per token behind the sampler's (csrc/topn.hip).
+        lm_head_dtype="int8" (route 1 only; `native=False`, `capture=True`, the CPU, or a request or checkpoint route 1 declines raise
+        ValueError("lm_head_dtype='int8': ..."), never a fall-back, and the keyword never reaches transformers): the decode step's head
+        reads a weight-only int8 copy of the lm_head with one fp32 scale per row (gq_dense_gemv_i8; `Transformer.set_lm_head_dtype`:
+        N*K + 4N bytes next to the fp16 head, which the prompt pass and `score` keep reading).  None / "fp16": a call without the keyword;
+        a request without it switches the decoder back and frees the copy."""
         prev_precision = self.precision
         if 'precision' in kwargs:
             self.set_precision(kwargs.pop('precision'))
@@ -446,6 +451,9 @@ class AnyPrecisionForCausalLM(nn.Module):
         # a request it cannot serve raises -- it never falls back to an fp16 cache silently.  (popped: it never reaches transformers)
         from .model import kv_cache_dtype_name
         kv = kv_cache_dtype_name(kwargs.pop('kv_cache_dtype', None))
+        # lm_head_dtype="int8": the fused decode step's head over a weight-only int8 copy (Transformer.set_lm_head_dtype).  Route 1 only,
+        # never a fall-back; None / "fp16" is a call without the keyword.  (popped as well; validated inside the try)
+        hd = kwargs.pop('lm_head_dtype', None)
         # output_logprobs=True: per-token log-probabilities from the fused sampler.  Route 1 only, never a fall-back.  (popped as well)
         lp = bool(kwargs.pop('output_logprobs', False))
         top_n = kwargs.pop('top_logprobs', None)  # (popped as well; validated inside the try: the precision is restored on a refusal)
@@ -454,6 +462,10 @@ class AnyPrecisionForCausalLM(nn.Module):
             if top_n is not None and not check_top_logprobs(top_n, lp):  # (the keyword, once given, asks for a list: None alone is "off" here)
                 raise ValueError(f"top_logprobs must be an integer in 1..20, not {top_n!r}")
             top_n = int(top_n or 0)  # (top_n > 0 implies lp: every refusal of output_logprobs below is one of top_logprobs)
+            from .head_q8 import lm_head_dtype_name
+            hd = lm_head_dtype_name(hd)
+            if hd == "int8" and (native is False or capture is True):
+                raise ValueError("lm_head_dtype='int8': served by the fused decode model only (not with native=False or capture=True)")
             if lp and (native is False or capture is True):
                 raise ValueError("output_logprobs=True: served by the fused decode model only (not with native=False or capture=True)")
             if kv == "fp8" and (native is False or capture is True):
@@ -465,6 +477,8 @@ class AnyPrecisionForCausalLM(nn.Module):
                 req, why = None, "the fused routes need the GPU"
             if kv == "fp8" and req is None:
                 raise ValueError("kv_cache_dtype='fp8': " + why)
+            if hd == "int8" and req is None:
+                raise ValueError("lm_head_dtype='int8': " + why)
             if lp and req is None:
                 raise ValueError("output_logprobs=True: " + why)
             if native is True and req is None:
@@ -475,6 +489,9 @@ class AnyPrecisionForCausalLM(nn.Module):
                 # see every tensor)
                 dec = self._native_decoder_or_none(self.precision, release_planes=native is True)
                 if dec is not None and req["T"] + req["max_new"] > dec.config.block_size:
+                    if hd == "int8":
+                        raise ValueError(f"lm_head_dtype='int8': prompt + max_new_tokens = {req['T'] + req['max_new']} exceeds the fused "
+                                         f"model's context ({dec.config.block_size})")
                     if lp:
                         raise ValueError(f"output_logprobs=True: prompt + max_new_tokens = {req['T'] + req['max_new']} exceeds the fused "
                                          f"model's context ({dec.config.block_size})")
@@ -487,6 +504,8 @@ class AnyPrecisionForCausalLM(nn.Module):
                     # (the captured step ends in the fused sampler: 128 blocks x 2048 logits at the most.  Qwen3's published vocabulary,
                     # 151936, is within it; a checkpoint beyond 262144 keeps `native_decoder()` / `decode_native` / `prefill_native`,
                     # not this route)
+                    if hd == "int8":
+                        raise ValueError(f"lm_head_dtype='int8': vocabulary {dec.config.vocab_size} exceeds the fused sampler's {SAMPLER_MAX_VOCAB}")
                     if lp:
                         raise ValueError(f"output_logprobs=True: vocabulary {dec.config.vocab_size} exceeds the fused sampler's {SAMPLER_MAX_VOCAB}")
                     if native is True:
@@ -495,7 +514,10 @@ class AnyPrecisionForCausalLM(nn.Module):
                 if dec is not None and kv == "fp8" and dec.kv8_unserved():
                     raise ValueError("kv_cache_dtype='fp8': " + dec.kv8_unserved())
                 if dec is not None:
-                    return self._generate_native(dec, req, kv_cache_dtype=kv, logprobs=lp, top_logprobs=top_n)
+                    return self._generate_native(dec, req, kv_cache_dtype=kv, logprobs=lp, top_logprobs=top_n, lm_head_dtype=hd)
+                if hd == "int8":
+                    why_not = getattr(self, "_no_native_reason", None)
+                    raise ValueError("lm_head_dtype='int8': this checkpoint has no fused decode form at %d bits%s" % (self.precision, ": " + why_not if why_not else ""))
                 if lp:
                     why_not = getattr(self, "_no_native_reason", None)
                     raise ValueError("output_logprobs=True: this checkpoint has no fused decode form at %d bits%s" % (self.precision, ": " + why_not if why_not else ""))
@@ -803,7 +825,7 @@ class AnyPrecisionForCausalLM(nn.Module):
             req["streamer"].end()
         return out
 
-    def _generate_native(self, dec, req, chunk=32, kv_cache_dtype="fp16", logprobs=False, top_logprobs=0):
+    def _generate_native(self, dec, req, chunk=32, kv_cache_dtype="fp16", logprobs=False, top_logprobs=0, lm_head_dtype="fp16"):
         from . import generate as gen
         ids, T, max_new = req["ids"].to(self.device), req["T"], req["max_new"]
         total = T + max_new
@@ -814,9 +836,15 @@ class AnyPrecisionForCausalLM(nn.Module):
         # only; a longer cache costs memory, not time).  Beyond 16384 positions the request's own length.
         cap = total if total > 16384 else max(256, 1 << (total - 1).bit_length())
         dec.setup_caches(1, min(cap, dec.config.block_size), kv_cache_dtype=kv_cache_dtype)
+        if dec.lm_head_dtype != lm_head_dtype:  # (the request's head, fp16 without the keyword)
+            self._evict("graph")  # (a switch re-allocates the step's buffers: no cached graph survives it, whichever head it was captured under)
+            try:
+                dec.set_lm_head_dtype(lm_head_dtype)
+            except ValueError as e:
+                raise ValueError(str(e) if str(e).startswith("lm_head_dtype='int8': ") else "lm_head_dtype='int8': " + str(e)) from None
         key = (self.precision, dec.max_seq_length, dec.kv_cache_dtype, req["temperature"], req["top_k"], req["top_p"], req["repetition_penalty"], req["suppress_tokens"]) \
             + ((("logprobs", True), ) if logprobs else ()) + ((("min_p", req["min_p"]), ) if req["min_p"] else ()) \
-            + ((("top_logprobs", top_logprobs), ) if top_logprobs else ())
+            + ((("top_logprobs", top_logprobs), ) if top_logprobs else ()) + ((("lm_head", "int8"), ) if lm_head_dtype == "int8" else ())
         graph = self._native_cache.get(("graph",) + key)
         if graph is None:
             self._evict("graph")
@@ -914,7 +942,7 @@ class AnyPrecisionForCausalLM(nn.Module):
         raise NotImplementedError("layer fusion inside the HF module tree is not implemented (as in the reference); use "
                                   "native_decoder(bitwidth) for the fused QKV / Up-Gate decode path")
 
-    def native_decoder(self, bitwidth: Optional[int] = None, release_planes: bool = False, kv_cache_dtype=None):
+    def native_decoder(self, bitwidth: Optional[int] = None, release_planes: bool = False, kv_cache_dtype=None, lm_head_dtype=None):
         """the same checkpoint as the fused gpt-fast `Transformer` (fused QKV / Up-Gate Any-Precision linears at one precision)
         whose bs=1 decode step runs as the captured 5-launches-per-layer HIP graph.  Built from the module tree's tensors BY
         REFERENCE: embedding, lm_head, norms, o_proj and down_proj are the same storage; q/k/v and gate/up are concatenated into the
@@ -923,8 +951,12 @@ class AnyPrecisionForCausalLM(nn.Module):
         GuidedQuant case: the module tree's own q/k/v/gate/up planes are released as the fused tensors are built (one copy of every
         weight; restored from the fused tensors the first time the module tree is used again through this wrapper, a linear's forward,
         `state_dict()` of the wrapper or of `self.model`, or `.to()` -- `_restore_module_tree`).  The default keeps the module tree whole
-        (the fused q/k/v/gate/up tensors are then a second copy: 1.1 GB for an 8B 2-bit model)."""
+        (the fused q/k/v/gate/up tensors are then a second copy: 1.1 GB for an 8B 2-bit model).
+        lm_head_dtype ("fp16" / "int8"; None: the decoder's head as it is): the decoder comes back with that head
+        (Transformer.set_lm_head_dtype: the int8 copy costs N*K + 4N bytes next to the shared fp16 head)."""
+        from .head_q8 import lm_head_dtype_name
         from .model import kv_cache_dtype_name
+        hd = None if lm_head_dtype is None else lm_head_dtype_name(lm_head_dtype)
         kv = None if kv_cache_dtype is None else kv_cache_dtype_name(kv_cache_dtype)
         bitwidth = bitwidth or min(self.precisions)
         dec = self._native_cache.get(("decoder", bitwidth))
@@ -940,6 +972,8 @@ class AnyPrecisionForCausalLM(nn.Module):
             if kv == "fp8" and dec.kv8_unserved():
                 raise ValueError("kv_cache_dtype='fp8': " + dec.kv8_unserved())
             dec.setup_caches(max(1, dec.max_batch_size), max(8, dec.max_seq_length), kv_cache_dtype=kv)
+        if hd is not None and hd != dec.lm_head_dtype:
+            dec.set_lm_head_dtype(hd)
         return dec
 
     def _layer_linears(self, layer):

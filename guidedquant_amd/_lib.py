@@ -30,7 +30,7 @@ EXPORTS = [
     "gq_token_set_build", "gq_sample_topk_rep", "gq_attn_prefill_supported", "gq_attn_prefill",
     "gq_rope_cache_rows_kv8", "gq_attn_decode_roped_kv8", "gq_attn_prefill_kv8", "gq_head_nll_ws_bytes", "gq_head_nll",
     "gq_sample_topk_lp", "gq_attn_prefill_packed", "gq_rope_cache_rows_packed",
-    "gq_sample_full_ws_bytes", "gq_sample_full", "gq_sample_topk_lp_topn", "gq_sample_full_topn",
+    "gq_sample_full_ws_bytes", "gq_sample_full", "gq_sample_topk_lp_topn", "gq_sample_full_topn", "gq_dense_gemv_i8",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -129,6 +129,7 @@ def lib():
         L.gq_attn_decode_roped_window.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, u32, vp]
         L.gq_attn_decode_qtip.argtypes = [ctypes.POINTER(GqQtipOut), vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, vp]
         L.gq_dense_gemv_f16.argtypes = [vp, vp, vp, u32, u32, vp, f32, vp]
+        L.gq_dense_gemv_i8.argtypes = [vp, vp, vp, vp, u32, u32, vp, f32, vp]  # (x, Wq, scale, out, N, K, norm_weight, eps, stream)
         L.gq_sample_topk.argtypes = [vp, u32, i32, f32, u32, vp, vp, vp, vp, vp, vp, vp]
         L.gq_sample_topk_ex.argtypes = [vp, u32, i32, f32, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp]
         L.gq_sample_topk_p.argtypes = [vp, u32, i32, f32, f32, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp]

@@ -201,6 +201,10 @@ class DecodeGraph:
         sig += [t.data_ptr() for b in m.layers for t in list(b.buffers(recurse=True)) + list(b.parameters(recurse=True))]
         if m._native is not None:
             sig += [m._native["x"].data_ptr(), m._native["logits"].data_ptr()]
+        # the head the step launches (Transformer.set_lm_head_dtype): a graph captured under one head does not replay under the other, nor
+        # over an int8 copy that has been made again
+        if getattr(m, "lm_head_dtype", "fp16") == "int8":
+            sig += ["int8"] + [t.data_ptr() for t in m.head_q8()]
         return tuple(sig)
 
     def check_bound(self):
@@ -441,11 +445,12 @@ def benchmark_decode(model: Transformer, device, num_samples=5, max_new_tokens=1
 
 def main(prompt=None, num_samples=5, max_new_tokens=100, batch_size=1, top_k=200, temperature=0.8, compile=2,
          compile_prefill=False, profile=None, device="cuda", model_name=None, backend=None, bitwidth=None,
-         checkpoint_path=None, config_path=None, dtype=None, print_result=False, random_init=False, kv_cache_dtype=None):
+         checkpoint_path=None, config_path=None, dtype=None, print_result=False, random_init=False, kv_cache_dtype=None, lm_head_dtype=None):
     """generate.py:268-389 -- same arguments and printed report.  `compile` selects the decode driver: 0 = eager per-token
     launches, >= 1 = the captured hipGraph of the decode step (the role torch.compile(mode='max-autotune') plays in the
     reference).  A tokenizer is only needed for a text prompt / --print_result; without one the BOS id of the model
-    family is used (the reference's benchmark setting, prompt=None)."""
+    family is used (the reference's benchmark setting, prompt=None).  lm_head_dtype="int8": the fused decode step's head over a
+    weight-only int8 copy (Transformer.set_lm_head_dtype; ValueError on the CPU or a model that is not fp16)."""
     print(f"Using device={device}")
     dtype = {"float16": torch.float16, "bfloat16": torch.bfloat16, "float32": torch.float32, None: torch.float16}.get(dtype, dtype)
     if batch_size != 1:
@@ -468,6 +473,8 @@ def main(prompt=None, num_samples=5, max_new_tokens=100, batch_size=1, top_k=200
     torch.manual_seed(1234)
     model_size, params = _get_model_size(model)
     model.setup_caches(1, prompt_length + max_new_tokens, kv_cache_dtype=kv_cache_dtype)
+    if lm_head_dtype is not None:
+        model.set_lm_head_dtype(lm_head_dtype)
     use_graph = bool(compile) and "cuda" in str(device)
     graph = DecodeGraph(model, device, temperature=temperature, top_k=top_k) if use_graph else None
     tps = []
@@ -523,6 +530,9 @@ if __name__ == "__main__":
     parser.add_argument('--random_init', action='store_true')
     parser.add_argument('--kv_cache_dtype', type=str, default=None, choices=["fp16", "fp8"],
                         help='fp8: the KV cache as e4m3 codes, scale 1.0 per head (fused Any-Precision models; default fp16)')
+    parser.add_argument('--lm_head_dtype', type=str, default=None, choices=["fp16", "int8"],
+                        help='int8: the decode step reads a weight-only int8 copy of the lm_head, one scale per row (default fp16)')
     a = parser.parse_args()
     main(a.prompt, a.num_samples, a.max_new_tokens, a.batch_size, a.top_k, a.temperature, a.compile, a.compile_prefill, a.profile,
-         a.device, a.model_name, a.backend, a.bitwidth, a.checkpoint_path, a.config_path, a.dtype, a.print_result, a.random_init, a.kv_cache_dtype)
+         a.device, a.model_name, a.backend, a.bitwidth, a.checkpoint_path, a.config_path, a.dtype, a.print_result, a.random_init, a.kv_cache_dtype,
+         a.lm_head_dtype)

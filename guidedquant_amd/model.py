@@ -404,19 +404,64 @@ class Transformer(nn.Module):
         self.cache_initialized = False
         self.fuse_linears = fuse_linears
         self._native = None
+        self.lm_head_dtype = "fp16"  # set_lm_head_dtype
+        self._head_q8 = None         # (q int8 [V, D], scale fp32 [V], the output.weight they were made from): plain attributes, not buffers
         # new weights (copied in place or assigned): the native step's buffers / launch plans / row pairing are rebuilt lazily
-        self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module._reset_native())
+        self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module._weights_changed())
 
     def _reset_native(self):
         self._native = None
         self._native_kind_cache = None
         self._alloc_gen = getattr(self, "_alloc_gen", 0) + 1  # captured graphs re-validate their pointers (generate.DecodeGraph.step)
 
+    def _weights_changed(self):
+        self._head_q8 = None  # (the int8 copy of the head follows output.weight; a cache that grows does not come through here)
+        self._reset_native()
+
     def _apply(self, fn, *a, **k):
         # .to() / .half() / .cuda() move or re-allocate every tensor a captured decode graph points at
         r = super()._apply(fn, *a, **k)
-        self._reset_native()
+        self._weights_changed()
         return r
+
+    def set_lm_head_dtype(self, name) -> None:
+        """The head of the fused decode step: None / "fp16" (the default: gq_dense_gemv_f16 over `output.weight`, as the reference) or
+        "int8" (gq_dense_gemv_i8 over a weight-only int8 copy with one fp32 scale per row, head_q8.quantize_rows_int8).  "int8"
+        quantises `output.weight` once, on its device, into tensors that are no part of the state_dict, and keeps `output.weight`: the
+        prompt pass, `score()` and the module forward read the fp16 head, a tied embedding is untouched.  Cost: N*K + 4N bytes NEXT TO
+        the fp16 head (0.53 GB for the 128256 x 4096 head of Llama-3.1-8B).  The copy is rebuilt when `output.weight` is another tensor
+        or has been written (load_state_dict, .to() / .half(), an in-place write), not when the caches grow.  ValueError on a CPU model
+        or a head that is not fp16."""
+        from .head_q8 import lm_head_dtype_name
+        name = lm_head_dtype_name(name)
+        if name == "int8":
+            self._head_q8_check()
+        self.lm_head_dtype = name
+        self._head_q8 = None
+        if name == "int8":
+            self.head_q8()
+        self._reset_native()
+
+    def _head_q8_check(self):
+        w = self.output.weight
+        if not w.is_cuda:
+            raise ValueError("lm_head_dtype='int8': the int8 head is served by the fused HIP decode step only, and the model is on the CPU")
+        if w.dtype != torch.float16:
+            raise ValueError(f"lm_head_dtype='int8': output.weight is {w.dtype}, not fp16")
+
+    def head_q8(self):
+        """(q int8 [V, D], scale fp32 [V]) of an int8-head model, made again where `output.weight` changed since they were made"""
+        from .head_q8 import quantize_rows_int8
+        assert self.lm_head_dtype == "int8", "head_q8: the model's head is fp16 (set_lm_head_dtype('int8'))"
+        w = self.output.weight
+        made = self._head_q8
+        key = (w.data_ptr(), 0 if w.is_inference() else w._version)  # (an inference tensor counts no writes: it cannot be written)
+        if made is None or made[2] != key:
+            self._head_q8_check()
+            q, scale = quantize_rows_int8(w.detach())
+            self._head_q8 = made = (q, scale, key)
+            self._alloc_gen = getattr(self, "_alloc_gen", 0) + 1  # (new tensors: captured graphs re-validate their pointers)
+        return made[0], made[1]
 
     @classmethod
     def from_name(cls, dtype, name: str, linear_class=nn.Linear, linear_kwargs=None, halve_layers=False,

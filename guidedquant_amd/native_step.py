@@ -176,7 +176,14 @@ class StepState(_Keyed):
                                               self.layer_split[layer], _ptr(self.attn_ws), self.layer_window[layer] or 0, sp), "gq_attn_decode_roped_kv8")
 
     def head(self, x):
+        """the one call site of the dense GEMV (both families): final RMSNorm + lm_head -> the fp16 logits.  An int8-head model
+        (Transformer.set_lm_head_dtype) launches gq_dense_gemv_i8 over its int8 copy, every other model what it always launched."""
         m, c = self.m, self.m.config
+        if getattr(m, "lm_head_dtype", "fp16") == "int8":
+            q, scale = m.head_q8()
+            _lib.check(_lib.lib().gq_dense_gemv_i8(x.data_ptr(), q.data_ptr(), scale.data_ptr(), self.logits.data_ptr(), c.vocab_size,
+                                                   c.dim, m.norm.weight.data_ptr(), c.norm_eps, _lib.current_stream_ptr()), "lm_head (int8)")
+            return self.logits
         _lib.check(_lib.lib().gq_dense_gemv_f16(x.data_ptr(), m.output.weight.data_ptr(), self.logits.data_ptr(), c.vocab_size,
                                                 c.dim, m.norm.weight.data_ptr(), c.norm_eps, _lib.current_stream_ptr()), "lm_head")
         return self.logits

@@ -96,6 +96,8 @@ class PipelinedDecoder:
                  feedback_group=None, use_graphs: Optional[bool] = None, seed: int = 1234, hop: Optional[str] = None):
         if getattr(model, "kv_cache_dtype", "fp16") == "fp8":  # (the stages address the cache slots themselves, two bytes per element)
             raise NotImplementedError("fp8 KV cache: layer-pipelined decode has no fp8 form (setup_caches(.., kv_cache_dtype='fp16'))")
+        if getattr(model, "lm_head_dtype", "fp16") == "int8":  # (the stages were measured and tested with the fp16 head only)
+            raise NotImplementedError("int8 lm_head: layer-pipelined decode has no int8 form (set_lm_head_dtype('fp16'))")
         if getattr(model.config, "layer_windows", None) is not None:  # (the stages build their masks and slots themselves)
             raise NotImplementedError("layer-pipelined decode has no sliding-window form (layer_windows)")
         self.model, self.rank, self.world, self.layers = model, rank, world, layers

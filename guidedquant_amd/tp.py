@@ -39,6 +39,8 @@ class TensorParallelDecoder:
         c = model.config
         if getattr(model, "kv_cache_dtype", "fp16") == "fp8":  # (this class launches attention itself, over fp16 caches)
             raise NotImplementedError("fp8 KV cache: tensor-parallel decode has no fp8 form (setup_caches(.., kv_cache_dtype='fp16'))")
+        if getattr(model, "lm_head_dtype", "fp16") == "int8":  # (this class launches its vocabulary slice of the fp16 head itself)
+            raise NotImplementedError("int8 lm_head: tensor-parallel decode has no int8 form (set_lm_head_dtype('fp16'))")
         assert model.fuse_linears, "tensor-parallel decode takes the fused (wqkv / w1w3) Any-Precision model"
         if c.qk_norm or c.attn_bias or c.n_head * c.head_dim != c.dim:
             # (this class builds its own launches: no QK-norm attention, no q / k / v bias, and the attention output is exchanged as a

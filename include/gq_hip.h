@@ -666,6 +666,18 @@ int gq_anyprec_gemv_qkv_rope_attn(const void *x, void *q_out, const uint32_t *qw
 int gq_dense_gemv_f16(const void *x, const void *W, void *out, uint32_t N, uint32_t K, const void *norm_weight, float eps,
                       void *stream);
 
+/* out[n] = fp16( scale[n] * sum_k rmsnorm?(x)[k] * Wq[n][k] )      the opt-in int8 lm_head (csrc/head_q8.hip): weight-only, one fp32
+ * scale per output row (guidedquant_amd/head_q8.py::quantize_rows_int8 makes Wq and scale from an fp16 head).
+ *   x, norm_weight, eps, out   what they are in gq_dense_gemv_f16; the RMSNorm prologue is that entry's own text, with its rounding points
+ *                              (the statistic in fp32, x * scale rounded to fp16, the fp16 product with the weight)
+ *   Wq      int8 [N][K], row-major, 16-byte aligned; every code is turned into its signed fp16 value before the product
+ *   scale   fp32 [N], 4-byte aligned; the fp32 sum of a row is multiplied by it (one fp32 rounding), then rounded to fp16
+ * K % 512 == 0 and the fp16 activations in LDS as in gq_dense_gemv_f16 (K <= 81408); anything else, a null or a misaligned pointer:
+ * GQ_EINVAL / GQ_ENOTSUP, nothing launched.  Rows past N are never written, no byte outside Wq[0 .. N*K) or scale[0 .. N) is read.
+ * Plan: GQ_DENSE_I8_BPC blocks per compute unit (default 3), GQ_DENSE_I8_RPB rows per block (a multiple of 16) instead. */
+int gq_dense_gemv_i8(const void *x, const void *Wq, const float *scale, void *out, uint32_t N, uint32_t K, const void *norm_weight, float eps,
+                     void *stream);
+
 /* Top-k sampling with the reference's distribution (inference/generate.py:53-73: logits / max(T,1e-5), top-k, softmax,
  * exponential-race draw).  work_val / work_idx: 128*32 floats / ints of scratch; counter: one int of RNG state in
  * device memory (incremented per call).  If tok_io / pos_io are non-NULL the sampled token is written to *tok_io and
