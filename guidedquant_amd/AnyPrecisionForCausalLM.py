@@ -441,7 +441,18 @@ class AnyPrecisionForCausalLM(nn.Module):
         ValueError("lm_head_dtype='int8': ..."), never a fall-back, and the keyword never reaches transformers): the decode step's head
         reads a weight-only int8 copy of the lm_head with one fp32 scale per row (gq_dense_gemv_i8; `Transformer.set_lm_head_dtype`:
         N*K + 4N bytes next to the fp16 head, which the prompt pass and `score` keep reading).  None / "fp16": a call without the keyword;
-        a request without it switches the decoder back and frees the copy."""
+        a request without it switches the decoder back and frees the copy.
+        frequency_penalty / presence_penalty (finite numbers) and logit_bias ({token id: finite bias}; the ids as ints or, as serving APIs
+        send them, as strings) -- route 1 only; `native=False`, `capture=True` or a request route 1 declines raise
+        ValueError("frequency_penalty: ...") (the name of the first of the three that is active), never a fall-back, and the keywords never
+        reach transformers: a serving API's additive adjustments inside the fused sampler's launches (gq_sample_topk_adj /
+        gq_sample_full_adj).  For a token with a listed bias b, or one THIS request has generated c > 0 times, the logit v becomes
+        fp16((v + b) - (c > 0 ? frequency_penalty * c + presence_penalty : 0)), every operation rounded in fp32 and the result to fp16;
+        every other token keeps its logit.  The prompt does not count (OpenAI's / vLLM's meaning; repetition_penalty, transformers'
+        processor, does include it).  They are logits processors, not warpers: a greedy request applies them too.  The additive terms
+        come first and the repetition penalty behind them (vLLM penalises repetition first); transformers' sequence_bias adds to fp32
+        scores without the rounding to fp16.  `logprobs` and `top_logprobs` stay the unprocessed distribution's, `sampled_logprobs`
+        sees the adjustment.  0, 0 and None / {}: a call without the keywords."""
         prev_precision = self.precision
         if 'precision' in kwargs:
             self.set_precision(kwargs.pop('precision'))
@@ -457,7 +468,17 @@ class AnyPrecisionForCausalLM(nn.Module):
         # output_logprobs=True: per-token log-probabilities from the fused sampler.  Route 1 only, never a fall-back.  (popped as well)
         lp = bool(kwargs.pop('output_logprobs', False))
         top_n = kwargs.pop('top_logprobs', None)  # (popped as well; validated inside the try: the precision is restored on a refusal)
+        # frequency_penalty / presence_penalty / logit_bias: additive adjustments inside the fused sampler.  Route 1 only, never a fall-back.
+        adj = {k: kwargs.pop(k, None) for k in ("frequency_penalty", "presence_penalty", "logit_bias")}  # (popped as well; validated inside the try)
         try:
+            from .fused_sampler import check_additive_penalty, check_logit_bias
+            adj = dict(frequency_penalty=check_additive_penalty("frequency_penalty", adj["frequency_penalty"]),
+                       presence_penalty=check_additive_penalty("presence_penalty", adj["presence_penalty"]),
+                       logit_bias=check_logit_bias(adj["logit_bias"], int(getattr(self.config, "vocab_size", 0) or 0)))
+            adj = {k: v for k, v in adj.items() if v}  # (the active ones; the first names the refusals below)
+            adj_name = next(iter(adj), None)
+            if adj_name and (native is False or capture is True):
+                raise ValueError(f"{adj_name}: served by the fused decode model only (not with native=False or capture=True)")
             from .fused_sampler import check_top_logprobs
             if top_n is not None and not check_top_logprobs(top_n, lp):  # (the keyword, once given, asks for a list: None alone is "off" here)
                 raise ValueError(f"top_logprobs must be an integer in 1..20, not {top_n!r}")
@@ -481,6 +502,8 @@ class AnyPrecisionForCausalLM(nn.Module):
                 raise ValueError("lm_head_dtype='int8': " + why)
             if lp and req is None:
                 raise ValueError("output_logprobs=True: " + why)
+            if adj_name and req is None:
+                raise ValueError(f"{adj_name}: " + why)
             if native is True and req is None:
                 raise ValueError("native=True: " + why)
             if req is not None and native is not False:
@@ -495,6 +518,9 @@ class AnyPrecisionForCausalLM(nn.Module):
                     if lp:
                         raise ValueError(f"output_logprobs=True: prompt + max_new_tokens = {req['T'] + req['max_new']} exceeds the fused "
                                          f"model's context ({dec.config.block_size})")
+                    if adj_name:
+                        raise ValueError(f"{adj_name}: prompt + max_new_tokens = {req['T'] + req['max_new']} exceeds the fused model's "
+                                         f"context ({dec.config.block_size})")
                     if native is True:
                         raise ValueError(f"native=True: prompt + max_new_tokens = {req['T'] + req['max_new']} exceeds the fused model's "
                                          f"context ({dec.config.block_size})")
@@ -508,19 +534,24 @@ class AnyPrecisionForCausalLM(nn.Module):
                         raise ValueError(f"lm_head_dtype='int8': vocabulary {dec.config.vocab_size} exceeds the fused sampler's {SAMPLER_MAX_VOCAB}")
                     if lp:
                         raise ValueError(f"output_logprobs=True: vocabulary {dec.config.vocab_size} exceeds the fused sampler's {SAMPLER_MAX_VOCAB}")
+                    if adj_name:
+                        raise ValueError(f"{adj_name}: vocabulary {dec.config.vocab_size} exceeds the fused sampler's {SAMPLER_MAX_VOCAB}")
                     if native is True:
                         raise ValueError(f"native=True: vocabulary {dec.config.vocab_size} exceeds the fused sampler's {SAMPLER_MAX_VOCAB}")
                     dec = None
                 if dec is not None and kv == "fp8" and dec.kv8_unserved():
                     raise ValueError("kv_cache_dtype='fp8': " + dec.kv8_unserved())
                 if dec is not None:
-                    return self._generate_native(dec, req, kv_cache_dtype=kv, logprobs=lp, top_logprobs=top_n, lm_head_dtype=hd)
+                    return self._generate_native(dec, req, kv_cache_dtype=kv, logprobs=lp, top_logprobs=top_n, lm_head_dtype=hd, adjust=adj)
                 if hd == "int8":
                     why_not = getattr(self, "_no_native_reason", None)
                     raise ValueError("lm_head_dtype='int8': this checkpoint has no fused decode form at %d bits%s" % (self.precision, ": " + why_not if why_not else ""))
                 if lp:
                     why_not = getattr(self, "_no_native_reason", None)
                     raise ValueError("output_logprobs=True: this checkpoint has no fused decode form at %d bits%s" % (self.precision, ": " + why_not if why_not else ""))
+                if adj_name:
+                    why_not = getattr(self, "_no_native_reason", None)
+                    raise ValueError("%s: this checkpoint has no fused decode form at %d bits%s" % (adj_name, self.precision, ": " + why_not if why_not else ""))
                 if kv == "fp8":
                     why_not = getattr(self, "_no_native_reason", None)
                     raise ValueError("kv_cache_dtype='fp8': no fused decode model serves this request%s" % (": " + why_not if why_not else " (context or vocabulary beyond it)"))
@@ -803,6 +834,7 @@ class AnyPrecisionForCausalLM(nn.Module):
         if req.get("do_sample"):
             sampler.reseed(self._fresh_rng_word())
         sampler.set_history(ids32)  # (the penalty's token set: all T prompt tokens, rebuilt per request)
+        sampler.reset_generated()  # (the counts of a frequency / presence penalty: this request has generated nothing yet)
         if req["streamer"] is not None:
             req["streamer"].put(ids.cpu())
         done, cut = 0, None
@@ -825,7 +857,7 @@ class AnyPrecisionForCausalLM(nn.Module):
             req["streamer"].end()
         return out
 
-    def _generate_native(self, dec, req, chunk=32, kv_cache_dtype="fp16", logprobs=False, top_logprobs=0, lm_head_dtype="fp16"):
+    def _generate_native(self, dec, req, chunk=32, kv_cache_dtype="fp16", logprobs=False, top_logprobs=0, lm_head_dtype="fp16", adjust=None):
         from . import generate as gen
         ids, T, max_new = req["ids"].to(self.device), req["T"], req["max_new"]
         total = T + max_new
@@ -844,7 +876,8 @@ class AnyPrecisionForCausalLM(nn.Module):
                 raise ValueError(str(e) if str(e).startswith("lm_head_dtype='int8': ") else "lm_head_dtype='int8': " + str(e)) from None
         key = (self.precision, dec.max_seq_length, dec.kv_cache_dtype, req["temperature"], req["top_k"], req["top_p"], req["repetition_penalty"], req["suppress_tokens"]) \
             + ((("logprobs", True), ) if logprobs else ()) + ((("min_p", req["min_p"]), ) if req["min_p"] else ()) \
-            + ((("top_logprobs", top_logprobs), ) if top_logprobs else ()) + ((("lm_head", "int8"), ) if lm_head_dtype == "int8" else ())
+            + ((("top_logprobs", top_logprobs), ) if top_logprobs else ()) + ((("lm_head", "int8"), ) if lm_head_dtype == "int8" else ()) \
+            + tuple((k, tuple(sorted(v.items())) if isinstance(v, dict) else v) for k, v in sorted((adjust or {}).items()))
         graph = self._native_cache.get(("graph",) + key)
         if graph is None:
             self._evict("graph")
@@ -854,7 +887,7 @@ class AnyPrecisionForCausalLM(nn.Module):
                                     seed=self._SAMPLER_SEED, temperature=req["temperature"], top_k=req["top_k"], top_p=req["top_p"], steps_per_replay=8,
                                     repetition_penalty=req["repetition_penalty"], suppress_tokens=req["suppress_tokens"],
                                     **({"logprobs": True} if logprobs else {}), **({"min_p": req["min_p"]} if req["min_p"] else {}),
-                                    **({"top_logprobs": top_logprobs} if top_logprobs else {}))
+                                    **({"top_logprobs": top_logprobs} if top_logprobs else {}), **(adjust or {}))
             self._native_cache[("graph",) + key] = graph
         ids32 = ids.view(-1).to(torch.int32)
 

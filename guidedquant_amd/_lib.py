@@ -31,6 +31,7 @@ EXPORTS = [
     "gq_rope_cache_rows_kv8", "gq_attn_decode_roped_kv8", "gq_attn_prefill_kv8", "gq_head_nll_ws_bytes", "gq_head_nll",
     "gq_sample_topk_lp", "gq_attn_prefill_packed", "gq_rope_cache_rows_packed",
     "gq_sample_full_ws_bytes", "gq_sample_full", "gq_sample_topk_lp_topn", "gq_sample_full_topn", "gq_dense_gemv_i8",
+    "gq_token_bias_build", "gq_sample_topk_adj", "gq_sample_full_adj",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -48,6 +49,11 @@ _VOID = ("gq_reset_env_cache", "gq_debug_set_timing_buffer", "gq_debug_set_qtip_
 class GqQtipIn(ctypes.Structure):  # include/gq_hip.h
     _fields_ = [("trellis", ctypes.c_void_p), ("SU", ctypes.c_void_p), ("tlut", ctypes.c_void_p), ("y32", ctypes.c_void_p),
                 ("M", ctypes.c_uint32)]
+
+
+class GqSampleAdjust(ctypes.Structure):  # include/gq_hip.h: the additive adjustments of gq_sample_topk_adj / gq_sample_full_adj
+    _fields_ = [("frequency_penalty", ctypes.c_float), ("presence_penalty", ctypes.c_float), ("bias_set", ctypes.c_void_p),
+                ("bias", ctypes.c_void_p), ("out_set", ctypes.c_void_p), ("out_count", ctypes.c_void_p)]
 
 
 class GqQtipXf(ctypes.Structure):
@@ -144,6 +150,10 @@ def lib():
         # (the top-n forms: top_n, top_ids, top_lps, topn_ws in front of the stream)
         L.gq_sample_topk_lp_topn.argtypes = L.gq_sample_topk_lp.argtypes[:-1] + [i32, vp, vp, vp, vp]
         L.gq_sample_full_topn.argtypes = L.gq_sample_full.argtypes[:-1] + [i32, vp, vp, vp, vp]
+        # (the adjusted forms: the top-n form's parameters, then the GqSampleAdjust in front of the stream)
+        L.gq_sample_topk_adj.argtypes = L.gq_sample_topk_lp_topn.argtypes[:-1] + [ctypes.POINTER(GqSampleAdjust), vp]
+        L.gq_sample_full_adj.argtypes = L.gq_sample_full_topn.argtypes[:-1] + [ctypes.POINTER(GqSampleAdjust), vp]
+        L.gq_token_bias_build.argtypes = [vp, vp, u32, u32, vp, vp, vp]  # (ids, values, n, vocab, bias_set, bias, stream)
         L.gq_sample_full_ws_bytes.restype = ctypes.c_size_t
         L.gq_token_set_build.argtypes = [vp, u32, u32, vp, i32, vp]
         L.gq_anyprec_gemv_cpu.argtypes = [vp, vp, vp, vp, u32, u32, u32, i32, i32, i32]

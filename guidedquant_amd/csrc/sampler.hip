@@ -123,6 +123,9 @@ struct Opt<true, T> {
 // The two kernels below are ONE text for every instance: <REP, LP> = <false, false> is what gq_sample_topk / _ex / _p launch (and what
 // bench.py and a default generate() run), <true, false> serves gq_sample_topk_rep, <., true> gq_sample_topk_lp.  The instructions of the
 // <false, false> instances are pinned (tools/cmp_kernels.py against the build before a change, profiles/sampler_unify_cmp_kernels.txt).
+// <true, true> with ADJ serves gq_sample_topk_adj (frequency / presence penalty, logit bias: a member token's adjusted fp16 pattern h' --
+// gqs::adjust16 -- stands in for its logit at the key site of stage 1, stage 2 counts the drawn token); ADJ = false leaves every other
+// instance the instructions it had (profiles/sampler_adjust_cmp_kernels.txt).
 // What moves an instance is not the sharing but the SHAPE of an expression: a conversion inside or outside the arm of a select turns a
 // v_cndmask into a branch, or four narrow loads into one wide one.  Where an instance's sequence or its measured time needs another
 // shape the text forks at compile time, on PLAIN or LP, under a comment `fork (site)` that names the instruction difference (DESIGN.md,
@@ -136,11 +139,12 @@ template <> struct Key1<false> { typedef u32 T; };
 // key = (order-preserving image of the value) << LB | (2^LB - 1 - position in the slice): the 16 bits of the fp16 logit, or (REP) the 32
 // bits of the penalised one.  The words of the two token sets are read where the logits are: a thread's EPT <= 8 consecutive tokens lie
 // in at most two of them (a slice starts at any token, not at a multiple of 32).
-template <int KM, int EPT, int LB, bool REP, bool LP>
+template <int KM, int EPT, int LB, bool REP, bool LP, bool ADJ>
 __global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32 V, float *cand_val, int *cand_idx, const int *ban, const int *pos_io,
-                                                     Opt<REP || LP, SampleRep> rep_, Opt<LP, float *> lp_ws_) {
+                                                     Opt<REP || LP, SampleRep> rep_, Opt<LP, float *> lp_ws_, Opt<ADJ, SampleAdj> adj_) {
     typedef typename Key1<REP>::T KeyT;
     constexpr bool PLAIN = !REP && !LP;
+    static_assert(!ADJ || (REP && LP), "the adjustment is built on the general form only");
     constexpr int VB = REP ? 32 : 16;  // value bits of a key
     static_assert(256 * EPT == 1 << LB && EPT <= 8 && VB + LB <= 8 * (int)sizeof(KeyT),
                   "a slice is one position per key of the block; a thread's tokens span two set words");
@@ -150,6 +154,7 @@ __global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32
     __shared__ float lpm[4], lpz[4];  // (LP) a wave's maximum and its sum of exp(v - maximum)
     const SampleRep rep = rep_.get();
     float *const lp_ws = lp_ws_.get();
+    const SampleAdj adj = adj_.get();
     const u32 per = (V + SAMP_BLOCKS - 1) / SAMP_BLOCKS;  // <= 256 * EPT
     const u32 lo = blockIdx.x * per, hi = min(lo + per, V);
     const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
@@ -161,6 +166,12 @@ __global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32
         const u32 w0 = g0 >> 5, w1 = min(g0 + (u32)EPT - 1u, hi - 1u) >> 5;
         if (rep.seen) sbits = ((u64)rep.seen[w0] | ((u64)(w1 != w0 ? rep.seen[w1] : 0u) << 32)) >> (g0 & 31u);
         if (rep.suppress) pbits = ((u64)rep.suppress[w0] | ((u64)(w1 != w0 ? rep.suppress[w1] : 0u) << 32)) >> (g0 & 31u);
+    }
+    u64 bbits = 0ull, cbits = 0ull;  // (ADJ) bit e: the token has a listed bias / has been generated: the two ways of being a member
+    if (ADJ && g0 < hi) {
+        const u32 w0 = g0 >> 5, w1 = min(g0 + (u32)EPT - 1u, hi - 1u) >> 5;
+        if (adj.bias_set) bbits = ((u64)adj.bias_set[w0] | ((u64)(w1 != w0 ? adj.bias_set[w1] : 0u) << 32)) >> (g0 & 31u);
+        if (adj.out_set) cbits = ((u64)adj.out_set[w0] | ((u64)(w1 != w0 ? adj.out_set[w1] : 0u) << 32)) >> (g0 & 31u);
     }
     KeyT key[EPT];
     float raw[EPT];  // (LP) every logit of the slice, the banned and the suppressed ones too; -inf past the end
@@ -180,6 +191,8 @@ __global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32
         KeyT k = 0;
         if constexpr (REP) {
             if (cand) {
+                // (ADJ) a member's adjusted pattern h' stands in for its logit from here on; raw[e] above stays raw
+                if constexpr (ADJ) hb = adjust_token(hb, gi, (bbits >> e) & 1ull, (cbits >> e) & 1ull, adj);
                 const float v = h2f(hb), sv = ((sbits >> e) & 1ull) ? penalise(v, rep.rp) : v;
                 if (sv == sv) k = ((u64)ordered_key32(__builtin_bit_cast(u32, sv)) << LB) | (u64)(LMASK - li);
             }
@@ -254,10 +267,11 @@ __global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32
 // no atomics) and leaves (M, log Z) in LDS; wave 0 loads the raw logits of its candidates in front of the nucleus code (the latency
 // hides behind it), normalises the kept candidates' a_c = s_c / T behind the race, and lane 0 stores the two numbers at the index
 // seq_out uses.
-template <int KM, int IB, bool REP, bool LP>
+template <int KM, int IB, bool REP, bool LP, bool ADJ>
 __global__ void __launch_bounds__(1024) sample_stage2(const float *cand_val, const int *cand_idx, int top_k, float temperature,
                                                       u32 seed, int *counter, int *tok_io, int *pos_io, int *next_tok, SampleEx ex,
-                                                      Opt<REP || LP, u32 *> seen_, Opt<REP || LP, u32> V_, Opt<LP, SampleLp> lp_) {
+                                                      Opt<REP || LP, u32 *> seen_, Opt<REP || LP, u32> V_, Opt<LP, SampleLp> lp_, Opt<ADJ, SampleAdj> adj_) {
+    static_assert(!ADJ || (REP && LP), "the adjustment is built on the general form only");
     static_assert(SAMP_BLOCKS == 128, "two partials per lane of wave 1");
     constexpr bool PLAIN = !REP && !LP;
     constexpr int EPT = KM / 8;  // candidates per thread
@@ -385,6 +399,7 @@ __global__ void __launch_bounds__(1024) sample_stage2(const float *cand_val, con
             if (l == 0) {
                 const int p = pos_io ? pos_io[0] : 0;  // (before sample_publish increments it)
                 sample_publish(tokc, ctr, counter, tok_io, pos_io, next_tok, ex, seen, V);
+                if constexpr (ADJ) sample_count(tokc, V, adj_.get());  // (the drawn token's count and its bit in out_set, next to `seen`)
                 chosen = tokc;
                 if ((u32)(p + 1) < lp.cap) {
                     if (lp.raw) lp.raw[p + 1] = lraw;
@@ -415,34 +430,52 @@ __global__ void __launch_bounds__(1024) token_set_build_kernel(const int *ids, u
     }
 }
 
+// the bias table of gq_token_bias_build: one block -- bias_set is cleared, the block meets, then every id in [0, V) sets its bit (a vector
+// atomic: ids of one word come from several threads) and stores its value; the ids are distinct, so no two threads store to one word
+__global__ void __launch_bounds__(1024) token_bias_build(const int *ids, const float *values, u32 n, u32 V, u32 *bias_set, float *bias) {
+    const u32 words = (V + 31u) / 32u;
+    for (u32 i = threadIdx.x; i < words; i += 1024u) bias_set[i] = 0u;
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < n; i += 1024u) {
+        const u32 t = (u32)ids[i];
+        if (t < V) {
+            atomicOr(bias_set + (t >> 5), 1u << (t & 31u));
+            bias[t] = values[i];
+        }
+    }
+}
+
 // (Measured and removed: a ONE-launch greedy draw -- one 1024-thread block keeps the largest key of its 16-byte units of the
 // logits -- for temperature 0.  21 us with a load loop, no better than the two launches above with all 16 loads of a thread in flight
 // (865.6 / 864.1 against 867.9 / 868.3 tokens/s): one CU takes the 250 KiB of logits slower than 128 blocks + one do.)
 
 // the pair of one form and width (logits per thread, local-position bits, token-id bits): candidates per block by top_k
-template <bool REP, bool LP, int EPT, int LB, int IB, int KM>
+template <bool REP, bool LP, bool ADJ, int EPT, int LB, int IB, int KM>
 void sample_launch_km(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter, float *work_val, int *work_idx,
-                      int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, const SampleRep &rep, u32 *seen, const SampleLp &lp, hipStream_t s) {
-    hipLaunchKernelGGL((sample_stage1<KM, EPT, LB, REP, LP>), dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban,
-                       pos_io, Opt<REP || LP, SampleRep>(rep), Opt<LP, float *>(lp.ws));
-    hipLaunchKernelGGL((sample_stage2<KM, IB, REP, LP>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io,
-                       next_tok, ex, Opt<REP || LP, u32 *>(seen), Opt<REP || LP, u32>(vocab), Opt<LP, SampleLp>(lp));
+                      int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, const SampleRep &rep, u32 *seen, const SampleLp &lp, const SampleAdj &adj,
+                      hipStream_t s) {
+    hipLaunchKernelGGL((sample_stage1<KM, EPT, LB, REP, LP, ADJ>), dim3(SAMP_BLOCKS), dim3(256), 0, s, (const uint16_t *)logits, vocab, work_val, work_idx, ex.ban,
+                       pos_io, Opt<REP || LP, SampleRep>(rep), Opt<LP, float *>(lp.ws), Opt<ADJ, SampleAdj>(adj));
+    hipLaunchKernelGGL((sample_stage2<KM, IB, REP, LP, ADJ>), dim3(1), dim3(1024), 0, s, work_val, work_idx, top_k, temperature, seed, counter, tok_io, pos_io,
+                       next_tok, ex, Opt<REP || LP, u32 *>(seen), Opt<REP || LP, u32>(vocab), Opt<LP, SampleLp>(lp), Opt<ADJ, SampleAdj>(adj));
 }
-template <bool REP, bool LP>
+template <bool REP, bool LP, bool ADJ = false>
 void sample_launch_form(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter, float *work_val, int *work_idx,
-                        int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, const SampleRep &rep, u32 *seen, const SampleLp &lp, hipStream_t s) {
+                        int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, const SampleRep &rep, u32 *seen, const SampleLp &lp, hipStream_t s,
+                        const SampleAdj &adj = SampleAdj{}) {
     if (vocab <= 131072u) {  // slices of <= 1024 logits, 17-bit token ids
-        if (top_k <= 32) sample_launch_km<REP, LP, 4, 10, 17, 32>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, rep, seen, lp, s);
-        else sample_launch_km<REP, LP, 4, 10, 17, 64>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, rep, seen, lp, s);
+        if (top_k <= 32) sample_launch_km<REP, LP, ADJ, 4, 10, 17, 32>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, rep, seen, lp, adj, s);
+        else sample_launch_km<REP, LP, ADJ, 4, 10, 17, 64>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, rep, seen, lp, adj, s);
     } else {  // slices of <= 2048 logits through the same 128 blocks, 18-bit token ids
-        if (top_k <= 32) sample_launch_km<REP, LP, 8, 11, 18, 32>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, rep, seen, lp, s);
-        else sample_launch_km<REP, LP, 8, 11, 18, 64>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, rep, seen, lp, s);
+        if (top_k <= 32) sample_launch_km<REP, LP, ADJ, 8, 11, 18, 32>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, rep, seen, lp, adj, s);
+        else sample_launch_km<REP, LP, ADJ, 8, 11, 18, 64>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, rep, seen, lp, adj, s);
     }
 }
-// rep == NULL: the instances of gq_sample_topk / _ex / _p;  lp != NULL (with rep): those of gq_sample_topk_lp
+// rep == NULL: the instances of gq_sample_topk / _ex / _p;  lp != NULL (with rep): those of gq_sample_topk_lp;  adj != NULL (with rep and lp, whose
+// pointers may all be NULL): those of gq_sample_topk_adj
 int sample_launch(const void *logits, uint32_t vocab, int top_k, float temperature, uint32_t seed, int *counter, float *work_val, int *work_idx,
                   int *tok_io, int *pos_io, int *next_tok, const SampleEx &ex, void *stream, const SampleRep *rep = nullptr, u32 *seen = nullptr,
-                  const SampleLp *lp = nullptr) {
+                  const SampleLp *lp = nullptr, const SampleAdj *adj = nullptr) {
     if (!logits || !counter || !work_val || !work_idx || !next_tok) return gq_fail(GQ_EINVAL, "null pointer argument.");
     if (top_k > SAMP_K) return gq_fail(GQ_ENOTSUP, "top_k > 64 is not supported by the fused sampler.");
     if (int rc = sample_vocab_ok(vocab)) return rc;
@@ -453,7 +486,9 @@ int sample_launch(const void *logits, uint32_t vocab, int top_k, float temperatu
     // does not pay for a penalty it does not use.  Measured on the 8B geometry: the fp32 keys cost 10.8 us per token, the
     // log-probabilities 0.9 us.)
     const bool plain = r.rp == 1.0f && !r.seen && !r.suppress && !seen;
-    if (rep && lp && plain)
+    if (rep && lp && adj)
+        sample_launch_form<true, true, true>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, r, seen, q, s, *adj);
+    else if (rep && lp && plain)
         sample_launch_form<false, true>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, r, seen, q, s);
     else if (rep && lp)
         sample_launch_form<true, true>(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, r, seen, q, s);
@@ -517,4 +552,40 @@ extern "C" int gq_token_set_build(const int *ids, uint32_t n, uint32_t vocab, ui
     hipLaunchKernelGGL(token_set_build_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, ids, n, vocab, set, clear);
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
+}
+
+extern "C" int gq_token_bias_build(const int *ids, const float *values, uint32_t n, uint32_t vocab, uint32_t *bias_set, float *bias, void *stream) {
+    if (!bias_set || !bias || (n && (!ids || !values)) || !vocab) return gq_fail(GQ_EINVAL, "gq_token_bias_build: null pointer argument or vocab == 0.");
+    hipLaunchKernelGGL(token_bias_build, dim3(1), dim3(1024), 0, (hipStream_t)stream, ids, values, n, vocab, bias_set, bias);
+    GQ_HIP_CHECK(hipGetLastError());
+    return GQ_OK;
+}
+
+extern "C" int gq_sample_topk_adj(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
+                                  float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                                  uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                                  uint32_t *seen, const uint32_t *suppress, float *lp_ws, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n,
+                                  int *top_ids, float *top_lps, void *topn_ws, const GqSampleAdjust *adj, void *stream) {
+    if (int rc = sample_adjust_ok(adj)) return rc;
+    if (sample_adjust_neutral(adj)) {  // the entry without the suffix: its launches, its refusals
+        if (top_n)
+            return gq_sample_topk_lp_topn(logits, vocab, top_k, top_p, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ban, seq_out,
+                                          seq_cap, embed_table, x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_ws, lp_raw, lp_drawn, lp_cap, top_n,
+                                          top_ids, top_lps, topn_ws, stream);
+        return gq_sample_topk_lp(logits, vocab, top_k, top_p, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ban, seq_out, seq_cap,
+                                 embed_table, x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_ws, lp_raw, lp_drawn, lp_cap, stream);
+    }
+    if (top_n)
+        if (int rc = gq_topn_check(vocab, top_n, top_ids, top_lps, topn_ws, lp_raw && lp_ws ? lp_ws : nullptr)) return rc;
+    if (int rc = sample_penalty_ok(repetition_penalty, seen)) return rc;
+    if (lp_raw && !lp_ws) return gq_fail(GQ_EINVAL, "gq_sample_topk_lp: lp_raw needs the lp_ws workspace (2 * 128 floats).");
+    SampleEx ex{};
+    if (int rc = sample_extras(ex, vocab, top_p, ban, seq_out, seq_cap, embed_table, x_out, dim, ssq_out)) return rc;
+    const SampleRep rep{repetition_penalty, seen, suppress};
+    const SampleLp lp{lp_raw ? lp_ws : nullptr, lp_raw, lp_drawn, lp_cap, (const uint16_t *)logits};
+    const SampleAdj a = sample_adjust_of(adj);
+    if (int rc = sample_launch(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, stream, &rep, seen, &lp, &a))
+        return rc;
+    if (!top_n) return GQ_OK;
+    return gq_topn_launch(logits, vocab, top_n, lp_ws, pos_io, top_ids, top_lps, lp_cap, topn_ws, stream);
 }

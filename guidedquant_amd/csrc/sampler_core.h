@@ -37,6 +37,40 @@ __device__ __forceinline__ bool is_nan16(uint16_t h) { return (h & 0x7FFFu) > 0x
 // (-0 is not < 0; the division is IEEE's, correctly rounded: the library is built without fast-math)
 __device__ __forceinline__ float penalise(float v, float rp) { return v < 0.f ? v * rp : v / rp; }
 
+// The additive adjustment of a MEMBER token's logit (gq_sample_topk_adj / gq_sample_full_adj: a token with a listed bias, or one the
+// request has generated c > 0 times), defined to give an fp16 logit again: v = the fp16 logit widened, p = c > 0 ? fl32(fl32(fp * c) + pp) : 0,
+// s = fl32(fl32(v + b) - p), h' = fp16(s) -- every operation rounded on its own (no fused multiply-add), the conversion to nearest even with
+// subnormals kept, overflow to +-inf, NaN staying NaN.  Everything behind it takes h' for the logit; a non-member is not passed through here
+// (its pattern stays as it is, -0 and NaN included).
+__device__ __forceinline__ uint16_t adjust16(uint16_t h, float b, u32 c, float fp, float pp) {
+    const float v = (float)__builtin_bit_cast(_Float16, h);
+    const float p = c > 0u ? __fadd_rn(__fmul_rn(fp, (float)c), pp) : 0.f;
+    const float s = __fsub_rn(__fadd_rn(v, b), p);
+    return __builtin_bit_cast(uint16_t, (_Float16)s);
+}
+// what the entries with the suffix _adj hand to their kernels: GqSampleAdjust (include/gq_hip.h) as the device sees it
+struct SampleAdj {
+    float fp, pp;
+    const u32 *bias_set;
+    const float *bias;
+    u32 *out_set, *out_count;
+};
+// the adjusted pattern of token gi with raw pattern h: bias[] and out_count[] are read for members only (the words of a non-member are undefined)
+__device__ __forceinline__ uint16_t adjust_token(uint16_t h, u32 gi, bool biased, bool counted, const SampleAdj &a) {
+    if (!biased && !counted) return h;
+    return adjust16(h, biased ? a.bias[gi] : 0.f, counted ? a.out_count[gi] : 0u, a.fp, a.pp);
+}
+// the state update of a draw, ONE lane, next to sample_publish: the drawn token's count and its bit in out_set (vector atomics; the next
+// step's first kernel reads both behind a kernel boundary).  out_count[t] means something for the tokens of out_set only, so a token's
+// first draw STORES 1 and a later one adds 1: clearing out_set alone starts a request.  The token of an empty candidate set counts nowhere.
+__device__ __forceinline__ void sample_count(int tokc, u32 V, const SampleAdj &a) {
+    if (a.out_set && (u32)tokc < V) {
+        const u32 bit = 1u << ((u32)tokc & 31u);
+        if (atomicOr(a.out_set + ((u32)tokc >> 5), bit) & bit) atomicAdd(a.out_count + (u32)tokc, 1u);
+        else a.out_count[(u32)tokc] = 1u;
+    }
+}
+
 // The exponential race: argmax_i (s_i / T - log q_i), q ~ Exp(1) = -log(u).  u in (0, 1] from 24 bits of a word tied to (seed, step
 // counter, TOKEN id) -- not to a slot, so every selector that keeps a token gives it the same number: one exact product by 2^-24
 __device__ __forceinline__ float race_u(u32 seed, u32 ctr, u32 id) {
@@ -169,5 +203,21 @@ inline int sample_penalty_ok(float repetition_penalty, const uint32_t *seen) {
         return gq_fail(GQ_EINVAL, "repetition_penalty must be finite and > 0 (1 = no penalty).");
     if (!seen && repetition_penalty != 1.0f) return gq_fail(GQ_EINVAL, "repetition_penalty != 1 needs the `seen` token set.");
     return GQ_OK;
+}
+// the refusals of a GqSampleAdjust (NULL: nothing is asked for), in front of every other check of the entries with the suffix _adj
+inline int sample_adjust_ok(const GqSampleAdjust *a) {
+    if (!a) return GQ_OK;
+    if (!(fabsf(a->frequency_penalty) < INFINITY) || !(fabsf(a->presence_penalty) < INFINITY))
+        return gq_fail(GQ_EINVAL, "frequency_penalty and presence_penalty must be finite (0 = no penalty).");
+    if (!a->bias_set != !a->bias) return gq_fail(GQ_EINVAL, "adjust: bias_set and bias come together or not at all.");
+    if (!a->out_set != !a->out_count) return gq_fail(GQ_EINVAL, "adjust: out_set and out_count come together or not at all.");
+    if (!a->out_set && (a->frequency_penalty != 0.f || a->presence_penalty != 0.f))
+        return gq_fail(GQ_EINVAL, "a frequency_penalty or presence_penalty != 0 needs out_set and out_count.");
+    return GQ_OK;
+}
+// (behind sample_adjust_ok) nothing is biased and nothing is counted: the entry without the suffix serves the call
+inline bool sample_adjust_neutral(const GqSampleAdjust *a) { return !a || (!a->bias_set && !a->out_set); }
+inline SampleAdj sample_adjust_of(const GqSampleAdjust *a) {
+    return SampleAdj{a->frequency_penalty, a->presence_penalty, a->bias_set, a->bias, a->out_set, a->out_count};
 }
 }  // namespace gqs

@@ -18,11 +18,16 @@
 //   full_race    128 blocks  the exponential race over the slice's candidates: the best (score, id) per block.
 //   full_finish  1 block     the best of the 128, the log-probabilities, publishing, the embedding fold.
 // gq_sample_full_topn (at the end of the file): the same six launches, then topn.hip's pair, which reads the partials full_hist left at WS_LP.
+// gq_sample_full_adj: the same six launches with the ADJ instances of the four kernels that read tokens -- a member token's adjusted fp16
+// pattern (gqs::adjust16) stands in for its logit in liveness, the histogram bin, the value s, the ties and the race; the log-probability
+// partials and lp_raw keep the raw pattern; full_finish counts the drawn token.
 // The value images, the penalty, the ban list, the race, the log-sum-exp merge, publishing and the embedding fold are sampler_core.h's: the
 // functions sampler.hip's kernels are built from, so the two samplers agree bit for bit where their contracts say so.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "gq_internal.h"
 #include "sampler_core.h"
@@ -71,6 +76,13 @@ struct Toks {
     float rp;  // 1: nobody is penalised
     const u32 *seen, *suppress;
 };
+// (gq_sample_full_adj) the same with the adjustment behind it: the kernels that read tokens are built twice, and the instances of
+// gq_sample_full take the argument list they had
+struct ToksAdj : Toks {
+    SampleAdj adj;
+};
+template <bool ADJ>
+using ToksOf = std::conditional_t<ADJ, ToksAdj, Toks>;
 struct Slice {
     u32 lo, hi;
     int bid[4] = {-1, -1, -1, -1};
@@ -83,21 +95,46 @@ __device__ __forceinline__ Slice slice_of(const Toks &t) {
     ban_ids(t.ban, t.pos_io, s.bid);
     return s;
 }
-// token gi of the slice: live or not, its raw pattern, whether the penalty applies, its value s
-struct Tok {
+// token gi of the slice: live or not, its raw pattern, whether the penalty applies, its value s -- and (ToksAdj) the adjusted pattern ha
+// that stands in for the logit everywhere but in the raw log-probabilities: liveness, the histogram bin and s are taken from it
+template <bool ADJ>
+struct TokOf {
     bool live, pen;
     uint16_t h;
     float s;
 };
-__device__ __forceinline__ Tok tok_of(const Toks &t, const Slice &sl, u32 gi) {
-    Tok k{false, false, (uint16_t)0xFC00u, NINF};
+template <>
+struct TokOf<true> {
+    bool live, pen;
+    uint16_t h;
+    float s;
+    uint16_t ha;
+};
+template <bool ADJ>
+__device__ __forceinline__ uint16_t binned(const TokOf<ADJ> k) {
+    if constexpr (ADJ) return k.ha;
+    else return k.h;
+}
+// (the adjusted pattern of token gi alone: full_finish asks for the drawn token's)
+__device__ __forceinline__ uint16_t adjusted(const Toks &, u32, uint16_t h) { return h; }
+__device__ __forceinline__ uint16_t adjusted(const ToksAdj &t, u32 gi, uint16_t h) {
+    const u32 bit = 1u << (gi & 31u);
+    return adjust_token(h, gi, t.adj.bias_set && (t.adj.bias_set[gi >> 5] & bit), t.adj.out_set && (t.adj.out_set[gi >> 5] & bit), t.adj);
+}
+template <typename TK>
+__device__ __forceinline__ auto tok_of(const TK &t, const Slice &sl, u32 gi) {
+    constexpr bool ADJ = std::is_same_v<TK, ToksAdj>;
+    TokOf<ADJ> k{false, false, (uint16_t)0xFC00u, NINF};
+    if constexpr (ADJ) k.ha = (uint16_t)0xFC00u;
     if (gi >= sl.hi) return k;
     k.h = t.logits[gi];
     const u32 bit = 1u << (gi & 31u);
     const bool sup = t.suppress && (t.suppress[gi >> 5] & bit);
-    k.live = !is_banned(gi, sl.bid) && !sup && !is_nan16(k.h);
+    uint16_t hv = k.h;
+    if constexpr (ADJ) hv = k.ha = adjusted(t, gi, k.h);
+    k.live = !is_banned(gi, sl.bid) && !sup && !is_nan16(hv);
     k.pen = t.rp != 1.0f && t.seen && (t.seen[gi >> 5] & bit);
-    const float v = h2f(k.h);
+    const float v = h2f(hv);
     k.s = k.pen ? penalise(v, t.rp) : v;
     return k;
 }
@@ -107,7 +144,8 @@ __global__ void __launch_bounds__(FT) full_zero(uint4 *hist, u32 n16, u32 *maxke
     if (blockIdx.x == 0 && threadIdx.x == 0) maxkey[0] = 0u;
 }
 
-__global__ void __launch_bounds__(FT) full_hist(Toks t, u32 *hist, u32 *maxkey, float *lp_part) {
+template <bool ADJ>
+__global__ void __launch_bounds__(FT) full_hist(ToksOf<ADJ> t, u32 *hist, u32 *maxkey, float *lp_part) {
     __shared__ float red[FT / 64];
     const Slice sl = slice_of(t);
     const u32 tid = threadIdx.x;
@@ -115,10 +153,10 @@ __global__ void __launch_bounds__(FT) full_hist(Toks t, u32 *hist, u32 *maxkey, 
     u32 top = 0u;
 #pragma unroll
     for (int e = 0; e < EPT; e++) {
-        const Tok k = tok_of(t, sl, sl.lo + tid * EPT + e);
-        raw[e] = h2f(k.h);  // (-inf past the end)
+        const auto k = tok_of(t, sl, sl.lo + tid * EPT + e);
+        raw[e] = h2f(k.h);  // (-inf past the end; the RAW pattern, adjusted or not)
         if (k.live) {
-            atomicAdd(hist + (k.pen ? NBIN : 0u) + ordered_key16(k.h), 1u);
+            atomicAdd(hist + (k.pen ? NBIN : 0u) + ordered_key16(binned(k)), 1u);
             top = max(top, image_of(k.s));
         }
     }
@@ -378,7 +416,8 @@ __global__ void __launch_bounds__(1024) full_scan(unsigned char *ws, ScanArgs A)
     }
 }
 
-__global__ void __launch_bounds__(FT) full_ties(Toks t, const unsigned char *ws, u32 *ties) {
+template <bool ADJ>
+__global__ void __launch_bounds__(FT) full_ties(ToksOf<ADJ> t, const unsigned char *ws, u32 *ties) {
     __shared__ u32 red[FT / 64];
     const Cut cut = *reinterpret_cast<const Cut *>(ws + WS_CUT);
     const u32 tid = threadIdx.x;
@@ -387,7 +426,7 @@ __global__ void __launch_bounds__(FT) full_ties(Toks t, const unsigned char *ws,
         const Slice sl = slice_of(t);
 #pragma unroll
         for (int e = 0; e < EPT; e++) {
-            const Tok k = tok_of(t, sl, sl.lo + tid * EPT + e);
+            const auto k = tok_of(t, sl, sl.lo + tid * EPT + e);
             c += (k.live && image_of(k.s) == cut.Kc) ? 1u : 0u;
         }
     }
@@ -398,7 +437,8 @@ __global__ void __launch_bounds__(FT) full_ties(Toks t, const unsigned char *ws,
     if (tid == 0) ties[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-__global__ void __launch_bounds__(FT) full_race(Toks t, const unsigned char *ws, const u32 *ties, float temperature, u32 seed, const int *counter,
+template <bool ADJ>
+__global__ void __launch_bounds__(FT) full_race(ToksOf<ADJ> t, const unsigned char *ws, const u32 *ties, float temperature, u32 seed, const int *counter,
                                                  float *best_score, int *best_tok) {
     __shared__ u32 wt[FT / 64];
     __shared__ float rs[FT / 64];
@@ -409,7 +449,7 @@ __global__ void __launch_bounds__(FT) full_race(Toks t, const unsigned char *ws,
     const float T = fmaxf(temperature, 1e-5f);
     const u32 ctr = (u32)counter[0];
     const bool inside = cut.rc < cut.gc;  // (block-uniform)
-    Tok k[EPT];
+    TokOf<ADJ> k[EPT];
     u32 mine = 0u;
 #pragma unroll
     for (int e = 0; e < EPT; e++) {
@@ -480,7 +520,8 @@ struct FinishArgs {
     float temperature;
 };
 
-__global__ void __launch_bounds__(1024) full_finish(Toks t, const unsigned char *ws, const float *best_score, const int *best_tok, const float *lp_part,
+template <bool ADJ>
+__global__ void __launch_bounds__(1024) full_finish(ToksOf<ADJ> t, const unsigned char *ws, const float *best_score, const int *best_tok, const float *lp_part,
                                                      FinishArgs F) {
     __shared__ int chosen;
     __shared__ float lpM, lpLogZ;
@@ -510,13 +551,16 @@ __global__ void __launch_bounds__(1024) full_finish(Toks t, const unsigned char 
             if ((u32)tokc < t.V) {  // (read before the token joins `seen`)
                 const float v = h2f(t.logits[tokc]);
                 const bool pen = t.rp != 1.0f && t.seen && (t.seen[(u32)tokc >> 5] & (1u << ((u32)tokc & 31u)));
-                const float a = (pen ? penalise(v, t.rp) : v) / fmaxf(F.temperature, 1e-5f);
+                // (ADJ) the race saw the adjusted pattern; lp_raw below keeps the raw one
+                const float va = ADJ ? h2f(adjusted(t, (u32)tokc, t.logits[tokc])) : v;
+                const float a = (pen ? penalise(va, t.rp) : va) / fmaxf(F.temperature, 1e-5f);
                 if (F.lp_raw) lraw = (v - lpM) - lpLogZ;
                 // a_tok - log sum_C exp(a_c) as (a_tok - m) - log(sum_C w): the candidates' mass is the exact integer sum of the scan
                 // (a == m: the first token's own value, infinite or not -- the difference is 0, as w_of has w = 1)
                 if (F.lp_drawn) ldrawn = (float)((double)(a == cut.m ? 0.f : a - cut.m) - log((double)cut.zkept * (1.0 / WONE)));
             }
             sample_publish(tokc, ctr, F.counter, F.tok_io, F.pos_io, F.next_tok, F.ex, F.seen_out, t.V);
+            if constexpr (ADJ) sample_count(tokc, t.V, t.adj);
             if ((u32)(p + 1) < F.lp_cap) {
                 if (F.lp_raw) F.lp_raw[p + 1] = lraw;
                 if (F.lp_drawn) F.lp_drawn[p + 1] = ldrawn;
@@ -531,12 +575,13 @@ __global__ void __launch_bounds__(1024) full_finish(Toks t, const unsigned char 
 }
 }  // namespace
 
-extern "C" size_t gq_sample_full_ws_bytes(uint32_t vocab) { return vocab > GQ_SAMPLER_MAX_VOCAB ? 0 : WS_BYTES; }
-
-extern "C" int gq_sample_full(const void *logits, uint32_t vocab, int top_k, float top_p, float min_p, float temperature, uint32_t seed,
-                              int *counter, void *ws, size_t ws_bytes, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
-                              uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
-                              uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, void *stream) {
+// the checks and the six launches of gq_sample_full (ADJ = false) and of gq_sample_full_adj with something to adjust
+namespace {
+template <bool ADJ>
+int full_launch(const void *logits, uint32_t vocab, int top_k, float top_p, float min_p, float temperature, uint32_t seed,
+                int *counter, void *ws, size_t ws_bytes, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, const SampleAdj &adj, void *stream) {
     if (!logits || !counter || !ws || !next_tok) return gq_fail(GQ_EINVAL, "gq_sample_full: null pointer argument.");
     if (int rc = sample_vocab_ok(vocab)) return rc;
     if (ws_bytes < WS_BYTES || ((uintptr_t)ws & 15u)) return gq_fail(GQ_EINVAL, "gq_sample_full: the workspace is gq_sample_full_ws_bytes(vocab) bytes, 16-byte aligned.");
@@ -549,21 +594,34 @@ extern "C" int gq_sample_full(const void *logits, uint32_t vocab, int top_k, flo
     hipStream_t s = (hipStream_t)stream;
     unsigned char *w8 = (unsigned char *)ws;
     const bool rep = repetition_penalty != 1.0f;
-    const Toks t{(const uint16_t *)logits, vocab, ban, pos_io, repetition_penalty, seen, suppress};
+    ToksOf<ADJ> t{};
+    static_cast<Toks &>(t) = Toks{(const uint16_t *)logits, vocab, ban, pos_io, repetition_penalty, seen, suppress};
+    if constexpr (ADJ) t.adj = adj;
     u32 *hist = (u32 *)(w8 + WS_HIST), *ties = (u32 *)(w8 + WS_TIES);
     float *best_score = (float *)(w8 + WS_BEST), *lp_part = (float *)(w8 + WS_LP);
     int *best_tok = (int *)(w8 + WS_BEST + 4 * FB);
     u32 *maxkey = (u32 *)(w8 + WS_MAXKEY);
     hipLaunchKernelGGL(full_zero, dim3(FB), dim3(FT), 0, s, (uint4 *)hist, (rep ? 2u : 1u) * NBIN / 4u, maxkey);
-    hipLaunchKernelGGL(full_hist, dim3(FB), dim3(FT), 0, s, t, hist, maxkey, lp_raw ? lp_part : nullptr);
+    hipLaunchKernelGGL(full_hist<ADJ>, dim3(FB), dim3(FT), 0, s, t, hist, maxkey, lp_raw ? lp_part : nullptr);
     hipLaunchKernelGGL(full_scan, dim3(1), dim3(1024), 0, s, w8, ScanArgs{top_k, top_p, min_p, temperature, repetition_penalty, rep ? 1 : 0});
-    hipLaunchKernelGGL(full_ties, dim3(FB), dim3(FT), 0, s, t, (const unsigned char *)w8, ties);
-    hipLaunchKernelGGL(full_race, dim3(FB), dim3(FT), 0, s, t, (const unsigned char *)w8, (const u32 *)ties, temperature, seed, (const int *)counter, best_score, best_tok);
+    hipLaunchKernelGGL(full_ties<ADJ>, dim3(FB), dim3(FT), 0, s, t, (const unsigned char *)w8, ties);
+    hipLaunchKernelGGL(full_race<ADJ>, dim3(FB), dim3(FT), 0, s, t, (const unsigned char *)w8, (const u32 *)ties, temperature, seed, (const int *)counter, best_score, best_tok);
     const FinishArgs F{counter, tok_io, pos_io, next_tok, ex, seen, lp_raw, lp_drawn, lp_cap, temperature};
-    hipLaunchKernelGGL(full_finish, dim3(1), dim3(1024), 0, s, t, (const unsigned char *)w8, (const float *)best_score, (const int *)best_tok,
+    hipLaunchKernelGGL(full_finish<ADJ>, dim3(1), dim3(1024), 0, s, t, (const unsigned char *)w8, (const float *)best_score, (const int *)best_tok,
                        (const float *)lp_part, F);
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
+}
+}  // namespace
+
+extern "C" size_t gq_sample_full_ws_bytes(uint32_t vocab) { return vocab > GQ_SAMPLER_MAX_VOCAB ? 0 : WS_BYTES; }
+
+extern "C" int gq_sample_full(const void *logits, uint32_t vocab, int top_k, float top_p, float min_p, float temperature, uint32_t seed,
+                              int *counter, void *ws, size_t ws_bytes, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                              uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                              uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, void *stream) {
+    return full_launch<false>(logits, vocab, top_k, top_p, min_p, temperature, seed, counter, ws, ws_bytes, tok_io, pos_io, next_tok, ban, seq_out, seq_cap,
+                              embed_table, x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_raw, lp_drawn, lp_cap, SampleAdj{}, stream);
 }
 
 extern "C" int gq_sample_full_topn(const void *logits, uint32_t vocab, int top_k, float top_p, float min_p, float temperature, uint32_t seed,
@@ -576,5 +634,26 @@ extern "C" int gq_sample_full_topn(const void *logits, uint32_t vocab, int top_k
                                 embed_table, x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_raw, lp_drawn, lp_cap, stream))
         return rc;
     // (the partials full_hist left for full_finish: the same words, combined in the same order)
+    return gq_topn_launch(logits, vocab, top_n, (const float *)((unsigned char *)ws + WS_LP), pos_io, top_ids, top_lps, lp_cap, topn_ws, stream);
+}
+
+extern "C" int gq_sample_full_adj(const void *logits, uint32_t vocab, int top_k, float top_p, float min_p, float temperature, uint32_t seed,
+                                  int *counter, void *ws, size_t ws_bytes, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                                  uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                                  uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n, int *top_ids,
+                                  float *top_lps, void *topn_ws, const GqSampleAdjust *adj, void *stream) {
+    if (int rc = sample_adjust_ok(adj)) return rc;
+    if (top_n)
+        if (int rc = gq_topn_check(vocab, top_n, top_ids, top_lps, topn_ws, lp_raw && ws ? ws : nullptr)) return rc;
+    if (sample_adjust_neutral(adj)) {  // the entry without the suffix: its launches, its refusals
+        if (int rc = gq_sample_full(logits, vocab, top_k, top_p, min_p, temperature, seed, counter, ws, ws_bytes, tok_io, pos_io, next_tok, ban, seq_out, seq_cap,
+                                    embed_table, x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_raw, lp_drawn, lp_cap, stream))
+            return rc;
+    } else if (int rc = full_launch<true>(logits, vocab, top_k, top_p, min_p, temperature, seed, counter, ws, ws_bytes, tok_io, pos_io, next_tok, ban, seq_out,
+                                          seq_cap, embed_table, x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_raw, lp_drawn, lp_cap,
+                                          sample_adjust_of(adj), stream)) {
+        return rc;
+    }
+    if (!top_n) return GQ_OK;
     return gq_topn_launch(logits, vocab, top_n, (const float *)((unsigned char *)ws + WS_LP), pos_io, top_ids, top_lps, lp_cap, topn_ws, stream);
 }

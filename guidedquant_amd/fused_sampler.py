@@ -11,8 +11,14 @@ needs is decided here and nowhere else:
                                           instances, about 10.8 us per token more;
   * a workspace of 32 candidates/block -> gq_sample_topk, the narrow call of the layer pipeline (draw only: no ban, no sequence store);
   * no top_k (None / 0), top_k > 64, or min_p > 0 -> gq_sample_full (csrc/sampler_full.hip: the whole vocabulary; it serves the penalty,
-                                          the sets and the log-probabilities itself, from its own workspace).
+                                          the sets and the log-probabilities itself, from its own workspace);
+  * frequency_penalty / presence_penalty != 0 or a logit_bias -> the entry with the suffix _adj (gq_sample_topk_adj / gq_sample_full_adj, by
+                                          the rule above), which takes everything the others take.  Without the three the sampler makes
+                                          exactly the calls listed above.
 """
+import ctypes
+import math
+
 import torch
 
 from . import _lib
@@ -31,6 +37,43 @@ def check_top_logprobs(n, logprobs):
     return int(n)
 
 
+def check_logit_bias(logit_bias, vocab_size):
+    """logit_bias as {int id: float}: None / empty = off; a dict (ids as ints or, as serving APIs send them, as strings) of finite values
+    with ids in [0, vocab_size) (ValueError otherwise)"""
+    if logit_bias is None:
+        return {}
+    if not isinstance(logit_bias, dict):
+        raise ValueError(f"logit_bias must be a dict {{token id: bias}}, not {type(logit_bias).__name__}")
+    out = {}
+    for k, v in logit_bias.items():
+        try:
+            if isinstance(k, (bool, float)):
+                raise ValueError
+            t = int(k)
+            b = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"logit_bias: {k!r}: {v!r} is no (token id, number) pair") from None
+        if not 0 <= t < vocab_size:
+            raise ValueError(f"logit_bias: token id {t} is outside [0, {vocab_size})")
+        if not math.isfinite(b) or not math.isfinite(torch.tensor(b, dtype=torch.float32).item()):
+            raise ValueError(f"logit_bias: the bias of token {t} must be a finite fp32 number, not {v!r}")
+        if t in out:
+            raise ValueError(f"logit_bias: token id {t} is listed twice")
+        out[t] = b
+    return out
+
+
+def check_additive_penalty(name, x):
+    """frequency_penalty / presence_penalty as a float: None = 0; finite (ValueError otherwise).  Negative values are served: they reward."""
+    try:
+        f = 0.0 if x is None else float(x)
+    except (TypeError, ValueError):
+        f = math.nan
+    if isinstance(x, (bool, str)) or not math.isfinite(f) or not math.isfinite(torch.tensor(f, dtype=torch.float32).item()):
+        raise ValueError(f"{name} must be a finite number (0 = off), not {x!r}")
+    return f
+
+
 class FusedSampler:
     """State: `counter` (the RNG counter word), `work_val` / `work_idx` (stage 1's candidates; a whole-vocabulary configuration -- `full`: top_k
     None / 0 / above 64, or min_p > 0 -- has `ws`, gq_sample_full's workspace, instead), `ban` (int32 {n, until_pos, id0..id3}:
@@ -39,10 +82,14 @@ class FusedSampler:
     `seen` on the device), `lp_ws` / `lp_raw` / `lp_drawn` (logprobs: the log-probability of every drawn token at [pos + 1], under the
     model's unprocessed distribution and under the one the draw was made from), `top_ids` / `top_lps` / `topn_ws` (top_logprobs = n in
     1..20, with logprobs: int32 / fp32 [seq_capacity, n], row [pos + 1] = the n most probable tokens of the unprocessed distribution and
-    their log-probabilities, against the log-sum-exp lp_raw is taken against).  A request without them allocates nothing extra."""
+    their log-probabilities, against the log-sum-exp lp_raw is taken against), `bias_set` / `bias` (a logit_bias: the bitmap of the
+    listed ids and fp32 [vocab], built once in the constructor), `out_set` / `out_count` (a frequency_penalty or presence_penalty != 0: the
+    bitmap and the uint32 counts of the tokens generated in THIS request -- every drawn token is counted on the device;
+    `reset_generated()` at the start of every request).  A request without them allocates nothing extra."""
 
     def __init__(self, vocab_size, device, top_k, top_p=1.0, temperature=1.0, seed=1234, seq_capacity=0, repetition_penalty=1.0,
-                 suppress_tokens=(), logprobs=False, candidates=64, min_p=0.0, top_logprobs=0):
+                 suppress_tokens=(), logprobs=False, candidates=64, min_p=0.0, top_logprobs=0, frequency_penalty=0.0, presence_penalty=0.0,
+                 logit_bias=None):
         self.min_p = float(min_p or 0.0)
         if not 0.0 <= self.min_p <= 1.0:
             raise ValueError(f"min_p must be in [0, 1], not {min_p!r}")
@@ -64,6 +111,13 @@ class FusedSampler:
             raise ValueError("a workspace of 32 candidates per block serves the draw alone (gq_sample_topk)")
         if self.narrow and self.full:
             raise ValueError("a workspace of 32 candidates per block serves top_k in 1..32 without min_p (gq_sample_topk)")
+        self.frequency_penalty = check_additive_penalty("frequency_penalty", frequency_penalty)
+        self.presence_penalty = check_additive_penalty("presence_penalty", presence_penalty)
+        self.logit_bias = check_logit_bias(logit_bias, int(vocab_size))
+        counted = self.frequency_penalty != 0.0 or self.presence_penalty != 0.0
+        self.adjusted = counted or bool(self.logit_bias)  # (the entries with the suffix _adj)
+        if self.narrow and self.adjusted:
+            raise ValueError("a workspace of 32 candidates per block serves the draw alone (gq_sample_topk)")
 
         def z(n, dtype=torch.int32):
             return torch.zeros((int(n), ), dtype=dtype, device=device)
@@ -91,6 +145,20 @@ class FusedSampler:
             n = self.top_logprobs
             self.top_ids, self.top_lps = z(seq_capacity * n).view(seq_capacity, n), z(seq_capacity * n, torch.float32).view(seq_capacity, n)
             self.topn_ws = z(_lib.TOPN_WS_BYTES // 8, torch.int64)
+        self.bias_set = self.bias = self.out_set = self.out_count = self._adj = None
+        if self.adjusted:
+            words = (self.vocab_size + 31) // 32
+            if self.logit_bias:
+                self.bias_set, self.bias = z(words), z(self.vocab_size, torch.float32)
+                ids = torch.tensor(list(self.logit_bias), dtype=torch.int32, device=device)
+                values = torch.tensor(list(self.logit_bias.values()), dtype=torch.float32, device=device)
+                _lib.check(_lib.lib().gq_token_bias_build(ids.data_ptr(), values.data_ptr(), ids.numel(), self.vocab_size, self.bias_set.data_ptr(),
+                                                         self.bias.data_ptr(), _lib.current_stream_ptr()), "gq_token_bias_build")
+            if counted:
+                self.out_set, self.out_count = z(words), z(self.vocab_size)
+            # (the struct is read by the C call on the host, at launch and at capture time: it lives as long as the sampler)
+            self._adj = _lib.GqSampleAdjust(self.frequency_penalty, self.presence_penalty, *(t.data_ptr() if t is not None else None for t in
+                                                                                          (self.bias_set, self.bias, self.out_set, self.out_count)))
 
     def build_set(self, words, ids, clear=True):
         """words = (clear: the set of `ids`; else: joined by `ids`), one launch outside any graph"""
@@ -116,10 +184,26 @@ class FusedSampler:
         else:
             self.counter.fill_(int(word))
 
+    def reset_generated(self):
+        """the start of a request: nothing has been generated yet -- `out_set` and `out_count` are cleared (the prompt does not count;
+        `set_history` does not touch them).  Without a frequency or presence penalty there is no count and nothing happens."""
+        if self.out_set is not None:
+            self.out_set.zero_()
+            self.out_count.zero_()
+
+    def count_generated(self, ids):
+        """tokens this request generated OUTSIDE the sampler (a first token drawn from the prompt pass's logits) join the counts: one
+        index_add and one set build, outside any graph.  Without a frequency or presence penalty nothing happens."""
+        if self.out_set is not None:
+            ids = (ids if torch.is_tensor(ids) else torch.tensor(list(ids))).to(device=self.out_count.device, dtype=torch.int64).view(-1)
+            self.out_count.index_add_(0, ids, torch.ones_like(ids, dtype=torch.int32))
+            self.build_set(self.out_set, ids, clear=False)
+
     def clear_warmup(self):
-        """the warm-up and capture-time draws joined `seen`: their bits go"""
+        """the warm-up and capture-time draws joined `seen` and were counted: their bits and counts go"""
         if self.seen is not None:
             self.seen.zero_()
+        self.reset_generated()
 
     def launch(self, logits, tok_io, pos_io, next_tok, embed_table=None, x_out=None, dim=0, ssq_out=None):
         """one draw from `logits` on the current stream: the token to `next_tok` and, fed back, to `tok_io`, with `pos_io` advanced;
@@ -132,7 +216,9 @@ class FusedSampler:
                     p(embed_table), p(x_out), dim, p(ssq_out), self.repetition_penalty, p(self.seen), p(self.suppress), p(self.lp_raw), p(self.lp_drawn),
                     self.lp_raw.numel() if self.lp_raw is not None else 0)
             name = "gq_sample_full"
-            if self.top_logprobs:
+            if self.adjusted:
+                name, args = "gq_sample_full_adj", args + (self.top_logprobs, p(self.top_ids), p(self.top_lps), p(self.topn_ws), ctypes.byref(self._adj))
+            elif self.top_logprobs:
                 name, args = "gq_sample_full_topn", args + (self.top_logprobs, p(self.top_ids), p(self.top_lps), p(self.topn_ws))
             return _lib.check(getattr(_lib.lib(), name)(*args, _lib.current_stream_ptr()), name)
         draw = (self.temperature, self.seed, p(self.counter), p(self.work_val), p(self.work_idx), p(tok_io), p(pos_io), p(next_tok))
@@ -141,10 +227,15 @@ class FusedSampler:
         else:
             name, args = "gq_sample_topk_p", (p(logits), self.vocab_size, int(self.top_k), self.top_p) + draw + (
                 p(self.ban), p(self.seq), self.seq.numel() if self.seq is not None else 0, p(embed_table), p(x_out), dim, p(ssq_out))
-            if self.logprobs or self.seen is not None:
+            if self.adjusted:  # (everything the others take: the sets and the log-probability arrays that do not exist go as NULL)
+                name, args = "gq_sample_topk_adj", args + (
+                    self.repetition_penalty, p(self.seen), p(self.suppress), p(self.lp_ws), p(self.lp_raw), p(self.lp_drawn),
+                    self.lp_raw.numel() if self.lp_raw is not None else 0, self.top_logprobs, p(self.top_ids), p(self.top_lps), p(self.topn_ws),
+                    ctypes.byref(self._adj))
+            elif self.logprobs or self.seen is not None:
                 name, args = "gq_sample_topk_rep", args + (self.repetition_penalty, p(self.seen), p(self.suppress))
-            if self.logprobs:
+            if self.logprobs and not self.adjusted:
                 name, args = "gq_sample_topk_lp", args + (p(self.lp_ws), p(self.lp_raw), p(self.lp_drawn), self.lp_raw.numel())
-            if self.top_logprobs:
+            if self.top_logprobs and not self.adjusted:
                 name, args = "gq_sample_topk_lp_topn", args + (self.top_logprobs, p(self.top_ids), p(self.top_lps), p(self.topn_ws))
         _lib.check(getattr(_lib.lib(), name)(*args, _lib.current_stream_ptr()), name)

@@ -99,7 +99,8 @@ class DecodeGraph:
     (the manual-graph path of generate.py:95-113)."""
 
     def __init__(self, model: Transformer, device, native_sampling=False, seed=1234, fold_embed=False, seq_capacity=0, steps_per_replay=1,
-                 repetition_penalty=1.0, suppress_tokens=None, logprobs=False, min_p=0.0, top_logprobs=0, **sampling_kwargs):
+                 repetition_penalty=1.0, suppress_tokens=None, logprobs=False, min_p=0.0, top_logprobs=0, frequency_penalty=0.0,
+                 presence_penalty=0.0, logit_bias=None, **sampling_kwargs):
         """native_sampling: draw the token with the fused HIP sampler (`self.sampler`, a fused_sampler.FusedSampler, which picks the
         entry point: same distribution as `sample`, own counter-based RNG) and feed token / position back inside the
         graph; `next_prob` is then not produced.  top_k in 1..64 without min_p launches the two-stage kernels it always launched; top_k
@@ -134,13 +135,23 @@ class DecodeGraph:
         where the vocabulary has fewer) and their log-probabilities `self.top_lps[pos + 1]` (fp32, against lp_raw's log-sum-exp: the drawn
         token's entry, where it is listed, equals lp_raw bit for bit) -- two launches behind the sampler's (gq_sample_topk_lp_topn /
         gq_sample_full_topn).  Ban list, suppress list, penalty, temperature and the filters do not enter the list.  0 (the default): the
-        step launches what it launches without the argument."""
+        step launches what it launches without the argument.
+        frequency_penalty / presence_penalty (finite, 0 = off) and logit_bias ({token id: finite bias}) -- native sampling only; ValueError
+        otherwise, never dropped: a serving API's three additive adjustments inside the sampler's launches (gq_sample_topk_adj /
+        gq_sample_full_adj; include/gq_hip.h has the formula: the adjusted logit is rounded to fp16, the additive terms come before the
+        repetition penalty, lp_raw and the top-n lists stay raw).  The penalties count the tokens GENERATED IN THIS REQUEST -- the prompt
+        does not count -- in `self.sampler.out_count`, on the device, so a multi-step replay feeds the counts back by itself; the counts
+        are EMPTY when the constructor returns and `reset_generated()` must be called at the start of every request.  With the defaults
+        the step makes exactly the call it makes without the arguments and allocates nothing."""
         prime_graph_rng_state(device)
         self.model = model
         self.native_sampling = bool(native_sampling) and model.native_ready()
         if not self.native_sampling and (min_p or 0.0) > 0.0:
             raise ValueError("min_p is served by the fused sampler only (native_sampling=True on a model with the fused decode step): the "
                              "torch-sampling graph does not apply it")
+        if not self.native_sampling and (frequency_penalty or presence_penalty or logit_bias):
+            raise ValueError("frequency_penalty / presence_penalty / logit_bias are served by the fused sampler only (native_sampling=True on a "
+                             "model with the fused decode step): the torch-sampling graph does not apply them")
         self.fold_embed = bool(fold_embed) and self.native_sampling
         self.steps_per_replay = max(1, int(steps_per_replay)) if self.native_sampling else 1
         self.seed = seed
@@ -159,7 +170,8 @@ class DecodeGraph:
             k = 1
         self.sampler = s = FusedSampler(model.config.vocab_size, device, k, sampling_kwargs.get("top_p"), sampling_kwargs.get("temperature", 1.0), seed,
                                         seq_capacity, repetition_penalty, suppress_tokens, logprobs, min_p=min_p if self.native_sampling else 0.0,
-                                        top_logprobs=top_logprobs)
+                                        top_logprobs=top_logprobs, frequency_penalty=frequency_penalty, presence_penalty=presence_penalty,
+                                        logit_bias=logit_bias)
         self.rng_counter, self.work_val, self.work_idx, self.ban, self.seq = s.counter, s.work_val, s.work_idx, s.ban, s.seq
         self.seen, self.suppress, self._lp_ws, self.lp_raw, self.lp_drawn = s.seen, s.suppress, s.lp_ws, s.lp_raw, s.lp_drawn
         self.repetition_penalty, self.logprobs = s.repetition_penalty, s.logprobs
@@ -180,6 +192,11 @@ class DecodeGraph:
         """the sequence so far (the prompt, with whatever was generated before): `seen` is rebuilt from it, outside the graph
         (FusedSampler.set_history).  To be called next to `set_token` before the first step of a request."""
         self.sampler.set_history(ids)
+
+    def reset_generated(self):
+        """the start of a request: the counts of the frequency / presence penalty are cleared, outside the graph
+        (FusedSampler.reset_generated; nothing happens without such a penalty)"""
+        self.sampler.reset_generated()
 
     def close(self):
         """destroy the captured graphs now (an owner that drops a DecodeGraph calls this instead of leaving the executable graphs to
@@ -281,6 +298,12 @@ def decode_n_tokens(model: Transformer, cur_token: torch.Tensor, input_pos: torc
     if use_graph:
         g = graph or DecodeGraph(model, cur_token.device, **sampling_kwargs)
         g.set_token(cur_token, input_pos)
+        # (a frequency / presence penalty counts this request's tokens: the counts start over, and a first token that the prompt pass
+        # drew -- input_pos > 0 -- is one of them)
+        if g.sampler.out_set is not None:
+            g.reset_generated()
+            if int(input_pos.view(-1)[0]) > 0:
+                g.sampler.count_generated(cur_token)
         for _ in range(num_new_tokens):
             g.step()
             new_tokens.append(g.next_tok.clone())
@@ -445,12 +468,16 @@ def benchmark_decode(model: Transformer, device, num_samples=5, max_new_tokens=1
 
 def main(prompt=None, num_samples=5, max_new_tokens=100, batch_size=1, top_k=200, temperature=0.8, compile=2,
          compile_prefill=False, profile=None, device="cuda", model_name=None, backend=None, bitwidth=None,
-         checkpoint_path=None, config_path=None, dtype=None, print_result=False, random_init=False, kv_cache_dtype=None, lm_head_dtype=None):
+         checkpoint_path=None, config_path=None, dtype=None, print_result=False, random_init=False, kv_cache_dtype=None, lm_head_dtype=None,
+         frequency_penalty=0.0, presence_penalty=0.0):
     """generate.py:268-389 -- same arguments and printed report.  `compile` selects the decode driver: 0 = eager per-token
     launches, >= 1 = the captured hipGraph of the decode step (the role torch.compile(mode='max-autotune') plays in the
     reference).  A tokenizer is only needed for a text prompt / --print_result; without one the BOS id of the model
     family is used (the reference's benchmark setting, prompt=None).  lm_head_dtype="int8": the fused decode step's head over a
-    weight-only int8 copy (Transformer.set_lm_head_dtype; ValueError on the CPU or a model that is not fp16)."""
+    weight-only int8 copy (Transformer.set_lm_head_dtype; ValueError on the CPU or a model that is not fp16).
+    frequency_penalty / presence_penalty != 0: the decode step draws with the fused sampler (DecodeGraph(native_sampling=True), its own
+    counter-based random numbers) and applies them there, over the tokens each sample has generated; ValueError without the captured
+    step (--compile 0, the CPU) or on a model without the fused decode step -- never dropped."""
     print(f"Using device={device}")
     dtype = {"float16": torch.float16, "bfloat16": torch.bfloat16, "float32": torch.float32, None: torch.float16}.get(dtype, dtype)
     if batch_size != 1:
@@ -476,7 +503,10 @@ def main(prompt=None, num_samples=5, max_new_tokens=100, batch_size=1, top_k=200
     if lm_head_dtype is not None:
         model.set_lm_head_dtype(lm_head_dtype)
     use_graph = bool(compile) and "cuda" in str(device)
-    graph = DecodeGraph(model, device, temperature=temperature, top_k=top_k) if use_graph else None
+    additive = dict(frequency_penalty=frequency_penalty, presence_penalty=presence_penalty) if frequency_penalty or presence_penalty else {}
+    if additive and not use_graph:
+        raise ValueError("frequency_penalty / presence_penalty are served by the captured decode step only (--compile >= 1 on a GPU)")
+    graph = DecodeGraph(model, device, native_sampling=bool(additive), temperature=temperature, top_k=top_k, **additive) if use_graph else None
     tps = []
     for i in range(-1 if use_graph else 0, num_samples):
         if "cuda" in str(device):
@@ -532,7 +562,11 @@ if __name__ == "__main__":
                         help='fp8: the KV cache as e4m3 codes, scale 1.0 per head (fused Any-Precision models; default fp16)')
     parser.add_argument('--lm_head_dtype', type=str, default=None, choices=["fp16", "int8"],
                         help='int8: the decode step reads a weight-only int8 copy of the lm_head, one scale per row (default fp16)')
+    parser.add_argument('--frequency_penalty', type=float, default=0.0,
+                        help='subtract this times the number of times a sample has generated a token from its logit (fused sampler; default 0)')
+    parser.add_argument('--presence_penalty', type=float, default=0.0,
+                        help='subtract this from the logit of every token a sample has generated (fused sampler; default 0)')
     a = parser.parse_args()
     main(a.prompt, a.num_samples, a.max_new_tokens, a.batch_size, a.top_k, a.temperature, a.compile, a.compile_prefill, a.profile,
          a.device, a.model_name, a.backend, a.bitwidth, a.checkpoint_path, a.config_path, a.dtype, a.print_result, a.random_init, a.kv_cache_dtype,
-         a.lm_head_dtype)
+         a.lm_head_dtype, a.frequency_penalty, a.presence_penalty)

@@ -859,6 +859,64 @@ int gq_sample_full_topn(const void *logits, uint32_t vocab, int top_k, float top
                         uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n, int *top_ids,
                         float *top_lps, void *topn_ws, void *stream);
 
+/* Additive adjustments of the logits inside the sampler's launches: a serving API's frequency_penalty, presence_penalty and logit_bias
+ * (csrc/sampler.hip, csrc/sampler_full.hip; the exact host model is tests/sampler_adj_model.py).  No [vocab] pass of its own, no host
+ * round trip: the counts are read and updated on the device, so a captured multi-step graph replays the entries.
+ *   member     token t is a member when its bit is set in bias_set (a listed bias of 0.0 still makes it one) or in out_set (the request has
+ *              generated it: out_count[t] > 0).  bias[t] is read for tokens of bias_set only, out_count[t] for tokens of out_set only.
+ *   formula    v = the fp16 logit widened to fp32, b = bias[t] (0 when not listed), c = out_count[t] (0 when not generated):
+ *                  p  = c > 0 ? fl32(fl32(frequency_penalty * (float)c) + presence_penalty) : 0
+ *                  s  = fl32(fl32(v + b) - p)
+ *                  h' = fp16(s): round to nearest even, subnormals kept, overflow to +-inf, NaN stays NaN.
+ *              Every operation is rounded on its own (no fused multiply-add).  The adjustment is DEFINED to give an fp16 logit: it costs at
+ *              most half an fp16 ulp of the logit, the precision the lm_head left in it.  A non-member keeps its bit pattern (-0 and NaN
+ *              included; a member's -0 with b = 0, p = 0 becomes +0).
+ *   adjusted   everything that draws sees h' in place of the fp16 logit: liveness (a NaN h' is no candidate), suppress / ban, the repetition
+ *              penalty (on h' widened, for tokens of `seen`, as in gq_sample_topk_rep), the order, top_k, temperature, nucleus, min_p, the race,
+ *              and lp_drawn.  A draw is therefore, bit for bit, the draw of the entry without the suffix on logits the host adjusted by
+ *              the formula -- next_tok, tok_io, pos_io, counter, seq_out, seen, x_out, ssq_out, lp_drawn (and gq_sample_full's report).
+ *   raw        lp_raw and the top-n rows keep reading the RAW logits: they describe the model's unprocessed distribution.
+ *   counts     out_count counts the tokens generated in this request; the prompt does not count (the meaning serving APIs give the two
+ *              penalties -- transformers' repetition_penalty, and `seen`, do include the prompt).  The caller clears out_set at the start
+ *              of a request; out_count[t] means something for the tokens of out_set only.
+ *   state      after the draw the publishing lane sets the token's bit in out_set and adds 1 to out_count[token] -- stores 1 when the bit
+ *              was not set before (vector atomics, next to the update of `seen`; the next call reads both behind a kernel boundary).  An
+ *              empty candidate set (token INT_MAX) leaves both alone.  Nothing else in the two arrays is written; bias_set and bias are
+ *              read only.
+ *   order      the additive terms come first, the repetition penalty behind them (vLLM applies its repetition penalty in front of the
+ *              frequency and presence terms).  transformers' sequence_bias adds to fp32 scores without the rounding to fp16.
+ * GqSampleAdjust: frequency_penalty, presence_penalty finite (0, 0 with out_set NULL: nothing is counted); bias_set (a token set) with bias
+ * (float [vocab]): both or neither; out_set (a token set) with out_count (uint32_t [vocab]): both or neither, required when a penalty is != 0.
+ * gq_token_bias_build: ONE launch that zeroes bias_set and then, for i < n, sets the bit of ids[i] and stores bias[ids[i]] = values[i].  Ids
+ * outside [0, vocab) are ignored; the ids are distinct (two values for one id: either is stored); the values are finite; the other words of
+ * bias are not written.  n == 0 just clears the set.
+ * gq_sample_topk_adj / gq_sample_full_adj: every parameter of gq_sample_topk_lp_topn / gq_sample_full_topn up to topn_ws, then adj.
+ *   top_n == 0   no list: top_ids, top_lps and topn_ws may be NULL and topn.hip's pair is not launched.
+ *   adj == NULL, or bias_set and out_set both NULL: the entry draws what the entry without the suffix draws, with its launches.
+ *   otherwise    gq_sample_topk_adj launches instances of the two-stage kernels of their own (fp32 keys, the log-probability code, every
+ *              pointer of it optional), gq_sample_full_adj instances of its token passes; the entries without the suffix launch what they
+ *              launched.
+ * Refusals, GQ_EINVAL, nothing launched or written: a penalty that is not finite, one pointer of a pair without the other, a penalty != 0
+ * without out_set.  Then the refusals of the entry without the suffix, with its codes (those of the top-n list only when top_n != 0). */
+typedef struct {
+    float frequency_penalty, presence_penalty; /* finite; 0, 0 with out_set NULL: nothing is counted */
+    const uint32_t *bias_set;
+    const float *bias; /* both or neither */
+    uint32_t *out_set;
+    uint32_t *out_count; /* both or neither; required when a penalty != 0 */
+} GqSampleAdjust;
+int gq_token_bias_build(const int *ids, const float *values, uint32_t n, uint32_t vocab, uint32_t *bias_set, float *bias, void *stream);
+int gq_sample_topk_adj(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
+                       float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                       uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                       uint32_t *seen, const uint32_t *suppress, float *lp_ws, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n,
+                       int *top_ids, float *top_lps, void *topn_ws, const GqSampleAdjust *adj, void *stream);
+int gq_sample_full_adj(const void *logits, uint32_t vocab, int top_k, float top_p, float min_p, float temperature, uint32_t seed,
+                       int *counter, void *ws, size_t ws_bytes, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                       uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                       uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n, int *top_ids,
+                       float *top_lps, void *topn_ws, const GqSampleAdjust *adj, void *stream);
+
 /* Test / tuning hooks (not part of the reference's surface).  gq_reset_env_cache: drop the cached GQ_* environment
  * knobs so that a test can flip them between calls.  gq_debug_set_timing_buffer: device buffer the plane kernels write
  * s_memtime phase stamps into (tools/phase_timing.py); NULL (default) disables it. */
