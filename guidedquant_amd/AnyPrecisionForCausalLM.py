@@ -452,7 +452,15 @@ class AnyPrecisionForCausalLM(nn.Module):
         processor, does include it).  They are logits processors, not warpers: a greedy request applies them too.  The additive terms
         come first and the repetition penalty behind them (vLLM penalises repetition first); transformers' sequence_bias adds to fp32
         scores without the rounding to fp16.  `logprobs` and `top_logprobs` stay the unprocessed distribution's, `sampled_logprobs`
-        sees the adjustment.  0, 0 and None / {}: a call without the keywords."""
+        sees the adjustment.  0, 0 and None / {}: a call without the keywords.
+        token_fsm=a `token_fsm.TokenFSM` (route 1 only; `native=False`, `capture=True`, a request route 1 declines, or min_new_tokens > 0 --
+        an EOS-only state under the ban would be empty -- raise ValueError("token_fsm: ..."), never a fall-back, and the keyword never
+        reaches transformers): constrained decoding inside the fused sampler's launches (gq_sample_topk_fsm / gq_sample_full_fsm).  Every
+        generated token is one the machine's current state allows -- the state's forbidden set stands in for the suppress list, so a
+        forbidden token takes no top_k place and `sampled_logprobs` is under the masked distribution -- and the drawn token moves the
+        state on the device: no host callback per token, and the multi-step replays keep working.  Every request starts in the machine's
+        start state.  `logprobs` and `top_logprobs` stay the unprocessed distribution's; the penalties, the suppress list and the bias
+        compose unchanged.  The decoder's sampler is keyed on the machine's content.  None: a call without the keyword."""
         prev_precision = self.precision
         if 'precision' in kwargs:
             self.set_precision(kwargs.pop('precision'))
@@ -470,12 +478,22 @@ class AnyPrecisionForCausalLM(nn.Module):
         top_n = kwargs.pop('top_logprobs', None)  # (popped as well; validated inside the try: the precision is restored on a refusal)
         # frequency_penalty / presence_penalty / logit_bias: additive adjustments inside the fused sampler.  Route 1 only, never a fall-back.
         adj = {k: kwargs.pop(k, None) for k in ("frequency_penalty", "presence_penalty", "logit_bias")}  # (popped as well; validated inside the try)
+        fsm = kwargs.pop("token_fsm", None)  # (popped as well; validated inside the try)
         try:
             from .fused_sampler import check_additive_penalty, check_logit_bias
             adj = dict(frequency_penalty=check_additive_penalty("frequency_penalty", adj["frequency_penalty"]),
                        presence_penalty=check_additive_penalty("presence_penalty", adj["presence_penalty"]),
                        logit_bias=check_logit_bias(adj["logit_bias"], int(getattr(self.config, "vocab_size", 0) or 0)))
             adj = {k: v for k, v in adj.items() if v}  # (the active ones; the first names the refusals below)
+            if fsm is not None:  # (the machine rides with the adjustments: the same route, the same refusals under its own name)
+                from .token_fsm import TokenFSM
+                if not isinstance(fsm, TokenFSM):
+                    raise ValueError(f"token_fsm: must be a guidedquant_amd.token_fsm.TokenFSM, not {type(fsm).__name__}")
+                try:
+                    fsm.check(int(getattr(self.config, "vocab_size", 0) or 0))
+                except ValueError as e:
+                    raise ValueError("token_fsm: " + str(e).removeprefix("token_fsm: ")) from None
+                adj = {"token_fsm": fsm, **adj}
             adj_name = next(iter(adj), None)
             if adj_name and (native is False or capture is True):
                 raise ValueError(f"{adj_name}: served by the fused decode model only (not with native=False or capture=True)")
@@ -504,6 +522,8 @@ class AnyPrecisionForCausalLM(nn.Module):
                 raise ValueError("output_logprobs=True: " + why)
             if adj_name and req is None:
                 raise ValueError(f"{adj_name}: " + why)
+            if fsm is not None and req["min_new"] > 0:
+                raise ValueError("token_fsm: not served together with min_new_tokens > 0 (a state that allows only EOS would be empty under the ban)")
             if native is True and req is None:
                 raise ValueError("native=True: " + why)
             if req is not None and native is not False:
@@ -835,6 +855,7 @@ class AnyPrecisionForCausalLM(nn.Module):
             sampler.reseed(self._fresh_rng_word())
         sampler.set_history(ids32)  # (the penalty's token set: all T prompt tokens, rebuilt per request)
         sampler.reset_generated()  # (the counts of a frequency / presence penalty: this request has generated nothing yet)
+        sampler.reset_fsm()  # (a token_fsm: the machine is in its start state)
         if req["streamer"] is not None:
             req["streamer"].put(ids.cpu())
         done, cut = 0, None
@@ -877,7 +898,7 @@ class AnyPrecisionForCausalLM(nn.Module):
         key = (self.precision, dec.max_seq_length, dec.kv_cache_dtype, req["temperature"], req["top_k"], req["top_p"], req["repetition_penalty"], req["suppress_tokens"]) \
             + ((("logprobs", True), ) if logprobs else ()) + ((("min_p", req["min_p"]), ) if req["min_p"] else ()) \
             + ((("top_logprobs", top_logprobs), ) if top_logprobs else ()) + ((("lm_head", "int8"), ) if lm_head_dtype == "int8" else ()) \
-            + tuple((k, tuple(sorted(v.items())) if isinstance(v, dict) else v) for k, v in sorted((adjust or {}).items()))
+            + tuple((k, tuple(sorted(v.items())) if isinstance(v, dict) else v.key() if k == "token_fsm" else v) for k, v in sorted((adjust or {}).items()))
         graph = self._native_cache.get(("graph",) + key)
         if graph is None:
             self._evict("graph")

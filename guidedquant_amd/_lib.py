@@ -32,6 +32,7 @@ EXPORTS = [
     "gq_sample_topk_lp", "gq_attn_prefill_packed", "gq_rope_cache_rows_packed",
     "gq_sample_full_ws_bytes", "gq_sample_full", "gq_sample_topk_lp_topn", "gq_sample_full_topn", "gq_dense_gemv_i8",
     "gq_token_bias_build", "gq_sample_topk_adj", "gq_sample_full_adj",
+    "gq_token_fsm_build", "gq_sample_topk_fsm", "gq_sample_full_fsm",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -54,6 +55,11 @@ class GqQtipIn(ctypes.Structure):  # include/gq_hip.h
 class GqSampleAdjust(ctypes.Structure):  # include/gq_hip.h: the additive adjustments of gq_sample_topk_adj / gq_sample_full_adj
     _fields_ = [("frequency_penalty", ctypes.c_float), ("presence_penalty", ctypes.c_float), ("bias_set", ctypes.c_void_p),
                 ("bias", ctypes.c_void_p), ("out_set", ctypes.c_void_p), ("out_count", ctypes.c_void_p)]
+
+
+class GqTokenFsm(ctypes.Structure):  # include/gq_hip.h: the token-level state machine of gq_sample_topk_fsm / gq_sample_full_fsm
+    _fields_ = [("masks", ctypes.c_void_p), ("words_per_state", ctypes.c_uint32), ("n_states", ctypes.c_uint32), ("row_ptr", ctypes.c_void_p),
+                ("edge_tok", ctypes.c_void_p), ("edge_next", ctypes.c_void_p), ("default_next", ctypes.c_void_p), ("state", ctypes.c_void_p)]
 
 
 class GqQtipXf(ctypes.Structure):
@@ -154,6 +160,11 @@ def lib():
         L.gq_sample_topk_adj.argtypes = L.gq_sample_topk_lp_topn.argtypes[:-1] + [ctypes.POINTER(GqSampleAdjust), vp]
         L.gq_sample_full_adj.argtypes = L.gq_sample_full_topn.argtypes[:-1] + [ctypes.POINTER(GqSampleAdjust), vp]
         L.gq_token_bias_build.argtypes = [vp, vp, u32, u32, vp, vp, vp]  # (ids, values, n, vocab, bias_set, bias, stream)
+        # (the state-machine forms: the adjusted form's parameters, then the GqTokenFsm in front of the stream)
+        L.gq_sample_topk_fsm.argtypes = L.gq_sample_topk_adj.argtypes[:-1] + [ctypes.POINTER(GqTokenFsm), vp]
+        L.gq_sample_full_fsm.argtypes = L.gq_sample_full_adj.argtypes[:-1] + [ctypes.POINTER(GqTokenFsm), vp]
+        # (row_ptr, edge_tok, edge_next, default_next, n_states, vocab, base_suppress, masks, stream)
+        L.gq_token_fsm_build.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp]
         L.gq_sample_full_ws_bytes.restype = ctypes.c_size_t
         L.gq_token_set_build.argtypes = [vp, u32, u32, vp, i32, vp]
         L.gq_anyprec_gemv_cpu.argtypes = [vp, vp, vp, vp, u32, u32, u32, i32, i32, i32]

@@ -125,7 +125,9 @@ struct Opt<true, T> {
 // <false, false> instances are pinned (tools/cmp_kernels.py against the build before a change, profiles/sampler_unify_cmp_kernels.txt).
 // <true, true> with ADJ serves gq_sample_topk_adj (frequency / presence penalty, logit bias: a member token's adjusted fp16 pattern h' --
 // gqs::adjust16 -- stands in for its logit at the key site of stage 1, stage 2 counts the drawn token); ADJ = false leaves every other
-// instance the instructions it had (profiles/sampler_adjust_cmp_kernels.txt).
+// instance the instructions it had (profiles/sampler_adjust_cmp_kernels.txt).  The same ADJ instances serve gq_sample_topk_fsm (a token-level
+// state machine: SampleAdj carries a SampleFsm; stage 1 takes the mask row of the machine's state for `suppress`, stage 2's publishing lane
+// makes the transition -- gqs::fsm_suppress, gqs::sample_fsm_step).
 // What moves an instance is not the sharing but the SHAPE of an expression: a conversion inside or outside the arm of a select turns a
 // v_cndmask into a branch, or four narrow loads into one wide one.  Where an instance's sequence or its measured time needs another
 // shape the text forks at compile time, on PLAIN or LP, under a comment `fork (site)` that names the instruction difference (DESIGN.md,
@@ -155,6 +157,8 @@ __global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32
     const SampleRep rep = rep_.get();
     float *const lp_ws = lp_ws_.get();
     const SampleAdj adj = adj_.get();
+    const u32 *suppress = rep.suppress;
+    if constexpr (ADJ) suppress = fsm_suppress(adj.fsm, suppress);  // (_fsm) the forbidden set of the machine's state stands in for the set
     const u32 per = (V + SAMP_BLOCKS - 1) / SAMP_BLOCKS;  // <= 256 * EPT
     const u32 lo = blockIdx.x * per, hi = min(lo + per, V);
     const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
@@ -165,7 +169,7 @@ __global__ void __launch_bounds__(256) sample_stage1(const uint16_t *logits, u32
     if (REP && g0 < hi) {  // (words of tokens < hi <= V only: a set is ceil(V / 32) words)
         const u32 w0 = g0 >> 5, w1 = min(g0 + (u32)EPT - 1u, hi - 1u) >> 5;
         if (rep.seen) sbits = ((u64)rep.seen[w0] | ((u64)(w1 != w0 ? rep.seen[w1] : 0u) << 32)) >> (g0 & 31u);
-        if (rep.suppress) pbits = ((u64)rep.suppress[w0] | ((u64)(w1 != w0 ? rep.suppress[w1] : 0u) << 32)) >> (g0 & 31u);
+        if (suppress) pbits = ((u64)suppress[w0] | ((u64)(w1 != w0 ? suppress[w1] : 0u) << 32)) >> (g0 & 31u);
     }
     u64 bbits = 0ull, cbits = 0ull;  // (ADJ) bit e: the token has a listed bias / has been generated: the two ways of being a member
     if (ADJ && g0 < hi) {
@@ -399,7 +403,10 @@ __global__ void __launch_bounds__(1024) sample_stage2(const float *cand_val, con
             if (l == 0) {
                 const int p = pos_io ? pos_io[0] : 0;  // (before sample_publish increments it)
                 sample_publish(tokc, ctr, counter, tok_io, pos_io, next_tok, ex, seen, V);
-                if constexpr (ADJ) sample_count(tokc, V, adj_.get());  // (the drawn token's count and its bit in out_set, next to `seen`)
+                if constexpr (ADJ) {
+                    sample_count(tokc, V, adj_.get());  // (the drawn token's count and its bit in out_set, next to `seen`)
+                    sample_fsm_step(tokc, V, adj_.get().fsm);  // (_fsm) the machine's transition: the next draw's stage 1 reads the word
+                }
                 chosen = tokc;
                 if ((u32)(p + 1) < lp.cap) {
                     if (lp.raw) lp.raw[p + 1] = lraw;
@@ -442,6 +449,33 @@ __global__ void __launch_bounds__(1024) token_bias_build(const int *ids, const f
             atomicOr(bias_set + (t >> 5), 1u << (t & 31u));
             bias[t] = values[i];
         }
+    }
+}
+
+// the mask rows of gq_token_fsm_build: block s builds row s of `masks`, the FORBIDDEN set of state s -- the row is filled by the state's
+// default (default_next[s] < 0: every token forbidden, else none), the block meets, every edge of the row then forbids (edge_next < 0) or
+// allows its token, the block meets again, and the request's static set and the bits at and past V in the last word are OR-ed on top.  The
+// second and third phase use vector atomics only (tokens of one word come from several threads; no thread reads back a word another one
+// stored).  An edge token outside [0, V) is ignored.
+__global__ void __launch_bounds__(256) token_fsm_build(const int *row_ptr, const int *edge_tok, const int *edge_next, const int *default_next, u32 V,
+                                                        const u32 *base, u32 *masks) {
+    const u32 words = (V + 31u) / 32u, s = blockIdx.x;
+    u32 *row = masks + (size_t)s * words;
+    const u32 fill = default_next[s] < 0 ? 0xFFFFFFFFu : 0u;
+    for (u32 i = threadIdx.x; i < words; i += 256u) row[i] = fill;
+    __syncthreads();
+    const int lo = row_ptr[s], hi = row_ptr[s + 1];
+    for (int e = lo + (int)threadIdx.x; e < hi; e += 256) {
+        const u32 t = (u32)edge_tok[e];
+        if (t >= V) continue;
+        if (edge_next[e] < 0) atomicOr(row + (t >> 5), 1u << (t & 31u));
+        else atomicAnd(row + (t >> 5), ~(1u << (t & 31u)));
+    }
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < words; i += 256u) {
+        u32 m = base ? base[i] : 0u;
+        if (i == words - 1u && (V & 31u)) m |= 0xFFFFFFFFu << (V & 31u);
+        if (m) atomicOr(row + i, m);
     }
 }
 
@@ -561,13 +595,24 @@ extern "C" int gq_token_bias_build(const int *ids, const float *values, uint32_t
     return GQ_OK;
 }
 
-extern "C" int gq_sample_topk_adj(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
-                                  float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
-                                  uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
-                                  uint32_t *seen, const uint32_t *suppress, float *lp_ws, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n,
-                                  int *top_ids, float *top_lps, void *topn_ws, const GqSampleAdjust *adj, void *stream) {
+extern "C" int gq_token_fsm_build(const int *row_ptr, const int *edge_tok, const int *edge_next, const int *default_next, uint32_t n_states,
+                                  uint32_t vocab, const uint32_t *base_suppress, uint32_t *masks, void *stream) {
+    if (!row_ptr || !edge_next || !default_next || !masks || !n_states || !vocab)
+        return gq_fail(GQ_EINVAL, "gq_token_fsm_build: null pointer argument, n_states == 0 or vocab == 0.");
+    hipLaunchKernelGGL(token_fsm_build, dim3(n_states), dim3(256), 0, (hipStream_t)stream, row_ptr, edge_tok, edge_next, default_next, vocab, base_suppress, masks);
+    GQ_HIP_CHECK(hipGetLastError());
+    return GQ_OK;
+}
+
+// gq_sample_topk_adj (fsm == NULL) and gq_sample_topk_fsm: one body
+static int sample_topk_adj_fsm(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
+                               float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                               uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                               uint32_t *seen, const uint32_t *suppress, float *lp_ws, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n,
+                               int *top_ids, float *top_lps, void *topn_ws, const GqSampleAdjust *adj, const GqTokenFsm *fsm, void *stream) {
     if (int rc = sample_adjust_ok(adj)) return rc;
-    if (sample_adjust_neutral(adj)) {  // the entry without the suffix: its launches, its refusals
+    if (int rc = sample_fsm_ok(fsm, vocab)) return rc;
+    if (!fsm && sample_adjust_neutral(adj)) {  // the entry without the suffix: its launches, its refusals
         if (top_n)
             return gq_sample_topk_lp_topn(logits, vocab, top_k, top_p, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ban, seq_out,
                                           seq_cap, embed_table, x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_ws, lp_raw, lp_drawn, lp_cap, top_n,
@@ -583,9 +628,29 @@ extern "C" int gq_sample_topk_adj(const void *logits, uint32_t vocab, int top_k,
     if (int rc = sample_extras(ex, vocab, top_p, ban, seq_out, seq_cap, embed_table, x_out, dim, ssq_out)) return rc;
     const SampleRep rep{repetition_penalty, seen, suppress};
     const SampleLp lp{lp_raw ? lp_ws : nullptr, lp_raw, lp_drawn, lp_cap, (const uint16_t *)logits};
-    const SampleAdj a = sample_adjust_of(adj);
+    const SampleAdj a = fsm ? sample_fsm_of(adj, fsm) : sample_adjust_of(adj);
     if (int rc = sample_launch(logits, vocab, top_k, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ex, stream, &rep, seen, &lp, &a))
         return rc;
     if (!top_n) return GQ_OK;
     return gq_topn_launch(logits, vocab, top_n, lp_ws, pos_io, top_ids, top_lps, lp_cap, topn_ws, stream);
+}
+
+extern "C" int gq_sample_topk_adj(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
+                                  float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                                  uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                                  uint32_t *seen, const uint32_t *suppress, float *lp_ws, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n,
+                                  int *top_ids, float *top_lps, void *topn_ws, const GqSampleAdjust *adj, void *stream) {
+    return sample_topk_adj_fsm(logits, vocab, top_k, top_p, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ban, seq_out, seq_cap,
+                               embed_table, x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_ws, lp_raw, lp_drawn, lp_cap, top_n, top_ids, top_lps,
+                               topn_ws, adj, nullptr, stream);
+}
+
+extern "C" int gq_sample_topk_fsm(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
+                                  float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                                  uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                                  uint32_t *seen, const uint32_t *suppress, float *lp_ws, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n,
+                                  int *top_ids, float *top_lps, void *topn_ws, const GqSampleAdjust *adj, const GqTokenFsm *fsm, void *stream) {
+    return sample_topk_adj_fsm(logits, vocab, top_k, top_p, temperature, seed, counter, work_val, work_idx, tok_io, pos_io, next_tok, ban, seq_out, seq_cap,
+                               embed_table, x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_ws, lp_raw, lp_drawn, lp_cap, top_n, top_ids, top_lps,
+                               topn_ws, adj, fsm, stream);
 }

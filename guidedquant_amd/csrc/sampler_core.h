@@ -48,12 +48,47 @@ __device__ __forceinline__ uint16_t adjust16(uint16_t h, float b, u32 c, float f
     const float s = __fsub_rn(__fadd_rn(v, b), p);
     return __builtin_bit_cast(uint16_t, (_Float16)s);
 }
-// what the entries with the suffix _adj hand to their kernels: GqSampleAdjust (include/gq_hip.h) as the device sees it
+// The token-level state machine of the entries with the suffix _fsm: GqTokenFsm (include/gq_hip.h) as the device sees it.  state == NULL:
+// none.  Row s of `masks` (`stride` words) is the FORBIDDEN set of state s in the layout of `suppress`; row s of the CSR table (edge_tok
+// ascending in [row_ptr[s], row_ptr[s + 1])) and default_next[s] give the state behind a drawn token, -1 = none.
+struct SampleFsm {
+    int *state;
+    const u32 *masks;
+    u32 stride, n_states;
+    const int *row_ptr, *edge_tok, *edge_next, *default_next;
+};
+// the state word as the kernels take it: a word outside [0, n_states) (the caller's mistake) is read as the last state, so that no row
+// outside the tables is addressed
+__device__ __forceinline__ u32 fsm_state_of(const SampleFsm &f) { return min((u32)f.state[0], f.n_states - 1u); }
+// the `suppress` bitmap of this draw: the mask row of the current state (a wave-uniform load at kernel entry: the previous draw's last
+// kernel wrote the word, behind a kernel boundary), or without a machine the caller's set
+__device__ __forceinline__ const u32 *fsm_suppress(const SampleFsm &f, const u32 *suppress) {
+    return f.state ? f.masks + (size_t)fsm_state_of(f) * f.stride : suppress;
+}
+// the transition, ONE lane, next to sample_publish: a binary search of the drawn token in the state's row, a hit gives edge_next, a miss
+// default_next; an ordinary vector store.  The token of an empty candidate set, or a result of -1, leaves the state as it is.
+__device__ __forceinline__ void sample_fsm_step(int tokc, u32 V, const SampleFsm &f) {
+    if (!f.state || (u32)tokc >= V) return;
+    const u32 s = fsm_state_of(f);
+    int lo = f.row_ptr[s], hi = f.row_ptr[s + 1], nx = f.default_next[s];
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1), t = f.edge_tok[mid];
+        if (t == tokc) {
+            nx = f.edge_next[mid];
+            break;
+        }
+        if (t < tokc) lo = mid + 1;
+        else hi = mid;
+    }
+    if (nx >= 0 && (u32)nx < f.n_states) f.state[0] = nx;
+}
+// what the entries with the suffix _adj hand to their kernels: GqSampleAdjust (include/gq_hip.h) as the device sees it, and (_fsm) the machine
 struct SampleAdj {
     float fp, pp;
     const u32 *bias_set;
     const float *bias;
     u32 *out_set, *out_count;
+    SampleFsm fsm;
 };
 // the adjusted pattern of token gi with raw pattern h: bias[] and out_count[] are read for members only (the words of a non-member are undefined)
 __device__ __forceinline__ uint16_t adjust_token(uint16_t h, u32 gi, bool biased, bool counted, const SampleAdj &a) {
@@ -218,6 +253,22 @@ inline int sample_adjust_ok(const GqSampleAdjust *a) {
 // (behind sample_adjust_ok) nothing is biased and nothing is counted: the entry without the suffix serves the call
 inline bool sample_adjust_neutral(const GqSampleAdjust *a) { return !a || (!a->bias_set && !a->out_set); }
 inline SampleAdj sample_adjust_of(const GqSampleAdjust *a) {
-    return SampleAdj{a->frequency_penalty, a->presence_penalty, a->bias_set, a->bias, a->out_set, a->out_count};
+    return SampleAdj{a->frequency_penalty, a->presence_penalty, a->bias_set, a->bias, a->out_set, a->out_count, SampleFsm{}};
+}
+// the refusals of a GqTokenFsm (NULL: no machine), in front of every other check of the entries with the suffix _fsm.  The tables live on
+// the device: their CONTENT is the builder's business (guidedquant_amd/token_fsm.py validates it), here only the struct is checked.
+inline int sample_fsm_ok(const GqTokenFsm *f, uint32_t vocab) {
+    if (!f) return GQ_OK;
+    if (!f->masks || !f->row_ptr || !f->edge_next || !f->default_next || !f->state)
+        return gq_fail(GQ_EINVAL, "fsm: masks, row_ptr, edge_next, default_next and state must not be NULL.");
+    if (!f->n_states) return gq_fail(GQ_EINVAL, "fsm: n_states must be >= 1.");
+    if (f->words_per_state != (vocab + 31u) / 32u) return gq_fail(GQ_EINVAL, "fsm: words_per_state must be ceil(vocab / 32).");
+    return GQ_OK;
+}
+// a machine next to an adjustment (NULL or neutral: nothing is biased and nothing is counted)
+inline SampleAdj sample_fsm_of(const GqSampleAdjust *a, const GqTokenFsm *f) {
+    SampleAdj s = sample_adjust_neutral(a) ? SampleAdj{} : sample_adjust_of(a);
+    s.fsm = SampleFsm{f->state, f->masks, f->words_per_state, f->n_states, f->row_ptr, f->edge_tok, f->edge_next, f->default_next};
+    return s;
 }
 }  // namespace gqs

@@ -18,6 +18,8 @@
 //   full_race    128 blocks  the exponential race over the slice's candidates: the best (score, id) per block.
 //   full_finish  1 block     the best of the 128, the log-probabilities, publishing, the embedding fold.
 // gq_sample_full_topn (at the end of the file): the same six launches, then topn.hip's pair, which reads the partials full_hist left at WS_LP.
+// gq_sample_full_fsm: gq_sample_full_adj's launches with a token-level state machine: the forbidden set of the machine's state (a row of
+// its masks, chosen by a device word) stands in for `suppress` in the three passes that read it, full_finish makes the transition.
 // gq_sample_full_adj: the same six launches with the ADJ instances of the four kernels that read tokens -- a member token's adjusted fp16
 // pattern (gqs::adjust16) stands in for its logit in liveness, the histogram bin, the value s, the ties and the race; the log-probability
 // partials and lp_raw keep the raw pattern; full_finish counts the drawn token.
@@ -147,6 +149,7 @@ __global__ void __launch_bounds__(FT) full_zero(uint4 *hist, u32 n16, u32 *maxke
 template <bool ADJ>
 __global__ void __launch_bounds__(FT) full_hist(ToksOf<ADJ> t, u32 *hist, u32 *maxkey, float *lp_part) {
     __shared__ float red[FT / 64];
+    if constexpr (ADJ) t.suppress = fsm_suppress(t.adj.fsm, t.suppress);  // (_fsm) the forbidden set of the machine's state stands in for the set
     const Slice sl = slice_of(t);
     const u32 tid = threadIdx.x;
     float raw[EPT];
@@ -419,6 +422,7 @@ __global__ void __launch_bounds__(1024) full_scan(unsigned char *ws, ScanArgs A)
 template <bool ADJ>
 __global__ void __launch_bounds__(FT) full_ties(ToksOf<ADJ> t, const unsigned char *ws, u32 *ties) {
     __shared__ u32 red[FT / 64];
+    if constexpr (ADJ) t.suppress = fsm_suppress(t.adj.fsm, t.suppress);  // (_fsm) the forbidden set of the machine's state stands in for the set
     const Cut cut = *reinterpret_cast<const Cut *>(ws + WS_CUT);
     const u32 tid = threadIdx.x;
     u32 c = 0u;
@@ -443,6 +447,7 @@ __global__ void __launch_bounds__(FT) full_race(ToksOf<ADJ> t, const unsigned ch
     __shared__ u32 wt[FT / 64];
     __shared__ float rs[FT / 64];
     __shared__ int rt[FT / 64];
+    if constexpr (ADJ) t.suppress = fsm_suppress(t.adj.fsm, t.suppress);  // (_fsm) the forbidden set of the machine's state stands in for the set
     const Cut cut = *reinterpret_cast<const Cut *>(ws + WS_CUT);
     const Slice sl = slice_of(t);
     const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u;
@@ -560,7 +565,10 @@ __global__ void __launch_bounds__(1024) full_finish(ToksOf<ADJ> t, const unsigne
                 if (F.lp_drawn) ldrawn = (float)((double)(a == cut.m ? 0.f : a - cut.m) - log((double)cut.zkept * (1.0 / WONE)));
             }
             sample_publish(tokc, ctr, F.counter, F.tok_io, F.pos_io, F.next_tok, F.ex, F.seen_out, t.V);
-            if constexpr (ADJ) sample_count(tokc, t.V, t.adj);
+            if constexpr (ADJ) {
+                sample_count(tokc, t.V, t.adj);
+                sample_fsm_step(tokc, t.V, t.adj.fsm);  // (_fsm) the machine's transition: the next draw's full_hist reads the word
+            }
             if ((u32)(p + 1) < F.lp_cap) {
                 if (F.lp_raw) F.lp_raw[p + 1] = lraw;
                 if (F.lp_drawn) F.lp_drawn[p + 1] = ldrawn;
@@ -637,23 +645,45 @@ extern "C" int gq_sample_full_topn(const void *logits, uint32_t vocab, int top_k
     return gq_topn_launch(logits, vocab, top_n, (const float *)((unsigned char *)ws + WS_LP), pos_io, top_ids, top_lps, lp_cap, topn_ws, stream);
 }
 
-extern "C" int gq_sample_full_adj(const void *logits, uint32_t vocab, int top_k, float top_p, float min_p, float temperature, uint32_t seed,
-                                  int *counter, void *ws, size_t ws_bytes, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
-                                  uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
-                                  uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n, int *top_ids,
-                                  float *top_lps, void *topn_ws, const GqSampleAdjust *adj, void *stream) {
+// gq_sample_full_adj (fsm == NULL) and gq_sample_full_fsm: one body
+static int sample_full_adj_fsm(const void *logits, uint32_t vocab, int top_k, float top_p, float min_p, float temperature, uint32_t seed,
+                               int *counter, void *ws, size_t ws_bytes, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                               uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                               uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n, int *top_ids,
+                               float *top_lps, void *topn_ws, const GqSampleAdjust *adj, const GqTokenFsm *fsm, void *stream) {
     if (int rc = sample_adjust_ok(adj)) return rc;
+    if (int rc = sample_fsm_ok(fsm, vocab)) return rc;
     if (top_n)
         if (int rc = gq_topn_check(vocab, top_n, top_ids, top_lps, topn_ws, lp_raw && ws ? ws : nullptr)) return rc;
-    if (sample_adjust_neutral(adj)) {  // the entry without the suffix: its launches, its refusals
+    if (!fsm && sample_adjust_neutral(adj)) {  // the entry without the suffix: its launches, its refusals
         if (int rc = gq_sample_full(logits, vocab, top_k, top_p, min_p, temperature, seed, counter, ws, ws_bytes, tok_io, pos_io, next_tok, ban, seq_out, seq_cap,
                                     embed_table, x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_raw, lp_drawn, lp_cap, stream))
             return rc;
     } else if (int rc = full_launch<true>(logits, vocab, top_k, top_p, min_p, temperature, seed, counter, ws, ws_bytes, tok_io, pos_io, next_tok, ban, seq_out,
                                           seq_cap, embed_table, x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_raw, lp_drawn, lp_cap,
-                                          sample_adjust_of(adj), stream)) {
+                                          fsm ? sample_fsm_of(adj, fsm) : sample_adjust_of(adj), stream)) {
         return rc;
     }
     if (!top_n) return GQ_OK;
     return gq_topn_launch(logits, vocab, top_n, (const float *)((unsigned char *)ws + WS_LP), pos_io, top_ids, top_lps, lp_cap, topn_ws, stream);
+}
+
+extern "C" int gq_sample_full_adj(const void *logits, uint32_t vocab, int top_k, float top_p, float min_p, float temperature, uint32_t seed,
+                                  int *counter, void *ws, size_t ws_bytes, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                                  uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                                  uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n, int *top_ids,
+                                  float *top_lps, void *topn_ws, const GqSampleAdjust *adj, void *stream) {
+    return sample_full_adj_fsm(logits, vocab, top_k, top_p, min_p, temperature, seed, counter, ws, ws_bytes, tok_io, pos_io, next_tok, ban, seq_out, seq_cap,
+                               embed_table, x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_raw, lp_drawn, lp_cap, top_n, top_ids, top_lps, topn_ws, adj,
+                               nullptr, stream);
+}
+
+extern "C" int gq_sample_full_fsm(const void *logits, uint32_t vocab, int top_k, float top_p, float min_p, float temperature, uint32_t seed,
+                                  int *counter, void *ws, size_t ws_bytes, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                                  uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                                  uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n, int *top_ids,
+                                  float *top_lps, void *topn_ws, const GqSampleAdjust *adj, const GqTokenFsm *fsm, void *stream) {
+    return sample_full_adj_fsm(logits, vocab, top_k, top_p, min_p, temperature, seed, counter, ws, ws_bytes, tok_io, pos_io, next_tok, ban, seq_out, seq_cap,
+                               embed_table, x_out, dim, ssq_out, repetition_penalty, seen, suppress, lp_raw, lp_drawn, lp_cap, top_n, top_ids, top_lps, topn_ws, adj,
+                               fsm, stream);
 }

@@ -14,7 +14,10 @@ needs is decided here and nowhere else:
                                           the sets and the log-probabilities itself, from its own workspace);
   * frequency_penalty / presence_penalty != 0 or a logit_bias -> the entry with the suffix _adj (gq_sample_topk_adj / gq_sample_full_adj, by
                                           the rule above), which takes everything the others take.  Without the three the sampler makes
-                                          exactly the calls listed above.
+                                          exactly the calls listed above;
+  * token_fsm = a TokenFSM             -> the entry with the suffix _fsm (gq_sample_topk_fsm / gq_sample_full_fsm, by the same rule): the _adj
+                                          entry's parameters and the machine's tables; constrained decoding inside the same launches.
+                                          Without a machine the sampler makes exactly the calls listed above.
 """
 import ctypes
 import math
@@ -22,6 +25,7 @@ import math
 import torch
 
 from . import _lib
+from .token_fsm import TokenFSM
 
 BLOCKS = 128  # (stage 1's grid: the workspace holds `candidates` entries of each block)
 
@@ -85,11 +89,14 @@ class FusedSampler:
     their log-probabilities, against the log-sum-exp lp_raw is taken against), `bias_set` / `bias` (a logit_bias: the bitmap of the
     listed ids and fp32 [vocab], built once in the constructor), `out_set` / `out_count` (a frequency_penalty or presence_penalty != 0: the
     bitmap and the uint32 counts of the tokens generated in THIS request -- every drawn token is counted on the device;
-    `reset_generated()` at the start of every request).  A request without them allocates nothing extra."""
+    `reset_generated()` at the start of every request), `fsm_tables` / `fsm_masks` / `fsm_state` (a token_fsm: the machine's CSR tables, its
+    mask rows -- uint32 [n_states, ceil(vocab / 32)], a state's FORBIDDEN set joined with the suppress list, built once in the constructor
+    by gq_token_fsm_build -- and the device word every draw reads its row by and moves; `reset_fsm()` at the start of every request).  A
+    request without them allocates nothing extra."""
 
     def __init__(self, vocab_size, device, top_k, top_p=1.0, temperature=1.0, seed=1234, seq_capacity=0, repetition_penalty=1.0,
                  suppress_tokens=(), logprobs=False, candidates=64, min_p=0.0, top_logprobs=0, frequency_penalty=0.0, presence_penalty=0.0,
-                 logit_bias=None):
+                 logit_bias=None, token_fsm=None):
         self.min_p = float(min_p or 0.0)
         if not 0.0 <= self.min_p <= 1.0:
             raise ValueError(f"min_p must be in [0, 1], not {min_p!r}")
@@ -118,6 +125,16 @@ class FusedSampler:
         self.adjusted = counted or bool(self.logit_bias)  # (the entries with the suffix _adj)
         if self.narrow and self.adjusted:
             raise ValueError("a workspace of 32 candidates per block serves the draw alone (gq_sample_topk)")
+        if token_fsm is not None and not isinstance(token_fsm, TokenFSM):
+            raise ValueError(f"token_fsm must be a guidedquant_amd.token_fsm.TokenFSM, not {type(token_fsm).__name__}")
+        if self.narrow and token_fsm is not None:
+            raise ValueError("token_fsm: a workspace of 32 candidates per block serves the draw alone (gq_sample_topk)")
+        self.token_fsm = token_fsm
+        if token_fsm is not None:
+            token_fsm.check(self.vocab_size)  # (ids inside the vocabulary, no dead end, the size of the masks)
+            for s in token_fsm._reachable if suppress_tokens else ():  # (the suppress list joins every state's forbidden set)
+                if token_fsm.default_next[s] < 0 and not set(token_fsm.allowed(s).tolist()) - set(suppress_tokens):
+                    raise ValueError(f"token_fsm: state {s} allows no token that suppress_tokens leaves (a dead end)")
 
         def z(n, dtype=torch.int32):
             return torch.zeros((int(n), ), dtype=dtype, device=device)
@@ -160,6 +177,19 @@ class FusedSampler:
             self._adj = _lib.GqSampleAdjust(self.frequency_penalty, self.presence_penalty, *(t.data_ptr() if t is not None else None for t in
                                                                                           (self.bias_set, self.bias, self.out_set, self.out_count)))
 
+        self.fsm_tables = self.fsm_masks = self.fsm_state = self._fsm = None
+        if token_fsm is not None:
+            f, words = token_fsm, (self.vocab_size + 31) // 32
+            # (a machine without edges still gets one word per edge table: the C call takes no NULL for edge_next)
+            self.fsm_tables = tuple(torch.tensor(a.tolist() or [0], dtype=torch.int32, device=device)
+                                    for a in (f.row_ptr, f.edge_tok, f.edge_next, f.default_next))
+            self.fsm_masks, self.fsm_state = z(f.n_states * words).view(f.n_states, words), z(1)
+            _lib.check(_lib.lib().gq_token_fsm_build(*(t.data_ptr() for t in self.fsm_tables), f.n_states, self.vocab_size,
+                                                    self.suppress.data_ptr() if self.suppress is not None else None, self.fsm_masks.data_ptr(),
+                                                    _lib.current_stream_ptr()), "gq_token_fsm_build")
+            self._fsm = _lib.GqTokenFsm(self.fsm_masks.data_ptr(), words, f.n_states, *(t.data_ptr() for t in self.fsm_tables), self.fsm_state.data_ptr())
+            self.reset_fsm()
+
     def build_set(self, words, ids, clear=True):
         """words = (clear: the set of `ids`; else: joined by `ids`), one launch outside any graph"""
         ids = ids.to(device=words.device, dtype=torch.int32).contiguous().view(-1)
@@ -199,11 +229,28 @@ class FusedSampler:
             self.out_count.index_add_(0, ids, torch.ones_like(ids, dtype=torch.int32))
             self.build_set(self.out_set, ids, clear=False)
 
+    def reset_fsm(self, state=None):
+        """the start of a request: the machine is in `state` (None: its start state).  Next to set_history / reset_generated; without a
+        token_fsm nothing happens."""
+        if self.token_fsm is not None:
+            self._fsm_host = self.token_fsm._state(state)
+            self.fsm_state.fill_(self._fsm_host)
+
+    def advance_fsm(self, ids):
+        """tokens this request produced OUTSIDE the sampler (a first token drawn from the prompt pass's logits) move the machine: walked on
+        the host from the state reset_fsm / the last advance_fsm left, and the state word written.  ValueError at a token the machine
+        forbids.  Without a token_fsm nothing happens."""
+        if self.token_fsm is not None:
+            ids = ids.view(-1).tolist() if torch.is_tensor(ids) else list(ids)
+            self.reset_fsm(self.token_fsm.walk(ids, self._fsm_host))
+
     def clear_warmup(self):
-        """the warm-up and capture-time draws joined `seen` and were counted: their bits and counts go"""
+        """the warm-up and capture-time draws joined `seen`, were counted and moved the machine: their bits and counts go, the state is
+        the start state again"""
         if self.seen is not None:
             self.seen.zero_()
         self.reset_generated()
+        self.reset_fsm()
 
     def launch(self, logits, tok_io, pos_io, next_tok, embed_table=None, x_out=None, dim=0, ssq_out=None):
         """one draw from `logits` on the current stream: the token to `next_tok` and, fed back, to `tok_io`, with `pos_io` advanced;
@@ -216,7 +263,10 @@ class FusedSampler:
                     p(embed_table), p(x_out), dim, p(ssq_out), self.repetition_penalty, p(self.seen), p(self.suppress), p(self.lp_raw), p(self.lp_drawn),
                     self.lp_raw.numel() if self.lp_raw is not None else 0)
             name = "gq_sample_full"
-            if self.adjusted:
+            if self.token_fsm is not None:
+                name, args = "gq_sample_full_fsm", args + (self.top_logprobs, p(self.top_ids), p(self.top_lps), p(self.topn_ws),
+                                                           ctypes.byref(self._adj) if self.adjusted else None, ctypes.byref(self._fsm))
+            elif self.adjusted:
                 name, args = "gq_sample_full_adj", args + (self.top_logprobs, p(self.top_ids), p(self.top_lps), p(self.topn_ws), ctypes.byref(self._adj))
             elif self.top_logprobs:
                 name, args = "gq_sample_full_topn", args + (self.top_logprobs, p(self.top_ids), p(self.top_lps), p(self.topn_ws))
@@ -227,15 +277,17 @@ class FusedSampler:
         else:
             name, args = "gq_sample_topk_p", (p(logits), self.vocab_size, int(self.top_k), self.top_p) + draw + (
                 p(self.ban), p(self.seq), self.seq.numel() if self.seq is not None else 0, p(embed_table), p(x_out), dim, p(ssq_out))
-            if self.adjusted:  # (everything the others take: the sets and the log-probability arrays that do not exist go as NULL)
+            if self.adjusted or self.token_fsm is not None:  # (everything the others take: the sets and the log-probability arrays that do not exist go as NULL)
                 name, args = "gq_sample_topk_adj", args + (
                     self.repetition_penalty, p(self.seen), p(self.suppress), p(self.lp_ws), p(self.lp_raw), p(self.lp_drawn),
                     self.lp_raw.numel() if self.lp_raw is not None else 0, self.top_logprobs, p(self.top_ids), p(self.top_lps), p(self.topn_ws),
-                    ctypes.byref(self._adj))
+                    ctypes.byref(self._adj) if self.adjusted else None)
+                if self.token_fsm is not None:
+                    name, args = "gq_sample_topk_fsm", args + (ctypes.byref(self._fsm), )
             elif self.logprobs or self.seen is not None:
                 name, args = "gq_sample_topk_rep", args + (self.repetition_penalty, p(self.seen), p(self.suppress))
-            if self.logprobs and not self.adjusted:
+            if self.logprobs and not self.adjusted and self.token_fsm is None:
                 name, args = "gq_sample_topk_lp", args + (p(self.lp_ws), p(self.lp_raw), p(self.lp_drawn), self.lp_raw.numel())
-            if self.top_logprobs and not self.adjusted:
+            if self.top_logprobs and not self.adjusted and self.token_fsm is None:
                 name, args = "gq_sample_topk_lp_topn", args + (self.top_logprobs, p(self.top_ids), p(self.top_lps), p(self.topn_ws))
         _lib.check(getattr(_lib.lib(), name)(*args, _lib.current_stream_ptr()), name)

@@ -100,7 +100,7 @@ class DecodeGraph:
 
     def __init__(self, model: Transformer, device, native_sampling=False, seed=1234, fold_embed=False, seq_capacity=0, steps_per_replay=1,
                  repetition_penalty=1.0, suppress_tokens=None, logprobs=False, min_p=0.0, top_logprobs=0, frequency_penalty=0.0,
-                 presence_penalty=0.0, logit_bias=None, **sampling_kwargs):
+                 presence_penalty=0.0, logit_bias=None, token_fsm=None, **sampling_kwargs):
         """native_sampling: draw the token with the fused HIP sampler (`self.sampler`, a fused_sampler.FusedSampler, which picks the
         entry point: same distribution as `sample`, own counter-based RNG) and feed token / position back inside the
         graph; `next_prob` is then not produced.  top_k in 1..64 without min_p launches the two-stage kernels it always launched; top_k
@@ -142,7 +142,13 @@ class DecodeGraph:
         repetition penalty, lp_raw and the top-n lists stay raw).  The penalties count the tokens GENERATED IN THIS REQUEST -- the prompt
         does not count -- in `self.sampler.out_count`, on the device, so a multi-step replay feeds the counts back by itself; the counts
         are EMPTY when the constructor returns and `reset_generated()` must be called at the start of every request.  With the defaults
-        the step makes exactly the call it makes without the arguments and allocates nothing."""
+        the step makes exactly the call it makes without the arguments and allocates nothing.
+        token_fsm (a token_fsm.TokenFSM; native sampling only, ValueError("token_fsm: ...") otherwise, never dropped): constrained decoding
+        inside the sampler's launches (gq_sample_topk_fsm / gq_sample_full_fsm): every draw sees the forbidden set of the machine's state in
+        place of the suppress list, and the drawn token moves the state word on the device -- a multi-step replay walks the machine by
+        itself.  The state is the machine's START state when the constructor returns (the warm-up and capture-time draws are undone);
+        `reset_fsm()` must be called at the start of every request.  Without it the step makes exactly the call it makes without the
+        argument and allocates nothing."""
         prime_graph_rng_state(device)
         self.model = model
         self.native_sampling = bool(native_sampling) and model.native_ready()
@@ -152,6 +158,9 @@ class DecodeGraph:
         if not self.native_sampling and (frequency_penalty or presence_penalty or logit_bias):
             raise ValueError("frequency_penalty / presence_penalty / logit_bias are served by the fused sampler only (native_sampling=True on a "
                              "model with the fused decode step): the torch-sampling graph does not apply them")
+        if not self.native_sampling and token_fsm is not None:
+            raise ValueError("token_fsm: served by the fused sampler only (native_sampling=True on a model with the fused decode step): the "
+                             "torch-sampling graph has no state machine")
         self.fold_embed = bool(fold_embed) and self.native_sampling
         self.steps_per_replay = max(1, int(steps_per_replay)) if self.native_sampling else 1
         self.seed = seed
@@ -171,7 +180,7 @@ class DecodeGraph:
         self.sampler = s = FusedSampler(model.config.vocab_size, device, k, sampling_kwargs.get("top_p"), sampling_kwargs.get("temperature", 1.0), seed,
                                         seq_capacity, repetition_penalty, suppress_tokens, logprobs, min_p=min_p if self.native_sampling else 0.0,
                                         top_logprobs=top_logprobs, frequency_penalty=frequency_penalty, presence_penalty=presence_penalty,
-                                        logit_bias=logit_bias)
+                                        logit_bias=logit_bias, token_fsm=token_fsm)
         self.rng_counter, self.work_val, self.work_idx, self.ban, self.seq = s.counter, s.work_val, s.work_idx, s.ban, s.seq
         self.seen, self.suppress, self._lp_ws, self.lp_raw, self.lp_drawn = s.seen, s.suppress, s.lp_ws, s.lp_raw, s.lp_drawn
         self.repetition_penalty, self.logprobs = s.repetition_penalty, s.logprobs
@@ -197,6 +206,11 @@ class DecodeGraph:
         """the start of a request: the counts of the frequency / presence penalty are cleared, outside the graph
         (FusedSampler.reset_generated; nothing happens without such a penalty)"""
         self.sampler.reset_generated()
+
+    def reset_fsm(self, state=None):
+        """the start of a request: the machine of a token_fsm is in `state` (None: its start state), outside the graph
+        (FusedSampler.reset_fsm; nothing happens without a machine)"""
+        self.sampler.reset_fsm(state)
 
     def close(self):
         """destroy the captured graphs now (an owner that drops a DecodeGraph calls this instead of leaving the executable graphs to
@@ -304,6 +318,10 @@ def decode_n_tokens(model: Transformer, cur_token: torch.Tensor, input_pos: torc
             g.reset_generated()
             if int(input_pos.view(-1)[0]) > 0:
                 g.sampler.count_generated(cur_token)
+        if g.sampler.token_fsm is not None:  # (a machine starts over too, and walks a first token the prompt pass drew)
+            g.reset_fsm()
+            if int(input_pos.view(-1)[0]) > 0:
+                g.sampler.advance_fsm(cur_token)
         for _ in range(num_new_tokens):
             g.step()
             new_tokens.append(g.next_tok.clone())

@@ -917,6 +917,47 @@ int gq_sample_full_adj(const void *logits, uint32_t vocab, int top_k, float top_
                        uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n, int *top_ids,
                        float *top_lps, void *topn_ws, const GqSampleAdjust *adj, void *stream);
 
+/* Constrained decoding: a token-level finite state machine inside the sampler's launches (gq_sample_topk_fsm, gq_sample_full_fsm; tables
+ * built by gq_token_fsm_build; guidedquant_amd/token_fsm.py has the host description and its validation).
+ *   tables     S states over a vocabulary of V tokens, CSR, all int32 on the device: row_ptr[S + 1]; edge_tok[E], strictly ascending inside
+ *              a row; edge_next[E], the state behind the token or -1 = the token is forbidden in this state; default_next[S], what a
+ *              token without an edge does: -1 = forbidden, >= 0 = allowed and leads there.
+ *   masks      uint32_t [S][words_per_state], words_per_state = ceil(V / 32): row s is the FORBIDDEN set of state s in the layout of
+ *              `suppress` (bit t % 32 of word t / 32).  gq_token_fsm_build, ONE launch outside any graph: a row is all ones or all zeros by
+ *              the default, then one bit per edge, OR-ed with base_suppress (a token set, or NULL) -- the request's static suppress list --
+ *              and the bits at and past V in the last word are set.  An edge token outside [0, V) is ignored.
+ *   state      one device word.  Every kernel of a draw that reads `suppress` reads masks + state[0] * words_per_state instead (the
+ *              `suppress` argument of the entry is then not read: its set is in the masks); a word outside [0, S) is read as S - 1.
+ *   draw       everything that draws sees the mask exactly as it sees `suppress`: a forbidden token takes no top-k place, lp_drawn is
+ *              under the masked distribution; lp_raw and the top-n rows keep the unprocessed distribution; the ban list, the repetition
+ *              penalty and the additive adjustments compose unchanged.  A draw is, bit for bit, the draw of the entry without the suffix
+ *              with `suppress` = the mask row of the current state.
+ *   transition the publishing lane of the last kernel searches the drawn token in the state's row (binary search): a hit gives edge_next, a
+ *              miss default_next; the result is stored to state[0] (the next call reads it behind a kernel boundary: no launch is added).
+ *              The token of an empty candidate set (INT_MAX), or a result of -1, leaves the state as it is.
+ * gq_sample_topk_fsm / gq_sample_full_fsm: every parameter of gq_sample_topk_adj / gq_sample_full_adj up to adj, then fsm.  fsm == NULL: the
+ * _adj entry serves the call.  Otherwise the _adj entries' own kernel instances run, with adj NULL or neutral as well.
+ * Refusals, GQ_EINVAL, nothing launched or written: masks, row_ptr, edge_next, default_next or state NULL (edge_tok may be NULL when no
+ * state has an edge), n_states == 0, words_per_state != ceil(vocab / 32); then those of the _adj entry. */
+typedef struct {
+    const uint32_t *masks; /* [n_states][words_per_state], built by gq_token_fsm_build */
+    uint32_t words_per_state, n_states;
+    const int32_t *row_ptr, *edge_tok, *edge_next, *default_next;
+    int32_t *state; /* one device word: the current state */
+} GqTokenFsm;
+int gq_token_fsm_build(const int *row_ptr, const int *edge_tok, const int *edge_next, const int *default_next, uint32_t n_states, uint32_t vocab,
+                       const uint32_t *base_suppress, uint32_t *masks, void *stream);
+int gq_sample_topk_fsm(const void *logits, uint32_t vocab, int top_k, float top_p, float temperature, uint32_t seed, int *counter,
+                       float *work_val, int *work_idx, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                       uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                       uint32_t *seen, const uint32_t *suppress, float *lp_ws, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n,
+                       int *top_ids, float *top_lps, void *topn_ws, const GqSampleAdjust *adj, const GqTokenFsm *fsm, void *stream);
+int gq_sample_full_fsm(const void *logits, uint32_t vocab, int top_k, float top_p, float min_p, float temperature, uint32_t seed,
+                       int *counter, void *ws, size_t ws_bytes, int *tok_io, int *pos_io, int *next_tok, const int *ban, int *seq_out,
+                       uint32_t seq_cap, const void *embed_table, void *x_out, uint32_t dim, float *ssq_out, float repetition_penalty,
+                       uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n, int *top_ids,
+                       float *top_lps, void *topn_ws, const GqSampleAdjust *adj, const GqTokenFsm *fsm, void *stream);
+
 /* Test / tuning hooks (not part of the reference's surface).  gq_reset_env_cache: drop the cached GQ_* environment
  * knobs so that a test can flip them between calls.  gq_debug_set_timing_buffer: device buffer the plane kernels write
  * s_memtime phase stamps into (tools/phase_timing.py); NULL (default) disables it. */
