@@ -33,6 +33,7 @@ EXPORTS = [
     "gq_sample_full_ws_bytes", "gq_sample_full", "gq_sample_topk_lp_topn", "gq_sample_full_topn", "gq_dense_gemv_i8",
     "gq_token_bias_build", "gq_sample_topk_adj", "gq_sample_full_adj",
     "gq_token_fsm_build", "gq_sample_topk_fsm", "gq_sample_full_fsm",
+    "gq_attn_decode_split_kv8",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -185,6 +186,7 @@ def lib():
         # (the fp8 cache forms: scales / reciprocal scales fp32 [n_kv_head] behind the caches)
         L.gq_rope_cache_rows_kv8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, f32, vp, vp]
         L.gq_attn_decode_roped_kv8.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, u32, vp]
+        L.gq_attn_decode_split_kv8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, vp, vp, f32, vp, u32, vp]
         L.gq_attn_prefill_kv8.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, f32, u32, vp]
         # (the packed pass: seg_begin behind the caches and no start; pos, row in front of the tables)
         L.gq_attn_prefill_packed.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, f32, u32, vp]

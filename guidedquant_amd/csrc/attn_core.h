@@ -86,6 +86,31 @@ __device__ __forceinline__ void unpack8_fp8(const uint2 &row, float (&f)[8]) {
         f[4 * e] = lo[0], f[4 * e + 1] = lo[1], f[4 * e + 2] = hi[0], f[4 * e + 3] = hi[1];
     }
 }
+// 8 fp16 values (4 words) -> 8 OCP e4m3 codes by THE write rule of the fp8 cache, the only rounding the format adds:
+//   code = fp8_rne(clamp(float(x16) * inv, -448, 448))
+// inv = 1 / scale of the KV head, an fp32 the host computed (no division here).  The clamp is explicit (v_med3_f32): v_cvt_pk_fp8_f32
+// turns a magnitude beyond 448 into NaN, not into 448; +-Inf clamps to +-448.  The host model:
+// (x16.float() * inv).clamp(-448, 448).to(torch.float8_e4m3fn).  A NaN must be stored as a NaN code, and the clamp loses it (v_med3_f32
+// with a NaN operand returns the smaller of the other two, -448): NAN_PASS puts the NaNs among the products v back behind the clamp.
+// Users: the row write (prefill.hip) and the fp8 decode attention that writes its own row (attn_kv8.hip).
+template <bool NAN_PASS>
+__device__ __forceinline__ uint2 fp8_quant8(const float (&v)[8]) {
+    float f[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        f[k] = __builtin_amdgcn_fmed3f(v[k], -448.f, 448.f);
+        if constexpr (NAN_PASS) f[k] = v[k] != v[k] ? v[k] : f[k];
+    }
+    u32 o[2];
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+        int r = 0;
+        r = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * e], f[4 * e + 1], r, false);
+        r = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * e + 2], f[4 * e + 3], r, true);
+        o[e] = (u32)r;
+    }
+    return make_uint2(o[0], o[1]);
+}
 // the cache format of a launch: element type, the load of a lane's 8 dims of a row (16 bytes of fp16, 8 bytes of fp8), its unpack
 template <bool KV8>
 struct CacheFmt {

@@ -875,6 +875,29 @@ extern "C" int gq_attn_decode_roped_kv8(const void *q, const int *pos, const voi
                                      k_scale, v_scale);
 }
 
+// what attn_kv8.hip (gq_attn_decode_split_kv8: the fp8-cache form of the gq_attn_decode_split family, a translation unit of its own)
+// takes from this one: the family's argument checks and its combine launch
+int gq_attn_check_args(bool any_null, const char *misaligned, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t n_split,
+                       const float *workspace) {
+    return attn_check_args(any_null, misaligned, false, 0u, n_head, n_kv_head, head_dim, n_split, workspace);
+}
+void gq_attn_combine_launch(const float *workspace, void *out, uint32_t n_head, uint32_t head_dim, uint32_t n_split, const int *pos,
+                            uint32_t max_seq, uint32_t window, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+#define GQ_LAUNCH_COMBINE(HD_)                                                                                                         \
+    do {                                                                                                                               \
+        if (window)                                                                                                                    \
+            hipLaunchKernelGGL((attn_combine_kernel<HD_, true>), dim3(n_head), dim3(HD_), 0, s, workspace, (uint16_t *)out, n_split, pos, \
+                               max_seq, AttnWindow<true>{window});                                                                     \
+        else                                                                                                                           \
+            hipLaunchKernelGGL((attn_combine_kernel<HD_, false>), dim3(n_head), dim3(HD_), 0, s, workspace, (uint16_t *)out, n_split, pos, \
+                               max_seq, AttnWindow<false>{});                                                                          \
+    } while (0)
+    if (head_dim == 128) GQ_LAUNCH_COMBINE(128);
+    else GQ_LAUNCH_COMBINE(64);
+#undef GQ_LAUNCH_COMBINE
+}
+
 extern "C" int gq_attn_decode(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache,
                               void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
                               float scale, void *stream) {

@@ -52,6 +52,14 @@ int gq_topn_check(uint32_t vocab, int n, const void *top_ids, const void *top_lp
 int gq_topn_launch(const void *logits, uint32_t vocab, int n, const float *lse_part, const int *pos_io, int *top_ids, float *top_lps, uint32_t cap,
                    void *ws, void *stream);
 
+// Host pieces of the gq_attn_decode_split family (decode.hip) its fp8-cache form (attn_kv8.hip) shares: the argument checks every
+// attention launch makes, in their order (any_null / misaligned: the entry's own findings), and the split-KV combine launch behind a
+// launch with n_split > 1 (window 0: no window).
+int gq_attn_check_args(bool any_null, const char *misaligned, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t n_split,
+                       const float *workspace);
+void gq_attn_combine_launch(const float *workspace, void *out, uint32_t n_head, uint32_t head_dim, uint32_t n_split, const int *pos,
+                            uint32_t max_seq, uint32_t window, void *stream);
+
 // Host pieces the two QTIP translation units share (qtip.hip: the trellis side, qtip_xf.hip: the transform side, which defines them).
 extern unsigned long long *g_qdbg;  // optional per-wave phase stamps (gq_debug_set_qtip_timing_buffer; tools/qtip_phase_timing.py)
 float gq_inv_sqrt_f(uint32_t n);    // (float)n^-1/2, rounded from double like the scale argument of hadamard()

@@ -12,10 +12,12 @@
 #include <hip/hip_runtime.h>
 
 #include "gq_internal.h"
+#include "attn_core.h"
 #include "wave_util.h"
 
 namespace {
 using u32 = uint32_t;
+using gq_attn::fp8_quant8;  // THE write rule of the fp8 cache (attn_core.h)
 using gqw::f2h;
 using gqw::h16;
 using gqw::h2f;
@@ -109,31 +111,6 @@ __device__ __forceinline__ void rope_unit(const uint4 a, const uint4 b, const ui
         }
         o1[e] = r1, o2[e] = r2;
     }
-}
-
-// 8 fp16 values (4 words) -> 8 OCP e4m3 codes by THE write rule of the fp8 cache, the only rounding the format adds:
-//   code = fp8_rne(clamp(float(x16) * inv, -448, 448))
-// inv = 1 / scale of the KV head, an fp32 the host computed (no division here).  The clamp is explicit (v_med3_f32): v_cvt_pk_fp8_f32
-// turns a magnitude beyond 448 into NaN, not into 448; +-Inf clamps to +-448.  The host model:
-// (x16.float() * inv).clamp(-448, 448).to(torch.float8_e4m3fn).  A NaN must be stored as a NaN code, and the clamp loses it (v_med3_f32
-// with a NaN operand returns the smaller of the other two, -448): NAN_PASS puts the NaNs among the products v back behind the clamp.
-template <bool NAN_PASS>
-__device__ __forceinline__ uint2 fp8_quant8(const float (&v)[8]) {
-    float f[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        f[k] = __builtin_amdgcn_fmed3f(v[k], -448.f, 448.f);
-        if constexpr (NAN_PASS) f[k] = v[k] != v[k] ? v[k] : f[k];
-    }
-    u32 o[2];
-#pragma unroll
-    for (int e = 0; e < 2; e++) {
-        int r = 0;
-        r = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * e], f[4 * e + 1], r, false);
-        r = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * e + 2], f[4 * e + 3], r, true);
-        o[e] = (u32)r;
-    }
-    return make_uint2(o[0], o[1]);
 }
 
 // a thread's two units (elements d .. d + 7 and d + HD / 2 .. of a head's row `dst`): as they are into an fp16 row (q_out, an fp16

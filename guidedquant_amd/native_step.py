@@ -65,6 +65,11 @@ qtip_attn_fold = _knob("GQ_QTIP_ATTN_FOLD", "1")
 # longer repeat RMSNorm . SU . Hadamard.  Needs power-of-two widths on that edge and the plain launch forms (no folding, no one-launch
 # form).
 qtip_pre = _knob("GQ_QTIP_PRE", "0")
+# (default OFF): the fp8 cache's two launches behind the wqkv GEMV -- gq_rope_cache_rows_kv8 (S = 1), gq_attn_decode_roped_kv8 -- as ONE,
+# gq_attn_decode_split_kv8: bit-identical logits and cache bytes, one launch per layer less.  Measured on the 8B geometry, 32768-row cache
+# (profiles/kv8_fold.json): 860 vs 812 tokens/s at 50 cached positions, 663-672 vs 649-653 at 4095, but 494-499 vs 558-560 at 16000 and
+# 397-399 vs 463-465 at 32000 (one query head per block against the two-launch route's four heads of a KV group): opt-in
+kv8_fold = _knob("GQ_KV8_FOLD", "0")
 
 
 def attn_split_knob(planned):
@@ -139,9 +144,10 @@ class StepState(_Keyed):
         self.layer_split = [self.attn_split if w is None else plan(w) for w in self.layer_window]
         ns_max = max([self.attn_split] + self.layer_split)  # (one workspace, sized for the largest)
         self.attn_ws = torch.zeros(c.n_head * ns_max * (c.head_dim + 2), dtype=torch.float32, device=dev) if ns_max > 1 else None
-        # an fp8 KV cache (Transformer.setup_caches(.., kv_cache_dtype="fp8")): the rotated q of attend_kv8
+        # an fp8 KV cache (Transformer.setup_caches(.., kv_cache_dtype="fp8")): the rotated q of attend_kv8's two-launch route (a state
+        # built under GQ_KV8_FOLD=1 does without; a step that finds the knob off again allocates it then)
         self.kv8 = getattr(model, "kv_cache_dtype", "fp16") == "fp8"
-        self.q8 = torch.zeros(c.n_head * c.head_dim, **f16) if self.kv8 else None
+        self.q8 = torch.zeros(c.n_head * c.head_dim, **f16) if self.kv8 and not kv8_fold() else None
 
     def kv(self, at, slot):
         """the K / V cache of batch slot `slot` of one attention module"""
@@ -166,8 +172,18 @@ class StepState(_Keyed):
     def attend_kv8(self, at, pos, kv, sp, layer):
         """the fp8 cache's route of one layer, behind the plain wqkv GEMV: gq_rope_cache_rows_kv8 (S = 1, the graph's position word; the
         layer's norm weights or bias) rotates q into its own buffer and writes the cache row, gq_attn_decode_roped_kv8 attends it with the
-        layer's window and split plan.  One route for Llama, Mistral, Qwen2 and Qwen3; one launch per layer more than the fp16 routes."""
+        layer's window and split plan.  One route for Llama, Mistral, Qwen2 and Qwen3; one launch per layer more than the fp16 routes.
+        GQ_KV8_FOLD=1: the two as ONE launch on the packed vector, gq_attn_decode_split_kv8 -- the same cache bytes and the same output."""
         m, c, L, kvc = self.m, self.m.config, _lib.lib(), at.kv_cache
+        if kv8_fold():
+            _lib.check(L.gq_attn_decode_split_kv8(self.qkv.data_ptr(), pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), *kv,
+                                                  kvc.k_inv.data_ptr(), kvc.v_inv.data_ptr(), kvc.k_scale.data_ptr(), kvc.v_scale.data_ptr(), self.y.data_ptr(),
+                                                  c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, 1.0 / math.sqrt(c.head_dim),
+                                                  self.layer_split[layer], _ptr(self.attn_ws), *qk_norm_args(at, c), _ptr(at.wqkv.bias),
+                                                  self.layer_window[layer] or 0, sp), "gq_attn_decode_split_kv8")
+            return
+        if self.q8 is None:
+            self.q8 = torch.zeros(c.n_head * c.head_dim, dtype=torch.float16, device=self.x.device)
         _lib.check(L.gq_rope_cache_rows_kv8(self.qkv.data_ptr(), pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), self.q8.data_ptr(), *kv,
                                             kvc.k_inv.data_ptr(), kvc.v_inv.data_ptr(), 1, c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, *qk_norm_args(at, c),
                                             _ptr(at.wqkv.bias), sp), "gq_rope_cache_rows_kv8")

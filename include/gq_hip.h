@@ -239,6 +239,20 @@ int gq_rope_cache_rows_packed(const void *qkv, const int *pos, const int *row, c
  *   every attended row, the current token's included (its dequantised value is what is attended: a result is a function of the cache
  *   alone).  The same geometry, solo rule, split length, stream assignment and merge order (csrc/attn_core.h); one 8-byte load per lane
  *   and row.  Partials reach the workspace multiplied by v_scale; the combine launch is the fp16 one.  *pos >= max_seq: NaN output.
+ * gq_attn_decode_split_kv8: the gq_attn_decode_split family over fp8 caches, one entry for its forms -- q_norm_weight / k_norm_weight (both
+ *   or neither; eps): gq_attn_decode_split_qknorm; qkv_bias: gq_attn_decode_split_bias; both: GQ_EINVAL; window >= 1: the _window form of
+ *   the chosen one, 0: no window.  ONE launch (+ the combine launch when n_split > 1) takes the packed q | k | v vector behind the plain
+ *   wqkv GEMV.  Rounding points: the optional fp16 bias add on q, k and v, or the per-head RMSNorm of q and k (fp32 sum of squares in the
+ *   order of gq_rope_cache_rows_kv8, x * rsqrt(ssq / head_dim + eps) rounded to fp16, fp16 product with the weight), then the rotation in
+ *   three fp16 operations: the fp16 values the fp16 path would attend and store.  k and v of the current token are then quantised by the
+ *   write rule (k_inv / v_inv) and the block attends their DEQUANTISED codes: a result is a function of the cache alone.  The row *pos
+ *   of both caches is written by the first query head of each KV group in the split that covers *pos, 8 codes per 8-byte store; no other
+ *   byte of either cache is touched.  Cached rows: the read rule as in gq_attn_decode_roped_kv8 (k_scale in the score factor, v_scale
+ *   on the merged sum; partials reach the workspace multiplied by v_scale), geometry, solo rule, stream assignment and merge order of
+ *   csrc/attn_core.h.  *pos >= max_seq: nothing is written to the caches, NaN output.  head_dim 64 or 128 (GQ_ENOTSUP else, nothing
+ *   written); n_split in 1..64, workspace as for gq_attn_decode_split; qkv, the tables, the caches, the weights and the bias 16-byte aligned.
+ *   CONTRACT: for any input the entry leaves, bit for bit, the cache bytes and the out vector that gq_rope_cache_rows_kv8 (S = 1) followed
+ *   by gq_attn_decode_roped_kv8 leave for the same n_split and window.
  * gq_attn_prefill_kv8: gq_attn_prefill over fp8 caches; tiles are converted to fp16 between the global load and LDS, so the LDS image
  *   and both matrix products are those of gq_attn_prefill.  Governed by gq_attn_prefill_supported like it.
  */
@@ -249,6 +263,11 @@ int gq_rope_cache_rows_kv8(const void *qkv, const int *pos, const void *cos_tabl
 int gq_attn_decode_roped_kv8(const void *q, const int *pos, const void *k_cache, const void *v_cache, const float *k_scale,
                              const float *v_scale, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
                              float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream);
+int gq_attn_decode_split_kv8(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *k_cache, void *v_cache,
+                             const float *k_inv, const float *v_inv, const float *k_scale, const float *v_scale, void *out, uint32_t n_head,
+                             uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split, float *workspace,
+                             const void *q_norm_weight, const void *k_norm_weight, float eps, const void *qkv_bias, uint32_t window,
+                             void *stream);
 int gq_attn_prefill_kv8(const void *q, const void *k_cache, const void *v_cache, const float *k_scale, const float *v_scale, void *out,
                         uint32_t S, uint32_t start, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale,
                         uint32_t window, void *stream);

@@ -1,13 +1,17 @@
 """What an fp8 (e4m3) KV cache costs and saves on the fused decode route: the Llama-3.1-8B geometry, random init, 2 bits, a cache of 32768
-rows -- `kv_cache_dtype="fp8"` against the default fp16 cache, the two alternating in one process (`--rounds` rounds of fp16, fp8):
+rows -- `kv_cache_dtype="fp8"` against the default fp16 cache, and the fp8 route with its two attention launches folded into one
+(GQ_KV8_FOLD=1, gq_attn_decode_split_kv8), the three alternating in one process (`--rounds` rounds of fp16, fp8, fp8-fold):
 
   tok_s          in-graph decode (captured DecodeGraph, ten token steps per replay, fused sampler) from 50 (the short-context step: the price
                  of the fp8 route's extra launch per layer) / 4095 / 16000 / 32000 cached positions: `--steps` token steps, `--repeats` windows;
   attn_us        layer 0's attention launch (+ its combine launch) alone at the position, `--launches` launches between two events;
-                 fp8 also `row_write_us`: the gq_rope_cache_rows_kv8 launch (S = 1) the fp16 route has no counterpart of;
-  prefill_ms     the prompt pass of 8192 tokens (chunks of 4096, the HIP prompt attention of the cache's dtype).
-No threshold is asserted and no speed is promised: the record says what came out, losses included.  Writes profiles/kv8_decode.json.
-    python tools/kv8_decode_timing.py [--rounds 2] [--steps 20] [--warmup 10] [--repeats 3] [--launches 200]
+                 fp8 also `row_write_us`: the gq_rope_cache_rows_kv8 launch (S = 1) the fp16 route has no counterpart of; fp8-fold: the
+                 one gq_attn_decode_split_kv8 launch (+ combine), which writes the row itself;
+  prefill_ms     the prompt pass of 8192 tokens (chunks of 4096, the HIP prompt attention of the cache's dtype; not repeated for
+                 fp8-fold, whose prompt pass is fp8's).
+No threshold is asserted and no speed is promised: the record says what came out, losses included.  Writes profiles/kv8_fold.json
+(profiles/kv8_decode.json: the record of the two legs, from before the third existed).
+    python tools/kv8_decode_timing.py [--rounds 2] [--steps 20] [--warmup 10] [--repeats 3] [--launches 200] [--out FILE]
 """
 import argparse
 import json
@@ -18,7 +22,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-OUT = os.path.join(ROOT, "profiles", "kv8_decode.json")
+OUT = os.path.join(ROOT, "profiles", "kv8_fold.json")
 MAX_SEQ, POSITIONS, PROMPT = 32768, (50, 4095, 16000, 32000), 8192
 
 
@@ -49,6 +53,8 @@ def attn_us(model, pos, launches, repeats):
         entry = "gq_attn_decode_roped" if roped else "gq_attn_decode_split"
         return _timed(lambda: st.attend(entry, st.qkv.data_ptr(), posd, kv, sp, layer=0), launches, repeats), None
     kvc, ws = at.kv_cache, st.attn_ws.data_ptr() if st.attn_ws is not None else None
+    if os.environ.get("GQ_KV8_FOLD", "0") != "0":  # (the route's own call: one launch that rotates, writes the row and attends)
+        return _timed(lambda: st.attend_kv8(at, posd, kv, sp, 0), launches, repeats), None
 
     def attend():
         _lib.check(L.gq_attn_decode_roped_kv8(st.q8.data_ptr(), posd.data_ptr(), *kv, kvc.k_scale.data_ptr(), kvc.v_scale.data_ptr(), st.y.data_ptr(), c.n_head,
@@ -106,6 +112,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--launches", type=int, default=200)
+    ap.add_argument("--out", default=OUT)
     args = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "needs a GPU (the HIP path has no fallback)"
@@ -118,14 +125,16 @@ def main():
     cfg = ModelArgs(**dict(transformer_configs["meta-llama/Meta-Llama-3.1-8B"], block_size=MAX_SEQ))
     model = Transformer(torch.float16, cfg, linear_class=APLinear, linear_kwargs=dict(bitwidth=2, device=dev))
     model = random_init_(model.to(device=dev, dtype=torch.float16)).eval()
-    rec = dict(protocol="random init, 2-bit, Llama-3.1-8B geometry, cache of %d rows, scales 1.0; fp16 and fp8 caches alternating, %d rounds; tok_s: "
+    rec = dict(protocol="random init, 2-bit, Llama-3.1-8B geometry, cache of %d rows, scales 1.0; fp16, fp8 and fp8 with GQ_KV8_FOLD=1 alternating, %d rounds; tok_s: "
                "DecodeGraph with 10 steps per replay, %d warm-up steps, %d-step window, %d windows; attn_us / row_write_us: layer 0's launches, %d "
                "launches between two events, %d runs; prefill_ms: %d tokens, two timed runs behind a warm-up"
                % (MAX_SEQ, args.rounds, args.warmup, args.steps, args.repeats, args.launches, args.repeats, PROMPT),
                positions=list(POSITIONS), rounds=[])
     g = torch.Generator(device=dev)
     for r in range(args.rounds):
-        for kv in ("fp16", "fp8"):
+        for leg_name in ("fp16", "fp8", "fp8-fold"):
+            kv = leg_name.split("-")[0]
+            os.environ["GQ_KV8_FOLD"] = "1" if leg_name == "fp8-fold" else "0"  # (read by every step issued or captured)
             model.setup_caches(1, MAX_SEQ, kv_cache_dtype=kv)
             assert model.native_ready() and model.kv_cache_dtype == kv
             g.manual_seed(1)
@@ -133,16 +142,17 @@ def main():
                 for t in (b.attention.kv_cache.k_cache, b.attention.kv_cache.v_cache):
                     t.copy_((torch.rand(t.shape[1:], device=dev, generator=g) - 0.5).half().to(t.dtype)[None])
             st = model._native_state()
-            leg = dict(round=r, kv_cache_dtype=kv, n_split=st.layer_split[0],
+            leg = dict(round=r, leg=leg_name, kv_cache_dtype=kv, n_split=st.layer_split[0],
                        cache_bytes=sum(t.numel() * t.element_size() for b in model.layers for t in (b.attention.kv_cache.k_cache, b.attention.kv_cache.v_cache)))
             for pos in POSITIONS:
                 a, w = attn_us(model, pos, args.launches, args.repeats)
                 leg["pos_%d" % pos] = dict(attn_us=a, **(dict(row_write_us=w) if w is not None else {}),
                                            tok_s=tok_s(model, dev, pos, args.steps, args.warmup, args.repeats))
-            leg["prefill_ms"], leg["prefill_attn"] = prefill_ms(model, dev)
+            if leg_name != "fp8-fold":
+                leg["prefill_ms"], leg["prefill_attn"] = prefill_ms(model, dev)
             rec["rounds"].append(leg)
             print(json.dumps(leg), flush=True)
-            with open(OUT, "w") as f:  # (written leg by leg: a run cut short leaves what it measured)
+            with open(args.out, "w") as f:  # (written leg by leg: a run cut short leaves what it measured)
                 json.dump(rec, f, indent=1)
                 f.write("\n")
     print(json.dumps(rec))
