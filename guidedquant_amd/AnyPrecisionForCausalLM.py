@@ -165,6 +165,7 @@ class AnyPrecisionForCausalLM(nn.Module):
         self._load_quantized_modules()
         self._native_cache = {}
         self._released = None
+        self._adapter = None  # load_adapter / set_adapter: the LoRA adapter every fused decode model of this wrapper serves
         self.register_state_dict_pre_hook(lambda module, prefix, keep_vars: module._restore_module_tree())
         # (also when the HF model inside is asked directly: self.model.state_dict() / save_pretrained.  Through a weak reference -- the
         # wrapper owns captured graphs and must stay collectable by reference counting alone, see _graphs.py)
@@ -479,7 +480,10 @@ class AnyPrecisionForCausalLM(nn.Module):
         # frequency_penalty / presence_penalty / logit_bias: additive adjustments inside the fused sampler.  Route 1 only, never a fall-back.
         adj = {k: kwargs.pop(k, None) for k in ("frequency_penalty", "presence_penalty", "logit_bias")}  # (popped as well; validated inside the try)
         fsm = kwargs.pop("token_fsm", None)  # (popped as well; validated inside the try)
+        lora = self._adapter is not None  # (load_adapter: route 1 only, every refusal below under "lora: ", never a fall-back)
         try:
+            if lora and (native is False or capture is True):
+                raise ValueError("lora: the adapter is served by the fused decode model only (not with native=False or capture=True)")
             from .fused_sampler import check_additive_penalty, check_logit_bias
             adj = dict(frequency_penalty=check_additive_penalty("frequency_penalty", adj["frequency_penalty"]),
                        presence_penalty=check_additive_penalty("presence_penalty", adj["presence_penalty"]),
@@ -514,6 +518,8 @@ class AnyPrecisionForCausalLM(nn.Module):
                 if (native is not False or capture is True) else (None, "opted out")
             if req is not None and self.device.type != "cuda":
                 req, why = None, "the fused routes need the GPU"
+            if lora and req is None:
+                raise ValueError("lora: " + why)
             if kv == "fp8" and req is None:
                 raise ValueError("kv_cache_dtype='fp8': " + why)
             if hd == "int8" and req is None:
@@ -532,6 +538,9 @@ class AnyPrecisionForCausalLM(nn.Module):
                 # see every tensor)
                 dec = self._native_decoder_or_none(self.precision, release_planes=native is True)
                 if dec is not None and req["T"] + req["max_new"] > dec.config.block_size:
+                    if lora:
+                        raise ValueError(f"lora: prompt + max_new_tokens = {req['T'] + req['max_new']} exceeds the fused model's "
+                                         f"context ({dec.config.block_size})")
                     if hd == "int8":
                         raise ValueError(f"lm_head_dtype='int8': prompt + max_new_tokens = {req['T'] + req['max_new']} exceeds the fused "
                                          f"model's context ({dec.config.block_size})")
@@ -550,6 +559,8 @@ class AnyPrecisionForCausalLM(nn.Module):
                     # (the captured step ends in the fused sampler: 128 blocks x 2048 logits at the most.  Qwen3's published vocabulary,
                     # 151936, is within it; a checkpoint beyond 262144 keeps `native_decoder()` / `decode_native` / `prefill_native`,
                     # not this route)
+                    if lora:
+                        raise ValueError(f"lora: vocabulary {dec.config.vocab_size} exceeds the fused sampler's {SAMPLER_MAX_VOCAB}")
                     if hd == "int8":
                         raise ValueError(f"lm_head_dtype='int8': vocabulary {dec.config.vocab_size} exceeds the fused sampler's {SAMPLER_MAX_VOCAB}")
                     if lp:
@@ -561,6 +572,9 @@ class AnyPrecisionForCausalLM(nn.Module):
                     dec = None
                 if dec is not None and kv == "fp8" and dec.kv8_unserved():
                     raise ValueError("kv_cache_dtype='fp8': " + dec.kv8_unserved())
+                if lora and (dec is None or kv == "fp8"):
+                    why_not = getattr(self, "_no_native_reason", None) or ("the fp8 KV cache is not served under an adapter" if dec is not None else None)
+                    raise ValueError("lora: this checkpoint has no fused decode form at %d bits%s" % (self.precision, ": " + why_not if why_not else ""))
                 if dec is not None:
                     return self._generate_native(dec, req, kv_cache_dtype=kv, logprobs=lp, top_logprobs=top_n, lm_head_dtype=hd, adjust=adj)
                 if hd == "int8":
@@ -623,6 +637,8 @@ class AnyPrecisionForCausalLM(nn.Module):
             raise ValueError(f"score: token ids must lie in [0, {vocab})")
         if kv == "fp8" and native is False:
             raise ValueError("kv_cache_dtype='fp8': served by the fused decode model only (not with native=False)")
+        if self._adapter is not None and (native is False or kv == "fp8"):
+            raise ValueError("lora: the adapter is served by the fused decode model with an fp16 cache only")
         prev_precision = self.precision
         if precision is not None:
             self.set_precision(precision)
@@ -642,6 +658,8 @@ class AnyPrecisionForCausalLM(nn.Module):
                         dec, why = None, "the fused model's prompt pass does not serve this model"
             if dec is None and kv == "fp8":
                 raise ValueError("kv_cache_dtype='fp8': " + why)
+            if dec is None and self._adapter is not None:
+                raise ValueError("lora: " + why)
             if dec is None and native is True:
                 raise ValueError("native=True: " + why)
             if dec is not None:
@@ -996,7 +1014,36 @@ class AnyPrecisionForCausalLM(nn.Module):
         raise NotImplementedError("layer fusion inside the HF module tree is not implemented (as in the reference); use "
                                   "native_decoder(bitwidth) for the fused QKV / Up-Gate decode path")
 
-    def native_decoder(self, bitwidth: Optional[int] = None, release_planes: bool = False, kv_cache_dtype=None, lm_head_dtype=None):
+    def load_adapter(self, path_or_state_dict, config=None):
+        """A peft LoRA adapter beside the quantized base (lora.py): a directory (adapter_config.json + adapter_model.bin, or .safetensors
+        where that package is importable) or a state dict with `config` (the fields of adapter_config.json).  q / k / v / o / down targets;
+        ValueError("lora: ...") for what is not served.  From here on every fused decode model of this wrapper serves the adapter, and
+        `generate` / `score` raise ValueError("lora: ...") instead of taking a route that would ignore it (native=False, capture=True,
+        a request or checkpoint route 1 declines).  `set_adapter(None)` takes it off again.  Returns the LoraAdapter."""
+        from .lora import LoraAdapter
+        if isinstance(path_or_state_dict, (str, os.PathLike)):
+            if config is not None:
+                raise ValueError("lora: a directory brings its own adapter_config.json")
+            ad = LoraAdapter.from_dir(os.fspath(path_or_state_dict))
+        else:
+            if config is None:
+                raise ValueError("lora: a state dict needs the adapter's config (the fields of adapter_config.json)")
+            ad = LoraAdapter.from_peft(path_or_state_dict, config)
+        self.set_adapter(ad)
+        return ad
+
+    def set_adapter(self, adapter):
+        """the LoRA adapter of the fused decode models (a lora.LoraAdapter or None); graphs captured under the old one are dropped"""
+        self._evict("graph")
+        for key, dec in self._native_cache.items():
+            if key[0] == "decoder":
+                dec.set_adapter(adapter)
+        self._adapter = adapter
+
+    _KEEP_ADAPTER = object()
+
+    def native_decoder(self, bitwidth: Optional[int] = None, release_planes: bool = False, kv_cache_dtype=None, lm_head_dtype=None,
+                       adapter=_KEEP_ADAPTER):
         """the same checkpoint as the fused gpt-fast `Transformer` (fused QKV / Up-Gate Any-Precision linears at one precision)
         whose bs=1 decode step runs as the captured 5-launches-per-layer HIP graph.  Built from the module tree's tensors BY
         REFERENCE: embedding, lm_head, norms, o_proj and down_proj are the same storage; q/k/v and gate/up are concatenated into the
@@ -1007,7 +1054,9 @@ class AnyPrecisionForCausalLM(nn.Module):
         `state_dict()` of the wrapper or of `self.model`, or `.to()` -- `_restore_module_tree`).  The default keeps the module tree whole
         (the fused q/k/v/gate/up tensors are then a second copy: 1.1 GB for an 8B 2-bit model).
         lm_head_dtype ("fp16" / "int8"; None: the decoder's head as it is): the decoder comes back with that head
-        (Transformer.set_lm_head_dtype: the int8 copy costs N*K + 4N bytes next to the shared fp16 head)."""
+        (Transformer.set_lm_head_dtype: the int8 copy costs N*K + 4N bytes next to the shared fp16 head).
+        adapter (a lora.LoraAdapter or None; not given: the wrapper's own, `load_adapter`): the decoder comes back serving it
+        (Transformer.set_adapter; ValueError("lora: ...") where its shapes do not match)."""
         from .head_q8 import lm_head_dtype_name
         from .model import kv_cache_dtype_name
         hd = None if lm_head_dtype is None else lm_head_dtype_name(lm_head_dtype)
@@ -1028,6 +1077,10 @@ class AnyPrecisionForCausalLM(nn.Module):
             dec.setup_caches(max(1, dec.max_batch_size), max(8, dec.max_seq_length), kv_cache_dtype=kv)
         if hd is not None and hd != dec.lm_head_dtype:
             dec.set_lm_head_dtype(hd)
+        want = self._adapter if adapter is self._KEEP_ADAPTER else adapter
+        if dec.adapter is not want:
+            self._evict("graph")
+            dec.set_adapter(want)
         return dec
 
     def _layer_linears(self, layer):

@@ -34,6 +34,7 @@ EXPORTS = [
     "gq_token_bias_build", "gq_sample_topk_adj", "gq_sample_full_adj",
     "gq_token_fsm_build", "gq_sample_topk_fsm", "gq_sample_full_fsm",
     "gq_attn_decode_split_kv8",
+    "gq_lora_n_partials", "gq_lora_down", "gq_lora_up",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -61,6 +62,11 @@ class GqSampleAdjust(ctypes.Structure):  # include/gq_hip.h: the additive adjust
 class GqTokenFsm(ctypes.Structure):  # include/gq_hip.h: the token-level state machine of gq_sample_topk_fsm / gq_sample_full_fsm
     _fields_ = [("masks", ctypes.c_void_p), ("words_per_state", ctypes.c_uint32), ("n_states", ctypes.c_uint32), ("row_ptr", ctypes.c_void_p),
                 ("edge_tok", ctypes.c_void_p), ("edge_next", ctypes.c_void_p), ("default_next", ctypes.c_void_p), ("state", ctypes.c_void_p)]
+
+
+class GqLoraSeg(ctypes.Structure):  # include/gq_hip.h: one segment of gq_lora_up (rows, its slice of t, its rows of B, lora_alpha / r)
+    _fields_ = [("row_begin", ctypes.c_uint32), ("row_end", ctypes.c_uint32), ("t_begin", ctypes.c_uint32), ("rank", ctypes.c_uint32),
+                ("b_offset", ctypes.c_uint32), ("scale", ctypes.c_float)]
 
 
 class GqQtipXf(ctypes.Structure):
@@ -143,6 +149,10 @@ def lib():
         L.gq_attn_decode_qtip.argtypes = [ctypes.POINTER(GqQtipOut), vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, vp]
         L.gq_dense_gemv_f16.argtypes = [vp, vp, vp, u32, u32, vp, f32, vp]
         L.gq_dense_gemv_i8.argtypes = [vp, vp, vp, vp, u32, u32, vp, f32, vp]  # (x, Wq, scale, out, N, K, norm_weight, eps, stream)
+        L.gq_lora_n_partials.argtypes = [u32]
+        L.gq_lora_down.argtypes = [vp, vp, f32, vp, u32, u32, vp, vp]  # (x, norm_weight, eps, A, R, K, partials, stream)
+        # (partials, n_partials, R, B, segments, n_segments, base, out, N, stream)
+        L.gq_lora_up.argtypes = [vp, u32, u32, vp, ctypes.POINTER(GqLoraSeg), u32, vp, vp, u32, vp]
         L.gq_sample_topk.argtypes = [vp, u32, i32, f32, u32, vp, vp, vp, vp, vp, vp, vp]
         L.gq_sample_topk_ex.argtypes = [vp, u32, i32, f32, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp]
         L.gq_sample_topk_p.argtypes = [vp, u32, i32, f32, f32, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp]

@@ -51,6 +51,8 @@ def prefill(model: Transformer, x: torch.Tensor, input_pos: torch.Tensor, **samp
     import os
     if os.environ.get("GQ_PREFILL_NATIVE", "1") != "0" and model.cache_initialized and model.prefill_ready(x):
         logits = model.prefill_native(x, input_pos, start=0, last_only=True)
+    elif getattr(model, "adapter", None) is not None and x.numel() == 1 and model.native_ready():
+        logits = model.decode_native(x.view(1).to(torch.int32), input_pos.view(1))  # (a one-token prompt under a LoRA adapter: the fused step)
     else:
         logits = model(x, input_pos)
     return sample(logits, **sampling_kwargs)[0]
@@ -236,6 +238,10 @@ class DecodeGraph:
         # over an int8 copy that has been made again
         if getattr(m, "lm_head_dtype", "fp16") == "int8":
             sig += ["int8"] + [t.data_ptr() for t in m.head_q8()]
+        # the LoRA adapter the step launches beside the base (Transformer.set_adapter): a graph captured under one does not replay under another
+        ad = getattr(m, "adapter", None)
+        if ad is not None:
+            sig += ["lora"] + [t.data_ptr() for lay in m.adapter_layers for site in lay.values() if site is not None for t in (site.A, site.B)]
         return tuple(sig)
 
     def check_bound(self):
@@ -487,7 +493,7 @@ def benchmark_decode(model: Transformer, device, num_samples=5, max_new_tokens=1
 def main(prompt=None, num_samples=5, max_new_tokens=100, batch_size=1, top_k=200, temperature=0.8, compile=2,
          compile_prefill=False, profile=None, device="cuda", model_name=None, backend=None, bitwidth=None,
          checkpoint_path=None, config_path=None, dtype=None, print_result=False, random_init=False, kv_cache_dtype=None, lm_head_dtype=None,
-         frequency_penalty=0.0, presence_penalty=0.0):
+         frequency_penalty=0.0, presence_penalty=0.0, adapter=None):
     """generate.py:268-389 -- same arguments and printed report.  `compile` selects the decode driver: 0 = eager per-token
     launches, >= 1 = the captured hipGraph of the decode step (the role torch.compile(mode='max-autotune') plays in the
     reference).  A tokenizer is only needed for a text prompt / --print_result; without one the BOS id of the model
@@ -495,7 +501,9 @@ def main(prompt=None, num_samples=5, max_new_tokens=100, batch_size=1, top_k=200
     weight-only int8 copy (Transformer.set_lm_head_dtype; ValueError on the CPU or a model that is not fp16).
     frequency_penalty / presence_penalty != 0: the decode step draws with the fused sampler (DecodeGraph(native_sampling=True), its own
     counter-based random numbers) and applies them there, over the tokens each sample has generated; ValueError without the captured
-    step (--compile 0, the CPU) or on a model without the fused decode step -- never dropped."""
+    step (--compile 0, the CPU) or on a model without the fused decode step -- never dropped.
+    adapter: a peft LoRA adapter directory (lora.LoraAdapter.from_dir, Transformer.set_adapter): q / k / v / o / down targets beside the
+    quantized base on the fused decode step; ValueError / NotImplementedError where the step declines, never ignored."""
     print(f"Using device={device}")
     dtype = {"float16": torch.float16, "bfloat16": torch.bfloat16, "float32": torch.float32, None: torch.float16}.get(dtype, dtype)
     if batch_size != 1:
@@ -520,6 +528,11 @@ def main(prompt=None, num_samples=5, max_new_tokens=100, batch_size=1, top_k=200
     model.setup_caches(1, prompt_length + max_new_tokens, kv_cache_dtype=kv_cache_dtype)
     if lm_head_dtype is not None:
         model.set_lm_head_dtype(lm_head_dtype)
+    if adapter is not None:
+        from .lora import LoraAdapter
+        if not model.native_ready():
+            raise ValueError("lora: --adapter is served by the fused decode step only (a fused Any-Precision model in fp16 on the GPU)")
+        model.set_adapter(LoraAdapter.from_dir(adapter))
     use_graph = bool(compile) and "cuda" in str(device)
     additive = dict(frequency_penalty=frequency_penalty, presence_penalty=presence_penalty) if frequency_penalty or presence_penalty else {}
     if additive and not use_graph:
@@ -584,7 +597,9 @@ if __name__ == "__main__":
                         help='subtract this times the number of times a sample has generated a token from its logit (fused sampler; default 0)')
     parser.add_argument('--presence_penalty', type=float, default=0.0,
                         help='subtract this from the logit of every token a sample has generated (fused sampler; default 0)')
+    parser.add_argument('--adapter', type=str, default=None,
+                        help='a peft LoRA adapter directory (q / k / v / o / down targets) served beside the quantized base on the fused decode step')
     a = parser.parse_args()
     main(a.prompt, a.num_samples, a.max_new_tokens, a.batch_size, a.top_k, a.temperature, a.compile, a.compile_prefill, a.profile,
          a.device, a.model_name, a.backend, a.bitwidth, a.checkpoint_path, a.config_path, a.dtype, a.print_result, a.random_init, a.kv_cache_dtype,
-         a.lm_head_dtype, a.frequency_penalty, a.presence_penalty)
+         a.lm_head_dtype, a.frequency_penalty, a.presence_penalty, a.adapter)

@@ -405,6 +405,7 @@ class Transformer(nn.Module):
         self.fuse_linears = fuse_linears
         self._native = None
         self.lm_head_dtype = "fp16"  # set_lm_head_dtype
+        self.adapter, self.adapter_layers = None, None  # set_adapter: the LoraAdapter and its sites per layer as bound to this model
         self._head_q8 = None         # (q int8 [V, D], scale fp32 [V], the output.weight they were made from): plain attributes, not buffers
         # new weights (copied in place or assigned): the native step's buffers / launch plans / row pairing are rebuilt lazily
         self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module._weights_changed())
@@ -440,6 +441,20 @@ class Transformer(nn.Module):
         self._head_q8 = None
         if name == "int8":
             self.head_q8()
+        self._reset_native()
+
+    def set_adapter(self, adapter) -> None:
+        """A LoRA adapter (lora.LoraAdapter) beside the quantized base, or None: the fused decode step adds its q / k / v, o and down
+        deltas with two side launches per site (native_step.ApStep.layers, csrc/lora.hip), the prompt pass and `score_native` with torch
+        matmuls per row.  The adapter is checked against the model's shapes and moved to its device (ValueError("lora: ...")); the
+        native step is rebuilt, so a DecodeGraph captured under one adapter does not replay under another.  Fused Any-Precision models
+        on the GPU with an fp16 cache only -- what the step declines raises when it is built, nothing falls back; the module-by-module
+        `forward` refuses while an adapter is set."""
+        if adapter is not None:
+            if not self.fuse_linears:
+                raise NotImplementedError("lora: served on fused-linear Any-Precision models only (QTIP models are not)")
+        self.adapter_layers = adapter.bind(self.config, self.output.weight.device) if adapter is not None else None
+        self.adapter = adapter
         self._reset_native()
 
     def _head_q8_check(self):
@@ -535,6 +550,8 @@ class Transformer(nn.Module):
 
     def forward(self, idx: Tensor, input_pos: Optional[Tensor] = None) -> Tensor:
         assert self.cache_initialized, "Caches must be initialized first"
+        if self.adapter is not None:
+            raise ValueError("lora: the module-by-module forward does not apply the adapter (decode_native / prefill_native do)")
         if self.causal_mask is not None:
             mask = self.causal_mask[None, None, input_pos]
             wmask = {w: wm[None, None, input_pos] for w, wm in self.window_masks.items()}  # (empty for a model without windows)

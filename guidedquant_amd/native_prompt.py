@@ -97,6 +97,8 @@ def prompt_pass(model, idx, input_pos, start: int, last_only: bool, chunk: Optio
     cfg = model.config
     S, H, Hkv, hd = idx.numel(), cfg.n_head, cfg.n_local_heads, cfg.head_dim
     assert model.prefill_ready(idx) and input_pos.numel() == S and input_pos.dtype == torch.int32 and start + S <= model.max_seq_length
+    if getattr(model, "adapter", None) is not None:
+        model._native_state()  # (the refusals of an adapter are the decode step's: raised here too, before a row is written)
     if chunk is None:
         chunk = int(os.environ.get("GQ_PREFILL_CHUNK", "4096"))
     assert chunk >= 1, chunk
@@ -214,16 +216,26 @@ class _Piece:
 
             def norm(n, delta):
                 _lib.check(L.gq_rmsnorm_rows(x.data_ptr(), native_step._ptr(delta), n.weight.data_ptr(), self.xn.data_ptr(), S, D, n.eps, st), "gq_rmsnorm_rows")
-            for b, win in zip(m.layers, cfg.layer_windows or (None,) * len(m.layers)):
+            ad = getattr(m, "adapter", None)  # (a LoRA adapter: the three deltas of lora.py per row, with torch matmuls on the rows)
+            no_lora = dict(qkv=None, o=None, down=None)
+            for li, (b, win) in enumerate(zip(m.layers, cfg.layer_windows or (None,) * len(m.layers))):
                 att, ff = b.attention, b.feed_forward
+                lora = m.adapter_layers[li] if ad is not None else no_lora
                 norm(b.input_layernorm, pending)
                 qkv = torch.cat([att.wq(xn), att.wk(xn), att.wv(xn)], dim=-1) if qt else att.wqkv(xn)
+                if lora["qkv"] is not None:  # (in front of the row-write entry: the delta is rotated and cached with q / k / v)
+                    qkv = qkv.view(S, -1) + lora["qkv"].delta_rows(self.xn)
                 y = self.rows_and_attention(att, qkv.view(S, -1), win, st)
-                norm(b.post_attention_layernorm, att.wo(y).view(S, D))
+                o = att.wo(y).view(S, D)
+                if lora["o"] is not None:
+                    o = o + lora["o"].delta_rows(y.reshape(S, -1))
+                norm(b.post_attention_layernorm, o)
                 gu = torch.cat([ff.w1(xn), ff.w3(xn)], dim=-1) if qt else ff.w1w3(xn)
                 paired = 1 if not qt and getattr(ff.w1w3, "gq_row_pairs", False) else 0  # (QTIP: gate | up side by side)
                 _lib.check(L.gq_silu_mul_rows(gu.view(S, 2 * inter).data_ptr(), self.hbuf.data_ptr(), S, inter, paired, st), "gq_silu_mul_rows")
                 pending = ff.w2(self.hbuf.view(1, S, inter)).view(S, D)
+                if lora["down"] is not None:
+                    pending = pending + lora["down"].delta_rows(self.hbuf)
         return pending
 
 
@@ -345,6 +357,8 @@ def score_packed(model, seqs, rows: Optional[Tensor] = None):
     and whether it is the most probable one; a sequence's last row has no next token (logprob 0, hit False)."""
     if model.kv_cache_dtype == "fp8":
         raise NotImplementedError("packed scoring: fp8 KV cache")
+    if getattr(model, "adapter", None) is not None:
+        raise NotImplementedError("lora: packed scoring is not served under an adapter (score the sequences one by one)")
     cfg = model.config
     lens = [int(s.numel()) for s in seqs]
     if not lens or min(lens) < 2:

@@ -245,6 +245,8 @@ class ApStep(StepState):
         c = model.config
         if self.kv8 and model.kv8_unserved():
             raise ValueError("fp8 KV cache: " + model.kv8_unserved())
+        self.adapter = getattr(model, "adapter", None)  # (Transformer.set_adapter: a LoraAdapter, or None)
+        self.lora_layers = getattr(model, "adapter_layers", None)  # (its sites per layer as bound to THIS model: LoraAdapter.bind)
         # workspace of the down projection where the library splits its rows along K over blocks (K > 16384: 70B)
         wb = max(int(_lib.lib().gq_anyprec_gemv_fused_ws_bytes(c.dim, c.intermediate_size, b.feed_forward.w2.bitwidth, 1)) for b in model.layers)
         if wb:
@@ -259,6 +261,27 @@ class ApStep(StepState):
         else:
             assert not any(getattr(b.feed_forward.w1w3, "gq_row_pairs", False) for b in model.layers), \
                 "GQ_NATIVE_PAIRS=0 on a model whose gate/up rows were already paired"
+        if self.adapter is not None:
+            self._adapter_buffers()
+
+    def _adapter_buffers(self):
+        """what a LoRA adapter adds to the state (lora.py, csrc/lora.hip): the partial sums of gq_lora_down, and per site the vector its
+        gq_lora_up writes -- the q | k | v delta (+ the checkpoint's bias) the attention launch adds, the residuals of wo and w2 with
+        their delta.  The refusals: none of them falls back."""
+        c, ad, dev = self.m.config, self.adapter, self.x.device
+        if self.kv8:
+            raise NotImplementedError("lora: the fp8 KV cache is not served under an adapter (setup_caches(.., kv_cache_dtype='fp16'))")
+        if c.qk_norm and ad.targets("qkv"):
+            raise ValueError("lora: q / k / v targets on a QK-norm model (Qwen3): no attention launch has both the norm and a bias; "
+                             "o_proj / down_proj targets are served")
+        if ad.targets("qkv") and c.head_dim not in (64, 128):
+            raise ValueError(f"lora: q / k / v targets need head_dim 64 or 128 (gq_attn_decode_split_bias), not {c.head_dim}")
+        if ad.targets("down") and not self.pairs:
+            raise ValueError("lora: a down_proj target needs the paired gate / up rows (GQ_NATIVE_PAIRS=1): without them no launch "
+                             "writes the silu * up vector")
+        f16 = dict(dtype=torch.float16, device=dev)
+        self.lora_ws = torch.zeros(64 * 192, dtype=torch.float32, device=dev)
+        self.qkv_delta, self.xr, self.hr = torch.zeros_like(self.qkv), torch.zeros(c.dim, **f16), torch.zeros(c.dim, **f16)
 
     def layers(self, x, pos, l0, l1, slot=0, ssq_ready=False):
         from .model import pair_gate_up_rows_
@@ -277,6 +300,13 @@ class ApStep(StepState):
         xp, ssq = x.data_ptr(), self.ssq.data_ptr()
         ws = (self.ap_ws.data_ptr(), self.ap_ws.numel() * 4) if self.ap_ws is not None else (None, 0)
         x_has_ssq = ssq_ready  # the slots hold the statistics of the current x
+        no_lora = dict(qkv=None, o=None, down=None)
+
+        def side(site, x_in, base, out, norm_weight=None):
+            """the two launches of a LoRA site (gq_lora_down, gq_lora_up): out = base + delta(x_in); the pointer of out"""
+            site.launch(L, x_in, norm_weight, c.norm_eps if norm_weight else 0.0, self.lora_ws.data_ptr(), base, out.data_ptr(), sp)
+            return out.data_ptr()
+
         for li, blk in enumerate(m.layers[l0:l1]):
             at, ff = blk.attention, blk.feed_forward
             kv = self.kv(at, slot)
@@ -290,7 +320,15 @@ class ApStep(StepState):
             rope = (pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), *kv, c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length)
             # RoPE + KV-cache write in the epilogue of the wqkv GEMV, attention without them, where the library serves the layer's
             # wqkv that way (fast mode, 2-bit, K <= 4096: csrc/ap_stream.hip); else the two launches of rounds 1-3
-            if self.kv8:
+            lora = self.lora_layers[l0 + li] if self.adapter is not None else no_lora
+            if lora["qkv"] is not None:
+                # an adapter on q / k / v: its delta belongs in front of the rotation like Qwen2's bias -- plain wqkv GEMV, the two LoRA
+                # launches on the same x and norm weight into qkv_delta (= bias + delta on a Qwen2 model), then the bias form of the
+                # attention launch with that vector
+                launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
+                side(lora["qkv"], xp, _ptr(at.wqkv.bias), self.qkv_delta, blk.input_layernorm.weight.data_ptr())
+                self.attend("gq_attn_decode_split_bias", qkv, pos, kv, sp, (self.qkv_delta.data_ptr(),), layer=l0 + li)
+            elif self.kv8:
                 launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
                 self.attend_kv8(at, pos, kv, sp, l0 + li)
             elif c.qk_norm:
@@ -317,18 +355,22 @@ class ApStep(StepState):
                 launch("gq_anyprec_gemv_fused", *wqkv, None, 0)
                 self.attend("gq_attn_decode_split", qkv, pos, kv, sp, layer=l0 + li)
             # x, out, weights, norm weight, eps, residual (wo's input width is n_head * head_dim: not dim for a model with a head_dim of its own)
-            wo = (y, h, *_lin(at.wo), None, 0.0, xp)
+            # (an adapter on o: the residual wo adds is x + delta(y), written by the LoRA launches behind the attention)
+            res_o = side(lora["o"], y, xp, self.xr) if lora["o"] is not None else xp
+            wo = (y, h, *_lin(at.wo), None, 0.0, res_o)
             w13 = (h, gu, *_lin(ff.w1w3), blk.post_attention_layernorm.weight.data_ptr(), c.norm_eps, None)
-            w2 = (gu, xp, *_lin(ff.w2), None, 0.0, h)
             if self.pairs:  # flags, workspace, its bytes, statistics in, statistics out
                 w13_ssq = ssq if ho["w13"] else None
                 launch("gq_anyprec_gemv_fused_ho", *wo, 1, None, 0, None, w13_ssq)
                 launch("gq_anyprec_gemv_fused_ho", *w13, 4, None, 0, w13_ssq, None)
+                # (an adapter on down: the residual w2 adds is h + delta(silu * up), behind the w1w3 launch that writes the vector)
+                res_d = side(lora["down"], gu, h, self.hr) if lora["down"] is not None else h
+                w2 = (gu, xp, *_lin(ff.w2), None, 0.0, res_d)
                 launch("gq_anyprec_gemv_fused_ho", *w2, 1, *ws, None, w2_ssq)
             else:
                 launch("gq_anyprec_gemv_fused", *wo, 1)
                 launch("gq_anyprec_gemv_fused", *w13, 0)
-                launch("gq_anyprec_gemv_fused", *w2, 1 | 2)
+                launch("gq_anyprec_gemv_fused", gu, xp, *_lin(ff.w2), None, 0.0, h, 1 | 2)
             x_has_ssq = w2_ssq is not None
 
 
@@ -577,6 +619,8 @@ class QtipStep(StepState):
 
     def __init__(self, model):
         super().__init__(model)
+        if getattr(model, "adapter", None) is not None:
+            raise NotImplementedError("lora: QTIP models are not served under an adapter")
         if self.kv8:
             raise NotImplementedError("fp8 KV cache: QTIP models keep the fp16 cache (gq_attn_decode_qtip has no fp8 form)")
         c, dev = model.config, self.x.device

@@ -39,6 +39,8 @@ class TensorParallelDecoder:
         c = model.config
         if getattr(model, "kv_cache_dtype", "fp16") == "fp8":  # (this class launches attention itself, over fp16 caches)
             raise NotImplementedError("fp8 KV cache: tensor-parallel decode has no fp8 form (setup_caches(.., kv_cache_dtype='fp16'))")
+        if getattr(model, "adapter", None) is not None:  # (this class launches its slices of the linears itself: no LoRA side launches)
+            raise NotImplementedError("lora: tensor-parallel decode is not served under an adapter (set_adapter(None))")
         if getattr(model, "lm_head_dtype", "fp16") == "int8":  # (this class launches its vocabulary slice of the fp16 head itself)
             raise NotImplementedError("int8 lm_head: tensor-parallel decode has no int8 form (set_lm_head_dtype('fp16'))")
         assert model.fuse_linears, "tensor-parallel decode takes the fused (wqkv / w1w3) Any-Precision model"

@@ -977,6 +977,32 @@ int gq_sample_full_fsm(const void *logits, uint32_t vocab, int top_k, float top_
                        uint32_t *seen, const uint32_t *suppress, float *lp_raw, float *lp_drawn, uint32_t lp_cap, int top_n, int *top_ids,
                        float *top_lps, void *topn_ws, const GqSampleAdjust *adj, const GqTokenFsm *fsm, void *stream);
 
+/* LoRA adapters beside the quantized base (csrc/lora.hip): one site's contribution, two launches.
+ *   xh[k]  = x[k], or with norm_weight the RMSNorm of x with the rounding points of gq_dense_gemv_f16's prologue: the statistic in fp32 (per
+ *            block, from x), fp16(fp32(x * rs)), then the fp16 product with the weight
+ *   t[j]   = sum_k A[j][k] * xh[k]                          fp32 (v_mfma_f32_16x16x32_f16), j < R
+ *   d[n]   = fp16( scale_seg * sum_{j in seg(n)} B[n][j] * t[j] )   fp32 sum, one fp16 rounding; 0 for a row of no segment
+ *   out[n] = fp16( base[n] + d[n] )                         ONE fp16 add; d == 0: base[n] bit for bit (a -0 stays); base == NULL: out = d
+ * gq_lora_down: A fp16 [R][K] row-major -- the segments' A matrices stacked, each padded with zero rows to a multiple of 16 rows.  K is cut
+ *   into gq_lora_n_partials(K) slices (multiples of 64, the last one ragged), one block each; block p writes its fp32 sums to
+ *   partials[p * R .. p * R + R).  No atomics, no grid barrier.  K % 64 == 0, K <= 65536; R % 16 == 0, 16 <= R <= 192.
+ * gq_lora_up: every block adds the n_partials partial sums in ascending order, in a fixed association, into t (LDS), then forms 64 rows of
+ *   d and out.  segments: HOST array of 1..3 GqLoraSeg, read at the call (a captured launch keeps the values), ascending and disjoint in
+ *   rows; rank the padded rank (16, 32, 48 or 64), t_begin % 16 == 0, t_begin + rank <= R, b_offset % 8 == 0.  B fp16: segment s holds
+ *   [row_end - row_begin][rank] row-major at element b_offset.  All device pointers 16-byte aligned (out and base: 2-byte).
+ * Both: stream-ordered, one launch, bit-reproducible; a violation of the above is GQ_EINVAL (shape beyond the limits: GQ_ENOTSUP), nothing
+ * launched or written. */
+typedef struct GqLoraSeg {
+    uint32_t row_begin, row_end; /* output rows [row_begin, row_end) */
+    uint32_t t_begin, rank;      /* t[t_begin .. t_begin + rank) */
+    uint32_t b_offset;           /* elements */
+    float scale;                 /* lora_alpha / r */
+} GqLoraSeg;
+uint32_t gq_lora_n_partials(uint32_t K); /* 0 for a K the entries refuse */
+int gq_lora_down(const void *x, const void *norm_weight, float eps, const void *A, uint32_t R, uint32_t K, float *partials, void *stream);
+int gq_lora_up(const float *partials, uint32_t n_partials, uint32_t R, const void *B, const GqLoraSeg *segments, uint32_t n_segments,
+               const void *base, void *out, uint32_t N, void *stream);
+
 /* Test / tuning hooks (not part of the reference's surface).  gq_reset_env_cache: drop the cached GQ_* environment
  * knobs so that a test can flip them between calls.  gq_debug_set_timing_buffer: device buffer the plane kernels write
  * s_memtime phase stamps into (tools/phase_timing.py); NULL (default) disables it. */
