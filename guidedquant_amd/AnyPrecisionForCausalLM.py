@@ -603,17 +603,23 @@ class AnyPrecisionForCausalLM(nn.Module):
 
     # -- scoring: log-likelihood and perplexity of given token ids ------------------------------------------------------
     @staticmethod
-    def _score_rows(logits, targets, rows=512):
+    def _score_rows(logits, targets, rows=512, top_n=0):
         """(logprob fp32 [n], top1 [n]) of logits [n, V] and targets [n]: float -> log_softmax -> gather / argmax in blocks of `rows`
-        rows (the torch scoring head of Transformer._score_head; HF's loss upcasts the same way)"""
-        lps, tops = [], []
+        rows (the torch scoring head of Transformer._score_head; HF's loss upcasts the same way).  With top_n also (ids int64 [n, top_n],
+        fp32 [n, top_n]) by the same head's definition (native_prompt.top_rows)"""
+        lps, tops, lists = [], [], []
         for a in range(0, logits.shape[0], rows):
             ls = torch.nn.functional.log_softmax(logits[a:a + rows].float(), dim=-1)
             lps.append(ls.gather(1, targets[a:a + rows, None])[:, 0])
             tops.append(ls.argmax(dim=-1))
+            if top_n:
+                from .native_prompt import top_rows
+                lists.append(top_rows(logits[a:a + rows], ls, top_n))
+        if top_n:
+            return torch.cat(lps), torch.cat(tops), torch.cat([i for i, _ in lists]), torch.cat([v for _, v in lists])
         return torch.cat(lps), torch.cat(tops)
 
-    def score(self, input_ids, precision=None, kv_cache_dtype=None, native=None):
+    def score(self, input_ids, precision=None, kv_cache_dtype=None, native=None, top_logprobs=None):
         """Log-probabilities of one token sequence ([1, T] or [T], T >= 2): dict(logprobs fp32 [T - 1], greedy bool [T - 1], nll float)
         with logprobs[i] = log p(ids[i + 1] | ids[:i + 1]), greedy[i] = (the most probable next token is ids[i + 1]) and nll the mean of
         -logprobs -- the `outputs.loss` of the module tree for `labels=input_ids` (any_precision/evaluate/eval.py:222-223).
@@ -621,9 +627,16 @@ class AnyPrecisionForCausalLM(nn.Module):
         [T, V] logits in memory) when the checkpoint has one at this precision and T fits its context, else the module tree's forward
         and the same formula in torch.  native=False opts out, native=True raises instead of falling back, and
         kv_cache_dtype="fp8" (the fused model's e4m3 cache) never falls back silently.  Ids outside [0, vocab) raise ValueError before
-        anything is launched."""
+        anything is launched.
+        top_logprobs=n, 1..20 (anything else but None: ValueError): the dict gains `top_logprobs_ids` int64 [T - 1, n] -- the n most
+        probable tokens of the distribution logprobs[i] was taken from, most probable first, equal logits by ascending id, -1 where the
+        vocabulary has fewer -- and `top_logprobs` fp32 [T - 1, n], their log-probabilities (-inf beside a -1): the keys and dtypes
+        of `generate(..., top_logprobs=n)`.  On the fused route the scoring head selects them in its own launch (gq_head_nll_topn); the
+        module tree and the CPU sort in torch.  Without the keyword nothing changes."""
         from .model import kv_cache_dtype_name
+        from .native_prompt import check_top_logprobs
         kv = kv_cache_dtype_name(kv_cache_dtype)
+        top_n = check_top_logprobs(top_logprobs)
         ids = torch.as_tensor(input_ids)
         if ids.is_floating_point() or ids.dim() not in (1, 2) or (ids.dim() == 2 and ids.shape[0] != 1):
             raise ValueError("score: input_ids must be one sequence of token ids, [1, T] or [T]")
@@ -670,15 +683,17 @@ class AnyPrecisionForCausalLM(nn.Module):
                 if not (dec.max_seq_length >= cap and dec.max_batch_size >= 1 and dec.kv_cache_dtype == kv):
                     self._evict("graph")
                 dec.setup_caches(1, cap, kv_cache_dtype=kv)
+            lists = ()
             with torch.inference_mode():
                 if dec is not None:
-                    lp, greedy = dec.score_native(ids.to(self.device).to(torch.int32))
+                    lp, greedy, *lists = dec.score_native(ids.to(self.device).to(torch.int32), **({"top_logprobs": top_n} if top_n else {}))
                 else:
                     dev_ids = ids.to(self.device).long()
                     logits = self.model(input_ids=dev_ids.view(1, -1)).logits[0, :-1]
-                    lp, top1 = self._score_rows(logits, dev_ids[1:])
+                    lp, top1, *lists = self._score_rows(logits, dev_ids[1:], **({"top_n": top_n} if top_n else {}))
                     greedy = top1 == dev_ids[1:]
-            return dict(logprobs=lp, greedy=greedy, nll=float(-lp.double().mean()))
+            return dict(logprobs=lp, greedy=greedy, nll=float(-lp.double().mean()),
+                        **(dict(top_logprobs_ids=lists[0], top_logprobs=lists[1]) if top_n else {}))
         finally:
             self.set_precision(prev_precision)
 

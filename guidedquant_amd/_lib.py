@@ -35,6 +35,7 @@ EXPORTS = [
     "gq_token_fsm_build", "gq_sample_topk_fsm", "gq_sample_full_fsm",
     "gq_attn_decode_split_kv8",
     "gq_lora_n_partials", "gq_lora_down", "gq_lora_up",
+    "gq_head_nll_topn_ws_bytes", "gq_head_nll_topn",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -204,6 +205,9 @@ def lib():
         # (the scoring head: xn, W, target, S, V, D, logprob, lse, top1, splits, ws, ws_bytes, stream)
         L.gq_head_nll_ws_bytes.argtypes = [u32, u32, u32, u32]
         L.gq_head_nll.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp, u32, vp, ctypes.c_size_t, vp]
+        # (the top-n form: top_n, top_ids, top_lps behind top1; top_n behind splits for the workspace)
+        L.gq_head_nll_topn_ws_bytes.argtypes = [u32, u32, u32, u32, i32]
+        L.gq_head_nll_topn.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp, i32, vp, vp, u32, vp, ctypes.c_size_t, vp]
         L.gq_anyprec_pack.argtypes = [vp, vp, u32, u32, i32, vp]
         L.gq_lnq_cd_block.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, vp]
         L.gq_debug_set_timing_buffer.argtypes = [vp]
@@ -231,12 +235,13 @@ def lib():
             if name in _VOID:
                 getattr(L, name).restype = None
             elif name not in ("gq_last_error", "gq_anyprec_gemm_ws_bytes", "gq_anyprec_gemv_fused_ws_bytes", "gq_qtip_gemm_ws_bytes",
-                              "gq_head_nll_ws_bytes"):
+                              "gq_head_nll_ws_bytes", "gq_head_nll_topn_ws_bytes"):
                 getattr(L, name).restype = i32
         L.gq_anyprec_gemm_ws_bytes.restype = ctypes.c_size_t
         L.gq_anyprec_gemv_fused_ws_bytes.restype = ctypes.c_size_t
         L.gq_qtip_gemm_ws_bytes.restype = ctypes.c_size_t
         L.gq_head_nll_ws_bytes.restype = ctypes.c_size_t
+        L.gq_head_nll_topn_ws_bytes.restype = ctypes.c_size_t
         L.gq_last_error.restype = ctypes.c_char_p
         _lib = L
     return _lib

@@ -19,6 +19,24 @@
 // Each block writes one partial {max, sum, target logit, best value, best id} per (row, split); a split without a tile writes the
 // neutral element.  head_nll_merge_kernel folds the partials of a row in ascending split order: deterministic.
 // The tile loops hold no integer division.
+//
+// gq_head_nll_topn is the same pass with the n <= 20 best (fp16 logit, id) pairs of every row next to it: head_nll_kernel<true>.
+//   * where the lists live: a row's n best so far, sorted (value descending, id ascending), in LDS -- 128 rows x 20 x {float, int} =
+//     20 KB beside sW / sX, and only the rows of the wave that owns them: no barrier guards them.  Every lane keeps its row's n-th pair
+//     (the threshold) in two registers.
+//   * per tile a lane compares its 2 x 32 fresh logits with the threshold: a 4-bit mask per score block a, one ballot per mask.  Only
+//     where a ballot is not empty does the wave leave the fast path, and then it inserts the candidates ONE AT A TIME, wave-uniformly:
+//     the candidate goes to scalar registers (v_readlane from its lane), lane j reads entry j of the row's list, a ballot of "entry j
+//     stays in front" counts the position, the lanes behind it move their entry down one slot, and the row's four lanes take the new
+//     threshold.  A candidate that an earlier insert of the same tile has overtaken finds position n and writes nothing.  An insert is
+//     rare behind a split's first tiles -- about n ln(tiles x 128 / n) per row and split -- so it is allowed to be serial.
+//     The order is total on (value, id), so a list does not depend on the order of the inserts.  A NaN compares false and never enters;
+//     a column >= V is masked; an empty slot is (-inf, NO_ID), which every token -- a -inf logit included -- overtakes.
+//   * per (row, split) the block writes its list behind the five planes; head_nll_merge_kernel runs UNCHANGED on the five planes, and
+//     head_nll_topn_merge_kernel (one wave per row) folds the lists in ascending split order: each lane ranks its entry of the merged
+//     list and of the split's list among the 2 n by counting (v_readlane over the other list), the first n go through LDS to their
+//     rank, and lane j stores id_j and fp32(logit_j) - lse -- the subtraction logprob is made by, against the same lse.
+// No float atomics, no register array under a run-time index, no integer division in the tile loop.
 #include <hip/hip_runtime.h>
 
 #include "gq_internal.h"
@@ -38,12 +56,29 @@ constexpr float NEG = -1.0e30f;      // below every fp16 value and finite: NEG -
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr int NO_ID = 0x7FFFFFFF;
 constexpr u32 MAX_SPLITS = 65535u;
+constexpr u32 TN = 20;               // list slots per row (GQ_TOPN_MAX of include/gq_hip.h)
+static_assert(TN == GQ_TOPN_MAX, "the list stride is the largest top_n");
 
 // the partials of a (split, row): five planes [splits][S]
 struct Partials {
     float *m, *sum, *tgt, *bestv;
     int *besti;
 };
+
+// the top-n instance's lists: planes [splits][S][n] behind the partials (nothing in the plain instance)
+template <bool TOPN>
+struct Lists {};
+template <>
+struct Lists<true> {
+    u32 n;
+    float *val;
+    int *id;
+};
+
+// (value, id) a in front of (value, id) b: the order of every list
+__device__ __forceinline__ bool in_front(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
+__device__ __forceinline__ float lane_f(float x, u32 lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), (int)lane)); }
+__device__ __forceinline__ int lane_i(int x, u32 lane) { return __builtin_amdgcn_readlane(x, (int)lane); }
 
 __device__ __forceinline__ void fold(float &m, float &sum, float &tl, float &bv, int &bi, float om, float os, float ot, float ov, int oi) {
     const float mn = fmaxf(m, om);
@@ -56,10 +91,14 @@ __device__ __forceinline__ void fold(float &m, float &sum, float &tl, float &bv,
     }
 }
 
-__global__ void __launch_bounds__(256) head_nll_kernel(const uint16_t *__restrict__ xn, const uint16_t *__restrict__ W, const int *__restrict__ target,
-                                                       u32 S, u32 V, u32 D, u32 tiles_per_split, Partials ws) {
+// (two blocks per CU for the top-n instance by request: left to itself the compiler took 308 registers for it, one block per CU; the
+// plain instance keeps the bounds, and the code, it always had)
+template <bool TOPN>
+__global__ void __launch_bounds__(256, TOPN ? 2 : 1) head_nll_kernel(const uint16_t *__restrict__ xn, const uint16_t *__restrict__ W, const int *__restrict__ target,
+                                                       u32 S, u32 V, u32 D, u32 tiles_per_split, Partials ws, Lists<TOPN> top) {
     __shared__ __attribute__((aligned(16))) h16 sW[BV * LD];
     __shared__ __attribute__((aligned(16))) h16 sX[BS * LD];
+    __shared__ uint2 sL[TOPN ? BS * TN : 1];  // {value bits, id} [row][slot]; rows 32 w .. 32 w + 31 are wave w's alone
 
     const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u, g = l >> 4, li = l & 15u;
     const u32 s0 = blockIdx.x * BS, split = blockIdx.y;
@@ -102,6 +141,12 @@ __global__ void __launch_bounds__(256) head_nll_kernel(const uint16_t *__restric
         // NaN logit is in the row's sum.)
         m_run[b] = NEG, l_run[b] = 0.f, t_run[b] = -__builtin_inff(), bv[b] = NEG, bi[b] = NO_ID;
     }
+    // the threshold of the lane's two rows: the n-th pair of the list
+    float tv[2] = {-__builtin_inff(), -__builtin_inff()};
+    int ti[2] = {NO_ID, NO_ID};
+    if constexpr (TOPN) {
+        for (u32 i = l; i < 32u * TN; i += 64u) sL[32u * w * TN + i] = make_uint2((u32)__float_as_int(-__builtin_inff()), (u32)NO_ID);
+    }
 
     if (t0 < t1) {
         GQ_HEAD_LOAD_STEP(t0, 0u)
@@ -140,6 +185,43 @@ __global__ void __launch_bounds__(256) head_nll_kernel(const uint16_t *__restric
 
         // the tile's 128 logits of each column: rounded to fp16 once, then the online softmax, the target and the best pair
         const u32 vb = vt * BV + 4u * g;
+        if constexpr (TOPN) {  // (from the accumulators, in front of the softmax, four logits at a time)
+#pragma unroll
+            for (u32 b = 0; b < 2; b++) {
+#pragma unroll
+                for (u32 a = 0; a < 8; a++) {
+                    float x4[4];
+                    u32 pm = 0u;  // the lane's logits of score block a in front of its row's threshold
+#pragma unroll
+                    for (u32 r = 0; r < 4; r++) {
+                        const u32 v = vb + 16u * a + r;
+                        x4[r] = (float)(h16)acc[a][b][r];
+                        pm |= (v < V && in_front(x4[r], (int)v, tv[b], ti[b])) ? (1u << r) : 0u;
+                    }
+                    for (unsigned long long bal = __ballot(pm != 0u); bal != 0ull; bal = __ballot(pm != 0u)) {
+                        const u32 cl = (u32)__builtin_amdgcn_readfirstlane((int)__builtin_ctzll(bal));  // the candidate's lane
+                        const u32 r = (u32)__builtin_ctz(pm | 16u);
+                        const float mine = r == 0u ? x4[0] : r == 1u ? x4[1] : r == 2u ? x4[2] : x4[3];
+                        const float cv = lane_f(mine, cl);
+                        const int ci = (int)(vt * BV + 16u * a + 4u * (cl >> 4) + (u32)lane_i((int)r, cl));
+                        const u32 base = (32u * w + 16u * b + (cl & 15u)) * TN;
+                        const uint2 e = sL[base + min(l, top.n - 1u)];
+                        const float ev = __int_as_float((int)e.x);
+                        const u32 pos = (u32)__popcll(__ballot(l < top.n && in_front(ev, (int)e.y, cv, ci)));  // (sorted: a prefix)
+                        if (pos < top.n) {
+                            if (l >= pos && l + 1u < top.n) sL[base + l + 1u] = e;
+                            if (l == pos) sL[base + pos] = make_uint2((u32)__float_as_int(cv), (u32)ci);
+                            // the row's new n-th pair: the candidate, or what stood at n - 2
+                            const u32 src = top.n >= 2u ? top.n - 2u : 0u;
+                            const float nv = pos + 1u == top.n ? cv : lane_f(ev, src);
+                            const int ni = pos + 1u == top.n ? ci : lane_i((int)e.y, src);
+                            if (li == (cl & 15u)) tv[b] = nv, ti[b] = ni;
+                        }
+                        if (l == cl) pm &= pm - 1u;
+                    }
+                }
+            }
+        }
 #pragma unroll
         for (u32 b = 0; b < 2; b++) {
             float x[8][4];
@@ -194,6 +276,17 @@ __global__ void __launch_bounds__(256) head_nll_kernel(const uint16_t *__restric
             ws.besti[o] = bi[b];
         }
     }
+    if constexpr (TOPN) {
+        for (u32 rr = 0; rr < 32u; rr++) {
+            const u32 row = s0 + 32u * w + rr;
+            if (row < S && l < top.n) {
+                const uint2 e = sL[(32u * w + rr) * TN + l];
+                const size_t o = ((size_t)split * S + row) * top.n + l;
+                top.val[o] = __int_as_float((int)e.x);
+                top.id[o] = (int)e.y;
+            }
+        }
+    }
 }
 
 __global__ void __launch_bounds__(256) head_nll_merge_kernel(Partials ws, const int *__restrict__ target, u32 S, u32 splits, float *__restrict__ logprob,
@@ -216,6 +309,41 @@ __global__ void __launch_bounds__(256) head_nll_merge_kernel(Partials ws, const 
     logprob[row] = target[row] < 0 ? 0.0f : tl - z;
     if (lse) lse[row] = z;
     if (top1) top1[row] = bi;
+}
+
+// One wave per row.  Lane j < n holds entry j of the merged list (m) and of the next split's (s); both are sorted and, but for empty
+// slots, hold different ids.  rank(m_j) = j + #{s in front of m_j}, rank(s_j) = j + #{m not behind s_j}: a permutation of 0 .. 2 n - 1
+// (equal pairs -- empty slots -- keep m first), and ranks below n are the new list.
+__global__ void __launch_bounds__(256) head_nll_topn_merge_kernel(const float *__restrict__ val, const int *__restrict__ id, u32 S, u32 splits, u32 n,
+                                                                  const float *__restrict__ lse, int *__restrict__ top_ids, float *__restrict__ top_lps) {
+    __shared__ uint2 sm[4][TN];
+    const u32 w = threadIdx.x >> 6, l = threadIdx.x & 63u, row = blockIdx.x * 4u + w;
+    if (row >= S) return;  // (a whole wave; the kernel has no block barrier)
+    float mv = -__builtin_inff();
+    int mi = NO_ID;
+    for (u32 sp = 0; sp < splits; sp++) {
+        const size_t o = ((size_t)sp * S + row) * n + l;
+        const float sv = l < n ? val[o] : -__builtin_inff();
+        const int si = l < n ? id[o] : NO_ID;
+        u32 rm = l, rs = l;
+        for (u32 k = 0; k < n; k++) {
+            rm += in_front(lane_f(sv, k), lane_i(si, k), mv, mi) ? 1u : 0u;
+            rs += in_front(sv, si, lane_f(mv, k), lane_i(mi, k)) ? 0u : 1u;
+        }
+        if (l < n && rm < n) sm[w][rm] = make_uint2((u32)__float_as_int(mv), (u32)mi);
+        if (l < n && rs < n) sm[w][rs] = make_uint2((u32)__float_as_int(sv), (u32)si);
+        __builtin_amdgcn_wave_barrier();
+        if (l < n) {
+            const uint2 e = sm[w][l];
+            mv = __int_as_float((int)e.x), mi = (int)e.y;
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (l < n) {
+        const size_t o = (size_t)row * n + l;
+        top_ids[o] = mi == NO_ID ? -1 : mi;
+        top_lps[o] = mi == NO_ID ? -__builtin_inff() : mv - lse[row];
+    }
 }
 
 // the vocabulary splits of a launch: the caller's, or enough blocks for two per compute unit with at least 8 tiles each
@@ -249,10 +377,49 @@ extern "C" int gq_head_nll(const void *xn, const void *W, const int *target, uin
     float *f = (float *)ws;
     const Partials p = {f, f + plane, f + 2 * plane, f + 3 * plane, (int *)(f + 4 * plane)};
     const u32 ntiles = (V + BV - 1u) / BV, tps = (ntiles + ns - 1u) / ns;
-    hipLaunchKernelGGL(head_nll_kernel, dim3((S + BS - 1u) / BS, ns), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)xn, (const uint16_t *)W, target, S,
-                       V, D, tps, p);
+    hipLaunchKernelGGL(head_nll_kernel<false>, dim3((S + BS - 1u) / BS, ns), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)xn, (const uint16_t *)W,
+                       target, S, V, D, tps, p, Lists<false>{});
     GQ_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(head_nll_merge_kernel, dim3((S + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, p, target, S, ns, logprob, lse, top1);
+    GQ_HIP_CHECK(hipGetLastError());
+    return GQ_OK;
+}
+
+// the workspace of the top-n form: the five planes, a row of lse (for a caller that asks for none), then the lists' two planes
+extern "C" size_t gq_head_nll_topn_ws_bytes(uint32_t S, uint32_t V, uint32_t D, uint32_t splits, int top_n) {
+    (void)D;
+    if (S == 0 || V == 0 || top_n < 1 || top_n > (int)TN) return 0;
+    const size_t plane = (size_t)pick_splits(S, V, splits) * S;
+    return (plane * 5u + S + plane * (size_t)top_n * 2u) * sizeof(float);
+}
+
+extern "C" int gq_head_nll_topn(const void *xn, const void *W, const int *target, uint32_t S, uint32_t V, uint32_t D, float *logprob, float *lse, int *top1,
+                                int top_n, int *top_ids, float *top_lps, uint32_t splits, void *ws, size_t ws_bytes, void *stream) {
+    if (top_n < 1 || top_n > (int)TN) return gq_fail(GQ_EINVAL, "gq_head_nll_topn: top_n must be in 1..20.");
+    if (D == 0 || D % 64u != 0) return gq_fail(GQ_ENOTSUP, "gq_head_nll_topn: D must be a multiple of 64.");
+    if (S == 0 || V == 0) return gq_fail(GQ_EINVAL, "gq_head_nll_topn: S >= 1 and V >= 1.");
+    if (!xn || !W || !target || !logprob || !top_ids || !top_lps || !ws) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    if (((uintptr_t)xn | (uintptr_t)W) & 15u) return gq_fail(GQ_EINVAL, "gq_head_nll_topn: 16-byte aligned xn and W.");
+    if (((uintptr_t)target | (uintptr_t)logprob | (uintptr_t)lse | (uintptr_t)top1 | (uintptr_t)top_ids | (uintptr_t)top_lps | (uintptr_t)ws) & 3u)
+        return gq_fail(GQ_EINVAL, "gq_head_nll_topn: 4-byte aligned target, outputs and workspace.");
+    if (V > 0x7FFFFF00u || (uint64_t)S * D > 0xFFFFFFFFull) return gq_fail(GQ_ENOTSUP, "gq_head_nll_topn: V below 2^31, S * D below 2^32.");
+    if (splits > MAX_SPLITS) return gq_fail(GQ_EINVAL, "gq_head_nll_topn: at most 65535 splits.");
+    const u32 ns = pick_splits(S, V, splits), n = (u32)top_n;
+    const size_t plane = (size_t)ns * S;
+    if (ws_bytes < (plane * 5u + S + plane * n * 2u) * sizeof(float))
+        return gq_fail(GQ_EINVAL, "gq_head_nll_topn: workspace smaller than gq_head_nll_topn_ws_bytes.");
+    float *f = (float *)ws;
+    const Partials p = {f, f + plane, f + 2 * plane, f + 3 * plane, (int *)(f + 4 * plane)};
+    float *z = lse ? lse : f + 5 * plane;
+    const Lists<true> lists = {n, f + 5 * plane + S, (int *)(f + 5 * plane + S + plane * n)};
+    const u32 ntiles = (V + BV - 1u) / BV, tps = (ntiles + ns - 1u) / ns;
+    hipLaunchKernelGGL(head_nll_kernel<true>, dim3((S + BS - 1u) / BS, ns), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)xn, (const uint16_t *)W,
+                       target, S, V, D, tps, p, lists);
+    GQ_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(head_nll_merge_kernel, dim3((S + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, p, target, S, ns, logprob, z, top1);
+    GQ_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(head_nll_topn_merge_kernel, dim3((S + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, (const float *)lists.val, (const int *)lists.id, S,
+                       ns, n, (const float *)z, top_ids, top_lps);
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
 }

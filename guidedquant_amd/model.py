@@ -666,21 +666,26 @@ class Transformer(nn.Module):
     # (8B geometry: 3.2 against 3.6 ms at 2048 rows, 6.4 against 7.1 ms at 4096; profiles/score_head.json)
     SCORE_HEAD_AUTO = "1"
 
-    def _score_head(self, x: Tensor, targets: Tensor, kernel: bool):
+    def _score_head(self, x: Tensor, targets: Tensor, kernel: bool, top_n: int = 0):
         """the scoring head on the residual rows x fp16 [n, D] and targets int32 [n] (negative: ignored, logprob 0): (logprob fp32 [n],
         top1 [n]).  Both forms read the fp16 rows norm(x) the logits head feeds to `self.output`: the kernel gq_head_nll
-        (csrc/head_nll.hip; no logits in memory), or output -> float -> log_softmax -> gather / argmax in blocks of SCORE_HEAD_ROWS rows."""
-        return native_prompt.score_head(self, x, targets, kernel)
+        (csrc/head_nll.hip; no logits in memory), or output -> float -> log_softmax -> gather / argmax in blocks of SCORE_HEAD_ROWS rows.
+        top_n in 1..20 adds (ids int64 [n, top_n], log-probabilities fp32 [n, top_n]): gq_head_nll_topn, or a stable sort in the torch head."""
+        return native_prompt.score_head(self, x, targets, kernel, top_n)
 
-    def score_native(self, idx: Tensor, chunk: Optional[int] = None):
+    def score_native(self, idx: Tensor, chunk: Optional[int] = None, top_logprobs: Optional[int] = None):
         """Log-probabilities of a token sequence on the HIP prompt pass: (logprob fp32 [S - 1], greedy bool [S - 1]) with
         logprob[i] = log p(idx[i + 1] | idx[:i + 1]) and greedy[i] = (the most probable next token == idx[i + 1]) -- what the module tree's
         `labels=` loss and lm-eval's loglikelihood are made of.  The pass is `prefill_native`'s from position 0 (the same pieces, caches,
         GQ_PREFILL_CHUNK and GQ_PREFILL_ATTN; everything `prefill_ready` serves, the fp8 cache included) with the scoring head on every
         piece, so no [S, V] logits exist.  GQ_SCORE_HEAD: "1" the kernel gq_head_nll, "0" the torch head in blocks of 512 rows, "auto"
         (default) SCORE_HEAD_AUTO where the kernel serves the shape (dim % 64 == 0, fp16) and the torch head elsewhere.
-        `last_prefill_plan["head"]` records it ("hip-nll" | "torch").  The caches hold the sequence afterwards, as after a prompt."""
-        return native_prompt.score(self, idx, chunk)
+        `last_prefill_plan["head"]` records it ("hip-nll" | "torch").  The caches hold the sequence afterwards, as after a prompt.
+        top_logprobs=n (1..20; anything else but None: ValueError) adds two results, (ids int64 [S - 1, n], fp32 [S - 1, n]): the n most
+        probable tokens of the distribution logprob[i] was taken from, most probable first, equal logits by ascending id, with their
+        log-probabilities -- selected inside the head's own launch (gq_head_nll_topn; the plan then says "hip-nll-topn"), or by a stable
+        sort behind the torch head.  Without the keyword the pass makes the calls it always made."""
+        return native_prompt.score(self, idx, chunk, top_logprobs)
 
     def score_packed_native(self, seqs, rows: Optional[Tensor] = None):
         """Log-probabilities of SEVERAL token sequences in one HIP prompt pass (varlen attention): the sequences are laid end to end as

@@ -9,7 +9,8 @@ through the C ABI (include/gq_hip.h) and the quantized linears' own forwards.
     with the element-wise steps as one launch each (csrc/prefill.hip) and the attention as gq_attn_prefill / _kv8 (csrc/prefill_attn.hip) or
     torch SDPA over the cache rows [0, start + S).
   * the heads: logits (`Transformer.output`), or the scoring head (`score_head`: gq_head_nll, or log_softmax in row blocks), chosen by
-    `score_head_choice`, a pure function of the GQ_SCORE_HEAD mode.
+    `score_head_choice`, a pure function of the GQ_SCORE_HEAD mode.  With `top_logprobs=n` the head also lists every row's n most probable
+    tokens (gq_head_nll_topn, or `top_rows` behind the torch head).
 
   * packed scoring: `pack_plan` (first fit in input order) and `score_packed` -- several short sequences as ONE piece, `_PackedPiece`'s
     `rows_and_attention` through gq_rope_cache_rows_packed and gq_attn_prefill_packed (or SDPA under the block-diagonal `packed_mask`).
@@ -91,8 +92,8 @@ def ready(model, idx) -> bool:
 
 # ------------------------------------------------------------------------------------------------ the pass
 def prompt_pass(model, idx, input_pos, start: int, last_only: bool, chunk: Optional[int], score: Optional[dict] = None):
-    """the chunk loop of `prefill_native` (score None: its logits) and of `score_native` (score = dict(targets int32 [S], kernel bool):
-    every piece runs the scoring head on its rows; the list of the pieces' (logprob, top1))"""
+    """the chunk loop of `prefill_native` (score None: its logits) and of `score_native` (score = dict(targets int32 [S], kernel bool[,
+    top_n]): every piece runs the scoring head on its rows; the list of the pieces' (logprob, top1[, top ids, top log-probabilities]))"""
     L = _lib.lib()
     cfg = model.config
     S, H, Hkv, hd = idx.numel(), cfg.n_head, cfg.n_local_heads, cfg.head_dim
@@ -142,7 +143,7 @@ def _run_piece(model, idx, input_pos, start: int, bufs: dict, plan: str, head: b
         return None
     x = x + pending
     if score is not None:
-        return score_head(model, x, score["targets"], score["kernel"])
+        return score_head(model, x, score["targets"], score["kernel"], score.get("top_n", 0))
     x = x[-1:] if last_only else x
     return model.output(model.norm(x)).view(1, -1, cfg.vocab_size)
 
@@ -240,8 +241,37 @@ class _Piece:
 
 
 # ------------------------------------------------------------------------------------------------ scoring
-def score_head(model, x, targets, kernel: bool):
-    """`Transformer._score_head`: the kernel gq_head_nll, or the torch head in blocks of the model's SCORE_HEAD_ROWS rows"""
+def check_top_logprobs(n):
+    """`score`'s top_logprobs as an int: None = off, else 1 .. _lib.TOPN_MAX (ValueError otherwise)"""
+    if n is None:
+        return 0
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= _lib.TOPN_MAX:
+        raise ValueError(f"top_logprobs: an integer in 1..{_lib.TOPN_MAX} (None: off), not {n!r}")
+    return n
+
+
+def top_rows(logits: Tensor, ls: Tensor, n: int):
+    """the torch definition of a row's top-n list, on logits [rows, V] and their fp32 log_softmax `ls`: (ids int64 [rows, n], fp32
+    [rows, n]) -- the n largest logits, largest first, equal logits by ascending id (a STABLE descending sort), each with its entry of
+    `ls`; a NaN logit is never listed, and with fewer than n listable tokens the tail is -1 / -inf (the rule of gq_head_nll_topn)"""
+    key = logits.float()
+    nan = torch.isnan(key)
+    order = torch.sort(torch.where(nan, torch.full_like(key, float("-inf")), key), dim=-1, descending=True, stable=True).indices
+    if bool(nan.any()):  # (behind every token that is none, -inf logits included: a second stable pass, over the flags)
+        order = order.gather(1, torch.sort(nan.gather(1, order).to(torch.uint8), dim=-1, stable=True).indices)
+    ids = order[:, :n]
+    lps = ls.gather(1, ids)
+    listed = torch.arange(ids.shape[1], device=ids.device)[None, :] < (~nan).sum(dim=-1, keepdim=True)
+    ids = torch.where(listed, ids, torch.full_like(ids, -1))
+    lps = torch.where(listed, lps, torch.full_like(lps, float("-inf")))
+    if ids.shape[1] < n:  # (a vocabulary smaller than n)
+        ids, lps = F.pad(ids, (0, n - ids.shape[1]), value=-1), F.pad(lps, (0, n - lps.shape[1]), value=float("-inf"))
+    return ids, lps
+
+
+def score_head(model, x, targets, kernel: bool, top_n: int = 0):
+    """`Transformer._score_head`: the kernel gq_head_nll, or the torch head in blocks of the model's SCORE_HEAD_ROWS rows.  With top_n
+    the kernel is gq_head_nll_topn, the torch head adds `top_rows`, and the result gains (ids int64 [n, top_n], fp32 [n, top_n])"""
     n, V = x.shape[0], model.config.vocab_size
     if kernel:
         L = _lib.lib()
@@ -251,23 +281,37 @@ def score_head(model, x, targets, kernel: bool):
         lp = torch.empty(n, dtype=torch.float32, device=x.device)
         top1 = torch.empty(n, dtype=torch.int32, device=x.device)
         with torch.cuda.device(x.device):  # (the automatic split follows the compute units of the model's device: one guard for both calls)
+            if top_n:
+                ids = torch.empty((n, top_n), dtype=torch.int32, device=x.device)
+                lps = torch.empty((n, top_n), dtype=torch.float32, device=x.device)
+                nws = int(L.gq_head_nll_topn_ws_bytes(n, V, xn.shape[1], 0, top_n))
+                ws = torch.empty(max(nws, 4), dtype=torch.uint8, device=x.device)
+                _lib.check(L.gq_head_nll_topn(xn.data_ptr(), W.data_ptr(), targets.data_ptr(), n, V, xn.shape[1], lp.data_ptr(), None, top1.data_ptr(),
+                                              top_n, ids.data_ptr(), lps.data_ptr(), 0, ws.data_ptr(), nws, _lib.current_stream_ptr()), "gq_head_nll_topn")
+                return lp, top1, ids.long(), lps
             nws = int(L.gq_head_nll_ws_bytes(n, V, xn.shape[1], 0))
             ws = torch.empty(max(nws, 4), dtype=torch.uint8, device=x.device)
             _lib.check(L.gq_head_nll(xn.data_ptr(), W.data_ptr(), targets.data_ptr(), n, V, xn.shape[1], lp.data_ptr(), None, top1.data_ptr(), 0,
                                      ws.data_ptr(), nws, _lib.current_stream_ptr()), "gq_head_nll")
         return lp, top1
-    lps, tops = [], []
+    lps, tops, lists = [], [], []
     for a in range(0, n, model.SCORE_HEAD_ROWS):
         t = targets[a:a + model.SCORE_HEAD_ROWS].long()
-        ls = F.log_softmax(model.output(model.norm(x[a:a + model.SCORE_HEAD_ROWS])).float(), dim=-1)
+        logits = model.output(model.norm(x[a:a + model.SCORE_HEAD_ROWS]))
+        ls = F.log_softmax(logits.float(), dim=-1)
         lp = ls.gather(1, t.clamp(min=0)[:, None])[:, 0]
         lps.append(torch.where(t >= 0, lp, torch.zeros_like(lp)))
         tops.append(ls.argmax(dim=-1).to(torch.int32))
+        if top_n:
+            lists.append(top_rows(logits, ls, top_n))
+    if top_n:
+        return torch.cat(lps), torch.cat(tops), torch.cat([i for i, _ in lists]), torch.cat([v for _, v in lists])
     return torch.cat(lps), torch.cat(tops)
 
 
-def score(model, idx, chunk: Optional[int] = None):
+def score(model, idx, chunk: Optional[int] = None, top_logprobs: Optional[int] = None):
     """`Transformer.score_native`: the pass from position 0 with the scoring head on every piece"""
+    top_n = check_top_logprobs(top_logprobs)
     flat = idx.reshape(-1)
     S = flat.numel()
     assert model.prefill_ready(idx) and 2 <= S <= model.max_seq_length
@@ -276,10 +320,12 @@ def score(model, idx, chunk: Optional[int] = None):
     flat = flat.to(torch.int32)
     targets = torch.cat([flat[1:], torch.full((1, ), -1, dtype=torch.int32, device=flat.device)])
     pos = torch.arange(0, S, device=flat.device, dtype=torch.int32)
-    out = prompt_pass(model, flat, pos, 0, False, chunk, score=dict(targets=targets, kernel=kernel))
-    model.last_prefill_plan["head"] = "hip-nll" if kernel else "torch"
+    out = prompt_pass(model, flat, pos, 0, False, chunk, score=dict(targets=targets, kernel=kernel, **({"top_n": top_n} if top_n else {})))
+    model.last_prefill_plan["head"] = ("hip-nll-topn" if top_n else "hip-nll") if kernel else "torch"
     lp = torch.cat([o[0] for o in out])[:S - 1]
     top1 = torch.cat([o[1] for o in out])[:S - 1]
+    if top_n:
+        return lp, top1 == flat[1:], torch.cat([o[2] for o in out])[:S - 1], torch.cat([o[3] for o in out])[:S - 1]
     return lp, top1 == flat[1:]
 
 

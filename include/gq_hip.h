@@ -293,6 +293,29 @@ int gq_head_nll(const void *xn, const void *W, const int *target, uint32_t S, ui
                 int *top1, uint32_t splits, void *ws, size_t ws_bytes, void *stream);
 
 /*
+ * The scoring head with the top-n alternatives of every row (a serving API's echo + logprobs = n, prompt_logprobs = n): gq_head_nll's
+ * pass with the n best of each row selected in the same launch -- no second pass over W, no logits in memory.
+ *   logit, lse, logprob, top1, the `splits` rule and the D % 64 rule are gq_head_nll's, and logprob / lse / top1 are bit-equal to its
+ *   results for the same `splits`.
+ *   top_n                1 .. 20 (GQ_TOPN_MAX); anything else is GQ_EINVAL and nothing is written
+ *   top_ids[s][0 .. n)   int: the n tokens with the largest fp16 logit[s][v], largest first, equal logits (-0 == +0) by ascending id --
+ *                        the order of the decode route's lists.  The order is total on (value, id): the ids depend neither on `splits`
+ *                        nor on the run.
+ *   top_lps[s][j]        fp32(logit[s][top_ids[s][j]]) - lse[s]: ONE fp32 subtraction against the lse that logprob uses, so where
+ *                        target[s] is listed its entry equals logprob[s] bit for bit.
+ * A NaN logit is never listed (a row whose lse is NaN still lists its tokens that are no NaN, with NaN log-probabilities); a -inf logit
+ * is.  With fewer than n listable tokens (V < n, NaNs) the tail is id -1 / -inf.  A negative target still gets its row's list.
+ * top_ids and top_lps must not be NULL; lse and top1 may be.  The workspace holds gq_head_nll's five words per (row, range), one row
+ * of lse and the ranges' lists, n pairs per (row, range): gq_head_nll_topn_ws_bytes for the same S, V, D, splits, top_n (0 for a top_n
+ * outside the range); smaller: GQ_EINVAL.  Three launches: the pass, gq_head_nll's fold, and the fold of the lists in ascending range
+ * order.
+ */
+size_t gq_head_nll_topn_ws_bytes(uint32_t S, uint32_t V, uint32_t D, uint32_t splits, int top_n);
+int gq_head_nll_topn(const void *xn, const void *W, const int *target, uint32_t S, uint32_t V, uint32_t D, float *logprob, float *lse,
+                     int *top1, int top_n, int *top_ids /* [S][top_n] */, float *top_lps /* [S][top_n] */, uint32_t splits, void *ws,
+                     size_t ws_bytes, void *stream);
+
+/*
  * Host (CPU) twins of the two Any-Precision entry points: same arguments with HOST pointers, no stream; `nthreads` <= 0
  * uses the OpenMP default.  They serve BASELINE.json configs[0] ("CPU reference APLinear path via generate.py"): the module
  * semantics of inference/APLinear.py:35-60 with the tensors in host memory (the reference hard-codes 'cuda',

@@ -1,6 +1,7 @@
 """Score a file of token ids on the fused prompt path and print ONE JSON line: perplexity by the reference's definition
 (any_precision/evaluate/eval.py:205-226: non-overlapping chunks of --chunk_size tokens, the mean of the chunks' mean negative
 log-likelihoods, exp of it; a shorter tail is dropped), the per-chunk values, the share of greedy hits.  No tokenizer and no dataset:
+--top_logprobs N adds the N most probable tokens of every position and their log-probabilities, per chunk;
 the ids come from an .npy file or an .npz entry (--key, default the first array), the model from the arguments of
 guidedquant_amd/generate.py (`Transformer.score_native`: the HIP prompt pass with the scoring head; GQ_SCORE_HEAD picks the head).
     python tools/score_tokens.py tokens.npy --model_name meta-llama/Meta-Llama-3.1-8B --backend ap --bitwidth 2 --checkpoint_path DIR
@@ -40,6 +41,7 @@ def main():
     ap.add_argument("--backend", type=str, default="ap", choices=["ap", "qtip"])
     ap.add_argument("--random_init", action="store_true")
     ap.add_argument("--kv_cache_dtype", type=str, default=None, choices=["fp16", "fp8"])
+    ap.add_argument("--top_logprobs", type=int, default=None, help="1..20: the n most probable tokens of every position, with their log-probabilities")
     a = ap.parse_args()
     import torch
     from guidedquant_amd.generate import load_model
@@ -56,14 +58,19 @@ def main():
     dev_ids = torch.from_numpy(ids[:n * a.chunk_size]).to(device=a.device, dtype=torch.int32)
     if not model.prefill_ready(dev_ids[:a.chunk_size]):
         raise SystemExit("the fused prompt pass does not serve this model on this device (no fallback)")
-    nlls, hits = [], 0
+    nlls, hits, top_ids, top_lps = [], 0, [], []
     with torch.no_grad():
         for i in range(n):
-            lp, greedy = model.score_native(dev_ids[i * a.chunk_size:(i + 1) * a.chunk_size])
+            lp, greedy, *lists = model.score_native(dev_ids[i * a.chunk_size:(i + 1) * a.chunk_size],
+                                                    **({} if a.top_logprobs is None else {"top_logprobs": a.top_logprobs}))
             nlls.append(float(-lp.double().mean()))
             hits += int(greedy.sum())
+            if lists:  # (per chunk, [chunk_size - 1][n] each)
+                top_ids.append(lists[0].tolist())
+                top_lps.append(lists[1].tolist())
     print(json.dumps(dict(ppl=math.exp(sum(nlls) / n), nll_per_chunk=nlls, chunks=n, chunk_size=a.chunk_size, tokens_dropped=len(ids) - n * a.chunk_size,
-                          greedy_share=hits / (n * (a.chunk_size - 1)), head=model.last_prefill_plan["head"], kv_cache_dtype=model.kv_cache_dtype)))
+                          greedy_share=hits / (n * (a.chunk_size - 1)), head=model.last_prefill_plan["head"], kv_cache_dtype=model.kv_cache_dtype,
+                          **({} if a.top_logprobs is None else dict(top_logprobs_ids=top_ids, top_logprobs=top_lps)))))
 
 
 if __name__ == "__main__":
