@@ -467,7 +467,8 @@ class AnyPrecisionForCausalLM(nn.Module):
             self.set_precision(kwargs.pop('precision'))
         native = kwargs.pop('native', None)
         capture = kwargs.pop('capture', None)
-        # kv_cache_dtype="fp8": the KV cache of the fused decode model as e4m3 codes (Transformer.setup_caches).  Served by route 1 only;
+        # kv_cache_dtype="fp8" / "fp8_row": the KV cache of the fused decode model as e4m3 codes with a scale per head / an exponent byte per
+        # cached row (Transformer.setup_caches).  Served by route 1 only;
         # a request it cannot serve raises -- it never falls back to an fp16 cache silently.  (popped: it never reaches transformers)
         from .model import kv_cache_dtype_name
         kv = kv_cache_dtype_name(kwargs.pop('kv_cache_dtype', None))
@@ -511,8 +512,8 @@ class AnyPrecisionForCausalLM(nn.Module):
                 raise ValueError("lm_head_dtype='int8': served by the fused decode model only (not with native=False or capture=True)")
             if lp and (native is False or capture is True):
                 raise ValueError("output_logprobs=True: served by the fused decode model only (not with native=False or capture=True)")
-            if kv == "fp8" and (native is False or capture is True):
-                raise ValueError("kv_cache_dtype='fp8': served by the fused decode model only (not with native=False or capture=True)")
+            if kv != "fp16" and (native is False or capture is True):
+                raise ValueError(f"kv_cache_dtype='{kv}': served by the fused decode model only (not with native=False or capture=True)")
             # (full_sampler: route 1's sampler draws from the whole vocabulary; route 2 keeps the 64-candidate kernels and their answers)
             req, why = self._route_request(args, kwargs, sampler_processors=True, full_sampler=capture is not True) \
                 if (native is not False or capture is True) else (None, "opted out")
@@ -520,8 +521,8 @@ class AnyPrecisionForCausalLM(nn.Module):
                 req, why = None, "the fused routes need the GPU"
             if lora and req is None:
                 raise ValueError("lora: " + why)
-            if kv == "fp8" and req is None:
-                raise ValueError("kv_cache_dtype='fp8': " + why)
+            if kv != "fp16" and req is None:
+                raise ValueError(f"kv_cache_dtype='{kv}': " + why)
             if hd == "int8" and req is None:
                 raise ValueError("lm_head_dtype='int8': " + why)
             if lp and req is None:
@@ -570,10 +571,10 @@ class AnyPrecisionForCausalLM(nn.Module):
                     if native is True:
                         raise ValueError(f"native=True: vocabulary {dec.config.vocab_size} exceeds the fused sampler's {SAMPLER_MAX_VOCAB}")
                     dec = None
-                if dec is not None and kv == "fp8" and dec.kv8_unserved():
-                    raise ValueError("kv_cache_dtype='fp8': " + dec.kv8_unserved())
-                if lora and (dec is None or kv == "fp8"):
-                    why_not = getattr(self, "_no_native_reason", None) or ("the fp8 KV cache is not served under an adapter" if dec is not None else None)
+                if dec is not None and kv != "fp16" and dec.kv8_unserved():
+                    raise ValueError(f"kv_cache_dtype='{kv}': " + dec.kv8_unserved())
+                if lora and (dec is None or kv != "fp16"):
+                    why_not = getattr(self, "_no_native_reason", None) or (f"the {kv} KV cache is not served under an adapter" if dec is not None else None)
                     raise ValueError("lora: this checkpoint has no fused decode form at %d bits%s" % (self.precision, ": " + why_not if why_not else ""))
                 if dec is not None:
                     return self._generate_native(dec, req, kv_cache_dtype=kv, logprobs=lp, top_logprobs=top_n, lm_head_dtype=hd, adjust=adj)
@@ -586,9 +587,9 @@ class AnyPrecisionForCausalLM(nn.Module):
                 if adj_name:
                     why_not = getattr(self, "_no_native_reason", None)
                     raise ValueError("%s: this checkpoint has no fused decode form at %d bits%s" % (adj_name, self.precision, ": " + why_not if why_not else ""))
-                if kv == "fp8":
+                if kv != "fp16":
                     why_not = getattr(self, "_no_native_reason", None)
-                    raise ValueError("kv_cache_dtype='fp8': no fused decode model serves this request%s" % (": " + why_not if why_not else " (context or vocabulary beyond it)"))
+                    raise ValueError(f"kv_cache_dtype='{kv}': no fused decode model serves this request%s" % (": " + why_not if why_not else " (context or vocabulary beyond it)"))
                 if native is True:
                     why_not = getattr(self, "_no_native_reason", None)
                     raise ValueError("native=True: this checkpoint has no fused decode form at %d bits%s" % (self.precision, ": " + why_not if why_not else ""))
@@ -626,7 +627,7 @@ class AnyPrecisionForCausalLM(nn.Module):
         Routing follows `generate`: the fused decode model's HIP prompt pass with the scoring head (`Transformer.score_native`: no
         [T, V] logits in memory) when the checkpoint has one at this precision and T fits its context, else the module tree's forward
         and the same formula in torch.  native=False opts out, native=True raises instead of falling back, and
-        kv_cache_dtype="fp8" (the fused model's e4m3 cache) never falls back silently.  Ids outside [0, vocab) raise ValueError before
+        kv_cache_dtype="fp8" / "fp8_row" (the fused model's e4m3 caches) never falls back silently.  Ids outside [0, vocab) raise ValueError before
         anything is launched.
         top_logprobs=n, 1..20 (anything else but None: ValueError): the dict gains `top_logprobs_ids` int64 [T - 1, n] -- the n most
         probable tokens of the distribution logprobs[i] was taken from, most probable first, equal logits by ascending id, -1 where the
@@ -648,9 +649,9 @@ class AnyPrecisionForCausalLM(nn.Module):
         vocab = int(self.config.vocab_size)
         if int(host.min()) < 0 or int(host.max()) >= vocab:
             raise ValueError(f"score: token ids must lie in [0, {vocab})")
-        if kv == "fp8" and native is False:
-            raise ValueError("kv_cache_dtype='fp8': served by the fused decode model only (not with native=False)")
-        if self._adapter is not None and (native is False or kv == "fp8"):
+        if kv != "fp16" and native is False:
+            raise ValueError(f"kv_cache_dtype='{kv}': served by the fused decode model only (not with native=False)")
+        if self._adapter is not None and (native is False or kv != "fp16"):
             raise ValueError("lora: the adapter is served by the fused decode model with an fp16 cache only")
         prev_precision = self.precision
         if precision is not None:
@@ -665,12 +666,12 @@ class AnyPrecisionForCausalLM(nn.Module):
                     why = getattr(self, "_no_native_reason", None) or "this checkpoint has no fused decode form at %d bits" % self.precision
                     if dec is not None and T > dec.config.block_size:
                         dec, why = None, f"{T} tokens exceed the fused model's context ({dec.config.block_size})"
-                    if dec is not None and kv == "fp8" and dec.kv8_unserved():
+                    if dec is not None and kv != "fp16" and dec.kv8_unserved():
                         dec, why = None, dec.kv8_unserved()
                     if dec is not None and not dec.prefill_ready(ids.to(self.device).to(torch.int32)):
                         dec, why = None, "the fused model's prompt pass does not serve this model"
-            if dec is None and kv == "fp8":
-                raise ValueError("kv_cache_dtype='fp8': " + why)
+            if dec is None and kv != "fp16":
+                raise ValueError(f"kv_cache_dtype='{kv}': " + why)
             if dec is None and self._adapter is not None:
                 raise ValueError("lora: " + why)
             if dec is None and native is True:
@@ -1087,8 +1088,8 @@ class AnyPrecisionForCausalLM(nn.Module):
             self._native_cache[("decoder", bitwidth)] = dec
         if kv is not None and (kv != dec.kv_cache_dtype or not dec.cache_initialized):
             # (kv_cache_dtype given: the decoder comes back with caches of that dtype -- the ones it has, re-allocated, or 8 positions)
-            if kv == "fp8" and dec.kv8_unserved():
-                raise ValueError("kv_cache_dtype='fp8': " + dec.kv8_unserved())
+            if kv != "fp16" and dec.kv8_unserved():
+                raise ValueError(f"kv_cache_dtype='{kv}': " + dec.kv8_unserved())
             dec.setup_caches(max(1, dec.max_batch_size), max(8, dec.max_seq_length), kv_cache_dtype=kv)
         if hd is not None and hd != dec.lm_head_dtype:
             dec.set_lm_head_dtype(hd)

@@ -36,6 +36,7 @@ EXPORTS = [
     "gq_attn_decode_split_kv8",
     "gq_lora_n_partials", "gq_lora_down", "gq_lora_up",
     "gq_head_nll_topn_ws_bytes", "gq_head_nll_topn",
+    "gq_rope_cache_rows_kv8r", "gq_attn_decode_roped_kv8r", "gq_attn_prefill_kv8r",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -199,6 +200,10 @@ def lib():
         L.gq_attn_decode_roped_kv8.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, u32, vp]
         L.gq_attn_decode_split_kv8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, vp, vp, f32, vp, u32, vp]
         L.gq_attn_prefill_kv8.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, f32, u32, vp]
+        # (the per-row scaled fp8 cache forms: the exponent tensors uint8 [n_kv_head][max_seq] where the fp8 forms take their scales)
+        L.gq_rope_cache_rows_kv8r.argtypes = L.gq_rope_cache_rows_kv8.argtypes
+        L.gq_attn_decode_roped_kv8r.argtypes = L.gq_attn_decode_roped_kv8.argtypes
+        L.gq_attn_prefill_kv8r.argtypes = L.gq_attn_prefill_kv8.argtypes
         # (the packed pass: seg_begin behind the caches and no start; pos, row in front of the tables)
         L.gq_attn_prefill_packed.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, f32, u32, vp]
         L.gq_rope_cache_rows_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, f32, vp]

@@ -134,6 +134,34 @@ template <>
 struct AttnKv8<true> {
     const float *k_scale, *v_scale;
 };
+// ------------------------------------------------------------------------------------------------ the per-row scaled fp8 cache
+// kv_cache_dtype="fp8_row": e4m3 codes as above, and ONE exponent byte per (KV head, cached row) beside them, uint8 [n_kv_head][max_seq]
+// in e8m0: value = fp16(code) * 2^(byte - 127).  No per-head scale, nothing to calibrate: the write puts the row's largest finite
+// magnitude at the top of the e4m3 range.  THE exponent rule, on a = the fp16 bits of that magnitude (0 for a row without a finite
+// non-zero element; max over magnitudes = max over their bits):
+//   t = (a + 0xFF) >> 10      the fp16 exponent field, one more where the mantissa field exceeds 0x300: 448 = 1.75 * 2^8, so that
+//                             t - 23 = ceil(log2(amax / 448)) for every normal amax
+//   byte = clamp(t, 8, 30) + 104      e = byte - 127 in [-15, 7]: code * 2^e stays an fp16 value (2^-9 * 2^-15 = 2^-24; 448 * 2^7 = 57344)
+// Integer arithmetic alone, no log2, no divide; the host model is model.fp8_row_quantize.  Both factors are built from the byte:
+__device__ __forceinline__ u32 row_exp_byte(u32 amax_bits) { return min(max((amax_bits + 0xFFu) >> 10, 8u), 30u) + 104u; }
+__device__ __forceinline__ float row_exp_scale(u32 byte) { return __builtin_bit_cast(float, byte << 23); }        // 2^e: the read rule
+__device__ __forceinline__ float row_exp_inv(u32 byte) { return __builtin_bit_cast(float, (254u - byte) << 23); }  // 2^-e: the write rule
+// the largest of a value over each aligned group of 4 or 8 lanes (the thread units that hold one (row, head) of the row write), in every
+// lane of the group: the DPP butterflies of row_sum, no LDS round trip.  eight: wave-uniform.  The lanes of a group are active together.
+__device__ __forceinline__ u32 group_umax(u32 v, bool eight) {
+    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false));  // quad_perm [1,0,3,2]
+    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false));  // quad_perm [2,3,0,1]
+    if (eight) v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false));  // row_half_mirror
+    return v;
+}
+// the exponent bytes of a launch over such a cache (compile-time like AttnKv8: every other instance takes an empty argument)
+template <bool ROW>
+struct AttnRowExp {};
+template <>
+struct AttnRowExp<true> {
+    const uint8_t *k_exp, *v_exp;  // uint8 [n_kv_head][max_seq] of the batch slot
+};
+
 // the online softmax of one stream over a batch of U rows (scores pu, -3e38 = no row; V rows vfu): the rows share ONE rescale of the
 // running (max, sum, weighted V) -- one exp for the old maximum and one per row
 template <int U>

@@ -370,11 +370,16 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
 // KV8: the caches hold OCP e4m3 codes (gq_attn_decode_roped_kv8): a row is one 8-byte load per lane and unpack8_fp8, the K scale of the
 // head's KV group is folded into the score factor, the V scale multiplies the merged weighted sum (the final one in front of the
 // division, a split's partial one in front of the workspace, so that attn_combine_kernel serves as it is).  Everything else is shared.
-template <int HD, int QH, bool WIN = false, bool KV8 = false>
+// ROW (with KV8; gq_attn_decode_roped_kv8r): the per-row scaled fp8 caches of attn_core.h.  A row's exponent byte is requested WITH the
+// row -- the lanes that share the row ask for the same byte, in the speculative batch and in every later one, so that no round trip is
+// added to a launch that waits on memory -- and 2^e multiplies the 8 unpacked values in front of every product: exact, so from there on
+// the floats are those of the fp16 instance over a cache that holds code * 2^e.  No per-head scale is read.
+template <int HD, int QH, bool WIN = false, bool KV8 = false, bool ROW = false>
 __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint16_t *q, const int *pos_ptr, const typename gq_attn::CacheFmt<KV8>::elem *kc,
                                                                      const typename gq_attn::CacheFmt<KV8>::elem *vc, uint16_t *out, u32 H, u32 Hkv,
                                                                      u32 max_seq, float scale, u32 nsplit, float *ws, AttnWindow<WIN> wn,
-                                                                     gq_attn::AttnKv8<KV8> k8) {
+                                                                     gq_attn::AttnKv8<KV8 && !ROW> k8, gq_attn::AttnRowExp<ROW> rx) {
+    static_assert(!ROW || KV8, "the per-row scaled form is a form of the fp8 caches");
     using Fmt = gq_attn::CacheFmt<KV8>;
     using Row = typename Fmt::row;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -400,6 +405,10 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
 #pragma unroll
     for (int qh = 0; qh < QH; qh++) q4[qh] = *reinterpret_cast<const uint4 *>(q + (size_t)(h0 + qh) * HD + ld * 8);
     Row kv[U], vv[U];
+    constexpr int UE = ROW ? U : 1;  // (the exponent bytes of the rows in flight: ROW only)
+    u32 ke[UE], ve[UE];
+    const uint8_t *keg = nullptr, *veg = nullptr;
+    if constexpr (ROW) keg = rx.k_exp + (size_t)g * max_seq, veg = rx.v_exp + (size_t)g * max_seq;
     u32 t0 = w * PPW * U;
 #pragma unroll
     for (int u = 0; u < U; u++) {
@@ -409,8 +418,9 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         const bool in = sp < (u32)QH && t < max_seq && t < (u32)GQ_ATTN_SPEC;
         kv[u] = in ? *reinterpret_cast<const Row *>(kcg + (size_t)t * HD + ld * 8) : Fmt::zero();
         vv[u] = in ? *reinterpret_cast<const Row *>(vcg + (size_t)t * HD + ld * 8) : Fmt::zero();
+        if constexpr (ROW) ke[u] = in ? (u32)keg[t] : 127u, ve[u] = in ? (u32)veg[t] : 127u;
     }
-    if constexpr (KV8) scale *= k8.k_scale[g];  // (block-uniform: one scalar load next to the position's)
+    if constexpr (KV8 && !ROW) scale *= k8.k_scale[g];  // (block-uniform: one scalar load next to the position's)
     const u32 pos = (u32)pos_ptr[0];
     if (pos >= max_seq) {  // decoding past the cache: the head's output is poisoned (NaN logits), like attn_decode_kernel
         if (sp == 0u && tid < (u32)QH * HD) out[(size_t)h0 * HD + tid] = 0x7e00u;
@@ -445,22 +455,24 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
 #pragma unroll
         for (int e = 0; e < 8; e++) acc[qh][e] = 0.f;
     }
-    auto request = [&](Row (&kd)[U], Row (&vd)[U], u32 tb) {
+    auto request = [&](Row (&kd)[U], Row (&vd)[U], u32 (&ked)[UE], u32 (&ved)[UE], u32 tb) {
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const u32 t = tb + (u32)u * PPW + sub;
             const bool in = t < p1;
             kd[u] = in ? *reinterpret_cast<const Row *>(kcg + (size_t)t * HD + ld * 8) : Fmt::zero();
             vd[u] = in ? *reinterpret_cast<const Row *>(vcg + (size_t)t * HD + ld * 8) : Fmt::zero();
+            if constexpr (ROW) ked[u] = in ? (u32)keg[t] : 127u, ved[u] = in ? (u32)veg[t] : 127u;
         }
     };
     t0 = p0 + w * PPW * U;
     const bool have = p0 == 0u && t0 + PPW * U <= (u32)GQ_ATTN_SPEC;  // the batch at t0 is already in registers
-    if (!have && t0 < p1) request(kv, vv, t0);
+    if (!have && t0 < p1) request(kv, vv, ke, ve, t0);
     for (; t0 < p1; t0 += NW * PPW * U) {
         Row kn[U], vn[U];
+        u32 ken[UE], ven[UE];
         const bool more = QH > 1 && t0 + NW * PPW * U < p1;  // (QH > 1: the next pass is on its way while this one is multiplied)
-        if (more) request(kn, vn, t0 + NW * PPW * U);
+        if (more) request(kn, vn, ken, ven, t0 + NW * PPW * U);
         float pu[QH][U], vfu[U][8];
 #pragma unroll
         for (int u = 0; u < U; u++) {
@@ -468,7 +480,16 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
             const bool valid = t < p1;
             float kf[8];
             Fmt::unpack(kv[u], kf);
-            if constexpr (KV8) {
+            if constexpr (ROW) {  // (the read rule: fp16(code) * 2^e, exact; a stale row's byte may be anything -- replaced below like its codes)
+                const float sk = gq_attn::row_exp_scale(ke[u]), sv = gq_attn::row_exp_scale(ve[u]);
+                float vf[8];
+                Fmt::unpack(vv[u], vf);
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    kf[e] *= sk;
+                    vfu[u][e] = valid ? vf[e] * sv : 0.f;
+                }
+            } else if constexpr (KV8) {
                 float vf[8];
                 Fmt::unpack(vv[u], vf);
 #pragma unroll
@@ -499,8 +520,12 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         if (QH > 1) {
 #pragma unroll
             for (int u = 0; u < U; u++) kv[u] = kn[u], vv[u] = vn[u];
+            if constexpr (ROW) {
+#pragma unroll
+                for (int u = 0; u < U; u++) ke[u] = ken[u], ve[u] = ven[u];
+            }
         } else if (t0 + NW * PPW * U < p1) {
-            request(kv, vv, t0 + NW * PPW * U);
+            request(kv, vv, ke, ve, t0 + NW * PPW * U);
         }
     }
     const u32 stream = w * PPW + sub;
@@ -537,7 +562,7 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         for (u32 g8 = 0; g8 < ng; g8++)
 #pragma unroll
             for (u32 k = 0; k < 8u; k++) gq_attn::merge_step<HD>(scq, rq, fq, 8u * g8 + k, dd, o, sum);
-        if constexpr (KV8) o *= k8.v_scale[g];
+        if constexpr (KV8 && !ROW) o *= k8.v_scale[g];
         if (nsplit > 1u) {
             float *wp = ws + ((size_t)h * nsplit + sp) * (HD + 2u);
             wp[dd] = o;
@@ -795,17 +820,19 @@ extern "C" int gq_attn_decode_qtip(const GqQtipOut *qkv_lin, const int *pos, con
 // Attention of the decode step when the wqkv launch has already rotated q / k and written k / v of the current token into the
 // caches (gq_anyprec_gemv_qkv_rope): q fp16 [n_head * head_dim] rotated; the caches hold every position <= *pos.
 namespace {
-template <bool WIN, bool KV8 = false>
+template <bool WIN, bool KV8 = false, bool ROW = false>
 int roped_launch(const void *q, const int *pos, const void *k_cache, const void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head,
                  uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream,
-                 const float *k_scale = nullptr, const float *v_scale = nullptr) {
+                 const float *k_scale = nullptr, const float *v_scale = nullptr, const void *k_exp = nullptr, const void *v_exp = nullptr) {
     using CE = typename gq_attn::CacheFmt<KV8>::elem;
-    const bool any_null = !q || !pos || !k_cache || !v_cache || !out || (KV8 && (!k_scale || !v_scale));
+    const bool any_null = !q || !pos || !k_cache || !v_cache || !out || (KV8 && !ROW && (!k_scale || !v_scale)) || (ROW && (!k_exp || !v_exp));
     if (const int rc = attn_check_args(any_null, nullptr, WIN, window, n_head, n_kv_head, head_dim, n_split, workspace)) return rc;
     AttnWindow<WIN> wn{};
     if constexpr (WIN) wn = AttnWindow<true>{window};
-    gq_attn::AttnKv8<KV8> k8{};
-    if constexpr (KV8) k8 = gq_attn::AttnKv8<true>{k_scale, v_scale};
+    gq_attn::AttnKv8<KV8 && !ROW> k8{};
+    if constexpr (KV8 && !ROW) k8 = gq_attn::AttnKv8<true>{k_scale, v_scale};
+    gq_attn::AttnRowExp<ROW> rx{};
+    if constexpr (ROW) rx = gq_attn::AttnRowExp<true>{(const uint8_t *)k_exp, (const uint8_t *)v_exp};
     if (((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15u) return gq_fail(GQ_EINVAL, "buffers must be 16-byte aligned.");
     hipStream_t s = (hipStream_t)stream;
     // grouped-query models with a split cache: the 4 query heads of a KV group in one block (every cached row loaded once)
@@ -817,10 +844,10 @@ int roped_launch(const void *q, const int *pos, const void *k_cache, const void 
     const dim3 grid(n_head / qh, gqa_p ? copies : n_split);
     if (gqa_p && !WIN) {
         static GqPerDeviceOnce once;
-        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<128, 4, false, KV8>), 160 * 1024));
-        hipLaunchKernelGGL((attn_roped_kernel<128, 4, false, KV8>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<128, 4>::bytes()), s, (const uint16_t *)q, pos,
+        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<128, 4, false, KV8, ROW>), 160 * 1024));
+        hipLaunchKernelGGL((attn_roped_kernel<128, 4, false, KV8, ROW>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<128, 4>::bytes()), s, (const uint16_t *)q, pos,
                            (const CE *)k_cache, (const CE *)v_cache, (uint16_t *)out, n_head, n_kv_head, max_seq, scale, 1u, workspace,
-                           AttnWindow<false>{}, k8);
+                           AttnWindow<false>{}, k8, rx);
         GQ_HIP_CHECK(hipGetLastError());
         return GQ_OK;
     }
@@ -831,10 +858,10 @@ int roped_launch(const void *q, const int *pos, const void *k_cache, const void 
 #define GQ_LAUNCH_ROPED(HD_, QH_)                                                                                                    \
     do {                                                                                                                             \
         static GqPerDeviceOnce once;                                                                                                 \
-        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<HD_, QH_, WIN, KV8>), 160 * 1024));        \
-        hipLaunchKernelGGL((attn_roped_kernel<HD_, QH_, WIN, KV8>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<HD_, QH_>::bytes()), s, \
+        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<HD_, QH_, WIN, KV8, ROW>), 160 * 1024));   \
+        hipLaunchKernelGGL((attn_roped_kernel<HD_, QH_, WIN, KV8, ROW>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<HD_, QH_>::bytes()), s, \
                            (const uint16_t *)q, pos, (const CE *)k_cache, (const CE *)v_cache, (uint16_t *)out, n_head,               \
-                           n_kv_head, max_seq, scale, n_split, workspace, wn, k8);                                                   \
+                           n_kv_head, max_seq, scale, n_split, workspace, wn, k8, rx);                                               \
         if (n_split > 1u)                                                                                                            \
             hipLaunchKernelGGL((attn_combine_kernel<HD_, WIN>), dim3(n_head), dim3(HD_), 0, s, workspace, (uint16_t *)out, n_split,   \
                                pos, max_seq, wn);                                                                                    \
@@ -873,6 +900,18 @@ extern "C" int gq_attn_decode_roped_kv8(const void *q, const int *pos, const voi
                                         k_scale, v_scale);
     return roped_launch<false, true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, 0u, stream,
                                      k_scale, v_scale);
+}
+
+// the per-row scaled fp8 cache form (csrc/attn_core.h): the same launches over caches of one byte per element with one exponent byte per
+// (KV head, row), k_exp / v_exp uint8 [n_kv_head][max_seq] of the batch slot; window 0: the whole context
+extern "C" int gq_attn_decode_roped_kv8r(const void *q, const int *pos, const void *k_cache, const void *v_cache, const void *k_exp,
+                                         const void *v_exp, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                                         float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream) {
+    if (window)
+        return roped_launch<true, true, true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, window, stream,
+                                              nullptr, nullptr, k_exp, v_exp);
+    return roped_launch<false, true, true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, 0u, stream,
+                                           nullptr, nullptr, k_exp, v_exp);
 }
 
 // what attn_kv8.hip (gq_attn_decode_split_kv8: the fp8-cache form of the gq_attn_decode_split family, a translation unit of its own)

@@ -148,6 +148,23 @@ __device__ __forceinline__ void store_units(E *dst, u32 d, u32 HD, const u32 (&w
     }
 }
 
+// the per-row scaled fp8 cache (attn_core.h): the largest finite magnitude of the head's HD values -- this thread's 16, then the
+// HD / 16 threads of the (row, head), neighbouring lanes that are active together, by group_umax -- gives the row's exponent byte by
+// integer arithmetic; the codes are fp8_quant8 of x * 2^-e (store_units), the byte is stored by the group's first thread.  A non-finite
+// element takes no part in the maximum: +-Inf clamps to +-448 at any exponent, a NaN stores a NaN code.
+__device__ __forceinline__ void store_units_row(uint8_t *dst, uint8_t *exp_byte, u32 d, u32 HD, const u32 (&w1)[4], const u32 (&w2)[4]) {
+    u32 a = 0u;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const u32 m1 = (w1[k >> 1] >> (16 * (k & 1))) & 0x7FFFu, m2 = (w2[k >> 1] >> (16 * (k & 1))) & 0x7FFFu;
+        a = max(a, m1 < 0x7C00u ? m1 : 0u);
+        a = max(a, m2 < 0x7C00u ? m2 : 0u);
+    }
+    const u32 byte = gq_attn::row_exp_byte(gq_attn::group_umax(a, HD == 128u));
+    if (d == 0u) *exp_byte = (uint8_t)byte;
+    store_units(dst, d, HD, w1, w2, gq_attn::row_exp_inv(byte));
+}
+
 template <bool KV8>
 struct CacheElem {
     typedef uint16_t type;
@@ -171,21 +188,28 @@ struct CacheElem<true> {
 // PKD (gq_rope_cache_rows_packed: several sequences as one run of rows): the cache row is tail.row[s], apart from the RoPE position
 //   pos[s] inside the row's own sequence.  Every other form has the empty tail and writes row pos[s].
 // The loop bound is block-uniform in every form (QKN needs it: whole groups are active or idle together, total is a multiple of HD / 16).
-template <bool PKD>
+// K8R (gq_rope_cache_rows_kv8r, with KV8): the per-row scaled fp8 caches -- k and v through store_units_row, their exponent bytes to
+//   tail.k_exp / tail.v_exp [Hkv][max_seq]; k_inv / v_inv are not read.
+template <bool PKD, bool K8R = false>
 struct RowsTail {};
 template <>
-struct RowsTail<true> {
+struct RowsTail<true, false> {
     const int *row;
 };
+template <>
+struct RowsTail<false, true> {
+    uint8_t *k_exp, *v_exp;
+};
 
-template <bool QKN, bool QB, bool KV8, bool PKD = false>
+template <bool QKN, bool QB, bool KV8, bool PKD = false, bool K8R = false>
 __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__restrict__ qkv, const int *__restrict__ pos,
                                                               const uint16_t *__restrict__ cos_t, const uint16_t *__restrict__ sin_t,
                                                               uint16_t *__restrict__ q_out, typename CacheElem<KV8>::type *__restrict__ kc,
                                                               typename CacheElem<KV8>::type *__restrict__ vc, const float *__restrict__ k_inv,
                                                               const float *__restrict__ v_inv, const uint16_t *__restrict__ qnw,
                                                               const uint16_t *__restrict__ knw, float eps, const uint16_t *__restrict__ bias, u32 S,
-                                                              u32 H, u32 Hkv, u32 HD, u32 max_seq, RowsTail<PKD> tail) {
+                                                              u32 H, u32 Hkv, u32 HD, u32 max_seq, RowsTail<PKD, K8R> tail) {
+    static_assert(!K8R || (KV8 && !PKD), "the per-row scaled form is a form of the fp8 caches");
     const u32 upr = HD / 16u, heads = H + 2u * Hkv, total = S * heads * upr;  // units of 8 in the first half
     for (u32 base = blockIdx.x * 256u; base < total; base += gridDim.x * 256u) {
         const u32 i = base + threadIdx.x;
@@ -234,9 +258,13 @@ __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__
         if (hh >= H + Hkv) {  // v: stored as it is
             if (cr < max_seq) {
                 const u32 g = hh - H - Hkv;
-                float inv = 0.f;
-                if constexpr (KV8) inv = v_inv[g];
-                store_units(vc + ((size_t)g * max_seq + cr) * HD, d, HD, x1, x2, inv);
+                if constexpr (K8R) {
+                    store_units_row(vc + ((size_t)g * max_seq + cr) * HD, tail.v_exp + (size_t)g * max_seq + cr, d, HD, x1, x2);
+                } else {
+                    float inv = 0.f;
+                    if constexpr (KV8) inv = v_inv[g];
+                    store_units(vc + ((size_t)g * max_seq + cr) * HD, d, HD, x1, x2, inv);
+                }
             }
             continue;
         }
@@ -267,9 +295,13 @@ __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__
             store_units(q_out + ((size_t)hh * S + s) * HD, d, HD, o1, o2, 0.f);
         } else if (cr < max_seq) {
             const u32 g = hh - H;
-            float inv = 0.f;
-            if constexpr (KV8) inv = k_inv[g];
-            store_units(kc + ((size_t)g * max_seq + cr) * HD, d, HD, o1, o2, inv);
+            if constexpr (K8R) {
+                store_units_row(kc + ((size_t)g * max_seq + cr) * HD, tail.k_exp + (size_t)g * max_seq + cr, d, HD, o1, o2);
+            } else {
+                float inv = 0.f;
+                if constexpr (KV8) inv = k_inv[g];
+                store_units(kc + ((size_t)g * max_seq + cr) * HD, d, HD, o1, o2, inv);
+            }
         }
     }
 }
@@ -322,7 +354,8 @@ struct RowsEntry {
 // the bias form with a bias, the fp8 form with `kv8` (k_inv / v_inv are read by that form only)
 int rope_cache_rows(const RowsEntry &e, bool kv8, const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
                     void *v_cache, const float *k_inv, const float *v_inv, u32 S, u32 n_head, u32 n_kv_head, u32 head_dim, u32 max_seq,
-                    const void *q_norm_weight, const void *k_norm_weight, float eps, const void *qkv_bias, void *stream, const int *row = nullptr) {
+                    const void *q_norm_weight, const void *k_norm_weight, float eps, const void *qkv_bias, void *stream, const int *row = nullptr,
+                    void *k_exp = nullptr, void *v_exp = nullptr) {
     if (S == 0) return GQ_OK;
     // (QKN: the statistic of a head is added inside an aligned group of head_dim / 16 lanes: a power of two, within one wave)
     const bool hd_ok = e.any_hd16 ? (head_dim != 0 && head_dim % 16u == 0) : (head_dim == 64u || head_dim == 128u);
@@ -334,14 +367,20 @@ int rope_cache_rows(const RowsEntry &e, bool kv8, const void *qkv, const int *po
     if (total >= 0x7FFFFFFFull) return gq_fail(GQ_ENOTSUP, e.too_large);
     const u32 nb = (u32)((total + 255u) / 256u);
     const dim3 grid(nb > 65535u ? 65535u : nb), block(256);
-#define GQ_LAUNCH_ROWS(QKN_, QB_, KV8_, PKD_, TAIL_)                                                                                          \
-    hipLaunchKernelGGL((rope_cache_rows_kernel<QKN_, QB_, KV8_, PKD_>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)qkv, pos,      \
+#define GQ_LAUNCH_ROWS_EX(QKN_, QB_, KV8_, PKD_, TAIL_, K8R_)                                                                                  \
+    hipLaunchKernelGGL((rope_cache_rows_kernel<QKN_, QB_, KV8_, PKD_, K8R_>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)qkv, pos, \
                        (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)q_out, (CacheElem<KV8_>::type *)k_cache,         \
                        (CacheElem<KV8_>::type *)v_cache, k_inv, v_inv, (const uint16_t *)q_norm_weight, (const uint16_t *)k_norm_weight, eps, \
                        (const uint16_t *)qkv_bias, S, n_head, n_kv_head, head_dim, max_seq, TAIL_)
+#define GQ_LAUNCH_ROWS(QKN_, QB_, KV8_, PKD_, TAIL_) GQ_LAUNCH_ROWS_EX(QKN_, QB_, KV8_, PKD_, TAIL_, false)
     const RowsTail<false> none = {};
     const RowsTail<true> rows = {row};
-    if (row) {  // (the packed pass: fp16 caches)
+    const RowsTail<false, true> ex = {(uint8_t *)k_exp, (uint8_t *)v_exp};
+    if (k_exp) {  // (the per-row scaled fp8 caches)
+        if (q_norm_weight) GQ_LAUNCH_ROWS_EX(true, false, true, false, ex, true);
+        else if (qkv_bias) GQ_LAUNCH_ROWS_EX(false, true, true, false, ex, true);
+        else GQ_LAUNCH_ROWS_EX(false, false, true, false, ex, true);
+    } else if (row) {  // (the packed pass: fp16 caches)
         if (q_norm_weight) GQ_LAUNCH_ROWS(true, false, false, true, rows);
         else GQ_LAUNCH_ROWS(false, false, false, true, rows);
     } else if (kv8) {
@@ -354,6 +393,7 @@ int rope_cache_rows(const RowsEntry &e, bool kv8, const void *qkv, const int *po
         GQ_LAUNCH_ROWS(false, false, false, false, none);
     }
 #undef GQ_LAUNCH_ROWS
+#undef GQ_LAUNCH_ROWS_EX
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
 }
@@ -402,6 +442,21 @@ extern "C" int gq_rope_cache_rows_kv8(const void *qkv, const int *pos, const voi
                                 "gq_rope_cache_rows_kv8: problem too large."};
     return rope_cache_rows(e, true, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, k_inv, v_inv, S, n_head, n_kv_head, head_dim, max_seq, q_norm_weight,
                            k_norm_weight, eps, qkv_bias, stream);
+}
+
+extern "C" int gq_rope_cache_rows_kv8r(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
+                                       void *v_cache, void *k_exp, void *v_exp, uint32_t S, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim,
+                                       uint32_t max_seq, const void *q_norm_weight, const void *k_norm_weight, float eps, const void *qkv_bias,
+                                       void *stream) {
+    if (!qkv || !pos || !cos_table || !sin_table || !q_out || !k_cache || !v_cache || !k_exp || !v_exp) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    const bool qkn = q_norm_weight || k_norm_weight;
+    if (qkn && (!q_norm_weight || !k_norm_weight)) return gq_fail(GQ_EINVAL, "gq_rope_cache_rows_kv8r: both norm weights or none.");
+    if (qkn && qkv_bias) return gq_fail(GQ_EINVAL, "gq_rope_cache_rows_kv8r: the norm form and the bias form do not combine.");
+    static const RowsEntry e = {false, "gq_rope_cache_rows_kv8r: head_dim must be 64 or 128.", "gq_rope_cache_rows_kv8r: 16-byte aligned pointers.",
+                                "gq_rope_cache_rows_kv8r: problem too large."};
+    // (the exponent bytes are stored one at a time: no alignment asked of k_exp / v_exp)
+    return rope_cache_rows(e, true, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim, max_seq, q_norm_weight,
+                           k_norm_weight, eps, qkv_bias, stream, nullptr, k_exp, v_exp);
 }
 
 extern "C" int gq_rope_cache_rows_packed(const void *qkv, const int *pos, const int *row, const void *cos_table, const void *sin_table, void *q_out,

@@ -83,18 +83,39 @@ struct TileFmt<true> {
         }
         return make_uint4(o[0], o[1], o[2], o[3]);
     }
+    // the per-row scaled form (ROW, gq_attn_prefill_kv8r; csrc/attn_core.h): fp16(code) * 2^e with the row's exponent byte, e in [-15, 7] --
+    // the product is an fp16 value, so the rounding to fp16 is exact and the LDS image is that of an fp16 cache holding code * 2^e
+    static __device__ __forceinline__ uint4 to_f16_row(const chunk &v, u32 byte) {
+        const float sc = __builtin_bit_cast(float, byte << 23);
+        const u32 w[2] = {v.x, v.y};
+        u32 o[4];
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[e], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[e], true);
+            o[2 * e] = (u32)__builtin_bit_cast(uint16_t, (h16)(lo[0] * sc)) | ((u32)__builtin_bit_cast(uint16_t, (h16)(lo[1] * sc)) << 16);
+            o[2 * e + 1] = (u32)__builtin_bit_cast(uint16_t, (h16)(hi[0] * sc)) | ((u32)__builtin_bit_cast(uint16_t, (h16)(hi[1] * sc)) << 16);
+        }
+        return make_uint4(o[0], o[1], o[2], o[3]);
+    }
 };
 
 // the kernel's last argument: the scales of an fp8 cache, or -- PACKED, fp16 caches -- the segment begins (an instance that is neither
 // keeps the empty struct it had: its arguments and its code are those of the kernel without the flag)
-template <bool KV8, bool PACKED>
+// -- or, ROW, the exponent bytes of a per-row scaled fp8 cache, uint8 [n_kv_head][max_seq]
+template <bool KV8, bool PACKED, bool ROW = false>
 struct TailArg {
     typedef typename TileFmt<KV8>::Scales type;
 };
 template <>
-struct TailArg<false, true> {
+struct TailArg<false, true, false> {
     struct type {
         const int *seg_begin;
+    };
+};
+template <>
+struct TailArg<true, false, true> {
+    struct type {
+        const uint8_t *k_exp, *v_exp;
     };
 };
 
@@ -112,12 +133,15 @@ __device__ __forceinline__ u32 packed_lo(const int *__restrict__ seg_begin, u32 
 // that segment's rows only -- P = 0 alone does not keep another sequence's rows out: 0 x NaN inside an MFMA is NaN.  For a row the
 // products and their order are those of the one-sequence kernel (a masked key adds +-0 either way), so row i is bit for bit row i of
 // gq_attn_prefill(S = i + 1, start = 0, window = min(i - seg_begin[i] + 1, window)).
-template <int HD, bool KV8 = false, bool PACKED = false>
+// ROW (with KV8): a thread fetches the exponent bytes of its chunks' rows with the chunks (the CH threads of a row ask for the same byte)
+// and multiplies between the global load and the LDS store; the scales of the per-head form are not read.
+template <int HD, bool KV8 = false, bool PACKED = false, bool ROW = false>
 __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__restrict__ q, const typename TileFmt<KV8>::elem *__restrict__ kc,
                                                            const typename TileFmt<KV8>::elem *__restrict__ vc, uint16_t *__restrict__ out, u32 S,
                                                            u32 start, u32 H, u32 group, u32 max_seq, float c, u32 window,
-                                                           typename TailArg<KV8, PACKED>::type sc) {
+                                                           typename TailArg<KV8, PACKED, ROW>::type sc) {
     static_assert(!(KV8 && PACKED), "the packed pass has fp16 caches");
+    static_assert(!ROW || KV8, "the per-row scaled form is a form of the fp8 caches");
     using Fmt = TileFmt<KV8>;
     using Chunk = typename Fmt::chunk;
     constexpr u32 LD = HD + 8;             // halves per LDS row: 16 bytes of padding
@@ -132,7 +156,9 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
     const u32 q0 = (gridDim.x - 1u - blockIdx.x) * BQ;  // the long rows of the triangle first
     const u32 T = start + S;
     const typename Fmt::elem *kbase = kc + (size_t)kvh * max_seq * HD, *vbase = vc + (size_t)kvh * max_seq * HD;
-    if constexpr (KV8) c *= sc.k_scale[kvh];  // (the K scale: one factor of the scores)
+    if constexpr (KV8 && !ROW) c *= sc.k_scale[kvh];  // (the K scale: one factor of the scores)
+    const uint8_t *kebase = nullptr, *vebase = nullptr;
+    if constexpr (ROW) kebase = sc.k_exp + (size_t)kvh * max_seq, vebase = sc.v_exp + (size_t)kvh * max_seq;
 
     // the block's key range: [klo, khi] covers every key one of its rows attends
     const u32 p_lo = start + q0, khi = start + min(q0 + BQ - 1u, S - 1u);
@@ -163,6 +189,7 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
     }
 
     Chunk kreg[NCH], vreg[NCH];
+    u32 kexp[ROW ? NCH : 1], vexp[ROW ? NCH : 1];  // (ROW: the exponent bytes of the chunks' rows)
     auto load_tile = [&](u32 kt) {
 #pragma unroll
         for (u32 i = 0; i < NCH; i++) {
@@ -170,9 +197,11 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
             if (t < T) {
                 kreg[i] = *reinterpret_cast<const Chunk *>(kbase + (size_t)t * HD + 8u * col);
                 vreg[i] = *reinterpret_cast<const Chunk *>(vbase + (size_t)t * HD + 8u * col);
+                if constexpr (ROW) kexp[i] = kebase[t], vexp[i] = vebase[t];
             } else {
                 kreg[i] = Fmt::zero();
                 vreg[i] = Fmt::zero();
+                if constexpr (ROW) kexp[i] = 127u, vexp[i] = 127u;
             }
         }
     };
@@ -188,8 +217,13 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
 #pragma unroll
         for (u32 i = 0; i < NCH; i++) {
             const u32 id = tid + 256u * i, row = id / CH, col = id % CH;
-            *reinterpret_cast<uint4 *>(&sK[row * LD + 8u * col]) = Fmt::to_f16(kreg[i]);
-            *reinterpret_cast<uint4 *>(&sV[row * LD + 8u * col]) = Fmt::to_f16(vreg[i]);
+            if constexpr (ROW) {
+                *reinterpret_cast<uint4 *>(&sK[row * LD + 8u * col]) = Fmt::to_f16_row(kreg[i], kexp[i]);
+                *reinterpret_cast<uint4 *>(&sV[row * LD + 8u * col]) = Fmt::to_f16_row(vreg[i], vexp[i]);
+            } else {
+                *reinterpret_cast<uint4 *>(&sK[row * LD + 8u * col]) = Fmt::to_f16(kreg[i]);
+                *reinterpret_cast<uint4 *>(&sV[row * LD + 8u * col]) = Fmt::to_f16(vreg[i]);
+            }
         }
         __syncthreads();
         if (kt < kt1) load_tile(kt + 1u);  // in flight under the products below
@@ -299,7 +333,7 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
     l_run += __shfl_xor(l_run, 32, 64);
     if (qrow < S) {
         float inv = 1.0f / l_run;
-        if constexpr (KV8) inv *= sc.v_scale[kvh];  // (the V scale: on the output, in front of its one fp16 rounding)
+        if constexpr (KV8 && !ROW) inv *= sc.v_scale[kvh];  // (the V scale: on the output, in front of its one fp16 rounding)
         uint16_t *orow = out + (size_t)qrow * H * HD + (size_t)head * HD + 4u * g;
 #pragma unroll
         for (u32 d = 0; d < DB; d++) {
@@ -315,10 +349,10 @@ extern "C" int gq_attn_prefill_supported(uint32_t n_head, uint32_t n_kv_head, ui
 }
 
 namespace {
-template <bool KV8, bool PACKED = false>
+template <bool KV8, bool PACKED = false, bool ROW = false>
 int prefill_attn_launch(const void *q, const void *k_cache, const void *v_cache, void *out, uint32_t S, uint32_t start, uint32_t n_head,
                         uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t window, void *stream,
-                        typename TailArg<KV8, PACKED>::type sc) {
+                        typename TailArg<KV8, PACKED, ROW>::type sc) {
     using CE = typename TileFmt<KV8>::elem;
     if (!gq_attn_prefill_supported(n_head, n_kv_head, head_dim))
         return gq_fail(GQ_ENOTSUP, "gq_attn_prefill: head_dim 64 or 128, n_head a multiple of n_kv_head.");
@@ -337,10 +371,10 @@ int prefill_attn_launch(const void *q, const void *k_cache, const void *v_cache,
     const dim3 grid((S + BQ - 1u) / BQ, n_head), block(256);
     const uint32_t group = n_head / n_kv_head;
     if (head_dim == 64u)
-        hipLaunchKernelGGL((prefill_attn_kernel<64, KV8, PACKED>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
+        hipLaunchKernelGGL((prefill_attn_kernel<64, KV8, PACKED, ROW>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
                            (uint16_t *)out, S, start, n_head, group, max_seq, c, window, sc);
     else
-        hipLaunchKernelGGL((prefill_attn_kernel<128, KV8, PACKED>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
+        hipLaunchKernelGGL((prefill_attn_kernel<128, KV8, PACKED, ROW>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
                            (uint16_t *)out, S, start, n_head, group, max_seq, c, window, sc);
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
@@ -357,6 +391,14 @@ extern "C" int gq_attn_prefill_kv8(const void *q, const void *k_cache, const voi
                                    uint32_t window, void *stream) {
     if (!k_scale || !v_scale) return gq_fail(GQ_EINVAL, "null pointer argument.");
     return prefill_attn_launch<true>(q, k_cache, v_cache, out, S, start, n_head, n_kv_head, head_dim, max_seq, scale, window, stream, {k_scale, v_scale});
+}
+
+extern "C" int gq_attn_prefill_kv8r(const void *q, const void *k_cache, const void *v_cache, const void *k_exp, const void *v_exp, void *out,
+                                    uint32_t S, uint32_t start, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale,
+                                    uint32_t window, void *stream) {
+    if (!k_exp || !v_exp) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    return prefill_attn_launch<true, false, true>(q, k_cache, v_cache, out, S, start, n_head, n_kv_head, head_dim, max_seq, scale, window, stream,
+                                                  {(const uint8_t *)k_exp, (const uint8_t *)v_exp});
 }
 
 extern "C" int gq_attn_prefill_packed(const void *q, const void *k_cache, const void *v_cache, const int *seg_begin, void *out, uint32_t S,

@@ -226,7 +226,7 @@ class DecodeGraph:
         buffers) and max_seq_length; `setup_caches` with a longer length re-allocates all of them"""
         m = self.model
         sig = [m.max_seq_length, m.max_batch_size, m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), getattr(m, "kv_cache_dtype", "fp16")]
-        # (an fp8 cache's scale buffers are buffers of the layers: their pointers are in the list below; their VALUES are read by the
+        # (an fp8 cache's scale buffers and an fp8_row cache's exponent tensors are buffers of the layers: their pointers are in the list below; their VALUES are read by the
         # kernels at every replay)
         sig += [b.attention.kv_cache.k_cache.data_ptr() for b in m.layers]
         # the weight tensors the captured launches read (model.to() / .half() or an in-place re-pair after a sub-module
@@ -349,7 +349,7 @@ def decode_n_tokens(model: Transformer, cur_token: torch.Tensor, input_pos: torc
 @torch.no_grad()
 def generate(model: Transformer, prompt: torch.Tensor, max_new_tokens: int, batch_size: int = 1, callback=lambda x: x,
              use_graph=True, graph: Optional[DecodeGraph] = None, kv_cache_dtype=None, **sampling_kwargs) -> torch.Tensor:
-    """kv_cache_dtype: None / "fp16" / "fp8" (Transformer.setup_caches); a `graph` must have been captured over caches of that dtype"""
+    """kv_cache_dtype: None / "fp16" / "fp8" / "fp8_row" (Transformer.setup_caches); a `graph` must have been captured over caches of that dtype"""
     T = prompt.size(-1)
     T_new = T + max_new_tokens
     max_seq_length = min(T_new, model.config.block_size)
@@ -589,8 +589,9 @@ if __name__ == "__main__":
     parser.add_argument('--backend', type=str, default=None, choices=["ap", "lutgemm", "qtip", None])
     parser.add_argument('--print_result', action='store_true')
     parser.add_argument('--random_init', action='store_true')
-    parser.add_argument('--kv_cache_dtype', type=str, default=None, choices=["fp16", "fp8"],
-                        help='fp8: the KV cache as e4m3 codes, scale 1.0 per head (fused Any-Precision models; default fp16)')
+    parser.add_argument('--kv_cache_dtype', type=str, default=None, choices=["fp16", "fp8", "fp8_row"],
+                        help='fp8: the KV cache as e4m3 codes, scale 1.0 per head; fp8_row: e4m3 codes with an exponent byte per cached row, '
+                             'nothing to calibrate (fused Any-Precision models; default fp16)')
     parser.add_argument('--lm_head_dtype', type=str, default=None, choices=["fp16", "int8"],
                         help='int8: the decode step reads a weight-only int8 copy of the lm_head, one scale per row (default fp16)')
     parser.add_argument('--frequency_penalty', type=float, default=0.0,

@@ -182,10 +182,11 @@ FP8_MAX = 448.0  # the largest e4m3 magnitude
 
 
 def kv_cache_dtype_name(kv_cache_dtype) -> str:
-    """None / "fp16" -> "fp16" (the cache in the model's own dtype: the default), "fp8" -> "fp8" (OCP e4m3 codes + a scale per KV head)"""
+    """None / "fp16" -> "fp16" (the cache in the model's own dtype: the default), "fp8" -> "fp8" (OCP e4m3 codes + a scale per KV head),
+    "fp8_row" -> "fp8_row" (the same codes + one exponent byte per cached row and KV head: no scale to calibrate)"""
     name = "fp16" if kv_cache_dtype is None else str(kv_cache_dtype)
-    if name not in ("fp16", "fp8"):
-        raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r}: None, 'fp16' or 'fp8'")
+    if name not in ("fp16", "fp8", "fp8_row"):
+        raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r}: None, 'fp16' or 'fp8', or 'fp8_row'")
     return name
 
 
@@ -195,21 +196,51 @@ def fp8_quantize(x16: Tensor, inv: Tensor) -> Tensor:
     return (x16.float() * inv[:, None, None]).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
 
 
+FP8_ROW_EXP_ONE = 127  # the exponent byte of the scale 1.0 (e8m0: scale = 2^(byte - 127))
+
+
+def fp8_row_quantize(x16: Tensor):
+    """THE write rule of the per-row scaled fp8 cache (include/gq_hip.h), the host model of csrc/prefill.hip store_units_row, bit for bit.
+    x16 fp16 [.., head_dim]: every vector along the last dimension is one (row, KV head).  Returns (codes uint8 [.., head_dim],
+    exponent bytes uint8 [..]).  The exponent comes from the fp16 bits of the largest finite magnitude `a` by integer operations:
+        t = (a + 0xFF) >> 10           the exponent field, one more where the mantissa field exceeds 0x300 (448 = 1.75 * 2^8)
+        byte = clamp(t, 8, 30) + 104   e = byte - 127 = clamp(ceil(log2(amax / 448)), -15, 7); a == 0: e = -15
+        code = fp8_rne(clamp(float(x16) * 2^-e, -448, 448))    2^-e built from its bits, (254 - byte) << 23: the product is exact"""
+    assert x16.dtype == torch.float16
+    mag = x16.contiguous().view(torch.int16).to(torch.int32) & 0x7FFF
+    a = torch.where(mag < 0x7C00, mag, torch.zeros_like(mag)).amax(dim=-1)  # (Inf and NaN take no part)
+    byte = (((a + 0xFF) >> 10).clamp(8, 30) + 104)
+    inv = ((254 - byte) << 23).to(torch.int32).view(torch.float32)
+    codes = (x16.float() * inv[..., None]).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes, byte.to(torch.uint8)
+
+
+def fp8_row_scale(exp_byte: Tensor) -> Tensor:
+    """2^(byte - 127) as fp32, from its bits"""
+    return (exp_byte.to(torch.int32) << 23).view(torch.float32)
+
+
 class KVCache(nn.Module):
     """k_cache / v_cache [batch][n_kv_head][max_seq][head_dim] in `dtype`.  fp8=True: torch.float8_e4m3fn caches with four fp32
     [n_kv_head] buffers -- k_scale / v_scale (value = code * scale, default 1.0) and their reciprocals k_inv / v_inv, which the host
-    fills (`set_scales`: torch.reciprocal; no kernel divides).  `dtype` is then what `update` dequantises to."""
+    fills (`set_scales`: torch.reciprocal; no kernel divides).  `dtype` is then what `update` dequantises to.
+    fp8_row=True: the same caches of codes with k_exp / v_exp uint8 [batch][n_kv_head][max_seq] instead, one e8m0 exponent byte per
+    cached row and KV head (`fp8_row_quantize`); no scales."""
 
-    def __init__(self, max_batch_size, max_seq_length, n_heads, head_dim, dtype=torch.half, device=None, fp8=False):
+    def __init__(self, max_batch_size, max_seq_length, n_heads, head_dim, dtype=torch.half, device=None, fp8=False, fp8_row=False):
         super().__init__()
+        assert not (fp8 and fp8_row)
         cache_shape = (max_batch_size, n_heads, max_seq_length, head_dim)
-        self.fp8, self.out_dtype = bool(fp8), dtype
-        store = torch.float8_e4m3fn if fp8 else dtype
+        self.fp8, self.fp8_row, self.out_dtype = bool(fp8), bool(fp8_row), dtype
+        store = torch.float8_e4m3fn if fp8 or fp8_row else dtype
         self.register_buffer('k_cache', torch.zeros(cache_shape, dtype=store, device=device))
         self.register_buffer('v_cache', torch.zeros(cache_shape, dtype=store, device=device))
         if fp8:
             for name in ("k_scale", "v_scale", "k_inv", "v_inv"):
                 self.register_buffer(name, torch.ones(n_heads, dtype=torch.float32, device=device))
+        if fp8_row:
+            for name in ("k_exp", "v_exp"):
+                self.register_buffer(name, torch.full(cache_shape[:3], FP8_ROW_EXP_ONE, dtype=torch.uint8, device=device))
 
     def set_scales(self, k_scale, v_scale):
         """new scales IN PLACE (the kernels read them from device memory: a captured graph sees them at its next replay)"""
@@ -223,8 +254,18 @@ class KVCache(nn.Module):
         """the read rule: value = float(code) * scale, handed on in the model's dtype"""
         return (cache.float() * scale[:, None, None]).to(self.out_dtype)
 
+    def dequant_rows(self, cache, exp_byte):
+        """the read rule of the per-row form: value = fp16(code) * 2^(byte - 127), exact in fp16"""
+        return (cache.float() * fp8_row_scale(exp_byte)[..., None]).to(self.out_dtype)
+
     def update(self, input_pos, k_val, v_val):
         assert input_pos.shape[0] == k_val.shape[2]
+        if self.fp8_row:  # (as below: stored by the write rule, returned dequantised)
+            for cache, exp, val in ((self.k_cache, self.k_exp, k_val), (self.v_cache, self.v_exp, v_val)):
+                codes, byte = fp8_row_quantize(val.to(torch.float16))
+                cache.view(torch.uint8)[:, :, input_pos] = codes
+                exp[:, :, input_pos] = byte
+            return self.dequant_rows(self.k_cache, self.k_exp), self.dequant_rows(self.v_cache, self.v_exp)
         if self.fp8:  # stored by the write rule, returned dequantised: the module forward restates what the HIP route computes
             self.k_cache.view(torch.uint8)[:, :, input_pos] = fp8_quantize(k_val, self.k_inv)
             self.v_cache.view(torch.uint8)[:, :, input_pos] = fp8_quantize(v_val, self.v_inv)
@@ -485,7 +526,7 @@ class Transformer(nn.Module):
                    halve_layers=halve_layers, fuse_linears=fuse_linears)
 
     def kv8_unserved(self) -> Optional[str]:
-        """why the fused HIP route cannot serve this model with an fp8 KV cache (None: it can).  Host logic, no device needed."""
+        """why the fused HIP route cannot serve this model with an fp8 or fp8_row KV cache (None: it can).  Host logic, no device needed."""
         from .APLinear import APLinear
         if not self.fuse_linears:
             return "the model is not a fused-linear Any-Precision model"
@@ -498,14 +539,14 @@ class Transformer(nn.Module):
         return None
 
     def setup_caches(self, max_batch_size, max_seq_length, kv_cache_dtype=None):
-        """kv_cache_dtype: None / "fp16" (the default: caches in the model's dtype) or "fp8" (e4m3 codes, a scale per layer and KV head,
-        `set_kv_scales`; served by the fused Any-Precision route and the module forward).  A change of the dtype re-allocates the caches
-        even when their size suffices."""
+        """kv_cache_dtype: None / "fp16" (the default: caches in the model's dtype), "fp8" (e4m3 codes, a scale per layer and KV head,
+        `set_kv_scales`) or "fp8_row" (e4m3 codes, an exponent byte per cached row and KV head, nothing to set); both served by the fused
+        Any-Precision route and the module forward.  A change of the dtype re-allocates the caches even when their size suffices."""
         kv = kv_cache_dtype_name(kv_cache_dtype)
         if self.max_seq_length >= max_seq_length and self.max_batch_size >= max_batch_size and kv == self.kv_cache_dtype:
             return
-        if kv == "fp8" and not self.fuse_linears and type(self.layers[0].attention.wq).__name__ == "QuantizedLinear":
-            raise NotImplementedError("fp8 KV cache: QTIP models keep the fp16 cache (gq_attn_decode_qtip has no fp8 form)")
+        if kv != "fp16" and not self.fuse_linears and type(self.layers[0].attention.wq).__name__ == "QuantizedLinear":
+            raise NotImplementedError(f"{kv} KV cache: QTIP models keep the fp16 cache (gq_attn_decode_qtip has no fp8 form)")
         head_dim = self.config.head_dim
         max_seq_length = find_multiple(max_seq_length, 8)
         self.max_seq_length = max_seq_length
@@ -513,7 +554,8 @@ class Transformer(nn.Module):
         dtype = self.output.weight.dtype
         device = self.output.weight.device
         for b in self.layers:
-            b.attention.kv_cache = KVCache(max_batch_size, max_seq_length, self.config.n_local_heads, head_dim, dtype, device, fp8=(kv == "fp8"))
+            b.attention.kv_cache = KVCache(max_batch_size, max_seq_length, self.config.n_local_heads, head_dim, dtype, device, fp8=(kv == "fp8"),
+                                           fp8_row=(kv == "fp8_row"))
         self.kv_cache_dtype = kv
         # the [n, n] tables only for a cache of at most MASK_TABLE_MAX rows (tests and pipeline.py index them); above it every consumer
         # builds the rows it needs from the positions (mask_rows: the same bits)
@@ -534,6 +576,8 @@ class Transformer(nn.Module):
         """the scales of an fp8 cache, fp32 [n_layer][n_kv_head] each (value = code * scale; default 1.0), every entry finite and > 0.
         Written in place into the caches' buffers, reciprocals with them: no re-allocation, a captured decode graph needs no re-capture.
         Rows already in the caches keep their codes: set the scales before the prompt."""
+        if self.cache_initialized and self.kv_cache_dtype == "fp8_row":
+            raise ValueError("set_kv_scales: an fp8_row cache has no per-head scales (one exponent byte per cached row, written with the row)")
         if not (self.cache_initialized and self.kv_cache_dtype == "fp8"):
             raise ValueError("set_kv_scales: the caches are not fp8 (setup_caches(.., kv_cache_dtype='fp8') first)")
         shape = (len(self.layers), self.config.n_local_heads)

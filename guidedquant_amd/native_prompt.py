@@ -64,15 +64,15 @@ def _sdpa_gqa(q, k, v, mask, rep):
 
 
 # ------------------------------------------------------------------------------------------------ what a pass decides on the host
-def attention_plan(mode: str, n_pieces: int, kv8: bool, supported: bool) -> str:
+def attention_plan(mode: str, n_pieces: int, kv8: bool, supported: bool, row: bool = False) -> str:
     """the attention of every layer of a pass: "hip" (gq_attn_prefill) | "sdpa", on an fp8 cache "hip-kv8" (gq_attn_prefill_kv8) |
-    "sdpa-kv8" (SDPA on the dequantised rows).  mode = GQ_PREFILL_ATTN: "0" never the kernel, "1" the kernel wherever the library supports
-    the geometry, "auto" the kernel inside a chunked pass (a prompt of one piece launches what it always did) -- and for any number of
+    "sdpa-kv8" (SDPA on the dequantised rows), on a per-row scaled one (kv8 and row) "hip-kv8r" (gq_attn_prefill_kv8r) | "sdpa-kv8r".
+    mode = GQ_PREFILL_ATTN: "0" never the kernel, "1" the kernel wherever the library supports the geometry, "auto" the kernel inside a chunked pass (a prompt of one piece launches what it always did) -- and for any number of
     pieces on an fp8 cache"""
     if mode not in ("auto", "0", "1"):
         raise ValueError(f"GQ_PREFILL_ATTN={mode!r}: auto, 0 or 1")
     hip = mode != "0" and (mode == "1" or n_pieces > 1 or kv8) and supported
-    return ("hip" if hip else "sdpa") + ("-kv8" if kv8 else "")
+    return ("hip" if hip else "sdpa") + (("-kv8r" if row else "-kv8") if kv8 else "")
 
 
 def score_head_choice(mode: str, served: bool, auto: str) -> bool:
@@ -105,13 +105,14 @@ def prompt_pass(model, idx, input_pos, start: int, last_only: bool, chunk: Optio
     assert chunk >= 1, chunk
     pieces = prefill_chunks(S, chunk, start)
     mode = os.environ.get("GQ_PREFILL_ATTN", "auto")
-    kv8 = model.kv_cache_dtype == "fp8"
-    plan = attention_plan(mode, len(pieces), kv8, True)  # (the plan where the library serves the geometry; a bad mode raises here)
+    row = model.kv_cache_dtype == "fp8_row"
+    kv8 = row or model.kv_cache_dtype == "fp8"
+    plan = attention_plan(mode, len(pieces), kv8, True, row)  # (the plan where the library serves the geometry; a bad mode raises here)
     if kv8:
         assert model._native_kind() == "ap" and model.kv8_unserved() is None, model.kv8_unserved()
     needs_library = plan.startswith("hip")  # (mode and pieces want the kernel: only then does the library's answer decide, and is it asked)
     if needs_library and not L.gq_attn_prefill_supported(H, Hkv, hd):
-        plan = attention_plan(mode, len(pieces), kv8, False)
+        plan = attention_plan(mode, len(pieces), kv8, False, row)
     model.last_prefill_plan = dict(chunks=pieces, attn=[plan] * len(model.layers))
     dev = idx.device
     Sc = min(chunk, S)
@@ -180,11 +181,13 @@ class _Piece:
         m, cfg, L, kvc = self.m, self.m.config, _lib.lib(), att.kv_cache
         S, H, Hkv, hd = self.S, cfg.n_head, cfg.n_local_heads, cfg.head_dim
         kc, vc = kvc.k_cache, kvc.v_cache
-        kv8 = self.plan.endswith("-kv8")
+        kv8, kv8r = self.plan.endswith("-kv8"), self.plan.endswith("-kv8r")
         rows = (qkv.data_ptr(), self.pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), self.q.data_ptr(), kc.data_ptr(), vc.data_ptr())
         shape = (S, H, Hkv, hd, kc.shape[2])
         if kv8:
             entry, args = "gq_rope_cache_rows_kv8", (*rows, kvc.k_inv.data_ptr(), kvc.v_inv.data_ptr(), *shape, *native_step.qk_norm_args(att, cfg), None)
+        elif kv8r:  # (the same entry shape: the exponent tensors of batch slot 0 where the fp8 form takes its reciprocal scales)
+            entry, args = "gq_rope_cache_rows_kv8r", (*rows, kvc.k_exp.data_ptr(), kvc.v_exp.data_ptr(), *shape, *native_step.qk_norm_args(att, cfg), None)
         elif cfg.qk_norm:
             entry, args = "gq_qknorm_rope_cache_rows", (*rows, *shape, *native_step.qk_norm_args(att, cfg))
         else:
@@ -192,6 +195,8 @@ class _Piece:
         _lib.check(getattr(L, entry)(*args, st), entry)
         if self.plan.startswith("hip"):
             entry, scales = ("gq_attn_prefill_kv8", (kvc.k_scale.data_ptr(), kvc.v_scale.data_ptr())) if kv8 else ("gq_attn_prefill", ())
+            if kv8r:
+                entry, scales = "gq_attn_prefill_kv8r", (kvc.k_exp.data_ptr(), kvc.v_exp.data_ptr())
             _lib.check(getattr(L, entry)(self.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), *scales, self.y.data_ptr(), S, self.start, H, Hkv, hd, kc.shape[2],
                                          1.0 / math.sqrt(hd), 0 if win is None else int(win), st), entry)
             return self.y.view(1, S, H * hd)
@@ -199,6 +204,8 @@ class _Piece:
         k, v = kc[:1, :, :T], vc[:1, :, :T]
         if kv8:
             k, v = kvc.dequant(k, kvc.k_scale), kvc.dequant(v, kvc.v_scale)
+        elif kv8r:
+            k, v = kvc.dequant_rows(k, kvc.k_exp[:1, :, :T]), kvc.dequant_rows(v, kvc.v_exp[:1, :, :T])
         return _sdpa_gqa(self.q.unsqueeze(0), k, v, self.sdpa_mask(win), H // Hkv).transpose(1, 2).reshape(1, S, H * hd)
 
     def layers(self, x):
@@ -401,8 +408,8 @@ def score_packed(model, seqs, rows: Optional[Tensor] = None):
     piece of S = sum of their lengths rows -- never chunked -- with the scoring head on the rows `rows` (bool [S]; None: every row).
     Returns (logprob fp32 [k], hit bool [k]) over the head's rows in packed order: logprob of the next token of the row's own sequence
     and whether it is the most probable one; a sequence's last row has no next token (logprob 0, hit False)."""
-    if model.kv_cache_dtype == "fp8":
-        raise NotImplementedError("packed scoring: fp8 KV cache")
+    if model.kv_cache_dtype != "fp16":
+        raise NotImplementedError("packed scoring: %s KV cache" % model.kv_cache_dtype)
     if getattr(model, "adapter", None) is not None:
         raise NotImplementedError("lora: packed scoring is not served under an adapter (score the sequences one by one)")
     cfg = model.config

@@ -147,7 +147,9 @@ class StepState(_Keyed):
         # an fp8 KV cache (Transformer.setup_caches(.., kv_cache_dtype="fp8")): the rotated q of attend_kv8's two-launch route (a state
         # built under GQ_KV8_FOLD=1 does without; a step that finds the knob off again allocates it then)
         self.kv8 = getattr(model, "kv_cache_dtype", "fp16") == "fp8"
-        self.q8 = torch.zeros(c.n_head * c.head_dim, **f16) if self.kv8 and not kv8_fold() else None
+        # a per-row scaled fp8 cache (kv_cache_dtype="fp8_row"): always the two-launch route, attend_kv8r
+        self.kv8r = getattr(model, "kv_cache_dtype", "fp16") == "fp8_row"
+        self.q8 = torch.zeros(c.n_head * c.head_dim, **f16) if (self.kv8 and not kv8_fold()) or self.kv8r else None
 
     def kv(self, at, slot):
         """the K / V cache of batch slot `slot` of one attention module"""
@@ -190,6 +192,21 @@ class StepState(_Keyed):
         _lib.check(L.gq_attn_decode_roped_kv8(self.q8.data_ptr(), pos.data_ptr(), *kv, kvc.k_scale.data_ptr(), kvc.v_scale.data_ptr(), self.y.data_ptr(),
                                               c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, 1.0 / math.sqrt(c.head_dim),
                                               self.layer_split[layer], _ptr(self.attn_ws), self.layer_window[layer] or 0, sp), "gq_attn_decode_roped_kv8")
+
+    def attend_kv8r(self, at, pos, kv, sp, layer, slot):
+        """the per-row scaled fp8 cache's route of one layer, behind the plain wqkv GEMV -- attend_kv8's two launches with the exponent
+        tensors of the batch slot where it passes scales: gq_rope_cache_rows_kv8r (S = 1, the graph's position word; the layer's norm weights
+        or bias) rotates q, derives the exponents of the new k and v rows and writes codes and bytes, gq_attn_decode_roped_kv8r attends with
+        the layer's window and split plan.  One route for Llama, Mistral, Qwen2 and Qwen3."""
+        m, c, L, kvc = self.m, self.m.config, _lib.lib(), at.kv_cache
+        off = slot * c.n_local_heads * m.max_seq_length  # (one byte per KV head and row)
+        ex = kvc.k_exp.data_ptr() + off, kvc.v_exp.data_ptr() + off
+        _lib.check(L.gq_rope_cache_rows_kv8r(self.qkv.data_ptr(), pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), self.q8.data_ptr(), *kv, *ex,
+                                             1, c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, *qk_norm_args(at, c), _ptr(at.wqkv.bias), sp),
+                   "gq_rope_cache_rows_kv8r")
+        _lib.check(L.gq_attn_decode_roped_kv8r(self.q8.data_ptr(), pos.data_ptr(), *kv, *ex, self.y.data_ptr(), c.n_head, c.n_local_heads, c.head_dim,
+                                               m.max_seq_length, 1.0 / math.sqrt(c.head_dim), self.layer_split[layer], _ptr(self.attn_ws),
+                                               self.layer_window[layer] or 0, sp), "gq_attn_decode_roped_kv8r")
 
     def head(self, x):
         """the one call site of the dense GEMV (both families): final RMSNorm + lm_head -> the fp16 logits.  An int8-head model
@@ -243,8 +260,8 @@ class ApStep(StepState):
         from .model import pair_gate_up_rows_
         super().__init__(model)
         c = model.config
-        if self.kv8 and model.kv8_unserved():
-            raise ValueError("fp8 KV cache: " + model.kv8_unserved())
+        if (self.kv8 or self.kv8r) and model.kv8_unserved():
+            raise ValueError(model.kv_cache_dtype + " KV cache: " + model.kv8_unserved())
         self.adapter = getattr(model, "adapter", None)  # (Transformer.set_adapter: a LoraAdapter, or None)
         self.lora_layers = getattr(model, "adapter_layers", None)  # (its sites per layer as bound to THIS model: LoraAdapter.bind)
         # workspace of the down projection where the library splits its rows along K over blocks (K > 16384: 70B)
@@ -269,8 +286,8 @@ class ApStep(StepState):
         gq_lora_up writes -- the q | k | v delta (+ the checkpoint's bias) the attention launch adds, the residuals of wo and w2 with
         their delta.  The refusals: none of them falls back."""
         c, ad, dev = self.m.config, self.adapter, self.x.device
-        if self.kv8:
-            raise NotImplementedError("lora: the fp8 KV cache is not served under an adapter (setup_caches(.., kv_cache_dtype='fp16'))")
+        if self.kv8 or self.kv8r:
+            raise NotImplementedError("lora: the %s KV cache is not served under an adapter (setup_caches(.., kv_cache_dtype='fp16'))" % self.m.kv_cache_dtype)
         if c.qk_norm and ad.targets("qkv"):
             raise ValueError("lora: q / k / v targets on a QK-norm model (Qwen3): no attention launch has both the norm and a bias; "
                              "o_proj / down_proj targets are served")
@@ -331,6 +348,9 @@ class ApStep(StepState):
             elif self.kv8:
                 launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
                 self.attend_kv8(at, pos, kv, sp, l0 + li)
+            elif self.kv8r:
+                launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
+                self.attend_kv8r(at, pos, kv, sp, l0 + li, slot)
             elif c.qk_norm:
                 # Qwen3: q and k are normalised per head BEFORE the rotation, so the wqkv launch must not rotate (its RoPE epilogue holds a
                 # head's rows in eight 16-row groups: no per-head statistic there) -- plain wqkv GEMV, then ONE attention launch that
@@ -621,8 +641,8 @@ class QtipStep(StepState):
         super().__init__(model)
         if getattr(model, "adapter", None) is not None:
             raise NotImplementedError("lora: QTIP models are not served under an adapter")
-        if self.kv8:
-            raise NotImplementedError("fp8 KV cache: QTIP models keep the fp16 cache (gq_attn_decode_qtip has no fp8 form)")
+        if self.kv8 or self.kv8r:
+            raise NotImplementedError(model.kv_cache_dtype + " KV cache: QTIP models keep the fp16 cache (gq_attn_decode_qtip has no fp8 form)")
         c, dev = model.config, self.x.device
         self.g = torch.zeros(c.intermediate_size, dtype=torch.float16, device=dev)
         self.u = torch.zeros(c.intermediate_size, dtype=torch.float16, device=dev)

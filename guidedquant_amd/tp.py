@@ -37,8 +37,9 @@ class TensorParallelDecoder:
 
     def __init__(self, model: Transformer, group, rank: int, world: int, max_new_tokens: int, temperature=0.0, top_k=32, seed=1234, bos_id=1):
         c = model.config
-        if getattr(model, "kv_cache_dtype", "fp16") == "fp8":  # (this class launches attention itself, over fp16 caches)
-            raise NotImplementedError("fp8 KV cache: tensor-parallel decode has no fp8 form (setup_caches(.., kv_cache_dtype='fp16'))")
+        kv = getattr(model, "kv_cache_dtype", "fp16")
+        if kv != "fp16":  # (this class launches attention itself, over fp16 caches)
+            raise NotImplementedError(f"{kv} KV cache: tensor-parallel decode has no fp8 form (setup_caches(.., kv_cache_dtype='fp16'))")
         if getattr(model, "adapter", None) is not None:  # (this class launches its slices of the linears itself: no LoRA side launches)
             raise NotImplementedError("lora: tensor-parallel decode is not served under an adapter (set_adapter(None))")
         if getattr(model, "lm_head_dtype", "fp16") == "int8":  # (this class launches its vocabulary slice of the fp16 head itself)

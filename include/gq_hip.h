@@ -273,6 +273,40 @@ int gq_attn_prefill_kv8(const void *q, const void *k_cache, const void *v_cache,
                         uint32_t window, void *stream);
 
 /*
+ * The per-row scaled fp8 KV cache (kv_cache_dtype="fp8_row"): the e4m3 codes of the fp8 cache, [n_kv_head][max_seq][head_dim] per batch
+ * slot, and ONE exponent byte per (KV head, cached row) for K and for V, uint8 [n_kv_head][max_seq] per batch slot, in e8m0: the row's
+ * scale is 2^(byte - 127).  No per-head scale and nothing to calibrate: every row's largest finite magnitude sits at the top of the e4m3
+ * range.
+ *   write rule  for the head_dim fp16 values x16 of one (row, KV head) -- what the fp16 path would have stored:
+ *               a    = the largest |x16| over the finite elements, as its fp16 bit pattern (0: none, or all zero)
+ *               byte = clamp((a + 0xFF) >> 10, 8, 30) + 104,  e = byte - 127 = clamp(ceil(log2(amax / 448)), -15, 7)
+ *                      (448 = 1.75 * 2^8: the fp16 exponent field, one more where the mantissa field exceeds 0x300; integer arithmetic)
+ *               code = fp8_rne(clamp(float(x16) * 2^-e, -448, 448)).  +-Inf clamps to +-448, a NaN stores a NaN code.  Magnitudes
+ *               above 448 * 2^7 = 57344 (e would be 8) saturate at 57344; below 2^-15 * 448 every row uses e = -15, where the smallest code
+ *               is 2^-24, fp16's own.
+ *   read rule   value = fp16(code) * 2^e: an fp16 value for every code and every e in [-15, 7], so the product is exact and is applied
+ *               where the codes are unpacked, in front of every product.  The results equal, bit for bit, those of the fp16 entries on
+ *               an fp16 cache that holds code * 2^e.
+ * gq_rope_cache_rows_kv8r: gq_rope_cache_rows_kv8 with the exponent tensors in place of the reciprocal scales (the same norm and bias
+ *   forms, head_dims, checks; q_out bit for bit the fp16 entries').  Writes head_dim codes and one byte per (written row, KV head) into
+ *   each cache; positions >= max_seq write nothing.  k_exp / v_exp need no alignment.
+ * gq_attn_decode_roped_kv8r: gq_attn_decode_roped_kv8 with the exponent tensors in place of the scales; a row's byte is requested with
+ *   the row.  Geometry, solo rule, stream assignment, merge order and the combine launch are unchanged.
+ * gq_attn_prefill_kv8r: gq_attn_prefill_kv8 likewise; a tile's exponent bytes are loaded with the tile and multiply between the global
+ *   load and the LDS store.  Rows [0, start + S) hold bytes the write rule produced.
+ */
+int gq_rope_cache_rows_kv8r(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
+                            void *v_cache, void *k_exp, void *v_exp, uint32_t S, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim,
+                            uint32_t max_seq, const void *q_norm_weight, const void *k_norm_weight, float eps, const void *qkv_bias,
+                            void *stream);
+int gq_attn_decode_roped_kv8r(const void *q, const int *pos, const void *k_cache, const void *v_cache, const void *k_exp, const void *v_exp,
+                              void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale,
+                              uint32_t n_split, float *workspace, uint32_t window, void *stream);
+int gq_attn_prefill_kv8r(const void *q, const void *k_cache, const void *v_cache, const void *k_exp, const void *v_exp, void *out, uint32_t S,
+                         uint32_t start, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale,
+                         uint32_t window, void *stream);
+
+/*
  * The scoring head of the prompt pass: per-token log-probabilities without the logits (csrc/head_nll.hip).  What the reference's
  * perplexity loop computes with the module tree and `labels=` (any_precision/evaluate/eval.py:205-226: lm_head logits [1, S, V] in
  * fp16, HF's loss upcasts them to fp32 and takes the cross entropy) from the rows behind the final RMSNorm, in one pass over the
