@@ -467,8 +467,8 @@ class AnyPrecisionForCausalLM(nn.Module):
             self.set_precision(kwargs.pop('precision'))
         native = kwargs.pop('native', None)
         capture = kwargs.pop('capture', None)
-        # kv_cache_dtype="fp8" / "fp8_row": the KV cache of the fused decode model as e4m3 codes with a scale per head / an exponent byte per
-        # cached row (Transformer.setup_caches).  Served by route 1 only;
+        # kv_cache_dtype="fp8" / "fp8_row" / "mxfp4": the KV cache of the fused decode model as e4m3 codes with a scale per head / an exponent
+        # byte per cached row, or as e2m1 codes with an exponent byte per block of 32 elements (Transformer.setup_caches).  Served by route 1 only;
         # a request it cannot serve raises -- it never falls back to an fp16 cache silently.  (popped: it never reaches transformers)
         from .model import kv_cache_dtype_name
         kv = kv_cache_dtype_name(kwargs.pop('kv_cache_dtype', None))
@@ -627,7 +627,7 @@ class AnyPrecisionForCausalLM(nn.Module):
         Routing follows `generate`: the fused decode model's HIP prompt pass with the scoring head (`Transformer.score_native`: no
         [T, V] logits in memory) when the checkpoint has one at this precision and T fits its context, else the module tree's forward
         and the same formula in torch.  native=False opts out, native=True raises instead of falling back, and
-        kv_cache_dtype="fp8" / "fp8_row" (the fused model's e4m3 caches) never falls back silently.  Ids outside [0, vocab) raise ValueError before
+        kv_cache_dtype="fp8" / "fp8_row" / "mxfp4" (the fused model's e4m3 and e2m1 caches) never falls back silently.  Ids outside [0, vocab) raise ValueError before
         anything is launched.
         top_logprobs=n, 1..20 (anything else but None: ValueError): the dict gains `top_logprobs_ids` int64 [T - 1, n] -- the n most
         probable tokens of the distribution logprobs[i] was taken from, most probable first, equal logits by ascending id, -1 where the

@@ -37,6 +37,7 @@ EXPORTS = [
     "gq_lora_n_partials", "gq_lora_down", "gq_lora_up",
     "gq_head_nll_topn_ws_bytes", "gq_head_nll_topn",
     "gq_rope_cache_rows_kv8r", "gq_attn_decode_roped_kv8r", "gq_attn_prefill_kv8r",
+    "gq_rope_cache_rows_mx4", "gq_attn_decode_roped_mx4", "gq_attn_prefill_mx4",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -204,6 +205,10 @@ def lib():
         L.gq_rope_cache_rows_kv8r.argtypes = L.gq_rope_cache_rows_kv8.argtypes
         L.gq_attn_decode_roped_kv8r.argtypes = L.gq_attn_decode_roped_kv8.argtypes
         L.gq_attn_prefill_kv8r.argtypes = L.gq_attn_prefill_kv8.argtypes
+        # (the MXFP4 cache forms: codes two per byte, the exponent tensors uint8 [n_kv_head][max_seq][head_dim / 32])
+        L.gq_rope_cache_rows_mx4.argtypes = L.gq_rope_cache_rows_kv8.argtypes
+        L.gq_attn_decode_roped_mx4.argtypes = L.gq_attn_decode_roped_kv8.argtypes
+        L.gq_attn_prefill_mx4.argtypes = L.gq_attn_prefill_kv8.argtypes
         # (the packed pass: seg_begin behind the caches and no start; pos, row in front of the tables)
         L.gq_attn_prefill_packed.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, f32, u32, vp]
         L.gq_rope_cache_rows_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, f32, vp]

@@ -159,8 +159,48 @@ template <bool ROW>
 struct AttnRowExp {};
 template <>
 struct AttnRowExp<true> {
-    const uint8_t *k_exp, *v_exp;  // uint8 [n_kv_head][max_seq] of the batch slot
+    const uint8_t *k_exp, *v_exp;  // uint8 [n_kv_head][max_seq] of the batch slot ([n_kv_head][max_seq][head_dim / 32]: the MXFP4 form)
 };
+// ------------------------------------------------------------------------------------------------ the MXFP4 cache
+// kv_cache_dtype="mxfp4" (OCP microscaling): e2m1 codes, two per byte (element 2j in the low nibble of byte j), uint8
+// [n_kv_head][max_seq][head_dim / 2], and ONE e8m0 exponent byte per block of 32 consecutive elements of a head's row, uint8
+// [n_kv_head][max_seq][head_dim / 32]: value = e2m1(code) * 2^(byte - 127), magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6.  The scale of the
+// per-row fp8 form moved from the row to the block.  THE exponent rule, on a = the largest fp16 magnitude bits of the block's 32 values:
+//   t = (a + 0x1FF) >> 10     the fp16 exponent field, one more where the mantissa field exceeds 0x200: 6 = 1.5 * 2^2, so that
+//                             t - 17 = ceil(log2(amax / 6)) for every normal amax
+//   field = clamp(t, 2, 30) + 110     e = field - 127 in [-15, 13]: code * 2^e stays an fp16 value (0.5 * 2^-15 = 2^-16; 6 * 2^13 = 49152)
+//   byte = 0xFF where a >= 0x7C00 (the block holds an Inf or a NaN: every element of it reads back NaN), else field
+// The codes are taken at 2^-(field - 127) in both cases (a non-finite block: e = 13, its non-finite elements saturate to +-6).
+__device__ __forceinline__ u32 mx4_exp_field(u32 amax_bits) { return min(max((amax_bits + 0x1FFu) >> 10, 2u), 30u) + 110u; }
+__device__ __forceinline__ u32 mx4_exp_byte(u32 amax_bits) { return amax_bits >= 0x7C00u ? 0xFFu : mx4_exp_field(amax_bits); }
+// one e2m1 code (sign in bit 3) of the fp16 value h at the scale inv = 2^-e, round to nearest, ties to the even mantissa: y = |h| * inv
+// is exact in fp32.  y < 1 (the codes 0, 0.5, 1: a grid of 0.5): the fp32 addition y + 2^22 rounds to that grid, ties to even, and leaves
+// the code in its two low bits.  y >= 1: one mantissa bit is kept -- the fp32 bits rounded to bit 22, ties to even, make (exponent, bit)
+// = code + 252; anything from 7 on (above 6, Inf, NaN) saturates to the code of 6.
+__device__ __forceinline__ u32 mx4_code(uint16_t h, float inv) {
+    const float y = gqw::h2f((uint16_t)(h & 0x7FFFu)) * inv;
+    const u32 b = __builtin_bit_cast(u32, y);
+    const u32 sub = __builtin_bit_cast(u32, y + 4194304.0f) & 3u;
+    const u32 nrm = min(((b + 0x1FFFFFu + ((b >> 22) & 1u)) >> 22) - 252u, 7u);
+    return (y < 1.0f ? sub : nrm) | (((u32)h >> 12) & 8u);
+}
+// 8 fp16 values (4 words) -> 8 codes in one word, element k in nibble k
+__device__ __forceinline__ u32 mx4_quant8(const u32 (&w)[4], float inv) {
+    u32 o = 0u;
+#pragma unroll
+    for (int k = 0; k < 8; k++) o |= mx4_code((uint16_t)(w[k >> 1] >> (16 * (k & 1))), inv) << (4 * k);
+    return o;
+}
+// the read rule: 2^e of a block as fp32, NaN for the byte 0xFF; 4 bytes of codes -> 8 values by v_cvt_scalef32_pk_f32_fp4 at the scale
+// 1.0 (the e2m1 magnitudes, exact), times 2^e: every product is an fp16 value, so from here on the floats are those unpack8 gives for an
+// fp16 row that holds code * 2^e -- and a NaN scale makes all 8 NaN, zero codes included
+__device__ __forceinline__ float mx4_scale(u32 byte) { return byte == 0xFFu ? __builtin_nanf("") : __builtin_bit_cast(float, byte << 23); }
+__device__ __forceinline__ void unpack8_mx4(u32 row, float sc, float (&f)[8]) {
+    const auto p0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(row, 1.0f, 0), p1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(row, 1.0f, 1);
+    const auto p2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(row, 1.0f, 2), p3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(row, 1.0f, 3);
+    f[0] = p0[0] * sc, f[1] = p0[1] * sc, f[2] = p1[0] * sc, f[3] = p1[1] * sc;
+    f[4] = p2[0] * sc, f[5] = p2[1] * sc, f[6] = p3[0] * sc, f[7] = p3[1] * sc;
+}
 
 // the online softmax of one stream over a batch of U rows (scores pu, -3e38 = no row; V rows vfu): the rows share ONE rescale of the
 // running (max, sum, weighted V) -- one exp for the old maximum and one per row

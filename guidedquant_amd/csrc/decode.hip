@@ -8,6 +8,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "gq_internal.h"
 #include "attn_core.h"
 #include "dense_stage.h"
@@ -374,14 +376,25 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
 // row -- the lanes that share the row ask for the same byte, in the speculative batch and in every later one, so that no round trip is
 // added to a launch that waits on memory -- and 2^e multiplies the 8 unpacked values in front of every product: exact, so from there on
 // the floats are those of the fp16 instance over a cache that holds code * 2^e.  No per-head scale is read.
-template <int HD, int QH, bool WIN = false, bool KV8 = false, bool ROW = false>
+// MX4 (with ROW; gq_attn_decode_roped_mx4): the MXFP4 caches of attn_core.h, the per-row form with the scale moved to the block of 32
+// elements.  A lane's 8 elements of a row are one 4-byte load of e2m1 codes; they lie in ONE block (lane ld: block ld / 4), whose exponent
+// byte the lane requests directly, with the row, in the batches the ROW form requests its row byte in.  unpack8_mx4 applies 2^e where the
+// fp8 forms unpack.  The lane-to-element map, hence every sum and its order, is the fp16 instance's.
+template <int HD, int QH, bool WIN = false, bool KV8 = false, bool ROW = false, bool MX4 = false>
 __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint16_t *q, const int *pos_ptr, const typename gq_attn::CacheFmt<KV8>::elem *kc,
                                                                      const typename gq_attn::CacheFmt<KV8>::elem *vc, uint16_t *out, u32 H, u32 Hkv,
                                                                      u32 max_seq, float scale, u32 nsplit, float *ws, AttnWindow<WIN> wn,
                                                                      gq_attn::AttnKv8<KV8 && !ROW> k8, gq_attn::AttnRowExp<ROW> rx) {
     static_assert(!ROW || KV8, "the per-row scaled form is a form of the fp8 caches");
+    static_assert(!MX4 || ROW, "the MXFP4 form is the per-row scaled form with the exponent per block");
     using Fmt = gq_attn::CacheFmt<KV8>;
-    using Row = typename Fmt::row;
+    using Row = typename std::conditional<MX4, u32, typename Fmt::row>::type;
+    constexpr u32 RE = MX4 ? HD / 2 : HD, LE = MX4 ? 4 : 8;  // cache elements of a row, of a lane's 8 dims
+    constexpr u32 XR = MX4 ? HD / 32 : 1;                    // exponent bytes of a row
+    const auto row_zero = [] {
+        if constexpr (MX4) return 0u;
+        else return Fmt::zero();
+    };
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     using Geo = AttnGeom<HD>;
     using L = gq_attn::RopedLds<HD, QH>;
@@ -399,7 +412,7 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
     const u32 h0 = blockIdx.x * QH, g = kv_group_of(h0, H, Hkv), sp = blockIdx.y;
 #endif
     const u32 sub = l / LPP, ld = l % LPP;
-    const typename Fmt::elem *kcg = kc + (size_t)g * max_seq * HD, *vcg = vc + (size_t)g * max_seq * HD;
+    const typename Fmt::elem *kcg = kc + (size_t)g * max_seq * RE, *vcg = vc + (size_t)g * max_seq * RE;
     // requests that do not depend on the position: q, and (blocks that may start at row 0) the first batch of cached rows
     uint4 q4[QH];
 #pragma unroll
@@ -408,7 +421,8 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
     constexpr int UE = ROW ? U : 1;  // (the exponent bytes of the rows in flight: ROW only)
     u32 ke[UE], ve[UE];
     const uint8_t *keg = nullptr, *veg = nullptr;
-    if constexpr (ROW) keg = rx.k_exp + (size_t)g * max_seq, veg = rx.v_exp + (size_t)g * max_seq;
+    if constexpr (ROW) keg = rx.k_exp + (size_t)g * max_seq * XR, veg = rx.v_exp + (size_t)g * max_seq * XR;
+    if constexpr (MX4) keg += ld / 4u, veg += ld / 4u;  // (the lane's block)
     u32 t0 = w * PPW * U;
 #pragma unroll
     for (int u = 0; u < U; u++) {
@@ -416,9 +430,9 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         // (only the first GQ_ATTN_SPEC rows: every row requested ahead of the position is HBM traffic whether it is needed or not --
         // 128 rows x 32 heads = 2 MiB per layer, which costs what the saved round trip gains)
         const bool in = sp < (u32)QH && t < max_seq && t < (u32)GQ_ATTN_SPEC;
-        kv[u] = in ? *reinterpret_cast<const Row *>(kcg + (size_t)t * HD + ld * 8) : Fmt::zero();
-        vv[u] = in ? *reinterpret_cast<const Row *>(vcg + (size_t)t * HD + ld * 8) : Fmt::zero();
-        if constexpr (ROW) ke[u] = in ? (u32)keg[t] : 127u, ve[u] = in ? (u32)veg[t] : 127u;
+        kv[u] = in ? *reinterpret_cast<const Row *>(kcg + (size_t)t * RE + ld * LE) : row_zero();
+        vv[u] = in ? *reinterpret_cast<const Row *>(vcg + (size_t)t * RE + ld * LE) : row_zero();
+        if constexpr (ROW) ke[u] = in ? (u32)keg[(size_t)t * XR] : 127u, ve[u] = in ? (u32)veg[(size_t)t * XR] : 127u;
     }
     if constexpr (KV8 && !ROW) scale *= k8.k_scale[g];  // (block-uniform: one scalar load next to the position's)
     const u32 pos = (u32)pos_ptr[0];
@@ -460,9 +474,9 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         for (int u = 0; u < U; u++) {
             const u32 t = tb + (u32)u * PPW + sub;
             const bool in = t < p1;
-            kd[u] = in ? *reinterpret_cast<const Row *>(kcg + (size_t)t * HD + ld * 8) : Fmt::zero();
-            vd[u] = in ? *reinterpret_cast<const Row *>(vcg + (size_t)t * HD + ld * 8) : Fmt::zero();
-            if constexpr (ROW) ked[u] = in ? (u32)keg[t] : 127u, ved[u] = in ? (u32)veg[t] : 127u;
+            kd[u] = in ? *reinterpret_cast<const Row *>(kcg + (size_t)t * RE + ld * LE) : row_zero();
+            vd[u] = in ? *reinterpret_cast<const Row *>(vcg + (size_t)t * RE + ld * LE) : row_zero();
+            if constexpr (ROW) ked[u] = in ? (u32)keg[(size_t)t * XR] : 127u, ved[u] = in ? (u32)veg[(size_t)t * XR] : 127u;
         }
     };
     t0 = p0 + w * PPW * U;
@@ -479,8 +493,14 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
             const u32 t = t0 + (u32)u * PPW + sub;
             const bool valid = t < p1;
             float kf[8];
-            Fmt::unpack(kv[u], kf);
-            if constexpr (ROW) {  // (the read rule: fp16(code) * 2^e, exact; a stale row's byte may be anything -- replaced below like its codes)
+            if constexpr (!MX4) Fmt::unpack(kv[u], kf);
+            if constexpr (MX4) {  // (the read rule of the block: e2m1(code) * 2^e, exact, NaN for the byte 0xFF; stale rows as below)
+                float vf[8];
+                gq_attn::unpack8_mx4(kv[u], gq_attn::mx4_scale(ke[u]), kf);
+                gq_attn::unpack8_mx4(vv[u], gq_attn::mx4_scale(ve[u]), vf);
+#pragma unroll
+                for (int e = 0; e < 8; e++) vfu[u][e] = valid ? vf[e] : 0.f;
+            } else if constexpr (ROW) {  // (the read rule: fp16(code) * 2^e, exact; a stale row's byte may be anything -- replaced below like its codes)
                 const float sk = gq_attn::row_exp_scale(ke[u]), sv = gq_attn::row_exp_scale(ve[u]);
                 float vf[8];
                 Fmt::unpack(vv[u], vf);
@@ -820,7 +840,7 @@ extern "C" int gq_attn_decode_qtip(const GqQtipOut *qkv_lin, const int *pos, con
 // Attention of the decode step when the wqkv launch has already rotated q / k and written k / v of the current token into the
 // caches (gq_anyprec_gemv_qkv_rope): q fp16 [n_head * head_dim] rotated; the caches hold every position <= *pos.
 namespace {
-template <bool WIN, bool KV8 = false, bool ROW = false>
+template <bool WIN, bool KV8 = false, bool ROW = false, bool MX4 = false>
 int roped_launch(const void *q, const int *pos, const void *k_cache, const void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head,
                  uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream,
                  const float *k_scale = nullptr, const float *v_scale = nullptr, const void *k_exp = nullptr, const void *v_exp = nullptr) {
@@ -844,8 +864,8 @@ int roped_launch(const void *q, const int *pos, const void *k_cache, const void 
     const dim3 grid(n_head / qh, gqa_p ? copies : n_split);
     if (gqa_p && !WIN) {
         static GqPerDeviceOnce once;
-        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<128, 4, false, KV8, ROW>), 160 * 1024));
-        hipLaunchKernelGGL((attn_roped_kernel<128, 4, false, KV8, ROW>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<128, 4>::bytes()), s, (const uint16_t *)q, pos,
+        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<128, 4, false, KV8, ROW, MX4>), 160 * 1024));
+        hipLaunchKernelGGL((attn_roped_kernel<128, 4, false, KV8, ROW, MX4>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<128, 4>::bytes()), s, (const uint16_t *)q, pos,
                            (const CE *)k_cache, (const CE *)v_cache, (uint16_t *)out, n_head, n_kv_head, max_seq, scale, 1u, workspace,
                            AttnWindow<false>{}, k8, rx);
         GQ_HIP_CHECK(hipGetLastError());
@@ -858,8 +878,8 @@ int roped_launch(const void *q, const int *pos, const void *k_cache, const void 
 #define GQ_LAUNCH_ROPED(HD_, QH_)                                                                                                    \
     do {                                                                                                                             \
         static GqPerDeviceOnce once;                                                                                                 \
-        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<HD_, QH_, WIN, KV8, ROW>), 160 * 1024));   \
-        hipLaunchKernelGGL((attn_roped_kernel<HD_, QH_, WIN, KV8, ROW>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<HD_, QH_>::bytes()), s, \
+        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<HD_, QH_, WIN, KV8, ROW, MX4>), 160 * 1024));   \
+        hipLaunchKernelGGL((attn_roped_kernel<HD_, QH_, WIN, KV8, ROW, MX4>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<HD_, QH_>::bytes()), s, \
                            (const uint16_t *)q, pos, (const CE *)k_cache, (const CE *)v_cache, (uint16_t *)out, n_head,               \
                            n_kv_head, max_seq, scale, n_split, workspace, wn, k8, rx);                                               \
         if (n_split > 1u)                                                                                                            \
@@ -912,6 +932,18 @@ extern "C" int gq_attn_decode_roped_kv8r(const void *q, const int *pos, const vo
                                               nullptr, nullptr, k_exp, v_exp);
     return roped_launch<false, true, true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, 0u, stream,
                                            nullptr, nullptr, k_exp, v_exp);
+}
+
+// the MXFP4 cache form (csrc/attn_core.h): the same launches over caches of e2m1 codes, two per byte, with one exponent byte per (KV head,
+// row, block of 32 elements), k_exp / v_exp uint8 [n_kv_head][max_seq][head_dim / 32] of the batch slot; window 0: the whole context
+extern "C" int gq_attn_decode_roped_mx4(const void *q, const int *pos, const void *k_cache, const void *v_cache, const void *k_exp,
+                                        const void *v_exp, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
+                                        float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream) {
+    if (window)
+        return roped_launch<true, true, true, true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, window,
+                                                    stream, nullptr, nullptr, k_exp, v_exp);
+    return roped_launch<false, true, true, true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, 0u, stream,
+                                                 nullptr, nullptr, k_exp, v_exp);
 }
 
 // what attn_kv8.hip (gq_attn_decode_split_kv8: the fp8-cache form of the gq_attn_decode_split family, a translation unit of its own)

@@ -165,6 +165,28 @@ __device__ __forceinline__ void store_units_row(uint8_t *dst, uint8_t *exp_byte,
     store_units(dst, d, HD, w1, w2, gq_attn::row_exp_inv(byte));
 }
 
+// the MXFP4 cache (attn_core.h): a block of 32 consecutive elements is the FIRST units of the 4 threads of an aligned quad (d = 0, 8, 16, 24
+// mod 32) or their SECOND units (the same, HD / 2 further on), so a thread takes part in two blocks.  The largest magnitude bits of each
+// -- this thread's 8, then the quad by two DPP steps (group_umax), no LDS round trip -- give the block's exponent by integer arithmetic;
+// each unit's 8 codes (mx4_quant8 at 2^-e) are ONE 32-bit store into the row `dst` of HD / 2 bytes, and the quad's first thread stores the
+// two exponent bytes (byte stores of the vector unit) into the row `exp_row` of HD / 32 bytes.  The lanes of a quad are active together.
+__device__ __forceinline__ void store_units_mx4(uint8_t *dst, uint8_t *exp_row, u32 d, u32 HD, const u32 (&w1)[4], const u32 (&w2)[4]) {
+    u32 a1 = 0u, a2 = 0u;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        a1 = max(a1, (w1[k >> 1] >> (16 * (k & 1))) & 0x7FFFu);
+        a2 = max(a2, (w2[k >> 1] >> (16 * (k & 1))) & 0x7FFFu);
+    }
+    a1 = gq_attn::group_umax(a1, false);
+    a2 = gq_attn::group_umax(a2, false);
+    if ((d & 31u) == 0u) {
+        exp_row[d / 32u] = (uint8_t)gq_attn::mx4_exp_byte(a1);
+        exp_row[(d + HD / 2u) / 32u] = (uint8_t)gq_attn::mx4_exp_byte(a2);
+    }
+    *reinterpret_cast<u32 *>(dst + d / 2u) = gq_attn::mx4_quant8(w1, gq_attn::row_exp_inv(gq_attn::mx4_exp_field(a1)));
+    *reinterpret_cast<u32 *>(dst + (d + HD / 2u) / 2u) = gq_attn::mx4_quant8(w2, gq_attn::row_exp_inv(gq_attn::mx4_exp_field(a2)));
+}
+
 template <bool KV8>
 struct CacheElem {
     typedef uint16_t type;
@@ -190,6 +212,8 @@ struct CacheElem<true> {
 // The loop bound is block-uniform in every form (QKN needs it: whole groups are active or idle together, total is a multiple of HD / 16).
 // K8R (gq_rope_cache_rows_kv8r, with KV8): the per-row scaled fp8 caches -- k and v through store_units_row, their exponent bytes to
 //   tail.k_exp / tail.v_exp [Hkv][max_seq]; k_inv / v_inv are not read.
+// MX4 (gq_rope_cache_rows_mx4, with K8R): the MXFP4 caches -- k and v through store_units_mx4 into rows of HD / 2 bytes, the exponent
+//   bytes to tail.k_exp / tail.v_exp [Hkv][max_seq][HD / 32].
 template <bool PKD, bool K8R = false>
 struct RowsTail {};
 template <>
@@ -201,7 +225,7 @@ struct RowsTail<false, true> {
     uint8_t *k_exp, *v_exp;
 };
 
-template <bool QKN, bool QB, bool KV8, bool PKD = false, bool K8R = false>
+template <bool QKN, bool QB, bool KV8, bool PKD = false, bool K8R = false, bool MX4 = false>
 __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__restrict__ qkv, const int *__restrict__ pos,
                                                               const uint16_t *__restrict__ cos_t, const uint16_t *__restrict__ sin_t,
                                                               uint16_t *__restrict__ q_out, typename CacheElem<KV8>::type *__restrict__ kc,
@@ -210,6 +234,7 @@ __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__
                                                               const uint16_t *__restrict__ knw, float eps, const uint16_t *__restrict__ bias, u32 S,
                                                               u32 H, u32 Hkv, u32 HD, u32 max_seq, RowsTail<PKD, K8R> tail) {
     static_assert(!K8R || (KV8 && !PKD), "the per-row scaled form is a form of the fp8 caches");
+    static_assert(!MX4 || K8R, "the MXFP4 form is the per-row scaled form with the exponent per block");
     const u32 upr = HD / 16u, heads = H + 2u * Hkv, total = S * heads * upr;  // units of 8 in the first half
     for (u32 base = blockIdx.x * 256u; base < total; base += gridDim.x * 256u) {
         const u32 i = base + threadIdx.x;
@@ -258,7 +283,9 @@ __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__
         if (hh >= H + Hkv) {  // v: stored as it is
             if (cr < max_seq) {
                 const u32 g = hh - H - Hkv;
-                if constexpr (K8R) {
+                if constexpr (MX4) {
+                    store_units_mx4(vc + ((size_t)g * max_seq + cr) * (HD / 2u), tail.v_exp + ((size_t)g * max_seq + cr) * (HD / 32u), d, HD, x1, x2);
+                } else if constexpr (K8R) {
                     store_units_row(vc + ((size_t)g * max_seq + cr) * HD, tail.v_exp + (size_t)g * max_seq + cr, d, HD, x1, x2);
                 } else {
                     float inv = 0.f;
@@ -295,7 +322,9 @@ __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__
             store_units(q_out + ((size_t)hh * S + s) * HD, d, HD, o1, o2, 0.f);
         } else if (cr < max_seq) {
             const u32 g = hh - H;
-            if constexpr (K8R) {
+            if constexpr (MX4) {
+                store_units_mx4(kc + ((size_t)g * max_seq + cr) * (HD / 2u), tail.k_exp + ((size_t)g * max_seq + cr) * (HD / 32u), d, HD, o1, o2);
+            } else if constexpr (K8R) {
                 store_units_row(kc + ((size_t)g * max_seq + cr) * HD, tail.k_exp + (size_t)g * max_seq + cr, d, HD, o1, o2);
             } else {
                 float inv = 0.f;
@@ -355,7 +384,7 @@ struct RowsEntry {
 int rope_cache_rows(const RowsEntry &e, bool kv8, const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
                     void *v_cache, const float *k_inv, const float *v_inv, u32 S, u32 n_head, u32 n_kv_head, u32 head_dim, u32 max_seq,
                     const void *q_norm_weight, const void *k_norm_weight, float eps, const void *qkv_bias, void *stream, const int *row = nullptr,
-                    void *k_exp = nullptr, void *v_exp = nullptr) {
+                    void *k_exp = nullptr, void *v_exp = nullptr, bool mx4 = false) {
     if (S == 0) return GQ_OK;
     // (QKN: the statistic of a head is added inside an aligned group of head_dim / 16 lanes: a power of two, within one wave)
     const bool hd_ok = e.any_hd16 ? (head_dim != 0 && head_dim % 16u == 0) : (head_dim == 64u || head_dim == 128u);
@@ -367,8 +396,8 @@ int rope_cache_rows(const RowsEntry &e, bool kv8, const void *qkv, const int *po
     if (total >= 0x7FFFFFFFull) return gq_fail(GQ_ENOTSUP, e.too_large);
     const u32 nb = (u32)((total + 255u) / 256u);
     const dim3 grid(nb > 65535u ? 65535u : nb), block(256);
-#define GQ_LAUNCH_ROWS_EX(QKN_, QB_, KV8_, PKD_, TAIL_, K8R_)                                                                                  \
-    hipLaunchKernelGGL((rope_cache_rows_kernel<QKN_, QB_, KV8_, PKD_, K8R_>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)qkv, pos, \
+#define GQ_LAUNCH_ROWS_EX(QKN_, QB_, KV8_, PKD_, TAIL_, K8R_, ...)                                                                             \
+    hipLaunchKernelGGL((rope_cache_rows_kernel<QKN_, QB_, KV8_, PKD_, K8R_, ##__VA_ARGS__>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)qkv, pos, \
                        (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)q_out, (CacheElem<KV8_>::type *)k_cache,         \
                        (CacheElem<KV8_>::type *)v_cache, k_inv, v_inv, (const uint16_t *)q_norm_weight, (const uint16_t *)k_norm_weight, eps, \
                        (const uint16_t *)qkv_bias, S, n_head, n_kv_head, head_dim, max_seq, TAIL_)
@@ -376,7 +405,11 @@ int rope_cache_rows(const RowsEntry &e, bool kv8, const void *qkv, const int *po
     const RowsTail<false> none = {};
     const RowsTail<true> rows = {row};
     const RowsTail<false, true> ex = {(uint8_t *)k_exp, (uint8_t *)v_exp};
-    if (k_exp) {  // (the per-row scaled fp8 caches)
+    if (mx4) {  // (the MXFP4 caches)
+        if (q_norm_weight) GQ_LAUNCH_ROWS_EX(true, false, true, false, ex, true, true);
+        else if (qkv_bias) GQ_LAUNCH_ROWS_EX(false, true, true, false, ex, true, true);
+        else GQ_LAUNCH_ROWS_EX(false, false, true, false, ex, true, true);
+    } else if (k_exp) {  // (the per-row scaled fp8 caches)
         if (q_norm_weight) GQ_LAUNCH_ROWS_EX(true, false, true, false, ex, true);
         else if (qkv_bias) GQ_LAUNCH_ROWS_EX(false, true, true, false, ex, true);
         else GQ_LAUNCH_ROWS_EX(false, false, true, false, ex, true);
@@ -457,6 +490,22 @@ extern "C" int gq_rope_cache_rows_kv8r(const void *qkv, const int *pos, const vo
     // (the exponent bytes are stored one at a time: no alignment asked of k_exp / v_exp)
     return rope_cache_rows(e, true, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim, max_seq, q_norm_weight,
                            k_norm_weight, eps, qkv_bias, stream, nullptr, k_exp, v_exp);
+}
+
+// the MXFP4 form: codes [n_kv_head][max_seq][head_dim / 2], exponent bytes [n_kv_head][max_seq][head_dim / 32] (csrc/attn_core.h)
+extern "C" int gq_rope_cache_rows_mx4(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
+                                      void *v_cache, void *k_exp, void *v_exp, uint32_t S, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim,
+                                      uint32_t max_seq, const void *q_norm_weight, const void *k_norm_weight, float eps, const void *qkv_bias,
+                                      void *stream) {
+    if (!qkv || !pos || !cos_table || !sin_table || !q_out || !k_cache || !v_cache || !k_exp || !v_exp) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    const bool qkn = q_norm_weight || k_norm_weight;
+    if (qkn && (!q_norm_weight || !k_norm_weight)) return gq_fail(GQ_EINVAL, "gq_rope_cache_rows_mx4: both norm weights or none.");
+    if (qkn && qkv_bias) return gq_fail(GQ_EINVAL, "gq_rope_cache_rows_mx4: the norm form and the bias form do not combine.");
+    static const RowsEntry e = {false, "gq_rope_cache_rows_mx4: head_dim must be 64 or 128.", "gq_rope_cache_rows_mx4: 16-byte aligned pointers.",
+                                "gq_rope_cache_rows_mx4: problem too large."};
+    // (a row of codes is head_dim / 2 >= 32 bytes: 4-byte stores stay aligned in a 16-byte aligned cache; the exponent bytes need none)
+    return rope_cache_rows(e, true, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim, max_seq, q_norm_weight,
+                           k_norm_weight, eps, qkv_bias, stream, nullptr, k_exp, v_exp, true);
 }
 
 extern "C" int gq_rope_cache_rows_packed(const void *qkv, const int *pos, const int *row, const void *cos_table, const void *sin_table, void *q_out,

@@ -32,7 +32,10 @@
 // zeros (0 x NaN inside an MFMA is NaN), so nothing at or behind row max_seq is touched.  The tile loops hold no integer division.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "gq_internal.h"
+#include "attn_core.h"
 #include "wave_util.h"
 
 namespace {
@@ -97,6 +100,18 @@ struct TileFmt<true> {
         }
         return make_uint4(o[0], o[1], o[2], o[3]);
     }
+    // the MXFP4 form (MX4, gq_attn_prefill_mx4; csrc/attn_core.h): a chunk of 8 elements is 4 bytes of e2m1 codes inside ONE block of 32,
+    // unpacked by v_cvt_scalef32_pk_f32_fp4 and multiplied by the block's 2^e (NaN for the byte 0xFF) -- fp16 values, so the rounding to
+    // fp16 is exact and the LDS image is that of an fp16 cache holding code * 2^e
+    static __device__ __forceinline__ uint4 to_f16_mx4(u32 v, u32 byte) {
+        float f[8];
+        gq_attn::unpack8_mx4(v, gq_attn::mx4_scale(byte), f);
+        u32 o[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+            o[e] = (u32)__builtin_bit_cast(uint16_t, (h16)f[2 * e]) | ((u32)__builtin_bit_cast(uint16_t, (h16)f[2 * e + 1]) << 16);
+        return make_uint4(o[0], o[1], o[2], o[3]);
+    }
 };
 
 // the kernel's last argument: the scales of an fp8 cache, or -- PACKED, fp16 caches -- the segment begins (an instance that is neither
@@ -135,15 +150,20 @@ __device__ __forceinline__ u32 packed_lo(const int *__restrict__ seg_begin, u32 
 // gq_attn_prefill(S = i + 1, start = 0, window = min(i - seg_begin[i] + 1, window)).
 // ROW (with KV8): a thread fetches the exponent bytes of its chunks' rows with the chunks (the CH threads of a row ask for the same byte)
 // and multiplies between the global load and the LDS store; the scales of the per-head form are not read.
-template <int HD, bool KV8 = false, bool PACKED = false, bool ROW = false>
+// MX4 (with ROW): rows of HD / 2 bytes of e2m1 codes, a chunk is one 4-byte load, and the byte fetched with it is that of the chunk's
+// block (col / 4) in exponent rows of HD / 32 bytes.
+template <int HD, bool KV8 = false, bool PACKED = false, bool ROW = false, bool MX4 = false>
 __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__restrict__ q, const typename TileFmt<KV8>::elem *__restrict__ kc,
                                                            const typename TileFmt<KV8>::elem *__restrict__ vc, uint16_t *__restrict__ out, u32 S,
                                                            u32 start, u32 H, u32 group, u32 max_seq, float c, u32 window,
                                                            typename TailArg<KV8, PACKED, ROW>::type sc) {
     static_assert(!(KV8 && PACKED), "the packed pass has fp16 caches");
     static_assert(!ROW || KV8, "the per-row scaled form is a form of the fp8 caches");
+    static_assert(!MX4 || ROW, "the MXFP4 form is the per-row scaled form with the exponent per block");
     using Fmt = TileFmt<KV8>;
-    using Chunk = typename Fmt::chunk;
+    using Chunk = typename std::conditional<MX4, u32, typename Fmt::chunk>::type;
+    constexpr u32 RE = MX4 ? HD / 2 : HD, CE = MX4 ? 4 : 8;  // cache elements of a row, of a chunk
+    constexpr u32 XR = MX4 ? HD / 32 : 1;                    // exponent bytes of a row
     constexpr u32 LD = HD + 8;             // halves per LDS row: 16 bytes of padding
     constexpr u32 CH = HD / 8;             // 16-byte chunks per row
     constexpr u32 NCH = BK * CH / 256;     // chunks per thread and matrix
@@ -155,10 +175,10 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
     const u32 head = blockIdx.y, kvh = head / group;  // (once per block)
     const u32 q0 = (gridDim.x - 1u - blockIdx.x) * BQ;  // the long rows of the triangle first
     const u32 T = start + S;
-    const typename Fmt::elem *kbase = kc + (size_t)kvh * max_seq * HD, *vbase = vc + (size_t)kvh * max_seq * HD;
+    const typename Fmt::elem *kbase = kc + (size_t)kvh * max_seq * RE, *vbase = vc + (size_t)kvh * max_seq * RE;
     if constexpr (KV8 && !ROW) c *= sc.k_scale[kvh];  // (the K scale: one factor of the scores)
     const uint8_t *kebase = nullptr, *vebase = nullptr;
-    if constexpr (ROW) kebase = sc.k_exp + (size_t)kvh * max_seq, vebase = sc.v_exp + (size_t)kvh * max_seq;
+    if constexpr (ROW) kebase = sc.k_exp + (size_t)kvh * max_seq * XR, vebase = sc.v_exp + (size_t)kvh * max_seq * XR;
 
     // the block's key range: [klo, khi] covers every key one of its rows attends
     const u32 p_lo = start + q0, khi = start + min(q0 + BQ - 1u, S - 1u);
@@ -195,9 +215,13 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
         for (u32 i = 0; i < NCH; i++) {
             const u32 id = tid + 256u * i, row = id / CH, col = id % CH, t = kt * BK + row;  // (CH: a power of two)
             if (t < T) {
-                kreg[i] = *reinterpret_cast<const Chunk *>(kbase + (size_t)t * HD + 8u * col);
-                vreg[i] = *reinterpret_cast<const Chunk *>(vbase + (size_t)t * HD + 8u * col);
-                if constexpr (ROW) kexp[i] = kebase[t], vexp[i] = vebase[t];
+                kreg[i] = *reinterpret_cast<const Chunk *>(kbase + (size_t)t * RE + CE * col);
+                vreg[i] = *reinterpret_cast<const Chunk *>(vbase + (size_t)t * RE + CE * col);
+                if constexpr (MX4) kexp[i] = kebase[(size_t)t * XR + col / 4u], vexp[i] = vebase[(size_t)t * XR + col / 4u];
+                else if constexpr (ROW) kexp[i] = kebase[t], vexp[i] = vebase[t];
+            } else if constexpr (MX4) {
+                kreg[i] = 0u, vreg[i] = 0u;
+                kexp[i] = 127u, vexp[i] = 127u;
             } else {
                 kreg[i] = Fmt::zero();
                 vreg[i] = Fmt::zero();
@@ -217,7 +241,10 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
 #pragma unroll
         for (u32 i = 0; i < NCH; i++) {
             const u32 id = tid + 256u * i, row = id / CH, col = id % CH;
-            if constexpr (ROW) {
+            if constexpr (MX4) {
+                *reinterpret_cast<uint4 *>(&sK[row * LD + 8u * col]) = Fmt::to_f16_mx4(kreg[i], kexp[i]);
+                *reinterpret_cast<uint4 *>(&sV[row * LD + 8u * col]) = Fmt::to_f16_mx4(vreg[i], vexp[i]);
+            } else if constexpr (ROW) {
                 *reinterpret_cast<uint4 *>(&sK[row * LD + 8u * col]) = Fmt::to_f16_row(kreg[i], kexp[i]);
                 *reinterpret_cast<uint4 *>(&sV[row * LD + 8u * col]) = Fmt::to_f16_row(vreg[i], vexp[i]);
             } else {
@@ -349,7 +376,7 @@ extern "C" int gq_attn_prefill_supported(uint32_t n_head, uint32_t n_kv_head, ui
 }
 
 namespace {
-template <bool KV8, bool PACKED = false, bool ROW = false>
+template <bool KV8, bool PACKED = false, bool ROW = false, bool MX4 = false>
 int prefill_attn_launch(const void *q, const void *k_cache, const void *v_cache, void *out, uint32_t S, uint32_t start, uint32_t n_head,
                         uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t window, void *stream,
                         typename TailArg<KV8, PACKED, ROW>::type sc) {
@@ -371,10 +398,10 @@ int prefill_attn_launch(const void *q, const void *k_cache, const void *v_cache,
     const dim3 grid((S + BQ - 1u) / BQ, n_head), block(256);
     const uint32_t group = n_head / n_kv_head;
     if (head_dim == 64u)
-        hipLaunchKernelGGL((prefill_attn_kernel<64, KV8, PACKED, ROW>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
+        hipLaunchKernelGGL((prefill_attn_kernel<64, KV8, PACKED, ROW, MX4>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
                            (uint16_t *)out, S, start, n_head, group, max_seq, c, window, sc);
     else
-        hipLaunchKernelGGL((prefill_attn_kernel<128, KV8, PACKED, ROW>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
+        hipLaunchKernelGGL((prefill_attn_kernel<128, KV8, PACKED, ROW, MX4>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
                            (uint16_t *)out, S, start, n_head, group, max_seq, c, window, sc);
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
@@ -399,6 +426,14 @@ extern "C" int gq_attn_prefill_kv8r(const void *q, const void *k_cache, const vo
     if (!k_exp || !v_exp) return gq_fail(GQ_EINVAL, "null pointer argument.");
     return prefill_attn_launch<true, false, true>(q, k_cache, v_cache, out, S, start, n_head, n_kv_head, head_dim, max_seq, scale, window, stream,
                                                   {(const uint8_t *)k_exp, (const uint8_t *)v_exp});
+}
+
+extern "C" int gq_attn_prefill_mx4(const void *q, const void *k_cache, const void *v_cache, const void *k_exp, const void *v_exp, void *out,
+                                   uint32_t S, uint32_t start, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale,
+                                   uint32_t window, void *stream) {
+    if (!k_exp || !v_exp) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    return prefill_attn_launch<true, false, true, true>(q, k_cache, v_cache, out, S, start, n_head, n_kv_head, head_dim, max_seq, scale, window, stream,
+                                                        {(const uint8_t *)k_exp, (const uint8_t *)v_exp});
 }
 
 extern "C" int gq_attn_prefill_packed(const void *q, const void *k_cache, const void *v_cache, const int *seg_begin, void *out, uint32_t S,

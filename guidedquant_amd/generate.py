@@ -349,7 +349,7 @@ def decode_n_tokens(model: Transformer, cur_token: torch.Tensor, input_pos: torc
 @torch.no_grad()
 def generate(model: Transformer, prompt: torch.Tensor, max_new_tokens: int, batch_size: int = 1, callback=lambda x: x,
              use_graph=True, graph: Optional[DecodeGraph] = None, kv_cache_dtype=None, **sampling_kwargs) -> torch.Tensor:
-    """kv_cache_dtype: None / "fp16" / "fp8" / "fp8_row" (Transformer.setup_caches); a `graph` must have been captured over caches of that dtype"""
+    """kv_cache_dtype: None / "fp16" / "fp8" / "fp8_row" / "mxfp4" (Transformer.setup_caches); a `graph` must have been captured over caches of that dtype"""
     T = prompt.size(-1)
     T_new = T + max_new_tokens
     max_seq_length = min(T_new, model.config.block_size)
@@ -589,9 +589,10 @@ if __name__ == "__main__":
     parser.add_argument('--backend', type=str, default=None, choices=["ap", "lutgemm", "qtip", None])
     parser.add_argument('--print_result', action='store_true')
     parser.add_argument('--random_init', action='store_true')
-    parser.add_argument('--kv_cache_dtype', type=str, default=None, choices=["fp16", "fp8", "fp8_row"],
+    parser.add_argument('--kv_cache_dtype', type=str, default=None, choices=["fp16", "fp8", "fp8_row", "mxfp4"],
                         help='fp8: the KV cache as e4m3 codes, scale 1.0 per head; fp8_row: e4m3 codes with an exponent byte per cached row, '
-                             'nothing to calibrate (fused Any-Precision models; default fp16)')
+                             'nothing to calibrate; mxfp4: e2m1 codes, two per byte, with an exponent byte per block of 32 elements '
+                             '(fused Any-Precision models; default fp16)')
     parser.add_argument('--lm_head_dtype', type=str, default=None, choices=["fp16", "int8"],
                         help='int8: the decode step reads a weight-only int8 copy of the lm_head, one scale per row (default fp16)')
     parser.add_argument('--frequency_penalty', type=float, default=0.0,

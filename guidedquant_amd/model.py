@@ -183,10 +183,11 @@ FP8_MAX = 448.0  # the largest e4m3 magnitude
 
 def kv_cache_dtype_name(kv_cache_dtype) -> str:
     """None / "fp16" -> "fp16" (the cache in the model's own dtype: the default), "fp8" -> "fp8" (OCP e4m3 codes + a scale per KV head),
-    "fp8_row" -> "fp8_row" (the same codes + one exponent byte per cached row and KV head: no scale to calibrate)"""
+    "fp8_row" -> "fp8_row" (the same codes + one exponent byte per cached row and KV head: no scale to calibrate), "mxfp4" -> "mxfp4"
+    (OCP microscaling: e2m1 codes, two per byte, + one exponent byte per block of 32 elements)"""
     name = "fp16" if kv_cache_dtype is None else str(kv_cache_dtype)
-    if name not in ("fp16", "fp8", "fp8_row"):
-        raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r}: None, 'fp16' or 'fp8', or 'fp8_row'")
+    if name not in ("fp16", "fp8", "fp8_row", "mxfp4"):
+        raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r}: None, 'fp16' or 'fp8', or 'fp8_row', or 'mxfp4'")
     return name
 
 
@@ -220,19 +221,64 @@ def fp8_row_scale(exp_byte: Tensor) -> Tensor:
     return (exp_byte.to(torch.int32) << 23).view(torch.float32)
 
 
+MX4_BLOCK = 32  # elements that share one exponent byte (OCP microscaling)
+MX4_MAGNITUDES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # e2m1: the magnitude of code & 7; bit 3 is the sign
+
+
+def mxfp4_quantize(x16: Tensor):
+    """THE write rule of the MXFP4 cache (include/gq_hip.h), the host model of csrc/prefill.hip store_units_mx4, bit for bit.
+    x16 fp16 [.., head_dim], head_dim a multiple of 32: every run of 32 elements along the last dimension is one block.  Returns (codes
+    uint8 [.., head_dim / 2], element 2j in the low nibble of byte j; exponent bytes uint8 [.., head_dim / 32]).  On a = the largest
+    fp16 magnitude bits of the block:
+        field = clamp((a + 0x1FF) >> 10, 2, 30) + 110    e = field - 127 = clamp(ceil(log2(amax / 6)), -15, 13); a == 0: e = -15
+        byte  = 0xFF where a >= 0x7C00 (an Inf or a NaN in the block), else field
+        code  = the nearest of the 8 magnitudes to |x16| * 2^-e, a tie to the even code (= the even mantissa), 7 for a NaN; | sign << 3"""
+    assert x16.dtype == torch.float16 and x16.shape[-1] % MX4_BLOCK == 0
+    bits = x16.contiguous().view(torch.int16).to(torch.int32)
+    a = (bits & 0x7FFF).unflatten(-1, (-1, MX4_BLOCK)).amax(dim=-1)
+    field = ((a + 0x1FF) >> 10).clamp(2, 30) + 110
+    inv = ((254 - field) << 23).to(torch.int32).view(torch.float32)
+    y = x16.float().abs().unflatten(-1, (-1, MX4_BLOCK)) * inv[..., None]  # (exact: a power of two)
+    code = torch.zeros_like(y, dtype=torch.int32)
+    for i, mid in enumerate((0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)):  # (the midpoint between the codes i and i + 1 goes to the even one)
+        code += ((y > mid) | ((y == mid) & bool(i & 1))).to(torch.int32)
+    code = torch.where(y.isnan(), torch.full_like(code, 7), code).flatten(-2) | ((bits >> 12) & 8)
+    byte = torch.where(a >= 0x7C00, torch.full_like(field, 0xFF), field)
+    return (code[..., 0::2] | (code[..., 1::2] << 4)).to(torch.uint8), byte.to(torch.uint8)
+
+
+def mxfp4_dequant(codes: Tensor, exps: Tensor, dtype=torch.float16) -> Tensor:
+    """the read rule of the MXFP4 cache: value = e2m1(code) * 2^(byte - 127), exact in fp16 for the bytes the write rule produces; every
+    element of a block with the byte 0xFF is NaN.  codes uint8 [.., head_dim / 2], exps uint8 [.., head_dim / 32] -> [.., head_dim]"""
+    c = codes.to(torch.int32)
+    nib = torch.stack((c & 0xF, c >> 4), dim=-1).flatten(-2)
+    mag = torch.tensor(MX4_MAGNITUDES, dtype=torch.float32, device=codes.device)[nib & 7]
+    val = torch.where((nib & 8) != 0, -mag, mag)
+    e = exps.to(torch.int32)
+    scale = torch.where(e == 0xFF, torch.full_like(e, 0x7FC00000), e << 23).view(torch.float32)
+    return (val.unflatten(-1, (-1, MX4_BLOCK)) * scale[..., None]).flatten(-2).to(dtype)
+
+
 class KVCache(nn.Module):
     """k_cache / v_cache [batch][n_kv_head][max_seq][head_dim] in `dtype`.  fp8=True: torch.float8_e4m3fn caches with four fp32
     [n_kv_head] buffers -- k_scale / v_scale (value = code * scale, default 1.0) and their reciprocals k_inv / v_inv, which the host
     fills (`set_scales`: torch.reciprocal; no kernel divides).  `dtype` is then what `update` dequantises to.
     fp8_row=True: the same caches of codes with k_exp / v_exp uint8 [batch][n_kv_head][max_seq] instead, one e8m0 exponent byte per
-    cached row and KV head (`fp8_row_quantize`); no scales."""
+    cached row and KV head (`fp8_row_quantize`); no scales.
+    mxfp4=True: uint8 caches [batch][n_kv_head][max_seq][head_dim / 2] of e2m1 codes, two per byte, with k_exp / v_exp uint8
+    [batch][n_kv_head][max_seq][head_dim / 32], one e8m0 exponent byte per block of 32 elements (`mxfp4_quantize`); no scales."""
 
-    def __init__(self, max_batch_size, max_seq_length, n_heads, head_dim, dtype=torch.half, device=None, fp8=False, fp8_row=False):
+    def __init__(self, max_batch_size, max_seq_length, n_heads, head_dim, dtype=torch.half, device=None, fp8=False, fp8_row=False, mxfp4=False):
         super().__init__()
-        assert not (fp8 and fp8_row)
+        assert bool(fp8) + bool(fp8_row) + bool(mxfp4) <= 1
         cache_shape = (max_batch_size, n_heads, max_seq_length, head_dim)
-        self.fp8, self.fp8_row, self.out_dtype = bool(fp8), bool(fp8_row), dtype
+        self.fp8, self.fp8_row, self.mxfp4, self.out_dtype = bool(fp8), bool(fp8_row), bool(mxfp4), dtype
         store = torch.float8_e4m3fn if fp8 or fp8_row else dtype
+        if mxfp4:
+            assert head_dim % MX4_BLOCK == 0, head_dim
+            cache_shape, store = cache_shape[:3] + (head_dim // 2,), torch.uint8
+            for name in ("k_exp", "v_exp"):
+                self.register_buffer(name, torch.full(cache_shape[:3] + (head_dim // MX4_BLOCK,), FP8_ROW_EXP_ONE, dtype=torch.uint8, device=device))
         self.register_buffer('k_cache', torch.zeros(cache_shape, dtype=store, device=device))
         self.register_buffer('v_cache', torch.zeros(cache_shape, dtype=store, device=device))
         if fp8:
@@ -260,6 +306,10 @@ class KVCache(nn.Module):
 
     def update(self, input_pos, k_val, v_val):
         assert input_pos.shape[0] == k_val.shape[2]
+        if self.mxfp4:  # (as below: stored by the write rule, returned dequantised)
+            for cache, exp, val in ((self.k_cache, self.k_exp, k_val), (self.v_cache, self.v_exp, v_val)):
+                cache[:, :, input_pos], exp[:, :, input_pos] = mxfp4_quantize(val.to(torch.float16))
+            return mxfp4_dequant(self.k_cache, self.k_exp, self.out_dtype), mxfp4_dequant(self.v_cache, self.v_exp, self.out_dtype)
         if self.fp8_row:  # (as below: stored by the write rule, returned dequantised)
             for cache, exp, val in ((self.k_cache, self.k_exp, k_val), (self.v_cache, self.v_exp, v_val)):
                 codes, byte = fp8_row_quantize(val.to(torch.float16))
@@ -526,7 +576,7 @@ class Transformer(nn.Module):
                    halve_layers=halve_layers, fuse_linears=fuse_linears)
 
     def kv8_unserved(self) -> Optional[str]:
-        """why the fused HIP route cannot serve this model with an fp8 or fp8_row KV cache (None: it can).  Host logic, no device needed."""
+        """why the fused HIP route cannot serve this model with an fp8, fp8_row or mxfp4 KV cache (None: it can).  Host logic, no device needed."""
         from .APLinear import APLinear
         if not self.fuse_linears:
             return "the model is not a fused-linear Any-Precision model"
@@ -540,8 +590,8 @@ class Transformer(nn.Module):
 
     def setup_caches(self, max_batch_size, max_seq_length, kv_cache_dtype=None):
         """kv_cache_dtype: None / "fp16" (the default: caches in the model's dtype), "fp8" (e4m3 codes, a scale per layer and KV head,
-        `set_kv_scales`) or "fp8_row" (e4m3 codes, an exponent byte per cached row and KV head, nothing to set); both served by the fused
-        Any-Precision route and the module forward.  A change of the dtype re-allocates the caches even when their size suffices."""
+        `set_kv_scales`), "fp8_row" (e4m3 codes, an exponent byte per cached row and KV head, nothing to set) or "mxfp4" (e2m1 codes, two
+        per byte, an exponent byte per block of 32 elements, nothing to set); all served by the fused Any-Precision route and the module forward.  A change of the dtype re-allocates the caches even when their size suffices."""
         kv = kv_cache_dtype_name(kv_cache_dtype)
         if self.max_seq_length >= max_seq_length and self.max_batch_size >= max_batch_size and kv == self.kv_cache_dtype:
             return
@@ -555,7 +605,7 @@ class Transformer(nn.Module):
         device = self.output.weight.device
         for b in self.layers:
             b.attention.kv_cache = KVCache(max_batch_size, max_seq_length, self.config.n_local_heads, head_dim, dtype, device, fp8=(kv == "fp8"),
-                                           fp8_row=(kv == "fp8_row"))
+                                           fp8_row=(kv == "fp8_row"), mxfp4=(kv == "mxfp4"))
         self.kv_cache_dtype = kv
         # the [n, n] tables only for a cache of at most MASK_TABLE_MAX rows (tests and pipeline.py index them); above it every consumer
         # builds the rows it needs from the positions (mask_rows: the same bits)
@@ -578,6 +628,8 @@ class Transformer(nn.Module):
         Rows already in the caches keep their codes: set the scales before the prompt."""
         if self.cache_initialized and self.kv_cache_dtype == "fp8_row":
             raise ValueError("set_kv_scales: an fp8_row cache has no per-head scales (one exponent byte per cached row, written with the row)")
+        if self.cache_initialized and self.kv_cache_dtype == "mxfp4":
+            raise ValueError("set_kv_scales: an mxfp4 cache has no per-head scales (one exponent byte per block of 32 elements, written with the row)")
         if not (self.cache_initialized and self.kv_cache_dtype == "fp8"):
             raise ValueError("set_kv_scales: the caches are not fp8 (setup_caches(.., kv_cache_dtype='fp8') first)")
         shape = (len(self.layers), self.config.n_local_heads)

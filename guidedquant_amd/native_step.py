@@ -149,12 +149,15 @@ class StepState(_Keyed):
         self.kv8 = getattr(model, "kv_cache_dtype", "fp16") == "fp8"
         # a per-row scaled fp8 cache (kv_cache_dtype="fp8_row"): always the two-launch route, attend_kv8r
         self.kv8r = getattr(model, "kv_cache_dtype", "fp16") == "fp8_row"
-        self.q8 = torch.zeros(c.n_head * c.head_dim, **f16) if (self.kv8 and not kv8_fold()) or self.kv8r else None
+        # an MXFP4 cache (kv_cache_dtype="mxfp4"): the same two-launch route over its entries, attend_mx4
+        self.mx4 = getattr(model, "kv_cache_dtype", "fp16") == "mxfp4"
+        self.q8 = torch.zeros(c.n_head * c.head_dim, **f16) if (self.kv8 and not kv8_fold()) or self.kv8r or self.mx4 else None
 
     def kv(self, at, slot):
         """the K / V cache of batch slot `slot` of one attention module"""
         c = self.m.config
-        off = slot * kv_slot_bytes(c.n_local_heads, self.m.max_seq_length, c.head_dim, at.kv_cache.k_cache.element_size())
+        # (the last dimension of the cache tensor: head_dim, or head_dim / 2 bytes of an MXFP4 cache's codes)
+        off = slot * kv_slot_bytes(c.n_local_heads, self.m.max_seq_length, at.kv_cache.k_cache.shape[-1], at.kv_cache.k_cache.element_size())
         return at.kv_cache.k_cache.data_ptr() + off, at.kv_cache.v_cache.data_ptr() + off
 
     def attend(self, entry, src, pos, kv, sp, extra=(), layer=None):
@@ -208,6 +211,21 @@ class StepState(_Keyed):
                                                m.max_seq_length, 1.0 / math.sqrt(c.head_dim), self.layer_split[layer], _ptr(self.attn_ws),
                                                self.layer_window[layer] or 0, sp), "gq_attn_decode_roped_kv8r")
 
+    def attend_mx4(self, at, pos, kv, sp, layer, slot):
+        """the MXFP4 cache's route of one layer, behind the plain wqkv GEMV -- attend_kv8r's two launches over the MXFP4 entries:
+        gq_rope_cache_rows_mx4 (S = 1, the graph's position word; the layer's norm weights or bias) rotates q, derives the exponents of the
+        blocks of the new k and v rows and writes codes and bytes, gq_attn_decode_roped_mx4 attends with the layer's window and split plan.
+        One route for Llama, Mistral, Qwen2 and Qwen3.  (`kv`: StepState.kv's pointers, a slot of n_kv_head * max_seq * head_dim / 2 bytes)"""
+        m, c, L, kvc = self.m, self.m.config, _lib.lib(), at.kv_cache
+        off = slot * c.n_local_heads * m.max_seq_length * (c.head_dim // 32)  # (one byte per KV head, row and block)
+        ex = kvc.k_exp.data_ptr() + off, kvc.v_exp.data_ptr() + off
+        _lib.check(L.gq_rope_cache_rows_mx4(self.qkv.data_ptr(), pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), self.q8.data_ptr(), *kv, *ex,
+                                            1, c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, *qk_norm_args(at, c), _ptr(at.wqkv.bias), sp),
+                   "gq_rope_cache_rows_mx4")
+        _lib.check(L.gq_attn_decode_roped_mx4(self.q8.data_ptr(), pos.data_ptr(), *kv, *ex, self.y.data_ptr(), c.n_head, c.n_local_heads, c.head_dim,
+                                              m.max_seq_length, 1.0 / math.sqrt(c.head_dim), self.layer_split[layer], _ptr(self.attn_ws),
+                                              self.layer_window[layer] or 0, sp), "gq_attn_decode_roped_mx4")
+
     def head(self, x):
         """the one call site of the dense GEMV (both families): final RMSNorm + lm_head -> the fp16 logits.  An int8-head model
         (Transformer.set_lm_head_dtype) launches gq_dense_gemv_i8 over its int8 copy, every other model what it always launched."""
@@ -260,7 +278,7 @@ class ApStep(StepState):
         from .model import pair_gate_up_rows_
         super().__init__(model)
         c = model.config
-        if (self.kv8 or self.kv8r) and model.kv8_unserved():
+        if (self.kv8 or self.kv8r or self.mx4) and model.kv8_unserved():
             raise ValueError(model.kv_cache_dtype + " KV cache: " + model.kv8_unserved())
         self.adapter = getattr(model, "adapter", None)  # (Transformer.set_adapter: a LoraAdapter, or None)
         self.lora_layers = getattr(model, "adapter_layers", None)  # (its sites per layer as bound to THIS model: LoraAdapter.bind)
@@ -286,7 +304,7 @@ class ApStep(StepState):
         gq_lora_up writes -- the q | k | v delta (+ the checkpoint's bias) the attention launch adds, the residuals of wo and w2 with
         their delta.  The refusals: none of them falls back."""
         c, ad, dev = self.m.config, self.adapter, self.x.device
-        if self.kv8 or self.kv8r:
+        if self.kv8 or self.kv8r or self.mx4:
             raise NotImplementedError("lora: the %s KV cache is not served under an adapter (setup_caches(.., kv_cache_dtype='fp16'))" % self.m.kv_cache_dtype)
         if c.qk_norm and ad.targets("qkv"):
             raise ValueError("lora: q / k / v targets on a QK-norm model (Qwen3): no attention launch has both the norm and a bias; "
@@ -351,6 +369,9 @@ class ApStep(StepState):
             elif self.kv8r:
                 launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
                 self.attend_kv8r(at, pos, kv, sp, l0 + li, slot)
+            elif self.mx4:
+                launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
+                self.attend_mx4(at, pos, kv, sp, l0 + li, slot)
             elif c.qk_norm:
                 # Qwen3: q and k are normalised per head BEFORE the rotation, so the wqkv launch must not rotate (its RoPE epilogue holds a
                 # head's rows in eight 16-row groups: no per-head statistic there) -- plain wqkv GEMV, then ONE attention launch that
@@ -641,7 +662,7 @@ class QtipStep(StepState):
         super().__init__(model)
         if getattr(model, "adapter", None) is not None:
             raise NotImplementedError("lora: QTIP models are not served under an adapter")
-        if self.kv8 or self.kv8r:
+        if self.kv8 or self.kv8r or self.mx4:
             raise NotImplementedError(model.kv_cache_dtype + " KV cache: QTIP models keep the fp16 cache (gq_attn_decode_qtip has no fp8 form)")
         c, dev = model.config, self.x.device
         self.g = torch.zeros(c.intermediate_size, dtype=torch.float16, device=dev)

@@ -307,6 +307,46 @@ int gq_attn_prefill_kv8r(const void *q, const void *k_cache, const void *v_cache
                          uint32_t window, void *stream);
 
 /*
+ * The MXFP4 KV cache (kv_cache_dtype="mxfp4", OCP microscaling): e2m1 codes, two per byte, uint8 [n_kv_head][max_seq][head_dim / 2] per
+ * batch slot -- element 2j in the low nibble of byte j; a code is the sign bit and e2m1, magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 -- and ONE
+ * e8m0 exponent byte per block of 32 consecutive elements of a head's row for K and for V, uint8 [n_kv_head][max_seq][head_dim / 32] per
+ * batch slot: the block's scale is 2^(byte - 127).  A head_dim-128 row takes 68 bytes (fp16: 256, fp8_row: 129).  Nothing to calibrate.
+ *   write rule  for the 32 fp16 values x16 of one block -- what the fp16 path would have stored (k: after bias or QK-norm and rotation):
+ *               a     = the largest |x16| of the block as its fp16 bit pattern
+ *               field = clamp((a + 0x1FF) >> 10, 2, 30) + 110,  e = field - 127 = clamp(ceil(log2(amax / 6)), -15, 13)
+ *                       (6 = 1.5 * 2^2: the fp16 exponent field, one more where the mantissa field exceeds 0x200; integer arithmetic;
+ *                       an all-zero block: e = -15)
+ *               byte  = field, or 0xFF where the block holds an Inf or a NaN (a >= 0x7C00)
+ *               code  = e2m1_rne(x16 * 2^-e), ties to the even mantissa (0.25 -> 0, 0.75 -> 1, 2.5 -> 2, 5 -> 4), the sign kept (-0 too);
+ *                       magnitudes above 6 * 2^13 = 49152 (e would be 14), and Inf and NaN, saturate to +-6.  Integer arithmetic on the
+ *                       fp32 bits of the exact product, not the hardware conversion: the rule fixes every input, non-finite ones included.
+ *               |x - deq| <= 2^e where 4 * 2^e <= |x| <= 6 * 2^e (half the step 2 * 2^e of the top binade), <= 2^(e-1) where
+ *               2 * 2^e <= |x| < 4 * 2^e, <= 2^(e-2) below: everywhere but behind the clamp at 49152.  With 2^e < amax / 3 unless e = -15.
+ *   read rule   value = e2m1(code) * 2^e, an fp16 value for every code and every e in [-15, 13] (0.5 * 2^-15 = 2^-16; 6 * 2^13 <
+ *               65504), so the product is exact and is applied where the codes are unpacked.  A block with the byte 0xFF reads back as
+ *               32 NaNs.  The results equal, bit for bit, those of the fp16 entries on an fp16 cache that holds code * 2^e.
+ * gq_rope_cache_rows_mx4: the entry shape, forms (plain, both norm weights, or qkv_bias), head_dims (64, 128: anything else GQ_ENOTSUP
+ *   with nothing written) and checks of gq_rope_cache_rows_kv8r; q_out bit for bit the fp16 entries'.  S = 1 with the position word on the
+ *   device is the decode step.  Writes head_dim / 2 bytes of codes and head_dim / 32 exponent bytes per (written row, KV head) into each
+ *   cache; positions >= max_seq write nothing.  The caches 16-byte aligned; k_exp / v_exp need no alignment.
+ * gq_attn_decode_roped_mx4: gq_attn_decode_roped_kv8r over these caches (window 0: the whole context; n_split, workspace and the NaN
+ *   result at *pos >= max_seq as there).  A lane's 8 elements of a row are one 4-byte load, the byte of their block is requested with
+ *   it.  Geometry, solo rule, split length, stream assignment, merge order and the combine launch are those of gq_attn_decode_roped.
+ * gq_attn_prefill_mx4: gq_attn_prefill over these caches (gq_attn_prefill_supported): tiles are converted to fp16 between the global
+ *   load and LDS, the LDS image and both matrix products are gq_attn_prefill's.  Rows [0, start + S) hold what the write rule produced.
+ */
+int gq_rope_cache_rows_mx4(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
+                           void *v_cache, void *k_exp, void *v_exp, uint32_t S, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim,
+                           uint32_t max_seq, const void *q_norm_weight, const void *k_norm_weight, float eps, const void *qkv_bias,
+                           void *stream);
+int gq_attn_decode_roped_mx4(const void *q, const int *pos, const void *k_cache, const void *v_cache, const void *k_exp, const void *v_exp,
+                             void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale,
+                             uint32_t n_split, float *workspace, uint32_t window, void *stream);
+int gq_attn_prefill_mx4(const void *q, const void *k_cache, const void *v_cache, const void *k_exp, const void *v_exp, void *out, uint32_t S,
+                        uint32_t start, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale,
+                        uint32_t window, void *stream);
+
+/*
  * The scoring head of the prompt pass: per-token log-probabilities without the logits (csrc/head_nll.hip).  What the reference's
  * perplexity loop computes with the module tree and `labels=` (any_precision/evaluate/eval.py:205-226: lm_head logits [1, S, V] in
  * fp16, HF's loss upcasts them to fp32 and takes the cross entropy) from the rows behind the final RMSNorm, in one pass over the
