@@ -620,7 +620,7 @@ class AnyPrecisionForCausalLM(nn.Module):
             return torch.cat(lps), torch.cat(tops), torch.cat([i for i, _ in lists]), torch.cat([v for _, v in lists])
         return torch.cat(lps), torch.cat(tops)
 
-    def score(self, input_ids, precision=None, kv_cache_dtype=None, native=None, top_logprobs=None):
+    def score(self, input_ids, precision=None, kv_cache_dtype=None, native=None, top_logprobs=None, lm_head_dtype=None):
         """Log-probabilities of one token sequence ([1, T] or [T], T >= 2): dict(logprobs fp32 [T - 1], greedy bool [T - 1], nll float)
         with logprobs[i] = log p(ids[i + 1] | ids[:i + 1]), greedy[i] = (the most probable next token is ids[i + 1]) and nll the mean of
         -logprobs -- the `outputs.loss` of the module tree for `labels=input_ids` (any_precision/evaluate/eval.py:222-223).
@@ -633,10 +633,17 @@ class AnyPrecisionForCausalLM(nn.Module):
         probable tokens of the distribution logprobs[i] was taken from, most probable first, equal logits by ascending id, -1 where the
         vocabulary has fewer -- and `top_logprobs` fp32 [T - 1, n], their log-probabilities (-inf beside a -1): the keys and dtypes
         of `generate(..., top_logprobs=n)`.  On the fused route the scoring head selects them in its own launch (gq_head_nll_topn); the
-        module tree and the CPU sort in torch.  Without the keyword nothing changes."""
+        module tree and the CPU sort in torch.  Without the keyword nothing changes.
+        lm_head_dtype="int8" scores the model `generate(..., lm_head_dtype="int8")` decodes: the scoring head reads the int8 copy of the
+        lm_head (gq_head_nll_i8 / gq_head_nll_i8_topn; `Transformer.score_native`).  `generate`'s rules: it is the request's head -- fp16
+        without the keyword, whatever an earlier request left on the decoder; native=False, the CPU or a checkpoint without a fused form
+        raise ValueError("lm_head_dtype='int8': ..."), never a fall-back; the keyword never reaches the module tree.  It composes with
+        kv_cache_dtype= and top_logprobs=."""
+        from .head_q8 import lm_head_dtype_name
         from .model import kv_cache_dtype_name
         from .native_prompt import check_top_logprobs
         kv = kv_cache_dtype_name(kv_cache_dtype)
+        hd = lm_head_dtype_name(lm_head_dtype)
         top_n = check_top_logprobs(top_logprobs)
         ids = torch.as_tensor(input_ids)
         if ids.is_floating_point() or ids.dim() not in (1, 2) or (ids.dim() == 2 and ids.shape[0] != 1):
@@ -651,6 +658,8 @@ class AnyPrecisionForCausalLM(nn.Module):
             raise ValueError(f"score: token ids must lie in [0, {vocab})")
         if kv != "fp16" and native is False:
             raise ValueError(f"kv_cache_dtype='{kv}': served by the fused decode model only (not with native=False)")
+        if hd == "int8" and native is False:
+            raise ValueError("lm_head_dtype='int8': served by the fused decode model only (not with native=False)")
         if self._adapter is not None and (native is False or kv != "fp16"):
             raise ValueError("lora: the adapter is served by the fused decode model with an fp16 cache only")
         prev_precision = self.precision
@@ -672,11 +681,14 @@ class AnyPrecisionForCausalLM(nn.Module):
                         dec, why = None, "the fused model's prompt pass does not serve this model"
             if dec is None and kv != "fp16":
                 raise ValueError(f"kv_cache_dtype='{kv}': " + why)
+            if dec is None and hd == "int8":
+                raise ValueError("lm_head_dtype='int8': " + why)
             if dec is None and self._adapter is not None:
                 raise ValueError("lora: " + why)
             if dec is None and native is True:
                 raise ValueError("native=True: " + why)
             if dec is not None:
+                self._request_head(dec, hd)
                 # the caches sized as `_generate_native` sizes them, and like there allocated OUTSIDE inference mode (tensors made inside
                 # it refuse in-place updates elsewhere: set_kv_scales, the module forward's cache write); graphs captured over caches
                 # about to be replaced go first
@@ -687,7 +699,8 @@ class AnyPrecisionForCausalLM(nn.Module):
             lists = ()
             with torch.inference_mode():
                 if dec is not None:
-                    lp, greedy, *lists = dec.score_native(ids.to(self.device).to(torch.int32), **({"top_logprobs": top_n} if top_n else {}))
+                    lp, greedy, *lists = dec.score_native(ids.to(self.device).to(torch.int32), **({"top_logprobs": top_n} if top_n else {}),
+                                                          **({"lm_head_dtype": "int8"} if hd == "int8" else {}))
                 else:
                     dev_ids = ids.to(self.device).long()
                     logits = self.model(input_ids=dev_ids.view(1, -1)).logits[0, :-1]
@@ -702,7 +715,8 @@ class AnyPrecisionForCausalLM(nn.Module):
         """Perplexity of a 1-D token stream by the reference's definition (any_precision/evaluate/eval.py:205-226): the stream is cut
         into len // chunk_size non-overlapping chunks (a shorter tail is dropped), each chunk's mean negative log-likelihood is taken
         on its own (`score`; its first token is context only), and the result is exp of the mean of those means.
-        Returns dict(ppl, nll_per_chunk).  `score_kwargs` (precision, kv_cache_dtype, native) go to `score`."""
+        Returns dict(ppl, nll_per_chunk).  `score_kwargs` (precision, kv_cache_dtype, native, lm_head_dtype) go to `score`:
+        perplexity(ids, lm_head_dtype="int8") is the perplexity of the model the int8 head decodes."""
         ids = torch.as_tensor(token_ids)
         if ids.dim() != 1:
             raise ValueError("perplexity: token_ids must be a 1-D stream of token ids")
@@ -716,7 +730,8 @@ class AnyPrecisionForCausalLM(nn.Module):
 
     def loglikelihood(self, context_ids, continuation_ids, **score_kwargs):
         """lm-eval's pair for a (context, continuation): (the sum of the continuation tokens' log-probabilities given everything in
-        front of them, whether every one of them is the model's most probable token), from ONE pass over context + continuation."""
+        front of them, whether every one of them is the model's most probable token), from ONE pass over context + continuation.
+        `score_kwargs` go to `score` (lm_head_dtype="int8" among them: the int8 head's model)."""
         ctx, cont = torch.as_tensor(context_ids).reshape(-1), torch.as_tensor(continuation_ids).reshape(-1)
         if ctx.numel() < 1 or cont.numel() < 1:
             raise ValueError("loglikelihood: a context and a continuation of at least one token each")
@@ -738,7 +753,7 @@ class AnyPrecisionForCausalLM(nn.Module):
             raise ValueError(f"{what}: token ids must lie in [0, {vocab})")
         return host
 
-    def _score_packs(self, seqs, tails, pack_tokens, precision, native, what):
+    def _score_packs(self, seqs, tails, pack_tokens, precision, native, what, lm_head_dtype=None):
         """[(logprobs fp32 [t_i], greedy bool [t_i])] in input order: the last `tails[i]` log-probabilities of sequence i (None: all of its
         T_i - 1).  On the fused route the sequences go through `Transformer.score_packed_native` in packs (native_prompt.pack_plan: first
         fit in input order), and only the rows asked for reach the scoring head; a sequence longer than a pack, and every sequence off the
@@ -746,6 +761,9 @@ class AnyPrecisionForCausalLM(nn.Module):
         if pack_tokens is not None and int(pack_tokens) < 2:
             raise ValueError(f"{what}: pack_tokens must be at least 2")
         from . import native_prompt
+        from .head_q8 import lm_head_dtype_name
+        hd = lm_head_dtype_name(lm_head_dtype)
+        head = {"lm_head_dtype": "int8"} if hd == "int8" else {}  # (the request's head: `score`'s rules, and its refusals off the fused route)
 
         def tail(lp, greedy, t):
             return (lp, greedy) if t is None else (lp[-t:], greedy[-t:])
@@ -770,9 +788,10 @@ class AnyPrecisionForCausalLM(nn.Module):
             if dec is None:
                 out = []
                 for s, t in zip(seqs, tails):
-                    r = self.score(s, native=native)
+                    r = self.score(s, native=native, **head)
                     out.append(tail(r["logprobs"], r["greedy"], t))
                 return out
+            self._request_head(dec, hd)
             capacity = native_prompt.pack_capacity(dec) if pack_tokens is None else min(int(pack_tokens), int(dec.config.block_size))
             lens = [int(s.numel()) for s in seqs]
             packs = native_prompt.pack_plan(lens, capacity)
@@ -786,8 +805,8 @@ class AnyPrecisionForCausalLM(nn.Module):
                 dec.setup_caches(1, cap, kv_cache_dtype="fp16")
             for p in packs:
                 if sum(lens[i] for i in p) > capacity:  # (one sequence longer than a pack: the one-sequence pass, chunked as it is there)
-                    r = self.score(seqs[p[0]], native=native)
-                    out[p[0]] = tail(r["logprobs"], r["greedy"], tails[p[0]])
+                    r = self.score(seqs[p[0]], native=native, **head)
+                    out[p[0]] =tail(r["logprobs"], r["greedy"], tails[p[0]])
                     continue
                 dev_seqs = [seqs[i].to(self.device).to(torch.int32) for i in p]
                 rows, counts = None, [lens[i] - 1 if tails[i] is None else tails[i] for i in p]
@@ -798,7 +817,7 @@ class AnyPrecisionForCausalLM(nn.Module):
                         b += lens[i]
                     rows = mask.to(self.device)
                 with torch.inference_mode():
-                    lp, hit = dec.score_packed_native(dev_seqs, rows)
+                    lp, hit = dec.score_packed_native(dev_seqs, rows, **head)
                 b = 0
                 for i, c in zip(p, counts):
                     out[i] = (lp[b:b + c], hit[b:b + c])
@@ -807,22 +826,22 @@ class AnyPrecisionForCausalLM(nn.Module):
         finally:
             self.set_precision(prev_precision)
 
-    def score_many(self, list_of_ids, pack_tokens=None, precision=None, native=None):
+    def score_many(self, list_of_ids, pack_tokens=None, precision=None, native=None, lm_head_dtype=None):
         """`score` for many sequences: a list of its dicts (logprobs fp32 [T_i - 1], greedy bool [T_i - 1], nll float) in input order.
         On the fused route the sequences are packed -- first fit in input order into packs of at most `pack_tokens` rows (default: the
         smaller of GQ_PREFILL_CHUNK and the model's context) -- and every pack is ONE prompt pass (`Transformer.score_packed_native`:
         varlen attention, the weights read once per pack instead of once per sequence); a sequence longer than a pack goes through
         `score`.  A packed result is a rounding of the same model as `score`'s, not bit-equal to it: the GEMMs see other row counts.
         Validation, `precision` and `native` as in `score`: off the fused route (native=False, no fused form, the CPU) this is a loop
-        over `score`, and native=True raises instead of falling back.  fp16 KV cache."""
+        over `score`, and native=True raises instead of falling back.  fp16 KV cache.  lm_head_dtype as in `score`."""
         seqs = [self._checked_ids(ids, "score_many") for ids in list_of_ids]
-        res = self._score_packs(seqs, [None] * len(seqs), pack_tokens, precision, native, "score_many")
+        res = self._score_packs(seqs, [None] * len(seqs), pack_tokens, precision, native, "score_many", lm_head_dtype)
         return [dict(logprobs=lp, greedy=g, nll=float(-lp.double().mean())) for lp, g in res]
 
-    def loglikelihood_many(self, pairs, pack_tokens=None, precision=None, native=None):
+    def loglikelihood_many(self, pairs, pack_tokens=None, precision=None, native=None, lm_head_dtype=None):
         """`loglikelihood` for many (context, continuation) pairs -- the requests lm-eval issues by the thousand: a list of (sum of the
         continuation's log-probabilities, all of them greedy) in input order, packed like `score_many`.  Only the rows that predict a
-        continuation token reach the final norm and the lm_head."""
+        continuation token reach the final norm and the lm_head.  lm_head_dtype as in `score`."""
         seqs, tails = [], []
         for ctx, cont in pairs:
             ctx, cont = torch.as_tensor(ctx).reshape(-1), torch.as_tensor(cont).reshape(-1)
@@ -830,7 +849,7 @@ class AnyPrecisionForCausalLM(nn.Module):
                 raise ValueError("loglikelihood_many: a context and a continuation of at least one token each")
             seqs.append(self._checked_ids(torch.cat([ctx.cpu(), cont.cpu()]), "loglikelihood_many"))
             tails.append(int(cont.numel()))
-        res = self._score_packs(seqs, tails, pack_tokens, precision, native, "loglikelihood_many")
+        res = self._score_packs(seqs, tails, pack_tokens, precision, native, "loglikelihood_many", lm_head_dtype)
         return [(float(lp.double().sum()), bool(g.all())) for lp, g in res]
 
     # -- route 1: the fused decode model ---------------------------------------------------------------------------------
@@ -912,6 +931,15 @@ class AnyPrecisionForCausalLM(nn.Module):
             req["streamer"].end()
         return out
 
+    def _request_head(self, dec, lm_head_dtype):
+        """the decoder with the request's head: fp16 without the keyword, whatever an earlier request left on it"""
+        if dec.lm_head_dtype != lm_head_dtype:
+            self._evict("graph")  # (a switch re-allocates the step's buffers: no cached graph survives it, whichever head it was captured under)
+            try:
+                dec.set_lm_head_dtype(lm_head_dtype)
+            except ValueError as e:
+                raise ValueError(str(e) if str(e).startswith("lm_head_dtype='int8': ") else "lm_head_dtype='int8': " + str(e)) from None
+
     def _generate_native(self, dec, req, chunk=32, kv_cache_dtype="fp16", logprobs=False, top_logprobs=0, lm_head_dtype="fp16", adjust=None):
         from . import generate as gen
         ids, T, max_new = req["ids"].to(self.device), req["T"], req["max_new"]
@@ -923,13 +951,8 @@ class AnyPrecisionForCausalLM(nn.Module):
         # only; a longer cache costs memory, not time).  Beyond 16384 positions the request's own length.
         cap = total if total > 16384 else max(256, 1 << (total - 1).bit_length())
         dec.setup_caches(1, min(cap, dec.config.block_size), kv_cache_dtype=kv_cache_dtype)
-        if dec.lm_head_dtype != lm_head_dtype:  # (the request's head, fp16 without the keyword)
-            self._evict("graph")  # (a switch re-allocates the step's buffers: no cached graph survives it, whichever head it was captured under)
-            try:
-                dec.set_lm_head_dtype(lm_head_dtype)
-            except ValueError as e:
-                raise ValueError(str(e) if str(e).startswith("lm_head_dtype='int8': ") else "lm_head_dtype='int8': " + str(e)) from None
-        key = (self.precision, dec.max_seq_length, dec.kv_cache_dtype, req["temperature"], req["top_k"], req["top_p"], req["repetition_penalty"], req["suppress_tokens"]) \
+        self._request_head(dec, lm_head_dtype)
+        key =(self.precision, dec.max_seq_length, dec.kv_cache_dtype, req["temperature"], req["top_k"], req["top_p"], req["repetition_penalty"], req["suppress_tokens"]) \
             + ((("logprobs", True), ) if logprobs else ()) + ((("min_p", req["min_p"]), ) if req["min_p"] else ()) \
             + ((("top_logprobs", top_logprobs), ) if top_logprobs else ()) + ((("lm_head", "int8"), ) if lm_head_dtype == "int8" else ()) \
             + tuple((k, tuple(sorted(v.items())) if isinstance(v, dict) else v.key() if k == "token_fsm" else v) for k, v in sorted((adjust or {}).items()))

@@ -38,6 +38,7 @@ EXPORTS = [
     "gq_head_nll_topn_ws_bytes", "gq_head_nll_topn",
     "gq_rope_cache_rows_kv8r", "gq_attn_decode_roped_kv8r", "gq_attn_prefill_kv8r",
     "gq_rope_cache_rows_mx4", "gq_attn_decode_roped_mx4", "gq_attn_prefill_mx4",
+    "gq_head_nll_i8", "gq_head_nll_i8_topn",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -218,6 +219,9 @@ def lib():
         # (the top-n form: top_n, top_ids, top_lps behind top1; top_n behind splits for the workspace)
         L.gq_head_nll_topn_ws_bytes.argtypes = [u32, u32, u32, u32, i32]
         L.gq_head_nll_topn.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp, i32, vp, vp, u32, vp, ctypes.c_size_t, vp]
+        # the int8 head's forms: scale behind Wq, the rest as above
+        L.gq_head_nll_i8.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, u32, vp, ctypes.c_size_t, vp]
+        L.gq_head_nll_i8_topn.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, i32, vp, vp, u32, vp, ctypes.c_size_t, vp]
         L.gq_anyprec_pack.argtypes = [vp, vp, u32, u32, i32, vp]
         L.gq_lnq_cd_block.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, vp]
         L.gq_debug_set_timing_buffer.argtypes = [vp]

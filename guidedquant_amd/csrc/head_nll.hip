@@ -37,10 +37,24 @@
 //     list and of the split's list among the 2 n by counting (v_readlane over the other list), the first n go through LDS to their
 //     rank, and lane j stores id_j and fp32(logit_j) - lse -- the subtraction logprob is made by, against the same lse.
 // No float atomics, no register array under a run-time index, no integer division in the tile loop.
+//
+// gq_head_nll_i8 / gq_head_nll_i8_topn score the int8 lm_head of the decode step (W8A16: head_q8.hip's model) through the SAME kernel
+// text, head_nll_kernel<TOPN, true>: logit = fp16(fl32(scale[v] * sum_k xn[s][k] q[v][k])).  Only the operand path and one multiply differ:
+//   * a step's W tile is 128 rows x 64 BYTES: two 16-byte loads per thread (row id >> 2, 16 codes each) where the fp16 tile takes four,
+//     one step ahead in two named registers, like the fp16 loads;
+//   * between the load and the LDS store every code becomes the fp16 integer it is (q8_conv.h: xor, two v_perm_b32, v_pk_add_f16 -- once
+//     per block and element), so sW holds fp16 numbers and the LDS reads and the MFMA loop are the fp16 instance's.  The products of
+//     fp16 integers with fp16 activations are exact in the fp32 accumulator's multiplier, as in the decode GEMV;
+//   * the tile's 128 fp32 scales (scale[min(v, V - 1)]) are requested with the tile's first step by threads 0..127, stored to LDS with it
+//     (512 bytes) and read as one float4 per score block in the epilogue: no scale lives in a register across the K loop.  The
+//     accumulators are multiplied in place, in fp32, in front of the ONE fp16 rounding; the top-n candidates and the softmax then read
+//     the same rounded logits, and everything behind them -- lists, partials, both merge kernels, the splits rule -- is shared.
+// The int8 MFMA is not used: it would want int8 activations, another model than the decode step's.
 #include <hip/hip_runtime.h>
 
 #include "gq_internal.h"
 #include "wave_util.h"
+#include "q8_conv.h"
 
 namespace {
 using u32 = uint32_t;
@@ -75,6 +89,14 @@ struct Lists<true> {
     int *id;
 };
 
+// the int8 instances' fp32 scale per vocabulary row [V] (nothing in the fp16 instances)
+template <bool Q8>
+struct RowScale {};
+template <>
+struct RowScale<true> {
+    const float *scale;
+};
+
 // (value, id) a in front of (value, id) b: the order of every list
 __device__ __forceinline__ bool in_front(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
 __device__ __forceinline__ float lane_f(float x, u32 lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), (int)lane)); }
@@ -93,12 +115,15 @@ __device__ __forceinline__ void fold(float &m, float &sum, float &tl, float &bv,
 
 // (two blocks per CU for the top-n instance by request: left to itself the compiler took 308 registers for it, one block per CU; the
 // plain instance keeps the bounds, and the code, it always had)
-template <bool TOPN>
+// Q8: W is the int8 head, BV x BKK BYTES per step (two 16-byte loads per thread: row id >> 2, columns 16 (id & 3) .. + 15), turned into
+// fp16 integers between the load and the LDS store; q8.scale rides through LDS beside the tile and meets the accumulators once per tile.
+template <bool TOPN, bool Q8>
 __global__ void __launch_bounds__(256, TOPN ? 2 : 1) head_nll_kernel(const uint16_t *__restrict__ xn, const uint16_t *__restrict__ W, const int *__restrict__ target,
-                                                       u32 S, u32 V, u32 D, u32 tiles_per_split, Partials ws, Lists<TOPN> top) {
+                                                       u32 S, u32 V, u32 D, u32 tiles_per_split, Partials ws, Lists<TOPN> top, RowScale<Q8> q8) {
     __shared__ __attribute__((aligned(16))) h16 sW[BV * LD];
     __shared__ __attribute__((aligned(16))) h16 sX[BS * LD];
     __shared__ uint2 sL[TOPN ? BS * TN : 1];  // {value bits, id} [row][slot]; rows 32 w .. 32 w + 31 are wave w's alone
+    __shared__ __attribute__((aligned(16))) float sS[Q8 ? BV : 4];  // the tile's row scales (the int8 instances)
 
     const u32 tid = threadIdx.x, w = tid >> 6, l = tid & 63u, g = l >> 4, li = l & 15u;
     const u32 s0 = blockIdx.x * BS, split = blockIdx.y;
@@ -122,11 +147,34 @@ __global__ void __launch_bounds__(256, TOPN ? 2 : 1) head_nll_kernel(const uint1
         w_ = *reinterpret_cast<const uint4 *>(W + (size_t)v_ * D + (kc_) + 8u * (id_ & 7u));      \
         x_ = *reinterpret_cast<const uint4 *>(xn + xoff[i_] + (kc_));                             \
     }
-#define GQ_HEAD_LOAD_STEP(vt_, kc_) \
-    GQ_HEAD_LOAD(0, w0, x0, vt_, kc_) GQ_HEAD_LOAD(1, w1, x1, vt_, kc_) GQ_HEAD_LOAD(2, w2, x2, vt_, kc_) GQ_HEAD_LOAD(3, w3, x3, vt_, kc_)
+    // the int8 step: 16 codes per load (w0, w1), the four xn chunks as above, and with a tile's first step its 128 scales (sc, tid < BV)
+    float sc = 0.f;
+#define GQ_HEAD_LOADQ(i_, w_, vt_, kc_)                                                                                                  \
+    {                                                                                                                                    \
+        const u32 id_ = tid + 256u * (i_), v_ = min((vt_) * BV + (id_ >> 2), V - 1u);                                                    \
+        w_ = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(W) + (size_t)v_ * D + (kc_) + 16u * (id_ & 3u));         \
+    }
+#define GQ_HEAD_LOADX(i_, x_, kc_) x_ = *reinterpret_cast<const uint4 *>(xn + xoff[i_] + (kc_));
+#define GQ_HEAD_LOAD_STEP(vt_, kc_)                                                                                                          \
+    if constexpr (Q8) {                                                                                                                      \
+        GQ_HEAD_LOADQ(0, w0, vt_, kc_) GQ_HEAD_LOADQ(1, w1, vt_, kc_)                                                                        \
+        GQ_HEAD_LOADX(0, x0, kc_) GQ_HEAD_LOADX(1, x1, kc_) GQ_HEAD_LOADX(2, x2, kc_) GQ_HEAD_LOADX(3, x3, kc_)                              \
+        if ((kc_) == 0u && tid < BV) sc = q8.scale[min((vt_) * BV + tid, V - 1u)];                                                           \
+    } else {                                                                                                                                 \
+        GQ_HEAD_LOAD(0, w0, x0, vt_, kc_) GQ_HEAD_LOAD(1, w1, x1, vt_, kc_) GQ_HEAD_LOAD(2, w2, x2, vt_, kc_) GQ_HEAD_LOAD(3, w3, x3, vt_, kc_) \
+    }
 #define GQ_HEAD_STAGE(i_, w_, x_)                           \
     *reinterpret_cast<uint4 *>(&sW[srow[i_]]) = w_;         \
     *reinterpret_cast<uint4 *>(&sX[srow[i_]]) = x_;
+#define GQ_HEAD_STAGEQ(i_, w_)                                                           \
+    {                                                                                    \
+        const u32 id_ = tid + 256u * (i_), o_ = (id_ >> 2) * LD + 16u * (id_ & 3u);      \
+        uint4 lo_, hi_;                                                                  \
+        gqw::q8_row16(w_, lo_, hi_);                                                     \
+        *reinterpret_cast<uint4 *>(&sW[o_]) = lo_;                                       \
+        *reinterpret_cast<uint4 *>(&sW[o_ + 8u]) = hi_;                                  \
+    }
+#define GQ_HEAD_STAGEX(i_, x_) *reinterpret_cast<uint4 *>(&sX[srow[i_]]) = x_;
 
     // the wave's two columns per lane: rows s0 + 32 w + 16 b + li
     int tg[2];
@@ -160,7 +208,13 @@ __global__ void __launch_bounds__(256, TOPN ? 2 : 1) head_nll_kernel(const uint1
 
         for (u32 kc = 0; kc < D; kc += BKK) {
             __syncthreads();  // every wave is through with the step in LDS
-            GQ_HEAD_STAGE(0, w0, x0) GQ_HEAD_STAGE(1, w1, x1) GQ_HEAD_STAGE(2, w2, x2) GQ_HEAD_STAGE(3, w3, x3)
+            if constexpr (Q8) {  // (the barrier above is also behind the previous tile's epilogue, the last reader of sS)
+                GQ_HEAD_STAGEQ(0, w0) GQ_HEAD_STAGEQ(1, w1)
+                GQ_HEAD_STAGEX(0, x0) GQ_HEAD_STAGEX(1, x1) GQ_HEAD_STAGEX(2, x2) GQ_HEAD_STAGEX(3, x3)
+                if (kc == 0u && tid < BV) sS[tid] = sc;
+            } else {
+                GQ_HEAD_STAGE(0, w0, x0) GQ_HEAD_STAGE(1, w1, x1) GQ_HEAD_STAGE(2, w2, x2) GQ_HEAD_STAGE(3, w3, x3)
+            }
             __syncthreads();
             {  // the next step, of this tile or the first of the next one, in flight under the products below
                 u32 nk = kc + BKK, nt = vt;
@@ -185,6 +239,16 @@ __global__ void __launch_bounds__(256, TOPN ? 2 : 1) head_nll_kernel(const uint1
 
         // the tile's 128 logits of each column: rounded to fp16 once, then the online softmax, the target and the best pair
         const u32 vb = vt * BV + 4u * g;
+        if constexpr (Q8) {  // scale[v] * acc in fp32, in place: the ONE fp16 rounding below is then the model's (include/gq_hip.h)
+#pragma unroll
+            for (u32 a = 0; a < 8; a++) {
+                const float4 s4 = *reinterpret_cast<const float4 *>(&sS[16u * a + 4u * g]);
+#pragma unroll
+                for (u32 b = 0; b < 2; b++) {
+                    acc[a][b][0] *= s4.x, acc[a][b][1] *= s4.y, acc[a][b][2] *= s4.z, acc[a][b][3] *= s4.w;
+                }
+            }
+        }
         if constexpr (TOPN) {  // (from the accumulators, in front of the softmax, four logits at a time)
 #pragma unroll
             for (u32 b = 0; b < 2; b++) {
@@ -256,6 +320,10 @@ __global__ void __launch_bounds__(256, TOPN ? 2 : 1) head_nll_kernel(const uint1
 #undef GQ_HEAD_LOAD_STEP
 #undef GQ_HEAD_LOAD
 #undef GQ_HEAD_STAGE
+#undef GQ_HEAD_LOADQ
+#undef GQ_HEAD_LOADX
+#undef GQ_HEAD_STAGEQ
+#undef GQ_HEAD_STAGEX
     // the four lane groups of a column, then one partial per (row, split)
 #pragma unroll
     for (u32 b = 0; b < 2; b++) {
@@ -377,8 +445,8 @@ extern "C" int gq_head_nll(const void *xn, const void *W, const int *target, uin
     float *f = (float *)ws;
     const Partials p = {f, f + plane, f + 2 * plane, f + 3 * plane, (int *)(f + 4 * plane)};
     const u32 ntiles = (V + BV - 1u) / BV, tps = (ntiles + ns - 1u) / ns;
-    hipLaunchKernelGGL(head_nll_kernel<false>, dim3((S + BS - 1u) / BS, ns), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)xn, (const uint16_t *)W,
-                       target, S, V, D, tps, p, Lists<false>{});
+    hipLaunchKernelGGL((head_nll_kernel<false, false>), dim3((S + BS - 1u) / BS, ns), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)xn,
+                       (const uint16_t *)W, target, S, V, D, tps, p, Lists<false>{}, RowScale<false>{});
     GQ_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(head_nll_merge_kernel, dim3((S + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, p, target, S, ns, logprob, lse, top1);
     GQ_HIP_CHECK(hipGetLastError());
@@ -413,8 +481,8 @@ extern "C" int gq_head_nll_topn(const void *xn, const void *W, const int *target
     float *z = lse ? lse : f + 5 * plane;
     const Lists<true> lists = {n, f + 5 * plane + S, (int *)(f + 5 * plane + S + plane * n)};
     const u32 ntiles = (V + BV - 1u) / BV, tps = (ntiles + ns - 1u) / ns;
-    hipLaunchKernelGGL(head_nll_kernel<true>, dim3((S + BS - 1u) / BS, ns), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)xn, (const uint16_t *)W,
-                       target, S, V, D, tps, p, lists);
+    hipLaunchKernelGGL((head_nll_kernel<true, false>), dim3((S + BS - 1u) / BS, ns), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)xn,
+                       (const uint16_t *)W, target, S, V, D, tps, p, lists, RowScale<false>{});
     GQ_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(head_nll_merge_kernel, dim3((S + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, p, target, S, ns, logprob, z, top1);
     GQ_HIP_CHECK(hipGetLastError());
@@ -422,4 +490,54 @@ extern "C" int gq_head_nll_topn(const void *xn, const void *W, const int *target
                        ns, n, (const float *)z, top_ids, top_lps);
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
+}
+
+// the int8 head: both entries, top_n == 0 the plain one.  The checks, the workspaces and the launches behind the pass are the fp16 entries'.
+static int head_nll_i8(const void *xn, const void *Wq, const float *scale, const int *target, u32 S, u32 V, u32 D, float *logprob, float *lse, int *top1,
+                       int top_n, int *top_ids, float *top_lps, u32 splits, void *ws, size_t ws_bytes, void *stream) {
+    if (D == 0 || D % 64u != 0) return gq_fail(GQ_ENOTSUP, "gq_head_nll_i8: D must be a multiple of 64.");
+    if (S == 0 || V == 0) return gq_fail(GQ_EINVAL, "gq_head_nll_i8: S >= 1 and V >= 1.");
+    if (!xn || !Wq || !scale || !target || !logprob || !ws || (top_n && (!top_ids || !top_lps))) return gq_fail(GQ_EINVAL, "null pointer argument.");
+    if (((uintptr_t)xn | (uintptr_t)Wq) & 15u) return gq_fail(GQ_EINVAL, "gq_head_nll_i8: 16-byte aligned xn and Wq.");
+    if (((uintptr_t)scale | (uintptr_t)target | (uintptr_t)logprob | (uintptr_t)lse | (uintptr_t)top1 | (uintptr_t)top_ids | (uintptr_t)top_lps | (uintptr_t)ws) & 3u)
+        return gq_fail(GQ_EINVAL, "gq_head_nll_i8: 4-byte aligned scale, target, outputs and workspace.");
+    if (V > 0x7FFFFF00u || (uint64_t)S * D > 0xFFFFFFFFull) return gq_fail(GQ_ENOTSUP, "gq_head_nll_i8: V below 2^31, S * D below 2^32.");
+    if (splits > MAX_SPLITS) return gq_fail(GQ_EINVAL, "gq_head_nll_i8: at most 65535 splits.");
+    const u32 ns = pick_splits(S, V, splits), n = (u32)top_n;
+    const size_t plane = (size_t)ns * S;
+    if (ws_bytes < (plane * 5u + (n ? S + plane * n * 2u : 0u)) * sizeof(float))
+        return gq_fail(GQ_EINVAL, "gq_head_nll_i8: workspace smaller than gq_head_nll_ws_bytes / gq_head_nll_topn_ws_bytes.");
+    float *f = (float *)ws;
+    const Partials p = {f, f + plane, f + 2 * plane, f + 3 * plane, (int *)(f + 4 * plane)};
+    float *z = (lse || !n) ? lse : f + 5 * plane;
+    const Lists<true> lists = {n, f + 5 * plane + S, (int *)(f + 5 * plane + S + plane * n)};
+    const u32 ntiles = (V + BV - 1u) / BV, tps = (ntiles + ns - 1u) / ns;
+    const dim3 grid((S + BS - 1u) / BS, ns);
+    if (n)
+        hipLaunchKernelGGL((head_nll_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t *)xn, (const uint16_t *)Wq, target, S, V, D,
+                           tps, p, lists, RowScale<true>{scale});
+    else
+        hipLaunchKernelGGL((head_nll_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t *)xn, (const uint16_t *)Wq, target, S, V, D,
+                           tps, p, Lists<false>{}, RowScale<true>{scale});
+    GQ_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(head_nll_merge_kernel, dim3((S + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, p, target, S, ns, logprob, z, top1);
+    GQ_HIP_CHECK(hipGetLastError());
+    if (n) {
+        hipLaunchKernelGGL(head_nll_topn_merge_kernel, dim3((S + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, (const float *)lists.val, (const int *)lists.id,
+                           S, ns, n, (const float *)z, top_ids, top_lps);
+        GQ_HIP_CHECK(hipGetLastError());
+    }
+    return GQ_OK;
+}
+
+extern "C" int gq_head_nll_i8(const void *xn, const void *Wq, const float *scale, const int *target, uint32_t S, uint32_t V, uint32_t D, float *logprob,
+                              float *lse, int *top1, uint32_t splits, void *ws, size_t ws_bytes, void *stream) {
+    return head_nll_i8(xn, Wq, scale, target, S, V, D, logprob, lse, top1, 0, nullptr, nullptr, splits, ws, ws_bytes, stream);
+}
+
+extern "C" int gq_head_nll_i8_topn(const void *xn, const void *Wq, const float *scale, const int *target, uint32_t S, uint32_t V, uint32_t D, float *logprob,
+                                   float *lse, int *top1, int top_n, int *top_ids, float *top_lps, uint32_t splits, void *ws, size_t ws_bytes,
+                                   void *stream) {
+    if (top_n < 1 || top_n > (int)TN) return gq_fail(GQ_EINVAL, "gq_head_nll_i8_topn: top_n must be in 1..20.");
+    return head_nll_i8(xn, Wq, scale, target, S, V, D, logprob, lse, top1, top_n, top_ids, top_lps, splits, ws, ws_bytes, stream);
 }

@@ -5,16 +5,14 @@
 // a wave reduction, lane 0 stores.  A 16-byte load holds 16 weights per lane, so a wave covers 1024 columns per step; with
 // K % 1024 == 512 the upper half of the wave sits out the last step.
 //
-// int8 -> fp16 (1.75 VALU instructions per weight; the stream leaves room for about 2): one v_xor turns the four bytes of a dword into
-// biased codes q + 128, two v_perm_b32 place each under the high byte 0x64 -- the fp16 number 1024 + (q + 128), exact -- and one
-// v_pk_add_f16 of -1152 per pair gives q itself, exact again (|q| <= 128, every intermediate an integer below 2048).  The signed value
-// exists BEFORE the product: nothing biased is accumulated, no correction term is subtracted from a sum.
+// int8 -> fp16: q8_conv.h (q8_pair), exact for -128..127, the signed value BEFORE the product.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "gq_internal.h"
 #include "wave_util.h"
 #include "dense_stage.h"
+#include "q8_conv.h"
 
 namespace {
 
@@ -22,17 +20,9 @@ typedef uint32_t u32;
 using gqw::h16;
 using gqw::h16x2;
 using gqw::h2u;
+using gqw::q8_pair;
 using gqw::u32x4;
 using gqw::wave_reduce_bcast;
-
-// the signed fp16 pair of bytes (2 * HI, 2 * HI + 1) of a dword of biased codes (b = q ^ 0x80)
-template <int HI>
-__device__ __forceinline__ h16x2 q8_pair(u32 biased) {
-    // v_perm_b32: selector bytes 0..3 take the bytes of the second operand, 4..7 those of the first
-    const u32 p = __builtin_amdgcn_perm(0x64646464u, biased, HI ? 0x04030402u : 0x04010400u);  // (0x64, b1, 0x64, b0): 1024 + b each
-    const h16 off = (h16)-1152.0f;
-    return __builtin_bit_cast(h16x2, p) + (h16x2){off, off};
-}
 
 template <int RW>
 __global__ void __launch_bounds__(256) dense_gemv_i8_kernel(const uint16_t *x, const uint8_t *Wq, const float *scale, uint16_t *out, u32 N, u32 K,

@@ -520,7 +520,8 @@ class Transformer(nn.Module):
         """The head of the fused decode step: None / "fp16" (the default: gq_dense_gemv_f16 over `output.weight`, as the reference) or
         "int8" (gq_dense_gemv_i8 over a weight-only int8 copy with one fp32 scale per row, head_q8.quantize_rows_int8).  "int8"
         quantises `output.weight` once, on its device, into tensors that are no part of the state_dict, and keeps `output.weight`: the
-        prompt pass, `score()` and the module forward read the fp16 head, a tied embedding is untouched.  Cost: N*K + 4N bytes NEXT TO
+        prompt pass and the module forward read the fp16 head, `score()` reads it unless asked for lm_head_dtype="int8"
+        (`score_native`), a tied embedding is untouched.  Cost: N*K + 4N bytes NEXT TO
         the fp16 head (0.53 GB for the 128256 x 4096 head of Llama-3.1-8B).  The copy is rebuilt when `output.weight` is another tensor
         or has been written (load_state_dict, .to() / .half(), an in-place write), not when the caches grow.  ValueError on a CPU model
         or a head that is not fp16."""
@@ -762,14 +763,15 @@ class Transformer(nn.Module):
     # (8B geometry: 3.2 against 3.6 ms at 2048 rows, 6.4 against 7.1 ms at 4096; profiles/score_head.json)
     SCORE_HEAD_AUTO = "1"
 
-    def _score_head(self, x: Tensor, targets: Tensor, kernel: bool, top_n: int = 0):
+    def _score_head(self, x: Tensor, targets: Tensor, kernel: bool, top_n: int = 0, q8: bool = False):
         """the scoring head on the residual rows x fp16 [n, D] and targets int32 [n] (negative: ignored, logprob 0): (logprob fp32 [n],
         top1 [n]).  Both forms read the fp16 rows norm(x) the logits head feeds to `self.output`: the kernel gq_head_nll
         (csrc/head_nll.hip; no logits in memory), or output -> float -> log_softmax -> gather / argmax in blocks of SCORE_HEAD_ROWS rows.
-        top_n in 1..20 adds (ids int64 [n, top_n], log-probabilities fp32 [n, top_n]): gq_head_nll_topn, or a stable sort in the torch head."""
-        return native_prompt.score_head(self, x, targets, kernel, top_n)
+        top_n in 1..20 adds (ids int64 [n, top_n], log-probabilities fp32 [n, top_n]): gq_head_nll_topn, or a stable sort in the torch head.
+        q8: the int8 head `head_q8()` in place of `output.weight` (gq_head_nll_i8 / gq_head_nll_i8_topn, or native_prompt.logits_q8)."""
+        return native_prompt.score_head(self, x, targets, kernel, top_n, q8)
 
-    def score_native(self, idx: Tensor, chunk: Optional[int] = None, top_logprobs: Optional[int] = None):
+    def score_native(self, idx: Tensor, chunk: Optional[int] = None, top_logprobs: Optional[int] = None, lm_head_dtype=None):
         """Log-probabilities of a token sequence on the HIP prompt pass: (logprob fp32 [S - 1], greedy bool [S - 1]) with
         logprob[i] = log p(idx[i + 1] | idx[:i + 1]) and greedy[i] = (the most probable next token == idx[i + 1]) -- what the module tree's
         `labels=` loss and lm-eval's loglikelihood are made of.  The pass is `prefill_native`'s from position 0 (the same pieces, caches,
@@ -780,10 +782,13 @@ class Transformer(nn.Module):
         top_logprobs=n (1..20; anything else but None: ValueError) adds two results, (ids int64 [S - 1, n], fp32 [S - 1, n]): the n most
         probable tokens of the distribution logprob[i] was taken from, most probable first, equal logits by ascending id, with their
         log-probabilities -- selected inside the head's own launch (gq_head_nll_topn; the plan then says "hip-nll-topn"), or by a stable
-        sort behind the torch head.  Without the keyword the pass makes the calls it always made."""
-        return native_prompt.score(self, idx, chunk, top_logprobs)
+        sort behind the torch head.  Without the keyword the pass makes the calls it always made.
+        lm_head_dtype: None / "fp16" score `output.weight`, on an int8-head model too; "int8" scores the head the decode step reads,
+        logit = fp16(scale[v] * sum_k xn[k] q[v][k]) over `head_q8()` (gq_head_nll_i8 / gq_head_nll_i8_topn, or the torch form in blocks;
+        the plan says "hip-nll-i8" | "hip-nll-i8-topn" | "torch-i8") and needs `set_lm_head_dtype("int8")` first, else ValueError."""
+        return native_prompt.score(self, idx, chunk, top_logprobs, lm_head_dtype)
 
-    def score_packed_native(self, seqs, rows: Optional[Tensor] = None):
+    def score_packed_native(self, seqs, rows: Optional[Tensor] = None, lm_head_dtype=None):
         """Log-probabilities of SEVERAL token sequences in one HIP prompt pass (varlen attention): the sequences are laid end to end as
         one run of S rows from cache row 0 and go through every layer as ONE piece, so the weights are read once per pack.  Row i is
         rotated by its position inside its own sequence (gq_rope_cache_rows_packed) and attends only rows of its own sequence, causally
@@ -791,8 +796,8 @@ class Transformer(nn.Module):
         block-diagonal mask).  `rows` (bool [S]): only these rows reach the final norm and the scoring head.  Returns (logprob fp32 [k],
         hit bool [k]) over the head's rows in packed order (native_prompt.score_packed).  fp16 caches only; the caches grow to S rows
         where they are smaller and hold the pack afterwards.  `last_prefill_plan` records chunks=[(0, S)], attn "hip-packed" |
-        "sdpa-packed" per layer, the head and packed=dict(sequences, rows, head_rows)."""
-        return native_prompt.score_packed(self, seqs, rows)
+        "sdpa-packed" per layer, the head and packed=dict(sequences, rows, head_rows).  lm_head_dtype: as in `score_native`."""
+        return native_prompt.score_packed(self, seqs, rows, lm_head_dtype)
 
     def decode_native(self, tok: Tensor, pos: Tensor) -> Tensor:
         """One bs=1 decode step.  tok, pos: int32 device tensors with one element.  Returns logits fp16 [1,1,V]

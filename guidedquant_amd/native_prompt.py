@@ -10,7 +10,8 @@ through the C ABI (include/gq_hip.h) and the quantized linears' own forwards.
     torch SDPA over the cache rows [0, start + S).
   * the heads: logits (`Transformer.output`), or the scoring head (`score_head`: gq_head_nll, or log_softmax in row blocks), chosen by
     `score_head_choice`, a pure function of the GQ_SCORE_HEAD mode.  With `top_logprobs=n` the head also lists every row's n most probable
-    tokens (gq_head_nll_topn, or `top_rows` behind the torch head).
+    tokens (gq_head_nll_topn, or `top_rows` behind the torch head).  With `lm_head_dtype="int8"` the head reads the model's int8 copy
+    (gq_head_nll_i8 / gq_head_nll_i8_topn, or `logits_q8` in front of the torch steps): the model the decode step decodes.
 
   * packed scoring: `pack_plan` (first fit in input order) and `score_packed` -- several short sequences as ONE piece, `_PackedPiece`'s
     `rows_and_attention` through gq_rope_cache_rows_packed and gq_attn_prefill_packed (or SDPA under the block-diagonal `packed_mask`).
@@ -144,7 +145,7 @@ def _run_piece(model, idx, input_pos, start: int, bufs: dict, plan: str, head: b
         return None
     x = x + pending
     if score is not None:
-        return score_head(model, x, score["targets"], score["kernel"], score.get("top_n", 0))
+        return score_head(model, x, score["targets"], score["kernel"], score.get("top_n", 0), **({"q8": True} if score.get("q8") else {}))
     x = x[-1:] if last_only else x
     return model.output(model.norm(x)).view(1, -1, cfg.vocab_size)
 
@@ -283,10 +284,58 @@ def top_rows(logits: Tensor, ls: Tensor, n: int):
     return ids, lps
 
 
-def score_head(model, x, targets, kernel: bool, top_n: int = 0):
+SCORE_HEAD_Q8_COLS = 16384  # vocabulary rows per block of the torch int8 head: its fp32 copy of the codes stays at 16384 x D x 4 bytes
+
+
+def head_request(model, lm_head_dtype) -> bool:
+    """the `lm_head_dtype` of a scoring request: False for None / "fp16" (whatever head the model decodes with), True for "int8", which
+    the model must already hold (`Transformer.set_lm_head_dtype`)"""
+    from .head_q8 import lm_head_dtype_name
+    if lm_head_dtype is None or lm_head_dtype_name(lm_head_dtype) == "fp16":
+        return False
+    if model.lm_head_dtype != "int8":
+        raise ValueError("lm_head_dtype='int8': the model's head is fp16 (set_lm_head_dtype('int8') first)")
+    return True
+
+
+def logits_q8(xn: Tensor, q: Tensor, scale: Tensor) -> Tensor:
+    """the torch definition of the int8 head's logits on fp16 rows xn [n, D]: fp16((xn.float() @ q.float().T) * scale), in blocks of
+    SCORE_HEAD_Q8_COLS vocabulary rows so that no [V, D] fp32 copy of the head exists"""
+    xf = xn.float()
+    out = torch.empty((xn.shape[0], q.shape[0]), dtype=torch.float16, device=xn.device)
+    for v in range(0, q.shape[0], SCORE_HEAD_Q8_COLS):
+        out[:, v:v + SCORE_HEAD_Q8_COLS] = ((xf @ q[v:v + SCORE_HEAD_Q8_COLS].float().T) * scale[None, v:v + SCORE_HEAD_Q8_COLS]).half()
+    return out
+
+
+def score_head(model, x, targets, kernel: bool, top_n: int = 0, q8: bool = False):
     """`Transformer._score_head`: the kernel gq_head_nll, or the torch head in blocks of the model's SCORE_HEAD_ROWS rows.  With top_n
-    the kernel is gq_head_nll_topn, the torch head adds `top_rows`, and the result gains (ids int64 [n, top_n], fp32 [n, top_n])"""
+    the kernel is gq_head_nll_topn, the torch head adds `top_rows`, and the result gains (ids int64 [n, top_n], fp32 [n, top_n]).
+    q8: the model's int8 head (`model.head_q8()`) in place of `output.weight` -- gq_head_nll_i8 / gq_head_nll_i8_topn, or `logits_q8`
+    in front of the same torch steps"""
     n, V = x.shape[0], model.config.vocab_size
+    if kernel and q8:
+        L = _lib.lib()
+        xn = model.norm(x).contiguous()
+        q, scale = model.head_q8()
+        assert xn.dtype == torch.float16 and q.dtype == torch.int8 and q.is_contiguous() and scale.dtype == torch.float32 and scale.numel() == V
+        assert targets.dtype == torch.int32 and targets.numel() == n
+        lp = torch.empty(n, dtype=torch.float32, device=x.device)
+        top1 = torch.empty(n, dtype=torch.int32, device=x.device)
+        head = (xn.data_ptr(), q.data_ptr(), scale.data_ptr(), targets.data_ptr(), n, V, xn.shape[1], lp.data_ptr(), None, top1.data_ptr())
+        with torch.cuda.device(x.device):
+            if top_n:
+                ids = torch.empty((n, top_n), dtype=torch.int32, device=x.device)
+                lps = torch.empty((n, top_n), dtype=torch.float32, device=x.device)
+                nws = int(L.gq_head_nll_topn_ws_bytes(n, V, xn.shape[1], 0, top_n))
+                ws = torch.empty(max(nws, 4), dtype=torch.uint8, device=x.device)
+                _lib.check(L.gq_head_nll_i8_topn(*head, top_n, ids.data_ptr(), lps.data_ptr(), 0, ws.data_ptr(), nws, _lib.current_stream_ptr()),
+                           "gq_head_nll_i8_topn")
+                return lp, top1, ids.long(), lps
+            nws = int(L.gq_head_nll_ws_bytes(n, V, xn.shape[1], 0))
+            ws = torch.empty(max(nws, 4), dtype=torch.uint8, device=x.device)
+            _lib.check(L.gq_head_nll_i8(*head, 0, ws.data_ptr(), nws, _lib.current_stream_ptr()), "gq_head_nll_i8")
+        return lp, top1
     if kernel:
         L = _lib.lib()
         xn = model.norm(x).contiguous()
@@ -311,7 +360,8 @@ def score_head(model, x, targets, kernel: bool, top_n: int = 0):
     lps, tops, lists = [], [], []
     for a in range(0, n, model.SCORE_HEAD_ROWS):
         t = targets[a:a + model.SCORE_HEAD_ROWS].long()
-        logits = model.output(model.norm(x[a:a + model.SCORE_HEAD_ROWS]))
+        xn = model.norm(x[a:a + model.SCORE_HEAD_ROWS])
+        logits = logits_q8(xn, *model.head_q8()) if q8 else model.output(xn)
         ls = F.log_softmax(logits.float(), dim=-1)
         lp = ls.gather(1, t.clamp(min=0)[:, None])[:, 0]
         lps.append(torch.where(t >= 0, lp, torch.zeros_like(lp)))
@@ -323,9 +373,17 @@ def score_head(model, x, targets, kernel: bool, top_n: int = 0):
     return torch.cat(lps), torch.cat(tops)
 
 
-def score(model, idx, chunk: Optional[int] = None, top_logprobs: Optional[int] = None):
+def head_name(kernel: bool, top_n: int, q8: bool) -> str:
+    """`last_prefill_plan["head"]`"""
+    if not kernel:
+        return "torch-i8" if q8 else "torch"
+    return "hip-nll" + ("-i8" if q8 else "") + ("-topn" if top_n else "")
+
+
+def score(model, idx, chunk: Optional[int] = None, top_logprobs: Optional[int] = None, lm_head_dtype=None):
     """`Transformer.score_native`: the pass from position 0 with the scoring head on every piece"""
     top_n = check_top_logprobs(top_logprobs)
+    q8 = head_request(model, lm_head_dtype)
     flat = idx.reshape(-1)
     S = flat.numel()
     assert model.prefill_ready(idx) and 2 <= S <= model.max_seq_length
@@ -334,8 +392,9 @@ def score(model, idx, chunk: Optional[int] = None, top_logprobs: Optional[int] =
     flat = flat.to(torch.int32)
     targets = torch.cat([flat[1:], torch.full((1, ), -1, dtype=torch.int32, device=flat.device)])
     pos = torch.arange(0, S, device=flat.device, dtype=torch.int32)
-    out = prompt_pass(model, flat, pos, 0, False, chunk, score=dict(targets=targets, kernel=kernel, **({"top_n": top_n} if top_n else {})))
-    model.last_prefill_plan["head"] = ("hip-nll-topn" if top_n else "hip-nll") if kernel else "torch"
+    out = prompt_pass(model, flat, pos, 0, False, chunk,
+                      score=dict(targets=targets, kernel=kernel, **({"top_n": top_n} if top_n else {}), **({"q8": True} if q8 else {})))
+    model.last_prefill_plan["head"] = head_name(kernel, top_n, q8)
     lp = torch.cat([o[0] for o in out])[:S - 1]
     top1 = torch.cat([o[1] for o in out])[:S - 1]
     if top_n:
@@ -410,7 +469,7 @@ class _PackedPiece(_Piece):
         return _sdpa_gqa(self.q.unsqueeze(0), kc[:1, :, :S], vc[:1, :, :S], self.masks[win], H // Hkv).transpose(1, 2).reshape(1, S, H * hd)
 
 
-def score_packed(model, seqs, rows: Optional[Tensor] = None):
+def score_packed(model, seqs, rows: Optional[Tensor] = None, lm_head_dtype=None):
     """`Transformer.score_packed_native`: the sequences `seqs` (1-D int tensors on the model's device, two tokens or more each) as ONE
     piece of S = sum of their lengths rows -- never chunked -- with the scoring head on the rows `rows` (bool [S]; None: every row).
     Returns (logprob fp32 [k], hit bool [k]) over the head's rows in packed order: logprob of the next token of the row's own sequence
@@ -419,6 +478,7 @@ def score_packed(model, seqs, rows: Optional[Tensor] = None):
         raise NotImplementedError("packed scoring: %s KV cache" % model.kv_cache_dtype)
     if getattr(model, "adapter", None) is not None:
         raise NotImplementedError("lora: packed scoring is not served under an adapter (score the sequences one by one)")
+    q8 = head_request(model, lm_head_dtype)
     cfg = model.config
     lens = [int(s.numel()) for s in seqs]
     if not lens or min(lens) < 2:
@@ -455,9 +515,9 @@ def score_packed(model, seqs, rows: Optional[Tensor] = None):
         sel = torch.nonzero(rows.to(dev)).reshape(-1)
         x, targets = x[sel] + pending[sel], targets[sel].contiguous()
     k = int(x.shape[0])
-    model.last_prefill_plan = dict(chunks=[(0, S)], attn=[plan] * len(model.layers), head="hip-nll" if kernel else "torch",
+    model.last_prefill_plan = dict(chunks=[(0, S)], attn=[plan] * len(model.layers), head=head_name(kernel, 0, q8),
                                    packed=dict(sequences=len(lens), rows=S, head_rows=k))
     if k == 0:
         return torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.bool, device=dev)
-    lp, top1 = score_head(model, x, targets, kernel)
+    lp, top1 = score_head(model, x, targets, kernel, **({"q8": True} if q8 else {}))
     return lp, top1 == targets

@@ -390,6 +390,25 @@ int gq_head_nll_topn(const void *xn, const void *W, const int *target, uint32_t 
                      size_t ws_bytes, void *stream);
 
 /*
+ * The scoring head over the int8 lm_head of the decode step (W8A16; csrc/head_nll.hip, the Q8 instances): what gq_head_nll and
+ * gq_head_nll_topn compute, of the model that gq_dense_gemv_i8 decodes.
+ *   xn fp16 [S][D], Wq int8 [V][D] contiguous, scale fp32 [V] (head_q8.quantize_rows_int8), target int [S]
+ *   acc[s][v]   = sum_k xn[s][k] * q[v][k]            fp32 accumulation on v_mfma_f32_16x16x32_f16 from exact products (every int8 code
+ *                                                     is an fp16 value)
+ *   logit[s][v] = fp16( fl32( scale[v] * acc[s][v] ) )   ONE fp16 rounding, behind the scale
+ * gq_dense_gemv_i8's formula in another summation order: a rounding of the same model, not bit-equal to the decode step's logits.
+ * Everything behind the logit is gq_head_nll's, unchanged: lse, logprob (0.0f for a negative target), the lowest-id top1, the `splits`
+ * rule, the partials and their ascending fold, D % 64 == 0 (else GQ_ENOTSUP), and for the _topn form top_n, top_ids, top_lps and their
+ * order.  The workspaces are gq_head_nll_ws_bytes / gq_head_nll_topn_ws_bytes for the same S, V, D, splits(, top_n); smaller: GQ_EINVAL.
+ * A NULL Wq or scale is GQ_EINVAL; nothing is written where an entry refuses.  xn and Wq 16-byte aligned.
+ */
+int gq_head_nll_i8(const void *xn, const void *Wq, const float *scale, const int *target, uint32_t S, uint32_t V, uint32_t D, float *logprob,
+                   float *lse, int *top1, uint32_t splits, void *ws, size_t ws_bytes, void *stream);
+int gq_head_nll_i8_topn(const void *xn, const void *Wq, const float *scale, const int *target, uint32_t S, uint32_t V, uint32_t D,
+                        float *logprob, float *lse, int *top1, int top_n, int *top_ids /* [S][top_n] */, float *top_lps /* [S][top_n] */,
+                        uint32_t splits, void *ws, size_t ws_bytes, void *stream);
+
+/*
  * Host (CPU) twins of the two Any-Precision entry points: same arguments with HOST pointers, no stream; `nthreads` <= 0
  * uses the OpenMP default.  They serve BASELINE.json configs[0] ("CPU reference APLinear path via generate.py"): the module
  * semantics of inference/APLinear.py:35-60 with the tensors in host memory (the reference hard-codes 'cuda',

@@ -2,6 +2,7 @@
 (any_precision/evaluate/eval.py:205-226: non-overlapping chunks of --chunk_size tokens, the mean of the chunks' mean negative
 log-likelihoods, exp of it; a shorter tail is dropped), the per-chunk values, the share of greedy hits.  No tokenizer and no dataset:
 --top_logprobs N adds the N most probable tokens of every position and their log-probabilities, per chunk;
+--lm_head_dtype int8 scores through the int8 copy of the lm_head, the model `generate(..., lm_head_dtype="int8")` decodes;
 the ids come from an .npy file or an .npz entry (--key, default the first array), the model from the arguments of
 guidedquant_amd/generate.py (`Transformer.score_native`: the HIP prompt pass with the scoring head; GQ_SCORE_HEAD picks the head).
     python tools/score_tokens.py tokens.npy --model_name meta-llama/Meta-Llama-3.1-8B --backend ap --bitwidth 2 --checkpoint_path DIR
@@ -42,6 +43,8 @@ def main():
     ap.add_argument("--random_init", action="store_true")
     ap.add_argument("--kv_cache_dtype", type=str, default=None, choices=["fp16", "fp8"])
     ap.add_argument("--top_logprobs", type=int, default=None, help="1..20: the n most probable tokens of every position, with their log-probabilities")
+    ap.add_argument("--lm_head_dtype", type=str, default=None, choices=["fp16", "int8"],
+                    help="int8: score the model the int8 lm_head decodes (Transformer.set_lm_head_dtype; the JSON line's head says hip-nll-i8)")
     a = ap.parse_args()
     import torch
     from guidedquant_amd.generate import load_model
@@ -55,6 +58,9 @@ def main():
     if a.chunk_size > model.config.block_size:
         raise SystemExit(f"--chunk_size {a.chunk_size} exceeds the model's context ({model.config.block_size})")
     model.setup_caches(1, a.chunk_size, kv_cache_dtype=a.kv_cache_dtype)
+    head = {"lm_head_dtype": "int8"} if a.lm_head_dtype == "int8" else {}
+    if head:
+        model.set_lm_head_dtype("int8")
     dev_ids = torch.from_numpy(ids[:n * a.chunk_size]).to(device=a.device, dtype=torch.int32)
     if not model.prefill_ready(dev_ids[:a.chunk_size]):
         raise SystemExit("the fused prompt pass does not serve this model on this device (no fallback)")
@@ -62,7 +68,7 @@ def main():
     with torch.no_grad():
         for i in range(n):
             lp, greedy, *lists = model.score_native(dev_ids[i * a.chunk_size:(i + 1) * a.chunk_size],
-                                                    **({} if a.top_logprobs is None else {"top_logprobs": a.top_logprobs}))
+                                                    **({} if a.top_logprobs is None else {"top_logprobs": a.top_logprobs}), **head)
             nlls.append(float(-lp.double().mean()))
             hits += int(greedy.sum())
             if lists:  # (per chunk, [chunk_size - 1][n] each)
