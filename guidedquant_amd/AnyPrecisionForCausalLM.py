@@ -620,7 +620,7 @@ class AnyPrecisionForCausalLM(nn.Module):
             return torch.cat(lps), torch.cat(tops), torch.cat([i for i, _ in lists]), torch.cat([v for _, v in lists])
         return torch.cat(lps), torch.cat(tops)
 
-    def score(self, input_ids, precision=None, kv_cache_dtype=None, native=None, top_logprobs=None, lm_head_dtype=None):
+    def score(self, input_ids, precision=None, kv_cache_dtype=None, native=None, top_logprobs=None, lm_head_dtype=None, ref_precision=None):
         """Log-probabilities of one token sequence ([1, T] or [T], T >= 2): dict(logprobs fp32 [T - 1], greedy bool [T - 1], nll float)
         with logprobs[i] = log p(ids[i + 1] | ids[:i + 1]), greedy[i] = (the most probable next token is ids[i + 1]) and nll the mean of
         -logprobs -- the `outputs.loss` of the module tree for `labels=input_ids` (any_precision/evaluate/eval.py:222-223).
@@ -638,13 +638,29 @@ class AnyPrecisionForCausalLM(nn.Module):
         lm_head (gq_head_nll_i8 / gq_head_nll_i8_topn; `Transformer.score_native`).  `generate`'s rules: it is the request's head -- fp16
         without the keyword, whatever an earlier request left on the decoder; native=False, the CPU or a checkpoint without a fused form
         raise ValueError("lm_head_dtype='int8': ..."), never a fall-back; the keyword never reaches the module tree.  It composes with
-        kv_cache_dtype= and top_logprobs=."""
+        kv_cache_dtype= and top_logprobs=.
+        ref_precision=r (one of the parent's precisions, else ValueError("ref_precision: ...")) measures how far the model at `precision`
+        is from the same parent at r: the dict gains `kl` fp32 [T - 1] -- KL(P_r || P_precision) of the distribution logprobs[i] was taken
+        from, in nats, not clamped at 0 -- `kl_mean` (float) and `top1_agree` bool [T - 1] (the two models' most probable tokens are the
+        same token).  Two passes: the reference pass at r keeps only its final-norm rows ([T, D] fp16), then the scoring pass at
+        `precision` runs the KL head beside the scoring head (gq_head_kl: the lm_head streamed once for both models, no [T, V] logits of
+        either; `Transformer.score_native(ref_hidden=)`).  logprobs, greedy and nll are those of the call without the keyword.  Off the
+        fused route the same definition comes from two module forwards (native_prompt.kl_rows).  Declined, never dropped:
+        ValueError("ref_precision: ...") together with top_logprobs or lm_head_dtype="int8", and through perplexity, loglikelihood,
+        score_many and loglikelihood_many."""
         from .head_q8 import lm_head_dtype_name
         from .model import kv_cache_dtype_name
         from .native_prompt import check_top_logprobs
         kv = kv_cache_dtype_name(kv_cache_dtype)
         hd = lm_head_dtype_name(lm_head_dtype)
         top_n = check_top_logprobs(top_logprobs)
+        if ref_precision is not None:
+            if isinstance(ref_precision, bool) or ref_precision not in self.precisions:
+                raise ValueError(f"ref_precision: {ref_precision!r} is not one of the parent's precisions {list(self.precisions)}")
+            if top_n:
+                raise ValueError("ref_precision: not served together with top_logprobs (two requests: one for the lists, one for the divergence)")
+            if hd == "int8":
+                raise ValueError("ref_precision: not served together with lm_head_dtype='int8' (the KL head compares two models over ONE fp16 lm_head)")
         ids = torch.as_tensor(input_ids)
         if ids.is_floating_point() or ids.dim() not in (1, 2) or (ids.dim() == 2 and ids.shape[0] != 1):
             raise ValueError("score: input_ids must be one sequence of token ids, [1, T] or [T]")
@@ -663,53 +679,84 @@ class AnyPrecisionForCausalLM(nn.Module):
         if self._adapter is not None and (native is False or kv != "fp16"):
             raise ValueError("lora: the adapter is served by the fused decode model with an fp16 cache only")
         prev_precision = self.precision
-        if precision is not None:
-            self.set_precision(precision)
         try:
-            dec, why = None, "opted out"
-            if native is not False:
-                if self.device.type != "cuda":
-                    why = "the fused routes need the GPU"
-                else:
-                    dec = self._native_decoder_or_none(self.precision, release_planes=native is True)
-                    why = getattr(self, "_no_native_reason", None) or "this checkpoint has no fused decode form at %d bits" % self.precision
-                    if dec is not None and T > dec.config.block_size:
-                        dec, why = None, f"{T} tokens exceed the fused model's context ({dec.config.block_size})"
-                    if dec is not None and kv != "fp16" and dec.kv8_unserved():
-                        dec, why = None, dec.kv8_unserved()
-                    if dec is not None and not dec.prefill_ready(ids.to(self.device).to(torch.int32)):
-                        dec, why = None, "the fused model's prompt pass does not serve this model"
-            if dec is None and kv != "fp16":
-                raise ValueError(f"kv_cache_dtype='{kv}': " + why)
-            if dec is None and hd == "int8":
-                raise ValueError("lm_head_dtype='int8': " + why)
-            if dec is None and self._adapter is not None:
-                raise ValueError("lora: " + why)
-            if dec is None and native is True:
-                raise ValueError("native=True: " + why)
-            if dec is not None:
-                self._request_head(dec, hd)
-                # the caches sized as `_generate_native` sizes them, and like there allocated OUTSIDE inference mode (tensors made inside
-                # it refuse in-place updates elsewhere: set_kv_scales, the module forward's cache write); graphs captured over caches
-                # about to be replaced go first
-                cap = min(T if T > 16384 else max(256, 1 << (T - 1).bit_length()), dec.config.block_size)
-                if not (dec.max_seq_length >= cap and dec.max_batch_size >= 1 and dec.kv_cache_dtype == kv):
-                    self._evict("graph")
-                dec.setup_caches(1, cap, kv_cache_dtype=kv)
-            lists = ()
-            with torch.inference_mode():
-                if dec is not None:
-                    lp, greedy, *lists = dec.score_native(ids.to(self.device).to(torch.int32), **({"top_logprobs": top_n} if top_n else {}),
-                                                          **({"lm_head_dtype": "int8"} if hd == "int8" else {}))
-                else:
-                    dev_ids = ids.to(self.device).long()
-                    logits = self.model(input_ids=dev_ids.view(1, -1)).logits[0, :-1]
-                    lp, top1, *lists = self._score_rows(logits, dev_ids[1:], **({"top_n": top_n} if top_n else {}))
-                    greedy = top1 == dev_ids[1:]
-            return dict(logprobs=lp, greedy=greedy, nll=float(-lp.double().mean()),
-                        **(dict(top_logprobs_ids=lists[0], top_logprobs=lists[1]) if top_n else {}))
+            ref = None
+            if ref_precision is not None:  # the reference pass first: it leaves its rows, the scoring pass everything else
+                self.set_precision(ref_precision)
+                ref = self._score_pass(ids, T, kv, hd, native, 0, rows_only=True)
+                self.set_precision(prev_precision)
+            if precision is not None:
+                self.set_precision(precision)
+            return self._score_pass(ids, T, kv, hd, native, top_n, ref=ref)
         finally:
             self.set_precision(prev_precision)
+
+    def _score_pass(self, ids, T, kv, hd, native, top_n, rows_only=False, ref=None):
+        """one pass of `score` over the checked ids at the precision that is set: the routing, then `score`'s dict.
+        rows_only (the reference pass of `ref_precision=`): no head -- ("rows", the final-norm rows fp16 [T, D]) from the fused route,
+        ("logits", fp16 [T - 1, V]) from the module tree.  ref (what that pass returned): the dict gains kl, kl_mean, top1_agree; a
+        reference that came from the module tree sends this pass there too (the same definition from the two logit matrices)."""
+        if ref is not None and ref[0] == "logits":
+            native = False  # (a request that insists on the fused route -- native=True, a quantised cache, an adapter -- raised in the reference pass)
+        dec, why = None, "opted out"
+        if native is not False:
+            if self.device.type != "cuda":
+                why = "the fused routes need the GPU"
+            else:
+                dec = self._native_decoder_or_none(self.precision, release_planes=native is True)
+                why = getattr(self, "_no_native_reason", None) or "this checkpoint has no fused decode form at %d bits" % self.precision
+                if dec is not None and T > dec.config.block_size:
+                    dec, why = None, f"{T} tokens exceed the fused model's context ({dec.config.block_size})"
+                if dec is not None and kv != "fp16" and dec.kv8_unserved():
+                    dec, why = None, dec.kv8_unserved()
+                if dec is not None and not dec.prefill_ready(ids.to(self.device).to(torch.int32)):
+                    dec, why = None, "the fused model's prompt pass does not serve this model"
+        if dec is None and kv != "fp16":
+            raise ValueError(f"kv_cache_dtype='{kv}': " + why)
+        if dec is None and hd == "int8":
+            raise ValueError("lm_head_dtype='int8': " + why)
+        if dec is None and self._adapter is not None:
+            raise ValueError("lora: " + why)
+        if dec is None and native is True:
+            raise ValueError("native=True: " + why)
+        if dec is not None:
+            self._request_head(dec, hd)
+            # the caches sized as `_generate_native` sizes them, and like there allocated OUTSIDE inference mode (tensors made inside
+            # it refuse in-place updates elsewhere: set_kv_scales, the module forward's cache write); graphs captured over caches
+            # about to be replaced go first
+            cap = min(T if T > 16384 else max(256, 1 << (T - 1).bit_length()), dec.config.block_size)
+            if not (dec.max_seq_length >= cap and dec.max_batch_size >= 1 and dec.kv_cache_dtype == kv):
+                self._evict("graph")
+            dec.setup_caches(1, cap, kv_cache_dtype=kv)
+        lists = ()
+        with torch.inference_mode():
+            if rows_only:
+                if dec is not None:
+                    return "rows", dec._final_rows_native(ids.to(self.device).to(torch.int32))
+                return "logits", self.model(input_ids=ids.to(self.device).long().view(1, -1)).logits[0, :-1]
+            if dec is not None:
+                lp, greedy, *lists = dec.score_native(ids.to(self.device).to(torch.int32), **({"top_logprobs": top_n} if top_n else {}),
+                                                      **({"lm_head_dtype": "int8"} if hd == "int8" else {}),
+                                                      **({"ref_hidden": ref[1]} if ref is not None else {}))
+            else:
+                dev_ids = ids.to(self.device).long()
+                logits = self.model(input_ids=dev_ids.view(1, -1)).logits[0, :-1]
+                lp, top1, *lists = self._score_rows(logits, dev_ids[1:], **({"top_n": top_n} if top_n else {}))
+                greedy = top1 == dev_ids[1:]
+                if ref is not None:
+                    from .native_prompt import kl_rows
+                    lm_head = self.model.get_output_embeddings() if hasattr(self.model, "get_output_embeddings") else self.model.lm_head
+                    kl, tp, tq = kl_rows(ref[1] if ref[0] == "logits" else lm_head(ref[1][:-1]), logits)
+                    lists = (kl, tp == tq)
+        return dict(logprobs=lp, greedy=greedy, nll=float(-lp.double().mean()),
+                    **(dict(top_logprobs_ids=lists[0], top_logprobs=lists[1]) if top_n else {}),
+                    **(dict(kl=lists[0], kl_mean=float(lists[0].double().mean()), top1_agree=lists[1]) if ref is not None else {}))
+
+    @staticmethod
+    def _decline_ref_precision(ref_precision, what):
+        """`ref_precision=` is `score`'s alone: the callers that reduce a score to one number, and the packed ones, say so"""
+        if ref_precision is not None:
+            raise ValueError(f"ref_precision: not served through {what} (call score(ids, precision=, ref_precision=) on the sequence)")
 
     def perplexity(self, token_ids, chunk_size=2048, **score_kwargs):
         """Perplexity of a 1-D token stream by the reference's definition (any_precision/evaluate/eval.py:205-226): the stream is cut
@@ -717,6 +764,7 @@ class AnyPrecisionForCausalLM(nn.Module):
         on its own (`score`; its first token is context only), and the result is exp of the mean of those means.
         Returns dict(ppl, nll_per_chunk).  `score_kwargs` (precision, kv_cache_dtype, native, lm_head_dtype) go to `score`:
         perplexity(ids, lm_head_dtype="int8") is the perplexity of the model the int8 head decodes."""
+        self._decline_ref_precision(score_kwargs.get("ref_precision"), "perplexity")
         ids = torch.as_tensor(token_ids)
         if ids.dim() != 1:
             raise ValueError("perplexity: token_ids must be a 1-D stream of token ids")
@@ -732,6 +780,7 @@ class AnyPrecisionForCausalLM(nn.Module):
         """lm-eval's pair for a (context, continuation): (the sum of the continuation tokens' log-probabilities given everything in
         front of them, whether every one of them is the model's most probable token), from ONE pass over context + continuation.
         `score_kwargs` go to `score` (lm_head_dtype="int8" among them: the int8 head's model)."""
+        self._decline_ref_precision(score_kwargs.get("ref_precision"), "loglikelihood")
         ctx, cont = torch.as_tensor(context_ids).reshape(-1), torch.as_tensor(continuation_ids).reshape(-1)
         if ctx.numel() < 1 or cont.numel() < 1:
             raise ValueError("loglikelihood: a context and a continuation of at least one token each")
@@ -826,22 +875,25 @@ class AnyPrecisionForCausalLM(nn.Module):
         finally:
             self.set_precision(prev_precision)
 
-    def score_many(self, list_of_ids, pack_tokens=None, precision=None, native=None, lm_head_dtype=None):
+    def score_many(self, list_of_ids, pack_tokens=None, precision=None, native=None, lm_head_dtype=None, ref_precision=None):
         """`score` for many sequences: a list of its dicts (logprobs fp32 [T_i - 1], greedy bool [T_i - 1], nll float) in input order.
         On the fused route the sequences are packed -- first fit in input order into packs of at most `pack_tokens` rows (default: the
         smaller of GQ_PREFILL_CHUNK and the model's context) -- and every pack is ONE prompt pass (`Transformer.score_packed_native`:
         varlen attention, the weights read once per pack instead of once per sequence); a sequence longer than a pack goes through
         `score`.  A packed result is a rounding of the same model as `score`'s, not bit-equal to it: the GEMMs see other row counts.
         Validation, `precision` and `native` as in `score`: off the fused route (native=False, no fused form, the CPU) this is a loop
-        over `score`, and native=True raises instead of falling back.  fp16 KV cache.  lm_head_dtype as in `score`."""
+        over `score`, and native=True raises instead of falling back.  fp16 KV cache.  lm_head_dtype as in `score`.
+        ref_precision is `score`'s alone: ValueError("ref_precision: ...") here and in `loglikelihood_many`."""
+        self._decline_ref_precision(ref_precision, "score_many")
         seqs = [self._checked_ids(ids, "score_many") for ids in list_of_ids]
         res = self._score_packs(seqs, [None] * len(seqs), pack_tokens, precision, native, "score_many", lm_head_dtype)
         return [dict(logprobs=lp, greedy=g, nll=float(-lp.double().mean())) for lp, g in res]
 
-    def loglikelihood_many(self, pairs, pack_tokens=None, precision=None, native=None, lm_head_dtype=None):
+    def loglikelihood_many(self, pairs, pack_tokens=None, precision=None, native=None, lm_head_dtype=None, ref_precision=None):
         """`loglikelihood` for many (context, continuation) pairs -- the requests lm-eval issues by the thousand: a list of (sum of the
         continuation's log-probabilities, all of them greedy) in input order, packed like `score_many`.  Only the rows that predict a
         continuation token reach the final norm and the lm_head.  lm_head_dtype as in `score`."""
+        self._decline_ref_precision(ref_precision, "loglikelihood_many")
         seqs, tails = [], []
         for ctx, cont in pairs:
             ctx, cont = torch.as_tensor(ctx).reshape(-1), torch.as_tensor(cont).reshape(-1)

@@ -39,6 +39,7 @@ EXPORTS = [
     "gq_rope_cache_rows_kv8r", "gq_attn_decode_roped_kv8r", "gq_attn_prefill_kv8r",
     "gq_rope_cache_rows_mx4", "gq_attn_decode_roped_mx4", "gq_attn_prefill_mx4",
     "gq_head_nll_i8", "gq_head_nll_i8_topn",
+    "gq_head_kl_ws_bytes", "gq_head_kl",
 ]
 ATTN_FLAG_STRIDE = 32  # include/gq_hip.h GQ_ATTN_FLAG_STRIDE
 SSQ_SLOTS = 1024  # include/gq_hip.h GQ_SSQ_SLOTS
@@ -222,6 +223,9 @@ def lib():
         # the int8 head's forms: scale behind Wq, the rest as above
         L.gq_head_nll_i8.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, u32, vp, ctypes.c_size_t, vp]
         L.gq_head_nll_i8_topn.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, i32, vp, vp, u32, vp, ctypes.c_size_t, vp]
+        # (the KL head: xp, xq, W, S, V, D, kl, lse_p, lse_q, top1_p, top1_q, splits, ws, ws_bytes, stream)
+        L.gq_head_kl_ws_bytes.argtypes = [u32, u32, u32, u32]
+        L.gq_head_kl.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, u32, vp, ctypes.c_size_t, vp]
         L.gq_anyprec_pack.argtypes = [vp, vp, u32, u32, i32, vp]
         L.gq_lnq_cd_block.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, u32, vp]
         L.gq_debug_set_timing_buffer.argtypes = [vp]
@@ -249,13 +253,14 @@ def lib():
             if name in _VOID:
                 getattr(L, name).restype = None
             elif name not in ("gq_last_error", "gq_anyprec_gemm_ws_bytes", "gq_anyprec_gemv_fused_ws_bytes", "gq_qtip_gemm_ws_bytes",
-                              "gq_head_nll_ws_bytes", "gq_head_nll_topn_ws_bytes"):
+                              "gq_head_nll_ws_bytes", "gq_head_nll_topn_ws_bytes", "gq_head_kl_ws_bytes"):
                 getattr(L, name).restype = i32
         L.gq_anyprec_gemm_ws_bytes.restype = ctypes.c_size_t
         L.gq_anyprec_gemv_fused_ws_bytes.restype = ctypes.c_size_t
         L.gq_qtip_gemm_ws_bytes.restype = ctypes.c_size_t
         L.gq_head_nll_ws_bytes.restype = ctypes.c_size_t
         L.gq_head_nll_topn_ws_bytes.restype = ctypes.c_size_t
+        L.gq_head_kl_ws_bytes.restype = ctypes.c_size_t
         L.gq_last_error.restype = ctypes.c_char_p
         _lib = L
     return _lib

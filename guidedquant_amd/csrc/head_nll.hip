@@ -55,6 +55,7 @@
 #include "gq_internal.h"
 #include "wave_util.h"
 #include "q8_conv.h"
+#include "head_tile.h"
 
 namespace {
 using u32 = uint32_t;
@@ -62,15 +63,11 @@ using gqw::f32x4;
 using gqw::h16;
 using gqw::h16x8;
 
-constexpr u32 BS = 128, BV = 128, BKK = 64;
-constexpr u32 LD = BKK + 8;          // halves per LDS row: 16 bytes of padding
+using gqh::BKK, gqh::BS, gqh::BV, gqh::LD, gqh::LOG2E, gqh::MAX_SPLITS, gqh::NEG, gqh::NO_ID;  // (head_tile.h: shared with head_kl.hip)
+using gqh::pick_splits;
 constexpr u32 NCH = BV * (BKK / 8) / 256;  // 16-byte chunks per thread and matrix
 static_assert(BS == BV && NCH == 4, "one chunk map for both tiles");
-constexpr float NEG = -1.0e30f;      // below every fp16 value and finite: NEG - NEG = 0, never Inf - Inf
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr int NO_ID = 0x7FFFFFFF;
-constexpr u32 MAX_SPLITS = 65535u;
-constexpr u32 TN = 20;               // list slots per row (GQ_TOPN_MAX of include/gq_hip.h)
+constexpr u32 TN = 20;              // list slots per row (GQ_TOPN_MAX of include/gq_hip.h)
 static_assert(TN == GQ_TOPN_MAX, "the list stride is the largest top_n");
 
 // the partials of a (split, row): five planes [splits][S]
@@ -412,14 +409,6 @@ __global__ void __launch_bounds__(256) head_nll_topn_merge_kernel(const float *_
         top_ids[o] = mi == NO_ID ? -1 : mi;
         top_lps[o] = mi == NO_ID ? -__builtin_inff() : mv - lse[row];
     }
-}
-
-// the vocabulary splits of a launch: the caller's, or enough blocks for two per compute unit with at least 8 tiles each
-u32 pick_splits(u32 S, u32 V, u32 splits) {
-    if (splits) return splits;
-    const u32 row_tiles = (S + BS - 1u) / BS, ntiles = (V + BV - 1u) / BV;
-    const u32 want = (2u * (u32)gq_cu_count() + row_tiles - 1u) / row_tiles;
-    return max(1u, min(min(want, ntiles / 8u), MAX_SPLITS));
 }
 }  // namespace
 

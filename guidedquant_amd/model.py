@@ -771,7 +771,13 @@ class Transformer(nn.Module):
         q8: the int8 head `head_q8()` in place of `output.weight` (gq_head_nll_i8 / gq_head_nll_i8_topn, or native_prompt.logits_q8)."""
         return native_prompt.score_head(self, x, targets, kernel, top_n, q8)
 
-    def score_native(self, idx: Tensor, chunk: Optional[int] = None, top_logprobs: Optional[int] = None, lm_head_dtype=None):
+    def _final_rows_native(self, idx: Tensor, chunk: Optional[int] = None) -> Tensor:
+        """`score_native`'s pass with no head: the rows behind the final RMSNorm, fp16 [S, D] (the `ref_hidden` of another precision's
+        `score_native`).  `last_prefill_plan["head"]` says "rows"."""
+        return native_prompt.final_rows(self, idx, chunk)
+
+    def score_native(self, idx: Tensor, chunk: Optional[int] = None, top_logprobs: Optional[int] = None, lm_head_dtype=None,
+                     ref_hidden: Optional[Tensor] = None):
         """Log-probabilities of a token sequence on the HIP prompt pass: (logprob fp32 [S - 1], greedy bool [S - 1]) with
         logprob[i] = log p(idx[i + 1] | idx[:i + 1]) and greedy[i] = (the most probable next token == idx[i + 1]) -- what the module tree's
         `labels=` loss and lm-eval's loglikelihood are made of.  The pass is `prefill_native`'s from position 0 (the same pieces, caches,
@@ -785,8 +791,14 @@ class Transformer(nn.Module):
         sort behind the torch head.  Without the keyword the pass makes the calls it always made.
         lm_head_dtype: None / "fp16" score `output.weight`, on an int8-head model too; "int8" scores the head the decode step reads,
         logit = fp16(scale[v] * sum_k xn[k] q[v][k]) over `head_q8()` (gq_head_nll_i8 / gq_head_nll_i8_topn, or the torch form in blocks;
-        the plan says "hip-nll-i8" | "hip-nll-i8-topn" | "torch-i8") and needs `set_lm_head_dtype("int8")` first, else ValueError."""
-        return native_prompt.score(self, idx, chunk, top_logprobs, lm_head_dtype)
+        the plan says "hip-nll-i8" | "hip-nll-i8-topn" | "torch-i8") and needs `set_lm_head_dtype("int8")` first, else ValueError.
+        ref_hidden=H (fp16 [S, D]: the final-norm rows of a REFERENCE model that shares this model's lm_head -- another precision of the
+        same Any-Precision parent) adds two results, (kl fp32 [S - 1], top1_agree bool [S - 1]): KL(P_ref || P_this) of the distribution
+        logprob[i] was taken from, not clamped at 0, and whether the two models' most probable tokens agree.  Each piece runs gq_head_kl
+        (csrc/head_kl.hip: `output.weight` streamed once for both models, no logits in memory; the plan says "hip-kl") beside the
+        gq_head_nll call that still produces logprob and greedy, bit-equal to the call without the keyword; under GQ_SCORE_HEAD=0 or an
+        unserved shape both are the torch forms ("torch-kl": native_prompt.kl_rows).  Not with top_logprobs or the int8 head: ValueError."""
+        return native_prompt.score(self, idx, chunk, top_logprobs, lm_head_dtype, ref_hidden)
 
     def score_packed_native(self, seqs, rows: Optional[Tensor] = None, lm_head_dtype=None):
         """Log-probabilities of SEVERAL token sequences in one HIP prompt pass (varlen attention): the sequences are laid end to end as

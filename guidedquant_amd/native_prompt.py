@@ -12,6 +12,8 @@ through the C ABI (include/gq_hip.h) and the quantized linears' own forwards.
     `score_head_choice`, a pure function of the GQ_SCORE_HEAD mode.  With `top_logprobs=n` the head also lists every row's n most probable
     tokens (gq_head_nll_topn, or `top_rows` behind the torch head).  With `lm_head_dtype="int8"` the head reads the model's int8 copy
     (gq_head_nll_i8 / gq_head_nll_i8_topn, or `logits_q8` in front of the torch steps): the model the decode step decodes.
+    With `ref_hidden=` (the final-norm rows of another precision of the same parent, from `final_rows`) every piece also runs the KL
+    head (`kl_head`: gq_head_kl, or `kl_rows` on the two logit blocks): KL(P_ref || P_this) and the two top-1 ids per row.
 
   * packed scoring: `pack_plan` (first fit in input order) and `score_packed` -- several short sequences as ONE piece, `_PackedPiece`'s
     `rows_and_attention` through gq_rope_cache_rows_packed and gq_attn_prefill_packed (or SDPA under the block-diagonal `packed_mask`).
@@ -94,7 +96,9 @@ def ready(model, idx) -> bool:
 # ------------------------------------------------------------------------------------------------ the pass
 def prompt_pass(model, idx, input_pos, start: int, last_only: bool, chunk: Optional[int], score: Optional[dict] = None):
     """the chunk loop of `prefill_native` (score None: its logits) and of `score_native` (score = dict(targets int32 [S], kernel bool[,
-    top_n]): every piece runs the scoring head on its rows; the list of the pieces' (logprob, top1[, top ids, top log-probabilities]))"""
+    top_n]): every piece runs the scoring head on its rows; the list of the pieces' (logprob, top1[, top ids, top log-probabilities]).
+    score = dict(targets, kernel, ref fp16 [S, D]) adds the KL head against the reference rows `ref` to every piece: (logprob, top1, kl,
+    top1 of the reference, top1 of this model); score = dict(rows=True) runs no head and lists the pieces' final-norm rows)"""
     L = _lib.lib()
     cfg = model.config
     S, H, Hkv, hd = idx.numel(), cfg.n_head, cfg.n_local_heads, cfg.head_dim
@@ -124,7 +128,7 @@ def prompt_pass(model, idx, input_pos, start: int, last_only: bool, chunk: Optio
     for a, n in pieces:
         o = a - start
         head = (not last_only) or a + n == start + S
-        piece_score = None if score is None else dict(score, targets=score["targets"][o:o + n])
+        piece_score = None if score is None else {k: v[o:o + n] if k in ("targets", "ref") else v for k, v in score.items()}
         r = _run_piece(model, flat[o:o + n], input_pos[o:o + n], a, bufs, plan, head, last_only, piece_score)
         if head:
             out.append(r)
@@ -144,6 +148,10 @@ def _run_piece(model, idx, input_pos, start: int, bufs: dict, plan: str, head: b
     if not head:
         return None
     x = x + pending
+    if score is not None and score.get("rows"):  # (`final_rows`: the head's input instead of a head)
+        return model.norm(x).contiguous()
+    if score is not None and score.get("ref") is not None:  # (the scoring head as without a reference, then the KL head beside it)
+        return (*score_head(model, x, score["targets"], score["kernel"]), *kl_head(model, x, score["ref"], score["kernel"]))
     if score is not None:
         return score_head(model, x, score["targets"], score["kernel"], score.get("top_n", 0), **({"q8": True} if score.get("q8") else {}))
     x = x[-1:] if last_only else x
@@ -373,30 +381,89 @@ def score_head(model, x, targets, kernel: bool, top_n: int = 0, q8: bool = False
     return torch.cat(lps), torch.cat(tops)
 
 
-def head_name(kernel: bool, top_n: int, q8: bool) -> str:
+def kl_rows(lp: Tensor, lq: Tensor, rows: int = 512):
+    """the torch definition of the KL head on two blocks of logits [n, V], P's and Q's: (kl fp32 [n] = KL(P || Q), top1 of P, top1 of Q), in
+    blocks of `rows` rows -- both blocks -> fp32 log_softmax -> (p.exp() * (logp - logq)).sum(-1), plus argmax.  Not clamped; equal
+    blocks give exactly 0."""
+    kls, tp, tq = [], [], []
+    for a in range(0, lp.shape[0], rows):
+        logp, logq = F.log_softmax(lp[a:a + rows].float(), dim=-1), F.log_softmax(lq[a:a + rows].float(), dim=-1)
+        kls.append((logp.exp() * (logp - logq)).sum(-1))
+        tp.append(logp.argmax(dim=-1).to(torch.int32))
+        tq.append(logq.argmax(dim=-1).to(torch.int32))
+    return torch.cat(kls), torch.cat(tp), torch.cat(tq)
+
+
+def kl_head(model, x, ref, kernel: bool):
+    """the KL head on the residual rows x fp16 [n, D] of this model against the final-norm rows `ref` fp16 [n, D] of the reference model,
+    both through this model's `output.weight`: (kl fp32 [n] = KL(P_ref || P_this), top1 of the reference [n], top1 of this model [n]).
+    The kernel gq_head_kl (csrc/head_kl.hip: W streamed once for both, no logits in memory), or `kl_rows` on the two logit blocks of
+    the model's SCORE_HEAD_ROWS rows"""
+    n, V = x.shape[0], model.config.vocab_size
+    assert ref.dtype == torch.float16 and tuple(ref.shape) == tuple(x.shape) and ref.device == x.device
+    if kernel:
+        L = _lib.lib()
+        xq, xp = model.norm(x).contiguous(), ref.contiguous()
+        W = model.output.weight
+        assert xq.dtype == torch.float16 and W.dtype == torch.float16 and W.is_contiguous()
+        kl = torch.empty(n, dtype=torch.float32, device=x.device)
+        tp, tq = torch.empty(n, dtype=torch.int32, device=x.device), torch.empty(n, dtype=torch.int32, device=x.device)
+        with torch.cuda.device(x.device):
+            nws = int(L.gq_head_kl_ws_bytes(n, V, xq.shape[1], 0))
+            ws = torch.empty(max(nws, 4), dtype=torch.uint8, device=x.device)
+            _lib.check(L.gq_head_kl(xp.data_ptr(), xq.data_ptr(), W.data_ptr(), n, V, xq.shape[1], kl.data_ptr(), None, None, tp.data_ptr(), tq.data_ptr(), 0,
+                                    ws.data_ptr(), nws, _lib.current_stream_ptr()), "gq_head_kl")
+        return kl, tp, tq
+    out = [kl_rows(model.output(ref[a:a + model.SCORE_HEAD_ROWS]), model.output(model.norm(x[a:a + model.SCORE_HEAD_ROWS])), model.SCORE_HEAD_ROWS)
+           for a in range(0, n, model.SCORE_HEAD_ROWS)]
+    return tuple(torch.cat([o[i] for o in out]) for i in range(3))
+
+
+def head_name(kernel: bool, top_n: int, q8: bool, kl: bool = False) -> str:
     """`last_prefill_plan["head"]`"""
+    if kl:
+        return "hip-kl" if kernel else "torch-kl"
     if not kernel:
         return "torch-i8" if q8 else "torch"
     return "hip-nll" + ("-i8" if q8 else "") + ("-topn" if top_n else "")
 
 
-def score(model, idx, chunk: Optional[int] = None, top_logprobs: Optional[int] = None, lm_head_dtype=None):
+def final_rows(model, idx, chunk: Optional[int] = None) -> Tensor:
+    """the pass of `score` from position 0 with no head: the rows behind the final RMSNorm, fp16 [S, D] -- what a later
+    `score(..., ref_hidden=)` of another precision of the same parent compares itself with"""
+    flat = idx.reshape(-1).to(torch.int32)
+    S = flat.numel()
+    assert model.prefill_ready(idx) and 2 <= S <= model.max_seq_length
+    out = prompt_pass(model, flat, torch.arange(0, S, device=flat.device, dtype=torch.int32), 0, False, chunk, score=dict(rows=True))
+    model.last_prefill_plan["head"] = "rows"
+    return torch.cat(out)
+
+
+def score(model, idx, chunk: Optional[int] = None, top_logprobs: Optional[int] = None, lm_head_dtype=None, ref_hidden: Optional[Tensor] = None):
     """`Transformer.score_native`: the pass from position 0 with the scoring head on every piece"""
     top_n = check_top_logprobs(top_logprobs)
     q8 = head_request(model, lm_head_dtype)
+    if ref_hidden is not None and (top_n or q8):
+        raise ValueError("ref_hidden: not together with top_logprobs or lm_head_dtype='int8'")
     flat = idx.reshape(-1)
     S = flat.numel()
     assert model.prefill_ready(idx) and 2 <= S <= model.max_seq_length
+    if ref_hidden is not None:
+        if ref_hidden.dtype != torch.float16 or tuple(ref_hidden.shape) != (S, model.config.dim) or ref_hidden.device != flat.device:
+            raise ValueError(f"ref_hidden: fp16 [{S}, {model.config.dim}] on the model's device")
     served = model.config.dim % 64 == 0 and model.output.weight.dtype == torch.float16  # (else the kernel answers GQ_ENOTSUP)
     kernel = score_head_choice(os.environ.get("GQ_SCORE_HEAD", "auto"), served, model.SCORE_HEAD_AUTO)
     flat = flat.to(torch.int32)
     targets = torch.cat([flat[1:], torch.full((1, ), -1, dtype=torch.int32, device=flat.device)])
     pos = torch.arange(0, S, device=flat.device, dtype=torch.int32)
     out = prompt_pass(model, flat, pos, 0, False, chunk,
-                      score=dict(targets=targets, kernel=kernel, **({"top_n": top_n} if top_n else {}), **({"q8": True} if q8 else {})))
-    model.last_prefill_plan["head"] = head_name(kernel, top_n, q8)
+                      score=dict(targets=targets, kernel=kernel, **({"top_n": top_n} if top_n else {}), **({"q8": True} if q8 else {}),
+                                 **({"ref": ref_hidden} if ref_hidden is not None else {})))
+    model.last_prefill_plan["head"] = head_name(kernel, top_n, q8, ref_hidden is not None)
     lp = torch.cat([o[0] for o in out])[:S - 1]
     top1 = torch.cat([o[1] for o in out])[:S - 1]
+    if ref_hidden is not None:
+        return lp, top1 == flat[1:], torch.cat([o[2] for o in out])[:S - 1], torch.cat([o[3] == o[4] for o in out])[:S - 1]
     if top_n:
         return lp, top1 == flat[1:], torch.cat([o[2] for o in out])[:S - 1], torch.cat([o[3] for o in out])[:S - 1]
     return lp, top1 == flat[1:]

@@ -409,6 +409,28 @@ int gq_head_nll_i8_topn(const void *xn, const void *Wq, const float *scale, cons
                         uint32_t splits, void *ws, size_t ws_bytes, void *stream);
 
 /*
+ * The KL head (csrc/head_kl.hip): the divergence between the next-token distributions of two models that share one lm_head -- two
+ * precisions of an Any-Precision parent -- per row, in one pass over W and without a logit of either in memory.
+ *   xp fp16 [S][D]   the rows behind the final RMSNorm of the reference model (P);  xq fp16 [S][D] the same rows of the model under test (Q)
+ *   W  fp16 [V][D]   output.weight as stored
+ *   lp[s][v] = fp16(sum_k xp[s][k] W[v][k]), lq[s][v] likewise from xq: gq_head_nll's logit (fp32 accumulation on
+ *              v_mfma_f32_16x16x32_f16, ONE fp16 rounding)
+ *   lse_p[s], lse_q[s]   fp32 log sum_v exp(logit) of each model
+ *   kl[s]      = sum_v exp(lp - lse_p) (lp - lq) - lse_p + lse_q = KL(P || Q), evaluated online per (row, vocabulary range) as
+ *                m_p, s_p = sum exp(lp - m_p), a = sum exp(lp - m_p) (lp - lq), m_q, s_q and folded as a / s_p - (m_p + log s_p) +
+ *                (m_q + log s_q).  NOT clamped at 0: round-off may leave a tiny negative value.  A row with xp == xq bit for bit is 0.0f.
+ *   top1_p[s], top1_q[s]   the lowest id among the largest fp16 logits of each model (gq_head_nll's top1)
+ * kl must not be NULL; lse_p, lse_q, top1_p, top1_q may be.  Any S >= 1 and V >= 1; D % 64 == 0, else GQ_ENOTSUP.  `splits` as in
+ * gq_head_nll (0: the library's choice, the same as there).  The partials -- nine words per (row, range) -- go through `ws`
+ * (gq_head_kl_ws_bytes for the same S, V, D, splits; smaller: GQ_EINVAL) and a second launch folds them in ascending range order: the
+ * results depend on `splits`, never on the run.  Nothing is written where the entry refuses.  xp, xq and W 16-byte aligned.
+ * A row with a non-finite logit follows the fp32 arithmetic of the formulas (NaN or Inf as they give); it does not disturb other rows.
+ */
+size_t gq_head_kl_ws_bytes(uint32_t S, uint32_t V, uint32_t D, uint32_t splits);
+int gq_head_kl(const void *xp, const void *xq, const void *W, uint32_t S, uint32_t V, uint32_t D, float *kl, float *lse_p, float *lse_q,
+               int *top1_p, int *top1_q, uint32_t splits, void *ws, size_t ws_bytes, void *stream);
+
+/*
  * Host (CPU) twins of the two Any-Precision entry points: same arguments with HOST pointers, no stream; `nthreads` <= 0
  * uses the OpenMP default.  They serve BASELINE.json configs[0] ("CPU reference APLinear path via generate.py"): the module
  * semantics of inference/APLinear.py:35-60 with the tensors in host memory (the reference hard-codes 'cuda',

@@ -3,6 +3,7 @@
 log-likelihoods, exp of it; a shorter tail is dropped), the per-chunk values, the share of greedy hits.  No tokenizer and no dataset:
 --top_logprobs N adds the N most probable tokens of every position and their log-probabilities, per chunk;
 --lm_head_dtype int8 scores through the int8 copy of the lm_head, the model `generate(..., lm_head_dtype="int8")` decodes;
+--ref_precision R adds kl_mean (the mean over chunks of KL(P_R || P_bitwidth), nats per token) and top1_agree_share against the same parent at R bits;
 the ids come from an .npy file or an .npz entry (--key, default the first array), the model from the arguments of
 guidedquant_amd/generate.py (`Transformer.score_native`: the HIP prompt pass with the scoring head; GQ_SCORE_HEAD picks the head).
     python tools/score_tokens.py tokens.npy --model_name meta-llama/Meta-Llama-3.1-8B --backend ap --bitwidth 2 --checkpoint_path DIR
@@ -45,7 +46,13 @@ def main():
     ap.add_argument("--top_logprobs", type=int, default=None, help="1..20: the n most probable tokens of every position, with their log-probabilities")
     ap.add_argument("--lm_head_dtype", type=str, default=None, choices=["fp16", "int8"],
                     help="int8: score the model the int8 lm_head decodes (Transformer.set_lm_head_dtype; the JSON line's head says hip-nll-i8)")
+    ap.add_argument("--ref_precision", type=int, default=None, choices=[2, 3, 4, 5, 6, 7, 8],
+                    help="R: also report the KL divergence KL(P_R || P_bitwidth) and the top-1 agreement against the same parent at R bits "
+                         "(the KL head gq_head_kl; --ref_checkpoint_path holds the R-bit conversion, default --checkpoint_path)")
+    ap.add_argument("--ref_checkpoint_path", type=str, default=None)
     a = ap.parse_args()
+    if a.ref_precision is not None and (a.top_logprobs is not None or a.lm_head_dtype == "int8" or a.backend != "ap"):
+        raise SystemExit("--ref_precision: not together with --top_logprobs or --lm_head_dtype int8, and on the ap backend only")
     import torch
     from guidedquant_amd.generate import load_model
     ids = load_ids(a.tokens, a.key)
@@ -64,11 +71,25 @@ def main():
     dev_ids = torch.from_numpy(ids[:n * a.chunk_size]).to(device=a.device, dtype=torch.int32)
     if not model.prefill_ready(dev_ids[:a.chunk_size]):
         raise SystemExit("the fused prompt pass does not serve this model on this device (no fallback)")
-    nlls, hits, top_ids, top_lps = [], 0, [], []
+    ref = None
+    if a.ref_precision is not None:  # the same parent at R bits: one lm_head, embedding and final norm for both models
+        ref = load_model(a.model_name, a.device, a.backend, a.ref_precision, random_init=a.random_init, checkpoint_path=a.ref_checkpoint_path or a.checkpoint_path)
+        if a.random_init:
+            ref.output.weight, ref.tok_embeddings.weight, ref.norm.weight = model.output.weight, model.tok_embeddings.weight, model.norm.weight
+        elif not torch.equal(ref.output.weight, model.output.weight):
+            raise SystemExit("--ref_precision: the two checkpoints do not share their lm_head (not two precisions of one parent)")
+        ref.setup_caches(1, a.chunk_size, kv_cache_dtype=a.kv_cache_dtype)
+    nlls, hits, top_ids, top_lps, kls, agree = [], 0, [], [], [], 0
     with torch.no_grad():
         for i in range(n):
-            lp, greedy, *lists = model.score_native(dev_ids[i * a.chunk_size:(i + 1) * a.chunk_size],
-                                                    **({} if a.top_logprobs is None else {"top_logprobs": a.top_logprobs}), **head)
+            chunk = dev_ids[i * a.chunk_size:(i + 1) * a.chunk_size]
+            if ref is not None:
+                lp, greedy, kl, same = model.score_native(chunk, ref_hidden=ref._final_rows_native(chunk))
+                kls.append(float(kl.double().mean()))
+                agree += int(same.sum())
+                lists = ()
+            else:
+                lp, greedy, *lists = model.score_native(chunk, **({} if a.top_logprobs is None else {"top_logprobs": a.top_logprobs}), **head)
             nlls.append(float(-lp.double().mean()))
             hits += int(greedy.sum())
             if lists:  # (per chunk, [chunk_size - 1][n] each)
@@ -76,7 +97,9 @@ def main():
                 top_lps.append(lists[1].tolist())
     print(json.dumps(dict(ppl=math.exp(sum(nlls) / n), nll_per_chunk=nlls, chunks=n, chunk_size=a.chunk_size, tokens_dropped=len(ids) - n * a.chunk_size,
                           greedy_share=hits / (n * (a.chunk_size - 1)), head=model.last_prefill_plan["head"], kv_cache_dtype=model.kv_cache_dtype,
-                          **({} if a.top_logprobs is None else dict(top_logprobs_ids=top_ids, top_logprobs=top_lps)))))
+                          **({} if a.top_logprobs is None else dict(top_logprobs_ids=top_ids, top_logprobs=top_lps)),
+                          **({} if ref is None else dict(ref_precision=a.ref_precision, kl_mean=sum(kls) / n, kl_per_chunk=kls,
+                                                         top1_agree_share=agree / (n * (a.chunk_size - 1)))))))
 
 
 if __name__ == "__main__":
