@@ -23,6 +23,7 @@
 
 #include "ap_dispatch.h"
 #include "attn_core.h"
+#include "kv_fmt.h"
 #include "plane_mfma.h"
 
 using namespace gqp;
@@ -1021,7 +1022,7 @@ __device__ __forceinline__ void fuse_attn_head(const StreamArgs &a, const AttnFu
     }
     FUSE_STAMP(3);
     float qreg[8];
-    gq_attn::unpack8(make_uint4(q4.x, q4.y, q4.z, q4.w), qreg);
+    gq_kv::unpack8(make_uint4(q4.x, q4.y, q4.z, q4.w), qreg);
     const float scale = f.scale;
     float m_run = -3.0e38f, s_run = 0.f, acc[8];
 #pragma unroll
@@ -1034,7 +1035,7 @@ __device__ __forceinline__ void fuse_attn_head(const StreamArgs &a, const AttnFu
             const bool valid = t < p1;
             const u32 vw[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
             float kf[8];
-            gq_attn::unpack8(kv[u], kf);
+            gq_kv::unpack8(kv[u], kf);
 #pragma unroll
             for (int e = 0; e < 4; e++) {
                 vfu[u][2 * e] = valid ? h2f((uint16_t)(vw[e] & 0xFFFF)) : 0.f;

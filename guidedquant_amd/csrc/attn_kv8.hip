@@ -21,6 +21,7 @@
 
 #include "gq_internal.h"
 #include "attn_core.h"
+#include "kv_fmt.h"
 #include "wave_util.h"
 
 namespace {
@@ -210,9 +211,9 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kv8_kernel(const 
             // the write rule, then the read rule's conversion: what LDS holds is what the cache row holds
 #pragma unroll
             for (int k = 0; k < 8; k++) f1[k] *= inv, f2[k] *= inv;
-            const uint2 q1 = gq_attn::fp8_quant8<true>(f1), q2 = gq_attn::fp8_quant8<true>(f2);
-            gq_attn::unpack8_fp8(q1, f1);
-            gq_attn::unpack8_fp8(q2, f2);
+            const uint2 q1 = gq_kv::fp8_quant8<true>(f1), q2 = gq_kv::fp8_quant8<true>(f2);
+            gq_kv::unpack8_fp8(q1, f1);
+            gq_kv::unpack8_fp8(q2, f2);
             if (l < UPR) {
                 float *cur = w == 1u ? kcur : vcur;
                 stage8(cur + d, f1), stage8(cur + d + HD / 2, f2);
@@ -247,8 +248,8 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kv8_kernel(const 
         for (int u = 0; u < U; u++) {
             const u32 t = t0 + (u32)u * PPW + sub;
             float kf[8];
-            gq_attn::unpack8_fp8(kv[u], kf);
-            gq_attn::unpack8_fp8(vv[u], vfu[u]);
+            gq_kv::unpack8_fp8(kv[u], kf);
+            gq_kv::unpack8_fp8(vv[u], vfu[u]);
             if (t == pos) {  // (the current token: staged in LDS above, its cache row may not have landed)
 #pragma unroll
                 for (int e = 0; e < 8; e++) kf[e] = kcur[ld * 8 + e], vfu[u][e] = vcur[ld * 8 + e];

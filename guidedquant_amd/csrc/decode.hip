@@ -13,6 +13,7 @@
 #include "gq_internal.h"
 #include "attn_core.h"
 #include "dense_stage.h"
+#include "kv_fmt.h"
 #include "wave_util.h"
 #include "fwht.h"
 #include "qtip_xform.h"
@@ -30,6 +31,7 @@ using gqw::wave_reduce_bcast;
 using gq_attn::AttnGeom;
 using gq_attn::AttnWindow;
 using gq_attn::window_lo;
+using gq_kv::Fmt;
 
 // KV group of query head h: h / (H / Hkv).  Both divisions sit in front of the first load of an attention launch (the cache base
 // needs g) -- ~25 scalar / vector instructions each on this chip (no integer divide); the group size is a power of two for every
@@ -369,32 +371,27 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_decode_kernel(const uint
 // A short context (the `solo` rule) is finished by ONE block per head: block (hq, sp < QH) takes head hq * QH + sp alone.
 // WIN: the window form (attn_core.h, AttnWindow).  The rows requested ahead of the position are usable only when lo == 0; with lo > 0 they
 // are dropped (p0 >= lo > 0 below) and the first batch is requested once lo is known.
-// KV8: the caches hold OCP e4m3 codes (gq_attn_decode_roped_kv8): a row is one 8-byte load per lane and unpack8_fp8, the K scale of the
+// F, the cache format (kv_fmt.h: Traits<F> gives the element type, the load of a lane's 8 dims, its unpack; Side<F> what is passed
+// beside the caches).  The lane-to-element map, hence every sum and its order, is the fp16 instance's in every format:
+// Fmt::FP8 (gq_attn_decode_roped_kv8): the caches hold OCP e4m3 codes: a row is one 8-byte load per lane, the K scale of the
 // head's KV group is folded into the score factor, the V scale multiplies the merged weighted sum (the final one in front of the
 // division, a split's partial one in front of the workspace, so that attn_combine_kernel serves as it is).  Everything else is shared.
-// ROW (with KV8; gq_attn_decode_roped_kv8r): the per-row scaled fp8 caches of attn_core.h.  A row's exponent byte is requested WITH the
+// Fmt::FP8_ROW (gq_attn_decode_roped_kv8r): the per-row scaled fp8 caches.  A row's exponent byte is requested WITH the
 // row -- the lanes that share the row ask for the same byte, in the speculative batch and in every later one, so that no round trip is
 // added to a launch that waits on memory -- and 2^e multiplies the 8 unpacked values in front of every product: exact, so from there on
 // the floats are those of the fp16 instance over a cache that holds code * 2^e.  No per-head scale is read.
-// MX4 (with ROW; gq_attn_decode_roped_mx4): the MXFP4 caches of attn_core.h, the per-row form with the scale moved to the block of 32
+// Fmt::MX4 (gq_attn_decode_roped_mx4): the MXFP4 caches, the per-row form with the scale moved to the block of 32
 // elements.  A lane's 8 elements of a row are one 4-byte load of e2m1 codes; they lie in ONE block (lane ld: block ld / 4), whose exponent
-// byte the lane requests directly, with the row, in the batches the ROW form requests its row byte in.  unpack8_mx4 applies 2^e where the
-// fp8 forms unpack.  The lane-to-element map, hence every sum and its order, is the fp16 instance's.
-template <int HD, int QH, bool WIN = false, bool KV8 = false, bool ROW = false, bool MX4 = false>
-__global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint16_t *q, const int *pos_ptr, const typename gq_attn::CacheFmt<KV8>::elem *kc,
-                                                                     const typename gq_attn::CacheFmt<KV8>::elem *vc, uint16_t *out, u32 H, u32 Hkv,
+// byte the lane requests directly, with the row, in the batches the per-row form requests its row byte in.
+template <int HD, int QH, bool WIN = false, Fmt F = Fmt::F16>
+__global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint16_t *q, const int *pos_ptr, const typename gq_kv::Traits<F>::elem *kc,
+                                                                     const typename gq_kv::Traits<F>::elem *vc, uint16_t *out, u32 H, u32 Hkv,
                                                                      u32 max_seq, float scale, u32 nsplit, float *ws, AttnWindow<WIN> wn,
-                                                                     gq_attn::AttnKv8<KV8 && !ROW> k8, gq_attn::AttnRowExp<ROW> rx) {
-    static_assert(!ROW || KV8, "the per-row scaled form is a form of the fp8 caches");
-    static_assert(!MX4 || ROW, "the MXFP4 form is the per-row scaled form with the exponent per block");
-    using Fmt = gq_attn::CacheFmt<KV8>;
-    using Row = typename std::conditional<MX4, u32, typename Fmt::row>::type;
-    constexpr u32 RE = MX4 ? HD / 2 : HD, LE = MX4 ? 4 : 8;  // cache elements of a row, of a lane's 8 dims
-    constexpr u32 XR = MX4 ? HD / 32 : 1;                    // exponent bytes of a row
-    const auto row_zero = [] {
-        if constexpr (MX4) return 0u;
-        else return Fmt::zero();
-    };
+                                                                     gq_kv::Side<F> sd) {
+    using T = gq_kv::Traits<F>;
+    using Row = typename T::load;
+    constexpr u32 RE = HD / T::ROW_DIV, LE = T::LANE;  // cache elements of a row, of a lane's 8 dims
+    constexpr u32 XR = T::exp_bytes(HD);               // exponent bytes of a row
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     using Geo = AttnGeom<HD>;
     using L = gq_attn::RopedLds<HD, QH>;
@@ -412,17 +409,17 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
     const u32 h0 = blockIdx.x * QH, g = kv_group_of(h0, H, Hkv), sp = blockIdx.y;
 #endif
     const u32 sub = l / LPP, ld = l % LPP;
-    const typename Fmt::elem *kcg = kc + (size_t)g * max_seq * RE, *vcg = vc + (size_t)g * max_seq * RE;
+    const typename T::elem *kcg = kc + (size_t)g * max_seq * RE, *vcg = vc + (size_t)g * max_seq * RE;
     // requests that do not depend on the position: q, and (blocks that may start at row 0) the first batch of cached rows
     uint4 q4[QH];
 #pragma unroll
     for (int qh = 0; qh < QH; qh++) q4[qh] = *reinterpret_cast<const uint4 *>(q + (size_t)(h0 + qh) * HD + ld * 8);
     Row kv[U], vv[U];
-    constexpr int UE = ROW ? U : 1;  // (the exponent bytes of the rows in flight: ROW only)
+    constexpr int UE = T::row_exp ? U : 1;  // (the exponent bytes of the rows in flight: the formats that have them)
     u32 ke[UE], ve[UE];
     const uint8_t *keg = nullptr, *veg = nullptr;
-    if constexpr (ROW) keg = rx.k_exp + (size_t)g * max_seq * XR, veg = rx.v_exp + (size_t)g * max_seq * XR;
-    if constexpr (MX4) keg += ld / 4u, veg += ld / 4u;  // (the lane's block)
+    if constexpr (T::row_exp) keg = sd.k_exp + (size_t)g * max_seq * XR, veg = sd.v_exp + (size_t)g * max_seq * XR;
+    if constexpr (T::block_exp) keg += ld / 4u, veg += ld / 4u;  // (the lane's block)
     u32 t0 = w * PPW * U;
 #pragma unroll
     for (int u = 0; u < U; u++) {
@@ -430,11 +427,11 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         // (only the first GQ_ATTN_SPEC rows: every row requested ahead of the position is HBM traffic whether it is needed or not --
         // 128 rows x 32 heads = 2 MiB per layer, which costs what the saved round trip gains)
         const bool in = sp < (u32)QH && t < max_seq && t < (u32)GQ_ATTN_SPEC;
-        kv[u] = in ? *reinterpret_cast<const Row *>(kcg + (size_t)t * RE + ld * LE) : row_zero();
-        vv[u] = in ? *reinterpret_cast<const Row *>(vcg + (size_t)t * RE + ld * LE) : row_zero();
-        if constexpr (ROW) ke[u] = in ? (u32)keg[(size_t)t * XR] : 127u, ve[u] = in ? (u32)veg[(size_t)t * XR] : 127u;
+        kv[u] = in ? *reinterpret_cast<const Row *>(kcg + (size_t)t * RE + ld * LE) : T::zero();
+        vv[u] = in ? *reinterpret_cast<const Row *>(vcg + (size_t)t * RE + ld * LE) : T::zero();
+        if constexpr (T::row_exp) ke[u] = in ? (u32)keg[(size_t)t * XR] : 127u, ve[u] = in ? (u32)veg[(size_t)t * XR] : 127u;
     }
-    if constexpr (KV8 && !ROW) scale *= k8.k_scale[g];  // (block-uniform: one scalar load next to the position's)
+    if constexpr (T::head_scale) scale *= sd.k_scale[g];  // (block-uniform: one scalar load next to the position's)
     const u32 pos = (u32)pos_ptr[0];
     if (pos >= max_seq) {  // decoding past the cache: the head's output is poisoned (NaN logits), like attn_decode_kernel
         if (sp == 0u && tid < (u32)QH * HD) out[(size_t)h0 * HD + tid] = 0x7e00u;
@@ -460,7 +457,7 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
             for (int j = 1; j < QH; j++)
                 if (sp == (u32)j) qq = q4[j];
         }
-        gq_attn::unpack8(qq, qreg[qh]);
+        gq_kv::unpack8(qq, qreg[qh]);
     }
     float m_run[QH], s_run[QH], acc[QH][8];
 #pragma unroll
@@ -474,9 +471,9 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         for (int u = 0; u < U; u++) {
             const u32 t = tb + (u32)u * PPW + sub;
             const bool in = t < p1;
-            kd[u] = in ? *reinterpret_cast<const Row *>(kcg + (size_t)t * RE + ld * LE) : row_zero();
-            vd[u] = in ? *reinterpret_cast<const Row *>(vcg + (size_t)t * RE + ld * LE) : row_zero();
-            if constexpr (ROW) ked[u] = in ? (u32)keg[(size_t)t * XR] : 127u, ved[u] = in ? (u32)veg[(size_t)t * XR] : 127u;
+            kd[u] = in ? *reinterpret_cast<const Row *>(kcg + (size_t)t * RE + ld * LE) : T::zero();
+            vd[u] = in ? *reinterpret_cast<const Row *>(vcg + (size_t)t * RE + ld * LE) : T::zero();
+            if constexpr (T::row_exp) ked[u] = in ? (u32)keg[(size_t)t * XR] : 127u, ved[u] = in ? (u32)veg[(size_t)t * XR] : 127u;
         }
     };
     t0 = p0 + w * PPW * U;
@@ -492,35 +489,35 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         for (int u = 0; u < U; u++) {
             const u32 t = t0 + (u32)u * PPW + sub;
             const bool valid = t < p1;
+            // (the read rule of the format: exact, NaN for an MXFP4 block of the byte 0xFF; a stale row's codes and bytes may be anything --
+            // its V row is zeroed here, its scores are replaced below)
+            u32 kb = 0u, vb = 0u;
+            if constexpr (T::row_exp) kb = ke[u], vb = ve[u];
             float kf[8];
-            if constexpr (!MX4) Fmt::unpack(kv[u], kf);
-            if constexpr (MX4) {  // (the read rule of the block: e2m1(code) * 2^e, exact, NaN for the byte 0xFF; stale rows as below)
-                float vf[8];
-                gq_attn::unpack8_mx4(kv[u], gq_attn::mx4_scale(ke[u]), kf);
-                gq_attn::unpack8_mx4(vv[u], gq_attn::mx4_scale(ve[u]), vf);
-#pragma unroll
-                for (int e = 0; e < 8; e++) vfu[u][e] = valid ? vf[e] : 0.f;
-            } else if constexpr (ROW) {  // (the read rule: fp16(code) * 2^e, exact; a stale row's byte may be anything -- replaced below like its codes)
-                const float sk = gq_attn::row_exp_scale(ke[u]), sv = gq_attn::row_exp_scale(ve[u]);
-                float vf[8];
-                Fmt::unpack(vv[u], vf);
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    kf[e] *= sk;
-                    vfu[u][e] = valid ? vf[e] * sv : 0.f;
-                }
-            } else if constexpr (KV8) {
-                float vf[8];
-                Fmt::unpack(vv[u], vf);
-#pragma unroll
-                for (int e = 0; e < 8; e++) vfu[u][e] = valid ? vf[e] : 0.f;
-            } else {
+            if constexpr (F == Fmt::F16) {  // (V straight from its words, the spelling these instances had: through T::unpack QH = 4 schedules otherwise)
+                T::unpack(kv[u], kb, kf);
                 const u32 vw[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
                     vfu[u][2 * e] = valid ? h2f((uint16_t)(vw[e] & 0xFFFF)) : 0.f;
                     vfu[u][2 * e + 1] = valid ? h2f((uint16_t)(vw[e] >> 16)) : 0.f;
                 }
+            } else if constexpr (F == Fmt::FP8_ROW) {  // (the two factors side by side, the spelling these instances had: T::unpack twice schedules otherwise)
+                gq_kv::unpack8_fp8(kv[u], kf);
+                const float sk = gq_kv::row_exp_scale(kb), sv = gq_kv::row_exp_scale(vb);
+                float vf[8];
+                gq_kv::unpack8_fp8(vv[u], vf);
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    kf[e] *= sk;
+                    vfu[u][e] = valid ? vf[e] * sv : 0.f;
+                }
+            } else {
+                float vf[8];
+                T::unpack(kv[u], kb, kf);
+                T::unpack(vv[u], vb, vf);
+#pragma unroll
+                for (int e = 0; e < 8; e++) vfu[u][e] = valid ? vf[e] : 0.f;
             }
 #pragma unroll
             for (int qh = 0; qh < QH; qh++) {
@@ -540,7 +537,7 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         if (QH > 1) {
 #pragma unroll
             for (int u = 0; u < U; u++) kv[u] = kn[u], vv[u] = vn[u];
-            if constexpr (ROW) {
+            if constexpr (T::row_exp) {
 #pragma unroll
                 for (int u = 0; u < U; u++) ke[u] = ken[u], ve[u] = ven[u];
             }
@@ -582,7 +579,7 @@ __global__ void __launch_bounds__(64 * ATTN_WAVES) attn_roped_kernel(const uint1
         for (u32 g8 = 0; g8 < ng; g8++)
 #pragma unroll
             for (u32 k = 0; k < 8u; k++) gq_attn::merge_step<HD>(scq, rq, fq, 8u * g8 + k, dd, o, sum);
-        if constexpr (KV8 && !ROW) o *= k8.v_scale[g];
+        if constexpr (T::head_scale) o *= sd.v_scale[g];
         if (nsplit > 1u) {
             float *wp = ws + ((size_t)h * nsplit + sp) * (HD + 2u);
             wp[dd] = o;
@@ -840,19 +837,19 @@ extern "C" int gq_attn_decode_qtip(const GqQtipOut *qkv_lin, const int *pos, con
 // Attention of the decode step when the wqkv launch has already rotated q / k and written k / v of the current token into the
 // caches (gq_anyprec_gemv_qkv_rope): q fp16 [n_head * head_dim] rotated; the caches hold every position <= *pos.
 namespace {
-template <bool WIN, bool KV8 = false, bool ROW = false, bool MX4 = false>
+template <bool WIN, Fmt F = Fmt::F16>
 int roped_launch(const void *q, const int *pos, const void *k_cache, const void *v_cache, void *out, uint32_t n_head, uint32_t n_kv_head,
                  uint32_t head_dim, uint32_t max_seq, float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream,
-                 const float *k_scale = nullptr, const float *v_scale = nullptr, const void *k_exp = nullptr, const void *v_exp = nullptr) {
-    using CE = typename gq_attn::CacheFmt<KV8>::elem;
-    const bool any_null = !q || !pos || !k_cache || !v_cache || !out || (KV8 && !ROW && (!k_scale || !v_scale)) || (ROW && (!k_exp || !v_exp));
+                 const void *k_side = nullptr, const void *v_side = nullptr) {  // (the format's Side: scales or exponent bytes)
+    using T = gq_kv::Traits<F>;
+    using CE = typename T::elem;
+    const bool any_null = !q || !pos || !k_cache || !v_cache || !out || ((T::head_scale || T::row_exp) && (!k_side || !v_side));
     if (const int rc = attn_check_args(any_null, nullptr, WIN, window, n_head, n_kv_head, head_dim, n_split, workspace)) return rc;
     AttnWindow<WIN> wn{};
     if constexpr (WIN) wn = AttnWindow<true>{window};
-    gq_attn::AttnKv8<KV8 && !ROW> k8{};
-    if constexpr (KV8 && !ROW) k8 = gq_attn::AttnKv8<true>{k_scale, v_scale};
-    gq_attn::AttnRowExp<ROW> rx{};
-    if constexpr (ROW) rx = gq_attn::AttnRowExp<true>{(const uint8_t *)k_exp, (const uint8_t *)v_exp};
+    gq_kv::Side<F> sd{};
+    if constexpr (T::head_scale) sd = {(const float *)k_side, (const float *)v_side};
+    if constexpr (T::row_exp) sd = {(const uint8_t *)k_side, (const uint8_t *)v_side};
     if (((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15u) return gq_fail(GQ_EINVAL, "buffers must be 16-byte aligned.");
     hipStream_t s = (hipStream_t)stream;
     // grouped-query models with a split cache: the 4 query heads of a KV group in one block (every cached row loaded once)
@@ -864,10 +861,10 @@ int roped_launch(const void *q, const int *pos, const void *k_cache, const void 
     const dim3 grid(n_head / qh, gqa_p ? copies : n_split);
     if (gqa_p && !WIN) {
         static GqPerDeviceOnce once;
-        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<128, 4, false, KV8, ROW, MX4>), 160 * 1024));
-        hipLaunchKernelGGL((attn_roped_kernel<128, 4, false, KV8, ROW, MX4>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<128, 4>::bytes()), s, (const uint16_t *)q, pos,
+        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<128, 4, false, F>), 160 * 1024));
+        hipLaunchKernelGGL((attn_roped_kernel<128, 4, false, F>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<128, 4>::bytes()), s, (const uint16_t *)q, pos,
                            (const CE *)k_cache, (const CE *)v_cache, (uint16_t *)out, n_head, n_kv_head, max_seq, scale, 1u, workspace,
-                           AttnWindow<false>{}, k8, rx);
+                           AttnWindow<false>{}, sd);
         GQ_HIP_CHECK(hipGetLastError());
         return GQ_OK;
     }
@@ -878,10 +875,10 @@ int roped_launch(const void *q, const int *pos, const void *k_cache, const void 
 #define GQ_LAUNCH_ROPED(HD_, QH_)                                                                                                    \
     do {                                                                                                                             \
         static GqPerDeviceOnce once;                                                                                                 \
-        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<HD_, QH_, WIN, KV8, ROW, MX4>), 160 * 1024));   \
-        hipLaunchKernelGGL((attn_roped_kernel<HD_, QH_, WIN, KV8, ROW, MX4>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<HD_, QH_>::bytes()), s, \
+        GQ_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void *>(attn_roped_kernel<HD_, QH_, WIN, F>), 160 * 1024));   \
+        hipLaunchKernelGGL((attn_roped_kernel<HD_, QH_, WIN, F>), grid, dim3(64 * ATTN_WAVES), (gq_attn::RopedLds<HD_, QH_>::bytes()), s, \
                            (const uint16_t *)q, pos, (const CE *)k_cache, (const CE *)v_cache, (uint16_t *)out, n_head,               \
-                           n_kv_head, max_seq, scale, n_split, workspace, wn, k8, rx);                                               \
+                           n_kv_head, max_seq, scale, n_split, workspace, wn, sd);                                                   \
         if (n_split > 1u)                                                                                                            \
             hipLaunchKernelGGL((attn_combine_kernel<HD_, WIN>), dim3(n_head), dim3(HD_), 0, s, workspace, (uint16_t *)out, n_split,   \
                                pos, max_seq, wn);                                                                                    \
@@ -916,34 +913,34 @@ extern "C" int gq_attn_decode_roped_kv8(const void *q, const int *pos, const voi
                                         const float *v_scale, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
                                         float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream) {
     if (window)
-        return roped_launch<true, true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, window, stream,
-                                        k_scale, v_scale);
-    return roped_launch<false, true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, 0u, stream,
-                                     k_scale, v_scale);
+        return roped_launch<true, Fmt::FP8>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, window, stream,
+                                            k_scale, v_scale);
+    return roped_launch<false, Fmt::FP8>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, 0u, stream,
+                                         k_scale, v_scale);
 }
 
-// the per-row scaled fp8 cache form (csrc/attn_core.h): the same launches over caches of one byte per element with one exponent byte per
+// the per-row scaled fp8 cache form (csrc/kv_fmt.h): the same launches over caches of one byte per element with one exponent byte per
 // (KV head, row), k_exp / v_exp uint8 [n_kv_head][max_seq] of the batch slot; window 0: the whole context
 extern "C" int gq_attn_decode_roped_kv8r(const void *q, const int *pos, const void *k_cache, const void *v_cache, const void *k_exp,
                                          const void *v_exp, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
                                          float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream) {
     if (window)
-        return roped_launch<true, true, true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, window, stream,
-                                              nullptr, nullptr, k_exp, v_exp);
-    return roped_launch<false, true, true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, 0u, stream,
-                                           nullptr, nullptr, k_exp, v_exp);
+        return roped_launch<true, Fmt::FP8_ROW>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, window,
+                                                stream, k_exp, v_exp);
+    return roped_launch<false, Fmt::FP8_ROW>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, 0u, stream,
+                                             k_exp, v_exp);
 }
 
-// the MXFP4 cache form (csrc/attn_core.h): the same launches over caches of e2m1 codes, two per byte, with one exponent byte per (KV head,
+// the MXFP4 cache form (csrc/kv_fmt.h): the same launches over caches of e2m1 codes, two per byte, with one exponent byte per (KV head,
 // row, block of 32 elements), k_exp / v_exp uint8 [n_kv_head][max_seq][head_dim / 32] of the batch slot; window 0: the whole context
 extern "C" int gq_attn_decode_roped_mx4(const void *q, const int *pos, const void *k_cache, const void *v_cache, const void *k_exp,
                                         const void *v_exp, void *out, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq,
                                         float scale, uint32_t n_split, float *workspace, uint32_t window, void *stream) {
     if (window)
-        return roped_launch<true, true, true, true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, window,
-                                                    stream, nullptr, nullptr, k_exp, v_exp);
-    return roped_launch<false, true, true, true>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, 0u, stream,
-                                                 nullptr, nullptr, k_exp, v_exp);
+        return roped_launch<true, Fmt::MX4>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, window, stream,
+                                            k_exp, v_exp);
+    return roped_launch<false, Fmt::MX4>(q, pos, k_cache, v_cache, out, n_head, n_kv_head, head_dim, max_seq, scale, n_split, workspace, 0u, stream,
+                                         k_exp, v_exp);
 }
 
 // what attn_kv8.hip (gq_attn_decode_split_kv8: the fp8-cache form of the gq_attn_decode_split family, a translation unit of its own)

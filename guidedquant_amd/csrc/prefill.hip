@@ -11,13 +11,16 @@
 // All of them are HBM-bound streams over [S][D] fp16 rows; 16-byte accesses, one block per row (norm) / grid-stride.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "gq_internal.h"
-#include "attn_core.h"
+#include "kv_fmt.h"
 #include "wave_util.h"
 
 namespace {
 using u32 = uint32_t;
-using gq_attn::fp8_quant8;  // THE write rule of the fp8 cache (attn_core.h)
+using gq_kv::Fmt;
+using gq_kv::fp8_quant8;  // THE write rule of the fp8 cache (kv_fmt.h)
 using gqw::f2h;
 using gqw::h16;
 using gqw::h2f;
@@ -148,7 +151,7 @@ __device__ __forceinline__ void store_units(E *dst, u32 d, u32 HD, const u32 (&w
     }
 }
 
-// the per-row scaled fp8 cache (attn_core.h): the largest finite magnitude of the head's HD values -- this thread's 16, then the
+// the per-row scaled fp8 cache (kv_fmt.h): the largest finite magnitude of the head's HD values -- this thread's 16, then the
 // HD / 16 threads of the (row, head), neighbouring lanes that are active together, by group_umax -- gives the row's exponent byte by
 // integer arithmetic; the codes are fp8_quant8 of x * 2^-e (store_units), the byte is stored by the group's first thread.  A non-finite
 // element takes no part in the maximum: +-Inf clamps to +-448 at any exponent, a NaN stores a NaN code.
@@ -160,12 +163,12 @@ __device__ __forceinline__ void store_units_row(uint8_t *dst, uint8_t *exp_byte,
         a = max(a, m1 < 0x7C00u ? m1 : 0u);
         a = max(a, m2 < 0x7C00u ? m2 : 0u);
     }
-    const u32 byte = gq_attn::row_exp_byte(gq_attn::group_umax(a, HD == 128u));
+    const u32 byte = gq_kv::row_exp_byte(gq_kv::group_umax(a, HD == 128u));
     if (d == 0u) *exp_byte = (uint8_t)byte;
-    store_units(dst, d, HD, w1, w2, gq_attn::row_exp_inv(byte));
+    store_units(dst, d, HD, w1, w2, gq_kv::row_exp_inv(byte));
 }
 
-// the MXFP4 cache (attn_core.h): a block of 32 consecutive elements is the FIRST units of the 4 threads of an aligned quad (d = 0, 8, 16, 24
+// the MXFP4 cache (kv_fmt.h): a block of 32 consecutive elements is the FIRST units of the 4 threads of an aligned quad (d = 0, 8, 16, 24
 // mod 32) or their SECOND units (the same, HD / 2 further on), so a thread takes part in two blocks.  The largest magnitude bits of each
 // -- this thread's 8, then the quad by two DPP steps (group_umax), no LDS round trip -- give the block's exponent by integer arithmetic;
 // each unit's 8 codes (mx4_quant8 at 2^-e) are ONE 32-bit store into the row `dst` of HD / 2 bytes, and the quad's first thread stores the
@@ -177,29 +180,21 @@ __device__ __forceinline__ void store_units_mx4(uint8_t *dst, uint8_t *exp_row, 
         a1 = max(a1, (w1[k >> 1] >> (16 * (k & 1))) & 0x7FFFu);
         a2 = max(a2, (w2[k >> 1] >> (16 * (k & 1))) & 0x7FFFu);
     }
-    a1 = gq_attn::group_umax(a1, false);
-    a2 = gq_attn::group_umax(a2, false);
+    a1 = gq_kv::group_umax(a1, false);
+    a2 = gq_kv::group_umax(a2, false);
     if ((d & 31u) == 0u) {
-        exp_row[d / 32u] = (uint8_t)gq_attn::mx4_exp_byte(a1);
-        exp_row[(d + HD / 2u) / 32u] = (uint8_t)gq_attn::mx4_exp_byte(a2);
+        exp_row[d / 32u] = (uint8_t)gq_kv::mx4_exp_byte(a1);
+        exp_row[(d + HD / 2u) / 32u] = (uint8_t)gq_kv::mx4_exp_byte(a2);
     }
-    *reinterpret_cast<u32 *>(dst + d / 2u) = gq_attn::mx4_quant8(w1, gq_attn::row_exp_inv(gq_attn::mx4_exp_field(a1)));
-    *reinterpret_cast<u32 *>(dst + (d + HD / 2u) / 2u) = gq_attn::mx4_quant8(w2, gq_attn::row_exp_inv(gq_attn::mx4_exp_field(a2)));
+    *reinterpret_cast<u32 *>(dst + d / 2u) = gq_kv::mx4_quant8(w1, gq_kv::row_exp_inv(gq_kv::mx4_exp_field(a1)));
+    *reinterpret_cast<u32 *>(dst + (d + HD / 2u) / 2u) = gq_kv::mx4_quant8(w2, gq_kv::row_exp_inv(gq_kv::mx4_exp_field(a2)));
 }
-
-template <bool KV8>
-struct CacheElem {
-    typedef uint16_t type;
-};
-template <>
-struct CacheElem<true> {
-    typedef uint8_t type;
-};
 
 // THE row write of the prompt pass (and of the fp8 decode step, S = 1), one kernel for every layout:
 //   qkv [S][(H + 2 Hkv) HD] -> q_out [H][S][HD] (rotated), k_cache / v_cache [Hkv][max_seq][HD] at pos[s] (k rotated).
 // One thread per (token, head of q | k | v, 8 elements of the FIRST half): it owns elements d .. d + 7 and d + HD / 2 ..
-// KV8: caches of one byte per element -- the same fp16 values up to the store (q_out is bit for bit what the fp16 form writes), k / v
+// F, the cache format (kv_fmt.h); q_out is bit for bit what the fp16 form writes in every format.
+// Fmt::FP8 (gq_rope_cache_rows_kv8): caches of one byte per element -- the same fp16 values up to the store, k / v
 //   stored by fp8_quant8 with the reciprocal scale of their KV head (k_inv / v_inv: read in this form only).
 // QKN: Qwen3's per-head RMSNorm of q and k in front of the rotation (modeling_qwen3.Qwen3Attention.forward: q_norm / k_norm =
 //   Qwen3RMSNorm over head_dim, weights [HD] shared by the heads): the HD / 16 threads of a (token, head) are neighbouring lanes of one
@@ -210,31 +205,45 @@ struct CacheElem<true> {
 // PKD (gq_rope_cache_rows_packed: several sequences as one run of rows): the cache row is tail.row[s], apart from the RoPE position
 //   pos[s] inside the row's own sequence.  Every other form has the empty tail and writes row pos[s].
 // The loop bound is block-uniform in every form (QKN needs it: whole groups are active or idle together, total is a multiple of HD / 16).
-// K8R (gq_rope_cache_rows_kv8r, with KV8): the per-row scaled fp8 caches -- k and v through store_units_row, their exponent bytes to
+// Fmt::FP8_ROW (gq_rope_cache_rows_kv8r): the per-row scaled fp8 caches -- k and v through store_units_row, their exponent bytes to
 //   tail.k_exp / tail.v_exp [Hkv][max_seq]; k_inv / v_inv are not read.
-// MX4 (gq_rope_cache_rows_mx4, with K8R): the MXFP4 caches -- k and v through store_units_mx4 into rows of HD / 2 bytes, the exponent
+// Fmt::MX4 (gq_rope_cache_rows_mx4): the MXFP4 caches -- k and v through store_units_mx4 into rows of HD / 2 bytes, the exponent
 //   bytes to tail.k_exp / tail.v_exp [Hkv][max_seq][HD / 32].
-template <bool PKD, bool K8R = false>
-struct RowsTail {};
-template <>
-struct RowsTail<true, false> {
+struct PackedRows {
     const int *row;
 };
-template <>
-struct RowsTail<false, true> {
-    uint8_t *k_exp, *v_exp;
-};
+// the kernel's last argument: the cache rows of the packed pass, else the exponent bytes the format writes (empty where it writes none)
+template <Fmt F, bool PKD>
+using RowsTail = std::conditional_t<PKD, PackedRows, gq_kv::WriteSide<gq_kv::Traits<F>::row_exp>>;
 
-template <bool QKN, bool QB, bool KV8, bool PKD = false, bool K8R = false, bool MX4 = false>
+// one (row, head) of k or v into the cache row `cr` of KV head g, by the write rule of the format (inv: the reciprocal scales, fp8 alone)
+template <Fmt F>
+__device__ __forceinline__ void store_kv(typename gq_kv::Traits<F>::elem *cache, uint8_t *exp, const float *__restrict__ inv, u32 g, u32 max_seq, u32 cr,
+                                         u32 d, u32 HD, const u32 (&w1)[4], const u32 (&w2)[4]) {
+    using T = gq_kv::Traits<F>;
+    // (the row index is spelled out per address: from a shared one the per-row instances compute their addresses another way)
+    if constexpr (T::block_exp) {
+        store_units_mx4(cache + ((size_t)g * max_seq + cr) * (HD / 2u), exp + ((size_t)g * max_seq + cr) * (HD / 32u), d, HD, w1, w2);
+    } else if constexpr (T::row_exp) {
+        store_units_row(cache + ((size_t)g * max_seq + cr) * HD, exp + (size_t)g * max_seq + cr, d, HD, w1, w2);
+    } else {
+        float f = 0.f;
+        if constexpr (T::head_scale) f = inv[g];
+        store_units(cache + ((size_t)g * max_seq + cr) * HD, d, HD, w1, w2, f);
+    }
+}
+
+template <bool QKN, bool QB, Fmt F, bool PKD = false>
 __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__restrict__ qkv, const int *__restrict__ pos,
                                                               const uint16_t *__restrict__ cos_t, const uint16_t *__restrict__ sin_t,
-                                                              uint16_t *__restrict__ q_out, typename CacheElem<KV8>::type *__restrict__ kc,
-                                                              typename CacheElem<KV8>::type *__restrict__ vc, const float *__restrict__ k_inv,
+                                                              uint16_t *__restrict__ q_out, typename gq_kv::Traits<F>::elem *__restrict__ kc,
+                                                              typename gq_kv::Traits<F>::elem *__restrict__ vc, const float *__restrict__ k_inv,
                                                               const float *__restrict__ v_inv, const uint16_t *__restrict__ qnw,
                                                               const uint16_t *__restrict__ knw, float eps, const uint16_t *__restrict__ bias, u32 S,
-                                                              u32 H, u32 Hkv, u32 HD, u32 max_seq, RowsTail<PKD, K8R> tail) {
-    static_assert(!K8R || (KV8 && !PKD), "the per-row scaled form is a form of the fp8 caches");
-    static_assert(!MX4 || K8R, "the MXFP4 form is the per-row scaled form with the exponent per block");
+                                                              u32 H, u32 Hkv, u32 HD, u32 max_seq, RowsTail<F, PKD> tail) {
+    static_assert(!PKD || F == Fmt::F16, "the packed pass has fp16 caches");
+    uint8_t *k_exp = nullptr, *v_exp = nullptr;
+    if constexpr (gq_kv::Traits<F>::row_exp) k_exp = tail.k_exp, v_exp = tail.v_exp;
     const u32 upr = HD / 16u, heads = H + 2u * Hkv, total = S * heads * upr;  // units of 8 in the first half
     for (u32 base = blockIdx.x * 256u; base < total; base += gridDim.x * 256u) {
         const u32 i = base + threadIdx.x;
@@ -281,18 +290,7 @@ __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__
         }
         if (!active) continue;
         if (hh >= H + Hkv) {  // v: stored as it is
-            if (cr < max_seq) {
-                const u32 g = hh - H - Hkv;
-                if constexpr (MX4) {
-                    store_units_mx4(vc + ((size_t)g * max_seq + cr) * (HD / 2u), tail.v_exp + ((size_t)g * max_seq + cr) * (HD / 32u), d, HD, x1, x2);
-                } else if constexpr (K8R) {
-                    store_units_row(vc + ((size_t)g * max_seq + cr) * HD, tail.v_exp + (size_t)g * max_seq + cr, d, HD, x1, x2);
-                } else {
-                    float inv = 0.f;
-                    if constexpr (KV8) inv = v_inv[g];
-                    store_units(vc + ((size_t)g * max_seq + cr) * HD, d, HD, x1, x2, inv);
-                }
-            }
+            if (cr < max_seq) store_kv<F>(vc, v_exp, v_inv, hh - H - Hkv, max_seq, cr, d, HD, x1, x2);
             continue;
         }
         if constexpr (QKN) {
@@ -321,16 +319,7 @@ __global__ void __launch_bounds__(256) rope_cache_rows_kernel(const uint16_t *__
         if (hh < H) {
             store_units(q_out + ((size_t)hh * S + s) * HD, d, HD, o1, o2, 0.f);
         } else if (cr < max_seq) {
-            const u32 g = hh - H;
-            if constexpr (MX4) {
-                store_units_mx4(kc + ((size_t)g * max_seq + cr) * (HD / 2u), tail.k_exp + ((size_t)g * max_seq + cr) * (HD / 32u), d, HD, o1, o2);
-            } else if constexpr (K8R) {
-                store_units_row(kc + ((size_t)g * max_seq + cr) * HD, tail.k_exp + (size_t)g * max_seq + cr, d, HD, o1, o2);
-            } else {
-                float inv = 0.f;
-                if constexpr (KV8) inv = k_inv[g];
-                store_units(kc + ((size_t)g * max_seq + cr) * HD, d, HD, o1, o2, inv);
-            }
+            store_kv<F>(kc, k_exp, k_inv, hh - H, max_seq, cr, d, HD, o1, o2);
         }
     }
 }
@@ -379,12 +368,13 @@ struct RowsEntry {
     const char *bad_hd, *unaligned, *too_large;
 };
 
-// the checks from `S == 0` on, the grid rule and the launch of rope_cache_rows_kernel<QKN, QB, KV8>: the norm form with norm weights,
-// the bias form with a bias, the fp8 form with `kv8` (k_inv / v_inv are read by that form only)
-int rope_cache_rows(const RowsEntry &e, bool kv8, const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
+// the checks from `S == 0` on, the grid rule and the launch of rope_cache_rows_kernel<QKN, QB, F>: the norm form with norm weights,
+// the bias form with a bias (k_inv / v_inv are read by Fmt::FP8 only, k_exp / v_exp by the formats with exponent bytes)
+template <Fmt F>
+int rope_cache_rows(const RowsEntry &e, const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
                     void *v_cache, const float *k_inv, const float *v_inv, u32 S, u32 n_head, u32 n_kv_head, u32 head_dim, u32 max_seq,
                     const void *q_norm_weight, const void *k_norm_weight, float eps, const void *qkv_bias, void *stream, const int *row = nullptr,
-                    void *k_exp = nullptr, void *v_exp = nullptr, bool mx4 = false) {
+                    void *k_exp = nullptr, void *v_exp = nullptr) {
     if (S == 0) return GQ_OK;
     // (QKN: the statistic of a head is added inside an aligned group of head_dim / 16 lanes: a power of two, within one wave)
     const bool hd_ok = e.any_hd16 ? (head_dim != 0 && head_dim % 16u == 0) : (head_dim == 64u || head_dim == 128u);
@@ -396,37 +386,31 @@ int rope_cache_rows(const RowsEntry &e, bool kv8, const void *qkv, const int *po
     if (total >= 0x7FFFFFFFull) return gq_fail(GQ_ENOTSUP, e.too_large);
     const u32 nb = (u32)((total + 255u) / 256u);
     const dim3 grid(nb > 65535u ? 65535u : nb), block(256);
-#define GQ_LAUNCH_ROWS_EX(QKN_, QB_, KV8_, PKD_, TAIL_, K8R_, ...)                                                                             \
-    hipLaunchKernelGGL((rope_cache_rows_kernel<QKN_, QB_, KV8_, PKD_, K8R_, ##__VA_ARGS__>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)qkv, pos, \
-                       (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)q_out, (CacheElem<KV8_>::type *)k_cache,         \
-                       (CacheElem<KV8_>::type *)v_cache, k_inv, v_inv, (const uint16_t *)q_norm_weight, (const uint16_t *)k_norm_weight, eps, \
-                       (const uint16_t *)qkv_bias, S, n_head, n_kv_head, head_dim, max_seq, TAIL_)
-#define GQ_LAUNCH_ROWS(QKN_, QB_, KV8_, PKD_, TAIL_) GQ_LAUNCH_ROWS_EX(QKN_, QB_, KV8_, PKD_, TAIL_, false)
-    const RowsTail<false> none = {};
-    const RowsTail<true> rows = {row};
-    const RowsTail<false, true> ex = {(uint8_t *)k_exp, (uint8_t *)v_exp};
-    if (mx4) {  // (the MXFP4 caches)
-        if (q_norm_weight) GQ_LAUNCH_ROWS_EX(true, false, true, false, ex, true, true);
-        else if (qkv_bias) GQ_LAUNCH_ROWS_EX(false, true, true, false, ex, true, true);
-        else GQ_LAUNCH_ROWS_EX(false, false, true, false, ex, true, true);
-    } else if (k_exp) {  // (the per-row scaled fp8 caches)
-        if (q_norm_weight) GQ_LAUNCH_ROWS_EX(true, false, true, false, ex, true);
-        else if (qkv_bias) GQ_LAUNCH_ROWS_EX(false, true, true, false, ex, true);
-        else GQ_LAUNCH_ROWS_EX(false, false, true, false, ex, true);
-    } else if (row) {  // (the packed pass: fp16 caches)
-        if (q_norm_weight) GQ_LAUNCH_ROWS(true, false, false, true, rows);
-        else GQ_LAUNCH_ROWS(false, false, false, true, rows);
-    } else if (kv8) {
-        if (q_norm_weight) GQ_LAUNCH_ROWS(true, false, true, false, none);
-        else if (qkv_bias) GQ_LAUNCH_ROWS(false, true, true, false, none);
-        else GQ_LAUNCH_ROWS(false, false, true, false, none);
-    } else if (q_norm_weight) {
-        GQ_LAUNCH_ROWS(true, false, false, false, none);
+    using CE = typename gq_kv::Traits<F>::elem;
+#define GQ_LAUNCH_ROWS(QKN_, QB_, F_, PKD_, ...)                                                                                               \
+    hipLaunchKernelGGL((rope_cache_rows_kernel<QKN_, QB_, F_, PKD_>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)qkv, pos,       \
+                       (const uint16_t *)cos_table, (const uint16_t *)sin_table, (uint16_t *)q_out, (CE *)k_cache, (CE *)v_cache, k_inv, v_inv, \
+                       (const uint16_t *)q_norm_weight, (const uint16_t *)k_norm_weight, eps, (const uint16_t *)qkv_bias, S, n_head,          \
+                       n_kv_head, head_dim, max_seq, RowsTail<F_, PKD_>{__VA_ARGS__})
+    if constexpr (F == Fmt::F16) {  // (no bias form: the prompt pass's linears add the bias themselves)
+        if (row) {                  // (the packed pass)
+            if (q_norm_weight) GQ_LAUNCH_ROWS(true, false, Fmt::F16, true, row);
+            else GQ_LAUNCH_ROWS(false, false, Fmt::F16, true, row);
+        } else if (q_norm_weight) {
+            GQ_LAUNCH_ROWS(true, false, Fmt::F16, false);
+        } else {
+            GQ_LAUNCH_ROWS(false, false, Fmt::F16, false);
+        }
+    } else if constexpr (gq_kv::Traits<F>::row_exp) {
+        if (q_norm_weight) GQ_LAUNCH_ROWS(true, false, F, false, (uint8_t *)k_exp, (uint8_t *)v_exp);
+        else if (qkv_bias) GQ_LAUNCH_ROWS(false, true, F, false, (uint8_t *)k_exp, (uint8_t *)v_exp);
+        else GQ_LAUNCH_ROWS(false, false, F, false, (uint8_t *)k_exp, (uint8_t *)v_exp);
     } else {
-        GQ_LAUNCH_ROWS(false, false, false, false, none);
+        if (q_norm_weight) GQ_LAUNCH_ROWS(true, false, F, false);
+        else if (qkv_bias) GQ_LAUNCH_ROWS(false, true, F, false);
+        else GQ_LAUNCH_ROWS(false, false, F, false);
     }
 #undef GQ_LAUNCH_ROWS
-#undef GQ_LAUNCH_ROWS_EX
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
 }
@@ -448,8 +432,8 @@ extern "C" int gq_rope_cache_rows(const void *qkv, const int *pos, const void *c
     if (!qkv || !pos || !cos_table || !sin_table || !q_out || !k_cache || !v_cache) return gq_fail(GQ_EINVAL, "null pointer argument.");
     static const RowsEntry e = {true, "gq_rope_cache_rows: head_dim must be a multiple of 16.", "gq_rope_cache_rows: 16-byte aligned pointers.",
                                 "gq_rope_cache_rows: problem too large."};
-    return rope_cache_rows(e, false, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim, max_seq,
-                           nullptr, nullptr, 0.f, nullptr, stream);
+    return rope_cache_rows<Fmt::F16>(e, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim, max_seq,
+                                     nullptr, nullptr, 0.f, nullptr, stream);
 }
 
 extern "C" int gq_qknorm_rope_cache_rows(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
@@ -459,8 +443,8 @@ extern "C" int gq_qknorm_rope_cache_rows(const void *qkv, const int *pos, const 
         return gq_fail(GQ_EINVAL, "null pointer argument.");
     static const RowsEntry e = {false, "gq_qknorm_rope_cache_rows: head_dim must be 64 or 128.", "gq_qknorm_rope_cache_rows: 16-byte aligned pointers.",
                                 "gq_qknorm_rope_cache_rows: problem too large."};
-    return rope_cache_rows(e, false, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim, max_seq,
-                           q_norm_weight, k_norm_weight, eps, nullptr, stream);
+    return rope_cache_rows<Fmt::F16>(e, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim, max_seq,
+                                     q_norm_weight, k_norm_weight, eps, nullptr, stream);
 }
 
 extern "C" int gq_rope_cache_rows_kv8(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
@@ -473,8 +457,8 @@ extern "C" int gq_rope_cache_rows_kv8(const void *qkv, const int *pos, const voi
     if (qkn && qkv_bias) return gq_fail(GQ_EINVAL, "gq_rope_cache_rows_kv8: the norm form and the bias form do not combine.");
     static const RowsEntry e = {false, "gq_rope_cache_rows_kv8: head_dim must be 64 or 128.", "gq_rope_cache_rows_kv8: 16-byte aligned pointers.",
                                 "gq_rope_cache_rows_kv8: problem too large."};
-    return rope_cache_rows(e, true, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, k_inv, v_inv, S, n_head, n_kv_head, head_dim, max_seq, q_norm_weight,
-                           k_norm_weight, eps, qkv_bias, stream);
+    return rope_cache_rows<Fmt::FP8>(e, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, k_inv, v_inv, S, n_head, n_kv_head, head_dim, max_seq,
+                                     q_norm_weight, k_norm_weight, eps, qkv_bias, stream);
 }
 
 extern "C" int gq_rope_cache_rows_kv8r(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
@@ -488,11 +472,11 @@ extern "C" int gq_rope_cache_rows_kv8r(const void *qkv, const int *pos, const vo
     static const RowsEntry e = {false, "gq_rope_cache_rows_kv8r: head_dim must be 64 or 128.", "gq_rope_cache_rows_kv8r: 16-byte aligned pointers.",
                                 "gq_rope_cache_rows_kv8r: problem too large."};
     // (the exponent bytes are stored one at a time: no alignment asked of k_exp / v_exp)
-    return rope_cache_rows(e, true, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim, max_seq, q_norm_weight,
-                           k_norm_weight, eps, qkv_bias, stream, nullptr, k_exp, v_exp);
+    return rope_cache_rows<Fmt::FP8_ROW>(e, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim, max_seq,
+                                         q_norm_weight, k_norm_weight, eps, qkv_bias, stream, nullptr, k_exp, v_exp);
 }
 
-// the MXFP4 form: codes [n_kv_head][max_seq][head_dim / 2], exponent bytes [n_kv_head][max_seq][head_dim / 32] (csrc/attn_core.h)
+// the MXFP4 form: codes [n_kv_head][max_seq][head_dim / 2], exponent bytes [n_kv_head][max_seq][head_dim / 32] (csrc/kv_fmt.h)
 extern "C" int gq_rope_cache_rows_mx4(const void *qkv, const int *pos, const void *cos_table, const void *sin_table, void *q_out, void *k_cache,
                                       void *v_cache, void *k_exp, void *v_exp, uint32_t S, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim,
                                       uint32_t max_seq, const void *q_norm_weight, const void *k_norm_weight, float eps, const void *qkv_bias,
@@ -504,8 +488,8 @@ extern "C" int gq_rope_cache_rows_mx4(const void *qkv, const int *pos, const voi
     static const RowsEntry e = {false, "gq_rope_cache_rows_mx4: head_dim must be 64 or 128.", "gq_rope_cache_rows_mx4: 16-byte aligned pointers.",
                                 "gq_rope_cache_rows_mx4: problem too large."};
     // (a row of codes is head_dim / 2 >= 32 bytes: 4-byte stores stay aligned in a 16-byte aligned cache; the exponent bytes need none)
-    return rope_cache_rows(e, true, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim, max_seq, q_norm_weight,
-                           k_norm_weight, eps, qkv_bias, stream, nullptr, k_exp, v_exp, true);
+    return rope_cache_rows<Fmt::MX4>(e, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim, max_seq,
+                                     q_norm_weight, k_norm_weight, eps, qkv_bias, stream, nullptr, k_exp, v_exp);
 }
 
 extern "C" int gq_rope_cache_rows_packed(const void *qkv, const int *pos, const int *row, const void *cos_table, const void *sin_table, void *q_out,
@@ -519,7 +503,7 @@ extern "C" int gq_rope_cache_rows_packed(const void *qkv, const int *pos, const 
                                     "gq_rope_cache_rows_packed: problem too large."};
     static const RowsEntry norm = {false, "gq_rope_cache_rows_packed: head_dim must be 64 or 128 with the norm weights.",
                                    "gq_rope_cache_rows_packed: 16-byte aligned pointers.", "gq_rope_cache_rows_packed: problem too large."};
-    return rope_cache_rows(qkn ? norm : plain, false, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim,
+    return rope_cache_rows<Fmt::F16>(qkn ? norm : plain, qkv, pos, cos_table, sin_table, q_out, k_cache, v_cache, nullptr, nullptr, S, n_head, n_kv_head, head_dim,
                            max_seq, q_norm_weight, k_norm_weight, eps, nullptr, stream, row);
 }
 

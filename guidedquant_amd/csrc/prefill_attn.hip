@@ -35,7 +35,7 @@
 #include <type_traits>
 
 #include "gq_internal.h"
-#include "attn_core.h"
+#include "kv_fmt.h"
 #include "wave_util.h"
 
 namespace {
@@ -56,40 +56,18 @@ __device__ __forceinline__ h16x4 lds_read_tr(const h16 *p) {
     return __builtin_bit_cast(h16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)p));
 }
 
-// the cache format of an instance.  fp8 (gq_attn_prefill_kv8): a chunk of 8 elements is 8 bytes of OCP e4m3 codes, converted to fp16 --
-// exactly: every e4m3 value is an fp16 value -- between the global load and the LDS store, so the LDS image, the fragments and both
-// products are those of the fp16 instance on the same numbers; the scales (fp32 per KV head, device memory) stay outside the products
-template <bool KV8>
-struct TileFmt {
-    typedef uint16_t elem;
-    typedef uint4 chunk;
-    struct Scales {};
-    static __device__ __forceinline__ chunk zero() { return make_uint4(0u, 0u, 0u, 0u); }
-    static __device__ __forceinline__ uint4 to_f16(const chunk &v) { return v; }
-};
-template <>
-struct TileFmt<true> {
-    typedef uint8_t elem;
-    typedef uint2 chunk;
-    struct Scales {
-        const float *k_scale, *v_scale;
-    };
-    static __device__ __forceinline__ chunk zero() { return make_uint2(0u, 0u); }
-    static __device__ __forceinline__ uint4 to_f16(const chunk &v) {
-        const u32 w[2] = {v.x, v.y};
-        u32 o[4];
-#pragma unroll
-        for (int e = 0; e < 2; e++) {
-            const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[e], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[e], true);
-            o[2 * e] = (u32)__builtin_bit_cast(uint16_t, (h16)lo[0]) | ((u32)__builtin_bit_cast(uint16_t, (h16)lo[1]) << 16);
-            o[2 * e + 1] = (u32)__builtin_bit_cast(uint16_t, (h16)hi[0]) | ((u32)__builtin_bit_cast(uint16_t, (h16)hi[1]) << 16);
-        }
-        return make_uint4(o[0], o[1], o[2], o[3]);
-    }
-    // the per-row scaled form (ROW, gq_attn_prefill_kv8r; csrc/attn_core.h): fp16(code) * 2^e with the row's exponent byte, e in [-15, 7] --
-    // the product is an fp16 value, so the rounding to fp16 is exact and the LDS image is that of an fp16 cache holding code * 2^e
-    static __device__ __forceinline__ uint4 to_f16_row(const chunk &v, u32 byte) {
-        const float sc = __builtin_bit_cast(float, byte << 23);
+// the tile conversion of a format F (kv_fmt.h): a chunk of 8 elements -- 16 bytes of fp16, 8 bytes of OCP e4m3 codes, 4 bytes of e2m1
+// codes inside ONE block of 32 -- becomes 8 fp16 values between the global load and the LDS store, by the format's read rule (Traits<F>::
+// unpack with the exponent byte of the chunk's row or block) and one rounding to fp16.  The rounding is exact: every e4m3 value, every
+// fp16(code) * 2^e of the per-row form (e in [-15, 7]) and every e2m1(code) * 2^e of an MXFP4 block (NaN for the byte 0xFF) is an fp16
+// value.  So the LDS image, the fragments and both products are those of the fp16 instance over a cache that holds the same numbers; the
+// per-head scales of Fmt::FP8 (fp32 per KV head, device memory) stay outside the products.
+template <gq_kv::Fmt F>
+__device__ __forceinline__ uint4 to_f16(typename gq_kv::Traits<F>::load v, u32 byte) {
+    if constexpr (F == gq_kv::Fmt::F16) {
+        return v;
+    } else if constexpr (F == gq_kv::Fmt::FP8_ROW) {  // (2^e applied pair by pair, the spelling this form had: behind Traits::unpack the tile loop schedules otherwise)
+        const float sc = gq_kv::row_exp_scale(byte);
         const u32 w[2] = {v.x, v.y};
         u32 o[4];
 #pragma unroll
@@ -99,40 +77,25 @@ struct TileFmt<true> {
             o[2 * e + 1] = (u32)__builtin_bit_cast(uint16_t, (h16)(hi[0] * sc)) | ((u32)__builtin_bit_cast(uint16_t, (h16)(hi[1] * sc)) << 16);
         }
         return make_uint4(o[0], o[1], o[2], o[3]);
-    }
-    // the MXFP4 form (MX4, gq_attn_prefill_mx4; csrc/attn_core.h): a chunk of 8 elements is 4 bytes of e2m1 codes inside ONE block of 32,
-    // unpacked by v_cvt_scalef32_pk_f32_fp4 and multiplied by the block's 2^e (NaN for the byte 0xFF) -- fp16 values, so the rounding to
-    // fp16 is exact and the LDS image is that of an fp16 cache holding code * 2^e
-    static __device__ __forceinline__ uint4 to_f16_mx4(u32 v, u32 byte) {
+    } else {
         float f[8];
-        gq_attn::unpack8_mx4(v, gq_attn::mx4_scale(byte), f);
+        gq_kv::Traits<F>::unpack(v, byte, f);
         u32 o[4];
 #pragma unroll
         for (int e = 0; e < 4; e++)
             o[e] = (u32)__builtin_bit_cast(uint16_t, (h16)f[2 * e]) | ((u32)__builtin_bit_cast(uint16_t, (h16)f[2 * e + 1]) << 16);
         return make_uint4(o[0], o[1], o[2], o[3]);
     }
-};
+}
 
-// the kernel's last argument: the scales of an fp8 cache, or -- PACKED, fp16 caches -- the segment begins (an instance that is neither
-// keeps the empty struct it had: its arguments and its code are those of the kernel without the flag)
-// -- or, ROW, the exponent bytes of a per-row scaled fp8 cache, uint8 [n_kv_head][max_seq]
-template <bool KV8, bool PACKED, bool ROW = false>
-struct TailArg {
-    typedef typename TileFmt<KV8>::Scales type;
+// the kernel's last argument: what the format passes beside the caches (kv_fmt.h, Side<F>: nothing, the scales of an fp8 cache, the
+// exponent bytes) or -- PACKED, fp16 caches -- the segment begins (an instance that has neither keeps the empty struct it had: its
+// arguments and its code are those of the kernel without the flag)
+struct SegBegin {
+    const int *seg_begin;
 };
-template <>
-struct TailArg<false, true, false> {
-    struct type {
-        const int *seg_begin;
-    };
-};
-template <>
-struct TailArg<true, false, true> {
-    struct type {
-        const uint8_t *k_exp, *v_exp;
-    };
-};
+template <gq_kv::Fmt F, bool PACKED>
+using AttnTail = std::conditional_t<PACKED, SegBegin, gq_kv::Side<F>>;
 
 // PACKED: the first key row `i` attends: its segment's begin, clamped to i (a malformed array never leaves rows [0, S)), or the window's
 __device__ __forceinline__ u32 packed_lo(const int *__restrict__ seg_begin, u32 i, u32 window) {
@@ -148,22 +111,19 @@ __device__ __forceinline__ u32 packed_lo(const int *__restrict__ seg_begin, u32 
 // that segment's rows only -- P = 0 alone does not keep another sequence's rows out: 0 x NaN inside an MFMA is NaN.  For a row the
 // products and their order are those of the one-sequence kernel (a masked key adds +-0 either way), so row i is bit for bit row i of
 // gq_attn_prefill(S = i + 1, start = 0, window = min(i - seg_begin[i] + 1, window)).
-// ROW (with KV8): a thread fetches the exponent bytes of its chunks' rows with the chunks (the CH threads of a row ask for the same byte)
-// and multiplies between the global load and the LDS store; the scales of the per-head form are not read.
-// MX4 (with ROW): rows of HD / 2 bytes of e2m1 codes, a chunk is one 4-byte load, and the byte fetched with it is that of the chunk's
+// F, the cache format (kv_fmt.h).  Fmt::FP8_ROW: a thread fetches the exponent bytes of its chunks' rows with the chunks (the CH threads of
+// a row ask for the same byte) and multiplies between the global load and the LDS store; no per-head scale is read.
+// Fmt::MX4: rows of HD / 2 bytes of e2m1 codes, a chunk is one 4-byte load, and the byte fetched with it is that of the chunk's
 // block (col / 4) in exponent rows of HD / 32 bytes.
-template <int HD, bool KV8 = false, bool PACKED = false, bool ROW = false, bool MX4 = false>
-__global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__restrict__ q, const typename TileFmt<KV8>::elem *__restrict__ kc,
-                                                           const typename TileFmt<KV8>::elem *__restrict__ vc, uint16_t *__restrict__ out, u32 S,
-                                                           u32 start, u32 H, u32 group, u32 max_seq, float c, u32 window,
-                                                           typename TailArg<KV8, PACKED, ROW>::type sc) {
-    static_assert(!(KV8 && PACKED), "the packed pass has fp16 caches");
-    static_assert(!ROW || KV8, "the per-row scaled form is a form of the fp8 caches");
-    static_assert(!MX4 || ROW, "the MXFP4 form is the per-row scaled form with the exponent per block");
-    using Fmt = TileFmt<KV8>;
-    using Chunk = typename std::conditional<MX4, u32, typename Fmt::chunk>::type;
-    constexpr u32 RE = MX4 ? HD / 2 : HD, CE = MX4 ? 4 : 8;  // cache elements of a row, of a chunk
-    constexpr u32 XR = MX4 ? HD / 32 : 1;                    // exponent bytes of a row
+template <int HD, gq_kv::Fmt F = gq_kv::Fmt::F16, bool PACKED = false>
+__global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__restrict__ q, const typename gq_kv::Traits<F>::elem *__restrict__ kc,
+                                                           const typename gq_kv::Traits<F>::elem *__restrict__ vc, uint16_t *__restrict__ out, u32 S,
+                                                           u32 start, u32 H, u32 group, u32 max_seq, float c, u32 window, AttnTail<F, PACKED> sc) {
+    static_assert(!PACKED || F == gq_kv::Fmt::F16, "the packed pass has fp16 caches");
+    using Tr = gq_kv::Traits<F>;
+    using Chunk = typename Tr::load;
+    constexpr u32 RE = HD / Tr::ROW_DIV, CE = Tr::LANE;  // cache elements of a row, of a chunk
+    constexpr u32 XR = Tr::exp_bytes(HD);               // exponent bytes of a row
     constexpr u32 LD = HD + 8;             // halves per LDS row: 16 bytes of padding
     constexpr u32 CH = HD / 8;             // 16-byte chunks per row
     constexpr u32 NCH = BK * CH / 256;     // chunks per thread and matrix
@@ -175,10 +135,10 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
     const u32 head = blockIdx.y, kvh = head / group;  // (once per block)
     const u32 q0 = (gridDim.x - 1u - blockIdx.x) * BQ;  // the long rows of the triangle first
     const u32 T = start + S;
-    const typename Fmt::elem *kbase = kc + (size_t)kvh * max_seq * RE, *vbase = vc + (size_t)kvh * max_seq * RE;
-    if constexpr (KV8 && !ROW) c *= sc.k_scale[kvh];  // (the K scale: one factor of the scores)
+    const typename Tr::elem *kbase = kc + (size_t)kvh * max_seq * RE, *vbase = vc + (size_t)kvh * max_seq * RE;
+    if constexpr (Tr::head_scale) c *= sc.k_scale[kvh];  // (the K scale: one factor of the scores)
     const uint8_t *kebase = nullptr, *vebase = nullptr;
-    if constexpr (ROW) kebase = sc.k_exp + (size_t)kvh * max_seq * XR, vebase = sc.v_exp + (size_t)kvh * max_seq * XR;
+    if constexpr (Tr::row_exp) kebase = sc.k_exp + (size_t)kvh * max_seq * XR, vebase = sc.v_exp + (size_t)kvh * max_seq * XR;
 
     // the block's key range: [klo, khi] covers every key one of its rows attends
     const u32 p_lo = start + q0, khi = start + min(q0 + BQ - 1u, S - 1u);
@@ -209,7 +169,7 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
     }
 
     Chunk kreg[NCH], vreg[NCH];
-    u32 kexp[ROW ? NCH : 1], vexp[ROW ? NCH : 1];  // (ROW: the exponent bytes of the chunks' rows)
+    u32 kexp[Tr::row_exp ? NCH : 1], vexp[Tr::row_exp ? NCH : 1];  // (the exponent bytes of the chunks' rows or blocks, where the format has them)
     auto load_tile = [&](u32 kt) {
 #pragma unroll
         for (u32 i = 0; i < NCH; i++) {
@@ -217,15 +177,12 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
             if (t < T) {
                 kreg[i] = *reinterpret_cast<const Chunk *>(kbase + (size_t)t * RE + CE * col);
                 vreg[i] = *reinterpret_cast<const Chunk *>(vbase + (size_t)t * RE + CE * col);
-                if constexpr (MX4) kexp[i] = kebase[(size_t)t * XR + col / 4u], vexp[i] = vebase[(size_t)t * XR + col / 4u];
-                else if constexpr (ROW) kexp[i] = kebase[t], vexp[i] = vebase[t];
-            } else if constexpr (MX4) {
-                kreg[i] = 0u, vreg[i] = 0u;
-                kexp[i] = 127u, vexp[i] = 127u;
+                if constexpr (Tr::block_exp) kexp[i] = kebase[(size_t)t * XR + col / 4u], vexp[i] = vebase[(size_t)t * XR + col / 4u];
+                else if constexpr (Tr::row_exp) kexp[i] = kebase[t], vexp[i] = vebase[t];
             } else {
-                kreg[i] = Fmt::zero();
-                vreg[i] = Fmt::zero();
-                if constexpr (ROW) kexp[i] = 127u, vexp[i] = 127u;
+                kreg[i] = Tr::zero();
+                vreg[i] = Tr::zero();
+                if constexpr (Tr::row_exp) kexp[i] = 127u, vexp[i] = 127u;
             }
         }
     };
@@ -241,16 +198,8 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
 #pragma unroll
         for (u32 i = 0; i < NCH; i++) {
             const u32 id = tid + 256u * i, row = id / CH, col = id % CH;
-            if constexpr (MX4) {
-                *reinterpret_cast<uint4 *>(&sK[row * LD + 8u * col]) = Fmt::to_f16_mx4(kreg[i], kexp[i]);
-                *reinterpret_cast<uint4 *>(&sV[row * LD + 8u * col]) = Fmt::to_f16_mx4(vreg[i], vexp[i]);
-            } else if constexpr (ROW) {
-                *reinterpret_cast<uint4 *>(&sK[row * LD + 8u * col]) = Fmt::to_f16_row(kreg[i], kexp[i]);
-                *reinterpret_cast<uint4 *>(&sV[row * LD + 8u * col]) = Fmt::to_f16_row(vreg[i], vexp[i]);
-            } else {
-                *reinterpret_cast<uint4 *>(&sK[row * LD + 8u * col]) = Fmt::to_f16(kreg[i]);
-                *reinterpret_cast<uint4 *>(&sV[row * LD + 8u * col]) = Fmt::to_f16(vreg[i]);
-            }
+            *reinterpret_cast<uint4 *>(&sK[row * LD + 8u * col]) = to_f16<F>(kreg[i], Tr::row_exp ? kexp[i] : 0u);
+            *reinterpret_cast<uint4 *>(&sV[row * LD + 8u * col]) = to_f16<F>(vreg[i], Tr::row_exp ? vexp[i] : 0u);
         }
         __syncthreads();
         if (kt < kt1) load_tile(kt + 1u);  // in flight under the products below
@@ -360,7 +309,7 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(const uint16_t *__res
     l_run += __shfl_xor(l_run, 32, 64);
     if (qrow < S) {
         float inv = 1.0f / l_run;
-        if constexpr (KV8 && !ROW) inv *= sc.v_scale[kvh];  // (the V scale: on the output, in front of its one fp16 rounding)
+        if constexpr (Tr::head_scale) inv *= sc.v_scale[kvh];  // (the V scale: on the output, in front of its one fp16 rounding)
         uint16_t *orow = out + (size_t)qrow * H * HD + (size_t)head * HD + 4u * g;
 #pragma unroll
         for (u32 d = 0; d < DB; d++) {
@@ -376,11 +325,11 @@ extern "C" int gq_attn_prefill_supported(uint32_t n_head, uint32_t n_kv_head, ui
 }
 
 namespace {
-template <bool KV8, bool PACKED = false, bool ROW = false, bool MX4 = false>
+template <gq_kv::Fmt F, bool PACKED = false>
 int prefill_attn_launch(const void *q, const void *k_cache, const void *v_cache, void *out, uint32_t S, uint32_t start, uint32_t n_head,
                         uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t window, void *stream,
-                        typename TailArg<KV8, PACKED, ROW>::type sc) {
-    using CE = typename TileFmt<KV8>::elem;
+                        AttnTail<F, PACKED> sc) {
+    using CE = typename gq_kv::Traits<F>::elem;
     if (!gq_attn_prefill_supported(n_head, n_kv_head, head_dim))
         return gq_fail(GQ_ENOTSUP, "gq_attn_prefill: head_dim 64 or 128, n_head a multiple of n_kv_head.");
     if (!q || !k_cache || !v_cache || !out) return gq_fail(GQ_EINVAL, "null pointer argument.");
@@ -398,10 +347,10 @@ int prefill_attn_launch(const void *q, const void *k_cache, const void *v_cache,
     const dim3 grid((S + BQ - 1u) / BQ, n_head), block(256);
     const uint32_t group = n_head / n_kv_head;
     if (head_dim == 64u)
-        hipLaunchKernelGGL((prefill_attn_kernel<64, KV8, PACKED, ROW, MX4>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
+        hipLaunchKernelGGL((prefill_attn_kernel<64, F, PACKED>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
                            (uint16_t *)out, S, start, n_head, group, max_seq, c, window, sc);
     else
-        hipLaunchKernelGGL((prefill_attn_kernel<128, KV8, PACKED, ROW, MX4>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
+        hipLaunchKernelGGL((prefill_attn_kernel<128, F, PACKED>), grid, block, 0, (hipStream_t)stream, (const uint16_t *)q, (const CE *)k_cache, (const CE *)v_cache,
                            (uint16_t *)out, S, start, n_head, group, max_seq, c, window, sc);
     GQ_HIP_CHECK(hipGetLastError());
     return GQ_OK;
@@ -410,34 +359,34 @@ int prefill_attn_launch(const void *q, const void *k_cache, const void *v_cache,
 
 extern "C" int gq_attn_prefill(const void *q, const void *k_cache, const void *v_cache, void *out, uint32_t S, uint32_t start, uint32_t n_head,
                                uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t window, void *stream) {
-    return prefill_attn_launch<false>(q, k_cache, v_cache, out, S, start, n_head, n_kv_head, head_dim, max_seq, scale, window, stream, {});
+    return prefill_attn_launch<gq_kv::Fmt::F16>(q, k_cache, v_cache, out, S, start, n_head, n_kv_head, head_dim, max_seq, scale, window, stream, {});
 }
 
 extern "C" int gq_attn_prefill_kv8(const void *q, const void *k_cache, const void *v_cache, const float *k_scale, const float *v_scale, void *out,
                                    uint32_t S, uint32_t start, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale,
                                    uint32_t window, void *stream) {
     if (!k_scale || !v_scale) return gq_fail(GQ_EINVAL, "null pointer argument.");
-    return prefill_attn_launch<true>(q, k_cache, v_cache, out, S, start, n_head, n_kv_head, head_dim, max_seq, scale, window, stream, {k_scale, v_scale});
+    return prefill_attn_launch<gq_kv::Fmt::FP8>(q, k_cache, v_cache, out, S, start, n_head, n_kv_head, head_dim, max_seq, scale, window, stream, {k_scale, v_scale});
 }
 
 extern "C" int gq_attn_prefill_kv8r(const void *q, const void *k_cache, const void *v_cache, const void *k_exp, const void *v_exp, void *out,
                                     uint32_t S, uint32_t start, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale,
                                     uint32_t window, void *stream) {
     if (!k_exp || !v_exp) return gq_fail(GQ_EINVAL, "null pointer argument.");
-    return prefill_attn_launch<true, false, true>(q, k_cache, v_cache, out, S, start, n_head, n_kv_head, head_dim, max_seq, scale, window, stream,
-                                                  {(const uint8_t *)k_exp, (const uint8_t *)v_exp});
+    return prefill_attn_launch<gq_kv::Fmt::FP8_ROW>(q, k_cache, v_cache, out, S, start, n_head, n_kv_head, head_dim, max_seq, scale, window, stream,
+                                                    {(const uint8_t *)k_exp, (const uint8_t *)v_exp});
 }
 
 extern "C" int gq_attn_prefill_mx4(const void *q, const void *k_cache, const void *v_cache, const void *k_exp, const void *v_exp, void *out,
                                    uint32_t S, uint32_t start, uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale,
                                    uint32_t window, void *stream) {
     if (!k_exp || !v_exp) return gq_fail(GQ_EINVAL, "null pointer argument.");
-    return prefill_attn_launch<true, false, true, true>(q, k_cache, v_cache, out, S, start, n_head, n_kv_head, head_dim, max_seq, scale, window, stream,
-                                                        {(const uint8_t *)k_exp, (const uint8_t *)v_exp});
+    return prefill_attn_launch<gq_kv::Fmt::MX4>(q, k_cache, v_cache, out, S, start, n_head, n_kv_head, head_dim, max_seq, scale, window, stream,
+                                                {(const uint8_t *)k_exp, (const uint8_t *)v_exp});
 }
 
 extern "C" int gq_attn_prefill_packed(const void *q, const void *k_cache, const void *v_cache, const int *seg_begin, void *out, uint32_t S,
                                       uint32_t n_head, uint32_t n_kv_head, uint32_t head_dim, uint32_t max_seq, float scale, uint32_t window,
                                       void *stream) {
-    return prefill_attn_launch<false, true>(q, k_cache, v_cache, out, S, 0u, n_head, n_kv_head, head_dim, max_seq, scale, window, stream, {seg_begin});
+    return prefill_attn_launch<gq_kv::Fmt::F16, true>(q, k_cache, v_cache, out, S, 0u, n_head, n_kv_head, head_dim, max_seq, scale, window, stream, {seg_begin});
 }

@@ -30,7 +30,7 @@ BASELINE.json's configs name and the reference table lacks
 """
 import math
 from dataclasses import dataclass
-from typing import Optional
+from typing import Callable, Optional
 
 import torch
 import torch.nn as nn
@@ -186,7 +186,7 @@ def kv_cache_dtype_name(kv_cache_dtype) -> str:
     "fp8_row" -> "fp8_row" (the same codes + one exponent byte per cached row and KV head: no scale to calibrate), "mxfp4" -> "mxfp4"
     (OCP microscaling: e2m1 codes, two per byte, + one exponent byte per block of 32 elements)"""
     name = "fp16" if kv_cache_dtype is None else str(kv_cache_dtype)
-    if name not in ("fp16", "fp8", "fp8_row", "mxfp4"):
+    if name not in KV_FORMATS:
         raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r}: None, 'fp16' or 'fp8', or 'fp8_row', or 'mxfp4'")
     return name
 
@@ -259,72 +259,115 @@ def mxfp4_dequant(codes: Tensor, exps: Tensor, dtype=torch.float16) -> Tensor:
     return (val.unflatten(-1, (-1, MX4_BLOCK)) * scale[..., None]).flatten(-2).to(dtype)
 
 
+@dataclass(frozen=True)
+class KVFormat:
+    """one KV-cache format, as the host routes ask for it (the device side: csrc/kv_fmt.h, Traits / Side of the same four)"""
+    name: str
+    store: Optional[torch.dtype]  # the caches' dtype (None: the model's own)
+    nibbles: int                  # 4-bit units per element: a row of a head is head_dim * nibbles / 2 bytes
+    exp_block: Optional[int]      # elements that share an e8m0 exponent byte: None no exponents, 0 the whole row
+    head_scales: bool             # k_scale / v_scale per KV head with their reciprocals k_inv / v_inv
+    suffix: str                   # of the prompt pass's attention plan
+    rows: str                     # the C entries: row write,
+    decode: str                   # decode attention behind it,
+    prompt: str                   # prompt attention
+    quantize: Optional[Callable] = None  # (x [.., head_dim], reciprocal scales | None) -> (codes uint8, exponent bytes | None): the write rule
+    dequant: Optional[Callable] = None   # (codes, scales | exponent bytes, dtype) -> values: the read rule of the SDPA fallback and `update`
+    exp_note: str = ""            # (why there are no scales to set)
+
+    @property
+    def quantized(self) -> bool:
+        return self.quantize is not None
+
+    def row_bytes(self, head_dim: int) -> int:
+        return head_dim * self.nibbles // 2
+
+    def exp_bytes(self, head_dim: int) -> int:
+        """exponent bytes of a (KV head, cached row)"""
+        return 0 if self.exp_block is None else head_dim // (self.exp_block or head_dim)
+
+    def side(self, kvc, write: bool, slot: int = 0) -> tuple:
+        """beside the caches an entry takes nothing, the reciprocal scales (row write) or the scales (attention), or the slot's exponent tensors"""
+        if self.head_scales:
+            return (kvc.k_inv.data_ptr(), kvc.v_inv.data_ptr()) if write else (kvc.k_scale.data_ptr(), kvc.v_scale.data_ptr())
+        if self.exp_block is None:
+            return ()
+        off = slot * kvc.k_exp[0].numel()  # (one byte per KV head, row and block)
+        return kvc.k_exp.data_ptr() + off, kvc.v_exp.data_ptr() + off
+
+
+# (the read rules of the two fp8 forms: value = float(code) * scale of the KV head; value = fp16(code) * 2^(byte - 127), exact in fp16)
+KV_FORMATS = {f.name: f for f in (
+    KVFormat("fp16", None, 4, None, False, "", "gq_rope_cache_rows", "gq_attn_decode_roped", "gq_attn_prefill"),
+    KVFormat("fp8", torch.float8_e4m3fn, 2, None, True, "-kv8", "gq_rope_cache_rows_kv8", "gq_attn_decode_roped_kv8", "gq_attn_prefill_kv8",
+             lambda x, inv: (fp8_quantize(x, inv), None), lambda c, scale, dtype: (c.float() * scale[:, None, None]).to(dtype)),
+    KVFormat("fp8_row", torch.float8_e4m3fn, 2, 0, False, "-kv8r", "gq_rope_cache_rows_kv8r", "gq_attn_decode_roped_kv8r", "gq_attn_prefill_kv8r",
+             lambda x, inv: fp8_row_quantize(x.to(torch.float16)), lambda c, byte, dtype: (c.float() * fp8_row_scale(byte)[..., None]).to(dtype),
+             "one exponent byte per cached row"),
+    KVFormat("mxfp4", torch.uint8, 1, MX4_BLOCK, False, "-mx4", "gq_rope_cache_rows_mx4", "gq_attn_decode_roped_mx4", "gq_attn_prefill_mx4",
+             lambda x, inv: mxfp4_quantize(x.to(torch.float16)), mxfp4_dequant, "one exponent byte per block of 32 elements"),
+)}
+
+
 class KVCache(nn.Module):
-    """k_cache / v_cache [batch][n_kv_head][max_seq][head_dim] in `dtype`.  fp8=True: torch.float8_e4m3fn caches with four fp32
+    """k_cache / v_cache [batch][n_kv_head][max_seq][head_dim] in `dtype`, or in the format `kv_cache_dtype` names (KV_FORMATS; the
+    keywords fp8 / fp8_row / mxfp4 name the same three).  fp8: torch.float8_e4m3fn caches with four fp32
     [n_kv_head] buffers -- k_scale / v_scale (value = code * scale, default 1.0) and their reciprocals k_inv / v_inv, which the host
     fills (`set_scales`: torch.reciprocal; no kernel divides).  `dtype` is then what `update` dequantises to.
-    fp8_row=True: the same caches of codes with k_exp / v_exp uint8 [batch][n_kv_head][max_seq] instead, one e8m0 exponent byte per
+    fp8_row: the same caches of codes with k_exp / v_exp uint8 [batch][n_kv_head][max_seq] instead, one e8m0 exponent byte per
     cached row and KV head (`fp8_row_quantize`); no scales.
-    mxfp4=True: uint8 caches [batch][n_kv_head][max_seq][head_dim / 2] of e2m1 codes, two per byte, with k_exp / v_exp uint8
+    mxfp4: uint8 caches [batch][n_kv_head][max_seq][head_dim / 2] of e2m1 codes, two per byte, with k_exp / v_exp uint8
     [batch][n_kv_head][max_seq][head_dim / 32], one e8m0 exponent byte per block of 32 elements (`mxfp4_quantize`); no scales."""
 
-    def __init__(self, max_batch_size, max_seq_length, n_heads, head_dim, dtype=torch.half, device=None, fp8=False, fp8_row=False, mxfp4=False):
+    def __init__(self, max_batch_size, max_seq_length, n_heads, head_dim, dtype=torch.half, device=None, fp8=False, fp8_row=False, mxfp4=False,
+                 kv_cache_dtype=None):
         super().__init__()
-        assert bool(fp8) + bool(fp8_row) + bool(mxfp4) <= 1
-        cache_shape = (max_batch_size, n_heads, max_seq_length, head_dim)
-        self.fp8, self.fp8_row, self.mxfp4, self.out_dtype = bool(fp8), bool(fp8_row), bool(mxfp4), dtype
-        store = torch.float8_e4m3fn if fp8 or fp8_row else dtype
-        if mxfp4:
-            assert head_dim % MX4_BLOCK == 0, head_dim
-            cache_shape, store = cache_shape[:3] + (head_dim // 2,), torch.uint8
-            for name in ("k_exp", "v_exp"):
-                self.register_buffer(name, torch.full(cache_shape[:3] + (head_dim // MX4_BLOCK,), FP8_ROW_EXP_ONE, dtype=torch.uint8, device=device))
-        self.register_buffer('k_cache', torch.zeros(cache_shape, dtype=store, device=device))
-        self.register_buffer('v_cache', torch.zeros(cache_shape, dtype=store, device=device))
-        if fp8:
+        named = [n for n, on in (("fp8", fp8), ("fp8_row", fp8_row), ("mxfp4", mxfp4)) if on] + ([] if kv_cache_dtype is None else [kv_cache_dtype])
+        assert len(named) <= 1
+        f = self.fmt = KV_FORMATS[kv_cache_dtype_name(named[0] if named else None)]
+        self.fp8, self.fp8_row, self.mxfp4, self.out_dtype = f.name == "fp8", f.name == "fp8_row", f.name == "mxfp4", dtype
+        store = f.store or dtype
+        assert f.exp_block is None or head_dim % (f.exp_block or 1) == 0, head_dim
+        rows = (max_batch_size, n_heads, max_seq_length)
+        elems = head_dim if f.store is None else f.row_bytes(head_dim)  # (the stored formats have elements of one byte)
+        for name in ("k_cache", "v_cache"):
+            self.register_buffer(name, torch.zeros(rows + (elems, ), dtype=store, device=device))
+        if f.head_scales:
             for name in ("k_scale", "v_scale", "k_inv", "v_inv"):
                 self.register_buffer(name, torch.ones(n_heads, dtype=torch.float32, device=device))
-        if fp8_row:
+        if f.exp_block is not None:  # ([batch][n_kv_head][max_seq] per row, [..][head_dim / 32] per block)
             for name in ("k_exp", "v_exp"):
-                self.register_buffer(name, torch.full(cache_shape[:3], FP8_ROW_EXP_ONE, dtype=torch.uint8, device=device))
+                self.register_buffer(name, torch.full(rows + ((f.exp_bytes(head_dim), ) if f.exp_block else ()), FP8_ROW_EXP_ONE, dtype=torch.uint8, device=device))
 
     def set_scales(self, k_scale, v_scale):
         """new scales IN PLACE (the kernels read them from device memory: a captured graph sees them at its next replay)"""
-        assert self.fp8
+        assert self.fmt.head_scales
         self.k_scale.copy_(k_scale)
         self.v_scale.copy_(v_scale)
         self.k_inv.copy_(torch.reciprocal(self.k_scale))
         self.v_inv.copy_(torch.reciprocal(self.v_scale))
 
-    def dequant(self, cache, scale):
-        """the read rule: value = float(code) * scale, handed on in the model's dtype"""
-        return (cache.float() * scale[:, None, None]).to(self.out_dtype)
-
-    def dequant_rows(self, cache, exp_byte):
-        """the read rule of the per-row form: value = fp16(code) * 2^(byte - 127), exact in fp16"""
-        return (cache.float() * fp8_row_scale(exp_byte)[..., None]).to(self.out_dtype)
+    def values(self, which: str, sl=()):
+        """the "k" / "v" rows `sl` (an index into [batch][n_kv_head][max_seq]) by the format's read rule, in the model's dtype"""
+        f, cache = self.fmt, getattr(self, which + "_cache")[sl]
+        if not f.quantized:
+            return cache
+        return f.dequant(cache, getattr(self, which + "_scale") if f.head_scales else getattr(self, which + "_exp")[sl], self.out_dtype)
 
     def update(self, input_pos, k_val, v_val):
         assert input_pos.shape[0] == k_val.shape[2]
-        if self.mxfp4:  # (as below: stored by the write rule, returned dequantised)
-            for cache, exp, val in ((self.k_cache, self.k_exp, k_val), (self.v_cache, self.v_exp, v_val)):
-                cache[:, :, input_pos], exp[:, :, input_pos] = mxfp4_quantize(val.to(torch.float16))
-            return mxfp4_dequant(self.k_cache, self.k_exp, self.out_dtype), mxfp4_dequant(self.v_cache, self.v_exp, self.out_dtype)
-        if self.fp8_row:  # (as below: stored by the write rule, returned dequantised)
-            for cache, exp, val in ((self.k_cache, self.k_exp, k_val), (self.v_cache, self.v_exp, v_val)):
-                codes, byte = fp8_row_quantize(val.to(torch.float16))
-                cache.view(torch.uint8)[:, :, input_pos] = codes
-                exp[:, :, input_pos] = byte
-            return self.dequant_rows(self.k_cache, self.k_exp), self.dequant_rows(self.v_cache, self.v_exp)
-        if self.fp8:  # stored by the write rule, returned dequantised: the module forward restates what the HIP route computes
-            self.k_cache.view(torch.uint8)[:, :, input_pos] = fp8_quantize(k_val, self.k_inv)
-            self.v_cache.view(torch.uint8)[:, :, input_pos] = fp8_quantize(v_val, self.v_inv)
-            return self.dequant(self.k_cache, self.k_scale), self.dequant(self.v_cache, self.v_scale)
-        k_out = self.k_cache
-        v_out = self.v_cache
-        k_out[:, :, input_pos] = k_val
-        v_out[:, :, input_pos] = v_val
-        return k_out, v_out
+        f = self.fmt
+        for which, val in (("k", k_val), ("v", v_val)):
+            cache = getattr(self, which + "_cache")
+            if not f.quantized:
+                cache[:, :, input_pos] = val
+                continue
+            # stored by the write rule, returned dequantised: the module forward restates what the HIP route computes
+            codes, byte = f.quantize(val, getattr(self, which + "_inv", None))
+            cache.view(torch.uint8)[:, :, input_pos] = codes
+            if byte is not None:
+                getattr(self, which + "_exp")[:, :, input_pos] = byte
+        return self.values("k"), self.values("v")
 
 
 class RMSNorm(nn.Module):
@@ -605,8 +648,7 @@ class Transformer(nn.Module):
         dtype = self.output.weight.dtype
         device = self.output.weight.device
         for b in self.layers:
-            b.attention.kv_cache = KVCache(max_batch_size, max_seq_length, self.config.n_local_heads, head_dim, dtype, device, fp8=(kv == "fp8"),
-                                           fp8_row=(kv == "fp8_row"), mxfp4=(kv == "mxfp4"))
+            b.attention.kv_cache = KVCache(max_batch_size, max_seq_length, self.config.n_local_heads, head_dim, dtype, device, kv_cache_dtype=kv)
         self.kv_cache_dtype = kv
         # the [n, n] tables only for a cache of at most MASK_TABLE_MAX rows (tests and pipeline.py index them); above it every consumer
         # builds the rows it needs from the positions (mask_rows: the same bits)
@@ -627,11 +669,10 @@ class Transformer(nn.Module):
         """the scales of an fp8 cache, fp32 [n_layer][n_kv_head] each (value = code * scale; default 1.0), every entry finite and > 0.
         Written in place into the caches' buffers, reciprocals with them: no re-allocation, a captured decode graph needs no re-capture.
         Rows already in the caches keep their codes: set the scales before the prompt."""
-        if self.cache_initialized and self.kv_cache_dtype == "fp8_row":
-            raise ValueError("set_kv_scales: an fp8_row cache has no per-head scales (one exponent byte per cached row, written with the row)")
-        if self.cache_initialized and self.kv_cache_dtype == "mxfp4":
-            raise ValueError("set_kv_scales: an mxfp4 cache has no per-head scales (one exponent byte per block of 32 elements, written with the row)")
-        if not (self.cache_initialized and self.kv_cache_dtype == "fp8"):
+        f = KV_FORMATS[self.kv_cache_dtype]
+        if self.cache_initialized and f.exp_block is not None:
+            raise ValueError(f"set_kv_scales: an {f.name} cache has no per-head scales ({f.exp_note}, written with the row)")
+        if not (self.cache_initialized and f.head_scales):
             raise ValueError("set_kv_scales: the caches are not fp8 (setup_caches(.., kv_cache_dtype='fp8') first)")
         shape = (len(self.layers), self.config.n_local_heads)
         ts = []

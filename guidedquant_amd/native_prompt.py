@@ -72,10 +72,17 @@ def attention_plan(mode: str, n_pieces: int, kv8: bool, supported: bool, row: bo
     "sdpa-kv8" (SDPA on the dequantised rows), on a per-row scaled one (kv8 and row) "hip-kv8r" (gq_attn_prefill_kv8r) | "sdpa-kv8r".
     mode = GQ_PREFILL_ATTN: "0" never the kernel, "1" the kernel wherever the library supports the geometry, "auto" the kernel inside a chunked pass (a prompt of one piece launches what it always did) -- and for any number of
     pieces on an fp8 cache.  On an MXFP4 cache (kv8 and mx4) "hip-mx4" (gq_attn_prefill_mx4) | "sdpa-mx4"."""
+    from .model import KV_FORMATS  # (model.py imports this module: resolved at the call)
+    return format_plan(mode, n_pieces, KV_FORMATS["mxfp4" if kv8 and mx4 else "fp8_row" if kv8 and row else "fp8" if kv8 else "fp16"], supported)
+
+
+def format_plan(mode: str, n_pieces: int, fmt, supported: bool) -> str:
+    """`attention_plan` on a row of model.KV_FORMATS: a quantised cache takes the kernel for any number of pieces, and names itself in the
+    plan by its suffix"""
     if mode not in ("auto", "0", "1"):
         raise ValueError(f"GQ_PREFILL_ATTN={mode!r}: auto, 0 or 1")
-    hip = mode != "0" and (mode == "1" or n_pieces > 1 or kv8) and supported
-    return ("hip" if hip else "sdpa") + (("-mx4" if mx4 else "-kv8r" if row else "-kv8") if kv8 else "")
+    hip = mode != "0" and (mode == "1" or n_pieces > 1 or fmt.quantized) and supported
+    return ("hip" if hip else "sdpa") + fmt.suffix
 
 
 def score_head_choice(mode: str, served: bool, auto: str) -> bool:
@@ -110,14 +117,13 @@ def prompt_pass(model, idx, input_pos, start: int, last_only: bool, chunk: Optio
     assert chunk >= 1, chunk
     pieces = prefill_chunks(S, chunk, start)
     mode = os.environ.get("GQ_PREFILL_ATTN", "auto")
-    row, mx4 = model.kv_cache_dtype == "fp8_row", model.kv_cache_dtype == "mxfp4"
-    kv8 = row or mx4 or model.kv_cache_dtype == "fp8"  # (the quantised caches: the kernel for any number of pieces)
-    plan = attention_plan(mode, len(pieces), kv8, True, row, mx4)  # (the plan where the library serves the geometry; a bad mode raises here)
-    if kv8:
+    fmt = model.layers[0].attention.kv_cache.fmt  # (model.KV_FORMATS[model.kv_cache_dtype]: every layer's cache has it)
+    plan = format_plan(mode, len(pieces), fmt, True)  # (the plan where the library serves the geometry; a bad mode raises here)
+    if fmt.quantized:
         assert model._native_kind() == "ap" and model.kv8_unserved() is None, model.kv8_unserved()
     needs_library = plan.startswith("hip")  # (mode and pieces want the kernel: only then does the library's answer decide, and is it asked)
     if needs_library and not L.gq_attn_prefill_supported(H, Hkv, hd):
-        plan = attention_plan(mode, len(pieces), kv8, False, row, mx4)
+        plan = format_plan(mode, len(pieces), fmt, False)
     model.last_prefill_plan = dict(chunks=pieces, attn=[plan] * len(model.layers))
     dev = idx.device
     Sc = min(chunk, S)
@@ -185,43 +191,27 @@ class _Piece:
     def rows_and_attention(self, att, qkv, win, st):
         """RoPE + KV-cache row write and the attention of one layer on its q | k | v rows `qkv` [S][(H + 2 Hkv) hd]: y [1, S, H hd].
         ONE row-write launch per cache layout and block layout -- gq_rope_cache_rows, gq_qknorm_rope_cache_rows (Qwen3: the per-head RMSNorm
-        of q and k in front of the rotation) or, on an fp8 cache, gq_rope_cache_rows_kv8 (the norm weights ride along; a bias is already in
-        the rows: the quantized linear added it) -- then the plan's attention over batch slot 0 of the caches"""
-        m, cfg, L, kvc = self.m, self.m.config, _lib.lib(), att.kv_cache
+        of q and k in front of the rotation) or, on a quantised cache, the row write of its format (model.KV_FORMATS: the norm weights ride
+        along; a bias is already in the rows: the quantized linear added it) with what the format passes beside the caches -- then the
+        plan's attention over batch slot 0 of the caches: the format's entry, or SDPA on the rows as its read rule gives them"""
+        m, cfg, L, kvc, f = self.m, self.m.config, _lib.lib(), att.kv_cache, att.kv_cache.fmt  # (the plan ends in the format's suffix)
         S, H, Hkv, hd = self.S, cfg.n_head, cfg.n_local_heads, cfg.head_dim
         kc, vc = kvc.k_cache, kvc.v_cache
-        kv8, kv8r, mx4 = self.plan.endswith("-kv8"), self.plan.endswith("-kv8r"), self.plan.endswith("-mx4")
         rows = (qkv.data_ptr(), self.pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), self.q.data_ptr(), kc.data_ptr(), vc.data_ptr())
         shape = (S, H, Hkv, hd, kc.shape[2])
-        if kv8:
-            entry, args = "gq_rope_cache_rows_kv8", (*rows, kvc.k_inv.data_ptr(), kvc.v_inv.data_ptr(), *shape, *native_step.qk_norm_args(att, cfg), None)
-        elif kv8r:  # (the same entry shape: the exponent tensors of batch slot 0 where the fp8 form takes its reciprocal scales)
-            entry, args = "gq_rope_cache_rows_kv8r", (*rows, kvc.k_exp.data_ptr(), kvc.v_exp.data_ptr(), *shape, *native_step.qk_norm_args(att, cfg), None)
-        elif mx4:  # (likewise: the exponent tensors [n_kv_head][max_seq][head_dim / 32] of batch slot 0)
-            entry, args = "gq_rope_cache_rows_mx4", (*rows, kvc.k_exp.data_ptr(), kvc.v_exp.data_ptr(), *shape, *native_step.qk_norm_args(att, cfg), None)
+        if f.quantized:
+            entry, args = f.rows, (*rows, *f.side(kvc, True), *shape, *native_step.qk_norm_args(att, cfg), None)
         elif cfg.qk_norm:
             entry, args = "gq_qknorm_rope_cache_rows", (*rows, *shape, *native_step.qk_norm_args(att, cfg))
         else:
-            entry, args = "gq_rope_cache_rows", (*rows, *shape)
+            entry, args = f.rows, (*rows, *shape)
         _lib.check(getattr(L, entry)(*args, st), entry)
         if self.plan.startswith("hip"):
-            entry, scales = ("gq_attn_prefill_kv8", (kvc.k_scale.data_ptr(), kvc.v_scale.data_ptr())) if kv8 else ("gq_attn_prefill", ())
-            if kv8r:
-                entry, scales = "gq_attn_prefill_kv8r", (kvc.k_exp.data_ptr(), kvc.v_exp.data_ptr())
-            elif mx4:
-                entry, scales = "gq_attn_prefill_mx4", (kvc.k_exp.data_ptr(), kvc.v_exp.data_ptr())
-            _lib.check(getattr(L, entry)(self.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), *scales, self.y.data_ptr(), S, self.start, H, Hkv, hd, kc.shape[2],
-                                         1.0 / math.sqrt(hd), 0 if win is None else int(win), st), entry)
+            _lib.check(getattr(L, f.prompt)(self.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), *f.side(kvc, False), self.y.data_ptr(), S, self.start, H, Hkv, hd,
+                                            kc.shape[2], 1.0 / math.sqrt(hd), 0 if win is None else int(win), st), f.prompt)
             return self.y.view(1, S, H * hd)
-        T = self.start + S
-        k, v = kc[:1, :, :T], vc[:1, :, :T]
-        if kv8:
-            k, v = kvc.dequant(k, kvc.k_scale), kvc.dequant(v, kvc.v_scale)
-        elif kv8r:
-            k, v = kvc.dequant_rows(k, kvc.k_exp[:1, :, :T]), kvc.dequant_rows(v, kvc.v_exp[:1, :, :T])
-        elif mx4:
-            from .model import mxfp4_dequant
-            k, v = mxfp4_dequant(k,kvc.k_exp[:1, :, :T]), mxfp4_dequant(v, kvc.v_exp[:1, :, :T])
+        seen = (slice(0, 1), slice(None), slice(0, self.start + S))
+        k, v = kvc.values("k", seen), kvc.values("v", seen)
         return _sdpa_gqa(self.q.unsqueeze(0), k, v, self.sdpa_mask(win), H // Hkv).transpose(1, 2).reshape(1, S, H * hd)
 
     def layers(self, x):

@@ -144,14 +144,14 @@ class StepState(_Keyed):
         self.layer_split = [self.attn_split if w is None else plan(w) for w in self.layer_window]
         ns_max = max([self.attn_split] + self.layer_split)  # (one workspace, sized for the largest)
         self.attn_ws = torch.zeros(c.n_head * ns_max * (c.head_dim + 2), dtype=torch.float32, device=dev) if ns_max > 1 else None
-        # an fp8 KV cache (Transformer.setup_caches(.., kv_cache_dtype="fp8")): the rotated q of attend_kv8's two-launch route (a state
-        # built under GQ_KV8_FOLD=1 does without; a step that finds the knob off again allocates it then)
-        self.kv8 = getattr(model, "kv_cache_dtype", "fp16") == "fp8"
-        # a per-row scaled fp8 cache (kv_cache_dtype="fp8_row"): always the two-launch route, attend_kv8r
-        self.kv8r = getattr(model, "kv_cache_dtype", "fp16") == "fp8_row"
-        # an MXFP4 cache (kv_cache_dtype="mxfp4"): the same two-launch route over its entries, attend_mx4
-        self.mx4 = getattr(model, "kv_cache_dtype", "fp16") == "mxfp4"
-        self.q8 = torch.zeros(c.n_head * c.head_dim, **f16) if (self.kv8 and not kv8_fold()) or self.kv8r or self.mx4 else None
+        # the cache format (model.KV_FORMATS, Transformer.setup_caches(.., kv_cache_dtype=..)).  A quantised cache: the rotated q of
+        # attend_quant's two-launch route (an fp8 state built under GQ_KV8_FOLD=1 does without; a step that finds the knob off again
+        # allocates it then)
+        from .model import KV_FORMATS
+        self.kvfmt = KV_FORMATS[getattr(model, "kv_cache_dtype", "fp16")]
+        self.q8 = torch.zeros(c.n_head * c.head_dim, **f16) if self.kvfmt.quantized and not (self.kv8 and kv8_fold()) else None
+
+    kv8 = property(lambda self: self.kvfmt.name == "fp8")  # (per-head scales: the one format with the folded route, attend_kv8)
 
     def kv(self, at, slot):
         """the K / V cache of batch slot `slot` of one attention module"""
@@ -174,57 +174,33 @@ class StepState(_Keyed):
         _lib.check(getattr(_lib.lib(), entry)(src, pos.data_ptr(), *rope, *kv, self.y.data_ptr(), c.n_head, c.n_local_heads, c.head_dim,
                                               m.max_seq_length, 1.0 / math.sqrt(c.head_dim), ns, _ptr(self.attn_ws), *extra, sp), entry)
 
-    def attend_kv8(self, at, pos, kv, sp, layer):
-        """the fp8 cache's route of one layer, behind the plain wqkv GEMV: gq_rope_cache_rows_kv8 (S = 1, the graph's position word; the
-        layer's norm weights or bias) rotates q into its own buffer and writes the cache row, gq_attn_decode_roped_kv8 attends it with the
-        layer's window and split plan.  One route for Llama, Mistral, Qwen2 and Qwen3; one launch per layer more than the fp16 routes.
+    def attend_kv8(self, at, pos, kv, sp, layer, slot=0):
+        """the fp8 cache's route of one layer, behind the plain wqkv GEMV: attend_quant's two launches, gq_rope_cache_rows_kv8 and
+        gq_attn_decode_roped_kv8; one launch per layer more than the fp16 routes.
         GQ_KV8_FOLD=1: the two as ONE launch on the packed vector, gq_attn_decode_split_kv8 -- the same cache bytes and the same output."""
         m, c, L, kvc = self.m, self.m.config, _lib.lib(), at.kv_cache
-        if kv8_fold():
-            _lib.check(L.gq_attn_decode_split_kv8(self.qkv.data_ptr(), pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), *kv,
-                                                  kvc.k_inv.data_ptr(), kvc.v_inv.data_ptr(), kvc.k_scale.data_ptr(), kvc.v_scale.data_ptr(), self.y.data_ptr(),
-                                                  c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, 1.0 / math.sqrt(c.head_dim),
-                                                  self.layer_split[layer], _ptr(self.attn_ws), *qk_norm_args(at, c), _ptr(at.wqkv.bias),
-                                                  self.layer_window[layer] or 0, sp), "gq_attn_decode_split_kv8")
-            return
+        if not kv8_fold():
+            return self.attend_quant(at, pos, kv, sp, layer, slot)
+        _lib.check(L.gq_attn_decode_split_kv8(self.qkv.data_ptr(), pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), *kv,
+                                              kvc.k_inv.data_ptr(), kvc.v_inv.data_ptr(), kvc.k_scale.data_ptr(), kvc.v_scale.data_ptr(), self.y.data_ptr(),
+                                              c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, 1.0 / math.sqrt(c.head_dim),
+                                              self.layer_split[layer], _ptr(self.attn_ws), *qk_norm_args(at, c), _ptr(at.wqkv.bias),
+                                              self.layer_window[layer] or 0, sp), "gq_attn_decode_split_kv8")
+
+    def attend_quant(self, at, pos, kv, sp, layer, slot=0):
+        """a quantised cache's route of one layer, behind the plain wqkv GEMV, over the entries of its format (model.KV_FORMATS): the row
+        write (S = 1, the graph's position word; the layer's norm weights or bias) rotates q into its own buffer and writes the new k and v
+        rows by the format's write rule, the decode attention attends with the layer's window and split plan.  Beside the caches (`kv`:
+        StepState.kv's pointers of the slot) they take the format's `side`.  One route for Llama, Mistral, Qwen2 and Qwen3."""
+        m, c, L, kvc, f = self.m, self.m.config, _lib.lib(), at.kv_cache, self.kvfmt
         if self.q8 is None:
             self.q8 = torch.zeros(c.n_head * c.head_dim, dtype=torch.float16, device=self.x.device)
-        _lib.check(L.gq_rope_cache_rows_kv8(self.qkv.data_ptr(), pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), self.q8.data_ptr(), *kv,
-                                            kvc.k_inv.data_ptr(), kvc.v_inv.data_ptr(), 1, c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, *qk_norm_args(at, c),
-                                            _ptr(at.wqkv.bias), sp), "gq_rope_cache_rows_kv8")
-        _lib.check(L.gq_attn_decode_roped_kv8(self.q8.data_ptr(), pos.data_ptr(), *kv, kvc.k_scale.data_ptr(), kvc.v_scale.data_ptr(), self.y.data_ptr(),
-                                              c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, 1.0 / math.sqrt(c.head_dim),
-                                              self.layer_split[layer], _ptr(self.attn_ws), self.layer_window[layer] or 0, sp), "gq_attn_decode_roped_kv8")
-
-    def attend_kv8r(self, at, pos, kv, sp, layer, slot):
-        """the per-row scaled fp8 cache's route of one layer, behind the plain wqkv GEMV -- attend_kv8's two launches with the exponent
-        tensors of the batch slot where it passes scales: gq_rope_cache_rows_kv8r (S = 1, the graph's position word; the layer's norm weights
-        or bias) rotates q, derives the exponents of the new k and v rows and writes codes and bytes, gq_attn_decode_roped_kv8r attends with
-        the layer's window and split plan.  One route for Llama, Mistral, Qwen2 and Qwen3."""
-        m, c, L, kvc = self.m, self.m.config, _lib.lib(), at.kv_cache
-        off = slot * c.n_local_heads * m.max_seq_length  # (one byte per KV head and row)
-        ex = kvc.k_exp.data_ptr() + off, kvc.v_exp.data_ptr() + off
-        _lib.check(L.gq_rope_cache_rows_kv8r(self.qkv.data_ptr(), pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), self.q8.data_ptr(), *kv, *ex,
-                                             1, c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, *qk_norm_args(at, c), _ptr(at.wqkv.bias), sp),
-                   "gq_rope_cache_rows_kv8r")
-        _lib.check(L.gq_attn_decode_roped_kv8r(self.q8.data_ptr(), pos.data_ptr(), *kv, *ex, self.y.data_ptr(), c.n_head, c.n_local_heads, c.head_dim,
-                                               m.max_seq_length, 1.0 / math.sqrt(c.head_dim), self.layer_split[layer], _ptr(self.attn_ws),
-                                               self.layer_window[layer] or 0, sp), "gq_attn_decode_roped_kv8r")
-
-    def attend_mx4(self, at, pos, kv, sp, layer, slot):
-        """the MXFP4 cache's route of one layer, behind the plain wqkv GEMV -- attend_kv8r's two launches over the MXFP4 entries:
-        gq_rope_cache_rows_mx4 (S = 1, the graph's position word; the layer's norm weights or bias) rotates q, derives the exponents of the
-        blocks of the new k and v rows and writes codes and bytes, gq_attn_decode_roped_mx4 attends with the layer's window and split plan.
-        One route for Llama, Mistral, Qwen2 and Qwen3.  (`kv`: StepState.kv's pointers, a slot of n_kv_head * max_seq * head_dim / 2 bytes)"""
-        m, c, L, kvc = self.m, self.m.config, _lib.lib(), at.kv_cache
-        off = slot * c.n_local_heads * m.max_seq_length * (c.head_dim // 32)  # (one byte per KV head, row and block)
-        ex = kvc.k_exp.data_ptr() + off, kvc.v_exp.data_ptr() + off
-        _lib.check(L.gq_rope_cache_rows_mx4(self.qkv.data_ptr(), pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), self.q8.data_ptr(), *kv, *ex,
-                                            1, c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, *qk_norm_args(at, c), _ptr(at.wqkv.bias), sp),
-                   "gq_rope_cache_rows_mx4")
-        _lib.check(L.gq_attn_decode_roped_mx4(self.q8.data_ptr(), pos.data_ptr(), *kv, *ex, self.y.data_ptr(), c.n_head, c.n_local_heads, c.head_dim,
-                                              m.max_seq_length, 1.0 / math.sqrt(c.head_dim), self.layer_split[layer], _ptr(self.attn_ws),
-                                              self.layer_window[layer] or 0, sp), "gq_attn_decode_roped_mx4")
+        _lib.check(getattr(L, f.rows)(self.qkv.data_ptr(), pos.data_ptr(), m.rope_cos.data_ptr(), m.rope_sin.data_ptr(), self.q8.data_ptr(), *kv,
+                                      *f.side(kvc, True, slot), 1, c.n_head, c.n_local_heads, c.head_dim, m.max_seq_length, *qk_norm_args(at, c),
+                                      _ptr(at.wqkv.bias), sp), f.rows)
+        _lib.check(getattr(L, f.decode)(self.q8.data_ptr(), pos.data_ptr(), *kv, *f.side(kvc, False, slot), self.y.data_ptr(), c.n_head, c.n_local_heads,
+                                        c.head_dim, m.max_seq_length, 1.0 / math.sqrt(c.head_dim), self.layer_split[layer], _ptr(self.attn_ws),
+                                        self.layer_window[layer] or 0, sp), f.decode)
 
     def head(self, x):
         """the one call site of the dense GEMV (both families): final RMSNorm + lm_head -> the fp16 logits.  An int8-head model
@@ -278,7 +254,7 @@ class ApStep(StepState):
         from .model import pair_gate_up_rows_
         super().__init__(model)
         c = model.config
-        if (self.kv8 or self.kv8r or self.mx4) and model.kv8_unserved():
+        if self.kvfmt.quantized and model.kv8_unserved():
             raise ValueError(model.kv_cache_dtype + " KV cache: " + model.kv8_unserved())
         self.adapter = getattr(model, "adapter", None)  # (Transformer.set_adapter: a LoraAdapter, or None)
         self.lora_layers = getattr(model, "adapter_layers", None)  # (its sites per layer as bound to THIS model: LoraAdapter.bind)
@@ -304,7 +280,7 @@ class ApStep(StepState):
         gq_lora_up writes -- the q | k | v delta (+ the checkpoint's bias) the attention launch adds, the residuals of wo and w2 with
         their delta.  The refusals: none of them falls back."""
         c, ad, dev = self.m.config, self.adapter, self.x.device
-        if self.kv8 or self.kv8r or self.mx4:
+        if self.kvfmt.quantized:
             raise NotImplementedError("lora: the %s KV cache is not served under an adapter (setup_caches(.., kv_cache_dtype='fp16'))" % self.m.kv_cache_dtype)
         if c.qk_norm and ad.targets("qkv"):
             raise ValueError("lora: q / k / v targets on a QK-norm model (Qwen3): no attention launch has both the norm and a bias; "
@@ -363,15 +339,9 @@ class ApStep(StepState):
                 launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
                 side(lora["qkv"], xp, _ptr(at.wqkv.bias), self.qkv_delta, blk.input_layernorm.weight.data_ptr())
                 self.attend("gq_attn_decode_split_bias", qkv, pos, kv, sp, (self.qkv_delta.data_ptr(),), layer=l0 + li)
-            elif self.kv8:
+            elif self.kvfmt.quantized:
                 launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
-                self.attend_kv8(at, pos, kv, sp, l0 + li)
-            elif self.kv8r:
-                launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
-                self.attend_kv8r(at, pos, kv, sp, l0 + li, slot)
-            elif self.mx4:
-                launch("gq_anyprec_gemv_fused_ho", *wqkv, None, 0, None, 0, ssq_in, None)
-                self.attend_mx4(at, pos, kv, sp, l0 + li, slot)
+                (self.attend_kv8 if self.kv8 else self.attend_quant)(at, pos, kv, sp, l0 + li, slot)
             elif c.qk_norm:
                 # Qwen3: q and k are normalised per head BEFORE the rotation, so the wqkv launch must not rotate (its RoPE epilogue holds a
                 # head's rows in eight 16-row groups: no per-head statistic there) -- plain wqkv GEMV, then ONE attention launch that
@@ -662,7 +632,7 @@ class QtipStep(StepState):
         super().__init__(model)
         if getattr(model, "adapter", None) is not None:
             raise NotImplementedError("lora: QTIP models are not served under an adapter")
-        if self.kv8 or self.kv8r or self.mx4:
+        if self.kvfmt.quantized:
             raise NotImplementedError(model.kv_cache_dtype + " KV cache: QTIP models keep the fp16 cache (gq_attn_decode_qtip has no fp8 form)")
         c, dev = model.config, self.x.device
         self.g = torch.zeros(c.intermediate_size, dtype=torch.float16, device=dev)

@@ -19,7 +19,7 @@ import tempfile
 
 KNOBS = ("GQ_NATIVE_QTIP", "GQ_ATTN_GQA", "GQ_ATTN_SPLIT", "GQ_NATIVE_PAIRS", "GQ_SSQ_HANDOVER", "GQ_QTIP_KSPLIT", "GQ_QTIP_KSPLIT_GROUP",
          "GQ_QTIP_FOLD", "GQ_QTIP_ONE_LAUNCH", "GQ_QTIP_OUT_SEG", "GQ_QTIP_MLP_MID", "GQ_QTIP_ATTN_FOLD", "GQ_QTIP_PRE",
-         "GQ_QKV_ATTN", "GQ_PL_MIN_MWEIGHTS", "GQ_ST_KSPLIT", "GQ_HADAMARD_TABLES")
+         "GQ_QKV_ATTN", "GQ_PL_MIN_MWEIGHTS", "GQ_ST_KSPLIT", "GQ_HADAMARD_TABLES", "GQ_KV8_FOLD")
 STATE_KEYS = ("x", "h", "y", "qkv", "ssq", "attn_flags", "gu", "logits", "attn_ws", "ap_ws", "g", "u", "y32", "xs16", "xt", "z32")
 
 SMALL = dict(dim=512, n_head=4, n_local_heads=2, intermediate_size=1024, vocab_size=384)       # (the lm_head takes K % 512 == 0)
@@ -29,7 +29,7 @@ Q4096 = dict(dim=4096, n_head=32, n_local_heads=8, intermediate_size=4096, vocab
 QWIDE = dict(dim=8192, n_head=64, n_local_heads=8, intermediate_size=4096, vocab_size=384)       # ... and of the q / k / v group
 QFACTOR = dict(dim=1024, n_head=8, n_local_heads=8, intermediate_size=11008, vocab_size=384)   # 11008 = 172 * 64 (Llama-2-7b's MLP)
 
-# name -> (family, bits, ModelArgs fields, cache length, knobs)
+# name -> (family, bits, ModelArgs fields, cache length, knobs[, KV cache dtype: "fp16" where there is none])
 CONFIGS = {
     "ap4": ("ap", 4, SMALL, 64, {}),
     "ap6_no_pairs": ("ap", 6, SMALL, 64, {"GQ_NATIVE_PAIRS": "0"}),
@@ -56,6 +56,10 @@ CONFIGS = {
     "qtip_one_launch": ("qtip", 2, QSMALL, 64, {"GQ_QTIP_ONE_LAUNCH": "1"}),
     "qtip_pre": ("qtip", 2, QSMALL, 64, {"GQ_QTIP_PRE": "1"}),
     "qtip_long_cache": ("qtip", 2, QSMALL, 1100, {}),
+    "ap4_kv8": ("ap", 4, SMALL, 64, {}, "fp8"),
+    "ap4_kv8_fold": ("ap", 4, SMALL, 64, {"GQ_KV8_FOLD": "1"}, "fp8"),
+    "ap4_kv8r": ("ap", 4, SMALL, 64, {}, "fp8_row"),
+    "ap4_mx4": ("ap", 4, SMALL, 64, {}, "mxfp4"),
 }
 
 
@@ -128,7 +132,7 @@ def regions_of(model):
     return out
 
 
-def _build(family, bits, shape, cache):
+def _build(family, bits, shape, cache, kv="fp16"):
     import torch
     from guidedquant_amd import model as gm
     from guidedquant_amd.generate import load_model
@@ -139,7 +143,7 @@ def _build(family, bits, shape, cache):
     finally:
         del gm.transformer_configs[name]
     with torch.device("cuda:0"):
-        m.setup_caches(max_batch_size=1, max_seq_length=cache)
+        m.setup_caches(max_batch_size=1, max_seq_length=cache, kv_cache_dtype=kv)
     return m
 
 
@@ -148,7 +152,7 @@ def record(name):
     import numpy as np
     import torch
     from guidedquant_amd import _lib, qtip
-    family, bits, shape, cache, knobs = CONFIGS[name]
+    family, bits, shape, cache, knobs, kv = (*CONFIGS[name], "fp16")[:6]
     L = _lib.lib()
     saved = {k: os.environ.pop(k) for k in KNOBS if k in os.environ}
     tmp = tempfile.TemporaryDirectory()
@@ -161,8 +165,8 @@ def record(name):
         qtip._tables = None
         L.gq_reset_env_cache()
         _lib.check(L.gq_set_ap_mode(0), "gq_set_ap_mode")
-        m = _build(family, bits, shape, cache)
-        assert m._native_kind() == family, (name, m._native_kind())
+        m = _build(family, bits, shape, cache, kv)
+        assert m._native_kind() == family and m.kv_cache_dtype == kv, (name, m._native_kind(), m.kv_cache_dtype)
         tok = torch.tensor([5], dtype=torch.int32, device="cuda:0")
         pos = torch.tensor([3], dtype=torch.int32, device="cuda:0")
         m._native_state()
@@ -226,6 +230,20 @@ def _both(*preds):
     return lambda calls: all(p(calls) for p in preds)
 
 
+def _kv_route(sfx, side):
+    """a quantised cache's two launches per layer behind the plain wqkv GEMV: the row write (S = 1) and the attention of the format, each
+    with the layer's own `side` tensors (reciprocal scales / scales, or the exponent tensors of batch slot 0) behind the caches"""
+    rows, attn = "gq_rope_cache_rows" + sfx, "gq_attn_decode_roped" + sfx
+    want = [tuple(f"layers.{i}.attention.kv_cache.{n}+0" for n in pair) for i in (0, 1) for pair in side]
+
+    def pred(c):
+        got = [(c_[1][7], c_[1][8]) if c_[0] == rows else (c_[1][4], c_[1][5]) for c_ in c if c_[0] in (rows, attn)]
+        return (_names(c).count(rows) == 2 and _names(c).count(attn) == 2 and got == want and all(a[9] == 1 for a in _args(c, rows))
+                and _never("gq_attn_decode_split_kv8", "gq_attn_decode_split", "gq_attn_decode_roped")(c)
+                and sum(n.startswith(("gq_rope_cache_rows", "gq_attn_decode")) for n in _names(c)) == 4)
+    return pred
+
+
 def _ks(calls):
     """the split-K part counts of a log's QTIP matvec launches (last scalar of gq_qtip_linear_in)"""
     return [a[11] for a in _args(calls, "gq_qtip_linear_in")]
@@ -271,6 +289,15 @@ COVERAGE = [
     ("QTIP GQ_QTIP_ONE_LAUNCH=1", "qtip_one_launch", _both(_calls("gq_qtip_linear"), _never("gq_qtip_linear_out", "gq_qtip_linear_out_seg"))),
     ("QTIP GQ_QTIP_PRE=1", "qtip_pre", _both(_calls("gq_qtip_linear_out_in"), _has("xt[2]+"))),
     ("QTIP cache > 1024: attn_split 4", "qtip_long_cache", lambda c: all(a[12] == 4 and a[13] == "attn_ws+0" for a in _args(c, "gq_attn_decode_qtip"))),
+    ("fp8 cache: gq_rope_cache_rows_kv8 with the reciprocal scales, gq_attn_decode_roped_kv8 with the scales", "ap4_kv8",
+     _kv_route("_kv8", (("k_inv", "v_inv"), ("k_scale", "v_scale")))),
+    ("fp8 cache, GQ_KV8_FOLD=1: ONE launch per layer, gq_attn_decode_split_kv8 with reciprocals and scales", "ap4_kv8_fold",
+     lambda c: [tuple(a[6:10]) for a in _args(c, "gq_attn_decode_split_kv8")]
+     == [tuple(f"layers.{i}.attention.kv_cache.{n}+0" for n in ("k_inv", "v_inv", "k_scale", "v_scale")) for i in (0, 1)]
+     and not any(n.startswith(("gq_rope_cache_rows", "gq_attn_decode_roped")) for n in _names(c))),
+    ("fp8_row cache: the two launches with the exponent bytes [n_kv_head][max_seq] of the slot", "ap4_kv8r", _kv_route("_kv8r", (("k_exp", "v_exp"), ) * 2)),
+    ("mxfp4 cache: the two launches with the exponent bytes [n_kv_head][max_seq][head_dim / 32] of the slot", "ap4_mx4",
+     _kv_route("_mx4", (("k_exp", "v_exp"), ) * 2)),
 ]
 
 

@@ -33,6 +33,10 @@ CONFIGS = {
     "qwen3_kv8": ("qwen3", "fp8", "prefill", CHUNK, False, {}),
     "qwen2_kv8": ("qwen2", "fp8", "prefill", CHUNK, False, {}),
     "llama_kv8_sdpa": ("llama-2bit", "fp8", "prefill", CHUNK, False, {"GQ_PREFILL_ATTN": "0"}),
+    "llama_kv8r": ("llama-2bit", "fp8_row", "prefill", CHUNK, False, {}),
+    "qwen3_kv8r": ("qwen3", "fp8_row", "prefill", CHUNK, False, {}),
+    "llama_mx4": ("llama-2bit", "mxfp4", "prefill", CHUNK, False, {}),
+    "llama_mx4_sdpa": ("llama-2bit", "mxfp4", "prefill", CHUNK, False, {"GQ_PREFILL_ATTN": "0"}),
     "qtip_chunked": ("qtip", "fp16", "prefill", CHUNK, False, {}),
     "llama_score_kernel": ("llama-2bit", "fp16", "score", CHUNK, False, {"GQ_SCORE_HEAD": "1"}),
     "llama_score_torch": ("llama-2bit", "fp16", "score", CHUNK, False, {"GQ_SCORE_HEAD": "0"}),
@@ -103,8 +107,8 @@ def record(name):
 
 
 # ------------------------------------------------------------------------------------------------ coverage
-ATTN = ("gq_attn_prefill", "gq_attn_prefill_kv8")
-ROWS = ("gq_rope_cache_rows", "gq_qknorm_rope_cache_rows", "gq_rope_cache_rows_kv8")
+ATTN = ("gq_attn_prefill", "gq_attn_prefill_kv8", "gq_attn_prefill_kv8r", "gq_attn_prefill_mx4")
+ROWS = ("gq_rope_cache_rows", "gq_qknorm_rope_cache_rows", "gq_rope_cache_rows_kv8", "gq_rope_cache_rows_kv8r", "gq_rope_cache_rows_mx4")
 V = 1024
 
 
@@ -123,15 +127,27 @@ def _no_bias_role(calls):
     return not any("bias" in r for r in _roles(calls))
 
 
-def _kv8(norm):
+def _quant(norm, sfx="-kv8", write=("k_inv", "v_inv"), read=("k_scale", "v_scale")):
+    """a quantised cache: the row write of the format with `write` of the layer's cache behind the caches (the reciprocal scales of an fp8
+    cache; the exponent tensors of the others), its attention entry with `read` there, nothing through another format's entries"""
+    rows, attn = "gq_rope_cache_rows_" + sfx[1:], "gq_attn_prefill_" + sfx[1:]
+
     def pred(c):
-        a = _args(c, "gq_rope_cache_rows_kv8")
+        a, t = _args(c, rows), _args(c, attn)
         want = [(f"layers.{i}.attention.q_norm.weight+0", f"layers.{i}.attention.k_norm.weight+0") if norm else ("null", "null") for i in (0, 1)] * 2
-        return (_only_rows(c, "gq_rope_cache_rows_kv8") and [(x[14], x[15]) for x in a] == want and all(x[17] == "null" for x in a)
-                and all(x[7].endswith("kv_cache.k_inv+0") and x[8].endswith("kv_cache.v_inv+0") for x in a)
-                and [x[7] for x in _args(c, "gq_attn_prefill_kv8")] == [0, 0, 16, 16] and "gq_attn_prefill" not in _names(c)
-                and _result(c)["attn"] == ["hip-kv8"] * 2)
+        return (_only_rows(c, rows) and [(x[14], x[15]) for x in a] == want and all(x[17] == "null" for x in a)
+                and [(x[7], x[8]) for x in a] == [tuple(f"layers.{i}.attention.kv_cache.{n}+0" for n in write) for i in (0, 1)] * 2
+                and [(x[3], x[4]) for x in t] == [tuple(f"layers.{i}.attention.kv_cache.{n}+0" for n in read) for i in (0, 1)] * 2
+                and [x[7] for x in t] == [0, 0, 16, 16] and not any(n in _names(c) for n in ATTN if n != attn)
+                and _result(c)["attn"] == ["hip" + sfx] * 2)
     return pred
+
+
+def _kv8(norm):
+    return _quant(norm)
+
+
+EXP = ("k_exp", "v_exp")
 
 
 # (branch, configuration, what its log must show)
@@ -155,6 +171,13 @@ COVERAGE = [
     ("fp8 cache, qwen2: a null bias (the linears added it)", "qwen2_kv8", lambda c: _kv8(False)(c) and _no_bias_role(c)),
     ("fp8 cache, GQ_PREFILL_ATTN=0: no prefill attention entry", "llama_kv8_sdpa",
      lambda c: not any(n in _names(c) for n in ATTN) and _only_rows(c, "gq_rope_cache_rows_kv8") and _result(c)["attn"] == ["sdpa-kv8"] * 2),
+    ("fp8_row cache, llama: gq_rope_cache_rows_kv8r + gq_attn_prefill_kv8r with the exponent bytes of the layer's cache", "llama_kv8r",
+     _quant(False, "-kv8r", EXP, EXP)),
+    ("fp8_row cache, qwen3: the norm weights ride in gq_rope_cache_rows_kv8r", "qwen3_kv8r", _quant(True, "-kv8r", EXP, EXP)),
+    ("mxfp4 cache, llama: gq_rope_cache_rows_mx4 + gq_attn_prefill_mx4 with the block exponent bytes of the layer's cache", "llama_mx4",
+     _quant(False, "-mx4", EXP, EXP)),
+    ("mxfp4 cache, GQ_PREFILL_ATTN=0: the row write of the format, no prefill attention entry (SDPA on mxfp4_dequant)", "llama_mx4_sdpa",
+     lambda c: not any(n in _names(c) for n in ATTN) and _only_rows(c, "gq_rope_cache_rows_mx4") and _result(c)["attn"] == ["sdpa-mx4"] * 2),
     ("QTIP: gate | up side by side, paired = 0 in gq_silu_mul_rows", "qtip_chunked",
      lambda c: [a[4] for a in _args(c, "gq_silu_mul_rows")] == [0] * 4 and _only_rows(c, "gq_rope_cache_rows")),
     ("AP: the paired gate / up rows of the decode step, paired = 1", "llama_chunked", lambda c: [a[4] for a in _args(c, "gq_silu_mul_rows")] == [1] * 4),

@@ -32,6 +32,9 @@ DEVICE_FUNCTIONS = {
     # what sampler.hip, sampler_full.hip and topn.hip compare bit for bit ("The sampler's shared arithmetic once")
     "sampler_core.h": ["hash32", "ordered_key16", "unordered_key16", "ordered_key32", "unordered_key32", "is_nan16", "penalise",
                        "race_u", "race_score", "better", "ban_ids", "is_banned", "lse_merge128", "sample_publish", "sample_embed"],
+    # the arithmetic of the KV-cache formats' write and read rules ("One KV-cache format descriptor")
+    "kv_fmt.h": ["unpack8", "unpack8_fp8", "fp8_quant8", "row_exp_byte", "row_exp_scale", "row_exp_inv", "group_umax",
+                 "mx4_exp_field", "mx4_exp_byte", "mx4_code", "mx4_quant8", "mx4_scale", "unpack8_mx4"],
 }
 SAMPLER_UNITS = ["sampler.hip", "sampler_full.hip", "topn.hip"]
 OTHER_DEFINITIONS = {  # pattern -> the one file
@@ -40,7 +43,9 @@ OTHER_DEFINITIONS = {  # pattern -> the one file
     r"0x00020000": "wave_util.h",  # the descriptor's flags word, named once (RSRC_FLAGS)
 }
 # names that must not come back: the reduction name that had two contracts, the second threshold, the helpers' former private spellings
-RETIRED = ["wave_reduce", "gq_wave_allsum", "GQ_ST_HOT_T", "g_dma16", "g_load16", "g_wait_vm", "g_rsrc"]
+RETIRED = ["wave_reduce", "gq_wave_allsum", "GQ_ST_HOT_T", "g_dma16", "g_load16", "g_wait_vm", "g_rsrc",
+           # the per-file cache format traits and argument structs that became gq_kv::Traits / Side (kv_fmt.h)
+           "CacheFmt", "CacheElem", "TileFmt", "TailArg", "AttnKv8", "AttnRowExp"]
 # build-time forks that were decided and taken out (DESIGN.md sections 3.5 - 3.7 keep the verdicts)
 REMOVED_FORKS = ["PL_SSQ_MODE", "PL_BOOB", "PL_LOOB", "ST_DPPIMG", "ST_TAU_SCALE", "ST_MAINPRIO", "ST_AUX",
                  # qtip.hip's, and the helpers nothing called
